@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- heatmap frames/s of the delay-and-sum sweep on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload headline] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload headline] [--batch B] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch of B synthetic frames already resident in HBM:
 (N > 1: the exchange of the batch from rank 0 -- RCCL over xGMI, overlapped with the previous step's
@@ -23,7 +23,12 @@ library has initialised the GPU before main() runs): profile one rank's slab ins
 Workloads: c1, c2, headline, c3, c4 = BASELINE.json configs on the whole grid; c5 = configs[4], 1024 frames
 in flight on ONE rank's slab of the 256x256 grid (1/8 of the rows; with N GPUs the N first slabs of 8N).
 
-At N = 1 the line also carries, next to the batched `value`:
+A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step` and the "roofline" / "valu"
+figures of the timed sweep launches.  --dump-outputs DIR then writes the powers of the last timed step (rank 0's slab) as
+DIR/power.npy.  Every check and every other measurement below runs only with --full.
+
+With --full at N > 1: "parity" below and the post-run gather check of the assembled heatmap.  With --full at N = 1 the
+line also carries, next to the batched `value`:
   "parity"            GPU vs the oracle on EVERY pixel of frame 0, unfloored (tests/util.parity_report); "dc_ok": the run's math mode
                       within 1e-5 of the reference-built goldens at every DC offset (parity_dc)
   "single_frame"      one frame per call, the regime the reference's live display runs in; "other_mode": the same in the other fp32 mode
@@ -74,8 +79,8 @@ RUN_TIMEOUT_S = 900        # N > 1: everything after the rendezvous, per rank
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 20; c5: 6)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps before them (default 3; c5: 2)")
     ap.add_argument("--workload", default="headline", help="c1 | c2 | headline | c3 | c4 | c5")
     ap.add_argument("--batch", type=int, default=0,
                     help="frames per step; default 128 x GPUs (c5: 1024 x GPUs), which keeps every rank's launch at its one-GPU size")
@@ -83,12 +88,20 @@ def parse_args(argv=None):
                     help="exact (the library's default): the reference's operation and mic order, within 1e-5 of it on any input; "
                          "fast: the re-ordered fp32 sweep (opt-in: within 1e-5 on zero-mean input only)")
     ap.add_argument("--interp", default="lerp", choices=["lerp", "fir8"], help="fir8: the 8-tap variant of delay()")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget; 0 disables")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: CPU baseline budget; 0 disables")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip single_frame / pcie_inclusive / bf16 / workloads / projected_scaling")
+                    help="--full: skip single_frame / pcie_inclusive / bf16 / workloads / projected_scaling")
+    ap.add_argument("--full", action="store_true",
+                    help="also check parity against the CPU oracle and run the other legs (single frame, other modes and "
+                         "workloads, projected scaling, CPU baseline); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the powers of the last one as DIR/power.npy (float32)")
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--selftest-launcher", default="", help=argparse.SUPPRESS)  # tests: ok | fail
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if (args.steps is not None and args.steps < 1) or (args.warmup is not None and args.warmup < 0):
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ------------------------------------------------------------------------------------------ launcher
@@ -525,9 +538,8 @@ def main():
     c5 = args.workload == "c5"
     spec = S.WORKLOADS["c4" if c5 else args.workload]
     B = args.batch or default_batch(world, c5)
-    K, W = args.steps, args.warmup
-    if c5 and args.steps == 20 and args.warmup == 3:
-        K, W = 6, 2  # a 1024-frame step is 8x the default one
+    K = args.steps if args.steps is not None else (6 if c5 else 20)  # (c5: a 1024-frame step is 8x the default one)
+    W = args.warmup if args.warmup is not None else (2 if c5 else 3)
     wl_name = (f"c5: 512 mics x 256x256 x 256, {B} frames in flight, one rank's slab of {C5_SLABS * world} "
                f"({spec.res // (C5_SLABS * world)} rows) per GPU") if c5 else spec.name
 
@@ -593,11 +605,13 @@ def main():
         elapsed = float(t.item())
     step_kernel_ms = [a.elapsed_time(b) for a, b in zip(*events)]  # this rank's sweep launch, every timed step
     kernel_ms = float(np.mean(step_kernel_ms))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), d_power)
 
     # ---- parity of what was just computed: frame 0, EVERY pixel of this rank's slab, unfloored
     st = eng.stats()
     parity = None
-    if rank == 0:
+    if rank == 0 and args.full:
         parity = full_grid_parity(d_power[0].cpu().numpy(), host_first[0], job.off_abs, frac, args.math, args.interp)
         parity["what"] = (f"frame 0 of the timed batch, all {shard.pixel_count} pixels of rank 0's slab, GPU vs oracle.das_f32 "
                           f"(the reference's operations) and vs exact fp64 sums; `ok` = max_rel_unfloored <= 1e-5, flat")
@@ -691,9 +705,10 @@ def main():
                 "unit": "TFLOP/s", "frac": launch_flops / (kernel_ms * 1e-3) / 1e12 / VALU_PEAK_TFLOPS,
                 "note": "algorithmic flops (4 per pixel, mic and sample) over the measured kernel time",
             },
-            "parity_max_rel_err": parity["max_rel_unfloored"],
-            "parity": parity,
         }
+        if parity is not None:
+            out["parity_max_rel_err"] = parity["max_rel_unfloored"]
+            out["parity"] = parity
         if alt is not None:
             out["alt_sharding"] = alt
         if world > 1:
@@ -702,7 +717,7 @@ def main():
             out["rehearsal"] = "all ranks on one GPU over gloo: logic check only, not a scaling number"
 
     # ---- N = 1: the other regimes of the same path, and the CPU reference, beside the batched value
-    if world == 1 and not args.no_extras and args.math in ("exact", "fast") and args.interp == "lerp":
+    if world == 1 and args.full and not args.no_extras and args.math in ("exact", "fast") and args.interp == "lerp":
         other = "fast" if args.math == "exact" else "exact"
         math_ids = {"fast": pkg.MATH_F32_FAST, "exact": pkg.MATH_F32_EXACT}
 
@@ -797,7 +812,7 @@ def main():
         except Exception as exc:  # noqa: BLE001 -- an optional leg
             out["projected_scaling_strong"] = {"error": str(exc)}
 
-    if world == 1 and args.cpu_seconds > 0:
+    if world == 1 and args.full and args.cpu_seconds > 0:
         out["cpu_baseline"] = cpu_baseline(spec, off, frac, host_first[0], args.cpu_seconds, args.interp)
         out["cpu_baseline"]["pixels"] = int(shard.pixel_count)
         out["speedup_vs_cpu_1t"] = out["value"] / out["cpu_baseline"]["value"]  # (the run's math mode: the default unless --math says otherwise)
@@ -811,7 +826,7 @@ def main():
     if run_guard:  # the measured part is over: from here on nothing may turn a finished run into exit status 4
         run_guard.__exit__(None, None, None)
         run_guard = None
-    if world > 1 and os.environ.get("BENCH_GATHER_CHECK", "1") == "1":  # (on by default: the RCCL schedules have only ever run over gloo)
+    if world > 1 and args.full and os.environ.get("BENCH_GATHER_CHECK", "1") == "1":  # (on by default: the RCCL schedules have only ever run over gloo)
         # (a check AFTER the result line: a collective that hangs here ends the process with status 0 and a line on stderr)
         check_guard = Watchdog(120, "gather check: timed out -- the result line above stands; the post-run heatmap gather", status=0)
         check_guard.__enter__()
@@ -834,6 +849,19 @@ def main():
     job.close()
     if world > 1:
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir: Path, d_power, limit_bytes=60 << 20, seed=0):
+    """d_power [frames, pixels] of the last timed step -> out_dir/power.npy, float32.  Over `limit_bytes` (under 64 MB) a fixed,
+    seeded sample of whole frames (rows, in ascending order) is written instead."""
+    power = d_power.cpu().numpy()
+    if power.nbytes > limit_bytes:
+        keep = max(1, limit_bytes // (power.shape[1] * power.itemsize))
+        rows = np.sort(np.random.default_rng(seed).choice(power.shape[0], size=keep, replace=False))
+        power = power[rows]
+        print(f"[bench] --dump-outputs: {keep} of {d_power.shape[0]} frames (seeded sample) written", file=sys.stderr)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    np.save(out_dir / "power.npy", np.ascontiguousarray(power, np.float32))
 
 
 def parity_dc(pkg):

@@ -26,12 +26,21 @@ _i32p = C.POINTER(C.c_int32)
 _u8p = C.POINTER(C.c_uint8)
 
 
+def _in_reference_tree(rel: str) -> Optional[Path]:
+    """REFERENCE_TREE / rel when it can be read; None when the tree is absent or not readable by this user."""
+    path = REFERENCE_TREE / rel
+    try:
+        return path if path.is_file() and os.access(path, os.R_OK) else None
+    except OSError:  # (pathlib raises PermissionError when a parent directory is not searchable)
+        return None
+
+
 def build(ref: bool = True) -> None:
     """make the restatement, and (when the reference tree is present) oracle/_ref."""
     if os.environ.get("AWPU_NO_BUILD") == "1":  # set by the profiling scripts: no child processes under rocprofv3
         raise RuntimeError("AWPU_NO_BUILD=1: the oracle library is missing or stale and may not be built from this process")
     subprocess.run(["make", "-s", "-C", str(HERE), "oracle"], check=True)
-    if ref and (REFERENCE_TREE / "src/dsp/delay.cpp").exists():
+    if ref and _in_reference_tree("src/dsp/delay.cpp"):
         subprocess.run(["make", "-s", "-C", str(HERE), "ref"], check=True)
 
 
@@ -258,8 +267,8 @@ def reference_fir_table():
     into the repo); None when the reference tree is absent (GPU box)."""
     import re
 
-    path = REFERENCE_TREE / "src/dsp/filter.h"
-    if not path.exists():
+    path = _in_reference_tree("src/dsp/filter.h")
+    if path is None:
         return None
     nums = re.findall(r"-?\d+\.\d+(?:[eE][-+]?\d+)?", path.read_text().split("filter_coeffs")[1])
     table = np.array(nums[: 101 * 8], dtype=np.float32).reshape(101, 8)

@@ -60,6 +60,24 @@ def test_batch_grows_with_the_ranks():
     assert bench.parse_args(["--gpus", "8"]).batch == 0 and bench.parse_args(["--batch", "64"]).batch == 64
 
 
+def test_dump_outputs_keeps_a_seeded_sample_of_whole_frames(tmp_path):
+    """--dump-outputs writes float32 powers; over its size limit a fixed, seeded sample of whole frames, the same every run."""
+    import numpy as np
+    import torch
+
+    bench = load_bench()
+    assert not bench.parse_args([]).full and bench.parse_args(["--full"]).full
+    power = torch.arange(40 * 100, dtype=torch.float32).reshape(40, 100)
+    bench.dump_outputs(tmp_path / "all", power)
+    assert np.array_equal(np.load(tmp_path / "all" / "power.npy"), power.numpy())
+    for run in ("a", "b"):
+        bench.dump_outputs(tmp_path / run, power, limit_bytes=10 * 100 * 4)
+    a, b = np.load(tmp_path / "a" / "power.npy"), np.load(tmp_path / "b" / "power.npy")
+    assert a.dtype == np.float32 and a.shape == (10, 100) and np.array_equal(a, b)
+    rows = a[:, 0].astype(int) // 100
+    assert list(rows) == sorted(set(rows)) and np.array_equal(a, power.numpy()[rows])
+
+
 def test_no_child_ranks_under_a_profiler():
     """Under rocprofv3 (or the repo's profiling scripts, which set AWPU_UNDER_PROFILER=1) the GPU is initialised before
     main() runs; starting torch.distributed.run from there is the exec this pool forbids.  --gpus N must refuse."""

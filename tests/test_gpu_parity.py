@@ -1604,7 +1604,7 @@ def test_bench_two_ranks_on_one_gpu_assemble_the_oracle_heatmap():
         if schedule:  # the schedule that spreads rank 0's pack pass over the ranks, pinned (over gloo it is slow, not wrong)
             env["BENCH_BCAST"] = schedule
         proc = subprocess.run([sys.executable, str(repo / "bench.py"), "--gpus", "2", "--workload", "c2", "--steps", "2", "--warmup", "1",
-                               "--cpu-seconds", "0"], env=env, capture_output=True, text=True, timeout=600)
+                               "--cpu-seconds", "0", "--full"], env=env, capture_output=True, text=True, timeout=600)
         assert proc.returncode == 0, proc.stderr[-3000:]
         lines = [ln for ln in proc.stdout.splitlines() if ln.startswith("{")]
         assert len(lines) == 1, proc.stdout[-2000:]
@@ -1615,6 +1615,37 @@ def test_bench_two_ranks_on_one_gpu_assemble_the_oracle_heatmap():
         assert "gather check: ok" in proc.stderr, proc.stderr[-3000:]
         if schedule:
             assert rec["config"]["frame_exchange"]["mode"] == schedule
+
+
+def test_bench_plain_run_times_only_and_dumps_the_last_step(oracle, pkg, tmp_path):
+    """A plain `bench.py` run times exactly --steps steps and prints the headline line without the --full legs; with
+    --dump-outputs the powers of its last timed step are written as float32, and they are the oracle's powers of the
+    run's seeded frames (frames b0 = 0 and 64 come from make_frames(seed + b0))."""
+    import json
+    import subprocess
+    import sys
+
+    repo = Path(__file__).resolve().parent.parent
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    proc = subprocess.run([sys.executable, str(repo / "bench.py"), "--gpus", "1", "--workload", "c2", "--steps", "3", "--warmup", "1",
+                           "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=300)
+    assert proc.returncode == 0, proc.stderr[-3000:]
+    lines = [ln for ln in proc.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, proc.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec["metric"] == "heatmap frames/sec" and rec["unit"] == "frames/s" and rec["higher_is_better"] is True
+    assert rec["dtype"] == "f32" and rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] > 0
+    assert not {"parity", "cpu_baseline", "single_frame", "workloads", "projected_scaling"} & set(rec)
+    S = pkg.synthetic
+    spec = S.WORKLOADS["c2"]
+    power = np.load(tmp_path / "power.npy")
+    assert power.dtype == np.float32 and power.shape == (128, spec.n_pixels)
+    xyz = S.geometry(spec)
+    off, frac = S.delay_table(spec, xyz)
+    for b in (0, 64):
+        frame = S.make_frames(xyz, 1, seed=1234 + b)[0]
+        rep = util.parity_report(power[b], oracle.das_f32(frame, off, frac))
+        assert rep["ok"], rep
 
 
 def test_dc_offset_frames_batched_sweep_is_closer_to_exact_than_the_reference(pkg, oracle):

@@ -10,7 +10,7 @@ trap 'cp "$out/keep.so" beamforming-lk_amd/libawpu_hip.so' EXIT  # whatever happ
 for rep in $(seq 1 ${REPS:-3}); do
 for v in "$@"; do
   cp tools/ab/$v beamforming-lk_amd/libawpu_hip.so
-  timeout -k 10 200 python bench.py --cpu-seconds 0 --no-extras ${BENCH_ARGS:-} > $out/${v}_$rep.json 2> $out/${v}_$rep.err
+  timeout -k 10 200 python bench.py --full --cpu-seconds 0 --no-extras ${BENCH_ARGS:-} > $out/${v}_$rep.json 2> $out/${v}_$rep.err
   python - "$out/${v}_$rep.json" $v <<'PY'
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][0])

@@ -12,9 +12,11 @@ timeout -k 10 600 python bench.py "$@" > $out/bench.json 2> $out/bench.err && ec
 python3 - $out/bench.json <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
-print("value %.0f frames/s  ms/step %.3f  kernel %s %.3f ms (min %.3f median %.3f)  valu %.3f  parity %.2e ok=%s" % (
+print("value %.0f frames/s  ms/step %.3f  kernel %s %.3f ms (min %.3f median %.3f)  valu %.3f" % (
     d["value"], d["ms_per_step"], d["roofline"]["kernel"], d["roofline"]["kernel_ms"], d["roofline"].get("kernel_ms_min", 0),
-    d["roofline"].get("kernel_ms_median", 0), d["valu"]["frac"], d["parity_max_rel_err"], d["parity"]["ok"]))
+    d["roofline"].get("kernel_ms_median", 0), d["valu"]["frac"]))
+if "parity" in d:  # (bench.py --full)
+    print("parity %.2e ok=%s" % (d["parity_max_rel_err"], d["parity"]["ok"]))
 if "single_frame" in d:
     s = d["single_frame"]; print("single_frame: %s %.1f us/frame valu %.3f parity %.2e" % (s.get("kernel"), s["ms_per_frame_device"] * 1e3, s["valu_frac"], s["parity_max_rel_err"]))
 if "reference_default" in d:

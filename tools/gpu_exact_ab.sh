@@ -12,7 +12,7 @@ timeout -k 10 600 python -m pytest tests -m gpu -x -q -s -k "${TESTS:-exact_mode
 for rep in $(seq 1 ${REPS:-2}); do
 for shape in "${@:-default}"; do
   if [ "$shape" = default ]; then unset AWPU_SHAPE; else export AWPU_SHAPE=$shape; fi
-  timeout -k 10 200 python bench.py --math exact --cpu-seconds 0 --no-extras ${BENCH_ARGS:-} > $out/${shape}_$rep.json 2> $out/${shape}_$rep.err \
+  timeout -k 10 200 python bench.py --full --math exact --cpu-seconds 0 --no-extras ${BENCH_ARGS:-} > $out/${shape}_$rep.json 2> $out/${shape}_$rep.err \
     || { echo "bench $shape FAILED"; tail -20 $out/${shape}_$rep.err; exit 1; }
   python - "$out/${shape}_$rep.json" $shape <<'PY'
 import json,sys

@@ -19,11 +19,11 @@ echo "profile exact done"
 fi
 if [ "$part" != "profiles" ]; then
 for wl in headline c1 c2 c3 c4 c5; do
-  timeout -k 10 500 python bench.py --workload $wl > $out/bench_$wl.json 2> $out/bench_$wl.err
+  timeout -k 10 500 python bench.py --full --workload $wl > $out/bench_$wl.json 2> $out/bench_$wl.err
   echo "bench $wl done"
 done
-timeout -k 10 400 python bench.py --workload c3 --interp fir8 > $out/bench_c3_fir8.json 2> $out/bench_c3_fir8.err
-timeout -k 10 400 python bench.py --math exact --no-extras > $out/bench_headline_exact.json 2> $out/bench_headline_exact.err
-BENCH_REHEARSAL=1 BENCH_GATHER_CHECK=1 timeout -k 10 300 python bench.py --gpus 2 --steps 3 --warmup 1 > $out/bench_rehearsal2.json 2> $out/bench_rehearsal2.err
+timeout -k 10 400 python bench.py --full --workload c3 --interp fir8 > $out/bench_c3_fir8.json 2> $out/bench_c3_fir8.err
+timeout -k 10 400 python bench.py --full --math exact --no-extras > $out/bench_headline_exact.json 2> $out/bench_headline_exact.err
+BENCH_REHEARSAL=1 BENCH_GATHER_CHECK=1 timeout -k 10 300 python bench.py --full --gpus 2 --steps 3 --warmup 1 > $out/bench_rehearsal2.json 2> $out/bench_rehearsal2.err
 fi
 echo all done

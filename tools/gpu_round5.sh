@@ -16,10 +16,10 @@ declare -A ARGS=( [default]="" [fast]="--math fast" [batch1]="--batch 1 --steps 
 for c in "${cfgs[@]}"; do
   a=${ARGS[$c]}
   d=$out/$c; mkdir -p $d
-  if [ "$c" = default ]; then  # the full default line, as the driver runs it
-    timeout -k 10 400 python bench.py > $d/bench.json 2> $d/bench.err || { echo "bench $c failed"; tail -5 $d/bench.err; exit 1; }
+  if [ "$c" = default ]; then  # the default line with every --full leg
+    timeout -k 10 400 python bench.py --full > $d/bench.json 2> $d/bench.err || { echo "bench $c failed"; tail -5 $d/bench.err; exit 1; }
   else
-    timeout -k 10 300 python bench.py --cpu-seconds 0 --no-extras $a > $d/bench.json 2> $d/bench.err || { echo "bench $c failed"; tail -5 $d/bench.err; exit 1; }
+    timeout -k 10 300 python bench.py --full --cpu-seconds 0 --no-extras $a > $d/bench.json 2> $d/bench.err || { echo "bench $c failed"; tail -5 $d/bench.err; exit 1; }
   fi
   echo "bench $c done"
   export AWPU_UNDER_PROFILER=1
