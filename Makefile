@@ -10,16 +10,16 @@ HIPCC ?= /opt/rocm/bin/hipcc
 PKG := beamforming-lk_amd
 CSRC := $(PKG)/csrc
 LIB := $(PKG)/libawpu_hip.so
-KERNEL_SRC := $(CSRC)/das_kernels.hip $(CSRC)/das_fast.hip $(CSRC)/awpu_hip.cpp $(CSRC)/geometry_host.cpp
+KERNEL_SRC := $(CSRC)/das_kernels.hip $(CSRC)/das_fast.hip $(CSRC)/track_kernels.hip $(CSRC)/awpu_hip.cpp $(CSRC)/geometry_host.cpp
 HOST_SRC := $(PKG)/host/mimo_worker_hip.cpp $(PKG)/host/aw_processing_unit_hip.cpp $(PKG)/host/pipeline_hip.cpp \
-            $(PKG)/host/aw_processing_unit.cpp
+            $(PKG)/host/aw_processing_unit.cpp $(PKG)/host/spherical_gradient_hip.cpp
 # OPENCV_CFLAGS: where <opencv2/core.hpp> lives; defaults to the tests' few-line stand-in for cv::Mat (no OpenCV here)
 OPENCV_CFLAGS ?= -Itests/host/mock_opencv
 
 .PHONY: lib oracle host-test example trips clean
 lib: $(LIB)
 
-$(LIB): $(KERNEL_SRC) $(CSRC)/das_kernels.h $(CSRC)/das_fast_trip.inc include/awpu_hip.h
+$(LIB): $(KERNEL_SRC) $(CSRC)/das_kernels.h $(CSRC)/das_fast_trip.inc include/awpu_hip.h include/awpu_hip_track.h
 	$(HIPCC) --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -Wall -Wno-unused-result -Werror=inline-asm -x hip \
 	    -Iinclude -I$(CSRC) $(KERNEL_SRC) -o $@
 
@@ -40,6 +40,9 @@ host-test: $(LIB) oracle
 	g++ -O2 -std=c++17 -pthread -DAWPU_WITH_OPENCV $(OPENCV_CFLAGS) -Iinclude -I$(PKG)/host -Ioracle tests/host/test_exact_signatures.cpp $(HOST_SRC) \
 	    -L$(PKG) -lawpu_hip -Loracle -loracle_das -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -Wl,-rpath,'$$ORIGIN/../../oracle' -Wl,-rpath,/opt/rocm/lib \
 	    -o tests/host/test_exact_signatures
+	g++ -O2 -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -I$(PKG)/host tests/host/test_spherical_gradient.cpp \
+	    $(PKG)/host/spherical_gradient_hip.cpp -L$(PKG) -lawpu_hip -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN/../../$(PKG)' \
+	    -Wl,-rpath,/opt/rocm/lib -o tests/host/test_spherical_gradient
 
 example: $(LIB)
 	gcc -O2 -Wall -Iinclude examples/heatmap_min.c -L$(PKG) -lawpu_hip -lm -Wl,-rpath,'$$ORIGIN/../$(PKG)' \
@@ -48,5 +51,5 @@ example: $(LIB)
 	    -Wl,-rpath,/opt/rocm/lib -o examples/live_call_rate
 
 clean:
-	rm -f $(LIB) tests/host/test_mimo_worker tests/host/test_exact_signatures examples/heatmap_min examples/live_call_rate
+	rm -f $(LIB) tests/host/test_mimo_worker tests/host/test_exact_signatures tests/host/test_spherical_gradient examples/heatmap_min examples/live_call_rate
 	$(MAKE) -C oracle clean

@@ -141,6 +141,39 @@ _SIGNATURES = {
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
 
+class Particle(C.Structure):
+    """awpu_particle_t (include/awpu_hip_track.h)."""
+    _fields_ = [
+        ("theta", C.c_double),
+        ("phi", C.c_double),
+        ("spread", C.c_double),
+        ("rate", C.c_double),
+        ("steps", C.c_int32),
+        ("error", C.c_float),
+        ("grad_theta", C.c_double),
+        ("grad_phi", C.c_double),
+        ("radius", C.c_double),
+        ("power", C.c_float * 4),
+    ]
+
+
+# particle tracking: the entry points of include/awpu_hip_track.h (EXPORTED_SYMBOLS is awpu_hip.h's set)
+_TRACK_SIGNATURES = {
+    "awpu_hip_set_antenna": (C.c_int, [C.c_void_p, _f32p, C.c_int32]),
+    "awpu_hip_steer_table_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32, _i32p,
+                                              _f32p]),
+    "awpu_hip_track": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Particle), C.c_int32, C.c_double, C.c_double,
+                                 C.POINTER(C.c_double), _f32p]),
+}
+TRACK_SYMBOLS = tuple(_TRACK_SIGNATURES)
+
+# numpy view of awpu_particle_t: what Engine.track returns, one record per particle
+PARTICLE_DTYPE = np.dtype([("theta", "<f8"), ("phi", "<f8"), ("spread", "<f8"), ("rate", "<f8"), ("steps", "<i4"),
+                           ("error", "<f4"), ("grad_theta", "<f8"), ("grad_phi", "<f8"), ("radius", "<f8"),
+                           ("power", "<f4", (4,))], align=True)
+assert PARTICLE_DTYPE.itemsize == C.sizeof(Particle) == 80
+
+
 def load(build: bool = True) -> C.CDLL:
     """Load (building first if stale) the in-tree libawpu_hip.so."""
     global _lib
@@ -161,7 +194,7 @@ def load(build: bool = True) -> C.CDLL:
     if not path.exists():
         raise RuntimeError(f"{path} is missing and there is no CPU fallback")
     lib = C.CDLL(str(path))
-    for name, (res, args) in _SIGNATURES.items():
+    for name, (res, args) in list(_SIGNATURES.items()) + list(_TRACK_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -279,6 +312,23 @@ def heatmap_u8(power: np.ndarray) -> np.ndarray:
 
 
 # ------------------------------------------------------------------------------- engine
+
+
+class TrackResult:
+    """What Engine.track hands back: the particles after the call and the call's reference power / beams."""
+
+    def __init__(self, particles: np.ndarray, reference: float, beams: Optional[np.ndarray]):
+        self.particles = particles
+        self.reference = reference
+        self.beams = beams
+
+    def __getattr__(self, name):
+        if name in PARTICLE_DTYPE.names:
+            return self.particles[name]
+        raise AttributeError(name)
+
+    def __len__(self):
+        return self.particles.size
 
 
 class Engine:
@@ -452,6 +502,54 @@ class Engine:
         _check(self._lib.awpu_hip_beams(self._h, C.c_void_p(d_frame_ptr), _i32(off), _f32(frac), n, _f32(power),
                                         _f32(out) if want_beams else None), "awpu_hip_beams")
         return power, out
+
+    def set_antenna(self, xyz: np.ndarray) -> None:
+        """The element positions xyz [3, n] (stream ids, n <= lut_stride) the particles steer with (awpu_hip_set_antenna)."""
+        xyz = np.ascontiguousarray(xyz, np.float32)
+        if xyz.ndim != 2 or xyz.shape[0] != 3:
+            raise ValueError("xyz must be [3, n]")
+        _check(self._lib.awpu_hip_set_antenna(self._h, _f32(xyz), xyz.shape[1]), "awpu_hip_set_antenna")
+        self._antenna_n = xyz.shape[1]
+
+    def steer_table_device(self, theta, phi):
+        """steer_table for the handle's antenna, computed on the device -> (off, frac) [n_dir, n]."""
+        theta = np.ascontiguousarray(np.atleast_1d(theta), np.float64)
+        phi = np.ascontiguousarray(np.atleast_1d(phi), np.float64)
+        if theta.shape != phi.shape or theta.ndim != 1:
+            raise ValueError("theta and phi must be 1-D and alike")
+        # (the row length is the n of the last set_antenna call through this Engine: set the antenna here, not through the
+        # C entry point on the same handle)
+        n = getattr(self, "_antenna_n", 0)
+        if not n:
+            raise AwpuError(ERR_STATE, "steer_table_device", "antenna not set (Engine.set_antenna)")
+        off = np.empty((theta.size, n), np.int32)
+        frac = np.empty((theta.size, n), np.float32)
+        dp = C.POINTER(C.c_double)
+        _check(self._lib.awpu_hip_steer_table_device(self._h, theta.ctypes.data_as(dp), phi.ctypes.data_as(dp), theta.size,
+                                                     _i32(off), _f32(frac)), "awpu_hip_steer_table_device")
+        return off, frac
+
+    def track(self, theta, phi, spread, rate, steps, theta_limit: float, reference: Optional[float] = None,
+              d_frame_ptr: int = 0, want_beams: bool = False):
+        """awpu_hip_track: every particle k advanced by steps[k] gradient steps in one launch.  theta/phi/spread/rate/steps are
+        per particle (scalars broadcast); reference None = computed on the device; d_frame_ptr 0 = the ingest ring.
+        -> TrackResult: .particles (PARTICLE_DTYPE records after the call), .theta, .phi, .error, .grad_theta,
+        .grad_phi, .radius, .power [n, 4], .reference, .beams [n, 256] or None."""
+        theta = np.atleast_1d(np.asarray(theta, np.float64))
+        n = max(theta.size, np.size(phi), np.size(spread), np.size(rate), np.size(steps))
+        parts = np.zeros(n, PARTICLE_DTYPE)
+        parts["theta"], parts["phi"] = np.broadcast_to(theta, n), np.broadcast_to(np.asarray(phi, np.float64), n)
+        parts["spread"], parts["rate"] = np.broadcast_to(np.asarray(spread, np.float64), n), np.broadcast_to(np.asarray(rate, np.float64), n)
+        steps = np.broadcast_to(np.asarray(steps, np.int64), n)
+        if steps.size and (steps.min() < 0 or steps.max() > 4096):  # (before the int32 field could wrap it into range)
+            raise AwpuError(ERR_INVALID, "awpu_hip_track", "steps outside [0, 4096]")
+        parts["steps"] = steps
+        used = C.c_double(0.0)
+        beams = np.empty((n, 256), np.float32) if want_beams else None
+        _check(self._lib.awpu_hip_track(self._h, C.c_void_p(d_frame_ptr), parts.ctypes.data_as(C.POINTER(Particle)), n,
+                                        float(theta_limit), -1.0 if reference is None else float(reference), C.byref(used),
+                                        _f32(beams) if want_beams else None), "awpu_hip_track")
+        return TrackResult(parts, float(used.value), beams)
 
     def live_block(self, wire, rows: int, cols: int, out_rows: int = 0, out_cols: int = 0,
                    d_colormap_ptr: int = 0, want_power: bool = True, out=None):

@@ -2,6 +2,7 @@
 // packing, frame upload, kernel dispatch.  No CPU fallback: every compute entry point ends
 // in a gfx950 kernel launch or an error status.
 #include "awpu_hip.h"
+#include "awpu_hip_track.h"
 
 #include <hip/hip_runtime.h>
 
@@ -120,6 +121,14 @@ struct awpu_hip {
     awpu::LutEntry *d_beam_lut = nullptr;  // [beam_cap][usable] entries of awpu_hip_beams
     float *d_beam_out = nullptr;           // [beam_cap] powers then [beam_cap][256] beams
     size_t beam_cap = 0, beam_lut_cap = 0;
+    // particle tracking (awpu_hip_track.h)
+    std::vector<float> antenna;            // [3][antenna_n] element positions by stream id (awpu_hip_set_antenna); empty = none
+    float *d_xyz = nullptr;                // ... on the device
+    std::vector<int32_t> track_index;      // the active mics d_track_index holds
+    int32_t *d_track_index = nullptr;
+    size_t track_index_cap = 0;
+    unsigned char *d_track = nullptr;      // particles, then the reference used, then [n][256] beams (steer_table_device: angles, tables)
+    size_t track_cap = 0;                  // bytes
     float *d_fir = nullptr;  // [101][8] coefficient table (AWPU_INTERP_FIR8)
     float *d_ring = nullptr;            // [n_streams][2048] history ring (awpu_hip_ingest_block)
     uint8_t *d_display = nullptr;       // awpu_hip_live_block: peak (one float), compact image, upscaled image
@@ -348,6 +357,12 @@ void release_device(awpu_hip *h) {
     dev_free(h->d_calib);
     dev_free(h->d_beam_lut);
     dev_free(h->d_beam_out);
+    dev_free(h->d_xyz);
+    dev_free(h->d_track_index);
+    h->track_index_cap = 0;
+    h->track_index.clear();
+    dev_free(h->d_track);
+    h->track_cap = 0;
     dev_free(h->d_fir);
     dev_free(h->d_ring);
     dev_free(h->d_pack);
@@ -2568,6 +2583,145 @@ int awpu_hip_beams(awpu_hip_t *h, const float *d_frame, const int32_t *off, cons
         AWPU_HIP_TRY(hipMemcpyAsync(beams, d_beams, (size_t) n_dir * awpu::kSamples * sizeof(float),
                                     hipMemcpyDeviceToHost, h->stream));
     AWPU_HIP_TRY(hipStreamSynchronize(h->stream));  // `entries` must outlive the upload
+    return AWPU_OK;
+}
+
+// ---- particle tracking (include/awpu_hip_track.h; kernels in track_kernels.hip) ---------------------------------------
+
+int awpu_hip_set_antenna(awpu_hip_t *h, const float *xyz, int32_t n) {
+    if (h && !h->parts.empty()) h = h->parts[0];  // not pixel-sharded: a device group answers with its first device
+    AWPU_CTX(h);
+    if (!h || !xyz) return invalid("null argument");
+    if (n < 1 || n > h->cfg.lut_stride) return invalid("n outside [1, lut_stride]");
+    for (int k = 0; k < 3 * n; k++)
+        if (!std::isfinite(xyz[k])) return invalid("element position not finite");
+    // the aperture in samples bounds every delay a direction can form (tau = projection * scale - its minimum), so
+    // with it at most 256 every table entry has off in [0, 256] and delay() reads inside [0, 512]
+    double widest = 0.0;
+    for (int a = 0; a < n; a++)
+        for (int b = a + 1; b < n; b++) {
+            const double dx = (double) xyz[a] - xyz[b], dy = (double) xyz[n + a] - xyz[n + b], dz = (double) xyz[2 * n + a] - xyz[2 * n + b];
+            widest = std::max(widest, dx * dx + dy * dy + dz * dz);
+        }
+    if (std::sqrt(widest) * (48828.0 / 340.0) > (double) awpu::kSamples)
+        return fail(AWPU_ERR_RANGE, "antenna aperture exceeds 256 samples: delays would read outside the frame history");
+    AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
+    if (h->antenna.size() != (size_t) 3 * n) {
+        dev_free(h->d_xyz);
+        h->antenna.clear();
+        AWPU_HIP_TRY(hipMalloc(&h->d_xyz, (size_t) 3 * n * sizeof(float)));
+    }
+    AWPU_HIP_TRY(hipMemcpy(h->d_xyz, xyz, (size_t) 3 * n * sizeof(float), hipMemcpyHostToDevice));
+    h->antenna.assign(xyz, xyz + (size_t) 3 * n);
+    return AWPU_OK;
+}
+
+namespace {
+
+int ensure_track_buffer(awpu_hip *h, size_t bytes) {
+    if (h->track_cap >= bytes) return AWPU_OK;
+    dev_free(h->d_track);
+    h->track_cap = 0;
+    AWPU_HIP_TRY(hipMalloc(&h->d_track, bytes));
+    h->track_cap = bytes;
+    return AWPU_OK;
+}
+
+size_t align16(size_t n) { return (n + 15) & ~(size_t) 15; }
+
+static_assert(sizeof(awpu_particle_t) == 80, "awpu_particle_t is part of the ABI (include/awpu_hip_track.h)");
+
+}  // namespace
+
+int awpu_hip_steer_table_device(awpu_hip_t *h, const double *theta, const double *phi, int32_t n_dir, int32_t *off,
+                                float *frac) {
+    if (h && !h->parts.empty()) h = h->parts[0];  // not pixel-sharded: a device group answers with its first device
+    AWPU_CTX(h);
+    if (!h || !theta || !phi || !off || !frac) return invalid("null argument");
+    if (n_dir < 1 || n_dir > 65535) return invalid("n_dir outside [1, 65535]");
+    if (h->antenna.empty()) return fail(AWPU_ERR_STATE, "antenna not set (awpu_hip_set_antenna)");
+    const int n = (int) (h->antenna.size() / 3);
+    AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
+    const size_t angles = align16((size_t) n_dir * sizeof(double)), table = (size_t) n_dir * n;
+    if (int rc = ensure_track_buffer(h, 2 * angles + table * (sizeof(int32_t) + sizeof(float)))) return rc;
+    double *d_theta = (double *) h->d_track, *d_phi = (double *) (h->d_track + angles);
+    int32_t *d_off = (int32_t *) (h->d_track + 2 * angles);
+    float *d_frac = (float *) (d_off + table);
+    AWPU_HIP_TRY(hipMemcpyAsync(d_theta, theta, (size_t) n_dir * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    AWPU_HIP_TRY(hipMemcpyAsync(d_phi, phi, (size_t) n_dir * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    AWPU_HIP_TRY(awpu::launch_steer_table(h->d_xyz, n, d_theta, d_phi, n_dir, d_off, d_frac, h->stream));
+    AWPU_HIP_TRY(hipMemcpyAsync(off, d_off, table * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    AWPU_HIP_TRY(hipMemcpyAsync(frac, d_frac, table * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    AWPU_HIP_TRY(hipStreamSynchronize(h->stream));
+    return AWPU_OK;
+}
+
+int awpu_hip_track(awpu_hip_t *h, const float *d_frame, awpu_particle_t *p, int32_t n, double theta_limit,
+                   double reference, double *reference_used, float *beams) {
+    if (h && !h->parts.empty()) h = h->parts[0];  // not pixel-sharded: a device group answers with its first device
+    AWPU_CTX(h);
+    if (!h || !p) return invalid("null argument");
+    if (n < 1 || n > 65535) return invalid("n outside [1, 65535]");
+    if (!(theta_limit > 0.0) || !std::isfinite(theta_limit)) return invalid("theta_limit must be finite and > 0");
+    if (!std::isfinite(reference)) return invalid("reference not finite");
+    for (int k = 0; k < n; k++) {
+        if (p[k].steps < 0 || p[k].steps > 4096) return invalid("steps outside [0, 4096]");
+        if (!std::isfinite(p[k].theta) || !std::isfinite(p[k].phi) || !std::isfinite(p[k].spread) || !std::isfinite(p[k].rate))
+            return invalid("particle direction, spread or rate not finite");
+    }
+    if (h->antenna.empty()) return fail(AWPU_ERR_STATE, "antenna not set (awpu_hip_set_antenna)");
+    if (!h->have_mics || h->index.empty()) return fail(AWPU_ERR_STATE, "active mics not set");
+    const int n_el = (int) (h->antenna.size() / 3);
+    for (int id : h->index)
+        if (id >= n_el) return fail(AWPU_ERR_STATE, "an active mic is not an element of the antenna");
+    int pitch = h->cfg.hist;
+    const float *frame = d_frame;
+    if (!frame) {  // the current snapshot of the ingest ring
+        if (!h->d_ring) return fail(AWPU_ERR_STATE, "no block ingested yet");
+        frame = h->d_ring + h->ring_pos;
+        pitch = 2048;
+    } else if (h->cfg.hist < 2 * awpu::kSamples + 1) {
+        return fail(AWPU_ERR_RANGE, "history shorter than 513 samples: a steered delay can read outside it");
+    }
+    AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
+    const int U = h->usable();
+    if (h->track_index != h->index) {
+        if (h->track_index_cap < (size_t) U) {
+            dev_free(h->d_track_index);
+            h->track_index_cap = 0;
+            AWPU_HIP_TRY(hipMalloc(&h->d_track_index, (size_t) U * sizeof(int32_t)));
+            h->track_index_cap = U;
+        }
+        h->track_index.clear();
+        AWPU_HIP_TRY(hipMemcpy(h->d_track_index, h->index.data(), (size_t) U * sizeof(int32_t), hipMemcpyHostToDevice));
+        h->track_index = h->index;
+    }
+    const size_t particles = (size_t) n * sizeof(awpu_particle_t), head = align16(particles + sizeof(double));
+    if (int rc = ensure_track_buffer(h, head + (beams ? (size_t) n * awpu::kSamples * sizeof(float) : 0))) return rc;
+    awpu::TrackArgs a{};
+    a.frame = frame;
+    a.pitch = pitch;
+    a.xyz = h->d_xyz;
+    a.n = n_el;
+    a.index = h->d_track_index;
+    a.usable = U;
+    a.particles = h->d_track;
+    a.n_particles = n;
+    a.theta_limit = theta_limit;
+    a.reference = reference;
+    a.reference_out = (double *) (h->d_track + particles);
+    a.beams = beams ? (float *) (h->d_track + head) : nullptr;
+    AWPU_HIP_TRY(hipMemcpyAsync(h->d_track, p, particles, hipMemcpyHostToDevice, h->stream));
+    AWPU_HIP_TRY(awpu::launch_track(a, h->stream));
+    double used = 0.0;
+    std::vector<unsigned char> back(particles + sizeof(double));
+    AWPU_HIP_TRY(hipMemcpyAsync(back.data(), h->d_track, back.size(), hipMemcpyDeviceToHost, h->stream));
+    if (beams)
+        AWPU_HIP_TRY(hipMemcpyAsync(beams, a.beams, (size_t) n * awpu::kSamples * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    AWPU_HIP_TRY(hipStreamSynchronize(h->stream));
+    std::memcpy(p, back.data(), particles);
+    std::memcpy(&used, back.data() + particles, sizeof(double));
+    if (reference_used) *reference_used = used;
     return AWPU_OK;
 }
 

@@ -331,6 +331,76 @@ hipError_t launch_heatmap(const float *d_power, int n, int batch, float *d_peak,
 hipError_t launch_das_beams(const float *d_frame, const LutEntry *d_entries, int usable, int n_dir, float *d_power,
                             float *d_beams, hipStream_t stream);
 
+// The body of das_beam_kernel, shared with gradient_track_kernel (track_kernels.hip) so that both give the same bits for
+// the same table.  A workgroup of 256 lanes, lane i = output sample i; NB beams at once, rows[q * row_stride + s] the
+// entry of beam q and active mic s (global or LDS).  Every beam visits the mics in the reference's order with delay()'s
+// operations (d = cur - next; t = fma(frac, d, next); out += t), src/dsp/delay.cpp:16-26.
+template <int NB>
+__device__ __forceinline__ void beam_sums(const float *frame, const LutEntry *rows, size_t row_stride, int usable, int i,
+                                          float (&out)[NB]) {
+#pragma unroll
+    for (int q = 0; q < NB; q++) out[q] = 0.0f;
+    for (int s = 0; s < usable; s++) {
+#pragma unroll
+        for (int q = 0; q < NB; q++) {
+            const LutEntry e = rows[q * row_stride + s];  // uniform
+            const float *x = frame + e.off_rel + i;
+            const float cur = x[0], nxt = x[1];
+            const float d = cur - nxt;
+            const float t = __builtin_fmaf(e.frac, d, nxt);
+            out[q] = out[q] + t;
+        }
+    }
+}
+
+// power = sum_{i=1..254} MA[i]^2 / N_SAMPLES of each beam (particle.cpp:68-77), in every lane.  line [NB][256] and
+// partial [NB][4] are LDS; the call holds two barriers.
+template <int NB>
+__device__ __forceinline__ void beam_powers(const float (&out)[NB], int i, float (*line)[kSamples], float (*partial)[kSamples / 64],
+                                            float (&power)[NB]) {
+#pragma unroll
+    for (int q = 0; q < NB; q++) line[q][i] = out[q];
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < NB; q++) {
+        float sq = 0.0f;
+        if (i >= 1 && i <= kSamples - 2) {
+            const float ma = out[q] * 0.5f - 0.25f * (line[q][i + 1] + line[q][i - 1]);
+            sq = ma * ma;
+        }
+#pragma unroll
+        for (int s = 32; s >= 1; s >>= 1) sq += __shfl_xor(sq, s);
+        if ((i & 63) == 0) partial[q][i >> 6] = sq;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < NB; q++) power[q] = (partial[q][0] + partial[q][1] + partial[q][2] + partial[q][3]) / (float) kSamples;
+}
+
+// ---- particle tracking (track_kernels.hip) ----------------------------------------------------------------------------
+// Particle::steer on the device for the directions theta/phi [n_dir] (double), elements d_xyz [3][n]:
+// d_off / d_frac [n_dir][n], bit-identical to awpu_hip_steer_table
+hipError_t launch_steer_table(const float *d_xyz, int n, const double *d_theta, const double *d_phi, int n_dir, int32_t *d_off,
+                              float *d_frac, hipStream_t stream);
+
+struct TrackArgs {
+    const float *frame;    // snapshot: stream id s starts at frame + s * pitch
+    int32_t pitch;
+    const float *xyz;      // [3][n] element positions by stream id
+    int32_t n;
+    const int32_t *index;  // [usable] active stream ids, the reference's order
+    int32_t usable;
+    void *particles;       // awpu_particle_t [n_particles] (include/awpu_hip_track.h), in and out
+    int32_t n_particles;
+    double theta_limit;
+    double reference;      // <= 0: computed by the kernel
+    double *reference_out; // the value used (written by workgroup 0)
+    float *beams;          // [n_particles][256] das() at the final directions, or null
+};
+// LDS bytes gradient_track_kernel asks for: the four neighbours' tables of `usable` entries
+size_t track_lds_bytes(int usable);
+hipError_t launch_track(const TrackArgs &a, hipStream_t stream);
+
 // geometry_host.cpp: the per-pixel half of computeDelayLUT for the device builder (rot [row_count * columns][12])
 void pixel_rotations(int rows, int columns, float fov_deg, int row_begin, int row_count, float *rot);
 float samples_per_metre();  // (float) (48828 / 340), antenna.cpp:90

@@ -246,36 +246,19 @@ hipError_t launch_heatmap(const float *d_power, int n, int batch, float *d_peak,
 // next); out += t), so the 256-sample beam -- the signal MISOWorker hands to the audio path,
 // miso.cpp:46 -- is bit-identical to the reference's.  A direction reads 64 x 257 floats that all
 // directions share, straight from L2: no LDS staging at this size.  power = sum MA^2 / N_SAMPLES
-// (particle.cpp:68-77: not divided by the mic count, unlike the MIMO sweep).
+// (particle.cpp:68-77: not divided by the mic count, unlike the MIMO sweep).  The body is beam_sums / beam_powers
+// (das_kernels.h), which gradient_track_kernel shares.
 // ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kSamples) void das_beam_kernel(const float *frame, const LutEntry *entries, int usable,
                                                             float *power, float *beams) {
-    __shared__ float line[kSamples];
-    __shared__ float partial[kSamples / 64];
+    __shared__ float line[1][kSamples];
+    __shared__ float partial[1][kSamples / 64];
     const int i = threadIdx.x;
-    const LutEntry *row = entries + (size_t) blockIdx.x * usable;
-    float out = 0.0f;
-    for (int s = 0; s < usable; s++) {
-        const LutEntry e = row[s];  // uniform: scalar load
-        const float *x = frame + e.off_rel + i;
-        const float cur = x[0], nxt = x[1];
-        const float d = cur - nxt;
-        const float t = __builtin_fmaf(e.frac, d, nxt);
-        out = out + t;
-    }
-    if (beams) beams[(size_t) blockIdx.x * kSamples + i] = out;
-    line[i] = out;
-    __syncthreads();
-    float sq = 0.0f;
-    if (i >= 1 && i <= kSamples - 2) {
-        const float ma = out * 0.5f - 0.25f * (line[i + 1] + line[i - 1]);
-        sq = ma * ma;
-    }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) sq += __shfl_xor(sq, s);
-    if ((i & 63) == 0) partial[i >> 6] = sq;
-    __syncthreads();
-    if (i == 0 && power) power[blockIdx.x] = (partial[0] + partial[1] + partial[2] + partial[3]) / (float) kSamples;
+    float out[1], pw[1];
+    beam_sums<1>(frame, entries + (size_t) blockIdx.x * usable, 0, usable, i, out);
+    if (beams) beams[(size_t) blockIdx.x * kSamples + i] = out[0];
+    beam_powers<1>(out, i, line, partial, pw);
+    if (i == 0 && power) power[blockIdx.x] = pw[0];
 }
 
 hipError_t launch_das_beams(const float *d_frame, const LutEntry *d_entries, int usable, int n_dir, float *d_power,
