@@ -1318,7 +1318,8 @@ __global__ __launch_bounds__(1024, 4) void das_exact_quad_kernel(ExactQuadArgs a
 // 8 + 4 per distinct address -- and the pre-epilogue sums are still the reference's bits (a.sums exports them).
 // Workgroup = 16 waves, a wave NQ quads of four vertically adjacent pixels (tile = 4 NQ rows x 16 columns: twice the pixels per
 // barrier, the 16-byte elements halve the mics per chunk); the whole item -- chunk loop, in-block refill, barrier -- runs inside
-// sweep_exact_nd_item<NQ> (tools/gen_trip_asm.py, block_exact_nd).  Epilogue, item order: das_exact_quad_kernel's.
+// sweep_exact_nd_item<NQ> (tools/gen_trip_asm.py, block_exact_nd).  Epilogue, item order: das_exact_quad_kernel's.  NQ = 2 sweeps the two quads as one
+// octet: each distinct LDS address of the eight rows is read once per mic.
 // ---------------------------------------------------------------------------------------
 // (next, cur - next) of one sample with the per-mic gain on both samples first, every operation rounded on its own: hipcc's
 // __fmul_rn / __fsub_rn are plain `*` and `-`, which it contracts into an FMA where it can (caught by the gains case of

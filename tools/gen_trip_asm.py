@@ -661,7 +661,7 @@ ND_TIMING = os.environ.get("ND_TIMING", "")  # tuning builds only (see the end o
 ND_PRIO = int(os.environ.get("ND_PRIO", "5"))  # tuning builds only: the wave-priority scheme of block_exact_nd's trips
 
 
-def block_exact_nd(name, nq, nk=4, nw=16, refill=True):
+def block_exact_nd(name, nq, nk=4, nw=16, refill=True, octet=False):
     """Reference-order sweep (AWPU_MATH_F32_EXACT, round 5) of a WHOLE item -- frame pair x tile, `nq` quads of four vertically
     adjacent pixels per wave -- on the {next, d} layout: pack_nd_kernel stores, per mic and sample t of the window, the 16-byte element
         { next_a, next_b, d_a, d_b },   next = X[t + 1],  d = X[t] - X[t + 1]      (a, b = the two frames of the pair)
@@ -680,6 +680,13 @@ def block_exact_nd(name, nq, nk=4, nw=16, refill=True):
     reference's and X), then the pixels that sweep X, then the request of X for the next mic, then the pixels on the reference's
     elements -- so X has three pixels' worth of FMAs to land.
 
+    octet = True (nq = 2, das_exact_nd_kernel<2>): the two quads are ONE octet, eight rows of a column, swept mic by mic.  In row order
+    a run of pixels with one address reads it once; runs alternate between the mic's first slot (R[m]) and X, and each run's read goes
+    out where the run before it begins, so it has that run's FMAs to land; the other R slot takes the next mic's first run at the mic's
+    head.  Every pattern takes that path (no read-on-the-spot case).  A trip is two mics x eight pixels (32 SGPRs, a s_load_dwordx4 per
+    pixel: quad A's four at the first mic's head, quad B's at the second's); every wait is lgkmcnt(0), the only count that proves a
+    scalar load, which returns out of order.  Headline: 2.18 sets of reads per octet and mic instead of 2 x 1.51.
+
     Item structure (the production quad block's, _block_quad_item): chunk loop, in-block refill of the other LDS image (one 16 KiB
     piece at the head of each trip), vmcnt wait and workgroup barrier inside the block, the next chunk's first entries already in
     SGPRs when a chunk begins (a quad's table is contiguous across chunks; the running prefetch switches between the quads' tables
@@ -696,6 +703,7 @@ def block_exact_nd(name, nq, nk=4, nw=16, refill=True):
 
     nw = waves per workgroup (a refill piece is nw x 1 KiB): 16.  (8 and 4 were built for single frames on small grids -- c2 76.6 ->
     71.7 / 68.9 us -- until one pixel per wave, block_exact_solo, replaced them.)"""
+    assert not octet or (nq == 2 and nk == 4 and refill)
     DMA_PIECE = nw * 1024
     w = 2 * nk  # registers per pixel's out[]
     O = [[ND_ACC + 4 * w * q + w * p for p in range(4)] for q in range(nq)]
@@ -857,7 +865,80 @@ def block_exact_nd(name, nq, nk=4, nw=16, refill=True):
             L += mic_step(cur, st, rslot, nbase, ni)
         return L
 
+    # ---- octet form (nq = 2, nk = 4): both quads of the wave swept mic by mic, every distinct address of the eight read once ----
+    def of_(base, P, j):  # octet sets: pixel P's entries of the trip's mics j = 0, 1 at base + 4 P
+        return base + 4 * P + 2 * j
+
+    def oterms(P, base, j, slot):
+        fs = f"s[{of_(base, P, j)}:{of_(base, P, j) + 1}]"
+        Op = O[P >> 2][P & 3]
+        L = []
+        for k0 in range(0, nk, 2):
+            for k in (k0, k0 + 1):
+                L.append(f"v_pk_fma_f32 {opair(TT, k - k0)}, {fs}, {d_of(slot, k)}, {nxt_of(slot, k)} op_sel_hi:[0,1,1]")
+            for k in (k0, k0 + 1):
+                L.append(f"v_pk_add_f32 {opair(Op, k)}, {opair(Op, k)}, {opair(TT, k - k0)}")
+        return L
+
+    def oct_loads(nbase, half):
+        """the next set's entries of quad `half` (pixels 4 half ..): one s_load_dwordx4 per pixel, its two mics' (f, addr)"""
+        if half == 0:
+            return [f"s_load_dwordx4 s[{nbase + 4 * P}:{nbase + 4 * P + 3}], %[ptr], s{S_PF_} offset:{hex(32 * P)}" for P in range(4)]
+        return [f"s_add_u32 s{S_TMP}, s{S_PF_}, %[qstride]"] + [
+            f"s_load_dwordx4 s[{nbase + 4 * P}:{nbase + 4 * P + 3}], %[ptr], s{S_TMP} offset:{hex(32 * (P - 4))}" for P in range(4, 8)]
+
+    def oct_mic(par, m):
+        """mic m of a trip out of set E[par].  Runs of equal addresses in row order alternate between slots A (= R[m], which holds
+        the first run's elements on entry) and X; a run's read is issued where the run before it begins (the scan of its addresses
+        finds where it ends), so it has that run's FMAs to land.  R[1 - m] receives the next mic's first run at the head."""
+        cur, nxt = E[par], E[1 - par]
+        u = uid()
+        slot = {"A": R[m], "X": X}
+        other = {"A": "X", "X": "A"}
+        a = lambda P: of_(cur, P, m) + 1
+        if m == 0:
+            # this mic's first run, and the set's quad-B entries: only a zero count proves a scalar load (they return out of order)
+            L = ["s_waitcnt lgkmcnt(0)"]
+            L += reads(R[1], of_(cur, 0, 1) + 1)  # the next mic's first run
+            L += oct_loads(nxt, 0)
+        else:
+            L = ["s_waitcnt lgkmcnt(0)"]  # this mic's first run, and the next set's quad-A entries
+            L += reads(R[0], of_(nxt, 0, 0) + 1)  # the next trip's first mic's first run
+            L += oct_loads(nxt, 1) + [f"s_add_u32 s{S_PF_}, s{S_PF_}, {112 if par == 0 else 16}"]
+
+        def scan(P, s):  # run P.. on slot s: request the next run (its first pixel e) into the other slot, then sweep from P
+            Ls = []
+            for e in range(P + 1, 8):
+                Ls += [f"s_cmp_lg_u32 s{a(e)}, s{a(P)}", f"s_cbranch_scc1 .Lor{P}_{e}{s}{u}"]
+                cold.extend([f".Lor{P}_{e}{s}{u}:"] + reads(slot[other[s]], a(e)) + [f"s_branch .Loc{P}{s}{u}"])
+            return Ls
+
+        L += scan(0, "A")
+        for s in ("A", "X"):  # the chains: pixel q on slot s, then on to q + 1 on the same slot or, where the address steps, the other
+            for q in range(8):
+                L += [f".Loc{q}{s}{u}:"] + oterms(q, cur, m, slot[s])
+                if q < 7:
+                    L += [f"s_cmp_lg_u32 s{a(q + 1)}, s{a(q)}", f"s_cbranch_scc1 .Lot{q + 1}{s}{u}"]
+                    t = other[s]
+                    cold.extend([f".Lot{q + 1}{s}{u}:", "s_waitcnt lgkmcnt(0)"] + scan(q + 1, t) + [f"s_branch .Loc{q + 1}{t}{u}"])
+            if s == "A":
+                L.append(f"s_branch .Loend{u}")
+        L.append(f".Loend{u}:")
+        return L
+
+    def trip_oct(par):
+        L = []
+        for _ in range(16 // nw):
+            L += dma_piece()
+        if ND_PRIO == 3 or (ND_PRIO == 5 and par == 0):
+            L += select_prio(S_PRIO, 1, QUAD_XMAP)
+        else:
+            L += select_prio(S_RANK, 0, QUAD_YMAP)
+        return L + oct_mic(par, 0) + oct_mic(par, 1)
+
     def first_reads(base):
+        if octet:
+            return reads(R[0], of_(base, 0, 0) + 1)
         return reads(R[0], a_of(base, REF, 0)) + request_x(base, 0)
 
     def refill_params(first):
@@ -926,14 +1007,25 @@ def block_exact_nd(name, nq, nk=4, nw=16, refill=True):
     L += [f"s_mov_b32 s{S_M0}, m0", f"s_mov_b32 s{S_CH}, %[nch]", f"s_mov_b32 s{S_DELTA}, %[delta]",
           f"s_mov_b64 s[{S_SB}:{S_SB + 1}], %[isrc]", f"s_mov_b32 s{S_DST}, %[ddst]"]
     L += refill_params(first=True)
-    L += load_set(E[0], 0, literal=True)
-    L += chunk_groups() + [f"s_movk_i32 s{S_PF_}, 0x80"]
-    if nq > 1:
-        L += [f"s_mov_b32 s{S_PFO}, %[qstride]"]
-    L += ["s_waitcnt lgkmcnt(0)"] + first_reads(E[0])
+    if octet:
+        # set 0 = group 0's first two mics of all eight pixels; a group is two trips, out of set 0 then set 1, so a chunk always
+        # ends on set 1 and hands set 0 (the next chunk's first entries) to the boundary
+        L += [f"s_load_dwordx4 s[{E[0] + 4 * P}:{E[0] + 4 * P + 3}], %[ptr], {hex(32 * P)}" for P in range(4)]
+        L += [f"s_load_dwordx4 s[{E[0] + 4 * P}:{E[0] + 4 * P + 3}], %[ptr], %[qstride] offset:{hex(32 * (P - 4))}" for P in range(4, 8)]
+        L += chunk_groups() + [f"s_movk_i32 s{S_PF_}, 0x10"]
+        L += ["s_waitcnt lgkmcnt(0)"] + first_reads(E[0])
+        L += [".LN0_0_%=:"] + trip_oct(0) + trip_oct(1)
+        L += [f"s_sub_u32 s{S_LEFT_}, s{S_LEFT_}, 1", f"s_cmp_lg_u32 s{S_LEFT_}, 0", "s_cbranch_scc1 .LN0_0_%="]
+        L += boundary(E[0], ".LN0_0_%=")
+    else:
+        L += load_set(E[0], 0, literal=True)
+        L += chunk_groups() + [f"s_movk_i32 s{S_PF_}, 0x80"]
+        if nq > 1:
+            L += [f"s_mov_b32 s{S_PFO}, %[qstride]"]
+        L += ["s_waitcnt lgkmcnt(0)"] + first_reads(E[0])
     # quad q's trips: .LNq_0 runs out of set 0, .LNq_1 out of set 1; a quad's chunk that ends on a trip out of set s hands set 1 - s
     # (already loaded: the next quad's, or -- after the last quad -- the first quad's entries of the next chunk) to what follows
-    for q in range(nq):
+    for q in range(0 if octet else nq):
         qz[0] = q
         last = q == nq - 1
         after0 = f".LNhand{q}_%=" if not last else ".LNbndA_%="
@@ -2192,7 +2284,7 @@ def main():
     out.append(block_exact_shared("sweep_duo_exact", 128 - 57 - 3))  # das_exact_pair_kernel (AWPU_MATH_F32_EXACT)
     out.append(block_exact_quad("sweep_quad_exact"))  # das_exact_quad_kernel (AWPU_MATH_F32_EXACT, row length known; round 4)
     out.append(block_exact_nd("sweep_exact_nd_item1", 1))  # das_exact_nd_kernel<1>: the {next, d} layout, one quad per wave
-    out.append(block_exact_nd("sweep_exact_nd_item2", 2))  # das_exact_nd_kernel<2>: two quads per wave (the default batch kernel of the reference order)
+    out.append(block_exact_nd("sweep_exact_nd_item2", 2, octet=True))  # das_exact_nd_kernel<2>: an octet per wave (the default batch kernel of the reference order)
     out.append(block_exact_nd("sweep_exact_ndh_item1", 1, nk=2))  # das_exact_ndh_kernel<1, *>: single frames, the halves form of the layout
     out.append(block_exact_nd("sweep_exact_ndh_item2", 2, nk=2))  # das_exact_ndh_kernel<2, *>
     out.append(block_exact_nd("sweep_exact_ndh_resident1", 1, nk=2, refill=False))  # das_exact_ndh_kernel<1, true>: every mic resident, nothing to refill
