@@ -167,6 +167,14 @@ _TRACK_SIGNATURES = {
 }
 TRACK_SYMBOLS = tuple(_TRACK_SIGNATURES)
 
+# runs of consecutive blocks: the entry points of include/awpu_hip_blocks.h
+_BLOCK_SIGNATURES = {
+    "awpu_hip_process_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, _f32p]),
+    "awpu_hip_process_samples": (C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int32, _f32p]),
+    "awpu_hip_process_samples_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+}
+BLOCK_SYMBOLS = tuple(_BLOCK_SIGNATURES)
+
 # numpy view of awpu_particle_t: what Engine.track returns, one record per particle
 PARTICLE_DTYPE = np.dtype([("theta", "<f8"), ("phi", "<f8"), ("spread", "<f8"), ("rate", "<f8"), ("steps", "<i4"),
                            ("error", "<f4"), ("grad_theta", "<f8"), ("grad_phi", "<f8"), ("radius", "<f8"),
@@ -194,7 +202,7 @@ def load(build: bool = True) -> C.CDLL:
     if not path.exists():
         raise RuntimeError(f"{path} is missing and there is no CPU fallback")
     lib = C.CDLL(str(path))
-    for name, (res, args) in list(_SIGNATURES.items()) + list(_TRACK_SIGNATURES.items()):
+    for name, (res, args) in list(_SIGNATURES.items()) + list(_TRACK_SIGNATURES.items()) + list(_BLOCK_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -416,6 +424,37 @@ class Engine:
         frames = np.empty((self.cfg.n_streams, HIST), np.float32)
         _check(self._lib.awpu_hip_ring_snapshot(self._h, _f32(frames)), "ring_snapshot")
         return frames
+
+    def process_blocks(self, wire, stride: int = DATAGRAM_BYTES) -> np.ndarray:
+        """A run of consecutive blocks of wire datagrams (bytes-like, n_blocks x 256 datagrams `stride` bytes apart) ->
+        power [n_blocks, pixels]: row k = process_ring() after k + 1 ingest_block() calls, and the ring is left there
+        (awpu_hip_process_blocks)."""
+        buf = np.frombuffer(wire, dtype=np.uint8)
+        if stride < DATAGRAM_BYTES or buf.size % (256 * stride) or buf.size == 0:
+            raise ValueError(f"wire must be a whole number of blocks of 256 datagrams {stride} bytes apart")
+        n_blocks = buf.size // (256 * stride)
+        power = np.empty((n_blocks, self.pixel_count), np.float32)
+        _check(self._lib.awpu_hip_process_blocks(self._h, buf.ctypes.data_as(C.c_void_p), stride, n_blocks, _f32(power)),
+               "awpu_hip_process_blocks")
+        return power
+
+    def process_samples(self, samples: np.ndarray) -> np.ndarray:
+        """The same from unpacked samples [n_streams, N] (N a multiple of 256, oldest first) -> power [N // 256, pixels]
+        (awpu_hip_process_samples)."""
+        samples = np.ascontiguousarray(samples, np.float32)
+        if samples.ndim != 2 or samples.shape[0] != self.cfg.n_streams or samples.shape[1] % 256 or samples.shape[1] == 0:
+            raise ValueError(f"samples must be [{self.cfg.n_streams}, N] with N a positive multiple of 256")
+        n_blocks = samples.shape[1] // 256
+        power = np.empty((n_blocks, self.pixel_count), np.float32)
+        _check(self._lib.awpu_hip_process_samples(self._h, _f32(samples), samples.shape[1], n_blocks, _f32(power)),
+               "awpu_hip_process_samples")
+        return power
+
+    def process_samples_device(self, d_samples_ptr: int, pitch: int, n_blocks: int, d_power_ptr: int, stream: int = 0) -> None:
+        """The same on device pointers (samples [n_streams, pitch], power [n_blocks, pixels]) on `stream`; asynchronous."""
+        _check(self._lib.awpu_hip_process_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks,
+                                                         C.c_void_p(d_power_ptr), C.c_void_p(stream)),
+               "awpu_hip_process_samples_device")
 
     def set_fir_table(self, coeffs: np.ndarray) -> None:
         """The caller's [101, 8] coefficient table of the FIR variant (src/dsp/filter.h:10-112)."""

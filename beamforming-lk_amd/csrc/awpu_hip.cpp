@@ -2,6 +2,7 @@
 // packing, frame upload, kernel dispatch.  No CPU fallback: every compute entry point ends
 // in a gfx950 kernel launch or an error status.
 #include "awpu_hip.h"
+#include "awpu_hip_blocks.h"
 #include "awpu_hip_track.h"
 
 #include <hip/hip_runtime.h>
@@ -16,8 +17,10 @@
 #include <string>
 #include <array>
 #include <map>
+#include <thread>
 #include <vector>
 
+#include "block_kernels.h"
 #include "das_kernels.h"
 
 namespace {
@@ -204,6 +207,19 @@ struct awpu_hip {
     bool stage_used[2] = {false, false};
     bool tile_used[2] = {false, false}, fan_used[2] = {false, false};
     bool in_flight = false;                 // awpu_hip_process_async without its awpu_hip_wait yet
+    // runs of blocks (awpu_hip_blocks.h), by sweep piece: piece i's history [n_streams][768 + 256 * piece] in d_blk_hist[i & 1], its
+    // windows in d_blk_frames; the host forms stage piece i's input in pinned h_blk_in[i & 1], upload it to d_blk_in[i & 1] on
+    // copy_stream and bring its powers back through pinned h_blk_out[i & 1]
+    float *d_blk_hist[2] = {nullptr, nullptr};
+    float *d_blk_frames = nullptr;
+    void *h_blk_in[2] = {nullptr, nullptr}, *d_blk_in[2] = {nullptr, nullptr};
+    float *h_blk_out[2] = {nullptr, nullptr};
+    size_t blk_hist_cap = 0, blk_frames_cap = 0, blk_in_cap = 0, blk_out_cap = 0;  // floats, floats, bytes, floats (per buffer)
+    // ev_blk_in[b]: h_blk_in[b] may be refilled; ev_blk_hist[b]: d_blk_hist[b] formed; ev_blk_cut[b]: ... and read by the cut;
+    // ev_blk_swept[b]: d_power's half b holds its piece's powers; ev_blk_out[b]: ... and h_blk_out[b] too; ev_blk_ring: orders a
+    // run after the work queued on the handle's stream, and the handle's stream after a device-form run on the caller's stream
+    hipEvent_t ev_blk_in[2] = {nullptr, nullptr}, ev_blk_hist[2] = {nullptr, nullptr}, ev_blk_cut[2] = {nullptr, nullptr},
+               ev_blk_swept[2] = {nullptr, nullptr}, ev_blk_out[2] = {nullptr, nullptr}, ev_blk_ring = nullptr;
 
     awpu_hip_stats stats{};
     std::string last_error;                  // awpu_hip_last_error_of
@@ -380,6 +396,16 @@ void release_device(awpu_hip *h) {
     dev_free(h->d_fan[0]);
     dev_free(h->d_fan[1]);
     h->fan_cap = 0;
+    for (int b = 0; b < 2; b++) {
+        dev_free(h->d_blk_hist[b]);
+        dev_free(h->d_blk_in[b]);
+        if (h->h_blk_in[b]) (void) hipHostFree(h->h_blk_in[b]);
+        if (h->h_blk_out[b]) (void) hipHostFree(h->h_blk_out[b]);
+        h->h_blk_in[b] = nullptr;
+        h->h_blk_out[b] = nullptr;
+    }
+    dev_free(h->d_blk_frames);
+    h->blk_hist_cap = h->blk_frames_cap = h->blk_in_cap = h->blk_out_cap = 0;
     for (int b = 0; b < 2; b++) {
         if (b == 0) {
             if (h->h_live_in) (void) hipHostFree(h->h_live_in);
@@ -1720,6 +1746,13 @@ struct TimingOff {
 };
 
 
+// frames per sweep launch of a host batch: large batches go up in pieces of whole frame pairs, so that piece k+1 crosses PCIe
+// while piece k is swept (enqueue_host_process; a run of blocks sweeps its chunks the same way)
+int host_piece(int batch) {
+    const int n_pieces = batch >= 128 ? 4 : (batch >= 64 ? 2 : 1);
+    return ((batch + n_pieces - 1) / n_pieces + 1) & ~1;
+}
+
 // upload of host frames + the sweep into h->d_power, all on h->stream, nothing waited for
 int enqueue_host_process(awpu_hip *h, const float *frames, int batch) {
     int rc = check_ready(h, batch);
@@ -1737,8 +1770,8 @@ int enqueue_host_process(awpu_hip *h, const float *frames, int batch) {
     if (rc != AWPU_OK) return rc;
     // Large batches go up in pieces on a second stream, so that piece k+1 crosses PCIe while piece k is swept (the
     // pieces are whole frame pairs: the same arithmetic as one launch).  last_kernel_ms then spans all the sweeps.
-    const int n_pieces = batch >= 128 ? 4 : (batch >= 64 ? 2 : 1);
-    const int piece = ((batch + n_pieces - 1) / n_pieces + 1) & ~1;
+    const int piece = host_piece(batch);
+    const int n_pieces = (batch + piece - 1) / piece;
     if (n_pieces > 1) {
         if (!h->copy_stream) AWPU_HIP_TRY(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
         for (hipEvent_t *ev : {&h->ev_copied[0], &h->ev_copied[1]})
@@ -2359,7 +2392,9 @@ int awpu_hip_destroy(awpu_hip_t *h) {
     if (h->copy_stream) (void) hipStreamSynchronize(h->copy_stream);
     release_device(h);
     for (hipEvent_t ev : {h->ev_begin, h->ev_end, h->ev_fan, h->ev_copied[0], h->ev_copied[1], h->ev_swept[0], h->ev_swept[1], h->ev_done,
-                          h->ev_staged[0], h->ev_staged[1], h->ev_tile_free[0], h->ev_tile_free[1], h->ev_staged_read[0], h->ev_staged_read[1]})
+                          h->ev_staged[0], h->ev_staged[1], h->ev_tile_free[0], h->ev_tile_free[1], h->ev_staged_read[0], h->ev_staged_read[1],
+                          h->ev_blk_in[0], h->ev_blk_in[1], h->ev_blk_hist[0], h->ev_blk_hist[1], h->ev_blk_cut[0], h->ev_blk_cut[1],
+                          h->ev_blk_swept[0], h->ev_blk_swept[1], h->ev_blk_out[0], h->ev_blk_out[1], h->ev_blk_ring})
         if (ev) (void) hipEventDestroy(ev);
     if (h->stream) (void) hipStreamDestroy(h->stream);
     if (h->copy_stream) (void) hipStreamDestroy(h->copy_stream);
@@ -2826,19 +2861,25 @@ int awpu_hip_process_device_sums(awpu_hip_t *h, const float *d_frames, int32_t b
 
 namespace {
 
+// the ingest ring and its one-block staging, allocated at first use: the ring starts zeroed (on h->stream)
+int ensure_ring(awpu_hip *h) {
+    if (h->d_ring) return AWPU_OK;
+    const size_t ring_bytes = (size_t) h->cfg.n_streams * 2048 * sizeof(float);
+    AWPU_HIP_TRY(hipMalloc(&h->d_ring, ring_bytes));
+    AWPU_HIP_TRY(hipMemsetAsync(h->d_ring, 0, ring_bytes, h->stream));
+    AWPU_HIP_TRY(hipMalloc(&h->d_datagrams, (size_t) awpu::kSamples * AWPU_DATAGRAM_BYTES));
+    h->ring_pos = 0;
+    return AWPU_OK;
+}
+
 // H2D of one block of raw datagrams + the unpack launch, enqueued on the handle's stream (no wait)
 int enqueue_ingest(awpu_hip *h, const void *datagrams, int32_t stride_bytes) {
     if (!h || !datagrams) return invalid("null argument");
     if (h->cfg.hist != AWPU_HIST || h->cfg.n_streams > 256) return invalid("ingest needs hist 1024 and <= 256 streams");
     if (stride_bytes < AWPU_DATAGRAM_BYTES) return invalid("datagram stride below 1032 bytes");
     AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
-    const size_t ring_bytes = (size_t) h->cfg.n_streams * 2048 * sizeof(float);
-    if (!h->d_ring) {
-        AWPU_HIP_TRY(hipMalloc(&h->d_ring, ring_bytes));
-        AWPU_HIP_TRY(hipMemsetAsync(h->d_ring, 0, ring_bytes, h->stream));
-        AWPU_HIP_TRY(hipMalloc(&h->d_datagrams, (size_t) awpu::kSamples * AWPU_DATAGRAM_BYTES));
-        h->ring_pos = 0;
-    }
+    const int rc = ensure_ring(h);
+    if (rc != AWPU_OK) return rc;
     // tight copy of the 256 datagrams (the header travels too: 8 bytes each, ignored like the
     // reference ignores msg.counter, pipeline.cpp:264-267)
     AWPU_HIP_TRY(hipMemcpy2DAsync(h->d_datagrams, AWPU_DATAGRAM_BYTES, datagrams, (size_t) stride_bytes,
@@ -3050,6 +3091,281 @@ int awpu_hip_ring_snapshot(awpu_hip_t *h, float *frames) {
                                   AWPU_HIST * sizeof(float), h->cfg.n_streams, hipMemcpyDeviceToHost, h->stream));
     AWPU_HIP_TRY(hipStreamSynchronize(h->stream));
     return AWPU_OK;
+}
+
+// ---- runs of consecutive blocks (include/awpu_hip_blocks.h) ---------------------------------------------------------------
+// A run is cut into chunks of at most max_batch blocks, and every chunk into the pieces awpu_hip_process sweeps a batch of that
+// size in (host_piece): the same launches as that call on the same snapshots, so the same bits.  Piece i gets a history
+// [n_streams][768 + 256 * piece] on the device: the 768 samples before it (the ring's snapshot for the first piece, the tail
+// of piece i-1's history after it), then its new samples.  Its snapshots' windows are cut into the layout awpu_hip_process
+// uploads (kCompact; kFull without a compact window) and swept by launch().  The host forms stage piece i + 1 in pinned memory,
+// upload it and form its history on copy_stream while piece i is cut and swept on the handle's stream; the powers of piece i
+// come back through pinned memory on copy_stream while piece i + 1 is swept.  (Pieces rather than whole chunks: the first
+// piece's staging is the one nothing hides, and the buffers are a piece long.)
+namespace {
+
+struct BlockRun {
+    const unsigned char *wire = nullptr;  // datagrams, `stride` bytes apart (host)
+    int32_t stride = 0;
+    const float *samples = nullptr;       // [n_streams][pitch] floats, host or (device) device memory
+    int64_t pitch = 0;
+    bool device = false;
+};
+
+// device buffers for pieces of at most `piece` frames (and, for the host forms, the pinned staging and the second stream)
+int ensure_blk_buffers(awpu_hip *h, const BlockRun &src, int piece, int width) {
+    const size_t S = (size_t) h->cfg.n_streams;
+    const size_t hist_floats = S * (awpu::kBlockPrefix + (size_t) awpu::kSamples * piece);
+    if (h->blk_hist_cap < hist_floats) {
+        for (int b = 0; b < 2; b++) dev_free(h->d_blk_hist[b]);
+        h->blk_hist_cap = 0;
+        for (int b = 0; b < 2; b++) AWPU_HIP_TRY(hipMalloc(&h->d_blk_hist[b], hist_floats * sizeof(float)));
+        h->blk_hist_cap = hist_floats;
+    }
+    const size_t frames_floats = S * width * (size_t) piece;
+    if (h->blk_frames_cap < frames_floats) {
+        dev_free(h->d_blk_frames);
+        h->blk_frames_cap = 0;
+        AWPU_HIP_TRY(hipMalloc(&h->d_blk_frames, frames_floats * sizeof(float)));
+        h->blk_frames_cap = frames_floats;
+    }
+    if (!h->ev_blk_ring) AWPU_HIP_TRY(hipEventCreateWithFlags(&h->ev_blk_ring, hipEventDisableTiming));
+    if (src.device) return AWPU_OK;
+    const size_t in_bytes = (size_t) awpu::kSamples * piece * (src.wire ? (size_t) AWPU_DATAGRAM_BYTES : S * sizeof(float));
+    if (h->blk_in_cap < in_bytes) {
+        for (int b = 0; b < 2; b++) {
+            dev_free(h->d_blk_in[b]);
+            if (h->h_blk_in[b]) (void) hipHostFree(h->h_blk_in[b]);
+            h->h_blk_in[b] = nullptr;
+        }
+        h->blk_in_cap = 0;
+        for (int b = 0; b < 2; b++) {
+            AWPU_HIP_TRY(hipHostMalloc(&h->h_blk_in[b], in_bytes, hipHostMallocDefault));
+            AWPU_HIP_TRY(hipMalloc(&h->d_blk_in[b], in_bytes));
+        }
+        h->blk_in_cap = in_bytes;
+    }
+    const size_t out_floats = (size_t) piece * h->cfg.pixel_count;
+    if (h->blk_out_cap < out_floats) {
+        for (int b = 0; b < 2; b++) {
+            if (h->h_blk_out[b]) (void) hipHostFree(h->h_blk_out[b]);
+            h->h_blk_out[b] = nullptr;
+        }
+        h->blk_out_cap = 0;
+        for (int b = 0; b < 2; b++) AWPU_HIP_TRY(hipHostMalloc(&h->h_blk_out[b], out_floats * sizeof(float), hipHostMallocDefault));
+        h->blk_out_cap = out_floats;
+    }
+    if (!h->copy_stream) AWPU_HIP_TRY(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
+    for (hipEvent_t *ev : {&h->ev_blk_in[0], &h->ev_blk_in[1], &h->ev_blk_hist[0], &h->ev_blk_hist[1], &h->ev_blk_cut[0],
+                           &h->ev_blk_cut[1], &h->ev_blk_swept[0], &h->ev_blk_swept[1], &h->ev_blk_out[0], &h->ev_blk_out[1]})
+        if (!*ev) AWPU_HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+    return ensure_power(h, (size_t) 2 * piece * h->cfg.pixel_count);  // two pieces' powers: one swept, one on its way back
+}
+
+// blocks [g0, g0 + nb) of a host form into pinned staging h_blk_in[b]: tight datagrams, or rows of 256 * nb samples.  Pieces of
+// 1 MB and more are copied by up to 8 threads, each a contiguous share of the rows (the headline's 32-block pieces: 8.4 MB, 8
+// threads); where a thread cannot be started, the calling thread copies its share.
+void stage_blocks(awpu_hip *h, const BlockRun &src, int g0, int nb, int b) {
+    unsigned char *dst = static_cast<unsigned char *>(h->h_blk_in[b]);
+    const size_t n = (size_t) awpu::kSamples * nb;
+    const size_t rows = src.wire ? n : (size_t) h->cfg.n_streams;
+    const auto copy = [&](size_t r0, size_t r1) {
+        if (src.wire) {
+            const unsigned char *from = src.wire + (size_t) g0 * awpu::kSamples * src.stride;
+            if (src.stride == AWPU_DATAGRAM_BYTES) {
+                std::memcpy(dst + r0 * AWPU_DATAGRAM_BYTES, from + r0 * AWPU_DATAGRAM_BYTES, (r1 - r0) * AWPU_DATAGRAM_BYTES);
+            } else {
+                for (size_t i = r0; i < r1; i++) std::memcpy(dst + i * AWPU_DATAGRAM_BYTES, from + i * src.stride, AWPU_DATAGRAM_BYTES);
+            }
+            return;
+        }
+        for (size_t s = r0; s < r1; s++)
+            std::memcpy(dst + s * n * sizeof(float), src.samples + s * src.pitch + (size_t) g0 * awpu::kSamples, n * sizeof(float));
+    };
+    const size_t bytes = n * (src.wire ? (size_t) AWPU_DATAGRAM_BYTES : rows * sizeof(float));
+    const size_t n_threads = std::min<size_t>({8, rows, bytes >> 20});
+    if (n_threads < 2) {
+        copy(0, rows);
+        return;
+    }
+    std::vector<std::thread> pool;
+    size_t k = 1;
+    try {
+        pool.reserve(n_threads - 1);
+        for (; k < n_threads; k++) pool.emplace_back(copy, rows * k / n_threads, rows * (k + 1) / n_threads);
+    } catch (...) {  // (std::system_error must not cross the C ABI)
+    }
+    copy(0, rows / n_threads);
+    if (k < n_threads) copy(rows * k / n_threads, rows);
+    for (auto &th : pool) th.join();
+}
+
+// the run; host forms: `power` [n_blocks][pixel_count] host, synchronous; device form: `d_out` on `user` (NULL = h->stream)
+int run_blocks(awpu_hip *h, const BlockRun &src, int n_blocks, float *power, float *d_out, hipStream_t user) {
+    if (!h->parts.empty()) return fail(AWPU_ERR_STATE, "a device group does not take runs of blocks");
+    if (h->in_flight) return fail(AWPU_ERR_STATE, "an awpu_hip_process_async call is in flight on this handle: awpu_hip_wait first");
+    const awpu_hip_cfg &c = h->cfg;
+    if (c.hist != AWPU_HIST) return invalid("runs of blocks need hist 1024");
+    if (src.wire && c.n_streams > 256) return invalid("the wire carries at most 256 streams");
+    const int chunk = std::min<int>(n_blocks, c.max_batch);
+    int rc = check_ready(h, chunk);
+    if (rc != AWPU_OK) return rc;
+    std::vector<std::pair<int, int>> pieces;  // (first block, blocks): every chunk in awpu_hip_process's pieces
+    int piece_max = 1;
+    for (int c0 = 0; c0 < n_blocks; c0 += chunk) {
+        const int nc = std::min(chunk, n_blocks - c0), piece = host_piece(nc);
+        for (int k0 = 0; k0 < nc; k0 += piece) {
+            pieces.emplace_back(c0 + k0, std::min(piece, nc - k0));
+            piece_max = std::max(piece_max, pieces.back().second);
+        }
+    }
+    const bool compact = h->compact_hist > 0;
+    const int width = compact ? h->compact_hist : AWPU_HIST, lo = compact ? h->wstart : 0;
+    rc = ensure_ring(h);
+    if (rc == AWPU_OK) rc = ensure_blk_buffers(h, src, piece_max, width);
+    if (rc != AWPU_OK) return rc;
+    const int S = c.n_streams, pitch = awpu::kBlockPrefix + awpu::kSamples * piece_max;
+    const size_t P = (size_t) c.pixel_count;
+    const bool host = !src.device;
+    hipStream_t sw = host ? h->stream : (user ? user : h->stream);  // cut and sweep
+    hipStream_t up = host ? h->copy_stream : sw;                    // upload and history
+    const bool keep_timing = h->timing;
+    if (!host) h->timing = false;  // asynchronous: the caller times its own stream
+    const int n_pieces = (int) pieces.size();
+    // host forms: piece j's powers, in h_blk_out[j & 1] once ev_blk_out[j & 1] has passed, to the caller's rows
+    const auto deliver = [&](int j) -> int {
+        AWPU_HIP_TRY(hipEventSynchronize(h->ev_blk_out[j & 1]));
+        std::memcpy(power + (size_t) pieces[j].first * P, h->h_blk_out[j & 1], (size_t) pieces[j].second * P * sizeof(float));
+        return AWPU_OK;
+    };
+    const auto body = [&]() -> int {
+        // whatever is queued on the handle's stream -- the ring's zeroing, the ring writes and cuts of a device-form run not yet
+        // over -- comes first: the upload side reads the ring and rewrites the histories
+        if (up != h->stream) {
+            AWPU_HIP_TRY(hipEventRecord(h->ev_blk_ring, h->stream));
+            AWPU_HIP_TRY(hipStreamWaitEvent(up, h->ev_blk_ring, 0));
+        }
+        const float *prev = h->d_ring + h->ring_pos + awpu::kSamples;  // the last 768 samples of the current snapshot
+        long long prev_pitch = 2048;
+        for (int i = 0; i < n_pieces; i++) {
+            const int b = i & 1, g0 = pieces[i].first, nb = pieces[i].second;
+            float *hist = h->d_blk_hist[b];
+            if (host) {
+                if (i >= 2) AWPU_HIP_TRY(hipEventSynchronize(h->ev_blk_in[b]));  // piece i-2's upload out of h_blk_in[b] is over
+                stage_blocks(h, src, g0, nb, b);
+                const size_t bytes = (size_t) awpu::kSamples * nb * (src.wire ? (size_t) AWPU_DATAGRAM_BYTES : S * sizeof(float));
+                AWPU_HIP_TRY(hipMemcpyAsync(h->d_blk_in[b], h->h_blk_in[b], bytes, hipMemcpyHostToDevice, up));
+                AWPU_HIP_TRY(hipEventRecord(h->ev_blk_in[b], up));
+                if (i >= 2) AWPU_HIP_TRY(hipStreamWaitEvent(up, h->ev_blk_cut[b], 0));  // piece i-2's windows are cut out of d_blk_hist[b]
+            }
+            AWPU_HIP_TRY(awpu::launch_copy_rows(prev, prev_pitch, hist, pitch, awpu::kBlockPrefix, S, up));
+            if (src.wire) {
+                AWPU_HIP_TRY(awpu::launch_unpack_blocks(h->d_blk_in[b], nb, S, hist, pitch, awpu::kBlockPrefix, up));
+            } else {
+                const float *rows = host ? static_cast<const float *>(h->d_blk_in[b]) : src.samples + (size_t) g0 * awpu::kSamples;
+                AWPU_HIP_TRY(awpu::launch_copy_rows(rows, host ? (long long) awpu::kSamples * nb : (long long) src.pitch,
+                                                    hist + awpu::kBlockPrefix, pitch, awpu::kSamples * nb, S, up));
+            }
+            if (host) {
+                AWPU_HIP_TRY(hipEventRecord(h->ev_blk_hist[b], up));
+                AWPU_HIP_TRY(hipStreamWaitEvent(sw, h->ev_blk_hist[b], 0));
+            }
+            AWPU_HIP_TRY(awpu::launch_cut_windows(hist, pitch, S, nb, lo, width, h->d_blk_frames, sw));
+            if (host) AWPU_HIP_TRY(hipEventRecord(h->ev_blk_cut[b], sw));
+            if (host && keep_timing && i == 0) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, sw));
+            h->timing = false;
+            rc = launch(h, h->d_blk_frames, nb, host ? h->d_power + (size_t) b * piece_max * P : d_out + (size_t) g0 * P, sw,
+                        compact ? kCompact : kFull);
+            h->timing = keep_timing && host;
+            if (rc != AWPU_OK) return rc;
+            if (host) {
+                AWPU_HIP_TRY(hipEventRecord(h->ev_blk_swept[b], sw));
+                if (i >= 1) {  // piece i-1's powers go back into pinned memory behind its sweep, while piece i is swept ...
+                    AWPU_HIP_TRY(hipStreamWaitEvent(up, h->ev_blk_swept[b ^ 1], 0));
+                    AWPU_HIP_TRY(hipMemcpyAsync(h->h_blk_out[b ^ 1], h->d_power + (size_t) (b ^ 1) * piece_max * P,
+                                                (size_t) pieces[i - 1].second * P * sizeof(float), hipMemcpyDeviceToHost, up));
+                    AWPU_HIP_TRY(hipEventRecord(h->ev_blk_out[b ^ 1], up));
+                }
+                if (i >= 2) {  // ... and piece i-2's, long back, go to the caller before h_blk_out[b] is written again
+                    rc = deliver(i - 2);
+                    if (rc != AWPU_OK) return rc;
+                }
+            }
+            prev = hist + (size_t) awpu::kSamples * nb;
+            prev_pitch = pitch;
+        }
+        const int last_b = (n_pieces - 1) & 1, last_nb = pieces.back().second;
+        if (host && keep_timing) AWPU_HIP_TRY(hipEventRecord(h->ev_end, sw));
+        // the ring as n_blocks ingests leave it: its snapshot = the last 1024 samples of the last history
+        const int pos = (int) ((h->ring_pos + (long long) awpu::kSamples * n_blocks) % AWPU_HIST);
+        AWPU_HIP_TRY(awpu::launch_ring_write(h->d_blk_hist[last_b], pitch, awpu::kSamples * (last_nb - 1), S, h->d_ring, pos, sw));
+        h->ring_pos = pos;
+        if (!host) {
+            if (sw != h->stream) {  // later calls on the ring (the handle's stream) come after this one
+                AWPU_HIP_TRY(hipEventRecord(h->ev_blk_ring, sw));
+                AWPU_HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_blk_ring, 0));
+            }
+            return AWPU_OK;
+        }
+        AWPU_HIP_TRY(hipStreamWaitEvent(up, h->ev_blk_swept[last_b], 0));
+        AWPU_HIP_TRY(hipMemcpyAsync(h->h_blk_out[last_b], h->d_power + (size_t) last_b * piece_max * P, (size_t) last_nb * P * sizeof(float),
+                                    hipMemcpyDeviceToHost, up));
+        AWPU_HIP_TRY(hipEventRecord(h->ev_blk_out[last_b], up));
+        for (int j = std::max(0, n_pieces - 2); j < n_pieces; j++) {
+            rc = deliver(j);
+            if (rc != AWPU_OK) return rc;
+        }
+        AWPU_HIP_TRY(hipStreamSynchronize(up));
+        return wait_and_time(h);
+    };
+    rc = body();
+    h->timing = keep_timing;
+    if (rc != AWPU_OK && host) {  // nothing of the call may still read the caller's or the handle's buffers
+        (void) hipStreamSynchronize(h->copy_stream);
+        (void) hipStreamSynchronize(h->stream);
+    }
+    return rc;
+}
+
+}  // namespace
+
+int awpu_hip_process_blocks(awpu_hip_t *h, const void *datagrams, int32_t stride_bytes, int32_t n_blocks, float *power) {
+    // (arguments first: none of these reads the handle)
+    if (!h) return invalid("null handle");
+    if (!datagrams || !power) return invalid("null argument");
+    if (n_blocks < 1) return invalid("n_blocks below 1");
+    if (stride_bytes < AWPU_DATAGRAM_BYTES) return invalid("datagram stride below 1032 bytes");
+    AWPU_CTX(h);
+    BlockRun src;
+    src.wire = static_cast<const unsigned char *>(datagrams);
+    src.stride = stride_bytes;
+    return run_blocks(h, src, n_blocks, power, nullptr, nullptr);
+}
+
+int awpu_hip_process_samples(awpu_hip_t *h, const float *samples, int64_t pitch, int32_t n_blocks, float *power) {
+    if (!h) return invalid("null handle");
+    if (!samples || !power) return invalid("null argument");
+    if (n_blocks < 1) return invalid("n_blocks below 1");
+    if (pitch < (int64_t) awpu::kSamples * n_blocks) return invalid("pitch below 256 * n_blocks");
+    AWPU_CTX(h);
+    BlockRun src;
+    src.samples = samples;
+    src.pitch = pitch;
+    return run_blocks(h, src, n_blocks, power, nullptr, nullptr);
+}
+
+int awpu_hip_process_samples_device(awpu_hip_t *h, const float *d_samples, int64_t pitch, int32_t n_blocks, float *d_power,
+                                    void *stream) {
+    if (!h) return invalid("null handle");
+    if (!d_samples || !d_power) return invalid("null argument");
+    if (n_blocks < 1) return invalid("n_blocks below 1");
+    if (pitch < (int64_t) awpu::kSamples * n_blocks) return invalid("pitch below 256 * n_blocks");
+    AWPU_CTX(h);
+    BlockRun src;
+    src.samples = d_samples;
+    src.pitch = pitch;
+    src.device = true;
+    return run_blocks(h, src, n_blocks, nullptr, d_power, static_cast<hipStream_t>(stream));
 }
 
 int awpu_hip_heatmap_u8_device(awpu_hip_t *h, const float *d_power, int32_t n, int32_t batch, float *d_peak,
