@@ -21,7 +21,7 @@ OPENCV_CFLAGS ?= -Itests/host/mock_opencv
 lib: $(LIB)
 
 $(LIB): $(KERNEL_SRC) $(CSRC)/das_kernels.h $(CSRC)/block_kernels.h $(CSRC)/das_fast_trip.inc include/awpu_hip.h include/awpu_hip_track.h \
-        include/awpu_hip_blocks.h
+        include/awpu_hip_blocks.h include/awpu_hip_listen.h
 	$(HIPCC) --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -Wall -Wno-unused-result -Werror=inline-asm -x hip \
 	    -Iinclude -I$(CSRC) $(KERNEL_SRC) -o $@
 

@@ -23,7 +23,7 @@ SOURCES = [CSRC / "das_kernels.hip", CSRC / "das_fast.hip", CSRC / "track_kernel
 GENERATOR = REPO / "tools" / "gen_trip_asm.py"
 TRIP_INC = CSRC / "das_fast_trip.inc"
 HEADERS = [CSRC / "das_kernels.h", CSRC / "block_kernels.h", GENERATOR, REPO / "include" / "awpu_hip.h", REPO / "include" / "awpu_hip_track.h",
-           REPO / "include" / "awpu_hip_blocks.h"]
+           REPO / "include" / "awpu_hip_blocks.h", REPO / "include" / "awpu_hip_listen.h"]
 
 
 def hipcc_path() -> str:

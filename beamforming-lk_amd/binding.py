@@ -175,6 +175,16 @@ _BLOCK_SIGNATURES = {
 }
 BLOCK_SYMBOLS = tuple(_BLOCK_SIGNATURES)
 
+# listening to such runs: the entry points of include/awpu_hip_listen.h
+_LISTEN_TAIL = [C.c_int32, C.POINTER(Particle), C.c_int32, C.c_double, C.c_double]  # n_blocks, listeners, n, theta_limit, reference
+_LISTEN_SIGNATURES = {
+    "awpu_hip_listen_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, *_LISTEN_TAIL, _f32p, C.c_int64, C.POINTER(Particle), _f32p]),
+    "awpu_hip_listen_samples": (C.c_int, [C.c_void_p, _f32p, C.c_int64, *_LISTEN_TAIL, _f32p, C.c_int64, C.POINTER(Particle), _f32p]),
+    "awpu_hip_listen_samples_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, *_LISTEN_TAIL, C.c_void_p, C.c_int64, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]),
+}
+LISTEN_SYMBOLS = tuple(_LISTEN_SIGNATURES)
+
 # numpy view of awpu_particle_t: what Engine.track returns, one record per particle
 PARTICLE_DTYPE = np.dtype([("theta", "<f8"), ("phi", "<f8"), ("spread", "<f8"), ("rate", "<f8"), ("steps", "<i4"),
                            ("error", "<f4"), ("grad_theta", "<f8"), ("grad_phi", "<f8"), ("radius", "<f8"),
@@ -202,7 +212,8 @@ def load(build: bool = True) -> C.CDLL:
     if not path.exists():
         raise RuntimeError(f"{path} is missing and there is no CPU fallback")
     lib = C.CDLL(str(path))
-    for name, (res, args) in list(_SIGNATURES.items()) + list(_TRACK_SIGNATURES.items()) + list(_BLOCK_SIGNATURES.items()):
+    for name, (res, args) in list(_SIGNATURES.items()) + list(_TRACK_SIGNATURES.items()) + list(_BLOCK_SIGNATURES.items()) + \
+            list(_LISTEN_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -339,6 +350,42 @@ class TrackResult:
         return self.particles.size
 
 
+class ListenResult:
+    """What Engine.listen_* hand back: .audio [n, 256 * n_blocks] (a row = a listener's channel at 48 828 Hz), .listeners
+    (PARTICLE_DTYPE records after the run: pass them as `theta` to the next call to carry the trackers on), .trail
+    [n_blocks, n] records or None, .power [n_blocks, pixels] or None; .theta, .phi, ... are the listeners' fields."""
+
+    def __init__(self, audio, listeners: np.ndarray, trail, power):
+        self.audio = audio
+        self.listeners = listeners
+        self.trail = trail
+        self.power = power
+
+    def __getattr__(self, name):
+        if name in PARTICLE_DTYPE.names:
+            return self.listeners[name]
+        raise AttributeError(name)
+
+    def __len__(self):
+        return self.listeners.size
+
+
+def _particles(theta, phi, spread, rate, steps, where: str) -> np.ndarray:
+    """PARTICLE_DTYPE records from per-particle values (scalars broadcast), or a copy of such records passed as `theta`."""
+    if isinstance(theta, np.ndarray) and theta.dtype == PARTICLE_DTYPE:
+        return np.ascontiguousarray(theta).reshape(-1).copy()
+    theta = np.atleast_1d(np.asarray(theta, np.float64))
+    n = max(theta.size, np.size(phi), np.size(spread), np.size(rate), np.size(steps))
+    parts = np.zeros(n, PARTICLE_DTYPE)
+    parts["theta"], parts["phi"] = np.broadcast_to(theta, n), np.broadcast_to(np.asarray(phi, np.float64), n)
+    parts["spread"], parts["rate"] = np.broadcast_to(np.asarray(spread, np.float64), n), np.broadcast_to(np.asarray(rate, np.float64), n)
+    steps = np.broadcast_to(np.asarray(steps, np.int64), n)
+    if steps.size and (steps.min() < 0 or steps.max() > 4096):  # (before the int32 field could wrap it into range)
+        raise AwpuError(ERR_INVALID, where, "steps outside [0, 4096]")
+    parts["steps"] = steps
+    return parts
+
+
 class Engine:
     """One awpu_hip handle = one MIMO worker's sweep state on one GPU (src/dsp/mimo.h:74-91)."""
 
@@ -455,6 +502,55 @@ class Engine:
         _check(self._lib.awpu_hip_process_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks,
                                                          C.c_void_p(d_power_ptr), C.c_void_p(stream)),
                "awpu_hip_process_samples_device")
+
+    def _listen(self, call, where, n_blocks, particles, theta_limit, reference, want_trail, want_power) -> ListenResult:
+        parts = _particles(*particles, where)
+        n = parts.size
+        audio = np.empty((n, 256 * n_blocks), np.float32)
+        trail = np.zeros((n_blocks, n), PARTICLE_DTYPE) if want_trail else None
+        power = np.empty((n_blocks, self.pixel_count), np.float32) if want_power else None
+        pp = C.POINTER(Particle)
+        _check(call(n_blocks, parts.ctypes.data_as(pp), n, float(theta_limit), -1.0 if reference is None else float(reference),
+                    _f32(audio), audio.shape[1], trail.ctypes.data_as(pp) if want_trail else None, _f32(power) if want_power else None),
+               where)
+        return ListenResult(audio, parts, trail, power)
+
+    def listen_blocks(self, wire, theta, phi, spread, rate, steps, theta_limit: float, reference: Optional[float] = None,
+                      stride: int = DATAGRAM_BYTES, want_trail: bool = True, want_power: bool = False) -> ListenResult:
+        """Listen to a run of consecutive blocks of wire datagrams (as process_blocks takes them): per block, listener l takes
+        steps[l] gradient steps (0 = a fixed, steered listener) and its delayed-and-summed signal at where it then points is
+        256 samples of its audio row; the ring is left where the run ends (awpu_hip_listen_blocks).  theta/phi/spread/rate/steps
+        are per listener (scalars broadcast), or `theta` is the .listeners of an earlier result (the rest then None);
+        reference None = from each block's own snapshot, as MISOWorker does.  -> ListenResult."""
+        buf = np.frombuffer(wire, dtype=np.uint8)
+        if stride < DATAGRAM_BYTES or buf.size % (256 * stride) or buf.size == 0:
+            raise ValueError(f"wire must be a whole number of blocks of 256 datagrams {stride} bytes apart")
+        return self._listen(lambda *rest: self._lib.awpu_hip_listen_blocks(self._h, buf.ctypes.data_as(C.c_void_p), stride, *rest),
+                            "awpu_hip_listen_blocks", buf.size // (256 * stride), (theta, phi, spread, rate, steps), theta_limit,
+                            reference, want_trail, want_power)
+
+    def listen_samples(self, samples: np.ndarray, theta, phi, spread, rate, steps, theta_limit: float,
+                       reference: Optional[float] = None, want_trail: bool = True, want_power: bool = False) -> ListenResult:
+        """The same from unpacked samples [n_streams, N] (N a multiple of 256, oldest first) (awpu_hip_listen_samples)."""
+        samples = np.ascontiguousarray(samples, np.float32)
+        if samples.ndim != 2 or samples.shape[0] != self.cfg.n_streams or samples.shape[1] % 256 or samples.shape[1] == 0:
+            raise ValueError(f"samples must be [{self.cfg.n_streams}, N] with N a positive multiple of 256")
+        return self._listen(lambda *rest: self._lib.awpu_hip_listen_samples(self._h, _f32(samples), samples.shape[1], *rest),
+                            "awpu_hip_listen_samples", samples.shape[1] // 256, (theta, phi, spread, rate, steps), theta_limit,
+                            reference, want_trail, want_power)
+
+    def listen_samples_device(self, d_samples_ptr: int, pitch: int, n_blocks: int, theta, phi, spread, rate, steps, theta_limit: float,
+                              d_audio_ptr: int, audio_pitch: int, reference: Optional[float] = None, d_trail_ptr: int = 0,
+                              d_power_ptr: int = 0, stream: int = 0) -> np.ndarray:
+        """The same on device pointers (samples [n_streams, pitch], audio [n, audio_pitch], trail [n_blocks, n] records or 0,
+        power [n_blocks, pixels] or 0) on `stream`; returns the listeners after the run (PARTICLE_DTYPE records), for which it
+        waits (awpu_hip_listen_samples_device)."""
+        parts = _particles(theta, phi, spread, rate, steps, "awpu_hip_listen_samples_device")
+        _check(self._lib.awpu_hip_listen_samples_device(
+            self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, parts.ctypes.data_as(C.POINTER(Particle)), parts.size,
+            float(theta_limit), -1.0 if reference is None else float(reference), C.c_void_p(d_audio_ptr), audio_pitch,
+            C.c_void_p(d_trail_ptr), C.c_void_p(d_power_ptr), C.c_void_p(stream)), "awpu_hip_listen_samples_device")
+        return parts
 
     def set_fir_table(self, coeffs: np.ndarray) -> None:
         """The caller's [101, 8] coefficient table of the FIR variant (src/dsp/filter.h:10-112)."""
@@ -574,15 +670,8 @@ class Engine:
         per particle (scalars broadcast); reference None = computed on the device; d_frame_ptr 0 = the ingest ring.
         -> TrackResult: .particles (PARTICLE_DTYPE records after the call), .theta, .phi, .error, .grad_theta,
         .grad_phi, .radius, .power [n, 4], .reference, .beams [n, 256] or None."""
-        theta = np.atleast_1d(np.asarray(theta, np.float64))
-        n = max(theta.size, np.size(phi), np.size(spread), np.size(rate), np.size(steps))
-        parts = np.zeros(n, PARTICLE_DTYPE)
-        parts["theta"], parts["phi"] = np.broadcast_to(theta, n), np.broadcast_to(np.asarray(phi, np.float64), n)
-        parts["spread"], parts["rate"] = np.broadcast_to(np.asarray(spread, np.float64), n), np.broadcast_to(np.asarray(rate, np.float64), n)
-        steps = np.broadcast_to(np.asarray(steps, np.int64), n)
-        if steps.size and (steps.min() < 0 or steps.max() > 4096):  # (before the int32 field could wrap it into range)
-            raise AwpuError(ERR_INVALID, "awpu_hip_track", "steps outside [0, 4096]")
-        parts["steps"] = steps
+        parts = _particles(theta, phi, spread, rate, steps, "awpu_hip_track")
+        n = parts.size
         used = C.c_double(0.0)
         beams = np.empty((n, 256), np.float32) if want_beams else None
         _check(self._lib.awpu_hip_track(self._h, C.c_void_p(d_frame_ptr), parts.ctypes.data_as(C.POINTER(Particle)), n,

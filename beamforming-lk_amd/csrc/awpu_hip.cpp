@@ -3,6 +3,7 @@
 // in a gfx950 kernel launch or an error status.
 #include "awpu_hip.h"
 #include "awpu_hip_blocks.h"
+#include "awpu_hip_listen.h"
 #include "awpu_hip_track.h"
 
 #include <hip/hip_runtime.h>
@@ -220,6 +221,15 @@ struct awpu_hip {
     // run after the work queued on the handle's stream, and the handle's stream after a device-form run on the caller's stream
     hipEvent_t ev_blk_in[2] = {nullptr, nullptr}, ev_blk_hist[2] = {nullptr, nullptr}, ev_blk_cut[2] = {nullptr, nullptr},
                ev_blk_swept[2] = {nullptr, nullptr}, ev_blk_out[2] = {nullptr, nullptr}, ev_blk_ring = nullptr;
+    // listening to such runs (awpu_hip_listen.h): the listeners on the device from piece to piece; the host forms get piece i's
+    // audio rows [n][256 * piece], then its trail, in d_listen_out[i & 1] and bring them back through pinned h_listen_out[i & 1].
+    // listen_stream: where the listen kernels run beside the sweeps when heatmaps are asked for too.
+    unsigned char *d_listeners = nullptr;
+    unsigned char *d_listen_out[2] = {nullptr, nullptr}, *h_listen_out[2] = {nullptr, nullptr};
+    size_t listeners_cap = 0, listen_out_cap = 0;  // bytes
+    hipStream_t listen_stream = nullptr;
+    // ev_listened[b]: the listen kernels have read d_blk_hist[b] (and written d_listen_out[b]); ev_listen_out[b]: h_listen_out[b] holds it
+    hipEvent_t ev_listened[2] = {nullptr, nullptr}, ev_listen_out[2] = {nullptr, nullptr};
 
     awpu_hip_stats stats{};
     std::string last_error;                  // awpu_hip_last_error_of
@@ -275,6 +285,7 @@ struct EnvKnobs {
     int exact_pairs = 1;           // 0: AWPU_MATH_F32_EXACT on the round-1 verification kernel (das_exact_kernel)
     int pair_cols = -1;            // 0 / 1: the pair shape pairs consecutive / vertically adjacent pixels (default: whichever coincides more)
     int group_copy = 0;            // AWPU_GROUP_FORCE_COPY
+    int listen_stream = 1;         // tuning: 0 = the listen kernels queue behind the sweeps instead of running beside them
     EnvKnobs() {
         if (const char *v = std::getenv("AWPU_GROUP_FORCE_COPY")) group_copy = std::atoi(v);
         if (const char *v = std::getenv("AWPU_LIVE_GRAPH")) live_graph = std::atoi(v);
@@ -300,6 +311,7 @@ struct EnvKnobs {
             else std::fprintf(stderr, "libawpu_hip: AWPU_SHAPE=%s is not a shape of this build; ignored\n", v);
         }
 #ifdef AWPU_TUNING_BUILD
+        if (const char *v = std::getenv("AWPU_LISTEN_STREAM")) listen_stream = std::atoi(v);
         if (const char *v = std::getenv("AWPU_FAST_QUADS")) quads = std::atoi(v);
         if (const char *v = std::getenv("AWPU_FAST_PAIRGROUP")) pair_group = std::atoi(v);
         if (const char *v = std::getenv("AWPU_QUAD_VARIANT")) quad_variant = std::atoi(v);
@@ -406,6 +418,13 @@ void release_device(awpu_hip *h) {
     }
     dev_free(h->d_blk_frames);
     h->blk_hist_cap = h->blk_frames_cap = h->blk_in_cap = h->blk_out_cap = 0;
+    dev_free(h->d_listeners);
+    for (int b = 0; b < 2; b++) {
+        dev_free(h->d_listen_out[b]);
+        if (h->h_listen_out[b]) (void) hipHostFree(h->h_listen_out[b]);
+        h->h_listen_out[b] = nullptr;
+    }
+    h->listeners_cap = h->listen_out_cap = 0;
     for (int b = 0; b < 2; b++) {
         if (b == 0) {
             if (h->h_live_in) (void) hipHostFree(h->h_live_in);
@@ -2390,14 +2409,17 @@ int awpu_hip_destroy(awpu_hip_t *h) {
     (void) hipSetDevice(h->cfg.device);
     if (h->stream) (void) hipStreamSynchronize(h->stream);
     if (h->copy_stream) (void) hipStreamSynchronize(h->copy_stream);
+    if (h->listen_stream) (void) hipStreamSynchronize(h->listen_stream);
     release_device(h);
     for (hipEvent_t ev : {h->ev_begin, h->ev_end, h->ev_fan, h->ev_copied[0], h->ev_copied[1], h->ev_swept[0], h->ev_swept[1], h->ev_done,
                           h->ev_staged[0], h->ev_staged[1], h->ev_tile_free[0], h->ev_tile_free[1], h->ev_staged_read[0], h->ev_staged_read[1],
                           h->ev_blk_in[0], h->ev_blk_in[1], h->ev_blk_hist[0], h->ev_blk_hist[1], h->ev_blk_cut[0], h->ev_blk_cut[1],
-                          h->ev_blk_swept[0], h->ev_blk_swept[1], h->ev_blk_out[0], h->ev_blk_out[1], h->ev_blk_ring})
+                          h->ev_blk_swept[0], h->ev_blk_swept[1], h->ev_blk_out[0], h->ev_blk_out[1], h->ev_blk_ring,
+                          h->ev_listened[0], h->ev_listened[1], h->ev_listen_out[0], h->ev_listen_out[1]})
         if (ev) (void) hipEventDestroy(ev);
     if (h->stream) (void) hipStreamDestroy(h->stream);
     if (h->copy_stream) (void) hipStreamDestroy(h->copy_stream);
+    if (h->listen_stream) (void) hipStreamDestroy(h->listen_stream);
     delete h;
     return AWPU_OK;
 }
@@ -2666,6 +2688,45 @@ size_t align16(size_t n) { return (n + 15) & ~(size_t) 15; }
 
 static_assert(sizeof(awpu_particle_t) == 80, "awpu_particle_t is part of the ABI (include/awpu_hip_track.h)");
 
+// what awpu_hip_track and the listen calls ask of their particles (none of it reads the handle)
+int check_particles(const awpu_particle_t *p, int32_t n, double theta_limit, double reference) {
+    if (n < 1 || n > 65535) return invalid("n outside [1, 65535]");
+    if (!(theta_limit > 0.0) || !std::isfinite(theta_limit)) return invalid("theta_limit must be finite and > 0");
+    if (!std::isfinite(reference)) return invalid("reference not finite");
+    for (int k = 0; k < n; k++) {
+        if (p[k].steps < 0 || p[k].steps > 4096) return invalid("steps outside [0, 4096]");
+        if (!std::isfinite(p[k].theta) || !std::isfinite(p[k].phi) || !std::isfinite(p[k].spread) || !std::isfinite(p[k].rate))
+            return invalid("particle direction, spread or rate not finite");
+    }
+    return AWPU_OK;
+}
+
+// ... and of the handle: the antenna, and the active mics inside it
+int check_antenna(const awpu_hip *h) {
+    if (h->antenna.empty()) return fail(AWPU_ERR_STATE, "antenna not set (awpu_hip_set_antenna)");
+    if (!h->have_mics || h->index.empty()) return fail(AWPU_ERR_STATE, "active mics not set");
+    const int n_el = (int) (h->antenna.size() / 3);
+    for (int id : h->index)
+        if (id >= n_el) return fail(AWPU_ERR_STATE, "an active mic is not an element of the antenna");
+    return AWPU_OK;
+}
+
+// d_track_index = the active mics
+int ensure_track_index(awpu_hip *h) {
+    const int U = h->usable();
+    if (h->track_index == h->index) return AWPU_OK;
+    if (h->track_index_cap < (size_t) U) {
+        dev_free(h->d_track_index);
+        h->track_index_cap = 0;
+        AWPU_HIP_TRY(hipMalloc(&h->d_track_index, (size_t) U * sizeof(int32_t)));
+        h->track_index_cap = U;
+    }
+    h->track_index.clear();
+    AWPU_HIP_TRY(hipMemcpy(h->d_track_index, h->index.data(), (size_t) U * sizeof(int32_t), hipMemcpyHostToDevice));
+    h->track_index = h->index;
+    return AWPU_OK;
+}
+
 }  // namespace
 
 int awpu_hip_steer_table_device(awpu_hip_t *h, const double *theta, const double *phi, int32_t n_dir, int32_t *off,
@@ -2696,19 +2757,9 @@ int awpu_hip_track(awpu_hip_t *h, const float *d_frame, awpu_particle_t *p, int3
     if (h && !h->parts.empty()) h = h->parts[0];  // not pixel-sharded: a device group answers with its first device
     AWPU_CTX(h);
     if (!h || !p) return invalid("null argument");
-    if (n < 1 || n > 65535) return invalid("n outside [1, 65535]");
-    if (!(theta_limit > 0.0) || !std::isfinite(theta_limit)) return invalid("theta_limit must be finite and > 0");
-    if (!std::isfinite(reference)) return invalid("reference not finite");
-    for (int k = 0; k < n; k++) {
-        if (p[k].steps < 0 || p[k].steps > 4096) return invalid("steps outside [0, 4096]");
-        if (!std::isfinite(p[k].theta) || !std::isfinite(p[k].phi) || !std::isfinite(p[k].spread) || !std::isfinite(p[k].rate))
-            return invalid("particle direction, spread or rate not finite");
-    }
-    if (h->antenna.empty()) return fail(AWPU_ERR_STATE, "antenna not set (awpu_hip_set_antenna)");
-    if (!h->have_mics || h->index.empty()) return fail(AWPU_ERR_STATE, "active mics not set");
+    if (int rc = check_particles(p, n, theta_limit, reference)) return rc;
+    if (int rc = check_antenna(h)) return rc;
     const int n_el = (int) (h->antenna.size() / 3);
-    for (int id : h->index)
-        if (id >= n_el) return fail(AWPU_ERR_STATE, "an active mic is not an element of the antenna");
     int pitch = h->cfg.hist;
     const float *frame = d_frame;
     if (!frame) {  // the current snapshot of the ingest ring
@@ -2720,17 +2771,7 @@ int awpu_hip_track(awpu_hip_t *h, const float *d_frame, awpu_particle_t *p, int3
     }
     AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
     const int U = h->usable();
-    if (h->track_index != h->index) {
-        if (h->track_index_cap < (size_t) U) {
-            dev_free(h->d_track_index);
-            h->track_index_cap = 0;
-            AWPU_HIP_TRY(hipMalloc(&h->d_track_index, (size_t) U * sizeof(int32_t)));
-            h->track_index_cap = U;
-        }
-        h->track_index.clear();
-        AWPU_HIP_TRY(hipMemcpy(h->d_track_index, h->index.data(), (size_t) U * sizeof(int32_t), hipMemcpyHostToDevice));
-        h->track_index = h->index;
-    }
+    if (int rc = ensure_track_index(h)) return rc;
     const size_t particles = (size_t) n * sizeof(awpu_particle_t), head = align16(particles + sizeof(double));
     if (int rc = ensure_track_buffer(h, head + (beams ? (size_t) n * awpu::kSamples * sizeof(float) : 0))) return rc;
     awpu::TrackArgs a{};
@@ -3112,8 +3153,51 @@ struct BlockRun {
     bool device = false;
 };
 
+// What a listen call (awpu_hip_listen.h) adds to a run; audio and trail are host memory in the host forms, device memory in the
+// device form.  Per piece, between its history and the ring write: the listen kernels on that history.
+struct ListenRun {
+    awpu_particle_t *listeners = nullptr;  // host, in/out
+    int32_t n = 0;
+    double theta_limit = 0.0, reference = 0.0;
+    float *audio = nullptr;
+    int64_t audio_pitch = 0;
+    awpu_particle_t *trail = nullptr;
+    bool sweep = false;                    // heatmaps asked for too
+};
+
+// piece-sized buffers of a listen run: the listeners' state, and for the host forms the way back of audio and trail
+int ensure_listen_buffers(awpu_hip *h, const ListenRun &ls, int piece, bool host) {
+    const size_t state = (size_t) ls.n * sizeof(awpu_particle_t);
+    if (h->listeners_cap < state) {
+        dev_free(h->d_listeners);
+        h->listeners_cap = 0;
+        AWPU_HIP_TRY(hipMalloc(&h->d_listeners, state));
+        h->listeners_cap = state;
+    }
+    if (!host) return AWPU_OK;
+    const size_t out_bytes = align16((size_t) ls.n * awpu::kSamples * piece * sizeof(float)) + (size_t) piece * state;
+    if (h->listen_out_cap < out_bytes) {
+        for (int b = 0; b < 2; b++) {
+            dev_free(h->d_listen_out[b]);
+            if (h->h_listen_out[b]) (void) hipHostFree(h->h_listen_out[b]);
+            h->h_listen_out[b] = nullptr;
+        }
+        h->listen_out_cap = 0;
+        for (int b = 0; b < 2; b++) {
+            AWPU_HIP_TRY(hipMalloc(&h->d_listen_out[b], out_bytes));
+            AWPU_HIP_TRY(hipHostMalloc(&h->h_listen_out[b], out_bytes, hipHostMallocDefault));
+        }
+        h->listen_out_cap = out_bytes;
+    }
+    if (ls.sweep && env().listen_stream && !h->listen_stream)
+        AWPU_HIP_TRY(hipStreamCreateWithFlags(&h->listen_stream, hipStreamNonBlocking));
+    for (hipEvent_t *ev : {&h->ev_listened[0], &h->ev_listened[1], &h->ev_listen_out[0], &h->ev_listen_out[1]})
+        if (!*ev) AWPU_HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+    return AWPU_OK;
+}
+
 // device buffers for pieces of at most `piece` frames (and, for the host forms, the pinned staging and the second stream)
-int ensure_blk_buffers(awpu_hip *h, const BlockRun &src, int piece, int width) {
+int ensure_blk_buffers(awpu_hip *h, const BlockRun &src, int piece, int width, bool sweep) {
     const size_t S = (size_t) h->cfg.n_streams;
     const size_t hist_floats = S * (awpu::kBlockPrefix + (size_t) awpu::kSamples * piece);
     if (h->blk_hist_cap < hist_floats) {
@@ -3122,7 +3206,7 @@ int ensure_blk_buffers(awpu_hip *h, const BlockRun &src, int piece, int width) {
         for (int b = 0; b < 2; b++) AWPU_HIP_TRY(hipMalloc(&h->d_blk_hist[b], hist_floats * sizeof(float)));
         h->blk_hist_cap = hist_floats;
     }
-    const size_t frames_floats = S * width * (size_t) piece;
+    const size_t frames_floats = sweep ? S * width * (size_t) piece : 0;  // (a listen run without heatmaps cuts no window)
     if (h->blk_frames_cap < frames_floats) {
         dev_free(h->d_blk_frames);
         h->blk_frames_cap = 0;
@@ -3145,7 +3229,7 @@ int ensure_blk_buffers(awpu_hip *h, const BlockRun &src, int piece, int width) {
         }
         h->blk_in_cap = in_bytes;
     }
-    const size_t out_floats = (size_t) piece * h->cfg.pixel_count;
+    const size_t out_floats = sweep ? (size_t) piece * h->cfg.pixel_count : 0;
     if (h->blk_out_cap < out_floats) {
         for (int b = 0; b < 2; b++) {
             if (h->h_blk_out[b]) (void) hipHostFree(h->h_blk_out[b]);
@@ -3159,7 +3243,7 @@ int ensure_blk_buffers(awpu_hip *h, const BlockRun &src, int piece, int width) {
     for (hipEvent_t *ev : {&h->ev_blk_in[0], &h->ev_blk_in[1], &h->ev_blk_hist[0], &h->ev_blk_hist[1], &h->ev_blk_cut[0],
                            &h->ev_blk_cut[1], &h->ev_blk_swept[0], &h->ev_blk_swept[1], &h->ev_blk_out[0], &h->ev_blk_out[1]})
         if (!*ev) AWPU_HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
-    return ensure_power(h, (size_t) 2 * piece * h->cfg.pixel_count);  // two pieces' powers: one swept, one on its way back
+    return sweep ? ensure_power(h, (size_t) 2 * piece * h->cfg.pixel_count) : AWPU_OK;  // two pieces' powers: one swept, one on its way back
 }
 
 // blocks [g0, g0 + nb) of a host form into pinned staging h_blk_in[b]: tight datagrams, or rows of 256 * nb samples.  Pieces of
@@ -3200,16 +3284,24 @@ void stage_blocks(awpu_hip *h, const BlockRun &src, int g0, int nb, int b) {
     for (auto &th : pool) th.join();
 }
 
-// the run; host forms: `power` [n_blocks][pixel_count] host, synchronous; device form: `d_out` on `user` (NULL = h->stream)
-int run_blocks(awpu_hip *h, const BlockRun &src, int n_blocks, float *power, float *d_out, hipStream_t user) {
+// the run; host forms: `power` [n_blocks][pixel_count] host, synchronous; device form: `d_out` on `user` (NULL = h->stream).
+// With `ls` the run is listened to as well (awpu_hip_listen.h), and swept only if ls->sweep.
+int run_blocks(awpu_hip *h, const BlockRun &src, int n_blocks, float *power, float *d_out, hipStream_t user, const ListenRun *ls = nullptr) {
     if (!h->parts.empty()) return fail(AWPU_ERR_STATE, "a device group does not take runs of blocks");
     if (h->in_flight) return fail(AWPU_ERR_STATE, "an awpu_hip_process_async call is in flight on this handle: awpu_hip_wait first");
     const awpu_hip_cfg &c = h->cfg;
     if (c.hist != AWPU_HIST) return invalid("runs of blocks need hist 1024");
     if (src.wire && c.n_streams > 256) return invalid("the wire carries at most 256 streams");
+    const bool sweep = !ls || ls->sweep;
     const int chunk = std::min<int>(n_blocks, c.max_batch);
-    int rc = check_ready(h, chunk);
+    int rc = ls ? check_antenna(h) : AWPU_OK;
     if (rc != AWPU_OK) return rc;
+    if (sweep) {
+        rc = check_ready(h, chunk);
+        if (rc != AWPU_OK) return rc;
+    } else {
+        AWPU_HIP_TRY(hipSetDevice(c.device));
+    }
     std::vector<std::pair<int, int>> pieces;  // (first block, blocks): every chunk in awpu_hip_process's pieces
     int piece_max = 1;
     for (int c0 = 0; c0 < n_blocks; c0 += chunk) {
@@ -3221,23 +3313,63 @@ int run_blocks(awpu_hip *h, const BlockRun &src, int n_blocks, float *power, flo
     }
     const bool compact = h->compact_hist > 0;
     const int width = compact ? h->compact_hist : AWPU_HIST, lo = compact ? h->wstart : 0;
+    const bool host = !src.device;
     rc = ensure_ring(h);
-    if (rc == AWPU_OK) rc = ensure_blk_buffers(h, src, piece_max, width);
+    if (rc == AWPU_OK) rc = ensure_blk_buffers(h, src, piece_max, width, sweep);
+    if (rc == AWPU_OK && ls) rc = ensure_track_index(h);
+    if (rc == AWPU_OK && ls) rc = ensure_listen_buffers(h, *ls, piece_max, host);
     if (rc != AWPU_OK) return rc;
     const int S = c.n_streams, pitch = awpu::kBlockPrefix + awpu::kSamples * piece_max;
     const size_t P = (size_t) c.pixel_count;
-    const bool host = !src.device;
     hipStream_t sw = host ? h->stream : (user ? user : h->stream);  // cut and sweep
     hipStream_t up = host ? h->copy_stream : sw;                    // upload and history
+    // the listen kernels: a few workgroups that walk a piece block by block, so beside the sweep of the same piece where there is
+    // one (host forms), and in the caller's order on the caller's stream in the device form
+    hipStream_t li = host && sweep && h->listen_stream && env().listen_stream ? h->listen_stream : sw;
     const bool keep_timing = h->timing;
-    if (!host) h->timing = false;  // asynchronous: the caller times its own stream
+    const bool time_it = keep_timing && host && sweep;
+    if (!time_it) h->timing = false;  // the device form is asynchronous: the caller times its own stream; nothing swept, nothing timed
     const int n_pieces = (int) pieces.size();
-    // host forms: piece j's powers, in h_blk_out[j & 1] once ev_blk_out[j & 1] has passed, to the caller's rows
+    const size_t state = ls ? (size_t) ls->n * sizeof(awpu_particle_t) : 0;
+    bool tracking = false, fixed = false;
+    for (int l = 0; ls && l < ls->n; l++) (ls->listeners[l].steps > 0 ? tracking : fixed) = true;
+    const auto audio_bytes = [&](int nb) { return align16((size_t) ls->n * awpu::kSamples * nb * sizeof(float)); };
+    // host forms: piece j's powers, in h_blk_out[j & 1] once ev_blk_out[j & 1] has passed, to the caller's rows; its audio rows and
+    // trail likewise out of h_listen_out[j & 1]
     const auto deliver = [&](int j) -> int {
-        AWPU_HIP_TRY(hipEventSynchronize(h->ev_blk_out[j & 1]));
-        std::memcpy(power + (size_t) pieces[j].first * P, h->h_blk_out[j & 1], (size_t) pieces[j].second * P * sizeof(float));
+        const int g0 = pieces[j].first, nb = pieces[j].second;
+        if (sweep) {
+            AWPU_HIP_TRY(hipEventSynchronize(h->ev_blk_out[j & 1]));
+            std::memcpy(power + (size_t) g0 * P, h->h_blk_out[j & 1], (size_t) nb * P * sizeof(float));
+        }
+        if (ls) {
+            AWPU_HIP_TRY(hipEventSynchronize(h->ev_listen_out[j & 1]));
+            const unsigned char *from = h->h_listen_out[j & 1];
+            const size_t row = (size_t) awpu::kSamples * nb;
+            for (int l = 0; l < ls->n; l++)
+                std::memcpy(ls->audio + (size_t) l * ls->audio_pitch + (size_t) awpu::kSamples * g0, from + l * row * sizeof(float), row * sizeof(float));
+            if (ls->trail) std::memcpy(ls->trail + (size_t) g0 * ls->n, from + audio_bytes(nb), (size_t) nb * state);
+        }
         return AWPU_OK;
     };
+    // host forms: piece j's powers, and what was heard in it, into pinned memory behind the kernels that write them
+    const auto fetch = [&](int j) -> int {
+        const int b = j & 1, nb = pieces[j].second;
+        if (sweep) {
+            AWPU_HIP_TRY(hipStreamWaitEvent(up, h->ev_blk_swept[b], 0));
+            AWPU_HIP_TRY(hipMemcpyAsync(h->h_blk_out[b], h->d_power + (size_t) b * piece_max * P, (size_t) nb * P * sizeof(float),
+                                        hipMemcpyDeviceToHost, up));
+            AWPU_HIP_TRY(hipEventRecord(h->ev_blk_out[b], up));
+        }
+        if (ls) {
+            AWPU_HIP_TRY(hipStreamWaitEvent(up, h->ev_listened[b], 0));
+            AWPU_HIP_TRY(hipMemcpyAsync(h->h_listen_out[b], h->d_listen_out[b], audio_bytes(nb) + (ls->trail ? (size_t) nb * state : 0),
+                                        hipMemcpyDeviceToHost, up));
+            AWPU_HIP_TRY(hipEventRecord(h->ev_listen_out[b], up));
+        }
+        return AWPU_OK;
+    };
+    std::vector<awpu_particle_t> heard(ls ? ls->n : 0);  // the listeners after the run
     const auto body = [&]() -> int {
         // whatever is queued on the handle's stream -- the ring's zeroing, the ring writes and cuts of a device-form run not yet
         // over -- comes first: the upload side reads the ring and rewrites the histories
@@ -3245,6 +3377,7 @@ int run_blocks(awpu_hip *h, const BlockRun &src, int n_blocks, float *power, flo
             AWPU_HIP_TRY(hipEventRecord(h->ev_blk_ring, h->stream));
             AWPU_HIP_TRY(hipStreamWaitEvent(up, h->ev_blk_ring, 0));
         }
+        if (ls) AWPU_HIP_TRY(hipMemcpyAsync(h->d_listeners, ls->listeners, state, hipMemcpyHostToDevice, up));  // (before the first history)
         const float *prev = h->d_ring + h->ring_pos + awpu::kSamples;  // the last 768 samples of the current snapshot
         long long prev_pitch = 2048;
         for (int i = 0; i < n_pieces; i++) {
@@ -3256,7 +3389,9 @@ int run_blocks(awpu_hip *h, const BlockRun &src, int n_blocks, float *power, flo
                 const size_t bytes = (size_t) awpu::kSamples * nb * (src.wire ? (size_t) AWPU_DATAGRAM_BYTES : S * sizeof(float));
                 AWPU_HIP_TRY(hipMemcpyAsync(h->d_blk_in[b], h->h_blk_in[b], bytes, hipMemcpyHostToDevice, up));
                 AWPU_HIP_TRY(hipEventRecord(h->ev_blk_in[b], up));
-                if (i >= 2) AWPU_HIP_TRY(hipStreamWaitEvent(up, h->ev_blk_cut[b], 0));  // piece i-2's windows are cut out of d_blk_hist[b]
+                // piece i-2's windows are cut out of d_blk_hist[b], and its listeners have heard it
+                if (i >= 2 && sweep) AWPU_HIP_TRY(hipStreamWaitEvent(up, h->ev_blk_cut[b], 0));
+                if (i >= 2 && ls) AWPU_HIP_TRY(hipStreamWaitEvent(up, h->ev_listened[b], 0));
             }
             AWPU_HIP_TRY(awpu::launch_copy_rows(prev, prev_pitch, hist, pitch, awpu::kBlockPrefix, S, up));
             if (src.wire) {
@@ -3269,22 +3404,49 @@ int run_blocks(awpu_hip *h, const BlockRun &src, int n_blocks, float *power, flo
             if (host) {
                 AWPU_HIP_TRY(hipEventRecord(h->ev_blk_hist[b], up));
                 AWPU_HIP_TRY(hipStreamWaitEvent(sw, h->ev_blk_hist[b], 0));
+                if (li != sw) AWPU_HIP_TRY(hipStreamWaitEvent(li, h->ev_blk_hist[b], 0));
             }
-            AWPU_HIP_TRY(awpu::launch_cut_windows(hist, pitch, S, nb, lo, width, h->d_blk_frames, sw));
-            if (host) AWPU_HIP_TRY(hipEventRecord(h->ev_blk_cut[b], sw));
-            if (host && keep_timing && i == 0) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, sw));
-            h->timing = false;
-            rc = launch(h, h->d_blk_frames, nb, host ? h->d_power + (size_t) b * piece_max * P : d_out + (size_t) g0 * P, sw,
-                        compact ? kCompact : kFull);
-            h->timing = keep_timing && host;
-            if (rc != AWPU_OK) return rc;
+            if (sweep) {
+                AWPU_HIP_TRY(awpu::launch_cut_windows(hist, pitch, S, nb, lo, width, h->d_blk_frames, sw));
+                if (host) AWPU_HIP_TRY(hipEventRecord(h->ev_blk_cut[b], sw));
+                if (time_it && i == 0) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, sw));
+                h->timing = false;
+                rc = launch(h, h->d_blk_frames, nb, host ? h->d_power + (size_t) b * piece_max * P : d_out + (size_t) g0 * P, sw,
+                            compact ? kCompact : kFull);
+                h->timing = time_it;
+                if (rc != AWPU_OK) return rc;
+                if (host) AWPU_HIP_TRY(hipEventRecord(h->ev_blk_swept[b], sw));
+            }
+            if (ls) {
+                // (d_listen_out[b] is free: piece i-2's way back out of it was queued on `up` before this piece's history)
+                awpu::ListenArgs a{};
+                a.hist = hist;
+                a.pitch = pitch;
+                a.n_blocks = nb;
+                a.xyz = h->d_xyz;
+                a.n = (int) (h->antenna.size() / 3);
+                a.index = h->d_track_index;
+                a.usable = h->usable();
+                a.listeners = h->d_listeners;
+                a.n_listeners = ls->n;
+                a.theta_limit = ls->theta_limit;
+                a.reference = ls->reference;
+                if (host) {
+                    a.audio = reinterpret_cast<float *>(h->d_listen_out[b]);
+                    a.audio_pitch = (long long) awpu::kSamples * nb;
+                    a.trail = ls->trail ? h->d_listen_out[b] + audio_bytes(nb) : nullptr;
+                } else {
+                    a.audio = ls->audio + (size_t) awpu::kSamples * g0;
+                    a.audio_pitch = ls->audio_pitch;
+                    a.trail = ls->trail ? ls->trail + (size_t) g0 * ls->n : nullptr;
+                }
+                AWPU_HIP_TRY(awpu::launch_listen(a, tracking, fixed, li));
+                if (host) AWPU_HIP_TRY(hipEventRecord(h->ev_listened[b], li));
+            }
             if (host) {
-                AWPU_HIP_TRY(hipEventRecord(h->ev_blk_swept[b], sw));
-                if (i >= 1) {  // piece i-1's powers go back into pinned memory behind its sweep, while piece i is swept ...
-                    AWPU_HIP_TRY(hipStreamWaitEvent(up, h->ev_blk_swept[b ^ 1], 0));
-                    AWPU_HIP_TRY(hipMemcpyAsync(h->h_blk_out[b ^ 1], h->d_power + (size_t) (b ^ 1) * piece_max * P,
-                                                (size_t) pieces[i - 1].second * P * sizeof(float), hipMemcpyDeviceToHost, up));
-                    AWPU_HIP_TRY(hipEventRecord(h->ev_blk_out[b ^ 1], up));
+                if (i >= 1) {  // piece i-1's results go back into pinned memory behind its kernels, while piece i is swept ...
+                    rc = fetch(i - 1);
+                    if (rc != AWPU_OK) return rc;
                 }
                 if (i >= 2) {  // ... and piece i-2's, long back, go to the caller before h_blk_out[b] is written again
                     rc = deliver(i - 2);
@@ -3295,36 +3457,58 @@ int run_blocks(awpu_hip *h, const BlockRun &src, int n_blocks, float *power, flo
             prev_pitch = pitch;
         }
         const int last_b = (n_pieces - 1) & 1, last_nb = pieces.back().second;
-        if (host && keep_timing) AWPU_HIP_TRY(hipEventRecord(h->ev_end, sw));
+        if (time_it) AWPU_HIP_TRY(hipEventRecord(h->ev_end, sw));
         // the ring as n_blocks ingests leave it: its snapshot = the last 1024 samples of the last history
         const int pos = (int) ((h->ring_pos + (long long) awpu::kSamples * n_blocks) % AWPU_HIST);
         AWPU_HIP_TRY(awpu::launch_ring_write(h->d_blk_hist[last_b], pitch, awpu::kSamples * (last_nb - 1), S, h->d_ring, pos, sw));
         h->ring_pos = pos;
+        if (ls) AWPU_HIP_TRY(hipMemcpyAsync(heard.data(), h->d_listeners, state, hipMemcpyDeviceToHost, li));
         if (!host) {
             if (sw != h->stream) {  // later calls on the ring (the handle's stream) come after this one
                 AWPU_HIP_TRY(hipEventRecord(h->ev_blk_ring, sw));
                 AWPU_HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_blk_ring, 0));
             }
+            if (ls) AWPU_HIP_TRY(hipStreamSynchronize(sw));  // the listeners' state is host memory
             return AWPU_OK;
         }
-        AWPU_HIP_TRY(hipStreamWaitEvent(up, h->ev_blk_swept[last_b], 0));
-        AWPU_HIP_TRY(hipMemcpyAsync(h->h_blk_out[last_b], h->d_power + (size_t) last_b * piece_max * P, (size_t) last_nb * P * sizeof(float),
-                                    hipMemcpyDeviceToHost, up));
-        AWPU_HIP_TRY(hipEventRecord(h->ev_blk_out[last_b], up));
+        rc = fetch(n_pieces - 1);
+        if (rc != AWPU_OK) return rc;
         for (int j = std::max(0, n_pieces - 2); j < n_pieces; j++) {
             rc = deliver(j);
             if (rc != AWPU_OK) return rc;
         }
         AWPU_HIP_TRY(hipStreamSynchronize(up));
+        if (li != sw) AWPU_HIP_TRY(hipStreamSynchronize(li));
         return wait_and_time(h);
     };
     rc = body();
     h->timing = keep_timing;
     if (rc != AWPU_OK && host) {  // nothing of the call may still read the caller's or the handle's buffers
         (void) hipStreamSynchronize(h->copy_stream);
+        if (h->listen_stream) (void) hipStreamSynchronize(h->listen_stream);
         (void) hipStreamSynchronize(h->stream);
     }
+    if (rc == AWPU_OK && ls) std::memcpy(ls->listeners, heard.data(), state);
     return rc;
+}
+
+// the checks of a listen call that read no handle; then the run
+int listen_run(awpu_hip *h, const BlockRun &src, int n_blocks, awpu_particle_t *listeners, int32_t n, double theta_limit, double reference,
+               float *audio, int64_t audio_pitch, awpu_particle_t *trail, float *power, hipStream_t user) {
+    if (!listeners || !audio) return invalid("null argument");
+    if (int rc = check_particles(listeners, n, theta_limit, reference)) return rc;
+    if (audio_pitch < (int64_t) awpu::kSamples * n_blocks) return invalid("audio_pitch below 256 * n_blocks");
+    AWPU_CTX(h);
+    ListenRun ls;
+    ls.listeners = listeners;
+    ls.n = n;
+    ls.theta_limit = theta_limit;
+    ls.reference = reference;
+    ls.audio = audio;
+    ls.audio_pitch = audio_pitch;
+    ls.trail = trail;
+    ls.sweep = power != nullptr;
+    return run_blocks(h, src, n_blocks, src.device ? nullptr : power, src.device ? power : nullptr, user, &ls);
 }
 
 }  // namespace
@@ -3366,6 +3550,49 @@ int awpu_hip_process_samples_device(awpu_hip_t *h, const float *d_samples, int64
     src.pitch = pitch;
     src.device = true;
     return run_blocks(h, src, n_blocks, nullptr, d_power, static_cast<hipStream_t>(stream));
+}
+
+// ---- listening to runs of blocks (include/awpu_hip_listen.h; kernels in track_kernels.hip) -----------------------------------
+
+int awpu_hip_listen_blocks(awpu_hip_t *h, const void *datagrams, int32_t stride_bytes, int32_t n_blocks, awpu_particle_t *listeners,
+                           int32_t n, double theta_limit, double reference, float *audio, int64_t audio_pitch, awpu_particle_t *trail,
+                           float *power) {
+    if (!h) return invalid("null handle");
+    if (!datagrams) return invalid("null argument");
+    if (n_blocks < 1) return invalid("n_blocks below 1");
+    if (stride_bytes < AWPU_DATAGRAM_BYTES) return invalid("datagram stride below 1032 bytes");
+    BlockRun src;
+    src.wire = static_cast<const unsigned char *>(datagrams);
+    src.stride = stride_bytes;
+    return listen_run(h, src, n_blocks, listeners, n, theta_limit, reference, audio, audio_pitch, trail, power, nullptr);
+}
+
+int awpu_hip_listen_samples(awpu_hip_t *h, const float *samples, int64_t pitch, int32_t n_blocks, awpu_particle_t *listeners, int32_t n,
+                            double theta_limit, double reference, float *audio, int64_t audio_pitch, awpu_particle_t *trail,
+                            float *power) {
+    if (!h) return invalid("null handle");
+    if (!samples) return invalid("null argument");
+    if (n_blocks < 1) return invalid("n_blocks below 1");
+    if (pitch < (int64_t) awpu::kSamples * n_blocks) return invalid("pitch below 256 * n_blocks");
+    BlockRun src;
+    src.samples = samples;
+    src.pitch = pitch;
+    return listen_run(h, src, n_blocks, listeners, n, theta_limit, reference, audio, audio_pitch, trail, power, nullptr);
+}
+
+int awpu_hip_listen_samples_device(awpu_hip_t *h, const float *d_samples, int64_t pitch, int32_t n_blocks, awpu_particle_t *listeners,
+                                   int32_t n, double theta_limit, double reference, float *d_audio, int64_t audio_pitch,
+                                   awpu_particle_t *d_trail, float *d_power, void *stream) {
+    if (!h) return invalid("null handle");
+    if (!d_samples) return invalid("null argument");
+    if (n_blocks < 1) return invalid("n_blocks below 1");
+    if (pitch < (int64_t) awpu::kSamples * n_blocks) return invalid("pitch below 256 * n_blocks");
+    BlockRun src;
+    src.samples = d_samples;
+    src.pitch = pitch;
+    src.device = true;
+    return listen_run(h, src, n_blocks, listeners, n, theta_limit, reference, d_audio, audio_pitch, d_trail, d_power,
+                      static_cast<hipStream_t>(stream));
 }
 
 int awpu_hip_heatmap_u8_device(awpu_hip_t *h, const float *d_power, int32_t n, int32_t batch, float *d_peak,

@@ -401,6 +401,27 @@ struct TrackArgs {
 size_t track_lds_bytes(int usable);
 hipError_t launch_track(const TrackArgs &a, hipStream_t stream);
 
+// MISOWorker::update for every block of a sweep piece's history (include/awpu_hip_listen.h; block_kernels.h for the history)
+struct ListenArgs {
+    const float *hist;     // snapshot k of the piece starts at hist + 256 * k; stream id s at + s * pitch
+    int32_t pitch;
+    int32_t n_blocks;
+    const float *xyz;      // [3][n] element positions by stream id
+    int32_t n;
+    const int32_t *index;  // [usable] active stream ids, the reference's order
+    int32_t usable;
+    void *listeners;       // awpu_particle_t [n_listeners]: the state before the piece, and after it
+    int32_t n_listeners;
+    double theta_limit;
+    double reference;      // <= 0: from stream 0 of each block's own snapshot
+    float *audio;          // audio[l * audio_pitch + 256 * k + i]
+    long long audio_pitch;
+    void *trail;           // awpu_particle_t [n_blocks][n_listeners]: every listener after every block, or null
+};
+// listen_blocks_kernel for the listeners with steps > 0 (`tracking`: there is one) and listen_fixed_kernel for those with
+// steps == 0 (`fixed`), on the same stream
+hipError_t launch_listen(const ListenArgs &a, bool tracking, bool fixed, hipStream_t stream);
+
 // geometry_host.cpp: the per-pixel half of computeDelayLUT for the device builder (rot [row_count * columns][12])
 void pixel_rotations(int rows, int columns, float fov_deg, int row_begin, int row_count, float *rot);
 float samples_per_metre();  // (float) (48828 / 340), antenna.cpp:90
