@@ -185,6 +185,33 @@ _LISTEN_SIGNATURES = {
 }
 LISTEN_SYMBOLS = tuple(_LISTEN_SIGNATURES)
 
+
+
+class Watch(C.Structure):
+    """awpu_watch_t (include/awpu_hip_watch.h)."""
+    _fields_ = [
+        ("first", C.c_int32),
+        ("every", C.c_int32),
+        ("rows", C.c_int32),
+        ("cols", C.c_int32),
+        ("out_rows", C.c_int32),
+        ("out_cols", C.c_int32),
+        ("flip", C.c_int32),
+        ("d_colormap", C.c_void_p),
+    ]
+
+
+# watching such runs: the entry points of include/awpu_hip_watch.h
+_WATCH_TAIL = [C.c_int32, C.POINTER(Watch)]  # n_blocks, w
+_WATCH_SIGNATURES = {
+    "awpu_hip_watch_count": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _i32p, _i32p]),
+    "awpu_hip_watch_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, *_WATCH_TAIL, _u8p, _u8p, _f32p]),
+    "awpu_hip_watch_samples": (C.c_int, [C.c_void_p, _f32p, C.c_int64, *_WATCH_TAIL, _u8p, _u8p, _f32p]),
+    "awpu_hip_watch_samples_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, *_WATCH_TAIL, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p]),
+}
+WATCH_SYMBOLS = tuple(_WATCH_SIGNATURES)
+
 # numpy view of awpu_particle_t: what Engine.track returns, one record per particle
 PARTICLE_DTYPE = np.dtype([("theta", "<f8"), ("phi", "<f8"), ("spread", "<f8"), ("rate", "<f8"), ("steps", "<i4"),
                            ("error", "<f4"), ("grad_theta", "<f8"), ("grad_phi", "<f8"), ("radius", "<f8"),
@@ -213,7 +240,7 @@ def load(build: bool = True) -> C.CDLL:
         raise RuntimeError(f"{path} is missing and there is no CPU fallback")
     lib = C.CDLL(str(path))
     for name, (res, args) in list(_SIGNATURES.items()) + list(_TRACK_SIGNATURES.items()) + list(_BLOCK_SIGNATURES.items()) + \
-            list(_LISTEN_SIGNATURES.items()):
+            list(_LISTEN_SIGNATURES.items()) + list(_WATCH_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -368,6 +395,28 @@ class ListenResult:
 
     def __len__(self):
         return self.listeners.size
+
+
+class WatchResult:
+    """What Engine.watch_* hand back: .image [n_frames, rows, cols] uint8 or None, .big [n_frames, out_rows, out_cols] (x 3 with a
+    colour table) or None, .power [n_frames, pixels] or None, and .next_first: the `first` of the call that continues the
+    recording.  Frame j shows block first + j * every of the call."""
+
+    def __init__(self, image, big, power, next_first: int):
+        self.image = image
+        self.big = big
+        self.power = power
+        self.next_first = next_first
+
+    def __len__(self):
+        return next(len(a) for a in (self.image, self.big, self.power) if a is not None)
+
+
+def watch_count(n_blocks: int, first: int, every: int):
+    """(frames a call of n_blocks blocks shows, the `first` of the call that continues it) (awpu_hip_watch_count)."""
+    n, nxt = C.c_int32(0), C.c_int32(0)
+    _check(load().awpu_hip_watch_count(n_blocks, first, every, C.byref(n), C.byref(nxt)), "awpu_hip_watch_count")
+    return int(n.value), int(nxt.value)
 
 
 def _particles(theta, phi, spread, rate, steps, where: str) -> np.ndarray:
@@ -551,6 +600,69 @@ class Engine:
             float(theta_limit), -1.0 if reference is None else float(reference), C.c_void_p(d_audio_ptr), audio_pitch,
             C.c_void_p(d_trail_ptr), C.c_void_p(d_power_ptr), C.c_void_p(stream)), "awpu_hip_listen_samples_device")
         return parts
+
+    def _watch(self, call, where, n_blocks, first, every, rows, cols, out_rows, out_cols, d_colormap_ptr, flip, want_image,
+               want_power, out) -> WatchResult:
+        n_frames, next_first = watch_count(n_blocks, first, every)
+        w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(d_colormap_ptr))
+
+        def array(shape, dtype, old):  # the earlier result's array where it has room (its first n_frames rows), else a new one
+            if isinstance(old, np.ndarray) and old.dtype == dtype and old.shape[1:] == shape[1:] and old.flags.c_contiguous:
+                base = old if old.base is None else old.base
+                if isinstance(base, np.ndarray) and base.dtype == dtype and base.shape[1:] == shape[1:] and len(base) >= shape[0]:
+                    return base[: shape[0]]
+            return np.empty(shape, dtype)
+
+        image = array((n_frames, rows, cols), np.uint8, getattr(out, "image", None)) if want_image else None
+        big = None
+        if out_rows:
+            big = array((n_frames, out_rows, out_cols, 3) if d_colormap_ptr else (n_frames, out_rows, out_cols), np.uint8,
+                        getattr(out, "big", None))
+        power = array((n_frames, self.pixel_count), np.float32, getattr(out, "power", None)) if want_power else None
+        # (an output that is wanted is never a null pointer, not even with no frame to write)
+        u8 = lambda a: None if a is None else C.cast(C.c_void_p(a.ctypes.data or 16), _u8p)
+        _check(call(n_blocks, C.byref(w), u8(image), u8(big), None if power is None else C.cast(C.c_void_p(power.ctypes.data or 16), _f32p)),
+               where)
+        return WatchResult(image, big, power, next_first)
+
+    def watch_blocks(self, wire, rows: int, cols: int, first: int = 0, every: int = 1, out_rows: int = 0, out_cols: int = 0,
+                     d_colormap_ptr: int = 0, flip: bool = False, stride: int = DATAGRAM_BYTES, want_image: bool = True,
+                     want_power: bool = False, out: Optional[WatchResult] = None) -> WatchResult:
+        """Watch a run of consecutive blocks of wire datagrams (as process_blocks takes them): every block is appended to the
+        ring, blocks first, first + every, ... are swept and shown -- the compact image [rows, cols], with out_rows / out_cols the
+        large one (upscaled, through the [256, 3] device colour table when d_colormap_ptr, mirrored when flip), on request the
+        powers (awpu_hip_watch_blocks).  -> WatchResult; pass its .next_first as `first` of the call that continues the run, and
+        the result itself as `out` when its arrays may be written again (a writer that is done with a chunk's frames: 3 MiB per
+        1024 x 1024 colour frame are then not allocated and paged in anew for every call)."""
+        buf = np.frombuffer(wire, dtype=np.uint8)
+        if stride < DATAGRAM_BYTES or buf.size % (256 * stride) or buf.size == 0:
+            raise ValueError(f"wire must be a whole number of blocks of 256 datagrams {stride} bytes apart")
+        return self._watch(lambda *rest: self._lib.awpu_hip_watch_blocks(self._h, buf.ctypes.data_as(C.c_void_p), stride, *rest),
+                           "awpu_hip_watch_blocks", buf.size // (256 * stride), first, every, rows, cols, out_rows, out_cols,
+                           d_colormap_ptr, flip, want_image, want_power, out)
+
+    def watch_samples(self, samples: np.ndarray, rows: int, cols: int, first: int = 0, every: int = 1, out_rows: int = 0,
+                      out_cols: int = 0, d_colormap_ptr: int = 0, flip: bool = False, want_image: bool = True,
+                      want_power: bool = False, out: Optional[WatchResult] = None) -> WatchResult:
+        """The same from unpacked samples [n_streams, N] (N a multiple of 256, oldest first) (awpu_hip_watch_samples)."""
+        samples = np.ascontiguousarray(samples, np.float32)
+        if samples.ndim != 2 or samples.shape[0] != self.cfg.n_streams or samples.shape[1] % 256 or samples.shape[1] == 0:
+            raise ValueError(f"samples must be [{self.cfg.n_streams}, N] with N a positive multiple of 256")
+        return self._watch(lambda *rest: self._lib.awpu_hip_watch_samples(self._h, _f32(samples), samples.shape[1], *rest),
+                           "awpu_hip_watch_samples", samples.shape[1] // 256, first, every, rows, cols, out_rows, out_cols,
+                           d_colormap_ptr, flip, want_image, want_power, out)
+
+    def watch_samples_device(self, d_samples_ptr: int, pitch: int, n_blocks: int, rows: int, cols: int, first: int = 0, every: int = 1,
+                             d_image_ptr: int = 0, d_big_ptr: int = 0, d_power_ptr: int = 0, out_rows: int = 0, out_cols: int = 0,
+                             d_colormap_ptr: int = 0, flip: bool = False, stream: int = 0) -> int:
+        """The same on device pointers (samples [n_streams, pitch]; image [n_frames, rows * cols], big [n_frames, out_rows,
+        out_cols (, 3)], power [n_frames, pixels], each or 0) on `stream`; asynchronous.  -> next_first
+        (awpu_hip_watch_samples_device)."""
+        w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(d_colormap_ptr))
+        _check(self._lib.awpu_hip_watch_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, C.byref(w),
+                                                       C.c_void_p(d_image_ptr), C.c_void_p(d_big_ptr), C.c_void_p(d_power_ptr),
+                                                       C.c_void_p(stream)), "awpu_hip_watch_samples_device")
+        return watch_count(n_blocks, first, every)[1]
 
     def set_fir_table(self, coeffs: np.ndarray) -> None:
         """The caller's [101, 8] coefficient table of the FIR variant (src/dsp/filter.h:10-112)."""

@@ -5,6 +5,7 @@
 #include "awpu_hip_blocks.h"
 #include "awpu_hip_listen.h"
 #include "awpu_hip_track.h"
+#include "awpu_hip_watch.h"
 
 #include <hip/hip_runtime.h>
 
@@ -14,6 +15,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <new>
 #include <string>
 #include <array>
@@ -23,6 +25,7 @@
 
 #include "block_kernels.h"
 #include "das_kernels.h"
+#include "watch_kernels.h"
 
 namespace {
 
@@ -139,6 +142,7 @@ struct awpu_hip {
     size_t display_cap = 0;             // bytes
     awpu::ResizeTap *d_taps = nullptr;  // column + row taps of the display upscale, for taps_key
     int taps_key[4] = {0, 0, 0, 0};     // {srows, scols, drows, dcols}
+    int taps_band_rows = 0;             // ... and the most compact rows a 16-row tile of the large image reads (watch_kernels.h)
     float *d_pack = nullptr;            // [pairs][usable][wp][2] sample-interleaved frame pairs
     size_t pack_cap = 0;                // floats
     unsigned char *d_datagrams = nullptr;  // staging for one block of wire datagrams
@@ -230,6 +234,12 @@ struct awpu_hip {
     hipStream_t listen_stream = nullptr;
     // ev_listened[b]: the listen kernels have read d_blk_hist[b] (and written d_listen_out[b]); ev_listen_out[b]: h_listen_out[b] holds it
     hipEvent_t ev_listened[2] = {nullptr, nullptr}, ev_listen_out[2] = {nullptr, nullptr};
+
+    // watching such runs (awpu_hip_watch.h): piece i's peaks, compact images and (host forms) large images in d_watch[i & 1]; the
+    // host forms bring the images back through pinned h_watch[i & 1].  The events are those of the runs above: ev_blk_swept[b] is
+    // recorded behind the display kernels, ev_blk_out[b] behind the images' way back.
+    uint8_t *d_watch[2] = {nullptr, nullptr}, *h_watch[2] = {nullptr, nullptr};
+    size_t watch_cap = 0, watch_host_cap = 0;  // bytes per buffer
 
     awpu_hip_stats stats{};
     std::string last_error;                  // awpu_hip_last_error_of
@@ -425,6 +435,12 @@ void release_device(awpu_hip *h) {
         h->h_listen_out[b] = nullptr;
     }
     h->listeners_cap = h->listen_out_cap = 0;
+    for (int b = 0; b < 2; b++) {
+        dev_free(h->d_watch[b]);
+        if (h->h_watch[b]) (void) hipHostFree(h->h_watch[b]);
+        h->h_watch[b] = nullptr;
+    }
+    h->watch_cap = h->watch_host_cap = 0;
     for (int b = 0; b < 2; b++) {
         if (b == 0) {
             if (h->h_live_in) (void) hipHostFree(h->h_live_in);
@@ -3197,9 +3213,12 @@ int ensure_listen_buffers(awpu_hip *h, const ListenRun &ls, int piece, bool host
 }
 
 // device buffers for pieces of at most `piece` frames (and, for the host forms, the pinned staging and the second stream)
-int ensure_blk_buffers(awpu_hip *h, const BlockRun &src, int piece, int width, bool sweep) {
+// (a watch run's history and staging hold hist_blocks / in_blocks blocks for a piece of `piece` frames: 0 = one per frame)
+int ensure_blk_buffers(awpu_hip *h, const BlockRun &src, int piece, int width, bool sweep, int hist_blocks = 0, int in_blocks = 0) {
     const size_t S = (size_t) h->cfg.n_streams;
-    const size_t hist_floats = S * (awpu::kBlockPrefix + (size_t) awpu::kSamples * piece);
+    if (hist_blocks < 1) hist_blocks = piece;
+    if (in_blocks < 1) in_blocks = piece;
+    const size_t hist_floats = S * (awpu::kBlockPrefix + (size_t) awpu::kSamples * hist_blocks);
     if (h->blk_hist_cap < hist_floats) {
         for (int b = 0; b < 2; b++) dev_free(h->d_blk_hist[b]);
         h->blk_hist_cap = 0;
@@ -3215,7 +3234,7 @@ int ensure_blk_buffers(awpu_hip *h, const BlockRun &src, int piece, int width, b
     }
     if (!h->ev_blk_ring) AWPU_HIP_TRY(hipEventCreateWithFlags(&h->ev_blk_ring, hipEventDisableTiming));
     if (src.device) return AWPU_OK;
-    const size_t in_bytes = (size_t) awpu::kSamples * piece * (src.wire ? (size_t) AWPU_DATAGRAM_BYTES : S * sizeof(float));
+    const size_t in_bytes = (size_t) awpu::kSamples * in_blocks * (src.wire ? (size_t) AWPU_DATAGRAM_BYTES : S * sizeof(float));
     if (h->blk_in_cap < in_bytes) {
         for (int b = 0; b < 2; b++) {
             dev_free(h->d_blk_in[b]);
@@ -3606,15 +3625,10 @@ int awpu_hip_heatmap_u8_device(awpu_hip_t *h, const float *d_power, int32_t n, i
     return AWPU_OK;
 }
 
-int awpu_hip_upscale_u8_device(awpu_hip_t *h, const uint8_t *d_pix, int32_t rows, int32_t cols, int32_t batch,
-                               const uint8_t *d_colormap, uint8_t *d_out, int32_t out_rows, int32_t out_cols,
-                               void *stream) {
-    if (h && !h->parts.empty()) h = h->parts[0];  // not pixel-sharded: a device group answers with its first device
-    AWPU_CTX(h);
-    if (!h || !d_pix || !d_out || rows < 1 || cols < 1 || batch < 1 || batch > 65535) return invalid("bad argument");
-    if (out_rows < rows || out_cols < cols || out_rows > 65535) return invalid("upscale only: out >= in, out_rows <= 65535");
-    AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+namespace {
+
+// h->d_taps = the column and row taps of rows x cols -> out_rows x out_cols, rebuilt when the shape changes
+int ensure_taps(awpu_hip *h, int rows, int cols, int out_rows, int out_cols, hipStream_t s) {
     const int key[4] = {rows, cols, out_rows, out_cols};
     if (!h->d_taps || std::memcmp(key, h->taps_key, sizeof(key)) != 0) {
         std::vector<awpu::ResizeTap> taps((size_t) out_cols + out_rows);
@@ -3626,7 +3640,23 @@ int awpu_hip_upscale_u8_device(awpu_hip_t *h, const uint8_t *d_pix, int32_t rows
         AWPU_HIP_TRY(hipMalloc(&h->d_taps, taps.size() * sizeof(awpu::ResizeTap)));
         AWPU_HIP_TRY(hipMemcpy(h->d_taps, taps.data(), taps.size() * sizeof(awpu::ResizeTap), hipMemcpyHostToDevice));
         std::memcpy(h->taps_key, key, sizeof(key));
+        h->taps_band_rows = awpu::watch_band_rows(taps.data() + out_cols, rows, out_rows);
     }
+    return AWPU_OK;
+}
+
+}  // namespace
+
+int awpu_hip_upscale_u8_device(awpu_hip_t *h, const uint8_t *d_pix, int32_t rows, int32_t cols, int32_t batch,
+                               const uint8_t *d_colormap, uint8_t *d_out, int32_t out_rows, int32_t out_cols,
+                               void *stream) {
+    if (h && !h->parts.empty()) h = h->parts[0];  // not pixel-sharded: a device group answers with its first device
+    AWPU_CTX(h);
+    if (!h || !d_pix || !d_out || rows < 1 || cols < 1 || batch < 1 || batch > 65535) return invalid("bad argument");
+    if (out_rows < rows || out_cols < cols || out_rows > 65535) return invalid("upscale only: out >= in, out_rows <= 65535");
+    AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+    if (int rc = ensure_taps(h, rows, cols, out_rows, out_cols, s)) return rc;
     AWPU_HIP_TRY(awpu::launch_upscale(d_pix, rows, cols, batch, h->d_taps, d_colormap, d_out, out_rows, out_cols, s));
     return AWPU_OK;
 }
@@ -3659,6 +3689,326 @@ int awpu_hip_resize_linear_u8(const uint8_t *pix, int32_t rows, int32_t cols, ui
             out[(size_t) dy * out_cols + dx] = awpu::resize_combine(sums[dx], sums[(size_t) out_cols + dx], ty.w0, ty.w1);
     }
     return AWPU_OK;
+}
+
+// ---- watching runs of blocks (include/awpu_hip_watch.h; kernels in watch_kernels.hip) ------------------------------------------
+// The run-of-blocks pipeline above with two differences.  A piece is nf SHOWN frames (awpu_hip_process's pieces of the chunks of
+// shown frames), and its history holds only the blocks its snapshots read (watch_kernels.h: 4 + min(every, 4) * (nf - 1) slots
+// of 256 samples), each piece's formed on its own -- blocks from before the call out of the ring's snapshot, the rest staged and
+// uploaded -- instead of continuing the piece before it.  And behind a piece's sweep comes its display step: launch_heatmap for
+// the whole piece, then the large image, both on the sweep's stream; the host forms bring images and powers back through pinned
+// memory on copy_stream while the next piece is swept.  The ring is written once, at the end, from the last four blocks of the
+// call: the tail of the last piece's history when the last block is shown, a four-slot history of its own otherwise.
+namespace {
+
+struct WatchRun {
+    awpu_watch_t w{};
+    int n_frames = 0;
+    uint8_t *image = nullptr, *big = nullptr;  // host memory in the host forms, device memory in the device form
+    float *power = nullptr;
+};
+
+// fn(lo, hi) over [0, n) by up to 8 threads when `bytes` (what the whole range copies) is 1 MB and more; like stage_blocks
+void parallel_ranges(size_t n, size_t bytes, const std::function<void(size_t, size_t)> &fn) {
+    const size_t n_threads = std::min<size_t>({8, n, bytes >> 20});
+    if (n_threads < 2) {
+        fn((size_t) 0, n);
+        return;
+    }
+    std::vector<std::thread> pool;
+    size_t k = 1;
+    try {
+        pool.reserve(n_threads - 1);
+        for (; k < n_threads; k++) pool.emplace_back(fn, n * k / n_threads, n * (k + 1) / n_threads);
+    } catch (...) {  // (std::system_error must not cross the C ABI)
+    }
+    fn((size_t) 0, n / n_threads);
+    if (k < n_threads) fn(n * k / n_threads, n);
+    for (auto &th : pool) th.join();
+}
+
+void parallel_copy(void *dst, const void *src, size_t bytes) {
+    parallel_ranges(bytes >> 16, bytes, [&](size_t lo, size_t hi) {  // 64 KB grains, the rest with the last
+        const size_t from = lo << 16, to = hi == (bytes >> 16) ? bytes : hi << 16;
+        std::memcpy(static_cast<unsigned char *>(dst) + from, static_cast<const unsigned char *>(src) + from, to - from);
+    });
+    if ((bytes >> 16) == 0) std::memcpy(dst, src, bytes);
+}
+
+// slots [q, slots) of a piece's history (watch_kernels.h) into pinned h_blk_in[b]: tight datagrams, or rows of 256 * (slots - q)
+void stage_watch(awpu_hip *h, const BlockRun &src, int b0, int every, int q, int slots, int b) {
+    unsigned char *dst = static_cast<unsigned char *>(h->h_blk_in[b]);
+    const int m = std::min(every, 4), ns = slots - q;
+    const size_t S = (size_t) h->cfg.n_streams, block_bytes = (size_t) awpu::kSamples * (src.wire ? (size_t) AWPU_DATAGRAM_BYTES : S * sizeof(float));
+    parallel_ranges((size_t) ns, block_bytes * ns, [&](size_t lo, size_t hi) {
+        for (size_t k = lo; k < hi; k++) {
+            const size_t blk = (size_t) awpu::watch_slot_block(q + (int) k, b0, every, m);
+            if (src.wire) {
+                const unsigned char *from = src.wire + blk * awpu::kSamples * src.stride;
+                unsigned char *to = dst + k * awpu::kSamples * AWPU_DATAGRAM_BYTES;
+                if (src.stride == AWPU_DATAGRAM_BYTES) {
+                    std::memcpy(to, from, (size_t) awpu::kSamples * AWPU_DATAGRAM_BYTES);
+                } else {
+                    for (int i = 0; i < awpu::kSamples; i++) std::memcpy(to + (size_t) i * AWPU_DATAGRAM_BYTES, from + (size_t) i * src.stride, AWPU_DATAGRAM_BYTES);
+                }
+            } else {
+                for (size_t s = 0; s < S; s++)
+                    std::memcpy(dst + ((s * ns + k) * awpu::kSamples) * sizeof(float), src.samples + s * src.pitch + blk * awpu::kSamples,
+                                awpu::kSamples * sizeof(float));
+            }
+        }
+    });
+}
+
+int ensure_watch_buffers(awpu_hip *h, size_t bytes, bool host) {
+    if (h->watch_cap < bytes) {
+        for (int b = 0; b < 2; b++) dev_free(h->d_watch[b]);
+        h->watch_cap = 0;
+        for (int b = 0; b < 2; b++) AWPU_HIP_TRY(hipMalloc(&h->d_watch[b], bytes));
+        h->watch_cap = bytes;
+    }
+    if (host && h->watch_host_cap < bytes) {
+        for (int b = 0; b < 2; b++) {
+            if (h->h_watch[b]) (void) hipHostFree(h->h_watch[b]);
+            h->h_watch[b] = nullptr;
+        }
+        h->watch_host_cap = 0;
+        for (int b = 0; b < 2; b++) AWPU_HIP_TRY(hipHostMalloc(&h->h_watch[b], bytes, hipHostMallocDefault));
+        h->watch_host_cap = bytes;
+    }
+    return AWPU_OK;
+}
+
+int run_watch(awpu_hip *h, const BlockRun &src, int n_blocks, const WatchRun &wr, hipStream_t user) {
+    if (!h->parts.empty()) return fail(AWPU_ERR_STATE, "a device group does not take runs of blocks");
+    if (h->in_flight) return fail(AWPU_ERR_STATE, "an awpu_hip_process_async call is in flight on this handle: awpu_hip_wait first");
+    const awpu_hip_cfg &c = h->cfg;
+    const awpu_watch_t &w = wr.w;
+    if (c.hist != AWPU_HIST) return invalid("runs of blocks need hist 1024");
+    if (src.wire && c.n_streams > 256) return invalid("the wire carries at most 256 streams");
+    if (c.pixel_count != c.n_pixels) return invalid("the display step needs the whole grid on this handle");
+    if ((long long) w.rows * w.cols != c.n_pixels) return invalid("rows x cols must be the grid");
+    const int n_frames = wr.n_frames, chunk = std::max(1, std::min<int>(n_frames, c.max_batch));
+    int rc = check_ready(h, chunk);
+    if (rc != AWPU_OK) return rc;
+    std::vector<std::pair<int, int>> pieces;  // (first frame, frames): every chunk of shown frames in awpu_hip_process's pieces
+    int piece_max = 1;
+    for (int c0 = 0; c0 < n_frames; c0 += chunk) {
+        const int nc = std::min(chunk, n_frames - c0), piece = host_piece(nc);
+        for (int k0 = 0; k0 < nc; k0 += piece) {
+            pieces.emplace_back(c0 + k0, std::min(piece, nc - k0));
+            piece_max = std::max(piece_max, pieces.back().second);
+        }
+    }
+    const int n_pieces = (int) pieces.size();
+    const bool compact = h->compact_hist > 0;
+    const int width = compact ? h->compact_hist : AWPU_HIST, lo = compact ? h->wstart : 0;
+    const bool host = !src.device;
+    const int S = c.n_streams, m = std::min(w.every, 4), slots_max = awpu::watch_slots(w.every, piece_max), pitch = awpu::kSamples * slots_max;
+    const size_t P = (size_t) c.pixel_count, big_bytes = (size_t) w.out_rows * w.out_cols * (w.d_colormap ? 3 : 1);
+    const bool want_small = wr.image || wr.big;
+    // the last block of the call shown: the ring's new snapshot is the tail of the last piece's history
+    const bool own_tail = n_frames == 0 || w.first + (n_frames - 1) * w.every != n_blocks - 1;
+    const size_t small_off = align16(sizeof(float) * piece_max), big_off = small_off + align16((size_t) piece_max * P);
+    hipStream_t sw = host ? h->stream : (user ? user : h->stream);  // cut, sweep, display
+    rc = ensure_ring(h);
+    if (rc == AWPU_OK) rc = ensure_blk_buffers(h, src, piece_max, width, true, slots_max - 3, slots_max);
+    if (rc == AWPU_OK && !host && !wr.power) rc = ensure_power(h, (size_t) piece_max * P);
+    if (rc == AWPU_OK && want_small) rc = ensure_watch_buffers(h, big_off + (host && wr.big ? (size_t) piece_max * big_bytes : 0), host);
+    if (rc == AWPU_OK && wr.big) rc = ensure_taps(h, w.rows, w.cols, w.out_rows, w.out_cols, sw);
+    if (rc != AWPU_OK) return rc;
+    hipStream_t up = host ? h->copy_stream : sw;  // upload and history
+    const bool keep_timing = h->timing;
+    const bool time_it = keep_timing && host && n_pieces > 0;
+    if (!time_it) h->timing = false;  // the device form is asynchronous: the caller times its own stream; nothing swept, nothing timed
+    // host forms: piece j's results, in pinned memory once ev_blk_out[j & 1] has passed, to the caller's rows
+    const auto deliver = [&](int j) -> int {
+        const int b = j & 1, j0 = pieces[j].first, nf = pieces[j].second;
+        AWPU_HIP_TRY(hipEventSynchronize(h->ev_blk_out[b]));
+        if (wr.power) std::memcpy(wr.power + (size_t) j0 * P, h->h_blk_out[b], (size_t) nf * P * sizeof(float));
+        if (wr.image) std::memcpy(wr.image + (size_t) j0 * P, h->h_watch[b] + small_off, (size_t) nf * P);
+        if (wr.big) parallel_copy(wr.big + (size_t) j0 * big_bytes, h->h_watch[b] + big_off, (size_t) nf * big_bytes);
+        return AWPU_OK;
+    };
+    // host forms: piece j's results into pinned memory behind the kernels that write them
+    const auto fetch = [&](int j) -> int {
+        const int b = j & 1, nf = pieces[j].second;
+        AWPU_HIP_TRY(hipStreamWaitEvent(up, h->ev_blk_swept[b], 0));
+        if (wr.power)
+            AWPU_HIP_TRY(hipMemcpyAsync(h->h_blk_out[b], h->d_power + (size_t) b * piece_max * P, (size_t) nf * P * sizeof(float), hipMemcpyDeviceToHost, up));
+        if (wr.image) AWPU_HIP_TRY(hipMemcpyAsync(h->h_watch[b] + small_off, h->d_watch[b] + small_off, (size_t) nf * P, hipMemcpyDeviceToHost, up));
+        if (wr.big) AWPU_HIP_TRY(hipMemcpyAsync(h->h_watch[b] + big_off, h->d_watch[b] + big_off, (size_t) nf * big_bytes, hipMemcpyDeviceToHost, up));
+        AWPU_HIP_TRY(hipEventRecord(h->ev_blk_out[b], up));
+        return AWPU_OK;
+    };
+    const auto body = [&]() -> int {
+        // whatever is queued on the handle's stream comes first: the upload side reads the ring and rewrites the histories
+        if (up != h->stream) {
+            AWPU_HIP_TRY(hipEventRecord(h->ev_blk_ring, h->stream));
+            AWPU_HIP_TRY(hipStreamWaitEvent(up, h->ev_blk_ring, 0));
+        }
+        const float *snapshot = h->d_ring + h->ring_pos;  // blocks -4 .. -1 of the call
+        int fetched = 0, delivered = 0;
+        for (int i = 0; i < n_pieces + (own_tail ? 1 : 0); i++) {
+            const bool tail = i == n_pieces;  // no frame: the last four blocks of the call, for the ring
+            const int b = i & 1, j0 = tail ? 0 : pieces[i].first, nf = tail ? 1 : pieces[i].second;
+            const int b0 = tail ? n_blocks - 1 : w.first + j0 * w.every, every = tail ? 1 : w.every;
+            const int slots = awpu::watch_slots(every, nf), q = std::max(0, std::min(3 - b0, 4));  // q slots hold blocks from before the call
+            float *hist = h->d_blk_hist[b];
+            if (host) {
+                if (i >= 2) AWPU_HIP_TRY(hipEventSynchronize(h->ev_blk_in[b]));  // piece i-2's upload out of h_blk_in[b] is over
+                stage_watch(h, src, b0, every, q, slots, b);
+                const size_t bytes = (size_t) awpu::kSamples * (slots - q) * (src.wire ? (size_t) AWPU_DATAGRAM_BYTES : S * sizeof(float));
+                AWPU_HIP_TRY(hipMemcpyAsync(h->d_blk_in[b], h->h_blk_in[b], bytes, hipMemcpyHostToDevice, up));
+                AWPU_HIP_TRY(hipEventRecord(h->ev_blk_in[b], up));
+                if (i >= 2) AWPU_HIP_TRY(hipStreamWaitEvent(up, h->ev_blk_cut[b], 0));  // piece i-2's windows are cut out of d_blk_hist[b]
+                if (q > 0) AWPU_HIP_TRY(awpu::launch_watch_gather(nullptr, 0, snapshot, b0, every, S, hist, pitch, 0, q, up));
+                if (src.wire) {
+                    AWPU_HIP_TRY(awpu::launch_unpack_blocks(h->d_blk_in[b], slots - q, S, hist, pitch, awpu::kSamples * q, up));
+                } else {
+                    const long long n = (long long) awpu::kSamples * (slots - q);
+                    AWPU_HIP_TRY(awpu::launch_copy_rows(static_cast<const float *>(h->d_blk_in[b]), n, hist + awpu::kSamples * q, pitch, (int) n, S, up));
+                }
+                AWPU_HIP_TRY(hipEventRecord(h->ev_blk_hist[b], up));
+                AWPU_HIP_TRY(hipStreamWaitEvent(sw, h->ev_blk_hist[b], 0));
+            } else {
+                AWPU_HIP_TRY(awpu::launch_watch_gather(src.samples, src.pitch, snapshot, b0, every, S, hist, pitch, 0, slots, sw));
+            }
+            if (!tail) {
+                AWPU_HIP_TRY(awpu::launch_watch_cut(hist, pitch, S, nf, awpu::kSamples * m, lo, width, h->d_blk_frames, sw));
+                if (host) AWPU_HIP_TRY(hipEventRecord(h->ev_blk_cut[b], sw));
+                if (time_it && i == 0) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, sw));
+                float *d_pow = host ? h->d_power + (size_t) b * piece_max * P : (wr.power ? wr.power + (size_t) j0 * P : h->d_power);
+                h->timing = false;
+                rc = launch(h, h->d_blk_frames, nf, d_pow, sw, compact ? kCompact : kFull);
+                h->timing = time_it;
+                if (rc != AWPU_OK) return rc;
+                if (want_small) {
+                    uint8_t *scratch = h->d_watch[host ? b : 0];
+                    uint8_t *d_small = host || !wr.image ? scratch + small_off : wr.image + (size_t) j0 * P;
+                    AWPU_HIP_TRY(awpu::launch_heatmap(d_pow, (int) P, nf, reinterpret_cast<float *>(scratch), false, d_small, sw));
+                    if (wr.big)
+                        AWPU_HIP_TRY(awpu::launch_watch_upscale(d_small, w.rows, w.cols, nf, h->d_taps, h->taps_band_rows, w.d_colormap, w.flip != 0,
+                                                                host ? scratch + big_off : wr.big + (size_t) j0 * big_bytes, w.out_rows,
+                                                                w.out_cols, sw));
+                }
+                if (host) AWPU_HIP_TRY(hipEventRecord(h->ev_blk_swept[b], sw));
+            }
+            if (host) {
+                if (i >= 1 && fetched < n_pieces) {  // piece i-1's results go back into pinned memory while piece i is swept ...
+                    rc = fetch(fetched++);
+                    if (rc != AWPU_OK) return rc;
+                }
+                if (i >= 2 && delivered < n_pieces) {  // ... and piece i-2's go to the caller before its pinned buffers are written again
+                    rc = deliver(delivered++);
+                    if (rc != AWPU_OK) return rc;
+                }
+            }
+        }
+        if (time_it) AWPU_HIP_TRY(hipEventRecord(h->ev_end, sw));
+        // the ring as n_blocks ingests leave it: its snapshot = the last four blocks of the call
+        const int pos = (int) ((h->ring_pos + (long long) awpu::kSamples * n_blocks) % AWPU_HIST);
+        const float *last_hist = h->d_blk_hist[(own_tail ? n_pieces : n_pieces - 1) & 1];
+        const int last = own_tail ? 0 : awpu::kSamples * (awpu::watch_slots(w.every, pieces.back().second) - 4);
+        AWPU_HIP_TRY(awpu::launch_ring_write(last_hist, pitch, last, S, h->d_ring, pos, sw));
+        h->ring_pos = pos;
+        if (!host) {
+            if (sw != h->stream) {  // later calls on the ring (the handle's stream) come after this one
+                AWPU_HIP_TRY(hipEventRecord(h->ev_blk_ring, sw));
+                AWPU_HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_blk_ring, 0));
+            }
+            return AWPU_OK;
+        }
+        while (fetched < n_pieces) {
+            rc = fetch(fetched++);
+            if (rc != AWPU_OK) return rc;
+        }
+        while (delivered < n_pieces) {
+            rc = deliver(delivered++);
+            if (rc != AWPU_OK) return rc;
+        }
+        AWPU_HIP_TRY(hipStreamSynchronize(up));
+        return wait_and_time(h);
+    };
+    rc = body();
+    h->timing = keep_timing;
+    if (rc != AWPU_OK && host) {  // nothing of the call may still read the caller's or the handle's buffers
+        (void) hipStreamSynchronize(h->copy_stream);
+        (void) hipStreamSynchronize(h->stream);
+    }
+    return rc;
+}
+
+// the checks of a watch call that read no handle; then the run
+int watch_run(awpu_hip *h, const BlockRun &src, int n_blocks, const awpu_watch_t *w, uint8_t *image, uint8_t *big, float *power, hipStream_t user) {
+    if (!w) return invalid("null argument");
+    if (!image && !big && !power) return invalid("no output asked for");
+    if (w->every < 1 || w->every > AWPU_WATCH_MAX_EVERY) return invalid("every outside [1, 1024]");
+    if (w->first < 0) return invalid("first below 0");
+    if (w->flip != 0 && w->flip != 1) return invalid("flip is 0 or 1");
+    if (w->rows < 1 || w->cols < 1) return invalid("rows and cols must be positive");
+    if (big && (w->out_rows < w->rows || w->out_cols < w->cols)) return invalid("upscale only: out >= in");
+    if (big && w->cols > AWPU_WATCH_MAX_COLS) return invalid("compact image wider than AWPU_WATCH_MAX_COLS");
+    WatchRun wr;
+    wr.w = *w;
+    int32_t next_first = 0;
+    if (int rc = awpu_hip_watch_count(n_blocks, w->first, w->every, &wr.n_frames, &next_first)) return rc;
+    wr.image = image;
+    wr.big = big;
+    wr.power = power;
+    AWPU_CTX(h);
+    return run_watch(h, src, n_blocks, wr, user);
+}
+
+}  // namespace
+
+int awpu_hip_watch_count(int32_t n_blocks, int32_t first, int32_t every, int32_t *n_frames, int32_t *next_first) {
+    if (!n_frames || !next_first) return invalid("null argument");
+    if (n_blocks < 1) return invalid("n_blocks below 1");
+    if (first < 0) return invalid("first below 0");
+    if (every < 1) return invalid("every below 1");
+    const int64_t shown = first >= n_blocks ? 0 : ((int64_t) n_blocks - first + every - 1) / every;
+    *n_frames = (int32_t) shown;
+    *next_first = (int32_t) (first + shown * every - n_blocks);
+    return AWPU_OK;
+}
+
+int awpu_hip_watch_blocks(awpu_hip_t *h, const void *datagrams, int32_t stride_bytes, int32_t n_blocks, const awpu_watch_t *w,
+                          uint8_t *image, uint8_t *big_image, float *power) {
+    // (arguments first: none of these reads the handle)
+    if (!h) return invalid("null handle");
+    if (!datagrams) return invalid("null argument");
+    if (n_blocks < 1) return invalid("n_blocks below 1");
+    if (stride_bytes < AWPU_DATAGRAM_BYTES) return invalid("datagram stride below 1032 bytes");
+    BlockRun src;
+    src.wire = static_cast<const unsigned char *>(datagrams);
+    src.stride = stride_bytes;
+    return watch_run(h, src, n_blocks, w, image, big_image, power, nullptr);
+}
+
+int awpu_hip_watch_samples(awpu_hip_t *h, const float *samples, int64_t pitch, int32_t n_blocks, const awpu_watch_t *w, uint8_t *image,
+                           uint8_t *big_image, float *power) {
+    if (!h) return invalid("null handle");
+    if (!samples) return invalid("null argument");
+    if (n_blocks < 1) return invalid("n_blocks below 1");
+    if (pitch < (int64_t) awpu::kSamples * n_blocks) return invalid("pitch below 256 * n_blocks");
+    BlockRun src;
+    src.samples = samples;
+    src.pitch = pitch;
+    return watch_run(h, src, n_blocks, w, image, big_image, power, nullptr);
+}
+
+int awpu_hip_watch_samples_device(awpu_hip_t *h, const float *d_samples, int64_t pitch, int32_t n_blocks, const awpu_watch_t *w,
+                                  uint8_t *d_image, uint8_t *d_big_image, float *d_power, void *stream) {
+    if (!h) return invalid("null handle");
+    if (!d_samples) return invalid("null argument");
+    if (n_blocks < 1) return invalid("n_blocks below 1");
+    if (pitch < (int64_t) awpu::kSamples * n_blocks) return invalid("pitch below 256 * n_blocks");
+    BlockRun src;
+    src.samples = d_samples;
+    src.pitch = pitch;
+    src.device = true;
+    return watch_run(h, src, n_blocks, w, d_image, d_big_image, d_power, static_cast<hipStream_t>(stream));
 }
 
 namespace {

@@ -1087,15 +1087,13 @@ __device__ __forceinline__ f2 pixel_pair_partial_exact(const f2 (&o)[4], int lan
     }
     return sum;
 }
-// (das_exact_pair_kernel and the FIR8 plane kernel keep one wave sum per pixel and frame: through store_powers8 -- per-lane
-// selects of the wave's four pixel indices -- the joint reduction measured 0.2-0.5 % SLOWER there, gpurun_out/epi3ab, round 4;
-// das_exact_quad_kernel computes the lane's pixel from row and column like das_quad_kernel and gains 0.65 %, gpurun_out/exq1)
-__device__ __forceinline__ f2 finish_pixel_pair_exact(const f2 (&o)[4], int lane) {
-    f2 sum = pixel_pair_partial_exact(o, lane);
-    sum.x = wave_sum(sum.x);
-    sum.y = wave_sum(sum.y);
-    return sum;
-}
+// (The FIR8 plane kernel keeps one wave sum per pixel and frame: through store_powers8 -- per-lane selects of the wave's four
+// pixel indices -- the joint reduction measured 0.2-0.5 % SLOWER there and in das_exact_pair_kernel, round 4;
+// das_exact_quad_kernel computes the lane's pixel from row and column like das_quad_kernel and gains 0.65 %.
+// das_exact_pair_kernel takes store_powers8 all the same: wave_sum adds a wave's 64 partial sums in another order than
+// wave_sum8, and every reference-order kernel must give a frame the same bits -- a frame swept alone (das_exact_ndp_kernel /
+// das_exact_ndh_kernel) and in a batch that falls to this kernel differed by up to 2.3e-7 relative on grids whose quads do not
+// share, e.g. 64 mics on 16 x 16, which broke what awpu_hip_blocks.h and awpu_hip_watch.h promise of the exact mode.)
 
 __global__ __launch_bounds__(1024, 4) void das_exact_pair_kernel(ExactPairArgs a) {
     constexpr int PPW = 4;
@@ -1199,12 +1197,11 @@ __global__ __launch_bounds__(1024, 4) void das_exact_pair_kernel(ExactPairArgs a
                 if (2 * pair + 1 < a.batch) a.sums[((size_t) (2 * pair + 1) * a.pixel_count + p) * kSamples + lane + 64 * k] = acc[pp][k].y;
             }
         }
-        const f2 sum = finish_pixel_pair_exact(acc[pp], lane);
-        if (lane == 0 && live[pp]) {
-            a.power[(size_t) (2 * pair) * a.pixel_count + p] = sum.x / norm;
-            if (2 * pair + 1 < a.batch) a.power[(size_t) (2 * pair + 1) * a.pixel_count + p] = sum.y / norm;
-        }
     }
+    // the wave_sum8 tree of the other reference-order kernels: the same bits for a frame whichever of them sweeps it
+    const f2 partial[4] = {pixel_pair_partial_exact(acc[0], lane), pixel_pair_partial_exact(acc[1], lane),
+                           pixel_pair_partial_exact(acc[2], lane), pixel_pair_partial_exact(acc[3], lane)};
+    store_powers8(partial, pix, live, pair, a.batch, a.pixel_count, norm, a.power, lane);
 }
 
 // ---------------------------------------------------------------------------------------

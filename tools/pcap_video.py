@@ -1,0 +1,230 @@
+#!/usr/bin/env python3
+"""The video of a recorded capture: what the reference's GUI loop records with key `r` (src/aw_control_unit/aw_control_unit.cpp:
+293-378: populateHeatmap, cv::resize, cv::applyColorMap, the optional cv::flip, videoWriter.write) for a .pcap of FPGA datagrams,
+in batched passes on the device (Engine.watch_blocks, include/awpu_hip_watch.h).  The capture is read by tools/pcap_heatmaps.py's
+reader (counter gaps reported, not repaired).
+
+  tools/pcap_video.py recording.pcap --port 21844 --cols 100 --every 3 --size 1024 --out heatmap
+
+Every block is ingested; every --every'th is swept and shown.  The default 3 gives 48828 / (256 * 3) = 63.6 frames per second, the
+nearest to the 60 the reference opens its writer with.  --chunk blocks go to the engine per call, each call continuing with the
+`next_first` of the one before, so a long capture streams through bounded memory.
+
+Output.  The reference writes MJPG; there is no JPEG encoder here, so the frames are written UNCOMPRESSED: AVI 1.0 files with one
+BGR24 `DIB ` stream (rows bottom-up, padded to 4 bytes, one `00db` chunk and one idx1 entry per frame, the exact frame rate as the
+rational dwRate / dwScale = 48828 / (256 * every), reduced), written with `struct` alone and split into numbered parts
+OUT.000.avi, OUT.001.avi, ... each below 1 GiB (AVI 1.0 stops at the RIFF size field).  --raw writes headerless BGR24 frames, rows
+top-down, into OUT.bgr instead (e.g. for `ffmpeg -f rawvideo -pix_fmt bgr24 -s 1024x1024 -r 48828/768 -i OUT.bgr`).
+
+Colours.  OpenCV's COLORMAP_JET / COLORMAP_OCEAN tables are not available here and equality with them is NOT claimed.  The tool
+builds a jet-like table of its own, piecewise linear in x = level / 255:
+    red = clip(1.5 - |4x - 3|),  green = clip(1.5 - |4x - 2|),  blue = clip(1.5 - |4x - 1|),   clip to [0, 1], times 255, rounded
+stored [256][3] in B, G, R order.  --gray shows level v as (v, v, v).  A caller with OpenCV passes its own [256][3] table to
+Engine.watch_blocks."""
+from __future__ import annotations
+
+import argparse
+import importlib
+import math
+import struct
+import sys
+from pathlib import Path
+
+import numpy as np
+
+SAMPLE_RATE, BLOCK = 48828, 256
+PART_LIMIT = (1 << 30) - 1  # bytes per AVI part, headers and index included
+
+
+def frame_rate(every: int):
+    """(dwRate, dwScale): 48828 / (256 * every) frames per second as a reduced fraction."""
+    g = math.gcd(SAMPLE_RATE, BLOCK * every)
+    return SAMPLE_RATE // g, BLOCK * every // g
+
+
+def jet_table() -> np.ndarray:
+    """The tool's own jet-like colour table [256][3], B G R (formula in the module docstring)."""
+    x = np.arange(256, dtype=np.float64) / 255.0
+    ramp = lambda centre: np.clip(1.5 - np.abs(4.0 * x - centre), 0.0, 1.0)
+    return np.rint(np.stack([ramp(1.0), ramp(2.0), ramp(3.0)], axis=1) * 255.0).astype(np.uint8)
+
+
+def gray_table() -> np.ndarray:
+    return np.repeat(np.arange(256, dtype=np.uint8)[:, None], 3, axis=1)
+
+
+class AviWriter:
+    """Uncompressed BGR24 AVI 1.0 files PREFIX.000.avi, PREFIX.001.avi, ...: a new part begins before one would pass `limit`
+    bytes.  write() takes a frame [height][width][3] uint8, B G R, rows top-down."""
+
+    HEADER = 12 + (12 + (8 + 56) + (12 + (8 + 56) + (8 + 40))) + 12  # RIFF, hdrl (avih, strl (strh, strf)), LIST movi
+
+    def __init__(self, prefix, width: int, height: int, every: int, limit: int = PART_LIMIT):
+        self.prefix, self.width, self.height, self.limit = str(prefix), width, height, limit
+        self.rate, self.scale = frame_rate(every)
+        self.row = (3 * width + 3) & ~3
+        self.frame_bytes = self.row * height
+        if self._size_with(1) > limit:
+            raise ValueError(f"one {width} x {height} frame does not fit a part of {limit} bytes")
+        self.paths, self.file, self.index = [], None, []
+
+    def _header(self, n_frames: int) -> bytes:
+        movi = 4 + n_frames * (8 + self.frame_bytes)
+        total = self.HEADER - 8 + n_frames * (8 + self.frame_bytes) + 8 + 16 * n_frames
+        avih = struct.pack("<14I", self.scale * 1000000 // self.rate, self.frame_bytes * self.rate // self.scale + 1, 0, 0x10, n_frames, 0, 1,
+                           self.frame_bytes, self.width, self.height, 0, 0, 0, 0)
+        strh = struct.pack("<4s4sIHHIIIIIIII4h", b"vids", b"DIB ", 0, 0, 0, 0, self.scale, self.rate, 0, n_frames, self.frame_bytes,
+                           0xFFFFFFFF, 0, 0, 0, self.width, self.height)
+        strf = struct.pack("<IiiHHIIiiII", 40, self.width, self.height, 1, 24, 0, self.frame_bytes, 0, 0, 0, 0)  # height > 0: bottom-up
+        strl = b"LIST" + struct.pack("<I", 4 + 8 + len(strh) + 8 + len(strf)) + b"strl" + b"strh" + struct.pack("<I", len(strh)) + strh + \
+            b"strf" + struct.pack("<I", len(strf)) + strf
+        hdrl = b"LIST" + struct.pack("<I", 4 + 8 + len(avih) + len(strl)) + b"hdrl" + b"avih" + struct.pack("<I", len(avih)) + avih + strl
+        out = b"RIFF" + struct.pack("<I", total) + b"AVI " + hdrl + b"LIST" + struct.pack("<I", movi) + b"movi"
+        assert len(out) == self.HEADER
+        return out
+
+    def _size_with(self, n_frames: int) -> int:
+        return self.HEADER + n_frames * (8 + self.frame_bytes) + 8 + 16 * n_frames
+
+    def _finish(self):
+        if self.file is None:
+            return
+        n = len(self.index)
+        self.file.write(b"idx1" + struct.pack("<I", 16 * n))
+        for k in range(n):
+            self.file.write(struct.pack("<4sIII", b"00db", 0x10, 4 + k * (8 + self.frame_bytes), self.frame_bytes))
+        self.file.seek(0)
+        self.file.write(self._header(n))
+        self.file.close()
+        self.file, self.index = None, []
+
+    def write(self, frame: np.ndarray) -> None:
+        if frame.shape != (self.height, self.width, 3) or frame.dtype != np.uint8:
+            raise ValueError(f"a frame is uint8 [{self.height}][{self.width}][3]")
+        if self.file is not None and self._size_with(len(self.index) + 1) > self.limit:
+            self._finish()
+        if self.file is None:
+            self.paths.append(f"{self.prefix}.{len(self.paths):03d}.avi")
+            self.file = open(self.paths[-1], "wb")
+            self.file.write(self._header(0))
+        rows = frame[::-1]  # a positive biHeight means the bottom row comes first
+        if self.row != 3 * self.width:
+            padded = np.zeros((self.height, self.row), np.uint8)
+            padded[:, : 3 * self.width] = rows.reshape(self.height, 3 * self.width)
+            rows = padded
+        self.file.write(b"00db" + struct.pack("<I", self.frame_bytes))
+        self.file.write(np.ascontiguousarray(rows).tobytes())
+        self.index.append(len(self.index))
+
+    def close(self) -> list:
+        self._finish()
+        return self.paths
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def read_avi(path):
+    """-> (frames [n][height][width][3] top-down, dwRate, dwScale) of a file AviWriter wrote, checking the sizes that frame it."""
+    blob = Path(path).read_bytes()
+    riff, size, avi = struct.unpack("<4sI4s", blob[:12])
+    assert riff == b"RIFF" and avi == b"AVI " and size == len(blob) - 8
+    avih = struct.unpack("<14I", blob[32: 32 + 56])
+    n, width, height = avih[4], avih[8], avih[9]
+    strh = struct.unpack("<4s4sIHHIIIIIIII4h", blob[108: 108 + 56])
+    assert strh[0] == b"vids" and strh[1] == b"DIB " and strh[9] == n
+    scale, rate = strh[6], strh[7]
+    strf = struct.unpack("<IiiHHIIiiII", blob[172: 172 + 40])
+    assert strf[:6] == (40, width, height, 1, 24, 0)
+    row = (3 * width + 3) & ~3
+    off = AviWriter.HEADER
+    assert blob[off - 12: off - 8] == b"LIST" and blob[off - 4: off] == b"movi"
+    assert struct.unpack("<I", blob[off - 8: off - 4])[0] == 4 + n * (8 + row * height)
+    frames = []
+    for k in range(n):
+        cid, nbytes = struct.unpack("<4sI", blob[off: off + 8])
+        assert cid == b"00db" and nbytes == row * height
+        rows = np.frombuffer(blob, np.uint8, nbytes, off + 8).reshape(height, row)[:, : 3 * width]
+        frames.append(rows.reshape(height, width, 3)[::-1])
+        off += 8 + nbytes
+    cid, nbytes = struct.unpack("<4sI", blob[off: off + 8])
+    assert cid == b"idx1" and nbytes == 16 * n and off + 8 + nbytes == len(blob)
+    for k in range(n):
+        assert struct.unpack("<4sIII", blob[off + 8 + 16 * k: off + 24 + 16 * k]) == (b"00db", 0x10, 4 + k * (8 + row * height), row * height)
+    return np.stack(frames) if frames else np.zeros((0, height, width, 3), np.uint8), rate, scale
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("pcap")
+    ap.add_argument("--port", type=int, required=True, help="UDP destination port of the FPGA datagrams")
+    ap.add_argument("--arrays", type=int, default=1, help="8x8 arrays side by side (stream id = a*64 + r*8 + c)")
+    ap.add_argument("--rows", type=int, default=1, help="rows of arrays")
+    ap.add_argument("--cols", type=int, default=100, help="heatmap resolution: cols x cols pixels")
+    ap.add_argument("--fov", type=float, default=180.0, help="field of view in degrees")
+    ap.add_argument("--every", type=int, default=3, help="show every Nth block (3: 63.6 frames per second)")
+    ap.add_argument("--size", type=int, default=1024, help="the video is size x size pixels (X_RES / Y_RES)")
+    ap.add_argument("--flip", action="store_true", help="mirror left-right, cv::flip(frame, frame, 1)")
+    ap.add_argument("--gray", action="store_true", help="levels as grey instead of the jet-like table")
+    ap.add_argument("--chunk", type=int, default=96, help="blocks per engine call")
+    ap.add_argument("--max-batch", type=int, default=32, help="frames per sweep launch (and per display piece held in memory)")
+    ap.add_argument("--raw", action="store_true", help="headerless BGR24 frames into OUT.bgr instead of AVI parts")
+    ap.add_argument("--out", default="heatmap", help="output prefix")
+    ap.add_argument("--device", type=int, default=0)
+    a = ap.parse_args(argv)
+    if a.every < 1 or a.chunk < 1 or a.size < a.cols:
+        ap.error("--every and --chunk are positive, --size is at least --cols")
+
+    sys.path.insert(0, str(Path(__file__).resolve().parent))
+    from pcap_heatmaps import blocks_of, read_pcap_payloads
+
+    payloads = read_pcap_payloads(a.pcap, a.port)
+    wire, n_blocks, gaps = blocks_of(payloads)
+    print(f"{len(payloads)} datagrams to port {a.port}: {n_blocks} blocks, {len(payloads) - 256 * n_blocks} left over")
+    for i, missing in gaps:
+        print(f"counter gap before datagram {i}: {missing} missing (not repaired)")
+    if n_blocks == 0:
+        print("no whole block of 256 datagrams")
+        return 1
+
+    sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+    pkg = importlib.import_module("beamforming-lk_amd")
+    import torch
+
+    xyz = pkg.create_tiled_antenna(a.arrays, a.rows)
+    off, frac = pkg.build_delay_table(xyz, a.cols, a.cols, a.fov)
+    n = xyz.shape[1]
+    if n > 256:
+        print(f"{n} mics: the wire carries 256 streams per datagram")
+        return 1
+    table = torch.from_numpy(gray_table() if a.gray else jet_table()).to(f"cuda:{a.device}")
+    rate, scale = frame_rate(a.every)
+    shown, first, block_bytes, res = 0, 0, 256 * 1032, None
+    raw = open(f"{a.out}.bgr", "wb") if a.raw else None
+    writer = None if a.raw else AviWriter(a.out, a.size, a.size, a.every)
+    with pkg.Engine(n_pixels=a.cols * a.cols, n_streams=n, max_batch=a.max_batch, grid_columns=a.cols, device=a.device) as eng:
+        eng.set_delay_table(off, frac)
+        eng.set_active_mics(None)
+        for b in range(0, n_blocks, a.chunk):
+            nb = min(a.chunk, n_blocks - b)
+            res = eng.watch_blocks(wire[b * block_bytes: (b + nb) * block_bytes], a.cols, a.cols, first=first, every=a.every,
+                                   out_rows=a.size, out_cols=a.size, d_colormap_ptr=table.data_ptr(), flip=a.flip, want_image=False,
+                                   out=res)  # (the frames of the chunk before are in the file)
+            first = res.next_first
+            for frame in res.big:
+                raw.write(frame.tobytes()) if raw else writer.write(frame)
+            shown += len(res.big)
+    if raw:
+        raw.close()
+        files = [f"{a.out}.bgr"]
+    else:
+        files = writer.close()
+    print(f"{shown} frames of {a.size} x {a.size} at {rate}/{scale} = {rate / scale:.3f} per second: {', '.join(files) or 'nothing written'}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
