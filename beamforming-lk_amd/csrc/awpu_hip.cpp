@@ -1,13 +1,7 @@
 // awpu_hip.cpp -- the C ABI of libawpu_hip.so (include/awpu_hip.h): handle lifetime, table
-// packing, frame upload, kernel dispatch.  No CPU fallback: every compute entry point ends
-// in a gfx950 kernel launch or an error status.
-#include "awpu_hip.h"
-#include "awpu_hip_blocks.h"
-#include "awpu_hip_listen.h"
-#include "awpu_hip_track.h"
-#include "awpu_hip_watch.h"
-
-#include <hip/hip_runtime.h>
+// packing, frame upload, kernel dispatch, the single-call paths, the ring, display, tracking and groups (the runs of
+// blocks: awpu_runs.cpp).  No CPU fallback: every compute entry point ends in a gfx950 kernel launch or an error status.
+#include "awpu_handle.h"
 
 #include <algorithm>
 #include <chrono>
@@ -15,43 +9,38 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <new>
 #include <string>
 #include <array>
 #include <map>
-#include <thread>
 #include <vector>
 
-#include "block_kernels.h"
 #include "das_kernels.h"
 #include "watch_kernels.h"
+
+using namespace awpu::host;
 
 namespace {
 
 thread_local std::string g_last_error;
-// the handle the calling thread is working on: errors are also kept in the handle, so that a thread
-// other than the one that ran into the error (a GUI thread asking about a worker's engine) can read them
-thread_local awpu_hip *g_ctx = nullptr;
-void note_error(const std::string &text);
+thread_local awpu_hip *g_ctx = nullptr;  // the handle the calling thread is working on (CtxScope)
 
-struct CtxScope {
-    awpu_hip *saved;
-    explicit CtxScope(awpu_hip *h) : saved(g_ctx) { g_ctx = h; }
-    ~CtxScope() { g_ctx = saved; }
-};
-#define AWPU_CTX(h) CtxScope ctx_scope_(h)
+}  // namespace
+
+namespace awpu::host {
+
+void note_error(const std::string &text) {
+    g_last_error = text;
+    if (g_ctx) g_ctx->last_error = text;
+}
+
+CtxScope::CtxScope(awpu_hip *h) : saved(g_ctx) { g_ctx = h; }
+CtxScope::~CtxScope() { g_ctx = saved; }
 
 int hip_fail(hipError_t e, const char *what) {
     note_error(std::string(what) + ": " + hipGetErrorString(e));
     return AWPU_ERR_HIP;
 }
-
-#define AWPU_HIP_TRY(call)                               \
-    do {                                                 \
-        hipError_t e_ = (call);                          \
-        if (e_ != hipSuccess) return hip_fail(e_, #call); \
-    } while (0)
 
 int invalid(const char *why) {
     note_error(why);
@@ -63,198 +52,9 @@ int fail(int status, const char *why) {
     return status;
 }
 
-template <class T>
-void dev_free(T *&p) {  // hipFree + forget
-    if (p) (void) hipFree(p);
-    p = nullptr;
-}
-
-}  // namespace
-
-struct awpu_hip {
-    awpu_hip_cfg cfg{};
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_begin = nullptr, ev_end = nullptr;
-    bool timing = true;
-
-    // host copies of what the reference keeps in MIMOWorker / Antenna
-    std::vector<int32_t> off;   // [pixel_count][lut_stride]  offsetDelays
-    std::vector<float> frac;    // [pixel_count][lut_stride]  fractionalDelays
-    std::vector<int32_t> index; // [usable]                   antenna.index
-    std::vector<float> gain;    // [n_streams] optional per-mic gain (awpu_hip_set_mic_gains); empty = none
-    bool have_table = false, have_mics = false, prepared = false;
-
-    // device state
-    awpu::LutEntry *d_lut = nullptr;
-    struct FastLut {
-        awpu::FastPlan plan;
-        awpu::FastEntry *d = nullptr;
-        size_t entries = 0;  // allocated (the launchers check their kernel's reach against it: das_kernels.h, Extents)
-    };
-    std::vector<FastLut> fast_luts;  // one per (frames per item, LDS image size) in use
-    awpu::FastEntry *d_exact_pair_lut = nullptr;  // reference-order sweep on the frame-pair layout (das_exact_pair_kernel)
-    size_t exact_pair_lut_entries = 0, fir_plane_lut_entries = 0;  // allocated entries of the tables below and above ...
-    size_t quad_lut_entries[8] = {0, 0, 0, 0, 0, 0, 0, 0};                  // ... and of the quad-major tables, by QuadLayout
-    awpu::QuadEntry *d_exact_quad_lut = nullptr;  // ... four vertically adjacent pixels per wave (das_exact_quad_kernel): quad-major, raw fractions
-    awpu::FastPlan exact_plan{};
-    unsigned *d_nd_queue = nullptr;               // das_exact_nd_kernel's eight item counters (one per XCD)
-    int2 *d_nd_items = nullptr;                   // ... and its item list (nd_items_kernel), valid for nd_items_key
-    size_t nd_items_cap = 0;
-    long long nd_items_key = -1;                  // (n_pairs, pair group, quads per wave) the list was built for; -1: none
-    int n_cus = 0;                                // compute units of the handle's device (persistent workgroups: one per CU)
-    awpu::QuadEntry *d_exact_nd_lut = nullptr;    // ... on the {next, d} layout (das_exact_nd_kernel): 16-byte elements, quad rows padded to an even count
-    awpu::FastPlan exact_nd_plan{};
-    bool exact_nd_ok = false;     // ... and the window fits the {next, d} image
-    awpu::QuadEntry *d_exact_ndh_lut = nullptr, *d_exact_ndhs_lut = nullptr;  // single frames: the halves form of that layout, chunked / every mic resident
-    awpu::FastPlan exact_ndh_plan{}, exact_ndhs_plan{};
-    bool exact_ndh_ok = false, exact_ndhs_ok = false, fast_ndp_ok = false;
-    bool exact_pairs_ok = false;  // AWPU_MATH_F32_EXACT + LERP and the window fits the pair image
-    float *sums_out = nullptr;    // awpu_hip_process_device_sums: where the launch in progress exports out[] (else null)
-    awpu::QuadEntry *d_quad_lut = nullptr;  // quad-major table of the quad shape (das_quad_kernel)
-    awpu::QuadEntry *d_quadh_lut = nullptr; // the same with the halves layout's LDS addresses (das_quadh_kernel)
-    awpu::QuadEntry *d_quadhs_lut = nullptr; // the same with slot = mic (das_quadh_stationary_kernel: every mic's row resident)
-    void *d_fir_plane_lut = nullptr;           // FIR8 on the four-plane layout: one dword per (pixel, mic): address, plane, coefficient row
-    awpu::FastPlan fir_plane_plan{};
-    std::vector<float> fir;                    // host copy of the [101][8] coefficient table (baked into the plane entries)
-    awpu::FastPlan quad_plan{}, quadh_plan{}, quadhs_plan{};
-    bool quadh_fits = false;      // single frames on the halves layout (das_quadh_kernel)
-    bool quadhs_fits = false;     // ... with every active mic's row in LDS at once (das_quadh_stationary_kernel: one 8x8 array does)
-    bool quad_ok = false;         // the table's statistics favour the quad shape (decided in prepare)
-    double quad_cost = 0.0;       // its expected packed VALU instructions per quad and mic (32 = no sharing at all)
-    double quad_differ = 3.0;     // pixels of a vertical quad (of three) whose integer delay differs from the second pixel's, per mic (table sample)
-    int32_t *d_index = nullptr;
-    float *d_gain = nullptr;  // [usable] gains in active-mic order, or null
-    float *d_calib = nullptr; // [64] per-mic mean squares (calibration)
-    awpu::LutEntry *d_beam_lut = nullptr;  // [beam_cap][usable] entries of awpu_hip_beams
-    float *d_beam_out = nullptr;           // [beam_cap] powers then [beam_cap][256] beams
-    size_t beam_cap = 0, beam_lut_cap = 0;
-    // particle tracking (awpu_hip_track.h)
-    std::vector<float> antenna;            // [3][antenna_n] element positions by stream id (awpu_hip_set_antenna); empty = none
-    float *d_xyz = nullptr;                // ... on the device
-    std::vector<int32_t> track_index;      // the active mics d_track_index holds
-    int32_t *d_track_index = nullptr;
-    size_t track_index_cap = 0;
-    unsigned char *d_track = nullptr;      // particles, then the reference used, then [n][256] beams (steer_table_device: angles, tables)
-    size_t track_cap = 0;                  // bytes
-    float *d_fir = nullptr;  // [101][8] coefficient table (AWPU_INTERP_FIR8)
-    float *d_ring = nullptr;            // [n_streams][2048] history ring (awpu_hip_ingest_block)
-    uint8_t *d_display = nullptr;       // awpu_hip_live_block: peak (one float), compact image, upscaled image
-    size_t display_cap = 0;             // bytes
-    awpu::ResizeTap *d_taps = nullptr;  // column + row taps of the display upscale, for taps_key
-    int taps_key[4] = {0, 0, 0, 0};     // {srows, scols, drows, dcols}
-    int taps_band_rows = 0;             // ... and the most compact rows a 16-row tile of the large image reads (watch_kernels.h)
-    float *d_pack = nullptr;            // [pairs][usable][wp][2] sample-interleaved frame pairs
-    size_t pack_cap = 0;                // floats
-    unsigned char *d_datagrams = nullptr;  // staging for one block of wire datagrams
-    int32_t *d_row_off_ring = nullptr;  // row offsets for frames read out of the ring (pitch 2048)
-    int ring_pos = 0;                   // where the next block goes = start of the snapshot
-    // awpu_hip_live_block as a HIP graph: the call's copies and launches captured once per (ring position, caller
-    // buffers, table generation) and replayed with one hipGraphLaunch
-    struct LiveGraph {
-        int ring_pos, stride, rows, cols, out_rows, out_cols;
-        const void *datagrams, *power, *image, *colormap, *big_image;
-        unsigned long long gen;
-        hipGraphExec_t exec;
-        unsigned long long last_use;  // live_clock at the last replay: the least recently used graph is evicted
-    };
-    std::vector<LiveGraph> live_graphs;
-    unsigned long long table_gen = 0;   // bumped whenever prepare() rebuilds the device tables
-    int live_warm = 0;                  // plain live calls made with the current tables AND this call shape (lazy allocations done after one)
-    unsigned long long live_shape = 0;  // the shape those calls had: image sizes, which outputs, colour table or not
-    const void *live_bufs[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // ... and the caller's buffers (a capture bakes them in)
-    unsigned long long live_clock = 0;
-    bool live_graph_broken = false;     // a capture failed on this runtime: never try again
-    bool have_fir = false;
-    int32_t *d_row_off = nullptr;
-    int32_t *d_row_off_compact = nullptr;  // the same for frames uploaded as [streams][compact_hist] windows
-    int compact_hist = 0;                  // 0 = the window cannot be cut out (it touches the newest sample)
-    float *d_frames = nullptr;
-    float *h_live_in = nullptr, *h_live_out = nullptr;  // pinned staging of awpu_hip_process's one-frame calls (the live path): window in, powers out
-    size_t live_in_cap = 0, live_out_cap = 0;           // in floats
-    unsigned live_calls = 0;                            // ... how many of them this handle has served (every 32nd is timed by events)
-    // ... their completion flag (the resident single-frame kernels with one quad per wave): the device counter the workgroups count themselves on, what it will read
-    // when every launch armed so far is over, the pinned flag and the sequence number of the last armed launch
-    unsigned long long *d_done_counter = nullptr, done_total = 0;
-    unsigned *h_done_flag = nullptr, done_seq = 0;
-    bool done_arm = false, done_used = false;           // arm: the next single-frame sweep is to raise the flag; used: it will
-    float *d_power = nullptr;
-    size_t frames_cap = 0, power_cap = 0;  // in floats
-    int wstart = 0, window = 0, tau_max = 0;
-    int pair_cols = 0;  // frame-pair sweep: > 0 = waves take vertically adjacent pixels (grid row length), 0 = consecutive
-
-    // device group (cfg.n_devices > 1): this handle owns no sweep state of its own, only one part per device
-    std::vector<awpu_hip *> parts;
-    // a part's pixels inside the group's range: (first pixel relative to the group's pixel_begin, count), ascending; the part's
-    // own table and power rows hold them back to back.  One range = a contiguous slab; several = row groups of four dealt
-    // round-robin over the devices (edge rows of the sine-space grid cost the quad shapes more than centre rows: DESIGN.md 6)
-    std::vector<std::pair<int, int>> ranges;
-    bool union_window_done = false;  // group: every part stages the union of the parts' windows (packed frames need one layout)
-    hipEvent_t ev_fan = nullptr;            // group: recorded on the caller's stream, awaited by every part
-    // a part's share of the fan-out (awpu_hip_process_device on a group): two window buffers, so that the copy of
-    // call k+1 (on copy_stream) runs beside the sweep of call k (on stream)
-    hipStream_t copy_stream = nullptr;
-    float *d_fan[2] = {nullptr, nullptr};
-    size_t fan_cap = 0;                     // floats per buffer
-    hipEvent_t ev_copied[2] = {nullptr, nullptr}, ev_swept[2] = {nullptr, nullptr}, ev_done = nullptr;
-    unsigned fan_turn = 0;
-    // how a part of a group reaches devices[0]: kPeerSame (the same GPU), kPeerDirect (peer copies over xGMI) or
-    // kPeerStaged (no peer access on this node: the window and the tiles cross pinned host memory, explicitly)
-    int peer = 0;
-    float *h_stage[2] = {nullptr, nullptr};  // group: pinned staging of the frames' window for the staged parts
-    size_t stage_cap = 0;                    // floats per buffer
-    int stage_lo = 0, stage_w = 0;           // group: the window [stage_lo, stage_lo + stage_w) of every stream that is staged
-    hipEvent_t ev_staged[2] = {nullptr, nullptr};   // group: window b is in h_stage[b]
-    unsigned stage_turn = 0;
-    float *h_tile[2] = {nullptr, nullptr};   // part (staged): pinned staging of its power tile on the way back
-    size_t tile_cap = 0;
-    hipEvent_t ev_tile_free[2] = {nullptr, nullptr};  // part (staged): the caller's stream has read h_tile[b]
-    hipEvent_t ev_staged_read[2] = {nullptr, nullptr};  // part (staged): its upload out of the group's h_stage[b] is done
-    bool stage_used[2] = {false, false};
-    bool tile_used[2] = {false, false}, fan_used[2] = {false, false};
-    bool in_flight = false;                 // awpu_hip_process_async without its awpu_hip_wait yet
-    // runs of blocks (awpu_hip_blocks.h), by sweep piece: piece i's history [n_streams][768 + 256 * piece] in d_blk_hist[i & 1], its
-    // windows in d_blk_frames; the host forms stage piece i's input in pinned h_blk_in[i & 1], upload it to d_blk_in[i & 1] on
-    // copy_stream and bring its powers back through pinned h_blk_out[i & 1]
-    float *d_blk_hist[2] = {nullptr, nullptr};
-    float *d_blk_frames = nullptr;
-    void *h_blk_in[2] = {nullptr, nullptr}, *d_blk_in[2] = {nullptr, nullptr};
-    float *h_blk_out[2] = {nullptr, nullptr};
-    size_t blk_hist_cap = 0, blk_frames_cap = 0, blk_in_cap = 0, blk_out_cap = 0;  // floats, floats, bytes, floats (per buffer)
-    // ev_blk_in[b]: h_blk_in[b] may be refilled; ev_blk_hist[b]: d_blk_hist[b] formed; ev_blk_cut[b]: ... and read by the cut;
-    // ev_blk_swept[b]: d_power's half b holds its piece's powers; ev_blk_out[b]: ... and h_blk_out[b] too; ev_blk_ring: orders a
-    // run after the work queued on the handle's stream, and the handle's stream after a device-form run on the caller's stream
-    hipEvent_t ev_blk_in[2] = {nullptr, nullptr}, ev_blk_hist[2] = {nullptr, nullptr}, ev_blk_cut[2] = {nullptr, nullptr},
-               ev_blk_swept[2] = {nullptr, nullptr}, ev_blk_out[2] = {nullptr, nullptr}, ev_blk_ring = nullptr;
-    // listening to such runs (awpu_hip_listen.h): the listeners on the device from piece to piece; the host forms get piece i's
-    // audio rows [n][256 * piece], then its trail, in d_listen_out[i & 1] and bring them back through pinned h_listen_out[i & 1].
-    // listen_stream: where the listen kernels run beside the sweeps when heatmaps are asked for too.
-    unsigned char *d_listeners = nullptr;
-    unsigned char *d_listen_out[2] = {nullptr, nullptr}, *h_listen_out[2] = {nullptr, nullptr};
-    size_t listeners_cap = 0, listen_out_cap = 0;  // bytes
-    hipStream_t listen_stream = nullptr;
-    // ev_listened[b]: the listen kernels have read d_blk_hist[b] (and written d_listen_out[b]); ev_listen_out[b]: h_listen_out[b] holds it
-    hipEvent_t ev_listened[2] = {nullptr, nullptr}, ev_listen_out[2] = {nullptr, nullptr};
-
-    // watching such runs (awpu_hip_watch.h): piece i's peaks, compact images and (host forms) large images in d_watch[i & 1]; the
-    // host forms bring the images back through pinned h_watch[i & 1].  The events are those of the runs above: ev_blk_swept[b] is
-    // recorded behind the display kernels, ev_blk_out[b] behind the images' way back.
-    uint8_t *d_watch[2] = {nullptr, nullptr}, *h_watch[2] = {nullptr, nullptr};
-    size_t watch_cap = 0, watch_host_cap = 0;  // bytes per buffer
-
-    awpu_hip_stats stats{};
-    std::string last_error;                  // awpu_hip_last_error_of
-    unsigned long long *d_diag = nullptr;    // AWPU_FAST_DEBUG=16 cycle stamps of the last launch
-    size_t diag_cap = 0;                     // in 64-bit words
-
-    int usable() const { return static_cast<int>(index.size()); }
-};
+}  // namespace awpu::host
 
 namespace {
-
-void note_error(const std::string &text) {
-    g_last_error = text;
-    if (g_ctx) g_ctx->last_error = text;
-}
 
 // diagnostics buffer of `words` 64-bit words, grown on demand (one per handle: handles on different
 // devices, or launches of different sizes, must not share it)
@@ -267,86 +67,61 @@ int ensure_diag(awpu_hip *h, size_t words) {
     return AWPU_OK;
 }
 
-// What the process environment can change.  The SHIPPING library reads three variables, none of them needed in production:
-//   AWPU_SHAPE             force one of the production sweep shapes wherever it can serve the call (tests sweep every shape
-//                          through the oracle this way; the default rule -- launch() below -- picks by table statistics and launch size):
-//                          pair | pair_vertical | pair_horizontal | quad | noquad | stationary | quadh | quadh_chunked | single_db | single_small |
-//                          fir8_planes | exact_pair | exact_quad | exact_nd1 | exact_nd2 | exact_ndp | exact_verify
-//   AWPU_LIVE_GRAPH=0      awpu_hip_live_block always enqueues its steps one by one (no HIP-graph replay)
-//   AWPU_GROUP_FORCE_COPY  device groups: 1 = a part on devices[0] takes the window-copy path too, 2 = through pinned host
-//                          memory (how one GPU exercises the paths a part on another GPU takes)
-// Everything else -- chunk geometry, XCD pair groups, persistent workgroups, priority variants, cycle stamps -- exists only in
-// builds with -DAWPU_TUNING_BUILD (AWPU_EXTRA_HIPCC_FLAGS; -DAWPU_TIMING_BUILD implies it), which read the round-1..3 variables
-// (AWPU_FAST_*, AWPU_FIR8_*, AWPU_QUAD_VARIANT, AWPU_EXACT_PAIRS) as before.  Read once per process.
-struct EnvKnobs {
-    int fpi = 0, ppw = 0, nw = 0;  // single-frame shape forced: frames per item (always 1 here), pixels per wave, 8 / 32
-    int pairs = -1;                // 0 / 1: never / always a frame-pair sweep (quad, stationary or pair shape) for batches >= 2
-    int debug = 0;                 // AWPU_FAST_DEBUG bits (tuning builds)
-    int fpw = 0;                   // tuning: consecutive frames per workgroup of the double-buffered single-frame shape
-    int quads = -1;                // 0 / 1: never / always (where the row length is known) the quad shapes
-    int pair_group = 0;            // tuning: frame pairs an XCD works on at a time (quad shape)
-    int quad_variant = 0;          // tuning: block variant (AWPU_QUAD_VARIANT)
-    int stationary = -1;           // 0 / 1: never / always (where the window fits the LDS) the stationary pair shape
-    int fir_planes = 1;            // 2: the four-plane FIR8 kernel for every batch >= 2 however small the grid
-    int fir_share = 1;             // tuning: 0 = the FIR8 plane kernel sweeps four consecutive pixels even where the row length is known
-    int wgs = 0;                   // tuning: persistent workgroups of the quad shape (0 = default rule, -1 = one workgroup per item)
-    int live_graph = 1;            // AWPU_LIVE_GRAPH
-    int halves = -1;               // 1: single frames on the halves layout for every call (where the quad table is built)
-    int exact_pairs = 1;           // 0: AWPU_MATH_F32_EXACT on the round-1 verification kernel (das_exact_kernel)
-    int pair_cols = -1;            // 0 / 1: the pair shape pairs consecutive / vertically adjacent pixels (default: whichever coincides more)
-    int group_copy = 0;            // AWPU_GROUP_FORCE_COPY
-    int listen_stream = 1;         // tuning: 0 = the listen kernels queue behind the sweeps instead of running beside them
-    EnvKnobs() {
-        if (const char *v = std::getenv("AWPU_GROUP_FORCE_COPY")) group_copy = std::atoi(v);
-        if (const char *v = std::getenv("AWPU_LIVE_GRAPH")) live_graph = std::atoi(v);
-        if (const char *v = std::getenv("AWPU_SHAPE")) {
-            const std::string shape(v);
-            if (shape == "pair" || shape == "pair_vertical" || shape == "pair_horizontal") {
-                pairs = 1, quads = 0, stationary = 0;
-                if (shape != "pair") pair_cols = shape == "pair_vertical";
-            } else if (shape == "quad") quads = 1;
-            else if (shape == "noquad") quads = 0;
-            else if (shape == "stationary") pairs = 1, quads = 0, stationary = 1;
-            else if (shape == "quadh") quads = 1, pairs = 0, halves = 1;
-            else if (shape == "quadh_chunked") quads = 1, pairs = 0, halves = 1, stationary = 0;  // never the resident-window variant
-            else if (shape == "single_db") pairs = 0, quads = 0, fpi = 1, ppw = 8, nw = 32;
-            else if (shape == "single_small") pairs = 0, quads = 0, fpi = 1, ppw = 2, nw = 8;
-            else if (shape == "fir8_planes") fir_planes = 2;
-            else if (shape == "exact_verify") exact_pairs = 0;
-            else if (shape == "exact_pair") exact_pairs = 2;  // the two-pixel reference-order block even where quads would run
-            else if (shape == "exact_quad") exact_pairs = 3;  // round 4's quad kernel on raw sample pairs (cur - next per pixel)
-            else if (shape == "exact_nd1") exact_pairs = 4;   // the {next, d} kernel with one quad per wave
-            else if (shape == "exact_nd2") exact_pairs = 5;   // ... with two
-            else if (shape == "exact_ndp") exact_pairs = 6;   // single frames: one pixel per wave (das_exact_ndp_kernel) wherever its rows can be chunked
-            else std::fprintf(stderr, "libawpu_hip: AWPU_SHAPE=%s is not a shape of this build; ignored\n", v);
-        }
-#ifdef AWPU_TUNING_BUILD
-        if (const char *v = std::getenv("AWPU_LISTEN_STREAM")) listen_stream = std::atoi(v);
-        if (const char *v = std::getenv("AWPU_FAST_QUADS")) quads = std::atoi(v);
-        if (const char *v = std::getenv("AWPU_FAST_PAIRGROUP")) pair_group = std::atoi(v);
-        if (const char *v = std::getenv("AWPU_QUAD_VARIANT")) quad_variant = std::atoi(v);
-        if (const char *v = std::getenv("AWPU_FAST_HALVES")) halves = std::atoi(v);
-        if (const char *v = std::getenv("AWPU_EXACT_PAIRS")) exact_pairs = std::atoi(v);
-        if (const char *v = std::getenv("AWPU_FAST_WGS")) wgs = std::atoi(v);
-        if (const char *v = std::getenv("AWPU_FIR8_PLANES")) fir_planes = std::atoi(v);
-        if (const char *v = std::getenv("AWPU_FIR8_SHARE")) fir_share = std::atoi(v);
-        if (const char *v = std::getenv("AWPU_FAST_STATIONARY")) stationary = std::atoi(v);
-        if (const char *v = std::getenv("AWPU_FAST_PAIRCOLS")) pair_cols = std::atoi(v);
-        if (const char *v = std::getenv("AWPU_FAST_VARIANT"))
-            if (std::sscanf(v, "%d,%d,%d", &fpi, &ppw, &nw) < 2) fpi = ppw = nw = 0;
-        if (const char *v = std::getenv("AWPU_FAST_PAIRS")) pairs = std::atoi(v);
-        if (const char *v = std::getenv("AWPU_FAST_DEBUG")) debug = std::atoi(v);
-#ifndef AWPU_TIMING_BUILD
-        debug &= awpu::kDebugSafeBits;  // the wrong-result timing switches exist only with -DAWPU_TIMING_BUILD (das_kernels.h)
-#endif
-        if (const char *v = std::getenv("AWPU_FAST_FPW")) fpw = std::atoi(v);
-#endif
+}  // namespace
+
+awpu::host::EnvKnobs::EnvKnobs() {
+    if (const char *v = std::getenv("AWPU_GROUP_FORCE_COPY")) group_copy = std::atoi(v);
+    if (const char *v = std::getenv("AWPU_LIVE_GRAPH")) live_graph = std::atoi(v);
+    if (const char *v = std::getenv("AWPU_SHAPE")) {
+        const std::string shape(v);
+        if (shape == "pair" || shape == "pair_vertical" || shape == "pair_horizontal") {
+            pairs = 1, quads = 0, stationary = 0;
+            if (shape != "pair") pair_cols = shape == "pair_vertical";
+        } else if (shape == "quad") quads = 1;
+        else if (shape == "noquad") quads = 0;
+        else if (shape == "stationary") pairs = 1, quads = 0, stationary = 1;
+        else if (shape == "quadh") quads = 1, pairs = 0, halves = 1;
+        else if (shape == "quadh_chunked") quads = 1, pairs = 0, halves = 1, stationary = 0;  // never the resident-window variant
+        else if (shape == "single_db") pairs = 0, quads = 0, fpi = 1, ppw = 8, nw = 32;
+        else if (shape == "single_small") pairs = 0, quads = 0, fpi = 1, ppw = 2, nw = 8;
+        else if (shape == "fir8_planes") fir_planes = 2;
+        else if (shape == "exact_verify") exact_pairs = 0;
+        else if (shape == "exact_pair") exact_pairs = 2;  // the two-pixel reference-order block even where quads would run
+        else if (shape == "exact_quad") exact_pairs = 3;  // round 4's quad kernel on raw sample pairs (cur - next per pixel)
+        else if (shape == "exact_nd1") exact_pairs = 4;   // the {next, d} kernel with one quad per wave
+        else if (shape == "exact_nd2") exact_pairs = 5;   // ... with two
+        else if (shape == "exact_ndp") exact_pairs = 6;   // single frames: one pixel per wave (das_exact_ndp_kernel) wherever its rows can be chunked
+        else std::fprintf(stderr, "libawpu_hip: AWPU_SHAPE=%s is not a shape of this build; ignored\n", v);
     }
-};
-const EnvKnobs &env() {
+#ifdef AWPU_TUNING_BUILD
+    if (const char *v = std::getenv("AWPU_LISTEN_STREAM")) listen_stream = std::atoi(v);
+    if (const char *v = std::getenv("AWPU_FAST_QUADS")) quads = std::atoi(v);
+    if (const char *v = std::getenv("AWPU_FAST_PAIRGROUP")) pair_group = std::atoi(v);
+    if (const char *v = std::getenv("AWPU_QUAD_VARIANT")) quad_variant = std::atoi(v);
+    if (const char *v = std::getenv("AWPU_FAST_HALVES")) halves = std::atoi(v);
+    if (const char *v = std::getenv("AWPU_EXACT_PAIRS")) exact_pairs = std::atoi(v);
+    if (const char *v = std::getenv("AWPU_FAST_WGS")) wgs = std::atoi(v);
+    if (const char *v = std::getenv("AWPU_FIR8_PLANES")) fir_planes = std::atoi(v);
+    if (const char *v = std::getenv("AWPU_FIR8_SHARE")) fir_share = std::atoi(v);
+    if (const char *v = std::getenv("AWPU_FAST_STATIONARY")) stationary = std::atoi(v);
+    if (const char *v = std::getenv("AWPU_FAST_PAIRCOLS")) pair_cols = std::atoi(v);
+    if (const char *v = std::getenv("AWPU_FAST_VARIANT"))
+        if (std::sscanf(v, "%d,%d,%d", &fpi, &ppw, &nw) < 2) fpi = ppw = nw = 0;
+    if (const char *v = std::getenv("AWPU_FAST_PAIRS")) pairs = std::atoi(v);
+    if (const char *v = std::getenv("AWPU_FAST_DEBUG")) debug = std::atoi(v);
+#ifndef AWPU_TIMING_BUILD
+    debug &= awpu::kDebugSafeBits;  // the wrong-result timing switches exist only with -DAWPU_TIMING_BUILD (das_kernels.h)
+#endif
+    if (const char *v = std::getenv("AWPU_FAST_FPW")) fpw = std::atoi(v);
+#endif
+}
+
+const EnvKnobs &awpu::host::env() {
     static const EnvKnobs knobs;  // initialised once, thread-safe
     return knobs;
 }
+
+namespace {
 
 // The captured live-block graphs hold raw device pointers (d_power, d_display, d_taps, d_ring, tables, d_pack):
 // whoever frees or reallocates one of those retires the graphs first.  The next live calls run step by step and
@@ -418,29 +193,11 @@ void release_device(awpu_hip *h) {
     dev_free(h->d_fan[0]);
     dev_free(h->d_fan[1]);
     h->fan_cap = 0;
-    for (int b = 0; b < 2; b++) {
-        dev_free(h->d_blk_hist[b]);
-        dev_free(h->d_blk_in[b]);
-        if (h->h_blk_in[b]) (void) hipHostFree(h->h_blk_in[b]);
-        if (h->h_blk_out[b]) (void) hipHostFree(h->h_blk_out[b]);
-        h->h_blk_in[b] = nullptr;
-        h->h_blk_out[b] = nullptr;
-    }
+    for (BufferPair *pair : {&h->blk_hist, &h->blk_in, &h->blk_out, &h->listen_out, &h->watch}) pair->release();
     dev_free(h->d_blk_frames);
-    h->blk_hist_cap = h->blk_frames_cap = h->blk_in_cap = h->blk_out_cap = 0;
+    h->blk_frames_cap = 0;
     dev_free(h->d_listeners);
-    for (int b = 0; b < 2; b++) {
-        dev_free(h->d_listen_out[b]);
-        if (h->h_listen_out[b]) (void) hipHostFree(h->h_listen_out[b]);
-        h->h_listen_out[b] = nullptr;
-    }
-    h->listeners_cap = h->listen_out_cap = 0;
-    for (int b = 0; b < 2; b++) {
-        dev_free(h->d_watch[b]);
-        if (h->h_watch[b]) (void) hipHostFree(h->h_watch[b]);
-        h->h_watch[b] = nullptr;
-    }
-    h->watch_cap = h->watch_host_cap = 0;
+    h->listeners_cap = 0;
     for (int b = 0; b < 2; b++) {
         if (b == 0) {
             if (h->h_live_in) (void) hipHostFree(h->h_live_in);
@@ -802,9 +559,6 @@ void choose_fast_variant(awpu_hip *h, int batch, int *fpi, int *ppw, int *nw) {
     if (*fpi == 2 && batch < 2) *fpi = 1;
 }
 
-// layout of d_frames: kFull [batch][n_streams][hist]; kCompact [batch][n_streams][compact_hist] with
-// sample 0 = history sample wstart; kRing one frame read in place from the ingest ring (rows 2048 apart)
-enum FrameLayout { kFull = 0, kCompact = 1, kRing = 2 };
 enum PeerPath { kPeerSame = 0, kPeerDirect = 1, kPeerStaged = 2 };
 
 // a launch is over: close the timing bracket and count it (also on the diagnostic paths)
@@ -1453,8 +1207,11 @@ int launch_quadsh_stationary(awpu_hip *h, const float *d_frames, int batch, floa
     if (qa.done.flag) done_flag_armed(h, qa.done);
     return finish_launch(h, batch, s, AWPU_KERNEL_QUADH_STATIONARY);
 }
+}  // namespace
 
-int launch(awpu_hip *h, const float *d_frames, int batch, float *d_power, hipStream_t s, int layout = kFull) {
+namespace awpu::host {
+
+int launch(awpu_hip *h, const float *d_frames, int batch, float *d_power, hipStream_t s, int layout) {
     const bool compact = layout == kCompact;
     const int hist_eff = compact ? h->compact_hist : (layout == kRing ? 2048 : h->cfg.hist);
     const int wstart_eff = compact ? 0 : h->wstart;
@@ -1650,6 +1407,10 @@ int ensure_power(awpu_hip *h, size_t need_power) {
     return AWPU_OK;
 }
 
+}  // namespace awpu::host
+
+namespace {
+
 // ------------------------------------------------------------------------------------------------
 // Device group (cfg.n_devices > 1): one handle, one part (an ordinary single-device engine) per GPU,
 // each owning a contiguous slab of the handle's pixels.  Everything below runs in the caller's thread; the parts'
@@ -1780,13 +1541,16 @@ struct TimingOff {
     ~TimingOff() { h->timing = keep; }
 };
 
+}  // namespace
 
 // frames per sweep launch of a host batch: large batches go up in pieces of whole frame pairs, so that piece k+1 crosses PCIe
 // while piece k is swept (enqueue_host_process; a run of blocks sweeps its chunks the same way)
-int host_piece(int batch) {
+int awpu::host::host_piece(int batch) {
     const int n_pieces = batch >= 128 ? 4 : (batch >= 64 ? 2 : 1);
     return ((batch + n_pieces - 1) / n_pieces + 1) & ~1;
 }
+
+namespace {
 
 // upload of host frames + the sweep into h->d_power, all on h->stream, nothing waited for
 int enqueue_host_process(awpu_hip *h, const float *frames, int batch) {
@@ -1859,8 +1623,6 @@ int enqueue_power_to_host(awpu_hip *h, int batch, float *power, size_t pitch) {
     }
     return AWPU_OK;
 }
-
-int wait_and_time(awpu_hip *h);
 
 // One frame in, one heatmap out, synchronously: the call MIMOWorker::update makes once per 256-sample block (mimo.cpp:100-103 is the
 // snapshot it replaces).  The caller's buffers are pageable (std::vector, mimo.h:83-88): a device copy straight out of / into them goes
@@ -1988,7 +1750,9 @@ int live_host_call(awpu_hip *h, const float *frames, float *power) {
     return AWPU_OK;
 }
 
-int wait_and_time(awpu_hip *h) {
+}  // namespace
+
+int awpu::host::wait_and_time(awpu_hip *h) {
     AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
     AWPU_HIP_TRY(hipStreamSynchronize(h->stream));
     if (h->timing) {
@@ -2000,6 +1764,8 @@ int wait_and_time(awpu_hip *h) {
     }
     return AWPU_OK;
 }
+
+namespace {
 
 int group_process(awpu_hip *g, const float *frames, int batch, float *power) {
     const size_t pitch = (size_t) g->cfg.pixel_count;
@@ -2345,6 +2111,83 @@ int group_stats(awpu_hip *g, awpu_hip_stats *out) {
 }
 
 }  // namespace
+
+// what the runs of blocks (awpu_runs.cpp) share with the calls below
+namespace awpu::host {
+
+size_t align16(size_t n) { return (n + 15) & ~(size_t) 15; }
+
+static_assert(sizeof(awpu_particle_t) == 80, "awpu_particle_t is part of the ABI (include/awpu_hip_track.h)");
+
+// what awpu_hip_track and the listen calls ask of their particles (none of it reads the handle)
+int check_particles(const awpu_particle_t *p, int32_t n, double theta_limit, double reference) {
+    if (n < 1 || n > 65535) return invalid("n outside [1, 65535]");
+    if (!(theta_limit > 0.0) || !std::isfinite(theta_limit)) return invalid("theta_limit must be finite and > 0");
+    if (!std::isfinite(reference)) return invalid("reference not finite");
+    for (int k = 0; k < n; k++) {
+        if (p[k].steps < 0 || p[k].steps > 4096) return invalid("steps outside [0, 4096]");
+        if (!std::isfinite(p[k].theta) || !std::isfinite(p[k].phi) || !std::isfinite(p[k].spread) || !std::isfinite(p[k].rate))
+            return invalid("particle direction, spread or rate not finite");
+    }
+    return AWPU_OK;
+}
+
+// ... and of the handle: the antenna, and the active mics inside it
+int check_antenna(const awpu_hip *h) {
+    if (h->antenna.empty()) return fail(AWPU_ERR_STATE, "antenna not set (awpu_hip_set_antenna)");
+    if (!h->have_mics || h->index.empty()) return fail(AWPU_ERR_STATE, "active mics not set");
+    const int n_el = (int) (h->antenna.size() / 3);
+    for (int id : h->index)
+        if (id >= n_el) return fail(AWPU_ERR_STATE, "an active mic is not an element of the antenna");
+    return AWPU_OK;
+}
+
+// d_track_index = the active mics
+int ensure_track_index(awpu_hip *h) {
+    const int U = h->usable();
+    if (h->track_index == h->index) return AWPU_OK;
+    if (h->track_index_cap < (size_t) U) {
+        dev_free(h->d_track_index);
+        h->track_index_cap = 0;
+        AWPU_HIP_TRY(hipMalloc(&h->d_track_index, (size_t) U * sizeof(int32_t)));
+        h->track_index_cap = U;
+    }
+    h->track_index.clear();
+    AWPU_HIP_TRY(hipMemcpy(h->d_track_index, h->index.data(), (size_t) U * sizeof(int32_t), hipMemcpyHostToDevice));
+    h->track_index = h->index;
+    return AWPU_OK;
+}
+
+// the ingest ring and its one-block staging, allocated at first use: the ring starts zeroed (on h->stream)
+int ensure_ring(awpu_hip *h) {
+    if (h->d_ring) return AWPU_OK;
+    const size_t ring_bytes = (size_t) h->cfg.n_streams * 2048 * sizeof(float);
+    AWPU_HIP_TRY(hipMalloc(&h->d_ring, ring_bytes));
+    AWPU_HIP_TRY(hipMemsetAsync(h->d_ring, 0, ring_bytes, h->stream));
+    AWPU_HIP_TRY(hipMalloc(&h->d_datagrams, (size_t) awpu::kSamples * AWPU_DATAGRAM_BYTES));
+    h->ring_pos = 0;
+    return AWPU_OK;
+}
+
+// h->d_taps = the column and row taps of rows x cols -> out_rows x out_cols, rebuilt when the shape changes
+int ensure_taps(awpu_hip *h, int rows, int cols, int out_rows, int out_cols, hipStream_t s) {
+    const int key[4] = {rows, cols, out_rows, out_cols};
+    if (!h->d_taps || std::memcmp(key, h->taps_key, sizeof(key)) != 0) {
+        std::vector<awpu::ResizeTap> taps((size_t) out_cols + out_rows);
+        awpu::resize_taps(cols, out_cols, true, taps.data());
+        awpu::resize_taps(rows, out_rows, false, taps.data() + out_cols);
+        AWPU_HIP_TRY(hipStreamSynchronize(s));  // an earlier launch may still read the old taps
+        retire_live_graphs(h);
+        dev_free(h->d_taps);
+        AWPU_HIP_TRY(hipMalloc(&h->d_taps, taps.size() * sizeof(awpu::ResizeTap)));
+        AWPU_HIP_TRY(hipMemcpy(h->d_taps, taps.data(), taps.size() * sizeof(awpu::ResizeTap), hipMemcpyHostToDevice));
+        std::memcpy(h->taps_key, key, sizeof(key));
+        h->taps_band_rows = awpu::watch_band_rows(taps.data() + out_cols, rows, out_rows);
+    }
+    return AWPU_OK;
+}
+
+}  // namespace awpu::host
 
 extern "C" {
 
@@ -2700,49 +2543,6 @@ int ensure_track_buffer(awpu_hip *h, size_t bytes) {
     return AWPU_OK;
 }
 
-size_t align16(size_t n) { return (n + 15) & ~(size_t) 15; }
-
-static_assert(sizeof(awpu_particle_t) == 80, "awpu_particle_t is part of the ABI (include/awpu_hip_track.h)");
-
-// what awpu_hip_track and the listen calls ask of their particles (none of it reads the handle)
-int check_particles(const awpu_particle_t *p, int32_t n, double theta_limit, double reference) {
-    if (n < 1 || n > 65535) return invalid("n outside [1, 65535]");
-    if (!(theta_limit > 0.0) || !std::isfinite(theta_limit)) return invalid("theta_limit must be finite and > 0");
-    if (!std::isfinite(reference)) return invalid("reference not finite");
-    for (int k = 0; k < n; k++) {
-        if (p[k].steps < 0 || p[k].steps > 4096) return invalid("steps outside [0, 4096]");
-        if (!std::isfinite(p[k].theta) || !std::isfinite(p[k].phi) || !std::isfinite(p[k].spread) || !std::isfinite(p[k].rate))
-            return invalid("particle direction, spread or rate not finite");
-    }
-    return AWPU_OK;
-}
-
-// ... and of the handle: the antenna, and the active mics inside it
-int check_antenna(const awpu_hip *h) {
-    if (h->antenna.empty()) return fail(AWPU_ERR_STATE, "antenna not set (awpu_hip_set_antenna)");
-    if (!h->have_mics || h->index.empty()) return fail(AWPU_ERR_STATE, "active mics not set");
-    const int n_el = (int) (h->antenna.size() / 3);
-    for (int id : h->index)
-        if (id >= n_el) return fail(AWPU_ERR_STATE, "an active mic is not an element of the antenna");
-    return AWPU_OK;
-}
-
-// d_track_index = the active mics
-int ensure_track_index(awpu_hip *h) {
-    const int U = h->usable();
-    if (h->track_index == h->index) return AWPU_OK;
-    if (h->track_index_cap < (size_t) U) {
-        dev_free(h->d_track_index);
-        h->track_index_cap = 0;
-        AWPU_HIP_TRY(hipMalloc(&h->d_track_index, (size_t) U * sizeof(int32_t)));
-        h->track_index_cap = U;
-    }
-    h->track_index.clear();
-    AWPU_HIP_TRY(hipMemcpy(h->d_track_index, h->index.data(), (size_t) U * sizeof(int32_t), hipMemcpyHostToDevice));
-    h->track_index = h->index;
-    return AWPU_OK;
-}
-
 }  // namespace
 
 int awpu_hip_steer_table_device(awpu_hip_t *h, const double *theta, const double *phi, int32_t n_dir, int32_t *off,
@@ -2917,17 +2717,6 @@ int awpu_hip_process_device_sums(awpu_hip_t *h, const float *d_frames, int32_t b
 }
 
 namespace {
-
-// the ingest ring and its one-block staging, allocated at first use: the ring starts zeroed (on h->stream)
-int ensure_ring(awpu_hip *h) {
-    if (h->d_ring) return AWPU_OK;
-    const size_t ring_bytes = (size_t) h->cfg.n_streams * 2048 * sizeof(float);
-    AWPU_HIP_TRY(hipMalloc(&h->d_ring, ring_bytes));
-    AWPU_HIP_TRY(hipMemsetAsync(h->d_ring, 0, ring_bytes, h->stream));
-    AWPU_HIP_TRY(hipMalloc(&h->d_datagrams, (size_t) awpu::kSamples * AWPU_DATAGRAM_BYTES));
-    h->ring_pos = 0;
-    return AWPU_OK;
-}
 
 // H2D of one block of raw datagrams + the unpack launch, enqueued on the handle's stream (no wait)
 int enqueue_ingest(awpu_hip *h, const void *datagrams, int32_t stride_bytes) {
@@ -3150,470 +2939,6 @@ int awpu_hip_ring_snapshot(awpu_hip_t *h, float *frames) {
     return AWPU_OK;
 }
 
-// ---- runs of consecutive blocks (include/awpu_hip_blocks.h) ---------------------------------------------------------------
-// A run is cut into chunks of at most max_batch blocks, and every chunk into the pieces awpu_hip_process sweeps a batch of that
-// size in (host_piece): the same launches as that call on the same snapshots, so the same bits.  Piece i gets a history
-// [n_streams][768 + 256 * piece] on the device: the 768 samples before it (the ring's snapshot for the first piece, the tail
-// of piece i-1's history after it), then its new samples.  Its snapshots' windows are cut into the layout awpu_hip_process
-// uploads (kCompact; kFull without a compact window) and swept by launch().  The host forms stage piece i + 1 in pinned memory,
-// upload it and form its history on copy_stream while piece i is cut and swept on the handle's stream; the powers of piece i
-// come back through pinned memory on copy_stream while piece i + 1 is swept.  (Pieces rather than whole chunks: the first
-// piece's staging is the one nothing hides, and the buffers are a piece long.)
-namespace {
-
-struct BlockRun {
-    const unsigned char *wire = nullptr;  // datagrams, `stride` bytes apart (host)
-    int32_t stride = 0;
-    const float *samples = nullptr;       // [n_streams][pitch] floats, host or (device) device memory
-    int64_t pitch = 0;
-    bool device = false;
-};
-
-// What a listen call (awpu_hip_listen.h) adds to a run; audio and trail are host memory in the host forms, device memory in the
-// device form.  Per piece, between its history and the ring write: the listen kernels on that history.
-struct ListenRun {
-    awpu_particle_t *listeners = nullptr;  // host, in/out
-    int32_t n = 0;
-    double theta_limit = 0.0, reference = 0.0;
-    float *audio = nullptr;
-    int64_t audio_pitch = 0;
-    awpu_particle_t *trail = nullptr;
-    bool sweep = false;                    // heatmaps asked for too
-};
-
-// piece-sized buffers of a listen run: the listeners' state, and for the host forms the way back of audio and trail
-int ensure_listen_buffers(awpu_hip *h, const ListenRun &ls, int piece, bool host) {
-    const size_t state = (size_t) ls.n * sizeof(awpu_particle_t);
-    if (h->listeners_cap < state) {
-        dev_free(h->d_listeners);
-        h->listeners_cap = 0;
-        AWPU_HIP_TRY(hipMalloc(&h->d_listeners, state));
-        h->listeners_cap = state;
-    }
-    if (!host) return AWPU_OK;
-    const size_t out_bytes = align16((size_t) ls.n * awpu::kSamples * piece * sizeof(float)) + (size_t) piece * state;
-    if (h->listen_out_cap < out_bytes) {
-        for (int b = 0; b < 2; b++) {
-            dev_free(h->d_listen_out[b]);
-            if (h->h_listen_out[b]) (void) hipHostFree(h->h_listen_out[b]);
-            h->h_listen_out[b] = nullptr;
-        }
-        h->listen_out_cap = 0;
-        for (int b = 0; b < 2; b++) {
-            AWPU_HIP_TRY(hipMalloc(&h->d_listen_out[b], out_bytes));
-            AWPU_HIP_TRY(hipHostMalloc(&h->h_listen_out[b], out_bytes, hipHostMallocDefault));
-        }
-        h->listen_out_cap = out_bytes;
-    }
-    if (ls.sweep && env().listen_stream && !h->listen_stream)
-        AWPU_HIP_TRY(hipStreamCreateWithFlags(&h->listen_stream, hipStreamNonBlocking));
-    for (hipEvent_t *ev : {&h->ev_listened[0], &h->ev_listened[1], &h->ev_listen_out[0], &h->ev_listen_out[1]})
-        if (!*ev) AWPU_HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
-    return AWPU_OK;
-}
-
-// device buffers for pieces of at most `piece` frames (and, for the host forms, the pinned staging and the second stream)
-// (a watch run's history and staging hold hist_blocks / in_blocks blocks for a piece of `piece` frames: 0 = one per frame)
-int ensure_blk_buffers(awpu_hip *h, const BlockRun &src, int piece, int width, bool sweep, int hist_blocks = 0, int in_blocks = 0) {
-    const size_t S = (size_t) h->cfg.n_streams;
-    if (hist_blocks < 1) hist_blocks = piece;
-    if (in_blocks < 1) in_blocks = piece;
-    const size_t hist_floats = S * (awpu::kBlockPrefix + (size_t) awpu::kSamples * hist_blocks);
-    if (h->blk_hist_cap < hist_floats) {
-        for (int b = 0; b < 2; b++) dev_free(h->d_blk_hist[b]);
-        h->blk_hist_cap = 0;
-        for (int b = 0; b < 2; b++) AWPU_HIP_TRY(hipMalloc(&h->d_blk_hist[b], hist_floats * sizeof(float)));
-        h->blk_hist_cap = hist_floats;
-    }
-    const size_t frames_floats = sweep ? S * width * (size_t) piece : 0;  // (a listen run without heatmaps cuts no window)
-    if (h->blk_frames_cap < frames_floats) {
-        dev_free(h->d_blk_frames);
-        h->blk_frames_cap = 0;
-        AWPU_HIP_TRY(hipMalloc(&h->d_blk_frames, frames_floats * sizeof(float)));
-        h->blk_frames_cap = frames_floats;
-    }
-    if (!h->ev_blk_ring) AWPU_HIP_TRY(hipEventCreateWithFlags(&h->ev_blk_ring, hipEventDisableTiming));
-    if (src.device) return AWPU_OK;
-    const size_t in_bytes = (size_t) awpu::kSamples * in_blocks * (src.wire ? (size_t) AWPU_DATAGRAM_BYTES : S * sizeof(float));
-    if (h->blk_in_cap < in_bytes) {
-        for (int b = 0; b < 2; b++) {
-            dev_free(h->d_blk_in[b]);
-            if (h->h_blk_in[b]) (void) hipHostFree(h->h_blk_in[b]);
-            h->h_blk_in[b] = nullptr;
-        }
-        h->blk_in_cap = 0;
-        for (int b = 0; b < 2; b++) {
-            AWPU_HIP_TRY(hipHostMalloc(&h->h_blk_in[b], in_bytes, hipHostMallocDefault));
-            AWPU_HIP_TRY(hipMalloc(&h->d_blk_in[b], in_bytes));
-        }
-        h->blk_in_cap = in_bytes;
-    }
-    const size_t out_floats = sweep ? (size_t) piece * h->cfg.pixel_count : 0;
-    if (h->blk_out_cap < out_floats) {
-        for (int b = 0; b < 2; b++) {
-            if (h->h_blk_out[b]) (void) hipHostFree(h->h_blk_out[b]);
-            h->h_blk_out[b] = nullptr;
-        }
-        h->blk_out_cap = 0;
-        for (int b = 0; b < 2; b++) AWPU_HIP_TRY(hipHostMalloc(&h->h_blk_out[b], out_floats * sizeof(float), hipHostMallocDefault));
-        h->blk_out_cap = out_floats;
-    }
-    if (!h->copy_stream) AWPU_HIP_TRY(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-    for (hipEvent_t *ev : {&h->ev_blk_in[0], &h->ev_blk_in[1], &h->ev_blk_hist[0], &h->ev_blk_hist[1], &h->ev_blk_cut[0],
-                           &h->ev_blk_cut[1], &h->ev_blk_swept[0], &h->ev_blk_swept[1], &h->ev_blk_out[0], &h->ev_blk_out[1]})
-        if (!*ev) AWPU_HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
-    return sweep ? ensure_power(h, (size_t) 2 * piece * h->cfg.pixel_count) : AWPU_OK;  // two pieces' powers: one swept, one on its way back
-}
-
-// blocks [g0, g0 + nb) of a host form into pinned staging h_blk_in[b]: tight datagrams, or rows of 256 * nb samples.  Pieces of
-// 1 MB and more are copied by up to 8 threads, each a contiguous share of the rows (the headline's 32-block pieces: 8.4 MB, 8
-// threads); where a thread cannot be started, the calling thread copies its share.
-void stage_blocks(awpu_hip *h, const BlockRun &src, int g0, int nb, int b) {
-    unsigned char *dst = static_cast<unsigned char *>(h->h_blk_in[b]);
-    const size_t n = (size_t) awpu::kSamples * nb;
-    const size_t rows = src.wire ? n : (size_t) h->cfg.n_streams;
-    const auto copy = [&](size_t r0, size_t r1) {
-        if (src.wire) {
-            const unsigned char *from = src.wire + (size_t) g0 * awpu::kSamples * src.stride;
-            if (src.stride == AWPU_DATAGRAM_BYTES) {
-                std::memcpy(dst + r0 * AWPU_DATAGRAM_BYTES, from + r0 * AWPU_DATAGRAM_BYTES, (r1 - r0) * AWPU_DATAGRAM_BYTES);
-            } else {
-                for (size_t i = r0; i < r1; i++) std::memcpy(dst + i * AWPU_DATAGRAM_BYTES, from + i * src.stride, AWPU_DATAGRAM_BYTES);
-            }
-            return;
-        }
-        for (size_t s = r0; s < r1; s++)
-            std::memcpy(dst + s * n * sizeof(float), src.samples + s * src.pitch + (size_t) g0 * awpu::kSamples, n * sizeof(float));
-    };
-    const size_t bytes = n * (src.wire ? (size_t) AWPU_DATAGRAM_BYTES : rows * sizeof(float));
-    const size_t n_threads = std::min<size_t>({8, rows, bytes >> 20});
-    if (n_threads < 2) {
-        copy(0, rows);
-        return;
-    }
-    std::vector<std::thread> pool;
-    size_t k = 1;
-    try {
-        pool.reserve(n_threads - 1);
-        for (; k < n_threads; k++) pool.emplace_back(copy, rows * k / n_threads, rows * (k + 1) / n_threads);
-    } catch (...) {  // (std::system_error must not cross the C ABI)
-    }
-    copy(0, rows / n_threads);
-    if (k < n_threads) copy(rows * k / n_threads, rows);
-    for (auto &th : pool) th.join();
-}
-
-// the run; host forms: `power` [n_blocks][pixel_count] host, synchronous; device form: `d_out` on `user` (NULL = h->stream).
-// With `ls` the run is listened to as well (awpu_hip_listen.h), and swept only if ls->sweep.
-int run_blocks(awpu_hip *h, const BlockRun &src, int n_blocks, float *power, float *d_out, hipStream_t user, const ListenRun *ls = nullptr) {
-    if (!h->parts.empty()) return fail(AWPU_ERR_STATE, "a device group does not take runs of blocks");
-    if (h->in_flight) return fail(AWPU_ERR_STATE, "an awpu_hip_process_async call is in flight on this handle: awpu_hip_wait first");
-    const awpu_hip_cfg &c = h->cfg;
-    if (c.hist != AWPU_HIST) return invalid("runs of blocks need hist 1024");
-    if (src.wire && c.n_streams > 256) return invalid("the wire carries at most 256 streams");
-    const bool sweep = !ls || ls->sweep;
-    const int chunk = std::min<int>(n_blocks, c.max_batch);
-    int rc = ls ? check_antenna(h) : AWPU_OK;
-    if (rc != AWPU_OK) return rc;
-    if (sweep) {
-        rc = check_ready(h, chunk);
-        if (rc != AWPU_OK) return rc;
-    } else {
-        AWPU_HIP_TRY(hipSetDevice(c.device));
-    }
-    std::vector<std::pair<int, int>> pieces;  // (first block, blocks): every chunk in awpu_hip_process's pieces
-    int piece_max = 1;
-    for (int c0 = 0; c0 < n_blocks; c0 += chunk) {
-        const int nc = std::min(chunk, n_blocks - c0), piece = host_piece(nc);
-        for (int k0 = 0; k0 < nc; k0 += piece) {
-            pieces.emplace_back(c0 + k0, std::min(piece, nc - k0));
-            piece_max = std::max(piece_max, pieces.back().second);
-        }
-    }
-    const bool compact = h->compact_hist > 0;
-    const int width = compact ? h->compact_hist : AWPU_HIST, lo = compact ? h->wstart : 0;
-    const bool host = !src.device;
-    rc = ensure_ring(h);
-    if (rc == AWPU_OK) rc = ensure_blk_buffers(h, src, piece_max, width, sweep);
-    if (rc == AWPU_OK && ls) rc = ensure_track_index(h);
-    if (rc == AWPU_OK && ls) rc = ensure_listen_buffers(h, *ls, piece_max, host);
-    if (rc != AWPU_OK) return rc;
-    const int S = c.n_streams, pitch = awpu::kBlockPrefix + awpu::kSamples * piece_max;
-    const size_t P = (size_t) c.pixel_count;
-    hipStream_t sw = host ? h->stream : (user ? user : h->stream);  // cut and sweep
-    hipStream_t up = host ? h->copy_stream : sw;                    // upload and history
-    // the listen kernels: a few workgroups that walk a piece block by block, so beside the sweep of the same piece where there is
-    // one (host forms), and in the caller's order on the caller's stream in the device form
-    hipStream_t li = host && sweep && h->listen_stream && env().listen_stream ? h->listen_stream : sw;
-    const bool keep_timing = h->timing;
-    const bool time_it = keep_timing && host && sweep;
-    if (!time_it) h->timing = false;  // the device form is asynchronous: the caller times its own stream; nothing swept, nothing timed
-    const int n_pieces = (int) pieces.size();
-    const size_t state = ls ? (size_t) ls->n * sizeof(awpu_particle_t) : 0;
-    bool tracking = false, fixed = false;
-    for (int l = 0; ls && l < ls->n; l++) (ls->listeners[l].steps > 0 ? tracking : fixed) = true;
-    const auto audio_bytes = [&](int nb) { return align16((size_t) ls->n * awpu::kSamples * nb * sizeof(float)); };
-    // host forms: piece j's powers, in h_blk_out[j & 1] once ev_blk_out[j & 1] has passed, to the caller's rows; its audio rows and
-    // trail likewise out of h_listen_out[j & 1]
-    const auto deliver = [&](int j) -> int {
-        const int g0 = pieces[j].first, nb = pieces[j].second;
-        if (sweep) {
-            AWPU_HIP_TRY(hipEventSynchronize(h->ev_blk_out[j & 1]));
-            std::memcpy(power + (size_t) g0 * P, h->h_blk_out[j & 1], (size_t) nb * P * sizeof(float));
-        }
-        if (ls) {
-            AWPU_HIP_TRY(hipEventSynchronize(h->ev_listen_out[j & 1]));
-            const unsigned char *from = h->h_listen_out[j & 1];
-            const size_t row = (size_t) awpu::kSamples * nb;
-            for (int l = 0; l < ls->n; l++)
-                std::memcpy(ls->audio + (size_t) l * ls->audio_pitch + (size_t) awpu::kSamples * g0, from + l * row * sizeof(float), row * sizeof(float));
-            if (ls->trail) std::memcpy(ls->trail + (size_t) g0 * ls->n, from + audio_bytes(nb), (size_t) nb * state);
-        }
-        return AWPU_OK;
-    };
-    // host forms: piece j's powers, and what was heard in it, into pinned memory behind the kernels that write them
-    const auto fetch = [&](int j) -> int {
-        const int b = j & 1, nb = pieces[j].second;
-        if (sweep) {
-            AWPU_HIP_TRY(hipStreamWaitEvent(up, h->ev_blk_swept[b], 0));
-            AWPU_HIP_TRY(hipMemcpyAsync(h->h_blk_out[b], h->d_power + (size_t) b * piece_max * P, (size_t) nb * P * sizeof(float),
-                                        hipMemcpyDeviceToHost, up));
-            AWPU_HIP_TRY(hipEventRecord(h->ev_blk_out[b], up));
-        }
-        if (ls) {
-            AWPU_HIP_TRY(hipStreamWaitEvent(up, h->ev_listened[b], 0));
-            AWPU_HIP_TRY(hipMemcpyAsync(h->h_listen_out[b], h->d_listen_out[b], audio_bytes(nb) + (ls->trail ? (size_t) nb * state : 0),
-                                        hipMemcpyDeviceToHost, up));
-            AWPU_HIP_TRY(hipEventRecord(h->ev_listen_out[b], up));
-        }
-        return AWPU_OK;
-    };
-    std::vector<awpu_particle_t> heard(ls ? ls->n : 0);  // the listeners after the run
-    const auto body = [&]() -> int {
-        // whatever is queued on the handle's stream -- the ring's zeroing, the ring writes and cuts of a device-form run not yet
-        // over -- comes first: the upload side reads the ring and rewrites the histories
-        if (up != h->stream) {
-            AWPU_HIP_TRY(hipEventRecord(h->ev_blk_ring, h->stream));
-            AWPU_HIP_TRY(hipStreamWaitEvent(up, h->ev_blk_ring, 0));
-        }
-        if (ls) AWPU_HIP_TRY(hipMemcpyAsync(h->d_listeners, ls->listeners, state, hipMemcpyHostToDevice, up));  // (before the first history)
-        const float *prev = h->d_ring + h->ring_pos + awpu::kSamples;  // the last 768 samples of the current snapshot
-        long long prev_pitch = 2048;
-        for (int i = 0; i < n_pieces; i++) {
-            const int b = i & 1, g0 = pieces[i].first, nb = pieces[i].second;
-            float *hist = h->d_blk_hist[b];
-            if (host) {
-                if (i >= 2) AWPU_HIP_TRY(hipEventSynchronize(h->ev_blk_in[b]));  // piece i-2's upload out of h_blk_in[b] is over
-                stage_blocks(h, src, g0, nb, b);
-                const size_t bytes = (size_t) awpu::kSamples * nb * (src.wire ? (size_t) AWPU_DATAGRAM_BYTES : S * sizeof(float));
-                AWPU_HIP_TRY(hipMemcpyAsync(h->d_blk_in[b], h->h_blk_in[b], bytes, hipMemcpyHostToDevice, up));
-                AWPU_HIP_TRY(hipEventRecord(h->ev_blk_in[b], up));
-                // piece i-2's windows are cut out of d_blk_hist[b], and its listeners have heard it
-                if (i >= 2 && sweep) AWPU_HIP_TRY(hipStreamWaitEvent(up, h->ev_blk_cut[b], 0));
-                if (i >= 2 && ls) AWPU_HIP_TRY(hipStreamWaitEvent(up, h->ev_listened[b], 0));
-            }
-            AWPU_HIP_TRY(awpu::launch_copy_rows(prev, prev_pitch, hist, pitch, awpu::kBlockPrefix, S, up));
-            if (src.wire) {
-                AWPU_HIP_TRY(awpu::launch_unpack_blocks(h->d_blk_in[b], nb, S, hist, pitch, awpu::kBlockPrefix, up));
-            } else {
-                const float *rows = host ? static_cast<const float *>(h->d_blk_in[b]) : src.samples + (size_t) g0 * awpu::kSamples;
-                AWPU_HIP_TRY(awpu::launch_copy_rows(rows, host ? (long long) awpu::kSamples * nb : (long long) src.pitch,
-                                                    hist + awpu::kBlockPrefix, pitch, awpu::kSamples * nb, S, up));
-            }
-            if (host) {
-                AWPU_HIP_TRY(hipEventRecord(h->ev_blk_hist[b], up));
-                AWPU_HIP_TRY(hipStreamWaitEvent(sw, h->ev_blk_hist[b], 0));
-                if (li != sw) AWPU_HIP_TRY(hipStreamWaitEvent(li, h->ev_blk_hist[b], 0));
-            }
-            if (sweep) {
-                AWPU_HIP_TRY(awpu::launch_cut_windows(hist, pitch, S, nb, lo, width, h->d_blk_frames, sw));
-                if (host) AWPU_HIP_TRY(hipEventRecord(h->ev_blk_cut[b], sw));
-                if (time_it && i == 0) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, sw));
-                h->timing = false;
-                rc = launch(h, h->d_blk_frames, nb, host ? h->d_power + (size_t) b * piece_max * P : d_out + (size_t) g0 * P, sw,
-                            compact ? kCompact : kFull);
-                h->timing = time_it;
-                if (rc != AWPU_OK) return rc;
-                if (host) AWPU_HIP_TRY(hipEventRecord(h->ev_blk_swept[b], sw));
-            }
-            if (ls) {
-                // (d_listen_out[b] is free: piece i-2's way back out of it was queued on `up` before this piece's history)
-                awpu::ListenArgs a{};
-                a.hist = hist;
-                a.pitch = pitch;
-                a.n_blocks = nb;
-                a.xyz = h->d_xyz;
-                a.n = (int) (h->antenna.size() / 3);
-                a.index = h->d_track_index;
-                a.usable = h->usable();
-                a.listeners = h->d_listeners;
-                a.n_listeners = ls->n;
-                a.theta_limit = ls->theta_limit;
-                a.reference = ls->reference;
-                if (host) {
-                    a.audio = reinterpret_cast<float *>(h->d_listen_out[b]);
-                    a.audio_pitch = (long long) awpu::kSamples * nb;
-                    a.trail = ls->trail ? h->d_listen_out[b] + audio_bytes(nb) : nullptr;
-                } else {
-                    a.audio = ls->audio + (size_t) awpu::kSamples * g0;
-                    a.audio_pitch = ls->audio_pitch;
-                    a.trail = ls->trail ? ls->trail + (size_t) g0 * ls->n : nullptr;
-                }
-                AWPU_HIP_TRY(awpu::launch_listen(a, tracking, fixed, li));
-                if (host) AWPU_HIP_TRY(hipEventRecord(h->ev_listened[b], li));
-            }
-            if (host) {
-                if (i >= 1) {  // piece i-1's results go back into pinned memory behind its kernels, while piece i is swept ...
-                    rc = fetch(i - 1);
-                    if (rc != AWPU_OK) return rc;
-                }
-                if (i >= 2) {  // ... and piece i-2's, long back, go to the caller before h_blk_out[b] is written again
-                    rc = deliver(i - 2);
-                    if (rc != AWPU_OK) return rc;
-                }
-            }
-            prev = hist + (size_t) awpu::kSamples * nb;
-            prev_pitch = pitch;
-        }
-        const int last_b = (n_pieces - 1) & 1, last_nb = pieces.back().second;
-        if (time_it) AWPU_HIP_TRY(hipEventRecord(h->ev_end, sw));
-        // the ring as n_blocks ingests leave it: its snapshot = the last 1024 samples of the last history
-        const int pos = (int) ((h->ring_pos + (long long) awpu::kSamples * n_blocks) % AWPU_HIST);
-        AWPU_HIP_TRY(awpu::launch_ring_write(h->d_blk_hist[last_b], pitch, awpu::kSamples * (last_nb - 1), S, h->d_ring, pos, sw));
-        h->ring_pos = pos;
-        if (ls) AWPU_HIP_TRY(hipMemcpyAsync(heard.data(), h->d_listeners, state, hipMemcpyDeviceToHost, li));
-        if (!host) {
-            if (sw != h->stream) {  // later calls on the ring (the handle's stream) come after this one
-                AWPU_HIP_TRY(hipEventRecord(h->ev_blk_ring, sw));
-                AWPU_HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_blk_ring, 0));
-            }
-            if (ls) AWPU_HIP_TRY(hipStreamSynchronize(sw));  // the listeners' state is host memory
-            return AWPU_OK;
-        }
-        rc = fetch(n_pieces - 1);
-        if (rc != AWPU_OK) return rc;
-        for (int j = std::max(0, n_pieces - 2); j < n_pieces; j++) {
-            rc = deliver(j);
-            if (rc != AWPU_OK) return rc;
-        }
-        AWPU_HIP_TRY(hipStreamSynchronize(up));
-        if (li != sw) AWPU_HIP_TRY(hipStreamSynchronize(li));
-        return wait_and_time(h);
-    };
-    rc = body();
-    h->timing = keep_timing;
-    if (rc != AWPU_OK && host) {  // nothing of the call may still read the caller's or the handle's buffers
-        (void) hipStreamSynchronize(h->copy_stream);
-        if (h->listen_stream) (void) hipStreamSynchronize(h->listen_stream);
-        (void) hipStreamSynchronize(h->stream);
-    }
-    if (rc == AWPU_OK && ls) std::memcpy(ls->listeners, heard.data(), state);
-    return rc;
-}
-
-// the checks of a listen call that read no handle; then the run
-int listen_run(awpu_hip *h, const BlockRun &src, int n_blocks, awpu_particle_t *listeners, int32_t n, double theta_limit, double reference,
-               float *audio, int64_t audio_pitch, awpu_particle_t *trail, float *power, hipStream_t user) {
-    if (!listeners || !audio) return invalid("null argument");
-    if (int rc = check_particles(listeners, n, theta_limit, reference)) return rc;
-    if (audio_pitch < (int64_t) awpu::kSamples * n_blocks) return invalid("audio_pitch below 256 * n_blocks");
-    AWPU_CTX(h);
-    ListenRun ls;
-    ls.listeners = listeners;
-    ls.n = n;
-    ls.theta_limit = theta_limit;
-    ls.reference = reference;
-    ls.audio = audio;
-    ls.audio_pitch = audio_pitch;
-    ls.trail = trail;
-    ls.sweep = power != nullptr;
-    return run_blocks(h, src, n_blocks, src.device ? nullptr : power, src.device ? power : nullptr, user, &ls);
-}
-
-}  // namespace
-
-int awpu_hip_process_blocks(awpu_hip_t *h, const void *datagrams, int32_t stride_bytes, int32_t n_blocks, float *power) {
-    // (arguments first: none of these reads the handle)
-    if (!h) return invalid("null handle");
-    if (!datagrams || !power) return invalid("null argument");
-    if (n_blocks < 1) return invalid("n_blocks below 1");
-    if (stride_bytes < AWPU_DATAGRAM_BYTES) return invalid("datagram stride below 1032 bytes");
-    AWPU_CTX(h);
-    BlockRun src;
-    src.wire = static_cast<const unsigned char *>(datagrams);
-    src.stride = stride_bytes;
-    return run_blocks(h, src, n_blocks, power, nullptr, nullptr);
-}
-
-int awpu_hip_process_samples(awpu_hip_t *h, const float *samples, int64_t pitch, int32_t n_blocks, float *power) {
-    if (!h) return invalid("null handle");
-    if (!samples || !power) return invalid("null argument");
-    if (n_blocks < 1) return invalid("n_blocks below 1");
-    if (pitch < (int64_t) awpu::kSamples * n_blocks) return invalid("pitch below 256 * n_blocks");
-    AWPU_CTX(h);
-    BlockRun src;
-    src.samples = samples;
-    src.pitch = pitch;
-    return run_blocks(h, src, n_blocks, power, nullptr, nullptr);
-}
-
-int awpu_hip_process_samples_device(awpu_hip_t *h, const float *d_samples, int64_t pitch, int32_t n_blocks, float *d_power,
-                                    void *stream) {
-    if (!h) return invalid("null handle");
-    if (!d_samples || !d_power) return invalid("null argument");
-    if (n_blocks < 1) return invalid("n_blocks below 1");
-    if (pitch < (int64_t) awpu::kSamples * n_blocks) return invalid("pitch below 256 * n_blocks");
-    AWPU_CTX(h);
-    BlockRun src;
-    src.samples = d_samples;
-    src.pitch = pitch;
-    src.device = true;
-    return run_blocks(h, src, n_blocks, nullptr, d_power, static_cast<hipStream_t>(stream));
-}
-
-// ---- listening to runs of blocks (include/awpu_hip_listen.h; kernels in track_kernels.hip) -----------------------------------
-
-int awpu_hip_listen_blocks(awpu_hip_t *h, const void *datagrams, int32_t stride_bytes, int32_t n_blocks, awpu_particle_t *listeners,
-                           int32_t n, double theta_limit, double reference, float *audio, int64_t audio_pitch, awpu_particle_t *trail,
-                           float *power) {
-    if (!h) return invalid("null handle");
-    if (!datagrams) return invalid("null argument");
-    if (n_blocks < 1) return invalid("n_blocks below 1");
-    if (stride_bytes < AWPU_DATAGRAM_BYTES) return invalid("datagram stride below 1032 bytes");
-    BlockRun src;
-    src.wire = static_cast<const unsigned char *>(datagrams);
-    src.stride = stride_bytes;
-    return listen_run(h, src, n_blocks, listeners, n, theta_limit, reference, audio, audio_pitch, trail, power, nullptr);
-}
-
-int awpu_hip_listen_samples(awpu_hip_t *h, const float *samples, int64_t pitch, int32_t n_blocks, awpu_particle_t *listeners, int32_t n,
-                            double theta_limit, double reference, float *audio, int64_t audio_pitch, awpu_particle_t *trail,
-                            float *power) {
-    if (!h) return invalid("null handle");
-    if (!samples) return invalid("null argument");
-    if (n_blocks < 1) return invalid("n_blocks below 1");
-    if (pitch < (int64_t) awpu::kSamples * n_blocks) return invalid("pitch below 256 * n_blocks");
-    BlockRun src;
-    src.samples = samples;
-    src.pitch = pitch;
-    return listen_run(h, src, n_blocks, listeners, n, theta_limit, reference, audio, audio_pitch, trail, power, nullptr);
-}
-
-int awpu_hip_listen_samples_device(awpu_hip_t *h, const float *d_samples, int64_t pitch, int32_t n_blocks, awpu_particle_t *listeners,
-                                   int32_t n, double theta_limit, double reference, float *d_audio, int64_t audio_pitch,
-                                   awpu_particle_t *d_trail, float *d_power, void *stream) {
-    if (!h) return invalid("null handle");
-    if (!d_samples) return invalid("null argument");
-    if (n_blocks < 1) return invalid("n_blocks below 1");
-    if (pitch < (int64_t) awpu::kSamples * n_blocks) return invalid("pitch below 256 * n_blocks");
-    BlockRun src;
-    src.samples = d_samples;
-    src.pitch = pitch;
-    src.device = true;
-    return listen_run(h, src, n_blocks, listeners, n, theta_limit, reference, d_audio, audio_pitch, d_trail, d_power,
-                      static_cast<hipStream_t>(stream));
-}
-
 int awpu_hip_heatmap_u8_device(awpu_hip_t *h, const float *d_power, int32_t n, int32_t batch, float *d_peak,
                                int32_t peak_given, uint8_t *d_pix, void *stream) {
     if (h && !h->parts.empty()) h = h->parts[0];  // not pixel-sharded: a device group answers with its first device
@@ -3624,28 +2949,6 @@ int awpu_hip_heatmap_u8_device(awpu_hip_t *h, const float *d_power, int32_t n, i
     AWPU_HIP_TRY(awpu::launch_heatmap(d_power, n, batch, d_peak, peak_given != 0, d_pix, s));
     return AWPU_OK;
 }
-
-namespace {
-
-// h->d_taps = the column and row taps of rows x cols -> out_rows x out_cols, rebuilt when the shape changes
-int ensure_taps(awpu_hip *h, int rows, int cols, int out_rows, int out_cols, hipStream_t s) {
-    const int key[4] = {rows, cols, out_rows, out_cols};
-    if (!h->d_taps || std::memcmp(key, h->taps_key, sizeof(key)) != 0) {
-        std::vector<awpu::ResizeTap> taps((size_t) out_cols + out_rows);
-        awpu::resize_taps(cols, out_cols, true, taps.data());
-        awpu::resize_taps(rows, out_rows, false, taps.data() + out_cols);
-        AWPU_HIP_TRY(hipStreamSynchronize(s));  // an earlier launch may still read the old taps
-        retire_live_graphs(h);
-        dev_free(h->d_taps);
-        AWPU_HIP_TRY(hipMalloc(&h->d_taps, taps.size() * sizeof(awpu::ResizeTap)));
-        AWPU_HIP_TRY(hipMemcpy(h->d_taps, taps.data(), taps.size() * sizeof(awpu::ResizeTap), hipMemcpyHostToDevice));
-        std::memcpy(h->taps_key, key, sizeof(key));
-        h->taps_band_rows = awpu::watch_band_rows(taps.data() + out_cols, rows, out_rows);
-    }
-    return AWPU_OK;
-}
-
-}  // namespace
 
 int awpu_hip_upscale_u8_device(awpu_hip_t *h, const uint8_t *d_pix, int32_t rows, int32_t cols, int32_t batch,
                                const uint8_t *d_colormap, uint8_t *d_out, int32_t out_rows, int32_t out_cols,
@@ -3689,326 +2992,6 @@ int awpu_hip_resize_linear_u8(const uint8_t *pix, int32_t rows, int32_t cols, ui
             out[(size_t) dy * out_cols + dx] = awpu::resize_combine(sums[dx], sums[(size_t) out_cols + dx], ty.w0, ty.w1);
     }
     return AWPU_OK;
-}
-
-// ---- watching runs of blocks (include/awpu_hip_watch.h; kernels in watch_kernels.hip) ------------------------------------------
-// The run-of-blocks pipeline above with two differences.  A piece is nf SHOWN frames (awpu_hip_process's pieces of the chunks of
-// shown frames), and its history holds only the blocks its snapshots read (watch_kernels.h: 4 + min(every, 4) * (nf - 1) slots
-// of 256 samples), each piece's formed on its own -- blocks from before the call out of the ring's snapshot, the rest staged and
-// uploaded -- instead of continuing the piece before it.  And behind a piece's sweep comes its display step: launch_heatmap for
-// the whole piece, then the large image, both on the sweep's stream; the host forms bring images and powers back through pinned
-// memory on copy_stream while the next piece is swept.  The ring is written once, at the end, from the last four blocks of the
-// call: the tail of the last piece's history when the last block is shown, a four-slot history of its own otherwise.
-namespace {
-
-struct WatchRun {
-    awpu_watch_t w{};
-    int n_frames = 0;
-    uint8_t *image = nullptr, *big = nullptr;  // host memory in the host forms, device memory in the device form
-    float *power = nullptr;
-};
-
-// fn(lo, hi) over [0, n) by up to 8 threads when `bytes` (what the whole range copies) is 1 MB and more; like stage_blocks
-void parallel_ranges(size_t n, size_t bytes, const std::function<void(size_t, size_t)> &fn) {
-    const size_t n_threads = std::min<size_t>({8, n, bytes >> 20});
-    if (n_threads < 2) {
-        fn((size_t) 0, n);
-        return;
-    }
-    std::vector<std::thread> pool;
-    size_t k = 1;
-    try {
-        pool.reserve(n_threads - 1);
-        for (; k < n_threads; k++) pool.emplace_back(fn, n * k / n_threads, n * (k + 1) / n_threads);
-    } catch (...) {  // (std::system_error must not cross the C ABI)
-    }
-    fn((size_t) 0, n / n_threads);
-    if (k < n_threads) fn(n * k / n_threads, n);
-    for (auto &th : pool) th.join();
-}
-
-void parallel_copy(void *dst, const void *src, size_t bytes) {
-    parallel_ranges(bytes >> 16, bytes, [&](size_t lo, size_t hi) {  // 64 KB grains, the rest with the last
-        const size_t from = lo << 16, to = hi == (bytes >> 16) ? bytes : hi << 16;
-        std::memcpy(static_cast<unsigned char *>(dst) + from, static_cast<const unsigned char *>(src) + from, to - from);
-    });
-    if ((bytes >> 16) == 0) std::memcpy(dst, src, bytes);
-}
-
-// slots [q, slots) of a piece's history (watch_kernels.h) into pinned h_blk_in[b]: tight datagrams, or rows of 256 * (slots - q)
-void stage_watch(awpu_hip *h, const BlockRun &src, int b0, int every, int q, int slots, int b) {
-    unsigned char *dst = static_cast<unsigned char *>(h->h_blk_in[b]);
-    const int m = std::min(every, 4), ns = slots - q;
-    const size_t S = (size_t) h->cfg.n_streams, block_bytes = (size_t) awpu::kSamples * (src.wire ? (size_t) AWPU_DATAGRAM_BYTES : S * sizeof(float));
-    parallel_ranges((size_t) ns, block_bytes * ns, [&](size_t lo, size_t hi) {
-        for (size_t k = lo; k < hi; k++) {
-            const size_t blk = (size_t) awpu::watch_slot_block(q + (int) k, b0, every, m);
-            if (src.wire) {
-                const unsigned char *from = src.wire + blk * awpu::kSamples * src.stride;
-                unsigned char *to = dst + k * awpu::kSamples * AWPU_DATAGRAM_BYTES;
-                if (src.stride == AWPU_DATAGRAM_BYTES) {
-                    std::memcpy(to, from, (size_t) awpu::kSamples * AWPU_DATAGRAM_BYTES);
-                } else {
-                    for (int i = 0; i < awpu::kSamples; i++) std::memcpy(to + (size_t) i * AWPU_DATAGRAM_BYTES, from + (size_t) i * src.stride, AWPU_DATAGRAM_BYTES);
-                }
-            } else {
-                for (size_t s = 0; s < S; s++)
-                    std::memcpy(dst + ((s * ns + k) * awpu::kSamples) * sizeof(float), src.samples + s * src.pitch + blk * awpu::kSamples,
-                                awpu::kSamples * sizeof(float));
-            }
-        }
-    });
-}
-
-int ensure_watch_buffers(awpu_hip *h, size_t bytes, bool host) {
-    if (h->watch_cap < bytes) {
-        for (int b = 0; b < 2; b++) dev_free(h->d_watch[b]);
-        h->watch_cap = 0;
-        for (int b = 0; b < 2; b++) AWPU_HIP_TRY(hipMalloc(&h->d_watch[b], bytes));
-        h->watch_cap = bytes;
-    }
-    if (host && h->watch_host_cap < bytes) {
-        for (int b = 0; b < 2; b++) {
-            if (h->h_watch[b]) (void) hipHostFree(h->h_watch[b]);
-            h->h_watch[b] = nullptr;
-        }
-        h->watch_host_cap = 0;
-        for (int b = 0; b < 2; b++) AWPU_HIP_TRY(hipHostMalloc(&h->h_watch[b], bytes, hipHostMallocDefault));
-        h->watch_host_cap = bytes;
-    }
-    return AWPU_OK;
-}
-
-int run_watch(awpu_hip *h, const BlockRun &src, int n_blocks, const WatchRun &wr, hipStream_t user) {
-    if (!h->parts.empty()) return fail(AWPU_ERR_STATE, "a device group does not take runs of blocks");
-    if (h->in_flight) return fail(AWPU_ERR_STATE, "an awpu_hip_process_async call is in flight on this handle: awpu_hip_wait first");
-    const awpu_hip_cfg &c = h->cfg;
-    const awpu_watch_t &w = wr.w;
-    if (c.hist != AWPU_HIST) return invalid("runs of blocks need hist 1024");
-    if (src.wire && c.n_streams > 256) return invalid("the wire carries at most 256 streams");
-    if (c.pixel_count != c.n_pixels) return invalid("the display step needs the whole grid on this handle");
-    if ((long long) w.rows * w.cols != c.n_pixels) return invalid("rows x cols must be the grid");
-    const int n_frames = wr.n_frames, chunk = std::max(1, std::min<int>(n_frames, c.max_batch));
-    int rc = check_ready(h, chunk);
-    if (rc != AWPU_OK) return rc;
-    std::vector<std::pair<int, int>> pieces;  // (first frame, frames): every chunk of shown frames in awpu_hip_process's pieces
-    int piece_max = 1;
-    for (int c0 = 0; c0 < n_frames; c0 += chunk) {
-        const int nc = std::min(chunk, n_frames - c0), piece = host_piece(nc);
-        for (int k0 = 0; k0 < nc; k0 += piece) {
-            pieces.emplace_back(c0 + k0, std::min(piece, nc - k0));
-            piece_max = std::max(piece_max, pieces.back().second);
-        }
-    }
-    const int n_pieces = (int) pieces.size();
-    const bool compact = h->compact_hist > 0;
-    const int width = compact ? h->compact_hist : AWPU_HIST, lo = compact ? h->wstart : 0;
-    const bool host = !src.device;
-    const int S = c.n_streams, m = std::min(w.every, 4), slots_max = awpu::watch_slots(w.every, piece_max), pitch = awpu::kSamples * slots_max;
-    const size_t P = (size_t) c.pixel_count, big_bytes = (size_t) w.out_rows * w.out_cols * (w.d_colormap ? 3 : 1);
-    const bool want_small = wr.image || wr.big;
-    // the last block of the call shown: the ring's new snapshot is the tail of the last piece's history
-    const bool own_tail = n_frames == 0 || w.first + (n_frames - 1) * w.every != n_blocks - 1;
-    const size_t small_off = align16(sizeof(float) * piece_max), big_off = small_off + align16((size_t) piece_max * P);
-    hipStream_t sw = host ? h->stream : (user ? user : h->stream);  // cut, sweep, display
-    rc = ensure_ring(h);
-    if (rc == AWPU_OK) rc = ensure_blk_buffers(h, src, piece_max, width, true, slots_max - 3, slots_max);
-    if (rc == AWPU_OK && !host && !wr.power) rc = ensure_power(h, (size_t) piece_max * P);
-    if (rc == AWPU_OK && want_small) rc = ensure_watch_buffers(h, big_off + (host && wr.big ? (size_t) piece_max * big_bytes : 0), host);
-    if (rc == AWPU_OK && wr.big) rc = ensure_taps(h, w.rows, w.cols, w.out_rows, w.out_cols, sw);
-    if (rc != AWPU_OK) return rc;
-    hipStream_t up = host ? h->copy_stream : sw;  // upload and history
-    const bool keep_timing = h->timing;
-    const bool time_it = keep_timing && host && n_pieces > 0;
-    if (!time_it) h->timing = false;  // the device form is asynchronous: the caller times its own stream; nothing swept, nothing timed
-    // host forms: piece j's results, in pinned memory once ev_blk_out[j & 1] has passed, to the caller's rows
-    const auto deliver = [&](int j) -> int {
-        const int b = j & 1, j0 = pieces[j].first, nf = pieces[j].second;
-        AWPU_HIP_TRY(hipEventSynchronize(h->ev_blk_out[b]));
-        if (wr.power) std::memcpy(wr.power + (size_t) j0 * P, h->h_blk_out[b], (size_t) nf * P * sizeof(float));
-        if (wr.image) std::memcpy(wr.image + (size_t) j0 * P, h->h_watch[b] + small_off, (size_t) nf * P);
-        if (wr.big) parallel_copy(wr.big + (size_t) j0 * big_bytes, h->h_watch[b] + big_off, (size_t) nf * big_bytes);
-        return AWPU_OK;
-    };
-    // host forms: piece j's results into pinned memory behind the kernels that write them
-    const auto fetch = [&](int j) -> int {
-        const int b = j & 1, nf = pieces[j].second;
-        AWPU_HIP_TRY(hipStreamWaitEvent(up, h->ev_blk_swept[b], 0));
-        if (wr.power)
-            AWPU_HIP_TRY(hipMemcpyAsync(h->h_blk_out[b], h->d_power + (size_t) b * piece_max * P, (size_t) nf * P * sizeof(float), hipMemcpyDeviceToHost, up));
-        if (wr.image) AWPU_HIP_TRY(hipMemcpyAsync(h->h_watch[b] + small_off, h->d_watch[b] + small_off, (size_t) nf * P, hipMemcpyDeviceToHost, up));
-        if (wr.big) AWPU_HIP_TRY(hipMemcpyAsync(h->h_watch[b] + big_off, h->d_watch[b] + big_off, (size_t) nf * big_bytes, hipMemcpyDeviceToHost, up));
-        AWPU_HIP_TRY(hipEventRecord(h->ev_blk_out[b], up));
-        return AWPU_OK;
-    };
-    const auto body = [&]() -> int {
-        // whatever is queued on the handle's stream comes first: the upload side reads the ring and rewrites the histories
-        if (up != h->stream) {
-            AWPU_HIP_TRY(hipEventRecord(h->ev_blk_ring, h->stream));
-            AWPU_HIP_TRY(hipStreamWaitEvent(up, h->ev_blk_ring, 0));
-        }
-        const float *snapshot = h->d_ring + h->ring_pos;  // blocks -4 .. -1 of the call
-        int fetched = 0, delivered = 0;
-        for (int i = 0; i < n_pieces + (own_tail ? 1 : 0); i++) {
-            const bool tail = i == n_pieces;  // no frame: the last four blocks of the call, for the ring
-            const int b = i & 1, j0 = tail ? 0 : pieces[i].first, nf = tail ? 1 : pieces[i].second;
-            const int b0 = tail ? n_blocks - 1 : w.first + j0 * w.every, every = tail ? 1 : w.every;
-            const int slots = awpu::watch_slots(every, nf), q = std::max(0, std::min(3 - b0, 4));  // q slots hold blocks from before the call
-            float *hist = h->d_blk_hist[b];
-            if (host) {
-                if (i >= 2) AWPU_HIP_TRY(hipEventSynchronize(h->ev_blk_in[b]));  // piece i-2's upload out of h_blk_in[b] is over
-                stage_watch(h, src, b0, every, q, slots, b);
-                const size_t bytes = (size_t) awpu::kSamples * (slots - q) * (src.wire ? (size_t) AWPU_DATAGRAM_BYTES : S * sizeof(float));
-                AWPU_HIP_TRY(hipMemcpyAsync(h->d_blk_in[b], h->h_blk_in[b], bytes, hipMemcpyHostToDevice, up));
-                AWPU_HIP_TRY(hipEventRecord(h->ev_blk_in[b], up));
-                if (i >= 2) AWPU_HIP_TRY(hipStreamWaitEvent(up, h->ev_blk_cut[b], 0));  // piece i-2's windows are cut out of d_blk_hist[b]
-                if (q > 0) AWPU_HIP_TRY(awpu::launch_watch_gather(nullptr, 0, snapshot, b0, every, S, hist, pitch, 0, q, up));
-                if (src.wire) {
-                    AWPU_HIP_TRY(awpu::launch_unpack_blocks(h->d_blk_in[b], slots - q, S, hist, pitch, awpu::kSamples * q, up));
-                } else {
-                    const long long n = (long long) awpu::kSamples * (slots - q);
-                    AWPU_HIP_TRY(awpu::launch_copy_rows(static_cast<const float *>(h->d_blk_in[b]), n, hist + awpu::kSamples * q, pitch, (int) n, S, up));
-                }
-                AWPU_HIP_TRY(hipEventRecord(h->ev_blk_hist[b], up));
-                AWPU_HIP_TRY(hipStreamWaitEvent(sw, h->ev_blk_hist[b], 0));
-            } else {
-                AWPU_HIP_TRY(awpu::launch_watch_gather(src.samples, src.pitch, snapshot, b0, every, S, hist, pitch, 0, slots, sw));
-            }
-            if (!tail) {
-                AWPU_HIP_TRY(awpu::launch_watch_cut(hist, pitch, S, nf, awpu::kSamples * m, lo, width, h->d_blk_frames, sw));
-                if (host) AWPU_HIP_TRY(hipEventRecord(h->ev_blk_cut[b], sw));
-                if (time_it && i == 0) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, sw));
-                float *d_pow = host ? h->d_power + (size_t) b * piece_max * P : (wr.power ? wr.power + (size_t) j0 * P : h->d_power);
-                h->timing = false;
-                rc = launch(h, h->d_blk_frames, nf, d_pow, sw, compact ? kCompact : kFull);
-                h->timing = time_it;
-                if (rc != AWPU_OK) return rc;
-                if (want_small) {
-                    uint8_t *scratch = h->d_watch[host ? b : 0];
-                    uint8_t *d_small = host || !wr.image ? scratch + small_off : wr.image + (size_t) j0 * P;
-                    AWPU_HIP_TRY(awpu::launch_heatmap(d_pow, (int) P, nf, reinterpret_cast<float *>(scratch), false, d_small, sw));
-                    if (wr.big)
-                        AWPU_HIP_TRY(awpu::launch_watch_upscale(d_small, w.rows, w.cols, nf, h->d_taps, h->taps_band_rows, w.d_colormap, w.flip != 0,
-                                                                host ? scratch + big_off : wr.big + (size_t) j0 * big_bytes, w.out_rows,
-                                                                w.out_cols, sw));
-                }
-                if (host) AWPU_HIP_TRY(hipEventRecord(h->ev_blk_swept[b], sw));
-            }
-            if (host) {
-                if (i >= 1 && fetched < n_pieces) {  // piece i-1's results go back into pinned memory while piece i is swept ...
-                    rc = fetch(fetched++);
-                    if (rc != AWPU_OK) return rc;
-                }
-                if (i >= 2 && delivered < n_pieces) {  // ... and piece i-2's go to the caller before its pinned buffers are written again
-                    rc = deliver(delivered++);
-                    if (rc != AWPU_OK) return rc;
-                }
-            }
-        }
-        if (time_it) AWPU_HIP_TRY(hipEventRecord(h->ev_end, sw));
-        // the ring as n_blocks ingests leave it: its snapshot = the last four blocks of the call
-        const int pos = (int) ((h->ring_pos + (long long) awpu::kSamples * n_blocks) % AWPU_HIST);
-        const float *last_hist = h->d_blk_hist[(own_tail ? n_pieces : n_pieces - 1) & 1];
-        const int last = own_tail ? 0 : awpu::kSamples * (awpu::watch_slots(w.every, pieces.back().second) - 4);
-        AWPU_HIP_TRY(awpu::launch_ring_write(last_hist, pitch, last, S, h->d_ring, pos, sw));
-        h->ring_pos = pos;
-        if (!host) {
-            if (sw != h->stream) {  // later calls on the ring (the handle's stream) come after this one
-                AWPU_HIP_TRY(hipEventRecord(h->ev_blk_ring, sw));
-                AWPU_HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_blk_ring, 0));
-            }
-            return AWPU_OK;
-        }
-        while (fetched < n_pieces) {
-            rc = fetch(fetched++);
-            if (rc != AWPU_OK) return rc;
-        }
-        while (delivered < n_pieces) {
-            rc = deliver(delivered++);
-            if (rc != AWPU_OK) return rc;
-        }
-        AWPU_HIP_TRY(hipStreamSynchronize(up));
-        return wait_and_time(h);
-    };
-    rc = body();
-    h->timing = keep_timing;
-    if (rc != AWPU_OK && host) {  // nothing of the call may still read the caller's or the handle's buffers
-        (void) hipStreamSynchronize(h->copy_stream);
-        (void) hipStreamSynchronize(h->stream);
-    }
-    return rc;
-}
-
-// the checks of a watch call that read no handle; then the run
-int watch_run(awpu_hip *h, const BlockRun &src, int n_blocks, const awpu_watch_t *w, uint8_t *image, uint8_t *big, float *power, hipStream_t user) {
-    if (!w) return invalid("null argument");
-    if (!image && !big && !power) return invalid("no output asked for");
-    if (w->every < 1 || w->every > AWPU_WATCH_MAX_EVERY) return invalid("every outside [1, 1024]");
-    if (w->first < 0) return invalid("first below 0");
-    if (w->flip != 0 && w->flip != 1) return invalid("flip is 0 or 1");
-    if (w->rows < 1 || w->cols < 1) return invalid("rows and cols must be positive");
-    if (big && (w->out_rows < w->rows || w->out_cols < w->cols)) return invalid("upscale only: out >= in");
-    if (big && w->cols > AWPU_WATCH_MAX_COLS) return invalid("compact image wider than AWPU_WATCH_MAX_COLS");
-    WatchRun wr;
-    wr.w = *w;
-    int32_t next_first = 0;
-    if (int rc = awpu_hip_watch_count(n_blocks, w->first, w->every, &wr.n_frames, &next_first)) return rc;
-    wr.image = image;
-    wr.big = big;
-    wr.power = power;
-    AWPU_CTX(h);
-    return run_watch(h, src, n_blocks, wr, user);
-}
-
-}  // namespace
-
-int awpu_hip_watch_count(int32_t n_blocks, int32_t first, int32_t every, int32_t *n_frames, int32_t *next_first) {
-    if (!n_frames || !next_first) return invalid("null argument");
-    if (n_blocks < 1) return invalid("n_blocks below 1");
-    if (first < 0) return invalid("first below 0");
-    if (every < 1) return invalid("every below 1");
-    const int64_t shown = first >= n_blocks ? 0 : ((int64_t) n_blocks - first + every - 1) / every;
-    *n_frames = (int32_t) shown;
-    *next_first = (int32_t) (first + shown * every - n_blocks);
-    return AWPU_OK;
-}
-
-int awpu_hip_watch_blocks(awpu_hip_t *h, const void *datagrams, int32_t stride_bytes, int32_t n_blocks, const awpu_watch_t *w,
-                          uint8_t *image, uint8_t *big_image, float *power) {
-    // (arguments first: none of these reads the handle)
-    if (!h) return invalid("null handle");
-    if (!datagrams) return invalid("null argument");
-    if (n_blocks < 1) return invalid("n_blocks below 1");
-    if (stride_bytes < AWPU_DATAGRAM_BYTES) return invalid("datagram stride below 1032 bytes");
-    BlockRun src;
-    src.wire = static_cast<const unsigned char *>(datagrams);
-    src.stride = stride_bytes;
-    return watch_run(h, src, n_blocks, w, image, big_image, power, nullptr);
-}
-
-int awpu_hip_watch_samples(awpu_hip_t *h, const float *samples, int64_t pitch, int32_t n_blocks, const awpu_watch_t *w, uint8_t *image,
-                           uint8_t *big_image, float *power) {
-    if (!h) return invalid("null handle");
-    if (!samples) return invalid("null argument");
-    if (n_blocks < 1) return invalid("n_blocks below 1");
-    if (pitch < (int64_t) awpu::kSamples * n_blocks) return invalid("pitch below 256 * n_blocks");
-    BlockRun src;
-    src.samples = samples;
-    src.pitch = pitch;
-    return watch_run(h, src, n_blocks, w, image, big_image, power, nullptr);
-}
-
-int awpu_hip_watch_samples_device(awpu_hip_t *h, const float *d_samples, int64_t pitch, int32_t n_blocks, const awpu_watch_t *w,
-                                  uint8_t *d_image, uint8_t *d_big_image, float *d_power, void *stream) {
-    if (!h) return invalid("null handle");
-    if (!d_samples) return invalid("null argument");
-    if (n_blocks < 1) return invalid("n_blocks below 1");
-    if (pitch < (int64_t) awpu::kSamples * n_blocks) return invalid("pitch below 256 * n_blocks");
-    BlockRun src;
-    src.samples = d_samples;
-    src.pitch = pitch;
-    src.device = true;
-    return watch_run(h, src, n_blocks, w, d_image, d_big_image, d_power, static_cast<hipStream_t>(stream));
 }
 
 namespace {

@@ -1,0 +1,760 @@
+// awpu_runs.cpp -- runs of consecutive blocks of a recording through one pipeline of pieces: a heatmap of every block
+// (include/awpu_hip_blocks.h), the beam audio of every block (awpu_hip_listen.h), display images of every Nth block
+// (awpu_hip_watch.h).  The handle and what is called here out of awpu_hip.cpp: awpu_handle.h.
+#include "awpu_handle.h"
+#include "awpu_hip_blocks.h"
+#include "awpu_hip_listen.h"
+#include "awpu_hip_watch.h"
+
+#include <algorithm>
+#include <cstring>
+#include <thread>
+#include <vector>
+
+#include "block_kernels.h"
+#include "watch_kernels.h"
+
+using namespace awpu::host;
+
+int awpu::host::BufferPair::ensure(size_t bytes, bool want_host, bool want_device) {
+    if (bytes == 0 || (cap >= bytes && (h[0] || !want_host) && (d[0] || !want_device))) return AWPU_OK;
+    want_host |= h[0] != nullptr;  // (what it held it keeps, at the new size)
+    want_device |= d[0] != nullptr;
+    bytes = std::max(bytes, cap);
+    release();
+    for (int b = 0; b < 2; b++) {
+        if (want_device) AWPU_HIP_TRY(hipMalloc(&d[b], bytes));
+        if (want_host) AWPU_HIP_TRY(hipHostMalloc(&h[b], bytes, hipHostMallocDefault));
+    }
+    cap = bytes;
+    return AWPU_OK;
+}
+
+void awpu::host::BufferPair::release() {
+    for (int b = 0; b < 2; b++) {
+        dev_free(d[b]);
+        if (h[b]) (void) hipHostFree(h[b]);
+        h[b] = nullptr;
+    }
+    cap = 0;
+}
+
+namespace {
+
+// where a run's samples come from
+struct BlockRun {
+    const unsigned char *wire = nullptr;  // datagrams, `stride` bytes apart (host)
+    int32_t stride = 0;
+    const float *samples = nullptr;       // [n_streams][pitch] floats, host or (device) device memory
+    int64_t pitch = 0;
+    bool device = false;
+};
+
+// ... from a call's arguments, or what is wrong with them (none of these reads the handle)
+int wire_source(const awpu_hip *h, const void *datagrams, int32_t stride_bytes, int32_t n_blocks, BlockRun *src) {
+    if (!h) return invalid("null handle");
+    if (!datagrams) return invalid("null argument");
+    if (n_blocks < 1) return invalid("n_blocks below 1");
+    if (stride_bytes < AWPU_DATAGRAM_BYTES) return invalid("datagram stride below 1032 bytes");
+    src->wire = static_cast<const unsigned char *>(datagrams);
+    src->stride = stride_bytes;
+    return AWPU_OK;
+}
+
+int sample_source(const awpu_hip *h, const float *samples, int64_t pitch, int32_t n_blocks, bool device, BlockRun *src) {
+    if (!h) return invalid("null handle");
+    if (!samples) return invalid("null argument");
+    if (n_blocks < 1) return invalid("n_blocks below 1");
+    if (pitch < (int64_t) awpu::kSamples * n_blocks) return invalid("pitch below 256 * n_blocks");
+    src->samples = samples;
+    src->pitch = pitch;
+    src->device = device;
+    return AWPU_OK;
+}
+
+// fn(lo, hi) over [0, n) by up to 8 threads, each a contiguous share, when `bytes` (what the whole range copies) is 1 MB and
+// more; where a thread cannot be started, the calling thread takes its share
+template <class F>
+void parallel_ranges(size_t n, size_t bytes, const F &fn) {
+    const size_t n_threads = std::min<size_t>({8, n, bytes >> 20});
+    if (n_threads < 2) {
+        fn((size_t) 0, n);
+        return;
+    }
+    std::vector<std::thread> pool;
+    size_t k = 1;
+    try {
+        pool.reserve(n_threads - 1);
+        for (; k < n_threads; k++) pool.emplace_back(fn, n * k / n_threads, n * (k + 1) / n_threads);
+    } catch (...) {  // (std::system_error must not cross the C ABI)
+    }
+    fn((size_t) 0, n / n_threads);
+    if (k < n_threads) fn(n * k / n_threads, n);
+    for (auto &th : pool) th.join();
+}
+
+void parallel_copy(void *dst, const void *src, size_t bytes) {
+    parallel_ranges(bytes >> 16, bytes, [&](size_t lo, size_t hi) {  // 64 KB grains, the rest with the last
+        const size_t from = lo << 16, to = hi == (bytes >> 16) ? bytes : hi << 16;
+        std::memcpy(static_cast<unsigned char *>(dst) + from, static_cast<const unsigned char *>(src) + from, to - from);
+    });
+    if ((bytes >> 16) == 0) std::memcpy(dst, src, bytes);
+}
+
+// ---- the pipeline -----------------------------------------------------------------------------------------------------------
+// A run is cut into chunks of at most max_batch items -- blocks, or the shown frames of a watch run --, and every chunk into the
+// pieces awpu_hip_process sweeps a batch of that size in (host_piece): the same launches as that call on the same snapshots, so
+// the same bits.  Piece i, in the buffers b = i & 1, gets a history on the device (blk_hist.d[b]: the samples its snapshots
+// read), the snapshots' windows are cut out of it into the layout awpu_hip_process uploads (kCompact; kFull without a compact
+// window) and swept by launch().  (Pieces rather than whole chunks: the first piece's staging is the one nothing hides, and the
+// buffers are a piece long.)  Three streams: `sw` cuts and sweeps, `up` uploads, forms histories and fetches results, `li` runs
+// the listen kernels beside the sweep of the same piece.  The host forms (sw = the handle's stream, up = copy_stream, li =
+// listen_stream where the handle has one and the run is swept, else sw), per piece:
+//   1. the host waits ev_blk_in[b] (i >= 2: piece i-2's upload is over), then stages the piece's input in pinned blk_in.h[b]
+//   2. upload to blk_in.d[b] on up, ev_blk_in[b] behind it
+//   3. up waits ev_blk_cut[b] (i >= 2, swept runs) and ev_listened[b] (i >= 2, listened runs): piece i-2 has read blk_hist.d[b]
+//   4. the history is formed on up, ev_blk_hist[b] behind it; sw waits it, and li where that is another stream
+//   5. the cut on sw, then ev_blk_cut[b]; ev_begin at piece 0; the sweep with the handle's own event bracket off; what the
+//      consumer shows of the powers; ev_blk_swept[b]
+//   6. the listen kernels on li, ev_listened[b] behind them
+//   7. piece i-1's results into pinned memory on up, behind ev_blk_swept / ev_listened, ev_blk_out / ev_listen_out behind them
+//      (so piece i-2's way back is queued on up before piece i's history is formed: listen_out.d[b] is free when 6 writes it)
+//   8. piece i-2's results to the caller, once hipEventSynchronize on those events returns
+// and at the end: ev_end; the ring as n_blocks ingests leave it, written on sw; the remaining fetches and deliveries; up and li
+// synchronised; wait_and_time.  An error synchronises every stream: nothing of the call may still read the caller's buffers.
+// The device form is asynchronous on the caller's stream (null: the handle's), which is sw, up and li at once: steps 4 to 6
+// without the events, results written in place, the handle's stream ordered behind the ring write through ev_blk_ring.  Either
+// form starts behind what is queued on the handle's stream (ev_blk_ring again): the ring's zeroing, a device-form run not over.
+
+struct Piece {
+    int i, b;      // i-th of the run, in the buffers b = i & 1
+    int first, n;  // its items: blocks, or shown frames
+    bool tail;     // the frameless last piece of a watch run: its history only feeds the ring
+};
+
+// what a consumer of a recording supplies to run_pieces
+struct Consumer {
+    int n_items = 0, n_blocks = 0;  // what is cut into pieces; the blocks the ring moves on by
+    bool sweep = true;              // false: nothing is cut, swept or timed (listening without heatmaps)
+    bool tail = false;              // a Piece::tail follows the last piece
+    bool listens = false;           // steps 6, and 7 and 8 for what was heard
+    float *power = nullptr;         // [n_items][pixel_count]: host memory in the host forms, device memory in the device form; or null
+    int pitch = 0;                  // floats per stream of a history (set by ensure)
+
+    virtual int check() { return AWPU_OK; }  // refusals of its own, before the handle is made ready
+    virtual int ensure(int piece_max, int lo, int width, hipStream_t sw) = 0;  // its buffers, for pieces of piece_max items
+    virtual int begin(hipStream_t) { return AWPU_OK; }                         // on up, before the first history
+    virtual int staged_blocks(const Piece &p) = 0;              // host forms: stages the input in blk_in.h[b]; the blocks to upload
+    virtual int history(const Piece &p, hipStream_t s) = 0;     // blk_hist.d[b], out of blk_in.d[b] (host forms) or the caller's samples
+    virtual int cut(const Piece &p, hipStream_t s) = 0;         // its snapshots' windows into d_blk_frames
+    virtual int show(const Piece &, float *, hipStream_t) { return AWPU_OK; }  // behind the sweep into d_pow, before ev_blk_swept
+    virtual int listen(const Piece &, hipStream_t) { return AWPU_OK; }
+    virtual int fetch_shown(const Piece &, hipStream_t) { return AWPU_OK; }    // host forms: besides the powers, into pinned memory
+    virtual int deliver_shown(const Piece &) { return AWPU_OK; }               // ... and on to the caller
+    virtual int fetch_heard(const Piece &, hipStream_t) { return AWPU_OK; }
+    virtual int deliver_heard(const Piece &) { return AWPU_OK; }
+    virtual int ring_from(const Piece &last) = 0;               // the sample of the last history the ring's new snapshot starts at
+    virtual int end(hipStream_t) { return AWPU_OK; }            // on li, behind the ring write
+
+  protected:
+    ~Consumer() = default;
+};
+
+float *hist_of(awpu_hip *h, int b) { return reinterpret_cast<float *>(h->blk_hist.d[b]); }
+
+// the buffers every run needs for pieces of `piece` frames whose history and staging hold hist_blocks / in_blocks blocks (and,
+// for the host forms, the second stream and the events)
+int ensure_run_buffers(awpu_hip *h, const BlockRun &src, int piece, int width, bool sweep, int hist_blocks, int in_blocks) {
+    const size_t S = (size_t) h->cfg.n_streams, P = (size_t) h->cfg.pixel_count;
+    int rc = h->blk_hist.ensure(S * (awpu::kBlockPrefix + (size_t) awpu::kSamples * hist_blocks) * sizeof(float), false);
+    if (rc != AWPU_OK) return rc;
+    const size_t frames_floats = sweep ? S * width * (size_t) piece : 0;  // (a listen run without heatmaps cuts no window)
+    if (h->blk_frames_cap < frames_floats) {
+        dev_free(h->d_blk_frames);
+        h->blk_frames_cap = 0;
+        AWPU_HIP_TRY(hipMalloc(&h->d_blk_frames, frames_floats * sizeof(float)));
+        h->blk_frames_cap = frames_floats;
+    }
+    if (!h->ev_blk_ring) AWPU_HIP_TRY(hipEventCreateWithFlags(&h->ev_blk_ring, hipEventDisableTiming));
+    if (src.device) return AWPU_OK;
+    rc = h->blk_in.ensure((size_t) awpu::kSamples * in_blocks * (src.wire ? (size_t) AWPU_DATAGRAM_BYTES : S * sizeof(float)), true);
+    if (rc == AWPU_OK) rc = h->blk_out.ensure(sweep ? piece * P * sizeof(float) : 0, true, false);
+    if (rc != AWPU_OK) return rc;
+    if (!h->copy_stream) AWPU_HIP_TRY(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
+    for (hipEvent_t *ev : {&h->ev_blk_in[0], &h->ev_blk_in[1], &h->ev_blk_hist[0], &h->ev_blk_hist[1], &h->ev_blk_cut[0],
+                           &h->ev_blk_cut[1], &h->ev_blk_swept[0], &h->ev_blk_swept[1], &h->ev_blk_out[0], &h->ev_blk_out[1]})
+        if (!*ev) AWPU_HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+    return sweep ? ensure_power(h, 2 * piece * P) : AWPU_OK;  // two pieces' powers: one swept, one on its way back
+}
+
+// the run; the host forms are synchronous, the device form runs on `user` (NULL = h->stream)
+int run_pieces(awpu_hip *h, const BlockRun &src, hipStream_t user, Consumer &c) {
+    if (!h->parts.empty()) return fail(AWPU_ERR_STATE, "a device group does not take runs of blocks");
+    if (h->in_flight) return fail(AWPU_ERR_STATE, "an awpu_hip_process_async call is in flight on this handle: awpu_hip_wait first");
+    const awpu_hip_cfg &cfg = h->cfg;
+    if (cfg.hist != AWPU_HIST) return invalid("runs of blocks need hist 1024");
+    if (src.wire && cfg.n_streams > 256) return invalid("the wire carries at most 256 streams");
+    int rc = c.check();
+    if (rc != AWPU_OK) return rc;
+    const int chunk = std::max(1, std::min<int>(c.n_items, cfg.max_batch));
+    if (c.sweep) {
+        rc = check_ready(h, chunk);
+        if (rc != AWPU_OK) return rc;
+    } else {
+        AWPU_HIP_TRY(hipSetDevice(cfg.device));
+    }
+    std::vector<Piece> pieces;
+    int piece_max = 1;
+    for (int c0 = 0; c0 < c.n_items; c0 += chunk) {
+        const int nc = std::min(chunk, c.n_items - c0), piece = host_piece(nc);
+        for (int k0 = 0; k0 < nc; k0 += piece) {
+            const int i = (int) pieces.size();
+            pieces.push_back({i, i & 1, c0 + k0, std::min(piece, nc - k0), false});
+            piece_max = std::max(piece_max, pieces.back().n);
+        }
+    }
+    const int n_pieces = (int) pieces.size();  // ... with results
+    if (c.tail) pieces.push_back({n_pieces, n_pieces & 1, 0, 0, true});
+    const bool compact = h->compact_hist > 0, host = !src.device;
+    const int S = cfg.n_streams;
+    const size_t P = (size_t) cfg.pixel_count;
+    hipStream_t sw = host ? h->stream : (user ? user : h->stream);
+    rc = ensure_ring(h);
+    if (rc == AWPU_OK) rc = c.ensure(piece_max, compact ? h->wstart : 0, compact ? h->compact_hist : AWPU_HIST, sw);
+    if (rc != AWPU_OK) return rc;
+    hipStream_t up = host ? h->copy_stream : sw;
+    hipStream_t li = host && c.sweep && h->listen_stream && env().listen_stream ? h->listen_stream : sw;
+    const bool keep_timing = h->timing;
+    const bool time_it = keep_timing && host && c.sweep && n_pieces > 0;
+    if (!time_it) h->timing = false;  // the device form is asynchronous: the caller times its own stream; nothing swept, nothing timed
+    const auto fetch = [&](const Piece &p) -> int {
+        if (c.sweep) {
+            AWPU_HIP_TRY(hipStreamWaitEvent(up, h->ev_blk_swept[p.b], 0));
+            if (c.power)
+                AWPU_HIP_TRY(hipMemcpyAsync(h->blk_out.h[p.b], h->d_power + (size_t) p.b * piece_max * P, (size_t) p.n * P * sizeof(float),
+                                            hipMemcpyDeviceToHost, up));
+            if (const int frc = c.fetch_shown(p, up)) return frc;
+            AWPU_HIP_TRY(hipEventRecord(h->ev_blk_out[p.b], up));
+        }
+        if (c.listens) {
+            AWPU_HIP_TRY(hipStreamWaitEvent(up, h->ev_listened[p.b], 0));
+            if (const int frc = c.fetch_heard(p, up)) return frc;
+            AWPU_HIP_TRY(hipEventRecord(h->ev_listen_out[p.b], up));
+        }
+        return AWPU_OK;
+    };
+    const auto deliver = [&](const Piece &p) -> int {
+        if (c.sweep) {
+            AWPU_HIP_TRY(hipEventSynchronize(h->ev_blk_out[p.b]));
+            if (c.power) std::memcpy(c.power + (size_t) p.first * P, h->blk_out.h[p.b], (size_t) p.n * P * sizeof(float));
+            if (const int drc = c.deliver_shown(p)) return drc;
+        }
+        if (c.listens) {
+            AWPU_HIP_TRY(hipEventSynchronize(h->ev_listen_out[p.b]));
+            if (const int drc = c.deliver_heard(p)) return drc;
+        }
+        return AWPU_OK;
+    };
+    const auto body = [&]() -> int {
+        if (up != h->stream) {
+            AWPU_HIP_TRY(hipEventRecord(h->ev_blk_ring, h->stream));
+            AWPU_HIP_TRY(hipStreamWaitEvent(up, h->ev_blk_ring, 0));
+        }
+        int brc = c.begin(up);
+        if (brc != AWPU_OK) return brc;
+        const size_t block_bytes = (size_t) awpu::kSamples * (src.wire ? (size_t) AWPU_DATAGRAM_BYTES : S * sizeof(float));
+        int fetched = 0, delivered = 0;
+        for (const Piece &p : pieces) {
+            const int i = p.i, b = p.b;
+            if (host) {
+                if (i >= 2) AWPU_HIP_TRY(hipEventSynchronize(h->ev_blk_in[b]));
+                const size_t bytes = block_bytes * c.staged_blocks(p);
+                AWPU_HIP_TRY(hipMemcpyAsync(h->blk_in.d[b], h->blk_in.h[b], bytes, hipMemcpyHostToDevice, up));
+                AWPU_HIP_TRY(hipEventRecord(h->ev_blk_in[b], up));
+                if (i >= 2 && c.sweep) AWPU_HIP_TRY(hipStreamWaitEvent(up, h->ev_blk_cut[b], 0));
+                if (i >= 2 && c.listens) AWPU_HIP_TRY(hipStreamWaitEvent(up, h->ev_listened[b], 0));
+            }
+            brc = c.history(p, up);
+            if (brc != AWPU_OK) return brc;
+            if (host) {
+                AWPU_HIP_TRY(hipEventRecord(h->ev_blk_hist[b], up));
+                AWPU_HIP_TRY(hipStreamWaitEvent(sw, h->ev_blk_hist[b], 0));
+                if (li != sw) AWPU_HIP_TRY(hipStreamWaitEvent(li, h->ev_blk_hist[b], 0));
+            }
+            if (c.sweep && !p.tail) {
+                brc = c.cut(p, sw);
+                if (brc != AWPU_OK) return brc;
+                if (host) AWPU_HIP_TRY(hipEventRecord(h->ev_blk_cut[b], sw));
+                if (time_it && i == 0) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, sw));
+                float *d_pow = host ? h->d_power + (size_t) b * piece_max * P : (c.power ? c.power + (size_t) p.first * P : h->d_power);
+                h->timing = false;
+                brc = launch(h, h->d_blk_frames, p.n, d_pow, sw, compact ? kCompact : kFull);
+                h->timing = time_it;
+                if (brc == AWPU_OK) brc = c.show(p, d_pow, sw);
+                if (brc != AWPU_OK) return brc;
+                if (host) AWPU_HIP_TRY(hipEventRecord(h->ev_blk_swept[b], sw));
+            }
+            if (c.listens) {
+                brc = c.listen(p, li);
+                if (brc != AWPU_OK) return brc;
+                if (host) AWPU_HIP_TRY(hipEventRecord(h->ev_listened[b], li));
+            }
+            if (host) {
+                if (i >= 1 && fetched < n_pieces && (brc = fetch(pieces[fetched++])) != AWPU_OK) return brc;
+                if (i >= 2 && delivered < n_pieces && (brc = deliver(pieces[delivered++])) != AWPU_OK) return brc;
+            }
+        }
+        if (time_it) AWPU_HIP_TRY(hipEventRecord(h->ev_end, sw));
+        const Piece &last = pieces.back();
+        const int pos = (int) ((h->ring_pos + (long long) awpu::kSamples * c.n_blocks) % AWPU_HIST);
+        AWPU_HIP_TRY(awpu::launch_ring_write(hist_of(h, last.b), c.pitch, c.ring_from(last), S, h->d_ring, pos, sw));
+        h->ring_pos = pos;
+        brc = c.end(li);
+        if (brc != AWPU_OK) return brc;
+        if (!host) {
+            if (sw != h->stream) {  // later calls on the ring (the handle's stream) come after this one
+                AWPU_HIP_TRY(hipEventRecord(h->ev_blk_ring, sw));
+                AWPU_HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_blk_ring, 0));
+            }
+            if (c.listens) AWPU_HIP_TRY(hipStreamSynchronize(sw));  // the listeners' state is host memory
+            return AWPU_OK;
+        }
+        while (fetched < n_pieces)
+            if ((brc = fetch(pieces[fetched++])) != AWPU_OK) return brc;
+        while (delivered < n_pieces)
+            if ((brc = deliver(pieces[delivered++])) != AWPU_OK) return brc;
+        AWPU_HIP_TRY(hipStreamSynchronize(up));
+        if (li != sw) AWPU_HIP_TRY(hipStreamSynchronize(li));
+        return wait_and_time(h);
+    };
+    rc = body();
+    h->timing = keep_timing;
+    if (rc != AWPU_OK && host) {
+        (void) hipStreamSynchronize(h->copy_stream);
+        if (h->listen_stream) (void) hipStreamSynchronize(h->listen_stream);
+        (void) hipStreamSynchronize(h->stream);
+    }
+    return rc;
+}
+
+// ---- a heatmap of every block, and listening (kernels in block_kernels.hip, track_kernels.hip) ---------------------------------
+// A piece is nb consecutive blocks.  Its history [n_streams][768 + 256 * piece] continues the one before it: the 768 samples
+// before the piece (the ring's snapshot for the first piece, the tail of piece i-1's history after it), then its new samples.
+
+// What a listen call adds to a run; audio and trail are host memory in the host forms, device memory in the device form.  Per
+// piece, between its history and the ring write: the listen kernels on that history.
+struct ListenRun {
+    awpu_particle_t *listeners = nullptr;  // host, in/out
+    int32_t n = 0;
+    double theta_limit = 0.0, reference = 0.0;
+    float *audio = nullptr;
+    int64_t audio_pitch = 0;
+    awpu_particle_t *trail = nullptr;
+};
+
+// blocks [g0, g0 + nb) of a host form into pinned staging blk_in.h[b]: tight datagrams, or rows of 256 * nb samples (the
+// headline's 32-block pieces: 8.4 MB, 8 threads)
+void stage_blocks(awpu_hip *h, const BlockRun &src, int g0, int nb, int b) {
+    unsigned char *dst = h->blk_in.h[b];
+    const size_t n = (size_t) awpu::kSamples * nb;
+    const size_t rows = src.wire ? n : (size_t) h->cfg.n_streams;
+    parallel_ranges(rows, n * (src.wire ? (size_t) AWPU_DATAGRAM_BYTES : rows * sizeof(float)), [&](size_t r0, size_t r1) {
+        if (src.wire) {
+            const unsigned char *from = src.wire + (size_t) g0 * awpu::kSamples * src.stride;
+            if (src.stride == AWPU_DATAGRAM_BYTES) {
+                std::memcpy(dst + r0 * AWPU_DATAGRAM_BYTES, from + r0 * AWPU_DATAGRAM_BYTES, (r1 - r0) * AWPU_DATAGRAM_BYTES);
+            } else {
+                for (size_t i = r0; i < r1; i++) std::memcpy(dst + i * AWPU_DATAGRAM_BYTES, from + i * src.stride, AWPU_DATAGRAM_BYTES);
+            }
+            return;
+        }
+        for (size_t s = r0; s < r1; s++)
+            std::memcpy(dst + s * n * sizeof(float), src.samples + s * src.pitch + (size_t) g0 * awpu::kSamples, n * sizeof(float));
+    });
+}
+
+struct BlockPieces final : Consumer {
+    awpu_hip *const h;
+    const BlockRun &src;
+    const ListenRun *const ls;
+    const bool host;
+    const size_t state;  // bytes of the listeners
+    bool tracking = false, fixed = false;
+    std::vector<awpu_particle_t> heard;  // the listeners after the run
+    int lo = 0, width = 0;
+    const float *prev = nullptr;  // the 768 samples before the next piece
+    long long prev_pitch = 2048;
+
+    BlockPieces(awpu_hip *h_, const BlockRun &src_, int n_blocks_, float *power_, const ListenRun *ls_)
+        : h(h_), src(src_), ls(ls_), host(!src_.device), state(ls_ ? (size_t) ls_->n * sizeof(awpu_particle_t) : 0), heard(ls_ ? ls_->n : 0) {
+        n_items = n_blocks = n_blocks_;
+        power = power_;
+        listens = ls != nullptr;
+        sweep = !ls || power;
+        for (int l = 0; ls && l < ls->n; l++) (ls->listeners[l].steps > 0 ? tracking : fixed) = true;
+    }
+    size_t audio_bytes(int nb) const { return align16((size_t) ls->n * awpu::kSamples * nb * sizeof(float)); }
+
+    int check() override { return ls ? check_antenna(h) : AWPU_OK; }
+    int ensure(int piece_max, int lo_, int width_, hipStream_t) override {
+        lo = lo_, width = width_;
+        pitch = awpu::kBlockPrefix + awpu::kSamples * piece_max;
+        prev = h->d_ring + h->ring_pos + awpu::kSamples;  // the last 768 samples of the current snapshot
+        int rc = ensure_run_buffers(h, src, piece_max, width, sweep, piece_max, piece_max);
+        if (rc != AWPU_OK || !ls) return rc;
+        rc = ensure_track_index(h);
+        if (rc != AWPU_OK) return rc;
+        // the listeners' state, and for the host forms the way back of a piece's audio rows [n][256 * piece] and trail
+        if (h->listeners_cap < state) {
+            dev_free(h->d_listeners);
+            h->listeners_cap = 0;
+            AWPU_HIP_TRY(hipMalloc(&h->d_listeners, state));
+            h->listeners_cap = state;
+        }
+        if (!host) return AWPU_OK;
+        rc = h->listen_out.ensure(audio_bytes(piece_max) + (size_t) piece_max * state, true);
+        if (rc != AWPU_OK) return rc;
+        if (sweep && env().listen_stream && !h->listen_stream)
+            AWPU_HIP_TRY(hipStreamCreateWithFlags(&h->listen_stream, hipStreamNonBlocking));
+        for (hipEvent_t *ev : {&h->ev_listened[0], &h->ev_listened[1], &h->ev_listen_out[0], &h->ev_listen_out[1]})
+            if (!*ev) AWPU_HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+        return AWPU_OK;
+    }
+    int begin(hipStream_t s) override {
+        if (ls) AWPU_HIP_TRY(hipMemcpyAsync(h->d_listeners, ls->listeners, state, hipMemcpyHostToDevice, s));
+        return AWPU_OK;
+    }
+    int staged_blocks(const Piece &p) override {
+        stage_blocks(h, src, p.first, p.n, p.b);
+        return p.n;
+    }
+    int history(const Piece &p, hipStream_t s) override {
+        const int S = h->cfg.n_streams;
+        float *hist = hist_of(h, p.b);
+        AWPU_HIP_TRY(awpu::launch_copy_rows(prev, prev_pitch, hist, pitch, awpu::kBlockPrefix, S, s));
+        if (src.wire) {
+            AWPU_HIP_TRY(awpu::launch_unpack_blocks(h->blk_in.d[p.b], p.n, S, hist, pitch, awpu::kBlockPrefix, s));
+        } else {
+            const float *rows = host ? reinterpret_cast<const float *>(h->blk_in.d[p.b]) : src.samples + (size_t) p.first * awpu::kSamples;
+            AWPU_HIP_TRY(awpu::launch_copy_rows(rows, host ? (long long) awpu::kSamples * p.n : (long long) src.pitch,
+                                                hist + awpu::kBlockPrefix, pitch, awpu::kSamples * p.n, S, s));
+        }
+        prev = hist + (size_t) awpu::kSamples * p.n;
+        prev_pitch = pitch;
+        return AWPU_OK;
+    }
+    int cut(const Piece &p, hipStream_t s) override {
+        AWPU_HIP_TRY(awpu::launch_cut_windows(hist_of(h, p.b), pitch, h->cfg.n_streams, p.n, lo, width, h->d_blk_frames, s));
+        return AWPU_OK;
+    }
+    int listen(const Piece &p, hipStream_t s) override {
+        awpu::ListenArgs a{};
+        a.hist = hist_of(h, p.b);
+        a.pitch = pitch;
+        a.n_blocks = p.n;
+        a.xyz = h->d_xyz;
+        a.n = (int) (h->antenna.size() / 3);
+        a.index = h->d_track_index;
+        a.usable = h->usable();
+        a.listeners = h->d_listeners;
+        a.n_listeners = ls->n;
+        a.theta_limit = ls->theta_limit;
+        a.reference = ls->reference;
+        if (host) {
+            a.audio = reinterpret_cast<float *>(h->listen_out.d[p.b]);
+            a.audio_pitch = (long long) awpu::kSamples * p.n;
+            a.trail = ls->trail ? h->listen_out.d[p.b] + audio_bytes(p.n) : nullptr;
+        } else {
+            a.audio = ls->audio + (size_t) awpu::kSamples * p.first;
+            a.audio_pitch = ls->audio_pitch;
+            a.trail = ls->trail ? ls->trail + (size_t) p.first * ls->n : nullptr;
+        }
+        AWPU_HIP_TRY(awpu::launch_listen(a, tracking, fixed, s));
+        return AWPU_OK;
+    }
+    int fetch_heard(const Piece &p, hipStream_t s) override {
+        AWPU_HIP_TRY(hipMemcpyAsync(h->listen_out.h[p.b], h->listen_out.d[p.b], audio_bytes(p.n) + (ls->trail ? (size_t) p.n * state : 0),
+                                    hipMemcpyDeviceToHost, s));
+        return AWPU_OK;
+    }
+    int deliver_heard(const Piece &p) override {
+        const unsigned char *from = h->listen_out.h[p.b];
+        const size_t row = (size_t) awpu::kSamples * p.n;
+        for (int l = 0; l < ls->n; l++)
+            std::memcpy(ls->audio + (size_t) l * ls->audio_pitch + (size_t) awpu::kSamples * p.first, from + l * row * sizeof(float), row * sizeof(float));
+        if (ls->trail) std::memcpy(ls->trail + (size_t) p.first * ls->n, from + audio_bytes(p.n), (size_t) p.n * state);
+        return AWPU_OK;
+    }
+    // the ring's snapshot = the last 1024 samples of the last history
+    int ring_from(const Piece &last) override { return awpu::kSamples * (last.n - 1); }
+    int end(hipStream_t s) override {
+        if (ls) AWPU_HIP_TRY(hipMemcpyAsync(heard.data(), h->d_listeners, state, hipMemcpyDeviceToHost, s));
+        return AWPU_OK;
+    }
+};
+
+// `power`: [n_blocks][pixel_count], host memory in the host forms, device memory in the device form.  With `ls` the run is
+// listened to as well, and swept only if powers are asked for.
+int run_blocks(awpu_hip *h, const BlockRun &src, int n_blocks, float *power, hipStream_t user, const ListenRun *ls = nullptr) {
+    BlockPieces c(h, src, n_blocks, power, ls);
+    const int rc = run_pieces(h, src, user, c);
+    if (rc == AWPU_OK && ls) std::memcpy(ls->listeners, c.heard.data(), c.state);
+    return rc;
+}
+
+// the checks of a listen call that read no handle; then the run
+int listen_run(awpu_hip *h, const BlockRun &src, int n_blocks, awpu_particle_t *listeners, int32_t n, double theta_limit, double reference,
+               float *audio, int64_t audio_pitch, awpu_particle_t *trail, float *power, hipStream_t user) {
+    if (!listeners || !audio) return invalid("null argument");
+    if (int rc = check_particles(listeners, n, theta_limit, reference)) return rc;
+    if (audio_pitch < (int64_t) awpu::kSamples * n_blocks) return invalid("audio_pitch below 256 * n_blocks");
+    AWPU_CTX(h);
+    const ListenRun ls{listeners, n, theta_limit, reference, audio, audio_pitch, trail};
+    return run_blocks(h, src, n_blocks, power, user, &ls);
+}
+
+// ---- display images of every Nth block (kernels in watch_kernels.hip) ------------------------------------------------------------
+// A piece is nf SHOWN frames, and its history holds only the blocks its snapshots read (watch_kernels.h: 4 + min(every, 4) *
+// (nf - 1) slots of 256 samples), each piece's formed on its own: blocks from before the call out of the ring's snapshot, the
+// rest staged and uploaded (host forms) or gathered out of the caller's samples (device form).  Behind a piece's sweep comes its
+// display step: launch_heatmap for the whole piece, then the large image.  The ring's new snapshot is the last four blocks of
+// the call: the tail of the last piece's history when the last block is shown, a four-slot history of its own (Piece::tail)
+// otherwise.
+
+struct WatchRun {
+    awpu_watch_t w{};
+    int n_frames = 0;
+    uint8_t *image = nullptr, *big = nullptr;  // host memory in the host forms, device memory in the device form
+    float *power = nullptr;
+};
+
+// slots [q, slots) of a piece's history (watch_kernels.h) into pinned blk_in.h[b]: tight datagrams, or rows of 256 * (slots - q)
+void stage_watch(awpu_hip *h, const BlockRun &src, int b0, int every, int q, int slots, int b) {
+    unsigned char *dst = h->blk_in.h[b];
+    const int m = std::min(every, 4), ns = slots - q;
+    const size_t S = (size_t) h->cfg.n_streams, block_bytes = (size_t) awpu::kSamples * (src.wire ? (size_t) AWPU_DATAGRAM_BYTES : S * sizeof(float));
+    parallel_ranges((size_t) ns, block_bytes * ns, [&](size_t lo, size_t hi) {
+        for (size_t k = lo; k < hi; k++) {
+            const size_t blk = (size_t) awpu::watch_slot_block(q + (int) k, b0, every, m);
+            if (src.wire) {
+                const unsigned char *from = src.wire + blk * awpu::kSamples * src.stride;
+                unsigned char *to = dst + k * awpu::kSamples * AWPU_DATAGRAM_BYTES;
+                if (src.stride == AWPU_DATAGRAM_BYTES) {
+                    std::memcpy(to, from, (size_t) awpu::kSamples * AWPU_DATAGRAM_BYTES);
+                } else {
+                    for (int i = 0; i < awpu::kSamples; i++) std::memcpy(to + (size_t) i * AWPU_DATAGRAM_BYTES, from + (size_t) i * src.stride, AWPU_DATAGRAM_BYTES);
+                }
+            } else {
+                for (size_t s = 0; s < S; s++)
+                    std::memcpy(dst + ((s * ns + k) * awpu::kSamples) * sizeof(float), src.samples + s * src.pitch + blk * awpu::kSamples,
+                                awpu::kSamples * sizeof(float));
+            }
+        }
+    });
+}
+
+struct WatchPieces final : Consumer {
+    awpu_hip *const h;
+    const BlockRun &src;
+    const WatchRun &wr;
+    const awpu_watch_t &w;
+    const bool host, want_small;
+    const int S, m;
+    const size_t P, big_bytes;
+    int lo = 0, width = 0;
+    size_t small_off = 0, big_off = 0;  // in a watch buffer: the peaks, then the compact images, then the large ones
+    const float *snapshot = nullptr;    // blocks -4 .. -1 of the call
+
+    WatchPieces(awpu_hip *h_, const BlockRun &src_, int n_blocks_, const WatchRun &wr_)
+        : h(h_), src(src_), wr(wr_), w(wr_.w), host(!src_.device), want_small(wr_.image || wr_.big), S(h_->cfg.n_streams), m(std::min(wr_.w.every, 4)),
+          P((size_t) h_->cfg.pixel_count), big_bytes((size_t) wr_.w.out_rows * wr_.w.out_cols * (wr_.w.d_colormap ? 3 : 1)) {
+        n_items = wr.n_frames;
+        n_blocks = n_blocks_;
+        power = wr.power;
+        // the last block of the call shown: the ring's new snapshot is the tail of the last piece's history
+        tail = n_items == 0 || w.first + (n_items - 1) * w.every != n_blocks - 1;
+    }
+    // the blocks of a piece: its first shown block, the step, the slots of its history, and how many of them hold blocks from before the call
+    struct Span {
+        int b0, every, slots, q;
+    };
+    Span span(const Piece &p) const {
+        const int b0 = p.tail ? n_blocks - 1 : w.first + p.first * w.every, every = p.tail ? 1 : w.every;
+        return {b0, every, awpu::watch_slots(every, p.tail ? 1 : p.n), std::max(0, std::min(3 - b0, 4))};
+    }
+
+    int check() override {
+        if (h->cfg.pixel_count != h->cfg.n_pixels) return invalid("the display step needs the whole grid on this handle");
+        if ((long long) w.rows * w.cols != h->cfg.n_pixels) return invalid("rows x cols must be the grid");
+        return AWPU_OK;
+    }
+    int ensure(int piece_max, int lo_, int width_, hipStream_t sw) override {
+        lo = lo_, width = width_;
+        const int slots_max = awpu::watch_slots(w.every, piece_max);
+        pitch = awpu::kSamples * slots_max;
+        small_off = align16(sizeof(float) * piece_max), big_off = small_off + align16((size_t) piece_max * P);
+        snapshot = h->d_ring + h->ring_pos;
+        int rc = ensure_run_buffers(h, src, piece_max, width, true, slots_max - 3, slots_max);
+        if (rc == AWPU_OK && !host && !wr.power) rc = ensure_power(h, (size_t) piece_max * P);
+        if (rc == AWPU_OK && want_small) rc = h->watch.ensure(big_off + (host && wr.big ? (size_t) piece_max * big_bytes : 0), host);
+        if (rc == AWPU_OK && wr.big) rc = ensure_taps(h, w.rows, w.cols, w.out_rows, w.out_cols, sw);
+        return rc;
+    }
+    int staged_blocks(const Piece &p) override {
+        const Span g = span(p);
+        stage_watch(h, src, g.b0, g.every, g.q, g.slots, p.b);
+        return g.slots - g.q;
+    }
+    int history(const Piece &p, hipStream_t s) override {
+        const Span g = span(p);
+        float *hist = hist_of(h, p.b);
+        if (!host) {
+            AWPU_HIP_TRY(awpu::launch_watch_gather(src.samples, src.pitch, snapshot, g.b0, g.every, S, hist, pitch, 0, g.slots, s));
+            return AWPU_OK;
+        }
+        if (g.q > 0) AWPU_HIP_TRY(awpu::launch_watch_gather(nullptr, 0, snapshot, g.b0, g.every, S, hist, pitch, 0, g.q, s));
+        if (src.wire) {
+            AWPU_HIP_TRY(awpu::launch_unpack_blocks(h->blk_in.d[p.b], g.slots - g.q, S, hist, pitch, awpu::kSamples * g.q, s));
+        } else {
+            const long long n = (long long) awpu::kSamples * (g.slots - g.q);
+            AWPU_HIP_TRY(awpu::launch_copy_rows(reinterpret_cast<const float *>(h->blk_in.d[p.b]), n, hist + awpu::kSamples * g.q, pitch, (int) n, S, s));
+        }
+        return AWPU_OK;
+    }
+    int cut(const Piece &p, hipStream_t s) override {
+        AWPU_HIP_TRY(awpu::launch_watch_cut(hist_of(h, p.b), pitch, S, p.n, awpu::kSamples * m, lo, width, h->d_blk_frames, s));
+        return AWPU_OK;
+    }
+    int show(const Piece &p, float *d_pow, hipStream_t s) override {
+        if (!want_small) return AWPU_OK;
+        uint8_t *scratch = h->watch.d[host ? p.b : 0];
+        uint8_t *d_small = host || !wr.image ? scratch + small_off : wr.image + (size_t) p.first * P;
+        AWPU_HIP_TRY(awpu::launch_heatmap(d_pow, (int) P, p.n, reinterpret_cast<float *>(scratch), false, d_small, s));
+        if (wr.big)
+            AWPU_HIP_TRY(awpu::launch_watch_upscale(d_small, w.rows, w.cols, p.n, h->d_taps, h->taps_band_rows, w.d_colormap, w.flip != 0,
+                                                    host ? scratch + big_off : wr.big + (size_t) p.first * big_bytes, w.out_rows, w.out_cols, s));
+        return AWPU_OK;
+    }
+    int fetch_shown(const Piece &p, hipStream_t s) override {
+        uint8_t *to = h->watch.h[p.b], *from = h->watch.d[p.b];
+        if (wr.image) AWPU_HIP_TRY(hipMemcpyAsync(to + small_off, from + small_off, (size_t) p.n * P, hipMemcpyDeviceToHost, s));
+        if (wr.big) AWPU_HIP_TRY(hipMemcpyAsync(to + big_off, from + big_off, (size_t) p.n * big_bytes, hipMemcpyDeviceToHost, s));
+        return AWPU_OK;
+    }
+    int deliver_shown(const Piece &p) override {
+        if (wr.image) std::memcpy(wr.image + (size_t) p.first * P, h->watch.h[p.b] + small_off, (size_t) p.n * P);
+        if (wr.big) parallel_copy(wr.big + (size_t) p.first * big_bytes, h->watch.h[p.b] + big_off, (size_t) p.n * big_bytes);
+        return AWPU_OK;
+    }
+    int ring_from(const Piece &last) override { return last.tail ? 0 : awpu::kSamples * (awpu::watch_slots(w.every, last.n) - 4); }
+};
+
+// the checks of a watch call that read no handle; then the run
+int watch_run(awpu_hip *h, const BlockRun &src, int n_blocks, const awpu_watch_t *w, uint8_t *image, uint8_t *big, float *power, hipStream_t user) {
+    if (!w) return invalid("null argument");
+    if (!image && !big && !power) return invalid("no output asked for");
+    if (w->every < 1 || w->every > AWPU_WATCH_MAX_EVERY) return invalid("every outside [1, 1024]");
+    if (w->first < 0) return invalid("first below 0");
+    if (w->flip != 0 && w->flip != 1) return invalid("flip is 0 or 1");
+    if (w->rows < 1 || w->cols < 1) return invalid("rows and cols must be positive");
+    if (big && (w->out_rows < w->rows || w->out_cols < w->cols)) return invalid("upscale only: out >= in");
+    if (big && w->cols > AWPU_WATCH_MAX_COLS) return invalid("compact image wider than AWPU_WATCH_MAX_COLS");
+    WatchRun wr;
+    wr.w = *w;
+    int32_t next_first = 0;
+    if (int rc = awpu_hip_watch_count(n_blocks, w->first, w->every, &wr.n_frames, &next_first)) return rc;
+    wr.image = image;
+    wr.big = big;
+    wr.power = power;
+    AWPU_CTX(h);
+    WatchPieces c(h, src, n_blocks, wr);
+    return run_pieces(h, src, user, c);
+}
+
+}  // namespace
+
+extern "C" {
+
+int awpu_hip_process_blocks(awpu_hip_t *h, const void *datagrams, int32_t stride_bytes, int32_t n_blocks, float *power) {
+    BlockRun src;
+    if (int rc = wire_source(h, datagrams, stride_bytes, n_blocks, &src)) return rc;
+    if (!power) return invalid("null argument");
+    AWPU_CTX(h);
+    return run_blocks(h, src, n_blocks, power, nullptr);
+}
+
+int awpu_hip_process_samples(awpu_hip_t *h, const float *samples, int64_t pitch, int32_t n_blocks, float *power) {
+    BlockRun src;
+    if (int rc = sample_source(h, samples, pitch, n_blocks, false, &src)) return rc;
+    if (!power) return invalid("null argument");
+    AWPU_CTX(h);
+    return run_blocks(h, src, n_blocks, power, nullptr);
+}
+
+int awpu_hip_process_samples_device(awpu_hip_t *h, const float *d_samples, int64_t pitch, int32_t n_blocks, float *d_power,
+                                    void *stream) {
+    BlockRun src;
+    if (int rc = sample_source(h, d_samples, pitch, n_blocks, true, &src)) return rc;
+    if (!d_power) return invalid("null argument");
+    AWPU_CTX(h);
+    return run_blocks(h, src, n_blocks, d_power, static_cast<hipStream_t>(stream));
+}
+
+int awpu_hip_listen_blocks(awpu_hip_t *h, const void *datagrams, int32_t stride_bytes, int32_t n_blocks, awpu_particle_t *listeners,
+                           int32_t n, double theta_limit, double reference, float *audio, int64_t audio_pitch, awpu_particle_t *trail,
+                           float *power) {
+    BlockRun src;
+    if (int rc = wire_source(h, datagrams, stride_bytes, n_blocks, &src)) return rc;
+    return listen_run(h, src, n_blocks, listeners, n, theta_limit, reference, audio, audio_pitch, trail, power, nullptr);
+}
+
+int awpu_hip_listen_samples(awpu_hip_t *h, const float *samples, int64_t pitch, int32_t n_blocks, awpu_particle_t *listeners, int32_t n,
+                            double theta_limit, double reference, float *audio, int64_t audio_pitch, awpu_particle_t *trail,
+                            float *power) {
+    BlockRun src;
+    if (int rc = sample_source(h, samples, pitch, n_blocks, false, &src)) return rc;
+    return listen_run(h, src, n_blocks, listeners, n, theta_limit, reference, audio, audio_pitch, trail, power, nullptr);
+}
+
+int awpu_hip_listen_samples_device(awpu_hip_t *h, const float *d_samples, int64_t pitch, int32_t n_blocks, awpu_particle_t *listeners,
+                                   int32_t n, double theta_limit, double reference, float *d_audio, int64_t audio_pitch,
+                                   awpu_particle_t *d_trail, float *d_power, void *stream) {
+    BlockRun src;
+    if (int rc = sample_source(h, d_samples, pitch, n_blocks, true, &src)) return rc;
+    return listen_run(h, src, n_blocks, listeners, n, theta_limit, reference, d_audio, audio_pitch, d_trail, d_power,
+                      static_cast<hipStream_t>(stream));
+}
+
+int awpu_hip_watch_count(int32_t n_blocks, int32_t first, int32_t every, int32_t *n_frames, int32_t *next_first) {
+    if (!n_frames || !next_first) return invalid("null argument");
+    if (n_blocks < 1) return invalid("n_blocks below 1");
+    if (first < 0) return invalid("first below 0");
+    if (every < 1) return invalid("every below 1");
+    const int64_t shown = first >= n_blocks ? 0 : ((int64_t) n_blocks - first + every - 1) / every;
+    *n_frames = (int32_t) shown;
+    *next_first = (int32_t) (first + shown * every - n_blocks);
+    return AWPU_OK;
+}
+
+int awpu_hip_watch_blocks(awpu_hip_t *h, const void *datagrams, int32_t stride_bytes, int32_t n_blocks, const awpu_watch_t *w,
+                          uint8_t *image, uint8_t *big_image, float *power) {
+    BlockRun src;
+    if (int rc = wire_source(h, datagrams, stride_bytes, n_blocks, &src)) return rc;
+    return watch_run(h, src, n_blocks, w, image, big_image, power, nullptr);
+}
+
+int awpu_hip_watch_samples(awpu_hip_t *h, const float *samples, int64_t pitch, int32_t n_blocks, const awpu_watch_t *w, uint8_t *image,
+                           uint8_t *big_image, float *power) {
+    BlockRun src;
+    if (int rc = sample_source(h, samples, pitch, n_blocks, false, &src)) return rc;
+    return watch_run(h, src, n_blocks, w, image, big_image, power, nullptr);
+}
+
+int awpu_hip_watch_samples_device(awpu_hip_t *h, const float *d_samples, int64_t pitch, int32_t n_blocks, const awpu_watch_t *w,
+                                  uint8_t *d_image, uint8_t *d_big_image, float *d_power, void *stream) {
+    BlockRun src;
+    if (int rc = sample_source(h, d_samples, pitch, n_blocks, true, &src)) return rc;
+    return watch_run(h, src, n_blocks, w, d_image, d_big_image, d_power, static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

@@ -66,7 +66,7 @@ def test_tuning_build_still_links(pkg, tmp_path):
     measurements DESIGN.md cites could not be repeated.  It reads the round-1..3 variables; the shipping library does not."""
     pkg._build.generate_blocks()
     out = tmp_path / "libawpu_tuning.so"
-    srcs = [str(CSRC / f) for f in ("das_kernels.hip", "das_fast.hip", "awpu_hip.cpp", "geometry_host.cpp")]
+    srcs = [str(f) for f in pkg._build.SOURCES]
     subprocess.run([pkg._build.hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-result",
                     "-Werror=inline-asm", "-x", "hip", "-DAWPU_TIMING_BUILD", f"-I{REPO / 'include'}", f"-I{CSRC}", *srcs, "-o", str(out)],
                    check=True, capture_output=True)
