@@ -56,10 +56,13 @@ def per_block_loop(eng, wire, n_blocks):
     return np.stack(out)
 
 
-def engine(pkg, off, frac, n_streams, res, max_batch, math=None, interp=0, fir=None):
+def engine(pkg, off, frac, n_streams, res, max_batch, math=None, interp=0, fir=None, index=None, gains=None):
+    """`index`: the active mics (None = all, in id order); `gains`: per-mic gains (None = off)."""
     eng = pkg.Engine(n_pixels=res * res, n_streams=n_streams, max_batch=max_batch, grid_columns=res, math=math, interp=interp)
     eng.set_delay_table(off, frac)
-    eng.set_active_mics(None)
+    eng.set_active_mics(index)
+    if gains is not None:
+        eng.set_mic_gains(gains)
     if fir is not None:
         eng.set_fir_table(fir)
     return eng

@@ -31,11 +31,17 @@ def wire_recording(oracle, n_blocks, n_streams, seed, dc=0):
     return b"".join(wire), np.concatenate(blocks, axis=1)
 
 
-def listen_engine(pkg, xyz, max_batch, table=None, res=32, math=None, mics=True):
-    eng = pkg.Engine(n_pixels=res * res, n_streams=xyz.shape[1], max_batch=max_batch, grid_columns=res, math=math)
+def listen_engine(pkg, xyz, max_batch, table=None, res=32, math=None, mics=True, index=None, gains=None, **kw):
+    """`index`: the active mics (None = all, in id order); `gains`: per-mic gains of the heatmaps; kw: interp, fir (the sweep's)."""
+    fir = kw.pop("fir", None)
+    eng = pkg.Engine(n_pixels=res * res, n_streams=xyz.shape[1], max_batch=max_batch, grid_columns=res, math=math, **kw)
     eng.set_antenna(xyz)
     if mics:
-        eng.set_active_mics(None)
+        eng.set_active_mics(index)
+    if gains is not None:
+        eng.set_mic_gains(gains)
+    if fir is not None:
+        eng.set_fir_table(fir)
     if table is not None:
         eng.set_delay_table(*table)
     return eng

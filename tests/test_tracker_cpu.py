@@ -113,6 +113,76 @@ def angle(a, b):
     return math.acos(min(1.0, s1 * s2 + c1 * c2 * math.cos(a[1] - b[1])))
 
 
+def listen_host(oracle, steer_fn, snaps, theta, phi, spread, rate, steps, limit, index, impl="oracle", das_impl=None, reference=None):
+    """MISOWorker::update (src/dsp/miso.cpp:27-55) for every snapshot of snaps [n_blocks, n_streams, hist], on the host: per
+    block the reference power of the block's own snapshot (unless given), per listener `steps` gradient steps (track_host on
+    Particle::beam over the mics `index`, in that order), then Particle::das where the listener then points.  The steps use
+    `impl` (oracle | ref), the audio `das_impl` (default: the same).
+    -> (audio [n, 256 * n_blocks], trail [n_blocks][n] of (theta, phi, state of the block's last step or None))."""
+    das_impl = das_impl or impl
+    n = len(theta)
+    where = [(float(theta[l]), float(phi[l])) for l in range(n)]
+    audio = np.empty((n, 256 * len(snaps)), np.float32)
+    trail = []
+    for k, snap in enumerate(snaps):
+        ref_power = reference_power(snap) if reference is None else reference
+        row = []
+        for l in range(n):
+            state = None
+            if steps[l] > 0:
+                state, _ = track_host(lambda off, frac: oracle.particle_beams(snap, off, frac, index=index, impl=impl)[0], steer_fn,
+                                      *where[l], float(spread[l]), float(rate[l]), int(steps[l]), limit, ref_power)
+                where[l] = (state["theta"], state["phi"])
+            off, frac = steer_fn([where[l][0]], [where[l][1]])
+            audio[l, 256 * k: 256 * (k + 1)] = oracle.particle_beams(snap, off, frac, index=index, impl=das_impl)[1][0]
+            row.append((where[l][0], where[l][1], state))
+        trail.append(row)
+    return audio, trail
+
+
+# ------------------------------------------------------------------------------------------------ ragged mic lists
+# AWProcessingUnit::calibrate leaves an active-mic list that is shorter than the array and not in id order.  The lists the
+# GPU tests (tests/test_gpu_active_mics.py) run the tracker, the listeners and the block runs on; seeded, and pinned by
+# test_mic_list_premises below.  The element with the lowest delay of a direction is a corner of the array
+# (MIN_HOLDERS): a list tells "minimum over every element" from "minimum over the active ones" only if it leaves them out.
+
+
+def _shuffled(ids, seed):
+    return np.random.default_rng(seed).permutation(np.asarray(list(ids), np.int32)).astype(np.int32)
+
+
+MIN_HOLDERS = {64: (0, 7, 56, 63), 100: (0, 56, 63, 71, 95), 256: (0, 56, 199, 255), 512: (0, 199, 312, 511)}  # by element count
+_INNER64 = [s for s in range(64) if s not in MIN_HOLDERS[64]]
+ONE = np.asarray([37], np.int32)
+THREE = np.asarray([60, 2, 33], np.int32)
+FIFTEEN = _shuffled(_INNER64, 41)[:15]
+SEVENTEEN = _shuffled(_INNER64, 41)[:17]
+NO_CORNERS60 = np.asarray(_INNER64, np.int32)                      # ascending; 60 = 15 * 4 = 3 * 16 + 12
+KEEP57_PERM = _shuffled([s for s in range(64) if s % 9 != 4], 42)  # the goldens' ragged list, shuffled; 57 = 14 * 4 + 1 = 3 * 16 + 9
+TILED205 = _shuffled([s for s in range(256) if s not in MIN_HOLDERS[256]], 43)[:205]  # create_tiled_antenna(4, 1); 205 = 51 * 4 + 1
+_ALL_BUT_THREE = [s for s in range(512) if s not in (0, 199, 511)]
+TILED509 = np.asarray(_ALL_BUT_THREE[300:] + _ALL_BUT_THREE[:300], np.int32)          # create_tiled_antenna(4, 2); not ascending
+CUT100_37 = _shuffled([s for s in range(100) if s not in MIN_HOLDERS[100]], 44)[:37]  # create_tiled_antenna(2, 1)'s first 100
+MIC_LISTS = {"one": ONE, "three": THREE, "fifteen": FIFTEEN, "seventeen": SEVENTEEN, "no_corners60": NO_CORNERS60,
+             "keep57_perm": KEEP57_PERM, "tiled205": TILED205, "tiled509": TILED509, "cut100_37": CUT100_37}
+# by element count: the lists that leave out every element of MIN_HOLDERS (keep57_perm keeps all four, tiled509 keeps 312)
+LISTS_WITHOUT_THE_HOLDERS = {64: ("one", "three", "fifteen", "seventeen", "no_corners60"), 100: ("cut100_37",), 256: ("tiled205",), 512: ()}
+
+
+def min_holders(off, frac):
+    """Per direction of a steering table over ALL elements: the ids of the elements whose delay is the minimum that
+    steering_vector_spherical removes (delay 0: off 256, frac 0)."""
+    zero = (np.asarray(off) == 256) & (np.asarray(frac) == 0.0)
+    return [np.nonzero(row)[0] for row in zero]
+
+
+def minimum_is_inactive(off, frac, index):
+    """The premise of a test that claims to tell the minimum over every element from the minimum over the active ones: in
+    every direction of the table no active mic has the lowest delay."""
+    active = set(int(s) for s in index)
+    return all(len(ids) > 0 and not active.intersection(ids.tolist()) for ids in min_holders(off, frac))
+
+
 # ------------------------------------------------------------------------------------------------ restatement checks
 
 
@@ -189,6 +259,90 @@ def test_single_tracker_converges_on_the_reference_delay(pkg, oracle):
         assert math.radians(2.9) < angle(path[-1], SOURCE) < math.radians(3.2)
         assert angle(CONVERGE_START, SOURCE) > math.radians(8.0)  # it did travel
     assert all(angle(f, finals[0]) < 1e-6 for f in finals)  # (their powers agree to rounding, the beams bit for bit)
+
+
+def seeded_directions(n, seed):
+    rng = np.random.default_rng(seed)
+    return rng.uniform(0.02, math.pi / 2, n), rng.uniform(0.0, 2 * math.pi, n)
+
+
+@pytest.mark.parametrize("elements", sorted(MIN_HOLDERS))
+def test_the_lowest_delay_sits_in_a_corner(pkg, elements):
+    """32 seeded directions and their monopulse neighbours (both spreads): one element holds the lowest delay, and it is one of
+    MIN_HOLDERS.  The `s % 9 != 4` list of the goldens keeps all four corners of the reference's array."""
+    xyz = {64: lambda: pkg.create_antenna(), 100: lambda: np.ascontiguousarray(pkg.create_tiled_antenna(2, 1)[:, :100]),
+           256: lambda: pkg.create_tiled_antenna(4, 1), 512: lambda: pkg.create_tiled_antenna(4, 2)}[elements]()
+    assert xyz.shape == (3, elements)
+    theta, phi = seeded_directions(32, 77)
+    near = [d for t, p in zip(theta, phi) for s in (TRACKER_SPREAD, SEEKER_SPREAD) for d in quadrant(t, p, s, math.pi / 2)[1]]
+    off, frac = pkg.steer_table(xyz, np.r_[theta, [t for t, _ in near]], np.r_[phi, [p for _, p in near]])
+    holders = min_holders(off, frac)
+    assert all(len(ids) == 1 for ids in holders)
+    assert {int(ids[0]) for ids in holders} <= set(MIN_HOLDERS[elements])
+    assert set(MIN_HOLDERS[64]) <= {s for s in range(64) if s % 9 != 4}
+    for name in LISTS_WITHOUT_THE_HOLDERS[elements]:
+        assert minimum_is_inactive(off, frac, MIC_LISTS[name]), name
+    assert not minimum_is_inactive(off, frac, np.arange(elements))
+
+
+def test_mic_lists_are_what_the_kernels_tails_need():
+    """Lengths around the 4-wide and 16-wide loops of the beams, ids unique, and which lists are out of id order."""
+    assert {k: v.size for k, v in MIC_LISTS.items()} == {"one": 1, "three": 3, "fifteen": 15, "seventeen": 17, "no_corners60": 60,
+                                                         "keep57_perm": 57, "tiled205": 205, "tiled509": 509, "cut100_37": 37}
+    for name, index in MIC_LISTS.items():
+        assert index.dtype == np.int32 and np.unique(index).size == index.size, name
+        ascending = bool((np.diff(index) > 0).all())
+        assert ascending == (name in ("one", "no_corners60")), name
+    assert np.array_equal(SEVENTEEN[:15], FIFTEEN) and sorted(KEEP57_PERM.tolist()) == [s for s in range(64) if s % 9 != 4]
+
+
+@pytest.mark.parametrize("name", ["three", "fifteen", "seventeen", "keep57_perm"])
+def test_mic_order_and_rows_change_the_beams(pkg, oracle, name):
+    """The reference sums the mics in index[] order: on the synthetic frame a list and its sorted self give different beam
+    samples, and reading row s instead of row index[s] changes them too.  So a GPU test on these lists is not vacuous."""
+    index = MIC_LISTS[name]
+    xyz = pkg.create_antenna()
+    frame = pkg.synthetic.make_frames(xyz, 1, seed=1234)[0]
+    off, frac = pkg.steer_table(xyz, *seeded_directions(32, 78))
+    _, beams = oracle.particle_beams(frame, off, frac, index=index)
+    _, ordered = oracle.particle_beams(frame, off, frac, index=np.sort(index))
+    differing = int((beams.view(np.uint32) != ordered.view(np.uint32)).sum())
+    print(f"{name}: {differing} of {beams.size} samples differ from the sorted list's")
+    assert differing > beams.size // 8
+    _, by_slot = oracle.particle_beams(frame, off, frac, index=np.arange(index.size))  # row s and delay s for index[s]
+    assert int((beams.view(np.uint32) != by_slot.view(np.uint32)).sum()) > beams.size // 2
+
+
+@pytest.mark.parametrize("name", ["keep57_perm", "three"])
+def test_listen_host_on_the_oracle_and_the_reference(pkg, oracle, name):
+    """listen_host on 6 blocks of a recording of the synthetic source, two tracking listeners and a fixed one on a ragged
+    list: the trackers move and stay finite, a fixed listener's rows are Particle::das of the snapshots, the first tracking
+    step is track_host's, and -- where the reference's delay() is built -- its audio is the oracle's bit for bit (the steps
+    taken on the oracle's powers: the two agree on a beam's samples to the bit, on the 254-term power sum to rounding)."""
+    index = MIC_LISTS[name]
+    xyz = pkg.create_antenna()
+    n_blocks = 6
+    rec = pkg.synthetic.make_frames(xyz, 1, seed=1234, hist=1024 + 256 * n_blocks)[0]
+    snaps = np.stack([rec[:, 256 * (k + 1): 256 * (k + 1) + 1024] for k in range(n_blocks)])
+    steer = lambda t, p: pkg.steer_table(xyz, t, p)
+    who = dict(theta=[0.5, 0.9, SOURCE[0] + 0.05], phi=[1.0, 4.0, SOURCE[1]], spread=[TRACKER_SPREAD, SEEKER_SPREAD, TRACKER_SPREAD],
+               rate=[PARTICLE_RATE / 10] * 3, steps=[3, 0, 1])
+    audio, trail = listen_host(oracle, steer, snaps, **who, limit=math.pi / 2, index=index)
+    assert np.isfinite(audio).all() and all(math.isfinite(t) and math.isfinite(p) for row in trail for t, p, _ in row)
+    assert (trail[-1][0][0], trail[-1][0][1]) != (0.5, 1.0) and trail[-1][1][:2] == (0.9, 4.0) and trail[-1][1][2] is None
+    off, frac = steer([0.9], [4.0])
+    for k in range(n_blocks):
+        assert np.array_equal(audio[1, 256 * k: 256 * (k + 1)], oracle.particle_beams(snaps[k], off, frac, index=index)[1][0])
+    first, _ = track_host(lambda o, f: oracle.particle_beams(snaps[0], o, f, index=index)[0], steer, 0.5, 1.0, TRACKER_SPREAD,
+                          PARTICLE_RATE / 10, 3, math.pi / 2, reference_power(snaps[0]))
+    assert (first["theta"], first["phi"]) == trail[0][0][:2]
+    if oracle._in_reference_tree("src/dsp/delay.cpp") and not oracle.ref_available():
+        oracle.build(ref=True)
+    if oracle.ref_available():
+        heard, _ = listen_host(oracle, steer, snaps, **who, limit=math.pi / 2, index=index, das_impl="ref")
+        assert heard.tobytes() == audio.tobytes()
+        _, by_ref = listen_host(oracle, steer, snaps, **who, limit=math.pi / 2, index=index, impl="ref")
+        assert all(angle(a[:2], b[:2]) < 1e-6 for ra, rb in zip(trail, by_ref) for a, b in zip(ra, rb))
 
 
 # ------------------------------------------------------------------------------------------------ the library
