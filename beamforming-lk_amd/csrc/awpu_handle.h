@@ -1,5 +1,6 @@
-// awpu_handle.h -- internal to libawpu_hip.so: the handle, the error helpers, and what the runs of blocks (awpu_runs.cpp) call
-// in awpu_hip.cpp.  Nothing here is part of the C ABI.
+// awpu_handle.h -- internal to libawpu_hip.so: the handle, the error helpers, and what its three host files call in one another:
+// awpu_hip.cpp (the C ABI and its call paths), awpu_sweep.cpp (tables, launchers, dispatch) and awpu_runs.cpp (the runs of blocks).
+// Nothing here is part of the C ABI.
 #pragma once
 
 #include "awpu_hip.h"
@@ -52,6 +53,23 @@ struct BufferPair {
     void release();
 };
 
+// The quad-major tables (awpu_sweep.cpp, build_quad_lut), one per layout: what the table's LDS addresses point into
+enum QuadLayout {
+    kQuadPairs = 0,           // the quad shape's frame pairs (das_quad_kernel)
+    kQuadExactNd,             // {next, d} of a frame pair (das_exact_nd_kernel): 16-byte elements, quad rows padded to an even count
+    kQuadHalves,              // the halves layout of single frames (das_quadh_kernel)
+    kQuadHalvesStationary,    // ... with slot = mic (das_quadh_stationary_kernel: every mic's row resident)
+    kQuadExact,               // raw sample pairs (das_exact_quad_kernel): the image, and the plan, of the exact pair table
+    kQuadExactNdh,            // single frames: the halves form of {next, d}, chunked (das_exact_ndh_kernel, das_exact_ndp_kernel)
+    kQuadExactNdhStationary,  // ... every mic resident
+    kQuadLayouts
+};
+struct QuadTable {
+    awpu::QuadEntry *d = nullptr;
+    size_t entries = 0;  // allocated (the launchers check their kernel's reach against it: das_kernels.h, Extents)
+    awpu::FastPlan plan{};  // set by prepare() where the window fits the layout's image
+};
+
 }  // namespace awpu::host
 
 struct awpu_hip {
@@ -76,30 +94,24 @@ struct awpu_hip {
     };
     std::vector<FastLut> fast_luts;  // one per (frames per item, LDS image size) in use
     awpu::FastEntry *d_exact_pair_lut = nullptr;  // reference-order sweep on the frame-pair layout (das_exact_pair_kernel)
-    size_t exact_pair_lut_entries = 0, fir_plane_lut_entries = 0;  // allocated entries of the tables below and above ...
-    size_t quad_lut_entries[8] = {0, 0, 0, 0, 0, 0, 0, 0};                  // ... and of the quad-major tables, by QuadLayout
-    awpu::QuadEntry *d_exact_quad_lut = nullptr;  // ... four vertically adjacent pixels per wave (das_exact_quad_kernel): quad-major, raw fractions
-    awpu::FastPlan exact_plan{};
+    size_t exact_pair_lut_entries = 0, fir_plane_lut_entries = 0;  // allocated entries of the table above and of the FIR8 plane table
+    awpu::FastPlan exact_plan{};                  // ... its plan, and that of quad_tables[kQuadExact]
+    awpu::host::QuadTable quad_tables[awpu::host::kQuadLayouts];  // the quad-major tables, by QuadLayout
     unsigned *d_nd_queue = nullptr;               // das_exact_nd_kernel's eight item counters (one per XCD)
     int2 *d_nd_items = nullptr;                   // ... and its item list (nd_items_kernel), valid for nd_items_key
     size_t nd_items_cap = 0;
     long long nd_items_key = -1;                  // (n_pairs, pair group, quads per wave) the list was built for; -1: none
     int n_cus = 0;                                // compute units of the handle's device (persistent workgroups: one per CU)
-    awpu::QuadEntry *d_exact_nd_lut = nullptr;    // ... on the {next, d} layout (das_exact_nd_kernel): 16-byte elements, quad rows padded to an even count
-    awpu::FastPlan exact_nd_plan{};
-    bool exact_nd_ok = false;     // ... and the window fits the {next, d} image
-    awpu::QuadEntry *d_exact_ndh_lut = nullptr, *d_exact_ndhs_lut = nullptr;  // single frames: the halves form of that layout, chunked / every mic resident
-    awpu::FastPlan exact_ndh_plan{}, exact_ndhs_plan{};
+    bool exact_nd_ok = false;     // ... and the window fits the {next, d} image (kQuadExactNd)
+    // single frames: ... its halves form, chunked / every mic resident; fast_ndp_ok: AWPU_MATH_F32_FAST takes the chunked one on small grids
     bool exact_ndh_ok = false, exact_ndhs_ok = false, fast_ndp_ok = false;
+    bool identity_mics = false;   // the active-mic list is 0 .. usable-1 (awpu_hip_set_active_mics(NULL)): rows need no look-up
     bool exact_pairs_ok = false;  // AWPU_MATH_F32_EXACT + LERP and the window fits the pair image
     float *sums_out = nullptr;    // awpu_hip_process_device_sums: where the launch in progress exports out[] (else null)
-    awpu::QuadEntry *d_quad_lut = nullptr;  // quad-major table of the quad shape (das_quad_kernel)
-    awpu::QuadEntry *d_quadh_lut = nullptr; // the same with the halves layout's LDS addresses (das_quadh_kernel)
-    awpu::QuadEntry *d_quadhs_lut = nullptr; // the same with slot = mic (das_quadh_stationary_kernel: every mic's row resident)
     void *d_fir_plane_lut = nullptr;           // FIR8 on the four-plane layout: one dword per (pixel, mic): address, plane, coefficient row
     awpu::FastPlan fir_plane_plan{};
+    bool fir_planes_ok = false;                // AWPU_MATH_F32_FAST + FIR8 and the window fits the plane image
     std::vector<float> fir;                    // host copy of the [101][8] coefficient table (baked into the plane entries)
-    awpu::FastPlan quad_plan{}, quadh_plan{}, quadhs_plan{};
     bool quadh_fits = false;      // single frames on the halves layout (das_quadh_kernel)
     bool quadhs_fits = false;     // ... with every active mic's row in LDS at once (das_quadh_stationary_kernel: one 8x8 array does)
     bool quad_ok = false;         // the table's statistics favour the quad shape (decided in prepare)
@@ -268,8 +280,18 @@ const EnvKnobs &env();
 // sample 0 = history sample wstart; kRing one frame read in place from the ingest ring (rows 2048 apart)
 enum FrameLayout { kFull = 0, kCompact = 1, kRing = 2 };
 
-// defined, and described, in awpu_hip.cpp
+// the sweep layer: defined, and described, in awpu_sweep.cpp
+int prepare(awpu_hip *h);
+void free_tables(awpu_hip *h);
 int launch(awpu_hip *h, const float *d_frames, int batch, float *d_power, hipStream_t s, int layout = kFull);
+bool takes_packed_pairs(awpu_hip *h, int batch, awpu::FastPlan *plan);
+int packed_shape(awpu_hip *h, int batch, awpu::FastPlan *plan);
+size_t packed_floats_of(const awpu_hip *h, const awpu::FastPlan &plan, int batch);
+int pack_for_sweep(awpu_hip *h, const awpu::FastPlan &plan, const float *d_frames, int batch, float *d_packed, hipStream_t s);
+int sweep_packed(awpu_hip *h, const awpu::FastPlan &plan, const float *d_packed, size_t packed_floats, int batch, float *d_power, hipStream_t s);
+
+// defined, and described, in awpu_hip.cpp
+void retire_live_graphs(awpu_hip *h);
 int check_ready(awpu_hip *h, int batch);
 int ensure_power(awpu_hip *h, size_t need_power);
 int ensure_ring(awpu_hip *h);

@@ -1,6 +1,7 @@
-// awpu_hip.cpp -- the C ABI of libawpu_hip.so (include/awpu_hip.h): handle lifetime, table
-// packing, frame upload, kernel dispatch, the single-call paths, the ring, display, tracking and groups (the runs of
-// blocks: awpu_runs.cpp).  No CPU fallback: every compute entry point ends in a gfx950 kernel launch or an error status.
+// awpu_hip.cpp -- the C ABI of libawpu_hip.so (include/awpu_hip.h) and its call paths: handle lifetime, setters, frame upload,
+// the single-call paths, the ring, display, tracking, device groups and the packed-frame entry points.  The tables, the kernel
+// launchers and the dispatch rule are the sweep layer (awpu_sweep.cpp); the runs of blocks are awpu_runs.cpp.  No CPU fallback:
+// every compute entry point ends in a gfx950 kernel launch or an error status.
 #include "awpu_handle.h"
 
 #include <algorithm>
@@ -11,8 +12,6 @@
 #include <cstring>
 #include <new>
 #include <string>
-#include <array>
-#include <map>
 #include <vector>
 
 #include "das_kernels.h"
@@ -53,21 +52,6 @@ int fail(int status, const char *why) {
 }
 
 }  // namespace awpu::host
-
-namespace {
-
-// diagnostics buffer of `words` 64-bit words, grown on demand (one per handle: handles on different
-// devices, or launches of different sizes, must not share it)
-int ensure_diag(awpu_hip *h, size_t words) {
-    if (h->diag_cap >= words) return AWPU_OK;
-    dev_free(h->d_diag);
-    h->diag_cap = 0;
-    AWPU_HIP_TRY(hipMalloc(&h->d_diag, words * sizeof(unsigned long long)));
-    h->diag_cap = words;
-    return AWPU_OK;
-}
-
-}  // namespace
 
 awpu::host::EnvKnobs::EnvKnobs() {
     if (const char *v = std::getenv("AWPU_GROUP_FORCE_COPY")) group_copy = std::atoi(v);
@@ -121,35 +105,20 @@ const EnvKnobs &awpu::host::env() {
     return knobs;
 }
 
-namespace {
-
 // The captured live-block graphs hold raw device pointers (d_power, d_display, d_taps, d_ring, tables, d_pack):
 // whoever frees or reallocates one of those retires the graphs first.  The next live calls run step by step and
 // capture again once the buffers have settled.
-void retire_live_graphs(awpu_hip *h) {
+void awpu::host::retire_live_graphs(awpu_hip *h) {
     for (auto &g : h->live_graphs) (void) hipGraphExecDestroy(g.exec);
     h->live_graphs.clear();
     h->live_warm = 0;
 }
 
-// grow-only device buffer shared by the sweep shapes that pack frames (pairs, quads, FIR8 planes)
-int ensure_pack(awpu_hip *h, size_t need) {
-    if (h->pack_cap >= need) return AWPU_OK;
-    retire_live_graphs(h);
-    dev_free(h->d_pack);
-    h->pack_cap = 0;
-    AWPU_HIP_TRY(hipMalloc(&h->d_pack, need * sizeof(float)));
-    h->pack_cap = need;
-    return AWPU_OK;
-}
+namespace {
 
 void release_device(awpu_hip *h) {
     retire_live_graphs(h);
-    dev_free(h->d_lut);
-    for (auto &l : h->fast_luts) dev_free(l.d);
-    h->fast_luts.clear();
-    dev_free(h->d_exact_pair_lut);
-    dev_free(h->d_exact_quad_lut);
+    free_tables(h);
     dev_free(h->d_nd_items);
     h->nd_items_cap = 0;
     h->nd_items_key = -1;
@@ -158,13 +127,6 @@ void release_device(awpu_hip *h) {
     if (h->h_done_flag) (void) hipHostFree(h->h_done_flag);
     h->h_done_flag = nullptr;
     h->done_total = 0;
-    dev_free(h->d_exact_nd_lut);
-    dev_free(h->d_exact_ndh_lut);
-    dev_free(h->d_exact_ndhs_lut);
-    dev_free(h->d_quad_lut);
-    dev_free(h->d_quadh_lut);
-    dev_free(h->d_quadhs_lut);
-    dev_free(h->d_fir_plane_lut);
     dev_free(h->d_index);
     dev_free(h->d_gain);
     dev_free(h->d_calib);
@@ -213,1171 +175,11 @@ void release_device(awpu_hip *h) {
     h->beam_cap = h->beam_lut_cap = h->pack_cap = h->frames_cap = h->power_cap = 0;
 }
 
-// Pack the reference-format tables into the kernels' layout once both the tables and the
-// active-mic list are known.  Validates that no entry reads outside the frame history:
-// delay() reads signal[0..256] from &signals[s][offset] (delay.cpp:19-22).
-int prepare(awpu_hip *h) {
-    const auto &c = h->cfg;
-    const int U = h->usable();
-    const int P = c.pixel_count;
-    int lo = c.hist, hi = -1;
-    for (int p = 0; p < P; p++) {
-        const int32_t *row = &h->off[(size_t) p * c.lut_stride];
-        for (int s = 0; s < U; s++) {
-            const int o = row[h->index[s]];
-            lo = std::min(lo, o);
-            hi = std::max(hi, o);
-        }
-    }
-    const int reach = c.interp == AWPU_INTERP_FIR8 ? awpu::kSamples + 6 : awpu::kSamples;  // last sample read past off
-    if (lo < 0 || hi + reach > c.hist - 1) {
-        return fail(AWPU_ERR_RANGE, "delay table entry reads outside the frame history");
-    }
-    if (c.window_end > c.window_begin) {  // a wider window asked for (ranks that exchange packed frames stage the union)
-        lo = std::min(lo, c.window_begin);
-        hi = std::max(hi, c.window_end - reach - 1);
-    }
-    h->wstart = lo;
-    h->window = hi - lo + reach + 1;
-    h->tau_max = awpu::kSamples - lo;
-
-    // (hipFree waits for the device: launches still reading the old tables finish first)
-    dev_free(h->d_lut);
-    dev_free(h->d_index);
-    for (auto &l : h->fast_luts) dev_free(l.d);
-    h->fast_luts.clear();
-    dev_free(h->d_exact_pair_lut);
-    dev_free(h->d_exact_quad_lut);
-    dev_free(h->d_exact_nd_lut);
-    dev_free(h->d_exact_ndh_lut);
-    dev_free(h->d_exact_ndhs_lut);
-    dev_free(h->d_quad_lut);
-    dev_free(h->d_quadh_lut);
-    dev_free(h->d_quadhs_lut);
-    dev_free(h->d_fir_plane_lut);
-    AWPU_HIP_TRY(hipMalloc(&h->d_index, (size_t) U * sizeof(int32_t)));
-    AWPU_HIP_TRY(hipMemcpy(h->d_index, h->index.data(), (size_t) U * sizeof(int32_t),
-                           hipMemcpyHostToDevice));
-    dev_free(h->d_gain);
-    if (!h->gain.empty()) {
-        std::vector<float> compact(U);
-        for (int s = 0; s < U; s++) compact[s] = h->gain[h->index[s]];
-        AWPU_HIP_TRY(hipMalloc(&h->d_gain, (size_t) U * sizeof(float)));
-        AWPU_HIP_TRY(hipMemcpy(h->d_gain, compact.data(), (size_t) U * sizeof(float), hipMemcpyHostToDevice));
-    }
-    {   // float offset, inside one frame, of staged row 2*s+q (copy q of active mic s)
-        dev_free(h->d_row_off);
-        const int upad = (U + 3) & ~3;
-        std::vector<int32_t> ro((size_t) 2 * upad + 8, h->index[0] * c.hist + lo);
-        for (int s = 0; s < U; s++)
-            for (int q = 0; q < 2; q++) ro[2 * s + q] = h->index[s] * c.hist + lo + q;
-        AWPU_HIP_TRY(hipMalloc(&h->d_row_off, ro.size() * sizeof(int32_t)));
-        AWPU_HIP_TRY(hipMemcpy(h->d_row_off, ro.data(), ro.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        // Host-buffer calls upload only the window [lo, lo + compact_hist) of every stream (the rest
-        // of the 1024-sample snapshot is never read: SURVEY 8a A10): a third of the PCIe bytes.
-        dev_free(h->d_row_off_compact);
-        const int ch = ((h->window + 3) & ~3) + 4;
-        h->compact_hist = lo + ch <= c.hist ? ch : 0;
-        if (c.hist == AWPU_HIST) {  // frames read in place from the ingest ring: rows 2048 floats apart
-            dev_free(h->d_row_off_ring);
-            std::vector<int32_t> rr(ro.size(), h->index[0] * 2048 + lo);
-            for (int s = 0; s < U; s++)
-                for (int q = 0; q < 2; q++) rr[2 * s + q] = h->index[s] * 2048 + lo + q;
-            AWPU_HIP_TRY(hipMalloc(&h->d_row_off_ring, rr.size() * sizeof(int32_t)));
-            AWPU_HIP_TRY(hipMemcpy(h->d_row_off_ring, rr.data(), rr.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
-        if (h->compact_hist) {
-            for (int s = 0; s < U; s++)
-                for (int q = 0; q < 2; q++) ro[2 * s + q] = h->index[s] * h->compact_hist + q;
-            for (size_t i = 2 * (size_t) U; i < ro.size(); i++) ro[i] = h->index[0] * h->compact_hist;
-            AWPU_HIP_TRY(hipMalloc(&h->d_row_off_compact, ro.size() * sizeof(int32_t)));
-            AWPU_HIP_TRY(hipMemcpy(h->d_row_off_compact, ro.data(), ro.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
-    }
-
-    h->exact_pairs_ok = c.math == AWPU_MATH_F32_EXACT && c.interp == AWPU_INTERP_LERP && awpu::pair_plan(h->window, U, &h->exact_plan);
-    h->exact_nd_ok = h->exact_pairs_ok && awpu::exact_nd_plan(h->window, U, &h->exact_nd_plan);
-    h->exact_ndh_ok = h->exact_pairs_ok && awpu::exact_ndh_plan(h->window, U, false, &h->exact_ndh_plan);
-    // (AWPU_MATH_F32_FAST sweeps single frames on small grids with the reference-order pixel-per-wave kernel too -- launch() -- : the
-    // same plan, the same table)
-    h->fast_ndp_ok = c.math == AWPU_MATH_F32_FAST && c.interp == AWPU_INTERP_LERP && awpu::exact_ndh_plan(h->window, U, false, &h->exact_ndh_plan);
-    h->exact_ndhs_ok = h->exact_pairs_ok && awpu::exact_ndh_plan(h->window, U, true, &h->exact_ndhs_plan);
-    if (c.math != AWPU_MATH_F32_FAST || c.interp == AWPU_INTERP_FIR8) {
-        int chunk = 0;
-        if (awpu::das_exact_lds_bytes(h->window, U, &chunk) == 0)
-            return invalid("delay window does not fit the LDS budget");
-        std::vector<awpu::LutEntry> packed((size_t) P * U);
-        for (int p = 0; p < P; p++) {
-            const int32_t *orow = &h->off[(size_t) p * c.lut_stride];
-            const float *frow = &h->frac[(size_t) p * c.lut_stride];
-            awpu::LutEntry *dst = &packed[(size_t) p * U];
-            for (int s = 0; s < U; s++) {
-                const int id = h->index[s];
-                dst[s].off_rel = orow[id] - lo;
-                dst[s].frac = frow[id];
-                if (c.interp == AWPU_INTERP_FIR8) {  // delay.cpp:32-33: the coefficient row
-                    const float get_filter = frow[id] * 100.0f + 0.5f;
-                    const int32_t k = (int32_t) get_filter;
-                    std::memcpy(&dst[s].frac, &k, sizeof(k));
-                }
-            }
-        }
-        AWPU_HIP_TRY(hipMalloc(&h->d_lut, packed.size() * sizeof(awpu::LutEntry)));
-        AWPU_HIP_TRY(hipMemcpy(h->d_lut, packed.data(), packed.size() * sizeof(awpu::LutEntry),
-                               hipMemcpyHostToDevice));
-    } else {
-        awpu::FastPlan plan;
-        if (!awpu::fast_plan(h->window, U, 1, awpu::kFastLdsBytes, &plan))
-            return invalid("delay window does not fit the LDS budget");
-    }
-
-    // Pairing of pixels inside a wave of the frame-pair sweep: the shared-read block saves a mic's LDS reads
-    // when the two pixels' integer delays coincide.  With the grid's row length known, compare consecutive
-    // pixels against vertically adjacent ones on a sample of the table and take the better.
-    h->pair_cols = 0;
-    {
-        const int cols = c.grid_columns;
-        if (cols > 0 && P % cols == 0 && c.pixel_begin % cols == 0 && P / cols >= 2) {
-            long same_h = 0, same_v = 0, seen = 0;
-            const int step = std::max(1, (P - cols) / 4096);
-            for (int p = 0; p + cols < P; p += step) {
-                if ((p % cols) + 1 >= cols) continue;
-                const int32_t *o0 = &h->off[(size_t) p * c.lut_stride];
-                const int32_t *oh = &h->off[(size_t) (p + 1) * c.lut_stride];
-                const int32_t *ov = &h->off[(size_t) (p + cols) * c.lut_stride];
-                for (int s = 0; s < U; s++) {
-                    const int id = h->index[s];
-                    same_h += o0[id] == oh[id];
-                    same_v += o0[id] == ov[id];
-                    seen++;
-                }
-            }
-            if (seen > 0 && same_v > same_h) h->pair_cols = cols;
-            if (env().pair_cols >= 0) h->pair_cols = env().pair_cols ? cols : 0;  // AWPU_SHAPE=pair_vertical / pair_horizontal: tests force either
-        }
-    }
-
-    // The quad shape (das_quad_kernel) shares arithmetic between four vertically adjacent pixels wherever their
-    // integer delays coincide with the second pixel's: 20 packed VALU instructions per quad and mic, +8 for every
-    // pixel that differs (-4 where the third and fourth differ together), against 32 without sharing.  Count it on a sample of the table; take the shape when it
-    // saves VALU work at all once its own address adds are counted (measured: a count of 30.2 -- BASELINE c2 -- is
-    // 4 % faster than the pair shape, 29.4 -- c3 -- 8 %, 25.3 -- the headline -- 20 %; AWPU_FAST_QUADS=0/1 forces either).
-    h->quad_ok = false;
-    h->quadh_fits = false;
-    h->quadhs_fits = false;
-    h->quad_cost = 0.0;
-    {
-        const int cols = c.grid_columns;
-        h->quad_differ = 3.0;
-        if (c.interp == AWPU_INTERP_LERP && cols > 0 && P % cols == 0 && c.pixel_begin % cols == 0) {
-            const int rows = P / cols;
-            long differ = 0, together = 0, seen = 0;  // `together`: pixels 2 and 3 away from the reference as one (4 less)
-            const int n_quads = ((rows + 3) / 4) * cols;
-            const int step = std::max(1, n_quads / 2048);
-            for (int q = 0; q < n_quads; q += step) {
-                const int r0 = (q / cols) * 4, col = q % cols;
-                const int32_t *o[4];
-                for (int k = 0; k < 4; k++) o[k] = &h->off[((size_t) std::min(r0 + k, rows - 1) * cols + col) * c.lut_stride];
-                for (int s = 0; s < U; s++) {
-                    const int id = h->index[s];
-                    differ += (o[0][id] != o[1][id]) + (o[2][id] != o[1][id]) + (o[3][id] != o[1][id]);
-                    together += o[2][id] != o[1][id] && o[2][id] == o[3][id];
-                }
-                seen += U;
-            }
-            h->quad_cost = seen ? 20.0 + (8.0 * (double) differ - 4.0 * (double) together) / (double) seen : 32.0;
-            h->quad_differ = seen ? (double) differ / (double) seen : 3.0;  // pixels of a quad (of three) that leave the reference pixel's address, per mic
-            const bool fast = c.math == AWPU_MATH_F32_FAST;
-            h->quad_ok = fast && h->quad_cost < 31.0 && awpu::pair_plan(h->window, U, &h->quad_plan);
-            if (fast && env().quads >= 0) h->quad_ok = env().quads != 0 && awpu::pair_plan(h->window, U, &h->quad_plan);
-            // the halves layout: a row holds the window less 128 samples, as (sample, sample + 128) pairs (its pack pass applies the gains)
-            h->quadh_fits = h->quad_ok && awpu::pair_plan(h->window - 128, U, &h->quadh_plan);
-            h->quadhs_fits = h->quadh_fits && awpu::quadh_stationary_plan(h->window, U, &h->quadhs_plan);
-        }
-    }
-
-    auto &st = h->stats;
-    st.tau_max = h->tau_max;
-    st.window = h->window;
-    st.usable = U;
-    st.alg_bytes_frame = 4ull * U * h->window + 8ull * P * U + 4ull * P;
-    st.alg_flops_frame = 4ull * P * U * awpu::kSamples + 6ull * P * (awpu::kSamples - 2);
-    st.kernel_variant = AWPU_KERNEL_NONE;
-    h->prepared = true;
-    h->table_gen++;  // graphs of awpu_hip_live_block captured against the old tables are stale
-    retire_live_graphs(h);
-    return AWPU_OK;
-}
-
-// The fast kernel's table for `fpi` frames per item: per (pixel, active mic s) the weights and
-// the LDS byte address of X[off] inside the staged image (das_fast.hip), rows padded to whole
-// groups of four with null entries (zero weights, address of a staged row).
-int build_fast_lut(awpu_hip *h, int fpi, int image_bytes, const awpu_hip::FastLut **out) {
-    for (const auto &l : h->fast_luts)
-        if (l.plan.fpi == fpi && l.plan.image_bytes == image_bytes) {
-            *out = &l;
-            return AWPU_OK;
-        }
-    const auto &c = h->cfg;
-    const int U = h->usable(), P = c.pixel_count;
-    awpu_hip::FastLut lut;
-    const bool pairs = image_bytes < 0;  // frame-pair layout: one image row per mic, 8-byte elements
-    const bool planned = image_bytes == -2 ? awpu::pair_plan_stationary(h->window, U, &lut.plan)  // every mic resident
-                         : pairs         ? awpu::pair_plan(h->window, U, &lut.plan)
-                                         : awpu::fast_plan(h->window, U, fpi, image_bytes, &lut.plan);
-    if (!planned) return invalid("delay window does not fit the LDS budget");
-    const awpu::FastPlan &plan = lut.plan;
-    // rows for whole pixel tiles (the kernels sweep every pixel slot of a workgroup; slots past the
-    // grid get null rows) + spare groups: the kernels prefetch entries past the row they sweep
-    // (with vertical pixel pairs the partner of a pixel in the last row lies one grid row past the table)
-    const int P_pad = (P + (pairs ? h->pair_cols : 0) + 127) / 128 * 128;
-    const size_t n = (size_t) P_pad * plan.usable_pad + 4 * awpu::kPairTablePrefetch;
-    std::vector<awpu::FastEntry> packed(n, awpu::FastEntry{0.0f, 0u, 0.0f, 0u});
-    for (int p = 0; p < P; p++) {
-        const int32_t *orow = &h->off[(size_t) p * c.lut_stride];
-        const float *frow = &h->frac[(size_t) p * c.lut_stride];
-        awpu::FastEntry *dst = &packed[(size_t) p * plan.usable_pad];
-        for (int s = 0; s < U; s++) {
-            const int id = h->index[s];
-            const int off_rel = orow[id] - h->wstart;
-            const int q = off_rel & 1;
-            const int j = s % plan.chunk;  // mic slot inside its chunk
-            dst[s].f = frow[id];
-            dst[s].g = 1.0f - frow[id];
-            if (!h->gain.empty()) {  // the per-mic gain rides on the two weights
-                dst[s].f *= h->gain[id];
-                dst[s].g *= h->gain[id];
-            }
-            dst[s].addr = pairs ? (uint32_t) (j * plan.row_bytes + off_rel * 8)
-                                : (uint32_t) ((j * 2 + q) * plan.row_bytes + (off_rel - q) * 4);
-        }
-    }
-    AWPU_HIP_TRY(hipMalloc(&lut.d, n * sizeof(awpu::FastEntry)));
-    AWPU_HIP_TRY(hipMemcpy(lut.d, packed.data(), n * sizeof(awpu::FastEntry), hipMemcpyHostToDevice));
-    lut.entries = n;
-    h->fast_luts.reserve(8);
-    h->fast_luts.push_back(lut);
-    *out = &h->fast_luts.back();
-    return AWPU_OK;
-}
-
-// The quad shape's table (das_fast.hip, das_quad_kernel): [quad][group of 4 mics][pixel 0..3][mic 0..3] x (f, LDS
-// address), quads = groups of four grid rows x columns padded to whole 16-column tiles.  Pixels past the grid
-// carry weight 0 and the address of the nearest pixel inside it (they then follow the shared path and add
-// nothing); padding mics (usable rounded up to 4) carry weight 0 and the address of their own, zero, row.
-enum QuadLayout { kQuadPairs = 0, kQuadExactNd = 1, kQuadHalves = 2, kQuadHalvesStationary = 3, kQuadExact = 4, kQuadExactNdh = 5, kQuadExactNdhStationary = 6 };
-int build_quad_lut(awpu_hip *h, int layout) {
-    awpu::QuadEntry *&d_lut = layout == kQuadHalves             ? h->d_quadh_lut
-                              : layout == kQuadHalvesStationary ? h->d_quadhs_lut
-                              : layout == kQuadExact            ? h->d_exact_quad_lut
-                              : layout == kQuadExactNd          ? h->d_exact_nd_lut
-                              : layout == kQuadExactNdh         ? h->d_exact_ndh_lut
-                              : layout == kQuadExactNdhStationary ? h->d_exact_ndhs_lut
-                                                                : h->d_quad_lut;
-    if (d_lut) return AWPU_OK;
-    const auto &c = h->cfg;
-    const awpu::FastPlan &plan = layout == kQuadHalves             ? h->quadh_plan
-                                 : layout == kQuadHalvesStationary ? h->quadhs_plan
-                                 : layout == kQuadExact            ? h->exact_plan
-                                 : layout == kQuadExactNd          ? h->exact_nd_plan
-                                 : layout == kQuadExactNdh         ? h->exact_ndh_plan
-                                 : layout == kQuadExactNdhStationary ? h->exact_ndhs_plan
-                                                                   : h->quad_plan;
-    const bool halves_nd = layout == kQuadExactNdh || layout == kQuadExactNdhStationary;
-    const bool raw = layout == kQuadExact || layout == kQuadExactNd || halves_nd;
-    const float centre = raw ? 0.0f : 0.5f;  // the reference-order sweeps take the fraction as it is (mimo.cpp:126)
-    const int elem = layout == kQuadExactNd || halves_nd ? 16 : 8;  // bytes per LDS element: {next, d} of a frame pair / of the two halves, or one sample pair
-    const int U = h->usable(), cols = c.grid_columns, rows = c.pixel_count / cols;
-    const int groups = plan.usable_pad / 4;
-    // (the {next, d} kernel gives a wave two quads, one quad row apart: its table has an even number of quad rows, the last one clamped;
-    // ... the single-frame form two quads one COLUMN apart: its table has whole tiles of 32 columns)
-    const int cols_pad = halves_nd ? (cols + 31) / 32 * 32 : (cols + 15) / 16 * 16, rows4 = layout == kQuadExactNd ? ((rows + 3) / 4 + 1) / 2 * 2 : (rows + 3) / 4;
-    const size_t n = (size_t) rows4 * cols_pad * groups * 16 + 2 * awpu::kQuadTablePrefetch;  // spare groups: the sweep prefetches one past the end
-    std::vector<awpu::QuadEntry> packed(n, awpu::QuadEntry{0.0f, 0u});
-    for (int r4 = 0; r4 < rows4; r4++)
-        for (int col = 0; col < cols_pad; col++) {
-            awpu::QuadEntry *dst = &packed[((size_t) r4 * cols_pad + col) * groups * 16];
-            for (int q = 0; q < 4; q++) {
-                const int row = 4 * r4 + q;
-                const bool inside = row < rows && col < cols;
-                const size_t p = (size_t) std::min(row, rows - 1) * cols + std::min(col, cols - 1);
-                const int32_t *orow = &h->off[p * c.lut_stride];
-                const float *frow = &h->frac[p * c.lut_stride];
-                for (int s = 0; s < plan.usable_pad; s++) {
-                    awpu::QuadEntry &e = dst[((s >> 2) * 4 + q) * 4 + (s & 3)];
-                    const int j = s % plan.chunk;  // mic slot inside its chunk
-                    if (s < U) {
-                        const int id = h->index[s];
-                        const int off_rel = orow[id] - h->wstart;
-                        e.f = inside ? frow[id] - centre : 0.0f;  // centred weight (das_fast.hip, das_quad_kernel); exact: as it is
-                        e.addr = (uint32_t) (j * plan.row_bytes + off_rel * elem);
-                    } else {  // padding mic: silence (the pack passes write zero rows)
-                        e.f = 0.0f;
-                        e.addr = (uint32_t) (j * plan.row_bytes);
-                    }
-                }
-            }
-        }
-    AWPU_HIP_TRY(hipMalloc(&d_lut, n * sizeof(awpu::QuadEntry)));
-    AWPU_HIP_TRY(hipMemcpy(d_lut, packed.data(), n * sizeof(awpu::QuadEntry), hipMemcpyHostToDevice));
-    h->quad_lut_entries[layout] = n;
-    return AWPU_OK;
-}
-
-// Kernel shape for a call.  AWPU_FAST_VARIANT="fpi,ppw[,nw]" overrides the heuristic (tuning
-// knob, read once): fpi frames per item, ppw pixels per wave, nw = 8 (8-wave workgroups, two per
-// CU) or 32 (the double-buffered 16-wave shape, one per CU).
-void choose_fast_variant(awpu_hip *h, int batch, int *fpi, int *ppw, int *nw) {
-    const int env_fpi = env().fpi, env_ppw = env().ppw, env_nw = env().nw;
-    // Prefer the double-buffered shape with the most pixels per wave that still gives every CU
-    // a workgroup; small grids fall back to 8-wave workgroups with fewer pixels per wave.
-    const long P = h->cfg.pixel_count;
-    auto wgs = [&](long pix_per_wg) { return (P + pix_per_wg - 1) / pix_per_wg * batch; };
-    *fpi = 1;
-    if (wgs(128) >= 256) {
-        *nw = 32;
-        *ppw = 8;
-    } else if (wgs(64) >= 256) {
-        *nw = 32;
-        *ppw = 4;
-    } else {
-        *nw = 8;
-        *ppw = wgs(32) >= 512 ? 4 : 2;
-    }
-    if (env_fpi == 1 || env_fpi == 2) *fpi = env_fpi;
-    if (env_ppw == 2 || env_ppw == 4 || env_ppw == 8) *ppw = env_ppw;
-    if (env_nw == 8 || env_nw == 32 || env_nw == 24) *nw = env_nw;
-    if (*nw == 32) {
-        *fpi = 1;
-        if (*ppw < 4) *ppw = 4;
-    }
-    if (*nw == 24) {
-        *fpi = 1;
-        *ppw = 4;
-    }
-    if (*fpi == 2 && *ppw == 8) *ppw = 4;
-    if (*fpi == 2 && batch < 2) *fpi = 1;
-}
-
 enum PeerPath { kPeerSame = 0, kPeerDirect = 1, kPeerStaged = 2 };
 
-// a launch is over: close the timing bracket and count it (also on the diagnostic paths)
-int finish_launch(awpu_hip *h, int batch, hipStream_t s, int kernel_id) {
-    h->stats.kernel_variant = kernel_id;
-    if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_end, s));
-    h->stats.launches += 1;
-    h->stats.frames += (uint64_t) batch;
-    return AWPU_OK;
-}
-
-// AWPU_FAST_DEBUG=16: per-wave cycle stamps of the launch just enqueued (12 words per wave) to stderr
-int dump_diag(awpu_hip *h, size_t n_waves, int wg_waves, const char *tag, hipStream_t s) {
-    AWPU_HIP_TRY(hipStreamSynchronize(s));
-    std::vector<unsigned long long> hb(n_waves * 12);
-    AWPU_HIP_TRY(hipMemcpy(hb.data(), h->d_diag, hb.size() * 8, hipMemcpyDeviceToHost));
-    double v[10] = {0};
-    std::vector<double> sw(wg_waves, 0), ba(wg_waves, 0);
-    for (size_t i = 0; i < n_waves; i++) {
-        for (int k = 0; k < 10; k++) v[k] += (double) hb[12 * i + k];
-        sw[i % wg_waves] += (double) hb[12 * i + 5];
-        ba[i % wg_waves] += (double) hb[12 * i + 8];
-    }
-    std::fprintf(stderr, "[awpu diag %s] waves %zu, per wave cycles: total %.0f | dma-issue %.0f sweep %.0f (in blocks %.0f = %.1f%%, "
-                 "first table wait %.0f) tail %.0f dma-wait %.0f barrier %.0f | per block %.0f\n", tag, n_waves, v[2] / n_waves,
-                 v[4] / n_waves, v[5] / n_waves, v[1] / n_waves, 100 * v[1] / v[2], v[0] / n_waves, v[6] / n_waves,
-                 v[7] / n_waves, v[8] / n_waves, v[1] / v[3]);
-    if (v[9] > 0)  // shader cycles over the 100 MHz real-time counter, both stamped by every wave (MI355X_MICROARCH.md, DVFS give-back item 6)
-        std::fprintf(stderr, "[awpu diag %s] in-kernel clock %.3f GHz (cycles %.0f / real time %.2f us per wave)\n", tag, v[2] / v[9] * 0.1,
-                     v[2] / n_waves, v[9] / n_waves * 0.01);
-    std::fprintf(stderr, "[awpu diag %s] wave slot sweep/barrier kcycles:", tag);
-    for (int k = 0; k < wg_waves; k++)
-        std::fprintf(stderr, " %d:%.0f/%.0f", k, sw[k] * wg_waves / n_waves / 1e3, ba[k] * wg_waves / n_waves / 1e3);
-    std::fprintf(stderr, "\n");
-    return AWPU_OK;
-}
-
-// The reference-order sweep on the frame-pair layout (das_exact_pair_kernel): the table is the pair shape's with the
-// UNSCALED fraction in .f (gains go on the samples, as in das_exact_kernel) and padding entries -- mics usable ..
-// usable_pad-1, and whole rows past the grid -- that read a row of zeros with fraction 0 (they add +0).
-int build_exact_pair_lut(awpu_hip *h) {
-    if (h->d_exact_pair_lut) return AWPU_OK;
-    const auto &c = h->cfg;
-    const awpu::FastPlan &plan = h->exact_plan;
-    const int U = h->usable(), P = c.pixel_count;
-    const int P_pad = (P + h->pair_cols + 127) / 128 * 128;  // whole tiles; with vertical pairs the partner of a last-row pixel lies one grid row past the table
-    const size_t n = (size_t) P_pad * plan.usable_pad + 4 * awpu::kPairTablePrefetch;  // spare groups: the block prefetches one past a row's end
-    std::vector<awpu::FastEntry> packed(n);
-    for (size_t i = 0; i < n; i++)  // null entry of slot s: the zero row of its own slot in the last chunk, or any row with fraction 0 ...
-        packed[i] = awpu::FastEntry{0.0f, (uint32_t) ((int) (i % plan.usable_pad) % plan.chunk * plan.row_bytes), 0.0f, 0u};
-    for (int p = 0; p < P; p++) {
-        const int32_t *orow = &h->off[(size_t) p * c.lut_stride];
-        const float *frow = &h->frac[(size_t) p * c.lut_stride];
-        awpu::FastEntry *dst = &packed[(size_t) p * plan.usable_pad];
-        for (int s = 0; s < U; s++) {
-            const int id = h->index[s];
-            dst[s].f = frow[id];  // the reference's `fraction`, mimo.cpp:126
-            dst[s].addr = (uint32_t) ((s % plan.chunk) * plan.row_bytes + (orow[id] - h->wstart) * 8);
-        }
-    }
-    AWPU_HIP_TRY(hipMalloc(&h->d_exact_pair_lut, n * sizeof(awpu::FastEntry)));
-    AWPU_HIP_TRY(hipMemcpy(h->d_exact_pair_lut, packed.data(), n * sizeof(awpu::FastEntry), hipMemcpyHostToDevice));
-    h->exact_pair_lut_entries = n;
-    return AWPU_OK;
-}
-
-// frame pairs an XCD works on at a time: as many as keep their samples in its 4 MiB L2 beside the table stream (launch_quads)
-int xcd_pair_group_bytes(size_t pair_bytes, int n_pairs) {
-    int g = (int) std::max<size_t>(1, (3u << 20) / pair_bytes);
-    g = g >= 8 ? 8 : g >= 4 ? 4 : g >= 2 ? 2 : 1;
-    while (g > 1 && g > n_pairs) g >>= 1;
-    return g;
-}
-int xcd_pair_group(const awpu::FastPlan &pp, int rows_per_pair, int n_pairs) {
-    const size_t pair_bytes = (size_t) rows_per_pair * pp.wr * 8;
-    int g = (int) std::max<size_t>(1, (3u << 20) / pair_bytes);
-    g = g >= 8 ? 8 : g >= 4 ? 4 : g >= 2 ? 2 : 1;
-    while (g > 1 && g > n_pairs) g >>= 1;
-    return g;
-}
-
-int launch_exact_pairs(awpu_hip *h, const float *d_frames, int batch, float *d_power, hipStream_t s, int hist_eff, int wstart_eff) {
-    int rc = build_exact_pair_lut(h);
-    if (rc != AWPU_OK) return rc;
-    const awpu::FastPlan &pp = h->exact_plan;
-    const size_t need = (size_t) ((std::max(h->cfg.max_batch, batch) + 1) / 2) * pp.usable_pad * pp.wr * 2;
-    if (const int prc = ensure_pack(h, need); prc != AWPU_OK) return prc;
-    awpu::ExactPairArgs a{};
-    a.packed = h->d_pack;
-    a.lut = h->d_exact_pair_lut;
-    a.power = d_power;
-    a.sums = h->sums_out;
-    a.usable = h->usable();
-    a.usable_pad = pp.usable_pad;
-    a.pixel_count = h->cfg.pixel_count;
-    a.wp = pp.wr;
-    a.chunk = pp.chunk;
-    a.batch = batch;
-    a.cols = h->pair_cols;
-    a.tiles = awpu::pair_tiles(a.pixel_count, a.cols);
-    a.n_pairs = (batch + 1) / 2;
-    a.pair_group = xcd_pair_group(pp, pp.usable_pad, a.n_pairs);
-    if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
-    AWPU_HIP_TRY(awpu::launch_pack_pairs(d_frames, h->cfg.n_streams, hist_eff, wstart_eff, h->d_index, h->usable(), pp.usable_pad,
-                                         h->d_gain, pp.wr, batch, h->d_pack, false, s));  // raw samples: no stencil in front of the reference's order
-    AWPU_HIP_TRY(awpu::launch_das_exact_pairs(a, {h->exact_pair_lut_entries, h->pack_cap}, s));
-    return finish_launch(h, batch, s, AWPU_KERNEL_EXACT_PAIR);
-}
-
-// ... four vertically adjacent pixels per wave where the row length is known (das_exact_quad_kernel): same bits, fewer LDS reads
-int launch_exact_quads(awpu_hip *h, const float *d_frames, int batch, float *d_power, hipStream_t s, int hist_eff, int wstart_eff) {
-    int rc = build_quad_lut(h, kQuadExact);
-    if (rc != AWPU_OK) return rc;
-    const awpu::FastPlan &pp = h->exact_plan;
-    const size_t need = (size_t) ((std::max(h->cfg.max_batch, batch) + 1) / 2) * pp.usable_pad * pp.wr * 2;
-    if (const int prc = ensure_pack(h, need); prc != AWPU_OK) return prc;
-    awpu::ExactQuadArgs a{};
-    a.packed = h->d_pack;
-    a.lut = h->d_exact_quad_lut;
-    a.power = d_power;
-    a.sums = h->sums_out;
-    a.usable = h->usable();
-    a.usable_pad = pp.usable_pad;
-    a.pixel_count = h->cfg.pixel_count;
-    a.wp = pp.wr;
-    a.chunk = pp.chunk;
-    a.batch = batch;
-    a.cols = h->cfg.grid_columns;
-    a.rows = h->cfg.pixel_count / a.cols;
-    a.tiles = awpu::quad_tiles(a.rows, a.cols);
-    a.n_pairs = (batch + 1) / 2;
-    a.pair_group = xcd_pair_group(pp, pp.usable_pad, a.n_pairs);
-    if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
-    AWPU_HIP_TRY(awpu::launch_pack_pairs(d_frames, h->cfg.n_streams, hist_eff, wstart_eff, h->d_index, h->usable(), pp.usable_pad,
-                                         h->d_gain, pp.wr, batch, h->d_pack, false, s));
-    AWPU_HIP_TRY(awpu::launch_das_exact_quads(a, {h->quad_lut_entries[kQuadExact], h->pack_cap}, s));
-    return finish_launch(h, batch, s, AWPU_KERNEL_EXACT_QUAD);
-}
-
-// ... on the {next, d} layout (das_exact_nd_kernel, round 5): cur - next formed once per sample by the pack pass; nq quads per wave
-int launch_exact_nd(awpu_hip *h, const float *d_frames, int batch, float *d_power, hipStream_t s, int hist_eff, int wstart_eff, int nq,
-                    const float *prepacked = nullptr, size_t prepacked_floats = 0) {
-    int rc = build_quad_lut(h, kQuadExactNd);
-    if (rc != AWPU_OK) return rc;
-    const awpu::FastPlan &pp = h->exact_nd_plan;
-    const size_t need = (size_t) ((std::max(h->cfg.max_batch, batch) + 1) / 2) * pp.usable_pad * pp.wr * 4;
-    if (!prepacked)
-        if (const int prc = ensure_pack(h, need); prc != AWPU_OK) return prc;
-    awpu::ExactNdArgs a{};
-    a.packed = prepacked ? prepacked : h->d_pack;
-    a.lut = h->d_exact_nd_lut;
-    a.power = d_power;
-    a.sums = h->sums_out;
-    a.usable = h->usable();
-    a.usable_pad = pp.usable_pad;
-    a.pixel_count = h->cfg.pixel_count;
-    a.wq = pp.wr;
-    a.chunk = pp.chunk;
-    a.batch = batch;
-    a.cols = h->cfg.grid_columns;
-    a.rows = h->cfg.pixel_count / a.cols;
-    a.nq = nq;
-    a.tiles = awpu::nd_tiles(a.rows, a.cols, nq);
-    a.n_pairs = (batch + 1) / 2;
-    a.pair_group = xcd_pair_group_bytes((size_t) pp.usable_pad * pp.row_bytes, a.n_pairs);
-    if (!h->d_nd_queue) {
-        AWPU_HIP_TRY(hipMalloc(&h->d_nd_queue, 9 * sizeof(unsigned)));
-        if (hipDeviceGetAttribute(&h->n_cus, hipDeviceAttributeMultiprocessorCount, h->cfg.device) != hipSuccess || h->n_cus < 1) h->n_cus = 256;
-    }
-    {   // the item list: rebuilt (by the launcher, on the stream) when the batch, the pair group or the tile shape changed
-        const size_t items = (size_t) a.n_pairs * a.tiles;
-        const long long key = ((long long) a.n_pairs << 24) | ((long long) a.pair_group << 8) | nq;
-        if (h->nd_items_cap < items) {
-            retire_live_graphs(h);
-            AWPU_HIP_TRY(hipStreamSynchronize(s));  // (a sweep in flight may still read the old list)
-            dev_free(h->d_nd_items);
-            h->nd_items_cap = 0;
-            AWPU_HIP_TRY(hipMalloc(&h->d_nd_items, items * sizeof(int2)));
-            h->nd_items_cap = items;
-            h->nd_items_key = -1;
-        }
-        a.items = h->d_nd_items;
-        a.build_items = h->nd_items_key != key;
-        h->nd_items_key = key;
-    }
-    a.queue = h->d_nd_queue;
-    a.wgs = h->n_cus;
-    {   // an eighth of every XCD's run goes to the common queue (the XCDs' speeds differ by ~6 %); short runs: one queue for the chip
-        const int per = (a.n_pairs * a.tiles + 7) / 8;
-        a.tail = per >= 32 ? (per + 7) / 8 : per;
-#ifdef AWPU_TUNING_BUILD
-        if (const char *v = std::getenv("AWPU_ND_TAIL")) a.tail = std::max(1, std::atoi(v) >= 100 ? per : per * std::atoi(v) / 100);  // percent of a run
-#endif
-    }
-    if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
-    if (!prepacked)
-        AWPU_HIP_TRY(awpu::launch_pack_nd(d_frames, h->cfg.n_streams, hist_eff, wstart_eff, h->d_index, h->usable(), pp.usable_pad, h->d_gain,
-                                          pp.wr, batch, h->d_pack, s));
-#ifdef AWPU_TUNING_BUILD
-    const size_t n_wgs = std::min<size_t>((size_t) a.n_pairs * a.tiles, (size_t) a.wgs);
-    if (env().debug & 16) {  // per-workgroup timeline (where, when, phases): printed below
-        if (const int drc = ensure_diag(h, n_wgs * 8); drc != AWPU_OK) return drc;
-        AWPU_HIP_TRY(hipMemsetAsync(h->d_diag, 0, n_wgs * 8 * sizeof(unsigned long long), s));
-        a.debug_out = h->d_diag;
-    }
-#endif
-    AWPU_HIP_TRY(awpu::launch_das_exact_nd(a, {h->quad_lut_entries[kQuadExactNd], prepacked ? prepacked_floats : h->pack_cap}, s));
-    rc = finish_launch(h, batch, s, AWPU_KERNEL_EXACT_ND);
-#ifdef AWPU_TUNING_BUILD
-    if (rc == AWPU_OK && (env().debug & 16)) {
-        AWPU_HIP_TRY(hipStreamSynchronize(s));
-        std::vector<unsigned long long> hb(n_wgs * 8);
-        AWPU_HIP_TRY(hipMemcpy(hb.data(), h->d_diag, hb.size() * 8, hipMemcpyDeviceToHost));
-        // group by compute unit (XCC, SE, CU of HW_ID), order by start: busy time, gaps between consecutive workgroups
-        std::map<unsigned long long, std::vector<std::array<unsigned long long, 5>>> by_cu;
-        unsigned long long first = ~0ull, last = 0;
-        double ph[3] = {0, 0, 0};
-        size_t n = 0;
-        for (size_t w = 0; w < n_wgs; w++) {
-            const unsigned long long *o = &hb[8 * w];
-            if (!o[7]) continue;
-            const unsigned hw = (unsigned) o[5], xcc = (unsigned) (o[5] >> 32) & 0xf;
-            const unsigned long long cu = ((unsigned long long) xcc << 16) | ((hw >> 8) & 0xff);  // HW_ID: CU_ID [11:8], SH_ID [12], SE_ID [15:13]
-            by_cu[cu].push_back({o[0], o[1], o[2], o[3], o[4]});
-            first = std::min(first, o[0]);
-            last = std::max(last, o[1]);
-            for (int k = 0; k < 3; k++) ph[k] += (double) o[2 + k];
-            n++;
-        }
-        double busy = 0, gaps = 0, head = 0, tail = 0;
-        size_t n_gaps = 0;
-        for (auto &kv : by_cu) {
-            auto &v = kv.second;
-            std::sort(v.begin(), v.end());
-            head += (double) (v.front()[0] - first);
-            tail += (double) (last - v.back()[1]);
-            for (size_t i = 0; i < v.size(); i++) {
-                busy += (double) (v[i][1] - v[i][0]);
-                if (i) gaps += (double) v[i][0] - (double) v[i - 1][1], n_gaps++;
-            }
-        }
-        {   // per XCD: when its last workgroup ended (relative to the launch's first stamp), mean busy time of its CUs, and the
-            // spread of workgroup durations by position in the item order
-            std::map<unsigned, std::array<double, 4>> xs;  // last end, busy sum, CU count, workgroups
-            for (auto &kv : by_cu) {
-                auto &x = xs[(unsigned) (kv.first >> 16)];
-                x[0] = std::max(x[0], (double) (kv.second.back()[1] - first));
-                for (auto &w : kv.second) x[1] += (double) (w[1] - w[0]);
-                x[2] += 1;
-                x[3] += (double) kv.second.size();
-            }
-            std::fprintf(stderr, "[awpu diag nd] per XCD (last end us / mean busy us / CUs / workgroups):");
-            for (auto &kv : xs) std::fprintf(stderr, " %u: %.0f/%.0f/%.0f/%.0f", kv.first, kv.second[0] * 0.01, kv.second[1] / kv.second[2] * 0.01, kv.second[2], kv.second[3]);
-            std::vector<double> dur;
-            for (size_t w = 0; w < n_wgs; w++) if (hb[8 * w + 7]) dur.push_back((double) (hb[8 * w + 1] - hb[8 * w]) * 0.01);
-            std::sort(dur.begin(), dur.end());
-            if (!dur.empty()) std::fprintf(stderr, "\n[awpu diag nd] workgroup duration us: min %.1f p10 %.1f median %.1f p90 %.1f max %.1f\n", dur.front(), dur[dur.size() / 10],
-                                           dur[dur.size() / 2], dur[dur.size() * 9 / 10], dur.back());
-        }
-        const double cus = (double) by_cu.size();
-        std::fprintf(stderr, "[awpu diag nd] %zu workgroups on %zu CUs, span %.1f us | per CU: busy %.1f us, gaps %.1f us (%.2f us each), idle before first %.1f us, "
-                     "after last %.1f us | per workgroup cycles: outside the block %.0f, in the sweep block %.0f, exit %.0f\n", n, by_cu.size(), (double) (last - first) * 0.01,
-                     busy / cus * 0.01, gaps / cus * 0.01, n_gaps ? gaps / (double) n_gaps * 0.01 : 0.0, head / cus * 0.01, tail / cus * 0.01, ph[0] / n, ph[1] / n, ph[2] / n);
-    }
-#endif
-    return rc;
-}
-
-// Does launch() sweep a batch of AWPU_MATH_F32_EXACT with das_exact_nd_kernel, and with how many quads per wave?  (The rule of launch()
-// and of the packed-frame entry points: asked before anything is packed.)
-bool takes_exact_nd(awpu_hip *h, int batch, int *nq) {
-    if (!h->exact_pairs_ok || !h->exact_nd_ok || h->cfg.grid_columns < 1) return false;
-    const int ex = env().exact_pairs;
-    if (ex == 0 || ex == 2 || ex == 3) return false;  // AWPU_SHAPE=exact_verify / exact_pair / exact_quad
-    const int cols = h->cfg.grid_columns, rows = h->cfg.pixel_count / cols;
-    // (quad_differ < 1.5: on average fewer than half of a quad's pixels leave the reference pixel's address for a mic; a square
-    // array's vertical and horizontal neighbours coincide equally often -- pair_cols stays 0 there -- and quads still pay)
-    const bool quads_pay = h->cfg.pixel_count % cols == 0 && h->cfg.pixel_begin % cols == 0 && h->quad_differ < 1.5;
-    if ((!(h->pair_cols > 0 || quads_pay) && ex != 4 && ex != 5 && ex != 6) || rows < 4) return false;  // (a forced shape runs on any table: the random tests)
-    // two quads per wave where that still fills the chip (AWPU_SHAPE=exact_nd1 / exact_nd2: one / two everywhere)
-    const long wgs2 = (long) awpu::nd_tiles(rows, cols, 2) * ((batch + 1) / 2);
-    *nq = ex == 4 ? 1 : ex == 5 ? 2 : (rows >= 8 && wgs2 >= 512 ? 2 : 1);
-    return true;
-}
-
-// The completion flag of the synchronous one-frame host call (das_kernels.h: DoneFlag; das_fast.hip: store_tile_and_signal): what the
-// next armed launch of `workgroups` workgroups gets, and what the handle remembers once that launch has gone out.
-int arm_done_flag(awpu_hip *h, unsigned long long workgroups, awpu::DoneFlag *out) {
-    if (!h->d_done_counter) {
-        AWPU_HIP_TRY(hipMalloc(&h->d_done_counter, sizeof(unsigned long long)));
-        AWPU_HIP_TRY(hipMemsetAsync(h->d_done_counter, 0, sizeof(unsigned long long), h->stream));
-        AWPU_HIP_TRY(hipStreamSynchronize(h->stream));  // (the handle's own stream: nothing device-wide from inside a sweep call)
-        AWPU_HIP_TRY(hipHostMalloc(&h->h_done_flag, 64, hipHostMallocDefault));
-        *h->h_done_flag = 0;
-        h->done_total = 0;
-    }
-    out->counter = h->d_done_counter;
-    out->flag = h->h_done_flag;
-    out->target = h->done_total + workgroups;
-    out->seq = h->done_seq + 1;
-    return AWPU_OK;
-}
-void done_flag_armed(awpu_hip *h, const awpu::DoneFlag &d) {
-    h->done_total = d.target;
-    h->done_seq = d.seq;
-    h->done_used = true;
-}
-
-// single frames in the reference's order: the halves form of the {next, d} layout (das_exact_ndh_kernel) -- every mic resident and
-// staged by the workgroups themselves (one array), or chunked behind a pack pre-pass.  `pitch` = floats between two streams of a frame
-int launch_exact_ndh(awpu_hip *h, const float *d_frames, int batch, float *d_power, hipStream_t s, int pitch, int wstart_eff, bool stationary,
-                     int nq, bool pixel_per_wave = false) {
-    int rc = build_quad_lut(h, stationary ? kQuadExactNdhStationary : kQuadExactNdh);
-    if (rc != AWPU_OK) return rc;
-    const awpu::FastPlan &pp = stationary ? h->exact_ndhs_plan : h->exact_ndh_plan;
-    if (!stationary) {
-        const size_t need = std::max((size_t) h->cfg.max_batch, (size_t) batch) * pp.usable_pad * pp.wr * 4;
-        if (const int prc = ensure_pack(h, need); prc != AWPU_OK) return prc;
-    }
-    awpu::ExactNdhArgs a{};
-    a.packed = stationary ? nullptr : h->d_pack;
-    a.frames = d_frames;
-    a.lut = stationary ? h->d_exact_ndhs_lut : h->d_exact_ndh_lut;
-    a.index = h->d_index;
-    a.gain = h->d_gain;
-    a.power = d_power;
-    a.sums = h->sums_out;
-    a.n_streams = h->cfg.n_streams;
-    a.pitch = pitch;
-    a.wstart = wstart_eff;
-    a.usable = h->usable();
-    a.usable_pad = pp.usable_pad;
-    a.pixel_count = h->cfg.pixel_count;
-    a.wh = pp.wr;
-    a.chunk = pp.chunk;
-    a.batch = batch;
-    a.cols = h->cfg.grid_columns;
-    a.rows = h->cfg.pixel_count / a.cols;
-    a.nq = nq;
-    a.tiles = pixel_per_wave ? awpu::ndp_tiles(a.rows, a.cols) : awpu::ndh_tiles(a.rows, a.cols, nq);
-    a.lut_cols = (a.cols + 31) / 32 * 32;
-    a.identity = 1;
-    for (int k = 0; k < a.usable && a.identity; k++) a.identity = h->index[k] == k;
-    h->done_used = false;
-    if (h->done_arm && s == h->stream && stationary && nq == 1 && !pixel_per_wave) {  // (the one-frame host call: live_host_call)
-        rc = arm_done_flag(h, (unsigned long long) batch * a.tiles, &a.done);
-        if (rc != AWPU_OK) return rc;
-    }
-    if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
-    if (!stationary)
-        AWPU_HIP_TRY(awpu::launch_pack_ndh(d_frames, h->cfg.n_streams, pitch, wstart_eff, a.identity ? nullptr : h->d_index, h->usable(), pp.usable_pad, h->d_gain, pp.wr,
-                                           batch, h->d_pack, s));
-    if (pixel_per_wave) {
-        AWPU_HIP_TRY(awpu::launch_das_exact_ndp(a, {h->quad_lut_entries[kQuadExactNdh], h->pack_cap}, s));
-    } else {
-        AWPU_HIP_TRY(awpu::launch_das_exact_ndh(a, stationary, {h->quad_lut_entries[stationary ? kQuadExactNdhStationary : kQuadExactNdh], stationary ? 0 : h->pack_cap}, s));
-    }
-    if (a.done.flag) done_flag_armed(h, a.done);  // (the launch went out: its workgroups will count themselves)
-    return finish_launch(h, batch, s, pixel_per_wave ? AWPU_KERNEL_EXACT_NDP : stationary ? AWPU_KERNEL_EXACT_NDH_STATIONARY : AWPU_KERNEL_EXACT_NDH);
-}
-
-int launch_exact(awpu_hip *h, const float *d_frames, int batch, float *d_power, hipStream_t s, int hist_eff, int wstart_eff) {
-    awpu::SweepArgs a{};
-    a.frames = d_frames;
-    a.lut = h->d_lut;
-    a.index = h->d_index;
-    a.power = d_power;
-    a.gain = h->d_gain;
-    a.n_streams = h->cfg.n_streams;
-    a.hist = hist_eff;
-    a.usable = h->usable();
-    a.pixel_count = h->cfg.pixel_count;
-    a.wstart = wstart_eff;
-    a.window = h->window;
-    a.batch = batch;
-    if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
-    if (h->cfg.interp == AWPU_INTERP_FIR8) {
-        AWPU_HIP_TRY(awpu::launch_das_fir8(a, h->d_fir, s));
-    } else {
-        AWPU_HIP_TRY(awpu::launch_das_exact(a, h->cfg.math == AWPU_MATH_BF16_ACC, s));
-    }
-    return finish_launch(h, batch, s, h->cfg.interp == AWPU_INTERP_FIR8 ? AWPU_KERNEL_FIR8 : AWPU_KERNEL_EXACT_VERIFY);
-}
-
-// FIR8 on the four-plane frame-pair layout (das_fir8_plane_kernel): a lane owns four consecutive outputs
-int launch_fir8_planes(awpu_hip *h, const float *d_frames, int batch, float *d_power, hipStream_t s, int hist_eff, int wstart_eff) {
-    const awpu::FastPlan &pp = h->fir_plane_plan;
-    const int U = h->usable(), P = h->cfg.pixel_count;
-    const int row_entries = pp.usable_pad;  // (a multiple of 4, like the chunk: the block sweeps groups of four items)
-    if (!h->d_fir_plane_lut) {
-        const uint32_t plane_bytes = (uint32_t) pp.row_bytes / 4;
-        // one dword per (pixel, mic); four spare: the block requests entries four items ahead.  Null entries (the
-        // padding of a row, the spares) read row 0 with the zero coefficient row.
-        std::vector<uint32_t> packed((size_t) P * row_entries + awpu::kFir8PlaneTablePrefetch, awpu::fir8_plane_word(0, 0, awpu::kFir8ZeroRow));
-        for (int p = 0; p < P; p++) {
-            const int32_t *orow = &h->off[(size_t) p * h->cfg.lut_stride];
-            const float *frow = &h->frac[(size_t) p * h->cfg.lut_stride];
-            for (int m = 0; m < U; m++) {
-                const int id = h->index[m];
-                const int32_t k = (int32_t) (frow[id] * 100.0f + 0.5f);  // delay.cpp:32-33: the coefficient row
-                const uint32_t first = (uint32_t) (orow[id] - h->wstart);  // row element of X[off]
-                const uint32_t addr = (uint32_t) (m % pp.chunk) * pp.row_bytes + (first & 3) * plane_bytes + (first >> 2) * 8;
-                packed[(size_t) p * row_entries + m] = awpu::fir8_plane_word(addr, first & 3, (uint32_t) k);
-            }
-        }
-        AWPU_HIP_TRY(hipMalloc(&h->d_fir_plane_lut, packed.size() * sizeof(uint32_t)));
-        AWPU_HIP_TRY(hipMemcpy(h->d_fir_plane_lut, packed.data(), packed.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-        h->fir_plane_lut_entries = packed.size();
-    }
-    const size_t need = (size_t) ((h->cfg.max_batch + 1) / 2) * U * pp.wr * 2;
-    if (const int prc = ensure_pack(h, need); prc != AWPU_OK) return prc;
-    awpu::PairArgs pa{};
-    pa.packed = h->d_pack;
-    pa.power = d_power;
-    pa.usable = U;
-    pa.usable_pad = row_entries;
-    pa.pixel_count = P;
-    pa.wp = pp.wr;
-    pa.chunk = pp.chunk;
-    pa.batch = batch;
-    // vertical pixel quads (samples shared between pixels of one column with the same integer delay) where the grid's row
-    // length is known and the rows are staged at the pitch that block is generated for; AWPU_FIR8_SHARE=0: consecutive pixels
-    {
-        const bool allow = env().fir_share != 0;
-        const int cols = h->cfg.grid_columns;
-        if (allow && cols > 0 && P % cols == 0 && h->cfg.pixel_begin % cols == 0 && (uint32_t) pp.wr * 2u == awpu::kFirStaticPlaneBytesHost)
-            pa.cols = cols;
-    }
-    if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
-    AWPU_HIP_TRY(awpu::launch_pack_planes(d_frames, h->cfg.n_streams, hist_eff, wstart_eff, h->d_index, U, h->d_gain, pp.wr,
-                                          batch, h->d_pack, s));
-    AWPU_HIP_TRY(awpu::launch_das_fir8_planes(pa, h->d_fir_plane_lut, h->d_fir, env().quad_variant, {h->fir_plane_lut_entries, h->pack_cap}, s));
-    return finish_launch(h, batch, s, AWPU_KERNEL_FIR8_PLANES);
-}
-
-// frame-pair shape: two frames per item, for batches on grids that fill the chip
-int launch_pairs(awpu_hip *h, const awpu_hip::FastLut *plut, const float *d_frames, int batch, float *d_power,
-                 hipStream_t s, int hist_eff, int wstart_eff, int stationary_tiles = 0, const float *prepacked = nullptr,
-                 size_t prepacked_floats = 0) {
-    const awpu::FastPlan &pp = plut->plan;
-    const size_t need = (size_t) ((h->cfg.max_batch + 1) / 2) * h->usable() * pp.wr * 2;
-    // the stationary shape stages its pairs itself, straight from the caller's frames (no pack pre-pass, no packed buffer)
-    const bool self_staged = stationary_tiles > 0 && !prepacked;
-    if (!prepacked && !self_staged)
-        if (const int prc = ensure_pack(h, need); prc != AWPU_OK) return prc;
-    awpu::PairArgs pa{};
-    pa.packed = prepacked ? prepacked : (self_staged ? nullptr : h->d_pack);
-    if (self_staged) {
-        pa.frames = d_frames;
-        pa.index = h->d_index;
-        pa.n_streams = h->cfg.n_streams;
-        pa.hist = hist_eff;
-        pa.wstart = wstart_eff;
-    }
-    pa.lut = plut->d;
-    pa.power = d_power;
-    pa.usable = h->usable();
-    pa.usable_pad = pp.usable_pad;
-    pa.pixel_count = h->cfg.pixel_count;
-    pa.wp = pp.wr;
-    pa.chunk = pp.chunk;
-    pa.batch = batch;
-    pa.cols = h->pair_cols;
-    pa.tiles = awpu::pair_tiles(h->cfg.pixel_count, h->pair_cols);
-    pa.n_pairs = (batch + 1) / 2;
-    pa.pair_group = xcd_pair_group(pp, h->usable(), pa.n_pairs);
-    pa.debug = env().debug;
-    pa.debug_out = nullptr;
-    size_t n_waves = 0;
-    if (stationary_tiles > 0) pa.debug &= ~16;  // (no stamped build of the stationary shape)
-    if (pa.debug & 16) {
-        n_waves = (size_t) 16 * ((batch + 1) / 2) * awpu::pair_tiles(h->cfg.pixel_count, h->pair_cols);
-        const int rc = ensure_diag(h, n_waves * 12);
-        if (rc != AWPU_OK) return rc;
-        pa.debug_out = h->d_diag;
-    }
-    if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
-    if (!prepacked && !self_staged)
-        AWPU_HIP_TRY(awpu::launch_pack_pairs(d_frames, h->cfg.n_streams, hist_eff, wstart_eff, h->d_index, h->usable(),
-                                             h->usable(), nullptr, pp.wr, batch, h->d_pack, true, s));  // gains ride on the table weights here
-    const awpu::Extents have{plut->entries, prepacked ? prepacked_floats : h->pack_cap};
-    if (stationary_tiles > 0) {
-        AWPU_HIP_TRY(awpu::launch_das_pairs_stationary(pa, stationary_tiles, have, s));
-    } else {
-        AWPU_HIP_TRY(awpu::launch_das_pairs(pa, have, s));
-    }
-    const int rc = finish_launch(h, batch, s, stationary_tiles > 0 ? AWPU_KERNEL_PAIR_STATIONARY : AWPU_KERNEL_PAIR);
-    if (rc != AWPU_OK || !(pa.debug & 16)) return rc;
-    return dump_diag(h, n_waves, 16, "pairs", s);
-}
-
-// quad shape: the frame-pair layout swept four vertically adjacent pixels at a time (das_quad_kernel)
-int launch_quads(awpu_hip *h, const float *d_frames, int batch, float *d_power, hipStream_t s, int hist_eff, int wstart_eff,
-                 const float *prepacked = nullptr, size_t prepacked_floats = 0) {
-    int rc = build_quad_lut(h, kQuadPairs);
-    if (rc != AWPU_OK) return rc;
-    const awpu::FastPlan &pp = h->quad_plan;
-    const size_t need = (size_t) ((h->cfg.max_batch + 1) / 2) * pp.usable_pad * pp.wr * 2;
-    if (!prepacked)
-        if (const int prc = ensure_pack(h, need); prc != AWPU_OK) return prc;
-    awpu::QuadArgs qa{};
-    qa.packed = prepacked ? prepacked : h->d_pack;
-    qa.lut = h->d_quad_lut;
-    qa.power = d_power;
-    qa.usable = h->usable();
-    qa.usable_pad = pp.usable_pad;
-    qa.pixel_count = h->cfg.pixel_count;
-    qa.wp = pp.wr;
-    qa.chunk = pp.chunk;
-    qa.batch = batch;
-    qa.cols = h->cfg.grid_columns;
-    qa.rows = h->cfg.pixel_count / qa.cols;
-    qa.tiles = awpu::quad_tiles(qa.rows, qa.cols);
-    qa.n_pairs = (batch + 1) / 2;
-    {   // frame pairs one XCD works on at a time: as many as keep their samples in its 4 MiB L2 beside the table stream.
-        // (Eight pairs at the headline shape, 5.9 MB of samples, run 1.2 % faster than four -- fewer table passes --
-        // but the samples then stream from beyond the L2: 3.2 GB of L2 misses per launch instead of 0.72 GB.  Not taken.)
-        const size_t pair_bytes = (size_t) pp.usable_pad * pp.wr * 8;
-        int g = env().pair_group > 0 ? env().pair_group : (int) std::max<size_t>(1, (3u << 20) / pair_bytes);
-        g = g >= 8 ? 8 : g >= 4 ? 4 : g >= 2 ? 2 : 1;
-        while (g > 1 && g > qa.n_pairs) g >>= 1;
-        qa.pair_group = g;
-    }
-    qa.debug = env().debug;
-    qa.variant = env().quad_variant;
-    // Persistent workgroups (one per CU, each walking its share of the items with the next item's first chunk
-    // prefetched) are 1.5 % faster than one workgroup per item on a chip they have to themselves, and fragile on one
-    // they share: their share of the items is static.  A handle that owns the whole grid has the GPU to itself; a
-    // handle that owns a slab is a rank of a multi-GPU run, beside which the broadcast of the next batch holds CUs.
-    qa.wgs = env().wgs;
-    if (qa.wgs == 0 && h->cfg.pixel_count == h->cfg.n_pixels) {
-        int n_cu = 0;
-        if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, h->cfg.device) == hipSuccess) qa.wgs = n_cu;
-    }
-    if (qa.wgs < 0) qa.wgs = 0;  // AWPU_FAST_WGS=-1: one workgroup per item everywhere
-    // Round 5: the persistent workgroups take their items from queues (one per XCD, a run's last eighth common to the chip) instead of
-    // static shares -- balanced whatever the XCDs' clocks and whoever else holds CUs, so a rank's slab takes them too
-    if (env().wgs == 0) {
-        if (!h->d_nd_queue) {
-            AWPU_HIP_TRY(hipMalloc(&h->d_nd_queue, 9 * sizeof(unsigned)));
-            if (hipDeviceGetAttribute(&h->n_cus, hipDeviceAttributeMultiprocessorCount, h->cfg.device) != hipSuccess || h->n_cus < 1) h->n_cus = 256;
-        }
-        if (h->n_cus < 1 && (hipDeviceGetAttribute(&h->n_cus, hipDeviceAttributeMultiprocessorCount, h->cfg.device) != hipSuccess || h->n_cus < 1))
-            h->n_cus = 256;
-        qa.queue = h->d_nd_queue;
-        qa.wgs = h->n_cus;
-        const int per = (qa.n_pairs * qa.tiles + 7) / 8;
-        qa.tail = per >= 32 ? (per + 7) / 8 : per;
-    }
-    qa.debug_out = nullptr;
-    size_t n_waves = 0;
-    if (qa.debug & 16) {
-        const long per_xcd = ((long) qa.n_pairs * qa.tiles + 7) / 8;
-        n_waves = (size_t) 16 * 8 * (size_t) (qa.wgs > 0 ? std::min<long>(per_xcd, std::max(1, qa.wgs / 8)) : per_xcd);
-        rc = ensure_diag(h, n_waves * 12);
-        if (rc != AWPU_OK) return rc;
-        AWPU_HIP_TRY(hipMemsetAsync(h->d_diag, 0, n_waves * 12 * sizeof(unsigned long long), s));
-        qa.debug_out = h->d_diag;
-    }
-    if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
-    if (!prepacked)
-        AWPU_HIP_TRY(awpu::launch_pack_pairs(d_frames, h->cfg.n_streams, hist_eff, wstart_eff, h->d_index, h->usable(),
-                                             pp.usable_pad, h->d_gain, pp.wr, batch, h->d_pack, true, s));
-    AWPU_HIP_TRY(awpu::launch_das_quads(qa, {h->quad_lut_entries[kQuadPairs], prepacked ? prepacked_floats : h->pack_cap}, s));
-    rc = finish_launch(h, batch, s, AWPU_KERNEL_QUAD);
-    if (rc != AWPU_OK || !(qa.debug & 16)) return rc;
-    return dump_diag(h, n_waves, 16, "quads", s);
-}
-
-// quad shape for single frames on the halves layout (das_quadh_kernel): a pack + filter pre-pass, then the sweep
-int launch_quadsh(awpu_hip *h, const float *d_frames, int batch, float *d_power, hipStream_t s, int pitch, int hist_eff, int wstart_eff,
-                  int qpw) {
-    int rc = build_quad_lut(h, kQuadHalves);
-    if (rc != AWPU_OK) return rc;
-    const awpu::FastPlan &pp = h->quadh_plan;
-    const size_t need = std::max((size_t) h->cfg.max_batch, (size_t) batch) * pp.usable_pad * pp.wr * 2;
-    if (const int prc = ensure_pack(h, need); prc != AWPU_OK) return prc;
-    awpu::QuadhArgs qa{};
-    qa.packed = h->d_pack;
-    qa.lut = h->d_quadh_lut;
-    qa.power = d_power;
-    qa.usable = h->usable();
-    qa.usable_pad = pp.usable_pad;
-    qa.pixel_count = h->cfg.pixel_count;
-    qa.wp = pp.wr;
-    qa.chunk = pp.chunk;
-    qa.batch = batch;
-    qa.cols = h->cfg.grid_columns;
-    qa.rows = h->cfg.pixel_count / qa.cols;
-    qa.debug = env().debug;
-    qa.debug_out = nullptr;
-    size_t n_waves = 0;
-    if (qa.debug & 16) {
-        n_waves = (size_t) 16 * batch * awpu::quad1_tiles(qa.rows, qa.cols, qpw);
-        rc = ensure_diag(h, n_waves * 12);
-        if (rc != AWPU_OK) return rc;
-        qa.debug_out = h->d_diag;
-    }
-    if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
-    bool identity = true;  // the active-mic list is 0 .. usable-1 (awpu_hip_set_active_mics(NULL)): the pre-pass needs no look-up
-    for (int k = 0; k < h->usable() && identity; k++) identity = h->index[k] == k;
-    AWPU_HIP_TRY(awpu::launch_pack_halves(d_frames, h->cfg.n_streams, pitch, hist_eff, wstart_eff, identity ? nullptr : h->d_index, h->usable(),
-                                          pp.usable_pad, h->d_gain, pp.wr, batch, h->d_pack, s));
-    AWPU_HIP_TRY(awpu::launch_das_quadh(qa, qpw, {h->quad_lut_entries[kQuadHalves], h->pack_cap}, s));
-    rc = finish_launch(h, batch, s, AWPU_KERNEL_QUADH);
-    if (rc != AWPU_OK || !(qa.debug & 16)) return rc;
-    return dump_diag(h, n_waves, 16, "quadsh", s);
-}
-
-// single frames of small arrays: every mic's halves row resident, the workgroup stages the window itself (das_quadh_stationary_kernel)
-int launch_quadsh_stationary(awpu_hip *h, const float *d_frames, int batch, float *d_power, hipStream_t s, int pitch, int hist_eff,
-                             int wstart_eff, int qpw) {
-    int rc = build_quad_lut(h, kQuadHalvesStationary);
-    if (rc != AWPU_OK) return rc;
-    const awpu::FastPlan &pp = h->quadhs_plan;
-    awpu::QuadhStationaryArgs qa{};
-    qa.frames = d_frames;
-    qa.lut = h->d_quadhs_lut;
-    qa.index = h->d_index;
-    qa.gain = h->d_gain;
-    qa.power = d_power;
-    qa.n_streams = h->cfg.n_streams;
-    qa.pitch = pitch;
-    qa.hist = hist_eff;
-    qa.wstart = wstart_eff;
-    qa.usable = h->usable();
-    qa.usable_pad = pp.usable_pad;
-    qa.pixel_count = h->cfg.pixel_count;
-    qa.wp = pp.wr;
-    qa.batch = batch;
-    qa.cols = h->cfg.grid_columns;
-    qa.rows = h->cfg.pixel_count / qa.cols;
-    qa.waves = 16;
-    qa.identity = 1;
-    for (int k = 0; k < qa.usable && qa.identity; k++) qa.identity = h->index[k] == k;
-    qa.row_limit = pitch;  // (the ring's rows are 2048 floats of which any 1024 + window are valid: double-written)
-    if (!awpu::quadh_stationary_raw(pp, qa.usable, wstart_eff, qa.row_limit, &qa.raw_begin, &qa.raw_wr, &qa.image_offset))
-        return invalid("the raw window does not fit the LDS beside the halves image");  // (launch() asks before it comes here)
-    h->done_used = false;
-    if (h->done_arm && s == h->stream && qpw == 1) {  // (the one-frame host call: live_host_call)
-        rc = arm_done_flag(h, (unsigned long long) batch * awpu::quad1_tiles(qa.rows, qa.cols, 1), &qa.done);
-        if (rc != AWPU_OK) return rc;
-    }
-    if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
-    AWPU_HIP_TRY(awpu::launch_das_quadh_stationary(qa, qpw, {h->quad_lut_entries[kQuadHalvesStationary], 0}, s));
-    if (qa.done.flag) done_flag_armed(h, qa.done);
-    return finish_launch(h, batch, s, AWPU_KERNEL_QUADH_STATIONARY);
-}
 }  // namespace
 
 namespace awpu::host {
-
-int launch(awpu_hip *h, const float *d_frames, int batch, float *d_power, hipStream_t s, int layout) {
-    const bool compact = layout == kCompact;
-    const int hist_eff = compact ? h->compact_hist : (layout == kRing ? 2048 : h->cfg.hist);
-    const int wstart_eff = compact ? 0 : h->wstart;
-    // FIR8 with fast math on a launch that fills the chip: the frame-pair kernels.  A single frame (or the odd last
-    // one) is swept as a pair with itself -- half the packed lanes idle, still 1.6 x the rate of das_fir8_kernel.
-    const long fir_wgs = (long) ((h->cfg.pixel_count + 63) / 64) * ((batch + 1) / 2);
-    if (h->cfg.interp == AWPU_INTERP_FIR8 && h->cfg.math == AWPU_MATH_F32_FAST && env().pairs != 0 &&
-        (fir_wgs >= (batch >= 2 ? 256 : 192) || (env().fir_planes == 2 && batch >= 2))) {
-        if (env().fir_planes && awpu::fir8_plane_plan(h->window, h->usable(), &h->fir_plane_plan))
-            return launch_fir8_planes(h, d_frames, batch, d_power, s, hist_eff, wstart_eff);
-    }
-    if (h->exact_pairs_ok && env().exact_pairs != 0) {
-        // vertical pixel quads on the {next, d} layout (round 5) where the row length is known and the table's statistics favour them
-        // (takes_exact_nd; AWPU_SHAPE=exact_quad: round 4's kernel on raw sample pairs; exact_pair: the two-pixel block everywhere)
-        int nq = 1;
-        const bool nd = takes_exact_nd(h, batch, &nq);
-        // one frame per call (MIMOWorker::update's regime): the halves form of the layout -- the two packed lanes are the two halves of
-        // the block, not a frame and its copy; every mic resident where one array's rows fit the LDS (no pre-pass)
-        const int ex = env().exact_pairs;
-        const bool grid_known = h->cfg.grid_columns >= 1 && h->cfg.pixel_count % h->cfg.grid_columns == 0;
-        if (batch == 1 && (ex == 1 || ex == 6) && grid_known && (h->exact_ndhs_ok || h->exact_ndh_ok)) {
-            const int rows = h->cfg.pixel_count / h->cfg.grid_columns, cols = h->cfg.grid_columns;
-            if (h->n_cus < 1 && (hipDeviceGetAttribute(&h->n_cus, hipDeviceAttributeMultiprocessorCount, h->cfg.device) != hipSuccess || h->n_cus < 1))
-                h->n_cus = 256;
-            // grids of at most 32 pixels per CU (two rounds of 16-wave workgroups): one PIXEL per wave (das_exact_ndp_kernel) -- a quad
-            // kernel leaves such a grid one or two waves per SIMD, and the frame then takes as long as one wave's instruction issue.
-            // Measured, 256 mics, one frame per call, quads -> pixels: 64 x 64 69.1 -> 31.6 us; 72^2 69.3 -> 52.1; 80^2 67.2 -> 53.3;
-            // 88^2 66.1 -> 56.5; 96^2 (a third round) 81.1 -> 76.4; 100^2 69.3 -> 77.9 (profiles/r05_single_frame_ablation.txt).  It shares
-            // no reads between pixels, so it also serves tables whose quads do not share (where the quad kernels are not chosen at all)
-            // One array (every mic resident in the quad kernel, no pre-pass) against pixels behind the pre-pass: 32^2 (its quads do not
-            // share: das_exact_pair_kernel) 36.9 -> 10.4 us; 48^2 22.3 -> 10.8; 64^2 21.1 -> 11.5; 80^2 20.3 -> 18.6; 100^2 (three rounds) 21.3 -> 26.0
-            bool solo = h->exact_ndh_ok && awpu::ndp_tiles(rows, cols) * (long) batch <= 2L * h->n_cus;
-            if (ex == 6) solo = h->exact_ndh_ok;
-#ifdef AWPU_TUNING_BUILD
-            if (const char *v = std::getenv("AWPU_NDH_WAVES")) solo = std::atoi(v) == 1 && h->exact_ndh_ok;
-#endif
-            if (solo) return launch_exact_ndh(h, d_frames, batch, d_power, s, hist_eff, wstart_eff, false, 1, true);
-            // (smaller workgroups of quads -- 8 or 4 waves, one round -- were the first answer to such grids: c2 76.6 -> 71.7 / 68.9 us;
-            // one pixel per wave replaced them)
-            if (nd) return launch_exact_ndh(h, d_frames, batch, d_power, s, hist_eff, wstart_eff, h->exact_ndhs_ok, (long) awpu::quad1_tiles(rows, cols, 2) >= 256 ? 2 : 1);
-        }
-        if (nd) return launch_exact_nd(h, d_frames, batch, d_power, s, hist_eff, wstart_eff, nq);
-        if (env().exact_pairs == 3 && h->pair_cols > 0 && h->cfg.pixel_count / h->cfg.grid_columns >= 4)
-            return launch_exact_quads(h, d_frames, batch, d_power, s, hist_eff, wstart_eff);
-        return launch_exact_pairs(h, d_frames, batch, d_power, s, hist_eff, wstart_eff);
-    }
-    if (h->sums_out) return fail(AWPU_ERR_STATE, "the pre-epilogue sums are exported by the frame-pair reference-order kernel only");
-    if (h->cfg.math != AWPU_MATH_F32_FAST || h->cfg.interp == AWPU_INTERP_FIR8)
-        return launch_exact(h, d_frames, batch, d_power, s, hist_eff, wstart_eff);
-
-    // ---- frame-pair shape: batches on grids that fill the chip (AWPU_FAST_PAIRS=0/1 overrides)
-    const int env_pairs = env().pairs;
-    const long pair_wgs = (long) awpu::pair_tiles(h->cfg.pixel_count, h->pair_cols) * ((batch + 1) / 2);
-    if (layout != kRing && batch >= 2 && h->quad_ok && env_pairs != 0 &&
-        ((long) awpu::quad_tiles(h->cfg.pixel_count / h->cfg.grid_columns, h->cfg.grid_columns) * ((batch + 1) / 2) >= 256 ||
-         env().quads == 1))
-        return launch_quads(h, d_frames, batch, d_power, s, hist_eff, wstart_eff);
-    // ---- stationary shape: the whole window of every active mic of a frame pair fits the LDS (one 8x8 array does)
-    if (layout != kRing && batch >= 2 && env_pairs != 0 && env().stationary != 0) {
-        awpu::FastPlan sp;
-        const long tiles = awpu::pair_tiles(h->cfg.pixel_count, h->pair_cols), pairs = (batch + 1) / 2;
-        if (awpu::pair_plan_stationary(h->window, h->usable(), &sp) && (pairs * tiles >= 128 || env().stationary == 1)) {
-            const awpu_hip::FastLut *slut = nullptr;
-            const int rc = build_fast_lut(h, 2, -2, &slut);
-            if (rc == AWPU_OK) {
-                // tiles per workgroup: enough to amortise the staging, few enough to leave every CU a workgroup
-#ifndef AWPU_STATIONARY_WGS
-#define AWPU_STATIONARY_WGS 256  // (tuning builds: -DAWPU_STATIONARY_WGS=512 ... through tools/build_variant.sh)
-#endif
-                const int tpw = (int) std::max<long>(1, std::min<long>(tiles, pairs * tiles / AWPU_STATIONARY_WGS));
-                return launch_pairs(h, slut, d_frames, batch, d_power, s, hist_eff, wstart_eff, tpw);
-            }
-            if (rc != AWPU_ERR_INVALID) return rc;
-        }
-    }
-    if (layout != kRing && batch >= 2 && env_pairs != 0 && (pair_wgs >= 256 || env_pairs == 1)) {
-        const awpu_hip::FastLut *plut = nullptr;
-        const int rc = build_fast_lut(h, 2, -1, &plut);
-        if (rc == AWPU_OK) return launch_pairs(h, plut, d_frames, batch, d_power, s, hist_eff, wstart_eff);
-        // a window too wide for the pair image is served by the single-frame shapes below; anything
-        // else (an allocation or copy that failed) is the caller's to know about
-        if (rc != AWPU_ERR_INVALID) return rc;
-    }
-    // ---- single frames on grids of at most 16 pixels per CU: the reference-order kernel with one pixel per wave
-    // (das_exact_ndp_kernel) is the fastest sweep this library has for them in ANY mode (c2, one frame per call: 47.6 us on this
-    // mode's 8-wave shape, 29.9 us there; c1 11.7 -> 10.1) and its powers are the reference's own arithmetic -- inside this
-    // mode's contract on any input.  Not when a shape of this mode is forced (AWPU_SHAPE: the tests sweep each through the oracle)
-    if (h->fast_ndp_ok && h->cfg.grid_columns >= 1 && h->cfg.pixel_count % h->cfg.grid_columns == 0 && env().fpi == 0 &&
-        env().halves == -1 && env().quads == -1 && env_pairs == -1 && env().stationary == -1) {
-        if (h->n_cus < 1 && (hipDeviceGetAttribute(&h->n_cus, hipDeviceAttributeMultiprocessorCount, h->cfg.device) != hipSuccess || h->n_cus < 1))
-            h->n_cus = 256;
-        if (awpu::ndp_tiles(h->cfg.pixel_count / h->cfg.grid_columns, h->cfg.grid_columns) * (long) batch <= h->n_cus)
-            return launch_exact_ndh(h, d_frames, batch, d_power, s, hist_eff, wstart_eff, false, 1, true);
-    }
-    // ---- single frames on a grid whose table favours the quad shape (a forced single-frame shape goes past): the halves
-    // layout behind a pack + filter pre-pass
-    if (h->quadhs_fits && env().fpi == 0 && env().halves != 0 && env().stationary != 0) {
-        // one 8x8 array (every mic's halves row fits the LDS): one launch, no pack pre-pass, no chunks.  A call this small is
-        // latency, not throughput: taken from 48 workgroups on (below that the 8-wave shapes spread a tiny grid over more CUs)
-        const int rows = h->cfg.pixel_count / h->cfg.grid_columns, cols = h->cfg.grid_columns;
-        const int qpw = (long) awpu::quad1_tiles(rows, cols, 2) * batch >= 256 ? 2 : 1;
-        int rb = 0, rw = 0, io = 0;
-        if (((long) awpu::quad1_tiles(rows, cols, qpw) * batch >= 48 || env().quads == 1 || env().halves == 1 || env().stationary == 1) &&
-            awpu::quadh_stationary_raw(h->quadhs_plan, h->usable(), wstart_eff, hist_eff, &rb, &rw, &io))
-            return launch_quadsh_stationary(h, d_frames, batch, d_power, s, hist_eff, layout == kRing ? AWPU_HIST : hist_eff, wstart_eff, qpw);
-    }
-    if (h->quadh_fits && env().fpi == 0 && env().halves != 0) {
-        const int rows = h->cfg.pixel_count / h->cfg.grid_columns, cols = h->cfg.grid_columns;
-        const int qpw = (long) awpu::quad1_tiles(rows, cols, 2) * batch >= 256 ? 2 : 1;
-        // from 96 workgroups on.  (Measured, one frame per call, 256 mics: a 100 x 100 grid = 175 workgroups 54.5 us here against
-        // 98.9 us for the 8-wave shape; 64 x 64 = 64 workgroups 56.5 against 47.8 -- this kernel's time is its 256-stage
-        // dependent chain whatever the grid, the 8-wave shape's grows with the pixels: they cross near 80 workgroups.  The
-        // threshold of rounds 2-3 was 192 and sent the four-array, default-resolution case to the slower shape.)
-        if ((long) awpu::quad1_tiles(rows, cols, qpw) * batch >= 96 || env().quads == 1 || env().halves == 1) {
-            // pitch between streams: the ring's rows are 2048 floats apart; the history a stream offers the filter is hist_eff
-            const int pitch = hist_eff;
-            return launch_quadsh(h, d_frames, batch, d_power, s, pitch, layout == kRing ? AWPU_HIST : hist_eff, wstart_eff, qpw);
-        }
-    }
-    int fpi = 1, ppw = 8, nw = 8;
-    choose_fast_variant(h, batch, &fpi, &ppw, &nw);
-    const awpu_hip::FastLut *lut = nullptr;
-    int rc = build_fast_lut(h, fpi, awpu::fast_image_bytes(nw), &lut);
-    if (rc != AWPU_OK && rc != AWPU_ERR_INVALID) return rc;
-    // the double-buffered shapes read whole 16-byte pieces of every staged row
-    if (nw != 8 && (rc != AWPU_OK || !awpu::fast_db_fits(lut->plan) || wstart_eff + 1 + lut->plan.wr > hist_eff)) {
-        nw = 8;
-        if (ppw > 4) ppw = 4;  // (the 8-wave shape is built for 2 and 4 pixels per wave)
-        rc = build_fast_lut(h, fpi, awpu::fast_image_bytes(nw), &lut);
-    }
-    if (rc != AWPU_OK) return rc;
-    const awpu::FastPlan &plan = lut->plan;
-    awpu::FastArgs a{};
-    a.frames = d_frames;
-    a.lut = lut->d;
-    a.index = h->d_index;
-    a.row_off = compact ? h->d_row_off_compact : (layout == kRing ? h->d_row_off_ring : h->d_row_off);
-    a.power = d_power;
-    a.n_streams = h->cfg.n_streams;
-    a.hist = hist_eff;
-    a.usable = h->usable();
-    a.usable_pad = plan.usable_pad;
-    a.pixel_count = h->cfg.pixel_count;
-    a.wstart = wstart_eff;
-    a.wr = plan.wr;
-    a.chunk = plan.chunk;
-    a.batch = batch;
-    // frames per persistent workgroup: measured, persistence over frames buys nothing
-    a.frames_per_wg = std::min(env().fpw > 0 ? env().fpw : 1, batch);
-    a.debug = env().debug;
-    a.debug_out = nullptr;
-    size_t n_waves = 0;
-    const int wg_waves = nw == 24 ? 12 : 16;
-    if ((a.debug & 16) && nw != 8) {  // the double-buffered shapes have a stamped build
-        n_waves = (size_t) wg_waves * ((batch + a.frames_per_wg - 1) / a.frames_per_wg) *
-                  ((h->cfg.pixel_count + wg_waves * ppw - 1) / (wg_waves * ppw));
-        rc = ensure_diag(h, n_waves * 12);
-        if (rc != AWPU_OK) return rc;
-        a.debug_out = h->d_diag;
-    }
-    if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
-    AWPU_HIP_TRY(awpu::launch_das_fast(a, fpi, ppw, nw, {lut->entries, 0}, s));
-    rc = finish_launch(h, batch, s, nw == 32 ? AWPU_KERNEL_SINGLE_DB : (nw == 8 && fpi == 1 && ppw <= 4 ? AWPU_KERNEL_SINGLE_SMALL : AWPU_KERNEL_TUNING));
-    if (rc != AWPU_OK || !a.debug_out) return rc;
-    return dump_diag(h, n_waves, wg_waves, "single", s);
-}
 
 int check_ready(awpu_hip *h, int batch) {
     if (!h) return invalid("null handle");
@@ -1776,59 +578,6 @@ int group_process(awpu_hip *g, const float *frames, int batch, float *power) {
     });
     if (rc != AWPU_OK) return rc;
     return for_each_part(g, [&](awpu_hip *part) { return wait_and_time(part); });
-}
-
-// Would launch() sweep this batch with one of the frame-pair shapes that read the packed layout (quad or pair)?  The rule of
-// awpu_hip_process_packed, asked before anything is packed.
-bool takes_packed_pairs(awpu_hip *h, int batch, awpu::FastPlan *plan) {
-    if (batch < 2 || h->cfg.interp != AWPU_INTERP_LERP || h->usable() % 4 != 0 || !h->gain.empty()) return false;
-    if (h->cfg.math == AWPU_MATH_F32_EXACT) {  // the reference's order: the {next, d} rows of das_exact_nd_kernel
-        int nq = 1;
-        if (!takes_exact_nd(h, batch, &nq)) return false;
-        *plan = h->exact_nd_plan;
-        return true;
-    }
-    if (h->cfg.math != AWPU_MATH_F32_FAST || env().pairs == 0) return false;
-    if (!awpu::pair_plan(h->window, h->usable(), plan)) return false;
-    const long pairs = (batch + 1) / 2;
-    const bool quad_fills = h->quad_ok && h->quad_plan.wr == plan->wr && h->quad_plan.usable_pad == h->usable() &&
-                            ((long) awpu::quad_tiles(h->cfg.pixel_count / h->cfg.grid_columns, h->cfg.grid_columns) * pairs >= 256 || env().quads == 1);
-    const bool pair_fills = (long) awpu::pair_tiles(h->cfg.pixel_count, h->pair_cols) * pairs >= 256 || env().pairs == 1;
-    return quad_fills || pair_fills;
-}
-
-// floats of `batch` frames in the packed layout of `plan` (rows of plan.row_bytes: sample pairs of a frame pair, or their {next, d}
-// elements), `usable` rows per pair (the packed entry points ask for usable % 4 == 0: no padding rows)
-size_t packed_floats_of(const awpu_hip *h, const awpu::FastPlan &plan, int batch) {
-    return (size_t) ((batch + 1) / 2) * h->usable() * (size_t) (plan.row_bytes / 4);
-}
-// the sweep's pack pass into a caller's buffer: pre-filtered sample pairs (FAST) or {next, d} elements (EXACT)
-int pack_for_sweep(awpu_hip *h, const awpu::FastPlan &plan, const float *d_frames, int batch, float *d_packed, hipStream_t s) {
-    if (h->cfg.math == AWPU_MATH_F32_EXACT)
-        AWPU_HIP_TRY(awpu::launch_pack_nd(d_frames, h->cfg.n_streams, h->cfg.hist, h->wstart, h->d_index, h->usable(), h->usable(), nullptr, plan.wr,
-                                          batch, d_packed, s));
-    else
-        AWPU_HIP_TRY(awpu::launch_pack_pairs(d_frames, h->cfg.n_streams, h->cfg.hist, h->wstart, h->d_index, h->usable(), h->usable(), nullptr,
-                                             plan.wr, batch, d_packed, true, s));
-    return AWPU_OK;
-}
-
-// the sweep of packed frame pairs (what awpu_hip_process_packed does once its arguments are checked)
-int sweep_packed(awpu_hip *h, const awpu::FastPlan &plan, const float *d_packed, size_t packed_floats, int batch, float *d_power,
-                 hipStream_t s) {
-    if (h->cfg.math == AWPU_MATH_F32_EXACT) {
-        int nq = 1;
-        if (!takes_exact_nd(h, batch, &nq)) return fail(AWPU_ERR_STATE, "packed frames: this batch is not swept by the {next, d} kernel");
-        return launch_exact_nd(h, nullptr, batch, d_power, s, h->cfg.hist, h->wstart, nq, d_packed, packed_floats);
-    }
-    const bool quad_fills = h->quad_ok && ((long) awpu::quad_tiles(h->cfg.pixel_count / h->cfg.grid_columns, h->cfg.grid_columns) *
-                                               ((batch + 1) / 2) >= 256 || env().quads == 1);
-    if (quad_fills && env().pairs != 0 && h->quad_plan.wr == plan.wr && h->quad_plan.usable_pad == h->usable())
-        return launch_quads(h, nullptr, batch, d_power, s, h->cfg.hist, h->wstart, d_packed, packed_floats);
-    const awpu_hip::FastLut *plut = nullptr;
-    const int rc = build_fast_lut(h, 2, -1, &plut);
-    if (rc != AWPU_OK) return rc;
-    return launch_pairs(h, plut, nullptr, batch, d_power, s, h->cfg.hist, h->wstart, 0, d_packed, packed_floats);
 }
 
 // Every part of a group stages the same window -- the union of what the parts' own rows touch -- so that ONE packed buffer
@@ -2996,26 +1745,12 @@ int awpu_hip_resize_linear_u8(const uint8_t *pix, int32_t rows, int32_t cols, ui
 
 namespace {
 
-// The layout both frame-pair shapes read when usable is a multiple of four and no gains are set:
-// [ceil(batch/2)][usable][wr][2] floats.  AWPU_ERR_STATE when this handle's sweep does not take packed frames.
+// the packed layout of a single-device handle that is ready for `batch` frames (packed_shape: awpu_sweep.cpp)
 int packed_plan(awpu_hip *h, int batch, awpu::FastPlan *plan) {
     if (!h) return invalid("null handle");
     if (!h->parts.empty()) return fail(AWPU_ERR_STATE, "packed frames: a device group exchanges its frames itself");
     const int rc = check_ready(h, batch);
-    if (rc != AWPU_OK) return rc;
-    if ((h->cfg.math != AWPU_MATH_F32_FAST && h->cfg.math != AWPU_MATH_F32_EXACT) || h->cfg.interp != AWPU_INTERP_LERP)
-        return fail(AWPU_ERR_STATE, "packed frames need AWPU_MATH_F32_EXACT or AWPU_MATH_F32_FAST, and AWPU_INTERP_LERP");
-    if (h->usable() % 4 != 0 || !h->gain.empty())
-        return fail(AWPU_ERR_STATE, "packed frames need usable % 4 == 0 and no mic gains (the shapes of a mode then read one layout)");
-    if (h->cfg.math == AWPU_MATH_F32_EXACT) {  // the {next, d} rows of das_exact_nd_kernel: where launch() takes that kernel for this batch
-        int nq = 1;
-        if (batch < 2 || !takes_exact_nd(h, batch, &nq))
-            return fail(AWPU_ERR_STATE, "packed frames in the reference's order need the grid's row length (grid_columns) and a batch of two or more");
-        *plan = h->exact_nd_plan;
-        return AWPU_OK;
-    }
-    if (!awpu::pair_plan(h->window, h->usable(), plan)) return fail(AWPU_ERR_STATE, "the window does not fit the frame-pair image");
-    return AWPU_OK;
+    return rc != AWPU_OK ? rc : packed_shape(h, batch, plan);
 }
 
 }  // namespace
@@ -3051,7 +1786,7 @@ int awpu_hip_process_packed(awpu_hip_t *h, const float *d_packed, int32_t batch,
     if (rc != AWPU_OK) return rc;
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
     TimingOff untimed(h);  // asynchronous path: the caller times its own stream
-    // the shape awpu_hip_process_device takes for this batch (same rule: same bits), as long as that is a frame-pair shape
+    // the shape awpu_hip_process_device takes for this batch, as long as that is a frame-pair shape (sweep_packed)
     // (the buffer is the caller's: awpu_hip_packed_bytes(batch) of it are taken to be there, and the sweep reads no further)
     return sweep_packed(h, plan, d_packed, packed_floats_of(h, plan, batch), batch, d_power, s);
 }

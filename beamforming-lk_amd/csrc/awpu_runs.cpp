@@ -1,6 +1,6 @@
 // awpu_runs.cpp -- runs of consecutive blocks of a recording through one pipeline of pieces: a heatmap of every block
 // (include/awpu_hip_blocks.h), the beam audio of every block (awpu_hip_listen.h), display images of every Nth block
-// (awpu_hip_watch.h).  The handle and what is called here out of awpu_hip.cpp: awpu_handle.h.
+// (awpu_hip_watch.h).  The handle and what is called here out of awpu_hip.cpp and awpu_sweep.cpp: awpu_handle.h.
 #include "awpu_handle.h"
 #include "awpu_hip_blocks.h"
 #include "awpu_hip_listen.h"

@@ -41,7 +41,7 @@ def test_generated_blocks_are_current(pkg, tmp_path):
     assert tracked.returncode != 0 or tracked.stdout.strip() == "", "the generated include is not to be committed"
 
 
-# the shapes launch() can pick without a tuning knob (awpu_hip.cpp); stamped (diagnostic) builds and the shapes only
+# the shapes launch() can pick without a tuning knob (awpu_sweep.cpp); stamped (diagnostic) builds and the shapes only
 # tuning builds reach are not timed and may spill
 PRODUCTION = [r"das_quad_kernelILb0ELi0E", r"das_quadh_kernelILi[12]ELb0E", r"das_quadh_stationary_kernelILi[12]E", r"das_pair_kernelILi4ELb0ELb1E",
               r"das_pair_stationary_kernelILb1E", r"das_fast_db_kernelILi16ELi[48]ELi\d+ELi4ELb0E",
@@ -82,13 +82,16 @@ def test_every_sweep_launcher_checks_its_reach():
     import re
     hdr = (REPO / "beamforming-lk_amd" / "csrc" / "das_kernels.h").read_text()
     src = (REPO / "beamforming-lk_amd" / "csrc" / "das_fast.hip").read_text()
-    host = (REPO / "beamforming-lk_amd" / "csrc" / "awpu_hip.cpp").read_text()
+    host = "".join((REPO / "beamforming-lk_amd" / "csrc" / f).read_text() for f in ("awpu_hip.cpp", "awpu_sweep.cpp"))
     sweeps = ["launch_das_pairs", "launch_das_pairs_stationary", "launch_das_exact_pairs", "launch_das_exact_quads", "launch_das_fir8_planes",
-              "launch_das_quads", "launch_das_quadh", "launch_das_quadh_stationary", "launch_das_fast"]
+              "launch_das_quads", "launch_das_quadh", "launch_das_quadh_stationary", "launch_das_fast", "launch_das_exact_nd",
+              "launch_das_exact_ndh", "launch_das_exact_ndp"]
     for name in sweeps:
         decl = re.search(r"hipError_t %s\(([^;]*)\);" % name, hdr)
         assert decl and "const Extents &have" in decl.group(1), name
-        for call in re.findall(r"awpu::%s\(([^;]*)\);" % name, host):
+        calls = re.findall(r"awpu::%s\(([^;]*)\);" % name, host)
+        assert calls, name  # (the launchers live in awpu_sweep.cpp)
+        for call in calls:
             assert "{" in call or "have" in call, (name, call)  # the host passes what it allocated
     assert src.count("within({") >= len(sweeps)
     for const in ("kPairTablePrefetch", "kQuadTablePrefetch", "kFir8PlaneTablePrefetch"):
