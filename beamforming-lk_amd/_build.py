@@ -17,7 +17,7 @@ CSRC = PKG_DIR / "csrc"
 LIB_PATH = PKG_DIR / "libawpu_hip.so"
 
 SOURCES = [CSRC / "das_kernels.hip", CSRC / "das_fast.hip", CSRC / "track_kernels.hip", CSRC / "block_kernels.hip", CSRC / "watch_kernels.hip",
-           CSRC / "awpu_hip.cpp", CSRC / "awpu_sweep.cpp", CSRC / "awpu_runs.cpp", CSRC / "geometry_host.cpp"]
+           CSRC / "awpu_hip.cpp", CSRC / "awpu_group.cpp", CSRC / "awpu_sweep.cpp", CSRC / "awpu_runs.cpp", CSRC / "geometry_host.cpp"]
 # das_fast_trip.inc -- the hand-scheduled inner loops of das_fast.hip -- is GENERATED at build time by tools/gen_trip_asm.py
 # (not tracked: ~19 000 lines of asm text whose source is the generator)
 GENERATOR = REPO / "tools" / "gen_trip_asm.py"

@@ -1,6 +1,6 @@
-// awpu_handle.h -- internal to libawpu_hip.so: the handle, the error helpers, and what its three host files call in one another:
-// awpu_hip.cpp (the C ABI and its call paths), awpu_sweep.cpp (tables, launchers, dispatch) and awpu_runs.cpp (the runs of blocks).
-// Nothing here is part of the C ABI.
+// awpu_handle.h -- internal to libawpu_hip.so: the handle, the owner types of what it holds on the device, the error helpers, and
+// what its four host files call in one another: awpu_hip.cpp (the C ABI and its call paths), awpu_group.cpp (the device group),
+// awpu_sweep.cpp (tables, launchers, dispatch) and awpu_runs.cpp (the runs of blocks).  Nothing here is part of the C ABI.
 #pragma once
 
 #include "awpu_hip.h"
@@ -8,6 +8,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <string>
 #include <utility>
 #include <vector>
@@ -38,19 +39,143 @@ int hip_fail(hipError_t e, const char *what);
 int invalid(const char *why);
 int fail(int status, const char *why);
 
+// ---- owner types: whatever the handle holds on the device frees itself with the handle.  A new buffer, event or stream needs its
+// declaration and nothing else.  Non-copyable, usable wherever the raw pointer / event / stream is; only the buffers are movable.
+
+struct DeviceMem {
+    static hipError_t alloc(void **p, size_t bytes) { return hipMalloc(p, bytes); }
+    static void free(void *p) { (void) hipFree(p); }
+    static constexpr const char *what = "hipMalloc";
+};
+template <unsigned Flags>
+struct PinnedMem {
+    static hipError_t alloc(void **p, size_t bytes) { return hipHostMalloc(p, bytes, Flags); }
+    static void free(void *p) { (void) hipHostFree(p); }
+    static constexpr const char *what = "hipHostMalloc";
+};
+
+// A grow-only buffer of T: ensure(n) leaves it holding at least n elements.  Growing frees first (hipFree waits for the device:
+// launches still reading the old buffer finish first), asks for exactly n, and a failed allocation leaves it empty -- cap 0 --
+// for the next call to try again.  Contents do not survive growing.
+template <class T, class Mem>
+struct Buffer {
+    T *p = nullptr;
+    size_t cap = 0;  // elements
+    Buffer() = default;
+    Buffer(const Buffer &) = delete;
+    Buffer &operator=(const Buffer &) = delete;
+    Buffer(Buffer &&o) noexcept { *this = std::move(o); }
+    Buffer &operator=(Buffer &&o) noexcept {  // (by exchange: what this one held goes with `o`)
+        std::swap(p, o.p), std::swap(cap, o.cap);
+        return *this;
+    }
+    ~Buffer() { release(); }
+    operator T *() const { return p; }
+    T *get() const { return p; }
+    bool holds(size_t n) const { return cap >= n; }
+    int ensure(size_t n) { return cap >= n ? (int) AWPU_OK : grow(n); }
+    int grow(size_t n) {  // (ensure() decides; a caller with something to do before the old pointer goes asks holds() and comes here)
+        release();
+        const hipError_t e = Mem::alloc(reinterpret_cast<void **>(&p), n * sizeof(T));
+        if (e != hipSuccess) {
+            p = nullptr;
+            return hip_fail(e, Mem::what);
+        }
+        cap = n;
+        return AWPU_OK;
+    }
+    void release() {
+        if (p) Mem::free(p);
+        p = nullptr, cap = 0;
+    }
+};
 template <class T>
-void dev_free(T *&p) {  // hipFree + forget
-    if (p) (void) hipFree(p);
-    p = nullptr;
-}
+using DeviceBuffer = Buffer<T, DeviceMem>;
+template <class T>
+using PinnedBuffer = Buffer<T, PinnedMem<hipHostMallocDefault>>;
+template <class T>
+using PortablePinnedBuffer = Buffer<T, PinnedMem<hipHostMallocPortable>>;  // pinned for every device (a group's staging)
+
+// a stream to wait for, and the device it belongs to
+struct StreamOn {
+    int device;
+    hipStream_t stream;
+};
+
+// Two buffers for work that alternates between them, with which of them have been used since they were allocated and whose
+// turn it is.  replace(): a pair that is too small (holds()) is replaced behind a synchronize of everybody who may still read it -- the
+// caller says who -- each on its own device, and allocated on `device`; the used flags start again, the turn goes on (every
+// reuse of a buffer waits for its last reader's event whatever the turn).  A failed allocation leaves cap() 0.
+template <class Buf>
+struct DoubleBuffer {
+    Buf b[2];
+    bool used[2] = {false, false};
+    unsigned turn = 0;
+    auto operator[](int k) const { return b[k].get(); }
+    size_t cap() const { return b[1].cap; }  // (of each; b[1] is allocated last)
+    bool holds(size_t n) const { return b[1].cap >= n; }
+    int next() { return (int) (turn++ & 1); }
+    template <class Readers>
+    int replace(size_t n, int device, const Readers &readers) {
+        for (const StreamOn &r : readers) {
+            AWPU_HIP_TRY(hipSetDevice(r.device));
+            AWPU_HIP_TRY(hipStreamSynchronize(r.stream));
+        }
+        AWPU_HIP_TRY(hipSetDevice(device));
+        b[0].release(), b[1].release();
+        used[0] = used[1] = false;
+        if (const int rc = b[0].grow(n); rc != AWPU_OK) return rc;
+        return b[1].grow(n);
+    }
+};
 
 // Two buffers of `cap` bytes each for the two pieces a run has in flight (piece i uses [i & 1]): device memory, pinned host
-// memory, or both.  Grow-only; a failed allocation leaves cap 0 and whatever was allocated, which the next ensure() frees.
+// memory, or both.  Grow-only; what it held it keeps, at the new size; a failed allocation leaves cap 0.
 struct BufferPair {
-    unsigned char *d[2] = {nullptr, nullptr}, *h[2] = {nullptr, nullptr};
+    DeviceBuffer<unsigned char> d[2];
+    PinnedBuffer<unsigned char> h[2];
     size_t cap = 0;
-    int ensure(size_t bytes, bool want_host, bool want_device = true);
-    void release();
+    int ensure(size_t bytes, bool want_host, bool want_device = true) {
+        if (bytes == 0 || (cap >= bytes && (h[0] || !want_host) && (d[0] || !want_device))) return AWPU_OK;
+        want_host |= h[0] != nullptr;
+        want_device |= d[0] != nullptr;
+        bytes = std::max(bytes, cap);
+        cap = 0;
+        for (int b = 0; b < 2; b++) d[b].release(), h[b].release();
+        for (int b = 0; b < 2; b++) {
+            if (const int rc = want_device ? d[b].grow(bytes) : (int) AWPU_OK; rc != AWPU_OK) return rc;
+            if (const int rc = want_host ? h[b].grow(bytes) : (int) AWPU_OK; rc != AWPU_OK) return rc;
+        }
+        cap = bytes;
+        return AWPU_OK;
+    }
+};
+
+// An event / a stream created at first ensure() and destroyed with its owner.  No timing unless asked to; `what` names a failure.
+template <class H, hipError_t (*Destroy)(H)>
+struct Owned {
+    H it = nullptr;
+    Owned() = default;
+    Owned(const Owned &) = delete;
+    Owned &operator=(const Owned &) = delete;
+    ~Owned() {
+        if (it) (void) Destroy(it);
+    }
+    operator H() const { return it; }
+};
+struct Event : Owned<hipEvent_t, hipEventDestroy> {
+    int ensure(unsigned flags = hipEventDisableTiming, const char *what = "hipEventCreateWithFlags") {
+        if (it) return AWPU_OK;
+        const hipError_t e = hipEventCreateWithFlags(&it, flags);
+        return e == hipSuccess ? (int) AWPU_OK : hip_fail(e, what);
+    }
+};
+struct Stream : Owned<hipStream_t, hipStreamDestroy> {
+    int ensure(const char *what = "hipStreamCreateWithFlags") {
+        if (it) return AWPU_OK;
+        const hipError_t e = hipStreamCreateWithFlags(&it, hipStreamNonBlocking);
+        return e == hipSuccess ? (int) AWPU_OK : hip_fail(e, what);
+    }
 };
 
 // The quad-major tables (awpu_sweep.cpp, build_quad_lut), one per layout: what the table's LDS addresses point into
@@ -65,17 +190,61 @@ enum QuadLayout {
     kQuadLayouts
 };
 struct QuadTable {
-    awpu::QuadEntry *d = nullptr;
+    DeviceBuffer<awpu::QuadEntry> d;
     size_t entries = 0;  // allocated (the launchers check their kernel's reach against it: das_kernels.h, Extents)
     awpu::FastPlan plan{};  // set by prepare() where the window fits the layout's image
+};
+
+// ---- the device group (awpu_group.cpp): what the group's handle owns, and what each of its parts owns as a member
+
+// how a part of a group reaches devices[0]: kPeerSame (the same GPU), kPeerDirect (peer copies over xGMI) or
+// kPeerStaged (no peer access on this node: the window and the tiles cross pinned host memory, explicitly)
+enum PeerPath { kPeerSame = 0, kPeerDirect = 1, kPeerStaged = 2 };
+
+// cfg.n_devices > 1: the handle owns no sweep state of its own, only one part (an ordinary single-device engine) per device
+struct Group {
+    std::vector<awpu_hip *> parts;
+    bool union_window_done = false;  // every part stages the union of the parts' windows (packed frames need one layout)
+    Event ev_fan;                    // recorded on the caller's stream, awaited by every part
+    DoubleBuffer<DeviceBuffer<float>> packed;  // the packed frame pairs of a call on devices[0], sized for cfg.max_batch
+    // pinned staging of what the staged parts get, sized for cfg.max_batch: the packed pairs, or the union of the parts' windows
+    // of every stream (which of them, and where the window starts, is the call's: Payload in awpu_group.cpp).  ev_staged[b]: it is there
+    DoubleBuffer<PortablePinnedBuffer<float>> stage;
+    Event ev_staged[2];
+};
+
+// a part's share of the fan-out (awpu_hip_process_device on a group).  Two receive buffers, so that the copy of call k+1 (on the
+// part's copy_stream) runs beside the sweep of call k (on its stream); the events that order them are the handle's ev_copied[]
+// (shared with the host batches' pieces) and ev_swept[] here
+struct GroupMember {
+    // the part's pixels inside the group's range: (first pixel relative to the group's pixel_begin, count), ascending; the part's
+    // own table and power rows hold them back to back.  One range = a contiguous slab; several = row groups of four dealt
+    // round-robin over the devices (edge rows of the sine-space grid cost the quad shapes more than centre rows: DESIGN.md 6)
+    std::vector<std::pair<int, int>> ranges;
+    PeerPath peer = kPeerSame;
+    DoubleBuffer<DeviceBuffer<float>> recv;
+    Event ev_swept[2], ev_done;
+    // staged parts only.  stage_used[b] / ev_staged_read[b]: its upload out of the group's stage[b] was enqueued / is done;
+    // tile: pinned staging of its power tile on the way back; ev_tile_free[b]: the caller's stream has read tile[b]
+    bool stage_used[2] = {false, false};
+    Event ev_staged_read[2];
+    DoubleBuffer<PortablePinnedBuffer<float>> tile;
+    Event ev_tile_free[2];
 };
 
 }  // namespace awpu::host
 
 struct awpu_hip {
+    template <class T>
+    using Dev = awpu::host::DeviceBuffer<T>;
+    template <class T>
+    using Pinned = awpu::host::PinnedBuffer<T>;
+    using Event = awpu::host::Event;
+    using Stream = awpu::host::Stream;
+
     awpu_hip_cfg cfg{};
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_begin = nullptr, ev_end = nullptr;
+    Stream stream;
+    Event ev_begin, ev_end;  // the only two events that carry timing
     bool timing = true;
 
     // host copies of what the reference keeps in MIMOWorker / Antenna
@@ -86,20 +255,19 @@ struct awpu_hip {
     bool have_table = false, have_mics = false, prepared = false;
 
     // device state
-    awpu::LutEntry *d_lut = nullptr;
+    Dev<awpu::LutEntry> d_lut;
     struct FastLut {
         awpu::FastPlan plan;
-        awpu::FastEntry *d = nullptr;
+        Dev<awpu::FastEntry> d;
         size_t entries = 0;  // allocated (the launchers check their kernel's reach against it: das_kernels.h, Extents)
     };
     std::vector<FastLut> fast_luts;  // one per (frames per item, LDS image size) in use
-    awpu::FastEntry *d_exact_pair_lut = nullptr;  // reference-order sweep on the frame-pair layout (das_exact_pair_kernel)
+    Dev<awpu::FastEntry> d_exact_pair_lut;  // reference-order sweep on the frame-pair layout (das_exact_pair_kernel)
     size_t exact_pair_lut_entries = 0, fir_plane_lut_entries = 0;  // allocated entries of the table above and of the FIR8 plane table
     awpu::FastPlan exact_plan{};                  // ... its plan, and that of quad_tables[kQuadExact]
     awpu::host::QuadTable quad_tables[awpu::host::kQuadLayouts];  // the quad-major tables, by QuadLayout
-    unsigned *d_nd_queue = nullptr;               // das_exact_nd_kernel's eight item counters (one per XCD)
-    int2 *d_nd_items = nullptr;                   // ... and its item list (nd_items_kernel), valid for nd_items_key
-    size_t nd_items_cap = 0;
+    Dev<unsigned> d_nd_queue;                     // das_exact_nd_kernel's eight item counters (one per XCD)
+    Dev<int2> d_nd_items;                         // ... and its item list (nd_items_kernel), valid for nd_items_key
     long long nd_items_key = -1;                  // (n_pairs, pair group, quads per wave) the list was built for; -1: none
     int n_cus = 0;                                // compute units of the handle's device (persistent workgroups: one per CU)
     bool exact_nd_ok = false;     // ... and the window fits the {next, d} image (kQuadExactNd)
@@ -108,7 +276,7 @@ struct awpu_hip {
     bool identity_mics = false;   // the active-mic list is 0 .. usable-1 (awpu_hip_set_active_mics(NULL)): rows need no look-up
     bool exact_pairs_ok = false;  // AWPU_MATH_F32_EXACT + LERP and the window fits the pair image
     float *sums_out = nullptr;    // awpu_hip_process_device_sums: where the launch in progress exports out[] (else null)
-    void *d_fir_plane_lut = nullptr;           // FIR8 on the four-plane layout: one dword per (pixel, mic): address, plane, coefficient row
+    Dev<uint32_t> d_fir_plane_lut;             // FIR8 on the four-plane layout: one dword per (pixel, mic): address, plane, coefficient row
     awpu::FastPlan fir_plane_plan{};
     bool fir_planes_ok = false;                // AWPU_MATH_F32_FAST + FIR8 and the window fits the plane image
     std::vector<float> fir;                    // host copy of the [101][8] coefficient table (baked into the plane entries)
@@ -117,31 +285,26 @@ struct awpu_hip {
     bool quad_ok = false;         // the table's statistics favour the quad shape (decided in prepare)
     double quad_cost = 0.0;       // its expected packed VALU instructions per quad and mic (32 = no sharing at all)
     double quad_differ = 3.0;     // pixels of a vertical quad (of three) whose integer delay differs from the second pixel's, per mic (table sample)
-    int32_t *d_index = nullptr;
-    float *d_gain = nullptr;  // [usable] gains in active-mic order, or null
-    float *d_calib = nullptr; // [64] per-mic mean squares (calibration)
-    awpu::LutEntry *d_beam_lut = nullptr;  // [beam_cap][usable] entries of awpu_hip_beams
-    float *d_beam_out = nullptr;           // [beam_cap] powers then [beam_cap][256] beams
-    size_t beam_cap = 0, beam_lut_cap = 0;
+    Dev<int32_t> d_index;
+    Dev<float> d_gain;   // [usable] gains in active-mic order, or null
+    Dev<float> d_calib;  // [64] per-mic mean squares (calibration)
+    Dev<awpu::LutEntry> d_beam_lut;  // [directions][usable] entries of awpu_hip_beams
+    Dev<float> d_beam_out;           // [n] powers then [n][256] beams, n = d_beam_out.cap / 257: the directions it was allocated for
     // particle tracking (awpu_hip_track.h)
     std::vector<float> antenna;            // [3][antenna_n] element positions by stream id (awpu_hip_set_antenna); empty = none
-    float *d_xyz = nullptr;                // ... on the device
+    Dev<float> d_xyz;                      // ... on the device
     std::vector<int32_t> track_index;      // the active mics d_track_index holds
-    int32_t *d_track_index = nullptr;
-    size_t track_index_cap = 0;
-    unsigned char *d_track = nullptr;      // particles, then the reference used, then [n][256] beams (steer_table_device: angles, tables)
-    size_t track_cap = 0;                  // bytes
-    float *d_fir = nullptr;  // [101][8] coefficient table (AWPU_INTERP_FIR8)
-    float *d_ring = nullptr;            // [n_streams][2048] history ring (awpu_hip_ingest_block)
-    uint8_t *d_display = nullptr;       // awpu_hip_live_block: peak (one float), compact image, upscaled image
-    size_t display_cap = 0;             // bytes
-    awpu::ResizeTap *d_taps = nullptr;  // column + row taps of the display upscale, for taps_key
+    Dev<int32_t> d_track_index;
+    Dev<unsigned char> d_track;            // particles, then the reference used, then [n][256] beams (steer_table_device: angles, tables)
+    Dev<float> d_fir;                   // [101][8] coefficient table (AWPU_INTERP_FIR8)
+    Dev<float> d_ring;                  // [n_streams][2048] history ring (awpu_hip_ingest_block)
+    Dev<uint8_t> d_display;             // awpu_hip_live_block: peak (one float), compact image, upscaled image
+    Dev<awpu::ResizeTap> d_taps;        // column + row taps of the display upscale, for taps_key
     int taps_key[4] = {0, 0, 0, 0};     // {srows, scols, drows, dcols}
     int taps_band_rows = 0;             // ... and the most compact rows a 16-row tile of the large image reads (watch_kernels.h)
-    float *d_pack = nullptr;            // [pairs][usable][wp][2] sample-interleaved frame pairs
-    size_t pack_cap = 0;                // floats
-    unsigned char *d_datagrams = nullptr;  // staging for one block of wire datagrams
-    int32_t *d_row_off_ring = nullptr;  // row offsets for frames read out of the ring (pitch 2048)
+    Dev<float> d_pack;                  // [pairs][usable][wp][2] sample-interleaved frame pairs
+    Dev<unsigned char> d_datagrams;     // staging for one block of wire datagrams
+    Dev<int32_t> d_row_off_ring;        // row offsets for frames read out of the ring (pitch 2048)
     int ring_pos = 0;                   // where the next block goes = start of the snapshot
     // awpu_hip_live_block as a HIP graph: the call's copies and launches captured once per (ring position, caller
     // buffers, table generation) and replayed with one hipGraphLaunch
@@ -160,73 +323,49 @@ struct awpu_hip {
     unsigned long long live_clock = 0;
     bool live_graph_broken = false;     // a capture failed on this runtime: never try again
     bool have_fir = false;
-    int32_t *d_row_off = nullptr;
-    int32_t *d_row_off_compact = nullptr;  // the same for frames uploaded as [streams][compact_hist] windows
+    Dev<int32_t> d_row_off;
+    Dev<int32_t> d_row_off_compact;        // the same for frames uploaded as [streams][compact_hist] windows
     int compact_hist = 0;                  // 0 = the window cannot be cut out (it touches the newest sample)
-    float *d_frames = nullptr;
-    float *h_live_in = nullptr, *h_live_out = nullptr;  // pinned staging of awpu_hip_process's one-frame calls (the live path): window in, powers out
-    size_t live_in_cap = 0, live_out_cap = 0;           // in floats
+    Dev<float> d_frames;
+    Pinned<float> h_live_in, h_live_out;                // pinned staging of awpu_hip_process's one-frame calls (the live path): window in, powers out
     unsigned live_calls = 0;                            // ... how many of them this handle has served (every 32nd is timed by events)
     // ... their completion flag (the resident single-frame kernels with one quad per wave): the device counter the workgroups count themselves on, what it will read
     // when every launch armed so far is over, the pinned flag and the sequence number of the last armed launch
-    unsigned long long *d_done_counter = nullptr, done_total = 0;
-    unsigned *h_done_flag = nullptr, done_seq = 0;
+    Dev<unsigned long long> d_done_counter;
+    unsigned long long done_total = 0;
+    Pinned<unsigned> h_done_flag;
+    unsigned done_seq = 0;
     bool done_arm = false, done_used = false;           // arm: the next single-frame sweep is to raise the flag; used: it will
-    float *d_power = nullptr;
-    size_t frames_cap = 0, power_cap = 0;  // in floats
+    Dev<float> d_power;
     int wstart = 0, window = 0, tau_max = 0;
     int pair_cols = 0;  // frame-pair sweep: > 0 = waves take vertically adjacent pixels (grid row length), 0 = consecutive
 
-    // device group (cfg.n_devices > 1): this handle owns no sweep state of its own, only one part per device
-    std::vector<awpu_hip *> parts;
-    // a part's pixels inside the group's range: (first pixel relative to the group's pixel_begin, count), ascending; the part's
-    // own table and power rows hold them back to back.  One range = a contiguous slab; several = row groups of four dealt
-    // round-robin over the devices (edge rows of the sine-space grid cost the quad shapes more than centre rows: DESIGN.md 6)
-    std::vector<std::pair<int, int>> ranges;
-    bool union_window_done = false;  // group: every part stages the union of the parts' windows (packed frames need one layout)
-    hipEvent_t ev_fan = nullptr;            // group: recorded on the caller's stream, awaited by every part
-    // a part's share of the fan-out (awpu_hip_process_device on a group): two window buffers, so that the copy of
-    // call k+1 (on copy_stream) runs beside the sweep of call k (on stream)
-    hipStream_t copy_stream = nullptr;
-    float *d_fan[2] = {nullptr, nullptr};
-    size_t fan_cap = 0;                     // floats per buffer
-    hipEvent_t ev_copied[2] = {nullptr, nullptr}, ev_swept[2] = {nullptr, nullptr}, ev_done = nullptr;
-    unsigned fan_turn = 0;
-    // how a part of a group reaches devices[0]: kPeerSame (the same GPU), kPeerDirect (peer copies over xGMI) or
-    // kPeerStaged (no peer access on this node: the window and the tiles cross pinned host memory, explicitly)
-    int peer = 0;
-    float *h_stage[2] = {nullptr, nullptr};  // group: pinned staging of the frames' window for the staged parts
-    size_t stage_cap = 0;                    // floats per buffer
-    int stage_lo = 0, stage_w = 0;           // group: the window [stage_lo, stage_lo + stage_w) of every stream that is staged
-    hipEvent_t ev_staged[2] = {nullptr, nullptr};   // group: window b is in h_stage[b]
-    unsigned stage_turn = 0;
-    float *h_tile[2] = {nullptr, nullptr};   // part (staged): pinned staging of its power tile on the way back
-    size_t tile_cap = 0;
-    hipEvent_t ev_tile_free[2] = {nullptr, nullptr};  // part (staged): the caller's stream has read h_tile[b]
-    hipEvent_t ev_staged_read[2] = {nullptr, nullptr};  // part (staged): its upload out of the group's h_stage[b] is done
-    bool stage_used[2] = {false, false};
-    bool tile_used[2] = {false, false}, fan_used[2] = {false, false};
+    // device group (awpu_group.cpp): `group` is empty unless cfg.n_devices > 1, `member` unless the handle is a part of one
+    awpu::host::Group group;
+    awpu::host::GroupMember member;
+    // a second stream for uploads that run beside the sweeps, and "upload b is over": shared by the pieces of a host batch
+    // (enqueue_host_process), the runs of blocks (awpu_runs.cpp) and a part's receive buffers, which is why they live here
+    // and not in `member`.  Created at first use; a part's at its creation
+    Stream copy_stream;
+    Event ev_copied[2];
     bool in_flight = false;                 // awpu_hip_process_async without its awpu_hip_wait yet
     // runs of blocks (awpu_runs.cpp), by piece: piece i's history [n_streams][768 + 256 * piece] in blk_hist.d[i & 1], its windows
     // in d_blk_frames; the host forms stage piece i's input in pinned blk_in.h[i & 1], upload it to blk_in.d[i & 1] on copy_stream
     // and bring its powers back through pinned blk_out.h[i & 1]
     awpu::host::BufferPair blk_hist, blk_in, blk_out;
-    float *d_blk_frames = nullptr;
-    size_t blk_frames_cap = 0;  // floats
+    Dev<float> d_blk_frames;
     // ev_blk_in[b]: blk_in.h[b] may be refilled; ev_blk_hist[b]: blk_hist.d[b] formed; ev_blk_cut[b]: ... and read by the cut;
     // ev_blk_swept[b]: d_power's half b holds its piece's powers; ev_blk_out[b]: ... and blk_out.h[b] too; ev_blk_ring: orders a
     // run after the work queued on the handle's stream, and the handle's stream after a device-form run on the caller's stream
-    hipEvent_t ev_blk_in[2] = {nullptr, nullptr}, ev_blk_hist[2] = {nullptr, nullptr}, ev_blk_cut[2] = {nullptr, nullptr},
-               ev_blk_swept[2] = {nullptr, nullptr}, ev_blk_out[2] = {nullptr, nullptr}, ev_blk_ring = nullptr;
+    Event ev_blk_in[2], ev_blk_hist[2], ev_blk_cut[2], ev_blk_swept[2], ev_blk_out[2], ev_blk_ring;
     // listening to such runs (awpu_hip_listen.h): the listeners on the device from piece to piece; the host forms get piece i's
     // audio rows [n][256 * piece], then its trail, in listen_out.d[i & 1] and bring them back through pinned listen_out.h[i & 1].
     // listen_stream: where the listen kernels run beside the sweeps when heatmaps are asked for too.
-    unsigned char *d_listeners = nullptr;
-    size_t listeners_cap = 0;  // bytes
+    Dev<unsigned char> d_listeners;
     awpu::host::BufferPair listen_out;
-    hipStream_t listen_stream = nullptr;
+    Stream listen_stream;
     // ev_listened[b]: the listen kernels have read blk_hist.d[b] (and written listen_out.d[b]); ev_listen_out[b]: listen_out.h[b] holds it
-    hipEvent_t ev_listened[2] = {nullptr, nullptr}, ev_listen_out[2] = {nullptr, nullptr};
+    Event ev_listened[2], ev_listen_out[2];
 
     // watching such runs (awpu_hip_watch.h): piece i's peaks, compact images and (host forms) large images in watch.d[i & 1]; the
     // host forms bring the images back through pinned watch.h[i & 1].  The events are those of the runs above: ev_blk_swept[b] is
@@ -235,8 +374,7 @@ struct awpu_hip {
 
     awpu_hip_stats stats{};
     std::string last_error;                  // awpu_hip_last_error_of
-    unsigned long long *d_diag = nullptr;    // AWPU_FAST_DEBUG=16 cycle stamps of the last launch
-    size_t diag_cap = 0;                     // in 64-bit words
+    Dev<unsigned long long> d_diag;          // AWPU_FAST_DEBUG=16 cycle stamps of the last launch
 
     int usable() const { return static_cast<int>(index.size()); }
 };
@@ -292,6 +430,9 @@ int sweep_packed(awpu_hip *h, const awpu::FastPlan &plan, const float *d_packed,
 
 // defined, and described, in awpu_hip.cpp
 void retire_live_graphs(awpu_hip *h);
+int enqueue_host_process(awpu_hip *h, const float *frames, int batch);
+int enqueue_power_to_host(awpu_hip *h, int batch, float *power, size_t pitch);
+int enqueue_ingest(awpu_hip *h, const void *datagrams, int32_t stride_bytes);
 int check_ready(awpu_hip *h, int batch);
 int ensure_power(awpu_hip *h, size_t need_power);
 int ensure_ring(awpu_hip *h);
@@ -303,4 +444,40 @@ int check_antenna(const awpu_hip *h);
 int ensure_track_index(awpu_hip *h);
 int ensure_taps(awpu_hip *h, int rows, int cols, int out_rows, int out_cols, hipStream_t s);
 
+
+// A buffer whose pointer the captured live-block graphs bake in (d_power, d_pack, d_display): they are retired before the old pointer
+// goes.  (prepare() and ensure_taps() retire for the tables and d_taps; launch_exact_nd for d_nd_items, a synchronize before it grows.)
+template <class B>
+int ensure_seen_by_live_graphs(awpu_hip *h, B &buf, size_t n) {
+    if (buf.holds(n)) return AWPU_OK;
+    retire_live_graphs(h);
+    return buf.grow(n);
+}
+
+// switches a handle's event bracket off for one asynchronous call and back on whichever way the call ends
+struct TimingOff {
+    awpu_hip *h;
+    bool keep;
+    explicit TimingOff(awpu_hip *h_) : h(h_), keep(h_->timing) { h->timing = false; }
+    ~TimingOff() { h->timing = keep; }
+};
+
+// the device group: defined, and described, in awpu_group.cpp.  The ABI functions hand a group's handle over to these
+inline bool is_group(const awpu_hip *h) { return !h->group.parts.empty(); }
+// calls that are not pixel-sharded: a device group answers with its first device
+inline awpu_hip *first_device(awpu_hip *h) { return h && is_group(h) ? h->group.parts[0] : h; }
+int create_group(awpu_hip_t **out, const awpu_hip_cfg &c);
+int group_set_delay_table(awpu_hip *g, const int32_t *off, const float *frac);
+int group_set_active_mics(awpu_hip *g, const int32_t *index, int32_t usable);
+int group_set_mic_gains(awpu_hip *g, const float *gains);
+int group_set_fir_table(awpu_hip *g, const float *coeffs);
+int group_process(awpu_hip *g, const float *frames, int batch, float *power);
+int group_process_async(awpu_hip *g, const float *frames, int batch, float *power);
+int group_wait(awpu_hip *g);
+int group_process_device(awpu_hip *g, const float *d_frames, int batch, float *d_power, hipStream_t stream);
+int group_ingest_block(awpu_hip *g, const void *datagrams, int32_t stride_bytes);
+int group_process_ring(awpu_hip *g, float *power);
+int group_synchronize(awpu_hip *g);
+int group_peer_status(awpu_hip *g, int32_t *status, int32_t n);
+int group_stats(awpu_hip *g, awpu_hip_stats *out);
 }  // namespace awpu::host

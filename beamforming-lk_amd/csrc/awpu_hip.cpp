@@ -1,7 +1,7 @@
 // awpu_hip.cpp -- the C ABI of libawpu_hip.so (include/awpu_hip.h) and its call paths: handle lifetime, setters, frame upload,
-// the single-call paths, the ring, display, tracking, device groups and the packed-frame entry points.  The tables, the kernel
-// launchers and the dispatch rule are the sweep layer (awpu_sweep.cpp); the runs of blocks are awpu_runs.cpp.  No CPU fallback:
-// every compute entry point ends in a gfx950 kernel launch or an error status.
+// the single-call paths, the ring, display, tracking and the packed-frame entry points.  The tables, the kernel launchers and
+// the dispatch rule are the sweep layer (awpu_sweep.cpp); the runs of blocks are awpu_runs.cpp; a device group's handle is
+// handed over to awpu_group.cpp.  No CPU fallback: every compute entry point ends in a gfx950 kernel launch or an error status.
 #include "awpu_handle.h"
 
 #include <algorithm>
@@ -106,78 +106,13 @@ const EnvKnobs &awpu::host::env() {
 }
 
 // The captured live-block graphs hold raw device pointers (d_power, d_display, d_taps, d_ring, tables, d_pack):
-// whoever frees or reallocates one of those retires the graphs first.  The next live calls run step by step and
-// capture again once the buffers have settled.
+// whoever frees or reallocates one of those retires the graphs first (the buffers that grow: ensure_seen_by_live_graphs,
+// awpu_handle.h).  The next live calls run step by step and capture again once the buffers have settled.
 void awpu::host::retire_live_graphs(awpu_hip *h) {
     for (auto &g : h->live_graphs) (void) hipGraphExecDestroy(g.exec);
     h->live_graphs.clear();
     h->live_warm = 0;
 }
-
-namespace {
-
-void release_device(awpu_hip *h) {
-    retire_live_graphs(h);
-    free_tables(h);
-    dev_free(h->d_nd_items);
-    h->nd_items_cap = 0;
-    h->nd_items_key = -1;
-    dev_free(h->d_nd_queue);
-    dev_free(h->d_done_counter);
-    if (h->h_done_flag) (void) hipHostFree(h->h_done_flag);
-    h->h_done_flag = nullptr;
-    h->done_total = 0;
-    dev_free(h->d_index);
-    dev_free(h->d_gain);
-    dev_free(h->d_calib);
-    dev_free(h->d_beam_lut);
-    dev_free(h->d_beam_out);
-    dev_free(h->d_xyz);
-    dev_free(h->d_track_index);
-    h->track_index_cap = 0;
-    h->track_index.clear();
-    dev_free(h->d_track);
-    h->track_cap = 0;
-    dev_free(h->d_fir);
-    dev_free(h->d_ring);
-    dev_free(h->d_pack);
-    dev_free(h->d_taps);
-    dev_free(h->d_display);
-    h->display_cap = 0;
-    dev_free(h->d_datagrams);
-    dev_free(h->d_row_off_ring);
-    dev_free(h->d_row_off);
-    dev_free(h->d_row_off_compact);
-    dev_free(h->d_frames);
-    dev_free(h->d_power);
-    dev_free(h->d_diag);
-    h->diag_cap = 0;
-    dev_free(h->d_fan[0]);
-    dev_free(h->d_fan[1]);
-    h->fan_cap = 0;
-    for (BufferPair *pair : {&h->blk_hist, &h->blk_in, &h->blk_out, &h->listen_out, &h->watch}) pair->release();
-    dev_free(h->d_blk_frames);
-    h->blk_frames_cap = 0;
-    dev_free(h->d_listeners);
-    h->listeners_cap = 0;
-    for (int b = 0; b < 2; b++) {
-        if (b == 0) {
-            if (h->h_live_in) (void) hipHostFree(h->h_live_in);
-            if (h->h_live_out) (void) hipHostFree(h->h_live_out);
-            h->h_live_in = h->h_live_out = nullptr;
-            h->live_in_cap = h->live_out_cap = 0;
-        }
-        if (h->h_stage[b]) (void) hipHostFree(h->h_stage[b]);
-        if (h->h_tile[b]) (void) hipHostFree(h->h_tile[b]);
-        h->h_stage[b] = h->h_tile[b] = nullptr;
-    }
-    h->stage_cap = h->tile_cap = 0;
-    h->beam_cap = h->beam_lut_cap = h->pack_cap = h->frames_cap = h->power_cap = 0;
-}
-
-enum PeerPath { kPeerSame = 0, kPeerDirect = 1, kPeerStaged = 2 };
-
-}  // namespace
 
 namespace awpu::host {
 
@@ -198,161 +133,14 @@ int check_ready(awpu_hip *h, int batch) {
     return AWPU_OK;
 }
 
-int ensure_power(awpu_hip *h, size_t need_power) {
-    if (h->power_cap < need_power) {
-        retire_live_graphs(h);  // (they write through the old pointer)
-        dev_free(h->d_power);
-        h->power_cap = 0;
-        AWPU_HIP_TRY(hipMalloc(&h->d_power, need_power * sizeof(float)));
-        h->power_cap = need_power;
-    }
-    return AWPU_OK;
-}
-
-}  // namespace awpu::host
-
-namespace {
-
-// ------------------------------------------------------------------------------------------------
-// Device group (cfg.n_devices > 1): one handle, one part (an ordinary single-device engine) per GPU,
-// each owning a contiguous slab of the handle's pixels.  Everything below runs in the caller's thread; the parts'
-// streams run concurrently.  No collective library: host frames are uploaded by every device itself, device
-// frames fan out from devices[0] by one peer copy per destination (a different xGMI link each).
-// ------------------------------------------------------------------------------------------------
-int create_group(awpu_hip_t **out, const awpu_hip_cfg &c) {
-    if (c.n_devices > AWPU_MAX_DEVICES) return invalid("n_devices above AWPU_MAX_DEVICES");
-    const int G = c.n_devices;
-    // slabs: whole grid rows when the row length is known and the handle's range is whole rows, else pixels
-    const bool by_rows = c.grid_columns > 0 && c.pixel_count % c.grid_columns == 0 && c.pixel_begin % c.grid_columns == 0;
-    int unit = by_rows ? c.grid_columns : 1;
-    // groups of four rows where that divides (the quad shapes sweep four rows at a time: slabs that start on a
-    // multiple of four rows sweep the same quads as one device would, and give the same bits)
-    if (by_rows && c.pixel_count % (4 * unit) == 0 && c.pixel_count / (4 * unit) >= G) unit *= 4;
-    const int units = c.pixel_count / unit;
-    if (units < G) return invalid("fewer grid rows (or pixels) than devices");
-    awpu_hip *g = new (std::nothrow) awpu_hip();
-    if (!g) return AWPU_ERR_NOMEM;
-    g->cfg = c;
-    g->cfg.device = c.devices[0];
-    // Row groups of four dealt round-robin (device k owns groups k, k + G, ...) where every device gets at least two of them:
-    // the sweep's cost per row grows from the centre of the sine-space grid outwards (fewer shared integer delays), and a
-    // group's call takes as long as its slowest device; contiguous slabs otherwise.  Either way a quad is four adjacent grid rows.
-    const bool interleave = by_rows && unit == 4 * c.grid_columns && units >= 2 * G;
-    int begin = 0;
-    for (int k = 0; k < G; k++) {
-        awpu_hip_cfg pc = c;
-        pc.n_devices = 1;
-        pc.device = c.devices[k];
-        const int n = units / G + (k < units % G ? 1 : 0);  // the first units % G devices take one more
-        std::vector<std::pair<int, int>> ranges;
-        if (interleave) {
-            for (int u = k; u < units; u += G) ranges.emplace_back(u * unit, unit);
-        } else {
-            ranges.emplace_back(begin * unit, n * unit);
-        }
-        pc.pixel_begin = c.pixel_begin + (interleave ? 0 : begin * unit);  // (a part's pixels are what `ranges` says; this only has to be a row start)
-        pc.pixel_count = n * unit;
-        begin += n;
-        awpu_hip *part = nullptr;
-        int rc = awpu_hip_create(&part, &pc);
-        if (rc == AWPU_OK) part->ranges = ranges;
-        if (rc == AWPU_OK) {  // what the fan-out needs on top of an ordinary engine
-            hipError_t e = hipStreamCreateWithFlags(&part->copy_stream, hipStreamNonBlocking);
-            for (int b = 0; b < 2 && e == hipSuccess; b++) {
-                e = hipEventCreateWithFlags(&part->ev_copied[b], hipEventDisableTiming);
-                if (e == hipSuccess) e = hipEventCreateWithFlags(&part->ev_swept[b], hipEventDisableTiming);
-                if (e == hipSuccess) e = hipEventCreateWithFlags(&part->ev_staged_read[b], hipEventDisableTiming);
-            }
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&part->ev_done, hipEventDisableTiming);
-            if (e != hipSuccess) rc = hip_fail(e, "group stream/event creation");
-            g->parts.push_back(part);
-        }
-        if (rc != AWPU_OK) {
-            const std::string why = g_last_error;
-            awpu_hip_destroy(g);
-            note_error(why);
-            return rc;
-        }
-    }
-    // Direct copies between devices[0] and the others need peer access both ways.  Asked for and CHECKED: a pair
-    // without it (another PCIe root, IOMMU settings, a container that hides the links) takes the explicit staged path
-    // through pinned host memory -- slower, correct, and said so in awpu_hip_last_error_of / awpu_hip_group_peer_status.
-    std::string staged_note;
-    for (int k = 0; k < G; k++) {
-        awpu_hip *part = g->parts[k];
-        if (c.devices[k] == c.devices[0]) {
-            part->peer = env().group_copy >= 2 ? kPeerStaged : kPeerSame;
-            continue;
-        }
-        int can_out = 0, can_in = 0;
-        hipError_t e_out = hipDeviceCanAccessPeer(&can_out, c.devices[0], c.devices[k]);
-        hipError_t e_in = hipDeviceCanAccessPeer(&can_in, c.devices[k], c.devices[0]);
-        if (e_out == hipSuccess && e_in == hipSuccess && can_out && can_in) {
-            e_out = hipSetDevice(c.devices[0]);
-            if (e_out == hipSuccess) e_out = hipDeviceEnablePeerAccess(c.devices[k], 0);
-            e_in = hipSetDevice(c.devices[k]);
-            if (e_in == hipSuccess) e_in = hipDeviceEnablePeerAccess(c.devices[0], 0);
-        }
-        const auto enabled = [](hipError_t e) { return e == hipSuccess || e == hipErrorPeerAccessAlreadyEnabled; };
-        part->peer = can_out && can_in && enabled(e_out) && enabled(e_in) && env().group_copy < 2 ? kPeerDirect : kPeerStaged;
-        if (part->peer == kPeerStaged) {
-            staged_note += "device " + std::to_string(c.devices[0]) + " <-> " + std::to_string(c.devices[k]) + ": " +
-                           (!(can_out && can_in) ? std::string("hipDeviceCanAccessPeer says no")
-                                                 : std::string("hipDeviceEnablePeerAccess: ") + hipGetErrorString(enabled(e_out) ? e_in : e_out)) + "; ";
-        }
-    }
-    (void) hipGetLastError();
-    if (!staged_note.empty())
-        g->last_error = "device group without peer access (" + staged_note + "): frames and tiles are staged through pinned host memory";
-    AWPU_HIP_TRY(hipSetDevice(c.devices[0]));
-    hipError_t e = hipEventCreateWithFlags(&g->ev_fan, hipEventDisableTiming);
-    for (int b = 0; b < 2 && e == hipSuccess; b++) e = hipEventCreateWithFlags(&g->ev_staged[b], hipEventDisableTiming);
-    // a staged part's ev_tile_free[] is recorded on the CALLER's stream (devices[0]) and only waited for on the part's own:
-    // an event must be recorded on a stream of the device it was created on, so these belong to devices[0], not the part's
-    for (awpu_hip *part : g->parts)
-        for (int b = 0; b < 2 && e == hipSuccess; b++) e = hipEventCreateWithFlags(&part->ev_tile_free[b], hipEventDisableTiming);
-    if (e != hipSuccess) {
-        awpu_hip_destroy(g);
-        return hip_fail(e, "group event creation");
-    }
-    *out = g;
-    return AWPU_OK;
-}
-
-// a part ran into an error: the group reports it as its own
-int part_failed(awpu_hip *g, awpu_hip *part, int rc) {
-    g->last_error = part->last_error.empty() ? g_last_error : part->last_error;
-    g_last_error = g->last_error;
-    return rc;
-}
-
-template <class F>
-int for_each_part(awpu_hip *g, F f) {
-    for (awpu_hip *part : g->parts) {
-        const int rc = f(part);
-        if (rc != AWPU_OK) return part_failed(g, part, rc);
-    }
-    return AWPU_OK;
-}
-
-// switches a handle's event bracket off for one asynchronous call and back on whichever way the call ends
-struct TimingOff {
-    awpu_hip *h;
-    bool keep;
-    explicit TimingOff(awpu_hip *h_) : h(h_), keep(h_->timing) { h->timing = false; }
-    ~TimingOff() { h->timing = keep; }
-};
-
-}  // namespace
+int ensure_power(awpu_hip *h, size_t need_power) { return ensure_seen_by_live_graphs(h, h->d_power, need_power); }
 
 // frames per sweep launch of a host batch: large batches go up in pieces of whole frame pairs, so that piece k+1 crosses PCIe
 // while piece k is swept (enqueue_host_process; a run of blocks sweeps its chunks the same way)
-int awpu::host::host_piece(int batch) {
+int host_piece(int batch) {
     const int n_pieces = batch >= 128 ? 4 : (batch >= 64 ? 2 : 1);
     return ((batch + n_pieces - 1) / n_pieces + 1) & ~1;
 }
-
-namespace {
 
 // upload of host frames + the sweep into h->d_power, all on h->stream, nothing waited for
 int enqueue_host_process(awpu_hip *h, const float *frames, int batch) {
@@ -361,22 +149,18 @@ int enqueue_host_process(awpu_hip *h, const float *frames, int batch) {
     const bool compact = h->compact_hist > 0;
     const int dev_hist = compact ? h->compact_hist : h->cfg.hist;
     const size_t need_frames = (size_t) h->cfg.n_streams * dev_hist * batch;
-    if (h->frames_cap < need_frames) {
-        dev_free(h->d_frames);
-        h->frames_cap = 0;
-        AWPU_HIP_TRY(hipMalloc(&h->d_frames, need_frames * sizeof(float)));
-        h->frames_cap = need_frames;
-    }
-    rc = ensure_power(h, (size_t) h->cfg.pixel_count * batch);
+    rc = h->d_frames.ensure(need_frames);
+    if (rc == AWPU_OK) rc = ensure_power(h, (size_t) h->cfg.pixel_count * batch);
     if (rc != AWPU_OK) return rc;
     // Large batches go up in pieces on a second stream, so that piece k+1 crosses PCIe while piece k is swept (the
     // pieces are whole frame pairs: the same arithmetic as one launch).  last_kernel_ms then spans all the sweeps.
     const int piece = host_piece(batch);
     const int n_pieces = (batch + piece - 1) / piece;
     if (n_pieces > 1) {
-        if (!h->copy_stream) AWPU_HIP_TRY(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-        for (hipEvent_t *ev : {&h->ev_copied[0], &h->ev_copied[1]})
-            if (!*ev) AWPU_HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+        rc = h->copy_stream.ensure();
+        for (awpu_hip::Event &ev : h->ev_copied)
+            if (rc == AWPU_OK) rc = ev.ensure();
+        if (rc != AWPU_OK) return rc;
     }
     const bool keep_timing = h->timing;
     int turn = 0;
@@ -409,7 +193,7 @@ int enqueue_host_process(awpu_hip *h, const float *frames, int batch) {
 // part's pixel ranges then land where they belong in the wider image), on h->stream
 int enqueue_power_to_host(awpu_hip *h, int batch, float *power, size_t pitch) {
     const size_t row = (size_t) h->cfg.pixel_count * sizeof(float);
-    if (h->ranges.empty()) {
+    if (h->member.ranges.empty()) {
         if (pitch == (size_t) h->cfg.pixel_count) {
             AWPU_HIP_TRY(hipMemcpyAsync(power, h->d_power, row * batch, hipMemcpyDeviceToHost, h->stream));
         } else {
@@ -418,13 +202,17 @@ int enqueue_power_to_host(awpu_hip *h, int batch, float *power, size_t pitch) {
         return AWPU_OK;
     }
     size_t done = 0;  // pixels of the part's own rows already sent
-    for (const auto &r : h->ranges) {
+    for (const auto &r : h->member.ranges) {
         AWPU_HIP_TRY(hipMemcpy2DAsync(power + r.first, pitch * sizeof(float), h->d_power + done, row, (size_t) r.second * sizeof(float),
                                       (size_t) batch, hipMemcpyDeviceToHost, h->stream));
         done += (size_t) r.second;
     }
     return AWPU_OK;
 }
+
+}  // namespace awpu::host
+
+namespace {
 
 // One frame in, one heatmap out, synchronously: the call MIMOWorker::update makes once per 256-sample block (mimo.cpp:100-103 is the
 // snapshot it replaces).  The caller's buffers are pageable (std::vector, mimo.h:83-88): a device copy straight out of / into them goes
@@ -445,28 +233,11 @@ int live_host_call(awpu_hip *h, const float *frames, float *power) {
     const bool compact = h->compact_hist > 0;
     const int dev_hist = compact ? h->compact_hist : h->cfg.hist;
     const size_t need_frames = (size_t) h->cfg.n_streams * dev_hist;
-    if (h->frames_cap < need_frames) {
-        dev_free(h->d_frames);
-        h->frames_cap = 0;
-        AWPU_HIP_TRY(hipMalloc(&h->d_frames, need_frames * sizeof(float)));
-        h->frames_cap = need_frames;
-    }
-    rc = ensure_power(h, (size_t) h->cfg.pixel_count);
+    rc = h->d_frames.ensure(need_frames);
+    if (rc == AWPU_OK) rc = ensure_power(h, (size_t) h->cfg.pixel_count);
+    if (rc == AWPU_OK) rc = h->h_live_in.ensure(need_frames);
+    if (rc == AWPU_OK) rc = h->h_live_out.ensure((size_t) h->cfg.pixel_count);
     if (rc != AWPU_OK) return rc;
-    if (h->live_in_cap < need_frames) {
-        if (h->h_live_in) (void) hipHostFree(h->h_live_in);
-        h->h_live_in = nullptr;
-        h->live_in_cap = 0;
-        AWPU_HIP_TRY(hipHostMalloc(&h->h_live_in, need_frames * sizeof(float), hipHostMallocDefault));
-        h->live_in_cap = need_frames;
-    }
-    if (h->live_out_cap < (size_t) h->cfg.pixel_count) {
-        if (h->h_live_out) (void) hipHostFree(h->h_live_out);
-        h->h_live_out = nullptr;
-        h->live_out_cap = 0;
-        AWPU_HIP_TRY(hipHostMalloc(&h->h_live_out, (size_t) h->cfg.pixel_count * sizeof(float), hipHostMallocDefault));
-        h->live_out_cap = (size_t) h->cfg.pixel_count;
-    }
 #ifdef AWPU_TUNING_BUILD
     static const bool live_timing = std::getenv("AWPU_LIVE_TIMING") != nullptr;
     static double t_acc[5] = {0, 0, 0, 0, 0};
@@ -521,7 +292,7 @@ int live_host_call(awpu_hip *h, const float *frames, float *power) {
                 // the stream's own completion decides
                 const auto spin_from = std::chrono::steady_clock::now();
                 for (unsigned spins = 0;; spins++) {
-                    if (__atomic_load_n(h->h_done_flag, __ATOMIC_ACQUIRE) == h->done_seq) {
+                    if (__atomic_load_n(h->h_done_flag.get(), __ATOMIC_ACQUIRE) == h->done_seq) {
                         seen = true;
                         break;
                     }
@@ -567,300 +338,6 @@ int awpu::host::wait_and_time(awpu_hip *h) {
     return AWPU_OK;
 }
 
-namespace {
-
-int group_process(awpu_hip *g, const float *frames, int batch, float *power) {
-    const size_t pitch = (size_t) g->cfg.pixel_count;
-    int rc = for_each_part(g, [&](awpu_hip *part) {
-        AWPU_CTX(part);
-        const int r = enqueue_host_process(part, frames, batch);
-        return r != AWPU_OK ? r : enqueue_power_to_host(part, batch, power, pitch);
-    });
-    if (rc != AWPU_OK) return rc;
-    return for_each_part(g, [&](awpu_hip *part) { return wait_and_time(part); });
-}
-
-// Every part of a group stages the same window -- the union of what the parts' own rows touch -- so that ONE packed buffer
-// serves them all (the layout's row length and first sample follow the window).  Results do not depend on the window.
-int group_union_window(awpu_hip *g, int batch) {
-    if (g->union_window_done) return AWPU_OK;
-    int lo = g->cfg.hist, hi = 0;
-    for (awpu_hip *part : g->parts) {
-        lo = std::min(lo, part->wstart);
-        hi = std::max(hi, part->wstart + part->window);
-    }
-    for (awpu_hip *part : g->parts) {
-        if (part->wstart == lo && part->wstart + part->window == hi) continue;
-        AWPU_CTX(part);
-        part->cfg.window_begin = lo;
-        part->cfg.window_end = hi;
-        part->prepared = false;
-        const int rc = check_ready(part, batch);
-        if (rc != AWPU_OK) return part_failed(g, part, rc);
-    }
-    g->union_window_done = true;
-    return AWPU_OK;
-}
-
-// a part's tile [batch][its pixels, back to back] -> the group's image [batch][pitch floats]: one 2-D copy per pixel range
-int tile_to_image(awpu_hip *part, const float *tile, float *image, size_t pitch_floats, int batch, hipMemcpyKind kind, hipStream_t s) {
-    const size_t row = (size_t) part->cfg.pixel_count * sizeof(float);
-    size_t done = 0;
-    for (const auto &r : part->ranges) {
-        AWPU_HIP_TRY(hipMemcpy2DAsync(image + r.first, pitch_floats * sizeof(float), tile + done, row, (size_t) r.second * sizeof(float),
-                                      (size_t) batch, kind, s));
-        done += (size_t) r.second;
-    }
-    return AWPU_OK;
-}
-
-// Frames and power in the memory of devices[0], on the caller's stream there.  What travels to the other devices:
-//   * batches that the parts sweep with a frame-pair shape (takes_packed_pairs): devices[0] runs the sweep's pack pass ONCE
-//     (two frames interleaved, filtered: the packed frame pairs of awpu_hip_pack_frames, the exchange format of the
-//     one-process-per-GPU path too) and every other device gets that buffer by ONE linear peer copy on its copy stream and
-//     sweeps it as it arrives -- no window cut on devices[0], no pack pass anywhere else;
-//   * everything else (single frames, FIR8, exact math, gains): the window of every stream that the tables touch, by one 2-D
-//     peer copy per device, and every device runs its whole sweep.
-// The parts' pixel ranges are swept concurrently; the tiles return by peer copies on the caller's stream, which thereby waits
-// for all of it.  Parts without peer access to devices[0] (kPeerStaged) get the same bytes through pinned host memory: ONE
-// copy down on the caller's stream for all of them, one copy up per part on its copy stream; their tiles return the same
-// way.  Two buffers everywhere, so that call k+1's copies run beside call k's sweeps.
-int group_process_device(awpu_hip *g, const float *d_frames, int batch, float *d_power, hipStream_t stream) {
-    const int dev0 = g->cfg.devices[0];
-    AWPU_HIP_TRY(hipSetDevice(dev0));
-    hipStream_t s = stream ? stream : g->parts[0]->stream;
-    int rc = for_each_part(g, [&](awpu_hip *part) {
-        AWPU_CTX(part);
-        return check_ready(part, batch);  // (tables packed: every part's window is known)
-    });
-    if (rc != AWPU_OK) return rc;
-    rc = group_union_window(g, batch);
-    if (rc != AWPU_OK) return rc;
-    g->stats.group_exchange = AWPU_EXCHANGE_WINDOWS;
-    auto in_place = [&](const awpu_hip *part) { return part->cfg.device == dev0 && !env().group_copy; };
-
-    // ---- packed frame pairs, where every part sweeps them
-    awpu::FastPlan pplan{};
-    bool packed = true;
-    for (awpu_hip *part : g->parts) {
-        awpu::FastPlan one{};
-        packed = packed && takes_packed_pairs(part, batch, &one);
-        if (packed && pplan.wr && (one.wr != pplan.wr || one.usable_pad != pplan.usable_pad)) packed = false;
-        pplan = one;
-    }
-    const size_t packed_floats = packed ? packed_floats_of(g->parts[0], pplan, batch) : 0;
-    int pb = 0;  // which of the group's two packed buffers this call fills
-    AWPU_HIP_TRY(hipSetDevice(dev0));
-    if (packed) {
-        g->stats.group_exchange = AWPU_EXCHANGE_PACKED_PAIRS;
-        const size_t cap = packed_floats_of(g->parts[0], pplan, g->cfg.max_batch);
-        if (g->fan_cap < cap) {  // (nobody may still be reading the old buffers)
-            for (awpu_hip *part : g->parts) {
-                AWPU_HIP_TRY(hipSetDevice(part->cfg.device));
-                AWPU_HIP_TRY(hipStreamSynchronize(part->copy_stream));
-                AWPU_HIP_TRY(hipStreamSynchronize(part->stream));
-            }
-            AWPU_HIP_TRY(hipSetDevice(dev0));
-            AWPU_HIP_TRY(hipStreamSynchronize(s));
-            dev_free(g->d_fan[0]);
-            dev_free(g->d_fan[1]);
-            g->fan_cap = 0;
-            AWPU_HIP_TRY(hipMalloc(&g->d_fan[0], cap * sizeof(float)));
-            AWPU_HIP_TRY(hipMalloc(&g->d_fan[1], cap * sizeof(float)));
-            g->fan_cap = cap;
-            g->fan_used[0] = g->fan_used[1] = false;
-        }
-        pb = (int) (g->fan_turn++ & 1);
-        if (g->fan_used[pb])  // buffer pb was read two calls ago: by the peers' copies and by the in-place parts' sweeps
-            for (awpu_hip *part : g->parts) AWPU_HIP_TRY(hipStreamWaitEvent(s, in_place(part) ? part->ev_swept[pb] : part->ev_copied[pb], 0));
-        awpu_hip *p0 = g->parts[0];
-        if (const int prc = pack_for_sweep(p0, pplan, d_frames, batch, g->d_fan[pb], s); prc != AWPU_OK) return prc;
-        g->fan_used[pb] = true;
-    }
-    AWPU_HIP_TRY(hipEventRecord(g->ev_fan, s));  // the frames (or their packed pairs) are in place once the caller's stream gets here
-
-    // ---- staged parts: what they need goes down to pinned memory once -- the packed buffer, or the union of their windows
-    int gb = 0;
-    bool any_staged = false;
-    for (awpu_hip *part : g->parts) any_staged |= part->peer == kPeerStaged && !in_place(part);
-    if (any_staged) {
-        int lo = 0, w = 0;
-        size_t need = 0;
-        if (packed) {
-            need = packed_floats_of(g->parts[0], pplan, g->cfg.max_batch);
-            lo = -1;  // (marks the packed payload: a change of payload re-sizes the staging like a change of window)
-            w = (int) pplan.wr;
-        } else {
-            lo = g->cfg.hist;
-            int hi = 0;
-            for (awpu_hip *part : g->parts) {
-                if (part->peer != kPeerStaged) continue;
-                const bool compact = part->compact_hist > 0;
-                lo = std::min(lo, compact ? part->wstart : 0);
-                hi = std::max(hi, compact ? part->wstart + part->compact_hist : part->cfg.hist);
-            }
-            w = hi - lo;
-            need = (size_t) g->cfg.n_streams * w * g->cfg.max_batch;
-        }
-        // (round-4 advisor) Only a buffer that is too SMALL is replaced, behind a synchronize of everybody who may still read it.  A
-        // change of payload -- packed pairs one call, raw windows the next: batches alternating with single frames -- keeps the
-        // buffers and their turn: every reuse of h_stage[gb] already waits for the uploads that read it two calls ago
-        // (ev_staged_read below), whatever they carried.
-        if (g->stage_cap < need) {
-            for (awpu_hip *part : g->parts) {  // nobody may still be reading the old staging buffers
-                AWPU_HIP_TRY(hipSetDevice(part->cfg.device));
-                AWPU_HIP_TRY(hipStreamSynchronize(part->copy_stream));
-            }
-            AWPU_HIP_TRY(hipSetDevice(dev0));
-            AWPU_HIP_TRY(hipStreamSynchronize(s));
-            for (int b = 0; b < 2; b++) {
-                if (g->h_stage[b]) (void) hipHostFree(g->h_stage[b]);
-                g->h_stage[b] = nullptr;
-            }
-            g->stage_cap = 0;
-            for (int b = 0; b < 2; b++) AWPU_HIP_TRY(hipHostMalloc(&g->h_stage[b], need * sizeof(float), hipHostMallocPortable));
-            g->stage_cap = need;
-            g->stage_turn = 0;
-            for (awpu_hip *part : g->parts) part->stage_used[0] = part->stage_used[1] = false;
-        }
-        g->stage_lo = lo;  // what THIS call's payload is (read by the uploads enqueued below, in this call)
-        g->stage_w = w;
-        gb = g->stage_turn++ & 1;
-        for (awpu_hip *part : g->parts)  // h_stage[gb] was read by the staged parts' uploads two calls ago
-            if (part->peer == kPeerStaged && !in_place(part) && part->stage_used[gb]) AWPU_HIP_TRY(hipStreamWaitEvent(s, part->ev_staged_read[gb], 0));
-        if (packed) {
-            AWPU_HIP_TRY(hipMemcpyAsync(g->h_stage[gb], g->d_fan[pb], packed_floats * sizeof(float), hipMemcpyDeviceToHost, s));
-        } else {
-            AWPU_HIP_TRY(hipMemcpy2DAsync(g->h_stage[gb], (size_t) w * sizeof(float), d_frames + lo, (size_t) g->cfg.hist * sizeof(float),
-                                          (size_t) w * sizeof(float), (size_t) batch * g->cfg.n_streams, hipMemcpyDeviceToHost, s));
-        }
-        AWPU_HIP_TRY(hipEventRecord(g->ev_staged[gb], s));
-    }
-
-    rc = for_each_part(g, [&](awpu_hip *part) {
-        AWPU_CTX(part);
-        AWPU_HIP_TRY(hipSetDevice(part->cfg.device));
-        int r = ensure_power(part, (size_t) part->cfg.pixel_count * batch);
-        if (r != AWPU_OK) return r;
-        TimingOff untimed(part);  // asynchronous path: the caller times its own stream
-        const bool staged = part->peer == kPeerStaged && !in_place(part);
-        if (in_place(part)) {  // same GPU: sweep the caller's frames (or the group's packed buffer) in place
-            AWPU_HIP_TRY(hipStreamWaitEvent(part->stream, g->ev_fan, 0));
-            if (packed) {
-                r = sweep_packed(part, pplan, g->d_fan[pb], g->fan_cap, batch, part->d_power, part->stream);
-                if (r == AWPU_OK) AWPU_HIP_TRY(hipEventRecord(part->ev_swept[pb], part->stream));
-            } else {
-                r = launch(part, d_frames, batch, part->d_power, part->stream, kFull);
-            }
-        } else {
-            const bool compact = part->compact_hist > 0;
-            const int dev_hist = compact ? part->compact_hist : part->cfg.hist;
-            const size_t need_window = (size_t) part->cfg.n_streams * dev_hist * part->cfg.max_batch;
-            const size_t need_packed = packed ? packed_floats_of(part, pplan, part->cfg.max_batch) : 0;
-            const size_t need = std::max(need_window, need_packed);
-            if (part->fan_cap < need) {
-                AWPU_HIP_TRY(hipStreamSynchronize(part->stream));
-                AWPU_HIP_TRY(hipStreamSynchronize(part->copy_stream));
-                dev_free(part->d_fan[0]);
-                dev_free(part->d_fan[1]);
-                part->fan_cap = 0;
-                AWPU_HIP_TRY(hipMalloc(&part->d_fan[0], need * sizeof(float)));
-                AWPU_HIP_TRY(hipMalloc(&part->d_fan[1], need * sizeof(float)));
-                part->fan_cap = need;
-                part->fan_used[0] = part->fan_used[1] = false;
-            }
-            // the part's own receive buffer follows the buffer it reads from: the group's packed buffer (pb) or, for a staged
-            // part, the staging buffer (gb); a window copy out of the caller's frames takes its own turns
-            const int b = staged ? gb : (packed ? pb : (int) (part->fan_turn++ & 1));
-            if (part->fan_used[b]) AWPU_HIP_TRY(hipStreamWaitEvent(part->copy_stream, part->ev_swept[b], 0));  // buffer b is free again
-            const size_t row = (size_t) dev_hist * sizeof(float);
-            if (staged) {
-                AWPU_HIP_TRY(hipStreamWaitEvent(part->copy_stream, g->ev_staged[gb], 0));
-                if (packed) {
-                    AWPU_HIP_TRY(hipMemcpyAsync(part->d_fan[b], g->h_stage[gb], packed_floats * sizeof(float), hipMemcpyHostToDevice, part->copy_stream));
-                } else {
-                    AWPU_HIP_TRY(hipMemcpy2DAsync(part->d_fan[b], row, g->h_stage[gb] + ((compact ? part->wstart : 0) - g->stage_lo),
-                                                  (size_t) g->stage_w * sizeof(float), row, (size_t) batch * part->cfg.n_streams,
-                                                  hipMemcpyHostToDevice, part->copy_stream));
-                }
-                AWPU_HIP_TRY(hipEventRecord(part->ev_staged_read[gb], part->copy_stream));
-                part->stage_used[gb] = true;
-            } else {
-                AWPU_HIP_TRY(hipStreamWaitEvent(part->copy_stream, g->ev_fan, 0));
-                if (packed) {  // ONE linear copy: the packed pairs of the whole batch
-                    AWPU_HIP_TRY(hipMemcpyAsync(part->d_fan[b], g->d_fan[pb], packed_floats * sizeof(float), hipMemcpyDeviceToDevice, part->copy_stream));
-                } else {
-                    AWPU_HIP_TRY(hipMemcpy2DAsync(part->d_fan[b], row, d_frames + (compact ? part->wstart : 0),
-                                                  (size_t) part->cfg.hist * sizeof(float), row, (size_t) batch * part->cfg.n_streams,
-                                                  hipMemcpyDeviceToDevice, part->copy_stream));
-                }
-            }
-            part->fan_used[b] = true;
-            AWPU_HIP_TRY(hipEventRecord(part->ev_copied[b], part->copy_stream));
-            AWPU_HIP_TRY(hipStreamWaitEvent(part->stream, part->ev_copied[b], 0));
-            r = packed ? sweep_packed(part, pplan, part->d_fan[b], part->fan_cap, batch, part->d_power, part->stream)
-                       : launch(part, part->d_fan[b], batch, part->d_power, part->stream, compact ? kCompact : kFull);
-            if (r == AWPU_OK) AWPU_HIP_TRY(hipEventRecord(part->ev_swept[b], part->stream));
-            if (r == AWPU_OK && staged) {  // the tile's way back starts on the part's own stream: device -> pinned
-                const size_t tile = (size_t) part->cfg.pixel_count * part->cfg.max_batch;
-                if (part->tile_cap < tile) {
-                    AWPU_HIP_TRY(hipStreamSynchronize(part->stream));
-                    for (int k = 0; k < 2; k++) {
-                        if (part->h_tile[k]) (void) hipHostFree(part->h_tile[k]);
-                        part->h_tile[k] = nullptr;
-                    }
-                    part->tile_cap = 0;
-                    for (int k = 0; k < 2; k++) AWPU_HIP_TRY(hipHostMalloc(&part->h_tile[k], tile * sizeof(float), hipHostMallocPortable));
-                    part->tile_cap = tile;
-                    part->tile_used[0] = part->tile_used[1] = false;
-                }
-                if (part->tile_used[gb]) AWPU_HIP_TRY(hipStreamWaitEvent(part->stream, part->ev_tile_free[gb], 0));
-                AWPU_HIP_TRY(hipMemcpyAsync(part->h_tile[gb], part->d_power, (size_t) part->cfg.pixel_count * batch * sizeof(float),
-                                            hipMemcpyDeviceToHost, part->stream));
-                part->tile_used[gb] = true;
-            }
-        }
-        if (r == AWPU_OK) AWPU_HIP_TRY(hipEventRecord(part->ev_done, part->stream));
-        return r;
-    });
-    if (rc != AWPU_OK) return rc;
-    AWPU_HIP_TRY(hipSetDevice(dev0));
-    const size_t pitch = (size_t) g->cfg.pixel_count;
-    for (awpu_hip *part : g->parts) {  // tiles back into the caller's [batch][pixel_count] image, range by range
-        AWPU_HIP_TRY(hipStreamWaitEvent(s, part->ev_done, 0));
-        const bool staged = part->peer == kPeerStaged && !in_place(part);
-        if (staged) {
-            rc = tile_to_image(part, part->h_tile[gb], d_power, pitch, batch, hipMemcpyHostToDevice, s);
-            if (rc != AWPU_OK) return rc;
-            AWPU_HIP_TRY(hipEventRecord(part->ev_tile_free[gb], s));
-        } else {
-            rc = tile_to_image(part, part->d_power, d_power, pitch, batch, hipMemcpyDeviceToDevice, s);
-            if (rc != AWPU_OK) return rc;
-        }
-    }
-    return AWPU_OK;
-}
-
-int group_stats(awpu_hip *g, awpu_hip_stats *out) {
-    awpu_hip_stats st = g->parts[0]->stats;
-    st.group_exchange = g->stats.group_exchange;
-    st.group_ranges = (int32_t) g->parts[0]->ranges.size();
-    for (size_t k = 1; k < g->parts.size(); k++) {
-        const awpu_hip_stats &p = g->parts[k]->stats;
-        st.launches += p.launches;
-        st.last_kernel_ms = std::max(st.last_kernel_ms, p.last_kernel_ms);   // the slabs run side by side
-        st.total_kernel_ms = std::max(st.total_kernel_ms, p.total_kernel_ms);
-        st.alg_bytes_frame += p.alg_bytes_frame;
-        st.alg_flops_frame += p.alg_flops_frame;
-        st.tau_max = std::max(st.tau_max, p.tau_max);
-        st.window = std::max(st.window, p.window);
-    }
-    *out = st;
-    return AWPU_OK;
-}
-
-}  // namespace
-
 // what the runs of blocks (awpu_runs.cpp) share with the calls below
 namespace awpu::host {
 
@@ -895,12 +372,7 @@ int check_antenna(const awpu_hip *h) {
 int ensure_track_index(awpu_hip *h) {
     const int U = h->usable();
     if (h->track_index == h->index) return AWPU_OK;
-    if (h->track_index_cap < (size_t) U) {
-        dev_free(h->d_track_index);
-        h->track_index_cap = 0;
-        AWPU_HIP_TRY(hipMalloc(&h->d_track_index, (size_t) U * sizeof(int32_t)));
-        h->track_index_cap = U;
-    }
+    if (const int rc = h->d_track_index.ensure((size_t) U); rc != AWPU_OK) return rc;
     h->track_index.clear();
     AWPU_HIP_TRY(hipMemcpy(h->d_track_index, h->index.data(), (size_t) U * sizeof(int32_t), hipMemcpyHostToDevice));
     h->track_index = h->index;
@@ -911,10 +383,28 @@ int ensure_track_index(awpu_hip *h) {
 int ensure_ring(awpu_hip *h) {
     if (h->d_ring) return AWPU_OK;
     const size_t ring_bytes = (size_t) h->cfg.n_streams * 2048 * sizeof(float);
-    AWPU_HIP_TRY(hipMalloc(&h->d_ring, ring_bytes));
+    if (const int rc = h->d_ring.ensure((size_t) h->cfg.n_streams * 2048); rc != AWPU_OK) return rc;
     AWPU_HIP_TRY(hipMemsetAsync(h->d_ring, 0, ring_bytes, h->stream));
-    AWPU_HIP_TRY(hipMalloc(&h->d_datagrams, (size_t) awpu::kSamples * AWPU_DATAGRAM_BYTES));
+    if (const int rc = h->d_datagrams.ensure((size_t) awpu::kSamples * AWPU_DATAGRAM_BYTES); rc != AWPU_OK) return rc;
     h->ring_pos = 0;
+    return AWPU_OK;
+}
+
+// H2D of one block of raw datagrams + the unpack launch, enqueued on the handle's stream (no wait)
+int enqueue_ingest(awpu_hip *h, const void *datagrams, int32_t stride_bytes) {
+    if (!h || !datagrams) return invalid("null argument");
+    if (h->cfg.hist != AWPU_HIST || h->cfg.n_streams > 256) return invalid("ingest needs hist 1024 and <= 256 streams");
+    if (stride_bytes < AWPU_DATAGRAM_BYTES) return invalid("datagram stride below 1032 bytes");
+    AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
+    const int rc = ensure_ring(h);
+    if (rc != AWPU_OK) return rc;
+    // tight copy of the 256 datagrams (the header travels too: 8 bytes each, ignored like the
+    // reference ignores msg.counter, pipeline.cpp:264-267)
+    AWPU_HIP_TRY(hipMemcpy2DAsync(h->d_datagrams, AWPU_DATAGRAM_BYTES, datagrams, (size_t) stride_bytes,
+                                  AWPU_DATAGRAM_BYTES, awpu::kSamples, hipMemcpyHostToDevice, h->stream));
+    AWPU_HIP_TRY(awpu::launch_unpack_block(h->d_datagrams, AWPU_DATAGRAM_BYTES, h->cfg.n_streams, h->d_ring,
+                                           h->ring_pos, h->stream));
+    h->ring_pos = (h->ring_pos + awpu::kSamples) % AWPU_HIST;  // Streams::forward
     return AWPU_OK;
 }
 
@@ -927,8 +417,7 @@ int ensure_taps(awpu_hip *h, int rows, int cols, int out_rows, int out_cols, hip
         awpu::resize_taps(rows, out_rows, false, taps.data() + out_cols);
         AWPU_HIP_TRY(hipStreamSynchronize(s));  // an earlier launch may still read the old taps
         retire_live_graphs(h);
-        dev_free(h->d_taps);
-        AWPU_HIP_TRY(hipMalloc(&h->d_taps, taps.size() * sizeof(awpu::ResizeTap)));
+        if (const int rc = h->d_taps.grow(taps.size()); rc != AWPU_OK) return rc;
         AWPU_HIP_TRY(hipMemcpy(h->d_taps, taps.data(), taps.size() * sizeof(awpu::ResizeTap), hipMemcpyHostToDevice));
         std::memcpy(h->taps_key, key, sizeof(key));
         h->taps_band_rows = awpu::watch_band_rows(taps.data() + out_cols, rows, out_rows);
@@ -998,13 +487,13 @@ int awpu_hip_create(awpu_hip_t **out, const awpu_hip_cfg *cfg) {
     awpu_hip *h = new (std::nothrow) awpu_hip();
     if (!h) return AWPU_ERR_NOMEM;
     h->cfg = c;
-    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreate(&h->ev_begin);
-    if (e == hipSuccess) e = hipEventCreate(&h->ev_end);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_fan, hipEventDisableTiming);
-    if (e != hipSuccess) {
+    const char *what = "stream/event creation";
+    int rc = h->stream.ensure(what);
+    if (rc == AWPU_OK) rc = h->ev_begin.ensure(hipEventDefault, what);
+    if (rc == AWPU_OK) rc = h->ev_end.ensure(hipEventDefault, what);
+    if (rc != AWPU_OK) {
         awpu_hip_destroy(h);
-        return hip_fail(e, "stream/event creation");
+        return rc;
     }
     *out = h;
     return AWPU_OK;
@@ -1012,50 +501,22 @@ int awpu_hip_create(awpu_hip_t **out, const awpu_hip_cfg *cfg) {
 
 int awpu_hip_destroy(awpu_hip_t *h) {
     if (!h) return AWPU_OK;
-    for (awpu_hip *part : h->parts) awpu_hip_destroy(part);
-    h->parts.clear();
+    for (awpu_hip *part : h->group.parts) awpu_hip_destroy(part);
+    h->group.parts.clear();
     (void) hipSetDevice(h->cfg.device);
     if (h->stream) (void) hipStreamSynchronize(h->stream);
     if (h->copy_stream) (void) hipStreamSynchronize(h->copy_stream);
     if (h->listen_stream) (void) hipStreamSynchronize(h->listen_stream);
-    release_device(h);
-    for (hipEvent_t ev : {h->ev_begin, h->ev_end, h->ev_fan, h->ev_copied[0], h->ev_copied[1], h->ev_swept[0], h->ev_swept[1], h->ev_done,
-                          h->ev_staged[0], h->ev_staged[1], h->ev_tile_free[0], h->ev_tile_free[1], h->ev_staged_read[0], h->ev_staged_read[1],
-                          h->ev_blk_in[0], h->ev_blk_in[1], h->ev_blk_hist[0], h->ev_blk_hist[1], h->ev_blk_cut[0], h->ev_blk_cut[1],
-                          h->ev_blk_swept[0], h->ev_blk_swept[1], h->ev_blk_out[0], h->ev_blk_out[1], h->ev_blk_ring,
-                          h->ev_listened[0], h->ev_listened[1], h->ev_listen_out[0], h->ev_listen_out[1]})
-        if (ev) (void) hipEventDestroy(ev);
-    if (h->stream) (void) hipStreamDestroy(h->stream);
-    if (h->copy_stream) (void) hipStreamDestroy(h->copy_stream);
-    if (h->listen_stream) (void) hipStreamDestroy(h->listen_stream);
-    delete h;
+    retire_live_graphs(h);
+    free_tables(h);
+    delete h;  // buffers, events and streams go with their owners (awpu_handle.h)
     return AWPU_OK;
 }
 
 int awpu_hip_set_delay_table(awpu_hip_t *h, const int32_t *off, const float *frac) {
     AWPU_CTX(h);
     if (!h || !off || !frac) return invalid("null argument");
-    if (!h->parts.empty()) {  // every device gets the rows of its pixel ranges, back to back
-        h->union_window_done = false;
-        return for_each_part(h, [&](awpu_hip *part) {
-            part->cfg.window_begin = h->cfg.window_begin;  // (the union window of the OLD table is void: back to the caller's, if any)
-            part->cfg.window_end = h->cfg.window_end;
-            const size_t stride = (size_t) h->cfg.lut_stride;
-            if (part->ranges.size() == 1) {
-                const size_t first = (size_t) part->ranges[0].first * stride;
-                return awpu_hip_set_delay_table(part, off + first, frac + first);
-            }
-            std::vector<int32_t> o((size_t) part->cfg.pixel_count * stride);
-            std::vector<float> f(o.size());
-            size_t done = 0;
-            for (const auto &r : part->ranges) {
-                std::memcpy(&o[done * stride], off + (size_t) r.first * stride, (size_t) r.second * stride * sizeof(int32_t));
-                std::memcpy(&f[done * stride], frac + (size_t) r.first * stride, (size_t) r.second * stride * sizeof(float));
-                done += (size_t) r.second;
-            }
-            return awpu_hip_set_delay_table(part, o.data(), f.data());
-        });
-    }
+    if (is_group(h)) return group_set_delay_table(h, off, frac);
     const size_t n = (size_t) h->cfg.pixel_count * h->cfg.lut_stride;
     for (size_t i = 0; i < n; i++) {
         if (!(frac[i] >= 0.0f && frac[i] <= 1.0f)) return invalid("fraction outside [0, 1]");
@@ -1070,14 +531,7 @@ int awpu_hip_set_delay_table(awpu_hip_t *h, const int32_t *off, const float *fra
 int awpu_hip_set_active_mics(awpu_hip_t *h, const int32_t *index, int32_t usable) {
     AWPU_CTX(h);
     if (!h) return invalid("null handle");
-    if (!h->parts.empty()) {
-        h->union_window_done = false;
-        return for_each_part(h, [&](awpu_hip *part) {
-            part->cfg.window_begin = h->cfg.window_begin;  // (as in awpu_hip_set_delay_table: the union is taken anew)
-            part->cfg.window_end = h->cfg.window_end;
-            return awpu_hip_set_active_mics(part, index, usable);
-        });
-    }
+    if (is_group(h)) return group_set_active_mics(h, index, usable);
     const int limit = std::min(h->cfg.n_streams, h->cfg.lut_stride);
     if (usable < 1 || usable > limit) return invalid("usable outside [1, min(n_streams, lut_stride)]");
     std::vector<int32_t> idx(usable);
@@ -1094,7 +548,7 @@ int awpu_hip_set_active_mics(awpu_hip_t *h, const int32_t *index, int32_t usable
 int awpu_hip_set_mic_gains(awpu_hip_t *h, const float *gains) {
     AWPU_CTX(h);
     if (!h) return invalid("null handle");
-    if (!h->parts.empty()) return for_each_part(h, [&](awpu_hip *part) { return awpu_hip_set_mic_gains(part, gains); });
+    if (is_group(h)) return group_set_mic_gains(h, gains);
     if (!gains) {
         h->gain.clear();
     } else {
@@ -1131,7 +585,7 @@ int usable_from_power(const float *power, float reference_power_level, int32_t *
 
 int calibrate_rows(awpu_hip *h, const float *d_rows, int pitch, int hist, float reference_power_level, int32_t *index,
                    float *correction, float *median, int32_t *usable, hipStream_t s) {
-    if (!h->d_calib) AWPU_HIP_TRY(hipMalloc(&h->d_calib, AWPU_ELEMENTS * sizeof(float)));
+    if (const int rc = h->d_calib.ensure(AWPU_ELEMENTS); rc != AWPU_OK) return rc;
     AWPU_HIP_TRY(awpu::launch_stream_power(d_rows, pitch, hist, AWPU_ELEMENTS, h->d_calib, s));
     float power[AWPU_ELEMENTS];
     AWPU_HIP_TRY(hipMemcpyAsync(power, h->d_calib, sizeof(power), hipMemcpyDeviceToHost, s));
@@ -1144,7 +598,7 @@ int calibrate_rows(awpu_hip *h, const float *d_rows, int pitch, int hist, float 
 
 int awpu_hip_calibrate_device(awpu_hip_t *h, const float *d_frame, int32_t array, float reference_power_level,
                               int32_t *index, float *correction, float *median, int32_t *usable, void *stream) {
-    if (h && !h->parts.empty()) h = h->parts[0];  // not pixel-sharded: a device group answers with its first device
+    h = first_device(h);
     AWPU_CTX(h);
     if (!h || !d_frame || !index || !correction || !usable) return invalid("null argument");
     if (array < 0 || (array + 1) * AWPU_ELEMENTS > h->cfg.n_streams) return invalid("array outside the streams");
@@ -1158,7 +612,7 @@ int awpu_hip_calibrate_device(awpu_hip_t *h, const float *d_frame, int32_t array
 int awpu_hip_calibrate_host(awpu_hip_t *h, const float *frame, int32_t array, float reference_power_level,
                              int32_t *index, float *correction, float *median, int32_t *usable) {
     const bool busy = h && h->in_flight;  // (the staging buffer below is the one an asynchronous call uploads into)
-    if (h && !h->parts.empty()) h = h->parts[0];  // not pixel-sharded: a device group answers with its first device
+    h = first_device(h);
     AWPU_CTX(h);
     if (!h || !frame || !index || !correction || !usable) return invalid("null argument");
     if (array < 0 || (array + 1) * AWPU_ELEMENTS > h->cfg.n_streams) return invalid("array outside the streams");
@@ -1167,12 +621,7 @@ int awpu_hip_calibrate_host(awpu_hip_t *h, const float *frame, int32_t array, fl
     AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
     // only the array's 64 streams travel; they share the frame staging buffer of awpu_hip_process
     const size_t need = (size_t) AWPU_ELEMENTS * h->cfg.hist;
-    if (h->frames_cap < need) {
-        dev_free(h->d_frames);
-        h->frames_cap = 0;
-        AWPU_HIP_TRY(hipMalloc(&h->d_frames, need * sizeof(float)));
-        h->frames_cap = need;
-    }
+    if (const int rc = h->d_frames.ensure(need); rc != AWPU_OK) return rc;
     AWPU_HIP_TRY(hipMemcpyAsync(h->d_frames, frame + (size_t) array * AWPU_ELEMENTS * h->cfg.hist, need * sizeof(float),
                                 hipMemcpyHostToDevice, h->stream));
     return calibrate_rows(h, h->d_frames, h->cfg.hist, h->cfg.hist, reference_power_level, index, correction, median,
@@ -1181,7 +630,7 @@ int awpu_hip_calibrate_host(awpu_hip_t *h, const float *frame, int32_t array, fl
 
 int awpu_hip_calibrate_ring(awpu_hip_t *h, int32_t array, float reference_power_level, int32_t *index,
                             float *correction, float *median, int32_t *usable) {
-    if (h && !h->parts.empty()) h = h->parts[0];  // not pixel-sharded: a device group answers with its first device
+    h = first_device(h);
     AWPU_CTX(h);
     if (!h || !index || !correction || !usable) return invalid("null argument");
     if (array < 0 || (array + 1) * AWPU_ELEMENTS > h->cfg.n_streams) return invalid("array outside the streams");
@@ -1195,7 +644,7 @@ int awpu_hip_calibrate_ring(awpu_hip_t *h, int32_t array, float reference_power_
 
 int awpu_hip_beams(awpu_hip_t *h, const float *d_frame, const int32_t *off, const float *frac, int32_t n_dir,
                    float *power, float *beams) {
-    if (h && !h->parts.empty()) h = h->parts[0];  // not pixel-sharded: a device group answers with its first device
+    h = first_device(h);
     AWPU_CTX(h);
     if (!h || !off || !frac || (!power && !beams)) return invalid("null argument");
     if (n_dir < 1 || n_dir > 65535) return invalid("n_dir outside [1, 65535]");
@@ -1226,19 +675,10 @@ int awpu_hip_beams(awpu_hip_t *h, const float *d_frame, const int32_t *off, cons
         }
     }
     AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
-    if (h->beam_lut_cap < entries.size()) {
-        dev_free(h->d_beam_lut);
-        h->beam_lut_cap = 0;
-        AWPU_HIP_TRY(hipMalloc(&h->d_beam_lut, entries.size() * sizeof(awpu::LutEntry)));
-        h->beam_lut_cap = entries.size();
-    }
-    if (h->beam_cap < (size_t) n_dir) {
-        dev_free(h->d_beam_out);
-        h->beam_cap = 0;
-        AWPU_HIP_TRY(hipMalloc(&h->d_beam_out, (size_t) n_dir * (1 + awpu::kSamples) * sizeof(float)));
-        h->beam_cap = n_dir;
-    }
-    float *d_power = h->d_beam_out, *d_beams = h->d_beam_out + h->beam_cap;
+    if (const int rc = h->d_beam_lut.ensure(entries.size()); rc != AWPU_OK) return rc;
+    if (const int rc = h->d_beam_out.ensure((size_t) n_dir * (1 + awpu::kSamples)); rc != AWPU_OK) return rc;
+    // [n] powers then [n][256] beams, n = the directions the buffer was allocated for (its layout follows its allocation)
+    float *d_power = h->d_beam_out, *d_beams = h->d_beam_out + h->d_beam_out.cap / (1 + awpu::kSamples);
     AWPU_HIP_TRY(hipMemcpyAsync(h->d_beam_lut, entries.data(), entries.size() * sizeof(awpu::LutEntry),
                                 hipMemcpyHostToDevice, h->stream));
     AWPU_HIP_TRY(awpu::launch_das_beams(frame, h->d_beam_lut, U, n_dir, d_power, beams ? d_beams : nullptr, h->stream));
@@ -1254,7 +694,7 @@ int awpu_hip_beams(awpu_hip_t *h, const float *d_frame, const int32_t *off, cons
 // ---- particle tracking (include/awpu_hip_track.h; kernels in track_kernels.hip) ---------------------------------------
 
 int awpu_hip_set_antenna(awpu_hip_t *h, const float *xyz, int32_t n) {
-    if (h && !h->parts.empty()) h = h->parts[0];  // not pixel-sharded: a device group answers with its first device
+    h = first_device(h);
     AWPU_CTX(h);
     if (!h || !xyz) return invalid("null argument");
     if (n < 1 || n > h->cfg.lut_stride) return invalid("n outside [1, lut_stride]");
@@ -1272,31 +712,17 @@ int awpu_hip_set_antenna(awpu_hip_t *h, const float *xyz, int32_t n) {
         return fail(AWPU_ERR_RANGE, "antenna aperture exceeds 256 samples: delays would read outside the frame history");
     AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
     if (h->antenna.size() != (size_t) 3 * n) {
-        dev_free(h->d_xyz);
         h->antenna.clear();
-        AWPU_HIP_TRY(hipMalloc(&h->d_xyz, (size_t) 3 * n * sizeof(float)));
+        if (const int rc = h->d_xyz.grow((size_t) 3 * n); rc != AWPU_OK) return rc;
     }
     AWPU_HIP_TRY(hipMemcpy(h->d_xyz, xyz, (size_t) 3 * n * sizeof(float), hipMemcpyHostToDevice));
     h->antenna.assign(xyz, xyz + (size_t) 3 * n);
     return AWPU_OK;
 }
 
-namespace {
-
-int ensure_track_buffer(awpu_hip *h, size_t bytes) {
-    if (h->track_cap >= bytes) return AWPU_OK;
-    dev_free(h->d_track);
-    h->track_cap = 0;
-    AWPU_HIP_TRY(hipMalloc(&h->d_track, bytes));
-    h->track_cap = bytes;
-    return AWPU_OK;
-}
-
-}  // namespace
-
 int awpu_hip_steer_table_device(awpu_hip_t *h, const double *theta, const double *phi, int32_t n_dir, int32_t *off,
                                 float *frac) {
-    if (h && !h->parts.empty()) h = h->parts[0];  // not pixel-sharded: a device group answers with its first device
+    h = first_device(h);
     AWPU_CTX(h);
     if (!h || !theta || !phi || !off || !frac) return invalid("null argument");
     if (n_dir < 1 || n_dir > 65535) return invalid("n_dir outside [1, 65535]");
@@ -1304,8 +730,8 @@ int awpu_hip_steer_table_device(awpu_hip_t *h, const double *theta, const double
     const int n = (int) (h->antenna.size() / 3);
     AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
     const size_t angles = align16((size_t) n_dir * sizeof(double)), table = (size_t) n_dir * n;
-    if (int rc = ensure_track_buffer(h, 2 * angles + table * (sizeof(int32_t) + sizeof(float)))) return rc;
-    double *d_theta = (double *) h->d_track, *d_phi = (double *) (h->d_track + angles);
+    if (int rc = h->d_track.ensure(2 * angles + table * (sizeof(int32_t) + sizeof(float)))) return rc;
+    double *d_theta = (double *) h->d_track.get(), *d_phi = (double *) (h->d_track + angles);
     int32_t *d_off = (int32_t *) (h->d_track + 2 * angles);
     float *d_frac = (float *) (d_off + table);
     AWPU_HIP_TRY(hipMemcpyAsync(d_theta, theta, (size_t) n_dir * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -1319,7 +745,7 @@ int awpu_hip_steer_table_device(awpu_hip_t *h, const double *theta, const double
 
 int awpu_hip_track(awpu_hip_t *h, const float *d_frame, awpu_particle_t *p, int32_t n, double theta_limit,
                    double reference, double *reference_used, float *beams) {
-    if (h && !h->parts.empty()) h = h->parts[0];  // not pixel-sharded: a device group answers with its first device
+    h = first_device(h);
     AWPU_CTX(h);
     if (!h || !p) return invalid("null argument");
     if (int rc = check_particles(p, n, theta_limit, reference)) return rc;
@@ -1338,7 +764,7 @@ int awpu_hip_track(awpu_hip_t *h, const float *d_frame, awpu_particle_t *p, int3
     const int U = h->usable();
     if (int rc = ensure_track_index(h)) return rc;
     const size_t particles = (size_t) n * sizeof(awpu_particle_t), head = align16(particles + sizeof(double));
-    if (int rc = ensure_track_buffer(h, head + (beams ? (size_t) n * awpu::kSamples * sizeof(float) : 0))) return rc;
+    if (int rc = h->d_track.ensure(head + (beams ? (size_t) n * awpu::kSamples * sizeof(float) : 0))) return rc;
     awpu::TrackArgs a{};
     a.frame = frame;
     a.pitch = pitch;
@@ -1369,11 +795,11 @@ int awpu_hip_track(awpu_hip_t *h, const float *d_frame, awpu_particle_t *p, int3
 int awpu_hip_set_fir_table(awpu_hip_t *h, const float *coeffs) {
     AWPU_CTX(h);
     if (!h || !coeffs) return invalid("null argument");
-    if (!h->parts.empty()) return for_each_part(h, [&](awpu_hip *part) { return awpu_hip_set_fir_table(part, coeffs); });
+    if (is_group(h)) return group_set_fir_table(h, coeffs);
     AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
     // (on the device: the caller's 101 rows followed by zero rows up to kFir8CoeffRows -- the plane kernel's padding
     // entries name row 101, and its entry requests run a few items past a row's end, where any 7-bit row may stand)
-    if (!h->d_fir) AWPU_HIP_TRY(hipMalloc(&h->d_fir, awpu::kFir8CoeffRows * 8 * sizeof(float)));
+    if (const int rc = h->d_fir.ensure(awpu::kFir8CoeffRows * 8); rc != AWPU_OK) return rc;
     AWPU_HIP_TRY(hipStreamSynchronize(h->stream));  // (a sweep still reading the old coefficients)
     AWPU_HIP_TRY(hipMemset(h->d_fir, 0, awpu::kFir8CoeffRows * 8 * sizeof(float)));
     AWPU_HIP_TRY(hipMemcpy(h->d_fir, coeffs, 101 * 8 * sizeof(float), hipMemcpyHostToDevice));
@@ -1387,8 +813,8 @@ int awpu_hip_process(awpu_hip_t *h, const float *frames, int32_t batch, float *p
     if (!h) return invalid("null handle");
     if (!frames || !power) return invalid("null argument");
     if (h->in_flight) return fail(AWPU_ERR_STATE, "an awpu_hip_process_async call is in flight on this handle: awpu_hip_wait first");
-    if (!h->parts.empty()) return group_process(h, frames, batch, power);
-    if (batch == 1 && h->ranges.empty()) return live_host_call(h, frames, power);
+    if (is_group(h)) return group_process(h, frames, batch, power);
+    if (batch == 1 && h->member.ranges.empty()) return live_host_call(h, frames, power);
     int rc = enqueue_host_process(h, frames, batch);
     if (rc != AWPU_OK) return rc;
     rc = enqueue_power_to_host(h, batch, power, (size_t) h->cfg.pixel_count);
@@ -1402,23 +828,8 @@ int awpu_hip_process_async(awpu_hip_t *h, const float *frames, int32_t batch, fl
     if (!frames || !power) return invalid("null argument");
     if (h->in_flight) return fail(AWPU_ERR_STATE, "a call is in flight already: awpu_hip_wait first");
     int rc;
-    if (!h->parts.empty()) {
-        const size_t pitch = (size_t) h->cfg.pixel_count;
-        rc = for_each_part(h, [&](awpu_hip *part) {
-            AWPU_CTX(part);
-            const int r = enqueue_host_process(part, frames, batch);
-            return r != AWPU_OK ? r : enqueue_power_to_host(part, batch, power, pitch);
-        });
-        if (rc != AWPU_OK) {  // parts before the failing one hold copies from `frames` and into `power` in flight, and
-            const std::string why = h->last_error;  // the caller is about to hear "failed": finish them before it does
-            for (awpu_hip *part : h->parts)
-                if (hipSetDevice(part->cfg.device) == hipSuccess) {
-                    if (part->copy_stream) (void) hipStreamSynchronize(part->copy_stream);
-                    (void) hipStreamSynchronize(part->stream);
-                }
-            (void) hipGetLastError();
-            note_error(why);
-        }
+    if (is_group(h)) {
+        rc = group_process_async(h, frames, batch, power);
     } else {
         rc = enqueue_host_process(h, frames, batch);
         if (rc == AWPU_OK) rc = enqueue_power_to_host(h, batch, power, (size_t) h->cfg.pixel_count);
@@ -1432,8 +843,7 @@ int awpu_hip_wait(awpu_hip_t *h) {
     if (!h) return invalid("null handle");
     if (!h->in_flight) return AWPU_OK;  // nothing to wait for
     h->in_flight = false;
-    if (!h->parts.empty()) return for_each_part(h, [&](awpu_hip *part) { return wait_and_time(part); });
-    return wait_and_time(h);
+    return is_group(h) ? group_wait(h) : wait_and_time(h);
 }
 
 int awpu_hip_process_device(awpu_hip_t *h, const float *d_frames, int32_t batch, float *d_power,
@@ -1441,7 +851,7 @@ int awpu_hip_process_device(awpu_hip_t *h, const float *d_frames, int32_t batch,
     AWPU_CTX(h);
     if (!h) return invalid("null handle");
     if (!d_frames || !d_power) return invalid("null argument");
-    if (!h->parts.empty()) return group_process_device(h, d_frames, batch, d_power, static_cast<hipStream_t>(stream));
+    if (is_group(h)) return group_process_device(h, d_frames, batch, d_power, static_cast<hipStream_t>(stream));
     const int rc = check_ready(h, batch);
     if (rc != AWPU_OK) return rc;
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
@@ -1453,7 +863,7 @@ int awpu_hip_process_device_sums(awpu_hip_t *h, const float *d_frames, int32_t b
     AWPU_CTX(h);
     if (!h) return invalid("null handle");
     if (!d_frames || !d_power || !d_sums) return invalid("null argument");
-    if (!h->parts.empty()) return invalid("the pre-epilogue sums are exported by single-device handles only");
+    if (is_group(h)) return invalid("the pre-epilogue sums are exported by single-device handles only");
     const int rc = check_ready(h, batch);
     if (rc != AWPU_OK) return rc;
     if (!h->exact_pairs_ok) return fail(AWPU_ERR_STATE, "the pre-epilogue sums need AWPU_MATH_F32_EXACT with AWPU_INTERP_LERP");
@@ -1465,42 +875,9 @@ int awpu_hip_process_device_sums(awpu_hip_t *h, const float *d_frames, int32_t b
     return lrc;
 }
 
-namespace {
-
-// H2D of one block of raw datagrams + the unpack launch, enqueued on the handle's stream (no wait)
-int enqueue_ingest(awpu_hip *h, const void *datagrams, int32_t stride_bytes) {
-    if (!h || !datagrams) return invalid("null argument");
-    if (h->cfg.hist != AWPU_HIST || h->cfg.n_streams > 256) return invalid("ingest needs hist 1024 and <= 256 streams");
-    if (stride_bytes < AWPU_DATAGRAM_BYTES) return invalid("datagram stride below 1032 bytes");
-    AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
-    const int rc = ensure_ring(h);
-    if (rc != AWPU_OK) return rc;
-    // tight copy of the 256 datagrams (the header travels too: 8 bytes each, ignored like the
-    // reference ignores msg.counter, pipeline.cpp:264-267)
-    AWPU_HIP_TRY(hipMemcpy2DAsync(h->d_datagrams, AWPU_DATAGRAM_BYTES, datagrams, (size_t) stride_bytes,
-                                  AWPU_DATAGRAM_BYTES, awpu::kSamples, hipMemcpyHostToDevice, h->stream));
-    AWPU_HIP_TRY(awpu::launch_unpack_block(h->d_datagrams, AWPU_DATAGRAM_BYTES, h->cfg.n_streams, h->d_ring,
-                                           h->ring_pos, h->stream));
-    h->ring_pos = (h->ring_pos + awpu::kSamples) % AWPU_HIST;  // Streams::forward
-    return AWPU_OK;
-}
-
-}  // namespace
-
 int awpu_hip_ingest_block(awpu_hip_t *h, const void *datagrams, int32_t stride_bytes) {
     AWPU_CTX(h);
-    if (h && !h->parts.empty()) {  // every device keeps the whole ring (264 KB per block each, over its own PCIe link)
-        int rc = for_each_part(h, [&](awpu_hip *part) {
-            AWPU_CTX(part);
-            return enqueue_ingest(part, datagrams, stride_bytes);
-        });
-        if (rc != AWPU_OK) return rc;
-        return for_each_part(h, [&](awpu_hip *part) {
-            AWPU_HIP_TRY(hipSetDevice(part->cfg.device));
-            AWPU_HIP_TRY(hipStreamSynchronize(part->stream));
-            return (int) AWPU_OK;
-        });
-    }
+    if (h && is_group(h)) return group_ingest_block(h, datagrams, stride_bytes);
     const int rc = enqueue_ingest(h, datagrams, stride_bytes);
     if (rc != AWPU_OK) return rc;
     // the staging buffer is reused by the next call: finish the copy before returning
@@ -1524,14 +901,9 @@ int enqueue_live_block(awpu_hip *h, const void *datagrams, int32_t stride_bytes,
     if (image || big_image) {
         const size_t channels = d_colormap ? 3 : 1;
         const size_t need = sizeof(float) + (size_t) n + (big_image ? (size_t) out_rows * out_cols * channels : 0);
-        if (h->display_cap < need) {
-            retire_live_graphs(h);
-            dev_free(h->d_display);
-            h->display_cap = 0;
-            AWPU_HIP_TRY(hipMalloc(&h->d_display, need));
-            h->display_cap = need;
-        }
-        float *d_peak = reinterpret_cast<float *>(h->d_display);
+        rc = ensure_seen_by_live_graphs(h, h->d_display, need);
+        if (rc != AWPU_OK) return rc;
+        float *d_peak = reinterpret_cast<float *>(h->d_display.get());
         uint8_t *d_small = h->d_display + sizeof(float), *d_big = d_small + n;
         AWPU_HIP_TRY(awpu::launch_heatmap(h->d_power, n, 1, d_peak, false, d_small, h->stream));
         if (image) AWPU_HIP_TRY(hipMemcpyAsync(image, d_small, (size_t) n, hipMemcpyDeviceToHost, h->stream));
@@ -1551,7 +923,7 @@ int awpu_hip_live_block(awpu_hip_t *h, const void *datagrams, int32_t stride_byt
                         int32_t cols, uint8_t *image, int32_t out_rows, int32_t out_cols, const uint8_t *d_colormap,
                         uint8_t *big_image) {
     AWPU_CTX(h);
-    if (h && !h->parts.empty()) return invalid("the display step needs the whole grid on one device");
+    if (h && is_group(h)) return invalid("the display step needs the whole grid on one device");
     if (h && h->in_flight) return fail(AWPU_ERR_STATE, "an awpu_hip_process_async call is in flight on this handle: awpu_hip_wait first");
     int rc = check_ready(h, 1);
     if (rc != AWPU_OK) return rc;
@@ -1646,19 +1018,7 @@ int awpu_hip_process_ring(awpu_hip_t *h, float *power) {
     AWPU_CTX(h);
     if (!h) return invalid("null handle");
     if (!power) return invalid("null argument");
-    if (!h->parts.empty()) {  // every device sweeps its slab of its own ring's snapshot
-        int grc = for_each_part(h, [&](awpu_hip *part) {
-            AWPU_CTX(part);
-            int r = check_ready(part, 1);
-            if (r != AWPU_OK) return r;
-            if (!part->d_ring) return fail(AWPU_ERR_STATE, "no block ingested yet");
-            r = ensure_power(part, (size_t) part->cfg.pixel_count);
-            if (r == AWPU_OK) r = launch(part, part->d_ring + part->ring_pos, 1, part->d_power, part->stream, kRing);
-            return r != AWPU_OK ? r : enqueue_power_to_host(part, 1, power, (size_t) h->cfg.pixel_count);
-        });
-        if (grc != AWPU_OK) return grc;
-        return for_each_part(h, [&](awpu_hip *part) { return wait_and_time(part); });
-    }
+    if (is_group(h)) return group_process_ring(h, power);
     int rc = check_ready(h, 1);
     if (rc != AWPU_OK) return rc;
     if (!h->d_ring) {
@@ -1675,7 +1035,7 @@ int awpu_hip_process_ring(awpu_hip_t *h, float *power) {
 }
 
 int awpu_hip_ring_snapshot(awpu_hip_t *h, float *frames) {
-    if (h && !h->parts.empty()) h = h->parts[0];  // not pixel-sharded: a device group answers with its first device
+    h = first_device(h);
     AWPU_CTX(h);
     if (!h || !frames) return invalid("null argument");
     if (!h->d_ring) {
@@ -1690,7 +1050,7 @@ int awpu_hip_ring_snapshot(awpu_hip_t *h, float *frames) {
 
 int awpu_hip_heatmap_u8_device(awpu_hip_t *h, const float *d_power, int32_t n, int32_t batch, float *d_peak,
                                int32_t peak_given, uint8_t *d_pix, void *stream) {
-    if (h && !h->parts.empty()) h = h->parts[0];  // not pixel-sharded: a device group answers with its first device
+    h = first_device(h);
     AWPU_CTX(h);
     if (!h || !d_power || !d_peak || !d_pix || n < 1 || batch < 1 || batch > 65535) return invalid("bad argument");
     AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
@@ -1702,7 +1062,7 @@ int awpu_hip_heatmap_u8_device(awpu_hip_t *h, const float *d_power, int32_t n, i
 int awpu_hip_upscale_u8_device(awpu_hip_t *h, const uint8_t *d_pix, int32_t rows, int32_t cols, int32_t batch,
                                const uint8_t *d_colormap, uint8_t *d_out, int32_t out_rows, int32_t out_cols,
                                void *stream) {
-    if (h && !h->parts.empty()) h = h->parts[0];  // not pixel-sharded: a device group answers with its first device
+    h = first_device(h);
     AWPU_CTX(h);
     if (!h || !d_pix || !d_out || rows < 1 || cols < 1 || batch < 1 || batch > 65535) return invalid("bad argument");
     if (out_rows < rows || out_cols < cols || out_rows > 65535) return invalid("upscale only: out >= in, out_rows <= 65535");
@@ -1748,7 +1108,7 @@ namespace {
 // the packed layout of a single-device handle that is ready for `batch` frames (packed_shape: awpu_sweep.cpp)
 int packed_plan(awpu_hip *h, int batch, awpu::FastPlan *plan) {
     if (!h) return invalid("null handle");
-    if (!h->parts.empty()) return fail(AWPU_ERR_STATE, "packed frames: a device group exchanges its frames itself");
+    if (is_group(h)) return fail(AWPU_ERR_STATE, "packed frames: a device group exchanges its frames itself");
     const int rc = check_ready(h, batch);
     return rc != AWPU_OK ? rc : packed_shape(h, batch, plan);
 }
@@ -1794,13 +1154,7 @@ int awpu_hip_process_packed(awpu_hip_t *h, const float *d_packed, int32_t batch,
 int awpu_hip_synchronize(awpu_hip_t *h) {
     AWPU_CTX(h);
     if (!h) return invalid("null handle");
-    if (!h->parts.empty())
-        return for_each_part(h, [&](awpu_hip *part) {
-            AWPU_HIP_TRY(hipSetDevice(part->cfg.device));
-            AWPU_HIP_TRY(hipStreamSynchronize(part->copy_stream));
-            AWPU_HIP_TRY(hipStreamSynchronize(part->stream));
-            return (int) AWPU_OK;
-        });
+    if (is_group(h)) return group_synchronize(h);
     AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
     AWPU_HIP_TRY(hipStreamSynchronize(h->stream));
     return AWPU_OK;
@@ -1809,17 +1163,9 @@ int awpu_hip_synchronize(awpu_hip_t *h) {
 int awpu_hip_group_peer_status(awpu_hip_t *h, int32_t *status, int32_t n) {
     AWPU_CTX(h);
     if (!h || !status || n < 1) return invalid("null argument");
-    const int have = h->parts.empty() ? 1 : (int) h->parts.size();
-    if (n < have) return invalid("status array shorter than the device group");
-    if (h->parts.empty()) {
-        status[0] = AWPU_PEER_SAME_DEVICE;
-    } else {
-        for (int k = 0; k < have; k++)
-            status[k] = h->parts[k]->peer == kPeerSame     ? AWPU_PEER_SAME_DEVICE
-                        : h->parts[k]->peer == kPeerDirect ? AWPU_PEER_DIRECT
-                                                           : AWPU_PEER_HOST_STAGED;
-    }
-    return have;
+    if (is_group(h)) return group_peer_status(h, status, n);
+    status[0] = AWPU_PEER_SAME_DEVICE;
+    return 1;
 }
 
 int awpu_hip_build_delay_table_device(int32_t device, const float *xyz, int32_t n, int32_t rows, int32_t columns, float fov_deg,
@@ -1838,37 +1184,30 @@ int awpu_hip_build_delay_table_device(int32_t device, const float *xyz, int32_t 
     const size_t P = (size_t) row_count * columns;
     std::vector<float> rot(P * 12);
     awpu::pixel_rotations(rows, columns, fov_deg, row_begin, row_count, rot.data());
-    float *d_xyz = nullptr, *d_rot = nullptr, *d_frac = nullptr;
-    int32_t *d_off = nullptr;
-    auto body = [&]() -> int {
-        AWPU_HIP_TRY(hipMalloc(&d_xyz, (size_t) 3 * n * sizeof(float)));
-        AWPU_HIP_TRY(hipMalloc(&d_rot, rot.size() * sizeof(float)));
-        AWPU_HIP_TRY(hipMalloc(&d_off, P * n * sizeof(int32_t)));
-        AWPU_HIP_TRY(hipMalloc(&d_frac, P * n * sizeof(float)));
-        AWPU_HIP_TRY(hipMemcpy(d_xyz, xyz, (size_t) 3 * n * sizeof(float), hipMemcpyHostToDevice));
-        AWPU_HIP_TRY(hipMemcpy(d_rot, rot.data(), rot.size() * sizeof(float), hipMemcpyHostToDevice));
-        // one launch per 32 768 pixels (the grid's x dimension is not the limit; this bounds a launch's run time)
-        for (size_t p0 = 0; p0 < P; p0 += 32768) {
-            const int np = (int) std::min<size_t>(32768, P - p0);
-            AWPU_HIP_TRY(awpu::launch_delay_table(d_xyz, n, d_rot + p0 * 12, np, awpu::samples_per_metre(), d_off + p0 * n, d_frac + p0 * n,
-                                                  nullptr));
-        }
-        AWPU_HIP_TRY(hipMemcpy(off, d_off, P * n * sizeof(int32_t), hipMemcpyDeviceToHost));
-        AWPU_HIP_TRY(hipMemcpy(frac, d_frac, P * n * sizeof(float), hipMemcpyDeviceToHost));
-        return AWPU_OK;
-    };
-    const int rc = body();
-    dev_free(d_xyz);
-    dev_free(d_rot);
-    dev_free(d_off);
-    dev_free(d_frac);
-    return rc;
+    DeviceBuffer<float> d_xyz, d_rot, d_frac;
+    DeviceBuffer<int32_t> d_off;
+    int rc = d_xyz.ensure((size_t) 3 * n);
+    if (rc == AWPU_OK) rc = d_rot.ensure(rot.size());
+    if (rc == AWPU_OK) rc = d_off.ensure(P * n);
+    if (rc == AWPU_OK) rc = d_frac.ensure(P * n);
+    if (rc != AWPU_OK) return rc;
+    AWPU_HIP_TRY(hipMemcpy(d_xyz, xyz, (size_t) 3 * n * sizeof(float), hipMemcpyHostToDevice));
+    AWPU_HIP_TRY(hipMemcpy(d_rot, rot.data(), rot.size() * sizeof(float), hipMemcpyHostToDevice));
+    // one launch per 32 768 pixels (the grid's x dimension is not the limit; this bounds a launch's run time)
+    for (size_t p0 = 0; p0 < P; p0 += 32768) {
+        const int np = (int) std::min<size_t>(32768, P - p0);
+        AWPU_HIP_TRY(awpu::launch_delay_table(d_xyz, n, d_rot + p0 * 12, np, awpu::samples_per_metre(), d_off + p0 * n, d_frac + p0 * n,
+                                              nullptr));
+    }
+    AWPU_HIP_TRY(hipMemcpy(off, d_off, P * n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    AWPU_HIP_TRY(hipMemcpy(frac, d_frac, P * n * sizeof(float), hipMemcpyDeviceToHost));
+    return AWPU_OK;
 }
 
 int awpu_hip_get_stats(awpu_hip_t *h, awpu_hip_stats *stats) {
     AWPU_CTX(h);
     if (!h || !stats) return invalid("null argument");
-    if (!h->parts.empty()) return group_stats(h, stats);
+    if (is_group(h)) return group_stats(h, stats);
     *stats = h->stats;
     return AWPU_OK;
 }

@@ -16,29 +16,6 @@
 
 using namespace awpu::host;
 
-int awpu::host::BufferPair::ensure(size_t bytes, bool want_host, bool want_device) {
-    if (bytes == 0 || (cap >= bytes && (h[0] || !want_host) && (d[0] || !want_device))) return AWPU_OK;
-    want_host |= h[0] != nullptr;  // (what it held it keeps, at the new size)
-    want_device |= d[0] != nullptr;
-    bytes = std::max(bytes, cap);
-    release();
-    for (int b = 0; b < 2; b++) {
-        if (want_device) AWPU_HIP_TRY(hipMalloc(&d[b], bytes));
-        if (want_host) AWPU_HIP_TRY(hipHostMalloc(&h[b], bytes, hipHostMallocDefault));
-    }
-    cap = bytes;
-    return AWPU_OK;
-}
-
-void awpu::host::BufferPair::release() {
-    for (int b = 0; b < 2; b++) {
-        dev_free(d[b]);
-        if (h[b]) (void) hipHostFree(h[b]);
-        h[b] = nullptr;
-    }
-    cap = 0;
-}
-
 namespace {
 
 // where a run's samples come from
@@ -160,7 +137,7 @@ struct Consumer {
     ~Consumer() = default;
 };
 
-float *hist_of(awpu_hip *h, int b) { return reinterpret_cast<float *>(h->blk_hist.d[b]); }
+float *hist_of(awpu_hip *h, int b) { return reinterpret_cast<float *>(h->blk_hist.d[b].get()); }
 
 // the buffers every run needs for pieces of `piece` frames whose history and staging hold hist_blocks / in_blocks blocks (and,
 // for the host forms, the second stream and the events)
@@ -169,27 +146,21 @@ int ensure_run_buffers(awpu_hip *h, const BlockRun &src, int piece, int width, b
     int rc = h->blk_hist.ensure(S * (awpu::kBlockPrefix + (size_t) awpu::kSamples * hist_blocks) * sizeof(float), false);
     if (rc != AWPU_OK) return rc;
     const size_t frames_floats = sweep ? S * width * (size_t) piece : 0;  // (a listen run without heatmaps cuts no window)
-    if (h->blk_frames_cap < frames_floats) {
-        dev_free(h->d_blk_frames);
-        h->blk_frames_cap = 0;
-        AWPU_HIP_TRY(hipMalloc(&h->d_blk_frames, frames_floats * sizeof(float)));
-        h->blk_frames_cap = frames_floats;
-    }
-    if (!h->ev_blk_ring) AWPU_HIP_TRY(hipEventCreateWithFlags(&h->ev_blk_ring, hipEventDisableTiming));
+    if (rc = h->d_blk_frames.ensure(frames_floats); rc != AWPU_OK) return rc;
+    if (rc = h->ev_blk_ring.ensure(); rc != AWPU_OK) return rc;
     if (src.device) return AWPU_OK;
     rc = h->blk_in.ensure((size_t) awpu::kSamples * in_blocks * (src.wire ? (size_t) AWPU_DATAGRAM_BYTES : S * sizeof(float)), true);
     if (rc == AWPU_OK) rc = h->blk_out.ensure(sweep ? piece * P * sizeof(float) : 0, true, false);
+    if (rc == AWPU_OK) rc = h->copy_stream.ensure();
+    for (auto *pair : {h->ev_blk_in, h->ev_blk_hist, h->ev_blk_cut, h->ev_blk_swept, h->ev_blk_out})
+        for (int b = 0; b < 2 && rc == AWPU_OK; b++) rc = pair[b].ensure();
     if (rc != AWPU_OK) return rc;
-    if (!h->copy_stream) AWPU_HIP_TRY(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-    for (hipEvent_t *ev : {&h->ev_blk_in[0], &h->ev_blk_in[1], &h->ev_blk_hist[0], &h->ev_blk_hist[1], &h->ev_blk_cut[0],
-                           &h->ev_blk_cut[1], &h->ev_blk_swept[0], &h->ev_blk_swept[1], &h->ev_blk_out[0], &h->ev_blk_out[1]})
-        if (!*ev) AWPU_HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
     return sweep ? ensure_power(h, 2 * piece * P) : AWPU_OK;  // two pieces' powers: one swept, one on its way back
 }
 
 // the run; the host forms are synchronous, the device form runs on `user` (NULL = h->stream)
 int run_pieces(awpu_hip *h, const BlockRun &src, hipStream_t user, Consumer &c) {
-    if (!h->parts.empty()) return fail(AWPU_ERR_STATE, "a device group does not take runs of blocks");
+    if (is_group(h)) return fail(AWPU_ERR_STATE, "a device group does not take runs of blocks");
     if (h->in_flight) return fail(AWPU_ERR_STATE, "an awpu_hip_process_async call is in flight on this handle: awpu_hip_wait first");
     const awpu_hip_cfg &cfg = h->cfg;
     if (cfg.hist != AWPU_HIST) return invalid("runs of blocks need hist 1024");
@@ -405,20 +376,14 @@ struct BlockPieces final : Consumer {
         rc = ensure_track_index(h);
         if (rc != AWPU_OK) return rc;
         // the listeners' state, and for the host forms the way back of a piece's audio rows [n][256 * piece] and trail
-        if (h->listeners_cap < state) {
-            dev_free(h->d_listeners);
-            h->listeners_cap = 0;
-            AWPU_HIP_TRY(hipMalloc(&h->d_listeners, state));
-            h->listeners_cap = state;
-        }
+        if (rc = h->d_listeners.ensure(state); rc != AWPU_OK) return rc;
         if (!host) return AWPU_OK;
         rc = h->listen_out.ensure(audio_bytes(piece_max) + (size_t) piece_max * state, true);
         if (rc != AWPU_OK) return rc;
-        if (sweep && env().listen_stream && !h->listen_stream)
-            AWPU_HIP_TRY(hipStreamCreateWithFlags(&h->listen_stream, hipStreamNonBlocking));
-        for (hipEvent_t *ev : {&h->ev_listened[0], &h->ev_listened[1], &h->ev_listen_out[0], &h->ev_listen_out[1]})
-            if (!*ev) AWPU_HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
-        return AWPU_OK;
+        if (sweep && env().listen_stream) rc = h->listen_stream.ensure();
+        for (auto *pair : {h->ev_listened, h->ev_listen_out})
+            for (int b = 0; b < 2 && rc == AWPU_OK; b++) rc = pair[b].ensure();
+        return rc;
     }
     int begin(hipStream_t s) override {
         if (ls) AWPU_HIP_TRY(hipMemcpyAsync(h->d_listeners, ls->listeners, state, hipMemcpyHostToDevice, s));
@@ -435,7 +400,7 @@ struct BlockPieces final : Consumer {
         if (src.wire) {
             AWPU_HIP_TRY(awpu::launch_unpack_blocks(h->blk_in.d[p.b], p.n, S, hist, pitch, awpu::kBlockPrefix, s));
         } else {
-            const float *rows = host ? reinterpret_cast<const float *>(h->blk_in.d[p.b]) : src.samples + (size_t) p.first * awpu::kSamples;
+            const float *rows = host ? reinterpret_cast<const float *>(h->blk_in.d[p.b].get()) : src.samples + (size_t) p.first * awpu::kSamples;
             AWPU_HIP_TRY(awpu::launch_copy_rows(rows, host ? (long long) awpu::kSamples * p.n : (long long) src.pitch,
                                                 hist + awpu::kBlockPrefix, pitch, awpu::kSamples * p.n, S, s));
         }
@@ -461,7 +426,7 @@ struct BlockPieces final : Consumer {
         a.theta_limit = ls->theta_limit;
         a.reference = ls->reference;
         if (host) {
-            a.audio = reinterpret_cast<float *>(h->listen_out.d[p.b]);
+            a.audio = reinterpret_cast<float *>(h->listen_out.d[p.b].get());
             a.audio_pitch = (long long) awpu::kSamples * p.n;
             a.trail = ls->trail ? h->listen_out.d[p.b] + audio_bytes(p.n) : nullptr;
         } else {
@@ -617,7 +582,7 @@ struct WatchPieces final : Consumer {
             AWPU_HIP_TRY(awpu::launch_unpack_blocks(h->blk_in.d[p.b], g.slots - g.q, S, hist, pitch, awpu::kSamples * g.q, s));
         } else {
             const long long n = (long long) awpu::kSamples * (g.slots - g.q);
-            AWPU_HIP_TRY(awpu::launch_copy_rows(reinterpret_cast<const float *>(h->blk_in.d[p.b]), n, hist + awpu::kSamples * g.q, pitch, (int) n, S, s));
+            AWPU_HIP_TRY(awpu::launch_copy_rows(reinterpret_cast<const float *>(h->blk_in.d[p.b].get()), n, hist + awpu::kSamples * g.q, pitch, (int) n, S, s));
         }
         return AWPU_OK;
     }

@@ -18,21 +18,10 @@ using namespace awpu::host;
 
 namespace {
 
-// diagnostics buffer of `words` 64-bit words, grown on demand (one per handle: handles on different
-// devices, or launches of different sizes, must not share it)
-int ensure_diag(awpu_hip *h, size_t words) {
-    if (h->diag_cap >= words) return AWPU_OK;
-    dev_free(h->d_diag);
-    h->diag_cap = 0;
-    AWPU_HIP_TRY(hipMalloc(&h->d_diag, words * sizeof(unsigned long long)));
-    h->diag_cap = words;
-    return AWPU_OK;
-}
-
 // The bracket of a stamped build (AWPU_FAST_DEBUG=16, tuning builds).  Before the launch: `words` of the diagnostics buffer for the
 // kernel's stamps, zeroed on the stream where not every slot is written.
 int diag_begin(awpu_hip *h, size_t words, bool zero, hipStream_t s, unsigned long long **out) {
-    if (const int rc = ensure_diag(h, words); rc != AWPU_OK) return rc;
+    if (const int rc = h->d_diag.ensure(words); rc != AWPU_OK) return rc;  // (one per handle: devices, and launch sizes, differ)
     if (zero) AWPU_HIP_TRY(hipMemsetAsync(h->d_diag, 0, words * sizeof(unsigned long long), s));
     *out = h->d_diag;
     return AWPU_OK;
@@ -127,15 +116,7 @@ int dump_nd_timeline(awpu_hip *h, size_t n_wgs, hipStream_t s) {
 #endif
 
 // grow-only device buffer shared by the sweep shapes that pack frames (pairs, quads, FIR8 planes)
-int ensure_pack(awpu_hip *h, size_t need) {
-    if (h->pack_cap >= need) return AWPU_OK;
-    retire_live_graphs(h);
-    dev_free(h->d_pack);
-    h->pack_cap = 0;
-    AWPU_HIP_TRY(hipMalloc(&h->d_pack, need * sizeof(float)));
-    h->pack_cap = need;
-    return AWPU_OK;
-}
+int ensure_pack(awpu_hip *h, size_t need) { return ensure_seen_by_live_graphs(h, h->d_pack, need); }
 
 }  // namespace
 
@@ -144,12 +125,11 @@ namespace awpu::host {
 // every table prepare() and the launchers build from the delay table and the active-mic list.  (hipFree waits for the device:
 // launches still reading the old tables finish first.)
 void free_tables(awpu_hip *h) {
-    dev_free(h->d_lut);
-    for (auto &l : h->fast_luts) dev_free(l.d);
+    h->d_lut.release();
     h->fast_luts.clear();
-    dev_free(h->d_exact_pair_lut);
-    for (QuadTable &q : h->quad_tables) dev_free(q.d);
-    dev_free(h->d_fir_plane_lut);
+    h->d_exact_pair_lut.release();
+    for (QuadTable &q : h->quad_tables) q.d.release();
+    h->d_fir_plane_lut.release();
 }
 
 // Pack the reference-format tables into the kernels' layout once both the tables and the
@@ -181,45 +161,44 @@ int prepare(awpu_hip *h) {
     h->tau_max = awpu::kSamples - lo;
 
     free_tables(h);
-    dev_free(h->d_index);
+    h->d_index.release();
     h->identity_mics = true;  // the active-mic list is 0 .. usable-1 (awpu_hip_set_active_mics(NULL)): rows need no look-up
     for (int k = 0; k < U && h->identity_mics; k++) h->identity_mics = h->index[k] == k;
-    AWPU_HIP_TRY(hipMalloc(&h->d_index, (size_t) U * sizeof(int32_t)));
+    if (const int rc = h->d_index.grow((size_t) U); rc != AWPU_OK) return rc;
     AWPU_HIP_TRY(hipMemcpy(h->d_index, h->index.data(), (size_t) U * sizeof(int32_t),
                            hipMemcpyHostToDevice));
-    dev_free(h->d_gain);
+    h->d_gain.release();
     if (!h->gain.empty()) {
         std::vector<float> compact(U);
         for (int s = 0; s < U; s++) compact[s] = h->gain[h->index[s]];
-        AWPU_HIP_TRY(hipMalloc(&h->d_gain, (size_t) U * sizeof(float)));
+        if (const int rc = h->d_gain.grow((size_t) U); rc != AWPU_OK) return rc;
         AWPU_HIP_TRY(hipMemcpy(h->d_gain, compact.data(), (size_t) U * sizeof(float), hipMemcpyHostToDevice));
     }
     {   // float offset, inside one frame, of staged row 2*s+q (copy q of active mic s)
-        dev_free(h->d_row_off);
+        h->d_row_off.release();
         const int upad = (U + 3) & ~3;
         std::vector<int32_t> ro((size_t) 2 * upad + 8, h->index[0] * c.hist + lo);
         for (int s = 0; s < U; s++)
             for (int q = 0; q < 2; q++) ro[2 * s + q] = h->index[s] * c.hist + lo + q;
-        AWPU_HIP_TRY(hipMalloc(&h->d_row_off, ro.size() * sizeof(int32_t)));
+        if (const int rc = h->d_row_off.grow(ro.size()); rc != AWPU_OK) return rc;
         AWPU_HIP_TRY(hipMemcpy(h->d_row_off, ro.data(), ro.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         // Host-buffer calls upload only the window [lo, lo + compact_hist) of every stream (the rest
         // of the 1024-sample snapshot is never read: SURVEY 8a A10): a third of the PCIe bytes.
-        dev_free(h->d_row_off_compact);
+        h->d_row_off_compact.release();
         const int ch = ((h->window + 3) & ~3) + 4;
         h->compact_hist = lo + ch <= c.hist ? ch : 0;
         if (c.hist == AWPU_HIST) {  // frames read in place from the ingest ring: rows 2048 floats apart
-            dev_free(h->d_row_off_ring);
             std::vector<int32_t> rr(ro.size(), h->index[0] * 2048 + lo);
             for (int s = 0; s < U; s++)
                 for (int q = 0; q < 2; q++) rr[2 * s + q] = h->index[s] * 2048 + lo + q;
-            AWPU_HIP_TRY(hipMalloc(&h->d_row_off_ring, rr.size() * sizeof(int32_t)));
+            if (const int rc = h->d_row_off_ring.grow(rr.size()); rc != AWPU_OK) return rc;
             AWPU_HIP_TRY(hipMemcpy(h->d_row_off_ring, rr.data(), rr.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         }
         if (h->compact_hist) {
             for (int s = 0; s < U; s++)
                 for (int q = 0; q < 2; q++) ro[2 * s + q] = h->index[s] * h->compact_hist + q;
             for (size_t i = 2 * (size_t) U; i < ro.size(); i++) ro[i] = h->index[0] * h->compact_hist;
-            AWPU_HIP_TRY(hipMalloc(&h->d_row_off_compact, ro.size() * sizeof(int32_t)));
+            if (const int rc = h->d_row_off_compact.grow(ro.size()); rc != AWPU_OK) return rc;
             AWPU_HIP_TRY(hipMemcpy(h->d_row_off_compact, ro.data(), ro.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         }
     }
@@ -254,7 +233,7 @@ int prepare(awpu_hip *h) {
                 }
             }
         }
-        AWPU_HIP_TRY(hipMalloc(&h->d_lut, packed.size() * sizeof(awpu::LutEntry)));
+        if (const int rc = h->d_lut.grow(packed.size()); rc != AWPU_OK) return rc;
         AWPU_HIP_TRY(hipMemcpy(h->d_lut, packed.data(), packed.size() * sizeof(awpu::LutEntry),
                                hipMemcpyHostToDevice));
     } else {
@@ -388,11 +367,11 @@ int build_fast_lut(awpu_hip *h, int fpi, int image_bytes, const awpu_hip::FastLu
                                 : (uint32_t) ((j * 2 + q) * plan.row_bytes + (off_rel - q) * 4);
         }
     }
-    AWPU_HIP_TRY(hipMalloc(&lut.d, n * sizeof(awpu::FastEntry)));
+    if (const int rc = lut.d.grow(n); rc != AWPU_OK) return rc;
     AWPU_HIP_TRY(hipMemcpy(lut.d, packed.data(), n * sizeof(awpu::FastEntry), hipMemcpyHostToDevice));
     lut.entries = n;
     h->fast_luts.reserve(8);
-    h->fast_luts.push_back(lut);
+    h->fast_luts.push_back(std::move(lut));
     *out = &h->fast_luts.back();
     return AWPU_OK;
 }
@@ -441,7 +420,7 @@ int build_quad_lut(awpu_hip *h, QuadLayout layout) {
                 }
             }
         }
-    AWPU_HIP_TRY(hipMalloc(&table.d, n * sizeof(awpu::QuadEntry)));
+    if (const int rc = table.d.grow(n); rc != AWPU_OK) return rc;
     AWPU_HIP_TRY(hipMemcpy(table.d, packed.data(), n * sizeof(awpu::QuadEntry), hipMemcpyHostToDevice));
     table.entries = n;
     return AWPU_OK;
@@ -470,7 +449,7 @@ int build_exact_pair_lut(awpu_hip *h) {
             dst[s].addr = (uint32_t) ((s % plan.chunk) * plan.row_bytes + (orow[id] - h->wstart) * 8);
         }
     }
-    AWPU_HIP_TRY(hipMalloc(&h->d_exact_pair_lut, n * sizeof(awpu::FastEntry)));
+    if (const int rc = h->d_exact_pair_lut.grow(n); rc != AWPU_OK) return rc;
     AWPU_HIP_TRY(hipMemcpy(h->d_exact_pair_lut, packed.data(), n * sizeof(awpu::FastEntry), hipMemcpyHostToDevice));
     h->exact_pair_lut_entries = n;
     return AWPU_OK;
@@ -497,7 +476,7 @@ int build_fir8_plane_lut(awpu_hip *h) {
             packed[(size_t) p * row_entries + m] = awpu::fir8_plane_word(addr, first & 3, (uint32_t) k);
         }
     }
-    AWPU_HIP_TRY(hipMalloc(&h->d_fir_plane_lut, packed.size() * sizeof(uint32_t)));
+    if (const int rc = h->d_fir_plane_lut.grow(packed.size()); rc != AWPU_OK) return rc;
     AWPU_HIP_TRY(hipMemcpy(h->d_fir_plane_lut, packed.data(), packed.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     h->fir_plane_lut_entries = packed.size();
     return AWPU_OK;
@@ -568,7 +547,7 @@ int xcd_pair_group(size_t pair_bytes, int n_pairs, int forced = 0) {
 // Persistent workgroups (one per CU) that take their `items` from queues, one per XCD: an eighth of every XCD's run goes to the
 // queue common to the chip (the XCDs' speeds differ by ~6 %); short runs: one queue for the chip.
 int arm_item_queues(awpu_hip *h, int items, unsigned **queue, int32_t *wgs, int32_t *tail) {
-    if (!h->d_nd_queue) AWPU_HIP_TRY(hipMalloc(&h->d_nd_queue, 9 * sizeof(unsigned)));
+    if (const int rc = h->d_nd_queue.ensure(9); rc != AWPU_OK) return rc;
     *queue = h->d_nd_queue;
     *wgs = cu_count(h);
     const int per = (items + 7) / 8;
@@ -608,7 +587,7 @@ int launch_exact_pairs(awpu_hip *h, const float *d_frames, int batch, float *d_p
     if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
     AWPU_HIP_TRY(awpu::launch_pack_pairs(d_frames, h->cfg.n_streams, hist_eff, wstart_eff, h->d_index, h->usable(), pp.usable_pad,
                                          h->d_gain, pp.wr, batch, h->d_pack, false, s));  // raw samples: no stencil in front of the reference's order
-    AWPU_HIP_TRY(awpu::launch_das_exact_pairs(a, {h->exact_pair_lut_entries, h->pack_cap}, s));
+    AWPU_HIP_TRY(awpu::launch_das_exact_pairs(a, {h->exact_pair_lut_entries, h->d_pack.cap}, s));
     return finish_launch(h, batch, s, AWPU_KERNEL_EXACT_PAIR);
 }
 
@@ -632,7 +611,7 @@ int launch_exact_quads(awpu_hip *h, const float *d_frames, int batch, float *d_p
     if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
     AWPU_HIP_TRY(awpu::launch_pack_pairs(d_frames, h->cfg.n_streams, hist_eff, wstart_eff, h->d_index, h->usable(), pp.usable_pad,
                                          h->d_gain, pp.wr, batch, h->d_pack, false, s));
-    AWPU_HIP_TRY(awpu::launch_das_exact_quads(a, {table.entries, h->pack_cap}, s));
+    AWPU_HIP_TRY(awpu::launch_das_exact_quads(a, {table.entries, h->d_pack.cap}, s));
     return finish_launch(h, batch, s, AWPU_KERNEL_EXACT_QUAD);
 }
 
@@ -660,13 +639,10 @@ int launch_exact_nd(awpu_hip *h, const float *d_frames, int batch, float *d_powe
     {   // the item list: rebuilt (by the launcher, on the stream) when the batch, the pair group or the tile shape changed
         const size_t items = (size_t) a.n_pairs * a.tiles;
         const long long key = ((long long) a.n_pairs << 24) | ((long long) a.pair_group << 8) | nq;
-        if (h->nd_items_cap < items) {
+        if (!h->d_nd_items.holds(items)) {
             retire_live_graphs(h);
             AWPU_HIP_TRY(hipStreamSynchronize(s));  // (a sweep in flight may still read the old list)
-            dev_free(h->d_nd_items);
-            h->nd_items_cap = 0;
-            AWPU_HIP_TRY(hipMalloc(&h->d_nd_items, items * sizeof(int2)));
-            h->nd_items_cap = items;
+            if (rc = h->d_nd_items.grow(items); rc != AWPU_OK) return rc;
             h->nd_items_key = -1;
         }
         a.items = h->d_nd_items;
@@ -689,7 +665,7 @@ int launch_exact_nd(awpu_hip *h, const float *d_frames, int batch, float *d_powe
     if (env().debug & 16)  // per-workgroup timeline (where, when, phases)
         if (const int drc = diag_begin(h, n_wgs * 8, true, s, &a.debug_out); drc != AWPU_OK) return drc;
 #endif
-    AWPU_HIP_TRY(awpu::launch_das_exact_nd(a, {table.entries, prepacked ? prepacked_floats : h->pack_cap}, s));
+    AWPU_HIP_TRY(awpu::launch_das_exact_nd(a, {table.entries, prepacked ? prepacked_floats : h->d_pack.cap}, s));
     rc = finish_launch(h, batch, s, AWPU_KERNEL_EXACT_ND);
 #ifdef AWPU_TUNING_BUILD
     if (rc == AWPU_OK && (env().debug & 16)) return dump_nd_timeline(h, n_wgs, s);
@@ -718,10 +694,10 @@ bool takes_exact_nd(awpu_hip *h, int batch, int *nq) {
 // next armed launch of `workgroups` workgroups gets, and what the handle remembers once that launch has gone out.
 int arm_done_flag(awpu_hip *h, unsigned long long workgroups, awpu::DoneFlag *out) {
     if (!h->d_done_counter) {
-        AWPU_HIP_TRY(hipMalloc(&h->d_done_counter, sizeof(unsigned long long)));
+        if (const int rc = h->d_done_counter.grow(1); rc != AWPU_OK) return rc;
         AWPU_HIP_TRY(hipMemsetAsync(h->d_done_counter, 0, sizeof(unsigned long long), h->stream));
         AWPU_HIP_TRY(hipStreamSynchronize(h->stream));  // (the handle's own stream: nothing device-wide from inside a sweep call)
-        AWPU_HIP_TRY(hipHostMalloc(&h->h_done_flag, 64, hipHostMallocDefault));
+        if (const int rc = h->h_done_flag.grow(16); rc != AWPU_OK) return rc;  // (a cache line of its own)
         *h->h_done_flag = 0;
         h->done_total = 0;
     }
@@ -777,9 +753,9 @@ int launch_exact_ndh(awpu_hip *h, const float *d_frames, int batch, float *d_pow
         AWPU_HIP_TRY(awpu::launch_pack_ndh(d_frames, h->cfg.n_streams, pitch, wstart_eff, a.identity ? nullptr : h->d_index, h->usable(), pp.usable_pad, h->d_gain, pp.wr,
                                            batch, h->d_pack, s));
     if (pixel_per_wave) {
-        AWPU_HIP_TRY(awpu::launch_das_exact_ndp(a, {table.entries, h->pack_cap}, s));
+        AWPU_HIP_TRY(awpu::launch_das_exact_ndp(a, {table.entries, h->d_pack.cap}, s));
     } else {
-        AWPU_HIP_TRY(awpu::launch_das_exact_ndh(a, stationary, {table.entries, stationary ? 0 : h->pack_cap}, s));
+        AWPU_HIP_TRY(awpu::launch_das_exact_ndh(a, stationary, {table.entries, stationary ? 0 : h->d_pack.cap}, s));
     }
     if (a.done.flag) done_flag_armed(h, a.done);  // (the launch went out: its workgroups will count themselves)
     return finish_launch(h, batch, s, pixel_per_wave ? AWPU_KERNEL_EXACT_NDP : stationary ? AWPU_KERNEL_EXACT_NDH_STATIONARY : AWPU_KERNEL_EXACT_NDH);
@@ -825,7 +801,7 @@ int launch_fir8_planes(awpu_hip *h, const float *d_frames, int batch, float *d_p
     if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
     AWPU_HIP_TRY(awpu::launch_pack_planes(d_frames, h->cfg.n_streams, hist_eff, wstart_eff, h->d_index, U, h->d_gain, pp.wr,
                                           batch, h->d_pack, s));
-    AWPU_HIP_TRY(awpu::launch_das_fir8_planes(pa, h->d_fir_plane_lut, h->d_fir, env().quad_variant, {h->fir_plane_lut_entries, h->pack_cap}, s));
+    AWPU_HIP_TRY(awpu::launch_das_fir8_planes(pa, h->d_fir_plane_lut, h->d_fir, env().quad_variant, {h->fir_plane_lut_entries, h->d_pack.cap}, s));
     return finish_launch(h, batch, s, AWPU_KERNEL_FIR8_PLANES);
 }
 
@@ -865,7 +841,7 @@ int launch_pairs(awpu_hip *h, const awpu_hip::FastLut *plut, const float *d_fram
     if (!prepacked && !self_staged)
         AWPU_HIP_TRY(awpu::launch_pack_pairs(d_frames, h->cfg.n_streams, hist_eff, wstart_eff, h->d_index, h->usable(),
                                              h->usable(), nullptr, pp.wr, batch, h->d_pack, true, s));  // gains ride on the table weights here
-    const awpu::Extents have{plut->entries, prepacked ? prepacked_floats : h->pack_cap};
+    const awpu::Extents have{plut->entries, prepacked ? prepacked_floats : h->d_pack.cap};
     if (stationary_tiles > 0) {
         AWPU_HIP_TRY(awpu::launch_das_pairs_stationary(pa, stationary_tiles, have, s));
     } else {
@@ -914,7 +890,7 @@ int launch_quads(awpu_hip *h, const float *d_frames, int batch, float *d_power, 
     if (!prepacked)
         AWPU_HIP_TRY(awpu::launch_pack_pairs(d_frames, h->cfg.n_streams, hist_eff, wstart_eff, h->d_index, h->usable(),
                                              pp.usable_pad, h->d_gain, pp.wr, batch, h->d_pack, true, s));
-    AWPU_HIP_TRY(awpu::launch_das_quads(qa, {table.entries, prepacked ? prepacked_floats : h->pack_cap}, s));
+    AWPU_HIP_TRY(awpu::launch_das_quads(qa, {table.entries, prepacked ? prepacked_floats : h->d_pack.cap}, s));
     return diag_end(h, finish_launch(h, batch, s, AWPU_KERNEL_QUAD), n_waves, 16, "quads", s);
 }
 
@@ -943,7 +919,7 @@ int launch_quadsh(awpu_hip *h, const float *d_frames, int batch, float *d_power,
     if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
     AWPU_HIP_TRY(awpu::launch_pack_halves(d_frames, h->cfg.n_streams, pitch, hist_eff, wstart_eff, h->identity_mics ? nullptr : h->d_index, h->usable(),
                                           pp.usable_pad, h->d_gain, pp.wr, batch, h->d_pack, s));
-    AWPU_HIP_TRY(awpu::launch_das_quadh(qa, qpw, {table.entries, h->pack_cap}, s));
+    AWPU_HIP_TRY(awpu::launch_das_quadh(qa, qpw, {table.entries, h->d_pack.cap}, s));
     return diag_end(h, finish_launch(h, batch, s, AWPU_KERNEL_QUADH), n_waves, 16, "quadsh", s);
 }
 
