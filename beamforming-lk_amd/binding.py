@@ -707,7 +707,7 @@ class Engine:
 
     def process_device_sums(self, d_frames_ptr: int, batch: int, d_power_ptr: int, d_sums_ptr: int, stream: int = 0) -> None:
         """process_device plus every pixel's out[0..255] before the epilogue into d_sums [batch, pixels, 256]
-        (awpu_hip_process_device_sums: MATH_F32_EXACT + INTERP_LERP only; bit-identical to the reference's out[])."""
+        (awpu_hip_process_device_sums: MATH_F32_EXACT only, either interpolation; bit-identical to the reference's out[])."""
         _check(self._lib.awpu_hip_process_device_sums(self._h, C.c_void_p(d_frames_ptr), batch, C.c_void_p(d_power_ptr),
                                                       C.c_void_p(d_sums_ptr), C.c_void_p(stream)),
                "awpu_hip_process_device_sums")

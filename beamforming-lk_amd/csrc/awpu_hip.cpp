@@ -866,7 +866,8 @@ int awpu_hip_process_device_sums(awpu_hip_t *h, const float *d_frames, int32_t b
     if (is_group(h)) return invalid("the pre-epilogue sums are exported by single-device handles only");
     const int rc = check_ready(h, batch);
     if (rc != AWPU_OK) return rc;
-    if (!h->exact_pairs_ok) return fail(AWPU_ERR_STATE, "the pre-epilogue sums need AWPU_MATH_F32_EXACT with AWPU_INTERP_LERP");
+    const bool exact_fir8 = h->cfg.math == AWPU_MATH_F32_EXACT && h->cfg.interp == AWPU_INTERP_FIR8;  // das_fir8_kernel, the reference's rounding
+    if (!h->exact_pairs_ok && !exact_fir8) return fail(AWPU_ERR_STATE, "the pre-epilogue sums need AWPU_MATH_F32_EXACT");
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
     TimingOff untimed(h);
     h->sums_out = d_sums;

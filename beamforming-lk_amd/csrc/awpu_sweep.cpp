@@ -768,6 +768,7 @@ int launch_exact(awpu_hip *h, const float *d_frames, int batch, float *d_power, 
     a.index = h->d_index;
     a.power = d_power;
     a.gain = h->d_gain;
+    a.sums = h->sums_out;  // (choose_shape: EXACT + FIR8 only)
     a.n_streams = h->cfg.n_streams;
     a.hist = hist_eff;
     a.usable = h->usable();
@@ -777,7 +778,9 @@ int launch_exact(awpu_hip *h, const float *d_frames, int batch, float *d_power, 
     a.batch = batch;
     if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
     if (h->cfg.interp == AWPU_INTERP_FIR8) {
-        AWPU_HIP_TRY(awpu::launch_das_fir8(a, h->d_fir, s));
+        // AWPU_MATH_F32_EXACT: the reference's rounding, a multiply and an add per tap; AWPU_MATH_F32_FAST (a launch too small for the
+        // plane kernel): one FMA per tap
+        AWPU_HIP_TRY(awpu::launch_das_fir8(a, h->d_fir, h->cfg.math == AWPU_MATH_F32_EXACT, s));
     } else {
         AWPU_HIP_TRY(awpu::launch_das_exact(a, h->cfg.math == AWPU_MATH_BF16_ACC, s));
     }
@@ -1069,7 +1072,8 @@ ShapeChoice choose_shape(awpu_hip *h, int batch, int layout, int hist_eff, int w
         if (ex == 3 && h->pair_cols > 0 && rows >= 4) return {kShapeExactQuads};
         return {kShapeExactPairs};
     }
-    if (h->sums_out) return {kShapeNone};  // (the pre-epilogue sums: the frame-pair reference-order kernels only)
+    // (the pre-epilogue sums: the frame-pair reference-order kernels above and das_fir8_kernel with the reference's rounding only)
+    if (h->sums_out && !(c.math == AWPU_MATH_F32_EXACT && c.interp == AWPU_INTERP_FIR8)) return {kShapeNone};
     if (c.math != AWPU_MATH_F32_FAST || c.interp == AWPU_INTERP_FIR8) return {kShapeExact};
 
     // ---- frame-pair shapes: batches on grids that fill the chip (AWPU_FAST_PAIRS=0/1 overrides), never off the ring
@@ -1160,7 +1164,7 @@ int launch(awpu_hip *h, const float *d_frames, int batch, float *d_power, hipStr
     case kShapeSingle: return launch_single(h, d_frames, batch, d_power, s, layout, hist_eff, wstart_eff, c.fpi, c.ppw, c.nw);
     case kShapeNone: break;
     }
-    return fail(AWPU_ERR_STATE, "the pre-epilogue sums are exported by the frame-pair reference-order kernel only");
+    return fail(AWPU_ERR_STATE, "the pre-epilogue sums are exported by the frame-pair reference-order kernels and the reference-rounding FIR8 kernel only");
 }
 
 // Would launch() sweep this batch with one of the frame-pair shapes that read the packed layout (quad or pair)?  The rule of

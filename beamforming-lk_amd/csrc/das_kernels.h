@@ -38,6 +38,7 @@ struct SweepArgs {
     const int32_t *index;  // [usable] stream id per active mic
     float *power;          // [batch][pixel_count]
     const float *gain;     // [usable] per-mic gain applied while staging, or nullptr (the reference has none)
+    float *sums;           // das_fir8_kernel with the reference's rounding only: optional [batch][pixel_count][256], out[] before the epilogue (tests), or null
     int32_t n_streams;
     int32_t hist;
     int32_t usable;
@@ -318,8 +319,9 @@ bool fast_db_fits(const FastPlan &plan);
 hipError_t launch_das_exact(const SweepArgs &a, bool bf16_accumulator, hipStream_t stream);
 
 // FIR8 variant: LutEntry.frac holds the coefficient-row index k as an int bit pattern; window
-// must cover off + 263.  d_coeffs = [101][8] floats on the device.
-hipError_t launch_das_fir8(const SweepArgs &a, const float *d_coeffs, hipStream_t stream);
+// must cover off + 263.  d_coeffs = [101][8] floats on the device.  reference_rounding: a multiply and an add per
+// tap (the sums are the reference build's bits; a.sums may export them), else one FMA per tap (a.sums must be null).
+hipError_t launch_das_fir8(const SweepArgs &a, const float *d_coeffs, bool reference_rounding, hipStream_t stream);
 
 // populateHeatmap on the device: d_peak[batch] receives (or, if peak_given, supplies) the per-frame
 // maximum; d_pix[batch][n] the 8-bit image.

@@ -126,12 +126,17 @@ __global__ __launch_bounds__(kExactThreads) void das_exact_kernel(SweepArgs a, i
 //     k = (int)(frac * 100 + 0.5);  out[n] += sum_{t<8} C[k][t] * X[off + n + t]
 // inside the same sweep and epilogue (mimo.cpp:121-151).  Not compiled in the reference's shipped
 // configuration (-mavx2 selects the linear variant); provided for completeness, same structure as
-// the exact kernel: lane l owns samples l+64k, taps accumulate in the reference's order
-// t = 0..7 (one FMA per tap where the reference has a multiply and an add).  The table entry
-// carries k (computed on the host with the reference's expression); the 8 coefficients of a
-// (pixel, mic) are wave-uniform and arrive by one scalar load.
+// the exact kernel: lane l owns samples l+64k, taps accumulate in the reference's order t = 0..7, mics in
+// index[] order.  The table entry carries k (computed on the host with the reference's expression); the 8
+// coefficients of a (pixel, mic) are wave-uniform and arrive by one scalar load.
+// REF_ROUNDING (AWPU_MATH_F32_EXACT): the reference's rounding as well -- the build that selects this delay() has
+// no FMA, so per tap it rounds the product and then the add into out[n]: p = c[t] * x; acc = acc + p, contraction
+// off.  The sums before the epilogue are then that build's out[] bit for bit, on any input (a.sums exports them:
+// [batch][pixel_count][256], lane l writing samples l + 64k).  Without it (AWPU_MATH_F32_FAST on launches too small
+// for das_fir8_plane_kernel): one FMA per tap -- one rounding where the reference has two; within 1e-5 of its
+// powers on zero-mean frames, not on biased ones (tests/test_gpu_parity.py records the error per offset).
 // ---------------------------------------------------------------------------------------
-template <int PPW>
+template <int PPW, bool REF_ROUNDING>
 __global__ __launch_bounds__(kExactThreads) void das_fir8_kernel(SweepArgs a, const float *coeffs, int chunk) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane = threadIdx.x & 63;
@@ -168,10 +173,21 @@ __global__ __launch_bounds__(kExactThreads) void das_fir8_kernel(SweepArgs a, co
                     const LutEntry e = row[m];
                     const float *c = coeffs + 8 * __float_as_int(e.frac);  // .frac carries the row index k
                     const float *x = lds + m * W + e.off_rel + lane;
+                    if constexpr (REF_ROUNDING) {
+#pragma clang fp contract(off)  // hipcc contracts a*b+c by default; the reference's x86 code rounds the product, then the sum
 #pragma unroll
-                    for (int k = 0; k < 4; k++)
+                        for (int k = 0; k < 4; k++)
 #pragma unroll
-                        for (int t = 0; t < 8; t++) acc[pp][k] = __builtin_fmaf(c[t], x[64 * k + t], acc[pp][k]);
+                            for (int t = 0; t < 8; t++) {
+                                const float prod = c[t] * x[64 * k + t];
+                                acc[pp][k] = acc[pp][k] + prod;
+                            }
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < 4; k++)
+#pragma unroll
+                            for (int t = 0; t < 8; t++) acc[pp][k] = __builtin_fmaf(c[t], x[64 * k + t], acc[pp][k]);
+                    }
                 }
             }
         }
@@ -180,19 +196,29 @@ __global__ __launch_bounds__(kExactThreads) void das_fir8_kernel(SweepArgs a, co
     for (int pp = 0; pp < PPW; pp++) {
         const int p = pix0 + pp;
         if (p < a.pixel_count) {
+            if constexpr (REF_ROUNDING) {
+                if (a.sums) {  // (tests: out[] before the moving average)
+                    float *o = a.sums + ((size_t) b * a.pixel_count + p) * kSamples + lane;
+#pragma unroll
+                    for (int k = 0; k < 4; k++) o[64 * k] = acc[pp][k];
+                }
+            }
             const float sum = epilogue_interleaved(acc[pp], lane);
             if (lane == 0) a.power[(size_t) b * a.pixel_count + p] = sum / (float) (kSamples * a.usable);
         }
     }
 }
 
-hipError_t launch_das_fir8(const SweepArgs &a, const float *d_coeffs, hipStream_t stream) {
+hipError_t launch_das_fir8(const SweepArgs &a, const float *d_coeffs, bool reference_rounding, hipStream_t stream) {
     int chunk = 0;
     const size_t lds = das_exact_lds_bytes(a.window, a.usable, &chunk);
-    if (lds == 0) return hipErrorInvalidValue;
+    if (lds == 0 || (a.sums && !reference_rounding)) return hipErrorInvalidValue;
     const int pix_per_block = (kExactThreads / 64) * kExactPPW;
     dim3 grid((a.pixel_count + pix_per_block - 1) / pix_per_block, a.batch);
-    hipLaunchKernelGGL(das_fir8_kernel<kExactPPW>, grid, dim3(kExactThreads), lds, stream, a, d_coeffs, chunk);
+    if (reference_rounding)
+        hipLaunchKernelGGL((das_fir8_kernel<kExactPPW, true>), grid, dim3(kExactThreads), lds, stream, a, d_coeffs, chunk);
+    else
+        hipLaunchKernelGGL((das_fir8_kernel<kExactPPW, false>), grid, dim3(kExactThreads), lds, stream, a, d_coeffs, chunk);
     return hipGetLastError();
 }
 

@@ -253,9 +253,11 @@ int awpu_hip_process_device(awpu_hip_t *h, const float *d_frames, int32_t batch,
 
 /* Verification export (no reference counterpart; the reference's `float out[N_SAMPLES]` of src/dsp/mimo.cpp:122 is a local):
  * the same sweep with every pixel's out[0..255] AFTER the last mic's delay() and BEFORE the moving average of
- * mimo.cpp:131-137 also written to d_sums [batch][pixel_count][256].  AWPU_MATH_F32_EXACT + AWPU_INTERP_LERP on a
- * single-device handle only (AWPU_ERR_STATE otherwise): those sums are bit-identical to what the reference's delay()
- * leaves in out[] (tests/test_gpu_parity.py checks them against the goldens its compiled object code produced). */
+ * mimo.cpp:131-137 also written to d_sums [batch][pixel_count][256].  AWPU_MATH_F32_EXACT on a single-device handle
+ * only (AWPU_ERR_STATE otherwise; AWPU_MATH_F32_FAST has an order of its own, with either interpolation): those sums are
+ * bit-identical to what the reference's delay() leaves in out[] -- with AWPU_INTERP_LERP the AVX2 build's, with
+ * AWPU_INTERP_FIR8 the 8-tap build's, which rounds a product and an add per tap (tests/test_gpu_parity.py checks both
+ * against the goldens the compiled object code produced, DC-biased frames included). */
 int awpu_hip_process_device_sums(awpu_hip_t *h, const float *d_frames, int32_t batch, float *d_power, float *d_sums,
                                  void *stream);
 

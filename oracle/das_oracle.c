@@ -161,7 +161,9 @@ void oracle_delay_lerp(float *out, const float *signal, float fraction) {
     }
 }
 
-/* src/dsp/delay.cpp:31-40 */
+/* src/dsp/delay.cpp:31-40.  The build that selects this variant has no FMA (no -mavx2 / -mfma) and keeps the source's
+ * order: product, then the add into out[n], i = 0..7.  With -ffp-contract=off this loop leaves the reference object
+ * code's bits in out[] (tests/test_oracle_golden.py, on the known answers and on whole sweeps). */
 void oracle_delay_fir8(float *out, const float *signal, float fraction, const float *coeffs) {
     const float get_filter = fraction * 100.0f + 0.5f;
     const int delay_int = (int) get_filter;
@@ -232,7 +234,7 @@ void oracle_particle_beams(const float *X, int hist, const int32_t *off, const f
 
 void oracle_das_fir8_f32(const float *X, int hist, const int32_t *off, const float *frac, int P,
                          int lut_stride, const int32_t *index, int usable, const float *coeffs,
-                         float *power) {
+                         float *power, float *out_dbg) {
     for (int m = 0; m < P; m++) {
         float out[ORACLE_N_SAMPLES] = {0.0f};
         int count = 0;
@@ -242,6 +244,7 @@ void oracle_das_fir8_f32(const float *X, int hist, const int32_t *off, const flo
                               frac[(size_t) m * lut_stride + i], coeffs);
             count++;
         }
+        if (out_dbg) memcpy(out_dbg + (size_t) m * ORACLE_N_SAMPLES, out, sizeof(out));
         power[m] = epilogue_f32(out, count);
     }
 }

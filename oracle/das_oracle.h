@@ -83,10 +83,12 @@ void oracle_das_bf16acc(const float *X, int hist, const int32_t *off, const floa
 /* same with every sum in fp64 (inputs still the fp32 tables). */
 void oracle_das_f64(const float *X, int hist, const int32_t *off, const float *frac, int P,
                     int lut_stride, const int32_t *index, int usable, double *power);
-/* FIR8 interpolation variant of the sweep (delay.cpp:31-40 inside mimo.cpp:121-151). */
+/* FIR8 interpolation variant of the sweep (delay.cpp:31-40 inside mimo.cpp:121-151): per tap a multiply, then an
+ * add into out[n], taps i = 0..7 in order -- what the reference's non-AVX2 build does (no FMA there), so out_dbg
+ * (optional [P][256] pre-epilogue sums, NULL to skip) is bit-identical to that build's out[]. */
 void oracle_das_fir8_f32(const float *X, int hist, const int32_t *off, const float *frac, int P,
                          int lut_stride, const int32_t *index, int usable, const float *coeffs,
-                         float *power);
+                         float *power, float *out_dbg);
 /* the same with every sum in double (tie-breaker only) */
 void oracle_das_fir8_f64(const float *X, int hist, const int32_t *off, const float *frac, int P,
                          int lut_stride, const int32_t *index, int usable, const float *coeffs,

@@ -67,7 +67,7 @@ def oracle() -> C.CDLL:
         lib.oracle_das_bf16acc.argtypes = [_f32p, C.c_int, _i32p, _f32p, C.c_int, C.c_int, _i32p, C.c_int, _f32p]
         lib.oracle_das_bf16acc.restype = None
         lib.oracle_das_f64.argtypes = [_f32p, C.c_int, _i32p, _f32p, C.c_int, C.c_int, _i32p, C.c_int, _f64p]
-        lib.oracle_das_fir8_f32.argtypes = [_f32p, C.c_int, _i32p, _f32p, C.c_int, C.c_int, _i32p, C.c_int, _f32p, _f32p]
+        lib.oracle_das_fir8_f32.argtypes = [_f32p, C.c_int, _i32p, _f32p, C.c_int, C.c_int, _i32p, C.c_int, _f32p, _f32p, _f32p]
         lib.oracle_das_fir8_f64.argtypes = [_f32p, C.c_int, _i32p, _f32p, C.c_int, C.c_int, _i32p, C.c_int, _f32p, _f64p]
         lib.oracle_particle_beams.argtypes = [_f32p, C.c_int, _i32p, _f32p, C.c_int, C.c_int, _i32p, C.c_int, _f32p, _f32p]
         lib.oracle_particle_beams.restype = None
@@ -225,9 +225,10 @@ def das_f64(X, off, frac, index=None) -> np.ndarray:
     return power
 
 
-def das_fir8_f32(X, off, frac, coeffs, index=None, impl="oracle"):
-    """FIR8 sweep (delay.cpp:31-40 inside mimo.cpp:121-151); impl = oracle | ref (the reference's own
-    non-AVX2 build, which carries its own table: `coeffs` must then be that table)."""
+def das_fir8_f32(X, off, frac, coeffs, index=None, impl="oracle", want_out=False):
+    """FIR8 sweep (delay.cpp:31-40 inside mimo.cpp:121-151): power[P] (and out[P,256], the sums before the
+    epilogue); impl = oracle | ref (the reference's own non-AVX2 build, which carries its own table: `coeffs`
+    must then be that table)."""
     X = np.ascontiguousarray(X, np.float32)
     off = np.ascontiguousarray(off, np.int32)
     frac = np.ascontiguousarray(frac, np.float32)
@@ -239,15 +240,16 @@ def das_fir8_f32(X, off, frac, coeffs, index=None, impl="oracle"):
     assert off[:, index].min() >= 0 and off[:, index].max() + 263 <= X.shape[1]
     P = off.shape[0]
     power = np.empty(P, np.float32)
+    out = np.empty((P, 256), np.float32) if want_out else None
     if impl == "oracle":
         oracle().oracle_das_fir8_f32(_p32(X), X.shape[1], _pi(off), _p32(frac), P, off.shape[1], _pi(index),
-                                     index.size, _p32(coeffs), _p32(power))
+                                     index.size, _p32(coeffs), _p32(power), _p32(out) if want_out else None)
     else:
         lib = ref("fir")
         assert lib.ref_variant() == 2
         lib.ref_das(_p32(X), X.shape[1], _pi(off), _p32(frac), P, off.shape[1], _pi(index), index.size,
-                    _p32(power), None)
-    return power
+                    _p32(power), _p32(out) if want_out else None)
+    return (power, out) if want_out else power
 
 
 def das_fir8_f64(X, off, frac, coeffs, index=None) -> np.ndarray:

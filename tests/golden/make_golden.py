@@ -2,7 +2,8 @@
 
 Run in the authoring container (needs /root/reference to build oracle/_ref):
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py              # every file
+    python tests/golden/make_golden.py fir8_dc      # only the DC-biased FIR8 sweeps (the other files stay as they are)
 
 What is stored is data only: table inputs (off, frac, index), seeds of the exact integer-hash
 frames (tests/util.hash_frames) and the outputs the reference kernel produced for them.
@@ -144,6 +145,46 @@ def sweep_case_dc(name, arrays_x, arrays_y, res, pixels, seed, hist=1024, fov=18
     print(f"{name}.npz", off.shape, "power range per offset", power.min(axis=1), power.max(axis=1))
 
 
+FIR8_DC_OFFSETS = np.array([0.0, 1e-4, 1e-3, 1e-2, 0.25], np.float32)
+
+
+def sweep_case_fir8_dc(name, arrays_x, arrays_y, res, pixels, seed, index=None, hist=1024, fov=180.0):
+    """sweep_case_dc for the reference's OTHER delay(), the 8-tap variant (libref_das_fir.so): X = hash_frames(seed) + offset
+    for every offset in FIR8_DC_OFFSETS (0 first: the files carry zero-mean out[] too).  That build has no FMA: per tap a
+    product and an add into out[n], taps 0..7 -- an implementation that rounds once per tap (an FMA chain) drifts from it
+    as the bias, and with it every out[n], grows.  Stored per offset: powers and the first four / the last pixel's out[]."""
+    xyz = O.create_tiled_antenna(arrays_x, arrays_y)
+    off, frac = O.compute_delay_lut(xyz, res, res, fov)
+    off, frac = off[pixels], frac[pixels]
+    n = xyz.shape[1]
+    X0 = util.hash_frames(n, hist, seed=seed)[0]
+    power = np.empty((FIR8_DC_OFFSETS.size, len(pixels)), np.float32)
+    out_first = np.empty((FIR8_DC_OFFSETS.size, 4, 256), np.float32)
+    out_last = np.empty((FIR8_DC_OFFSETS.size, 1, 256), np.float32)
+    for k, dc in enumerate(FIR8_DC_OFFSETS):
+        X = (X0 + dc).astype(np.float32)
+        power[k], out = O.das_fir8_f32(X, off, frac, np.zeros((101, 8), np.float32), index, impl="ref", want_out=True)
+        out_first[k], out_last[k] = out[:4], out[-1:]
+    np.savez_compressed(HERE / f"{name}.npz", arrays=np.array([arrays_x, arrays_y]), res=res, fov=fov, pixels=pixels,
+                        seed=seed, hist=hist, off=off, frac=frac,
+                        index=np.arange(n, dtype=np.int32) if index is None else index.astype(np.int32),
+                        offsets=FIR8_DC_OFFSETS, power=power, out_first=out_first, out_last=out_last)
+    print(f"{name}.npz", off.shape, "power range per offset", power.min(axis=1), power.max(axis=1))
+
+
+def fir8_dc_cases():
+    """DC-biased frames through the 8-tap build: 64 mics, a ragged list, 256 and 512 mics (one, a few and many LDS
+    chunks per pixel in the device kernel)."""
+    fir_dc_rng = np.random.Generator(np.random.PCG64(2026))  # (its own stream: every other draw stays what it was)
+    sweep_case_fir8_dc("sweep_c1_fir8_dc", 1, 1, 32, np.arange(1, 1024, 9), seed=131)
+    keep = np.sort(fir_dc_rng.choice(64, size=47, replace=False)).astype(np.int32)
+    sweep_case_fir8_dc("sweep_c1_ragged_fir8_dc", 1, 1, 32, np.arange(5, 1024, 23), seed=132, index=keep)
+    pix = np.unique(np.concatenate([[0, 127, 16256, 16383], fir_dc_rng.choice(16384, 36, replace=False)]))
+    sweep_case_fir8_dc("sweep_headline_fir8_dc", 4, 1, 128, pix, seed=133, hist=640)
+    pix = np.unique(np.concatenate([[0, 16383], fir_dc_rng.choice(16384, 18, replace=False)]))
+    sweep_case_fir8_dc("sweep_c3_fir8_dc", 4, 2, 128, pix, seed=134, hist=528)
+
+
 def steer_split(xyz, theta, phi):
     """Particle::steer, src/dsp/particle.cpp:37-49, on the restated steering vector."""
     off = np.empty((len(theta), xyz.shape[1]), np.int32)
@@ -174,8 +215,10 @@ def beams_case(name, seed, index=None):
     print(f"{name}.npz", beams.shape, "power range", power.min(), power.max())
 
 
-def main():
+def main(only=None):
     O.build(ref=True)
+    if only == "fir8_dc":
+        return fir8_dc_cases()
     delay_kat()
     beams_case("beams_c1", seed=106)
     beams_case("beams_c1_ragged", seed=107, index=np.array([s for s in range(64) if s % 9 != 4], np.int32))
@@ -207,7 +250,11 @@ def main():
     sweep_case_fir8("sweep_headline_fir8", 4, 1, 128, pix, seed=113, hist=640)
     pix = np.unique(np.concatenate([[0, 16383], rng.choice(16384, 18, replace=False)]))
     sweep_case_fir8("sweep_c3_fir8", 4, 2, 128, pix, seed=114, hist=528)
+    # ---- ... on DC-biased frames, with out[]
+    fir8_dc_cases()
 
 
 if __name__ == "__main__":
-    main()
+    if len(sys.argv) > 2 or (len(sys.argv) == 2 and sys.argv[1] != "fir8_dc"):
+        sys.exit("usage: make_golden.py [fir8_dc]")
+    main(sys.argv[1] if len(sys.argv) == 2 else None)

@@ -23,7 +23,8 @@ MATH = pkg.MATH_F32_EXACT if os.environ.get("AWPU_TEST_MATH") == "exact" else pk
 # [batch][streams][hist] layout in place; the host entry uploads a compacted window instead), each case
 # also swept as two pixel shards and, where the wire format allows (hist 1024, <= 256 streams), from the ring
 DEVICE_PATH = os.environ.get("AWPU_TEST_PATH") == "device"
-# AWPU_TEST_INTERP=fir8: the 8-tap table variant of delay() (reads 6 samples further); AWPU_TEST_REUSE=1:
+# AWPU_TEST_INTERP=fir8: the 8-tap table variant of delay() (reads 6 samples further; with AWPU_TEST_MATH=exact the
+# kernel with the reference's rounding, else -- as for LERP -- the FAST mode's kernels); AWPU_TEST_REUSE=1:
 # every case re-targets ONE handle per geometry (new table, new mic list, gains on and off) instead of a
 # fresh handle, so stale device tables or caches would show
 FIR8 = os.environ.get("AWPU_TEST_INTERP") == "fir8"
@@ -65,7 +66,7 @@ def main(seed: int, cases: int) -> int:
         X = util.hash_frames(n_streams, hist, seed=1000 + case, batch=batch)
         if FIR8:
             table = util.synthetic_fir_table()
-            with pkg.Engine(math=pkg.MATH_F32_FAST, n_pixels=P, n_streams=n_streams, lut_stride=lut_stride, hist=hist, max_batch=batch,
+            with pkg.Engine(math=MATH, n_pixels=P, n_streams=n_streams, lut_stride=lut_stride, hist=hist, max_batch=batch,
                             interp=pkg.binding.INTERP_FIR8) as eng:
                 eng.set_delay_table(off, frac)
                 eng.set_active_mics(index)

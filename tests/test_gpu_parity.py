@@ -333,15 +333,21 @@ def measured_fir_table():
     return np.load(GOLDEN / "delay_kat_fir8.npz")["impulse_response"]
 
 
-@pytest.mark.parametrize("name", FIR8_SWEEPS)
-def test_fir8_golden_vectors(pkg, name):
+def with_maths(values):
+    """(value, math) for every value and both math modes; the FAST leg keeps the id it had when it was the only one."""
+    return [pytest.param(v, m, id=v if m == "fast" else f"{v}-{m}") for v in values for m in MATHS]
+
+
+@pytest.mark.parametrize("name,math", with_maths(FIR8_SWEEPS))
+def test_fir8_golden_vectors(pkg, name, math):
     """AWPU_INTERP_FIR8 on the GPU vs the powers the reference's own non-AVX2 build produced (delay.cpp:31-40
-    inside mimo.cpp:121-151): 64, 256 and 512 mics, a ragged mic list, clipped corner pixels."""
+    inside mimo.cpp:121-151): 64, 256 and 512 mics, a ragged mic list, clipped corner pixels; in the default mode
+    (a multiply and an add per tap) and in AWPU_MATH_F32_FAST (one FMA per tap)."""
     g = np.load(GOLDEN / f"{name}.npz")
     ax, ay = g["arrays"]
     n = 64 * int(ax) * int(ay)
     X = util.hash_frames(n, int(g["hist"]), seed=int(g["seed"]))[0]
-    eng = pkg.Engine(math=pkg.MATH_F32_FAST, n_pixels=g["off"].shape[0], n_streams=n, hist=int(g["hist"]), interp=pkg.binding.INTERP_FIR8)
+    eng = pkg.Engine(math=math_id(pkg, math), n_pixels=g["off"].shape[0], n_streams=n, hist=int(g["hist"]), interp=pkg.binding.INTERP_FIR8)
     with eng:
         eng.set_delay_table(g["off"], g["frac"])
         eng.set_active_mics(g["index"])
@@ -373,10 +379,10 @@ def test_fir8_golden_vectors_on_the_batch_kernel(pkg, name):
         assert util.power_rel_err_unfloored(power[b], want) < util.POWER_RTOL
 
 
-@pytest.mark.parametrize("table_kind", ["synthetic", "reference"])
-def test_fir8_mode_vs_oracle(pkg, oracle, table_kind):
+@pytest.mark.parametrize("table_kind,math", with_maths(["synthetic", "reference"]))
+def test_fir8_mode_vs_oracle(pkg, oracle, table_kind, math):
     """AWPU_INTERP_FIR8 (delay.cpp:31-40): GPU vs the restated FIR sweep, 64 and 256 mics, with a
-    synthetic table and the reference's own (as measured from its compiled delay(), tests/golden)."""
+    synthetic table and the reference's own (as measured from its compiled delay(), tests/golden), in both math modes."""
     table = util.synthetic_fir_table() if table_kind == "synthetic" else measured_fir_table()
     for arrays, res, usable in [((1, 1), 16, 64), ((4, 1), 8, 200)]:
         xyz = oracle.create_tiled_antenna(*arrays)
@@ -384,7 +390,7 @@ def test_fir8_mode_vs_oracle(pkg, oracle, table_kind):
         n = xyz.shape[1]
         X = util.hash_frames(n, 1024, seed=50 + usable, batch=2)
         index = np.random.default_rng(usable).permutation(n)[:usable].astype(np.int32)
-        eng = pkg.Engine(math=pkg.MATH_F32_FAST, n_pixels=off.shape[0], n_streams=n, interp=pkg.binding.INTERP_FIR8, max_batch=2)
+        eng = pkg.Engine(math=math_id(pkg, math), n_pixels=off.shape[0], n_streams=n, interp=pkg.binding.INTERP_FIR8, max_batch=2)
         with eng:
             eng.set_delay_table(off, frac)
             eng.set_active_mics(index)
@@ -418,6 +424,159 @@ def test_fir8_batched_frame_pair_shape(pkg, oracle):
     assert util.power_rel_err(batch, single) < 2e-6
     for b in range(3):
         check_full_grid(oracle, batch[b], X[b], off, frac, f"fir8 batch frame {b}", index=index, fir_table=table)
+
+
+FIR8_DC_SWEEPS = ["sweep_c1_fir8_dc", "sweep_c1_ragged_fir8_dc", "sweep_headline_fir8_dc", "sweep_c3_fir8_dc"]
+_fir8_dc_cases = {}
+
+
+def fir8_dc_case(name):
+    """(golden, frames [5, n, hist]) of a DC-biased FIR8 golden: hash frames + {0, 1e-4, 1e-3, 1e-2, 0.25}; made once per file."""
+    if name not in _fir8_dc_cases:
+        g = np.load(GOLDEN / f"{name}.npz")
+        ax, ay = g["arrays"]
+        X0 = util.hash_frames(64 * int(ax) * int(ay), int(g["hist"]), seed=int(g["seed"]))[0]
+        frames = np.stack([(X0 + np.float32(dc)).astype(np.float32) for dc in g["offsets"]])
+        frames.setflags(write=False)
+        _fir8_dc_cases[name] = ({k: g[k] for k in g.files}, frames)
+    return _fir8_dc_cases[name]
+
+
+def fir8_engine(pkg, g, math, n_pixels=None, **kw):
+    n = 64 * int(g["arrays"][0]) * int(g["arrays"][1])
+    return pkg.Engine(n_pixels=n_pixels or g["off"].shape[0], n_streams=n, hist=int(g["hist"]), math=math, interp=pkg.binding.INTERP_FIR8, **kw)
+
+
+def _fir8_sums_through_the_abi(pkg, g, frames, gains=None):
+    """out [B, P, 256] of AWPU_MATH_F32_EXACT + AWPU_INTERP_FIR8 through awpu_hip_process_device_sums: the frames as one
+    batch and one frame per call (the same handle), each into a buffer pre-filled with NaN."""
+    import torch
+
+    B, P = frames.shape[0], g["off"].shape[0]
+    with fir8_engine(pkg, g, pkg.MATH_F32_EXACT, max_batch=B) as eng:
+        eng.set_delay_table(g["off"], g["frac"])
+        eng.set_active_mics(g["index"])
+        eng.set_fir_table(measured_fir_table())
+        eng.set_mic_gains(gains)
+        d_X = torch.from_numpy(np.array(frames, np.float32)).cuda()
+        d_P = torch.empty((2, B, P), dtype=torch.float32, device="cuda")
+        d_S = torch.full((2, B, P, 256), float("nan"), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        eng.process_device_sums(d_X.data_ptr(), B, d_P[0].data_ptr(), d_S[0].data_ptr())
+        for b in range(B):
+            eng.process_device_sums(d_X[b].data_ptr(), 1, d_P[1, b].data_ptr(), d_S[1, b].data_ptr())
+        eng.synchronize()
+        assert pkg.binding.KERNEL_NAMES[eng.stats().kernel_variant] == "fir8"
+        return d_S[0].cpu().numpy(), d_S[1].cpu().numpy()
+
+
+@pytest.mark.parametrize("name", FIR8_DC_SWEEPS)
+def test_fir8_exact_mode_sums_are_the_reference_bits(pkg, oracle, name):
+    """out[0..255] of a pixel before the moving average, from das_fir8_kernel with the reference's rounding (EXACT + FIR8,
+    awpu_hip_process_device_sums), against what the reference's non-AVX2 object code left in out[] on hash frames +
+    {0, 1e-4, 1e-3, 1e-2, 0.25} (golden out_first / out_last): BIT-identical -- per tap a product and an add, taps 0..7, mics
+    in index[] order -- with one, a few and many LDS chunks per pixel (64, 47 of 64, 256, 512 mics); every other pixel
+    against the restatement, which tests/test_oracle_golden.py pins to the same object code.  A batch of five and one
+    frame per call give the same bits.  The ragged file again with per-mic gains, against the restatement's out[] of the
+    prescaled frames."""
+    g, frames = fir8_dc_case(name)
+    table = measured_fir_table()
+    batch, single = _fir8_sums_through_the_abi(pkg, g, frames)
+    assert not np.isnan(batch).any() and not np.isnan(single).any()
+    for b in range(frames.shape[0]):
+        assert np.array_equal(batch[b, :4], g["out_first"][b]), (name, b)
+        assert np.array_equal(batch[b, -1:], g["out_last"][b]), (name, b)
+        _, want = oracle.das_fir8_f32(frames[b], g["off"], g["frac"], table, g["index"], want_out=True)
+        assert np.array_equal(batch[b], want), (name, b, np.argwhere(batch[b] != want)[:4])
+    assert np.array_equal(single, batch)
+    if name == "sweep_c1_ragged_fir8_dc":
+        gains = np.random.default_rng(17).uniform(0.5, 2.0, 64).astype(np.float32)
+        batch, single = _fir8_sums_through_the_abi(pkg, g, frames, gains=gains)
+        assert not np.isnan(batch).any()
+        for b in range(frames.shape[0]):
+            _, want = oracle.das_fir8_f32(frames[b] * gains[:, None], g["off"], g["frac"], table, g["index"], want_out=True)
+            assert np.array_equal(batch[b], want), (name, "gains", b)
+        assert np.array_equal(single, batch)
+
+
+def test_fir8_sums_are_refused_in_fast_mode(pkg):
+    """AWPU_MATH_F32_FAST + FIR8 has an order of its own (an FMA per tap, or the plane kernel's): no out[] to export."""
+    import torch
+
+    g, frames = fir8_dc_case("sweep_c1_fir8_dc")
+    P = g["off"].shape[0]
+    with fir8_engine(pkg, g, pkg.MATH_F32_FAST) as eng:
+        eng.set_delay_table(g["off"], g["frac"])
+        eng.set_active_mics(g["index"])
+        eng.set_fir_table(measured_fir_table())
+        d_X = torch.from_numpy(frames[:1].copy()).cuda()
+        d_P = torch.empty((1, P), dtype=torch.float32, device="cuda")
+        d_S = torch.empty((1, P, 256), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        with pytest.raises(pkg.AwpuError) as ei:
+            eng.process_device_sums(d_X.data_ptr(), 1, d_P.data_ptr(), d_S.data_ptr())
+        assert ei.value.status == pkg.binding.ERR_STATE
+
+
+@pytest.mark.parametrize("name", FIR8_DC_SWEEPS)
+def test_fir8_dc_biased_goldens_default_mode_flat_1e5(pkg, name):
+    """Engine(interp=FIR8) with the math left at the library's default, on the DC-biased FIR8 goldens: every pixel at every
+    offset within 1e-5 of the powers the reference's non-AVX2 build produced, flat, no floor -- INTEGRATION.md's "within 1e-5
+    of the reference on any input" for the 8-tap variant -- as a batch of five and one frame per call, which agree bit for
+    bit.  (An FMA per tap instead of the reference's product and add misses this with a bias of 0.25: 1.30e-5 at 256 mics and
+    1.42e-5 at 512, measured; with the reference's rounding at most 3.4e-7 at any offset.)"""
+    g, frames = fir8_dc_case(name)
+    with fir8_engine(pkg, g, None, max_batch=frames.shape[0]) as eng:
+        eng.set_delay_table(g["off"], g["frac"])
+        eng.set_active_mics(g["index"])
+        eng.set_fir_table(measured_fir_table())
+        batch = eng.process(frames)
+        assert pkg.binding.KERNEL_NAMES[eng.stats().kernel_variant] == "fir8"
+        single = np.stack([eng.process(frames[b]) for b in range(frames.shape[0])])
+        assert pkg.binding.KERNEL_NAMES[eng.stats().kernel_variant] == "fir8"
+    assert np.array_equal(single, batch)
+    curve = {float(dc): util.power_rel_err_unfloored(batch[k], g["power"][k]) for k, dc in enumerate(g["offsets"])}
+    print(f"parity_dc {name}: offset -> default mode max unfloored error vs the reference build: {curve}")
+    for dc, err in curve.items():
+        assert err <= util.POWER_RTOL, (name, dc, err)
+
+
+@pytest.mark.parametrize("name", FIR8_DC_SWEEPS)
+def test_fir8_dc_biased_goldens_fast_mode_recorded(pkg, oracle, name):
+    """AWPU_MATH_F32_FAST + FIR8 on the same goldens through both of its kernels: das_fir8_kernel with an FMA per tap (the
+    golden's pixels, a batch of five) and das_fir8_plane_kernel (the pixels tiled to 256 * 64 + 1, a batch of five: an odd
+    last pair; every copy of a pixel must agree with the golden).  Zero-mean: 1e-5, strict.  Biased: FAST's order is its own,
+    so only util.parity_report's named allowance is asserted -- max(1e-5, 3 x the reference's own distance to exact fp64 sums),
+    computed from the reference -- and the error per offset PRINTED."""
+    g, frames = fir8_dc_case(name)
+    table = measured_fir_table()
+    P, B = g["off"].shape[0], frames.shape[0]
+    reps = -(-(256 * 64 + 1) // P)
+    names = pkg.binding.KERNEL_NAMES
+    with fir8_engine(pkg, g, pkg.MATH_F32_FAST, max_batch=B) as eng:
+        eng.set_delay_table(g["off"], g["frac"])
+        eng.set_active_mics(g["index"])
+        eng.set_fir_table(table)
+        small = eng.process(frames)
+        assert names[eng.stats().kernel_variant] == "fir8"
+    with fir8_engine(pkg, g, pkg.MATH_F32_FAST, n_pixels=P * reps, max_batch=B) as eng:
+        eng.set_delay_table(np.tile(g["off"], (reps, 1)), np.tile(g["frac"], (reps, 1)))
+        eng.set_active_mics(g["index"])
+        eng.set_fir_table(table)
+        planes = eng.process(frames)
+        assert names[eng.stats().kernel_variant] == "fir8_planes"
+    curve = {}
+    for k, dc in enumerate(g["offsets"]):
+        ref64 = oracle.das_fir8_f64(frames[k], g["off"], g["frac"], table, g["index"])
+        reports = {"fir8": util.parity_report(small[k], g["power"][k], ref64),
+                   "fir8_planes": util.parity_report(planes[k], np.tile(g["power"][k], reps), np.tile(ref64, reps))}
+        curve[float(dc)] = {kern: (rep["max_rel_unfloored"], rep["noise_bound"]) for kern, rep in reports.items()}
+        for kern, rep in reports.items():
+            if dc == 0:
+                assert rep["ok"], (name, kern, float(dc), rep)
+            else:
+                assert rep["ok_within_reference_noise"], (name, kern, float(dc), rep)
+    print(f"parity_dc {name}: offset -> kernel -> (fast mode max unfloored error vs the reference build, bound): {curve}")
 
 
 def test_device_heatmap_equals_populate_heatmap(pkg, oracle):

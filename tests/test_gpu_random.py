@@ -26,6 +26,7 @@ pytestmark = pytest.mark.gpu
     {"AWPU_TEST_PATH": "device"},                               # device-resident frames + two pixel shards per case
     {"AWPU_TEST_INTERP": "fir8"},                               # the 8-tap variant of delay()
     {"AWPU_TEST_INTERP": "fir8", "AWPU_SHAPE": "fir8_planes"},  # ... on the four-plane frame-pair kernel for every batch >= 2
+    {"AWPU_TEST_INTERP": "fir8", "AWPU_TEST_MATH": "exact"},    # ... with the reference's rounding (a multiply and an add per tap)
     {"AWPU_TEST_REUSE": "1"},                                   # one handle re-targeted: tables, mic lists, gains
     {"AWPU_SHAPE": "pair_vertical", "AWPU_TEST_GRID": "1"},     # frame pairs, vertical pixel pairs
     {"AWPU_SHAPE": "quad", "AWPU_TEST_GRID": "1"},                               # quad shapes, random delays: every pixel differs
@@ -36,7 +37,7 @@ pytestmark = pytest.mark.gpu
     {"AWPU_SHAPE": "quadh", "AWPU_TEST_GRID": "1"},                              # single-frame quad shape on the halves layout for every call
     {"AWPU_SHAPE": "quadh", "AWPU_TEST_GRID": "1", "AWPU_TEST_COINCIDE": "1"},
     {"AWPU_SHAPE": "quadh_chunked", "AWPU_TEST_GRID": "1", "AWPU_TEST_COINCIDE": "1"},  # ... never its resident-window variant
-], ids=["pairs", "db", "small", "exact", "exact_grid", "exact_grid_pairs", "exact_verify", "exact_nd2_random", "exact_nd1_coincide", "exact_ndp_random", "exact_quad_r4", "device", "fir8", "fir8_planes", "reuse", "pairs_vertical",
+], ids=["pairs", "db", "small", "exact", "exact_grid", "exact_grid_pairs", "exact_verify", "exact_nd2_random", "exact_nd1_coincide", "exact_ndp_random", "exact_quad_r4", "device", "fir8", "fir8_planes", "fir8_exact", "reuse", "pairs_vertical",
         "quads_random", "quads_coincide", "pairs_coincide", "stationary", "stationary_grid", "quadh_every_call", "quadh_coincide",
         "quadh_chunked"])
 def test_random_tables(env):

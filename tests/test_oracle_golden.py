@@ -251,14 +251,14 @@ def fir8_table_from_fixture():
 
 def test_fir8_known_answers(oracle):
     """delay(), 8-tap variant (src/dsp/delay.cpp:31-40): the restatement fed the measured weights reproduces
-    what the reference's non-AVX2 build returned for a noise signal (the reference is -Ofast: its 8-term
-    sums are in the compiler's order, so a few ulp of the accumulator, not bits)."""
+    what the reference's non-AVX2 build returned for a noise signal, BIT for bit: that build has no FMA and its
+    compiled loop keeps the source's order -- per tap a product, then the add into out[n], taps 0..7."""
     g, table = fir8_table_from_fixture()
     sig = util.hash_frames(1, 320, seed=int(g["sig_seed"]), scale=1.0)[0, 0]
     acc0 = util.hash_frames(1, 256, seed=int(g["acc_seed"]), scale=4.0)[0, 0]
     for f, s0, want in zip(g["fractions"], g["starts"], g["expected"]):
         out = oracle.delay_fir8(acc0.copy(), sig[s0:s0 + 263], float(f), table)
-        assert np.abs(out - want).max() <= 4 * np.spacing(np.float32(np.abs(want).max()))
+        assert np.array_equal(out, want), f"fraction {f}"
     # the rounding of the row index (delay.cpp:32-33): 0.004 -> row 0, 0.005 -> row 1, 0.994 -> 99, 0.995 -> 100
     rows = (g["fractions"] * np.float32(100.0) + np.float32(0.5)).astype(np.int32)
     assert rows[:3].tolist() == [0, 0, 1] and rows[5:8].tolist() == [99, 100, 100]
@@ -287,6 +287,48 @@ def test_fir8_sweep_goldens(oracle, name):
     X = util.hash_frames(64 * int(ax) * int(ay), int(g["hist"]), seed=int(g["seed"]))[0]
     power = oracle.das_fir8_f32(X, g["off"], g["frac"], table, g["index"])
     assert util.power_rel_err(power, g["power"]) < 5e-6
+
+
+FIR8_DC_SWEEPS = ["sweep_c1_fir8_dc", "sweep_c1_ragged_fir8_dc", "sweep_headline_fir8_dc", "sweep_c3_fir8_dc"]
+
+
+@pytest.mark.parametrize("name", FIR8_DC_SWEEPS)
+def test_fir8_sweep_goldens_dc_biased(oracle, name):
+    """The restated FIR8 sweep on hash frames + {0, 1e-4, 1e-3, 1e-2, 0.25} (64 mics, a ragged list, 256 and 512 mics):
+    its pre-epilogue sums are the reference's non-AVX2 object code's out[] BIT for bit at every offset (a multiply and an
+    add per tap, taps 0..7, mics in index[] order); powers within test_fir8_sweep_goldens' 5e-6 (the -Ofast epilogue's
+    sum order; measured at most 8.0e-7).  Also prints the reference build's own distance to exact (fp64) sums."""
+    _, table = fir8_table_from_fixture()
+    g = np.load(GOLDEN / f"{name}.npz")
+    ax, ay = g["arrays"]
+    X0 = util.hash_frames(64 * int(ax) * int(ay), int(g["hist"]), seed=int(g["seed"]))[0]
+    assert g["offsets"].tolist() == np.array([0.0, 1e-4, 1e-3, 1e-2, 0.25], np.float32).tolist()
+    for k, dc in enumerate(g["offsets"]):
+        X = (X0 + np.float32(dc)).astype(np.float32)
+        power, out = oracle.das_fir8_f32(X, g["off"], g["frac"], table, g["index"], want_out=True)
+        assert np.array_equal(out[:4], g["out_first"][k]) and np.array_equal(out[-1:], g["out_last"][k]), (name, float(dc))
+        err = util.power_rel_err_unfloored(power, g["power"][k])
+        p64 = oracle.das_fir8_f64(X, g["off"], g["frac"], table, g["index"])
+        print(f"{name} offset {dc}: oracle vs reference build {err:.2e}, "
+              f"reference build vs exact {util.power_rel_err_unfloored(g['power'][k], p64):.2e}")
+        assert err < 5e-6, (name, float(dc), err)
+
+
+def test_fir8_sums_match_reference_build_live(oracle):
+    """out[] of the restated FIR8 sweep against out[] of the reference's non-AVX2 build on EVERY pixel of a 10 x 10 grid
+    of one array, zero-mean and with a bias of 0.25: bit-identical."""
+    if not oracle.ref_available("fir"):
+        pytest.skip("oracle/_ref FIR build not available")
+    _, table = fir8_table_from_fixture()
+    xyz = oracle.create_antenna()
+    off, frac = oracle.compute_delay_lut(xyz, 10, 10)
+    X0 = util.hash_frames(64, 1024, seed=46)[0]
+    for dc in (0.0, 0.25):
+        X = (X0 + np.float32(dc)).astype(np.float32)
+        p_o, out_o = oracle.das_fir8_f32(X, off, frac, table, want_out=True)
+        p_r, out_r = oracle.das_fir8_f32(X, off, frac, table, impl="ref", want_out=True)
+        assert np.array_equal(out_o, out_r), (dc, np.argwhere(out_o != out_r)[:4])
+        assert util.power_rel_err_unfloored(p_o, p_r) < 5e-6
 
 
 def test_bf16_accumulator_restatement(oracle):
