@@ -268,6 +268,8 @@ struct awpu_hip {
     awpu::host::QuadTable quad_tables[awpu::host::kQuadLayouts];  // the quad-major tables, by QuadLayout
     Dev<unsigned> d_nd_queue;                     // das_exact_nd_kernel's eight item counters (one per XCD)
     Dev<int2> d_nd_items;                         // ... and its item list (nd_items_kernel), valid for nd_items_key
+    Dev<unsigned> d_nd_starts;                    // ... and its tiles' start table (build_quad_lut(kQuadExactNd): nd_tile_window.h), bytes
+    size_t nd_start_entries = 0;
     long long nd_items_key = -1;                  // (n_pairs, pair group, quads per wave) the list was built for; -1: none
     int n_cus = 0;                                // compute units of the handle's device (persistent workgroups: one per CU)
     bool exact_nd_ok = false;     // ... and the window fits the {next, d} image (kQuadExactNd)

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "das_kernels.h"
+#include "nd_tile_window.h"
 
 using namespace awpu::host;
 
@@ -129,6 +130,7 @@ void free_tables(awpu_hip *h) {
     h->fast_luts.clear();
     h->d_exact_pair_lut.release();
     for (QuadTable &q : h->quad_tables) q.d.release();
+    h->d_nd_starts.release();
     h->d_fir_plane_lut.release();
 }
 
@@ -205,7 +207,9 @@ int prepare(awpu_hip *h) {
 
     h->exact_pairs_ok = c.math == AWPU_MATH_F32_EXACT && c.interp == AWPU_INTERP_LERP && awpu::pair_plan(h->window, U, &h->exact_plan);
     h->quad_tables[kQuadExact].plan = h->exact_plan;  // (the quad kernel on raw sample pairs sweeps the pair table's image: one plan)
-    h->exact_nd_ok = h->exact_pairs_ok && awpu::exact_nd_plan(h->window, U, &h->quad_tables[kQuadExactNd].plan);
+    // (whole rows here; build_quad_lut(kQuadExactNd) plans again with the tile window once it has walked the table: wr and usable_pad,
+    // all that is read before it, do not depend on the window)
+    h->exact_nd_ok = h->exact_pairs_ok && awpu::exact_nd_plan(h->window, U, 0, &h->quad_tables[kQuadExactNd].plan);
     h->exact_ndh_ok = h->exact_pairs_ok && awpu::exact_ndh_plan(h->window, U, false, &h->quad_tables[kQuadExactNdh].plan);
     // (AWPU_MATH_F32_FAST sweeps single frames on small grids with the reference-order pixel-per-wave kernel too -- launch() -- : the
     // same plan, the same table)
@@ -385,6 +389,18 @@ int build_quad_lut(awpu_hip *h, QuadLayout layout) {
     if (table.d) return AWPU_OK;
     const auto &c = h->cfg;
     const awpu::FastPlan &plan = table.plan;
+    std::vector<uint16_t> starts;  // kQuadExactNd: where each 8-row tile's window begins in a mic's row (nd_tile_window.h); others: none
+    if (layout == kQuadExactNd) {
+        const int cols = c.grid_columns, wq = plan.wr;
+        const int wq_tile = awpu::nd_tile_windows(h->off.data(), c.lut_stride, h->index.data(), h->usable(), plan.usable_pad, c.pixel_count / cols, cols,
+                                                  h->wstart, wq, &starts);
+        if (!awpu::exact_nd_plan(h->window, h->usable(), wq_tile, &table.plan)) return fail(AWPU_ERR_STATE, "the {next, d} image does not hold the tile window");
+        std::vector<unsigned> bytes(starts.size() + 16, 0u);  // + what a wave of a short last chunk reads past the last row (and never uses)
+        for (size_t i = 0; i < starts.size(); i++) bytes[i] = 16u * starts[i];
+        if (const int rc = h->d_nd_starts.grow(bytes.size()); rc != AWPU_OK) return rc;
+        AWPU_HIP_TRY(hipMemcpy(h->d_nd_starts, bytes.data(), bytes.size() * sizeof(unsigned), hipMemcpyHostToDevice));
+        h->nd_start_entries = bytes.size();
+    }
     const bool halves_nd = layout == kQuadExactNdh || layout == kQuadExactNdhStationary;
     const bool raw = layout == kQuadExact || layout == kQuadExactNd || halves_nd;
     const float centre = raw ? 0.0f : 0.5f;  // the reference-order sweeps take the fraction as it is (mimo.cpp:126)
@@ -410,7 +426,9 @@ int build_quad_lut(awpu_hip *h, QuadLayout layout) {
                     const int j = s % plan.chunk;  // mic slot inside its chunk
                     if (s < U) {
                         const int id = h->index[s];
-                        const int off_rel = orow[id] - h->wstart;
+                        int off_rel = orow[id] - h->wstart;
+                        if (layout == kQuadExactNd)  // the LDS row begins at the tile's start
+                            off_rel -= starts[((size_t) (r4 / 2) * (cols_pad / 16) + col / 16) * plan.usable_pad + s];
                         e.f = inside ? frow[id] - centre : 0.0f;  // centred weight (das_fast.hip, das_quad_kernel); exact: as it is
                         e.addr = (uint32_t) (j * plan.row_bytes + off_rel * elem);
                     } else {  // padding mic: silence (the pack passes write zero rows)
@@ -630,12 +648,19 @@ int launch_exact_nd(awpu_hip *h, const float *d_frames, int batch, float *d_powe
     a.lut = table.d;
     a.sums = h->sums_out;
     a.wq = pp.wr;
+    a.wq_tile = pp.row_bytes / 16;
+    a.starts = h->d_nd_starts;
+    a.start_entries = h->nd_start_entries;
     a.cols = h->cfg.grid_columns;
     a.rows = h->cfg.pixel_count / a.cols;
     a.nq = nq;
     a.tiles = awpu::nd_tiles(a.rows, a.cols, nq);
     a.n_pairs = (batch + 1) / 2;
-    a.pair_group = xcd_pair_group((size_t) pp.usable_pad * pp.row_bytes, a.n_pairs);
+    a.pair_group = xcd_pair_group((size_t) pp.usable_pad * pp.wr * 16, a.n_pairs, env().pair_group);
+    // Four pairs instead of two where four pairs' rows are at most 6 MiB (the headline: 5.7 MB): every XCD then walks the table twice per
+    // launch instead of four times, and a tile stages only its window of a row.  Alternating runs on one box: -0.30 % (5.378 against
+    // 5.394 ms per step; profiles/r13_tile_window_rate.txt).  Larger pairs (c3, the c5 slab) keep the rule above: not measured.
+    if (env().pair_group <= 0 && a.pair_group == 2 && a.n_pairs >= 4 && (size_t) pp.usable_pad * pp.wr * 16 * 4 <= (6u << 20)) a.pair_group = 4;
     {   // the item list: rebuilt (by the launcher, on the stream) when the batch, the pair group or the tile shape changed
         const size_t items = (size_t) a.n_pairs * a.tiles;
         const long long key = ((long long) a.n_pairs << 24) | ((long long) a.pair_group << 8) | nq;
@@ -657,9 +682,11 @@ int launch_exact_nd(awpu_hip *h, const float *d_frames, int batch, float *d_powe
     }
 #endif
     if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
-    if (!prepacked)
+    if (!prepacked) {  // (the pack pass zeroes the sweep's queues too: one dispatch less than a memset between the two)
         AWPU_HIP_TRY(awpu::launch_pack_nd(d_frames, h->cfg.n_streams, hist_eff, wstart_eff, h->d_index, h->usable(), pp.usable_pad, h->d_gain,
-                                          pp.wr, batch, h->d_pack, s));
+                                          pp.wr, batch, h->d_pack, a.queue, s));
+        a.queue_zeroed = 1;
+    }
 #ifdef AWPU_TUNING_BUILD
     const size_t n_wgs = std::min<size_t>((size_t) a.n_pairs * a.tiles, (size_t) a.wgs);
     if (env().debug & 16)  // per-workgroup timeline (where, when, phases)
@@ -1185,14 +1212,15 @@ bool takes_packed_pairs(awpu_hip *h, int batch, awpu::FastPlan *plan) {
 // floats of `batch` frames in the packed layout of `plan` (rows of plan.row_bytes: sample pairs of a frame pair, or their {next, d}
 // elements), `usable` rows per pair (the packed entry points ask for usable % 4 == 0: no padding rows)
 size_t packed_floats_of(const awpu_hip *h, const awpu::FastPlan &plan, int batch) {
-    return (size_t) ((batch + 1) / 2) * h->usable() * (size_t) (plan.row_bytes / 4);
+    // (the {next, d} plan's row_bytes is its LDS row, the tile window; its packed rows hold wr elements of four floats)
+    return (size_t) ((batch + 1) / 2) * h->usable() * (size_t) (plan.image_bytes == -4 ? plan.wr * 4 : plan.row_bytes / 4);
 }
 
 // the sweep's pack pass into a caller's buffer: pre-filtered sample pairs (FAST) or {next, d} elements (EXACT)
 int pack_for_sweep(awpu_hip *h, const awpu::FastPlan &plan, const float *d_frames, int batch, float *d_packed, hipStream_t s) {
     if (h->cfg.math == AWPU_MATH_F32_EXACT)
         AWPU_HIP_TRY(awpu::launch_pack_nd(d_frames, h->cfg.n_streams, h->cfg.hist, h->wstart, h->d_index, h->usable(), h->usable(), nullptr, plan.wr,
-                                          batch, d_packed, s));
+                                          batch, d_packed, nullptr, s));
     else
         AWPU_HIP_TRY(awpu::launch_pack_pairs(d_frames, h->cfg.n_streams, h->cfg.hist, h->wstart, h->d_index, h->usable(), h->usable(), nullptr,
                                              plan.wr, batch, d_packed, true, s));

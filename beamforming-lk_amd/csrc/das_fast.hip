@@ -35,6 +35,7 @@
 //         A += f*x   -> out[2l], out[2l+1]          Q += g*x   -> out[2l-1], out[2l]
 //         C += f*y   -> out[128+2l], out[129+2l]    R += g*y   -> out[127+2l], out[128+2l]
 #include "das_kernels.h"
+#include "nd_tile_window.h"
 
 #include <algorithm>
 #include <atomic>
@@ -1327,9 +1328,11 @@ __device__ __forceinline__ f2 next_and_difference(float cur, float next, float g
     return f2{n, c - n};                      // delay.cpp:21: cur - next
 }
 
+// `queue` (or null): the nine item counters of the sweep that follows on the stream, zeroed here by block 0 -- no dispatch of its own.
 __global__ void pack_nd_kernel(const float *frames, int n_streams, int hist, int wstart, const int32_t *index, int usable,
-                               const float *gain, int wq, int batch, float *packed) {
+                               const float *gain, int wq, int batch, float *packed, unsigned *queue) {
     const int pair = blockIdx.y, s = blockIdx.x, rows_out = gridDim.x;
+    if (queue && pair == 0 && s == 0 && threadIdx.x < 9) queue[threadIdx.x] = 0u;
     f4 *dst = (f4 *) packed + ((size_t) pair * rows_out + s) * wq;
     if (s >= usable) {  // padding rows (whole groups of four mics are swept): next = 0, d = 0 -> t = fma(0, 0, 0) = +0
         for (int t = threadIdx.x; t < wq; t += blockDim.x) dst[t] = f4{0.0f, 0.0f, 0.0f, 0.0f};
@@ -1413,8 +1416,7 @@ struct NdQueues {
 template <int NQ, bool SUMS>
 __global__ __launch_bounds__(1024, 4) void das_exact_nd_kernel(ExactNdArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int NW = 16, kThreads = NW * 64, BUF = kFastLdsBytes;
-    constexpr int kPieces = (BUF + kThreads * 16 - 1) / (kThreads * 16);
+    constexpr int NW = 16, BUF = kFastLdsBytes;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const unsigned lds_base = (unsigned) (unsigned long long) (const __attribute__((address_space(3))) char *) lds;
     int *mail = (int *) (lds + 2 * (BUF / 4));  // two ints behind the images: the items thread 0 took for the workgroup
@@ -1435,40 +1437,53 @@ __global__ __launch_bounds__(1024, 4) void das_exact_nd_kernel(ExactNdArgs a) {
 
     // where an item lies: a.items[item] = (frame pair, first quad of the tile in the table), written by nd_items_kernel in the order
     // (pair group, tile, pair) -- one scalar load per item here instead of five integer divisions and their constants
-    auto decode = [&](int item, int &pair, int &tile_quad) {
+    // ... and `starts` = the row of the start table that serves the item's tile: the 8-row tile (16 columns x two quad rows) it lies in
+    const int tiles_per_row = (a.cols + NW - 1) / NW;
+    auto decode = [&](int item, int &pair, int &tile_quad, const unsigned *&starts) {
         const int2 d = a.items[item];
         pair = __builtin_amdgcn_readfirstlane(d.x);
         tile_quad = __builtin_amdgcn_readfirstlane(d.y);
+        const int quad_row = (tile_quad >> 4) / tiles_per_row, col_tile = (tile_quad >> 4) - quad_row * tiles_per_row;
+        starts = a.starts + (size_t) ((quad_row >> 1) * tiles_per_row + col_tile) * a.usable_pad;
     };
-    const int tiles_per_row = (a.cols + NW - 1) / NW;
     const int groups_total = a.usable_pad >> 2;
     const size_t row_floats = (size_t) a.wq * 4;
     const int n_chunks = (a.usable_pad + a.chunk - 1) / a.chunk;
     const int first_mics = min(a.chunk, a.usable_pad), last_mics = a.usable_pad - (n_chunks - 1) * a.chunk;
-    const int ngf = __builtin_amdgcn_readfirstlane(first_mics >> 2), ngl = __builtin_amdgcn_readfirstlane(last_mics >> 2);
     const unsigned dbf = __builtin_amdgcn_readfirstlane((unsigned) ((size_t) a.chunk * row_floats * 4));
-    const unsigned dbl = __builtin_amdgcn_readfirstlane((unsigned) ((size_t) last_mics * row_floats * 4));
-    const unsigned db0 = __builtin_amdgcn_readfirstlane((unsigned) ((size_t) first_mics * row_floats * 4));
+    // The LDS holds, of every row, the wq_tile elements from the row's start on (the window the item's tile reads); wave w stages row w
+    // of every chunk (a chunk has at most 16), in pieces of 1 KiB, the last one under a lane mask
+    const int row_bytes = a.wq_tile * 16;
+    const int row_pieces = (row_bytes + 1023) >> 10;
+    const unsigned last_shift = (unsigned) (row_pieces * 64 - a.wq_tile);  // 64 - lanes of the last piece
     const int rank = wave >> 2;  // age order of this wave among the four that share its SIMD
+    // (the block's packed arguments: tools/gen_trip_asm.py, block_exact_nd)
+    const unsigned pka = __builtin_amdgcn_readfirstlane((unsigned) (first_mics >> 2) | (unsigned) (last_mics >> 2) << 8 | (unsigned) n_chunks << 16);
+    const unsigned pkb_item = (wave < a.chunk ? (unsigned) row_pieces : 0u) | (wave < last_mics ? (unsigned) row_pieces : 0u) << 8 | last_shift << 24 |
+                              (unsigned) rank << 30;
+    const unsigned pkb_next = wave < first_mics ? (unsigned) row_pieces << 16 : 0u;
     const int own_head = Q.head(xcd);  // items of this XCD's own queue
 
     int pair, tile;
-    decode(cur, pair, tile);
+    const unsigned *starts;
+    decode(cur, pair, tile, starts);
 #ifdef AWPU_TUNING_BUILD
     const unsigned long long rt_begin = a.debug_out ? __builtin_amdgcn_s_memrealtime() : 0ull;  // 100 MHz
     long long t_sweep = 0, t_other = 0, t_mark = __builtin_readcyclecounter();
     int n_items = 0;
 #endif
     {   // the first item's chunk 0 into image 0 (the block refills everything after it, the next item's first chunk included)
-        const float *pair_base = a.packed + (size_t) pair * a.usable_pad * row_floats;
-        const int n_pieces = (int) ((size_t) first_mics * row_floats / 4);
-#pragma unroll
-        for (int k = 0; k < kPieces; k++) {
-            const int piece = threadIdx.x + k * kThreads;
-            if (piece < n_pieces) {
-                float *dst = lds + (wave * 64 + k * kThreads) * 4;
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *) (pair_base + (size_t) piece * 4),
-                                                 (__attribute__((address_space(3))) void *) dst, 16, 0, 0);
+        if (wave < first_mics) {
+            const unsigned start = __builtin_amdgcn_readfirstlane(starts[wave]);  // bytes
+            const float *src = a.packed + ((size_t) pair * a.usable_pad + wave) * row_floats + (start >> 2);
+            const int lane = (int) (threadIdx.x & 63);
+            for (int k = 0; k < row_pieces; k++) {
+                const int el = k * 64 + lane;
+                if (el < a.wq_tile) {
+                    float *dst = lds + ((wave * row_bytes) >> 2) + k * 256;
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *) (src + (size_t) el * 4),
+                                                     (__attribute__((address_space(3))) void *) dst, 16, 0, 0);
+                }
             }
         }
     }
@@ -1485,7 +1500,8 @@ __global__ __launch_bounds__(1024, 4) void das_exact_nd_kernel(ExactNdArgs a) {
         const QuadEntry *quad_lut = a.lut + (size_t) quad0 * groups_total * 16;
         const float *pair_base = a.packed + (size_t) pair * a.usable_pad * row_floats;
         int pair_next = pair, tile_next = tile;
-        if (nxt >= 0) decode(nxt, pair_next, tile_next);
+        const unsigned *starts_next = starts;
+        if (nxt >= 0) decode(nxt, pair_next, tile_next, starts_next);
         const float *next_base = a.packed + (size_t) pair_next * a.usable_pad * row_floats;
         // Wave 0 asks its XCD's queue for the item after the next one INSIDE the sweep block (qptr: lane 0 adds one to that counter as
         // the block begins) and thread 0 looks at the answer after the sweep: the atomic's round trip -- microseconds, with every
@@ -1505,21 +1521,23 @@ __global__ __launch_bounds__(1024, 4) void das_exact_nd_kernel(ExactNdArgs a) {
             // -- it kept five -- is one it spills to scratch)
             unsigned tid = threadIdx.x;
             asm volatile("" : "+v"(tid));
-            const unsigned lane_bytes = tid * 16;
+            const unsigned lane_bytes = (tid & 63) * 16;
             const int buf = (int) (step & 1);
-            unsigned lane_addr = lds_base + buf * BUF + (tid & 63) * 16;
-            const unsigned ddst = __builtin_amdgcn_readfirstlane(lds_base + (buf ^ 1) * BUF + wave * 1024);
+            unsigned lane_addr = lds_base + buf * BUF + lane_bytes;
+            const unsigned ddst = __builtin_amdgcn_readfirstlane(lds_base + (buf ^ 1) * BUF + wave * row_bytes);
             const int delta = __builtin_amdgcn_readfirstlane(buf ? -BUF : BUF);
-            const unsigned dbn = __builtin_amdgcn_readfirstlane(nxt >= 0 ? db0 : 0u);
+            const unsigned pkb = __builtin_amdgcn_readfirstlane(pkb_item | (nxt >= 0 ? pkb_next : 0u));
+            // this wave's row of the item's chunk 0 and of the next item's, and its entries of the two tiles' start tables
+            const float *row_src = pair_base + (size_t) wave * row_floats, *row_next = next_base + (size_t) wave * row_floats;
             if constexpr (NQ == 1) {
-                sweep_exact_nd_item1(O[0][0], O[0][1], O[0][2], O[0][3], uniform_ptr(quad_lut), ngf, ngl, __builtin_amdgcn_readfirstlane(n_chunks),
-                                     lane_addr, rank, uniform_ptr(pair_base), dbf, dbl, uniform_ptr(next_base), dbn, ddst, delta, lane_bytes, qptr, ticket);
+                sweep_exact_nd_item1(O[0][0], O[0][1], O[0][2], O[0][3], uniform_ptr(quad_lut), pka, lane_addr, pkb, uniform_ptr(row_src), dbf,
+                                     uniform_ptr(row_next), ddst, delta, lane_bytes, uniform_ptr(starts + wave), uniform_ptr(starts_next + wave), qptr, ticket);
             } else {
                 static_assert(NQ == 2, "blocks are generated for one and two quads per wave");
                 const int qstride = __builtin_amdgcn_readfirstlane(tiles_per_row * NW * groups_total * 16 * (int) sizeof(QuadEntry));
-                sweep_exact_nd_item2(O[0][0], O[0][1], O[0][2], O[0][3], O[1][0], O[1][1], O[1][2], O[1][3], uniform_ptr(quad_lut), qstride, ngf, ngl,
-                                     __builtin_amdgcn_readfirstlane(n_chunks), lane_addr, rank, uniform_ptr(pair_base), dbf, dbl, uniform_ptr(next_base),
-                                     dbn, ddst, delta, lane_bytes, qptr, ticket);
+                sweep_exact_nd_item2(O[0][0], O[0][1], O[0][2], O[0][3], O[1][0], O[1][1], O[1][2], O[1][3], uniform_ptr(quad_lut), qstride, pka, lane_addr,
+                                     pkb, uniform_ptr(row_src), dbf, uniform_ptr(row_next), ddst, delta, lane_bytes, uniform_ptr(starts + wave),
+                                     uniform_ptr(starts_next + wave), qptr, ticket);
             }
             step += n_chunks;
         }
@@ -1571,6 +1589,7 @@ __global__ __launch_bounds__(1024, 4) void das_exact_nd_kernel(ExactNdArgs a) {
         cur = nxt;
         pair = pair_next;
         tile = tile_next;
+        starts = starts_next;
         nxt = __builtin_amdgcn_readfirstlane(mail[0]);
         __syncthreads();  // (everybody has read the mailbox before thread 0 writes it again)
     }
@@ -2843,13 +2862,13 @@ hipError_t launch_das_fir8_planes(const PairArgs &a, const void *d_entries, cons
     return launch_fir8_plane_variant<0>(a, d_entries, d_coeffs, have, stream);
 }
 
-bool exact_nd_plan(int window, int usable, FastPlan *plan) {
+bool exact_nd_plan(int window, int usable, int wq_tile, FastPlan *plan) {
     const int wq = window - 1;  // element t holds X[t+1] and X[t] - X[t+1]: one element less than samples
-    const size_t row_bytes = (size_t) wq * 16;
-    int chunk = (int) ((size_t) kFastLdsBytes / row_bytes);
-    chunk &= ~3;
-    if (chunk > 64) chunk = 64;
-    if (chunk < 4 || wq < kSamples) return false;
+    if (wq_tile <= 0 || wq_tile > wq) wq_tile = wq;  // (not known yet, or no tile reads less: whole rows)
+    const size_t row_bytes = (size_t) wq_tile * 16;  // of the LDS image: the window a tile reads; the packed rows in HBM keep wq elements
+    if (wq_tile < kSamples) return false;
+    int chunk = nd_chunk_mics(wq_tile, kFastLdsBytes);  // a row per wave
+    if (chunk < 4) return false;
     const int usable_pad = (usable + 3) & ~3;
     if (chunk > usable_pad) chunk = usable_pad;
     plan->fpi = 2;
@@ -2862,9 +2881,9 @@ bool exact_nd_plan(int window, int usable, FastPlan *plan) {
 }
 
 hipError_t launch_pack_nd(const float *d_frames, int n_streams, int hist, int wstart, const int32_t *d_index, int usable, int rows_out,
-                          const float *d_gain, int wq, int batch, float *d_packed, hipStream_t stream) {
+                          const float *d_gain, int wq, int batch, float *d_packed, unsigned *d_queue, hipStream_t stream) {
     hipLaunchKernelGGL(pack_nd_kernel, dim3(rows_out, (batch + 1) / 2), dim3(128), 0, stream, d_frames, n_streams, hist, wstart, d_index,
-                       usable, d_gain, wq, batch, d_packed);
+                       usable, d_gain, wq, batch, d_packed, d_queue);
     return hipGetLastError();
 }
 
@@ -2873,9 +2892,11 @@ static hipError_t launch_exact_nd_variant(const ExactNdArgs &a, hipStream_t stre
     static LdsFlags attr_set = {};
     constexpr int lds_bytes = 2 * kFastLdsBytes + 64;  // two images + the item mailbox
     if (hipError_t e = allow_lds((const void *) das_exact_nd_kernel<NQ, SUMS>, lds_bytes, attr_set); e != hipSuccess) return e;
-    // one persistent workgroup per CU (the LDS holds no second one), never more than there are items; the queues start at zero
+    // one persistent workgroup per CU (the LDS holds no second one), never more than there are items; the queues start at zero: the
+    // pack pass in front of this launch has zeroed them (a.queue_zeroed), or -- frames that arrive packed -- a memset does
     const long total = (long) a.n_pairs * a.tiles;
-    if (hipError_t e = hipMemsetAsync(a.queue, 0, 9 * sizeof(unsigned), stream); e != hipSuccess) return e;
+    if (!a.queue_zeroed)
+        if (hipError_t e = hipMemsetAsync(a.queue, 0, 9 * sizeof(unsigned), stream); e != hipSuccess) return e;
     if (a.build_items)
         hipLaunchKernelGGL(nd_items_kernel, dim3((unsigned) ((total + 255) / 256)), dim3(256), 0, stream, const_cast<int2 *>(a.items), a.n_pairs,
                            a.tiles, a.pair_group, (a.cols + 15) / 16, NQ);
@@ -2885,10 +2906,12 @@ static hipError_t launch_exact_nd_variant(const ExactNdArgs &a, hipStream_t stre
 
 hipError_t launch_das_exact_nd(const ExactNdArgs &a, const Extents &have, hipStream_t stream) {
     if ((a.nq != 1 && a.nq != 2) || !a.queue || !a.items || a.wgs < 1 || a.tail < 1) return hipErrorInvalidValue;
-    if (a.chunk < 4 || (a.chunk & 3) || (a.usable_pad & 3) || a.usable < 1 || a.usable > a.usable_pad || a.wq < kSamples ||
-        (size_t) a.chunk * a.wq * 16 > (size_t) kFastLdsBytes || a.cols < 1 || a.rows * a.cols != a.pixel_count)
+    if (a.chunk < 4 || (a.chunk & 3) || a.chunk > 16 || (a.usable_pad & 3) || a.usable < 1 || a.usable > a.usable_pad || a.wq_tile < kSamples ||
+        a.wq_tile > a.wq || (size_t) a.chunk * a.wq_tile * 16 > (size_t) kFastLdsBytes || a.cols < 1 || a.rows * a.cols != a.pixel_count)
         return hipErrorInvalidValue;
     if (a.n_pairs != (a.batch + 1) / 2 || a.tiles != nd_tiles(a.rows, a.cols, a.nq) || a.pair_group < 1) return hipErrorInvalidValue;
+    // the start table: a row of usable_pad entries per 8-row tile + the 16 a wave of a short last chunk may read past the last row
+    if (!a.starts || a.start_entries < (size_t) nd_tiles(a.rows, a.cols, 2) * a.usable_pad + 16) return hipErrorInvalidValue;
     // reach: every quad of the grid padded to whole tiles (quad rows to a multiple of nq) + one group of prefetch; usable_pad rows of wq
     // 16-byte elements per frame pair
     if (!within({(size_t) nd_quad_count(a.rows, a.cols, a.nq) * (a.usable_pad / 4) * 16 + kQuadTablePrefetch,

@@ -158,14 +158,18 @@ hipError_t launch_das_exact_quads(const ExactQuadArgs &a, const Extents &have, h
 // fma(frac, d, next) and the add, in the reference's order (the same fp32 subtraction of the same operands: the same bits).
 struct ExactNdArgs {
     const float *packed;   // [pairs][usable_pad][wq][4], padding rows zero
-    const struct QuadEntry *lut;  // quad-major, raw fractions, addr = slot * wq * 16 + (off - wstart) * 16; quad rows padded to a multiple of nq
+    const struct QuadEntry *lut;  // quad-major, raw fractions, addr = slot * wq_tile * 16 + (off - wstart - start) * 16; quad rows padded to an even count
+    const unsigned *starts;       // [8-row tiles][usable_pad] (+ 16): byte offset into a mic's packed row of the window that tile reads (`start` x 16)
+    size_t start_entries;         // ... entries the table holds (the launcher checks its reach)
+    int32_t wq_tile;              // elements of a row that the LDS holds: 256 + the widest spread of a tile's delays for one mic (<= wq)
     float *power;          // [batch][pixel_count]
     float *sums;           // optional [batch][pixel_count][256]: out[] of every pixel before the epilogue (tests), or null
     int32_t usable, usable_pad, pixel_count, wq, chunk, batch;
     int32_t cols, rows;
     int32_t nq;            // quads per wave: a workgroup tile is 4 nq rows x 16 columns
     int32_t tiles, n_pairs, pair_group;  // nd_tiles(rows, cols, nq); frame pairs, and how many an XCD works on at a time
-    unsigned *queue;                     // [9] item counters (one per XCD + the common tail): device memory of the handle, zeroed by the launcher on the stream
+    unsigned *queue;                     // [9] item counters (one per XCD + the common tail): device memory of the handle, zeroed on the stream
+    int32_t queue_zeroed;                // ... by the pack pass in front of this launch (launch_pack_nd's d_queue); 0: the launcher's memset does it
     int32_t wgs;                         // persistent workgroups to launch: the device's CUs (one fits a CU)
     int32_t tail;                        // items at the end of every XCD's run that go to the common queue (>= the run: one queue for the chip)
     const int2 *items;                   // [n_pairs * tiles] (frame pair, first table quad of the tile), item order; device memory of the handle
@@ -174,9 +178,10 @@ struct ExactNdArgs {
 };
 inline int nd_tiles(int rows, int cols, int nq) { return (((rows + 3) / 4 + nq - 1) / nq) * ((cols + 15) / 16); }
 inline int nd_quad_count(int rows, int cols, int nq) { return (((rows + 3) / 4 + nq - 1) / nq) * nq * ((cols + 15) / 16) * 16; }  // table quads incl. padding
-bool exact_nd_plan(int window, int usable, FastPlan *plan);  // plan->wr = elements per row (window - 1), row_bytes = 16 wr
+// plan->wr = elements per packed row (window - 1); row_bytes = 16 wq_tile, the LDS row (wq_tile <= 0: whole rows); chunk <= 16, one row per wave
+bool exact_nd_plan(int window, int usable, int wq_tile, FastPlan *plan);
 hipError_t launch_pack_nd(const float *d_frames, int n_streams, int hist, int wstart, const int32_t *d_index, int usable, int rows_out,
-                          const float *d_gain, int wq, int batch, float *d_packed, hipStream_t stream);
+                          const float *d_gain, int wq, int batch, float *d_packed, unsigned *d_queue, hipStream_t stream);
 hipError_t launch_das_exact_nd(const ExactNdArgs &a, const Extents &have, hipStream_t stream);
 // ---- single frames in the reference's order: the HALVES form of the {next, d} layout (das_exact_ndh_kernel, round 5).  Element t of
 // a mic's row = { X[t+1], X[t+129], X[t] - X[t+1], X[t+128] - X[t+129] } (t from wstart; wh = window - 129 elements): the two packed

@@ -687,8 +687,9 @@ def block_exact_nd(name, nq, nk=4, nw=16, refill=True, octet=False):
     pixel: quad A's four at the first mic's head, quad B's at the second's); every wait is lgkmcnt(0), the only count that proves a
     scalar load, which returns out of order.  Headline: 2.18 sets of reads per octet and mic instead of 2 x 1.51.
 
-    Item structure (the production quad block's, _block_quad_item): chunk loop, in-block refill of the other LDS image (one 16 KiB
-    piece at the head of each trip), vmcnt wait and workgroup barrier inside the block, the next chunk's first entries already in
+    Item structure (the production quad block's, _block_quad_item): chunk loop, in-block refill of the other LDS image (a piece at the
+    head of each trip -- nk = 4: BY WHOLE ROWS, 1 KiB of the wave's own row of the chunk, the window its tile reads, `rows` below;
+    nk = 2: 16 KiB of the chunk as one linear stream), vmcnt wait and workgroup barrier inside the block, the next chunk's first entries already in
     SGPRs when a chunk begins (a quad's table is contiguous across chunks; the running prefetch switches between the quads' tables
     one trip before a quad's chunk ends).  nq = 2: per chunk quad A then quad B (`qstride` table bytes apart), each with its own
     pinned accumulators and its own copy of the trip code.
@@ -704,6 +705,10 @@ def block_exact_nd(name, nq, nk=4, nw=16, refill=True, octet=False):
     nw = waves per workgroup (a refill piece is nw x 1 KiB): 16.  (8 and 4 were built for single frames on small grids -- c2 76.6 ->
     71.7 / 68.9 us -- until one pixel per wave, block_exact_solo, replaced them.)"""
     assert not octet or (nq == 2 and nk == 4 and refill)
+    # the frame-pair blocks refill by whole rows: wave w copies row w of the chunk being fetched -- only the window its tile reads, from
+    # the row's `start` on (a scalar load from the tile's start table) -- in pieces of 1 KiB, the last one under a constant lane mask
+    rows = refill and nk == 4
+    assert not rows or nw == 16
     DMA_PIECE = nw * 1024
     w = 2 * nk  # registers per pixel's out[]
     O = [[ND_ACC + 4 * w * q + w * p for p in range(4)] for q in range(nq)]
@@ -719,6 +724,13 @@ def block_exact_nd(name, nq, nk=4, nw=16, refill=True, octet=False):
     LB = addr_t + 1 if nk == 2 else None
     E = (36, 68)
     S_NG, S_PFO, S_CH, S_SB, S_TMP, S_PF_, S_LEFT_, S_DST, S_REM, S_K, S_NP, S_M0, S_DELTA = 17, 18, 19, 20, 22, 23, 24, 25, 28, 29, 30, 31, 35
+    # rows: S_K = pieces of this wave's row still to copy, S_ST = the row's start in bytes, S_DSTB = the row's place in the image being filled
+    S_ST, S_DSTB = S_REM, S_NP
+    # rows: two packed scalar arguments.  pka = ngf | ngl << 8 | nch << 16;  pkb = pieces of a row for this wave in a full chunk | in the
+    # item's last chunk << 8 | in the next item's first chunk << 16 (0: no row of that chunk is this wave's) | (64 - lanes of a row's
+    # last piece) << 24 | rank << 30
+    F_NGF, F_NGL, F_NCH = "0x80000", "0x80008", "0x100010"
+    F_NPF, F_NPL, F_NPN, F_NSH = "0x80000", "0x80008", "0x80010", "0x60018"
 
     def f_of(base, p, i):
         return base + 8 * p + 2 * i
@@ -817,6 +829,15 @@ def block_exact_nd(name, nq, nk=4, nw=16, refill=True, octet=False):
         if not refill:
             return []
         u = uid()
+        if rows:  # 1 KiB of this wave's row, if any is left; the row's last piece under the plan's lane mask
+            return [f"s_cmp_eq_u32 s{S_K}, 0", f"s_cbranch_scc1 .Lndskip{u}",
+                    f"s_mov_b32 m0, s{S_DST}",
+                    f"s_cmp_lg_u32 s{S_K}, 1", f"s_cbranch_scc1 .Lndfull{u}",
+                    f"s_bfe_u32 s{S_TMP}, %[pkb], {F_NSH}", f"s_lshr_b64 exec, -1, s{S_TMP}", f".Lndfull{u}:",
+                    f"global_load_lds_dwordx4 %[lbytes], s[{S_SB}:{S_SB + 1}]",
+                    "s_mov_b64 exec, -1",
+                    f"s_add_u32 s{S_SB}, s{S_SB}, 0x400", f"s_addc_u32 s{S_SB + 1}, s{S_SB + 1}, 0",
+                    f"s_add_u32 s{S_DST}, s{S_DST}, 0x400", f"s_sub_u32 s{S_K}, s{S_K}, 1", f".Lndskip{u}:"]
         if LB is not None:
             return [f"v_cmp_gt_u32 vcc, s{S_REM}, v{LB}",  # lanes whose 16 bytes lie inside the chunk
                     f"s_cbranch_vccz .Lndskip{u}",
@@ -949,6 +970,21 @@ def block_exact_nd(name, nq, nk=4, nw=16, refill=True, octet=False):
             return []
         u = uid()
         L = []
+        if rows:
+            # S_ST holds the start of this wave's row of the chunk to fetch (start_load, proven by the lgkmcnt(0) in front of this)
+            if not first:
+                L += [f"s_sub_u32 s{S_DSTB}, s{S_DSTB}, s{S_DELTA}", f"s_sub_u32 s{S_DELTA}, 0, s{S_DELTA}"]  # the refill alternates images like the sweep, one ahead
+            return L + [f"s_mov_b32 s{S_DST}, s{S_DSTB}",
+                        f"s_cmp_eq_u32 s{S_CH}, 1", f"s_cbranch_scc1 .Lnrnext{u}",
+                        f"s_bfe_u32 s{S_TMP}, %[pka], {F_NCH}", f"s_sub_u32 s{S_TMP}, s{S_TMP}, s{S_CH}", f"s_add_u32 s{S_TMP}, s{S_TMP}, 1",  # the chunk to fetch
+                        f"s_mul_i32 s{S_TMP}, s{S_TMP}, %[dbf]", f"s_mov_b64 s[{S_SB}:{S_SB + 1}], %[isrc]",
+                        f"s_add_u32 s{S_SB}, s{S_SB}, s{S_TMP}", f"s_addc_u32 s{S_SB + 1}, s{S_SB + 1}, 0",
+                        f"s_bfe_u32 s{S_K}, %[pkb], {F_NPF}", f"s_bfe_u32 s{S_TMP}, %[pkb], {F_NPL}",
+                        f"s_cmp_eq_u32 s{S_CH}, 2", f"s_cselect_b32 s{S_K}, s{S_TMP}, s{S_K}",
+                        f"s_branch .Lnrset{u}", f".Lnrnext{u}:",
+                        f"s_mov_b64 s[{S_SB}:{S_SB + 1}], %[nsrc]", f"s_bfe_u32 s{S_K}, %[pkb], {F_NPN}",
+                        f".Lnrset{u}:",
+                        f"s_add_u32 s{S_SB}, s{S_SB}, s{S_ST}", f"s_addc_u32 s{S_SB + 1}, s{S_SB + 1}, 0"]
         if LB is not None:  # (nothing to undo: neither the source nor the destination base was advanced)
             if not first:
                 L += [f"s_sub_u32 s{S_DST}, s{S_DST}, s{S_DELTA}", f"s_sub_u32 s{S_DELTA}, 0, s{S_DELTA}"]
@@ -975,13 +1011,37 @@ def block_exact_nd(name, nq, nk=4, nw=16, refill=True, octet=False):
               f"s_lshr_b32 s{S_NP}, s{S_NP}, {DMA_PIECE.bit_length() - 1}"]
         return L
 
+    def start_load(first):
+        """rows: request S_ST, the start of this wave's row of the chunk that the NEXT refill_params sets up -- the item's chunk after the
+        one about to be swept, or the next item's first chunk (its tile's table: stnext).  Issued in front of an lgkmcnt(0) that is there
+        anyway; S_ST is dead by then (refill_params folded it into S_SB).  At a boundary S_CH still counts the chunk just swept."""
+        if not rows:
+            return []
+        u = uid()
+        last, none = (1, None) if first else (2, 1)
+        L = []
+        if none is not None:
+            L += [f"s_cmp_le_u32 s{S_CH}, {none}", f"s_cbranch_scc1 .Lnsdone{u}"]  # the item ends here: nothing to fetch
+        L += [f"s_cmp_eq_u32 s{S_CH}, {last}", f"s_cbranch_scc1 .Lnsnext{u}",
+              f"s_bfe_u32 s{S_TMP}, %[pka], {F_NCH}", f"s_sub_u32 s{S_TMP}, s{S_TMP}, s{S_CH}", f"s_add_u32 s{S_TMP}, s{S_TMP}, {last}",  # the chunk to fetch
+              f"s_bfe_u32 s{S_ST}, %[pka], {F_NGF}", f"s_mul_i32 s{S_TMP}, s{S_TMP}, s{S_ST}", f"s_lshl_b32 s{S_TMP}, s{S_TMP}, 4",  # x 4 mics x 4 bytes
+              f"s_load_dword s{S_ST}, %[stcur], s{S_TMP}", f"s_branch .Lnsdone{u}",
+              f".Lnsnext{u}:", f"s_load_dword s{S_ST}, %[stnext], 0x0", f".Lnsdone{u}:"]
+        return L
+
     def chunk_groups():  # S_NG = groups of four mics in the chunk about to be swept
+        if rows:
+            return [f"s_bfe_u32 s{S_NG}, %[pka], {F_NGF}", f"s_bfe_u32 s{S_TMP}, %[pka], {F_NGL}", f"s_cmp_eq_u32 s{S_CH}, 1",
+                    f"s_cselect_b32 s{S_NG}, s{S_TMP}, s{S_NG}", f"s_mov_b32 s{S_LEFT_}, s{S_NG}"]
         return [f"s_mov_b32 s{S_NG}, %[ngf]", f"s_cmp_eq_u32 s{S_CH}, 1", f"s_cselect_b32 s{S_NG}, %[ngl], s{S_NG}", f"s_mov_b32 s{S_LEFT_}, s{S_NG}"]
 
     def boundary(next_set, resume):
         u = uid()
         if not refill:
             L = ["s_waitcnt lgkmcnt(0)"]
+        elif rows:
+            L = start_load(first=False) + ["s_waitcnt lgkmcnt(0)",  # this chunk's last elements, the reads issued for a trip that does not come, the start
+                 f".Lnmore{u}:", f"s_cmp_eq_u32 s{S_K}, 0", f"s_cbranch_scc1 .Lnnomore{u}"] + dma_piece() + [f"s_branch .Lnmore{u}", f".Lnnomore{u}:"]
         elif LB is not None:
             piece = dma_piece()
             L = ["s_waitcnt lgkmcnt(0)", f".Lnmore{u}:"] + piece[:-1] + [f"s_branch .Lnmore{u}"] + piece[-1:]
@@ -994,7 +1054,10 @@ def block_exact_nd(name, nq, nk=4, nw=16, refill=True, octet=False):
         L += refill_params(first=False) + chunk_groups() + first_reads(next_set) + [f"s_branch {resume}"]
         return L
 
-    L = [f"s_mov_b32 s{S_PRIO}, %[rank]", f"s_mov_b32 s{S_RANK}, %[rank]"]
+    if rows:
+        L = [f"s_lshr_b32 s{S_RANK}, %[pkb], 30", f"s_mov_b32 s{S_PRIO}, s{S_RANK}"]
+    else:
+        L = [f"s_mov_b32 s{S_PRIO}, %[rank]", f"s_mov_b32 s{S_RANK}, %[rank]"]
     # float out[N_SAMPLES] = {0.0} (mimo.cpp:122), here and not in front of the block: the accumulators are outputs only, so the compiler
     # holds none of their registers while it computes the block's inputs
     L += [f"v_mov_b32 v{r}, 0" for q in range(nq) for p in range(4) for r in range(O[q][p], O[q][p] + w)]
@@ -1004,16 +1067,21 @@ def block_exact_nd(name, nq, nk=4, nw=16, refill=True, octet=False):
     L += ["s_cmp_eq_u64 %[qptr], 0", "s_cbranch_scc1 .LNnoq_%=", "s_mov_b64 exec, 1",
           f"v_mov_b32 v{TT}, 0", f"v_mov_b32 v{TT + 1}, 1", f"global_atomic_add %[ticket], v{TT}, v{TT + 1}, %[qptr] sc0",
           "s_mov_b64 exec, -1", ".LNnoq_%=:"]
-    L += [f"s_mov_b32 s{S_M0}, m0", f"s_mov_b32 s{S_CH}, %[nch]", f"s_mov_b32 s{S_DELTA}, %[delta]",
-          f"s_mov_b64 s[{S_SB}:{S_SB + 1}], %[isrc]", f"s_mov_b32 s{S_DST}, %[ddst]"]
-    L += refill_params(first=True)
+    if rows:
+        L += [f"s_mov_b32 s{S_M0}, m0", f"s_bfe_u32 s{S_CH}, %[pka], {F_NCH}", f"s_mov_b32 s{S_DELTA}, %[delta]", f"s_mov_b32 s{S_DSTB}, %[ddst]"]
+        L += start_load(first=True)
+    else:
+        L += [f"s_mov_b32 s{S_M0}, m0", f"s_mov_b32 s{S_CH}, %[nch]", f"s_mov_b32 s{S_DELTA}, %[delta]",
+              f"s_mov_b64 s[{S_SB}:{S_SB + 1}], %[isrc]", f"s_mov_b32 s{S_DST}, %[ddst]"]
+        L += refill_params(first=True)
+    first_refill = refill_params(first=True) if rows else []  # behind the lgkmcnt(0) that proves the start
     if octet:
         # set 0 = group 0's first two mics of all eight pixels; a group is two trips, out of set 0 then set 1, so a chunk always
         # ends on set 1 and hands set 0 (the next chunk's first entries) to the boundary
         L += [f"s_load_dwordx4 s[{E[0] + 4 * P}:{E[0] + 4 * P + 3}], %[ptr], {hex(32 * P)}" for P in range(4)]
         L += [f"s_load_dwordx4 s[{E[0] + 4 * P}:{E[0] + 4 * P + 3}], %[ptr], %[qstride] offset:{hex(32 * (P - 4))}" for P in range(4, 8)]
         L += chunk_groups() + [f"s_movk_i32 s{S_PF_}, 0x10"]
-        L += ["s_waitcnt lgkmcnt(0)"] + first_reads(E[0])
+        L += ["s_waitcnt lgkmcnt(0)"] + first_refill + first_reads(E[0])
         L += [".LN0_0_%=:"] + trip_oct(0) + trip_oct(1)
         L += [f"s_sub_u32 s{S_LEFT_}, s{S_LEFT_}, 1", f"s_cmp_lg_u32 s{S_LEFT_}, 0", "s_cbranch_scc1 .LN0_0_%="]
         L += boundary(E[0], ".LN0_0_%=")
@@ -1022,7 +1090,7 @@ def block_exact_nd(name, nq, nk=4, nw=16, refill=True, octet=False):
         L += chunk_groups() + [f"s_movk_i32 s{S_PF_}, 0x80"]
         if nq > 1:
             L += [f"s_mov_b32 s{S_PFO}, %[qstride]"]
-        L += ["s_waitcnt lgkmcnt(0)"] + first_reads(E[0])
+        L += ["s_waitcnt lgkmcnt(0)"] + first_refill + first_reads(E[0])
     # quad q's trips: .LNq_0 runs out of set 0, .LNq_1 out of set 1; a quad's chunk that ends on a trip out of set s hands set 1 - s
     # (already loaded: the next quad's, or -- after the last quad -- the first quad's entries of the next chunk) to what follows
     for q in range(0 if octet else nq):
@@ -1061,6 +1129,31 @@ def block_exact_nd(name, nq, nk=4, nw=16, refill=True, octet=False):
     acc_ops = ", ".join(f'"=&{{v[{O[q][p]}:{O[q][p] + w - 1}]}}"(O{q}{p})' for q in range(nq) for p in range(4))
     qs_param = ", int qstride" if nq > 1 else ""
     qs_op = ', [qstride] "s"(qstride)' if nq > 1 else ""
+    if rows:
+        return f"""// Reference-order sweep of a whole item (frame pair x tile) on the {{next, d}} layout, {nq} quad(s) of four vertically adjacent
+// pixels per wave: tools/gen_trip_asm.py, block_exact_nd.  `row` = the first quad's entries of the item's first group in the quad-major
+// table ([group][pixel][mic] x (fraction, address), contiguous across chunks){"; the second quad's lie qstride bytes on" if nq > 1 else ""}; reads one group
+// past a quad's last.  pka = groups of four mics in a full chunk | in the last chunk << 8 | chunks << 16.  The refill is by whole rows: this
+// wave copies ITS row of every chunk (row `wave` of the chunk), from the row's start on -- isrc = its row of chunk 0 in HBM (chunk c's lies
+// c x dbf bytes on), stcur = its entry of the tile's start table (bytes; chunk c's lies 4 x mics of a chunk x c bytes on) -- in pieces of
+// 1 KiB to ddst = its row's place in the image chunk 0 does NOT occupy; delta = (that image) - (chunk 0's image) in bytes; pkb = pieces of
+// a row for this wave in a full chunk | in the last chunk << 8 | in the NEXT item's first chunk << 16 (0 = that chunk has no row for this
+// wave, or there is no next item) | (64 - lanes of a row's last piece) << 24 | rank << 30; nsrc / stnext = the next item's row and start,
+// refilled beside this item's last chunk; lbytes = 16 x lane; lane_addr = the sweep's LDS address in chunk 0's image on entry, in the last
+// chunk's on exit; qptr != null (one wave of the workgroup): lane 0 adds 1 to that counter (device scope) and `ticket` returns what it held.
+// O_qp (outputs: the block zeroes them itself) = out[l + 64 k] of pixel p of quad q, both frames, pinned at v[{ND_ACC} + {4 * w} q + {w} p ..]; temps v{vregs[0]}..v{vregs[-1]}, s{sregs[0]}..s{sregs[-1]}.
+// Executes as many s_barrier instructions as the item has chunks.
+__device__ __forceinline__ void {name}({acc_params}, const void *row{qs_param}, unsigned pka, unsigned &lane_addr, unsigned pkb,
+                                       const void *isrc, unsigned dbf, const void *nsrc, unsigned ddst, int delta, unsigned lbytes,
+                                       const void *stcur, const void *stnext, const unsigned *qptr, unsigned &ticket) {{
+    asm volatile(
+{body}
+        : {acc_ops}, [lane] "+v"(lane_addr), [ticket] "=&v"(ticket)
+        : [ptr] "s"(row){qs_op}, [pka] "s"(pka), [pkb] "s"(pkb), [isrc] "s"(isrc), [dbf] "s"(dbf), [nsrc] "s"(nsrc), [ddst] "s"(ddst),
+          [delta] "s"(delta), [lbytes] "v"(lbytes), [stcur] "s"(stcur), [stnext] "s"(stnext), [qptr] "s"(qptr)
+        : {clobbers});
+}}
+"""
     return f"""// Reference-order sweep of a whole item (frame pair x tile) on the {{next, d}} layout, {nq} quad(s) of four vertically adjacent
 // pixels per wave: tools/gen_trip_asm.py, block_exact_nd.  `row` = the first quad's entries of the item's first group in the quad-major
 // table ([group][pixel][mic] x (fraction, address), contiguous across chunks){"; the second quad's lie qstride bytes on" if nq > 1 else ""}; reads one group
