@@ -20,7 +20,7 @@ OPENCV_CFLAGS ?= -Itests/host/mock_opencv
 .PHONY: lib oracle host-test example trips clean
 lib: $(LIB)
 
-$(LIB): $(KERNEL_SRC) $(CSRC)/awpu_handle.h $(CSRC)/das_kernels.h $(CSRC)/block_kernels.h $(CSRC)/watch_kernels.h $(CSRC)/das_fast_trip.inc include/awpu_hip.h include/awpu_hip_track.h \
+$(LIB): $(KERNEL_SRC) $(CSRC)/awpu_handle.h $(CSRC)/das_kernels.h $(CSRC)/sweep_plan.h $(CSRC)/nd_tile_window.h $(CSRC)/block_kernels.h $(CSRC)/watch_kernels.h $(CSRC)/das_fast_trip.inc include/awpu_hip.h include/awpu_hip_track.h \
         include/awpu_hip_blocks.h include/awpu_hip_listen.h include/awpu_hip_watch.h
 	$(HIPCC) --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -Wall -Wno-unused-result -Werror=inline-asm -x hip \
 	    -Iinclude -I$(CSRC) $(KERNEL_SRC) -o $@

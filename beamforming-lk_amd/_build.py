@@ -22,7 +22,7 @@ SOURCES = [CSRC / "das_kernels.hip", CSRC / "das_fast.hip", CSRC / "track_kernel
 # (not tracked: ~19 000 lines of asm text whose source is the generator)
 GENERATOR = REPO / "tools" / "gen_trip_asm.py"
 TRIP_INC = CSRC / "das_fast_trip.inc"
-HEADERS = [CSRC / "awpu_handle.h", CSRC / "das_kernels.h", CSRC / "block_kernels.h", CSRC / "watch_kernels.h", CSRC / "nd_tile_window.h", GENERATOR, REPO / "include" / "awpu_hip.h", REPO / "include" / "awpu_hip_track.h",
+HEADERS = [CSRC / "awpu_handle.h", CSRC / "das_kernels.h", CSRC / "block_kernels.h", CSRC / "watch_kernels.h", CSRC / "nd_tile_window.h", CSRC / "sweep_plan.h", GENERATOR, REPO / "include" / "awpu_hip.h", REPO / "include" / "awpu_hip_track.h",
            REPO / "include" / "awpu_hip_blocks.h", REPO / "include" / "awpu_hip_listen.h", REPO / "include" / "awpu_hip_watch.h"]
 
 

@@ -394,6 +394,18 @@ namespace awpu::host {
 // Everything else -- chunk geometry, XCD pair groups, persistent workgroups, priority variants, cycle stamps -- exists only in
 // builds with -DAWPU_TUNING_BUILD (AWPU_EXTRA_HIPCC_FLAGS; -DAWPU_TIMING_BUILD implies it), which read the round-1..3 variables
 // (AWPU_FAST_*, AWPU_FIR8_*, AWPU_QUAD_VARIANT, AWPU_EXACT_PAIRS) as before.  Read once per process.
+// what sweeps AWPU_MATH_F32_EXACT (AWPU_SHAPE=exact_*; the values are those AWPU_EXACT_PAIRS=<n> of a tuning build takes)
+enum class ExactShape : int {
+    kVerify = 0,   // the round-1 verification kernel (das_exact_kernel)
+    kDefault = 1,  // launch()'s rule
+    kPair = 2,     // the two-pixel reference-order block even where quads would run
+    kQuad = 3,     // round 4's quad kernel on raw sample pairs (cur - next per pixel)
+    kNd1 = 4,      // the {next, d} kernel with one quad per wave
+    kNd2 = 5,      // ... with two
+    kNdp = 6,      // single frames: one pixel per wave (das_exact_ndp_kernel) wherever its rows can be chunked
+};
+inline bool forces_exact_nd(ExactShape e) { return e == ExactShape::kNd1 || e == ExactShape::kNd2 || e == ExactShape::kNdp; }
+
 struct EnvKnobs {
     int fpi = 0, ppw = 0, nw = 0;  // single-frame shape forced: frames per item (always 1 here), pixels per wave, 8 / 32
     int pairs = -1;                // 0 / 1: never / always a frame-pair sweep (quad, stationary or pair shape) for batches >= 2
@@ -408,7 +420,7 @@ struct EnvKnobs {
     int wgs = 0;                   // tuning: persistent workgroups of the quad shape (0 = default rule, -1 = one workgroup per item)
     int live_graph = 1;            // AWPU_LIVE_GRAPH
     int halves = -1;               // 1: single frames on the halves layout for every call (where the quad table is built)
-    int exact_pairs = 1;           // 0: AWPU_MATH_F32_EXACT on the round-1 verification kernel (das_exact_kernel)
+    ExactShape exact_pairs = ExactShape::kDefault;
     int pair_cols = -1;            // 0 / 1: the pair shape pairs consecutive / vertically adjacent pixels (default: whichever coincides more)
     int group_copy = 0;            // AWPU_GROUP_FORCE_COPY
     int listen_stream = 1;         // tuning: 0 = the listen kernels queue behind the sweeps instead of running beside them

@@ -69,12 +69,12 @@ awpu::host::EnvKnobs::EnvKnobs() {
         else if (shape == "single_db") pairs = 0, quads = 0, fpi = 1, ppw = 8, nw = 32;
         else if (shape == "single_small") pairs = 0, quads = 0, fpi = 1, ppw = 2, nw = 8;
         else if (shape == "fir8_planes") fir_planes = 2;
-        else if (shape == "exact_verify") exact_pairs = 0;
-        else if (shape == "exact_pair") exact_pairs = 2;  // the two-pixel reference-order block even where quads would run
-        else if (shape == "exact_quad") exact_pairs = 3;  // round 4's quad kernel on raw sample pairs (cur - next per pixel)
-        else if (shape == "exact_nd1") exact_pairs = 4;   // the {next, d} kernel with one quad per wave
-        else if (shape == "exact_nd2") exact_pairs = 5;   // ... with two
-        else if (shape == "exact_ndp") exact_pairs = 6;   // single frames: one pixel per wave (das_exact_ndp_kernel) wherever its rows can be chunked
+        else if (shape == "exact_verify") exact_pairs = ExactShape::kVerify;
+        else if (shape == "exact_pair") exact_pairs = ExactShape::kPair;
+        else if (shape == "exact_quad") exact_pairs = ExactShape::kQuad;
+        else if (shape == "exact_nd1") exact_pairs = ExactShape::kNd1;
+        else if (shape == "exact_nd2") exact_pairs = ExactShape::kNd2;
+        else if (shape == "exact_ndp") exact_pairs = ExactShape::kNdp;
         else std::fprintf(stderr, "libawpu_hip: AWPU_SHAPE=%s is not a shape of this build; ignored\n", v);
     }
 #ifdef AWPU_TUNING_BUILD
@@ -83,7 +83,7 @@ awpu::host::EnvKnobs::EnvKnobs() {
     if (const char *v = std::getenv("AWPU_FAST_PAIRGROUP")) pair_group = std::atoi(v);
     if (const char *v = std::getenv("AWPU_QUAD_VARIANT")) quad_variant = std::atoi(v);
     if (const char *v = std::getenv("AWPU_FAST_HALVES")) halves = std::atoi(v);
-    if (const char *v = std::getenv("AWPU_EXACT_PAIRS")) exact_pairs = std::atoi(v);
+    if (const char *v = std::getenv("AWPU_EXACT_PAIRS")) exact_pairs = (ExactShape) std::atoi(v);
     if (const char *v = std::getenv("AWPU_FAST_WGS")) wgs = std::atoi(v);
     if (const char *v = std::getenv("AWPU_FIR8_PLANES")) fir_planes = std::atoi(v);
     if (const char *v = std::getenv("AWPU_FIR8_SHARE")) fir_share = std::atoi(v);

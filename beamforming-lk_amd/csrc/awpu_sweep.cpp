@@ -1,7 +1,8 @@
 // awpu_sweep.cpp -- the sweep layer of libawpu_hip.so: from a prepared handle and a batch of frames to kernel launches.  In order:
-// the diagnostics of the stamped builds, prepare() and the table builders, the small rules every launcher shares (CU count, XCD pair
-// group, item queues), one launcher per kernel, the dispatch rule (choose_shape decides, launch switches) and the packed-frame
-// forms of it.  What awpu_hip.cpp and awpu_runs.cpp call here is declared in awpu_handle.h.
+// the diagnostics of the stamped builds, prepare() and the table builders, the small rules every launcher shares (CU count, item
+// queues; the XCD pair group is sweep_plan.h's, beside the planners), one launcher per kernel, the dispatch rule (choose_shape
+// decides, launch switches) and the packed-frame forms of it.  What awpu_hip.cpp and awpu_runs.cpp call here is declared in
+// awpu_handle.h.
 #include "awpu_handle.h"
 
 #include <algorithm>
@@ -331,19 +332,19 @@ namespace {
 // The fast kernel's table for `fpi` frames per item: per (pixel, active mic s) the weights and
 // the LDS byte address of X[off] inside the staged image (das_fast.hip), rows padded to whole
 // groups of four with null entries (zero weights, address of a staged row).
-int build_fast_lut(awpu_hip *h, int fpi, int image_bytes, const awpu_hip::FastLut **out) {
+int build_fast_lut(awpu_hip *h, awpu::PackLayout layout, int fpi, int image_bytes, const awpu_hip::FastLut **out) {
     for (const auto &l : h->fast_luts)
-        if (l.plan.fpi == fpi && l.plan.image_bytes == image_bytes) {
+        if (l.plan.layout == layout && l.plan.fpi == fpi && l.plan.image_bytes == image_bytes) {
             *out = &l;
             return AWPU_OK;
         }
     const auto &c = h->cfg;
     const int U = h->usable(), P = c.pixel_count;
     awpu_hip::FastLut lut;
-    const bool pairs = image_bytes < 0;  // frame-pair layout: one image row per mic, 8-byte elements
-    const bool planned = image_bytes == -2 ? awpu::pair_plan_stationary(h->window, U, &lut.plan)  // every mic resident
-                         : pairs         ? awpu::pair_plan(h->window, U, &lut.plan)
-                                         : awpu::fast_plan(h->window, U, fpi, image_bytes, &lut.plan);
+    const bool pairs = layout != awpu::PackLayout::kSingle;  // frame-pair layout: one image row per mic, 8-byte elements
+    const bool planned = layout == awpu::PackLayout::kPairsStationary ? awpu::pair_plan_stationary(h->window, U, &lut.plan)  // every mic resident
+                         : pairs                                        ? awpu::pair_plan(h->window, U, &lut.plan)
+                                                                        : awpu::fast_plan(h->window, U, fpi, image_bytes, &lut.plan);
     if (!planned) return invalid("delay window does not fit the LDS budget");
     const awpu::FastPlan &plan = lut.plan;
     // rows for whole pixel tiles (the kernels sweep every pixel slot of a workgroup; slots past the
@@ -551,17 +552,6 @@ int cu_count(awpu_hip *h) {
     return h->n_cus;
 }
 
-// Frame pairs an XCD works on at a time: as many as keep their samples (pair_bytes each) in its 4 MiB L2 beside the table stream.
-// (Eight pairs at the headline shape, 5.9 MB of samples, run 1.2 % faster than four -- fewer table passes --
-// but the samples then stream from beyond the L2: 3.2 GB of L2 misses per launch instead of 0.72 GB.  Not taken.)
-// `forced`: AWPU_FAST_PAIRGROUP of the tuning builds.
-int xcd_pair_group(size_t pair_bytes, int n_pairs, int forced = 0) {
-    int g = forced > 0 ? forced : (int) std::max<size_t>(1, (3u << 20) / pair_bytes);
-    g = g >= 8 ? 8 : g >= 4 ? 4 : g >= 2 ? 2 : 1;
-    while (g > 1 && g > n_pairs) g >>= 1;
-    return g;
-}
-
 // Persistent workgroups (one per CU) that take their `items` from queues, one per XCD: an eighth of every XCD's run goes to the
 // queue common to the chip (the XCDs' speeds differ by ~6 %); short runs: one queue for the chip.
 int arm_item_queues(awpu_hip *h, int items, unsigned **queue, int32_t *wgs, int32_t *tail) {
@@ -601,7 +591,7 @@ int launch_exact_pairs(awpu_hip *h, const float *d_frames, int batch, float *d_p
     a.cols = h->pair_cols;
     a.tiles = awpu::pair_tiles(a.pixel_count, a.cols);
     a.n_pairs = (batch + 1) / 2;
-    a.pair_group = xcd_pair_group((size_t) pp.usable_pad * pp.wr * 8, a.n_pairs);
+    a.pair_group = awpu::xcd_pair_group((size_t) pp.usable_pad * pp.wr * 8, a.n_pairs);
     if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
     AWPU_HIP_TRY(awpu::launch_pack_pairs(d_frames, h->cfg.n_streams, hist_eff, wstart_eff, h->d_index, h->usable(), pp.usable_pad,
                                          h->d_gain, pp.wr, batch, h->d_pack, false, s));  // raw samples: no stencil in front of the reference's order
@@ -625,7 +615,7 @@ int launch_exact_quads(awpu_hip *h, const float *d_frames, int batch, float *d_p
     a.rows = h->cfg.pixel_count / a.cols;
     a.tiles = awpu::quad_tiles(a.rows, a.cols);
     a.n_pairs = (batch + 1) / 2;
-    a.pair_group = xcd_pair_group((size_t) pp.usable_pad * pp.wr * 8, a.n_pairs);
+    a.pair_group = awpu::xcd_pair_group((size_t) pp.usable_pad * pp.wr * 8, a.n_pairs);
     if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
     AWPU_HIP_TRY(awpu::launch_pack_pairs(d_frames, h->cfg.n_streams, hist_eff, wstart_eff, h->d_index, h->usable(), pp.usable_pad,
                                          h->d_gain, pp.wr, batch, h->d_pack, false, s));
@@ -656,7 +646,7 @@ int launch_exact_nd(awpu_hip *h, const float *d_frames, int batch, float *d_powe
     a.nq = nq;
     a.tiles = awpu::nd_tiles(a.rows, a.cols, nq);
     a.n_pairs = (batch + 1) / 2;
-    a.pair_group = xcd_pair_group((size_t) pp.usable_pad * pp.wr * 16, a.n_pairs, env().pair_group);
+    a.pair_group = awpu::xcd_pair_group((size_t) pp.usable_pad * pp.wr * 16, a.n_pairs, env().pair_group);
     // Four pairs instead of two where four pairs' rows are at most 6 MiB (the headline: 5.7 MB): every XCD then walks the table twice per
     // launch instead of four times, and a tile stages only its window of a row.  Alternating runs on one box: -0.30 % (5.378 against
     // 5.394 ms per step; profiles/r13_tile_window_rate.txt).  Larger pairs (c3, the c5 slab) keep the rule above: not measured.
@@ -704,16 +694,16 @@ int launch_exact_nd(awpu_hip *h, const float *d_frames, int batch, float *d_powe
 // and of the packed-frame entry points: asked before anything is packed.)
 bool takes_exact_nd(awpu_hip *h, int batch, int *nq) {
     if (!h->exact_pairs_ok || !h->exact_nd_ok || h->cfg.grid_columns < 1) return false;
-    const int ex = env().exact_pairs;
-    if (ex == 0 || ex == 2 || ex == 3) return false;  // AWPU_SHAPE=exact_verify / exact_pair / exact_quad
+    const ExactShape ex = env().exact_pairs;
+    if (ex == ExactShape::kVerify || ex == ExactShape::kPair || ex == ExactShape::kQuad) return false;
     const int cols = h->cfg.grid_columns, rows = h->cfg.pixel_count / cols;
     // (quad_differ < 1.5: on average fewer than half of a quad's pixels leave the reference pixel's address for a mic; a square
     // array's vertical and horizontal neighbours coincide equally often -- pair_cols stays 0 there -- and quads still pay)
     const bool quads_pay = h->cfg.pixel_count % cols == 0 && h->cfg.pixel_begin % cols == 0 && h->quad_differ < 1.5;
-    if ((!(h->pair_cols > 0 || quads_pay) && ex != 4 && ex != 5 && ex != 6) || rows < 4) return false;  // (a forced shape runs on any table: the random tests)
+    if ((!(h->pair_cols > 0 || quads_pay) && !forces_exact_nd(ex)) || rows < 4) return false;  // (a forced shape runs on any table: the random tests)
     // two quads per wave where that still fills the chip (AWPU_SHAPE=exact_nd1 / exact_nd2: one / two everywhere)
     const long wgs2 = (long) awpu::nd_tiles(rows, cols, 2) * ((batch + 1) / 2);
-    *nq = ex == 4 ? 1 : ex == 5 ? 2 : (rows >= 8 && wgs2 >= 512 ? 2 : 1);
+    *nq = ex == ExactShape::kNd1 ? 1 : ex == ExactShape::kNd2 ? 2 : (rows >= 8 && wgs2 >= 512 ? 2 : 1);
     return true;
 }
 
@@ -824,6 +814,7 @@ int launch_fir8_planes(awpu_hip *h, const float *d_frames, int batch, float *d_p
     fill_shared(pa, h, pp, batch, d_power);
     pa.packed = h->d_pack;
     pa.wp = pp.wr;
+    pa.pair_group = awpu::xcd_pair_group((size_t) U * pp.wr * 8, (batch + 1) / 2);
     // vertical pixel quads (samples shared between pixels of one column with the same integer delay) where the grid's row
     // length is known and the rows are staged at the pitch that block is generated for; AWPU_FIR8_SHARE=0: consecutive pixels
     if (env().fir_share != 0 && cols > 0 && P % cols == 0 && h->cfg.pixel_begin % cols == 0 && (uint32_t) pp.wr * 2u == awpu::kFirStaticPlaneBytesHost)
@@ -859,7 +850,7 @@ int launch_pairs(awpu_hip *h, const awpu_hip::FastLut *plut, const float *d_fram
     pa.cols = h->pair_cols;
     pa.tiles = awpu::pair_tiles(h->cfg.pixel_count, h->pair_cols);
     pa.n_pairs = (batch + 1) / 2;
-    pa.pair_group = xcd_pair_group((size_t) h->usable() * pp.wr * 8, pa.n_pairs);
+    pa.pair_group = awpu::xcd_pair_group((size_t) h->usable() * pp.wr * 8, pa.n_pairs);
     pa.debug = env().debug;
     size_t n_waves = 0;
     if (stationary_tiles > 0) pa.debug &= ~16;  // (no stamped build of the stationary shape)
@@ -898,7 +889,7 @@ int launch_quads(awpu_hip *h, const float *d_frames, int batch, float *d_power, 
     qa.rows = h->cfg.pixel_count / qa.cols;
     qa.tiles = awpu::quad_tiles(qa.rows, qa.cols);
     qa.n_pairs = (batch + 1) / 2;
-    qa.pair_group = xcd_pair_group((size_t) pp.usable_pad * pp.wr * 8, qa.n_pairs, env().pair_group);
+    qa.pair_group = awpu::xcd_pair_group((size_t) pp.usable_pad * pp.wr * 8, qa.n_pairs, env().pair_group);
     qa.debug = env().debug;
     qa.variant = env().quad_variant;
     // Persistent workgroups (one per CU, each walking its share of the items with the next item's first chunk
@@ -996,7 +987,7 @@ int launch_quadsh_stationary(awpu_hip *h, const float *d_frames, int batch, floa
 int launch_single(awpu_hip *h, const float *d_frames, int batch, float *d_power, hipStream_t s, int layout, int hist_eff, int wstart_eff,
                   int fpi, int ppw, int nw) {
     const awpu_hip::FastLut *lut = nullptr;
-    int rc = build_fast_lut(h, fpi, awpu::fast_image_bytes(nw), &lut);
+    int rc = build_fast_lut(h, awpu::PackLayout::kSingle, fpi, awpu::fast_image_bytes(nw), &lut);
     if (rc != AWPU_OK) return rc;
     const awpu::FastPlan &plan = lut->plan;
     awpu::FastArgs a{};
@@ -1068,8 +1059,8 @@ ShapeChoice choose_shape(awpu_hip *h, int batch, int layout, int hist_eff, int w
     if (h->fir_planes_ok && env().pairs != 0 && env().fir_planes &&
         (fir_wgs >= (batch >= 2 ? 256 : 192) || (env().fir_planes == 2 && batch >= 2)))
         return {kShapeFir8Planes};
-    const int ex = env().exact_pairs;
-    if (h->exact_pairs_ok && ex != 0) {
+    const ExactShape ex = env().exact_pairs;
+    if (h->exact_pairs_ok && ex != ExactShape::kVerify) {
         // vertical pixel quads on the {next, d} layout (round 5) where the row length is known and the table's statistics favour them
         // (takes_exact_nd; AWPU_SHAPE=exact_quad: round 4's kernel on raw sample pairs; exact_pair: the two-pixel block everywhere)
         int nq = 1;
@@ -1077,7 +1068,7 @@ ShapeChoice choose_shape(awpu_hip *h, int batch, int layout, int hist_eff, int w
         // one frame per call (MIMOWorker::update's regime): the halves form of the layout -- the two packed lanes are the two halves of
         // the block, not a frame and its copy; every mic resident where one array's rows fit the LDS (no pre-pass)
         const bool grid_known = cols >= 1 && P % cols == 0;
-        if (batch == 1 && (ex == 1 || ex == 6) && grid_known && (h->exact_ndhs_ok || h->exact_ndh_ok)) {
+        if (batch == 1 && (ex == ExactShape::kDefault || ex == ExactShape::kNdp) && grid_known && (h->exact_ndhs_ok || h->exact_ndh_ok)) {
             // grids of at most 32 pixels per CU (two rounds of 16-wave workgroups): one PIXEL per wave (das_exact_ndp_kernel) -- a quad
             // kernel leaves such a grid one or two waves per SIMD, and the frame then takes as long as one wave's instruction issue.
             // Measured, 256 mics, one frame per call, quads -> pixels: 64 x 64 69.1 -> 31.6 us; 72^2 69.3 -> 52.1; 80^2 67.2 -> 53.3;
@@ -1086,7 +1077,7 @@ ShapeChoice choose_shape(awpu_hip *h, int batch, int layout, int hist_eff, int w
             // One array (every mic resident in the quad kernel, no pre-pass) against pixels behind the pre-pass: 32^2 (its quads do not
             // share: das_exact_pair_kernel) 36.9 -> 10.4 us; 48^2 22.3 -> 10.8; 64^2 21.1 -> 11.5; 80^2 20.3 -> 18.6; 100^2 (three rounds) 21.3 -> 26.0
             bool solo = h->exact_ndh_ok && awpu::ndp_tiles(rows, cols) * (long) batch <= 2L * cu_count(h);
-            if (ex == 6) solo = h->exact_ndh_ok;
+            if (ex == ExactShape::kNdp) solo = h->exact_ndh_ok;
 #ifdef AWPU_TUNING_BUILD
             if (const char *v = std::getenv("AWPU_NDH_WAVES")) solo = std::atoi(v) == 1 && h->exact_ndh_ok;
 #endif
@@ -1096,7 +1087,7 @@ ShapeChoice choose_shape(awpu_hip *h, int batch, int layout, int hist_eff, int w
             if (nd) return {kShapeExactNdh, (long) awpu::quad1_tiles(rows, cols, 2) >= 256 ? 2 : 1, h->exact_ndhs_ok};
         }
         if (nd) return {kShapeExactNd, nq};
-        if (ex == 3 && h->pair_cols > 0 && rows >= 4) return {kShapeExactQuads};
+        if (ex == ExactShape::kQuad && h->pair_cols > 0 && rows >= 4) return {kShapeExactQuads};
         return {kShapeExactPairs};
     }
     // (the pre-epilogue sums: the frame-pair reference-order kernels above and das_fir8_kernel with the reference's rounding only)
@@ -1181,10 +1172,10 @@ int launch(awpu_hip *h, const float *d_frames, int batch, float *d_power, hipStr
     case kShapeExact: return launch_exact(h, d_frames, batch, d_power, s, hist_eff, wstart_eff);
     case kShapeQuads: return launch_quads(h, d_frames, batch, d_power, s, hist_eff, wstart_eff);
     case kShapePairsStationary:
-        if (const int rc = build_fast_lut(h, 2, -2, &lut); rc != AWPU_OK) return rc;
+        if (const int rc = build_fast_lut(h, awpu::PackLayout::kPairsStationary, 2, 0, &lut); rc != AWPU_OK) return rc;
         return launch_pairs(h, lut, d_frames, batch, d_power, s, hist_eff, wstart_eff, c.tiles_per_wg);
     case kShapePairs:
-        if (const int rc = build_fast_lut(h, 2, -1, &lut); rc != AWPU_OK) return rc;
+        if (const int rc = build_fast_lut(h, awpu::PackLayout::kPairs, 2, 0, &lut); rc != AWPU_OK) return rc;
         return launch_pairs(h, lut, d_frames, batch, d_power, s, hist_eff, wstart_eff);
     case kShapeQuadsh: return launch_quadsh(h, d_frames, batch, d_power, s, hist_eff, hist_ring, wstart_eff, c.qpw);
     case kShapeQuadshStationary: return launch_quadsh_stationary(h, d_frames, batch, d_power, s, hist_eff, hist_ring, wstart_eff, c.qpw);
@@ -1213,7 +1204,7 @@ bool takes_packed_pairs(awpu_hip *h, int batch, awpu::FastPlan *plan) {
 // elements), `usable` rows per pair (the packed entry points ask for usable % 4 == 0: no padding rows)
 size_t packed_floats_of(const awpu_hip *h, const awpu::FastPlan &plan, int batch) {
     // (the {next, d} plan's row_bytes is its LDS row, the tile window; its packed rows hold wr elements of four floats)
-    return (size_t) ((batch + 1) / 2) * h->usable() * (size_t) (plan.image_bytes == -4 ? plan.wr * 4 : plan.row_bytes / 4);
+    return (size_t) ((batch + 1) / 2) * h->usable() * (size_t) (plan.layout == awpu::PackLayout::kNd ? plan.wr * 4 : plan.row_bytes / 4);
 }
 
 // the sweep's pack pass into a caller's buffer: pre-filtered sample pairs (FAST) or {next, d} elements (EXACT)
@@ -1240,7 +1231,7 @@ int sweep_packed(awpu_hip *h, const awpu::FastPlan &plan, const float *d_packed,
     if (fast_batch_takes_quads(h, batch) && quad_plan_is(h, plan))
         return launch_quads(h, nullptr, batch, d_power, s, h->cfg.hist, h->wstart, d_packed, packed_floats);
     const awpu_hip::FastLut *plut = nullptr;
-    const int rc = build_fast_lut(h, 2, -1, &plut);
+    const int rc = build_fast_lut(h, awpu::PackLayout::kPairs, 2, 0, &plut);
     if (rc != AWPU_OK) return rc;
     return launch_pairs(h, plut, nullptr, batch, d_power, s, h->cfg.hist, h->wstart, 0, d_packed, packed_floats);
 }

@@ -34,8 +34,9 @@
 // (off & 1) -- a misaligned ds_read_b64 is a 64-cycle replay:
 //         A += f*x   -> out[2l], out[2l+1]          Q += g*x   -> out[2l-1], out[2l]
 //         C += f*y   -> out[128+2l], out[129+2l]    R += g*y   -> out[127+2l], out[128+2l]
+// Host side (bottom of this file): one launcher per kernel, each refusing what its kernel could not read.  How many mics a chunk
+// holds and which layouts fit the LDS is planned in sweep_plan.h (host only, tested on the CPU).
 #include "das_kernels.h"
-#include "nd_tile_window.h"
 
 #include <algorithm>
 #include <atomic>
@@ -114,7 +115,7 @@ __device__ __forceinline__ void sweep_group(Acc<FPI> &acc, const EntryGroup &e, 
 }
 
 #include "das_fast_trip.inc"
-static_assert(kFirStaticPlaneBytes == kFirStaticPlaneBytesHost, "das_kernels.h and tools/gen_trip_asm.py disagree on the FIR8 plane pitch");
+static_assert(kFirStaticPlaneBytes == kFirStaticPlaneBytesHost, "sweep_plan.h and tools/gen_trip_asm.py disagree on the FIR8 plane pitch");
 
 // The items of one wave for one staged chunk: PPW pixels x ng groups of four, one frame per
 // item, each pixel through one hand-scheduled asm block (das_fast_trip.inc).
@@ -2521,7 +2522,6 @@ __global__ __launch_bounds__(1024, 4) void das_quadh_kernel(QuadhArgs a) {
 // no refill.  LDS: [usable][raw_wr] floats raw + [usable_pad][wp] elements + a 4 KiB row table <= 156 KiB.
 // Table: the quad-major table with slot = mic (build_quad_lut, kQuadHalvesStationary).  grid = (frames, tiles).
 // ---------------------------------------------------------------------------------------
-constexpr int kQuadhsRowTableOffset = (2 * kFastLdsBytes - 4096) / 4;  // floats: the last 4 KiB hold the streams' row offsets
 template <int QPW>
 __global__ __launch_bounds__(1024, 4) void das_quadh_stationary_kernel(QuadhStationaryArgs a) {
     static_assert(QPW == 1 || QPW == 2, "one or two quads per wave");
@@ -2626,44 +2626,28 @@ __global__ __launch_bounds__(1024, 4) void das_quadh_stationary_kernel(QuadhStat
 }
 
 // ---------------------------------------------------------------------------------------
-// host side: geometry of the LDS image and the launch
+// host side: the launchers.  (The geometry of the LDS images -- what a chunk holds, which layouts fit -- is planned in sweep_plan.h.)
 // ---------------------------------------------------------------------------------------
-bool fast_plan(int window, int usable, int fpi, int image_bytes, FastPlan *plan) {
-    if (fpi != 1 && fpi != 2) return false;
-    const int wr = (window + 3) & ~3;  // rows are whole 16-byte pieces (and start 16-byte aligned)
-    const size_t row_bytes = (size_t) wr * sizeof(float);
-    const size_t frame_bytes = (size_t) image_bytes / fpi;
-    int chunk = (int) (frame_bytes / (2 * row_bytes));
-    chunk &= ~3;  // whole entry groups per chunk
-    if (chunk > 64) chunk = 64;
-    if (chunk < 4) return false;
-    const int usable_pad = (usable + 3) & ~3;
-    if (chunk > usable_pad) chunk = usable_pad;
-    plan->fpi = fpi;
-    plan->wr = wr;
-    plan->chunk = chunk;
-    plan->usable_pad = usable_pad;
-    plan->row_bytes = (int) row_bytes;
-    plan->image_bytes = image_bytes;
-    return true;
-}
 
-// Kernels that ask for more than 64 KiB of dynamic LDS need the limit raised once per function AND
-// per device (a process may hold handles on several GPUs); `done` is the caller's per-function flags.
+// Kernels that ask for more than 64 KiB of dynamic LDS need the limit raised once per function AND per device (a process may hold
+// handles on several GPUs): launch_lds raises it for its kernel, launches, and reports the launch's error.
 // The flags are atomics: every worker thread launches through its own handle, and two first launches may
 // meet here (setting the attribute twice is harmless; a torn flag would not be).
-typedef std::atomic<bool> LdsFlags[64];
-static hipError_t allow_lds(const void *kernel, int bytes, LdsFlags &done) {
+template <auto Kernel, class... Args>
+static hipError_t launch_lds(dim3 grid, dim3 block, int lds_bytes, hipStream_t stream, const Args &...args) {
+    static std::atomic<bool> done[64] = {};
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     if (dev < 0 || dev >= 64 || !done[dev].load(std::memory_order_acquire)) {
-        e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        e = hipFuncSetAttribute((const void *) Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
         if (e != hipSuccess) return e;
         if (dev >= 0 && dev < 64) done[dev].store(true, std::memory_order_release);
     }
-    return hipSuccess;
+    hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, stream, args...);
+    return hipGetLastError();
 }
+constexpr int kTwoImages = 2 * kFastLdsBytes;  // what the frame-pair and the quad kernels ask for
 
 // reach of the kernels (das_kernels.h, Extents): the furthest table entry / packed float a launch can load
 static bool within(const Extents &reach, const Extents &have) {
@@ -2679,47 +2663,33 @@ static size_t quad_table_reach(int rows, int cols, int usable_pad) {
     return (size_t) quad_count(rows, cols) * (usable_pad / 4) * 16 + kQuadTablePrefetch;
 }
 
+// The shapes every launcher refuses.  Chunk geometry: whole entry groups, and a chunk's rows inside one image
+static bool chunk_fits(int chunk, int usable_pad, size_t row_bytes, size_t image_bytes = kFastLdsBytes) {
+    return chunk >= 4 && !(chunk & 3) && !(usable_pad & 3) && chunk * row_bytes <= image_bytes;
+}
+// ... the items of an XCD-grouped launch: frame pairs x tiles, as the kernel decodes them
+static bool items_agree(int n_pairs, int batch, int tiles, int tiles_of_grid, int pair_group) {
+    return n_pairs == (batch + 1) / 2 && tiles == tiles_of_grid && pair_group >= 1;
+}
+// ... and the grid whose row length the table was built for
+static bool grid_is(int rows, int cols, int pixel_count) { return cols >= 1 && rows * cols == pixel_count; }
+// one workgroup per item, in eight equal runs (one per XCD)
+static dim3 xcd_grid(long items) { return dim3((unsigned) (8 * ((items + 7) / 8))); }
+
 template <int NW, int PPW, int FPI, int WPS>
 static hipError_t launch_variant(const FastArgs &a, hipStream_t stream) {
-    static LdsFlags attr_set = {};
-    if (hipError_t e = allow_lds((const void *) das_fast_kernel<NW, PPW, FPI, WPS>, kFastLdsBytes, attr_set); e != hipSuccess)
-        return e;
     const int pix_per_block = NW * PPW;
     dim3 grid((a.batch + FPI - 1) / FPI, (a.pixel_count + pix_per_block - 1) / pix_per_block);
     if (grid.y > 65535) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((das_fast_kernel<NW, PPW, FPI, WPS>), grid, dim3(NW * 64), kFastLdsBytes, stream, a);
-    return hipGetLastError();
+    return launch_lds<das_fast_kernel<NW, PPW, FPI, WPS>>(grid, dim3(NW * 64), kFastLdsBytes, stream, a);
 }
 
 template <int NW, int PPW, int BUF, int WPS, bool DIAG>
 static hipError_t launch_db(const FastArgs &a, hipStream_t stream) {
-    static LdsFlags attr_set = {};
-    constexpr int lds_bytes = 2 * BUF + kFastSideBytes;
-    if (hipError_t e = allow_lds((const void *) das_fast_db_kernel<NW, PPW, BUF, WPS, DIAG>, lds_bytes, attr_set); e != hipSuccess)
-        return e;
     const int pix_per_block = NW * PPW;
     dim3 grid((a.batch + a.frames_per_wg - 1) / a.frames_per_wg, (a.pixel_count + pix_per_block - 1) / pix_per_block);
     if (grid.y > 65535) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((das_fast_db_kernel<NW, PPW, BUF, WPS, DIAG>), grid, dim3(NW * 64), lds_bytes, stream, a);
-    return hipGetLastError();
-}
-
-bool pair_plan(int window, int usable, FastPlan *plan) {
-    const int wp = (window + 1) & ~1;  // rows of 8-byte elements, whole 16-byte pieces
-    const size_t row_bytes = (size_t) wp * 8;
-    int chunk = (int) ((size_t) kFastLdsBytes / row_bytes);
-    chunk &= ~3;
-    if (chunk > 64) chunk = 64;
-    if (chunk < 4) return false;
-    const int usable_pad = (usable + 3) & ~3;
-    if (chunk > usable_pad) chunk = usable_pad;
-    plan->fpi = 2;
-    plan->wr = wp;
-    plan->chunk = chunk;
-    plan->usable_pad = usable_pad;
-    plan->row_bytes = (int) row_bytes;
-    plan->image_bytes = -1;  // marks the frame-pair layout
-    return true;
+    return launch_lds<das_fast_db_kernel<NW, PPW, BUF, WPS, DIAG>>(grid, dim3(NW * 64), 2 * BUF + kFastSideBytes, stream, a);
 }
 
 hipError_t launch_pack_pairs(const float *d_frames, int n_streams, int hist, int wstart, const int32_t *d_index,
@@ -2738,41 +2708,19 @@ hipError_t launch_pack_pairs(const float *d_frames, int n_streams, int hist, int
 
 template <int PPW, bool DIAG, bool SHARE>
 static hipError_t launch_pair_variant(const PairArgs &a, const Extents &have, hipStream_t stream) {
-    static LdsFlags attr_set = {};
-    constexpr int lds_bytes = 2 * kFastLdsBytes;
-    if (hipError_t e = allow_lds((const void *) das_pair_kernel<PPW, DIAG, SHARE>, lds_bytes, attr_set); e != hipSuccess) return e;
     static_assert(16 * PPW == 64, "pair_tiles() counts 64-pixel tiles");
-    if (a.n_pairs != (a.batch + 1) / 2 || a.tiles != pair_tiles(a.pixel_count, a.cols) || a.pair_group < 1) return hipErrorInvalidValue;
+    if (!items_agree(a.n_pairs, a.batch, a.tiles, pair_tiles(a.pixel_count, a.cols), a.pair_group)) return hipErrorInvalidValue;
     // reach: the last pixel's row + one group of prefetch; `usable` rows of wp elements per frame pair, in whole 16-byte pieces
     if ((a.wp & 1) || !within({pair_table_rows(a.pixel_count, a.cols) * a.usable_pad + kPairTablePrefetch,
                                (size_t) a.n_pairs * a.usable * a.wp * 2}, have))
         return hipErrorInvalidValue;
-    const long total = (long) a.n_pairs * a.tiles;
-    dim3 grid((unsigned) (8 * ((total + 7) / 8)));
-    hipLaunchKernelGGL((das_pair_kernel<PPW, DIAG, SHARE>), grid, dim3(1024), lds_bytes, stream, a);
-    return hipGetLastError();
-}
-
-bool pair_plan_stationary(int window, int usable, FastPlan *plan) {
-    const int wp = (window + 1) & ~1;
-    const size_t row_bytes = (size_t) wp * 8;
-    const int usable_pad = (usable + 3) & ~3;
-    if ((size_t) usable * row_bytes > (size_t) 2 * kFastLdsBytes) return false;  // (null entries of padding mics point at row 0)
-    plan->fpi = 2;
-    plan->wr = wp;
-    plan->chunk = usable_pad;  // every mic has its own slot: addresses are not folded into chunks
-    plan->usable_pad = usable_pad;
-    plan->row_bytes = (int) row_bytes;
-    plan->image_bytes = -2;  // marks the stationary layout
-    return true;
+    return launch_lds<das_pair_kernel<PPW, DIAG, SHARE>>(xcd_grid((long) a.n_pairs * a.tiles), dim3(1024), kTwoImages, stream, a);
 }
 
 hipError_t launch_das_pairs_stationary(const PairArgs &a, int tiles_per_wg, const Extents &have, hipStream_t stream) {
-    static LdsFlags attr_set[2] = {};
-    constexpr int lds_bytes = 2 * kFastLdsBytes;
     const int n_tiles = pair_tiles(a.pixel_count, a.cols);
     // (self-staged pairs read the caller's frames inside [0, hist) of a stream: the kernel clips to the history itself)
-    if (tiles_per_wg < 1 || (a.wp & 1) || (size_t) a.usable * a.wp * 8 > (size_t) lds_bytes ||
+    if (tiles_per_wg < 1 || (a.wp & 1) || (size_t) a.usable * a.wp * 8 > (size_t) kTwoImages ||
         (a.frames && (!a.index || a.n_streams < 1 || a.wstart < 0 || a.wstart >= a.hist)) ||
         !within({pair_table_rows(a.pixel_count, a.cols) * a.usable_pad + kPairTablePrefetch,
                  a.frames ? 0 : (size_t) ((a.batch + 1) / 2) * a.usable * a.wp * 2}, have))
@@ -2780,43 +2728,9 @@ hipError_t launch_das_pairs_stationary(const PairArgs &a, int tiles_per_wg, cons
     dim3 grid((a.batch + 1) / 2, (n_tiles + tiles_per_wg - 1) / tiles_per_wg);
     if (grid.y > 65535) return hipErrorInvalidValue;
 #ifdef AWPU_TUNING_BUILD  // debug bit 4096: the pixel-major block without read sharing (the same bits)
-    if (a.debug & 4096) {
-        if (hipError_t e = allow_lds((const void *) das_pair_stationary_kernel<false>, lds_bytes, attr_set[0]); e != hipSuccess) return e;
-        hipLaunchKernelGGL(das_pair_stationary_kernel<false>, grid, dim3(1024), lds_bytes, stream, a, n_tiles, tiles_per_wg);
-        return hipGetLastError();
-    }
+    if (a.debug & 4096) return launch_lds<das_pair_stationary_kernel<false>>(grid, dim3(1024), kTwoImages, stream, a, n_tiles, tiles_per_wg);
 #endif
-    if (hipError_t e = allow_lds((const void *) das_pair_stationary_kernel<true>, lds_bytes, attr_set[1]); e != hipSuccess) return e;
-    hipLaunchKernelGGL(das_pair_stationary_kernel<true>, grid, dim3(1024), lds_bytes, stream, a, n_tiles, tiles_per_wg);
-    return hipGetLastError();
-}
-
-bool fir8_plane_plan(int window, int usable, FastPlan *plan) {
-    int wp = (window + 3) & ~3;  // four planes of wp / 4 elements
-    // windows of 321..384 samples (every BASELINE shape but the single 8x8 array) are staged at the plane pitch the
-    // one-address block is generated for (sweep_fir8_planes_static: 33 instead of 36 VALU instructions per item);
-    // AWPU_FIR8_STATIC=0 keeps the natural pitch for A/B runs
-#ifdef AWPU_TUNING_BUILD
-    static const bool allow_static = !(std::getenv("AWPU_FIR8_STATIC") && std::atoi(std::getenv("AWPU_FIR8_STATIC")) == 0);
-#else
-    constexpr bool allow_static = true;
-#endif
-    const int wp_static = (int) (kFirStaticPlaneBytes / 2);
-    if (allow_static && wp > wp_static - 64 && wp <= wp_static) wp = wp_static;
-    const size_t row_bytes = (size_t) wp * 8;
-    int chunk = (int) ((size_t) kFastLdsBytes / row_bytes);
-    chunk &= ~3;
-    if (chunk > 64) chunk = 64;
-    if (chunk < 4) return false;
-    const int usable_pad = (usable + 3) & ~3;
-    if (chunk > usable_pad) chunk = usable_pad;
-    plan->fpi = 2;
-    plan->wr = wp;
-    plan->chunk = chunk;
-    plan->usable_pad = usable_pad;
-    plan->row_bytes = (int) row_bytes;
-    plan->image_bytes = -3;  // marks the four-plane frame-pair layout
-    return true;
+    return launch_lds<das_pair_stationary_kernel<true>>(grid, dim3(1024), kTwoImages, stream, a, n_tiles, tiles_per_wg);
 }
 
 hipError_t launch_pack_planes(const float *d_frames, int n_streams, int hist, int wstart, const int32_t *d_index, int usable,
@@ -2830,25 +2744,15 @@ hipError_t launch_pack_planes(const float *d_frames, int n_streams, int hist, in
 template <int VAR>
 static hipError_t launch_fir8_plane_variant(const PairArgs &a, const void *d_entries, const float *d_coeffs, const Extents &have,
                                             hipStream_t stream) {
-    static LdsFlags attr_set = {};
-    constexpr int lds_bytes = 2 * kFastLdsBytes;
-    if (hipError_t e = allow_lds((const void *) das_fir8_plane_kernel<VAR>, lds_bytes, attr_set); e != hipSuccess) return e;
     const int n_pairs = (a.batch + 1) / 2;
     const int n_tiles = a.cols > 0 ? ((a.pixel_count / a.cols + 3) / 4) * ((a.cols + 15) / 16) : (a.pixel_count + 63) / 64;
     if (a.cols > 0 && (unsigned) a.wp * 2u != kFirStaticPlaneBytes) return hipErrorInvalidValue;  // (the shared block is generated for that pitch)
     // reach: slots past the grid repeat a pixel inside it -- pixel_count rows of one dword per mic, and the block's prefetch
-    if ((a.wp & 3) || !within({(size_t) a.pixel_count * a.usable_pad + kFir8PlaneTablePrefetch, (size_t) n_pairs * a.usable * a.wp * 2}, have))
+    if ((a.wp & 3) || a.pair_group < 1 ||
+        !within({(size_t) a.pixel_count * a.usable_pad + kFir8PlaneTablePrefetch, (size_t) n_pairs * a.usable * a.wp * 2}, have))
         return hipErrorInvalidValue;
-    // frame pairs an XCD works on at a time: as many as keep their packed samples in its 4 MiB L2 beside the table slices
-    const size_t pair_bytes = (size_t) a.usable * a.wp * 8;
-    int g = (int) std::max<size_t>(1, (3u << 20) / pair_bytes);
-    g = g >= 8 ? 8 : g >= 4 ? 4 : g >= 2 ? 2 : 1;
-    while (g > 1 && g > n_pairs) g >>= 1;
-    const long total = (long) n_pairs * n_tiles;
-    const long per_xcd = (total + 7) / 8;
-    hipLaunchKernelGGL(das_fir8_plane_kernel<VAR>, dim3((unsigned) (8 * per_xcd)), dim3(1024), lds_bytes, stream, a,
-                       (const FirPlaneEntry *) d_entries, d_coeffs, n_tiles, g);
-    return hipGetLastError();
+    return launch_lds<das_fir8_plane_kernel<VAR>>(xcd_grid((long) n_pairs * n_tiles), dim3(1024), kTwoImages, stream, a,
+                                                  (const FirPlaneEntry *) d_entries, d_coeffs, n_tiles, a.pair_group);
 }
 
 hipError_t launch_das_fir8_planes(const PairArgs &a, const void *d_entries, const float *d_coeffs, int variant, const Extents &have,
@@ -2862,24 +2766,6 @@ hipError_t launch_das_fir8_planes(const PairArgs &a, const void *d_entries, cons
     return launch_fir8_plane_variant<0>(a, d_entries, d_coeffs, have, stream);
 }
 
-bool exact_nd_plan(int window, int usable, int wq_tile, FastPlan *plan) {
-    const int wq = window - 1;  // element t holds X[t+1] and X[t] - X[t+1]: one element less than samples
-    if (wq_tile <= 0 || wq_tile > wq) wq_tile = wq;  // (not known yet, or no tile reads less: whole rows)
-    const size_t row_bytes = (size_t) wq_tile * 16;  // of the LDS image: the window a tile reads; the packed rows in HBM keep wq elements
-    if (wq_tile < kSamples) return false;
-    int chunk = nd_chunk_mics(wq_tile, kFastLdsBytes);  // a row per wave
-    if (chunk < 4) return false;
-    const int usable_pad = (usable + 3) & ~3;
-    if (chunk > usable_pad) chunk = usable_pad;
-    plan->fpi = 2;
-    plan->wr = wq;
-    plan->chunk = chunk;
-    plan->usable_pad = usable_pad;
-    plan->row_bytes = (int) row_bytes;
-    plan->image_bytes = -4;  // marks the {next, d} layout
-    return true;
-}
-
 hipError_t launch_pack_nd(const float *d_frames, int n_streams, int hist, int wstart, const int32_t *d_index, int usable, int rows_out,
                           const float *d_gain, int wq, int batch, float *d_packed, unsigned *d_queue, hipStream_t stream) {
     hipLaunchKernelGGL(pack_nd_kernel, dim3(rows_out, (batch + 1) / 2), dim3(128), 0, stream, d_frames, n_streams, hist, wstart, d_index,
@@ -2889,9 +2775,6 @@ hipError_t launch_pack_nd(const float *d_frames, int n_streams, int hist, int ws
 
 template <int NQ, bool SUMS>
 static hipError_t launch_exact_nd_variant(const ExactNdArgs &a, hipStream_t stream) {
-    static LdsFlags attr_set = {};
-    constexpr int lds_bytes = 2 * kFastLdsBytes + 64;  // two images + the item mailbox
-    if (hipError_t e = allow_lds((const void *) das_exact_nd_kernel<NQ, SUMS>, lds_bytes, attr_set); e != hipSuccess) return e;
     // one persistent workgroup per CU (the LDS holds no second one), never more than there are items; the queues start at zero: the
     // pack pass in front of this launch has zeroed them (a.queue_zeroed), or -- frames that arrive packed -- a memset does
     const long total = (long) a.n_pairs * a.tiles;
@@ -2900,16 +2783,16 @@ static hipError_t launch_exact_nd_variant(const ExactNdArgs &a, hipStream_t stre
     if (a.build_items)
         hipLaunchKernelGGL(nd_items_kernel, dim3((unsigned) ((total + 255) / 256)), dim3(256), 0, stream, const_cast<int2 *>(a.items), a.n_pairs,
                            a.tiles, a.pair_group, (a.cols + 15) / 16, NQ);
-    hipLaunchKernelGGL((das_exact_nd_kernel<NQ, SUMS>), dim3((unsigned) std::min<long>(total, std::max(1, a.wgs))), dim3(1024), lds_bytes, stream, a);
-    return hipGetLastError();
+    return launch_lds<das_exact_nd_kernel<NQ, SUMS>>(dim3((unsigned) std::min<long>(total, std::max(1, a.wgs))), dim3(1024),
+                                                     kTwoImages + 64, stream, a);  // two images + the item mailbox
 }
 
 hipError_t launch_das_exact_nd(const ExactNdArgs &a, const Extents &have, hipStream_t stream) {
     if ((a.nq != 1 && a.nq != 2) || !a.queue || !a.items || a.wgs < 1 || a.tail < 1) return hipErrorInvalidValue;
-    if (a.chunk < 4 || (a.chunk & 3) || a.chunk > 16 || (a.usable_pad & 3) || a.usable < 1 || a.usable > a.usable_pad || a.wq_tile < kSamples ||
-        a.wq_tile > a.wq || (size_t) a.chunk * a.wq_tile * 16 > (size_t) kFastLdsBytes || a.cols < 1 || a.rows * a.cols != a.pixel_count)
+    if (!chunk_fits(a.chunk, a.usable_pad, (size_t) a.wq_tile * 16) || a.chunk > 16 || a.usable < 1 || a.usable > a.usable_pad || a.wq_tile < kSamples ||
+        a.wq_tile > a.wq || !grid_is(a.rows, a.cols, a.pixel_count))
         return hipErrorInvalidValue;
-    if (a.n_pairs != (a.batch + 1) / 2 || a.tiles != nd_tiles(a.rows, a.cols, a.nq) || a.pair_group < 1) return hipErrorInvalidValue;
+    if (!items_agree(a.n_pairs, a.batch, a.tiles, nd_tiles(a.rows, a.cols, a.nq), a.pair_group)) return hipErrorInvalidValue;
     // the start table: a row of usable_pad entries per 8-row tile + the 16 a wave of a short last chunk may read past the last row
     if (!a.starts || a.start_entries < (size_t) nd_tiles(a.rows, a.cols, 2) * a.usable_pad + 16) return hipErrorInvalidValue;
     // reach: every quad of the grid padded to whole tiles (quad rows to a multiple of nq) + one group of prefetch; usable_pad rows of wq
@@ -2921,30 +2804,6 @@ hipError_t launch_das_exact_nd(const ExactNdArgs &a, const Extents &have, hipStr
     return a.nq == 2 ? launch_exact_nd_variant<2, false>(a, stream) : launch_exact_nd_variant<1, false>(a, stream);
 }
 
-bool exact_ndh_plan(int window, int usable, bool stationary, FastPlan *plan) {
-    const int wh = window - 129;  // element t holds samples t, t+1, t+128, t+129 of the window
-    if (wh < kSamples / 2) return false;
-    const size_t row_bytes = (size_t) wh * 16;
-    const int usable_pad = (usable + 3) & ~3;
-    int chunk;
-    if (stationary) {
-        if ((size_t) usable_pad * row_bytes > (size_t) 2 * kFastLdsBytes) return false;
-        chunk = usable_pad;  // every mic has its own slot
-    } else {
-        chunk = (int) ((size_t) kFastLdsBytes / row_bytes) & ~3;
-        if (chunk > 64) chunk = 64;
-        if (chunk < 4) return false;
-        if (chunk > usable_pad) chunk = usable_pad;
-    }
-    plan->fpi = 1;
-    plan->wr = wh;
-    plan->chunk = chunk;
-    plan->usable_pad = usable_pad;
-    plan->row_bytes = (int) row_bytes;
-    plan->image_bytes = stationary ? -6 : -5;  // marks the halves form of the {next, d} layout
-    return true;
-}
-
 hipError_t launch_pack_ndh(const float *d_frames, int n_streams, int pitch, int wstart, const int32_t *d_index, int usable, int rows_out,
                            const float *d_gain, int wh, int batch, float *d_packed, hipStream_t stream) {
     hipLaunchKernelGGL(pack_ndh_kernel, dim3(rows_out, batch), dim3(256), 0, stream, d_frames, n_streams, pitch, wstart, d_index, usable, d_gain,
@@ -2952,23 +2811,21 @@ hipError_t launch_pack_ndh(const float *d_frames, int n_streams, int pitch, int 
     return hipGetLastError();
 }
 
+// what the two single-frame {next, d} launchers share: mics, rows of at least half a block, the grid, one workgroup per (frame, tile)
+static bool ndh_shape_ok(const ExactNdhArgs &a, int tiles_of_grid, size_t image_bytes) {
+    return chunk_fits(a.chunk, a.usable_pad, (size_t) a.wh * 16, image_bytes) && a.usable >= 1 && a.usable <= a.usable_pad && a.wh >= kSamples / 2 &&
+           grid_is(a.rows, a.cols, a.pixel_count) && a.batch >= 1 && a.tiles == tiles_of_grid && (long) a.batch * a.tiles <= 0x7fffffffL;
+}
+
 template <int NQ, bool STATIONARY>
 static hipError_t launch_exact_ndh_variant(const ExactNdhArgs &a, hipStream_t stream) {
-    static LdsFlags attr_set = {};
-    constexpr int lds_bytes = 2 * kFastLdsBytes;
-    if (hipError_t e = allow_lds((const void *) das_exact_ndh_kernel<NQ, STATIONARY>, lds_bytes, attr_set); e != hipSuccess) return e;
-    hipLaunchKernelGGL((das_exact_ndh_kernel<NQ, STATIONARY>), dim3((unsigned) ((long) a.batch * a.tiles)), dim3(1024), lds_bytes, stream, a);
-    return hipGetLastError();
+    return launch_lds<das_exact_ndh_kernel<NQ, STATIONARY>>(dim3((unsigned) ((long) a.batch * a.tiles)), dim3(1024), kTwoImages, stream, a);
 }
 
 hipError_t launch_das_exact_ndh(const ExactNdhArgs &a, bool stationary, const Extents &have, hipStream_t stream) {
     if (a.nq != 1 && a.nq != 2) return hipErrorInvalidValue;
-    if (a.chunk < 4 || (a.chunk & 3) || (a.usable_pad & 3) || a.usable < 1 || a.usable > a.usable_pad || a.wh < kSamples / 2 || a.cols < 1 ||
-        a.rows * a.cols != a.pixel_count || a.batch < 1 || a.tiles != ndh_tiles(a.rows, a.cols, a.nq) || (long) a.batch * a.tiles > 0x7fffffffL)
-        return hipErrorInvalidValue;
-    if (stationary ? (a.chunk != a.usable_pad || (size_t) a.usable_pad * a.wh * 16 > (size_t) 2 * kFastLdsBytes || !a.frames || !a.index || a.pitch < 1)
-                   : ((size_t) a.chunk * a.wh * 16 > (size_t) kFastLdsBytes || !a.packed))
-        return hipErrorInvalidValue;
+    if (!ndh_shape_ok(a, ndh_tiles(a.rows, a.cols, a.nq), stationary ? kTwoImages : kFastLdsBytes)) return hipErrorInvalidValue;
+    if (stationary ? (a.chunk != a.usable_pad || !a.frames || !a.index || a.pitch < 1) : !a.packed) return hipErrorInvalidValue;
     // reach: every quad of the grid with its columns padded to whole tiles (16 nq) + one group of prefetch; chunked: usable_pad rows of wh
     // 16-byte elements per frame (stationary: the caller's frames, read inside [wstart, wstart + wh + 129) of a stream)
     if (a.lut_cols < (a.cols + 16 * a.nq - 1) / (16 * a.nq) * 16 * a.nq) return hipErrorInvalidValue;
@@ -2980,49 +2837,28 @@ hipError_t launch_das_exact_ndh(const ExactNdhArgs &a, bool stationary, const Ex
 }
 
 hipError_t launch_das_exact_ndp(const ExactNdhArgs &a, const Extents &have, hipStream_t stream) {
-    static LdsFlags attr_set = {};
-    constexpr int lds_bytes = 2 * kFastLdsBytes;
-    if (hipError_t e = allow_lds((const void *) das_exact_ndp_kernel, lds_bytes, attr_set); e != hipSuccess) return e;
-    if (a.chunk < 4 || (a.chunk & 3) || (a.usable_pad & 3) || a.usable < 1 || a.usable > a.usable_pad || a.wh < kSamples / 2 || a.cols < 1 ||
-        a.rows * a.cols != a.pixel_count || a.batch < 1 || a.tiles != ndp_tiles(a.rows, a.cols) || (long) a.batch * a.tiles > 0x7fffffffL ||
-        (size_t) a.chunk * a.wh * 16 > (size_t) kFastLdsBytes || !a.packed || a.lut_cols < (a.cols + 3) / 4 * 4)
-        return hipErrorInvalidValue;
+    if (!ndh_shape_ok(a, ndp_tiles(a.rows, a.cols), kFastLdsBytes) || !a.packed || a.lut_cols < (a.cols + 3) / 4 * 4) return hipErrorInvalidValue;
     // reach: every quad of the table + TWO groups of prefetch (the block requests entries two trips ahead); usable_pad rows of wh elements per frame
     const size_t quads = (size_t) ((a.rows + 3) / 4) * a.lut_cols;
     if (!within({quads * (a.usable_pad / 4) * 16 + 2 * kQuadTablePrefetch, (size_t) a.batch * a.usable_pad * a.wh * 4}, have)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(das_exact_ndp_kernel, dim3((unsigned) ((long) a.batch * a.tiles)), dim3(1024), lds_bytes, stream, a);
-    return hipGetLastError();
+    return launch_lds<das_exact_ndp_kernel>(dim3((unsigned) ((long) a.batch * a.tiles)), dim3(1024), kTwoImages, stream, a);
 }
 
 hipError_t launch_das_exact_quads(const ExactQuadArgs &a, const Extents &have, hipStream_t stream) {
-    static LdsFlags attr_set = {};
-    constexpr int lds_bytes = 2 * kFastLdsBytes;
-    if (hipError_t e = allow_lds((const void *) das_exact_quad_kernel, lds_bytes, attr_set); e != hipSuccess) return e;
-    if (a.chunk < 4 || (a.chunk & 3) || (a.usable_pad & 3) || (size_t) a.chunk * a.wp * 8 > (size_t) kFastLdsBytes || a.cols < 1 ||
-        a.rows * a.cols != a.pixel_count)
-        return hipErrorInvalidValue;
-    if (a.n_pairs != (a.batch + 1) / 2 || a.tiles != quad_tiles(a.rows, a.cols) || a.pair_group < 1) return hipErrorInvalidValue;
+    if (!chunk_fits(a.chunk, a.usable_pad, (size_t) a.wp * 8) || !grid_is(a.rows, a.cols, a.pixel_count)) return hipErrorInvalidValue;
+    if (!items_agree(a.n_pairs, a.batch, a.tiles, quad_tiles(a.rows, a.cols), a.pair_group)) return hipErrorInvalidValue;
     if ((a.wp & 1) || !within({quad_table_reach(a.rows, a.cols, a.usable_pad), (size_t) a.n_pairs * a.usable_pad * a.wp * 2}, have))
         return hipErrorInvalidValue;
-    const long total = (long) a.n_pairs * a.tiles;
-    dim3 grid((unsigned) (8 * ((total + 7) / 8)));
-    hipLaunchKernelGGL(das_exact_quad_kernel, grid, dim3(1024), lds_bytes, stream, a);
-    return hipGetLastError();
+    return launch_lds<das_exact_quad_kernel>(xcd_grid((long) a.n_pairs * a.tiles), dim3(1024), kTwoImages, stream, a);
 }
 
 hipError_t launch_das_exact_pairs(const ExactPairArgs &a, const Extents &have, hipStream_t stream) {
-    static LdsFlags attr_set = {};
-    constexpr int lds_bytes = 2 * kFastLdsBytes;
-    if (hipError_t e = allow_lds((const void *) das_exact_pair_kernel, lds_bytes, attr_set); e != hipSuccess) return e;
-    if (a.chunk < 4 || (a.chunk & 3) || (a.usable_pad & 3) || (size_t) a.chunk * a.wp * 8 > (size_t) kFastLdsBytes) return hipErrorInvalidValue;
-    if (a.n_pairs != (a.batch + 1) / 2 || a.tiles != pair_tiles(a.pixel_count, a.cols) || a.pair_group < 1) return hipErrorInvalidValue;
+    if (!chunk_fits(a.chunk, a.usable_pad, (size_t) a.wp * 8)) return hipErrorInvalidValue;
+    if (!items_agree(a.n_pairs, a.batch, a.tiles, pair_tiles(a.pixel_count, a.cols), a.pair_group)) return hipErrorInvalidValue;
     if ((a.wp & 1) || !within({pair_table_rows(a.pixel_count, a.cols) * a.usable_pad + kPairTablePrefetch,
                                (size_t) a.n_pairs * a.usable_pad * a.wp * 2}, have))
         return hipErrorInvalidValue;
-    const long total = (long) a.n_pairs * a.tiles;
-    dim3 grid((unsigned) (8 * ((total + 7) / 8)));
-    hipLaunchKernelGGL(das_exact_pair_kernel, grid, dim3(1024), lds_bytes, stream, a);
-    return hipGetLastError();
+    return launch_lds<das_exact_pair_kernel>(xcd_grid((long) a.n_pairs * a.tiles), dim3(1024), kTwoImages, stream, a);
 }
 
 hipError_t launch_das_pairs(const PairArgs &a, const Extents &have, hipStream_t stream) {
@@ -3036,16 +2872,14 @@ hipError_t launch_das_pairs(const PairArgs &a, const Extents &have, hipStream_t 
 
 template <bool DIAG, int VAR>
 static hipError_t launch_quad_variant(const QuadArgs &a, const Extents &have, hipStream_t stream) {
-    static LdsFlags attr_set = {};
-    constexpr int lds_bytes = 2 * kFastLdsBytes + 64;  // two images + the item mailbox of the queued launch
-    if (hipError_t e = allow_lds((const void *) das_quad_kernel<DIAG, VAR>, lds_bytes, attr_set); e != hipSuccess) return e;
+    constexpr int lds_bytes = kTwoImages + 64;  // two images + the item mailbox of the queued launch
     // One workgroup per item by default: the hardware hands items to CUs as they free up, which stays balanced when
     // something else (an RCCL broadcast of the next batch) holds a few CUs.  a.wgs > 0 (AWPU_FAST_WGS) launches that
     // many persistent workgroups instead, each walking several items with the next item's first chunk prefetched:
     // measured equal at the headline shape on an otherwise idle chip (5.41 vs 5.41 ms), and fragile when CUs are
     // shared (a static share of the items per workgroup).
-    if (a.rows * a.cols != a.pixel_count || a.n_pairs != (a.batch + 1) / 2 || a.tiles != quad_tiles(a.rows, a.cols) || a.pair_group < 1 ||
-        (a.wp & 1) || (a.usable_pad & 3) || (a.chunk & 3) || (size_t) a.chunk * a.wp * 8 > (size_t) kFastLdsBytes)
+    if (!grid_is(a.rows, a.cols, a.pixel_count) || !items_agree(a.n_pairs, a.batch, a.tiles, quad_tiles(a.rows, a.cols), a.pair_group) ||
+        (a.wp & 1) || !chunk_fits(a.chunk, a.usable_pad, (size_t) a.wp * 8))
         return hipErrorInvalidValue;
     if (!within({quad_table_reach(a.rows, a.cols, a.usable_pad), (size_t) a.n_pairs * a.usable_pad * a.wp * 2}, have)) return hipErrorInvalidValue;
     const long items = (long) a.n_pairs * a.tiles;
@@ -3053,15 +2887,13 @@ static hipError_t launch_quad_variant(const QuadArgs &a, const Extents &have, hi
     if (!DIAG && VAR == 0 && a.queue && a.wgs > 0) {  // persistent workgroups on the item queues (das_quad_kernel: `queued`)
         if (a.tail < 1) return hipErrorInvalidValue;
         if (hipError_t e = hipMemsetAsync(a.queue, 0, 9 * sizeof(unsigned), stream); e != hipSuccess) return e;
-        hipLaunchKernelGGL((das_quad_kernel<DIAG, VAR>), dim3((unsigned) std::min<long>(items, a.wgs)), dim3(1024), lds_bytes, stream, a);
-        return hipGetLastError();
+        return launch_lds<das_quad_kernel<DIAG, VAR>>(dim3((unsigned) std::min<long>(items, a.wgs)), dim3(1024), lds_bytes, stream, a);
     }
     QuadArgs b = a;
     b.queue = nullptr;  // (the stamped and the tuning instances keep the static shares)
     const long wgs_per_xcd = a.wgs > 0 ? std::min<long>(per_xcd, std::max(1, a.wgs / 8)) : per_xcd;
     if (8 * wgs_per_xcd > 0x7fffffffL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((das_quad_kernel<DIAG, VAR>), dim3((unsigned) (8 * wgs_per_xcd)), dim3(1024), lds_bytes, stream, b);
-    return hipGetLastError();
+    return launch_lds<das_quad_kernel<DIAG, VAR>>(dim3((unsigned) (8 * wgs_per_xcd)), dim3(1024), lds_bytes, stream, b);
 }
 
 hipError_t launch_das_quads(const QuadArgs &a, const Extents &have, hipStream_t stream) {
@@ -3076,25 +2908,14 @@ hipError_t launch_das_quads(const QuadArgs &a, const Extents &have, hipStream_t 
     return launch_quad_variant<false, 0>(a, have, stream);
 }
 
-int fast_image_bytes(int nw) { return nw == 24 ? kFastLdsBytesSmall : kFastLdsBytes; }
-
-bool fast_db_fits(const FastPlan &plan) {
-    return (size_t) 2 * plan.usable_pad * sizeof(int) <= (size_t) kFastSideBytes;
-}
-
 template <int QPW, bool DIAG>
 static hipError_t launch_quadh_variant(const QuadhArgs &a, const Extents &have, hipStream_t stream) {
-    static LdsFlags attr_set = {};
-    constexpr int lds_bytes = 2 * kFastLdsBytes;
-    if (hipError_t e = allow_lds((const void *) das_quadh_kernel<QPW, DIAG>, lds_bytes, attr_set); e != hipSuccess) return e;
-    if (a.rows * a.cols != a.pixel_count || (a.wp & 1) || (a.usable_pad & 3) || (a.chunk & 3) || a.chunk < 4 ||
-        (size_t) a.chunk * a.wp * 8 > (size_t) kFastLdsBytes ||
+    if (!grid_is(a.rows, a.cols, a.pixel_count) || (a.wp & 1) || !chunk_fits(a.chunk, a.usable_pad, (size_t) a.wp * 8) ||
         !within({quad_table_reach(a.rows, a.cols, a.usable_pad), (size_t) a.batch * a.usable_pad * a.wp * 2}, have))
         return hipErrorInvalidValue;
     dim3 grid(a.batch, quad1_tiles(a.rows, a.cols, QPW));
     if (grid.y > 65535) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((das_quadh_kernel<QPW, DIAG>), grid, dim3(1024), lds_bytes, stream, a);
-    return hipGetLastError();
+    return launch_lds<das_quadh_kernel<QPW, DIAG>>(grid, dim3(1024), kTwoImages, stream, a);
 }
 
 hipError_t launch_das_quadh(const QuadhArgs &a, int qpw, const Extents &have, hipStream_t stream) {
@@ -3104,55 +2925,19 @@ hipError_t launch_das_quadh(const QuadhArgs &a, int qpw, const Extents &have, hi
     return qpw == 2 ? launch_quadh_variant<2, false>(a, have, stream) : launch_quadh_variant<1, false>(a, have, stream);
 }
 
-bool quadh_stationary_plan(int window, int usable, FastPlan *plan) {
-    const int wp = (window - 128 + 1) & ~1;  // elements (sample t, sample t + 128) per row
-    if (wp < 130) return false;
-    const size_t row_bytes = (size_t) wp * 8;
-    const int usable_pad = (usable + 3) & ~3;
-    // the halves image + the raw rows it is filtered from (at most wp + 136 floats each) + the row table
-    if ((size_t) usable_pad * row_bytes + (size_t) usable * (wp + 130) * 4 > (size_t) kQuadhsRowTableOffset * 4) return false;
-    plan->fpi = 1;
-    plan->wr = wp;
-    plan->chunk = usable_pad;  // every mic has its own slot
-    plan->usable_pad = usable_pad;
-    plan->row_bytes = (int) row_bytes;
-    plan->image_bytes = -3;
-    return true;
-}
-
-// the raw rows a launch stages: history samples [raw_begin, raw_begin + raw_wr) of every active stream, whole 16-byte pieces;
-// false if they do not fit beside the image (the caller then takes das_quadh_kernel)
-bool quadh_stationary_raw(const FastPlan &plan, int usable, int wstart, int row_limit, int *raw_begin, int *raw_wr, int *image_offset) {
-    const int begin = std::max(0, wstart - 1) & ~3;
-    const int end = std::min(row_limit, (wstart + plan.wr + 128 + 1 + 3) & ~3);
-    if (end <= begin || ((end - begin) & 3)) return false;
-    const size_t raw_floats = (size_t) usable * (end - begin);
-    const size_t image_off = (raw_floats + 3) & ~(size_t) 3;
-    if (image_off * 4 + (size_t) plan.usable_pad * plan.row_bytes > (size_t) kQuadhsRowTableOffset * 4) return false;
-    if (usable > 1024) return false;  // (the row table)
-    *raw_begin = begin;
-    *raw_wr = end - begin;
-    *image_offset = (int) image_off;
-    return true;
-}
-
 template <int QPW>
 static hipError_t launch_quadh_stationary_variant(const QuadhStationaryArgs &a, const Extents &have, hipStream_t stream) {
-    static LdsFlags attr_set = {};
-    constexpr int lds_bytes = 2 * kFastLdsBytes;
-    if (hipError_t e = allow_lds((const void *) das_quadh_stationary_kernel<QPW>, lds_bytes, attr_set); e != hipSuccess) return e;
     if ((size_t) a.image_offset * 4 + (size_t) a.usable_pad * a.wp * 8 > (size_t) kQuadhsRowTableOffset * 4 || (a.usable_pad & 3) ||
         (a.raw_wr & 3) || (a.image_offset & 3) || (size_t) a.usable * a.raw_wr > (size_t) a.image_offset || a.usable > 1024 ||
         a.raw_begin + a.raw_wr > a.row_limit)
         return hipErrorInvalidValue;
     if (a.waves < 4 || a.waves > 16) return hipErrorInvalidValue;
     // (the samples are the caller's frames: rows [raw_begin, raw_begin + raw_wr) of a stream, inside row_limit -- checked above)
-    if (a.rows * a.cols != a.pixel_count || !within({quad_table_reach(a.rows, a.cols, a.usable_pad), 0}, have)) return hipErrorInvalidValue;
+    if (!grid_is(a.rows, a.cols, a.pixel_count) || !within({quad_table_reach(a.rows, a.cols, a.usable_pad), 0}, have)) return hipErrorInvalidValue;
     const int tile_cols = a.waves * QPW;
     dim3 grid(a.batch, ((a.rows + 3) / 4) * ((a.cols + tile_cols - 1) / tile_cols));
     if (grid.y > 65535) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((das_quadh_stationary_kernel<QPW>), grid, dim3(a.waves * 64), lds_bytes, stream, a);
-    return hipGetLastError();
+    return launch_lds<das_quadh_stationary_kernel<QPW>>(grid, dim3(a.waves * 64), kTwoImages, stream, a);
 }
 
 hipError_t launch_das_quadh_stationary(const QuadhStationaryArgs &a, int qpw, const Extents &have, hipStream_t stream) {

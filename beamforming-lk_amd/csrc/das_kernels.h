@@ -5,9 +5,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-namespace awpu {
+#if defined(AWPU_TIMING_BUILD) && !defined(AWPU_TUNING_BUILD)
+#define AWPU_TUNING_BUILD 1  // the timing experiments need the tuning knobs and the stamped kernels
+#endif
+#include "sweep_plan.h"  // kSamples, the LDS budget, FastPlan and the planners of every sweep layout (host only)
 
-constexpr int kSamples = 256;  // N_SAMPLES, src/fpga/streams.hpp:28
+namespace awpu {
 
 // AWPU_FAST_DEBUG bits.  The switches that give WRONG results (timing experiments: what does the kernel cost
 // without its refill / sweep / tail pass / barrier) exist only in builds with -DAWPU_TIMING_BUILD
@@ -15,9 +18,6 @@ constexpr int kSamples = 256;  // N_SAMPLES, src/fpga/streams.hpp:28
 // variable cannot reach them (awpu_hip.cpp masks it to kDebugSafeBits).
 constexpr int kDebugNoRefill = 1, kDebugNoSweep = 2, kDebugNoTail = 4, kDebugNoBarrier = 8, kDebugRegStaging = 64;
 constexpr int kDebugSafeBits = 16 | 256 | 512 | 4096;  // stamps, dispatch order, refill by rank, unshared block: same results
-#if defined(AWPU_TIMING_BUILD) && !defined(AWPU_TUNING_BUILD)
-#define AWPU_TUNING_BUILD 1  // the timing experiments need the tuning knobs and the stamped kernels
-#endif
 #ifdef AWPU_TIMING_BUILD
 #define AWPU_DBG(a, bit) ((a).debug & (bit))
 #else
@@ -49,10 +49,6 @@ struct SweepArgs {
 };
 
 // ---- fast kernel (das_fast.hip) ---------------------------------------------------------
-constexpr int kFastLdsBytes = 78 * 1024; // one staged image; a CU holds two (+ a 4 KiB side table)
-constexpr int kFastSideBytes = 4 * 1024;
-constexpr int kFastLdsBytesSmall = 38 * 1024;  // image of the two-workgroups-per-CU double-buffered shape
-
 // One 16-byte entry per (pixel, active mic): what one item needs, laid out so that f and g
 // start even SGPRs after an s_load_dwordx16 (packed-FMA scalar operands are aligned pairs).
 struct FastEntry {
@@ -75,14 +71,7 @@ constexpr int kPairTablePrefetch = 4;        // FastEntry: one group of four mic
 constexpr int kQuadTablePrefetch = 16;       // QuadEntry: one group (4 pixels x 4 mics) past the end of a quad's groups
 constexpr int kFir8PlaneTablePrefetch = 68;  // dwords: entries four items ahead + 64 past a chunk (block_fir8)
 
-struct FastPlan {
-    int fpi;         // frames per item (1 or 2)
-    int wr;          // floats per staged row (even)
-    int chunk;       // mics staged per pass (multiple of 4, <= 64)
-    int usable_pad;  // table row length, usable rounded up to 4 (null entries at the end)
-    int row_bytes;
-    int image_bytes;  // LDS bytes of one staged image
-};
+// (FastPlan -- a sweep's LDS geometry -- names its layout (PackLayout) and comes from that layout's planner: sweep_plan.h)
 
 struct FastArgs {
     const float *frames;   // [batch][n_streams][hist]
@@ -118,7 +107,6 @@ struct PairArgs {
 inline int pair_tiles(int pixel_count, int cols) {
     return cols > 0 ? ((pixel_count / cols + 1) / 2) * ((cols + 31) / 32) : (pixel_count + 63) / 64;
 }
-bool pair_plan(int window, int usable, FastPlan *plan);
 // rows_out >= usable rows per pair are written (the extra ones zero); d_gain [usable] (or null) scales row s;
 // filter: the rows carry the moving-average stencil of the samples, Y[t] = X[t]/2 - (X[t+1] + X[t-1])/4 -- what
 // das_pair_kernel, das_pair_stationary_kernel and das_quad_kernel sweep (their epilogue then has no stencil and
@@ -178,8 +166,6 @@ struct ExactNdArgs {
 };
 inline int nd_tiles(int rows, int cols, int nq) { return (((rows + 3) / 4 + nq - 1) / nq) * ((cols + 15) / 16); }
 inline int nd_quad_count(int rows, int cols, int nq) { return (((rows + 3) / 4 + nq - 1) / nq) * nq * ((cols + 15) / 16) * 16; }  // table quads incl. padding
-// plan->wr = elements per packed row (window - 1); row_bytes = 16 wq_tile, the LDS row (wq_tile <= 0: whole rows); chunk <= 16, one row per wave
-bool exact_nd_plan(int window, int usable, int wq_tile, FastPlan *plan);
 hipError_t launch_pack_nd(const float *d_frames, int n_streams, int hist, int wstart, const int32_t *d_index, int usable, int rows_out,
                           const float *d_gain, int wq, int batch, float *d_packed, unsigned *d_queue, hipStream_t stream);
 hipError_t launch_das_exact_nd(const ExactNdArgs &a, const Extents &have, hipStream_t stream);
@@ -215,7 +201,6 @@ struct ExactNdhArgs {
     DoneFlag done;         // the resident kernel with one quad per wave only
 };
 inline int ndh_tiles(int rows, int cols, int nq) { return ((rows + 3) / 4) * ((cols + 16 * nq - 1) / (16 * nq)); }
-bool exact_ndh_plan(int window, int usable, bool stationary, FastPlan *plan);  // plan->wr = wh, row_bytes = 16 wh
 hipError_t launch_pack_ndh(const float *d_frames, int n_streams, int pitch, int wstart, const int32_t *d_index, int usable, int rows_out,
                            const float *d_gain, int wh, int batch, float *d_packed, hipStream_t stream);
 hipError_t launch_das_exact_ndh(const ExactNdhArgs &a, bool stationary, const Extents &have, hipStream_t stream);
@@ -232,15 +217,12 @@ constexpr int kFir8ZeroRow = 101, kFir8CoeffRows = 128;
 inline uint32_t fir8_plane_word(uint32_t addr, uint32_t plane, uint32_t k) {
     return (addr & 0x3ffffu) | ((plane & 3u) << 18) | ((k & 0x7fu) << 20);
 }
-bool fir8_plane_plan(int window, int usable, FastPlan *plan);
 hipError_t launch_pack_planes(const float *d_frames, int n_streams, int hist, int wstart, const int32_t *d_index, int usable,
                               const float *d_gain, int wp, int batch, float *d_packed, hipStream_t stream);
-constexpr uint32_t kFirStaticPlaneBytesHost = 768;  // = kFirStaticPlaneBytes of das_fast_trip.inc (static_assert in das_fast.hip)
 hipError_t launch_das_fir8_planes(const PairArgs &a, const void *d_entries, const float *d_coeffs, int variant, const Extents &have,
                                   hipStream_t stream);
-// stationary shape: every active mic's window of a frame pair in LDS at once (plan->chunk = usable_pad); a
+// stationary shape: every active mic's window of a frame pair in LDS at once (pair_plan_stationary: plan->chunk = usable_pad); a
 // workgroup stages the pair once and sweeps tiles_per_wg tiles from it
-bool pair_plan_stationary(int window, int usable, FastPlan *plan);
 hipError_t launch_das_pairs_stationary(const PairArgs &a, int tiles_per_wg, const Extents &have, hipStream_t stream);
 
 // ---- quad shape (das_quad_kernel): the frame-pair layout swept four vertically adjacent pixels at a time with
@@ -302,22 +284,16 @@ struct QuadhStationaryArgs {
     int32_t waves;              // waves per workgroup = columns (x qpw) per tile: 16
     int32_t identity;           // the active-mic list is 0 .. usable-1 (awpu_hip_set_active_mics(NULL)): rows need no look-up
 };
-bool quadh_stationary_plan(int window, int usable, FastPlan *plan);
-bool quadh_stationary_raw(const FastPlan &plan, int usable, int wstart, int row_limit, int *raw_begin, int *raw_wr, int *image_offset);
 hipError_t launch_das_quadh_stationary(const QuadhStationaryArgs &a, int qpw, const Extents &have, hipStream_t stream);
 // `pitch` = floats between two streams of a frame (hist, or 2048 in the ingest ring), `hist` = samples of a stream's
 // history (neighbours of the filter outside it count as 0), wstart = first history sample of the window
 hipError_t launch_pack_halves(const float *d_frames, int n_streams, int pitch, int hist, int wstart, const int32_t *d_index, int usable,
                               int rows_out, const float *d_gain, int wp, int batch, float *d_packed, hipStream_t stream);
 
-// LDS image geometry for a window of `window` samples; false if it cannot fit.
-bool fast_plan(int window, int usable, int fpi, int image_bytes, FastPlan *plan);
-int fast_image_bytes(int nw);
 // fpi in {1,2} frames per item; ppw in {2,4,8} pixels per wave (8 only with fpi 1)
 // nw: 8 = 8-wave workgroups (two per CU, single image); 32 = double-buffered 16-wave workgroup, one
 // per CU; 24 = double-buffered 12-wave workgroups, two per CU (fpi 1 only for 24 and 32)
 hipError_t launch_das_fast(const FastArgs &a, int fpi, int ppw, int nw, const Extents &have, hipStream_t stream);
-bool fast_db_fits(const FastPlan &plan);
 
 // exact-order kernel (AWPU_MATH_F32_EXACT): sub, fma, add per sample, mics in order; with
 // bf16_accumulator (AWPU_MATH_BF16_ACC) the running sums are rounded to bf16 after every mic.
