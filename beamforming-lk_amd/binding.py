@@ -212,6 +212,49 @@ _WATCH_SIGNATURES = {
 }
 WATCH_SYMBOLS = tuple(_WATCH_SIGNATURES)
 
+FIND_MAX_RADIUS, FIND_MAX_SOURCES, FIND_MAX_PIXELS = 8, 32, 262144
+
+
+class Find(C.Structure):
+    """awpu_find_t (include/awpu_hip_find.h)."""
+    _fields_ = [
+        ("rows", C.c_int32),
+        ("cols", C.c_int32),
+        ("radius", C.c_int32),
+        ("max_sources", C.c_int32),
+        ("min_power", C.c_float),
+        ("min_ratio", C.c_float),
+        ("fov_deg", C.c_float),
+    ]
+
+
+class Source(C.Structure):
+    """awpu_source_t (include/awpu_hip_find.h)."""
+    _fields_ = [
+        ("pixel", C.c_int32),
+        ("power", C.c_float),
+        ("row", C.c_double),
+        ("col", C.c_double),
+        ("theta", C.c_double),
+        ("phi", C.c_double),
+    ]
+
+
+# finding sources: the entry points of include/awpu_hip_find.h
+_FIND_TAIL = [C.POINTER(Find), C.c_void_p, C.c_void_p]  # f, sources, count
+_FIND_SIGNATURES = {
+    "awpu_hip_find_peaks": (C.c_int, [_f32p, C.c_int32, *_FIND_TAIL]),
+    "awpu_hip_find_peaks_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, *_FIND_TAIL, C.c_void_p]),
+    "awpu_hip_find_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, *_WATCH_TAIL, *_FIND_TAIL, _f32p]),
+    "awpu_hip_find_samples": (C.c_int, [C.c_void_p, _f32p, C.c_int64, *_WATCH_TAIL, *_FIND_TAIL, _f32p]),
+    "awpu_hip_find_samples_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, *_WATCH_TAIL, *_FIND_TAIL, C.c_void_p, C.c_void_p]),
+}
+FIND_SYMBOLS = tuple(_FIND_SIGNATURES)
+
+# numpy view of awpu_source_t: what find_peaks and Engine.find_* return, max_sources records per frame
+SOURCE_DTYPE = np.dtype([("pixel", "<i4"), ("power", "<f4"), ("row", "<f8"), ("col", "<f8"), ("theta", "<f8"), ("phi", "<f8")], align=True)
+assert SOURCE_DTYPE.itemsize == C.sizeof(Source) == 40
+
 # numpy view of awpu_particle_t: what Engine.track returns, one record per particle
 PARTICLE_DTYPE = np.dtype([("theta", "<f8"), ("phi", "<f8"), ("spread", "<f8"), ("rate", "<f8"), ("steps", "<i4"),
                            ("error", "<f4"), ("grad_theta", "<f8"), ("grad_phi", "<f8"), ("radius", "<f8"),
@@ -240,7 +283,7 @@ def load(build: bool = True) -> C.CDLL:
         raise RuntimeError(f"{path} is missing and there is no CPU fallback")
     lib = C.CDLL(str(path))
     for name, (res, args) in list(_SIGNATURES.items()) + list(_TRACK_SIGNATURES.items()) + list(_BLOCK_SIGNATURES.items()) + \
-            list(_LISTEN_SIGNATURES.items()) + list(_WATCH_SIGNATURES.items()):
+            list(_LISTEN_SIGNATURES.items()) + list(_WATCH_SIGNATURES.items()) + list(_FIND_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -417,6 +460,40 @@ def watch_count(n_blocks: int, first: int, every: int):
     n, nxt = C.c_int32(0), C.c_int32(0)
     _check(load().awpu_hip_watch_count(n_blocks, first, every, C.byref(n), C.byref(nxt)), "awpu_hip_watch_count")
     return int(n.value), int(nxt.value)
+
+
+class FindResult:
+    """What find_peaks and Engine.find_* hand back: .sources [n_frames, max_sources] SOURCE_DTYPE records (unused entries:
+    pixel -1), .count [n_frames], .power [n_frames, pixels] or None, .next_first (the run forms: the `first` of the call that
+    continues the recording); .pixel, .row, .col, .theta, .phi are the records' fields.  Frame j of a run form is block first +
+    j * every of the call."""
+
+    def __init__(self, sources: np.ndarray, count: np.ndarray, power=None, next_first: int = 0):
+        self.sources = sources
+        self.count = count
+        self.power = power
+        self.next_first = next_first
+
+    def __getattr__(self, name):
+        if name in SOURCE_DTYPE.names:
+            return self.sources[name]
+        raise AttributeError(name)
+
+    def __len__(self):
+        return len(self.count)
+
+
+def find_peaks(power: np.ndarray, rows: int, cols: int, radius: int = 2, max_sources: int = 4, min_power: float = 0.0,
+               min_ratio: float = 0.0, fov_deg: float = 180.0) -> FindResult:
+    """The strongest peaks of power rows [n_frames, rows * cols] (or one row) on the host: the rule of include/awpu_hip_find.h
+    as executable C (awpu_hip_find_peaks)."""
+    power = np.ascontiguousarray(power, np.float32).reshape(-1, rows * cols)
+    f = Find(rows, cols, radius, max_sources, min_power, min_ratio, fov_deg)
+    sources = np.empty((len(power), max(max_sources, 0)), SOURCE_DTYPE)
+    count = np.empty(len(power), np.int32)
+    _check(load().awpu_hip_find_peaks(_f32(power), len(power), C.byref(f), sources.ctypes.data_as(C.c_void_p),
+                                      count.ctypes.data_as(C.c_void_p)), "awpu_hip_find_peaks")
+    return FindResult(sources, count)
 
 
 def _particles(theta, phi, spread, rate, steps, where: str) -> np.ndarray:
@@ -662,6 +739,62 @@ class Engine:
         _check(self._lib.awpu_hip_watch_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, C.byref(w),
                                                        C.c_void_p(d_image_ptr), C.c_void_p(d_big_ptr), C.c_void_p(d_power_ptr),
                                                        C.c_void_p(stream)), "awpu_hip_watch_samples_device")
+        return watch_count(n_blocks, first, every)[1]
+
+    def find_peaks_device(self, d_power_ptr: int, n_frames: int, rows: int, cols: int, d_sources_ptr: int, d_count_ptr: int,
+                          radius: int = 2, max_sources: int = 4, min_power: float = 0.0, min_ratio: float = 0.0, fov_deg: float = 180.0,
+                          stream: int = 0) -> None:
+        """find_peaks on device pointers (power [n_frames, rows * cols] floats, sources [n_frames, max_sources] records of 40
+        bytes, count [n_frames] int32) on `stream`; asynchronous (awpu_hip_find_peaks_device)."""
+        f = Find(rows, cols, radius, max_sources, min_power, min_ratio, fov_deg)
+        _check(self._lib.awpu_hip_find_peaks_device(self._h, C.c_void_p(d_power_ptr), n_frames, C.byref(f), C.c_void_p(d_sources_ptr),
+                                                    C.c_void_p(d_count_ptr), C.c_void_p(stream)), "awpu_hip_find_peaks_device")
+
+    def _find(self, call, where, n_blocks, rows, cols, first, every, find, want_power) -> FindResult:
+        n_frames, next_first = watch_count(n_blocks, first, every)
+        w = Watch(first, every, rows, cols, 0, 0, 0, None)
+        f = Find(rows, cols, find.get("radius", 2), find.get("max_sources", 4), find.get("min_power", 0.0), find.get("min_ratio", 0.0),
+                 find.get("fov_deg", 180.0))
+        sources = np.empty((n_frames, max(f.max_sources, 0)), SOURCE_DTYPE)
+        count = np.empty(n_frames, np.int32)
+        power = np.empty((n_frames, self.pixel_count), np.float32) if want_power else None
+        # (an output that is wanted is never a null pointer, not even with no frame to write)
+        ptr = lambda a: C.c_void_p(a.ctypes.data or 16)
+        _check(call(n_blocks, C.byref(w), C.byref(f), ptr(sources), ptr(count), C.cast(ptr(power), _f32p) if want_power else None), where)
+        return FindResult(sources, count, power, next_first)
+
+    def find_blocks(self, wire, rows: int, cols: int, first: int = 0, every: int = 1, stride: int = DATAGRAM_BYTES,
+                    want_power: bool = False, **find) -> FindResult:
+        """The sources in a run of consecutive blocks of wire datagrams (as watch_blocks takes them): every block is appended to
+        the ring, blocks first, first + every, ... are swept and their strongest peaks found on the device; find_peaks'
+        keywords (radius, max_sources, min_power, min_ratio, fov_deg) say what a source is (awpu_hip_find_blocks).  -> FindResult;
+        pass its .next_first as `first` of the call that continues the run."""
+        buf = np.frombuffer(wire, dtype=np.uint8)
+        if stride < DATAGRAM_BYTES or buf.size % (256 * stride) or buf.size == 0:
+            raise ValueError(f"wire must be a whole number of blocks of 256 datagrams {stride} bytes apart")
+        return self._find(lambda *rest: self._lib.awpu_hip_find_blocks(self._h, buf.ctypes.data_as(C.c_void_p), stride, *rest),
+                          "awpu_hip_find_blocks", buf.size // (256 * stride), rows, cols, first, every, find, want_power)
+
+    def find_samples(self, samples: np.ndarray, rows: int, cols: int, first: int = 0, every: int = 1, want_power: bool = False,
+                     **find) -> FindResult:
+        """The same from unpacked samples [n_streams, N] (N a multiple of 256, oldest first) (awpu_hip_find_samples)."""
+        samples = np.ascontiguousarray(samples, np.float32)
+        if samples.ndim != 2 or samples.shape[0] != self.cfg.n_streams or samples.shape[1] % 256 or samples.shape[1] == 0:
+            raise ValueError(f"samples must be [{self.cfg.n_streams}, N] with N a positive multiple of 256")
+        return self._find(lambda *rest: self._lib.awpu_hip_find_samples(self._h, _f32(samples), samples.shape[1], *rest),
+                          "awpu_hip_find_samples", samples.shape[1] // 256, rows, cols, first, every, find, want_power)
+
+    def find_samples_device(self, d_samples_ptr: int, pitch: int, n_blocks: int, rows: int, cols: int, d_sources_ptr: int,
+                            d_count_ptr: int, first: int = 0, every: int = 1, d_power_ptr: int = 0, stream: int = 0, **find) -> int:
+        """The same on device pointers (samples [n_streams, pitch]; sources [n_frames, max_sources] records of 40 bytes, count
+        [n_frames] int32, power [n_frames, pixels] or 0) on `stream`; asynchronous.  -> next_first
+        (awpu_hip_find_samples_device)."""
+        w = Watch(first, every, rows, cols, 0, 0, 0, None)
+        f = Find(rows, cols, find.get("radius", 2), find.get("max_sources", 4), find.get("min_power", 0.0), find.get("min_ratio", 0.0),
+                 find.get("fov_deg", 180.0))
+        _check(self._lib.awpu_hip_find_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, C.byref(w), C.byref(f),
+                                                      C.c_void_p(d_sources_ptr), C.c_void_p(d_count_ptr), C.c_void_p(d_power_ptr),
+                                                      C.c_void_p(stream)), "awpu_hip_find_samples_device")
         return watch_count(n_blocks, first, every)[1]
 
     def set_fir_table(self, coeffs: np.ndarray) -> None:

@@ -373,6 +373,9 @@ struct awpu_hip {
     // host forms bring the images back through pinned watch.h[i & 1].  The events are those of the runs above: ev_blk_swept[b] is
     // recorded behind the display kernels, ev_blk_out[b] behind the images' way back.
     awpu::host::BufferPair watch;
+    // finding in such runs (awpu_hip_find.h), host forms: piece i's counts, then its sources, in find_out.d[i & 1] and back through
+    // pinned find_out.h[i & 1], behind the same two events
+    awpu::host::BufferPair find_out;
 
     awpu_hip_stats stats{};
     std::string last_error;                  // awpu_hip_last_error_of

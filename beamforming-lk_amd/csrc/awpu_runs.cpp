@@ -1,8 +1,9 @@
 // awpu_runs.cpp -- runs of consecutive blocks of a recording through one pipeline of pieces: a heatmap of every block
 // (include/awpu_hip_blocks.h), the beam audio of every block (awpu_hip_listen.h), display images of every Nth block
-// (awpu_hip_watch.h).  The handle and what is called here out of awpu_hip.cpp and awpu_sweep.cpp: awpu_handle.h.
+// (awpu_hip_watch.h), the sources in every Nth block (awpu_hip_find.h).  The handle and what is called here out of awpu_hip.cpp and awpu_sweep.cpp: awpu_handle.h.
 #include "awpu_handle.h"
 #include "awpu_hip_blocks.h"
+#include "awpu_hip_find.h"
 #include "awpu_hip_listen.h"
 #include "awpu_hip_watch.h"
 
@@ -12,6 +13,8 @@
 #include <vector>
 
 #include "block_kernels.h"
+#include "find_kernels.h"
+#include "find_rule.h"
 #include "watch_kernels.h"
 
 using namespace awpu::host;
@@ -484,13 +487,22 @@ int listen_run(awpu_hip *h, const BlockRun &src, int n_blocks, awpu_particle_t *
 // rest staged and uploaded (host forms) or gathered out of the caller's samples (device form).  Behind a piece's sweep comes its
 // display step: launch_heatmap for the whole piece, then the large image.  The ring's new snapshot is the last four blocks of
 // the call: the tail of the last piece's history when the last block is shown, a four-slot history of its own (Piece::tail)
-// otherwise.
+// otherwise.  A find run (awpu_hip_find.h) is a watch run whose display step is the peak pass: launch_find_peaks on the piece's
+// powers, its counts and sources brought back (host forms) where the images would be.
+
+// what a find call adds to a watch run; sources and count are host memory in the host forms, device memory in the device form
+struct FindRun {
+    awpu_find_t f{};
+    awpu_source_t *sources = nullptr;  // [n_frames][max_sources]
+    int32_t *count = nullptr;          // [n_frames]
+};
 
 struct WatchRun {
     awpu_watch_t w{};
     int n_frames = 0;
     uint8_t *image = nullptr, *big = nullptr;  // host memory in the host forms, device memory in the device form
     float *power = nullptr;
+    const FindRun *find = nullptr;
 };
 
 // slots [q, slots) of a piece's history (watch_kernels.h) into pinned blk_in.h[b]: tight datagrams, or rows of 256 * (slots - q)
@@ -523,15 +535,17 @@ struct WatchPieces final : Consumer {
     const BlockRun &src;
     const WatchRun &wr;
     const awpu_watch_t &w;
+    const FindRun *const fr;
     const bool host, want_small;
     const int S, m;
     const size_t P, big_bytes;
     int lo = 0, width = 0;
     size_t small_off = 0, big_off = 0;  // in a watch buffer: the peaks, then the compact images, then the large ones
+    size_t sources_off = 0;             // in a find buffer: the counts, then the sources
     const float *snapshot = nullptr;    // blocks -4 .. -1 of the call
 
     WatchPieces(awpu_hip *h_, const BlockRun &src_, int n_blocks_, const WatchRun &wr_)
-        : h(h_), src(src_), wr(wr_), w(wr_.w), host(!src_.device), want_small(wr_.image || wr_.big), S(h_->cfg.n_streams), m(std::min(wr_.w.every, 4)),
+        : h(h_), src(src_), wr(wr_), w(wr_.w), fr(wr_.find), host(!src_.device), want_small(wr_.image || wr_.big), S(h_->cfg.n_streams), m(std::min(wr_.w.every, 4)),
           P((size_t) h_->cfg.pixel_count), big_bytes((size_t) wr_.w.out_rows * wr_.w.out_cols * (wr_.w.d_colormap ? 3 : 1)) {
         n_items = wr.n_frames;
         n_blocks = n_blocks_;
@@ -563,6 +577,8 @@ struct WatchPieces final : Consumer {
         if (rc == AWPU_OK && !host && !wr.power) rc = ensure_power(h, (size_t) piece_max * P);
         if (rc == AWPU_OK && want_small) rc = h->watch.ensure(big_off + (host && wr.big ? (size_t) piece_max * big_bytes : 0), host);
         if (rc == AWPU_OK && wr.big) rc = ensure_taps(h, w.rows, w.cols, w.out_rows, w.out_cols, sw);
+        sources_off = align16(sizeof(int32_t) * piece_max);
+        if (rc == AWPU_OK && fr && host) rc = h->find_out.ensure(sources_off + source_bytes(piece_max), true);
         return rc;
     }
     int staged_blocks(const Piece &p) override {
@@ -590,7 +606,14 @@ struct WatchPieces final : Consumer {
         AWPU_HIP_TRY(awpu::launch_watch_cut(hist_of(h, p.b), pitch, S, p.n, awpu::kSamples * m, lo, width, h->d_blk_frames, s));
         return AWPU_OK;
     }
+    size_t source_bytes(int nf) const { return (size_t) nf * fr->f.max_sources * sizeof(awpu_source_t); }
     int show(const Piece &p, float *d_pow, hipStream_t s) override {
+        if (fr) {
+            unsigned char *out = h->find_out.d[p.b];
+            AWPU_HIP_TRY(awpu::launch_find_peaks(d_pow, p.n, fr->f,
+                                                 host ? reinterpret_cast<awpu_source_t *>(out + sources_off) : fr->sources + (size_t) p.first * fr->f.max_sources,
+                                                 host ? reinterpret_cast<int32_t *>(out) : fr->count + p.first, s));
+        }
         if (!want_small) return AWPU_OK;
         uint8_t *scratch = h->watch.d[host ? p.b : 0];
         uint8_t *d_small = host || !wr.image ? scratch + small_off : wr.image + (size_t) p.first * P;
@@ -601,12 +624,17 @@ struct WatchPieces final : Consumer {
         return AWPU_OK;
     }
     int fetch_shown(const Piece &p, hipStream_t s) override {
+        if (fr) AWPU_HIP_TRY(hipMemcpyAsync(h->find_out.h[p.b], h->find_out.d[p.b], sources_off + source_bytes(p.n), hipMemcpyDeviceToHost, s));
         uint8_t *to = h->watch.h[p.b], *from = h->watch.d[p.b];
         if (wr.image) AWPU_HIP_TRY(hipMemcpyAsync(to + small_off, from + small_off, (size_t) p.n * P, hipMemcpyDeviceToHost, s));
         if (wr.big) AWPU_HIP_TRY(hipMemcpyAsync(to + big_off, from + big_off, (size_t) p.n * big_bytes, hipMemcpyDeviceToHost, s));
         return AWPU_OK;
     }
     int deliver_shown(const Piece &p) override {
+        if (fr) {
+            std::memcpy(fr->count + p.first, h->find_out.h[p.b], sizeof(int32_t) * p.n);
+            std::memcpy(fr->sources + (size_t) p.first * fr->f.max_sources, h->find_out.h[p.b] + sources_off, source_bytes(p.n));
+        }
         if (wr.image) std::memcpy(wr.image + (size_t) p.first * P, h->watch.h[p.b] + small_off, (size_t) p.n * P);
         if (wr.big) parallel_copy(wr.big + (size_t) p.first * big_bytes, h->watch.h[p.b] + big_off, (size_t) p.n * big_bytes);
         return AWPU_OK;
@@ -615,9 +643,10 @@ struct WatchPieces final : Consumer {
 };
 
 // the checks of a watch call that read no handle; then the run
-int watch_run(awpu_hip *h, const BlockRun &src, int n_blocks, const awpu_watch_t *w, uint8_t *image, uint8_t *big, float *power, hipStream_t user) {
+int watch_run(awpu_hip *h, const BlockRun &src, int n_blocks, const awpu_watch_t *w, uint8_t *image, uint8_t *big, float *power, hipStream_t user,
+              const FindRun *find = nullptr) {
     if (!w) return invalid("null argument");
-    if (!image && !big && !power) return invalid("no output asked for");
+    if (!image && !big && !power && !find) return invalid("no output asked for");
     if (w->every < 1 || w->every > AWPU_WATCH_MAX_EVERY) return invalid("every outside [1, 1024]");
     if (w->first < 0) return invalid("first below 0");
     if (w->flip != 0 && w->flip != 1) return invalid("flip is 0 or 1");
@@ -631,9 +660,22 @@ int watch_run(awpu_hip *h, const BlockRun &src, int n_blocks, const awpu_watch_t
     wr.image = image;
     wr.big = big;
     wr.power = power;
+    wr.find = find;
     AWPU_CTX(h);
     WatchPieces c(h, src, n_blocks, wr);
     return run_pieces(h, src, user, c);
+}
+
+// the checks of a find call that read no handle; then the watch run that finds: of `w` only first, every, rows and cols count
+int find_run(awpu_hip *h, const BlockRun &src, int n_blocks, const awpu_watch_t *w, const awpu_find_t *f, awpu_source_t *sources, int32_t *count,
+             float *power, hipStream_t user) {
+    if (!w || !sources || !count) return invalid("null argument");
+    if (const char *why = awpu::find_refusal(f)) return invalid(why);
+    if (f->rows != w->rows || f->cols != w->cols) return invalid("the find grid must be the watch grid");
+    awpu_watch_t shown{};
+    shown.first = w->first, shown.every = w->every, shown.rows = w->rows, shown.cols = w->cols;
+    const FindRun find{*f, sources, count};
+    return watch_run(h, src, n_blocks, &shown, nullptr, nullptr, power, user, &find);
 }
 
 }  // namespace
@@ -720,6 +762,39 @@ int awpu_hip_watch_samples_device(awpu_hip_t *h, const float *d_samples, int64_t
     BlockRun src;
     if (int rc = sample_source(h, d_samples, pitch, n_blocks, true, &src)) return rc;
     return watch_run(h, src, n_blocks, w, d_image, d_big_image, d_power, static_cast<hipStream_t>(stream));
+}
+
+int awpu_hip_find_peaks_device(awpu_hip_t *h, const float *d_power, int32_t n_frames, const awpu_find_t *f, awpu_source_t *d_sources,
+                               int32_t *d_count, void *stream) {
+    if (!h || !d_power || !d_sources || !d_count) return invalid("null argument");
+    if (n_frames < 1) return invalid("n_frames below 1");
+    if (const char *why = awpu::find_refusal(f)) return invalid(why);
+    h = first_device(h);
+    AWPU_CTX(h);
+    AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
+    AWPU_HIP_TRY(awpu::launch_find_peaks(d_power, n_frames, *f, d_sources, d_count, stream ? static_cast<hipStream_t>(stream) : h->stream));
+    return AWPU_OK;
+}
+
+int awpu_hip_find_blocks(awpu_hip_t *h, const void *datagrams, int32_t stride_bytes, int32_t n_blocks, const awpu_watch_t *w,
+                         const awpu_find_t *f, awpu_source_t *sources, int32_t *count, float *power) {
+    BlockRun src;
+    if (int rc = wire_source(h, datagrams, stride_bytes, n_blocks, &src)) return rc;
+    return find_run(h, src, n_blocks, w, f, sources, count, power, nullptr);
+}
+
+int awpu_hip_find_samples(awpu_hip_t *h, const float *samples, int64_t pitch, int32_t n_blocks, const awpu_watch_t *w,
+                          const awpu_find_t *f, awpu_source_t *sources, int32_t *count, float *power) {
+    BlockRun src;
+    if (int rc = sample_source(h, samples, pitch, n_blocks, false, &src)) return rc;
+    return find_run(h, src, n_blocks, w, f, sources, count, power, nullptr);
+}
+
+int awpu_hip_find_samples_device(awpu_hip_t *h, const float *d_samples, int64_t pitch, int32_t n_blocks, const awpu_watch_t *w,
+                                 const awpu_find_t *f, awpu_source_t *d_sources, int32_t *d_count, float *d_power, void *stream) {
+    BlockRun src;
+    if (int rc = sample_source(h, d_samples, pitch, n_blocks, true, &src)) return rc;
+    return find_run(h, src, n_blocks, w, f, d_sources, d_count, d_power, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"
