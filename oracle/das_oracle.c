@@ -15,6 +15,39 @@
 #include <stdlib.h>
 #include <string.h>
 
+/* ------------------------------------------------------- floating-point environment */
+
+/* The restatement is IEEE arithmetic with gradual underflow.  On x86 that is a property of the calling THREAD, not of this
+ * file: MXCSR's flush-to-zero (bit 15) and denormals-are-zero (bit 6) bits are switched on by the start-up code of any object
+ * linked with -ffast-math / -Ofast -- oracle/_ref is one, loaded into the same process by the tests.  So every arithmetic
+ * entry point clears the two bits for its own duration and hands the caller's MXCSR back.  Elsewhere: nothing. */
+#if defined(__x86_64__) || defined(__i386__) || defined(_M_X64)
+#include <xmmintrin.h>
+#define ORACLE_MXCSR_FTZ 0x8000u
+#define ORACLE_MXCSR_DAZ 0x0040u
+static inline unsigned fp_enter(void) {
+    const unsigned saved = _mm_getcsr();
+    _mm_setcsr(saved & ~(ORACLE_MXCSR_FTZ | ORACLE_MXCSR_DAZ));
+    return saved;
+}
+static inline void fp_leave(unsigned saved) { _mm_setcsr(saved); }
+unsigned oracle_fp_flush_bits(void) {
+    const unsigned csr = _mm_getcsr();
+    return ((csr & ORACLE_MXCSR_FTZ) ? ORACLE_FP_FTZ : 0u) | ((csr & ORACLE_MXCSR_DAZ) ? ORACLE_FP_DAZ : 0u);
+}
+void oracle_fp_set_flush_bits(unsigned bits) {
+    unsigned csr = _mm_getcsr() & ~(ORACLE_MXCSR_FTZ | ORACLE_MXCSR_DAZ);
+    if (bits & ORACLE_FP_FTZ) csr |= ORACLE_MXCSR_FTZ;
+    if (bits & ORACLE_FP_DAZ) csr |= ORACLE_MXCSR_DAZ;
+    _mm_setcsr(csr);
+}
+#else
+static inline unsigned fp_enter(void) { return 0u; }
+static inline void fp_leave(unsigned saved) { (void) saved; }
+unsigned oracle_fp_flush_bits(void) { return 0u; }
+void oracle_fp_set_flush_bits(unsigned bits) { (void) bits; }
+#endif
+
 /* ------------------------------------------------------------------ geometry */
 
 /* src/geometry/antenna.cpp:60-87.  Note the reference centres x with `rows`
@@ -153,18 +186,23 @@ void oracle_compute_delays_f64(const float *xyz, int n, int rows, int columns, f
 /* --------------------------------------------------------------------- delay */
 
 /* src/dsp/delay.cpp:16-26: out += fma(f, cur - next, next) per sample. */
-void oracle_delay_lerp(float *out, const float *signal, float fraction) {
+static void delay_lerp(float *out, const float *signal, float fraction) {
     for (int i = 0; i < ORACLE_N_SAMPLES; i++) {
         const float d = signal[i] - signal[i + 1];
         const float t = fmaf(fraction, d, signal[i + 1]);
         out[i] = out[i] + t;
     }
 }
+void oracle_delay_lerp(float *out, const float *signal, float fraction) {
+    const unsigned fp = fp_enter();
+    delay_lerp(out, signal, fraction);
+    fp_leave(fp);
+}
 
 /* src/dsp/delay.cpp:31-40.  The build that selects this variant has no FMA (no -mavx2 / -mfma) and keeps the source's
  * order: product, then the add into out[n], i = 0..7.  With -ffp-contract=off this loop leaves the reference object
  * code's bits in out[] (tests/test_oracle_golden.py, on the known answers and on whole sweeps). */
-void oracle_delay_fir8(float *out, const float *signal, float fraction, const float *coeffs) {
+static void delay_fir8(float *out, const float *signal, float fraction, const float *coeffs) {
     const float get_filter = fraction * 100.0f + 0.5f;
     const int delay_int = (int) get_filter;
     for (int n = 0; n < ORACLE_N_SAMPLES; ++n) {
@@ -172,6 +210,11 @@ void oracle_delay_fir8(float *out, const float *signal, float fraction, const fl
             out[n] += coeffs[delay_int * 8 + i] * signal[n + i];
         }
     }
+}
+void oracle_delay_fir8(float *out, const float *signal, float fraction, const float *coeffs) {
+    const unsigned fp = fp_enter();
+    delay_fir8(out, signal, fraction, coeffs);
+    fp_leave(fp);
 }
 
 /* --------------------------------------------------------------------- sweep */
@@ -192,6 +235,7 @@ static float epilogue_f32(const float *out, int count) {
 void oracle_das_f32(const float *X, int hist, const int32_t *off, const float *frac, int P,
                     int lut_stride, const int32_t *index, int usable, float *power,
                     float *out_dbg) {
+    const unsigned fp = fp_enter();
     for (int m = 0; m < P; m++) {
         float out[ORACLE_N_SAMPLES] = {0.0f};
         int count = 0;
@@ -199,12 +243,13 @@ void oracle_das_f32(const float *X, int hist, const int32_t *off, const float *f
             const int i = index[s];
             const float fraction = frac[(size_t) m * lut_stride + i];
             const int offset = off[(size_t) m * lut_stride + i];
-            oracle_delay_lerp(out, X + (size_t) i * hist + offset, fraction);
+            delay_lerp(out, X + (size_t) i * hist + offset, fraction);
             count++;
         }
         if (out_dbg) memcpy(out_dbg + (size_t) m * ORACLE_N_SAMPLES, out, sizeof(out));
         power[m] = epilogue_f32(out, count);
     }
+    fp_leave(fp);
 }
 
 /* Particle::beam and Particle::das, src/dsp/particle.cpp:51-82 and :88-103 (USE_BANDPASS 1,
@@ -214,12 +259,13 @@ void oracle_das_f32(const float *X, int hist, const int32_t *off, const float *f
  * result (MISOWorker hands it to the audio path, src/dsp/miso.cpp:46). */
 void oracle_particle_beams(const float *X, int hist, const int32_t *off, const float *frac, int n_dir,
                            int lut_stride, const int32_t *index, int usable, float *power, float *beams) {
+    const unsigned fp = fp_enter();
     for (int m = 0; m < n_dir; m++) {
         float out[ORACLE_N_SAMPLES] = {0.0f};
         for (int s = 0; s < usable; s++) {
             const int i = index[s];
-            oracle_delay_lerp(out, X + (size_t) i * hist + off[(size_t) m * lut_stride + i],
-                              frac[(size_t) m * lut_stride + i]);
+            delay_lerp(out, X + (size_t) i * hist + off[(size_t) m * lut_stride + i],
+                       frac[(size_t) m * lut_stride + i]);
         }
         float power_accumulator = 0.0f;
         for (int i = 1; i < ORACLE_N_SAMPLES - 1; i++) {
@@ -230,23 +276,26 @@ void oracle_particle_beams(const float *X, int hist, const int32_t *off, const f
         if (power) power[m] = power_accumulator;
         if (beams) memcpy(beams + (size_t) m * ORACLE_N_SAMPLES, out, sizeof(out));
     }
+    fp_leave(fp);
 }
 
 void oracle_das_fir8_f32(const float *X, int hist, const int32_t *off, const float *frac, int P,
                          int lut_stride, const int32_t *index, int usable, const float *coeffs,
                          float *power, float *out_dbg) {
+    const unsigned fp = fp_enter();
     for (int m = 0; m < P; m++) {
         float out[ORACLE_N_SAMPLES] = {0.0f};
         int count = 0;
         for (int s = 0; s < usable; s++) {
             const int i = index[s];
-            oracle_delay_fir8(out, X + (size_t) i * hist + off[(size_t) m * lut_stride + i],
-                              frac[(size_t) m * lut_stride + i], coeffs);
+            delay_fir8(out, X + (size_t) i * hist + off[(size_t) m * lut_stride + i],
+                       frac[(size_t) m * lut_stride + i], coeffs);
             count++;
         }
         if (out_dbg) memcpy(out_dbg + (size_t) m * ORACLE_N_SAMPLES, out, sizeof(out));
         power[m] = epilogue_f32(out, count);
     }
+    fp_leave(fp);
 }
 
 /* NOT a restatement of reference code: the checker of the build's own AWPU_MATH_BF16_ACC mode (BASELINE
@@ -262,6 +311,7 @@ static float oracle_round_bf16(float x) {
 
 void oracle_das_bf16acc(const float *X, int hist, const int32_t *off, const float *frac, int P,
                         int lut_stride, const int32_t *index, int usable, float *power) {
+    const unsigned fp = fp_enter();
     for (int m = 0; m < P; m++) {
         float out[ORACLE_N_SAMPLES];
         for (int i = 0; i < ORACLE_N_SAMPLES; i++) out[i] = 0.0f;
@@ -276,10 +326,12 @@ void oracle_das_bf16acc(const float *X, int hist, const int32_t *off, const floa
         }
         power[m] = epilogue_f32(out, usable);
     }
+    fp_leave(fp);
 }
 
 void oracle_das_f64(const float *X, int hist, const int32_t *off, const float *frac, int P,
                     int lut_stride, const int32_t *index, int usable, double *power) {
+    const unsigned fp = fp_enter();
     for (int m = 0; m < P; m++) {
         double out[ORACLE_N_SAMPLES];
         for (int i = 0; i < ORACLE_N_SAMPLES; i++) out[i] = 0.0;
@@ -299,6 +351,7 @@ void oracle_das_f64(const float *X, int hist, const int32_t *off, const float *f
         }
         power[m] = p / (double) (ORACLE_N_SAMPLES * usable);
     }
+    fp_leave(fp);
 }
 
 /* The FIR8 sweep (delay.cpp:31-40 inside mimo.cpp:121-151) with every sum in double: the tie-breaker that shows how
@@ -306,6 +359,7 @@ void oracle_das_f64(const float *X, int hist, const int32_t *off, const float *f
 void oracle_das_fir8_f64(const float *X, int hist, const int32_t *off, const float *frac, int P,
                          int lut_stride, const int32_t *index, int usable, const float *coeffs,
                          double *power) {
+    const unsigned fp = fp_enter();
     for (int m = 0; m < P; m++) {
         double out[ORACLE_N_SAMPLES];
         for (int i = 0; i < ORACLE_N_SAMPLES; i++) out[i] = 0.0;
@@ -324,6 +378,7 @@ void oracle_das_fir8_f64(const float *X, int hist, const int32_t *off, const flo
         }
         power[m] = p / (double) (ORACLE_N_SAMPLES * usable);
     }
+    fp_leave(fp);
 }
 
 /* ------------------------------------------------------------------- display */
@@ -409,6 +464,7 @@ static int cmp_float(const void *a, const void *b) {
 /* src/aw_processing_unit/aw_processing_unit.cpp:128-200 (one array). */
 int oracle_calibrate(const float *X, int hist, float reference_power_level, int32_t *index,
                      float *corr, float *median_out) {
+    const unsigned fp = fp_enter();
     float power[ORACLE_ELEMENTS];
     for (int s = 0; s < ORACLE_ELEMENTS; s++) {
         float pv = 0.0f;
@@ -433,6 +489,7 @@ int oracle_calibrate(const float *X, int hist, float reference_power_level, int3
         }
     }
     if (median_out) *median_out = median;
+    fp_leave(fp);
     return count;
 }
 

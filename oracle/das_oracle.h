@@ -33,6 +33,16 @@ extern "C" {
 #define ORACLE_ELEMENTS 64
 #define ORACLE_DISTANCE 0.02
 
+/* The floating-point environment (not reference code).  The restatement means IEEE arithmetic with gradual underflow: every
+ * arithmetic entry point below (the delay, sweep, beam and calibrate functions, fp32 and fp64) runs with the calling thread's
+ * flush-to-zero and denormals-are-zero modes (x86 MXCSR) switched off and restores the caller's mode on return.  The reference as
+ * built (-Ofast) runs with both on; the two agree bit for bit wherever samples, differences and sums are zero or normal.
+ * oracle_fp_flush_bits / oracle_fp_set_flush_bits read and set the two modes of the calling thread (0 / no-op off x86). */
+#define ORACLE_FP_FTZ 1u
+#define ORACLE_FP_DAZ 2u
+unsigned oracle_fp_flush_bits(void);
+void oracle_fp_set_flush_bits(unsigned bits);
+
 /* create_antenna, src/geometry/antenna.cpp:60-87.  xyz is 3 x (rows*columns),
  * row-major by coordinate (xyz[0*n+i]=x_i ...), element i = r*columns + c. */
 void oracle_create_antenna(int columns, int rows, float distance, float *xyz);

@@ -77,6 +77,10 @@ def oracle() -> C.CDLL:
         lib.oracle_calibrate.argtypes = [_f32p, C.c_int, C.c_float, _i32p, _f32p, _f32p]
         lib.oracle_calibrate.restype = C.c_int
         lib.oracle_unpack_exposure.argtypes = [_i32p, C.c_int, C.c_int, _f32p]
+        lib.oracle_fp_flush_bits.argtypes = []
+        lib.oracle_fp_flush_bits.restype = C.c_uint
+        lib.oracle_fp_set_flush_bits.argtypes = [C.c_uint]
+        lib.oracle_fp_set_flush_bits.restype = None
         for name in ("oracle_create_antenna", "oracle_create_tiled_antenna", "oracle_steering_delays_f32",
                      "oracle_steering_delays_f64", "oracle_compute_delay_lut", "oracle_compute_delays_f64",
                      "oracle_delay_lerp", "oracle_delay_fir8", "oracle_das_f32", "oracle_das_f64",
@@ -84,6 +88,45 @@ def oracle() -> C.CDLL:
             getattr(lib, name).restype = None
         _oracle = lib
     return _oracle
+
+
+FP_FTZ, FP_DAZ = 1, 2  # ORACLE_FP_FTZ, ORACLE_FP_DAZ (das_oracle.h)
+
+
+def fp_flush_bits() -> int:
+    """The calling thread's flush-to-zero / denormals-are-zero modes, FP_FTZ | FP_DAZ (0 where the host has no such mode)."""
+    return int(oracle().oracle_fp_flush_bits())
+
+
+def set_fp_flush_bits(bits: int) -> None:
+    oracle().oracle_fp_set_flush_bits(int(bits))
+
+
+def _sets_fp_mode(path: Path) -> bool:
+    """Was this oracle/_ref library built from the present ref_mimo_driver.cpp, whose entry points set the reference's mode?"""
+    return b"ref_sets_fp_mode" in path.read_bytes()
+
+
+class _InReferenceMode:
+    """A library whose calls run with flush-to-zero and denormals-are-zero set -- how the reference runs as built -- and hand the
+    caller's mode back.  For an oracle/_ref that was built from an earlier ref_mimo_driver.cpp and cannot be rebuilt here (prebuilt,
+    the reference tree absent): its entry points run in the caller's mode, so this sets the mode for them."""
+
+    def __init__(self, lib):
+        self._lib = lib
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+
+        def call(*args):
+            mode = fp_flush_bits()
+            set_fp_flush_bits(FP_FTZ | FP_DAZ)
+            try:
+                return fn(*args)
+            finally:
+                set_fp_flush_bits(mode)
+
+        return call
 
 
 def ref_available(variant: str = "avx2") -> bool:
@@ -94,11 +137,17 @@ def ref(variant: str = "avx2") -> C.CDLL:
     """The reference's compiled delay() + loop-nest driver.  Raises if oracle/_ref is absent."""
     if variant not in _refs:
         path = REF_AVX2_LIB if variant == "avx2" else REF_FIR_LIB
-        if not path.exists():
+        can_build = _in_reference_tree("src/dsp/delay.cpp") is not None and os.environ.get("AWPU_NO_BUILD") != "1"
+        if not path.exists() or (can_build and not _sets_fp_mode(path)):  # (absent, or left by an earlier ref_mimo_driver.cpp)
             build(ref=True)
         if not path.exists():
             raise FileNotFoundError(f"{path} missing and {REFERENCE_TREE} not available to build it")
+        # The library is linked with -Ofast: loading it runs gcc's fast-math start-up code, which switches flush-to-zero and
+        # denormals-are-zero on in THIS thread -- numpy and everything else in the process would flush subnormals from here on.
+        # The mode is put back; ref_mimo_driver.cpp's entry points switch it on for themselves.
+        mode = fp_flush_bits()
         lib = C.CDLL(str(path))
+        set_fp_flush_bits(mode)
         lib.ref_variant.restype = C.c_int
         lib.ref_delay.argtypes = [_f32p, _f32p, C.c_float]
         lib.ref_delay.restype = None
@@ -112,7 +161,7 @@ def ref(variant: str = "avx2") -> C.CDLL:
         lib.ref_das_bench_mt.argtypes = [_f32p, C.c_int, _i32p, _f32p, C.c_int, C.c_int, _i32p, C.c_int, _f32p,
                                          C.c_double, C.c_int, C.POINTER(C.c_int)]
         lib.ref_das_bench_mt.restype = C.c_double
-        _refs[variant] = lib
+        _refs[variant] = lib if _sets_fp_mode(path) else _InReferenceMode(lib)
     return _refs[variant]
 
 

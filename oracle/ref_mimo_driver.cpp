@@ -24,6 +24,28 @@
 /* the reference symbol, src/dsp/delay.h:31 */
 void delay(float *out, const float *signal, const float fraction);
 
+/* The reference's floating-point mode.  Its CMakeLists.txt:7 compiles and links everything with -Ofast -ffast-math, and gcc then
+ * links crtfastmath.o, whose start-up code switches flush-to-zero and denormals-are-zero on (x86 MXCSR bits 15 and 6) before
+ * main(): the reference executable's delay() runs with both set.  In a shared library that start-up code runs in whichever
+ * thread loads it, so what delay() did here used to depend on who had loaded the library.  Every entry point below therefore
+ * sets the two bits itself for its duration -- the reference as built -- and restores the caller's mode on return. */
+#if defined(__x86_64__) || defined(__i386__)
+#include <xmmintrin.h>
+namespace {
+struct ReferenceFpMode {
+    unsigned saved;
+    ReferenceFpMode() : saved(_mm_getcsr()) { _mm_setcsr(saved | 0x8040u); }
+    ~ReferenceFpMode() { _mm_setcsr(saved); }
+};
+}  // namespace
+#else
+namespace {
+struct ReferenceFpMode {
+    ~ReferenceFpMode() {}  // (non-trivial: no unused-variable warning)
+};
+}  // namespace
+#endif
+
 extern "C" {
 
 /* 1 = AVX2 linear interpolation (delay.cpp:16-26), 2 = 8-tap FIR (delay.cpp:31-40) */
@@ -35,11 +57,19 @@ int ref_variant(void) {
 #endif
 }
 
-void ref_delay(float *out, const float *signal, float fraction) { delay(out, signal, fraction); }
+/* 1: the entry points below run in the reference's floating-point mode whatever the caller's is.  (oracle_py.ref() looks for this
+ * symbol: a library built from an earlier version of this file runs in the caller's mode.) */
+int ref_sets_fp_mode(void) { return 1; }
+
+void ref_delay(float *out, const float *signal, float fraction) {
+    ReferenceFpMode fp;
+    delay(out, signal, fraction);
+}
 
 /* src/dsp/mimo.cpp:121-151 around the reference delay(). */
 void ref_das(const float *X, int hist, const int32_t *off, const float *frac, int P, int lut_stride,
              const int32_t *index, int usable, float *power, float *out_dbg) {
+    ReferenceFpMode fp;
     for (int m = 0; m < P; m++) {
         float out[N_SAMPLES] = {0.0};
         int count = 0;
@@ -92,6 +122,7 @@ double ref_das_bench_mt(const float *X, int hist, const int32_t *off, const floa
 /* src/dsp/particle.cpp:51-82 / :88-103 (Particle::beam, Particle::das) around the reference delay() */
 void ref_particle_beams(const float *X, int hist, const int32_t *off, const float *frac, int n_dir, int lut_stride,
                         const int32_t *index, int usable, float *power, float *beams) {
+    ReferenceFpMode fp;
     for (int m = 0; m < n_dir; m++) {
         float out[N_SAMPLES] = {0.0};
         for (int s = 0; s < usable; s++) {
