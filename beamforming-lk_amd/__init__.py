@@ -15,6 +15,8 @@ from .binding import (  # noqa: F401
     MATH_F32_FAST,
     AwpuError,
     Engine,
+    band_design,
+    band_filter,
     build_delay_table,
     build_delay_table_device,
     create_antenna,
@@ -28,6 +30,6 @@ from .binding import (  # noqa: F401
 
 __all__ = [
     "Engine", "AwpuError", "MATH_F32_EXACT", "MATH_F32_FAST", "MATH_BF16_ACC", "build_delay_table", "build_delay_table_device",
-    "create_antenna", "create_tiled_antenna", "steering_delays", "heatmap_u8", "find_peaks", "resize_linear_u8", "steer_table", "binding",
+    "create_antenna", "create_tiled_antenna", "steering_delays", "heatmap_u8", "find_peaks", "band_design", "band_filter", "resize_linear_u8", "steer_table", "binding",
     "synthetic", "_build",
 ]

@@ -251,6 +251,15 @@ _FIND_SIGNATURES = {
 }
 FIND_SYMBOLS = tuple(_FIND_SIGNATURES)
 
+# band-limited heatmaps: the entry points of include/awpu_hip_band.h
+BAND_MAX_TAPS = 128
+_BAND_SIGNATURES = {
+    "awpu_hip_band_filter": (C.c_int, [_f32p, C.c_int32, C.c_int64, C.c_int32, _f32p, C.c_int32, _f32p]),
+    "awpu_hip_band_design": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_int32, _f32p]),
+    "awpu_hip_set_band": (C.c_int, [C.c_void_p, _f32p, C.c_int32]),
+}
+BAND_SYMBOLS = tuple(_BAND_SIGNATURES)
+
 # numpy view of awpu_source_t: what find_peaks and Engine.find_* return, max_sources records per frame
 SOURCE_DTYPE = np.dtype([("pixel", "<i4"), ("power", "<f4"), ("row", "<f8"), ("col", "<f8"), ("theta", "<f8"), ("phi", "<f8")], align=True)
 assert SOURCE_DTYPE.itemsize == C.sizeof(Source) == 40
@@ -283,7 +292,7 @@ def load(build: bool = True) -> C.CDLL:
         raise RuntimeError(f"{path} is missing and there is no CPU fallback")
     lib = C.CDLL(str(path))
     for name, (res, args) in list(_SIGNATURES.items()) + list(_TRACK_SIGNATURES.items()) + list(_BLOCK_SIGNATURES.items()) + \
-            list(_LISTEN_SIGNATURES.items()) + list(_WATCH_SIGNATURES.items()) + list(_FIND_SIGNATURES.items()):
+            list(_LISTEN_SIGNATURES.items()) + list(_WATCH_SIGNATURES.items()) + list(_FIND_SIGNATURES.items()) + list(_BAND_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -494,6 +503,33 @@ def find_peaks(power: np.ndarray, rows: int, cols: int, radius: int = 2, max_sou
     _check(load().awpu_hip_find_peaks(_f32(power), len(power), C.byref(f), sources.ctypes.data_as(C.c_void_p),
                                       count.ctypes.data_as(C.c_void_p)), "awpu_hip_find_peaks")
     return FindResult(sources, count)
+
+
+def band_design(lo_hz: float, hi_hz: float, taps: int = 63, sample_rate: float = 48828.125) -> np.ndarray:
+    """Coefficients [taps] of a linear-phase band lo_hz .. hi_hz by the window method (awpu_hip_band_design: what fir1 does by
+    default); taps odd in [3, 127], lo_hz = 0 a low-pass, hi_hz = sample_rate / 2 a high-pass."""
+    c = np.empty(max(int(taps), 1), np.float32)
+    _check(load().awpu_hip_band_design(float(lo_hz), float(hi_hz), float(sample_rate), int(taps), _f32(c)), "awpu_hip_band_design")
+    return c
+
+
+def band_from_text(text: str, sample_rate: float = 48828.125) -> np.ndarray:
+    """'LO:HI[:TAPS]' (Hz; 63 taps unless given), as the tools' --band takes it -> band_design's coefficients."""
+    parts = text.split(":")
+    if len(parts) not in (2, 3):
+        raise ValueError(f"band '{text}': LO:HI or LO:HI:TAPS, in Hz")
+    return band_design(float(parts[0]), float(parts[1]), int(parts[2]) if len(parts) == 3 else 63, sample_rate)
+
+
+def band_filter(samples: np.ndarray, coeffs: np.ndarray) -> np.ndarray:
+    """Every row of `samples` [..., n] through the band's rule on the host (awpu_hip_band_filter): what a handle with these
+    coefficients sweeps in place of `samples`, bit for bit."""
+    x = np.ascontiguousarray(samples, np.float32)
+    c = np.ascontiguousarray(coeffs, np.float32).reshape(-1)
+    y = np.empty_like(x)
+    n = x.shape[-1] if x.ndim else 0
+    _check(load().awpu_hip_band_filter(_f32(x), x.size // n if n else 0, n, n, _f32(c), c.size, _f32(y)), "awpu_hip_band_filter")
+    return y
 
 
 def _particles(theta, phi, spread, rate, steps, where: str) -> np.ndarray:
@@ -961,6 +997,15 @@ class Engine:
         if gains.shape != (self.cfg.n_streams,):
             raise ValueError("gains must be [n_streams]")
         _check(self._lib.awpu_hip_set_mic_gains(self._h, _f32(gains)), "set_mic_gains")
+
+    def set_band(self, coeffs: Optional[np.ndarray]) -> None:
+        """The handle's band (awpu_hip_set_band): FIR coefficients [taps <= 128] every sweep's input goes through first, e.g.
+        band_design(6375, 9000); None = off.  Heatmaps, images and sources follow it; beams, tracking and audio do not."""
+        if coeffs is None:
+            _check(self._lib.awpu_hip_set_band(self._h, None, 0), "awpu_hip_set_band")
+            return
+        c = np.ascontiguousarray(coeffs, np.float32).reshape(-1)
+        _check(self._lib.awpu_hip_set_band(self._h, _f32(c), c.size), "awpu_hip_set_band")
 
     def _calibrated(self, call):
         index = np.empty(64, np.int32)

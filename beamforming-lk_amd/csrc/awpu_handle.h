@@ -377,6 +377,12 @@ struct awpu_hip {
     // pinned find_out.h[i & 1], behind the same two events
     awpu::host::BufferPair find_out;
 
+    // the band (awpu_hip_band.h): its coefficients (empty = none; they travel to the pre-pass as kernel arguments), and the
+    // filtered frames of a call whose own frames are the caller's or the ring's, in those frames' layout (band_sweep)
+    std::vector<float> band;
+    Dev<float> d_band;
+    int band_taps() const { return static_cast<int>(band.size()); }
+
     awpu_hip_stats stats{};
     std::string last_error;                  // awpu_hip_last_error_of
     Dev<unsigned long long> d_diag;          // AWPU_FAST_DEBUG=16 cycle stamps of the last launch
@@ -460,7 +466,8 @@ int check_particles(const awpu_particle_t *p, int32_t n, double theta_limit, dou
 int check_antenna(const awpu_hip *h);
 int ensure_track_index(awpu_hip *h);
 int ensure_taps(awpu_hip *h, int rows, int cols, int out_rows, int out_cols, hipStream_t s);
-
+int band_cut(awpu_hip *h, const float *in, long long in_frame, long long in_row, int in_lo, int batch, float *out, int layout, hipStream_t s);
+int band_sweep(awpu_hip *h, const float *in, long long in_frame, long long in_row, int in_lo, int batch, float *d_power, hipStream_t s, int layout);
 
 // A buffer whose pointer the captured live-block graphs bake in (d_power, d_pack, d_display): they are retired before the old pointer
 // goes.  (prepare() and ensure_taps() retire for the tables and d_taps; launch_exact_nd for d_nd_items, a synchronize before it grows.)

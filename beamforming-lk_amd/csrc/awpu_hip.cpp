@@ -1,5 +1,5 @@
 // awpu_hip.cpp -- the C ABI of libawpu_hip.so (include/awpu_hip.h) and its call paths: handle lifetime, setters, frame upload,
-// the single-call paths, the ring, display, tracking and the packed-frame entry points.  The tables, the kernel launchers and
+// the single-call paths, the ring, display, tracking, the packed-frame entry points and the band in front of the sweeps.  The tables, the kernel launchers and
 // the dispatch rule are the sweep layer (awpu_sweep.cpp); the runs of blocks are awpu_runs.cpp; a device group's handle is
 // handed over to awpu_group.cpp.  No CPU fallback: every compute entry point ends in a gfx950 kernel launch or an error status.
 #include "awpu_handle.h"
@@ -14,6 +14,9 @@
 #include <string>
 #include <vector>
 
+#include "awpu_hip_band.h"
+#include "band_kernels.h"
+#include "band_rule.h"
 #include "das_kernels.h"
 #include "watch_kernels.h"
 
@@ -116,6 +119,8 @@ void awpu::host::retire_live_graphs(awpu_hip *h) {
 
 namespace awpu::host {
 
+const char *const kBandHistory = "the band reads taps - 1 samples in front of the window: the delay table leaves a snapshot fewer";
+
 int check_ready(awpu_hip *h, int batch) {
     if (!h) return invalid("null handle");
     if (batch < 1 || batch > h->cfg.max_batch) return invalid("batch outside [1, max_batch]");
@@ -130,6 +135,7 @@ int check_ready(awpu_hip *h, int batch) {
         const int rc = prepare(h);
         if (rc != AWPU_OK) return rc;
     }
+    if (h->band_taps() - 1 > h->wstart) return fail(AWPU_ERR_RANGE, kBandHistory);
     return AWPU_OK;
 }
 
@@ -147,7 +153,8 @@ int enqueue_host_process(awpu_hip *h, const float *frames, int batch) {
     int rc = check_ready(h, batch);
     if (rc != AWPU_OK) return rc;
     const bool compact = h->compact_hist > 0;
-    const int dev_hist = compact ? h->compact_hist : h->cfg.hist;
+    const int pre = compact ? std::max(h->band_taps() - 1, 0) : 0;  // a band reads that many samples in front of the window: they travel too
+    const int dev_hist = (compact ? h->compact_hist : h->cfg.hist) + pre;
     const size_t need_frames = (size_t) h->cfg.n_streams * dev_hist * batch;
     rc = h->d_frames.ensure(need_frames);
     if (rc == AWPU_OK) rc = ensure_power(h, (size_t) h->cfg.pixel_count * batch);
@@ -170,7 +177,7 @@ int enqueue_host_process(awpu_hip *h, const float *frames, int batch) {
         float *dst = h->d_frames + (size_t) b0 * h->cfg.n_streams * dev_hist;
         const float *src = frames + (size_t) b0 * h->cfg.n_streams * h->cfg.hist;
         if (compact) {  // rows of compact_hist floats cut out of rows of hist floats: a third of the PCIe bytes
-            AWPU_HIP_TRY(hipMemcpy2DAsync(dst, (size_t) dev_hist * sizeof(float), src + h->wstart, (size_t) h->cfg.hist * sizeof(float),
+            AWPU_HIP_TRY(hipMemcpy2DAsync(dst, (size_t) dev_hist * sizeof(float), src + h->wstart - pre, (size_t) h->cfg.hist * sizeof(float),
                                           (size_t) dev_hist * sizeof(float), (size_t) nb * h->cfg.n_streams, hipMemcpyHostToDevice, up));
         } else {
             AWPU_HIP_TRY(hipMemcpyAsync(dst, src, (size_t) nb * h->cfg.n_streams * dev_hist * sizeof(float), hipMemcpyHostToDevice, up));
@@ -181,7 +188,8 @@ int enqueue_host_process(awpu_hip *h, const float *frames, int batch) {
             if (keep_timing && b0 == 0) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, h->stream));
             h->timing = false;
         }
-        rc = launch(h, dst, nb, h->d_power + (size_t) b0 * h->cfg.pixel_count, h->stream, compact ? kCompact : kFull);
+        rc = band_sweep(h, dst, (long long) h->cfg.n_streams * dev_hist, dev_hist, compact ? pre : h->wstart, nb,
+                        h->d_power + (size_t) b0 * h->cfg.pixel_count, h->stream, compact ? kCompact : kFull);
         h->timing = keep_timing;
         if (rc != AWPU_OK) return rc;
     }
@@ -208,6 +216,54 @@ int enqueue_power_to_host(awpu_hip *h, int batch, float *power, size_t pitch) {
         done += (size_t) r.second;
     }
     return AWPU_OK;
+}
+
+// The band's pre-pass (awpu_hip_band.h; band_kernels.hip): the window of `batch` frames, filtered, into `out` in a layout launch()
+// takes -- kCompact, kFull-shaped with only the window written, or kRing-shaped (one frame, rows 2048 floats apart, `out` standing
+// for the snapshot's start).  Sample j of (frame f, stream id) is in[f * in_frame + id * in_row + j]; in_lo = where history
+// sample wstart is in such a row, with the band's taps - 1 samples in front of it (check_ready has seen to that).  What is
+// written is what a band-less call stages: the window rounded up as compact_hist is, cut at the end of the history.
+int band_cut(awpu_hip *h, const float *in, long long in_frame, long long in_row, int in_lo, int batch, float *out, int layout, hipStream_t s) {
+    const int S = h->cfg.n_streams, taps = h->band_taps();
+    awpu::BandArgs a{};
+    a.in = in;
+    a.in_frame = in_frame, a.in_row = in_row;
+    a.in_first = in_lo - (taps - 1);
+    a.out = out;
+    a.out_row = layout == kCompact ? h->compact_hist : (layout == kRing ? 2048 : h->cfg.hist);
+    a.out_frame = layout == kRing ? 0 : a.out_row * S;
+    a.out_first = layout == kCompact ? 0 : h->wstart;
+    a.n = std::min(((h->window + 3) & ~3) + 4, h->cfg.hist - h->wstart);
+    a.index = h->d_index;
+    a.usable = h->usable();
+    a.n_frames = batch;
+    a.taps = taps;
+    std::copy(h->band.begin(), h->band.end(), a.coef);
+    AWPU_HIP_TRY(awpu::launch_band_filter(a, s));
+    return AWPU_OK;
+}
+
+// launch() on frames of the caller's or the ring's (kFull, kRing), or on windows uploaded with the band's history in front of them
+// (kCompact: rows of taps - 1 + compact_hist floats), through the band where the handle has one: the pre-pass into d_band in
+// `layout`, then the launch() a band-less handle makes for the same call -- the same layout and batch, so the same kernel.  The
+// handle's event bracket spans both
+int band_sweep(awpu_hip *h, const float *in, long long in_frame, long long in_row, int in_lo, int batch, float *d_power, hipStream_t s, int layout) {
+    if (h->band.empty()) return launch(h, in, batch, d_power, s, layout);
+    const size_t S = (size_t) h->cfg.n_streams;
+    const size_t need = layout == kRing ? S * 2048 : S * (size_t) (layout == kCompact ? h->compact_hist : h->cfg.hist) * batch;
+    if (!h->d_band.holds(need)) {  // (what no pre-pass writes and a sweep's wide loads may touch reads as zeros)
+        if (const int rc = h->d_band.grow(need); rc != AWPU_OK) return rc;
+        AWPU_HIP_TRY(hipMemsetAsync(h->d_band, 0, need * sizeof(float), s));
+    }
+    const bool timed = h->timing;
+    if (timed) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
+    int rc = band_cut(h, in, in_frame, in_row, in_lo, batch, h->d_band, layout, s);
+    if (rc != AWPU_OK) return rc;
+    h->timing = false;
+    rc = launch(h, h->d_band, batch, d_power, s, layout);
+    h->timing = timed;
+    if (rc == AWPU_OK && timed) AWPU_HIP_TRY(hipEventRecord(h->ev_end, s));
+    return rc;
 }
 
 }  // namespace awpu::host
@@ -808,13 +864,37 @@ int awpu_hip_set_fir_table(awpu_hip_t *h, const float *coeffs) {
     return AWPU_OK;
 }
 
+// ---- the band (include/awpu_hip_band.h; the rule itself: band_host.cpp, the pre-pass: band_kernels.hip) ----------------------------
+
+int awpu_hip_set_band(awpu_hip_t *h, const float *c, int32_t taps) {
+    AWPU_CTX(h);
+    if (!h) return invalid("null handle");
+    if (is_group(h)) return fail(AWPU_ERR_STATE, "a device group takes no band");
+    if (h->in_flight) return fail(AWPU_ERR_STATE, "an awpu_hip_process_async call is in flight on this handle: awpu_hip_wait first");
+    if (!c && taps == 0) {
+        h->band.clear();
+        return AWPU_OK;
+    }
+    if (const char *why = awpu::band_refusal(c, taps)) return invalid(why);
+    if (h->have_table && h->have_mics) {  // the window's start, as prepare() will find it
+        int lo = h->cfg.hist;
+        for (int p = 0; p < h->cfg.pixel_count; p++)
+            for (int id : h->index) lo = std::min(lo, h->off[(size_t) p * h->cfg.lut_stride + id]);
+        if (h->cfg.window_end > h->cfg.window_begin) lo = std::min(lo, h->cfg.window_begin);
+        if (taps - 1 > lo) return fail(AWPU_ERR_RANGE, kBandHistory);
+    }
+    h->band.assign(c, c + taps);
+    return AWPU_OK;
+}
+
 int awpu_hip_process(awpu_hip_t *h, const float *frames, int32_t batch, float *power) {
     AWPU_CTX(h);
     if (!h) return invalid("null handle");
     if (!frames || !power) return invalid("null argument");
     if (h->in_flight) return fail(AWPU_ERR_STATE, "an awpu_hip_process_async call is in flight on this handle: awpu_hip_wait first");
     if (is_group(h)) return group_process(h, frames, batch, power);
-    if (batch == 1 && h->member.ranges.empty()) return live_host_call(h, frames, power);
+    // (a band-limited frame takes the batches' path: the live path's upload is the bare window, and its completion flag the sweep's)
+    if (batch == 1 && h->member.ranges.empty() && h->band.empty()) return live_host_call(h, frames, power);
     int rc = enqueue_host_process(h, frames, batch);
     if (rc != AWPU_OK) return rc;
     rc = enqueue_power_to_host(h, batch, power, (size_t) h->cfg.pixel_count);
@@ -856,7 +936,7 @@ int awpu_hip_process_device(awpu_hip_t *h, const float *d_frames, int32_t batch,
     if (rc != AWPU_OK) return rc;
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
     TimingOff untimed(h);  // asynchronous path: the caller times its own stream
-    return launch(h, d_frames, batch, d_power, s);
+    return band_sweep(h, d_frames, (long long) h->cfg.n_streams * h->cfg.hist, h->cfg.hist, h->wstart, batch, d_power, s, kFull);
 }
 
 int awpu_hip_process_device_sums(awpu_hip_t *h, const float *d_frames, int32_t batch, float *d_power, float *d_sums, void *stream) {
@@ -871,7 +951,7 @@ int awpu_hip_process_device_sums(awpu_hip_t *h, const float *d_frames, int32_t b
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
     TimingOff untimed(h);
     h->sums_out = d_sums;
-    const int lrc = launch(h, d_frames, batch, d_power, s);
+    const int lrc = band_sweep(h, d_frames, (long long) h->cfg.n_streams * h->cfg.hist, h->cfg.hist, h->wstart, batch, d_power, s, kFull);
     h->sums_out = nullptr;
     return lrc;
 }
@@ -926,6 +1006,7 @@ int awpu_hip_live_block(awpu_hip_t *h, const void *datagrams, int32_t stride_byt
     AWPU_CTX(h);
     if (h && is_group(h)) return invalid("the display step needs the whole grid on one device");
     if (h && h->in_flight) return fail(AWPU_ERR_STATE, "an awpu_hip_process_async call is in flight on this handle: awpu_hip_wait first");
+    if (h && !h->band.empty()) return fail(AWPU_ERR_STATE, "the live block's captured step takes no band: clear it (awpu_hip_set_band) or ingest and sweep the ring");
     int rc = check_ready(h, 1);
     if (rc != AWPU_OK) return rc;
     const int n = h->cfg.n_pixels;
@@ -1028,7 +1109,7 @@ int awpu_hip_process_ring(awpu_hip_t *h, float *power) {
     const size_t need_power = (size_t) h->cfg.pixel_count;
     rc = ensure_power(h, need_power);
     if (rc != AWPU_OK) return rc;
-    rc = launch(h, h->d_ring + h->ring_pos, 1, h->d_power, h->stream, kRing);
+    rc = band_sweep(h, h->d_ring + h->ring_pos, 0, 2048, h->wstart, 1, h->d_power, h->stream, kRing);
     if (rc != AWPU_OK) return rc;
     AWPU_HIP_TRY(hipMemcpyAsync(power, h->d_power, need_power * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     AWPU_HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1110,6 +1191,7 @@ namespace {
 int packed_plan(awpu_hip *h, int batch, awpu::FastPlan *plan) {
     if (!h) return invalid("null handle");
     if (is_group(h)) return fail(AWPU_ERR_STATE, "packed frames: a device group exchanges its frames itself");
+    if (!h->band.empty()) return fail(AWPU_ERR_STATE, "packed frames are raw samples: a handle with a band neither packs nor sweeps them");
     const int rc = check_ready(h, batch);
     return rc != AWPU_OK ? rc : packed_shape(h, batch, plan);
 }

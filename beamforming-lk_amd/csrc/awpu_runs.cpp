@@ -95,7 +95,8 @@ void parallel_copy(void *dst, const void *src, size_t bytes) {
 //   3. up waits ev_blk_cut[b] (i >= 2, swept runs) and ev_listened[b] (i >= 2, listened runs): piece i-2 has read blk_hist.d[b]
 //   4. the history is formed on up, ev_blk_hist[b] behind it; sw waits it, and li where that is another stream
 //   5. the cut on sw, then ev_blk_cut[b]; ev_begin at piece 0; the sweep with the handle's own event bracket off; what the
-//      consumer shows of the powers; ev_blk_swept[b]
+//      consumer shows of the powers; ev_blk_swept[b].  On a handle with a band (awpu_hip_band.h) the cut is the band's pre-pass,
+//      which cuts and filters in one (band_cut), and ev_begin stands in front of it; nothing else of a run sees the band
 //   6. the listen kernels on li, ev_listened[b] behind them
 //   7. piece i-1's results into pinned memory on up, behind ev_blk_swept / ev_listened, ev_blk_out / ev_listen_out behind them
 //      (so piece i-2's way back is queued on up before piece i's history is formed: listen_out.d[b] is free when 6 writes it)
@@ -256,10 +257,12 @@ int run_pieces(awpu_hip *h, const BlockRun &src, hipStream_t user, Consumer &c) 
                 if (li != sw) AWPU_HIP_TRY(hipStreamWaitEvent(li, h->ev_blk_hist[b], 0));
             }
             if (c.sweep && !p.tail) {
+                const bool banded = !h->band.empty();  // the cut is then the band's pre-pass, and inside the timed span
+                if (time_it && i == 0 && banded) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, sw));
                 brc = c.cut(p, sw);
                 if (brc != AWPU_OK) return brc;
                 if (host) AWPU_HIP_TRY(hipEventRecord(h->ev_blk_cut[b], sw));
-                if (time_it && i == 0) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, sw));
+                if (time_it && i == 0 && !banded) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, sw));
                 float *d_pow = host ? h->d_power + (size_t) b * piece_max * P : (c.power ? c.power + (size_t) p.first * P : h->d_power);
                 h->timing = false;
                 brc = launch(h, h->d_blk_frames, p.n, d_pow, sw, compact ? kCompact : kFull);
@@ -412,6 +415,7 @@ struct BlockPieces final : Consumer {
         return AWPU_OK;
     }
     int cut(const Piece &p, hipStream_t s) override {
+        if (!h->band.empty()) return band_cut(h, hist_of(h, p.b), awpu::kSamples, pitch, h->wstart, p.n, h->d_blk_frames, h->compact_hist > 0 ? kCompact : kFull, s);
         AWPU_HIP_TRY(awpu::launch_cut_windows(hist_of(h, p.b), pitch, h->cfg.n_streams, p.n, lo, width, h->d_blk_frames, s));
         return AWPU_OK;
     }
@@ -603,6 +607,7 @@ struct WatchPieces final : Consumer {
         return AWPU_OK;
     }
     int cut(const Piece &p, hipStream_t s) override {
+        if (!h->band.empty()) return band_cut(h, hist_of(h, p.b), awpu::kSamples * m, pitch, h->wstart, p.n, h->d_blk_frames, h->compact_hist > 0 ? kCompact : kFull, s);
         AWPU_HIP_TRY(awpu::launch_watch_cut(hist_of(h, p.b), pitch, S, p.n, awpu::kSamples * m, lo, width, h->d_blk_frames, s));
         return AWPU_OK;
     }

@@ -72,6 +72,13 @@ int MIMOWorkerHip::setDelayLUT(const int32_t *off, const float *frac) {
     return last_status;
 }
 
+int MIMOWorkerHip::setBand(const float *c, int taps) {
+    if (!engine) return AWPU_ERR_INVALID;
+    std::lock_guard<std::mutex> guard(lock);
+    last_status = awpu_hip_set_band(engine, c, taps);
+    return last_status;
+}
+
 // mimo.cpp:97-151.  The snapshot loop is the reference's (every stream, so that antenna.index can
 // address any of them); the pixel x mic x sample sweep and the epilogue run on the GPU.
 void MIMOWorkerHip::update() {

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "awpu_hip.h"
+#include "awpu_hip_band.h"
 
 namespace awpu_host {
 
@@ -78,6 +79,11 @@ public:
     // heatmap is within 1e-5 of the reference's on every pixel, deep nulls included (INTEGRATION.md "Which math mode").
     // Call between blocks (it takes the worker lock).  Returns the C-ABI status.
     int setDelayLUT(const int32_t *off, const float *frac);
+
+    // The band every heatmap from now on is limited to (include/awpu_hip_band.h; the reference plans it: USE_BANDPASS,
+    // src/dsp/particle.h:17): c [taps] as awpu_hip_band_design gives them; nullptr with 0 taps = the whole signal again.
+    // Call between blocks (it takes the worker lock).  Returns the C-ABI status.
+    int setBand(const float *c, int taps);
 
     int status() const { return last_status; }                 // last C-ABI status (0 = OK)
     const std::vector<float> &power() const { return powerdB; }  // mimo.h:91

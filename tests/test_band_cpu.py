@@ -1,0 +1,266 @@
+"""Band-limited heatmaps (include/awpu_hip_band.h) on a box without a GPU: the three entry points are exported beside the other
+headers' and built from the listed files; awpu_hip_band_design equals a numpy restatement of the header's formula and its
+filters pass their band and stop the rest; awpu_hip_band_filter equals a restatement in rational arithmetic that rounds once
+per step, bit for bit; bad arguments are refused with nothing written; the host code runs clean under the address and
+undefined-behaviour sanitizers as a program of its own; the kernel compiles for gfx950 without spills or scratch."""
+import ctypes as C
+import re
+import subprocess
+from fractions import Fraction
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+REPO = Path(__file__).resolve().parent.parent
+CSRC = REPO / "beamforming-lk_amd" / "csrc"
+NAMES = ["awpu_hip_band_filter", "awpu_hip_band_design", "awpu_hip_set_band"]
+FS = 48828.125
+DESIGNS = [(6375.0, 9000.0, 63), (0.0, 4000.0, 31), (12000.0, FS / 2, 33), (1950.0, 3541.0, 127)]
+
+
+def test_band_symbols_exported_and_listed(pkg):
+    lib = pkg.binding.load()
+    B = pkg.binding
+    text = re.sub(r"/\*.*?\*/", "", (REPO / "include" / "awpu_hip_band.h").read_text(), flags=re.S)
+    assert sorted(set(re.findall(r"\b(awpu_hip_\w+)\s*\(", text))) == sorted(NAMES)
+    assert '#include "awpu_hip.h"' in text
+    assert int(re.search(r"#define AWPU_BAND_MAX_TAPS (\d+)", text).group(1)) == 128 == B.BAND_MAX_TAPS
+    assert sorted(B.BAND_SYMBOLS) == sorted(NAMES)
+    for name in NAMES:
+        assert hasattr(lib, name)
+    for other in (B.EXPORTED_SYMBOLS, B.TRACK_SYMBOLS, B.BLOCK_SYMBOLS, B.LISTEN_SYMBOLS, B.WATCH_SYMBOLS, B.FIND_SYMBOLS):
+        assert not set(B.BAND_SYMBOLS) & set(other)
+    assert lib.awpu_hip_abi_version() == 4
+    assert "awpu_hip_band" not in (REPO / "include" / "awpu_hip.h").read_text() and "set_band" not in (REPO / "include" / "awpu_hip.h").read_text()
+    H, S = pkg._build.HEADERS, pkg._build.SOURCES
+    assert REPO / "include" / "awpu_hip_band.h" in H and CSRC / "band_kernels.h" in H and CSRC / "band_rule.h" in H
+    assert CSRC / "band_kernels.hip" in S and CSRC / "band_host.cpp" in S
+    for build_file in ("CMakeLists.txt", "Makefile"):
+        for name in ("awpu_hip_band.h", "band_kernels.hip", "band_kernels.h", "band_rule.h", "band_host.cpp"):
+            assert name in (REPO / build_file).read_text(), (build_file, name)
+
+
+def test_band_header_compiles_as_c(tmp_path):
+    src = tmp_path / "one.c"
+    src.write_text('#include "awpu_hip_band.h"\n'
+                   "int main(void) { float c[AWPU_BAND_MAX_TAPS]; float x[4], y[4];\n"
+                   "  return awpu_hip_band_design(1.0, 2.0, 8.0, 3, c) + awpu_hip_band_filter(x, 1, 4, 4, c, 3, y) + awpu_hip_set_band(0, c, 3); }\n")
+    subprocess.run(["cc", "-std=c99", "-Wall", "-Werror", "-fsyntax-only", f"-I{REPO / 'include'}", str(src)], check=True, capture_output=True)
+
+
+def test_host_file_compiles_with_a_plain_host_compiler(tmp_path):
+    subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", f"-I{REPO / 'include'}", f"-I{CSRC}", "-c", str(CSRC / "band_host.cpp"),
+                    "-o", str(tmp_path / "band_host.o")], check=True, capture_output=True)
+
+
+# ------------------------------------------------------------------------------------------------ the design
+
+def design_np(lo, hi, taps, fs=FS):
+    """The header's formula, in numpy doubles."""
+    k = np.arange(taps, dtype=np.float64)
+    M = (taps - 1) / 2
+    f1, f2 = lo / fs, hi / fs
+    ideal = 2 * f2 * np.sinc(2 * f2 * (k - M)) - 2 * f1 * np.sinc(2 * f1 * (k - M))  # np.sinc(u) = sin(pi u) / (pi u), 1 at 0
+    h = ideal * (0.54 - 0.46 * np.cos(2 * np.pi * k / (taps - 1)))
+    g = abs(np.sum(h * np.exp(-2j * np.pi * k * (f1 + f2) / 2)))
+    return h / g
+
+
+def response(c, f, fs=FS):
+    k = np.arange(len(c), dtype=np.float64)
+    return np.abs(np.exp(-2j * np.pi * np.outer(np.atleast_1d(f), k) / fs) @ np.asarray(c, np.float64))
+
+
+@pytest.mark.parametrize("lo,hi,taps", DESIGNS)
+def test_design_equals_the_formula(pkg, lo, hi, taps):
+    c = pkg.binding.band_design(lo, hi, taps)
+    want = design_np(lo, hi, taps)
+    assert c.dtype == np.float32 and c.shape == (taps,)
+    err = float(np.abs(c - want).max())
+    print(f"design {lo:g}-{hi:g} Hz, {taps} taps: max |c - c_np| = {err:.3g} of max |c_np| = {np.abs(want).max():.3g}")
+    assert err <= 1e-6 * np.abs(want).max()
+
+
+@pytest.mark.parametrize("lo,hi,taps", DESIGNS)
+def test_design_passes_its_band_and_stops_the_rest(pkg, lo, hi, taps):
+    f = np.linspace(0.0, FS / 2, 2000)
+    outside = (f < lo - 3.3 * FS / taps) | (f > hi + 3.3 * FS / taps)
+    assert outside.sum() > 100
+    np_stop = float(response(design_np(lo, hi, taps), f[outside]).max())
+    assert np_stop <= 0.0027, np_stop  # the formula itself, on this grid
+    c = pkg.binding.band_design(lo, hi, taps)
+    centre, stop = float(response(c, (lo + hi) / 2)[0]), float(response(c, f[outside]).max())
+    print(f"design {lo:g}-{hi:g} Hz, {taps} taps: |H(centre)| = {centre:.9f}, stop band max {stop:.3g} (formula {np_stop:.3g})")
+    assert abs(centre - 1.0) <= 1e-6
+    assert stop < 0.005
+
+
+def test_design_default_rate_and_taps(pkg):
+    B = pkg.binding
+    assert np.array_equal(B.band_design(6375, 9000), B.band_design(6375, 9000, 63, 48828.125))
+
+
+def test_the_tools_band_option(pkg):
+    """--band LO:HI[:TAPS] of tools/pcap_video.py and tools/pcap_sources.py: 63 taps unless given."""
+    B = pkg.binding
+    assert np.array_equal(B.band_from_text("6375:9000"), B.band_design(6375, 9000, 63))
+    assert np.array_equal(B.band_from_text("0:4000.5:31"), B.band_design(0, 4000.5, 31))
+    for bad in ("6375", "1:2:3:4", "a:b"):
+        with pytest.raises(ValueError):
+            B.band_from_text(bad)
+    for tool in ("pcap_video.py", "pcap_sources.py"):
+        text = (REPO / "tools" / tool).read_text()
+        assert '"--band"' in text and "band_from_text(a.band)" in text
+
+
+def test_design_refusals_write_nothing(pkg):
+    lib = pkg.binding.load()
+    c = np.full(130, -7.0, np.float32)
+    p = c.ctypes.data_as(C.POINTER(C.c_float))
+    cases = [(1000.0, 2000.0, FS, 64), (1000.0, 2000.0, FS, 1), (1000.0, 2000.0, FS, 129), (2000.0, 2000.0, FS, 63), (3000.0, 2000.0, FS, 63),
+             (1000.0, FS / 2 + 1.0, FS, 63), (-1.0, 2000.0, FS, 63), (float("nan"), 2000.0, FS, 63), (1000.0, 2000.0, 0.0, 63)]
+    for lo, hi, fs, taps in cases:
+        assert lib.awpu_hip_band_design(lo, hi, fs, taps, p) == pkg.binding.ERR_INVALID, (lo, hi, fs, taps)
+    assert lib.awpu_hip_band_design(1000.0, 2000.0, FS, 63, None) == pkg.binding.ERR_INVALID
+    assert np.all(c == -7.0)
+    with pytest.raises(pkg.AwpuError) as e:
+        pkg.binding.band_design(1000, 2000, 64)
+    assert e.value.status == pkg.binding.ERR_INVALID
+
+
+# ------------------------------------------------------------------------------------------------ the filter
+
+def round_f32(s: Fraction) -> np.float32:
+    """A non-zero rational to the nearest float32, ties to even, subnormals included; a result that rounds to zero keeps its sign."""
+    a = abs(s)
+    e = a.numerator.bit_length() - a.denominator.bit_length()  # 2^(e-1) <= a < 2^(e+1)
+    if Fraction(2) ** e > a:
+        e -= 1
+    q = Fraction(2) ** (max(e, -126) - 23)
+    n = a / q
+    whole = n.numerator // n.denominator
+    rest = n - whole
+    if rest > Fraction(1, 2) or (rest == Fraction(1, 2) and whole & 1):
+        whole += 1
+    v = np.float32(float(whole * q))  # (exact: whole * q is a float32)
+    return -v if s < 0 else v
+
+
+def fmaf_exact(c: np.float32, x: np.float32, acc: np.float32) -> np.float32:
+    """fmaf(c, x, acc): the exact value of c * x + acc rounded once."""
+    p, a = Fraction(float(c)) * Fraction(float(x)), Fraction(float(acc))
+    if p == 0 and a == 0:  # a sum of zeros: -0 only when both are
+        p_negative = bool(np.signbit(c)) != bool(np.signbit(x))
+        return np.float32(-0.0) if p_negative and np.signbit(acc) else np.float32(0.0)
+    s = p + a
+    return np.float32(0.0) if s == 0 else round_f32(s)
+
+
+def filter_exact(x, c):
+    y = np.empty_like(x)
+    for r in range(x.shape[0]):
+        for t in range(x.shape[1]):
+            acc = np.float32(0.0)
+            for k in range(len(c)):
+                acc = fmaf_exact(c[k], x[r, t - k] if t >= k else np.float32(0.0), acc)
+            y[r, t] = acc
+    return y
+
+
+def test_rounding_helper_is_float32_rounding():
+    rng = np.random.default_rng(3)
+    for v in np.concatenate([rng.standard_normal(200) * 10.0 ** rng.integers(-44, 30, 200), [2.0 ** -149, 2.0 ** -150, 3 * 2.0 ** -150, 1 + 2.0 ** -24, 1 + 3 * 2.0 ** -24]]):
+        with np.errstate(under="ignore"):
+            want = np.float32(v)  # numpy rounds a double to nearest even
+        if v != 0.0:
+            got = round_f32(Fraction(float(v)))
+            assert got.view(np.uint32) == want.view(np.uint32), v
+
+
+def filter_input():
+    rng = np.random.default_rng(11)
+    x = (rng.standard_normal((8, 40)) * 10.0 ** rng.integers(-3, 2, (8, 40))).astype(np.float32)
+    x[0, 5], x[1, 0], x[2, 7], x[3, 39] = np.float32(1e-41), np.float32(0.0), np.float32(-0.0), np.float32(-3e-42)  # subnormals, 0, -0
+    x[4, :6] = [0.0, -0.0, 0.0, -0.0, 1e-45, -1e-45]
+    return x
+
+
+@pytest.mark.parametrize("taps", [1, 2, 7, 128])
+def test_filter_equals_the_rule_in_exact_arithmetic(pkg, taps):
+    x = filter_input()
+    assert np.any((x != 0) & (np.abs(x) < 1.2e-38)) and np.any(np.signbit(x) & (x == 0)) and np.any(x > 0) and np.any(x < 0)
+    rng = np.random.default_rng(100 + taps)
+    c = (rng.standard_normal(taps) * 10.0 ** rng.integers(-2, 1, taps)).astype(np.float32)
+    if taps >= 2:
+        c[1] = -abs(c[1])
+    assert taps == 1 or (np.any(c > 0) and np.any(c < 0))
+    got = pkg.binding.band_filter(x, c)
+    want = filter_exact(x, c)
+    assert got.dtype == np.float32 and got.shape == x.shape
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+
+
+def test_filter_identity_rows_and_pitch(pkg):
+    lib, B = pkg.binding.load(), pkg.binding
+    x = filter_input()
+    # one tap of 1.0 returns the input bit for bit, subnormals included -- but for -0, which the rule's first step adds to its +0
+    # accumulator: fmaf(1, -0, +0) = +0
+    same = B.band_filter(x, np.ones(1, np.float32))
+    assert np.array_equal(same.view(np.uint32), np.where(x == 0, np.float32(0.0), x).view(np.uint32))
+    assert np.array_equal(same.view(np.uint32)[x != 0], x.view(np.uint32)[x != 0]) and np.any(np.abs(x[x != 0]) < 1e-38)
+    # rows do not leak into each other: a pitch wider than the rows, what lies between them neither read nor written
+    c = np.random.default_rng(5).standard_normal(7).astype(np.float32)
+    wide = np.full((8, 50), np.nan, np.float32)
+    wide[:, :40] = x
+    out = np.full((8, 50), -7.0, np.float32)
+    fp = C.POINTER(C.c_float)
+    assert lib.awpu_hip_band_filter(wide.ctypes.data_as(fp), 8, 50, 40, c.ctypes.data_as(fp), 7, out.ctypes.data_as(fp)) == B.OK
+    assert np.array_equal(out[:, :40].view(np.uint32), B.band_filter(x, c).view(np.uint32)) and np.all(out[:, 40:] == -7.0)
+    # any leading shape: frames [batch, streams, n] are rows
+    assert np.array_equal(B.band_filter(x.reshape(2, 4, 40), c), B.band_filter(x, c).reshape(2, 4, 40))
+
+
+def test_filter_refusals_write_nothing(pkg):
+    lib, B = pkg.binding.load(), pkg.binding
+    fp = C.POINTER(C.c_float)
+    x, y = np.ones((2, 8), np.float32), np.full((2, 8), -7.0, np.float32)
+    good, bad = np.ones(129, np.float32), np.array([1.0, np.inf, 1.0], np.float32)
+    nan = np.array([np.nan], np.float32)
+    X, Y, G = x.ctypes.data_as(fp), y.ctypes.data_as(fp), good.ctypes.data_as(fp)
+    for args in ((X, 2, 8, 8, G, 0, Y), (X, 2, 8, 8, G, 129, Y), (X, 2, 8, 8, bad.ctypes.data_as(fp), 3, Y), (X, 2, 8, 8, nan.ctypes.data_as(fp), 1, Y),
+                 (None, 2, 8, 8, G, 3, Y), (X, 2, 8, 8, None, 3, Y), (X, 2, 8, 8, G, 3, None), (X, 2, 8, 8, G, 3, X), (X, 0, 8, 8, G, 3, Y),
+                 (X, 2, 8, 0, G, 3, Y), (X, 2, 7, 8, G, 3, Y)):
+        assert lib.awpu_hip_band_filter(*args) == B.ERR_INVALID
+    assert np.all(y == -7.0) and np.all(x == 1.0)
+
+
+# ------------------------------------------------------------------------------------------------ sanitizers, and the kernel's build
+
+def test_host_code_runs_clean_under_sanitizers(tmp_path):
+    """tests/host/band_rule_check.cpp with band_host.cpp: a program of its own under ASan and UBSan, largest and smallest sizes."""
+    exe = tmp_path / "band_rule_check"
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    f"-I{REPO / 'include'}", f"-I{CSRC}", str(REPO / "tests" / "host" / "band_rule_check.cpp"), str(CSRC / "band_host.cpp"),
+                    "-o", str(exe)], check=True, capture_output=True)
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "band rule: ok" in out.stdout, out.stdout + out.stderr
+
+
+def test_band_kernel_compiles_without_spills(tmp_path, pkg):
+    out = tmp_path / "band_kernels.s"
+    subprocess.run([pkg._build.hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", f"-I{REPO / 'include'}", f"-I{CSRC}",
+                    "-S", "--cuda-device-only", "-o", str(out), str(CSRC / "band_kernels.hip")], check=True, capture_output=True)
+    text = out.read_text()
+    meta = {}
+    for block in text.split("  - .agpr_count:")[1:]:
+        name = re.search(r"\.name:\s+(\S+)", block).group(1)
+        meta[name] = {k: int(re.search(rf"\.{k}:\s+(\d+)", block).group(1))
+                      for k in ("vgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size", "group_segment_fixed_size")}
+    assert len(meta) == 1 and "band_filter_kernel" in next(iter(meta)), sorted(meta)
+    m = next(iter(meta.values()))
+    print("band_filter_kernel:", m)
+    assert m["vgpr_spill_count"] == 0 and m["sgpr_spill_count"] == 0 and m["private_segment_fixed_size"] == 0, m
+    assert m["group_segment_fixed_size"] == 4 * 640 * 4  # four waves' rows: a chunk of 512 outputs and 127 samples of history each
+    # the rule's steps are fused multiply-adds (single or packed, one rounding a lane) and nothing else: no separate multiply or add of floats anywhere in the kernel
+    assert re.search(r"\bv_(pk_)?fmac?_f32", text) and not re.search(r"\bv_(pk_)?(mul|add|sub|mac)_f32", text)

@@ -5,6 +5,9 @@ tools/pcap_heatmaps.py's reader (counter gaps reported, not repaired).
 
   tools/pcap_sources.py recording.pcap --port 21844 --cols 100 --every 1 --max-sources 4 --min-ratio 0.25 --out sources.csv
 
+--band LO:HI[:TAPS] (Hz; 63 taps unless given) limits the heatmaps to a band, e.g. --band 6375:9000: the sources are those of the band
+(Engine.set_band with binding.band_design's coefficients, include/awpu_hip_band.h).
+
 Every block is ingested; every --every'th is swept and searched.  --chunk blocks go to the engine per call, each call continuing
 with the `next_first` of the one before, so a long capture streams through bounded memory.
 
@@ -70,6 +73,7 @@ def main(argv=None) -> int:
     ap.add_argument("--chunk", type=int, default=512, help="blocks per engine call")
     ap.add_argument("--max-batch", type=int, default=128, help="frames per sweep launch")
     ap.add_argument("--out", default="sources.csv")
+    ap.add_argument("--band", default=None, metavar="LO:HI[:TAPS]", help="limit the heatmaps to LO .. HI Hz (an FIR band of TAPS taps, 63 unless given)")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     if a.every < 1 or a.chunk < 1:
@@ -102,6 +106,8 @@ def main(argv=None) -> int:
         writer.writerow(HEADER)
         eng.set_delay_table(off, frac)
         eng.set_active_mics(None)
+        if a.band:
+            eng.set_band(pkg.binding.band_from_text(a.band))
         for b in range(0, n_blocks, a.chunk):
             nb = min(a.chunk, n_blocks - b)
             res = eng.find_blocks(wire[b * block_bytes: (b + nb) * block_bytes], a.cols, a.cols, first=first, every=a.every,

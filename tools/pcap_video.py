@@ -6,6 +6,9 @@ reader (counter gaps reported, not repaired).
 
   tools/pcap_video.py recording.pcap --port 21844 --cols 100 --every 3 --size 1024 --out heatmap
 
+--band LO:HI[:TAPS] (Hz; 63 taps unless given) limits the heatmaps to a band, e.g. --band 6375:9000: the video shows the band
+(Engine.set_band with binding.band_design's coefficients, include/awpu_hip_band.h).
+
 Every block is ingested; every --every'th is swept and shown.  The default 3 gives 48828 / (256 * 3) = 63.6 frames per second, the
 nearest to the 60 the reference opens its writer with.  --chunk blocks go to the engine per call, each call continuing with the
 `next_first` of the one before, so a long capture streams through bounded memory.
@@ -173,6 +176,7 @@ def main(argv=None) -> int:
     ap.add_argument("--max-batch", type=int, default=32, help="frames per sweep launch (and per display piece held in memory)")
     ap.add_argument("--raw", action="store_true", help="headerless BGR24 frames into OUT.bgr instead of AVI parts")
     ap.add_argument("--out", default="heatmap", help="output prefix")
+    ap.add_argument("--band", default=None, metavar="LO:HI[:TAPS]", help="limit the heatmaps to LO .. HI Hz (an FIR band of TAPS taps, 63 unless given)")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     if a.every < 1 or a.chunk < 1 or a.size < a.cols:
@@ -208,6 +212,8 @@ def main(argv=None) -> int:
     with pkg.Engine(n_pixels=a.cols * a.cols, n_streams=n, max_batch=a.max_batch, grid_columns=a.cols, device=a.device) as eng:
         eng.set_delay_table(off, frac)
         eng.set_active_mics(None)
+        if a.band:
+            eng.set_band(pkg.binding.band_from_text(a.band))
         for b in range(0, n_blocks, a.chunk):
             nb = min(a.chunk, n_blocks - b)
             res = eng.watch_blocks(wire[b * block_bytes: (b + nb) * block_bytes], a.cols, a.cols, first=first, every=a.every,
