@@ -11,7 +11,7 @@ PKG := beamforming-lk_amd
 CSRC := $(PKG)/csrc
 LIB := $(PKG)/libawpu_hip.so
 KERNEL_SRC := $(CSRC)/das_kernels.hip $(CSRC)/das_fast.hip $(CSRC)/track_kernels.hip $(CSRC)/block_kernels.hip $(CSRC)/watch_kernels.hip $(CSRC)/find_kernels.hip $(CSRC)/band_kernels.hip $(CSRC)/awpu_hip.cpp \
-              $(CSRC)/awpu_group.cpp $(CSRC)/awpu_sweep.cpp $(CSRC)/awpu_runs.cpp $(CSRC)/geometry_host.cpp $(CSRC)/find_host.cpp $(CSRC)/band_host.cpp
+              $(CSRC)/awpu_group.cpp $(CSRC)/awpu_sweep.cpp $(CSRC)/awpu_runs.cpp $(CSRC)/geometry_host.cpp $(CSRC)/find_host.cpp $(CSRC)/band_host.cpp $(CSRC)/awpu_focus.cpp
 HOST_SRC := $(PKG)/host/mimo_worker_hip.cpp $(PKG)/host/aw_processing_unit_hip.cpp $(PKG)/host/pipeline_hip.cpp \
             $(PKG)/host/aw_processing_unit.cpp $(PKG)/host/spherical_gradient_hip.cpp
 # OPENCV_CFLAGS: where <opencv2/core.hpp> lives; defaults to the tests' few-line stand-in for cv::Mat (no OpenCV here)

@@ -19,10 +19,16 @@ from .binding import (  # noqa: F401
     band_filter,
     build_delay_table,
     build_delay_table_device,
+    build_focus_table,
+    build_focus_table_device,
     create_antenna,
     create_tiled_antenna,
     find_peaks,
+    focus_delays,
+    focus_steer_table,
     heatmap_u8,
+    range_candidates,
+    range_pick,
     resize_linear_u8,
     steer_table,
     steering_delays,
@@ -30,6 +36,7 @@ from .binding import (  # noqa: F401
 
 __all__ = [
     "Engine", "AwpuError", "MATH_F32_EXACT", "MATH_F32_FAST", "MATH_BF16_ACC", "build_delay_table", "build_delay_table_device",
-    "create_antenna", "create_tiled_antenna", "steering_delays", "heatmap_u8", "find_peaks", "band_design", "band_filter", "resize_linear_u8", "steer_table", "binding",
+    "create_antenna", "create_tiled_antenna", "steering_delays", "heatmap_u8", "find_peaks", "band_design", "band_filter", "resize_linear_u8", "steer_table", "focus_delays", "focus_steer_table",
+    "build_focus_table", "build_focus_table_device", "range_pick", "range_candidates", "binding",
     "synthetic", "_build",
 ]

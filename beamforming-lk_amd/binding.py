@@ -260,6 +260,40 @@ _BAND_SIGNATURES = {
 }
 BAND_SYMBOLS = tuple(_BAND_SIGNATURES)
 
+RANGE_MAX_CANDIDATES = 64
+
+
+class Range(C.Structure):
+    """awpu_range_t (include/awpu_hip_focus.h)."""
+    _fields_ = [
+        ("index", C.c_int32),
+        ("power", C.c_float),
+        ("distance", C.c_double),
+    ]
+
+
+# focus and range: the entry points of include/awpu_hip_focus.h
+_f64p = C.POINTER(C.c_double)
+_LOCATE_TAIL = [*_WATCH_TAIL, *_FIND_TAIL]  # n_blocks, w, f, sources, count
+_FOCUS_SIGNATURES = {
+    "awpu_hip_focus_delays": (C.c_int, [_f32p, C.c_int32, C.c_double, C.c_double, C.c_double, _f32p]),
+    "awpu_hip_focus_steer_table": (C.c_int, [_f32p, C.c_int32, _f64p, _f64p, _f64p, C.c_int32, _i32p, _f32p]),
+    "awpu_hip_build_focus_table": (C.c_int, [_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_double, C.c_int32, C.c_int32, _i32p, _f32p]),
+    "awpu_hip_build_focus_table_device": (C.c_int, [C.c_int32, _f32p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_double, C.c_int32,
+                                                    C.c_int32, _i32p, _f32p]),
+    "awpu_hip_range": (C.c_int, [C.c_void_p, C.c_void_p, _f64p, _f64p, C.c_int32, _f64p, C.c_int32, _f32p, C.c_void_p]),
+    "awpu_hip_range_pick": (C.c_int, [_f32p, C.c_int32, _f64p, C.c_int32, C.c_void_p]),
+    "awpu_hip_locate_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, *_LOCATE_TAIL, _f32p, _f64p, C.c_int32, C.c_void_p, _f32p]),
+    "awpu_hip_locate_samples": (C.c_int, [C.c_void_p, _f32p, C.c_int64, *_LOCATE_TAIL, _f32p, _f64p, C.c_int32, C.c_void_p, _f32p]),
+    "awpu_hip_locate_samples_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, *_LOCATE_TAIL, C.c_void_p, _f64p, C.c_int32, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]),
+}
+FOCUS_SYMBOLS = tuple(_FOCUS_SIGNATURES)
+
+# numpy view of awpu_range_t: what range_pick, Engine.range and Engine.locate_* return (unused entries: index -1)
+RANGE_DTYPE = np.dtype([("index", "<i4"), ("power", "<f4"), ("distance", "<f8")], align=True)
+assert RANGE_DTYPE.itemsize == C.sizeof(Range) == 16
+
 # numpy view of awpu_source_t: what find_peaks and Engine.find_* return, max_sources records per frame
 SOURCE_DTYPE = np.dtype([("pixel", "<i4"), ("power", "<f4"), ("row", "<f8"), ("col", "<f8"), ("theta", "<f8"), ("phi", "<f8")], align=True)
 assert SOURCE_DTYPE.itemsize == C.sizeof(Source) == 40
@@ -292,7 +326,8 @@ def load(build: bool = True) -> C.CDLL:
         raise RuntimeError(f"{path} is missing and there is no CPU fallback")
     lib = C.CDLL(str(path))
     for name, (res, args) in list(_SIGNATURES.items()) + list(_TRACK_SIGNATURES.items()) + list(_BLOCK_SIGNATURES.items()) + \
-            list(_LISTEN_SIGNATURES.items()) + list(_WATCH_SIGNATURES.items()) + list(_FIND_SIGNATURES.items()) + list(_BAND_SIGNATURES.items()):
+            list(_LISTEN_SIGNATURES.items()) + list(_WATCH_SIGNATURES.items()) + list(_FIND_SIGNATURES.items()) + list(_BAND_SIGNATURES.items()) + \
+            list(_FOCUS_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -387,6 +422,77 @@ def steer_table(xyz: np.ndarray, theta, phi):
     _check(load().awpu_hip_steer_table(_f32(xyz), n, theta.ctypes.data_as(dp), phi.ctypes.data_as(dp), theta.size,
                                        _i32(off), _f32(frac)), "steer_table")
     return off, frac
+
+
+def focus_delays(xyz: np.ndarray, theta: float, phi: float, distance: float) -> np.ndarray:
+    """The delays [n] (samples, minimum 0) that focus the elements xyz on the point `distance` metres along (theta, phi): the rule
+    of include/awpu_hip_focus.h (awpu_hip_focus_delays); distance inf = steering_delays, bit for bit."""
+    xyz = np.ascontiguousarray(xyz, np.float32)
+    tau = np.empty(xyz.shape[1], np.float32)
+    _check(load().awpu_hip_focus_delays(_f32(xyz), xyz.shape[1], theta, phi, distance, _f32(tau)), "awpu_hip_focus_delays")
+    return tau
+
+
+def focus_steer_table(xyz: np.ndarray, theta, phi, distance):
+    """steer_table with a focus distance per direction (scalars broadcast) -> (off, frac) [n_dir, n] (awpu_hip_focus_steer_table)."""
+    xyz = np.ascontiguousarray(xyz, np.float32)
+    theta, phi, distance = np.broadcast_arrays(np.atleast_1d(np.asarray(theta, np.float64)), np.atleast_1d(np.asarray(phi, np.float64)),
+                                               np.atleast_1d(np.asarray(distance, np.float64)))
+    if theta.ndim != 1:
+        raise ValueError("theta, phi and distance must be 1-D and alike")
+    theta, phi, distance = (np.ascontiguousarray(a) for a in (theta, phi, distance))
+    n = xyz.shape[1]
+    off = np.empty((theta.size, n), np.int32)
+    frac = np.empty((theta.size, n), np.float32)
+    _check(load().awpu_hip_focus_steer_table(_f32(xyz), n, theta.ctypes.data_as(_f64p), phi.ctypes.data_as(_f64p),
+                                             distance.ctypes.data_as(_f64p), theta.size, _i32(off), _f32(frac)), "awpu_hip_focus_steer_table")
+    return off, frac
+
+
+def build_focus_table(xyz: np.ndarray, rows: int, columns: int, distance: float, fov_deg: float = 180.0, row_begin: int = 0,
+                      row_count: Optional[int] = None):
+    """build_delay_table with every pixel focused `distance` metres along its direction -> (off, frac) [row_count*columns, n]
+    (awpu_hip_build_focus_table); Engine.set_delay_table takes it as it is."""
+    xyz = np.ascontiguousarray(xyz, np.float32)
+    n = xyz.shape[1]
+    row_count = rows - row_begin if row_count is None else row_count
+    off = np.empty((max(row_count, 0) * columns, n), np.int32)
+    frac = np.empty((max(row_count, 0) * columns, n), np.float32)
+    _check(load().awpu_hip_build_focus_table(_f32(xyz), n, rows, columns, fov_deg, distance, row_begin, row_count, _i32(off), _f32(frac)),
+           "awpu_hip_build_focus_table")
+    return off, frac
+
+
+def build_focus_table_device(xyz: np.ndarray, rows: int, columns: int, distance: float, fov_deg: float = 180.0, row_begin: int = 0,
+                             row_count: Optional[int] = None, device: int = 0):
+    """The same table, its rows x columns x n part computed on HIP device `device` (bit-identical to build_focus_table)."""
+    xyz = np.ascontiguousarray(xyz, np.float32)
+    n = xyz.shape[1]
+    row_count = rows - row_begin if row_count is None else row_count
+    off = np.empty((max(row_count, 0) * columns, n), np.int32)
+    frac = np.empty((max(row_count, 0) * columns, n), np.float32)
+    _check(load().awpu_hip_build_focus_table_device(device, _f32(xyz), n, rows, columns, fov_deg, distance, row_begin, row_count,
+                                                    _i32(off), _f32(frac)), "awpu_hip_build_focus_table_device")
+    return off, frac
+
+
+def range_candidates(lo: float, hi: float, n: int) -> np.ndarray:
+    """n candidate distances from lo to hi metres (hi may be inf), uniform in 1 / d: where range_pick's refinement is exact for a
+    peak that is a parabola in 1 / d."""
+    with np.errstate(divide="ignore"):
+        return 1.0 / np.linspace(1.0 / lo, 1.0 / hi, int(n))
+
+
+def range_pick(power: np.ndarray, distance) -> np.ndarray:
+    """Which candidate distance wins for every row of power [n_src, n_dist], refined between the candidates -> RANGE_DTYPE records
+    [n_src] (awpu_hip_range_pick: the rule of include/awpu_hip_focus.h as executable C)."""
+    power = np.ascontiguousarray(power, np.float32)
+    distance = np.ascontiguousarray(np.atleast_1d(distance), np.float64)
+    power = power.reshape(-1, max(distance.size, 1))
+    best = np.zeros(len(power), RANGE_DTYPE)
+    _check(load().awpu_hip_range_pick(_f32(power), len(power), distance.ctypes.data_as(_f64p), distance.size,
+                                      best.ctypes.data_as(C.c_void_p)), "awpu_hip_range_pick")
+    return best
 
 
 def resize_linear_u8(pix: np.ndarray, out_rows: int, out_cols: int) -> np.ndarray:
@@ -490,6 +596,21 @@ class FindResult:
 
     def __len__(self):
         return len(self.count)
+
+
+class LocateResult(FindResult):
+    """What Engine.locate_* hand back: a FindResult plus .ranges [n_frames, max_sources] RANGE_DTYPE records (unused entries:
+    index -1) and .range_power [n_frames, max_sources, n_dist] or None; .distance is the records' field."""
+
+    def __init__(self, sources, count, power, next_first, ranges, range_power):
+        super().__init__(sources, count, power, next_first)
+        self.ranges = ranges
+        self.range_power = range_power
+
+    def __getattr__(self, name):
+        if name == "distance":
+            return self.ranges["distance"]
+        return super().__getattr__(name)
 
 
 def find_peaks(power: np.ndarray, rows: int, cols: int, radius: int = 2, max_sources: int = 4, min_power: float = 0.0,
@@ -831,6 +952,78 @@ class Engine:
         _check(self._lib.awpu_hip_find_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, C.byref(w), C.byref(f),
                                                       C.c_void_p(d_sources_ptr), C.c_void_p(d_count_ptr), C.c_void_p(d_power_ptr),
                                                       C.c_void_p(stream)), "awpu_hip_find_samples_device")
+        return watch_count(n_blocks, first, every)[1]
+
+    def range(self, theta, phi, distance, d_frame_ptr: int = 0):
+        """The beam power of every direction (theta[k], phi[k]) focused at every candidate distance[j] (metres, inf = a plane wave),
+        in one launch on raw samples; d_frame_ptr 0 = the ingest ring's snapshot -> (power [n_src, n_dist], best [n_src]
+        RANGE_DTYPE records = range_pick(power)) (awpu_hip_range)."""
+        theta = np.ascontiguousarray(np.atleast_1d(theta), np.float64)
+        phi = np.ascontiguousarray(np.atleast_1d(phi), np.float64)
+        distance = np.ascontiguousarray(np.atleast_1d(distance), np.float64)
+        if theta.shape != phi.shape or theta.ndim != 1 or distance.ndim != 1:
+            raise ValueError("theta and phi must be 1-D and alike, distance 1-D")
+        power = np.empty((theta.size, distance.size), np.float32)
+        best = np.zeros(theta.size, RANGE_DTYPE)
+        _check(self._lib.awpu_hip_range(self._h, C.c_void_p(d_frame_ptr), theta.ctypes.data_as(_f64p), phi.ctypes.data_as(_f64p), theta.size,
+                                        distance.ctypes.data_as(_f64p), distance.size, _f32(power) if power.size else None,
+                                        best.ctypes.data_as(C.c_void_p)), "awpu_hip_range")
+        return power, best
+
+    def _locate(self, call, where, n_blocks, rows, cols, first, every, distance, find, want_power, want_range_power) -> LocateResult:
+        n_frames, next_first = watch_count(n_blocks, first, every)
+        w = Watch(first, every, rows, cols, 0, 0, 0, None)
+        f = Find(rows, cols, find.get("radius", 2), find.get("max_sources", 4), find.get("min_power", 0.0), find.get("min_ratio", 0.0),
+                 find.get("fov_deg", 180.0))
+        distance = np.ascontiguousarray(np.atleast_1d(distance), np.float64)
+        ms = max(f.max_sources, 0)
+        sources = np.empty((n_frames, ms), SOURCE_DTYPE)
+        count = np.empty(n_frames, np.int32)
+        power = np.empty((n_frames, self.pixel_count), np.float32) if want_power else None
+        ranges = np.empty((n_frames, ms), RANGE_DTYPE)
+        range_power = np.empty((n_frames, ms, distance.size), np.float32) if want_range_power else None
+        ptr = lambda a: C.c_void_p(a.ctypes.data or 16)
+        _check(call(n_blocks, C.byref(w), C.byref(f), ptr(sources), ptr(count), C.cast(ptr(power), _f32p) if want_power else None,
+                    distance.ctypes.data_as(_f64p), distance.size, ptr(ranges), C.cast(ptr(range_power), _f32p) if want_range_power else None),
+               where)
+        return LocateResult(sources, count, power, next_first, ranges, range_power)
+
+    def locate_blocks(self, wire, rows: int, cols: int, distance, first: int = 0, every: int = 1, stride: int = DATAGRAM_BYTES,
+                      want_power: bool = False, want_range_power: bool = False, **find) -> LocateResult:
+        """find_blocks, and for every source it reports the beam power at that direction focused at every candidate `distance`
+        (metres, inf = a plane wave), swept on the block's raw snapshot while it is on the device, and the distance at which it
+        peaks (awpu_hip_locate_blocks).  Needs set_antenna.  -> LocateResult."""
+        buf = np.frombuffer(wire, dtype=np.uint8)
+        if stride < DATAGRAM_BYTES or buf.size % (256 * stride) or buf.size == 0:
+            raise ValueError(f"wire must be a whole number of blocks of 256 datagrams {stride} bytes apart")
+        return self._locate(lambda *rest: self._lib.awpu_hip_locate_blocks(self._h, buf.ctypes.data_as(C.c_void_p), stride, *rest),
+                            "awpu_hip_locate_blocks", buf.size // (256 * stride), rows, cols, first, every, distance, find, want_power,
+                            want_range_power)
+
+    def locate_samples(self, samples: np.ndarray, rows: int, cols: int, distance, first: int = 0, every: int = 1, want_power: bool = False,
+                       want_range_power: bool = False, **find) -> LocateResult:
+        """The same from unpacked samples [n_streams, N] (N a multiple of 256, oldest first) (awpu_hip_locate_samples)."""
+        samples = np.ascontiguousarray(samples, np.float32)
+        if samples.ndim != 2 or samples.shape[0] != self.cfg.n_streams or samples.shape[1] % 256 or samples.shape[1] == 0:
+            raise ValueError(f"samples must be [{self.cfg.n_streams}, N] with N a positive multiple of 256")
+        return self._locate(lambda *rest: self._lib.awpu_hip_locate_samples(self._h, _f32(samples), samples.shape[1], *rest),
+                            "awpu_hip_locate_samples", samples.shape[1] // 256, rows, cols, first, every, distance, find, want_power,
+                            want_range_power)
+
+    def locate_samples_device(self, d_samples_ptr: int, pitch: int, n_blocks: int, rows: int, cols: int, distance, d_sources_ptr: int,
+                              d_count_ptr: int, d_ranges_ptr: int, first: int = 0, every: int = 1, d_power_ptr: int = 0,
+                              d_range_power_ptr: int = 0, stream: int = 0, **find) -> int:
+        """The same on device pointers (as find_samples_device takes them; ranges [n_frames, max_sources] records of 16 bytes,
+        range_power [n_frames, max_sources, n_dist] floats or 0) on `stream`; asynchronous.  -> next_first
+        (awpu_hip_locate_samples_device)."""
+        w = Watch(first, every, rows, cols, 0, 0, 0, None)
+        f = Find(rows, cols, find.get("radius", 2), find.get("max_sources", 4), find.get("min_power", 0.0), find.get("min_ratio", 0.0),
+                 find.get("fov_deg", 180.0))
+        distance = np.ascontiguousarray(np.atleast_1d(distance), np.float64)
+        _check(self._lib.awpu_hip_locate_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, C.byref(w), C.byref(f),
+                                                        C.c_void_p(d_sources_ptr), C.c_void_p(d_count_ptr), C.c_void_p(d_power_ptr),
+                                                        distance.ctypes.data_as(_f64p), distance.size, C.c_void_p(d_ranges_ptr),
+                                                        C.c_void_p(d_range_power_ptr), C.c_void_p(stream)), "awpu_hip_locate_samples_device")
         return watch_count(n_blocks, first, every)[1]
 
     def set_fir_table(self, coeffs: np.ndarray) -> None:

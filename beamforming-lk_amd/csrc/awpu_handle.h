@@ -374,7 +374,8 @@ struct awpu_hip {
     // recorded behind the display kernels, ev_blk_out[b] behind the images' way back.
     awpu::host::BufferPair watch;
     // finding in such runs (awpu_hip_find.h), host forms: piece i's counts, then its sources, in find_out.d[i & 1] and back through
-    // pinned find_out.h[i & 1], behind the same two events
+    // pinned find_out.h[i & 1], behind the same two events; locating (awpu_hip_focus.h) adds its ranges and the candidates' powers
+    // behind them (the device form: only the powers nobody asked for, in find_out.d[0])
     awpu::host::BufferPair find_out;
 
     // the band (awpu_hip_band.h): its coefficients (empty = none; they travel to the pre-pass as kernel arguments), and the
@@ -465,6 +466,7 @@ size_t align16(size_t n);
 int check_particles(const awpu_particle_t *p, int32_t n, double theta_limit, double reference);
 int check_antenna(const awpu_hip *h);
 int ensure_track_index(awpu_hip *h);
+int check_candidates(const double *distance, int32_t n_dist);  // awpu_focus.cpp: the candidate distances of awpu_hip_focus.h
 int ensure_taps(awpu_hip *h, int rows, int cols, int out_rows, int out_cols, hipStream_t s);
 int band_cut(awpu_hip *h, const float *in, long long in_frame, long long in_row, int in_lo, int batch, float *out, int layout, hipStream_t s);
 int band_sweep(awpu_hip *h, const float *in, long long in_frame, long long in_row, int in_lo, int batch, float *d_power, hipStream_t s, int layout);

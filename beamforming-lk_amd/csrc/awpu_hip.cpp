@@ -18,6 +18,7 @@
 #include "band_kernels.h"
 #include "band_rule.h"
 #include "das_kernels.h"
+#include "focus_rule.h"
 #include "watch_kernels.h"
 
 using namespace awpu::host;
@@ -1251,8 +1252,14 @@ int awpu_hip_group_peer_status(awpu_hip_t *h, int32_t *status, int32_t n) {
     return 1;
 }
 
-int awpu_hip_build_delay_table_device(int32_t device, const float *xyz, int32_t n, int32_t rows, int32_t columns, float fov_deg,
-                                      int32_t row_begin, int32_t row_count, int32_t *off, float *frac) {
+}  // extern "C"
+
+namespace {
+
+// awpu_hip_build_delay_table_device (distance = +INFINITY) and awpu_hip_build_focus_table_device: the per-pixel rotations on the
+// host, the P x n part on `device`
+int build_table_on_device(int32_t device, const float *xyz, int32_t n, int32_t rows, int32_t columns, float fov_deg, double distance,
+                          int32_t row_begin, int32_t row_count, int32_t *off, float *frac) {
     if (!xyz || !off || !frac || n <= 0 || rows <= 0 || columns <= 0) return invalid("null or non-positive argument");
     if (row_begin < 0 || row_count < 0 || row_begin + row_count > rows) return invalid("rows outside the grid");
     if (row_count == 0) return AWPU_OK;
@@ -1279,12 +1286,30 @@ int awpu_hip_build_delay_table_device(int32_t device, const float *xyz, int32_t 
     // one launch per 32 768 pixels (the grid's x dimension is not the limit; this bounds a launch's run time)
     for (size_t p0 = 0; p0 < P; p0 += 32768) {
         const int np = (int) std::min<size_t>(32768, P - p0);
-        AWPU_HIP_TRY(awpu::launch_delay_table(d_xyz, n, d_rot + p0 * 12, np, awpu::samples_per_metre(), d_off + p0 * n, d_frac + p0 * n,
-                                              nullptr));
+        if (awpu::focus_is_plane_wave(distance))
+            AWPU_HIP_TRY(awpu::launch_delay_table(d_xyz, n, d_rot + p0 * 12, np, awpu::samples_per_metre(), d_off + p0 * n, d_frac + p0 * n,
+                                                  nullptr));
+        else
+            AWPU_HIP_TRY(awpu::launch_focus_table(d_xyz, n, d_rot + p0 * 12, np, distance, d_off + p0 * n, d_frac + p0 * n, nullptr));
     }
     AWPU_HIP_TRY(hipMemcpy(off, d_off, P * n * sizeof(int32_t), hipMemcpyDeviceToHost));
     AWPU_HIP_TRY(hipMemcpy(frac, d_frac, P * n * sizeof(float), hipMemcpyDeviceToHost));
     return AWPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int awpu_hip_build_delay_table_device(int32_t device, const float *xyz, int32_t n, int32_t rows, int32_t columns, float fov_deg,
+                                      int32_t row_begin, int32_t row_count, int32_t *off, float *frac) {
+    return build_table_on_device(device, xyz, n, rows, columns, fov_deg, (double) INFINITY, row_begin, row_count, off, frac);
+}
+
+int awpu_hip_build_focus_table_device(int32_t device, const float *xyz, int32_t n, int32_t rows, int32_t columns, float fov_deg,
+                                      double distance, int32_t row_begin, int32_t row_count, int32_t *off, float *frac) {
+    if (!awpu::focus_distance_ok(distance)) return invalid("distance must be > 0 (+INFINITY: a plane wave)");
+    return build_table_on_device(device, xyz, n, rows, columns, fov_deg, distance, row_begin, row_count, off, frac);
 }
 
 int awpu_hip_get_stats(awpu_hip_t *h, awpu_hip_stats *stats) {

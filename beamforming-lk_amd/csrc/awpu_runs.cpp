@@ -1,9 +1,10 @@
 // awpu_runs.cpp -- runs of consecutive blocks of a recording through one pipeline of pieces: a heatmap of every block
 // (include/awpu_hip_blocks.h), the beam audio of every block (awpu_hip_listen.h), display images of every Nth block
-// (awpu_hip_watch.h), the sources in every Nth block (awpu_hip_find.h).  The handle and what is called here out of awpu_hip.cpp and awpu_sweep.cpp: awpu_handle.h.
+// (awpu_hip_watch.h), the sources in every Nth block (awpu_hip_find.h) and their distances (awpu_hip_focus.h).  The handle and what is called here out of awpu_hip.cpp and awpu_sweep.cpp: awpu_handle.h.
 #include "awpu_handle.h"
 #include "awpu_hip_blocks.h"
 #include "awpu_hip_find.h"
+#include "awpu_hip_focus.h"
 #include "awpu_hip_listen.h"
 #include "awpu_hip_watch.h"
 
@@ -494,11 +495,22 @@ int listen_run(awpu_hip *h, const BlockRun &src, int n_blocks, awpu_particle_t *
 // otherwise.  A find run (awpu_hip_find.h) is a watch run whose display step is the peak pass: launch_find_peaks on the piece's
 // powers, its counts and sources brought back (host forms) where the images would be.
 
+// what a locate call (awpu_hip_focus.h) adds to a find run: behind a piece's peak pass, launch_range over every entry of its
+// sources on the snapshots of the piece's history -- raw samples, whatever the sweep was given --, picked on the device.  ranges
+// and range_power are host memory in the host forms, device memory in the device form
+struct LocateRun {
+    const double *distance = nullptr;  // [n_dist], host
+    int32_t n_dist = 0;
+    awpu_range_t *ranges = nullptr;    // [n_frames][max_sources]
+    float *range_power = nullptr;      // [n_frames][max_sources][n_dist], or null
+};
+
 // what a find call adds to a watch run; sources and count are host memory in the host forms, device memory in the device form
 struct FindRun {
     awpu_find_t f{};
     awpu_source_t *sources = nullptr;  // [n_frames][max_sources]
     int32_t *count = nullptr;          // [n_frames]
+    const LocateRun *locate = nullptr;
 };
 
 struct WatchRun {
@@ -540,16 +552,18 @@ struct WatchPieces final : Consumer {
     const WatchRun &wr;
     const awpu_watch_t &w;
     const FindRun *const fr;
+    const LocateRun *const lr;
     const bool host, want_small;
     const int S, m;
     const size_t P, big_bytes;
     int lo = 0, width = 0;
     size_t small_off = 0, big_off = 0;  // in a watch buffer: the peaks, then the compact images, then the large ones
     size_t sources_off = 0;             // in a find buffer: the counts, then the sources
+    size_t ranges_off = 0, rpower_off = 0;  // ... then (locate runs) the ranges and the candidates' powers; the device form keeps only the powers there, at 0
     const float *snapshot = nullptr;    // blocks -4 .. -1 of the call
 
     WatchPieces(awpu_hip *h_, const BlockRun &src_, int n_blocks_, const WatchRun &wr_)
-        : h(h_), src(src_), wr(wr_), w(wr_.w), fr(wr_.find), host(!src_.device), want_small(wr_.image || wr_.big), S(h_->cfg.n_streams), m(std::min(wr_.w.every, 4)),
+        : h(h_), src(src_), wr(wr_), w(wr_.w), fr(wr_.find), lr(wr_.find ? wr_.find->locate : nullptr), host(!src_.device), want_small(wr_.image || wr_.big), S(h_->cfg.n_streams), m(std::min(wr_.w.every, 4)),
           P((size_t) h_->cfg.pixel_count), big_bytes((size_t) wr_.w.out_rows * wr_.w.out_cols * (wr_.w.d_colormap ? 3 : 1)) {
         n_items = wr.n_frames;
         n_blocks = n_blocks_;
@@ -569,7 +583,7 @@ struct WatchPieces final : Consumer {
     int check() override {
         if (h->cfg.pixel_count != h->cfg.n_pixels) return invalid("the display step needs the whole grid on this handle");
         if ((long long) w.rows * w.cols != h->cfg.n_pixels) return invalid("rows x cols must be the grid");
-        return AWPU_OK;
+        return lr ? check_antenna(h) : (int) AWPU_OK;
     }
     int ensure(int piece_max, int lo_, int width_, hipStream_t sw) override {
         lo = lo_, width = width_;
@@ -582,6 +596,13 @@ struct WatchPieces final : Consumer {
         if (rc == AWPU_OK && want_small) rc = h->watch.ensure(big_off + (host && wr.big ? (size_t) piece_max * big_bytes : 0), host);
         if (rc == AWPU_OK && wr.big) rc = ensure_taps(h, w.rows, w.cols, w.out_rows, w.out_cols, sw);
         sources_off = align16(sizeof(int32_t) * piece_max);
+        if (lr) {
+            ranges_off = sources_off + align16(source_bytes(piece_max));
+            rpower_off = host ? ranges_off + (size_t) piece_max * fr->f.max_sources * sizeof(awpu_range_t) : 0;
+            if (rc == AWPU_OK) rc = ensure_track_index(h);
+            if (rc == AWPU_OK && (host || !lr->range_power)) rc = h->find_out.ensure(rpower_off + rpower_bytes(piece_max), host);
+            return rc;
+        }
         if (rc == AWPU_OK && fr && host) rc = h->find_out.ensure(sources_off + source_bytes(piece_max), true);
         return rc;
     }
@@ -612,12 +633,41 @@ struct WatchPieces final : Consumer {
         return AWPU_OK;
     }
     size_t source_bytes(int nf) const { return (size_t) nf * fr->f.max_sources * sizeof(awpu_source_t); }
+    size_t rpower_bytes(int nf) const { return (size_t) nf * fr->f.max_sources * lr->n_dist * sizeof(float); }
+    // the range pass of a piece: shown frame j's snapshot starts at sample 256 * m * j of the history, as the cut reads it
+    int range(const Piece &p, const awpu_source_t *d_sources, hipStream_t s) {
+        const int ms = fr->f.max_sources;
+        unsigned char *out = h->find_out.d[host ? p.b : 0];
+        awpu::RangeArgs a{};
+        a.frame_step = (long long) awpu::kSamples * m;
+        a.per_frame = ms;
+        a.pitch = pitch;
+        a.xyz = h->d_xyz;
+        a.n = (int) (h->antenna.size() / 3);
+        a.index = h->d_track_index;
+        a.usable = h->usable();
+        a.n_dist = lr->n_dist;
+        for (int j = 0; j < lr->n_dist; j++) a.distance[j] = lr->distance[j];
+        float *d_rpower = host || !lr->range_power ? reinterpret_cast<float *>(out + rpower_off) : lr->range_power + (size_t) p.first * ms * lr->n_dist;
+        awpu_range_t *d_ranges = host ? reinterpret_cast<awpu_range_t *>(out + ranges_off) : lr->ranges + (size_t) p.first * ms;
+        for (int j0 = 0; j0 < p.n; j0 += 1024) {  // (a launch's grid: at most 65535 sources)
+            const int nf = std::min(1024, p.n - j0);
+            a.frame = hist_of(h, p.b) + (size_t) j0 * a.frame_step;
+            a.sources = d_sources + (size_t) j0 * ms;
+            a.n_src = nf * ms;
+            a.power = d_rpower + (size_t) j0 * ms * lr->n_dist;
+            a.best = d_ranges + (size_t) j0 * ms;
+            AWPU_HIP_TRY(awpu::launch_range(a, s));
+        }
+        return AWPU_OK;
+    }
     int show(const Piece &p, float *d_pow, hipStream_t s) override {
         if (fr) {
             unsigned char *out = h->find_out.d[p.b];
-            AWPU_HIP_TRY(awpu::launch_find_peaks(d_pow, p.n, fr->f,
-                                                 host ? reinterpret_cast<awpu_source_t *>(out + sources_off) : fr->sources + (size_t) p.first * fr->f.max_sources,
-                                                 host ? reinterpret_cast<int32_t *>(out) : fr->count + p.first, s));
+            awpu_source_t *d_sources = host ? reinterpret_cast<awpu_source_t *>(out + sources_off) : fr->sources + (size_t) p.first * fr->f.max_sources;
+            AWPU_HIP_TRY(awpu::launch_find_peaks(d_pow, p.n, fr->f, d_sources, host ? reinterpret_cast<int32_t *>(out) : fr->count + p.first, s));
+            if (lr)
+                if (const int rc = range(p, d_sources, s)) return rc;
         }
         if (!want_small) return AWPU_OK;
         uint8_t *scratch = h->watch.d[host ? p.b : 0];
@@ -629,7 +679,9 @@ struct WatchPieces final : Consumer {
         return AWPU_OK;
     }
     int fetch_shown(const Piece &p, hipStream_t s) override {
-        if (fr) AWPU_HIP_TRY(hipMemcpyAsync(h->find_out.h[p.b], h->find_out.d[p.b], sources_off + source_bytes(p.n), hipMemcpyDeviceToHost, s));
+        if (fr)
+            AWPU_HIP_TRY(hipMemcpyAsync(h->find_out.h[p.b], h->find_out.d[p.b], lr ? rpower_off + rpower_bytes(p.n) : sources_off + source_bytes(p.n),
+                                        hipMemcpyDeviceToHost, s));
         uint8_t *to = h->watch.h[p.b], *from = h->watch.d[p.b];
         if (wr.image) AWPU_HIP_TRY(hipMemcpyAsync(to + small_off, from + small_off, (size_t) p.n * P, hipMemcpyDeviceToHost, s));
         if (wr.big) AWPU_HIP_TRY(hipMemcpyAsync(to + big_off, from + big_off, (size_t) p.n * big_bytes, hipMemcpyDeviceToHost, s));
@@ -639,6 +691,11 @@ struct WatchPieces final : Consumer {
         if (fr) {
             std::memcpy(fr->count + p.first, h->find_out.h[p.b], sizeof(int32_t) * p.n);
             std::memcpy(fr->sources + (size_t) p.first * fr->f.max_sources, h->find_out.h[p.b] + sources_off, source_bytes(p.n));
+        }
+        if (lr) {
+            const size_t entries = (size_t) p.first * fr->f.max_sources;
+            std::memcpy(lr->ranges + entries, h->find_out.h[p.b] + ranges_off, (size_t) p.n * fr->f.max_sources * sizeof(awpu_range_t));
+            if (lr->range_power) std::memcpy(lr->range_power + entries * lr->n_dist, h->find_out.h[p.b] + rpower_off, rpower_bytes(p.n));
         }
         if (wr.image) std::memcpy(wr.image + (size_t) p.first * P, h->watch.h[p.b] + small_off, (size_t) p.n * P);
         if (wr.big) parallel_copy(wr.big + (size_t) p.first * big_bytes, h->watch.h[p.b] + big_off, (size_t) p.n * big_bytes);
@@ -673,13 +730,16 @@ int watch_run(awpu_hip *h, const BlockRun &src, int n_blocks, const awpu_watch_t
 
 // the checks of a find call that read no handle; then the watch run that finds: of `w` only first, every, rows and cols count
 int find_run(awpu_hip *h, const BlockRun &src, int n_blocks, const awpu_watch_t *w, const awpu_find_t *f, awpu_source_t *sources, int32_t *count,
-             float *power, hipStream_t user) {
+             float *power, hipStream_t user, const LocateRun *locate = nullptr) {
     if (!w || !sources || !count) return invalid("null argument");
+    if (locate && !locate->ranges) return invalid("null argument");
+    if (locate)
+        if (const int rc = check_candidates(locate->distance, locate->n_dist)) return rc;
     if (const char *why = awpu::find_refusal(f)) return invalid(why);
     if (f->rows != w->rows || f->cols != w->cols) return invalid("the find grid must be the watch grid");
     awpu_watch_t shown{};
     shown.first = w->first, shown.every = w->every, shown.rows = w->rows, shown.cols = w->cols;
-    const FindRun find{*f, sources, count};
+    const FindRun find{*f, sources, count, locate};
     return watch_run(h, src, n_blocks, &shown, nullptr, nullptr, power, user, &find);
 }
 
@@ -800,6 +860,34 @@ int awpu_hip_find_samples_device(awpu_hip_t *h, const float *d_samples, int64_t 
     BlockRun src;
     if (int rc = sample_source(h, d_samples, pitch, n_blocks, true, &src)) return rc;
     return find_run(h, src, n_blocks, w, f, d_sources, d_count, d_power, static_cast<hipStream_t>(stream));
+}
+
+int awpu_hip_locate_blocks(awpu_hip_t *h, const void *datagrams, int32_t stride_bytes, int32_t n_blocks, const awpu_watch_t *w,
+                           const awpu_find_t *f, awpu_source_t *sources, int32_t *count, float *power, const double *distance,
+                           int32_t n_dist, awpu_range_t *ranges, float *range_power) {
+    BlockRun src;
+    if (int rc = wire_source(h, datagrams, stride_bytes, n_blocks, &src)) return rc;
+    const LocateRun locate{distance, n_dist, ranges, range_power};
+    return find_run(h, src, n_blocks, w, f, sources, count, power, nullptr, &locate);
+}
+
+int awpu_hip_locate_samples(awpu_hip_t *h, const float *samples, int64_t pitch, int32_t n_blocks, const awpu_watch_t *w,
+                            const awpu_find_t *f, awpu_source_t *sources, int32_t *count, float *power, const double *distance,
+                            int32_t n_dist, awpu_range_t *ranges, float *range_power) {
+    BlockRun src;
+    if (int rc = sample_source(h, samples, pitch, n_blocks, false, &src)) return rc;
+    const LocateRun locate{distance, n_dist, ranges, range_power};
+    return find_run(h, src, n_blocks, w, f, sources, count, power, nullptr, &locate);
+}
+
+int awpu_hip_locate_samples_device(awpu_hip_t *h, const float *d_samples, int64_t pitch, int32_t n_blocks, const awpu_watch_t *w,
+                                   const awpu_find_t *f, awpu_source_t *d_sources, int32_t *d_count, float *d_power,
+                                   const double *distance, int32_t n_dist, awpu_range_t *d_ranges, float *d_range_power,
+                                   void *stream) {
+    BlockRun src;
+    if (int rc = sample_source(h, d_samples, pitch, n_blocks, true, &src)) return rc;
+    const LocateRun locate{distance, n_dist, d_ranges, d_range_power};
+    return find_run(h, src, n_blocks, w, f, d_sources, d_count, d_power, static_cast<hipStream_t>(stream), &locate);
 }
 
 }  // extern "C"

@@ -405,6 +405,28 @@ struct ListenArgs {
 // steps == 0 (`fixed`), on the same stream
 hipError_t launch_listen(const ListenArgs &a, bool tracking, bool fixed, hipStream_t stream);
 
+// awpu_hip_range (include/awpu_hip_focus.h; range_kernel in track_kernels.hip): n_src sources x n_dist candidate distances in one
+// launch.  Source k reads the snapshot at frame + (k / per_frame) * frame_step (stream id s at + s * pitch) and steers to
+// theta[k] / phi[k], or, with `sources` (awpu_source_t [n_src], device memory), to that entry's theta / phi -- an entry with
+// pixel < 0 gets zeros.  `best`: awpu_range_t [n_src] picked on the device behind the sweep (awpu_hip_range_pick's bits), or null.
+struct RangeArgs {
+    const float *frame;
+    long long frame_step;
+    int32_t per_frame;
+    int32_t pitch;
+    const float *xyz;      // [3][n] element positions by stream id
+    int32_t n;
+    const int32_t *index;  // [usable] active stream ids, the reference's order
+    int32_t usable;
+    const double *theta, *phi;
+    const void *sources;
+    int32_t n_src, n_dist;
+    float *power;          // [n_src][n_dist]
+    void *best;
+    double distance[64];   // [n_dist] candidates: > 0, +INFINITY = a plane wave (AWPU_RANGE_MAX_CANDIDATES)
+};
+hipError_t launch_range(const RangeArgs &a, hipStream_t stream);
+
 // geometry_host.cpp: the per-pixel half of computeDelayLUT for the device builder (rot [row_count * columns][12])
 void pixel_rotations(int rows, int columns, float fov_deg, int row_begin, int row_count, float *rot);
 float samples_per_metre();  // (float) (48828 / 340), antenna.cpp:90
@@ -412,6 +434,11 @@ float samples_per_metre();  // (float) (48828 / 340), antenna.cpp:90
 // computeDelayLUT's P x n part on the device (das_kernels.hip, delay_table_kernel): d_rot [n_pixels][12] = Rz(phi)
 // row-major + row z of Ry(-theta), d_xyz [3][n]; d_off / d_frac [n_pixels][n]
 hipError_t launch_delay_table(const float *d_xyz, int n, const float *d_rot, int n_pixels, float scale, int32_t *d_off, float *d_frac,
+                              hipStream_t stream);
+
+// awpu_hip_build_focus_table's P x n part (das_kernels.hip, focus_table_kernel; include/awpu_hip_focus.h): the same d_rot, every
+// pixel focused `distance` metres (finite, > 0) along its direction; d_off / d_frac [n_pixels][n], the host builder's bits
+hipError_t launch_focus_table(const float *d_xyz, int n, const float *d_rot, int n_pixels, double distance, int32_t *d_off, float *d_frac,
                               hipStream_t stream);
 
 // mean square of `hist` samples of each of `n` rows (pitch floats apart), summed in sample order

@@ -10,6 +10,8 @@
 // Written for wave64 / 160 KiB LDS / gfx950 only.  No MFMA: this is a gather-and-reduce.
 #include "das_kernels.h"
 
+#include "focus_rule.h"
+
 namespace awpu {
 
 // ---------------------------------------------------------------------------------------
@@ -358,6 +360,41 @@ __global__ void delay_table_kernel(const float *xyz, int n, const float *rot, fl
 hipError_t launch_delay_table(const float *d_xyz, int n, const float *d_rot, int n_pixels, float scale, int32_t *d_off, float *d_frac,
                               hipStream_t stream) {
     hipLaunchKernelGGL(delay_table_kernel, dim3(n_pixels), dim3(256), 0, stream, d_xyz, n, d_rot, scale, d_off, d_frac);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// awpu_hip_build_focus_table on the device (include/awpu_hip_focus.h): delay_table_kernel's division of the work -- the
+// per-pixel rotations from the host, one workgroup per pixel -- with the focus rule's P x n part: the focus point from the
+// pixel's twelve floats, every element's path in double (focus_rule.h: the host builder's expressions, contraction off, the
+// correctly rounded square root), the longest path over the elements (a maximum: exact in any order), the delay and the
+// split of mimo.cpp:46-54.  Bit-identical to the host builder by construction.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void focus_table_kernel(const float *xyz, int n, const float *rot, double distance, int32_t *off, float *frac) {
+#pragma clang fp contract(off)
+    __shared__ double far_of_wave[4];
+    const int p = blockIdx.x;
+    double w[3], F[3];
+    focus_direction(rot + (size_t) p * 12, w);
+    focus_point(w, distance, F);
+    double far = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) far = fmax(far, focus_path(F, xyz[i], xyz[n + i], xyz[2 * n + i]));
+    for (int d = 32; d >= 1; d >>= 1) far = fmax(far, __shfl_xor(far, d));
+    if ((threadIdx.x & 63) == 0) far_of_wave[threadIdx.x >> 6] = far;
+    __syncthreads();
+    far = fmax(fmax(far_of_wave[0], far_of_wave[1]), fmax(far_of_wave[2], far_of_wave[3]));
+    for (int i = threadIdx.x; i < n; i += 256) {  // (recomputed: the same operations give the same bits)
+        const float tau = focus_delay(far, focus_path(F, xyz[i], xyz[n + i], xyz[2 * n + i]));
+        const float whole = truncf(tau);  // modf((double) tau, &whole): exact in float as well
+        frac[(size_t) p * n + i] = tau - whole;
+        off[(size_t) p * n + i] = kSamples - (int) whole;
+    }
+}
+
+hipError_t launch_focus_table(const float *d_xyz, int n, const float *d_rot, int n_pixels, double distance, int32_t *d_off, float *d_frac,
+                              hipStream_t stream) {
+    if (!focus_distance_ok(distance) || focus_is_plane_wave(distance)) return hipErrorInvalidValue;  // (a plane wave is launch_delay_table's)
+    hipLaunchKernelGGL(focus_table_kernel, dim3(n_pixels), dim3(256), 0, stream, d_xyz, n, d_rot, distance, d_off, d_frac);
     return hipGetLastError();
 }
 

@@ -16,6 +16,8 @@
 #include <vector>
 
 #include "awpu_hip.h"
+#include "awpu_hip_focus.h"
+#include "focus_rule.h"
 
 namespace {
 
@@ -54,6 +56,40 @@ void steering_delays(const float *xyz, int n, double theta, double phi, float *t
         lowest = std::fmin(lowest, tau[i]);
     }
     for (int i = 0; i < n; i++) tau[i] -= lowest;
+}
+
+// include/awpu_hip_focus.h, THE RULE: the delays of the point `distance` metres along the direction the twelve floats m (Rz row-major,
+// then row z of Ry: pixel_rotations' layout) steer to; the farthest element is read undelayed
+void focus_delays(const float *xyz, int n, const float *m, double distance, float *tau) {
+    double w[3], F[3];
+    awpu::focus_direction(m, w);
+    awpu::focus_point(w, distance, F);
+    double far = 0.0;  // (a path is >= 0)
+    for (int i = 0; i < n; i++) {
+        const double d = awpu::focus_path(F, xyz[i], xyz[n + i], xyz[2 * n + i]);
+        far = d > far ? d : far;
+    }
+    for (int i = 0; i < n; i++) tau[i] = awpu::focus_delay(far, awpu::focus_path(F, xyz[i], xyz[n + i], xyz[2 * n + i]));
+}
+
+// ... from a direction, as steering_delays() takes it
+void focus_delays(const float *xyz, int n, double theta, double phi, double distance, float *tau) {
+    const Rot rz = rotate_z(static_cast<float>(phi));
+    const Rot ry = rotate_y(-static_cast<float>(theta));
+    float m[12];
+    for (int a = 0; a < 3; a++)
+        for (int b = 0; b < 3; b++) m[3 * a + b] = rz.m[a][b];
+    for (int b = 0; b < 3; b++) m[9 + b] = ry.m[2][b];
+    focus_delays(xyz, n, m, distance, tau);
+}
+
+// mimo.cpp:46-54 / particle.cpp:39-47
+void split_delays(const float *tau, int n, int32_t *off, float *frac) {
+    for (int i = 0; i < n; i++) {
+        double whole;
+        frac[i] = static_cast<float>(std::modf(static_cast<double>(tau[i]), &whole));
+        off[i] = AWPU_N_SAMPLES - static_cast<int>(whole);
+    }
 }
 
 void element_position(int r, int c, int rows, int columns, float distance, float *x, float *y) {
@@ -180,6 +216,50 @@ int awpu_hip_build_delay_table(const float *xyz, int32_t n, int32_t rows, int32_
                 off[k * n + i] = AWPU_N_SAMPLES - static_cast<int>(whole);
             }
         }
+    }
+    return AWPU_OK;
+}
+
+// ---- focused tables (include/awpu_hip_focus.h) ----
+
+int awpu_hip_focus_delays(const float *xyz, int32_t n, double theta, double phi, double distance, float *tau) {
+    if (!xyz || !tau || n <= 0 || !awpu::focus_distance_ok(distance)) return AWPU_ERR_INVALID;
+    if (awpu::focus_is_plane_wave(distance)) return awpu_hip_steering_delays(xyz, n, theta, phi, tau);
+    focus_delays(xyz, n, theta, phi, distance, tau);
+    return AWPU_OK;
+}
+
+int awpu_hip_focus_steer_table(const float *xyz, int32_t n, const double *theta, const double *phi, const double *distance,
+                               int32_t n_dir, int32_t *off, float *frac) {
+    if (!xyz || !theta || !phi || !distance || !off || !frac || n <= 0 || n_dir <= 0) return AWPU_ERR_INVALID;
+    for (int d = 0; d < n_dir; d++)
+        if (!awpu::focus_distance_ok(distance[d])) return AWPU_ERR_INVALID;
+    std::vector<float> tau(n);
+    for (int d = 0; d < n_dir; d++) {
+        int32_t *o = off + (size_t) d * n;
+        float *f = frac + (size_t) d * n;
+        if (awpu::focus_is_plane_wave(distance[d])) {
+            if (const int rc = awpu_hip_steer_table(xyz, n, theta + d, phi + d, 1, o, f); rc != AWPU_OK) return rc;
+            continue;
+        }
+        focus_delays(xyz, n, theta[d], phi[d], distance[d], tau.data());
+        split_delays(tau.data(), n, o, f);
+    }
+    return AWPU_OK;
+}
+
+int awpu_hip_build_focus_table(const float *xyz, int32_t n, int32_t rows, int32_t columns, float fov_deg, double distance,
+                               int32_t row_begin, int32_t row_count, int32_t *off, float *frac) {
+    if (!xyz || !off || !frac || n <= 0 || rows <= 0 || columns <= 0) return AWPU_ERR_INVALID;
+    if (row_begin < 0 || row_count < 0 || row_begin + row_count > rows) return AWPU_ERR_INVALID;
+    if (!awpu::focus_distance_ok(distance)) return AWPU_ERR_INVALID;
+    if (awpu::focus_is_plane_wave(distance)) return awpu_hip_build_delay_table(xyz, n, rows, columns, fov_deg, row_begin, row_count, off, frac);
+    const size_t P = (size_t) row_count * columns;
+    std::vector<float> rot(P * 12), tau(n);
+    awpu::pixel_rotations(rows, columns, fov_deg, row_begin, row_count, rot.data());  // the pixel's theta and phi, as awpu_hip_build_delay_table forms them
+    for (size_t k = 0; k < P; k++) {
+        focus_delays(xyz, n, rot.data() + k * 12, distance, tau.data());
+        split_delays(tau.data(), n, off + k * n, frac + k * n);
     }
     return AWPU_OK;
 }

@@ -17,6 +17,7 @@
 #include "das_kernels.h"
 
 #include "awpu_hip_track.h"
+#include "focus_rule.h"
 
 namespace awpu {
 
@@ -589,6 +590,109 @@ hipError_t launch_listen(const ListenArgs &a, bool tracking, bool fixed, hipStre
     if (fixed)
         hipLaunchKernelGGL(listen_fixed_kernel, dim3(a.n_blocks, a.n_listeners), dim3(kThreads), (size_t) a.usable * sizeof(LutEntry),
                            stream, a);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// range_kernel: awpu_hip_range (include/awpu_hip_focus.h).  One workgroup of 256 lanes, lane = output sample, per (source, four
+// consecutive candidate distances); the whole n_src x n_dist sweep is one launch.  Per candidate the delays of every element are
+// formed on the device -- the focus rule's doubles (focus_rule.h: the host's expressions, contraction off) and the longest path
+// over all elements, or, for a candidate at infinity, steer_table_kernel's plane wave -- and the active mics' entries go to LDS;
+// then the four beams in one pass over the mics (beam_sums<4>: each in the reference's order, the four windows of a mic's row
+// overlapping in the cache) and their powers (beam_powers), which are das_beam_kernel's operations: the bits awpu_hip_beams
+// gives for awpu_hip_focus_steer_table's entries.  Candidates past n_dist repeat the last one and are not written.  The frame
+// is read straight from L2, as the trackers read it.  Plain stores, no atomics.
+// ---------------------------------------------------------------------------------------
+constexpr int kRangeBeams = 4;
+
+__global__ __launch_bounds__(kThreads) void range_kernel(RangeArgs a) {
+#pragma clang fp contract(off)
+    extern __shared__ __attribute__((aligned(16))) LutEntry entries[];  // [4][usable]
+    __shared__ float line[kRangeBeams][kSamples];
+    __shared__ float partial[kRangeBeams][kSamples / 64];
+    __shared__ float lowest_of_wave[4];
+    __shared__ double far_of_wave[4];
+    const int i = threadIdx.x, k = blockIdx.y, j0 = blockIdx.x * kRangeBeams;
+    const int U = a.usable, n = a.n;
+    float *const row = a.power + (size_t) k * a.n_dist;
+    double theta, phi;
+    if (a.sources) {  // a run's own sources: an unused entry has no direction
+        const awpu_source_t *src = static_cast<const awpu_source_t *>(a.sources) + k;
+        if (src->pixel < 0) {
+            if (i < kRangeBeams && j0 + i < a.n_dist) row[j0 + i] = 0.0f;
+            return;
+        }
+        theta = src->theta, phi = src->phi;
+    } else {
+        theta = a.theta[k], phi = a.phi[k];
+    }
+    const float *frame = a.frame + (long long) (k / a.per_frame) * a.frame_step;
+    const Steer r = steer_of(theta, phi);
+    const float m[12] = {r.cz, -r.sz, 0.0f, r.sz, r.cz, 0.0f, 0.0f, 0.0f, 1.0f, -r.sy, 0.0f, r.cy};  // pixel_rotations' layout
+    double w[3];
+    focus_direction(m, w);
+
+    for (int q = 0; q < kRangeBeams; q++) {
+        const double distance = a.distance[min(j0 + q, a.n_dist - 1)];
+        if (focus_is_plane_wave(distance)) {  // steer_table_kernel
+            float lo = __builtin_inff();
+            for (int e = i; e < n; e += kThreads) lo = fminf(lo, raw_delay(r, a.xyz, n, e));
+            lo = block_min(lo, lowest_of_wave);
+            for (int s = i; s < U; s += kThreads) {
+                const int id = a.index[s];
+                int32_t off;
+                float frac;
+                split_delay(raw_delay(r, a.xyz, n, id) - lo, &off, &frac);
+                entries[q * U + s] = LutEntry{id * a.pitch + off, frac};
+            }
+        } else {
+            double F[3];
+            focus_point(w, distance, F);
+            double far = 0.0;
+            for (int e = i; e < n; e += kThreads) far = fmax(far, focus_path(F, a.xyz[e], a.xyz[n + e], a.xyz[2 * n + e]));
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) far = fmax(far, __shfl_xor(far, d));
+            if ((i & 63) == 0) far_of_wave[i >> 6] = far;
+            __syncthreads();
+            far = fmax(fmax(far_of_wave[0], far_of_wave[1]), fmax(far_of_wave[2], far_of_wave[3]));
+            for (int s = i; s < U; s += kThreads) {
+                const int id = a.index[s];
+                int32_t off;
+                float frac;
+                split_delay(focus_delay(far, focus_path(F, a.xyz[id], a.xyz[n + id], a.xyz[2 * n + id])), &off, &frac);
+                entries[q * U + s] = LutEntry{id * a.pitch + off, frac};
+            }
+        }
+        __syncthreads();  // the reduction slots are free for the next candidate; after the last: the entries are there
+    }
+
+    float out[kRangeBeams], pw[kRangeBeams];
+    beam_sums<kRangeBeams>(frame, entries, (size_t) U, U, i, out);
+    beam_powers<kRangeBeams>(out, i, line, partial, pw);
+    if (i < kRangeBeams && j0 + i < a.n_dist) row[j0 + i] = i == 0 ? pw[0] : i == 1 ? pw[1] : i == 2 ? pw[2] : pw[3];
+}
+
+// awpu_hip_range_pick on the device for a run's ranges: one lane per source, the host definition's own expressions
+__global__ void range_pick_kernel(RangeArgs a) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= a.n_src) return;
+    awpu_range_t *out = static_cast<awpu_range_t *>(a.best) + k;
+    if (a.sources && static_cast<const awpu_source_t *>(a.sources)[k].pixel < 0) {
+        range_unused(out);
+        return;
+    }
+    range_pick_one(a.power + (size_t) k * a.n_dist, a.distance, a.n_dist, out);
+}
+
+hipError_t launch_range(const RangeArgs &a, hipStream_t stream) {
+    // every window a beam reads ([256 - d, 512 - d] of its snapshot, d in [0, 256]) lies inside the frame: the callers' business
+    if (!a.frame || !a.xyz || !a.index || !a.power || (!a.sources && (!a.theta || !a.phi)) || a.n_src < 1 || a.n_src > 65535 || a.n_dist < 1 ||
+        a.n_dist > AWPU_RANGE_MAX_CANDIDATES || a.usable < 1 || a.n < 1 || a.per_frame < 1)
+        return hipErrorInvalidValue;
+    for (int j = 0; j < a.n_dist; j++)
+        if (!focus_distance_ok(a.distance[j])) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(range_kernel, dim3((a.n_dist + kRangeBeams - 1) / kRangeBeams, a.n_src), dim3(kThreads), track_lds_bytes(a.usable), stream, a);
+    if (a.best) hipLaunchKernelGGL(range_pick_kernel, dim3((a.n_src + 63) / 64), dim3(64), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -101,6 +101,28 @@ def make_frames(xyz: np.ndarray, batch: int, seed: int = 1234, theta: float = SO
     return out
 
 
+def make_point_frames(xyz: np.ndarray, batch: int, distance: float, theta: float = SOURCE_THETA, phi: float = SOURCE_PHI,
+                      seed: int = 1234, hist: int = binding.HIST) -> np.ndarray:
+    """[batch, n_mics, hist] float32: make_frames' twin for a point source `distance` metres along (theta, phi).
+
+    The wave front is a sphere around the source: mic m, d_m metres from it, hears the carrier d_m * fs / c samples late, i.e.
+    advanced by binding.focus_delays' tau_m = (max d - d_m) * fs / c against the farthest mic -- so a table focused on the
+    source adds the mics coherently and a plane-wave table does not.  The amplitude is make_frames' at every mic (no 1 / d
+    fall-off: what is modelled is the curvature), and so are the noise draws.
+    """
+    n = xyz.shape[1]
+    tau = binding.focus_delays(xyz, theta, phi, distance).astype(np.float64)
+    rng = np.random.RandomState(seed)
+    t = np.arange(hist, dtype=np.float64)
+    out = np.empty((batch, n, hist), np.float32)
+    for b in range(batch):
+        phase = 2.0 * np.pi * CARRIER * (t[None, :] + b * binding.N_SAMPLES + tau[:, None]) / SAMPLE_RATE
+        raw = rng.randint(0, 2 ** 32, size=(n, hist), dtype=np.uint32).astype(np.float64)
+        noise = NOISE * (raw * (2.0 / 4294967296.0) - 1.0)
+        out[b] = (AMPLITUDE * np.sin(phase) + noise).astype(np.float32)
+    return out
+
+
 def source_pixel(spec: WorkloadSpec, theta: float = SOURCE_THETA, phi: float = SOURCE_PHI) -> Tuple[int, int]:
     """(row, column) of the grid cell whose direction is closest to (theta, phi).
 

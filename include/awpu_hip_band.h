@@ -16,7 +16,8 @@
  *                     awpu_hip_watch_*, `sources` / `count` / `power` of awpu_hip_find_blocks / _samples / _samples_device.
  *                     Per-mic gains stay where they are, behind the filter.
  *   Read raw samples, as without a band:  awpu_hip_beams, awpu_hip_track, awpu_hip_steer_table*, `audio` and `trail` of the
- *                     listen calls, awpu_hip_calibrate_*, awpu_hip_ring_snapshot, awpu_hip_ingest_block, the ring's content.
+ *                     listen calls, awpu_hip_range and `ranges` / `range_power` of awpu_hip_locate_* (awpu_hip_focus.h),
+ *                     awpu_hip_calibrate_*, awpu_hip_ring_snapshot, awpu_hip_ingest_block, the ring's content.
  *   Refused while a band is set (AWPU_ERR_STATE, nothing enqueued, handle and ring untouched):  awpu_hip_live_block (its
  *                     captured step), awpu_hip_pack_frames / _process_packed / _packed_bytes (the exchange format stays raw).
  *

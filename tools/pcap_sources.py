@@ -8,6 +8,12 @@ tools/pcap_heatmaps.py's reader (counter gaps reported, not repaired).
 --band LO:HI[:TAPS] (Hz; 63 taps unless given) limits the heatmaps to a band, e.g. --band 6375:9000: the sources are those of the band
 (Engine.set_band with binding.band_design's coefficients, include/awpu_hip_band.h).
 
+--focus METRES focuses the delay table on points METRES away instead of on plane waves (binding.build_focus_table,
+include/awpu_hip_focus.h): what a large array needs for anything in a room.  --range LO:HI:N also ranges every source: the beam power
+at its direction is swept over N focus distances from LO to HI metres, uniform in 1 / d (HI may be inf), on the block's raw samples
+while they are on the device (Engine.locate_blocks), and the distance at which it peaks is written as a last column, `distance`
+(metres, 17 significant digits; inf: a plane wave).
+
 Every block is ingested; every --every'th is swept and searched.  --chunk blocks go to the engine per call, each call continuing
 with the `next_first` of the one before, so a long capture streams through bounded memory.
 
@@ -30,31 +36,44 @@ import numpy as np
 HEADER = ["block", "rank", "pixel", "power", "row", "col", "theta", "phi"]
 
 
-def write_rows(writer, blocks, sources, count) -> int:
+def write_rows(writer, blocks, sources, count, ranges=None) -> int:
     """Lines for the frames of one result: blocks [n_frames] block numbers, sources [n_frames, max_sources] records, count
-    [n_frames].  -> lines written."""
+    [n_frames]; ranges [n_frames, max_sources] records or None (--range: the `distance` column).  -> lines written."""
     lines = 0
-    for block, entries, n in zip(blocks, sources, count):
+    for j, (block, entries, n) in enumerate(zip(blocks, sources, count)):
         for rank in range(int(n)):
             s = entries[rank]
             writer.writerow([int(block), rank, int(s["pixel"]), f"{np.float32(s['power']):.9g}"] +
-                            [f"{float(s[name]):.17g}" for name in ("row", "col", "theta", "phi")])
+                            [f"{float(s[name]):.17g}" for name in ("row", "col", "theta", "phi")] +
+                            ([] if ranges is None else [f"{float(ranges[j][rank]['distance']):.17g}"]))
             lines += 1
     return lines
 
 
 def read_rows(path):
-    """-> a structured array with the columns of HEADER (block, rank, pixel int64; power float32; the rest float64)."""
-    dtype = np.dtype([("block", "<i8"), ("rank", "<i8"), ("pixel", "<i8"), ("power", "<f4"), ("row", "<f8"), ("col", "<f8"),
-                      ("theta", "<f8"), ("phi", "<f8")])
+    """-> a structured array with the columns of HEADER (block, rank, pixel int64; power float32; the rest float64), and
+    `distance` (float64) where the file has that column."""
+    fields = [("block", "<i8"), ("rank", "<i8"), ("pixel", "<i8"), ("power", "<f4"), ("row", "<f8"), ("col", "<f8"),
+              ("theta", "<f8"), ("phi", "<f8")]
     with open(path, newline="") as f:
         rows = list(csv.reader(f))
-    if not rows or rows[0] != HEADER:
+    if not rows or rows[0] not in (HEADER, HEADER + ["distance"]):
         raise ValueError(f"{path}: not a sources file (header {rows[:1]})")
-    out = np.zeros(len(rows) - 1, dtype)
+    out = np.zeros(len(rows) - 1, np.dtype(fields + ([("distance", "<f8")] if len(rows[0]) > len(HEADER) else [])))
     for k, row in enumerate(rows[1:]):
         out[k] = (int(row[0]), int(row[1]), int(row[2]), np.float32(row[3]), *(float(v) for v in row[4:]))
     return out
+
+
+def candidates_from_text(pkg, text: str) -> np.ndarray:
+    """'LO:HI:N' (metres, HI may be inf; 2 <= N <= 64) -> N candidate distances uniform in 1 / d."""
+    parts = text.split(":")
+    if len(parts) != 3:
+        raise ValueError(f"range '{text}': LO:HI:N, in metres")
+    lo, hi, n = float(parts[0]), float(parts[1]), int(parts[2])
+    if not (0.0 < lo < hi) or not 2 <= n <= pkg.binding.RANGE_MAX_CANDIDATES:
+        raise ValueError(f"range '{text}': 0 < LO < HI and 2 <= N <= {pkg.binding.RANGE_MAX_CANDIDATES}")
+    return pkg.range_candidates(lo, hi, n)
 
 
 def main(argv=None) -> int:
@@ -74,6 +93,9 @@ def main(argv=None) -> int:
     ap.add_argument("--max-batch", type=int, default=128, help="frames per sweep launch")
     ap.add_argument("--out", default="sources.csv")
     ap.add_argument("--band", default=None, metavar="LO:HI[:TAPS]", help="limit the heatmaps to LO .. HI Hz (an FIR band of TAPS taps, 63 unless given)")
+    ap.add_argument("--focus", type=float, default=None, metavar="METRES", help="focus the delay table on points METRES away (default: plane waves)")
+    ap.add_argument("--range", default=None, metavar="LO:HI:N", dest="range_",
+                    help="range every source over N focus distances from LO to HI metres, uniform in 1 / d: the `distance` column")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     if a.every < 1 or a.chunk < 1:
@@ -94,7 +116,11 @@ def main(argv=None) -> int:
     sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
     pkg = importlib.import_module("beamforming-lk_amd")
     xyz = pkg.create_tiled_antenna(a.arrays, a.rows)
-    off, frac = pkg.build_delay_table(xyz, a.cols, a.cols, a.fov)
+    if a.focus is not None:
+        off, frac = pkg.build_focus_table(xyz, a.cols, a.cols, a.focus, a.fov)
+    else:
+        off, frac = pkg.build_delay_table(xyz, a.cols, a.cols, a.fov)
+    candidates = candidates_from_text(pkg, a.range_) if a.range_ else None
     n = xyz.shape[1]
     if n > 256:
         print(f"{n} mics: the wire carries 256 streams per datagram")
@@ -103,16 +129,20 @@ def main(argv=None) -> int:
     with open(a.out, "w", newline="") as f, \
             pkg.Engine(n_pixels=a.cols * a.cols, n_streams=n, max_batch=a.max_batch, grid_columns=a.cols, device=a.device) as eng:
         writer = csv.writer(f, lineterminator="\n")
-        writer.writerow(HEADER)
+        writer.writerow(HEADER + (["distance"] if candidates is not None else []))
         eng.set_delay_table(off, frac)
         eng.set_active_mics(None)
+        if candidates is not None:
+            eng.set_antenna(xyz)
         if a.band:
             eng.set_band(pkg.binding.band_from_text(a.band))
         for b in range(0, n_blocks, a.chunk):
             nb = min(a.chunk, n_blocks - b)
-            res = eng.find_blocks(wire[b * block_bytes: (b + nb) * block_bytes], a.cols, a.cols, first=first, every=a.every,
-                                  radius=a.radius, max_sources=a.max_sources, min_power=a.min_power, min_ratio=a.min_ratio, fov_deg=a.fov)
-            lines += write_rows(writer, b + first + a.every * np.arange(len(res)), res.sources, res.count)
+            find = dict(first=first, every=a.every, radius=a.radius, max_sources=a.max_sources, min_power=a.min_power, min_ratio=a.min_ratio,
+                        fov_deg=a.fov)
+            chunk = wire[b * block_bytes: (b + nb) * block_bytes]
+            res = eng.find_blocks(chunk, a.cols, a.cols, **find) if candidates is None else eng.locate_blocks(chunk, a.cols, a.cols, candidates, **find)
+            lines += write_rows(writer, b + first + a.every * np.arange(len(res)), res.sources, res.count, getattr(res, "ranges", None))
             first = res.next_first
             searched += len(res)
     print(f"{lines} sources in {searched} of {n_blocks} blocks: {a.out}")

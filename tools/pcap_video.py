@@ -9,6 +9,9 @@ reader (counter gaps reported, not repaired).
 --band LO:HI[:TAPS] (Hz; 63 taps unless given) limits the heatmaps to a band, e.g. --band 6375:9000: the video shows the band
 (Engine.set_band with binding.band_design's coefficients, include/awpu_hip_band.h).
 
+--focus METRES focuses the delay table on points METRES away instead of on plane waves (binding.build_focus_table,
+include/awpu_hip_focus.h): a large array in a room is in its sources' near field, where a plane-wave table blurs them.
+
 Every block is ingested; every --every'th is swept and shown.  The default 3 gives 48828 / (256 * 3) = 63.6 frames per second, the
 nearest to the 60 the reference opens its writer with.  --chunk blocks go to the engine per call, each call continuing with the
 `next_first` of the one before, so a long capture streams through bounded memory.
@@ -177,6 +180,8 @@ def main(argv=None) -> int:
     ap.add_argument("--raw", action="store_true", help="headerless BGR24 frames into OUT.bgr instead of AVI parts")
     ap.add_argument("--out", default="heatmap", help="output prefix")
     ap.add_argument("--band", default=None, metavar="LO:HI[:TAPS]", help="limit the heatmaps to LO .. HI Hz (an FIR band of TAPS taps, 63 unless given)")
+    ap.add_argument("--focus", type=float, default=None, metavar="METRES",
+                    help="focus the delay table on points METRES away instead of on plane waves (include/awpu_hip_focus.h)")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     if a.every < 1 or a.chunk < 1 or a.size < a.cols:
@@ -199,7 +204,10 @@ def main(argv=None) -> int:
     import torch
 
     xyz = pkg.create_tiled_antenna(a.arrays, a.rows)
-    off, frac = pkg.build_delay_table(xyz, a.cols, a.cols, a.fov)
+    if a.focus is not None:
+        off, frac = pkg.build_focus_table(xyz, a.cols, a.cols, a.focus, a.fov)
+    else:
+        off, frac = pkg.build_delay_table(xyz, a.cols, a.cols, a.fov)
     n = xyz.shape[1]
     if n > 256:
         print(f"{n} mics: the wire carries 256 streams per datagram")
