@@ -260,6 +260,34 @@ _BAND_SIGNATURES = {
 }
 BAND_SYMBOLS = tuple(_BAND_SIGNATURES)
 
+# spectral heatmaps: the entry points of include/awpu_hip_spectral.h
+SPECTRAL_MAX_BANDS = 4
+SPECTRAL_SCALE_COMMON, SPECTRAL_SCALE_PER_BAND = 0, 1
+
+
+class Spectral(C.Structure):
+    """awpu_spectral_t (include/awpu_hip_spectral.h)."""
+    _fields_ = [
+        ("n_bands", C.c_int32),
+        ("taps", C.c_int32 * SPECTRAL_MAX_BANDS),
+        ("coef", _f32p * SPECTRAL_MAX_BANDS),
+        ("channel", C.c_int32 * 3),
+        ("scale", C.c_int32),
+    ]
+
+
+_SPECTRAL_TAIL = [*_WATCH_TAIL, C.POINTER(Spectral)]  # n_blocks, w, sp
+_SPECTRAL_SIGNATURES = {
+    "awpu_hip_spectral_compose": (C.c_int, [_f32p, C.c_int64, C.c_int32, C.c_int32, _i32p, C.c_int32, _u8p, _u8p]),
+    "awpu_hip_process_bands": (C.c_int, [C.c_void_p, _f32p, C.c_int32, C.POINTER(Spectral), _f32p]),
+    "awpu_hip_process_bands_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Spectral), C.c_void_p, C.c_void_p]),
+    "awpu_hip_spectral_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, *_SPECTRAL_TAIL, _u8p, _u8p, _u8p, _f32p]),
+    "awpu_hip_spectral_samples": (C.c_int, [C.c_void_p, _f32p, C.c_int64, *_SPECTRAL_TAIL, _u8p, _u8p, _u8p, _f32p]),
+    "awpu_hip_spectral_samples_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, *_SPECTRAL_TAIL, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p]),
+}
+SPECTRAL_SYMBOLS = tuple(_SPECTRAL_SIGNATURES)
+
 RANGE_MAX_CANDIDATES = 64
 
 
@@ -327,7 +355,7 @@ def load(build: bool = True) -> C.CDLL:
     lib = C.CDLL(str(path))
     for name, (res, args) in list(_SIGNATURES.items()) + list(_TRACK_SIGNATURES.items()) + list(_BLOCK_SIGNATURES.items()) + \
             list(_LISTEN_SIGNATURES.items()) + list(_WATCH_SIGNATURES.items()) + list(_FIND_SIGNATURES.items()) + list(_BAND_SIGNATURES.items()) + \
-            list(_FOCUS_SIGNATURES.items()):
+            list(_FOCUS_SIGNATURES.items()) + list(_SPECTRAL_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -653,6 +681,53 @@ def band_filter(samples: np.ndarray, coeffs: np.ndarray) -> np.ndarray:
     return y
 
 
+def spectral_of(bands, channel=None, scale: int = SPECTRAL_SCALE_COMMON):
+    """(awpu_spectral_t, what keeps its coefficients alive) of `bands`, a sequence of coefficient arrays (band_design's, say);
+    channel None: byte c shows band c where there is one.  Nothing is judged here: the library refuses a bad set."""
+    if channel is None:
+        channel = [c if c < len(bands) else -1 for c in range(3)]
+    coeffs = [np.ascontiguousarray(c, np.float32).reshape(-1) for c in bands]
+    sp = Spectral()
+    sp.n_bands = len(coeffs)
+    for b, c in enumerate(coeffs[:SPECTRAL_MAX_BANDS]):
+        sp.taps[b] = c.size
+        sp.coef[b] = c.ctypes.data_as(_f32p)
+    sp.channel[:] = [int(c) for c in channel]
+    sp.scale = int(scale)
+    return sp, coeffs
+
+
+def spectral_compose(power: np.ndarray, channel=(0, 1, 2), scale: int = SPECTRAL_SCALE_COMMON):
+    """One frame's band powers [n_bands, n] -> (image [n, 3] uint8, dominant [n] uint8): the display rule of the spectral runs on
+    the host (awpu_hip_spectral_compose).  Byte c of a pixel shows band channel[c] (-1: 0), scaled by one maximum over the shown
+    bands (SPECTRAL_SCALE_COMMON) or by each band's own (SPECTRAL_SCALE_PER_BAND); dominant names the strongest band of all."""
+    power = np.ascontiguousarray(power, np.float32)
+    if power.ndim != 2:
+        raise ValueError("power must be [n_bands, n]")
+    n_bands, n = power.shape
+    image, dominant = np.empty((n, 3), np.uint8), np.empty(n, np.uint8)
+    ch = np.asarray(channel, np.int32).reshape(3)
+    _check(load().awpu_hip_spectral_compose(_f32(power), n, n_bands, n, _i32(ch), int(scale), image.ctypes.data_as(_u8p),
+                                            dominant.ctypes.data_as(_u8p)), "awpu_hip_spectral_compose")
+    return image, dominant
+
+
+class SpectralResult:
+    """What Engine.spectral_* hand back: .image [n_frames, rows, cols, 3] uint8 or None, .big [n_frames, out_rows, out_cols, 3] or
+    None, .dominant [n_frames, rows, cols] or None, .power [n_bands, n_frames, pixels] or None, and .next_first: the `first` of the
+    call that continues the recording.  Frame j shows block first + j * every of the call."""
+
+    def __init__(self, image, big, dominant, power, next_first: int):
+        self.image = image
+        self.big = big
+        self.dominant = dominant
+        self.power = power
+        self.next_first = next_first
+
+    def __len__(self):
+        return next(a.shape[1] if a is self.power else len(a) for a in (self.image, self.big, self.dominant, self.power) if a is not None)
+
+
 def _particles(theta, phi, spread, rate, steps, where: str) -> np.ndarray:
     """PARTICLE_DTYPE records from per-particle values (scalars broadcast), or a copy of such records passed as `theta`."""
     if isinstance(theta, np.ndarray) and theta.dtype == PARTICLE_DTYPE:
@@ -896,6 +971,78 @@ class Engine:
         _check(self._lib.awpu_hip_watch_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, C.byref(w),
                                                        C.c_void_p(d_image_ptr), C.c_void_p(d_big_ptr), C.c_void_p(d_power_ptr),
                                                        C.c_void_p(stream)), "awpu_hip_watch_samples_device")
+        return watch_count(n_blocks, first, every)[1]
+
+    def process_bands(self, frames: np.ndarray, bands) -> np.ndarray:
+        """frames [batch, n_streams, hist] through every band of `bands` (a sequence of up to four coefficient arrays) from one
+        upload and one pre-pass -> power [n_bands, batch, pixels]; power[b] is process() with set_band(bands[b]), bit for bit
+        (awpu_hip_process_bands)."""
+        frames = np.ascontiguousarray(frames, np.float32)
+        if frames.ndim != 3 or frames.shape[1:] != (self.cfg.n_streams, self.cfg.hist):
+            raise ValueError(f"frames must be [batch, {self.cfg.n_streams}, {self.cfg.hist}]")
+        sp, _keep = spectral_of(bands)
+        power = np.empty((max(sp.n_bands, 1), frames.shape[0], self.pixel_count), np.float32)
+        _check(self._lib.awpu_hip_process_bands(self._h, _f32(frames), frames.shape[0], C.byref(sp), _f32(power)), "awpu_hip_process_bands")
+        return power
+
+    def process_bands_device(self, d_frames_ptr: int, batch: int, bands, d_power_ptr: int, stream: int = 0) -> None:
+        """The same on device pointers (frames [batch, n_streams, hist], power [n_bands, batch, pixels]) on `stream`; asynchronous
+        (awpu_hip_process_bands_device)."""
+        sp, _keep = spectral_of(bands)
+        _check(self._lib.awpu_hip_process_bands_device(self._h, C.c_void_p(d_frames_ptr), batch, C.byref(sp), C.c_void_p(d_power_ptr),
+                                                       C.c_void_p(stream)), "awpu_hip_process_bands_device")
+
+    def _spectral(self, call, where, n_blocks, first, every, rows, cols, out_rows, out_cols, flip, bands, channel, scale, want_image,
+                  want_dominant, want_power) -> SpectralResult:
+        n_frames, next_first = watch_count(n_blocks, first, every)
+        w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(0))
+        sp, _keep = spectral_of(bands, channel, scale)
+        image = np.empty((n_frames, rows, cols, 3), np.uint8) if want_image else None
+        big = np.empty((n_frames, out_rows, out_cols, 3), np.uint8) if out_rows else None
+        dominant = np.empty((n_frames, rows, cols), np.uint8) if want_dominant else None
+        power = np.empty((max(sp.n_bands, 1), n_frames, self.pixel_count), np.float32) if want_power else None
+        # (an output that is wanted is never a null pointer, not even with no frame to write)
+        ptr = lambda a, t: None if a is None else C.cast(C.c_void_p(a.ctypes.data or 16), t)
+        _check(call(n_blocks, C.byref(w), C.byref(sp), ptr(image, _u8p), ptr(big, _u8p), ptr(dominant, _u8p), ptr(power, _f32p)), where)
+        return SpectralResult(image, big, dominant, power, next_first)
+
+    def spectral_blocks(self, wire, rows: int, cols: int, bands, channel=None, scale: int = SPECTRAL_SCALE_COMMON, first: int = 0,
+                        every: int = 1, out_rows: int = 0, out_cols: int = 0, flip: bool = False, stride: int = DATAGRAM_BYTES,
+                        want_image: bool = True, want_dominant: bool = True, want_power: bool = False) -> SpectralResult:
+        """Watch a run of wire datagrams (as watch_blocks takes them) in up to four bands at once: every block is appended to the
+        ring, blocks first, first + every, ... are filtered by every band of `bands` in one pre-pass and swept once per band; byte c
+        of a pixel of .image shows band channel[c] (None: band c where there is one; spectral_compose), .big is that image upscaled (and mirrored when flip),
+        .dominant the strongest band of every pixel, .power every band's powers (awpu_hip_spectral_blocks).  -> SpectralResult."""
+        buf = np.frombuffer(wire, dtype=np.uint8)
+        if stride < DATAGRAM_BYTES or buf.size % (256 * stride) or buf.size == 0:
+            raise ValueError(f"wire must be a whole number of blocks of 256 datagrams {stride} bytes apart")
+        return self._spectral(lambda *rest: self._lib.awpu_hip_spectral_blocks(self._h, buf.ctypes.data_as(C.c_void_p), stride, *rest),
+                              "awpu_hip_spectral_blocks", buf.size // (256 * stride), first, every, rows, cols, out_rows, out_cols, flip, bands,
+                              channel, scale, want_image, want_dominant, want_power)
+
+    def spectral_samples(self, samples: np.ndarray, rows: int, cols: int, bands, channel=None, scale: int = SPECTRAL_SCALE_COMMON,
+                         first: int = 0, every: int = 1, out_rows: int = 0, out_cols: int = 0, flip: bool = False, want_image: bool = True,
+                         want_dominant: bool = True, want_power: bool = False) -> SpectralResult:
+        """The same from unpacked samples [n_streams, N] (N a multiple of 256, oldest first) (awpu_hip_spectral_samples)."""
+        samples = np.ascontiguousarray(samples, np.float32)
+        if samples.ndim != 2 or samples.shape[0] != self.cfg.n_streams or samples.shape[1] % 256 or samples.shape[1] == 0:
+            raise ValueError(f"samples must be [{self.cfg.n_streams}, N] with N a positive multiple of 256")
+        return self._spectral(lambda *rest: self._lib.awpu_hip_spectral_samples(self._h, _f32(samples), samples.shape[1], *rest),
+                              "awpu_hip_spectral_samples", samples.shape[1] // 256, first, every, rows, cols, out_rows, out_cols, flip, bands,
+                              channel, scale, want_image, want_dominant, want_power)
+
+    def spectral_samples_device(self, d_samples_ptr: int, pitch: int, n_blocks: int, rows: int, cols: int, bands, channel=None,
+                                scale: int = SPECTRAL_SCALE_COMMON, first: int = 0, every: int = 1, d_image_ptr: int = 0, d_big_ptr: int = 0,
+                                d_dominant_ptr: int = 0, d_power_ptr: int = 0, out_rows: int = 0, out_cols: int = 0, flip: bool = False,
+                                stream: int = 0) -> int:
+        """The same on device pointers (samples [n_streams, pitch]; image [n_frames, rows * cols, 3], big [n_frames, out_rows, out_cols,
+        3], dominant [n_frames, rows * cols], power [n_bands, n_frames, pixels], each or 0) on `stream`; asynchronous.  -> next_first
+        (awpu_hip_spectral_samples_device)."""
+        w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(0))
+        sp, _keep = spectral_of(bands, channel, scale)
+        _check(self._lib.awpu_hip_spectral_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, C.byref(w), C.byref(sp),
+                                                          C.c_void_p(d_image_ptr), C.c_void_p(d_big_ptr), C.c_void_p(d_dominant_ptr),
+                                                          C.c_void_p(d_power_ptr), C.c_void_p(stream)), "awpu_hip_spectral_samples_device")
         return watch_count(n_blocks, first, every)[1]
 
     def find_peaks_device(self, d_power_ptr: int, n_frames: int, rows: int, cols: int, d_sources_ptr: int, d_count_ptr: int,

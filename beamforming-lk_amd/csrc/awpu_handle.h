@@ -4,6 +4,7 @@
 #pragma once
 
 #include "awpu_hip.h"
+#include "awpu_hip_spectral.h"
 #include "awpu_hip_track.h"
 
 #include <hip/hip_runtime.h>
@@ -379,10 +380,14 @@ struct awpu_hip {
     awpu::host::BufferPair find_out;
 
     // the band (awpu_hip_band.h): its coefficients (empty = none; they travel to the pre-pass as kernel arguments), and the
-    // filtered frames of a call whose own frames are the caller's or the ring's, in those frames' layout (band_sweep)
+    // filtered frames of a call whose own frames are the caller's or the ring's, in those frames' layout (band_sweep): a plane
+    // per band, where a spectral call (awpu_hip_spectral.h) brings several
     std::vector<float> band;
     Dev<float> d_band;
     int band_taps() const { return static_cast<int>(band.size()); }
+    // spectral runs (awpu_hip_spectral.h), by piece as `watch`: every frame's band maxima, its three-byte image, its dominant
+    // bands and (host forms) its large image
+    awpu::host::BufferPair spectral;
 
     awpu_hip_stats stats{};
     std::string last_error;                  // awpu_hip_last_error_of
@@ -438,6 +443,21 @@ struct EnvKnobs {
 };
 const EnvKnobs &env();
 
+// The bands in front of a sweep: none, the handle's own (awpu_hip_band.h) or those of a spectral call (awpu_hip_spectral.h).  The
+// coefficients stay their owner's: a set lives no longer than the call that made it.
+struct BandSet {
+    int n = 0;
+    int taps[AWPU_SPECTRAL_MAX_BANDS] = {0, 0, 0, 0};
+    const float *coef[AWPU_SPECTRAL_MAX_BANDS] = {nullptr, nullptr, nullptr, nullptr};
+    int max_taps() const { return std::max(std::max(taps[0], taps[1]), std::max(taps[2], taps[3])); }
+    int planes() const { return std::max(n, 1); }  // what a sweep's windows and powers are held in
+};
+inline BandSet own_band(const awpu_hip *h) {
+    BandSet set;
+    if (!h->band.empty()) set.n = 1, set.taps[0] = h->band_taps(), set.coef[0] = h->band.data();
+    return set;
+}
+
 // layout of d_frames: kFull [batch][n_streams][hist]; kCompact [batch][n_streams][compact_hist] with
 // sample 0 = history sample wstart; kRing one frame read in place from the ingest ring (rows 2048 apart)
 enum FrameLayout { kFull = 0, kCompact = 1, kRing = 2 };
@@ -454,10 +474,11 @@ int sweep_packed(awpu_hip *h, const awpu::FastPlan &plan, const float *d_packed,
 
 // defined, and described, in awpu_hip.cpp
 void retire_live_graphs(awpu_hip *h);
-int enqueue_host_process(awpu_hip *h, const float *frames, int batch);
+int enqueue_host_process(awpu_hip *h, const float *frames, int batch, const BandSet *bands = nullptr);  // (null: the handle's own band, if any)
 int enqueue_power_to_host(awpu_hip *h, int batch, float *power, size_t pitch);
 int enqueue_ingest(awpu_hip *h, const void *datagrams, int32_t stride_bytes);
 int check_ready(awpu_hip *h, int batch);
+extern const char *const kBandHistory;  // what AWPU_ERR_RANGE says where the bands' history does not fit a snapshot
 int ensure_power(awpu_hip *h, size_t need_power);
 int ensure_ring(awpu_hip *h);
 int host_piece(int batch);
@@ -468,8 +489,14 @@ int check_antenna(const awpu_hip *h);
 int ensure_track_index(awpu_hip *h);
 int check_candidates(const double *distance, int32_t n_dist);  // awpu_focus.cpp: the candidate distances of awpu_hip_focus.h
 int ensure_taps(awpu_hip *h, int rows, int cols, int out_rows, int out_cols, hipStream_t s);
-int band_cut(awpu_hip *h, const float *in, long long in_frame, long long in_row, int in_lo, int batch, float *out, int layout, hipStream_t s);
-int band_sweep(awpu_hip *h, const float *in, long long in_frame, long long in_row, int in_lo, int batch, float *d_power, hipStream_t s, int layout);
+int band_cut(awpu_hip *h, const BandSet &bands, const float *in, long long in_frame, long long in_row, int in_lo, int batch, float *out,
+             long long out_plane, int layout, hipStream_t s);
+int band_sweep(awpu_hip *h, const BandSet &bands, const float *in, long long in_frame, long long in_row, int in_lo, int batch, float *d_power,
+               long long power_plane, hipStream_t s, int layout);
+inline int band_sweep(awpu_hip *h, const float *in, long long in_frame, long long in_row, int in_lo, int batch, float *d_power, hipStream_t s, int layout) {
+    return band_sweep(h, own_band(h), in, in_frame, in_row, in_lo, batch, d_power, 0, s, layout);  // the handle's own band: the one-band case
+}
+int check_spectral(awpu_hip *h, const awpu_spectral_t *sp, BandSet *bands);  // a spectral call's bands, or why the handle does not take them
 
 // A buffer whose pointer the captured live-block graphs bake in (d_power, d_pack, d_display): they are retired before the old pointer
 // goes.  (prepare() and ensure_taps() retire for the tables and d_taps; launch_exact_nd for d_nd_items, a synchronize before it grows.)

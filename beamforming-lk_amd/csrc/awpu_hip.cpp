@@ -17,6 +17,8 @@
 #include "awpu_hip_band.h"
 #include "band_kernels.h"
 #include "band_rule.h"
+#include "spectral_kernels.h"
+#include "spectral_rule.h"
 #include "das_kernels.h"
 #include "focus_rule.h"
 #include "watch_kernels.h"
@@ -120,7 +122,7 @@ void awpu::host::retire_live_graphs(awpu_hip *h) {
 
 namespace awpu::host {
 
-const char *const kBandHistory = "the band reads taps - 1 samples in front of the window: the delay table leaves a snapshot fewer";
+extern const char *const kBandHistory = "the band reads taps - 1 samples in front of the window: the delay table leaves a snapshot fewer";
 
 int check_ready(awpu_hip *h, int batch) {
     if (!h) return invalid("null handle");
@@ -150,15 +152,17 @@ int host_piece(int batch) {
 }
 
 // upload of host frames + the sweep into h->d_power, all on h->stream, nothing waited for
-int enqueue_host_process(awpu_hip *h, const float *frames, int batch) {
+int enqueue_host_process(awpu_hip *h, const float *frames, int batch, const BandSet *given) {
     int rc = check_ready(h, batch);
     if (rc != AWPU_OK) return rc;
+    const BandSet bands = given ? *given : own_band(h);  // several: band b's powers of the batch at d_power + b * batch * pixel_count
+    if (bands.max_taps() - 1 > h->wstart) return fail(AWPU_ERR_RANGE, kBandHistory);
     const bool compact = h->compact_hist > 0;
-    const int pre = compact ? std::max(h->band_taps() - 1, 0) : 0;  // a band reads that many samples in front of the window: they travel too
+    const int pre = compact ? std::max(bands.max_taps() - 1, 0) : 0;  // a band reads that many samples in front of the window: they travel too
     const int dev_hist = (compact ? h->compact_hist : h->cfg.hist) + pre;
     const size_t need_frames = (size_t) h->cfg.n_streams * dev_hist * batch;
     rc = h->d_frames.ensure(need_frames);
-    if (rc == AWPU_OK) rc = ensure_power(h, (size_t) h->cfg.pixel_count * batch);
+    if (rc == AWPU_OK) rc = ensure_power(h, (size_t) h->cfg.pixel_count * batch * bands.planes());
     if (rc != AWPU_OK) return rc;
     // Large batches go up in pieces on a second stream, so that piece k+1 crosses PCIe while piece k is swept (the
     // pieces are whole frame pairs: the same arithmetic as one launch).  last_kernel_ms then spans all the sweeps.
@@ -189,8 +193,8 @@ int enqueue_host_process(awpu_hip *h, const float *frames, int batch) {
             if (keep_timing && b0 == 0) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, h->stream));
             h->timing = false;
         }
-        rc = band_sweep(h, dst, (long long) h->cfg.n_streams * dev_hist, dev_hist, compact ? pre : h->wstart, nb,
-                        h->d_power + (size_t) b0 * h->cfg.pixel_count, h->stream, compact ? kCompact : kFull);
+        rc = band_sweep(h, bands, dst, (long long) h->cfg.n_streams * dev_hist, dev_hist, compact ? pre : h->wstart, nb,
+                        h->d_power + (size_t) b0 * h->cfg.pixel_count, (long long) batch * h->cfg.pixel_count, h->stream, compact ? kCompact : kFull);
         h->timing = keep_timing;
         if (rc != AWPU_OK) return rc;
     }
@@ -219,52 +223,91 @@ int enqueue_power_to_host(awpu_hip *h, int batch, float *power, size_t pitch) {
     return AWPU_OK;
 }
 
-// The band's pre-pass (awpu_hip_band.h; band_kernels.hip): the window of `batch` frames, filtered, into `out` in a layout launch()
-// takes -- kCompact, kFull-shaped with only the window written, or kRing-shaped (one frame, rows 2048 floats apart, `out` standing
-// for the snapshot's start).  Sample j of (frame f, stream id) is in[f * in_frame + id * in_row + j]; in_lo = where history
-// sample wstart is in such a row, with the band's taps - 1 samples in front of it (check_ready has seen to that).  What is
-// written is what a band-less call stages: the window rounded up as compact_hist is, cut at the end of the history.
-int band_cut(awpu_hip *h, const float *in, long long in_frame, long long in_row, int in_lo, int batch, float *out, int layout, hipStream_t s) {
-    const int S = h->cfg.n_streams, taps = h->band_taps();
-    awpu::BandArgs a{};
+// The bands' pre-pass (awpu_hip_band.h, awpu_hip_spectral.h; band_kernels.hip for one band, spectral_kernels.hip for several): the
+// window of `batch` frames, filtered, into `out` in a layout launch() takes -- kCompact, kFull-shaped with only the window written,
+// or kRing-shaped (one frame, rows 2048 floats apart, `out` standing for the snapshot's start) --, band b's out_plane floats
+// behind band b-1's.  Sample j of (frame f, stream id) is in[f * in_frame + id * in_row + j]; in_lo = where history sample wstart
+// is in such a row, with the longest band's taps - 1 samples in front of it (the caller has seen to that).  What is written is
+// what a band-less call stages: the window rounded up as compact_hist is, cut at the end of the history.
+int band_cut(awpu_hip *h, const BandSet &bands, const float *in, long long in_frame, long long in_row, int in_lo, int batch, float *out,
+             long long out_plane, int layout, hipStream_t s) {
+    const int S = h->cfg.n_streams;
+    const long long out_row = layout == kCompact ? h->compact_hist : (layout == kRing ? 2048 : h->cfg.hist);
+    const long long out_frame = layout == kRing ? 0 : out_row * S;
+    const int out_first = layout == kCompact ? 0 : h->wstart;
+    const int n = std::min(((h->window + 3) & ~3) + 4, h->cfg.hist - h->wstart);
+    if (bands.n == 1) {
+        awpu::BandArgs a{};
+        a.in = in;
+        a.in_frame = in_frame, a.in_row = in_row;
+        a.in_first = in_lo - (bands.taps[0] - 1);
+        a.out = out;
+        a.out_row = out_row, a.out_frame = out_frame, a.out_first = out_first;
+        a.n = n;
+        a.index = h->d_index;
+        a.usable = h->usable();
+        a.n_frames = batch;
+        a.taps = bands.taps[0];
+        std::copy(bands.coef[0], bands.coef[0] + bands.taps[0], a.coef);
+        AWPU_HIP_TRY(awpu::launch_band_filter(a, s));
+        return AWPU_OK;
+    }
+    awpu::SpectralBandArgs a{};
     a.in = in;
     a.in_frame = in_frame, a.in_row = in_row;
-    a.in_first = in_lo - (taps - 1);
+    a.in_first = in_lo - (bands.max_taps() - 1);
     a.out = out;
-    a.out_row = layout == kCompact ? h->compact_hist : (layout == kRing ? 2048 : h->cfg.hist);
-    a.out_frame = layout == kRing ? 0 : a.out_row * S;
-    a.out_first = layout == kCompact ? 0 : h->wstart;
-    a.n = std::min(((h->window + 3) & ~3) + 4, h->cfg.hist - h->wstart);
+    a.out_row = out_row, a.out_frame = out_frame, a.out_plane = out_plane, a.out_first = out_first;
+    a.n = n;
     a.index = h->d_index;
     a.usable = h->usable();
     a.n_frames = batch;
-    a.taps = taps;
-    std::copy(h->band.begin(), h->band.end(), a.coef);
-    AWPU_HIP_TRY(awpu::launch_band_filter(a, s));
+    a.n_bands = bands.n;
+    a.max_taps = bands.max_taps();
+    for (int b = 0; b < bands.n; b++) {
+        a.taps[b] = bands.taps[b];
+        std::copy(bands.coef[b], bands.coef[b] + bands.taps[b], a.coef[b]);
+    }
+    AWPU_HIP_TRY(awpu::launch_spectral_filter(a, s));
     return AWPU_OK;
 }
 
-// launch() on frames of the caller's or the ring's (kFull, kRing), or on windows uploaded with the band's history in front of them
-// (kCompact: rows of taps - 1 + compact_hist floats), through the band where the handle has one: the pre-pass into d_band in
-// `layout`, then the launch() a band-less handle makes for the same call -- the same layout and batch, so the same kernel.  The
-// handle's event bracket spans both
-int band_sweep(awpu_hip *h, const float *in, long long in_frame, long long in_row, int in_lo, int batch, float *d_power, hipStream_t s, int layout) {
-    if (h->band.empty()) return launch(h, in, batch, d_power, s, layout);
+// launch() on frames of the caller's or the ring's (kFull, kRing), or on windows uploaded with the bands' history in front of them
+// (kCompact: rows of max taps - 1 + compact_hist floats), through the bands where there are any: the pre-pass into d_band in
+// `layout`, a plane per band, then for every band the launch() a band-less handle makes for the same call -- the same layout and
+// batch, so the same kernel -- into d_power + b * power_plane.  The handle's event bracket spans all of it
+int band_sweep(awpu_hip *h, const BandSet &bands, const float *in, long long in_frame, long long in_row, int in_lo, int batch, float *d_power,
+               long long power_plane, hipStream_t s, int layout) {
+    if (bands.n == 0) return launch(h, in, batch, d_power, s, layout);
     const size_t S = (size_t) h->cfg.n_streams;
-    const size_t need = layout == kRing ? S * 2048 : S * (size_t) (layout == kCompact ? h->compact_hist : h->cfg.hist) * batch;
+    const size_t plane = layout == kRing ? S * 2048 : S * (size_t) (layout == kCompact ? h->compact_hist : h->cfg.hist) * batch;
+    const size_t need = plane * bands.n;
     if (!h->d_band.holds(need)) {  // (what no pre-pass writes and a sweep's wide loads may touch reads as zeros)
         if (const int rc = h->d_band.grow(need); rc != AWPU_OK) return rc;
         AWPU_HIP_TRY(hipMemsetAsync(h->d_band, 0, need * sizeof(float), s));
     }
     const bool timed = h->timing;
     if (timed) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
-    int rc = band_cut(h, in, in_frame, in_row, in_lo, batch, h->d_band, layout, s);
+    int rc = band_cut(h, bands, in, in_frame, in_row, in_lo, batch, h->d_band, (long long) plane, layout, s);
     if (rc != AWPU_OK) return rc;
     h->timing = false;
-    rc = launch(h, h->d_band, batch, d_power, s, layout);
+    for (int b = 0; b < bands.n && rc == AWPU_OK; b++) rc = launch(h, h->d_band + b * plane, batch, d_power + b * power_plane, s, layout);
     h->timing = timed;
     if (rc == AWPU_OK && timed) AWPU_HIP_TRY(hipEventRecord(h->ev_end, s));
     return rc;
+}
+
+// The refusals of a spectral call (awpu_hip_spectral.h) that read the handle, in the header's order, and its bands as a set.  (The
+// missing table and the history rule come from check_ready and the caller: they need the prepared handle.)
+int check_spectral(awpu_hip *h, const awpu_spectral_t *sp, BandSet *bands) {
+    if (!h) return invalid("null handle");
+    if (const char *why = awpu::spectral_refusal(sp)) return invalid(why);
+    if (is_group(h)) return fail(AWPU_ERR_STATE, "a device group takes no bands");
+    if (h->in_flight) return fail(AWPU_ERR_STATE, "an awpu_hip_process_async call is in flight on this handle: awpu_hip_wait first");
+    if (!h->band.empty()) return fail(AWPU_ERR_STATE, "the handle has a band of its own: clear it (awpu_hip_set_band) before a spectral call");
+    bands->n = sp->n_bands;
+    for (int b = 0; b < sp->n_bands; b++) bands->taps[b] = sp->taps[b], bands->coef[b] = sp->coef[b];
+    return AWPU_OK;
 }
 
 }  // namespace awpu::host
@@ -938,6 +981,36 @@ int awpu_hip_process_device(awpu_hip_t *h, const float *d_frames, int32_t batch,
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
     TimingOff untimed(h);  // asynchronous path: the caller times its own stream
     return band_sweep(h, d_frames, (long long) h->cfg.n_streams * h->cfg.hist, h->cfg.hist, h->wstart, batch, d_power, s, kFull);
+}
+
+int awpu_hip_process_bands(awpu_hip_t *h, const float *frames, int32_t batch, const awpu_spectral_t *sp, float *power) {
+    AWPU_CTX(h);
+    if (!h) return invalid("null handle");
+    if (!frames || !power) return invalid("null argument");
+    BandSet bands;
+    int rc = check_spectral(h, sp, &bands);
+    if (rc != AWPU_OK) return rc;
+    rc = enqueue_host_process(h, frames, batch, &bands);
+    if (rc != AWPU_OK) return rc;
+    rc = enqueue_power_to_host(h, batch * bands.n, power, (size_t) h->cfg.pixel_count);
+    if (rc != AWPU_OK) return rc;
+    return wait_and_time(h);
+}
+
+int awpu_hip_process_bands_device(awpu_hip_t *h, const float *d_frames, int32_t batch, const awpu_spectral_t *sp, float *d_power, void *stream) {
+    AWPU_CTX(h);
+    if (!h) return invalid("null handle");
+    if (!d_frames || !d_power) return invalid("null argument");
+    BandSet bands;
+    int rc = check_spectral(h, sp, &bands);
+    if (rc != AWPU_OK) return rc;
+    rc = check_ready(h, batch);
+    if (rc != AWPU_OK) return rc;
+    if (bands.max_taps() - 1 > h->wstart) return fail(AWPU_ERR_RANGE, kBandHistory);
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+    TimingOff untimed(h);  // asynchronous path: the caller times its own stream
+    return band_sweep(h, bands, d_frames, (long long) h->cfg.n_streams * h->cfg.hist, h->cfg.hist, h->wstart, batch, d_power,
+                      (long long) batch * h->cfg.pixel_count, s, kFull);
 }
 
 int awpu_hip_process_device_sums(awpu_hip_t *h, const float *d_frames, int32_t batch, float *d_power, float *d_sums, void *stream) {

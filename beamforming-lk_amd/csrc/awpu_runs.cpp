@@ -1,11 +1,12 @@
 // awpu_runs.cpp -- runs of consecutive blocks of a recording through one pipeline of pieces: a heatmap of every block
 // (include/awpu_hip_blocks.h), the beam audio of every block (awpu_hip_listen.h), display images of every Nth block
-// (awpu_hip_watch.h), the sources in every Nth block (awpu_hip_find.h) and their distances (awpu_hip_focus.h).  The handle and what is called here out of awpu_hip.cpp and awpu_sweep.cpp: awpu_handle.h.
+// (awpu_hip_watch.h) -- in up to four bands at once (awpu_hip_spectral.h) --, the sources in every Nth block (awpu_hip_find.h) and their distances (awpu_hip_focus.h).  The handle and what is called here out of awpu_hip.cpp and awpu_sweep.cpp: awpu_handle.h.
 #include "awpu_handle.h"
 #include "awpu_hip_blocks.h"
 #include "awpu_hip_find.h"
 #include "awpu_hip_focus.h"
 #include "awpu_hip_listen.h"
+#include "awpu_hip_spectral.h"
 #include "awpu_hip_watch.h"
 
 #include <algorithm>
@@ -16,6 +17,8 @@
 #include "block_kernels.h"
 #include "find_kernels.h"
 #include "find_rule.h"
+#include "spectral_kernels.h"
+#include "spectral_rule.h"
 #include "watch_kernels.h"
 
 using namespace awpu::host;
@@ -96,8 +99,10 @@ void parallel_copy(void *dst, const void *src, size_t bytes) {
 //   3. up waits ev_blk_cut[b] (i >= 2, swept runs) and ev_listened[b] (i >= 2, listened runs): piece i-2 has read blk_hist.d[b]
 //   4. the history is formed on up, ev_blk_hist[b] behind it; sw waits it, and li where that is another stream
 //   5. the cut on sw, then ev_blk_cut[b]; ev_begin at piece 0; the sweep with the handle's own event bracket off; what the
-//      consumer shows of the powers; ev_blk_swept[b].  On a handle with a band (awpu_hip_band.h) the cut is the band's pre-pass,
-//      which cuts and filters in one (band_cut), and ev_begin stands in front of it; nothing else of a run sees the band
+//      consumer shows of the powers; ev_blk_swept[b].  With bands -- the handle's own (awpu_hip_band.h) or a spectral run's
+//      (awpu_hip_spectral.h) -- the cut is their pre-pass, which cuts and filters in one (band_cut) into a plane of d_blk_frames
+//      per band, and ev_begin stands in front of it; then one sweep per band, each the launch() of the band-by-band run, into a
+//      plane of the powers per band; nothing else of a run sees the bands
 //   6. the listen kernels on li, ev_listened[b] behind them
 //   7. piece i-1's results into pinned memory on up, behind ev_blk_swept / ev_listened, ev_blk_out / ev_listen_out behind them
 //      (so piece i-2's way back is queued on up before piece i's history is formed: listen_out.d[b] is free when 6 writes it)
@@ -120,7 +125,8 @@ struct Consumer {
     bool sweep = true;              // false: nothing is cut, swept or timed (listening without heatmaps)
     bool tail = false;              // a Piece::tail follows the last piece
     bool listens = false;           // steps 6, and 7 and 8 for what was heard
-    float *power = nullptr;         // [n_items][pixel_count]: host memory in the host forms, device memory in the device form; or null
+    float *power = nullptr;         // [n_items][pixel_count], per band: host memory in the host forms, device memory in the device form; or null
+    BandSet bands;                  // in front of the sweeps: the handle's own band unless check() has set a spectral run's
     int pitch = 0;                  // floats per stream of a history (set by ensure)
 
     virtual int check() { return AWPU_OK; }  // refusals of its own, before the handle is made ready
@@ -129,7 +135,8 @@ struct Consumer {
     virtual int staged_blocks(const Piece &p) = 0;              // host forms: stages the input in blk_in.h[b]; the blocks to upload
     virtual int history(const Piece &p, hipStream_t s) = 0;     // blk_hist.d[b], out of blk_in.d[b] (host forms) or the caller's samples
     virtual int cut(const Piece &p, hipStream_t s) = 0;         // its snapshots' windows into d_blk_frames
-    virtual int show(const Piece &, float *, hipStream_t) { return AWPU_OK; }  // behind the sweep into d_pow, before ev_blk_swept
+    // behind the sweeps into d_pow (band b's powers `plane` floats behind band b-1's), before ev_blk_swept
+    virtual int show(const Piece &, float *, long long, hipStream_t) { return AWPU_OK; }
     virtual int listen(const Piece &, hipStream_t) { return AWPU_OK; }
     virtual int fetch_shown(const Piece &, hipStream_t) { return AWPU_OK; }    // host forms: besides the powers, into pinned memory
     virtual int deliver_shown(const Piece &) { return AWPU_OK; }               // ... and on to the caller
@@ -146,21 +153,21 @@ float *hist_of(awpu_hip *h, int b) { return reinterpret_cast<float *>(h->blk_his
 
 // the buffers every run needs for pieces of `piece` frames whose history and staging hold hist_blocks / in_blocks blocks (and,
 // for the host forms, the second stream and the events)
-int ensure_run_buffers(awpu_hip *h, const BlockRun &src, int piece, int width, bool sweep, int hist_blocks, int in_blocks) {
+int ensure_run_buffers(awpu_hip *h, const BlockRun &src, int piece, int width, bool sweep, int hist_blocks, int in_blocks, int planes) {
     const size_t S = (size_t) h->cfg.n_streams, P = (size_t) h->cfg.pixel_count;
     int rc = h->blk_hist.ensure(S * (awpu::kBlockPrefix + (size_t) awpu::kSamples * hist_blocks) * sizeof(float), false);
     if (rc != AWPU_OK) return rc;
-    const size_t frames_floats = sweep ? S * width * (size_t) piece : 0;  // (a listen run without heatmaps cuts no window)
+    const size_t frames_floats = sweep ? S * width * (size_t) piece * planes : 0;  // (a listen run without heatmaps cuts no window)
     if (rc = h->d_blk_frames.ensure(frames_floats); rc != AWPU_OK) return rc;
     if (rc = h->ev_blk_ring.ensure(); rc != AWPU_OK) return rc;
     if (src.device) return AWPU_OK;
     rc = h->blk_in.ensure((size_t) awpu::kSamples * in_blocks * (src.wire ? (size_t) AWPU_DATAGRAM_BYTES : S * sizeof(float)), true);
-    if (rc == AWPU_OK) rc = h->blk_out.ensure(sweep ? piece * P * sizeof(float) : 0, true, false);
+    if (rc == AWPU_OK) rc = h->blk_out.ensure(sweep ? piece * P * planes * sizeof(float) : 0, true, false);
     if (rc == AWPU_OK) rc = h->copy_stream.ensure();
     for (auto *pair : {h->ev_blk_in, h->ev_blk_hist, h->ev_blk_cut, h->ev_blk_swept, h->ev_blk_out})
         for (int b = 0; b < 2 && rc == AWPU_OK; b++) rc = pair[b].ensure();
     if (rc != AWPU_OK) return rc;
-    return sweep ? ensure_power(h, 2 * piece * P) : AWPU_OK;  // two pieces' powers: one swept, one on its way back
+    return sweep ? ensure_power(h, 2 * piece * P * planes) : AWPU_OK;  // two pieces' powers: one swept, one on its way back
 }
 
 // the run; the host forms are synchronous, the device form runs on `user` (NULL = h->stream)
@@ -173,9 +180,12 @@ int run_pieces(awpu_hip *h, const BlockRun &src, hipStream_t user, Consumer &c) 
     int rc = c.check();
     if (rc != AWPU_OK) return rc;
     const int chunk = std::max(1, std::min<int>(c.n_items, cfg.max_batch));
+    if (c.bands.n == 0) c.bands = own_band(h);
+    const int planes = c.bands.planes();
     if (c.sweep) {
         rc = check_ready(h, chunk);
         if (rc != AWPU_OK) return rc;
+        if (c.bands.max_taps() - 1 > h->wstart) return fail(AWPU_ERR_RANGE, kBandHistory);
     } else {
         AWPU_HIP_TRY(hipSetDevice(cfg.device));
     }
@@ -206,8 +216,8 @@ int run_pieces(awpu_hip *h, const BlockRun &src, hipStream_t user, Consumer &c) 
     const auto fetch = [&](const Piece &p) -> int {
         if (c.sweep) {
             AWPU_HIP_TRY(hipStreamWaitEvent(up, h->ev_blk_swept[p.b], 0));
-            if (c.power)
-                AWPU_HIP_TRY(hipMemcpyAsync(h->blk_out.h[p.b], h->d_power + (size_t) p.b * piece_max * P, (size_t) p.n * P * sizeof(float),
+            if (c.power)  // (a piece's band planes lie back to back: p.n * P floats each)
+                AWPU_HIP_TRY(hipMemcpyAsync(h->blk_out.h[p.b], h->d_power + (size_t) p.b * piece_max * P * planes, (size_t) p.n * P * planes * sizeof(float),
                                             hipMemcpyDeviceToHost, up));
             if (const int frc = c.fetch_shown(p, up)) return frc;
             AWPU_HIP_TRY(hipEventRecord(h->ev_blk_out[p.b], up));
@@ -222,7 +232,9 @@ int run_pieces(awpu_hip *h, const BlockRun &src, hipStream_t user, Consumer &c) 
     const auto deliver = [&](const Piece &p) -> int {
         if (c.sweep) {
             AWPU_HIP_TRY(hipEventSynchronize(h->ev_blk_out[p.b]));
-            if (c.power) std::memcpy(c.power + (size_t) p.first * P, h->blk_out.h[p.b], (size_t) p.n * P * sizeof(float));
+            for (int k = 0; c.power && k < planes; k++)
+                std::memcpy(c.power + ((size_t) k * c.n_items + p.first) * P, reinterpret_cast<const float *>(h->blk_out.h[p.b].get()) + (size_t) k * p.n * P,
+                            (size_t) p.n * P * sizeof(float));
             if (const int drc = c.deliver_shown(p)) return drc;
         }
         if (c.listens) {
@@ -258,17 +270,21 @@ int run_pieces(awpu_hip *h, const BlockRun &src, hipStream_t user, Consumer &c) 
                 if (li != sw) AWPU_HIP_TRY(hipStreamWaitEvent(li, h->ev_blk_hist[b], 0));
             }
             if (c.sweep && !p.tail) {
-                const bool banded = !h->band.empty();  // the cut is then the band's pre-pass, and inside the timed span
+                const bool banded = c.bands.n > 0;  // the cut is then the bands' pre-pass, and inside the timed span
                 if (time_it && i == 0 && banded) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, sw));
                 brc = c.cut(p, sw);
                 if (brc != AWPU_OK) return brc;
                 if (host) AWPU_HIP_TRY(hipEventRecord(h->ev_blk_cut[b], sw));
                 if (time_it && i == 0 && !banded) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, sw));
-                float *d_pow = host ? h->d_power + (size_t) b * piece_max * P : (c.power ? c.power + (size_t) p.first * P : h->d_power);
+                // band k's powers: in the caller's plane k (device form with powers), else p.n * P floats behind band k-1's
+                float *d_pow = host ? h->d_power + (size_t) b * piece_max * P * planes : (c.power ? c.power + (size_t) p.first * P : h->d_power);
+                const long long pow_plane = !host && c.power ? (long long) c.n_items * P : (long long) p.n * P;
+                const size_t frames_plane = (size_t) S * (compact ? h->compact_hist : AWPU_HIST) * p.n;
                 h->timing = false;
-                brc = launch(h, h->d_blk_frames, p.n, d_pow, sw, compact ? kCompact : kFull);
+                for (int k = 0; k < planes && brc == AWPU_OK; k++)
+                    brc = launch(h, h->d_blk_frames + k * frames_plane, p.n, d_pow + k * pow_plane, sw, compact ? kCompact : kFull);
                 h->timing = time_it;
-                if (brc == AWPU_OK) brc = c.show(p, d_pow, sw);
+                if (brc == AWPU_OK) brc = c.show(p, d_pow, pow_plane, sw);
                 if (brc != AWPU_OK) return brc;
                 if (host) AWPU_HIP_TRY(hipEventRecord(h->ev_blk_swept[b], sw));
             }
@@ -378,7 +394,7 @@ struct BlockPieces final : Consumer {
         lo = lo_, width = width_;
         pitch = awpu::kBlockPrefix + awpu::kSamples * piece_max;
         prev = h->d_ring + h->ring_pos + awpu::kSamples;  // the last 768 samples of the current snapshot
-        int rc = ensure_run_buffers(h, src, piece_max, width, sweep, piece_max, piece_max);
+        int rc = ensure_run_buffers(h, src, piece_max, width, sweep, piece_max, piece_max, bands.planes());
         if (rc != AWPU_OK || !ls) return rc;
         rc = ensure_track_index(h);
         if (rc != AWPU_OK) return rc;
@@ -416,7 +432,7 @@ struct BlockPieces final : Consumer {
         return AWPU_OK;
     }
     int cut(const Piece &p, hipStream_t s) override {
-        if (!h->band.empty()) return band_cut(h, hist_of(h, p.b), awpu::kSamples, pitch, h->wstart, p.n, h->d_blk_frames, h->compact_hist > 0 ? kCompact : kFull, s);
+        if (bands.n) return band_cut(h, bands, hist_of(h, p.b), awpu::kSamples, pitch, h->wstart, p.n, h->d_blk_frames, (long long) h->cfg.n_streams * width * p.n, h->compact_hist > 0 ? kCompact : kFull, s);
         AWPU_HIP_TRY(awpu::launch_cut_windows(hist_of(h, p.b), pitch, h->cfg.n_streams, p.n, lo, width, h->d_blk_frames, s));
         return AWPU_OK;
     }
@@ -546,7 +562,7 @@ void stage_watch(awpu_hip *h, const BlockRun &src, int b0, int every, int q, int
     });
 }
 
-struct WatchPieces final : Consumer {
+struct WatchPieces : Consumer {
     awpu_hip *const h;
     const BlockRun &src;
     const WatchRun &wr;
@@ -591,8 +607,8 @@ struct WatchPieces final : Consumer {
         pitch = awpu::kSamples * slots_max;
         small_off = align16(sizeof(float) * piece_max), big_off = small_off + align16((size_t) piece_max * P);
         snapshot = h->d_ring + h->ring_pos;
-        int rc = ensure_run_buffers(h, src, piece_max, width, true, slots_max - 3, slots_max);
-        if (rc == AWPU_OK && !host && !wr.power) rc = ensure_power(h, (size_t) piece_max * P);
+        int rc = ensure_run_buffers(h, src, piece_max, width, true, slots_max - 3, slots_max, bands.planes());
+        if (rc == AWPU_OK && !host && !wr.power) rc = ensure_power(h, (size_t) piece_max * P * bands.planes());
         if (rc == AWPU_OK && want_small) rc = h->watch.ensure(big_off + (host && wr.big ? (size_t) piece_max * big_bytes : 0), host);
         if (rc == AWPU_OK && wr.big) rc = ensure_taps(h, w.rows, w.cols, w.out_rows, w.out_cols, sw);
         sources_off = align16(sizeof(int32_t) * piece_max);
@@ -628,7 +644,7 @@ struct WatchPieces final : Consumer {
         return AWPU_OK;
     }
     int cut(const Piece &p, hipStream_t s) override {
-        if (!h->band.empty()) return band_cut(h, hist_of(h, p.b), awpu::kSamples * m, pitch, h->wstart, p.n, h->d_blk_frames, h->compact_hist > 0 ? kCompact : kFull, s);
+        if (bands.n) return band_cut(h, bands, hist_of(h, p.b), awpu::kSamples * m, pitch, h->wstart, p.n, h->d_blk_frames, (long long) S * width * p.n, h->compact_hist > 0 ? kCompact : kFull, s);
         AWPU_HIP_TRY(awpu::launch_watch_cut(hist_of(h, p.b), pitch, S, p.n, awpu::kSamples * m, lo, width, h->d_blk_frames, s));
         return AWPU_OK;
     }
@@ -661,7 +677,7 @@ struct WatchPieces final : Consumer {
         }
         return AWPU_OK;
     }
-    int show(const Piece &p, float *d_pow, hipStream_t s) override {
+    int show(const Piece &p, float *d_pow, long long, hipStream_t s) override {
         if (fr) {
             unsigned char *out = h->find_out.d[p.b];
             awpu_source_t *d_sources = host ? reinterpret_cast<awpu_source_t *>(out + sources_off) : fr->sources + (size_t) p.first * fr->f.max_sources;
@@ -704,27 +720,111 @@ struct WatchPieces final : Consumer {
     int ring_from(const Piece &last) override { return last.tail ? 0 : awpu::kSamples * (awpu::watch_slots(w.every, last.n) - 4); }
 };
 
-// the checks of a watch call that read no handle; then the run
-int watch_run(awpu_hip *h, const BlockRun &src, int n_blocks, const awpu_watch_t *w, uint8_t *image, uint8_t *big, float *power, hipStream_t user,
-              const FindRun *find = nullptr) {
+// the checks of a watch call that read no handle (any_output: something is asked for; big: a large image is), and what it shows
+int check_watch(const awpu_watch_t *w, bool any_output, bool big, int n_blocks, WatchRun *wr) {
     if (!w) return invalid("null argument");
-    if (!image && !big && !power && !find) return invalid("no output asked for");
+    if (!any_output) return invalid("no output asked for");
     if (w->every < 1 || w->every > AWPU_WATCH_MAX_EVERY) return invalid("every outside [1, 1024]");
     if (w->first < 0) return invalid("first below 0");
     if (w->flip != 0 && w->flip != 1) return invalid("flip is 0 or 1");
     if (w->rows < 1 || w->cols < 1) return invalid("rows and cols must be positive");
     if (big && (w->out_rows < w->rows || w->out_cols < w->cols)) return invalid("upscale only: out >= in");
     if (big && w->cols > AWPU_WATCH_MAX_COLS) return invalid("compact image wider than AWPU_WATCH_MAX_COLS");
-    WatchRun wr;
-    wr.w = *w;
+    wr->w = *w;
     int32_t next_first = 0;
-    if (int rc = awpu_hip_watch_count(n_blocks, w->first, w->every, &wr.n_frames, &next_first)) return rc;
+    return awpu_hip_watch_count(n_blocks, w->first, w->every, &wr->n_frames, &next_first);
+}
+
+// those checks; then the run
+int watch_run(awpu_hip *h, const BlockRun &src, int n_blocks, const awpu_watch_t *w, uint8_t *image, uint8_t *big, float *power, hipStream_t user,
+              const FindRun *find = nullptr) {
+    WatchRun wr;
+    if (int rc = check_watch(w, image || big || power || find, big != nullptr, n_blocks, &wr)) return rc;
     wr.image = image;
     wr.big = big;
     wr.power = power;
     wr.find = find;
     AWPU_CTX(h);
     WatchPieces c(h, src, n_blocks, wr);
+    return run_pieces(h, src, user, c);
+}
+
+// ---- spectral runs (awpu_hip_spectral.h; kernels in spectral_kernels.hip) ------------------------------------------------------
+// A watch run with a set of bands of its own in front of the sweeps (run_pieces sweeps a piece once per band) and another display
+// step: launch_spectral_compose on the piece's band powers, then the large three-byte image.  Pieces, histories, the ring: the
+// watch run's.
+
+// what a spectral call adds to a watch run; the outputs are host memory in the host forms, device memory in the device form
+struct SpectralRun {
+    awpu_spectral_t sp{};
+    uint8_t *image = nullptr, *big = nullptr, *dominant = nullptr;
+};
+
+struct SpectralPieces final : WatchPieces {
+    const SpectralRun &sr;
+    const bool want_rgb;     // the three-byte image: asked for, or what the large one is made of
+    const size_t big3_bytes;
+    awpu::SpectralShow shown{};
+    size_t image_off = 0, dominant_off = 0, big3_off = 0;  // in a spectral buffer: the band maxima, the images, the dominant bands, the large images
+
+    SpectralPieces(awpu_hip *h_, const BlockRun &src_, int n_blocks_, const WatchRun &wr_, const SpectralRun &sr_)
+        : WatchPieces(h_, src_, n_blocks_, wr_), sr(sr_), want_rgb(sr_.image || sr_.big), big3_bytes((size_t) wr_.w.out_rows * wr_.w.out_cols * 3) {
+        shown.n_bands = sr.sp.n_bands, shown.scale = sr.sp.scale;
+        for (int c = 0; c < 3; c++) shown.channel[c] = sr.sp.channel[c];
+    }
+    int check() override {
+        if (const int rc = check_spectral(h, &sr.sp, &bands)) return rc;
+        return WatchPieces::check();
+    }
+    int ensure(int piece_max, int lo_, int width_, hipStream_t sw) override {
+        int rc = WatchPieces::ensure(piece_max, lo_, width_, sw);
+        image_off = align16(sizeof(float) * AWPU_SPECTRAL_MAX_BANDS * piece_max);
+        dominant_off = image_off + align16((size_t) piece_max * P * 3);
+        big3_off = dominant_off + align16((size_t) piece_max * P);
+        if (rc == AWPU_OK && (want_rgb || sr.dominant)) rc = h->spectral.ensure(big3_off + (host && sr.big ? (size_t) piece_max * big3_bytes : 0), host);
+        if (rc == AWPU_OK && sr.big) rc = ensure_taps(h, w.rows, w.cols, w.out_rows, w.out_cols, sw);
+        return rc;
+    }
+    int show(const Piece &p, float *d_pow, long long plane, hipStream_t s) override {
+        if (!want_rgb && !sr.dominant) return AWPU_OK;
+        uint8_t *scratch = h->spectral.d[host ? p.b : 0];
+        uint8_t *d_image = !want_rgb ? nullptr : (host || !sr.image ? scratch + image_off : sr.image + (size_t) p.first * P * 3);
+        uint8_t *d_dominant = !sr.dominant ? nullptr : (host ? scratch + dominant_off : sr.dominant + (size_t) p.first * P);
+        AWPU_HIP_TRY(awpu::launch_spectral_compose(d_pow, plane, (int) P, p.n, shown, reinterpret_cast<float *>(scratch), d_image, d_dominant, s));
+        if (sr.big)
+            AWPU_HIP_TRY(awpu::launch_spectral_upscale(d_image, w.rows, w.cols, p.n, h->d_taps, w.flip != 0,
+                                                       host ? scratch + big3_off : sr.big + (size_t) p.first * big3_bytes, w.out_rows, w.out_cols, s));
+        return AWPU_OK;
+    }
+    int fetch_shown(const Piece &p, hipStream_t s) override {
+        uint8_t *to = h->spectral.h[p.b], *from = h->spectral.d[p.b];
+        if (sr.image) AWPU_HIP_TRY(hipMemcpyAsync(to + image_off, from + image_off, (size_t) p.n * P * 3, hipMemcpyDeviceToHost, s));
+        if (sr.dominant) AWPU_HIP_TRY(hipMemcpyAsync(to + dominant_off, from + dominant_off, (size_t) p.n * P, hipMemcpyDeviceToHost, s));
+        if (sr.big) AWPU_HIP_TRY(hipMemcpyAsync(to + big3_off, from + big3_off, (size_t) p.n * big3_bytes, hipMemcpyDeviceToHost, s));
+        return AWPU_OK;
+    }
+    int deliver_shown(const Piece &p) override {
+        const uint8_t *from = h->spectral.h[p.b];
+        if (sr.image) std::memcpy(sr.image + (size_t) p.first * P * 3, from + image_off, (size_t) p.n * P * 3);
+        if (sr.dominant) std::memcpy(sr.dominant + (size_t) p.first * P, from + dominant_off, (size_t) p.n * P);
+        if (sr.big) parallel_copy(sr.big + (size_t) p.first * big3_bytes, from + big3_off, (size_t) p.n * big3_bytes);
+        return AWPU_OK;
+    }
+};
+
+// the checks of a spectral call that read no handle; then the run
+int spectral_run(awpu_hip *h, const BlockRun &src, int n_blocks, const awpu_watch_t *w, const awpu_spectral_t *sp, uint8_t *image, uint8_t *big,
+                 uint8_t *dominant, float *power, hipStream_t user) {
+    if (const char *why = awpu::spectral_refusal(sp)) return invalid(why);
+    WatchRun wr;
+    if (int rc = check_watch(w, image || big || dominant || power, big != nullptr, n_blocks, &wr)) return rc;
+    if (w->d_colormap) return invalid("a spectral image has its colours from the bands: no colour table");
+    wr.power = power;
+    SpectralRun sr;
+    sr.sp = *sp;
+    sr.image = image, sr.big = big, sr.dominant = dominant;
+    AWPU_CTX(h);
+    SpectralPieces c(h, src, n_blocks, wr, sr);
     return run_pieces(h, src, user, c);
 }
 
@@ -827,6 +927,28 @@ int awpu_hip_watch_samples_device(awpu_hip_t *h, const float *d_samples, int64_t
     BlockRun src;
     if (int rc = sample_source(h, d_samples, pitch, n_blocks, true, &src)) return rc;
     return watch_run(h, src, n_blocks, w, d_image, d_big_image, d_power, static_cast<hipStream_t>(stream));
+}
+
+int awpu_hip_spectral_blocks(awpu_hip_t *h, const void *datagrams, int32_t stride_bytes, int32_t n_blocks, const awpu_watch_t *w,
+                             const awpu_spectral_t *sp, uint8_t *image, uint8_t *big_image, uint8_t *dominant, float *power) {
+    BlockRun src;
+    if (int rc = wire_source(h, datagrams, stride_bytes, n_blocks, &src)) return rc;
+    return spectral_run(h, src, n_blocks, w, sp, image, big_image, dominant, power, nullptr);
+}
+
+int awpu_hip_spectral_samples(awpu_hip_t *h, const float *samples, int64_t pitch, int32_t n_blocks, const awpu_watch_t *w,
+                              const awpu_spectral_t *sp, uint8_t *image, uint8_t *big_image, uint8_t *dominant, float *power) {
+    BlockRun src;
+    if (int rc = sample_source(h, samples, pitch, n_blocks, false, &src)) return rc;
+    return spectral_run(h, src, n_blocks, w, sp, image, big_image, dominant, power, nullptr);
+}
+
+int awpu_hip_spectral_samples_device(awpu_hip_t *h, const float *d_samples, int64_t pitch, int32_t n_blocks, const awpu_watch_t *w,
+                                     const awpu_spectral_t *sp, uint8_t *d_image, uint8_t *d_big_image, uint8_t *d_dominant,
+                                     float *d_power, void *stream) {
+    BlockRun src;
+    if (int rc = sample_source(h, d_samples, pitch, n_blocks, true, &src)) return rc;
+    return spectral_run(h, src, n_blocks, w, sp, d_image, d_big_image, d_dominant, d_power, static_cast<hipStream_t>(stream));
 }
 
 int awpu_hip_find_peaks_device(awpu_hip_t *h, const float *d_power, int32_t n_frames, const awpu_find_t *f, awpu_source_t *d_sources,

@@ -9,6 +9,12 @@ reader (counter gaps reported, not repaired).
 --band LO:HI[:TAPS] (Hz; 63 taps unless given) limits the heatmaps to a band, e.g. --band 6375:9000: the video shows the band
 (Engine.set_band with binding.band_design's coefficients, include/awpu_hip_band.h).
 
+--bands LO:HI[:TAPS],LO:HI[:TAPS],LO:HI[:TAPS] (one to three entries, each as --band takes it) writes the colour-by-frequency
+video instead: every band is swept from one pass over the capture (Engine.spectral_blocks, include/awpu_hip_spectral.h) and shown
+in a colour of its own -- the lowest band red, the next green, the highest blue; the file's pixels are B, G, R, so byte 0 shows
+the highest band --, each level scaled by one maximum per frame over the shown bands (--band-scale per-band: by its band's own).
+The colour table plays no part.  --bands together with --band is an error.
+
 --focus METRES focuses the delay table on points METRES away instead of on plane waves (binding.build_focus_table,
 include/awpu_hip_focus.h): a large array in a room is in its sources' near field, where a plane-wave table blurs them.
 
@@ -163,6 +169,16 @@ def read_avi(path):
     return np.stack(frames) if frames else np.zeros((0, height, width, 3), np.uint8), rate, scale
 
 
+def bands_of_text(binding, text: str):
+    """--bands' text -> (the bands' coefficients, lowest band first; the band shown in byte 0, 1, 2 of a B G R pixel)."""
+    entries = [e for e in text.split(",")]
+    if not 1 <= len(entries) <= 3:
+        raise ValueError(f"bands '{text}': one to three LO:HI[:TAPS] entries, separated by commas")
+    entries.sort(key=lambda e: float(e.split(":")[0]))  # (band_from_text judges the entry itself)
+    bands = [binding.band_from_text(e) for e in entries]
+    return bands, tuple(2 - c if 2 - c < len(bands) else -1 for c in range(3))  # red (byte 2) = band 0, green = band 1, blue = band 2
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("pcap")
@@ -180,12 +196,16 @@ def main(argv=None) -> int:
     ap.add_argument("--raw", action="store_true", help="headerless BGR24 frames into OUT.bgr instead of AVI parts")
     ap.add_argument("--out", default="heatmap", help="output prefix")
     ap.add_argument("--band", default=None, metavar="LO:HI[:TAPS]", help="limit the heatmaps to LO .. HI Hz (an FIR band of TAPS taps, 63 unless given)")
+    ap.add_argument("--bands", default=None, metavar="LO:HI[:TAPS],...", help="one to three bands, each in a colour of its own: lowest red, next green, highest blue")
+    ap.add_argument("--band-scale", default="common", choices=("common", "per-band"), help="--bands: one maximum per frame over the bands, or each band's own")
     ap.add_argument("--focus", type=float, default=None, metavar="METRES",
                     help="focus the delay table on points METRES away instead of on plane waves (include/awpu_hip_focus.h)")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     if a.every < 1 or a.chunk < 1 or a.size < a.cols:
         ap.error("--every and --chunk are positive, --size is at least --cols")
+    if a.band and a.bands:
+        ap.error("--bands together with --band: one band through the colour table, or several bands as colours")
 
     sys.path.insert(0, str(Path(__file__).resolve().parent))
     from pcap_heatmaps import blocks_of, read_pcap_payloads
@@ -213,6 +233,9 @@ def main(argv=None) -> int:
         print(f"{n} mics: the wire carries 256 streams per datagram")
         return 1
     table = torch.from_numpy(gray_table() if a.gray else jet_table()).to(f"cuda:{a.device}")
+    if a.bands:
+        bands, channel = bands_of_text(pkg.binding, a.bands)
+        band_scale = pkg.binding.SPECTRAL_SCALE_COMMON if a.band_scale == "common" else pkg.binding.SPECTRAL_SCALE_PER_BAND
     rate, scale = frame_rate(a.every)
     shown, first, block_bytes, res = 0, 0, 256 * 1032, None
     raw = open(f"{a.out}.bgr", "wb") if a.raw else None
@@ -224,9 +247,13 @@ def main(argv=None) -> int:
             eng.set_band(pkg.binding.band_from_text(a.band))
         for b in range(0, n_blocks, a.chunk):
             nb = min(a.chunk, n_blocks - b)
-            res = eng.watch_blocks(wire[b * block_bytes: (b + nb) * block_bytes], a.cols, a.cols, first=first, every=a.every,
-                                   out_rows=a.size, out_cols=a.size, d_colormap_ptr=table.data_ptr(), flip=a.flip, want_image=False,
-                                   out=res)  # (the frames of the chunk before are in the file)
+            if a.bands:
+                res = eng.spectral_blocks(wire[b * block_bytes: (b + nb) * block_bytes], a.cols, a.cols, bands, channel, band_scale, first=first,
+                                          every=a.every, out_rows=a.size, out_cols=a.size, flip=a.flip, want_image=False, want_dominant=False)
+            else:
+                res = eng.watch_blocks(wire[b * block_bytes: (b + nb) * block_bytes], a.cols, a.cols, first=first, every=a.every,
+                                       out_rows=a.size, out_cols=a.size, d_colormap_ptr=table.data_ptr(), flip=a.flip, want_image=False,
+                                       out=res)  # (the frames of the chunk before are in the file)
             first = res.next_first
             for frame in res.big:
                 raw.write(frame.tobytes()) if raw else writer.write(frame)
