@@ -318,6 +318,31 @@ _FOCUS_SIGNATURES = {
 }
 FOCUS_SYMBOLS = tuple(_FOCUS_SIGNATURES)
 
+# exposure: the entry points of include/awpu_hip_expose.h
+EXPOSE_MEAN, EXPOSE_PEAK = 0, 1
+
+
+class Expose(C.Structure):
+    """awpu_expose_t (include/awpu_hip_expose.h)."""
+    _fields_ = [
+        ("length", C.c_int32),
+        ("mode", C.c_int32),
+    ]
+
+
+_EXPOSE_TAIL = [*_WATCH_TAIL, C.POINTER(Expose), C.POINTER(Find)]  # n_blocks, w, e, f
+_EXPOSE_SIGNATURES = {
+    "awpu_hip_expose_count": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _i32p, _i32p, _i32p, _i32p, _i32p]),
+    "awpu_hip_expose_rows": (C.c_int, [_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Expose), _f32p, _f32p]),
+    "awpu_hip_expose_rows_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Expose), C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
+    "awpu_hip_expose_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, *_EXPOSE_TAIL, _f32p, _u8p, _u8p, _f32p, C.c_void_p, C.c_void_p]),
+    "awpu_hip_expose_samples": (C.c_int, [C.c_void_p, _f32p, C.c_int64, *_EXPOSE_TAIL, _f32p, _u8p, _u8p, _f32p, C.c_void_p, C.c_void_p]),
+    "awpu_hip_expose_samples_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, *_EXPOSE_TAIL, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+EXPOSE_SYMBOLS = tuple(_EXPOSE_SIGNATURES)
+
 # numpy view of awpu_range_t: what range_pick, Engine.range and Engine.locate_* return (unused entries: index -1)
 RANGE_DTYPE = np.dtype([("index", "<i4"), ("power", "<f4"), ("distance", "<f8")], align=True)
 assert RANGE_DTYPE.itemsize == C.sizeof(Range) == 16
@@ -355,7 +380,7 @@ def load(build: bool = True) -> C.CDLL:
     lib = C.CDLL(str(path))
     for name, (res, args) in list(_SIGNATURES.items()) + list(_TRACK_SIGNATURES.items()) + list(_BLOCK_SIGNATURES.items()) + \
             list(_LISTEN_SIGNATURES.items()) + list(_WATCH_SIGNATURES.items()) + list(_FIND_SIGNATURES.items()) + list(_BAND_SIGNATURES.items()) + \
-            list(_FOCUS_SIGNATURES.items()) + list(_SPECTRAL_SIGNATURES.items()):
+            list(_FOCUS_SIGNATURES.items()) + list(_SPECTRAL_SIGNATURES.items()) + list(_EXPOSE_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -652,6 +677,56 @@ def find_peaks(power: np.ndarray, rows: int, cols: int, radius: int = 2, max_sou
     _check(load().awpu_hip_find_peaks(_f32(power), len(power), C.byref(f), sources.ctypes.data_as(C.c_void_p),
                                       count.ctypes.data_as(C.c_void_p)), "awpu_hip_find_peaks")
     return FindResult(sources, count)
+
+
+class ExposeResult:
+    """What Engine.expose_* hand back: .image, .big, .power as a WatchResult has them -- of the exposed frames --, .sources and
+    .count as a FindResult has them or None, .next_first (the `first` of the call that continues the recording) and .carry: the
+    open window's row [pixels], to be passed as `carry` to that call.  Frame j is exposed over the `length` blocks that end with
+    block first + j * every of the call."""
+
+    def __init__(self, image, big, power, sources, count, next_first: int, carry):
+        self.image = image
+        self.big = big
+        self.power = power
+        self.sources = sources
+        self.count = count
+        self.next_first = next_first
+        self.carry = carry
+
+    def __getattr__(self, name):
+        if name in SOURCE_DTYPE.names and self.__dict__.get("sources") is not None:
+            return self.sources[name]
+        raise AttributeError(name)
+
+    def __len__(self):
+        return next(len(a) for a in (self.image, self.big, self.power, self.count) if a is not None)
+
+
+def expose_count(n_blocks: int, first: int, every: int, length: int):
+    """(n_frames, next_first, carry_in, carry_out, n_swept) of a call of n_blocks blocks exposed over `length` blocks a frame
+    (awpu_hip_expose_count)."""
+    out = [C.c_int32(0) for _ in range(5)]
+    _check(load().awpu_hip_expose_count(n_blocks, first, every, length, *[C.byref(v) for v in out]), "awpu_hip_expose_count")
+    return tuple(int(v.value) for v in out)
+
+
+def expose_rows(power: np.ndarray, first: int, every: int, length: int, mode: int = EXPOSE_MEAN, carry: Optional[np.ndarray] = None):
+    """The rule of include/awpu_hip_expose.h as executable C (awpu_hip_expose_rows): power [n_blocks, n_pixels], every block's row
+    -> (frames [n_frames, n_pixels], next_first).  `carry` [n_pixels] float32 is the open window: read where the first window began
+    before these rows, written in place where the last one ends behind them; it may be None where neither is the case."""
+    power = np.ascontiguousarray(power, np.float32)
+    if power.ndim != 2 or power.size == 0:
+        raise ValueError("power must be [n_blocks, n_pixels]")
+    if carry is not None and (carry.dtype != np.float32 or carry.shape != (power.shape[1],) or not carry.flags.c_contiguous):
+        raise ValueError("carry must be a contiguous float32 array [n_pixels]")
+    e = Expose(length, mode)
+    n_frames, next_first = watch_count(len(power), first, every) if every >= 1 and first >= 0 else (0, 0)
+    frames = np.empty((n_frames, power.shape[1]), np.float32)
+    _check(load().awpu_hip_expose_rows(_f32(power), len(power), power.shape[1], first, every, C.byref(e),
+                                       None if carry is None else _f32(carry), C.cast(C.c_void_p(frames.ctypes.data or 16), _f32p)),
+           "awpu_hip_expose_rows")
+    return frames, next_first
 
 
 def band_design(lo_hz: float, hi_hz: float, taps: int = 63, sample_rate: float = 48828.125) -> np.ndarray:
@@ -1099,6 +1174,93 @@ class Engine:
         _check(self._lib.awpu_hip_find_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, C.byref(w), C.byref(f),
                                                       C.c_void_p(d_sources_ptr), C.c_void_p(d_count_ptr), C.c_void_p(d_power_ptr),
                                                       C.c_void_p(stream)), "awpu_hip_find_samples_device")
+        return watch_count(n_blocks, first, every)[1]
+
+    def expose_rows_device(self, d_power_ptr: int, n_blocks: int, n_pixels: int, first: int, every: int, length: int, d_frames_ptr: int,
+                           mode: int = EXPOSE_MEAN, d_carry_ptr: int = 0, stream: int = 0) -> int:
+        """expose_rows on device pointers (power [n_blocks, n_pixels], frames [n_frames, n_pixels], carry [n_pixels] or 0) on
+        `stream`; asynchronous.  -> next_first (awpu_hip_expose_rows_device)."""
+        e = Expose(length, mode)
+        _check(self._lib.awpu_hip_expose_rows_device(self._h, C.c_void_p(d_power_ptr), n_blocks, n_pixels, first, every, C.byref(e),
+                                                     C.c_void_p(d_carry_ptr), C.c_void_p(d_frames_ptr), C.c_void_p(stream)),
+               "awpu_hip_expose_rows_device")
+        return watch_count(n_blocks, first, every)[1]
+
+    def _expose(self, call, where, n_blocks, rows, cols, first, every, length, mode, carry, out_rows, out_cols, d_colormap_ptr, flip,
+                want_image, want_power, find) -> ExposeResult:
+        n_frames, next_first = watch_count(n_blocks, first, every)
+        w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(d_colormap_ptr))
+        e = Expose(length, mode)
+        if carry is None:  # a recording's first call: silence before it
+            carry = np.zeros(self.pixel_count, np.float32)
+        elif carry.dtype != np.float32 or carry.shape != (self.pixel_count,) or not carry.flags.c_contiguous:
+            raise ValueError("carry must be a contiguous float32 array [pixels]")
+        image = np.empty((n_frames, rows, cols), np.uint8) if want_image else None
+        big = np.empty((n_frames, out_rows, out_cols, 3) if d_colormap_ptr else (n_frames, out_rows, out_cols), np.uint8) if out_rows else None
+        power = np.empty((n_frames, self.pixel_count), np.float32) if want_power else None
+        f = sources = count = None
+        if find is not None:
+            f = Find(rows, cols, find.get("radius", 2), find.get("max_sources", 4), find.get("min_power", 0.0), find.get("min_ratio", 0.0),
+                     find.get("fov_deg", 180.0))
+            sources = np.empty((n_frames, max(f.max_sources, 0)), SOURCE_DTYPE)
+            count = np.empty(n_frames, np.int32)
+        # (an output that is wanted is never a null pointer, not even with no frame to write)
+        ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data or 16)
+        u8 = lambda a: None if a is None else C.cast(ptr(a), _u8p)
+        _check(call(n_blocks, C.byref(w), C.byref(e), None if f is None else C.byref(f), _f32(carry), u8(image), u8(big),
+                    None if power is None else C.cast(ptr(power), _f32p), ptr(sources), ptr(count)), where)
+        return ExposeResult(image, big, power, sources, count, next_first, carry)
+
+    def expose_blocks(self, wire, rows: int, cols: int, length: int, first: Optional[int] = None, every: Optional[int] = None,
+                      mode: int = EXPOSE_MEAN, carry: Optional[np.ndarray] = None, out_rows: int = 0, out_cols: int = 0,
+                      d_colormap_ptr: int = 0, flip: bool = False, stride: int = DATAGRAM_BYTES, want_image: bool = True,
+                      want_power: bool = False, find: Optional[dict] = None) -> ExposeResult:
+        """Watch a run of consecutive blocks of wire datagrams (as watch_blocks takes them) with every frame exposed over the
+        `length` blocks that end with its shown block: their mean power row, or with mode=EXPOSE_PEAK their per-pixel maximum
+        (awpu_hip_expose_blocks).  every defaults to length and first to length - 1: back-to-back windows from the recording's
+        first block on.  `find` (a dict of find_peaks' keywords, {} for the defaults) also finds the sources of every exposed
+        frame.  -> ExposeResult; pass its .next_first as `first` and its .carry as `carry` to the call that continues the run
+        (carry is written in place)."""
+        buf = np.frombuffer(wire, dtype=np.uint8)
+        if stride < DATAGRAM_BYTES or buf.size % (256 * stride) or buf.size == 0:
+            raise ValueError(f"wire must be a whole number of blocks of 256 datagrams {stride} bytes apart")
+        every = length if every is None else every
+        first = length - 1 if first is None else first
+        return self._expose(lambda *rest: self._lib.awpu_hip_expose_blocks(self._h, buf.ctypes.data_as(C.c_void_p), stride, *rest),
+                            "awpu_hip_expose_blocks", buf.size // (256 * stride), rows, cols, first, every, length, mode, carry, out_rows,
+                            out_cols, d_colormap_ptr, flip, want_image, want_power, find)
+
+    def expose_samples(self, samples: np.ndarray, rows: int, cols: int, length: int, first: Optional[int] = None,
+                       every: Optional[int] = None, mode: int = EXPOSE_MEAN, carry: Optional[np.ndarray] = None, out_rows: int = 0,
+                       out_cols: int = 0, d_colormap_ptr: int = 0, flip: bool = False, want_image: bool = True, want_power: bool = False,
+                       find: Optional[dict] = None) -> ExposeResult:
+        """The same from unpacked samples [n_streams, N] (N a multiple of 256, oldest first) (awpu_hip_expose_samples)."""
+        samples = np.ascontiguousarray(samples, np.float32)
+        if samples.ndim != 2 or samples.shape[0] != self.cfg.n_streams or samples.shape[1] % 256 or samples.shape[1] == 0:
+            raise ValueError(f"samples must be [{self.cfg.n_streams}, N] with N a positive multiple of 256")
+        every = length if every is None else every
+        first = length - 1 if first is None else first
+        return self._expose(lambda *rest: self._lib.awpu_hip_expose_samples(self._h, _f32(samples), samples.shape[1], *rest),
+                            "awpu_hip_expose_samples", samples.shape[1] // 256, rows, cols, first, every, length, mode, carry, out_rows,
+                            out_cols, d_colormap_ptr, flip, want_image, want_power, find)
+
+    def expose_samples_device(self, d_samples_ptr: int, pitch: int, n_blocks: int, rows: int, cols: int, length: int, first: int,
+                              every: int, mode: int = EXPOSE_MEAN, d_carry_ptr: int = 0, d_image_ptr: int = 0, d_big_ptr: int = 0,
+                              d_power_ptr: int = 0, d_sources_ptr: int = 0, d_count_ptr: int = 0, out_rows: int = 0, out_cols: int = 0,
+                              d_colormap_ptr: int = 0, flip: bool = False, stream: int = 0, find: Optional[dict] = None) -> int:
+        """The same on device pointers (samples [n_streams, pitch]; carry [pixels]; image, big, power as watch_samples_device
+        takes them, sources and count as find_samples_device does, each or 0) on `stream`; asynchronous.  -> next_first
+        (awpu_hip_expose_samples_device)."""
+        w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(d_colormap_ptr))
+        e = Expose(length, mode)
+        f = None
+        if find is not None:
+            f = Find(rows, cols, find.get("radius", 2), find.get("max_sources", 4), find.get("min_power", 0.0), find.get("min_ratio", 0.0),
+                     find.get("fov_deg", 180.0))
+        _check(self._lib.awpu_hip_expose_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, C.byref(w), C.byref(e),
+                                                        None if f is None else C.byref(f), C.c_void_p(d_carry_ptr), C.c_void_p(d_image_ptr),
+                                                        C.c_void_p(d_big_ptr), C.c_void_p(d_power_ptr), C.c_void_p(d_sources_ptr),
+                                                        C.c_void_p(d_count_ptr), C.c_void_p(stream)), "awpu_hip_expose_samples_device")
         return watch_count(n_blocks, first, every)[1]
 
     def range(self, theta, phi, distance, d_frame_ptr: int = 0):

@@ -378,6 +378,11 @@ struct awpu_hip {
     // pinned find_out.h[i & 1], behind the same two events; locating (awpu_hip_focus.h) adds its ranges and the candidates' powers
     // behind them (the device form: only the powers nobody asked for, in find_out.d[0])
     awpu::host::BufferPair find_out;
+    // exposing such runs (awpu_hip_expose.h): the open window's row [pixel_count] from piece to piece and from the caller's `carry`
+    // to it, and the frames that close inside piece i in expose.d[i & 1] (the device form: in expose.d[0], where nobody asked for
+    // them).  The host forms bring them back through pinned blk_out.h[i & 1], which an exposed run's swept powers never cross
+    Dev<float> d_expose_carry;
+    awpu::host::BufferPair expose;
 
     // the band (awpu_hip_band.h): its coefficients (empty = none; they travel to the pre-pass as kernel arguments), and the
     // filtered frames of a call whose own frames are the caller's or the ring's, in those frames' layout (band_sweep): a plane

@@ -1,8 +1,9 @@
 // awpu_runs.cpp -- runs of consecutive blocks of a recording through one pipeline of pieces: a heatmap of every block
 // (include/awpu_hip_blocks.h), the beam audio of every block (awpu_hip_listen.h), display images of every Nth block
-// (awpu_hip_watch.h) -- in up to four bands at once (awpu_hip_spectral.h) --, the sources in every Nth block (awpu_hip_find.h) and their distances (awpu_hip_focus.h).  The handle and what is called here out of awpu_hip.cpp and awpu_sweep.cpp: awpu_handle.h.
+// (awpu_hip_watch.h) -- in up to four bands at once (awpu_hip_spectral.h) --, the sources in every Nth block (awpu_hip_find.h), their distances (awpu_hip_focus.h), and all of a watch run's exposed over the blocks in front of every Nth (awpu_hip_expose.h).  The handle and what is called here out of awpu_hip.cpp and awpu_sweep.cpp: awpu_handle.h.
 #include "awpu_handle.h"
 #include "awpu_hip_blocks.h"
+#include "awpu_hip_expose.h"
 #include "awpu_hip_find.h"
 #include "awpu_hip_focus.h"
 #include "awpu_hip_listen.h"
@@ -15,6 +16,7 @@
 #include <vector>
 
 #include "block_kernels.h"
+#include "expose_kernels.h"
 #include "find_kernels.h"
 #include "find_rule.h"
 #include "spectral_kernels.h"
@@ -537,14 +539,16 @@ struct WatchRun {
     const FindRun *find = nullptr;
 };
 
-// slots [q, slots) of a piece's history (watch_kernels.h) into pinned blk_in.h[b]: tight datagrams, or rows of 256 * (slots - q)
-void stage_watch(awpu_hip *h, const BlockRun &src, int b0, int every, int q, int slots, int b) {
+// slots [q, slots) of a piece's history, slot s holding block block_of(s) of the call, into pinned blk_in.h[b]: tight datagrams,
+// or rows of 256 * (slots - q)
+template <class Map>
+void stage_slots(awpu_hip *h, const BlockRun &src, const Map &block_of, int q, int slots, int b) {
     unsigned char *dst = h->blk_in.h[b];
-    const int m = std::min(every, 4), ns = slots - q;
+    const int ns = slots - q;
     const size_t S = (size_t) h->cfg.n_streams, block_bytes = (size_t) awpu::kSamples * (src.wire ? (size_t) AWPU_DATAGRAM_BYTES : S * sizeof(float));
     parallel_ranges((size_t) ns, block_bytes * ns, [&](size_t lo, size_t hi) {
         for (size_t k = lo; k < hi; k++) {
-            const size_t blk = (size_t) awpu::watch_slot_block(q + (int) k, b0, every, m);
+            const size_t blk = (size_t) block_of(q + (int) k);
             if (src.wire) {
                 const unsigned char *from = src.wire + blk * awpu::kSamples * src.stride;
                 unsigned char *to = dst + k * awpu::kSamples * AWPU_DATAGRAM_BYTES;
@@ -560,6 +564,12 @@ void stage_watch(awpu_hip *h, const BlockRun &src, int b0, int every, int q, int
             }
         }
     });
+}
+
+// ... of a watch piece (watch_kernels.h)
+void stage_watch(awpu_hip *h, const BlockRun &src, int b0, int every, int q, int slots, int b) {
+    const int m = std::min(every, 4);
+    stage_slots(h, src, [=](int slot) { return awpu::watch_slot_block(slot, b0, every, m); }, q, slots, b);
 }
 
 struct WatchPieces : Consumer {
@@ -843,6 +853,215 @@ int find_run(awpu_hip *h, const BlockRun &src, int n_blocks, const awpu_watch_t 
     return watch_run(h, src, n_blocks, &shown, nullptr, nullptr, power, user, &find);
 }
 
+// ---- exposure (awpu_hip_expose.h; kernels in expose_kernels.hip) -----------------------------------------------------------------
+// The items of an exposed run are its SWEPT blocks, in order: the blocks of every window that lie inside the call, the skipped
+// ones between the windows left out.  With c = carry_in, item s is block q = (s + c) % L of window j = (s + c) / L, and (s + c) / L
+// frames close in front of it.  A piece is n consecutive items, and its history holds only the blocks their snapshots read, by the
+// slot map of expose_kernels.h: formed like a watch piece's, blocks from before the call out of the ring's snapshot, the rest
+// staged and uploaded (host forms) or gathered out of the caller's samples (device form).  The windows are cut a window's items at
+// a launch (consecutive blocks: launch_watch_cut, or the band's pre-pass, with a step of one block); where every == length the
+// whole piece is one.  Behind the piece's sweep comes launch_expose on its powers -- the open window arrives and leaves in
+// d_expose_carry --, and behind that the display step and the peak pass of a watch run on the frames that closed inside the
+// piece.  Their number varies from piece to piece, so exposed powers, images and sources all travel through show / fetch_shown /
+// deliver_shown and Consumer::power stays null.  The ring's new snapshot: as in a watch run.
+
+struct ExposeRun {
+    awpu_watch_t w{};
+    awpu_expose_t e{};
+    awpu::ExposeCount n{};
+    float *carry = nullptr;                    // host memory in the host forms, device memory in the device form, like the outputs
+    uint8_t *image = nullptr, *big = nullptr;
+    float *power = nullptr;
+    bool finds = false;
+    awpu_find_t f{};
+    awpu_source_t *sources = nullptr;
+    int32_t *count = nullptr;
+};
+
+struct ExposePieces final : Consumer {
+    awpu_hip *const h;
+    const BlockRun &src;
+    const ExposeRun &er;
+    const awpu_watch_t &w;
+    const bool host, want_small;
+    const int S, L, E, c_in;
+    const size_t P, big_bytes;
+    int lo = 0, width = 0;
+    size_t small_off = 0, big_off = 0;  // in a watch buffer: the peaks, then the compact images, then the large ones
+    size_t sources_off = 0;             // in a find buffer: the counts, then the sources
+    const float *snapshot = nullptr;    // blocks -4 .. -1 of the call
+    hipStream_t sw = nullptr;
+    std::vector<float> carried;         // host forms: the open window after the run
+
+    ExposePieces(awpu_hip *h_, const BlockRun &src_, int n_blocks_, const ExposeRun &er_)
+        : h(h_), src(src_), er(er_), w(er_.w), host(!src_.device), want_small(er_.image || er_.big), S(h_->cfg.n_streams), L(er_.e.length),
+          E(er_.w.every), c_in(er_.n.carry_in), P((size_t) h_->cfg.pixel_count),
+          big_bytes((size_t) er_.w.out_rows * er_.w.out_cols * (er_.w.d_colormap ? 3 : 1)) {
+        n_items = er.n.n_swept;
+        n_blocks = n_blocks_;
+        // the last block of the call swept: the ring's new snapshot is the tail of the last piece's history
+        tail = n_items == 0 || item_block(n_items - 1) != n_blocks - 1;
+    }
+    int item_block(int s) const { return w.first + (s + c_in) / L * E - (L - 1) + (s + c_in) % L; }
+    int frames_before(int s) const { return (s + c_in) / L; }
+    // the slot map of a piece's history
+    awpu::ExposeSlots map(const Piece &p) const {
+        if (p.tail) return {n_blocks - 1, 1, n_blocks - 1 + E, E, L, false};
+        const int q0 = (p.first + c_in) % L, k0 = item_block(p.first);
+        return {k0, std::min(p.n, L - q0), k0 - q0 + E, E, L, E - L >= 3};
+    }
+    static int slots_of(const Piece &p, const awpu::ExposeSlots &m) { return m.slots(p.tail ? 1 : p.n); }
+    // the most slots a piece of n items has: its items and, per window it touches, three blocks (own slots) or the gap (consecutive)
+    int slots_max(int n) const {
+        const int windows = (n + 2 * L - 2) / L;
+        return E - L >= 3 ? n + 3 * windows : n + 3 + (windows - 1) * (E - L);
+    }
+
+    int check() override {
+        if (h->cfg.pixel_count != h->cfg.n_pixels) return invalid("the display step needs the whole grid on this handle");
+        if ((long long) w.rows * w.cols != h->cfg.n_pixels) return invalid("rows x cols must be the grid");
+        return AWPU_OK;
+    }
+    size_t source_bytes(int nf) const { return (size_t) nf * er.f.max_sources * sizeof(awpu_source_t); }
+    int ensure(int piece_max, int lo_, int width_, hipStream_t sw_) override {
+        lo = lo_, width = width_, sw = sw_;
+        const int most = std::max(slots_max(piece_max), 4);
+        pitch = awpu::kSamples * most;
+        small_off = align16(sizeof(float) * piece_max), big_off = small_off + align16((size_t) piece_max * P);
+        sources_off = align16(sizeof(int32_t) * piece_max);
+        snapshot = h->d_ring + h->ring_pos;
+        int rc = ensure_run_buffers(h, src, piece_max, width, true, most - 3, most, bands.planes());
+        if (rc == AWPU_OK && !host) rc = ensure_power(h, (size_t) piece_max * P * bands.planes());
+        if (rc == AWPU_OK) rc = h->d_expose_carry.ensure(P);
+        if (rc == AWPU_OK && (host || !er.power)) rc = h->expose.ensure((size_t) piece_max * P * sizeof(float), false);
+        if (rc == AWPU_OK && want_small) rc = h->watch.ensure(big_off + (host && er.big ? (size_t) piece_max * big_bytes : 0), host);
+        if (rc == AWPU_OK && er.big) rc = ensure_taps(h, w.rows, w.cols, w.out_rows, w.out_cols, sw);
+        if (rc == AWPU_OK && er.finds && host) rc = h->find_out.ensure(sources_off + source_bytes(piece_max), true);
+        if (host && er.n.carry_out > 0) carried.resize(P);
+        return rc;
+    }
+    int begin(hipStream_t s) override {
+        if (c_in > 0)
+            AWPU_HIP_TRY(hipMemcpyAsync(h->d_expose_carry, er.carry, P * sizeof(float), host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+        return AWPU_OK;
+    }
+    int staged_blocks(const Piece &p) override {
+        const awpu::ExposeSlots m = map(p);
+        const int slots = slots_of(p, m), q = std::max(0, 3 - m.k0);
+        stage_slots(h, src, [&](int slot) { return m.slot_block(slot); }, q, slots, p.b);
+        return slots - q;
+    }
+    int history(const Piece &p, hipStream_t s) override {
+        const awpu::ExposeSlots m = map(p);
+        const int slots = slots_of(p, m), q = std::max(0, 3 - m.k0);  // slots [0, q) hold blocks from before the call
+        float *hist = hist_of(h, p.b);
+        if (!host) {
+            AWPU_HIP_TRY(awpu::launch_expose_gather(src.samples, src.pitch, snapshot, m, S, hist, pitch, 0, slots, s));
+            return AWPU_OK;
+        }
+        if (q > 0) AWPU_HIP_TRY(awpu::launch_expose_gather(nullptr, 0, snapshot, m, S, hist, pitch, 0, q, s));
+        if (src.wire) {
+            AWPU_HIP_TRY(awpu::launch_unpack_blocks(h->blk_in.d[p.b], slots - q, S, hist, pitch, awpu::kSamples * q, s));
+        } else {
+            const long long n = (long long) awpu::kSamples * (slots - q);
+            AWPU_HIP_TRY(awpu::launch_copy_rows(reinterpret_cast<const float *>(h->blk_in.d[p.b].get()), n, hist + awpu::kSamples * q, pitch, (int) n, S, s));
+        }
+        return AWPU_OK;
+    }
+    int cut(const Piece &p, hipStream_t s) override {
+        const awpu::ExposeSlots m = map(p);
+        const size_t frame = (size_t) S * width;
+        for (int i0 = 0, i1; i0 < p.n; i0 = i1) {  // items [i0, i1): consecutive blocks in consecutive slots
+            i1 = E == L ? p.n : (i0 < m.n0 ? m.n0 : std::min(i0 + L, p.n));
+            const float *from = hist_of(h, p.b) + (size_t) awpu::kSamples * m.item_slot(i0);
+            float *to = h->d_blk_frames + i0 * frame;
+            if (bands.n) {
+                if (const int rc = band_cut(h, bands, from, awpu::kSamples, pitch, h->wstart, i1 - i0, to, (long long) frame * p.n, h->compact_hist > 0 ? kCompact : kFull, s)) return rc;
+            } else {
+                AWPU_HIP_TRY(awpu::launch_watch_cut(from, pitch, S, i1 - i0, awpu::kSamples, lo, width, to, s));
+            }
+        }
+        return AWPU_OK;
+    }
+    int show(const Piece &p, float *d_pow, long long, hipStream_t s) override {
+        const int j0 = frames_before(p.first), nf = frames_before(p.first + p.n) - j0;
+        const awpu::ExposeWindows win{p.n, -((p.first + c_in) % L), L, L};
+        float *d_frames = host || !er.power ? reinterpret_cast<float *>(h->expose.d[host ? p.b : 0].get()) : er.power + (size_t) j0 * P;
+        AWPU_HIP_TRY(awpu::launch_expose(d_pow, (long long) P, win, er.e.mode, h->d_expose_carry, d_frames, s));
+        if (nf == 0) return AWPU_OK;
+        if (er.finds) {
+            unsigned char *out = h->find_out.d[p.b];
+            awpu_source_t *d_sources = host ? reinterpret_cast<awpu_source_t *>(out + sources_off) : er.sources + (size_t) j0 * er.f.max_sources;
+            AWPU_HIP_TRY(awpu::launch_find_peaks(d_frames, nf, er.f, d_sources, host ? reinterpret_cast<int32_t *>(out) : er.count + j0, s));
+        }
+        if (!want_small) return AWPU_OK;
+        uint8_t *scratch = h->watch.d[host ? p.b : 0];
+        uint8_t *d_small = host || !er.image ? scratch + small_off : er.image + (size_t) j0 * P;
+        AWPU_HIP_TRY(awpu::launch_heatmap(d_frames, (int) P, nf, reinterpret_cast<float *>(scratch), false, d_small, s));
+        if (er.big)
+            AWPU_HIP_TRY(awpu::launch_watch_upscale(d_small, w.rows, w.cols, nf, h->d_taps, h->taps_band_rows, w.d_colormap, w.flip != 0,
+                                                    host ? scratch + big_off : er.big + (size_t) j0 * big_bytes, w.out_rows, w.out_cols, s));
+        return AWPU_OK;
+    }
+    int fetch_shown(const Piece &p, hipStream_t s) override {
+        const int nf = frames_before(p.first + p.n) - frames_before(p.first);
+        if (nf == 0) return AWPU_OK;
+        if (er.power) AWPU_HIP_TRY(hipMemcpyAsync(h->blk_out.h[p.b], h->expose.d[p.b], (size_t) nf * P * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (er.finds) AWPU_HIP_TRY(hipMemcpyAsync(h->find_out.h[p.b], h->find_out.d[p.b], sources_off + source_bytes(nf), hipMemcpyDeviceToHost, s));
+        uint8_t *to = h->watch.h[p.b], *from = h->watch.d[p.b];
+        if (er.image) AWPU_HIP_TRY(hipMemcpyAsync(to + small_off, from + small_off, (size_t) nf * P, hipMemcpyDeviceToHost, s));
+        if (er.big) AWPU_HIP_TRY(hipMemcpyAsync(to + big_off, from + big_off, (size_t) nf * big_bytes, hipMemcpyDeviceToHost, s));
+        return AWPU_OK;
+    }
+    int deliver_shown(const Piece &p) override {
+        const int j0 = frames_before(p.first), nf = frames_before(p.first + p.n) - j0;
+        if (nf == 0) return AWPU_OK;
+        if (er.power) std::memcpy(er.power + (size_t) j0 * P, h->blk_out.h[p.b], (size_t) nf * P * sizeof(float));
+        if (er.finds) {
+            std::memcpy(er.count + j0, h->find_out.h[p.b], sizeof(int32_t) * nf);
+            std::memcpy(er.sources + (size_t) j0 * er.f.max_sources, h->find_out.h[p.b] + sources_off, source_bytes(nf));
+        }
+        if (er.image) std::memcpy(er.image + (size_t) j0 * P, h->watch.h[p.b] + small_off, (size_t) nf * P);
+        if (er.big) parallel_copy(er.big + (size_t) j0 * big_bytes, h->watch.h[p.b] + big_off, (size_t) nf * big_bytes);
+        return AWPU_OK;
+    }
+    int ring_from(const Piece &last) override { return awpu::kSamples * (slots_of(last, map(last)) - 4); }
+    // the open window, behind the last piece's exposure on the sweep's stream (whatever stream the listen kernels of other runs have)
+    int end(hipStream_t) override {
+        if (er.n.carry_out == 0) return AWPU_OK;
+        if (host)
+            AWPU_HIP_TRY(hipMemcpyAsync(carried.data(), h->d_expose_carry, P * sizeof(float), hipMemcpyDeviceToHost, sw));
+        else
+            AWPU_HIP_TRY(hipMemcpyAsync(er.carry, h->d_expose_carry, P * sizeof(float), hipMemcpyDeviceToDevice, sw));
+        return AWPU_OK;
+    }
+};
+
+// the checks of an expose call that read no handle; then the run
+int expose_run(awpu_hip *h, const BlockRun &src, int n_blocks, const awpu_watch_t *w, const awpu_expose_t *e, const awpu_find_t *f, float *carry,
+               uint8_t *image, uint8_t *big, float *power, awpu_source_t *sources, int32_t *count, hipStream_t user) {
+    WatchRun wr;
+    if (int rc = check_watch(w, image || big || power || sources || count, big != nullptr, n_blocks, &wr)) return rc;
+    if (const char *why = awpu::expose_refusal(e, w->every)) return invalid(why);
+    if (!sources != !count) return invalid("sources and count come together");
+    if (!f != !sources) return invalid("a find request exactly when sources and count are asked for");
+    if (f) {
+        if (const char *why = awpu::find_refusal(f)) return invalid(why);
+        if (f->rows != w->rows || f->cols != w->cols) return invalid("the find grid must be the watch grid");
+    }
+    ExposeRun er;
+    er.w = *w, er.e = *e;
+    er.n = awpu::expose_count(n_blocks, w->first, w->every, e->length);
+    if (!carry && (er.n.carry_in > 0 || er.n.carry_out > 0)) return invalid("null carry with a window open across the call's ends");
+    er.carry = carry, er.image = image, er.big = big, er.power = power;
+    if (f) er.finds = true, er.f = *f, er.sources = sources, er.count = count;
+    AWPU_CTX(h);
+    ExposePieces c(h, src, n_blocks, er);
+    const int rc = run_pieces(h, src, user, c);
+    if (rc == AWPU_OK && !src.device && er.n.carry_out > 0) std::memcpy(carry, c.carried.data(), c.carried.size() * sizeof(float));
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1010,6 +1229,46 @@ int awpu_hip_locate_samples_device(awpu_hip_t *h, const float *d_samples, int64_
     if (int rc = sample_source(h, d_samples, pitch, n_blocks, true, &src)) return rc;
     const LocateRun locate{distance, n_dist, d_ranges, d_range_power};
     return find_run(h, src, n_blocks, w, f, d_sources, d_count, d_power, static_cast<hipStream_t>(stream), &locate);
+}
+
+int awpu_hip_expose_rows_device(awpu_hip_t *h, const float *d_power, int32_t n_blocks, int32_t n_pixels, int32_t first, int32_t every,
+                                const awpu_expose_t *e, float *d_carry, float *d_frames, void *stream) {
+    if (!h || !d_power) return invalid("null argument");
+    if (n_blocks < 1 || n_pixels < 1 || first < 0 || every < 1) return invalid("n_blocks, n_pixels, every below 1 or first below 0");
+    if (const char *why = awpu::expose_refusal(e, every)) return invalid(why);
+    const awpu::ExposeCount n = awpu::expose_count(n_blocks, first, every, e->length);
+    if (!d_carry && (n.carry_in > 0 || n.carry_out > 0)) return invalid("null carry with a window open across the call's ends");
+    if (!d_frames && n.n_frames > 0) return invalid("null argument");
+    h = first_device(h);
+    AWPU_CTX(h);
+    AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
+    const awpu::ExposeWindows win{n_blocks, first - (e->length - 1), every, e->length};
+    AWPU_HIP_TRY(awpu::launch_expose(d_power, n_pixels, win, e->mode, d_carry, d_frames, stream ? static_cast<hipStream_t>(stream) : h->stream));
+    return AWPU_OK;
+}
+
+int awpu_hip_expose_blocks(awpu_hip_t *h, const void *datagrams, int32_t stride_bytes, int32_t n_blocks, const awpu_watch_t *w,
+                           const awpu_expose_t *e, const awpu_find_t *f, float *carry, uint8_t *image, uint8_t *big_image, float *power,
+                           awpu_source_t *sources, int32_t *count) {
+    BlockRun src;
+    if (int rc = wire_source(h, datagrams, stride_bytes, n_blocks, &src)) return rc;
+    return expose_run(h, src, n_blocks, w, e, f, carry, image, big_image, power, sources, count, nullptr);
+}
+
+int awpu_hip_expose_samples(awpu_hip_t *h, const float *samples, int64_t pitch, int32_t n_blocks, const awpu_watch_t *w,
+                            const awpu_expose_t *e, const awpu_find_t *f, float *carry, uint8_t *image, uint8_t *big_image, float *power,
+                            awpu_source_t *sources, int32_t *count) {
+    BlockRun src;
+    if (int rc = sample_source(h, samples, pitch, n_blocks, false, &src)) return rc;
+    return expose_run(h, src, n_blocks, w, e, f, carry, image, big_image, power, sources, count, nullptr);
+}
+
+int awpu_hip_expose_samples_device(awpu_hip_t *h, const float *d_samples, int64_t pitch, int32_t n_blocks, const awpu_watch_t *w,
+                                   const awpu_expose_t *e, const awpu_find_t *f, float *d_carry, uint8_t *d_image, uint8_t *d_big_image,
+                                   float *d_power, awpu_source_t *d_sources, int32_t *d_count, void *stream) {
+    BlockRun src;
+    if (int rc = sample_source(h, d_samples, pitch, n_blocks, true, &src)) return rc;
+    return expose_run(h, src, n_blocks, w, e, f, d_carry, d_image, d_big_image, d_power, d_sources, d_count, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -14,6 +14,10 @@ at its direction is swept over N focus distances from LO to HI metres, uniform i
 while they are on the device (Engine.locate_blocks), and the distance at which it peaks is written as a last column, `distance`
 (metres, 17 significant digits; inf: a plane wave).
 
+--exposure L searches heatmaps integrated over the L blocks that end with every --every'th (1 <= L <= --every): the mean of their
+power rows (Engine.expose_blocks, include/awpu_hip_expose.h), which steadies the peaks of a noise-like source; the open window is
+carried from one --chunk call to the next, and the first block searched is then block L - 1.  Off unless given; not with --range.
+
 Every block is ingested; every --every'th is swept and searched.  --chunk blocks go to the engine per call, each call continuing
 with the `next_first` of the one before, so a long capture streams through bounded memory.
 
@@ -96,10 +100,16 @@ def main(argv=None) -> int:
     ap.add_argument("--focus", type=float, default=None, metavar="METRES", help="focus the delay table on points METRES away (default: plane waves)")
     ap.add_argument("--range", default=None, metavar="LO:HI:N", dest="range_",
                     help="range every source over N focus distances from LO to HI metres, uniform in 1 / d: the `distance` column")
+    ap.add_argument("--exposure", type=int, default=None, metavar="L",
+                    help="search heatmaps integrated over the L blocks that end with the searched one, 1 <= L <= --every (include/awpu_hip_expose.h)")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     if a.every < 1 or a.chunk < 1:
         ap.error("--every and --chunk are positive")
+    if a.exposure is not None and not 1 <= a.exposure <= a.every:
+        ap.error("--exposure is between 1 and --every")
+    if a.exposure is not None and a.range_:
+        ap.error("--exposure together with --range: locate runs are not exposed")
 
     sys.path.insert(0, str(Path(__file__).resolve().parent))
     from pcap_heatmaps import blocks_of, read_pcap_payloads
@@ -125,7 +135,8 @@ def main(argv=None) -> int:
     if n > 256:
         print(f"{n} mics: the wire carries 256 streams per datagram")
         return 1
-    searched, lines, first, block_bytes = 0, 0, 0, 256 * 1032
+    searched, lines, first, block_bytes = 0, 0, 0 if a.exposure is None else a.exposure - 1, 256 * 1032
+    carry = None
     with open(a.out, "w", newline="") as f, \
             pkg.Engine(n_pixels=a.cols * a.cols, n_streams=n, max_batch=a.max_batch, grid_columns=a.cols, device=a.device) as eng:
         writer = csv.writer(f, lineterminator="\n")
@@ -141,7 +152,12 @@ def main(argv=None) -> int:
             find = dict(first=first, every=a.every, radius=a.radius, max_sources=a.max_sources, min_power=a.min_power, min_ratio=a.min_ratio,
                         fov_deg=a.fov)
             chunk = wire[b * block_bytes: (b + nb) * block_bytes]
-            res = eng.find_blocks(chunk, a.cols, a.cols, **find) if candidates is None else eng.locate_blocks(chunk, a.cols, a.cols, candidates, **find)
+            if a.exposure is not None:
+                what = {k: v for k, v in find.items() if k not in ("first", "every")}
+                res = eng.expose_blocks(chunk, a.cols, a.cols, a.exposure, first=first, every=a.every, carry=carry, want_image=False, find=what)
+                carry = res.carry
+            else:
+                res = eng.find_blocks(chunk, a.cols, a.cols, **find) if candidates is None else eng.locate_blocks(chunk, a.cols, a.cols, candidates, **find)
             lines += write_rows(writer, b + first + a.every * np.arange(len(res)), res.sources, res.count, getattr(res, "ranges", None))
             first = res.next_first
             searched += len(res)

@@ -18,6 +18,11 @@ The colour table plays no part.  --bands together with --band is an error.
 --focus METRES focuses the delay table on points METRES away instead of on plane waves (binding.build_focus_table,
 include/awpu_hip_focus.h): a large array in a room is in its sources' near field, where a plane-wave table blurs them.
 
+--exposure L integrates every frame over the L blocks that end with its shown block (1 <= L <= --every): the mean of their power
+rows, or with --peak-hold their per-pixel maximum (Engine.expose_blocks, include/awpu_hip_expose.h); L * 5.2 ms of sound per
+frame instead of 5.2, the open window carried from one --chunk call to the next.  The first frame is then block L - 1's.  Off
+unless given; not with --bands.
+
 Every block is ingested; every --every'th is swept and shown.  The default 3 gives 48828 / (256 * 3) = 63.6 frames per second, the
 nearest to the 60 the reference opens its writer with.  --chunk blocks go to the engine per call, each call continuing with the
 `next_first` of the one before, so a long capture streams through bounded memory.
@@ -200,10 +205,19 @@ def main(argv=None) -> int:
     ap.add_argument("--band-scale", default="common", choices=("common", "per-band"), help="--bands: one maximum per frame over the bands, or each band's own")
     ap.add_argument("--focus", type=float, default=None, metavar="METRES",
                     help="focus the delay table on points METRES away instead of on plane waves (include/awpu_hip_focus.h)")
+    ap.add_argument("--exposure", type=int, default=None, metavar="L",
+                    help="integrate every frame over the L blocks that end with its shown block, 1 <= L <= --every (include/awpu_hip_expose.h)")
+    ap.add_argument("--peak-hold", action="store_true", help="--exposure: the per-pixel maximum of the L blocks instead of their mean")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     if a.every < 1 or a.chunk < 1 or a.size < a.cols:
         ap.error("--every and --chunk are positive, --size is at least --cols")
+    if a.exposure is not None and not 1 <= a.exposure <= a.every:
+        ap.error("--exposure is between 1 and --every")
+    if a.exposure is not None and a.bands:
+        ap.error("--exposure together with --bands: spectral runs are not exposed")
+    if a.peak_hold and a.exposure is None:
+        ap.error("--peak-hold needs --exposure")
     if a.band and a.bands:
         ap.error("--bands together with --band: one band through the colour table, or several bands as colours")
 
@@ -238,6 +252,9 @@ def main(argv=None) -> int:
         band_scale = pkg.binding.SPECTRAL_SCALE_COMMON if a.band_scale == "common" else pkg.binding.SPECTRAL_SCALE_PER_BAND
     rate, scale = frame_rate(a.every)
     shown, first, block_bytes, res = 0, 0, 256 * 1032, None
+    carry = None
+    if a.exposure is not None:
+        first, mode = a.exposure - 1, pkg.binding.EXPOSE_PEAK if a.peak_hold else pkg.binding.EXPOSE_MEAN
     raw = open(f"{a.out}.bgr", "wb") if a.raw else None
     writer = None if a.raw else AviWriter(a.out, a.size, a.size, a.every)
     with pkg.Engine(n_pixels=a.cols * a.cols, n_streams=n, max_batch=a.max_batch, grid_columns=a.cols, device=a.device) as eng:
@@ -250,6 +267,11 @@ def main(argv=None) -> int:
             if a.bands:
                 res = eng.spectral_blocks(wire[b * block_bytes: (b + nb) * block_bytes], a.cols, a.cols, bands, channel, band_scale, first=first,
                                           every=a.every, out_rows=a.size, out_cols=a.size, flip=a.flip, want_image=False, want_dominant=False)
+            elif a.exposure is not None:
+                res = eng.expose_blocks(wire[b * block_bytes: (b + nb) * block_bytes], a.cols, a.cols, a.exposure, first=first, every=a.every,
+                                        mode=mode, carry=carry, out_rows=a.size, out_cols=a.size, d_colormap_ptr=table.data_ptr(), flip=a.flip,
+                                        want_image=False)
+                carry = res.carry
             else:
                 res = eng.watch_blocks(wire[b * block_bytes: (b + nb) * block_bytes], a.cols, a.cols, first=first, every=a.every,
                                        out_rows=a.size, out_cols=a.size, d_colormap_ptr=table.data_ptr(), flip=a.flip, want_image=False,
