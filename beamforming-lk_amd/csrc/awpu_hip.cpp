@@ -662,19 +662,23 @@ int awpu_hip_set_mic_gains(awpu_hip_t *h, const float *gains) {
 
 namespace {
 
-// aw_processing_unit.cpp:145-200 on the 64 mean squares of one array
+// aw_processing_unit.cpp:145-200 on the 64 mean squares of one array.  The reference sorts with operator<, which is no order
+// once a mean square is NaN (a NaN sample in the stream): the median then depends on where the NaN stands, and the NaN stream
+// passes both tests below (every comparison with NaN is false).  Defined here, and in oracle_calibrate alike: NaN sorts last
+// -- finite values ascending, then +inf, then NaN --, and a mic is usable only if its mean square and the median are finite
+// and the reference's two tests pass.  On all-finite mean squares these are the reference's bits.
 int usable_from_power(const float *power, float reference_power_level, int32_t *index, float *correction,
                       float *median_out) {
     float sorted[AWPU_ELEMENTS];
     std::copy(power, power + AWPU_ELEMENTS, sorted);
-    std::sort(sorted, sorted + AWPU_ELEMENTS);
+    std::sort(sorted, sorted + AWPU_ELEMENTS, [](float a, float b) { return std::isnan(b) ? !std::isnan(a) : a < b; });
     // the reference averages elements 32 and 33 of the sorted list (.cpp:150), in double, then rounds
     const float median = (float) ((sorted[AWPU_ELEMENTS / 2] + sorted[AWPU_ELEMENTS / 2 + 1]) / 2.0);
     int count = 0;
     for (int s = 0; s < AWPU_ELEMENTS; s++) {
         const bool far_off = std::fabs(power[s] - median) > 1e-4;  // float promoted against a double bound
         const bool dead = power[s] < median * 1e-3;
-        if (far_off || dead) continue;
+        if (!std::isfinite(power[s]) || !std::isfinite(median) || far_off || dead) continue;
         index[count] = s;
         correction[count] = reference_power_level / power[s];
         count++;

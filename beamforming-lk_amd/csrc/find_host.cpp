@@ -22,7 +22,7 @@ extern "C" int awpu_hip_find_peaks(const float *power, int32_t n_frames, const a
         float m;
         const uint32_t m_bits = (uint32_t) (best >> 32);
         std::memcpy(&m, &m_bits, sizeof m);
-        const float floor_ratio = f->min_ratio * m;
+        const float floor_ratio = awpu::find_floor_ratio(f->min_ratio, m);
         peaks.clear();
         for (int r = 0; r < rows; r++) {
             for (int c = 0; c < cols; c++) {

@@ -77,7 +77,7 @@ __global__ __launch_bounds__(kFindThreads) void find_peaks_kernel(const float *p
         best = key > best ? key : best;
     }
     best = block_max(best, slots[0]);
-    const float floor_ratio = min_ratio * __uint_as_float((uint32_t) (best >> 32));
+    const float floor_ratio = find_floor_ratio(min_ratio, __uint_as_float((uint32_t) (best >> 32)));
 
     for (int base = (tid >> 6) * 64; base < n; base += kFindThreads) {  // (the same for every lane of a wave)
         const int i = base + lane;

@@ -22,6 +22,10 @@ AWPU_FIND_HD inline unsigned long long find_key(uint32_t bits, uint32_t pixel) {
 }
 AWPU_FIND_HD inline uint32_t find_key_pixel(unsigned long long key) { return 0xFFFFFFFFu - (uint32_t) key; }
 
+// the ratio threshold below the frame's maximum m: min_ratio = 0 is no threshold whatever m is (0 * inf and 0 * NaN are NaN, and
+// a NaN threshold lets no pixel through); otherwise one fp32 multiply
+AWPU_FIND_HD inline float find_floor_ratio(float min_ratio, float m) { return min_ratio == 0.0f ? 0.0f : min_ratio * m; }
+
 // what is wrong with a request, or null
 inline const char *find_refusal(const awpu_find_t *f) {
     if (!f) return "null argument";

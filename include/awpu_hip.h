@@ -194,7 +194,13 @@ int awpu_hip_set_mic_gains(awpu_hip_t *h, const float *gains);
  * (SURVEY 8f N4), with the per-mic mean squares computed on the device: mean square of every mic of
  * array `array` (streams array*64 .. +63) over the snapshot, the median (elements 32 and 33 of the
  * sorted list, as the reference takes it), then the usable mics: those within 1e-4 of the median and
- * not below median*1e-3.  Outputs (host): index[64] (mic ids inside the array, ascending),
+ * not below median*1e-3.  Where a mean square is not finite (a NaN or +inf sample, a sample whose square
+ * overflows) the reference has no behaviour to match -- its std::sort is undefined on NaN and a NaN stream
+ * passes both of its tests --, so it is defined here: the list is sorted with NaN last (finite values
+ * ascending, then +inf, then NaN), so the median does not depend on which mic holds the NaN, and a mic is
+ * usable only if its mean square is finite, the median is finite, and the two tests above pass.  On
+ * all-finite mean squares the results are the reference's bits.
+ * Outputs (host): index[64] (mic ids inside the array, ascending),
  * correction[64] (reference_power_level / power), *median, *usable (entries filled).
  * _device: d_frame [n_streams][hist] in device memory, on `stream` (NULL = the handle's); returns
  * after the result has reached the host.  _ring: on the current snapshot of the ingest ring. */

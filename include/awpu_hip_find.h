@@ -9,14 +9,18 @@
  * awpu_hip_steer_table or to the listeners of awpu_hip_listen.h as they are.
  *
  * THE RULE.  Input: one power row p[rows * cols] of fp32 values, row-major, pixel i = r * cols + c -- the order
- * awpu_hip_build_delay_table emits.  Domain: finite, non-negative powers (what every sweep writes); for any other bit pattern
- * the calls terminate and stay inside their buffers -- no loop's trip count depends on the data -- and the content of the result
- * is unspecified.
+ * awpu_hip_build_delay_table emits.  Domain: every bit pattern.  The sweeps write exact 0, subnormals, +inf and NaN besides
+ * ordinary powers (a frame whose squares overflow, a frame holding a bad sample), and the run forms below hand those rows
+ * straight to the peak pass: the rule applies to them as written, no loop's trip count depends on the data, and the host and
+ * the device results are equal on all of them.
  *   Order.     Pixel a BEATS pixel b when bits(p[a]) > bits(p[b]) as unsigned 32-bit patterns, or the bits are equal and a < b.
- *              On the domain: larger power, then lower index.  The order is total: no result depends on scheduling.
+ *              On finite, non-negative powers: larger power, then lower index; +inf beats them, a NaN beats +inf, and any
+ *              pattern with the sign bit set (-0.0 included) beats all of those.  The order is total: no result depends on
+ *              scheduling.
  *   Maximum.   m = the power of the pixel that beats all others of the frame.
  *   Peak.      Pixel (r, c) is a peak when it beats every other pixel (r', c') of the grid with |r' - r| <= radius and
- *              |c' - c| <= radius, and p > 0, and p >= min_power, and p >= min_ratio * m (one fp32 multiply).
+ *              |c' - c| <= radius, and p > 0, and p >= min_power, and p >= floor_ratio, where floor_ratio = 0 when
+ *              min_ratio == 0 -- no ratio threshold, whatever m is -- and min_ratio * m (one fp32 multiply) otherwise.
  *   Report.    The min(max_sources, number of peaks) peaks that beat the others, strongest first; `count` = how many.  The unused
  *              ones of a frame's max_sources entries hold pixel = -1 and zeros elsewhere.
  *   Refinement (all in double).  For 0 < r < rows - 1, with a, b, c the powers at rows r - 1, r, r + 1 of column c:
@@ -27,7 +31,11 @@
  *              y = row * sep_rows - rows * sep_rows / 2 + sep_rows / 2, x from col likewise,
  *              theta = asin(min(sqrt(x * x + y * y), 1)), phi = atan2(y, x) of the unnormalised pair (the reference's x /= norm is
  *              0 / 0 at the centre of an odd grid; that pixel gets phi = 0).
- * So a constant positive frame has exactly one peak, pixel 0, and an all-zero frame has none.
+ * So a constant positive frame -- a constant +inf frame too, at every min_ratio -- has exactly one peak, pixel 0, and an
+ * all-zero frame has none.  Two consequences off the finite powers: a NaN pixel is never a peak (p > 0 is false) and beats its
+ * whole window, so no pixel within `radius` of it is a peak either; and with min_ratio > 0 a frame holding a NaN has no sources
+ * at all (m is that NaN, and so is floor_ratio; only a finite pixel with the sign bit set, which no sweep writes, beats a
+ * positive NaN and takes its place as m).  With min_ratio == 0 the peaks away from the NaN are reported as usual.
  *
  * pixel, power, count, row and col are the same bits from the host and the device entry points; theta and phi may differ in
  * their last bits (asin and atan2 of two maths libraries).

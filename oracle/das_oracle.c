@@ -456,12 +456,16 @@ int oracle_resize_linear_u8(const uint8_t *src, int srows, int scols, uint8_t *d
 
 /* --------------------------------------------------------------- calibration */
 
+/* finite values ascending, then +inf, then NaN: a total order (operator< alone is none once a NaN is there) */
 static int cmp_float(const void *a, const void *b) {
     const float x = *(const float *) a, y = *(const float *) b;
+    if (isnan(x) || isnan(y)) return (isnan(x) != 0) - (isnan(y) != 0);
     return (x > y) - (x < y);
 }
 
-/* src/aw_processing_unit/aw_processing_unit.cpp:128-200 (one array). */
+/* src/aw_processing_unit/aw_processing_unit.cpp:128-200 (one array).  For non-finite mean squares the reference has no behaviour
+ * to match (its std::sort is undefined on NaN, and a NaN stream passes both of its tests): NaN sorts last, and a mic is usable
+ * only if its mean square and the median are finite and the reference's two tests pass -- as awpu_hip_calibrate_* decide. */
 int oracle_calibrate(const float *X, int hist, float reference_power_level, int32_t *index,
                      float *corr, float *median_out) {
     const unsigned fp = fp_enter();
@@ -480,7 +484,8 @@ int oracle_calibrate(const float *X, int hist, float reference_power_level, int3
     int count = 0;
     for (int s = 0; s < ORACLE_ELEMENTS; s++) {
         const float diff = fabsf(power[s] - median);
-        if (diff > 1e-4) {
+        if (!isfinite(power[s]) || !isfinite(median)) {
+        } else if (diff > 1e-4) {
         } else if (power[s] < median * 1e-3) {
         } else {
             index[count] = s;

@@ -74,7 +74,8 @@ def all_peaks(frame, rows, cols, radius, min_power, min_ratio):
     index = np.arange(rows * cols, dtype=np.uint64).reshape(rows, cols)
     key = (bits << np.uint64(32)) | (np.uint64(0xFFFFFFFF) - index)  # a beats b <=> key[a] > key[b]
     m = p.reshape(-1)[int(np.argmax(key))]
-    floor_ratio = np.float32(min_ratio) * m  # one fp32 multiply
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):  # (m may be +inf or a NaN: the rule holds on every bit pattern)
+        floor_ratio = np.float32(0.0) if np.float32(min_ratio) == 0 else np.float32(min_ratio) * m  # no threshold, or one fp32 multiply
     assert floor_ratio.dtype == np.float32
     padded = np.zeros((rows + 2 * radius, cols + 2 * radius), np.uint64)  # (0 is below every key of the grid)
     padded[radius: radius + rows, radius: radius + cols] = key
@@ -82,14 +83,16 @@ def all_peaks(frame, rows, cols, radius, min_power, min_ratio):
     for dr in range(2 * radius + 1):
         for dc in range(2 * radius + 1):
             best = np.maximum(best, padded[dr: dr + rows, dc: dc + cols])
-    peak = (key == best) & (p > 0) & (p >= np.float32(min_power)) & (p >= floor_ratio)
+    with np.errstate(invalid="ignore"):
+        peak = (key == best) & (p > 0) & (p >= np.float32(min_power)) & (p >= floor_ratio)
     return np.sort(key[peak])[::-1]
 
 
 def offset(a, b, c):
     a, b, c = np.float64(a), np.float64(b), np.float64(c)
-    den = a - 2.0 * b + c
-    d = 0.5 * (a - c) / den if den < 0 else np.float64(0.0)
+    with np.errstate(invalid="ignore", over="ignore"):  # (a +inf peak: den is -inf or a NaN, and the offset 0)
+        den = a - 2.0 * b + c
+        d = 0.5 * (a - c) / den if den < 0 else np.float64(0.0)
     return min(max(d, -0.5), 0.5)
 
 

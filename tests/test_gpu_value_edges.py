@@ -2,8 +2,12 @@
 and up to overflowing squares, signed zeros, and infinities / NaN in a few samples (value_edges.py defines the tiers;
 test_value_edges_cpu.py checks that they are what they claim).  The default mode must give the IEEE restatement's pre-epilogue sums bit
 for bit on all of them -- gradual underflow included: a kernel, a build flag or a kernel descriptor that flushes subnormals fails here
-and nowhere else -- and powers within the flat 1e-5 (exactly 0 and +inf where the restatement says so).  AWPU_MATH_F32_FAST must be
-exactly invariant under powers of two.  In both modes a bad frame must stay inside its own slot of a batch.
+and nowhere else -- and powers within the flat 1e-5 (exactly 0 and +inf where the restatement says so).  Two tiers put subnormal,
+non-zero powers through the epilogue: at `dusk` the division by 256 * usable rounds into the subnormal range (powers within the flat
+1e-5 still), at `dim` every square is subnormal (powers within one unit of 2^-149, derived in gpu_value_edges_check.py, and none 0):
+a flushing square, a flushing add tree or a reciprocal-multiply in place of the division fails there.  AWPU_MATH_F32_FAST must be
+exactly invariant under powers of two, and within one unit of 2^-149 of its own scaled powers at those two tiers.  In both modes a
+bad frame must stay inside its own slot of a batch.
 
 One child process per forced AWPU_SHAPE (the library reads it once per process; gpu_value_edges_check.py); the child compares with the
 oracle itself and reports the kernel the handle ran, which must be the one the case is about."""
@@ -18,9 +22,9 @@ import pytest
 REPO = Path(__file__).resolve().parent.parent
 pytestmark = pytest.mark.gpu
 
-GRID = ["x0", "small", "big", "top", "under", "sub", "zeros", "nonfinite", "isolation"]  # batch 3: zeros holds both kinds
-SINGLE = ["x0", "small", "big", "top", "under", "sub", "zeros", "zero_row", "nonfinite"]
-FAST = ["x0", "small", "big", "top", "under", "sub", "isolation"]
+GRID = ["x0", "small", "big", "top", "dusk", "dim", "under", "sub", "zeros", "nonfinite", "isolation"]  # batch 3: zeros holds both kinds
+SINGLE = ["x0", "small", "big", "top", "dusk", "dim", "under", "sub", "zeros", "zero_row", "nonfinite"]
+FAST = ["x0", "small", "big", "top", "dusk", "dim", "under", "sub", "isolation"]
 
 # id: AWPU_SHAPE (None: the dispatch rule), case of value_edges.CASES, math, interpolation, checks, the kernel that must have run, extras
 CASES = {
@@ -47,7 +51,7 @@ CASES = {
     "fast_single_small": ("single_small", "grid37", "fast", "lerp", FAST, "single_small", {}),
     "fast_fir8_planes": ("fir8_planes", "grid37", "fast", "fir8", FAST, "fir8_planes", {}),
     "fast_fir8": (None, "grid37", "fast", "fir8", FAST, "fir8", {}),
-    # ---- awpu_hip_beams on the under and sub tiers
+    # ---- awpu_hip_beams on the dusk, dim, under and sub tiers
     "beams": (None, None, None, None, ["beams"], "beams", {}),
 }
 

@@ -9,6 +9,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+import util
 import value_edges as V
 
 REPO = Path(__file__).resolve().parent.parent
@@ -22,18 +23,70 @@ def case_of(name):
 
 
 @functools.lru_cache(maxsize=None)
-def swept(name, tier):
+def swept(name, tier, interp="lerp"):
     """(power, sums) of frame 0 of a tier; computed once, left unchanged."""
     from oracle import oracle_py
 
-    power, sums = V.oracle_sums(oracle_py, case_of(name), case_of(name).tier(tier)[0])
+    fir = util.synthetic_fir_table() if interp == "fir8" else None
+    power, sums = V.oracle_sums(oracle_py, case_of(name), case_of(name).tier(tier)[0], fir)
     power.setflags(write=False)
     sums.setflags(write=False)
     return power, sums
 
 
-def subnormal(x):
-    return (np.abs(x) < V.TINY) & (x != 0)
+subnormal = V.subnormal
+
+
+def epilogue_tier_conditions(tier, power, sums, divisor):
+    """What value_edges.py says of the dusk and dim tiers, on one oracle result; -> figures to print."""
+    assert not subnormal(sums).any(), (tier, "a pre-epilogue sum that is not zero is subnormal")
+    assert (subnormal(power)).all(), (tier, "an oracle power is zero or normal", V.units(power).min(), V.units(power).max())
+    assert V.same_bits(V.epilogue32(sums, divisor, "forward"), power), (tier, "the numpy restatement is not the oracle's epilogue")
+    worst = 0.0
+    for order in ("reversed", "pairwise"):
+        again = V.epilogue32(sums, divisor, order)
+        if tier == "dim":  # the sum of squares is a whole number of units below 2^24: exact in any order
+            assert V.same_bits(again, power), (tier, order, int((V.bits(again) != V.bits(power)).sum()))
+        else:
+            worst = max(worst, util.power_rel_err_unfloored(again, power))
+            assert worst <= util.POWER_RTOL, (tier, order, worst)
+    if tier == "dim":
+        assert V.units(power).max() * divisor < 2 ** 24, (tier, "the sum of squares may round")
+    return dict(units_min=float(V.units(power).min()), units_max=float(V.units(power).max()), reordered_rel=worst)
+
+
+# every (case, interpolation) the GPU cases of test_gpu_value_edges.py sweep
+SWEPT = [(name, "lerp") for name in V.CASES] + [("grid37", "fir8")]
+
+
+@pytest.mark.parametrize("name,interp", SWEPT)
+def test_the_epilogue_tiers_are_what_they_claim(oracle, name, interp):
+    """dusk and dim: sums normal, every oracle power subnormal and not 0; the epilogue restated in float32 numpy on the oracle's
+    sums, with the squares added in reversed and in pairwise order, stays within the flat 1e-5 at dusk and is the oracle's bits
+    at dim, where the sum of squares is a whole number of 2^-149 below 2^24."""
+    assert not V.host_flushes()
+    case = case_of(name)
+    p0, _ = swept(name, "x0", interp)
+    for tier in V.EPILOGUE:
+        power, sums = swept(name, tier, interp)
+        seen = epilogue_tier_conditions(tier, power, sums, 256 * len(case.index))
+        print(name, interp, tier, seen)
+        # the powers are the scaled ones rounded onto the subnormal grid, give or take the roundings below it
+        assert np.abs(V.units(power) - V.units(V.ldexp32(p0, 2 * V.SCALED[tier]))).max() <= 1.0, tier
+
+
+def test_the_epilogue_tiers_on_the_golden_beams(oracle):
+    """The same conditions for awpu_hip_beams' table (tests/golden/beams_c1.npz): its powers are divided by 256 alone."""
+    assert not V.host_flushes()
+    g = np.load(REPO / "tests" / "golden" / "beams_c1.npz")
+    x0 = util.hash_frames(64, 1024, seed=int(g["seed"]))[0]
+    for tier in V.EPILOGUE:
+        power, beams = oracle.particle_beams(V.scale_pow2(x0, V.BEAMS_SCALED[tier]), g["off"], g["frac"], g["index"])
+        seen = epilogue_tier_conditions(tier, power, beams, 256)
+        print("beams_c1", tier, V.BEAMS_SCALED[tier], seen)
+    # why the table's dusk is not the sweeps': at their k its powers are normal
+    power, _ = oracle.particle_beams(V.scale_pow2(x0, V.SCALED["dusk"]), g["off"], g["frac"], g["index"])
+    assert not subnormal(power).any()
 
 
 @pytest.mark.parametrize("name", list(V.CASES))

@@ -7,6 +7,10 @@ or X0 with a few samples replaced.  What a tier is, in terms of the IEEE restate
     small  k = -40   everything normal: sums and powers scale exactly
     big    k = +55   the same
     top    k = +120  sums finite and exactly scaled, every square overflows: every power +inf
+    dusk   k = -56   sums and most squares normal; the division by 256 * usable rounds into the subnormal range: every power
+                     subnormal and none 0 (about 1 M to 4.5 M units of 2^-149)
+    dim    k = -64   sums normal, every non-zero square subnormal, every power subnormal and none 0 (16 to 68 units); the sum of
+                     squares is a whole number of units below 2^24, so it is exact in any order
     under  k = -100  samples normal (or 0); differences and products partly subnormal; every power 0
     sub    k = -120  every non-zero sample subnormal, the sums subnormal; every power 0
     zeros            a frame of -0.0, and X0 with one active mic's row set to -0.0
@@ -24,8 +28,15 @@ import numpy as np
 
 import util
 
-SCALED = {"small": -40, "big": 55, "top": 120, "under": -100, "sub": -120}
+SCALED = {"small": -40, "big": 55, "top": 120, "dusk": -56, "dim": -64, "under": -100, "sub": -120}
+EPILOGUE = ("dusk", "dim")      # the tiers whose powers are subnormal and not 0: what the epilogue does below the normal range
+# awpu_hip_beams divides by 256 alone, not by 256 * usable: on the golden beams_c1 table 2^-56 X0 gives normal powers (93 M to 239 M
+# units of 2^-149; the smallest normal is 8.4 M).  No single k serves both: the table needs k <= -59 for subnormal powers, and below
+# k = -57 the sweeps' powers are so few units that a reordered sum of squares moves them by more than the flat 1e-5.  So the beams'
+# dusk is k = -59 -- 1.45 M to 3.73 M units, the band the sweeps' dusk is in -- and its dim is the sweeps' (1416 to 3642 units).
+BEAMS_SCALED = {"dusk": -59, "dim": -64}
 TINY = np.float32(2.0 ** -126)  # the smallest normal
+UNIT = 2.0 ** -149              # the subnormal step (a double: units() counts in it exactly)
 
 
 def host_flushes() -> bool:
@@ -47,6 +58,38 @@ def ldexp32(x: np.ndarray, k: int) -> np.ndarray:
     """ldexp in float32 (rounds once; exact wherever the result is normal)."""
     with np.errstate(under="ignore", over="ignore"):
         return np.ldexp(np.asarray(x, np.float32), k).astype(np.float32)
+
+
+def units(x) -> np.ndarray:
+    """x in units of 2^-149, as doubles (exact for every float32)."""
+    return np.asarray(x, np.float64) / UNIT
+
+
+def subnormal(x) -> np.ndarray:
+    return (np.abs(x) < TINY) & (x != 0)
+
+
+def epilogue32(sums: np.ndarray, divisor: int, order: str) -> np.ndarray:
+    """The epilogue of the restatement (oracle/das_oracle.c epilogue_f32) on sums [P, 256] in float32 numpy, one rounding per
+    operation: MA = out[i] * 0.5 - 0.25 * (out[i + 1] + out[i - 1]) for i = 1 .. 254, the sum of MA^2 in the order `forward` (the
+    restatement's own), `reversed` or `pairwise` (a tree over neighbours), then one division by `divisor` (256 * usable)."""
+    assert not host_flushes()
+    s = np.asarray(sums, np.float32)
+    with np.errstate(under="ignore", over="ignore", invalid="ignore"):
+        ma = s[:, 1:255] * np.float32(0.5) - np.float32(0.25) * (s[:, 2:256] + s[:, 0:254])
+        sq = ma * ma
+        assert sq.dtype == np.float32
+        if order == "pairwise":
+            while sq.shape[1] > 1:
+                if sq.shape[1] % 2:
+                    sq = np.concatenate([sq, np.zeros((len(sq), 1), np.float32)], axis=1)
+                sq = sq[:, 0::2] + sq[:, 1::2]
+            acc = sq[:, 0]
+        else:
+            acc = np.zeros(len(sq), np.float32)
+            for i in (range(sq.shape[1]) if order == "forward" else range(sq.shape[1] - 1, -1, -1)):
+                acc = acc + sq[:, i]
+        return (acc / np.float32(divisor)).astype(np.float32)
 
 
 def bits(x: np.ndarray) -> np.ndarray:
