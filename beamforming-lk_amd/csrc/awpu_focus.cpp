@@ -53,6 +53,7 @@ int awpu_hip_range(awpu_hip_t *h, const float *d_frame, const double *theta, con
         return fail(AWPU_ERR_RANGE, "history shorter than 513 samples: a focused delay can read outside it");
     }
     AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
+    if (int rc = enter_stream(h, h->stream)) return rc;
     if (int rc = ensure_track_index(h)) return rc;
     const size_t angles = align16((size_t) n_src * sizeof(double)), powers = (size_t) n_src * n_dist * sizeof(float);
     if (int rc = h->d_track.ensure(2 * angles + powers)) return rc;

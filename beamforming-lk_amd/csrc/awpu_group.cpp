@@ -41,6 +41,7 @@ void reset_union_window(awpu_hip *g) {
 
 // host frames: every part uploads them itself and sends its pixels' powers into the caller's image
 int enqueue_host_parts(awpu_hip *g, const float *frames, int batch, float *power) {
+    if (const int rc = group_enter_host(g); rc != AWPU_OK) return rc;
     return for_each_part(g, [&](awpu_hip *part) {
         AWPU_CTX(part);
         const int r = enqueue_host_process(part, frames, batch);
@@ -142,6 +143,8 @@ int create_group(awpu_hip_t **out, const awpu_hip_cfg &c) {
     AWPU_HIP_TRY(hipSetDevice(c.devices[0]));
     const char *what = "group event creation";
     int rc = g->group.ev_fan.ensure(hipEventDisableTiming, what);
+    if (rc == AWPU_OK) rc = g->ev_order.ensure(hipEventDisableTiming, what);
+    g->last_stream = g->group.parts[0]->stream;
     for (int b = 0; b < 2 && rc == AWPU_OK; b++) rc = g->group.ev_staged[b].ensure(hipEventDisableTiming, what);
     // a staged part's ev_tile_free[] is recorded on the CALLER's stream (devices[0]) and only waited for on the part's own:
     // an event must be recorded on a stream of the device it was created on, so these belong to devices[0], not the part's
@@ -186,6 +189,19 @@ int group_set_fir_table(awpu_hip *g, const float *coeffs) {
     return for_each_part(g, [&](awpu_hip *part) { return awpu_hip_set_fir_table(part, coeffs); });
 }
 
+// enter_stream (awpu_hip.cpp) for the group's host forms.  They enqueue on every part's own stream, so behind a device-form call on a
+// caller's stream -- whose tile copies still read the parts' d_power there -- every part's stream waits, not only the first's.  (The
+// other way round enter_stream itself serves: the caller's stream waits for the first part's, and the fan-out orders the rest.)
+int group_enter_host(awpu_hip *g) {
+    const hipStream_t own = g->group.parts[0]->stream;
+    if (g->last_stream == own) return AWPU_OK;
+    AWPU_HIP_TRY(hipSetDevice(g->cfg.devices[0]));
+    AWPU_HIP_TRY(hipEventRecord(g->ev_order, g->last_stream));
+    for (awpu_hip *part : g->group.parts) AWPU_HIP_TRY(hipStreamWaitEvent(part->stream, g->ev_order, 0));
+    g->last_stream = own;
+    return AWPU_OK;
+}
+
 int group_process(awpu_hip *g, const float *frames, int batch, float *power) {
     const int rc = enqueue_host_parts(g, frames, batch, power);
     return rc != AWPU_OK ? rc : group_wait(g);
@@ -211,6 +227,7 @@ int group_wait(awpu_hip *g) {
 }
 
 int group_ingest_block(awpu_hip *g, const void *datagrams, int32_t stride_bytes) {  // every device keeps the whole ring (264 KB per block each, over its own PCIe link)
+    if (const int erc = group_enter_host(g); erc != AWPU_OK) return erc;
     const int rc = for_each_part(g, [&](awpu_hip *part) {
         AWPU_CTX(part);
         return enqueue_ingest(part, datagrams, stride_bytes);
@@ -224,6 +241,7 @@ int group_ingest_block(awpu_hip *g, const void *datagrams, int32_t stride_bytes)
 }
 
 int group_process_ring(awpu_hip *g, float *power) {  // every device sweeps its pixels of its own ring's snapshot
+    if (const int erc = group_enter_host(g); erc != AWPU_OK) return erc;
     const int rc = for_each_part(g, [&](awpu_hip *part) {
         AWPU_CTX(part);
         int r = check_ready(part, 1);
@@ -237,6 +255,11 @@ int group_process_ring(awpu_hip *g, float *power) {  // every device sweeps its 
 }
 
 int group_synchronize(awpu_hip *g) {
+    if (const hipStream_t own = g->group.parts[0]->stream; g->last_stream != own) {  // a device-form call's tile copies, on its caller's stream
+        AWPU_HIP_TRY(hipSetDevice(g->cfg.devices[0]));
+        AWPU_HIP_TRY(hipStreamSynchronize(g->last_stream));
+        g->last_stream = own;
+    }
     return for_each_part(g, [](awpu_hip *part) {
         AWPU_HIP_TRY(hipSetDevice(part->cfg.device));
         AWPU_HIP_TRY(hipStreamSynchronize(part->copy_stream));
@@ -515,7 +538,9 @@ int awpu::host::group_process_device(awpu_hip *g, const float *d_frames, int bat
     Group &grp = g->group;
     AWPU_HIP_TRY(hipSetDevice(g->cfg.devices[0]));
     Fan f{g, stream ? stream : (hipStream_t) grp.parts[0]->stream, batch};
-    int rc = for_each_part(g, [&](awpu_hip *part) {
+    // behind the group's last call: its tile copies read the parts' d_power on that call's stream, its pack pass wrote grp.packed there
+    int rc = enter_stream(g, f.s);
+    if (rc == AWPU_OK) rc = for_each_part(g, [&](awpu_hip *part) {
         AWPU_CTX(part);
         return check_ready(part, batch);  // (tables packed: every part's window is known)
     });

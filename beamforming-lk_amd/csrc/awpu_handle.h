@@ -352,6 +352,11 @@ struct awpu_hip {
     Stream copy_stream;
     Event ev_copied[2];
     bool in_flight = false;                 // awpu_hip_process_async without its awpu_hip_wait yet
+    // call order across streams (awpu_hip.h, "Streams" (c); enter_stream below): the stream the handle's last call enqueued its
+    // work on -- the handle's own from creation and after awpu_hip_synchronize; a group's: its first part's, there -- and the
+    // event that takes the next call's stream behind it where that is another stream
+    hipStream_t last_stream = nullptr;
+    Event ev_order;
     // runs of blocks (awpu_runs.cpp), by piece: piece i's history [n_streams][768 + 256 * piece] in blk_hist.d[i & 1], its windows
     // in d_blk_frames; the host forms stage piece i's input in pinned blk_in.h[i & 1], upload it to blk_in.d[i & 1] on copy_stream
     // and bring its powers back through pinned blk_out.h[i & 1]
@@ -483,6 +488,8 @@ int enqueue_host_process(awpu_hip *h, const float *frames, int batch, const Band
 int enqueue_power_to_host(awpu_hip *h, int batch, float *power, size_t pitch);
 int enqueue_ingest(awpu_hip *h, const void *datagrams, int32_t stride_bytes);
 int check_ready(awpu_hip *h, int batch);
+int enter_stream(awpu_hip *h, hipStream_t s);  // the call that is about to enqueue on `s`, behind the handle's last call
+inline hipStream_t stream_of(const awpu_hip *h, void *stream) { return stream ? static_cast<hipStream_t>(stream) : (hipStream_t) h->stream; }
 extern const char *const kBandHistory;  // what AWPU_ERR_RANGE says where the bands' history does not fit a snapshot
 int ensure_power(awpu_hip *h, size_t need_power);
 int ensure_ring(awpu_hip *h);
@@ -533,6 +540,7 @@ int group_process(awpu_hip *g, const float *frames, int batch, float *power);
 int group_process_async(awpu_hip *g, const float *frames, int batch, float *power);
 int group_wait(awpu_hip *g);
 int group_process_device(awpu_hip *g, const float *d_frames, int batch, float *d_power, hipStream_t stream);
+int group_enter_host(awpu_hip *g);  // enter_stream for a group's host-form calls, which enqueue on the parts' own streams
 int group_ingest_block(awpu_hip *g, const void *datagrams, int32_t stride_bytes);
 int group_process_ring(awpu_hip *g, float *power);
 int group_synchronize(awpu_hip *g);

@@ -142,6 +142,23 @@ int check_ready(awpu_hip *h, int batch) {
     return AWPU_OK;
 }
 
+// Call order across streams, (c) of the stream contract in awpu_hip.h: every entry point that enqueues work comes through here with
+// the stream it resolved, the device current -- except the four that use nothing of the handle's but its tables (awpu_hip_pack_frames,
+// _heatmap_u8_device, _find_peaks_device, _expose_rows_device: they may run beside the handle's other work).  The handle's scratch
+// (d_pack, the item queues, d_band, d_power, the runs' buffers, the ring) has one owner at a time because a call on another stream
+// than the last one starts behind an event recorded on that last stream.  The same stream again -- every loop that drives a handle
+// from one stream -- records and awaits nothing.
+int enter_stream(awpu_hip *h, hipStream_t s) {
+    if (s == h->last_stream) return AWPU_OK;
+    if (h->last_stream) {
+        if (const int rc = h->ev_order.ensure(); rc != AWPU_OK) return rc;
+        AWPU_HIP_TRY(hipEventRecord(h->ev_order, h->last_stream));
+        AWPU_HIP_TRY(hipStreamWaitEvent(s, h->ev_order, 0));
+    }
+    h->last_stream = s;
+    return AWPU_OK;
+}
+
 int ensure_power(awpu_hip *h, size_t need_power) { return ensure_seen_by_live_graphs(h, h->d_power, need_power); }
 
 // frames per sweep launch of a host batch: large batches go up in pieces of whole frame pairs, so that piece k+1 crosses PCIe
@@ -154,6 +171,7 @@ int host_piece(int batch) {
 // upload of host frames + the sweep into h->d_power, all on h->stream, nothing waited for
 int enqueue_host_process(awpu_hip *h, const float *frames, int batch, const BandSet *given) {
     int rc = check_ready(h, batch);
+    if (rc == AWPU_OK) rc = enter_stream(h, h->stream);
     if (rc != AWPU_OK) return rc;
     const BandSet bands = given ? *given : own_band(h);  // several: band b's powers of the batch at d_power + b * batch * pixel_count
     if (bands.max_taps() - 1 > h->wstart) return fail(AWPU_ERR_RANGE, kBandHistory);
@@ -329,6 +347,7 @@ namespace {
 // first: what ships).
 int live_host_call(awpu_hip *h, const float *frames, float *power) {
     int rc = check_ready(h, 1);
+    if (rc == AWPU_OK) rc = enter_stream(h, h->stream);
     if (rc != AWPU_OK) return rc;
     const bool compact = h->compact_hist > 0;
     const int dev_hist = compact ? h->compact_hist : h->cfg.hist;
@@ -496,7 +515,8 @@ int enqueue_ingest(awpu_hip *h, const void *datagrams, int32_t stride_bytes) {
     if (h->cfg.hist != AWPU_HIST || h->cfg.n_streams > 256) return invalid("ingest needs hist 1024 and <= 256 streams");
     if (stride_bytes < AWPU_DATAGRAM_BYTES) return invalid("datagram stride below 1032 bytes");
     AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
-    const int rc = ensure_ring(h);
+    int rc = enter_stream(h, h->stream);
+    if (rc == AWPU_OK) rc = ensure_ring(h);
     if (rc != AWPU_OK) return rc;
     // tight copy of the 256 datagrams (the header travels too: 8 bytes each, ignored like the
     // reference ignores msg.counter, pipeline.cpp:264-267)
@@ -591,6 +611,7 @@ int awpu_hip_create(awpu_hip_t **out, const awpu_hip_cfg *cfg) {
     int rc = h->stream.ensure(what);
     if (rc == AWPU_OK) rc = h->ev_begin.ensure(hipEventDefault, what);
     if (rc == AWPU_OK) rc = h->ev_end.ensure(hipEventDefault, what);
+    h->last_stream = h->stream;
     if (rc != AWPU_OK) {
         awpu_hip_destroy(h);
         return rc;
@@ -708,7 +729,8 @@ int awpu_hip_calibrate_device(awpu_hip_t *h, const float *d_frame, int32_t array
     if (array < 0 || (array + 1) * AWPU_ELEMENTS > h->cfg.n_streams) return invalid("array outside the streams");
     if (h->cfg.hist > 16384) return invalid("history too long for the calibration kernel");
     AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+    hipStream_t s = stream_of(h, stream);
+    if (const int rc = enter_stream(h, s); rc != AWPU_OK) return rc;
     return calibrate_rows(h, d_frame + (size_t) array * AWPU_ELEMENTS * h->cfg.hist, h->cfg.hist, h->cfg.hist,
                           reference_power_level, index, correction, median, usable, s);
 }
@@ -723,6 +745,7 @@ int awpu_hip_calibrate_host(awpu_hip_t *h, const float *frame, int32_t array, fl
     if (h->cfg.hist > 16384) return invalid("history too long for the calibration kernel");
     if (busy) return fail(AWPU_ERR_STATE, "an awpu_hip_process_async call is in flight on this handle: awpu_hip_wait first");
     AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
+    if (const int rc = enter_stream(h, h->stream); rc != AWPU_OK) return rc;
     // only the array's 64 streams travel; they share the frame staging buffer of awpu_hip_process
     const size_t need = (size_t) AWPU_ELEMENTS * h->cfg.hist;
     if (const int rc = h->d_frames.ensure(need); rc != AWPU_OK) return rc;
@@ -742,6 +765,7 @@ int awpu_hip_calibrate_ring(awpu_hip_t *h, int32_t array, float reference_power_
         return fail(AWPU_ERR_STATE, "no block ingested yet");
     }
     AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
+    if (const int rc = enter_stream(h, h->stream); rc != AWPU_OK) return rc;
     return calibrate_rows(h, h->d_ring + (size_t) array * AWPU_ELEMENTS * 2048 + h->ring_pos, 2048, AWPU_HIST,
                           reference_power_level, index, correction, median, usable, h->stream);
 }
@@ -779,6 +803,7 @@ int awpu_hip_beams(awpu_hip_t *h, const float *d_frame, const int32_t *off, cons
         }
     }
     AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
+    if (const int rc = enter_stream(h, h->stream); rc != AWPU_OK) return rc;
     if (const int rc = h->d_beam_lut.ensure(entries.size()); rc != AWPU_OK) return rc;
     if (const int rc = h->d_beam_out.ensure((size_t) n_dir * (1 + awpu::kSamples)); rc != AWPU_OK) return rc;
     // [n] powers then [n][256] beams, n = the directions the buffer was allocated for (its layout follows its allocation)
@@ -833,6 +858,7 @@ int awpu_hip_steer_table_device(awpu_hip_t *h, const double *theta, const double
     if (h->antenna.empty()) return fail(AWPU_ERR_STATE, "antenna not set (awpu_hip_set_antenna)");
     const int n = (int) (h->antenna.size() / 3);
     AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
+    if (int rc = enter_stream(h, h->stream)) return rc;
     const size_t angles = align16((size_t) n_dir * sizeof(double)), table = (size_t) n_dir * n;
     if (int rc = h->d_track.ensure(2 * angles + table * (sizeof(int32_t) + sizeof(float)))) return rc;
     double *d_theta = (double *) h->d_track.get(), *d_phi = (double *) (h->d_track + angles);
@@ -865,6 +891,7 @@ int awpu_hip_track(awpu_hip_t *h, const float *d_frame, awpu_particle_t *p, int3
         return fail(AWPU_ERR_RANGE, "history shorter than 513 samples: a steered delay can read outside it");
     }
     AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
+    if (int rc = enter_stream(h, h->stream)) return rc;
     const int U = h->usable();
     if (int rc = ensure_track_index(h)) return rc;
     const size_t particles = (size_t) n * sizeof(awpu_particle_t), head = align16(particles + sizeof(double));
@@ -904,6 +931,7 @@ int awpu_hip_set_fir_table(awpu_hip_t *h, const float *coeffs) {
     // (on the device: the caller's 101 rows followed by zero rows up to kFir8CoeffRows -- the plane kernel's padding
     // entries name row 101, and its entry requests run a few items past a row's end, where any 7-bit row may stand)
     if (const int rc = h->d_fir.ensure(awpu::kFir8CoeffRows * 8); rc != AWPU_OK) return rc;
+    if (const int rc = enter_stream(h, h->stream); rc != AWPU_OK) return rc;
     AWPU_HIP_TRY(hipStreamSynchronize(h->stream));  // (a sweep still reading the old coefficients)
     AWPU_HIP_TRY(hipMemset(h->d_fir, 0, awpu::kFir8CoeffRows * 8 * sizeof(float)));
     AWPU_HIP_TRY(hipMemcpy(h->d_fir, coeffs, 101 * 8 * sizeof(float), hipMemcpyHostToDevice));
@@ -980,9 +1008,10 @@ int awpu_hip_process_device(awpu_hip_t *h, const float *d_frames, int32_t batch,
     if (!h) return invalid("null handle");
     if (!d_frames || !d_power) return invalid("null argument");
     if (is_group(h)) return group_process_device(h, d_frames, batch, d_power, static_cast<hipStream_t>(stream));
-    const int rc = check_ready(h, batch);
+    int rc = check_ready(h, batch);
+    hipStream_t s = stream_of(h, stream);
+    if (rc == AWPU_OK) rc = enter_stream(h, s);
     if (rc != AWPU_OK) return rc;
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
     TimingOff untimed(h);  // asynchronous path: the caller times its own stream
     return band_sweep(h, d_frames, (long long) h->cfg.n_streams * h->cfg.hist, h->cfg.hist, h->wstart, batch, d_power, s, kFull);
 }
@@ -1011,7 +1040,8 @@ int awpu_hip_process_bands_device(awpu_hip_t *h, const float *d_frames, int32_t 
     rc = check_ready(h, batch);
     if (rc != AWPU_OK) return rc;
     if (bands.max_taps() - 1 > h->wstart) return fail(AWPU_ERR_RANGE, kBandHistory);
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+    hipStream_t s = stream_of(h, stream);
+    if (rc = enter_stream(h, s); rc != AWPU_OK) return rc;
     TimingOff untimed(h);  // asynchronous path: the caller times its own stream
     return band_sweep(h, bands, d_frames, (long long) h->cfg.n_streams * h->cfg.hist, h->cfg.hist, h->wstart, batch, d_power,
                       (long long) batch * h->cfg.pixel_count, s, kFull);
@@ -1026,7 +1056,8 @@ int awpu_hip_process_device_sums(awpu_hip_t *h, const float *d_frames, int32_t b
     if (rc != AWPU_OK) return rc;
     const bool exact_fir8 = h->cfg.math == AWPU_MATH_F32_EXACT && h->cfg.interp == AWPU_INTERP_FIR8;  // das_fir8_kernel, the reference's rounding
     if (!h->exact_pairs_ok && !exact_fir8) return fail(AWPU_ERR_STATE, "the pre-epilogue sums need AWPU_MATH_F32_EXACT");
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+    hipStream_t s = stream_of(h, stream);
+    if (const int erc = enter_stream(h, s); erc != AWPU_OK) return erc;
     TimingOff untimed(h);
     h->sums_out = d_sums;
     const int lrc = band_sweep(h, d_frames, (long long) h->cfg.n_streams * h->cfg.hist, h->cfg.hist, h->wstart, batch, d_power, s, kFull);
@@ -1086,6 +1117,7 @@ int awpu_hip_live_block(awpu_hip_t *h, const void *datagrams, int32_t stride_byt
     if (h && h->in_flight) return fail(AWPU_ERR_STATE, "an awpu_hip_process_async call is in flight on this handle: awpu_hip_wait first");
     if (h && !h->band.empty()) return fail(AWPU_ERR_STATE, "the live block's captured step takes no band: clear it (awpu_hip_set_band) or ingest and sweep the ring");
     int rc = check_ready(h, 1);
+    if (rc == AWPU_OK) rc = enter_stream(h, h->stream);  // (before a capture opens: the steps' own calls then find nothing to record)
     if (rc != AWPU_OK) return rc;
     const int n = h->cfg.n_pixels;
     if (h->cfg.pixel_count != n) return invalid("the display step needs the whole grid on this handle");
@@ -1180,6 +1212,7 @@ int awpu_hip_process_ring(awpu_hip_t *h, float *power) {
     if (!power) return invalid("null argument");
     if (is_group(h)) return group_process_ring(h, power);
     int rc = check_ready(h, 1);
+    if (rc == AWPU_OK) rc = enter_stream(h, h->stream);
     if (rc != AWPU_OK) return rc;
     if (!h->d_ring) {
         return fail(AWPU_ERR_STATE, "no block ingested yet");
@@ -1202,6 +1235,7 @@ int awpu_hip_ring_snapshot(awpu_hip_t *h, float *frames) {
         return fail(AWPU_ERR_STATE, "no block ingested yet");
     }
     AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
+    if (const int rc = enter_stream(h, h->stream); rc != AWPU_OK) return rc;
     AWPU_HIP_TRY(hipMemcpy2DAsync(frames, AWPU_HIST * sizeof(float), h->d_ring + h->ring_pos, 2048 * sizeof(float),
                                   AWPU_HIST * sizeof(float), h->cfg.n_streams, hipMemcpyDeviceToHost, h->stream));
     AWPU_HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1214,7 +1248,7 @@ int awpu_hip_heatmap_u8_device(awpu_hip_t *h, const float *d_power, int32_t n, i
     AWPU_CTX(h);
     if (!h || !d_power || !d_peak || !d_pix || n < 1 || batch < 1 || batch > 65535) return invalid("bad argument");
     AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+    hipStream_t s = stream_of(h, stream);  // (no enter_stream: nothing of the handle's is used)
     AWPU_HIP_TRY(awpu::launch_heatmap(d_power, n, batch, d_peak, peak_given != 0, d_pix, s));
     return AWPU_OK;
 }
@@ -1227,7 +1261,8 @@ int awpu_hip_upscale_u8_device(awpu_hip_t *h, const uint8_t *d_pix, int32_t rows
     if (!h || !d_pix || !d_out || rows < 1 || cols < 1 || batch < 1 || batch > 65535) return invalid("bad argument");
     if (out_rows < rows || out_cols < cols || out_rows > 65535) return invalid("upscale only: out >= in, out_rows <= 65535");
     AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+    hipStream_t s = stream_of(h, stream);
+    if (int rc = enter_stream(h, s)) return rc;  // (ensure_taps' wait for `s` is then a wait for every earlier reader of the taps)
     if (int rc = ensure_taps(h, rows, cols, out_rows, out_cols, s)) return rc;
     AWPU_HIP_TRY(awpu::launch_upscale(d_pix, rows, cols, batch, h->d_taps, d_colormap, d_out, out_rows, out_cols, s));
     return AWPU_OK;
@@ -1292,7 +1327,9 @@ int awpu_hip_pack_frames(awpu_hip_t *h, const float *d_frames, int32_t batch, fl
     awpu::FastPlan plan;
     const int rc = packed_plan(h, batch, &plan);
     if (rc != AWPU_OK) return rc;
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+    // No enter_stream: the pass reads the caller's frames and the mic list and writes the caller's buffer -- nothing of the handle's that
+    // a call changes --, and the root of a multi-GPU job runs it on a side stream BESIDE the sweep in progress on the same handle
+    hipStream_t s = stream_of(h, stream);
     // (Measured: a throttled variant of this pass -- few persistent workgroups, non-temporal accesses -- meant to be gentler
     // on the sweep it runs beside, slowed that sweep MORE the longer it lasted: 256 / 512 / 1024 workgroups cost the ingest
     // rank 0.90 / 0.55 / 0.35 ms per 1024-frame step against 0.23 ms for this full-speed pass.  Short and fast wins.)
@@ -1305,7 +1342,8 @@ int awpu_hip_process_packed(awpu_hip_t *h, const float *d_packed, int32_t batch,
     awpu::FastPlan plan;
     int rc = packed_plan(h, batch, &plan);
     if (rc != AWPU_OK) return rc;
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+    hipStream_t s = stream_of(h, stream);
+    if (rc = enter_stream(h, s); rc != AWPU_OK) return rc;
     TimingOff untimed(h);  // asynchronous path: the caller times its own stream
     // the shape awpu_hip_process_device takes for this batch, as long as that is a frame-pair shape (sweep_packed)
     // (the buffer is the caller's: awpu_hip_packed_bytes(batch) of it are taken to be there, and the sweep reads no further)
@@ -1317,6 +1355,9 @@ int awpu_hip_synchronize(awpu_hip_t *h) {
     if (!h) return invalid("null handle");
     if (is_group(h)) return group_synchronize(h);
     AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
+    // (the last call's stream, where that is the caller's: every earlier one is behind it, and the handle's own -- enter_stream)
+    if (h->last_stream != h->stream) AWPU_HIP_TRY(hipStreamSynchronize(h->last_stream));
+    h->last_stream = h->stream;
     AWPU_HIP_TRY(hipStreamSynchronize(h->stream));
     return AWPU_OK;
 }

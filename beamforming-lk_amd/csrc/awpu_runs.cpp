@@ -207,7 +207,8 @@ int run_pieces(awpu_hip *h, const BlockRun &src, hipStream_t user, Consumer &c) 
     const int S = cfg.n_streams;
     const size_t P = (size_t) cfg.pixel_count;
     hipStream_t sw = host ? h->stream : (user ? user : h->stream);
-    rc = ensure_ring(h);
+    rc = enter_stream(h, sw);  // behind the handle's last call, whatever stream that was on (up and li follow sw: ev_blk_ring, ev_blk_hist)
+    if (rc == AWPU_OK) rc = ensure_ring(h);
     if (rc == AWPU_OK) rc = c.ensure(piece_max, compact ? h->wstart : 0, compact ? h->compact_hist : AWPU_HIST, sw);
     if (rc != AWPU_OK) return rc;
     hipStream_t up = host ? h->copy_stream : sw;
@@ -1178,7 +1179,8 @@ int awpu_hip_find_peaks_device(awpu_hip_t *h, const float *d_power, int32_t n_fr
     h = first_device(h);
     AWPU_CTX(h);
     AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
-    AWPU_HIP_TRY(awpu::launch_find_peaks(d_power, n_frames, *f, d_sources, d_count, stream ? static_cast<hipStream_t>(stream) : h->stream));
+    // (no enter_stream, here and in awpu_hip_expose_rows_device: nothing of the handle's is used)
+    AWPU_HIP_TRY(awpu::launch_find_peaks(d_power, n_frames, *f, d_sources, d_count, stream_of(h, stream)));
     return AWPU_OK;
 }
 
@@ -1243,7 +1245,7 @@ int awpu_hip_expose_rows_device(awpu_hip_t *h, const float *d_power, int32_t n_b
     AWPU_CTX(h);
     AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
     const awpu::ExposeWindows win{n_blocks, first - (e->length - 1), every, e->length};
-    AWPU_HIP_TRY(awpu::launch_expose(d_power, n_pixels, win, e->mode, d_carry, d_frames, stream ? static_cast<hipStream_t>(stream) : h->stream));
+    AWPU_HIP_TRY(awpu::launch_expose(d_power, n_pixels, win, e->mode, d_carry, d_frames, stream_of(h, stream)));
     return AWPU_OK;
 }
 

@@ -21,6 +21,28 @@
  *     (src/dsp/mimo.cpp:12).
  *   - there is NO CPU fallback: without a usable HIP device awpu_hip_create fails with
  *     AWPU_ERR_NO_DEVICE.
+ *
+ * Streams.  Every entry point that takes `stream` (a hipStream_t; NULL = the handle's own stream), in this header and in every
+ * header that includes it (the runs of blocks and what listens to, watches, finds in and integrates them), keeps these four rules:
+ *   (a) reads: it reads its device inputs only after everything enqueued earlier on `stream`;
+ *   (b) writes: its device outputs are complete for everything enqueued later on `stream`, and once the call has returned
+ *       the caller may enqueue on `stream` work that overwrites its inputs and its outputs;
+ *   (c) call order: the calls on one handle take effect in the order they were made, whatever stream each was enqueued on --
+ *       the host-form calls, which run on the handle's own stream, included.  No two calls ever use the device memory the
+ *       handle owns (packed frames, item queues, filtered frames, powers, the runs' buffers, the ring) at once: a call on
+ *       another stream than the handle's last call starts behind an event recorded on that last stream; a call on the same
+ *       stream records and awaits nothing.  For this the library records on the stream of the handle's LAST call at the
+ *       beginning of the next one: a stream passed to a handle must stay alive until a later call on that handle with
+ *       another stream has returned, or until awpu_hip_synchronize or awpu_hip_destroy.  Four entry points use no device
+ *       memory of the handle's besides its tables -- awpu_hip_pack_frames, awpu_hip_heatmap_u8_device, and the peak finder and the
+ *       row integrator on device buffers (the *_peaks_device and *_rows_device calls of their headers) -- and take no part in
+ *       this order: they follow their own `stream` alone and may run beside the handle's other calls (the root of a
+ *       multi-GPU job packs batch k+1 on a side stream while sweep k runs);
+ *   (d) none of this needs a host synchronisation by the caller.
+ * "Asynchronous" entry points return once their work is enqueued; those that bring results to the host (awpu_hip_calibrate_device,
+ * a listening run's listeners) wait for `stream` themselves before they return.  A device group (cfg.n_devices > 1) keeps the
+ * same rules on the caller's stream on devices[0].  The rules order the library's work; two host threads still may not
+ * be inside calls on one handle at once.
  */
 #ifndef AWPU_HIP_H
 #define AWPU_HIP_H
@@ -291,7 +313,8 @@ int awpu_hip_packed_bytes(awpu_hip_t *h, int32_t batch, uint64_t *bytes);
 int awpu_hip_pack_frames(awpu_hip_t *h, const float *d_frames, int32_t batch, float *d_packed, void *stream);
 int awpu_hip_process_packed(awpu_hip_t *h, const float *d_packed, int32_t batch, float *d_power, void *stream);
 
-/* blocks until everything enqueued through this handle has finished */
+/* blocks until everything enqueued through this handle has finished, on the handle's own streams and on the stream of its last
+ * call ("Streams" (c): every earlier call's stream is behind that one) */
 int awpu_hip_synchronize(awpu_hip_t *h);
 
 /* replaces: MIMOWorker::populateHeatmap (USE_DB 0), src/dsp/mimo.cpp:61-95, with the

@@ -51,7 +51,7 @@ int awpu_hip_process_blocks(awpu_hip_t *h, const void *datagrams, int32_t stride
 int awpu_hip_process_samples(awpu_hip_t *h, const float *samples, int64_t pitch, int32_t n_blocks, float *power);
 
 /* The same on device buffers: d_samples [n_streams][pitch] floats, d_power [n_blocks][pixel_count], enqueued on `stream`
- * (a hipStream_t, NULL = the handle's own); asynchronous like awpu_hip_process_device.  Later calls on the handle's ring
+ * (a hipStream_t, NULL = the handle's own; awpu_hip.h, "Streams"); asynchronous like awpu_hip_process_device.  Later calls on the handle's ring
  * are ordered after it. */
 int awpu_hip_process_samples_device(awpu_hip_t *h, const float *d_samples, int64_t pitch, int32_t n_blocks, float *d_power,
                                     void *stream);

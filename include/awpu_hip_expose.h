@@ -65,7 +65,7 @@ int awpu_hip_expose_rows(const float *power, int32_t n_blocks, int32_t n_pixels,
                          float *carry, float *frames);
 
 /* The same on device buffers (d_power, d_carry, d_frames in device memory), enqueued on `stream` (a hipStream_t, NULL = the
- * handle's own); asynchronous, like awpu_hip_find_peaks_device.  Needs no delay table: any power rows will do.  A device-group
+ * handle's own; awpu_hip.h, "Streams"); asynchronous, like awpu_hip_find_peaks_device.  Needs no delay table: any power rows will do.  A device-group
  * handle answers from its first device.  One thread owns its pixels through all rows of a window, so the add order is the
  * rule's by construction; no atomics, no cross-lane sums; the same bits as awpu_hip_expose_rows. */
 int awpu_hip_expose_rows_device(awpu_hip_t *h, const float *d_power, int32_t n_blocks, int32_t n_pixels, int32_t first, int32_t every,

@@ -78,7 +78,7 @@ typedef struct awpu_source {
 int awpu_hip_find_peaks(const float *power, int32_t n_frames, const awpu_find_t *f, awpu_source_t *sources, int32_t *count);
 
 /* The same on device buffers (d_power, d_sources, d_count in device memory), one workgroup per frame, enqueued on `stream` (a
- * hipStream_t, NULL = the handle's own); asynchronous, like awpu_hip_heatmap_u8_device.  Needs no delay table: any power rows
+ * hipStream_t, NULL = the handle's own; awpu_hip.h, "Streams"); asynchronous, like awpu_hip_heatmap_u8_device.  Needs no delay table: any power rows
  * will do, those of awpu_hip_process_device straight after it on the same stream for instance.  A device-group handle answers
  * from its first device.  Reads every frame (2 * radius + 1)^2 + max_sources times out of the cache; writes with plain vector
  * stores, no atomics. */

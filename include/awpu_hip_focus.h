@@ -103,7 +103,7 @@ int awpu_hip_range_pick(const float *power, int32_t n_src, const double *distanc
  * index = -1 and zeros (their range_power rows too).  Needs what awpu_hip_range needs besides the find run's requirements; the
  * refusals, the ring, `next_first` and mixing with the other run calls are exactly the find run's.  The range pass runs behind
  * each piece's peak pass while the piece's history is on the device; the device form takes its directions from d_sources on
- * the same stream and writes d_ranges / d_range_power in place. */
+ * the same stream and writes d_ranges / d_range_power in place (`stream`: awpu_hip.h, "Streams"). */
 int awpu_hip_locate_blocks(awpu_hip_t *h, const void *datagrams, int32_t stride_bytes, int32_t n_blocks, const awpu_watch_t *w,
                            const awpu_find_t *f, awpu_source_t *sources, int32_t *count, float *power, const double *distance,
                            int32_t n_dist, awpu_range_t *ranges, float *range_power);

@@ -71,7 +71,7 @@ int awpu_hip_listen_samples(awpu_hip_t *h, const float *samples, int64_t pitch, 
                             float *power);
 
 /* The same on device buffers: d_samples, d_audio [n][audio_pitch], d_trail (may be NULL) and d_power (may be NULL) in device
- * memory, written on `stream` (a hipStream_t, NULL = the handle's own) in the order of awpu_hip_process_samples_device; later
+ * memory, written on `stream` (a hipStream_t, NULL = the handle's own; awpu_hip.h, "Streams") in the order of awpu_hip_process_samples_device; later
  * calls on the handle's ring are ordered after it.  `listeners` is host memory like everywhere else: it is checked and uploaded
  * before anything is enqueued, and the call returns once the listeners' final state has been read back (80 bytes each), i.e.
  * after the work it enqueued on `stream`; no sample, audio or power crosses PCIe. */

@@ -72,7 +72,7 @@ int awpu_hip_spectral_compose(const float *power, int64_t band_pitch, int32_t n_
  *   AWPU_ERR_RANGE    max_b taps[b] - 1 exceeds the table's smallest `off` (the band's history rule, awpu_hip_band.h). */
 int awpu_hip_process_bands(awpu_hip_t *h, const float *frames, int32_t batch, const awpu_spectral_t *sp, float *power);
 
-/* The same on device buffers, enqueued on `stream` (a hipStream_t, NULL = the handle's own); asynchronous: power[b] is what
+/* The same on device buffers, enqueued on `stream` (a hipStream_t, NULL = the handle's own; awpu_hip.h, "Streams"); asynchronous: power[b] is what
  * awpu_hip_process_device writes with band b set. */
 int awpu_hip_process_bands_device(awpu_hip_t *h, const float *d_frames, int32_t batch, const awpu_spectral_t *sp, float *d_power,
                                   void *stream);

@@ -85,7 +85,7 @@ int awpu_hip_watch_samples(awpu_hip_t *h, const float *samples, int64_t pitch, i
                            uint8_t *big_image, float *power);
 
 /* The same on device buffers: d_samples, d_image, d_big_image and d_power in device memory, enqueued on `stream` (a hipStream_t,
- * NULL = the handle's own) in the order of awpu_hip_process_samples_device; asynchronous.  Later calls on the handle's ring are
+ * NULL = the handle's own; awpu_hip.h, "Streams") in the order of awpu_hip_process_samples_device; asynchronous.  Later calls on the handle's ring are
  * ordered after it.  Nothing crosses PCIe. */
 int awpu_hip_watch_samples_device(awpu_hip_t *h, const float *d_samples, int64_t pitch, int32_t n_blocks, const awpu_watch_t *w,
                                   uint8_t *d_image, uint8_t *d_big_image, float *d_power, void *stream);
