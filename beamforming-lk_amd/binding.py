@@ -74,7 +74,8 @@ PEER_SAME_DEVICE, PEER_DIRECT, PEER_HOST_STAGED = 0, 1, 2
 EXCHANGE_NONE, EXCHANGE_WINDOWS, EXCHANGE_PACKED_PAIRS = 0, 1, 2  # Stats.group_exchange
 # awpu_kernel_id (include/awpu_hip.h): Stats.kernel_variant after a launch
 KERNEL_NAMES = ("none", "quad", "pair", "pair_stationary", "quadh", "quadh_stationary", "single_db", "single_small", "fir8_planes",
-                "fir8", "exact_pair", "exact_verify", "tuning", "exact_quad", "exact_nd", "exact_ndh", "exact_ndh_stationary", "exact_ndp")
+                "fir8", "exact_pair", "exact_verify", "tuning", "exact_quad", "exact_nd", "exact_ndh", "exact_ndh_stationary", "exact_ndp",
+                "cohere")
 
 _lib: Optional[C.CDLL] = None
 
@@ -343,6 +344,32 @@ _EXPOSE_SIGNATURES = {
 }
 EXPOSE_SYMBOLS = tuple(_EXPOSE_SIGNATURES)
 
+# coherence heatmaps: the entry points of include/awpu_hip_cohere.h
+COHERE_WEIGHTED, COHERE_FACTOR = 0, 1
+
+
+class Cohere(C.Structure):
+    """awpu_cohere_t (include/awpu_hip_cohere.h)."""
+    _fields_ = [
+        ("show", C.c_int32),
+    ]
+
+
+_COHERE_TAIL = [*_WATCH_TAIL, C.POINTER(Cohere), C.POINTER(Find)]  # n_blocks, w, co, f
+_COHERE_SIGNATURES = {
+    "awpu_hip_cohere_host": (C.c_int, [_f32p, C.c_int32, C.c_int32, C.c_int32, _i32p, _f32p, C.c_int32, C.c_int32, _i32p, C.c_int32, _f32p,
+                                       _f32p, _f32p, _f32p, _f32p, _f32p]),
+    "awpu_hip_cohere": (C.c_int, [C.c_void_p, _f32p, C.c_int32, _f32p, _f32p, _f32p]),
+    "awpu_hip_cohere_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "awpu_hip_cohere_device_sums": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]),
+    "awpu_hip_cohere_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, *_COHERE_TAIL, _u8p, _u8p, _f32p, C.c_void_p, C.c_void_p]),
+    "awpu_hip_cohere_samples": (C.c_int, [C.c_void_p, _f32p, C.c_int64, *_COHERE_TAIL, _u8p, _u8p, _f32p, C.c_void_p, C.c_void_p]),
+    "awpu_hip_cohere_samples_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, *_COHERE_TAIL, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]),
+}
+COHERE_SYMBOLS = tuple(_COHERE_SIGNATURES)
+
 # numpy view of awpu_range_t: what range_pick, Engine.range and Engine.locate_* return (unused entries: index -1)
 RANGE_DTYPE = np.dtype([("index", "<i4"), ("power", "<f4"), ("distance", "<f8")], align=True)
 assert RANGE_DTYPE.itemsize == C.sizeof(Range) == 16
@@ -380,7 +407,8 @@ def load(build: bool = True) -> C.CDLL:
     lib = C.CDLL(str(path))
     for name, (res, args) in list(_SIGNATURES.items()) + list(_TRACK_SIGNATURES.items()) + list(_BLOCK_SIGNATURES.items()) + \
             list(_LISTEN_SIGNATURES.items()) + list(_WATCH_SIGNATURES.items()) + list(_FIND_SIGNATURES.items()) + list(_BAND_SIGNATURES.items()) + \
-            list(_FOCUS_SIGNATURES.items()) + list(_SPECTRAL_SIGNATURES.items()) + list(_EXPOSE_SIGNATURES.items()):
+            list(_FOCUS_SIGNATURES.items()) + list(_SPECTRAL_SIGNATURES.items()) + list(_EXPOSE_SIGNATURES.items()) + \
+            list(_COHERE_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -727,6 +755,46 @@ def expose_rows(power: np.ndarray, first: int, every: int, length: int, mode: in
                                        None if carry is None else _f32(carry), C.cast(C.c_void_p(frames.ctypes.data or 16), _f32p)),
            "awpu_hip_expose_rows")
     return frames, next_first
+
+
+def cohere_host(frames: np.ndarray, off: np.ndarray, frac: np.ndarray, index=None, gain=None, want_sums: bool = False):
+    """The rule of include/awpu_hip_cohere.h as executable C (awpu_hip_cohere_host): frames [batch, n_streams, hist] (or one
+    frame), off / frac [n_pixels, lut_stride], index = the active stream ids (default: all of the table's), gain [usable] in
+    their order or None.  -> (power, coherence, weighted) [batch, n_pixels], with want_sums also (sums, energy) [batch, n_pixels,
+    256]: out[] and e[] of every pixel; one frame in, rows without the batch axis out."""
+    frames = np.ascontiguousarray(frames, np.float32)
+    single = frames.ndim == 2
+    if single:
+        frames = frames[None]
+    off = np.ascontiguousarray(off, np.int32)
+    frac = np.ascontiguousarray(frac, np.float32)
+    if frames.ndim != 3 or off.ndim != 2 or off.shape != frac.shape:
+        raise ValueError("frames must be [batch, n_streams, hist], off and frac [n_pixels, lut_stride]")
+    index = np.arange(off.shape[1], dtype=np.int32) if index is None else np.ascontiguousarray(index, np.int32)
+    if gain is not None:
+        gain = np.ascontiguousarray(gain, np.float32)
+        if gain.shape != index.shape:
+            raise ValueError("gain must be [usable], in the active list's order")
+    batch, n_pixels = frames.shape[0], off.shape[0]
+    maps = [np.empty((batch, n_pixels), np.float32) for _ in range(3)]
+    wide = [np.empty((batch, n_pixels, 256), np.float32) for _ in range(2)] if want_sums else [None, None]
+    _check(load().awpu_hip_cohere_host(_f32(frames), batch, frames.shape[1], frames.shape[2], _i32(off), _f32(frac), off.shape[1], n_pixels,
+                                       _i32(index), len(index), None if gain is None else _f32(gain), *[_f32(m) for m in maps],
+                                       *[None if m is None else _f32(m) for m in wide]), "awpu_hip_cohere_host")
+    out = maps + wide if want_sums else maps
+    return tuple(m[0] for m in out) if single else tuple(out)
+
+
+class CohereResult:
+    """What Engine.cohere_blocks / cohere_samples hand back: .image, .big, .power as a WatchResult has them -- of the weighted
+    (or, with show=COHERE_FACTOR, the coherence) rows --, .sources and .count as a FindResult has them (None without `find`),
+    .next_first for the call that continues the run."""
+
+    def __init__(self, image, big, power, sources, count, next_first: int):
+        self.image, self.big, self.power, self.sources, self.count, self.next_first = image, big, power, sources, count, next_first
+
+    def __len__(self):
+        return len(next(a for a in (self.image, self.big, self.power, self.count) if a is not None))
 
 
 def band_design(lo_hz: float, hi_hz: float, taps: int = 63, sample_rate: float = 48828.125) -> np.ndarray:
@@ -1261,6 +1329,104 @@ class Engine:
                                                         None if f is None else C.byref(f), C.c_void_p(d_carry_ptr), C.c_void_p(d_image_ptr),
                                                         C.c_void_p(d_big_ptr), C.c_void_p(d_power_ptr), C.c_void_p(d_sources_ptr),
                                                         C.c_void_p(d_count_ptr), C.c_void_p(stream)), "awpu_hip_expose_samples_device")
+        return watch_count(n_blocks, first, every)[1]
+
+    def cohere(self, frames: np.ndarray, want=("power", "coherence", "weighted")):
+        """The coherence sweep of host frames [batch, n_streams, hist] (or one frame): -> a dict of the maps in `want`, each
+        [batch, pixels] (awpu_hip_cohere): "power" the delay-and-sum power, "coherence" the coherence factor in [0, 1],
+        "weighted" their product.  The handle's gains and band apply."""
+        frames = np.ascontiguousarray(frames, np.float32)
+        single = frames.ndim == 2
+        if single:
+            frames = frames[None]
+        if frames.shape[1:] != (self.cfg.n_streams, self.cfg.hist):
+            raise ValueError(f"frames must be [batch, {self.cfg.n_streams}, {self.cfg.hist}]")
+        names = ("power", "coherence", "weighted")
+        if not want or any(name not in names for name in want):
+            raise ValueError(f"want names some of {names}")
+        maps = {name: np.empty((frames.shape[0], self.pixel_count), np.float32) for name in names if name in want}
+        _check(self._lib.awpu_hip_cohere(self._h, _f32(frames), frames.shape[0], *[_f32(maps[name]) if name in maps else None for name in names]),
+               "awpu_hip_cohere")
+        return {name: m[0] for name, m in maps.items()} if single else maps
+
+    def cohere_device(self, d_frames_ptr: int, batch: int, d_power_ptr: int = 0, d_coherence_ptr: int = 0, d_weighted_ptr: int = 0,
+                      stream: int = 0) -> None:
+        """The same on device pointers (frames [batch, n_streams, hist]; each map [batch, pixels] or 0) on `stream`; asynchronous
+        (awpu_hip_cohere_device)."""
+        _check(self._lib.awpu_hip_cohere_device(self._h, C.c_void_p(d_frames_ptr), batch, C.c_void_p(d_power_ptr), C.c_void_p(d_coherence_ptr),
+                                                C.c_void_p(d_weighted_ptr), C.c_void_p(stream)), "awpu_hip_cohere_device")
+
+    def cohere_device_sums(self, d_frames_ptr: int, batch: int, d_sums_ptr: int = 0, d_energy_ptr: int = 0, d_power_ptr: int = 0,
+                           d_coherence_ptr: int = 0, d_weighted_ptr: int = 0, stream: int = 0) -> None:
+        """cohere_device plus every pixel's out[0..255] and e[0..255] into d_sums / d_energy [batch, pixels, 256], each or 0
+        (awpu_hip_cohere_device_sums): the rule's bits."""
+        _check(self._lib.awpu_hip_cohere_device_sums(self._h, C.c_void_p(d_frames_ptr), batch, C.c_void_p(d_power_ptr), C.c_void_p(d_coherence_ptr),
+                                                     C.c_void_p(d_weighted_ptr), C.c_void_p(d_sums_ptr), C.c_void_p(d_energy_ptr),
+                                                     C.c_void_p(stream)), "awpu_hip_cohere_device_sums")
+
+    def _cohere_run(self, call, where, n_blocks, rows, cols, first, every, show, out_rows, out_cols, d_colormap_ptr, flip, want_image,
+                    want_power, find) -> CohereResult:
+        n_frames, next_first = watch_count(n_blocks, first, every)
+        w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(d_colormap_ptr))
+        co = Cohere(show)
+        image = np.empty((n_frames, rows, cols), np.uint8) if want_image else None
+        big = np.empty((n_frames, out_rows, out_cols, 3) if d_colormap_ptr else (n_frames, out_rows, out_cols), np.uint8) if out_rows else None
+        power = np.empty((n_frames, self.pixel_count), np.float32) if want_power else None
+        f = sources = count = None
+        if find is not None:
+            f = Find(rows, cols, find.get("radius", 2), find.get("max_sources", 4), find.get("min_power", 0.0), find.get("min_ratio", 0.0),
+                     find.get("fov_deg", 180.0))
+            sources = np.empty((n_frames, max(f.max_sources, 0)), SOURCE_DTYPE)
+            count = np.empty(n_frames, np.int32)
+        # (an output that is wanted is never a null pointer, not even with no frame to write)
+        ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data or 16)
+        u8 = lambda a: None if a is None else C.cast(ptr(a), _u8p)
+        _check(call(n_blocks, C.byref(w), C.byref(co), None if f is None else C.byref(f), u8(image), u8(big),
+                    None if power is None else C.cast(ptr(power), _f32p), ptr(sources), ptr(count)), where)
+        return CohereResult(image, big, power, sources, count, next_first)
+
+    def cohere_blocks(self, wire, rows: int, cols: int, first: int = 0, every: int = 1, show: int = COHERE_WEIGHTED, out_rows: int = 0,
+                      out_cols: int = 0, d_colormap_ptr: int = 0, flip: bool = False, stride: int = DATAGRAM_BYTES, want_image: bool = True,
+                      want_power: bool = False, find: Optional[dict] = None) -> CohereResult:
+        """Watch a run of consecutive blocks of wire datagrams (as watch_blocks takes them) through the coherence sweep: every
+        shown frame is its coherence-weighted row, or with show=COHERE_FACTOR its coherence row (awpu_hip_cohere_blocks).  `find`
+        (a dict of find_peaks' keywords, {} for the defaults) also finds the sources of every frame.  -> CohereResult; pass its
+        .next_first as `first` of the call that continues the run."""
+        buf = np.frombuffer(wire, dtype=np.uint8)
+        if stride < DATAGRAM_BYTES or buf.size % (256 * stride) or buf.size == 0:
+            raise ValueError(f"wire must be a whole number of blocks of 256 datagrams {stride} bytes apart")
+        return self._cohere_run(lambda *rest: self._lib.awpu_hip_cohere_blocks(self._h, buf.ctypes.data_as(C.c_void_p), stride, *rest),
+                                "awpu_hip_cohere_blocks", buf.size // (256 * stride), rows, cols, first, every, show, out_rows, out_cols,
+                                d_colormap_ptr, flip, want_image, want_power, find)
+
+    def cohere_samples(self, samples: np.ndarray, rows: int, cols: int, first: int = 0, every: int = 1, show: int = COHERE_WEIGHTED,
+                       out_rows: int = 0, out_cols: int = 0, d_colormap_ptr: int = 0, flip: bool = False, want_image: bool = True,
+                       want_power: bool = False, find: Optional[dict] = None) -> CohereResult:
+        """The same from unpacked samples [n_streams, N] (N a multiple of 256, oldest first) (awpu_hip_cohere_samples)."""
+        samples = np.ascontiguousarray(samples, np.float32)
+        if samples.ndim != 2 or samples.shape[0] != self.cfg.n_streams or samples.shape[1] % 256 or samples.shape[1] == 0:
+            raise ValueError(f"samples must be [{self.cfg.n_streams}, N] with N a positive multiple of 256")
+        return self._cohere_run(lambda *rest: self._lib.awpu_hip_cohere_samples(self._h, _f32(samples), samples.shape[1], *rest),
+                                "awpu_hip_cohere_samples", samples.shape[1] // 256, rows, cols, first, every, show, out_rows, out_cols,
+                                d_colormap_ptr, flip, want_image, want_power, find)
+
+    def cohere_samples_device(self, d_samples_ptr: int, pitch: int, n_blocks: int, rows: int, cols: int, first: int = 0, every: int = 1,
+                              show: int = COHERE_WEIGHTED, d_image_ptr: int = 0, d_big_ptr: int = 0, d_power_ptr: int = 0,
+                              d_sources_ptr: int = 0, d_count_ptr: int = 0, out_rows: int = 0, out_cols: int = 0, d_colormap_ptr: int = 0,
+                              flip: bool = False, stream: int = 0, find: Optional[dict] = None) -> int:
+        """The same on device pointers (samples [n_streams, pitch]; image, big, power as watch_samples_device takes them, sources
+        and count as find_samples_device does, each or 0) on `stream`; asynchronous.  -> next_first
+        (awpu_hip_cohere_samples_device)."""
+        w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(d_colormap_ptr))
+        co = Cohere(show)
+        f = None
+        if find is not None:
+            f = Find(rows, cols, find.get("radius", 2), find.get("max_sources", 4), find.get("min_power", 0.0), find.get("min_ratio", 0.0),
+                     find.get("fov_deg", 180.0))
+        _check(self._lib.awpu_hip_cohere_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, C.byref(w), C.byref(co),
+                                                        None if f is None else C.byref(f), C.c_void_p(d_image_ptr), C.c_void_p(d_big_ptr),
+                                                        C.c_void_p(d_power_ptr), C.c_void_p(d_sources_ptr), C.c_void_p(d_count_ptr),
+                                                        C.c_void_p(stream)), "awpu_hip_cohere_samples_device")
         return watch_count(n_blocks, first, every)[1]
 
     def range(self, theta, phi, distance, d_frame_ptr: int = 0):

@@ -388,6 +388,10 @@ struct awpu_hip {
     // them).  The host forms bring them back through pinned blk_out.h[i & 1], which an exposed run's swept powers never cross
     Dev<float> d_expose_carry;
     awpu::host::BufferPair expose;
+    // coherence (awpu_hip_cohere.h): the sweep's table where prepare() builds no d_lut (AWPU_MATH_F32_FAST: ensure_cohere_table; freed
+    // with the other tables), and the maps of a host-form call on their way back, one plane [batch][pixel_count] per map asked for
+    Dev<awpu::LutEntry> d_cohere_lut;
+    Dev<float> d_cohere_out;
 
     // the band (awpu_hip_band.h): its coefficients (empty = none; they travel to the pre-pass as kernel arguments), and the
     // filtered frames of a call whose own frames are the caller's or the ring's, in those frames' layout (band_sweep): a plane
@@ -476,6 +480,13 @@ enum FrameLayout { kFull = 0, kCompact = 1, kRing = 2 };
 int prepare(awpu_hip *h);
 void free_tables(awpu_hip *h);
 int launch(awpu_hip *h, const float *d_frames, int batch, float *d_power, hipStream_t s, int layout = kFull);
+// what a coherence sweep (awpu_hip_cohere.h) writes, device memory, each or null: the three maps [batch][pixel_count], out[] and
+// e[] of every pixel [batch][pixel_count][256]
+struct CohereOut {
+    float *power = nullptr, *coherence = nullptr, *weighted = nullptr, *sums = nullptr, *energy = nullptr;
+};
+int ensure_cohere_table(awpu_hip *h);  // behind check_ready, before the call enqueues anything: the one step that may block
+int launch_cohere(awpu_hip *h, const float *d_frames, int batch, const CohereOut &out, hipStream_t s, int layout);
 bool takes_packed_pairs(awpu_hip *h, int batch, awpu::FastPlan *plan);
 int packed_shape(awpu_hip *h, int batch, awpu::FastPlan *plan);
 size_t packed_floats_of(const awpu_hip *h, const awpu::FastPlan &plan, int batch);
@@ -504,7 +515,7 @@ int ensure_taps(awpu_hip *h, int rows, int cols, int out_rows, int out_cols, hip
 int band_cut(awpu_hip *h, const BandSet &bands, const float *in, long long in_frame, long long in_row, int in_lo, int batch, float *out,
              long long out_plane, int layout, hipStream_t s);
 int band_sweep(awpu_hip *h, const BandSet &bands, const float *in, long long in_frame, long long in_row, int in_lo, int batch, float *d_power,
-               long long power_plane, hipStream_t s, int layout);
+               long long power_plane, hipStream_t s, int layout, const CohereOut *cohere = nullptr);
 inline int band_sweep(awpu_hip *h, const float *in, long long in_frame, long long in_row, int in_lo, int batch, float *d_power, hipStream_t s, int layout) {
     return band_sweep(h, own_band(h), in, in_frame, in_row, in_lo, batch, d_power, 0, s, layout);  // the handle's own band: the one-band case
 }

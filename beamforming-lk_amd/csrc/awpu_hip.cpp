@@ -293,10 +293,14 @@ int band_cut(awpu_hip *h, const BandSet &bands, const float *in, long long in_fr
 // launch() on frames of the caller's or the ring's (kFull, kRing), or on windows uploaded with the bands' history in front of them
 // (kCompact: rows of max taps - 1 + compact_hist floats), through the bands where there are any: the pre-pass into d_band in
 // `layout`, a plane per band, then for every band the launch() a band-less handle makes for the same call -- the same layout and
-// batch, so the same kernel -- into d_power + b * power_plane.  The handle's event bracket spans all of it
+// batch, so the same kernel -- into d_power + b * power_plane.  The handle's event bracket spans all of it.  With `cohere` the
+// sweep behind the pre-pass is the coherence sweep (awpu_hip_cohere.h: at most one band, d_power unused)
 int band_sweep(awpu_hip *h, const BandSet &bands, const float *in, long long in_frame, long long in_row, int in_lo, int batch, float *d_power,
-               long long power_plane, hipStream_t s, int layout) {
-    if (bands.n == 0) return launch(h, in, batch, d_power, s, layout);
+               long long power_plane, hipStream_t s, int layout, const CohereOut *cohere) {
+    const auto sweep = [&](const float *frames, float *power) {
+        return cohere ? launch_cohere(h, frames, batch, *cohere, s, layout) : launch(h, frames, batch, power, s, layout);
+    };
+    if (bands.n == 0) return sweep(in, d_power);
     const size_t S = (size_t) h->cfg.n_streams;
     const size_t plane = layout == kRing ? S * 2048 : S * (size_t) (layout == kCompact ? h->compact_hist : h->cfg.hist) * batch;
     const size_t need = plane * bands.n;
@@ -309,7 +313,7 @@ int band_sweep(awpu_hip *h, const BandSet &bands, const float *in, long long in_
     int rc = band_cut(h, bands, in, in_frame, in_row, in_lo, batch, h->d_band, (long long) plane, layout, s);
     if (rc != AWPU_OK) return rc;
     h->timing = false;
-    for (int b = 0; b < bands.n && rc == AWPU_OK; b++) rc = launch(h, h->d_band + b * plane, batch, d_power + b * power_plane, s, layout);
+    for (int b = 0; b < bands.n && rc == AWPU_OK; b++) rc = sweep(h->d_band + b * plane, d_power + b * power_plane);
     h->timing = timed;
     if (rc == AWPU_OK && timed) AWPU_HIP_TRY(hipEventRecord(h->ev_end, s));
     return rc;

@@ -1,8 +1,9 @@
 // awpu_runs.cpp -- runs of consecutive blocks of a recording through one pipeline of pieces: a heatmap of every block
 // (include/awpu_hip_blocks.h), the beam audio of every block (awpu_hip_listen.h), display images of every Nth block
-// (awpu_hip_watch.h) -- in up to four bands at once (awpu_hip_spectral.h) --, the sources in every Nth block (awpu_hip_find.h), their distances (awpu_hip_focus.h), and all of a watch run's exposed over the blocks in front of every Nth (awpu_hip_expose.h).  The handle and what is called here out of awpu_hip.cpp and awpu_sweep.cpp: awpu_handle.h.
+// (awpu_hip_watch.h) -- in up to four bands at once (awpu_hip_spectral.h) --, the sources in every Nth block (awpu_hip_find.h), their distances (awpu_hip_focus.h), and all of a watch run's exposed over the blocks in front of every Nth (awpu_hip_expose.h) or swept by the coherence sweep (awpu_hip_cohere.h).  The handle and what is called here out of awpu_hip.cpp and awpu_sweep.cpp: awpu_handle.h.
 #include "awpu_handle.h"
 #include "awpu_hip_blocks.h"
+#include "awpu_hip_cohere.h"
 #include "awpu_hip_expose.h"
 #include "awpu_hip_find.h"
 #include "awpu_hip_focus.h"
@@ -16,6 +17,7 @@
 #include <vector>
 
 #include "block_kernels.h"
+#include "cohere_rule.h"
 #include "expose_kernels.h"
 #include "find_kernels.h"
 #include "find_rule.h"
@@ -137,6 +139,10 @@ struct Consumer {
     virtual int staged_blocks(const Piece &p) = 0;              // host forms: stages the input in blk_in.h[b]; the blocks to upload
     virtual int history(const Piece &p, hipStream_t s) = 0;     // blk_hist.d[b], out of blk_in.d[b] (host forms) or the caller's samples
     virtual int cut(const Piece &p, hipStream_t s) = 0;         // its snapshots' windows into d_blk_frames
+    // the sweep of a piece's n windows (one band's) into d_pow: launch(), unless the consumer sweeps otherwise (CoherePieces)
+    virtual int sweep_frames(awpu_hip *h, const float *d_frames, int n, float *d_pow, hipStream_t s, int layout) {
+        return launch(h, d_frames, n, d_pow, s, layout);
+    }
     // behind the sweeps into d_pow (band b's powers `plane` floats behind band b-1's), before ev_blk_swept
     virtual int show(const Piece &, float *, long long, hipStream_t) { return AWPU_OK; }
     virtual int listen(const Piece &, hipStream_t) { return AWPU_OK; }
@@ -285,7 +291,7 @@ int run_pieces(awpu_hip *h, const BlockRun &src, hipStream_t user, Consumer &c) 
                 const size_t frames_plane = (size_t) S * (compact ? h->compact_hist : AWPU_HIST) * p.n;
                 h->timing = false;
                 for (int k = 0; k < planes && brc == AWPU_OK; k++)
-                    brc = launch(h, h->d_blk_frames + k * frames_plane, p.n, d_pow + k * pow_plane, sw, compact ? kCompact : kFull);
+                    brc = c.sweep_frames(h, h->d_blk_frames + k * frames_plane, p.n, d_pow + k * pow_plane, sw, compact ? kCompact : kFull);
                 h->timing = time_it;
                 if (brc == AWPU_OK) brc = c.show(p, d_pow, pow_plane, sw);
                 if (brc != AWPU_OK) return brc;
@@ -1063,6 +1069,49 @@ int expose_run(awpu_hip *h, const BlockRun &src, int n_blocks, const awpu_watch_
     return rc;
 }
 
+// ---- coherence runs (awpu_hip_cohere.h; kernel in cohere_kernels.hip) -------------------------------------------------------------
+// A watch run whose pieces are swept by the coherence sweep (launch_cohere) in place of launch(): the row a frame shows -- and
+// everything behind it: the display step, the peak pass, the powers' way back -- is its weighted or its coherence row.  Pieces,
+// histories, the band's pre-pass in the cut, the ring: the watch run's.
+struct CoherePieces final : WatchPieces {
+    const int show;
+    CoherePieces(awpu_hip *h_, const BlockRun &src_, int n_blocks_, const WatchRun &wr_, int show_) : WatchPieces(h_, src_, n_blocks_, wr_), show(show_) {}
+    int check() override {
+        if (h->cfg.interp != AWPU_INTERP_LERP) return fail(AWPU_ERR_STATE, "the coherence sweep interpolates linearly: AWPU_INTERP_FIR8 is not taken");
+        return WatchPieces::check();
+    }
+    int ensure(int piece_max, int lo_, int width_, hipStream_t sw) override {  // (the handle is ready; none of the run's work is enqueued yet)
+        const int rc = ensure_cohere_table(h);
+        return rc != AWPU_OK ? rc : WatchPieces::ensure(piece_max, lo_, width_, sw);
+    }
+    int sweep_frames(awpu_hip *, const float *d_frames, int n, float *d_pow, hipStream_t s, int layout) override {
+        CohereOut out;
+        (show == AWPU_COHERE_FACTOR ? out.coherence : out.weighted) = d_pow;
+        return launch_cohere(h, d_frames, n, out, s, layout);
+    }
+};
+
+// the checks of a coherence run that read no handle; then the run
+int cohere_run(awpu_hip *h, const BlockRun &src, int n_blocks, const awpu_watch_t *w, const awpu_cohere_t *co, const awpu_find_t *f, uint8_t *image,
+               uint8_t *big, float *power, awpu_source_t *sources, int32_t *count, hipStream_t user) {
+    WatchRun wr;
+    if (int rc = check_watch(w, image || big || power || sources || count, big != nullptr, n_blocks, &wr)) return rc;
+    if (const char *why = awpu::cohere_refusal(co)) return invalid(why);
+    if (!sources != !count) return invalid("sources and count come together");
+    if (!f != !sources) return invalid("a find request exactly when sources and count are asked for");
+    if (f) {
+        if (const char *why = awpu::find_refusal(f)) return invalid(why);
+        if (f->rows != w->rows || f->cols != w->cols) return invalid("the find grid must be the watch grid");
+    }
+    FindRun find;
+    if (f) find.f = *f, find.sources = sources, find.count = count;
+    wr.image = image, wr.big = big, wr.power = power;
+    wr.find = f ? &find : nullptr;
+    AWPU_CTX(h);
+    CoherePieces c(h, src, n_blocks, wr, co->show);
+    return run_pieces(h, src, user, c);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1271,6 +1320,30 @@ int awpu_hip_expose_samples_device(awpu_hip_t *h, const float *d_samples, int64_
     BlockRun src;
     if (int rc = sample_source(h, d_samples, pitch, n_blocks, true, &src)) return rc;
     return expose_run(h, src, n_blocks, w, e, f, d_carry, d_image, d_big_image, d_power, d_sources, d_count, static_cast<hipStream_t>(stream));
+}
+
+int awpu_hip_cohere_blocks(awpu_hip_t *h, const void *datagrams, int32_t stride_bytes, int32_t n_blocks, const awpu_watch_t *w,
+                           const awpu_cohere_t *co, const awpu_find_t *f, uint8_t *image, uint8_t *big_image, float *power,
+                           awpu_source_t *sources, int32_t *count) {
+    BlockRun src;
+    if (int rc = wire_source(h, datagrams, stride_bytes, n_blocks, &src)) return rc;
+    return cohere_run(h, src, n_blocks, w, co, f, image, big_image, power, sources, count, nullptr);
+}
+
+int awpu_hip_cohere_samples(awpu_hip_t *h, const float *samples, int64_t pitch, int32_t n_blocks, const awpu_watch_t *w,
+                            const awpu_cohere_t *co, const awpu_find_t *f, uint8_t *image, uint8_t *big_image, float *power,
+                            awpu_source_t *sources, int32_t *count) {
+    BlockRun src;
+    if (int rc = sample_source(h, samples, pitch, n_blocks, false, &src)) return rc;
+    return cohere_run(h, src, n_blocks, w, co, f, image, big_image, power, sources, count, nullptr);
+}
+
+int awpu_hip_cohere_samples_device(awpu_hip_t *h, const float *d_samples, int64_t pitch, int32_t n_blocks, const awpu_watch_t *w,
+                                   const awpu_cohere_t *co, const awpu_find_t *f, uint8_t *d_image, uint8_t *d_big_image, float *d_power,
+                                   awpu_source_t *d_sources, int32_t *d_count, void *stream) {
+    BlockRun src;
+    if (int rc = sample_source(h, d_samples, pitch, n_blocks, true, &src)) return rc;
+    return cohere_run(h, src, n_blocks, w, co, f, d_image, d_big_image, d_power, d_sources, d_count, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -13,6 +13,7 @@
 #include <map>
 #include <vector>
 
+#include "cohere_kernels.h"
 #include "das_kernels.h"
 #include "nd_tile_window.h"
 
@@ -128,6 +129,7 @@ namespace awpu::host {
 // launches still reading the old tables finish first.)
 void free_tables(awpu_hip *h) {
     h->d_lut.release();
+    h->d_cohere_lut.release();
     h->fast_luts.clear();
     h->d_exact_pair_lut.release();
     for (QuadTable &q : h->quad_tables) q.d.release();
@@ -1183,6 +1185,60 @@ int launch(awpu_hip *h, const float *d_frames, int batch, float *d_power, hipStr
     case kShapeNone: break;
     }
     return fail(AWPU_ERR_STATE, "the pre-epilogue sums are exported by the frame-pair reference-order kernels and the reference-rounding FIR8 kernel only");
+}
+
+// The coherence sweep's table on a prepared handle whose prepare() built no d_lut (AWPU_MATH_F32_FAST with AWPU_INTERP_LERP): the
+// same entries into d_cohere_lut, once per prepare() (free_tables drops it).  The copy blocks, so every coherence call comes here
+// behind check_ready and before it enqueues anything; a copy that fails leaves no table behind, and the next call builds it again.
+int ensure_cohere_table(awpu_hip *h) {
+    if (h->d_lut || h->d_cohere_lut) return AWPU_OK;
+    const int U = h->usable(), P = h->cfg.pixel_count;
+    if (awpu::das_exact_lds_bytes(h->window, U, nullptr) == 0) return invalid("delay window does not fit the LDS budget");
+    std::vector<awpu::LutEntry> packed((size_t) P * U);
+    for (int p = 0; p < P; p++)
+        for (int k = 0; k < U; k++) {
+            const size_t at = (size_t) p * h->cfg.lut_stride + h->index[k];
+            packed[(size_t) p * U + k] = {h->off[at] - h->wstart, h->frac[at]};
+        }
+    if (const int rc = h->d_cohere_lut.grow(packed.size()); rc != AWPU_OK) return rc;
+    const hipError_t e = hipMemcpy(h->d_cohere_lut, packed.data(), packed.size() * sizeof(awpu::LutEntry), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        h->d_cohere_lut.release();
+        return hip_fail(e, "hipMemcpy of the coherence sweep's table");
+    }
+    return AWPU_OK;
+}
+
+// The coherence sweep (awpu_hip_cohere.h; cohere_sweep_kernel), beside launch_exact: das_exact_kernel's arguments in the layouts
+// launch() takes (kFull, kCompact), whatever cfg.math is -- the rule has one arithmetic.  Its table is d_lut where prepare() built
+// it (every mode but AWPU_MATH_F32_FAST), else the same entries in d_cohere_lut (ensure_cohere_table).  Each output or null;
+// counted and timed like any sweep launch.  Nothing here waits for the device.
+int launch_cohere(awpu_hip *h, const float *d_frames, int batch, const CohereOut &out, hipStream_t s, int layout) {
+    if (h->cfg.interp != AWPU_INTERP_LERP) return fail(AWPU_ERR_STATE, "the coherence sweep interpolates linearly: AWPU_INTERP_FIR8 is not taken");
+    if (layout != kFull && layout != kCompact) return invalid("the coherence sweep takes whole frames or uploaded windows");
+    const int U = h->usable(), P = h->cfg.pixel_count;
+    const awpu::LutEntry *lut = h->d_lut ? h->d_lut.get() : h->d_cohere_lut.get();
+    if (!lut) return fail(AWPU_ERR_STATE, "the coherence sweep has no table: ensure_cohere_table comes first");
+    awpu::CohereArgs a{};
+    a.sweep.frames = d_frames;
+    a.sweep.lut = lut;
+    a.sweep.index = h->d_index;
+    a.sweep.power = out.power;
+    a.sweep.gain = h->d_gain;
+    a.sweep.sums = out.sums;
+    a.sweep.n_streams = h->cfg.n_streams;
+    a.sweep.hist = layout == kCompact ? h->compact_hist : h->cfg.hist;
+    a.sweep.usable = U;
+    a.sweep.pixel_count = P;
+    a.sweep.wstart = layout == kCompact ? 0 : h->wstart;
+    a.sweep.window = h->window;
+    a.sweep.batch = batch;
+    a.coherence = out.coherence;
+    a.weighted = out.weighted;
+    a.energy = out.energy;
+    if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
+    AWPU_HIP_TRY(awpu::launch_cohere_sweep(a, s));
+    return finish_launch(h, batch, s, AWPU_KERNEL_COHERE);
 }
 
 // Would launch() sweep this batch with one of the frame-pair shapes that read the packed layout (quad or pair)?  The rule of

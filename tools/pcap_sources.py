@@ -18,6 +18,10 @@ while they are on the device (Engine.locate_blocks), and the distance at which i
 power rows (Engine.expose_blocks, include/awpu_hip_expose.h), which steadies the peaks of a noise-like source; the open window is
 carried from one --chunk call to the next, and the first block searched is then block L - 1.  Off unless given; not with --range.
 
+--coherence [weighted|factor] searches the rows of the coherence sweep (Engine.cohere_blocks, include/awpu_hip_cohere.h): the power
+weighted by the coherence factor -- a source's side lobes are then no sources --, or with `factor` the coherence factor itself; the
+`power` column is that row's value.  Off unless given; not with --exposure or --range.
+
 Every block is ingested; every --every'th is swept and searched.  --chunk blocks go to the engine per call, each call continuing
 with the `next_first` of the one before, so a long capture streams through bounded memory.
 
@@ -102,10 +106,14 @@ def main(argv=None) -> int:
                     help="range every source over N focus distances from LO to HI metres, uniform in 1 / d: the `distance` column")
     ap.add_argument("--exposure", type=int, default=None, metavar="L",
                     help="search heatmaps integrated over the L blocks that end with the searched one, 1 <= L <= --every (include/awpu_hip_expose.h)")
+    ap.add_argument("--coherence", nargs="?", const="weighted", default=None, choices=("weighted", "factor"),
+                    help="search the coherence-weighted power, or the coherence factor itself (include/awpu_hip_cohere.h)")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     if a.every < 1 or a.chunk < 1:
         ap.error("--every and --chunk are positive")
+    if a.coherence and (a.exposure is not None or a.range_):
+        ap.error("--coherence together with --exposure or --range: those runs are not swept for coherence")
     if a.exposure is not None and not 1 <= a.exposure <= a.every:
         ap.error("--exposure is between 1 and --every")
     if a.exposure is not None and a.range_:
@@ -156,6 +164,10 @@ def main(argv=None) -> int:
                 what = {k: v for k, v in find.items() if k not in ("first", "every")}
                 res = eng.expose_blocks(chunk, a.cols, a.cols, a.exposure, first=first, every=a.every, carry=carry, want_image=False, find=what)
                 carry = res.carry
+            elif a.coherence:
+                what = {k: v for k, v in find.items() if k not in ("first", "every")}
+                show = pkg.binding.COHERE_FACTOR if a.coherence == "factor" else pkg.binding.COHERE_WEIGHTED
+                res = eng.cohere_blocks(chunk, a.cols, a.cols, first=first, every=a.every, show=show, want_image=False, find=what)
             else:
                 res = eng.find_blocks(chunk, a.cols, a.cols, **find) if candidates is None else eng.locate_blocks(chunk, a.cols, a.cols, candidates, **find)
             lines += write_rows(writer, b + first + a.every * np.arange(len(res)), res.sources, res.count, getattr(res, "ranges", None))

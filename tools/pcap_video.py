@@ -23,6 +23,10 @@ rows, or with --peak-hold their per-pixel maximum (Engine.expose_blocks, include
 frame instead of 5.2, the open window carried from one --chunk call to the next.  The first frame is then block L - 1's.  Off
 unless given; not with --bands.
 
+--coherence [weighted|factor] shows every frame through the coherence sweep (Engine.cohere_blocks, include/awpu_hip_cohere.h): its
+delay-and-sum power weighted by the coherence factor, which takes the side lobes of a source out of the picture, or with `factor`
+the coherence factor itself.  Off unless given; not with --bands or --exposure.
+
 Every block is ingested; every --every'th is swept and shown.  The default 3 gives 48828 / (256 * 3) = 63.6 frames per second, the
 nearest to the 60 the reference opens its writer with.  --chunk blocks go to the engine per call, each call continuing with the
 `next_first` of the one before, so a long capture streams through bounded memory.
@@ -208,6 +212,8 @@ def main(argv=None) -> int:
     ap.add_argument("--exposure", type=int, default=None, metavar="L",
                     help="integrate every frame over the L blocks that end with its shown block, 1 <= L <= --every (include/awpu_hip_expose.h)")
     ap.add_argument("--peak-hold", action="store_true", help="--exposure: the per-pixel maximum of the L blocks instead of their mean")
+    ap.add_argument("--coherence", nargs="?", const="weighted", default=None, choices=("weighted", "factor"),
+                    help="show the coherence-weighted power, or the coherence factor itself (include/awpu_hip_cohere.h)")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     if a.every < 1 or a.chunk < 1 or a.size < a.cols:
@@ -218,6 +224,8 @@ def main(argv=None) -> int:
         ap.error("--exposure together with --bands: spectral runs are not exposed")
     if a.peak_hold and a.exposure is None:
         ap.error("--peak-hold needs --exposure")
+    if a.coherence and (a.bands or a.exposure is not None):
+        ap.error("--coherence together with --bands or --exposure: those runs are not swept for coherence")
     if a.band and a.bands:
         ap.error("--bands together with --band: one band through the colour table, or several bands as colours")
 
@@ -272,6 +280,10 @@ def main(argv=None) -> int:
                                         mode=mode, carry=carry, out_rows=a.size, out_cols=a.size, d_colormap_ptr=table.data_ptr(), flip=a.flip,
                                         want_image=False)
                 carry = res.carry
+            elif a.coherence:
+                show = pkg.binding.COHERE_FACTOR if a.coherence == "factor" else pkg.binding.COHERE_WEIGHTED
+                res = eng.cohere_blocks(wire[b * block_bytes: (b + nb) * block_bytes], a.cols, a.cols, first=first, every=a.every, show=show,
+                                        out_rows=a.size, out_cols=a.size, d_colormap_ptr=table.data_ptr(), flip=a.flip, want_image=False)
             else:
                 res = eng.watch_blocks(wire[b * block_bytes: (b + nb) * block_bytes], a.cols, a.cols, first=first, every=a.every,
                                        out_rows=a.size, out_cols=a.size, d_colormap_ptr=table.data_ptr(), flip=a.flip, want_image=False,
