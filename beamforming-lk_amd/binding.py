@@ -437,6 +437,29 @@ def _i32(a: np.ndarray):
     return a.ctypes.data_as(_i32p)
 
 
+def _wire_blocks(wire, stride: int):
+    """(the bytes of wire datagrams `stride` bytes apart, how many blocks of 256 they are)."""
+    buf = np.frombuffer(wire, dtype=np.uint8)
+    if stride < DATAGRAM_BYTES or buf.size % (256 * stride) or buf.size == 0:
+        raise ValueError(f"wire must be a whole number of blocks of 256 datagrams {stride} bytes apart")
+    return buf, buf.size // (256 * stride)
+
+
+def _find_struct(rows: int, cols: int, find: Optional[dict]) -> Optional[Find]:
+    """find_peaks' keywords as the awpu_find_t of a run on a rows x cols grid; None (no find request) stays None."""
+    if find is None:
+        return None
+    return Find(rows, cols, find.get("radius", 2), find.get("max_sources", 4), find.get("min_power", 0.0), find.get("min_ratio", 0.0),
+                find.get("fov_deg", 180.0))
+
+
+def _out_ptr(a: Optional[np.ndarray], ctype=None):
+    """An output array as a call's argument: one that is wanted is never a null pointer, not even with no frame to write."""
+    if a is None:
+        return None
+    return C.c_void_p(a.ctypes.data or 16) if ctype is None else C.cast(C.c_void_p(a.ctypes.data or 16), ctype)
+
+
 # ----------------------------------------------------------------------------- geometry
 
 
@@ -973,14 +996,31 @@ class Engine:
         _check(self._lib.awpu_hip_ring_snapshot(self._h, _f32(frames)), "ring_snapshot")
         return frames
 
+    def _sample_blocks(self, samples):
+        """(unpacked samples [n_streams, N] as contiguous floats, how many blocks of 256 they are)."""
+        samples = np.ascontiguousarray(samples, np.float32)
+        if samples.ndim != 2 or samples.shape[0] != self.cfg.n_streams or samples.shape[1] % 256 or samples.shape[1] == 0:
+            raise ValueError(f"samples must be [{self.cfg.n_streams}, N] with N a positive multiple of 256")
+        return samples, samples.shape[1] // 256
+
+    def _shown_outputs(self, n_frames, w: Watch, want_image, want_power, f: Optional[Find] = None, new=lambda shape, dtype, name: np.empty(shape, dtype)):
+        """What a run shows of its n_frames frames: the arrays (image, big, power, sources, count), each or None, and their
+        pointers as the C calls take them; new(shape, dtype, name) allocates one."""
+        image = new((n_frames, w.rows, w.cols), np.uint8, "image") if want_image else None
+        big = None
+        if w.out_rows:
+            big = new((n_frames, w.out_rows, w.out_cols, 3) if w.d_colormap else (n_frames, w.out_rows, w.out_cols), np.uint8, "big")
+        power = new((n_frames, self.pixel_count), np.float32, "power") if want_power else None
+        sources = None if f is None else np.empty((n_frames, max(f.max_sources, 0)), SOURCE_DTYPE)
+        count = None if f is None else np.empty(n_frames, np.int32)
+        return (image, big, power, sources, count), (_out_ptr(image, _u8p), _out_ptr(big, _u8p), _out_ptr(power, _f32p), _out_ptr(sources),
+                                                    _out_ptr(count))
+
     def process_blocks(self, wire, stride: int = DATAGRAM_BYTES) -> np.ndarray:
         """A run of consecutive blocks of wire datagrams (bytes-like, n_blocks x 256 datagrams `stride` bytes apart) ->
         power [n_blocks, pixels]: row k = process_ring() after k + 1 ingest_block() calls, and the ring is left there
         (awpu_hip_process_blocks)."""
-        buf = np.frombuffer(wire, dtype=np.uint8)
-        if stride < DATAGRAM_BYTES or buf.size % (256 * stride) or buf.size == 0:
-            raise ValueError(f"wire must be a whole number of blocks of 256 datagrams {stride} bytes apart")
-        n_blocks = buf.size // (256 * stride)
+        buf, n_blocks = _wire_blocks(wire, stride)
         power = np.empty((n_blocks, self.pixel_count), np.float32)
         _check(self._lib.awpu_hip_process_blocks(self._h, buf.ctypes.data_as(C.c_void_p), stride, n_blocks, _f32(power)),
                "awpu_hip_process_blocks")
@@ -989,10 +1029,7 @@ class Engine:
     def process_samples(self, samples: np.ndarray) -> np.ndarray:
         """The same from unpacked samples [n_streams, N] (N a multiple of 256, oldest first) -> power [N // 256, pixels]
         (awpu_hip_process_samples)."""
-        samples = np.ascontiguousarray(samples, np.float32)
-        if samples.ndim != 2 or samples.shape[0] != self.cfg.n_streams or samples.shape[1] % 256 or samples.shape[1] == 0:
-            raise ValueError(f"samples must be [{self.cfg.n_streams}, N] with N a positive multiple of 256")
-        n_blocks = samples.shape[1] // 256
+        samples, n_blocks = self._sample_blocks(samples)
         power = np.empty((n_blocks, self.pixel_count), np.float32)
         _check(self._lib.awpu_hip_process_samples(self._h, _f32(samples), samples.shape[1], n_blocks, _f32(power)),
                "awpu_hip_process_samples")
@@ -1023,21 +1060,17 @@ class Engine:
         256 samples of its audio row; the ring is left where the run ends (awpu_hip_listen_blocks).  theta/phi/spread/rate/steps
         are per listener (scalars broadcast), or `theta` is the .listeners of an earlier result (the rest then None);
         reference None = from each block's own snapshot, as MISOWorker does.  -> ListenResult."""
-        buf = np.frombuffer(wire, dtype=np.uint8)
-        if stride < DATAGRAM_BYTES or buf.size % (256 * stride) or buf.size == 0:
-            raise ValueError(f"wire must be a whole number of blocks of 256 datagrams {stride} bytes apart")
+        buf, n_blocks = _wire_blocks(wire, stride)
         return self._listen(lambda *rest: self._lib.awpu_hip_listen_blocks(self._h, buf.ctypes.data_as(C.c_void_p), stride, *rest),
-                            "awpu_hip_listen_blocks", buf.size // (256 * stride), (theta, phi, spread, rate, steps), theta_limit,
+                            "awpu_hip_listen_blocks", n_blocks, (theta, phi, spread, rate, steps), theta_limit,
                             reference, want_trail, want_power)
 
     def listen_samples(self, samples: np.ndarray, theta, phi, spread, rate, steps, theta_limit: float,
                        reference: Optional[float] = None, want_trail: bool = True, want_power: bool = False) -> ListenResult:
         """The same from unpacked samples [n_streams, N] (N a multiple of 256, oldest first) (awpu_hip_listen_samples)."""
-        samples = np.ascontiguousarray(samples, np.float32)
-        if samples.ndim != 2 or samples.shape[0] != self.cfg.n_streams or samples.shape[1] % 256 or samples.shape[1] == 0:
-            raise ValueError(f"samples must be [{self.cfg.n_streams}, N] with N a positive multiple of 256")
+        samples, n_blocks = self._sample_blocks(samples)
         return self._listen(lambda *rest: self._lib.awpu_hip_listen_samples(self._h, _f32(samples), samples.shape[1], *rest),
-                            "awpu_hip_listen_samples", samples.shape[1] // 256, (theta, phi, spread, rate, steps), theta_limit,
+                            "awpu_hip_listen_samples", n_blocks, (theta, phi, spread, rate, steps), theta_limit,
                             reference, want_trail, want_power)
 
     def listen_samples_device(self, d_samples_ptr: int, pitch: int, n_blocks: int, theta, phi, spread, rate, steps, theta_limit: float,
@@ -1065,17 +1098,10 @@ class Engine:
                     return base[: shape[0]]
             return np.empty(shape, dtype)
 
-        image = array((n_frames, rows, cols), np.uint8, getattr(out, "image", None)) if want_image else None
-        big = None
-        if out_rows:
-            big = array((n_frames, out_rows, out_cols, 3) if d_colormap_ptr else (n_frames, out_rows, out_cols), np.uint8,
-                        getattr(out, "big", None))
-        power = array((n_frames, self.pixel_count), np.float32, getattr(out, "power", None)) if want_power else None
-        # (an output that is wanted is never a null pointer, not even with no frame to write)
-        u8 = lambda a: None if a is None else C.cast(C.c_void_p(a.ctypes.data or 16), _u8p)
-        _check(call(n_blocks, C.byref(w), u8(image), u8(big), None if power is None else C.cast(C.c_void_p(power.ctypes.data or 16), _f32p)),
-               where)
-        return WatchResult(image, big, power, next_first)
+        shown, ptrs = self._shown_outputs(n_frames, w, want_image, want_power,
+                                          new=lambda shape, dtype, name: array(shape, dtype, getattr(out, name, None)))
+        _check(call(n_blocks, C.byref(w), *ptrs[:3]), where)
+        return WatchResult(*shown[:3], next_first)
 
     def watch_blocks(self, wire, rows: int, cols: int, first: int = 0, every: int = 1, out_rows: int = 0, out_cols: int = 0,
                      d_colormap_ptr: int = 0, flip: bool = False, stride: int = DATAGRAM_BYTES, want_image: bool = True,
@@ -1086,22 +1112,18 @@ class Engine:
         powers (awpu_hip_watch_blocks).  -> WatchResult; pass its .next_first as `first` of the call that continues the run, and
         the result itself as `out` when its arrays may be written again (a writer that is done with a chunk's frames: 3 MiB per
         1024 x 1024 colour frame are then not allocated and paged in anew for every call)."""
-        buf = np.frombuffer(wire, dtype=np.uint8)
-        if stride < DATAGRAM_BYTES or buf.size % (256 * stride) or buf.size == 0:
-            raise ValueError(f"wire must be a whole number of blocks of 256 datagrams {stride} bytes apart")
+        buf, n_blocks = _wire_blocks(wire, stride)
         return self._watch(lambda *rest: self._lib.awpu_hip_watch_blocks(self._h, buf.ctypes.data_as(C.c_void_p), stride, *rest),
-                           "awpu_hip_watch_blocks", buf.size // (256 * stride), first, every, rows, cols, out_rows, out_cols,
+                           "awpu_hip_watch_blocks", n_blocks, first, every, rows, cols, out_rows, out_cols,
                            d_colormap_ptr, flip, want_image, want_power, out)
 
     def watch_samples(self, samples: np.ndarray, rows: int, cols: int, first: int = 0, every: int = 1, out_rows: int = 0,
                       out_cols: int = 0, d_colormap_ptr: int = 0, flip: bool = False, want_image: bool = True,
                       want_power: bool = False, out: Optional[WatchResult] = None) -> WatchResult:
         """The same from unpacked samples [n_streams, N] (N a multiple of 256, oldest first) (awpu_hip_watch_samples)."""
-        samples = np.ascontiguousarray(samples, np.float32)
-        if samples.ndim != 2 or samples.shape[0] != self.cfg.n_streams or samples.shape[1] % 256 or samples.shape[1] == 0:
-            raise ValueError(f"samples must be [{self.cfg.n_streams}, N] with N a positive multiple of 256")
+        samples, n_blocks = self._sample_blocks(samples)
         return self._watch(lambda *rest: self._lib.awpu_hip_watch_samples(self._h, _f32(samples), samples.shape[1], *rest),
-                           "awpu_hip_watch_samples", samples.shape[1] // 256, first, every, rows, cols, out_rows, out_cols,
+                           "awpu_hip_watch_samples", n_blocks, first, every, rows, cols, out_rows, out_cols,
                            d_colormap_ptr, flip, want_image, want_power, out)
 
     def watch_samples_device(self, d_samples_ptr: int, pitch: int, n_blocks: int, rows: int, cols: int, first: int = 0, every: int = 1,
@@ -1144,9 +1166,8 @@ class Engine:
         big = np.empty((n_frames, out_rows, out_cols, 3), np.uint8) if out_rows else None
         dominant = np.empty((n_frames, rows, cols), np.uint8) if want_dominant else None
         power = np.empty((max(sp.n_bands, 1), n_frames, self.pixel_count), np.float32) if want_power else None
-        # (an output that is wanted is never a null pointer, not even with no frame to write)
-        ptr = lambda a, t: None if a is None else C.cast(C.c_void_p(a.ctypes.data or 16), t)
-        _check(call(n_blocks, C.byref(w), C.byref(sp), ptr(image, _u8p), ptr(big, _u8p), ptr(dominant, _u8p), ptr(power, _f32p)), where)
+        _check(call(n_blocks, C.byref(w), C.byref(sp), _out_ptr(image, _u8p), _out_ptr(big, _u8p), _out_ptr(dominant, _u8p),
+                    _out_ptr(power, _f32p)), where)
         return SpectralResult(image, big, dominant, power, next_first)
 
     def spectral_blocks(self, wire, rows: int, cols: int, bands, channel=None, scale: int = SPECTRAL_SCALE_COMMON, first: int = 0,
@@ -1156,22 +1177,18 @@ class Engine:
         ring, blocks first, first + every, ... are filtered by every band of `bands` in one pre-pass and swept once per band; byte c
         of a pixel of .image shows band channel[c] (None: band c where there is one; spectral_compose), .big is that image upscaled (and mirrored when flip),
         .dominant the strongest band of every pixel, .power every band's powers (awpu_hip_spectral_blocks).  -> SpectralResult."""
-        buf = np.frombuffer(wire, dtype=np.uint8)
-        if stride < DATAGRAM_BYTES or buf.size % (256 * stride) or buf.size == 0:
-            raise ValueError(f"wire must be a whole number of blocks of 256 datagrams {stride} bytes apart")
+        buf, n_blocks = _wire_blocks(wire, stride)
         return self._spectral(lambda *rest: self._lib.awpu_hip_spectral_blocks(self._h, buf.ctypes.data_as(C.c_void_p), stride, *rest),
-                              "awpu_hip_spectral_blocks", buf.size // (256 * stride), first, every, rows, cols, out_rows, out_cols, flip, bands,
+                              "awpu_hip_spectral_blocks", n_blocks, first, every, rows, cols, out_rows, out_cols, flip, bands,
                               channel, scale, want_image, want_dominant, want_power)
 
     def spectral_samples(self, samples: np.ndarray, rows: int, cols: int, bands, channel=None, scale: int = SPECTRAL_SCALE_COMMON,
                          first: int = 0, every: int = 1, out_rows: int = 0, out_cols: int = 0, flip: bool = False, want_image: bool = True,
                          want_dominant: bool = True, want_power: bool = False) -> SpectralResult:
         """The same from unpacked samples [n_streams, N] (N a multiple of 256, oldest first) (awpu_hip_spectral_samples)."""
-        samples = np.ascontiguousarray(samples, np.float32)
-        if samples.ndim != 2 or samples.shape[0] != self.cfg.n_streams or samples.shape[1] % 256 or samples.shape[1] == 0:
-            raise ValueError(f"samples must be [{self.cfg.n_streams}, N] with N a positive multiple of 256")
+        samples, n_blocks = self._sample_blocks(samples)
         return self._spectral(lambda *rest: self._lib.awpu_hip_spectral_samples(self._h, _f32(samples), samples.shape[1], *rest),
-                              "awpu_hip_spectral_samples", samples.shape[1] // 256, first, every, rows, cols, out_rows, out_cols, flip, bands,
+                              "awpu_hip_spectral_samples", n_blocks, first, every, rows, cols, out_rows, out_cols, flip, bands,
                               channel, scale, want_image, want_dominant, want_power)
 
     def spectral_samples_device(self, d_samples_ptr: int, pitch: int, n_blocks: int, rows: int, cols: int, bands, channel=None,
@@ -1200,14 +1217,11 @@ class Engine:
     def _find(self, call, where, n_blocks, rows, cols, first, every, find, want_power) -> FindResult:
         n_frames, next_first = watch_count(n_blocks, first, every)
         w = Watch(first, every, rows, cols, 0, 0, 0, None)
-        f = Find(rows, cols, find.get("radius", 2), find.get("max_sources", 4), find.get("min_power", 0.0), find.get("min_ratio", 0.0),
-                 find.get("fov_deg", 180.0))
+        f = _find_struct(rows, cols, find)
         sources = np.empty((n_frames, max(f.max_sources, 0)), SOURCE_DTYPE)
         count = np.empty(n_frames, np.int32)
         power = np.empty((n_frames, self.pixel_count), np.float32) if want_power else None
-        # (an output that is wanted is never a null pointer, not even with no frame to write)
-        ptr = lambda a: C.c_void_p(a.ctypes.data or 16)
-        _check(call(n_blocks, C.byref(w), C.byref(f), ptr(sources), ptr(count), C.cast(ptr(power), _f32p) if want_power else None), where)
+        _check(call(n_blocks, C.byref(w), C.byref(f), _out_ptr(sources), _out_ptr(count), _out_ptr(power, _f32p)), where)
         return FindResult(sources, count, power, next_first)
 
     def find_blocks(self, wire, rows: int, cols: int, first: int = 0, every: int = 1, stride: int = DATAGRAM_BYTES,
@@ -1216,20 +1230,16 @@ class Engine:
         the ring, blocks first, first + every, ... are swept and their strongest peaks found on the device; find_peaks'
         keywords (radius, max_sources, min_power, min_ratio, fov_deg) say what a source is (awpu_hip_find_blocks).  -> FindResult;
         pass its .next_first as `first` of the call that continues the run."""
-        buf = np.frombuffer(wire, dtype=np.uint8)
-        if stride < DATAGRAM_BYTES or buf.size % (256 * stride) or buf.size == 0:
-            raise ValueError(f"wire must be a whole number of blocks of 256 datagrams {stride} bytes apart")
+        buf, n_blocks = _wire_blocks(wire, stride)
         return self._find(lambda *rest: self._lib.awpu_hip_find_blocks(self._h, buf.ctypes.data_as(C.c_void_p), stride, *rest),
-                          "awpu_hip_find_blocks", buf.size // (256 * stride), rows, cols, first, every, find, want_power)
+                          "awpu_hip_find_blocks", n_blocks, rows, cols, first, every, find, want_power)
 
     def find_samples(self, samples: np.ndarray, rows: int, cols: int, first: int = 0, every: int = 1, want_power: bool = False,
                      **find) -> FindResult:
         """The same from unpacked samples [n_streams, N] (N a multiple of 256, oldest first) (awpu_hip_find_samples)."""
-        samples = np.ascontiguousarray(samples, np.float32)
-        if samples.ndim != 2 or samples.shape[0] != self.cfg.n_streams or samples.shape[1] % 256 or samples.shape[1] == 0:
-            raise ValueError(f"samples must be [{self.cfg.n_streams}, N] with N a positive multiple of 256")
+        samples, n_blocks = self._sample_blocks(samples)
         return self._find(lambda *rest: self._lib.awpu_hip_find_samples(self._h, _f32(samples), samples.shape[1], *rest),
-                          "awpu_hip_find_samples", samples.shape[1] // 256, rows, cols, first, every, find, want_power)
+                          "awpu_hip_find_samples", n_blocks, rows, cols, first, every, find, want_power)
 
     def find_samples_device(self, d_samples_ptr: int, pitch: int, n_blocks: int, rows: int, cols: int, d_sources_ptr: int,
                             d_count_ptr: int, first: int = 0, every: int = 1, d_power_ptr: int = 0, stream: int = 0, **find) -> int:
@@ -1237,8 +1247,7 @@ class Engine:
         [n_frames] int32, power [n_frames, pixels] or 0) on `stream`; asynchronous.  -> next_first
         (awpu_hip_find_samples_device)."""
         w = Watch(first, every, rows, cols, 0, 0, 0, None)
-        f = Find(rows, cols, find.get("radius", 2), find.get("max_sources", 4), find.get("min_power", 0.0), find.get("min_ratio", 0.0),
-                 find.get("fov_deg", 180.0))
+        f = _find_struct(rows, cols, find)
         _check(self._lib.awpu_hip_find_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, C.byref(w), C.byref(f),
                                                       C.c_void_p(d_sources_ptr), C.c_void_p(d_count_ptr), C.c_void_p(d_power_ptr),
                                                       C.c_void_p(stream)), "awpu_hip_find_samples_device")
@@ -1263,21 +1272,10 @@ class Engine:
             carry = np.zeros(self.pixel_count, np.float32)
         elif carry.dtype != np.float32 or carry.shape != (self.pixel_count,) or not carry.flags.c_contiguous:
             raise ValueError("carry must be a contiguous float32 array [pixels]")
-        image = np.empty((n_frames, rows, cols), np.uint8) if want_image else None
-        big = np.empty((n_frames, out_rows, out_cols, 3) if d_colormap_ptr else (n_frames, out_rows, out_cols), np.uint8) if out_rows else None
-        power = np.empty((n_frames, self.pixel_count), np.float32) if want_power else None
-        f = sources = count = None
-        if find is not None:
-            f = Find(rows, cols, find.get("radius", 2), find.get("max_sources", 4), find.get("min_power", 0.0), find.get("min_ratio", 0.0),
-                     find.get("fov_deg", 180.0))
-            sources = np.empty((n_frames, max(f.max_sources, 0)), SOURCE_DTYPE)
-            count = np.empty(n_frames, np.int32)
-        # (an output that is wanted is never a null pointer, not even with no frame to write)
-        ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data or 16)
-        u8 = lambda a: None if a is None else C.cast(ptr(a), _u8p)
-        _check(call(n_blocks, C.byref(w), C.byref(e), None if f is None else C.byref(f), _f32(carry), u8(image), u8(big),
-                    None if power is None else C.cast(ptr(power), _f32p), ptr(sources), ptr(count)), where)
-        return ExposeResult(image, big, power, sources, count, next_first, carry)
+        f = _find_struct(rows, cols, find)
+        shown, ptrs = self._shown_outputs(n_frames, w, want_image, want_power, f)
+        _check(call(n_blocks, C.byref(w), C.byref(e), None if f is None else C.byref(f), _f32(carry), *ptrs), where)
+        return ExposeResult(*shown, next_first, carry)
 
     def expose_blocks(self, wire, rows: int, cols: int, length: int, first: Optional[int] = None, every: Optional[int] = None,
                       mode: int = EXPOSE_MEAN, carry: Optional[np.ndarray] = None, out_rows: int = 0, out_cols: int = 0,
@@ -1289,13 +1287,11 @@ class Engine:
         first block on.  `find` (a dict of find_peaks' keywords, {} for the defaults) also finds the sources of every exposed
         frame.  -> ExposeResult; pass its .next_first as `first` and its .carry as `carry` to the call that continues the run
         (carry is written in place)."""
-        buf = np.frombuffer(wire, dtype=np.uint8)
-        if stride < DATAGRAM_BYTES or buf.size % (256 * stride) or buf.size == 0:
-            raise ValueError(f"wire must be a whole number of blocks of 256 datagrams {stride} bytes apart")
+        buf, n_blocks = _wire_blocks(wire, stride)
         every = length if every is None else every
         first = length - 1 if first is None else first
         return self._expose(lambda *rest: self._lib.awpu_hip_expose_blocks(self._h, buf.ctypes.data_as(C.c_void_p), stride, *rest),
-                            "awpu_hip_expose_blocks", buf.size // (256 * stride), rows, cols, first, every, length, mode, carry, out_rows,
+                            "awpu_hip_expose_blocks", n_blocks, rows, cols, first, every, length, mode, carry, out_rows,
                             out_cols, d_colormap_ptr, flip, want_image, want_power, find)
 
     def expose_samples(self, samples: np.ndarray, rows: int, cols: int, length: int, first: Optional[int] = None,
@@ -1303,13 +1299,11 @@ class Engine:
                        out_cols: int = 0, d_colormap_ptr: int = 0, flip: bool = False, want_image: bool = True, want_power: bool = False,
                        find: Optional[dict] = None) -> ExposeResult:
         """The same from unpacked samples [n_streams, N] (N a multiple of 256, oldest first) (awpu_hip_expose_samples)."""
-        samples = np.ascontiguousarray(samples, np.float32)
-        if samples.ndim != 2 or samples.shape[0] != self.cfg.n_streams or samples.shape[1] % 256 or samples.shape[1] == 0:
-            raise ValueError(f"samples must be [{self.cfg.n_streams}, N] with N a positive multiple of 256")
+        samples, n_blocks = self._sample_blocks(samples)
         every = length if every is None else every
         first = length - 1 if first is None else first
         return self._expose(lambda *rest: self._lib.awpu_hip_expose_samples(self._h, _f32(samples), samples.shape[1], *rest),
-                            "awpu_hip_expose_samples", samples.shape[1] // 256, rows, cols, first, every, length, mode, carry, out_rows,
+                            "awpu_hip_expose_samples", n_blocks, rows, cols, first, every, length, mode, carry, out_rows,
                             out_cols, d_colormap_ptr, flip, want_image, want_power, find)
 
     def expose_samples_device(self, d_samples_ptr: int, pitch: int, n_blocks: int, rows: int, cols: int, length: int, first: int,
@@ -1321,10 +1315,7 @@ class Engine:
         (awpu_hip_expose_samples_device)."""
         w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(d_colormap_ptr))
         e = Expose(length, mode)
-        f = None
-        if find is not None:
-            f = Find(rows, cols, find.get("radius", 2), find.get("max_sources", 4), find.get("min_power", 0.0), find.get("min_ratio", 0.0),
-                     find.get("fov_deg", 180.0))
+        f = _find_struct(rows, cols, find)
         _check(self._lib.awpu_hip_expose_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, C.byref(w), C.byref(e),
                                                         None if f is None else C.byref(f), C.c_void_p(d_carry_ptr), C.c_void_p(d_image_ptr),
                                                         C.c_void_p(d_big_ptr), C.c_void_p(d_power_ptr), C.c_void_p(d_sources_ptr),
@@ -1369,21 +1360,10 @@ class Engine:
         n_frames, next_first = watch_count(n_blocks, first, every)
         w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(d_colormap_ptr))
         co = Cohere(show)
-        image = np.empty((n_frames, rows, cols), np.uint8) if want_image else None
-        big = np.empty((n_frames, out_rows, out_cols, 3) if d_colormap_ptr else (n_frames, out_rows, out_cols), np.uint8) if out_rows else None
-        power = np.empty((n_frames, self.pixel_count), np.float32) if want_power else None
-        f = sources = count = None
-        if find is not None:
-            f = Find(rows, cols, find.get("radius", 2), find.get("max_sources", 4), find.get("min_power", 0.0), find.get("min_ratio", 0.0),
-                     find.get("fov_deg", 180.0))
-            sources = np.empty((n_frames, max(f.max_sources, 0)), SOURCE_DTYPE)
-            count = np.empty(n_frames, np.int32)
-        # (an output that is wanted is never a null pointer, not even with no frame to write)
-        ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data or 16)
-        u8 = lambda a: None if a is None else C.cast(ptr(a), _u8p)
-        _check(call(n_blocks, C.byref(w), C.byref(co), None if f is None else C.byref(f), u8(image), u8(big),
-                    None if power is None else C.cast(ptr(power), _f32p), ptr(sources), ptr(count)), where)
-        return CohereResult(image, big, power, sources, count, next_first)
+        f = _find_struct(rows, cols, find)
+        shown, ptrs = self._shown_outputs(n_frames, w, want_image, want_power, f)
+        _check(call(n_blocks, C.byref(w), C.byref(co), None if f is None else C.byref(f), *ptrs), where)
+        return CohereResult(*shown, next_first)
 
     def cohere_blocks(self, wire, rows: int, cols: int, first: int = 0, every: int = 1, show: int = COHERE_WEIGHTED, out_rows: int = 0,
                       out_cols: int = 0, d_colormap_ptr: int = 0, flip: bool = False, stride: int = DATAGRAM_BYTES, want_image: bool = True,
@@ -1392,22 +1372,18 @@ class Engine:
         shown frame is its coherence-weighted row, or with show=COHERE_FACTOR its coherence row (awpu_hip_cohere_blocks).  `find`
         (a dict of find_peaks' keywords, {} for the defaults) also finds the sources of every frame.  -> CohereResult; pass its
         .next_first as `first` of the call that continues the run."""
-        buf = np.frombuffer(wire, dtype=np.uint8)
-        if stride < DATAGRAM_BYTES or buf.size % (256 * stride) or buf.size == 0:
-            raise ValueError(f"wire must be a whole number of blocks of 256 datagrams {stride} bytes apart")
+        buf, n_blocks = _wire_blocks(wire, stride)
         return self._cohere_run(lambda *rest: self._lib.awpu_hip_cohere_blocks(self._h, buf.ctypes.data_as(C.c_void_p), stride, *rest),
-                                "awpu_hip_cohere_blocks", buf.size // (256 * stride), rows, cols, first, every, show, out_rows, out_cols,
+                                "awpu_hip_cohere_blocks", n_blocks, rows, cols, first, every, show, out_rows, out_cols,
                                 d_colormap_ptr, flip, want_image, want_power, find)
 
     def cohere_samples(self, samples: np.ndarray, rows: int, cols: int, first: int = 0, every: int = 1, show: int = COHERE_WEIGHTED,
                        out_rows: int = 0, out_cols: int = 0, d_colormap_ptr: int = 0, flip: bool = False, want_image: bool = True,
                        want_power: bool = False, find: Optional[dict] = None) -> CohereResult:
         """The same from unpacked samples [n_streams, N] (N a multiple of 256, oldest first) (awpu_hip_cohere_samples)."""
-        samples = np.ascontiguousarray(samples, np.float32)
-        if samples.ndim != 2 or samples.shape[0] != self.cfg.n_streams or samples.shape[1] % 256 or samples.shape[1] == 0:
-            raise ValueError(f"samples must be [{self.cfg.n_streams}, N] with N a positive multiple of 256")
+        samples, n_blocks = self._sample_blocks(samples)
         return self._cohere_run(lambda *rest: self._lib.awpu_hip_cohere_samples(self._h, _f32(samples), samples.shape[1], *rest),
-                                "awpu_hip_cohere_samples", samples.shape[1] // 256, rows, cols, first, every, show, out_rows, out_cols,
+                                "awpu_hip_cohere_samples", n_blocks, rows, cols, first, every, show, out_rows, out_cols,
                                 d_colormap_ptr, flip, want_image, want_power, find)
 
     def cohere_samples_device(self, d_samples_ptr: int, pitch: int, n_blocks: int, rows: int, cols: int, first: int = 0, every: int = 1,
@@ -1419,10 +1395,7 @@ class Engine:
         (awpu_hip_cohere_samples_device)."""
         w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(d_colormap_ptr))
         co = Cohere(show)
-        f = None
-        if find is not None:
-            f = Find(rows, cols, find.get("radius", 2), find.get("max_sources", 4), find.get("min_power", 0.0), find.get("min_ratio", 0.0),
-                     find.get("fov_deg", 180.0))
+        f = _find_struct(rows, cols, find)
         _check(self._lib.awpu_hip_cohere_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, C.byref(w), C.byref(co),
                                                         None if f is None else C.byref(f), C.c_void_p(d_image_ptr), C.c_void_p(d_big_ptr),
                                                         C.c_void_p(d_power_ptr), C.c_void_p(d_sources_ptr), C.c_void_p(d_count_ptr),
@@ -1448,8 +1421,7 @@ class Engine:
     def _locate(self, call, where, n_blocks, rows, cols, first, every, distance, find, want_power, want_range_power) -> LocateResult:
         n_frames, next_first = watch_count(n_blocks, first, every)
         w = Watch(first, every, rows, cols, 0, 0, 0, None)
-        f = Find(rows, cols, find.get("radius", 2), find.get("max_sources", 4), find.get("min_power", 0.0), find.get("min_ratio", 0.0),
-                 find.get("fov_deg", 180.0))
+        f = _find_struct(rows, cols, find)
         distance = np.ascontiguousarray(np.atleast_1d(distance), np.float64)
         ms = max(f.max_sources, 0)
         sources = np.empty((n_frames, ms), SOURCE_DTYPE)
@@ -1457,10 +1429,8 @@ class Engine:
         power = np.empty((n_frames, self.pixel_count), np.float32) if want_power else None
         ranges = np.empty((n_frames, ms), RANGE_DTYPE)
         range_power = np.empty((n_frames, ms, distance.size), np.float32) if want_range_power else None
-        ptr = lambda a: C.c_void_p(a.ctypes.data or 16)
-        _check(call(n_blocks, C.byref(w), C.byref(f), ptr(sources), ptr(count), C.cast(ptr(power), _f32p) if want_power else None,
-                    distance.ctypes.data_as(_f64p), distance.size, ptr(ranges), C.cast(ptr(range_power), _f32p) if want_range_power else None),
-               where)
+        _check(call(n_blocks, C.byref(w), C.byref(f), _out_ptr(sources), _out_ptr(count), _out_ptr(power, _f32p),
+                    distance.ctypes.data_as(_f64p), distance.size, _out_ptr(ranges), _out_ptr(range_power, _f32p)), where)
         return LocateResult(sources, count, power, next_first, ranges, range_power)
 
     def locate_blocks(self, wire, rows: int, cols: int, distance, first: int = 0, every: int = 1, stride: int = DATAGRAM_BYTES,
@@ -1468,21 +1438,17 @@ class Engine:
         """find_blocks, and for every source it reports the beam power at that direction focused at every candidate `distance`
         (metres, inf = a plane wave), swept on the block's raw snapshot while it is on the device, and the distance at which it
         peaks (awpu_hip_locate_blocks).  Needs set_antenna.  -> LocateResult."""
-        buf = np.frombuffer(wire, dtype=np.uint8)
-        if stride < DATAGRAM_BYTES or buf.size % (256 * stride) or buf.size == 0:
-            raise ValueError(f"wire must be a whole number of blocks of 256 datagrams {stride} bytes apart")
+        buf, n_blocks = _wire_blocks(wire, stride)
         return self._locate(lambda *rest: self._lib.awpu_hip_locate_blocks(self._h, buf.ctypes.data_as(C.c_void_p), stride, *rest),
-                            "awpu_hip_locate_blocks", buf.size // (256 * stride), rows, cols, first, every, distance, find, want_power,
+                            "awpu_hip_locate_blocks", n_blocks, rows, cols, first, every, distance, find, want_power,
                             want_range_power)
 
     def locate_samples(self, samples: np.ndarray, rows: int, cols: int, distance, first: int = 0, every: int = 1, want_power: bool = False,
                        want_range_power: bool = False, **find) -> LocateResult:
         """The same from unpacked samples [n_streams, N] (N a multiple of 256, oldest first) (awpu_hip_locate_samples)."""
-        samples = np.ascontiguousarray(samples, np.float32)
-        if samples.ndim != 2 or samples.shape[0] != self.cfg.n_streams or samples.shape[1] % 256 or samples.shape[1] == 0:
-            raise ValueError(f"samples must be [{self.cfg.n_streams}, N] with N a positive multiple of 256")
+        samples, n_blocks = self._sample_blocks(samples)
         return self._locate(lambda *rest: self._lib.awpu_hip_locate_samples(self._h, _f32(samples), samples.shape[1], *rest),
-                            "awpu_hip_locate_samples", samples.shape[1] // 256, rows, cols, first, every, distance, find, want_power,
+                            "awpu_hip_locate_samples", n_blocks, rows, cols, first, every, distance, find, want_power,
                             want_range_power)
 
     def locate_samples_device(self, d_samples_ptr: int, pitch: int, n_blocks: int, rows: int, cols: int, distance, d_sources_ptr: int,
@@ -1492,8 +1458,7 @@ class Engine:
         range_power [n_frames, max_sources, n_dist] floats or 0) on `stream`; asynchronous.  -> next_first
         (awpu_hip_locate_samples_device)."""
         w = Watch(first, every, rows, cols, 0, 0, 0, None)
-        f = Find(rows, cols, find.get("radius", 2), find.get("max_sources", 4), find.get("min_power", 0.0), find.get("min_ratio", 0.0),
-                 find.get("fov_deg", 180.0))
+        f = _find_struct(rows, cols, find)
         distance = np.ascontiguousarray(np.atleast_1d(distance), np.float64)
         _check(self._lib.awpu_hip_locate_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, C.byref(w), C.byref(f),
                                                         C.c_void_p(d_sources_ptr), C.c_void_p(d_count_ptr), C.c_void_p(d_power_ptr),

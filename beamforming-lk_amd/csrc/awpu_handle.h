@@ -375,13 +375,14 @@ struct awpu_hip {
     // ev_listened[b]: the listen kernels have read blk_hist.d[b] (and written listen_out.d[b]); ev_listen_out[b]: listen_out.h[b] holds it
     Event ev_listened[2], ev_listen_out[2];
 
-    // watching such runs (awpu_hip_watch.h): piece i's peaks, compact images and (host forms) large images in watch.d[i & 1]; the
-    // host forms bring the images back through pinned watch.h[i & 1].  The events are those of the runs above: ev_blk_swept[b] is
-    // recorded behind the display kernels, ev_blk_out[b] behind the images' way back.
+    // watching such runs (awpu_hip_watch.h), exposed and coherence runs alike: piece i's peaks, compact images and (host forms)
+    // large images in watch.d[i & 1]; the host forms bring the images back through pinned watch.h[i & 1].  Laid out by the display
+    // step alone (struct Display in awpu_runs.cpp).  The events are those of the runs above: ev_blk_swept[b] is recorded behind the
+    // display kernels, ev_blk_out[b] behind the images' way back.
     awpu::host::BufferPair watch;
     // finding in such runs (awpu_hip_find.h), host forms: piece i's counts, then its sources, in find_out.d[i & 1] and back through
     // pinned find_out.h[i & 1], behind the same two events; locating (awpu_hip_focus.h) adds its ranges and the candidates' powers
-    // behind them (the device form: only the powers nobody asked for, in find_out.d[0])
+    // behind them (the device form: only the powers nobody asked for, in find_out.d[0]).  Laid out by the display step as well.
     awpu::host::BufferPair find_out;
     // exposing such runs (awpu_hip_expose.h): the open window's row [pixel_count] from piece to piece and from the caller's `carry`
     // to it, and the frames that close inside piece i in expose.d[i & 1] (the device form: in expose.d[0], where nobody asked for

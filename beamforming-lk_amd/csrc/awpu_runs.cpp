@@ -546,6 +546,122 @@ struct WatchRun {
     const FindRun *find = nullptr;
 };
 
+// The display step: what happens to the nf rows of powers that a piece shows -- a watch piece's swept frames, the frames that
+// closed inside an exposed piece --, for the outputs `wr` asks for.  The rows are on the device at d_rows, and j0 is the index of
+// the first of them in the call's outputs.  The host forms write into scratch with a pinned twin and bring it back (fetch,
+// deliver); the device form writes into the caller's arrays at j0 and keeps in scratch only what nobody asked for.  h->watch and
+// h->find_out are laid out here and nowhere else.
+struct Display {
+    awpu_hip *const h;
+    const WatchRun &wr;
+    const awpu_watch_t &w;
+    const FindRun *const fr;
+    const LocateRun *const lr;
+    const bool host, want_small;
+    const size_t P, big_bytes;
+    size_t small_off = 0, big_off = 0;  // in a watch buffer: the peaks, then the compact images, then the large ones
+    size_t sources_off = 0;             // in a find buffer: the counts, then the sources
+    size_t ranges_off = 0, rpower_off = 0;  // ... then (locate runs) the ranges and the candidates' powers; the device form keeps only the powers there, at 0
+
+    Display(awpu_hip *h_, const WatchRun &wr_, bool host_)
+        : h(h_), wr(wr_), w(wr_.w), fr(wr_.find), lr(wr_.find ? wr_.find->locate : nullptr), host(host_), want_small(wr_.image || wr_.big),
+          P((size_t) h_->cfg.pixel_count), big_bytes((size_t) wr_.w.out_rows * wr_.w.out_cols * (wr_.w.d_colormap ? 3 : 1)) {}
+    size_t source_bytes(int nf) const { return (size_t) nf * fr->f.max_sources * sizeof(awpu_source_t); }
+    size_t rpower_bytes(int nf) const { return (size_t) nf * fr->f.max_sources * lr->n_dist * sizeof(float); }
+
+    int check() const {
+        if (h->cfg.pixel_count != h->cfg.n_pixels) return invalid("the display step needs the whole grid on this handle");
+        if ((long long) w.rows * w.cols != h->cfg.n_pixels) return invalid("rows x cols must be the grid");
+        return lr ? check_antenna(h) : (int) AWPU_OK;
+    }
+    // its buffers, for pieces that show at most piece_max rows
+    int ensure(int piece_max, hipStream_t sw) {
+        small_off = align16(sizeof(float) * piece_max), big_off = small_off + align16((size_t) piece_max * P);
+        sources_off = align16(sizeof(int32_t) * piece_max);
+        int rc = want_small ? h->watch.ensure(big_off + (host && wr.big ? (size_t) piece_max * big_bytes : 0), host) : (int) AWPU_OK;
+        if (rc == AWPU_OK && wr.big) rc = ensure_taps(h, w.rows, w.cols, w.out_rows, w.out_cols, sw);
+        if (rc != AWPU_OK || !fr) return rc;
+        if (!lr) return host ? h->find_out.ensure(sources_off + source_bytes(piece_max), true) : (int) AWPU_OK;
+        ranges_off = sources_off + align16(source_bytes(piece_max));
+        rpower_off = host ? ranges_off + (size_t) piece_max * fr->f.max_sources * sizeof(awpu_range_t) : 0;
+        rc = ensure_track_index(h);
+        if (rc == AWPU_OK && (host || !lr->range_power)) rc = h->find_out.ensure(rpower_off + rpower_bytes(piece_max), host);
+        return rc;
+    }
+    // the range pass: launch_range over every entry of the rows' sources, picked on the device, on the rows' snapshots -- raw
+    // samples, whatever the sweep was given --: row k's starts at hist + frame_step * k
+    int range(int b, int j0, int nf, const awpu_source_t *d_sources, const float *hist, int hist_pitch, long long frame_step, hipStream_t s) {
+        const int ms = fr->f.max_sources;
+        unsigned char *out = h->find_out.d[host ? b : 0];
+        awpu::RangeArgs a{};
+        a.frame_step = frame_step;
+        a.per_frame = ms;
+        a.pitch = hist_pitch;
+        a.xyz = h->d_xyz;
+        a.n = (int) (h->antenna.size() / 3);
+        a.index = h->d_track_index;
+        a.usable = h->usable();
+        a.n_dist = lr->n_dist;
+        for (int j = 0; j < lr->n_dist; j++) a.distance[j] = lr->distance[j];
+        float *d_rpower = host || !lr->range_power ? reinterpret_cast<float *>(out + rpower_off) : lr->range_power + (size_t) j0 * ms * lr->n_dist;
+        awpu_range_t *d_ranges = host ? reinterpret_cast<awpu_range_t *>(out + ranges_off) : lr->ranges + (size_t) j0 * ms;
+        for (int k0 = 0; k0 < nf; k0 += 1024) {  // (a launch's grid: at most 65535 sources)
+            a.frame = hist + (size_t) k0 * frame_step;
+            a.sources = d_sources + (size_t) k0 * ms;
+            a.n_src = std::min(1024, nf - k0) * ms;
+            a.power = d_rpower + (size_t) k0 * ms * lr->n_dist;
+            a.best = d_ranges + (size_t) k0 * ms;
+            AWPU_HIP_TRY(awpu::launch_range(a, s));
+        }
+        return AWPU_OK;
+    }
+    // the peak pass, a locate run's range pass (a watch run's alone: its rows have snapshots, in `hist`), the compact image, the large one
+    int show(int b, int j0, int nf, const float *d_rows, hipStream_t s, const float *hist = nullptr, int hist_pitch = 0, long long frame_step = 0) {
+        if (nf == 0) return AWPU_OK;
+        if (fr) {
+            unsigned char *out = h->find_out.d[b];
+            awpu_source_t *d_sources = host ? reinterpret_cast<awpu_source_t *>(out + sources_off) : fr->sources + (size_t) j0 * fr->f.max_sources;
+            AWPU_HIP_TRY(awpu::launch_find_peaks(d_rows, nf, fr->f, d_sources, host ? reinterpret_cast<int32_t *>(out) : fr->count + j0, s));
+            if (lr)
+                if (const int rc = range(b, j0, nf, d_sources, hist, hist_pitch, frame_step, s)) return rc;
+        }
+        if (!want_small) return AWPU_OK;
+        uint8_t *scratch = h->watch.d[host ? b : 0];
+        uint8_t *d_small = host || !wr.image ? scratch + small_off : wr.image + (size_t) j0 * P;
+        AWPU_HIP_TRY(awpu::launch_heatmap(d_rows, (int) P, nf, reinterpret_cast<float *>(scratch), false, d_small, s));
+        if (wr.big)
+            AWPU_HIP_TRY(awpu::launch_watch_upscale(d_small, w.rows, w.cols, nf, h->d_taps, h->taps_band_rows, w.d_colormap, w.flip != 0,
+                                                    host ? scratch + big_off : wr.big + (size_t) j0 * big_bytes, w.out_rows, w.out_cols, s));
+        return AWPU_OK;
+    }
+    // host forms: into pinned memory, and on to the caller
+    int fetch(int b, int nf, hipStream_t s) {
+        if (nf == 0) return AWPU_OK;
+        if (fr)
+            AWPU_HIP_TRY(hipMemcpyAsync(h->find_out.h[b], h->find_out.d[b], lr ? rpower_off + rpower_bytes(nf) : sources_off + source_bytes(nf),
+                                        hipMemcpyDeviceToHost, s));
+        uint8_t *to = h->watch.h[b], *from = h->watch.d[b];
+        if (wr.image) AWPU_HIP_TRY(hipMemcpyAsync(to + small_off, from + small_off, (size_t) nf * P, hipMemcpyDeviceToHost, s));
+        if (wr.big) AWPU_HIP_TRY(hipMemcpyAsync(to + big_off, from + big_off, (size_t) nf * big_bytes, hipMemcpyDeviceToHost, s));
+        return AWPU_OK;
+    }
+    int deliver(int b, int j0, int nf) {
+        if (nf == 0) return AWPU_OK;
+        if (fr) {
+            std::memcpy(fr->count + j0, h->find_out.h[b], sizeof(int32_t) * nf);
+            std::memcpy(fr->sources + (size_t) j0 * fr->f.max_sources, h->find_out.h[b] + sources_off, source_bytes(nf));
+        }
+        if (lr) {
+            const size_t entries = (size_t) j0 * fr->f.max_sources;
+            std::memcpy(lr->ranges + entries, h->find_out.h[b] + ranges_off, (size_t) nf * fr->f.max_sources * sizeof(awpu_range_t));
+            if (lr->range_power) std::memcpy(lr->range_power + entries * lr->n_dist, h->find_out.h[b] + rpower_off, rpower_bytes(nf));
+        }
+        if (wr.image) std::memcpy(wr.image + (size_t) j0 * P, h->watch.h[b] + small_off, (size_t) nf * P);
+        if (wr.big) parallel_copy(wr.big + (size_t) j0 * big_bytes, h->watch.h[b] + big_off, (size_t) nf * big_bytes);
+        return AWPU_OK;
+    }
+};
+
 // slots [q, slots) of a piece's history, slot s holding block block_of(s) of the call, into pinned blk_in.h[b]: tight datagrams,
 // or rows of 256 * (slots - q)
 template <class Map>
@@ -579,25 +695,42 @@ void stage_watch(awpu_hip *h, const BlockRun &src, int b0, int every, int q, int
     stage_slots(h, src, [=](int slot) { return awpu::watch_slot_block(slot, b0, every, m); }, q, slots, b);
 }
 
+// the history of a gathered piece (watch, exposure), whose slots [0, q) hold blocks from before the call: gather(src, src_pitch, n)
+// fills slots [0, n) out of the ring's snapshot and src.  The device form: one gather out of the caller's samples; the host
+// forms: [0, q) gathered, the rest -- staged and uploaded -- unpacked or copied in at slot q
+template <class Gather>
+int gathered_history(awpu_hip *h, const BlockRun &src, int b, int q, int slots, int pitch, hipStream_t s, const Gather &gather) {
+    if (src.device) {
+        AWPU_HIP_TRY(gather(src.samples, (long long) src.pitch, slots));
+        return AWPU_OK;
+    }
+    const int S = h->cfg.n_streams;
+    float *hist = hist_of(h, b);
+    if (q > 0) AWPU_HIP_TRY(gather(nullptr, 0LL, q));
+    if (src.wire) {
+        AWPU_HIP_TRY(awpu::launch_unpack_blocks(h->blk_in.d[b], slots - q, S, hist, pitch, awpu::kSamples * q, s));
+    } else {
+        const long long n = (long long) awpu::kSamples * (slots - q);
+        AWPU_HIP_TRY(awpu::launch_copy_rows(reinterpret_cast<const float *>(h->blk_in.d[b].get()), n, hist + awpu::kSamples * q, pitch, (int) n, S, s));
+    }
+    return AWPU_OK;
+}
+
 struct WatchPieces : Consumer {
     awpu_hip *const h;
     const BlockRun &src;
     const WatchRun &wr;
     const awpu_watch_t &w;
-    const FindRun *const fr;
-    const LocateRun *const lr;
-    const bool host, want_small;
+    const bool host;
     const int S, m;
-    const size_t P, big_bytes;
+    const size_t P;
+    Display display;
     int lo = 0, width = 0;
-    size_t small_off = 0, big_off = 0;  // in a watch buffer: the peaks, then the compact images, then the large ones
-    size_t sources_off = 0;             // in a find buffer: the counts, then the sources
-    size_t ranges_off = 0, rpower_off = 0;  // ... then (locate runs) the ranges and the candidates' powers; the device form keeps only the powers there, at 0
     const float *snapshot = nullptr;    // blocks -4 .. -1 of the call
 
     WatchPieces(awpu_hip *h_, const BlockRun &src_, int n_blocks_, const WatchRun &wr_)
-        : h(h_), src(src_), wr(wr_), w(wr_.w), fr(wr_.find), lr(wr_.find ? wr_.find->locate : nullptr), host(!src_.device), want_small(wr_.image || wr_.big), S(h_->cfg.n_streams), m(std::min(wr_.w.every, 4)),
-          P((size_t) h_->cfg.pixel_count), big_bytes((size_t) wr_.w.out_rows * wr_.w.out_cols * (wr_.w.d_colormap ? 3 : 1)) {
+        : h(h_), src(src_), wr(wr_), w(wr_.w), host(!src_.device), S(h_->cfg.n_streams), m(std::min(wr_.w.every, 4)), P((size_t) h_->cfg.pixel_count),
+          display(h_, wr_, !src_.device) {
         n_items = wr.n_frames;
         n_blocks = n_blocks_;
         power = wr.power;
@@ -613,31 +746,15 @@ struct WatchPieces : Consumer {
         return {b0, every, awpu::watch_slots(every, p.tail ? 1 : p.n), std::max(0, std::min(3 - b0, 4))};
     }
 
-    int check() override {
-        if (h->cfg.pixel_count != h->cfg.n_pixels) return invalid("the display step needs the whole grid on this handle");
-        if ((long long) w.rows * w.cols != h->cfg.n_pixels) return invalid("rows x cols must be the grid");
-        return lr ? check_antenna(h) : (int) AWPU_OK;
-    }
+    int check() override { return display.check(); }
     int ensure(int piece_max, int lo_, int width_, hipStream_t sw) override {
         lo = lo_, width = width_;
         const int slots_max = awpu::watch_slots(w.every, piece_max);
         pitch = awpu::kSamples * slots_max;
-        small_off = align16(sizeof(float) * piece_max), big_off = small_off + align16((size_t) piece_max * P);
         snapshot = h->d_ring + h->ring_pos;
         int rc = ensure_run_buffers(h, src, piece_max, width, true, slots_max - 3, slots_max, bands.planes());
         if (rc == AWPU_OK && !host && !wr.power) rc = ensure_power(h, (size_t) piece_max * P * bands.planes());
-        if (rc == AWPU_OK && want_small) rc = h->watch.ensure(big_off + (host && wr.big ? (size_t) piece_max * big_bytes : 0), host);
-        if (rc == AWPU_OK && wr.big) rc = ensure_taps(h, w.rows, w.cols, w.out_rows, w.out_cols, sw);
-        sources_off = align16(sizeof(int32_t) * piece_max);
-        if (lr) {
-            ranges_off = sources_off + align16(source_bytes(piece_max));
-            rpower_off = host ? ranges_off + (size_t) piece_max * fr->f.max_sources * sizeof(awpu_range_t) : 0;
-            if (rc == AWPU_OK) rc = ensure_track_index(h);
-            if (rc == AWPU_OK && (host || !lr->range_power)) rc = h->find_out.ensure(rpower_off + rpower_bytes(piece_max), host);
-            return rc;
-        }
-        if (rc == AWPU_OK && fr && host) rc = h->find_out.ensure(sources_off + source_bytes(piece_max), true);
-        return rc;
+        return rc != AWPU_OK ? rc : display.ensure(piece_max, sw);
     }
     int staged_blocks(const Piece &p) override {
         const Span g = span(p);
@@ -646,96 +763,33 @@ struct WatchPieces : Consumer {
     }
     int history(const Piece &p, hipStream_t s) override {
         const Span g = span(p);
-        float *hist = hist_of(h, p.b);
-        if (!host) {
-            AWPU_HIP_TRY(awpu::launch_watch_gather(src.samples, src.pitch, snapshot, g.b0, g.every, S, hist, pitch, 0, g.slots, s));
-            return AWPU_OK;
-        }
-        if (g.q > 0) AWPU_HIP_TRY(awpu::launch_watch_gather(nullptr, 0, snapshot, g.b0, g.every, S, hist, pitch, 0, g.q, s));
-        if (src.wire) {
-            AWPU_HIP_TRY(awpu::launch_unpack_blocks(h->blk_in.d[p.b], g.slots - g.q, S, hist, pitch, awpu::kSamples * g.q, s));
-        } else {
-            const long long n = (long long) awpu::kSamples * (g.slots - g.q);
-            AWPU_HIP_TRY(awpu::launch_copy_rows(reinterpret_cast<const float *>(h->blk_in.d[p.b].get()), n, hist + awpu::kSamples * g.q, pitch, (int) n, S, s));
-        }
-        return AWPU_OK;
+        return gathered_history(h, src, p.b, g.q, g.slots, pitch, s, [&](const float *from, long long from_pitch, int n) {
+            return awpu::launch_watch_gather(from, from_pitch, snapshot, g.b0, g.every, S, hist_of(h, p.b), pitch, 0, n, s);
+        });
     }
     int cut(const Piece &p, hipStream_t s) override {
         if (bands.n) return band_cut(h, bands, hist_of(h, p.b), awpu::kSamples * m, pitch, h->wstart, p.n, h->d_blk_frames, (long long) S * width * p.n, h->compact_hist > 0 ? kCompact : kFull, s);
         AWPU_HIP_TRY(awpu::launch_watch_cut(hist_of(h, p.b), pitch, S, p.n, awpu::kSamples * m, lo, width, h->d_blk_frames, s));
         return AWPU_OK;
     }
-    size_t source_bytes(int nf) const { return (size_t) nf * fr->f.max_sources * sizeof(awpu_source_t); }
-    size_t rpower_bytes(int nf) const { return (size_t) nf * fr->f.max_sources * lr->n_dist * sizeof(float); }
-    // the range pass of a piece: shown frame j's snapshot starts at sample 256 * m * j of the history, as the cut reads it
-    int range(const Piece &p, const awpu_source_t *d_sources, hipStream_t s) {
-        const int ms = fr->f.max_sources;
-        unsigned char *out = h->find_out.d[host ? p.b : 0];
-        awpu::RangeArgs a{};
-        a.frame_step = (long long) awpu::kSamples * m;
-        a.per_frame = ms;
-        a.pitch = pitch;
-        a.xyz = h->d_xyz;
-        a.n = (int) (h->antenna.size() / 3);
-        a.index = h->d_track_index;
-        a.usable = h->usable();
-        a.n_dist = lr->n_dist;
-        for (int j = 0; j < lr->n_dist; j++) a.distance[j] = lr->distance[j];
-        float *d_rpower = host || !lr->range_power ? reinterpret_cast<float *>(out + rpower_off) : lr->range_power + (size_t) p.first * ms * lr->n_dist;
-        awpu_range_t *d_ranges = host ? reinterpret_cast<awpu_range_t *>(out + ranges_off) : lr->ranges + (size_t) p.first * ms;
-        for (int j0 = 0; j0 < p.n; j0 += 1024) {  // (a launch's grid: at most 65535 sources)
-            const int nf = std::min(1024, p.n - j0);
-            a.frame = hist_of(h, p.b) + (size_t) j0 * a.frame_step;
-            a.sources = d_sources + (size_t) j0 * ms;
-            a.n_src = nf * ms;
-            a.power = d_rpower + (size_t) j0 * ms * lr->n_dist;
-            a.best = d_ranges + (size_t) j0 * ms;
-            AWPU_HIP_TRY(awpu::launch_range(a, s));
-        }
-        return AWPU_OK;
-    }
+    // shown frame j's snapshot starts at sample 256 * m * j of the history, as the cut reads it
     int show(const Piece &p, float *d_pow, long long, hipStream_t s) override {
-        if (fr) {
-            unsigned char *out = h->find_out.d[p.b];
-            awpu_source_t *d_sources = host ? reinterpret_cast<awpu_source_t *>(out + sources_off) : fr->sources + (size_t) p.first * fr->f.max_sources;
-            AWPU_HIP_TRY(awpu::launch_find_peaks(d_pow, p.n, fr->f, d_sources, host ? reinterpret_cast<int32_t *>(out) : fr->count + p.first, s));
-            if (lr)
-                if (const int rc = range(p, d_sources, s)) return rc;
-        }
-        if (!want_small) return AWPU_OK;
-        uint8_t *scratch = h->watch.d[host ? p.b : 0];
-        uint8_t *d_small = host || !wr.image ? scratch + small_off : wr.image + (size_t) p.first * P;
-        AWPU_HIP_TRY(awpu::launch_heatmap(d_pow, (int) P, p.n, reinterpret_cast<float *>(scratch), false, d_small, s));
-        if (wr.big)
-            AWPU_HIP_TRY(awpu::launch_watch_upscale(d_small, w.rows, w.cols, p.n, h->d_taps, h->taps_band_rows, w.d_colormap, w.flip != 0,
-                                                    host ? scratch + big_off : wr.big + (size_t) p.first * big_bytes, w.out_rows, w.out_cols, s));
-        return AWPU_OK;
+        return display.show(p.b, p.first, p.n, d_pow, s, hist_of(h, p.b), pitch, (long long) awpu::kSamples * m);
     }
-    int fetch_shown(const Piece &p, hipStream_t s) override {
-        if (fr)
-            AWPU_HIP_TRY(hipMemcpyAsync(h->find_out.h[p.b], h->find_out.d[p.b], lr ? rpower_off + rpower_bytes(p.n) : sources_off + source_bytes(p.n),
-                                        hipMemcpyDeviceToHost, s));
-        uint8_t *to = h->watch.h[p.b], *from = h->watch.d[p.b];
-        if (wr.image) AWPU_HIP_TRY(hipMemcpyAsync(to + small_off, from + small_off, (size_t) p.n * P, hipMemcpyDeviceToHost, s));
-        if (wr.big) AWPU_HIP_TRY(hipMemcpyAsync(to + big_off, from + big_off, (size_t) p.n * big_bytes, hipMemcpyDeviceToHost, s));
-        return AWPU_OK;
-    }
-    int deliver_shown(const Piece &p) override {
-        if (fr) {
-            std::memcpy(fr->count + p.first, h->find_out.h[p.b], sizeof(int32_t) * p.n);
-            std::memcpy(fr->sources + (size_t) p.first * fr->f.max_sources, h->find_out.h[p.b] + sources_off, source_bytes(p.n));
-        }
-        if (lr) {
-            const size_t entries = (size_t) p.first * fr->f.max_sources;
-            std::memcpy(lr->ranges + entries, h->find_out.h[p.b] + ranges_off, (size_t) p.n * fr->f.max_sources * sizeof(awpu_range_t));
-            if (lr->range_power) std::memcpy(lr->range_power + entries * lr->n_dist, h->find_out.h[p.b] + rpower_off, rpower_bytes(p.n));
-        }
-        if (wr.image) std::memcpy(wr.image + (size_t) p.first * P, h->watch.h[p.b] + small_off, (size_t) p.n * P);
-        if (wr.big) parallel_copy(wr.big + (size_t) p.first * big_bytes, h->watch.h[p.b] + big_off, (size_t) p.n * big_bytes);
-        return AWPU_OK;
-    }
+    int fetch_shown(const Piece &p, hipStream_t s) override { return display.fetch(p.b, p.n, s); }
+    int deliver_shown(const Piece &p) override { return display.deliver(p.b, p.first, p.n); }
     int ring_from(const Piece &last) override { return last.tail ? 0 : awpu::kSamples * (awpu::watch_slots(w.every, last.n) - 4); }
 };
+
+// the find request of a call on the watch grid `w`: with sources and count or not at all, and then one find_peaks takes
+int check_find_request(const awpu_watch_t *w, const awpu_find_t *f, const awpu_source_t *sources, const int32_t *count) {
+    if (!sources != !count) return invalid("sources and count come together");
+    if (!f != !sources) return invalid("a find request exactly when sources and count are asked for");
+    if (!f) return AWPU_OK;
+    if (const char *why = awpu::find_refusal(f)) return invalid(why);
+    if (f->rows != w->rows || f->cols != w->cols) return invalid("the find grid must be the watch grid");
+    return AWPU_OK;
+}
 
 // the checks of a watch call that read no handle (any_output: something is asked for; big: a large image is), and what it shows
 int check_watch(const awpu_watch_t *w, bool any_output, bool big, int n_blocks, WatchRun *wr) {
@@ -852,8 +906,8 @@ int find_run(awpu_hip *h, const BlockRun &src, int n_blocks, const awpu_watch_t 
     if (locate && !locate->ranges) return invalid("null argument");
     if (locate)
         if (const int rc = check_candidates(locate->distance, locate->n_dist)) return rc;
-    if (const char *why = awpu::find_refusal(f)) return invalid(why);
-    if (f->rows != w->rows || f->cols != w->cols) return invalid("the find grid must be the watch grid");
+    if (!f) return invalid("null argument");
+    if (const int rc = check_find_request(w, f, sources, count)) return rc;
     awpu_watch_t shown{};
     shown.first = w->first, shown.every = w->every, shown.rows = w->rows, shown.cols = w->cols;
     const FindRun find{*f, sources, count, locate};
@@ -873,16 +927,10 @@ int find_run(awpu_hip *h, const BlockRun &src, int n_blocks, const awpu_watch_t 
 // deliver_shown and Consumer::power stays null.  The ring's new snapshot: as in a watch run.
 
 struct ExposeRun {
-    awpu_watch_t w{};
+    WatchRun shown;          // what it shows and where to: the outputs and the find request of a watch run, for the exposed frames
     awpu_expose_t e{};
     awpu::ExposeCount n{};
-    float *carry = nullptr;                    // host memory in the host forms, device memory in the device form, like the outputs
-    uint8_t *image = nullptr, *big = nullptr;
-    float *power = nullptr;
-    bool finds = false;
-    awpu_find_t f{};
-    awpu_source_t *sources = nullptr;
-    int32_t *count = nullptr;
+    float *carry = nullptr;  // host memory in the host forms, device memory in the device form, like the outputs
 };
 
 struct ExposePieces final : Consumer {
@@ -890,20 +938,19 @@ struct ExposePieces final : Consumer {
     const BlockRun &src;
     const ExposeRun &er;
     const awpu_watch_t &w;
-    const bool host, want_small;
+    const bool host;
     const int S, L, E, c_in;
-    const size_t P, big_bytes;
+    const size_t P;
+    Display display;
+    float *const exposed;               // the exposed frames' powers, or null (Consumer::power, the swept blocks', stays null)
     int lo = 0, width = 0;
-    size_t small_off = 0, big_off = 0;  // in a watch buffer: the peaks, then the compact images, then the large ones
-    size_t sources_off = 0;             // in a find buffer: the counts, then the sources
     const float *snapshot = nullptr;    // blocks -4 .. -1 of the call
     hipStream_t sw = nullptr;
     std::vector<float> carried;         // host forms: the open window after the run
 
     ExposePieces(awpu_hip *h_, const BlockRun &src_, int n_blocks_, const ExposeRun &er_)
-        : h(h_), src(src_), er(er_), w(er_.w), host(!src_.device), want_small(er_.image || er_.big), S(h_->cfg.n_streams), L(er_.e.length),
-          E(er_.w.every), c_in(er_.n.carry_in), P((size_t) h_->cfg.pixel_count),
-          big_bytes((size_t) er_.w.out_rows * er_.w.out_cols * (er_.w.d_colormap ? 3 : 1)) {
+        : h(h_), src(src_), er(er_), w(er_.shown.w), host(!src_.device), S(h_->cfg.n_streams), L(er_.e.length), E(er_.shown.w.every),
+          c_in(er_.n.carry_in), P((size_t) h_->cfg.pixel_count), display(h_, er_.shown, !src_.device), exposed(er_.shown.power) {
         n_items = er.n.n_swept;
         n_blocks = n_blocks_;
         // the last block of the call swept: the ring's new snapshot is the tail of the last piece's history
@@ -911,6 +958,7 @@ struct ExposePieces final : Consumer {
     }
     int item_block(int s) const { return w.first + (s + c_in) / L * E - (L - 1) + (s + c_in) % L; }
     int frames_before(int s) const { return (s + c_in) / L; }
+    int closed_in(const Piece &p) const { return frames_before(p.first + p.n) - frames_before(p.first); }  // the frames a piece shows
     // the slot map of a piece's history
     awpu::ExposeSlots map(const Piece &p) const {
         if (p.tail) return {n_blocks - 1, 1, n_blocks - 1 + E, E, L, false};
@@ -924,26 +972,17 @@ struct ExposePieces final : Consumer {
         return E - L >= 3 ? n + 3 * windows : n + 3 + (windows - 1) * (E - L);
     }
 
-    int check() override {
-        if (h->cfg.pixel_count != h->cfg.n_pixels) return invalid("the display step needs the whole grid on this handle");
-        if ((long long) w.rows * w.cols != h->cfg.n_pixels) return invalid("rows x cols must be the grid");
-        return AWPU_OK;
-    }
-    size_t source_bytes(int nf) const { return (size_t) nf * er.f.max_sources * sizeof(awpu_source_t); }
+    int check() override { return display.check(); }
     int ensure(int piece_max, int lo_, int width_, hipStream_t sw_) override {
         lo = lo_, width = width_, sw = sw_;
         const int most = std::max(slots_max(piece_max), 4);
         pitch = awpu::kSamples * most;
-        small_off = align16(sizeof(float) * piece_max), big_off = small_off + align16((size_t) piece_max * P);
-        sources_off = align16(sizeof(int32_t) * piece_max);
         snapshot = h->d_ring + h->ring_pos;
         int rc = ensure_run_buffers(h, src, piece_max, width, true, most - 3, most, bands.planes());
         if (rc == AWPU_OK && !host) rc = ensure_power(h, (size_t) piece_max * P * bands.planes());
         if (rc == AWPU_OK) rc = h->d_expose_carry.ensure(P);
-        if (rc == AWPU_OK && (host || !er.power)) rc = h->expose.ensure((size_t) piece_max * P * sizeof(float), false);
-        if (rc == AWPU_OK && want_small) rc = h->watch.ensure(big_off + (host && er.big ? (size_t) piece_max * big_bytes : 0), host);
-        if (rc == AWPU_OK && er.big) rc = ensure_taps(h, w.rows, w.cols, w.out_rows, w.out_cols, sw);
-        if (rc == AWPU_OK && er.finds && host) rc = h->find_out.ensure(sources_off + source_bytes(piece_max), true);
+        if (rc == AWPU_OK && (host || !exposed)) rc = h->expose.ensure((size_t) piece_max * P * sizeof(float), false);
+        if (rc == AWPU_OK) rc = display.ensure(piece_max, sw);
         if (host && er.n.carry_out > 0) carried.resize(P);
         return rc;
     }
@@ -960,20 +999,9 @@ struct ExposePieces final : Consumer {
     }
     int history(const Piece &p, hipStream_t s) override {
         const awpu::ExposeSlots m = map(p);
-        const int slots = slots_of(p, m), q = std::max(0, 3 - m.k0);  // slots [0, q) hold blocks from before the call
-        float *hist = hist_of(h, p.b);
-        if (!host) {
-            AWPU_HIP_TRY(awpu::launch_expose_gather(src.samples, src.pitch, snapshot, m, S, hist, pitch, 0, slots, s));
-            return AWPU_OK;
-        }
-        if (q > 0) AWPU_HIP_TRY(awpu::launch_expose_gather(nullptr, 0, snapshot, m, S, hist, pitch, 0, q, s));
-        if (src.wire) {
-            AWPU_HIP_TRY(awpu::launch_unpack_blocks(h->blk_in.d[p.b], slots - q, S, hist, pitch, awpu::kSamples * q, s));
-        } else {
-            const long long n = (long long) awpu::kSamples * (slots - q);
-            AWPU_HIP_TRY(awpu::launch_copy_rows(reinterpret_cast<const float *>(h->blk_in.d[p.b].get()), n, hist + awpu::kSamples * q, pitch, (int) n, S, s));
-        }
-        return AWPU_OK;
+        return gathered_history(h, src, p.b, std::max(0, 3 - m.k0), slots_of(p, m), pitch, s, [&](const float *from, long long from_pitch, int n) {
+            return awpu::launch_expose_gather(from, from_pitch, snapshot, m, S, hist_of(h, p.b), pitch, 0, n, s);
+        });
     }
     int cut(const Piece &p, hipStream_t s) override {
         const awpu::ExposeSlots m = map(p);
@@ -991,46 +1019,21 @@ struct ExposePieces final : Consumer {
         return AWPU_OK;
     }
     int show(const Piece &p, float *d_pow, long long, hipStream_t s) override {
-        const int j0 = frames_before(p.first), nf = frames_before(p.first + p.n) - j0;
+        const int j0 = frames_before(p.first);
         const awpu::ExposeWindows win{p.n, -((p.first + c_in) % L), L, L};
-        float *d_frames = host || !er.power ? reinterpret_cast<float *>(h->expose.d[host ? p.b : 0].get()) : er.power + (size_t) j0 * P;
-        AWPU_HIP_TRY(awpu::launch_expose(d_pow, (long long) P, win, er.e.mode, h->d_expose_carry, d_frames, s));
-        if (nf == 0) return AWPU_OK;
-        if (er.finds) {
-            unsigned char *out = h->find_out.d[p.b];
-            awpu_source_t *d_sources = host ? reinterpret_cast<awpu_source_t *>(out + sources_off) : er.sources + (size_t) j0 * er.f.max_sources;
-            AWPU_HIP_TRY(awpu::launch_find_peaks(d_frames, nf, er.f, d_sources, host ? reinterpret_cast<int32_t *>(out) : er.count + j0, s));
-        }
-        if (!want_small) return AWPU_OK;
-        uint8_t *scratch = h->watch.d[host ? p.b : 0];
-        uint8_t *d_small = host || !er.image ? scratch + small_off : er.image + (size_t) j0 * P;
-        AWPU_HIP_TRY(awpu::launch_heatmap(d_frames, (int) P, nf, reinterpret_cast<float *>(scratch), false, d_small, s));
-        if (er.big)
-            AWPU_HIP_TRY(awpu::launch_watch_upscale(d_small, w.rows, w.cols, nf, h->d_taps, h->taps_band_rows, w.d_colormap, w.flip != 0,
-                                                    host ? scratch + big_off : er.big + (size_t) j0 * big_bytes, w.out_rows, w.out_cols, s));
-        return AWPU_OK;
+        float *d_frames = host || !exposed ?reinterpret_cast<float *>(h->expose.d[host ? p.b : 0].get()) : exposed + (size_t) j0 * P;
+        AWPU_HIP_TRY(awpu::launch_expose(d_pow, (long long) P, win, er.e.mode, h->d_expose_carry, d_frames, s));  // (no frame closes: the carry still moves on)
+        return display.show(p.b, j0, closed_in(p), d_frames, s);
     }
     int fetch_shown(const Piece &p, hipStream_t s) override {
-        const int nf = frames_before(p.first + p.n) - frames_before(p.first);
-        if (nf == 0) return AWPU_OK;
-        if (er.power) AWPU_HIP_TRY(hipMemcpyAsync(h->blk_out.h[p.b], h->expose.d[p.b], (size_t) nf * P * sizeof(float), hipMemcpyDeviceToHost, s));
-        if (er.finds) AWPU_HIP_TRY(hipMemcpyAsync(h->find_out.h[p.b], h->find_out.d[p.b], sources_off + source_bytes(nf), hipMemcpyDeviceToHost, s));
-        uint8_t *to = h->watch.h[p.b], *from = h->watch.d[p.b];
-        if (er.image) AWPU_HIP_TRY(hipMemcpyAsync(to + small_off, from + small_off, (size_t) nf * P, hipMemcpyDeviceToHost, s));
-        if (er.big) AWPU_HIP_TRY(hipMemcpyAsync(to + big_off, from + big_off, (size_t) nf * big_bytes, hipMemcpyDeviceToHost, s));
-        return AWPU_OK;
+        const int nf = closed_in(p);
+        if (nf && exposed) AWPU_HIP_TRY(hipMemcpyAsync(h->blk_out.h[p.b], h->expose.d[p.b], (size_t) nf * P * sizeof(float), hipMemcpyDeviceToHost, s));
+        return display.fetch(p.b, nf, s);
     }
     int deliver_shown(const Piece &p) override {
-        const int j0 = frames_before(p.first), nf = frames_before(p.first + p.n) - j0;
-        if (nf == 0) return AWPU_OK;
-        if (er.power) std::memcpy(er.power + (size_t) j0 * P, h->blk_out.h[p.b], (size_t) nf * P * sizeof(float));
-        if (er.finds) {
-            std::memcpy(er.count + j0, h->find_out.h[p.b], sizeof(int32_t) * nf);
-            std::memcpy(er.sources + (size_t) j0 * er.f.max_sources, h->find_out.h[p.b] + sources_off, source_bytes(nf));
-        }
-        if (er.image) std::memcpy(er.image + (size_t) j0 * P, h->watch.h[p.b] + small_off, (size_t) nf * P);
-        if (er.big) parallel_copy(er.big + (size_t) j0 * big_bytes, h->watch.h[p.b] + big_off, (size_t) nf * big_bytes);
-        return AWPU_OK;
+        const int j0 = frames_before(p.first), nf = closed_in(p);
+        if (nf && exposed) std::memcpy(exposed + (size_t) j0 * P, h->blk_out.h[p.b], (size_t) nf * P * sizeof(float));
+        return display.deliver(p.b, j0, nf);
     }
     int ring_from(const Piece &last) override { return awpu::kSamples * (slots_of(last, map(last)) - 4); }
     // the open window, behind the last piece's exposure on the sweep's stream (whatever stream the listen kernels of other runs have)
@@ -1050,18 +1053,13 @@ int expose_run(awpu_hip *h, const BlockRun &src, int n_blocks, const awpu_watch_
     WatchRun wr;
     if (int rc = check_watch(w, image || big || power || sources || count, big != nullptr, n_blocks, &wr)) return rc;
     if (const char *why = awpu::expose_refusal(e, w->every)) return invalid(why);
-    if (!sources != !count) return invalid("sources and count come together");
-    if (!f != !sources) return invalid("a find request exactly when sources and count are asked for");
-    if (f) {
-        if (const char *why = awpu::find_refusal(f)) return invalid(why);
-        if (f->rows != w->rows || f->cols != w->cols) return invalid("the find grid must be the watch grid");
-    }
-    ExposeRun er;
-    er.w = *w, er.e = *e;
-    er.n = awpu::expose_count(n_blocks, w->first, w->every, e->length);
+    if (const int rc = check_find_request(w, f, sources, count)) return rc;
+    FindRun find;
+    if (f) find.f = *f, find.sources = sources, find.count = count;
+    wr.image = image, wr.big = big, wr.power = power;
+    wr.find = f ? &find : nullptr;
+    const ExposeRun er{wr, *e, awpu::expose_count(n_blocks, w->first, w->every, e->length), carry};
     if (!carry && (er.n.carry_in > 0 || er.n.carry_out > 0)) return invalid("null carry with a window open across the call's ends");
-    er.carry = carry, er.image = image, er.big = big, er.power = power;
-    if (f) er.finds = true, er.f = *f, er.sources = sources, er.count = count;
     AWPU_CTX(h);
     ExposePieces c(h, src, n_blocks, er);
     const int rc = run_pieces(h, src, user, c);
@@ -1097,12 +1095,7 @@ int cohere_run(awpu_hip *h, const BlockRun &src, int n_blocks, const awpu_watch_
     WatchRun wr;
     if (int rc = check_watch(w, image || big || power || sources || count, big != nullptr, n_blocks, &wr)) return rc;
     if (const char *why = awpu::cohere_refusal(co)) return invalid(why);
-    if (!sources != !count) return invalid("sources and count come together");
-    if (!f != !sources) return invalid("a find request exactly when sources and count are asked for");
-    if (f) {
-        if (const char *why = awpu::find_refusal(f)) return invalid(why);
-        if (f->rows != w->rows || f->cols != w->cols) return invalid("the find grid must be the watch grid");
-    }
+    if (const int rc = check_find_request(w, f, sources, count)) return rc;
     FindRun find;
     if (f) find.f = *f, find.sources = sources, find.count = count;
     wr.image = image, wr.big = big, wr.power = power;

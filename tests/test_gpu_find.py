@@ -88,8 +88,7 @@ def test_large_tie_heavy_frames(pkg, res):
 
 # ------------------------------------------------------------------------------------------------ the runs
 
-@pytest.fixture(scope="module")
-def c1(pkg, oracle):
+def c1_recording(pkg, oracle):
     """c1 (64 mics, 32 x 32): table, antenna, and 23 blocks of a plane wave in noise (synthetic.make_frames, one long history),
     quantised to the wire's 24 bits: (off, frac, xyz, wire, samples)."""
     S = pkg.synthetic
@@ -105,6 +104,11 @@ def c1(pkg, oracle):
         wire.append(make_datagrams(stream, counter0=256 * b))
         blocks.append(oracle.unpack_exposure(stream, 64))
     return off, frac, xyz, b"".join(wire), np.concatenate(blocks, axis=1)
+
+
+@pytest.fixture(scope="module")
+def c1(pkg, oracle):
+    return c1_recording(pkg, oracle)
 
 
 def same_sources(a, b):

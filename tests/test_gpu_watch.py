@@ -247,6 +247,92 @@ def test_split_and_interleaved_runs(pkg, ref100):
         assert np.array_equal(eng.ring_snapshot(), one_more)
 
 
+@pytest.fixture(scope="module")
+def c1(pkg, oracle):
+    """test_gpu_find's c1 recording (64 mics, 32 x 32, 23 blocks); that module imports this one, so it is imported here."""
+    from test_gpu_find import c1_recording
+
+    return c1_recording(pkg, oracle)
+
+
+def test_kinds_in_turn_on_one_handle(pkg, c1):
+    """The run kinds share the handle's display and find buffers (and the run buffers), which grow from device-only to device plus
+    pinned when a host form follows a device form: one engine (max_batch 4) takes the whole recording through watch_samples_device,
+    expose_samples, find_blocks, cohere_samples, locate_samples, watch_blocks and expose_samples_device in turn, and every result
+    equals the same call on a fresh engine.  Both engines ran process_samples(recording) first, so every call starts from the same
+    ring.  Images, counts, pixel / row / col and the powers' bits are equal, theta / phi within test_find_cpu.TOL, the ring
+    afterwards equal; device outputs are guarded.  The coherence run's large image is 49 x 65: the 17 x 33 one is below the 32 x 32
+    grid and is refused (upscale only), by both engines alike, before anything of the handle is touched."""
+    import torch
+
+    from test_gpu_expose import assert_sources, device_run
+
+    off, frac, xyz, wire, samples = c1
+    table, d_table = colour_table(11)
+    d_in = torch.from_numpy(np.ascontiguousarray(samples)).cuda()
+    find = dict(radius=2, max_sources=4, min_ratio=0.25)
+
+    def prepared():
+        eng = engine(pkg, off, frac, 64, 32, 4)
+        eng.set_antenna(xyz)
+        eng.process_samples(samples)
+        return eng
+
+    def watch_device(eng):
+        n_frames = len(range(1, 23, 2))
+        d_image = torch.full((n_frames * 1024 + 64,), 0xA5, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        nxt = eng.watch_samples_device(d_in.data_ptr(), samples.shape[1], 23, 32, 32, first=1, every=2, d_image_ptr=d_image.data_ptr())
+        eng.synchronize()
+        back = d_image.cpu().numpy()
+        assert np.all(back[n_frames * 1024:] == 0xA5)
+        return pkg.binding.WatchResult(back[: n_frames * 1024].reshape(n_frames, 32, 32), None, None, nxt)
+
+    def expose_device(eng):
+        d_carry = torch.zeros(1024, dtype=torch.float32, device="cuda")
+        got, _ = device_run(pkg, eng, d_in, samples.shape[1], 23, 2, 3, 2, pkg.binding.EXPOSE_MEAN, d_carry, d_table, (40, 56), True)
+        got.carry = d_carry.cpu().numpy()
+        return got
+
+    def refused_then_cohere(eng):
+        with pytest.raises(pkg.AwpuError) as ei:
+            eng.cohere_samples(samples, 32, 32, first=0, every=2, out_rows=17, out_cols=33, find=find)
+        assert "upscale only" in str(ei.value)
+        return eng.cohere_samples(samples, 32, 32, first=0, every=2, out_rows=49, out_cols=65, want_power=True, find=find)
+
+    calls = [
+        ("watch_samples_device", watch_device),
+        ("expose_samples", lambda e: e.expose_samples(samples, 32, 32, 2, first=2, every=3, out_rows=40, out_cols=56,
+                                                      d_colormap_ptr=d_table.data_ptr(), want_power=True, find=find)),
+        ("find_blocks", lambda e: e.find_blocks(wire, 32, 32, first=0, every=1, want_power=True, radius=2, max_sources=8, min_ratio=0.25)),
+        ("cohere_samples", refused_then_cohere),
+        ("locate_samples", lambda e: e.locate_samples(samples, 32, 32, [0.5, 2.0, np.inf], first=1, every=3, want_power=True,
+                                                      want_range_power=True, **find)),
+        ("watch_blocks", lambda e: e.watch_blocks(wire, 32, 32, first=0, every=1, out_rows=64, out_cols=64, d_colormap_ptr=d_table.data_ptr())),
+        ("expose_samples_device", expose_device),
+    ]
+    bits = lambda a: np.ascontiguousarray(a).view(np.uint32)
+    with prepared() as one:
+        for where, call in calls:
+            got = call(one)
+            with prepared() as fresh:
+                want = call(fresh)
+                assert np.array_equal(one.ring_snapshot(), fresh.ring_snapshot()), where
+            assert got.next_first == want.next_first and len(got) == len(want) > 0, where
+            for name in ("image", "big", "power", "carry", "range_power"):
+                a, b = getattr(got, name, None), getattr(want, name, None)
+                assert (a is None) == (b is None), (where, name)
+                if a is not None:
+                    assert a.shape == b.shape and np.array_equal(bits(a) if a.dtype == np.float32 else a, bits(b) if b.dtype == np.float32 else b), (where, name)
+            if getattr(want, "sources", None) is not None:
+                assert want.count.max() >= 1, where
+                assert_sources(got.sources, got.count, want, where)
+            if hasattr(want, "ranges"):
+                assert np.array_equal(got.ranges["index"], want.ranges["index"]) and (want.ranges["index"] >= 0).any(), where
+                assert np.array_equal(bits(got.ranges["power"]), bits(want.ranges["power"])), where
+                assert np.array_equal(got.ranges["distance"], want.ranges["distance"], equal_nan=True), where
+
+
 def test_samples_forms(pkg, oracle, small):
     """Item 9: the host samples form == the wire form; 512 streams, which the wire cannot carry; the device form == the host form."""
     import torch
