@@ -30,6 +30,10 @@ from .binding import (  # noqa: F401
     focus_delays,
     focus_steer_table,
     heatmap_u8,
+    peel_beam_length,
+    peel_host,
+    peel_sources,
+    peel_step_host,
     range_candidates,
     range_pick,
     resize_linear_u8,
@@ -39,7 +43,7 @@ from .binding import (  # noqa: F401
 
 __all__ = [
     "Engine", "AwpuError", "MATH_F32_EXACT", "MATH_F32_FAST", "MATH_BF16_ACC", "build_delay_table", "build_delay_table_device",
-    "create_antenna", "create_tiled_antenna", "steering_delays", "heatmap_u8", "find_peaks", "expose_count", "expose_rows", "cohere_host", "band_design", "band_filter", "resize_linear_u8", "steer_table", "focus_delays", "focus_steer_table",
+    "create_antenna", "create_tiled_antenna", "steering_delays", "heatmap_u8", "find_peaks", "expose_count", "expose_rows", "cohere_host", "peel_host", "peel_step_host", "peel_beam_length", "peel_sources", "band_design", "band_filter", "resize_linear_u8", "steer_table", "focus_delays", "focus_steer_table",
     "build_focus_table", "build_focus_table_device", "range_pick", "range_candidates", "binding",
     "synthetic", "_build",
 ]

@@ -16,14 +16,14 @@ REPO = PKG_DIR.parent
 CSRC = PKG_DIR / "csrc"
 LIB_PATH = PKG_DIR / "libawpu_hip.so"
 
-SOURCES = [CSRC / "das_kernels.hip", CSRC / "das_fast.hip", CSRC / "track_kernels.hip", CSRC / "block_kernels.hip", CSRC / "watch_kernels.hip", CSRC / "find_kernels.hip", CSRC / "band_kernels.hip", CSRC / "spectral_kernels.hip", CSRC / "expose_kernels.hip", CSRC / "cohere_kernels.hip",
-           CSRC / "awpu_hip.cpp", CSRC / "awpu_group.cpp", CSRC / "awpu_sweep.cpp", CSRC / "awpu_runs.cpp", CSRC / "geometry_host.cpp", CSRC / "find_host.cpp", CSRC / "band_host.cpp", CSRC / "spectral_host.cpp", CSRC / "awpu_focus.cpp", CSRC / "expose_host.cpp", CSRC / "awpu_cohere.cpp", CSRC / "cohere_host.cpp"]
+SOURCES = [CSRC / "das_kernels.hip", CSRC / "das_fast.hip", CSRC / "track_kernels.hip", CSRC / "block_kernels.hip", CSRC / "watch_kernels.hip", CSRC / "find_kernels.hip", CSRC / "band_kernels.hip", CSRC / "spectral_kernels.hip", CSRC / "expose_kernels.hip", CSRC / "cohere_kernels.hip", CSRC / "peel_kernels.hip",
+           CSRC / "awpu_hip.cpp", CSRC / "awpu_group.cpp", CSRC / "awpu_sweep.cpp", CSRC / "awpu_runs.cpp", CSRC / "geometry_host.cpp", CSRC / "find_host.cpp", CSRC / "band_host.cpp", CSRC / "spectral_host.cpp", CSRC / "awpu_focus.cpp", CSRC / "expose_host.cpp", CSRC / "awpu_cohere.cpp", CSRC / "cohere_host.cpp", CSRC / "awpu_peel.cpp", CSRC / "peel_host.cpp"]
 # das_fast_trip.inc -- the hand-scheduled inner loops of das_fast.hip -- is GENERATED at build time by tools/gen_trip_asm.py
 # (not tracked: ~19 000 lines of asm text whose source is the generator)
 GENERATOR = REPO / "tools" / "gen_trip_asm.py"
 TRIP_INC = CSRC / "das_fast_trip.inc"
-HEADERS = [CSRC / "awpu_handle.h", CSRC / "das_kernels.h", CSRC / "block_kernels.h", CSRC / "watch_kernels.h", CSRC / "find_kernels.h", CSRC / "find_rule.h", CSRC / "band_kernels.h", CSRC / "band_rule.h", CSRC / "spectral_kernels.h", CSRC / "spectral_rule.h", CSRC / "focus_rule.h", CSRC / "expose_kernels.h", CSRC / "expose_rule.h", CSRC / "cohere_kernels.h", CSRC / "cohere_rule.h", CSRC / "nd_tile_window.h", CSRC / "sweep_plan.h", GENERATOR, REPO / "include" / "awpu_hip.h", REPO / "include" / "awpu_hip_track.h",
-           REPO / "include" / "awpu_hip_blocks.h", REPO / "include" / "awpu_hip_listen.h", REPO / "include" / "awpu_hip_watch.h", REPO / "include" / "awpu_hip_find.h", REPO / "include" / "awpu_hip_band.h", REPO / "include" / "awpu_hip_focus.h", REPO / "include" / "awpu_hip_spectral.h", REPO / "include" / "awpu_hip_expose.h", REPO / "include" / "awpu_hip_cohere.h"]
+HEADERS = [CSRC / "awpu_handle.h", CSRC / "das_kernels.h", CSRC / "block_kernels.h", CSRC / "watch_kernels.h", CSRC / "find_kernels.h", CSRC / "find_rule.h", CSRC / "band_kernels.h", CSRC / "band_rule.h", CSRC / "spectral_kernels.h", CSRC / "spectral_rule.h", CSRC / "focus_rule.h", CSRC / "expose_kernels.h", CSRC / "expose_rule.h", CSRC / "cohere_kernels.h", CSRC / "cohere_rule.h", CSRC / "peel_kernels.h", CSRC / "peel_rule.h", CSRC / "nd_tile_window.h", CSRC / "sweep_plan.h", GENERATOR, REPO / "include" / "awpu_hip.h", REPO / "include" / "awpu_hip_track.h",
+           REPO / "include" / "awpu_hip_blocks.h", REPO / "include" / "awpu_hip_listen.h", REPO / "include" / "awpu_hip_watch.h", REPO / "include" / "awpu_hip_find.h", REPO / "include" / "awpu_hip_band.h", REPO / "include" / "awpu_hip_focus.h", REPO / "include" / "awpu_hip_spectral.h", REPO / "include" / "awpu_hip_expose.h", REPO / "include" / "awpu_hip_cohere.h", REPO / "include" / "awpu_hip_peel.h"]
 
 
 def hipcc_path() -> str:

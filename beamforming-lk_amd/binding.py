@@ -370,6 +370,41 @@ _COHERE_SIGNATURES = {
 }
 COHERE_SYMBOLS = tuple(_COHERE_SIGNATURES)
 
+# peeling sources: the entry points of include/awpu_hip_peel.h
+PEEL_MAX_STEPS, PEEL_MAX_MICS = 32, 256
+PEEL_MAP, PEEL_CLEAN, PEEL_RESIDUAL = 0, 1, 2  # what a peel run shows
+
+
+class Peel(C.Structure):
+    """awpu_peel_t (include/awpu_hip_peel.h)."""
+    _fields_ = [
+        ("steps", C.c_int32),
+        ("gain", C.c_float),
+        ("stop_ratio", C.c_float),
+    ]
+
+
+# numpy view of awpu_peel_step_t: what peel_host and Engine.peel return, `steps` records per frame (unused: pixel -1)
+PEEL_STEP_DTYPE = np.dtype([("pixel", "<i4"), ("before", "<f4"), ("removed", "<f4")])
+assert PEEL_STEP_DTYPE.itemsize == 12 and C.sizeof(Peel) == 12
+
+_PEEL_TABLE = [C.c_int32, C.c_int32, _i32p, _f32p, C.c_int32, C.c_int32, _i32p, C.c_int32]  # n_streams, hist, off, frac, lut_stride, n_pixels, index, usable
+_PEEL_TAIL = [*_WATCH_TAIL, C.POINTER(Peel), C.c_int32, C.POINTER(Find)]  # n_blocks, w, pe, show, f
+_PEEL_SIGNATURES = {
+    "awpu_hip_peel_beam_length": (C.c_int32, _PEEL_TABLE),
+    "awpu_hip_peel_step_host": (C.c_int, [_f32p, C.c_int32, *_PEEL_TABLE, _f32p, _i32p, C.c_float, _f32p]),
+    "awpu_hip_peel_host": (C.c_int, [_f32p, C.c_int32, *_PEEL_TABLE, _f32p, C.POINTER(Peel), C.c_void_p, _f32p, _f32p, _f32p, _f32p]),
+    "awpu_hip_peel_step_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
+    "awpu_hip_peel": (C.c_int, [C.c_void_p, _f32p, C.c_int32, C.POINTER(Peel), C.c_void_p, _f32p, _f32p, _f32p, _f32p]),
+    "awpu_hip_peel_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Peel), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    "awpu_hip_peel_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, *_PEEL_TAIL, _u8p, _u8p, _f32p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "awpu_hip_peel_samples": (C.c_int, [C.c_void_p, _f32p, C.c_int64, *_PEEL_TAIL, _u8p, _u8p, _f32p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "awpu_hip_peel_samples_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, *_PEEL_TAIL, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+PEEL_SYMBOLS = tuple(_PEEL_SIGNATURES)
+
 # numpy view of awpu_range_t: what range_pick, Engine.range and Engine.locate_* return (unused entries: index -1)
 RANGE_DTYPE = np.dtype([("index", "<i4"), ("power", "<f4"), ("distance", "<f8")], align=True)
 assert RANGE_DTYPE.itemsize == C.sizeof(Range) == 16
@@ -408,7 +443,7 @@ def load(build: bool = True) -> C.CDLL:
     for name, (res, args) in list(_SIGNATURES.items()) + list(_TRACK_SIGNATURES.items()) + list(_BLOCK_SIGNATURES.items()) + \
             list(_LISTEN_SIGNATURES.items()) + list(_WATCH_SIGNATURES.items()) + list(_FIND_SIGNATURES.items()) + list(_BAND_SIGNATURES.items()) + \
             list(_FOCUS_SIGNATURES.items()) + list(_SPECTRAL_SIGNATURES.items()) + list(_EXPOSE_SIGNATURES.items()) + \
-            list(_COHERE_SIGNATURES.items()):
+            list(_COHERE_SIGNATURES.items()) + list(_PEEL_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -806,6 +841,111 @@ def cohere_host(frames: np.ndarray, off: np.ndarray, frac: np.ndarray, index=Non
                                        *[None if m is None else _f32(m) for m in wide]), "awpu_hip_cohere_host")
     out = maps + wide if want_sums else maps
     return tuple(m[0] for m in out) if single else tuple(out)
+
+
+class PeelResult:
+    """What peel_host and Engine.peel hand back: .steps [batch, steps] records of PEEL_STEP_DTYPE (unused: pixel -1), .clean,
+    .residual, .map [batch, n_pixels], .frames the residual frames [batch, n_streams, hist] or None."""
+
+    def __init__(self, steps, clean, residual, map, frames):  # noqa: A002 (the header's name)
+        self.steps, self.clean, self.residual, self.map, self.frames = steps, clean, residual, map, frames
+
+
+def peel_source_records(steps: np.ndarray, rows: int, cols: int, max_sources: int, fov_deg: float = 180.0):
+    """The steps of a peel run's frames [n_frames, steps] as find results: -> (sources [n_frames, max_sources] SOURCE_DTYPE records,
+    count [n_frames]).  A frame's sources are its steps merged per pixel (peel_sources: the clean map's entries), strongest
+    first; row and col are the pixel's own (a step has no sub-pixel refinement), theta and phi its direction on the table's
+    sine-space grid, as awpu_hip_find.h gives them."""
+    steps = np.asarray(steps)
+    sources = np.zeros((len(steps), max_sources), SOURCE_DTYPE)
+    sources["pixel"] = -1
+    count = np.zeros(len(steps), np.int32)
+    sep_r, sep_c = (np.sin(np.float64(np.float32(fov_deg)) * (np.pi / 180.0) / 2.0) / (n / 2.0) for n in (rows, cols))
+    for j, frame in enumerate(steps):
+        merged = peel_sources(frame)[:max_sources]
+        count[j] = len(merged)
+        for k, (pixel, power) in enumerate(merged):
+            r, c = divmod(int(pixel), cols)
+            y = r * sep_r - rows * sep_r / 2.0 + sep_r / 2.0
+            x = c * sep_c - cols * sep_c / 2.0 + sep_c / 2.0
+            sources[j, k] = (pixel, power, r, c, np.arcsin(min(np.hypot(x, y), 1.0)), 0.0 if x == 0.0 and y == 0.0 else np.arctan2(y, x))
+    return sources, count
+
+
+class PeelRunResult:
+    """What Engine.peel_blocks / peel_samples hand back: .image, .big, .power as a WatchResult has them -- of the map (or, by
+    `show`, the clean or the residual) rows --, .steps [n_frames, steps] PEEL_STEP_DTYPE records, .sources and .count as a
+    FindResult has them (None without `find`), .next_first for the call that continues the run."""
+
+    def __init__(self, image, big, power, steps, sources, count, next_first: int):
+        self.image, self.big, self.power, self.steps, self.sources, self.count, self.next_first = image, big, power, steps, sources, count, next_first
+
+    def __len__(self):
+        return len(self.steps)
+
+
+def _peel_table(frames, off, frac, index, gain):
+    frames = np.ascontiguousarray(frames, np.float32)
+    off = np.ascontiguousarray(off, np.int32)
+    frac = np.ascontiguousarray(frac, np.float32)
+    if frames.ndim != 3 or off.ndim != 2 or off.shape != frac.shape:
+        raise ValueError("frames must be [batch, n_streams, hist], off and frac [n_pixels, lut_stride]")
+    index = np.arange(off.shape[1], dtype=np.int32) if index is None else np.ascontiguousarray(index, np.int32)
+    if gain is not None:
+        gain = np.ascontiguousarray(gain, np.float32)
+        if gain.shape != index.shape:
+            raise ValueError("gain must be [usable], in the active list's order")
+    table = (frames.shape[1], frames.shape[2], _i32(off), _f32(frac), off.shape[1], off.shape[0], _i32(index), len(index))
+    return frames, table, None if gain is None else _f32(gain), (off, frac, index, gain)  # (the arrays: kept alive by the caller)
+
+
+def peel_beam_length(n_streams: int, hist: int, off: np.ndarray, frac: np.ndarray, index=None) -> int:
+    """258 + 2 E: the samples of a peel step's beam for this table at these mics (awpu_hip_peel_beam_length)."""
+    _, table, _, _keep = _peel_table(np.zeros((1, n_streams, hist), np.float32), off, frac, index, None)
+    n = load().awpu_hip_peel_beam_length(*table)
+    if n < 0:
+        _check(n, "awpu_hip_peel_beam_length")
+    return n
+
+
+def peel_step_host(frames: np.ndarray, off: np.ndarray, frac: np.ndarray, pixel, loop_gain: float = 1.0, index=None, gain=None):
+    """One peel step as executable C (awpu_hip_peel_step_host): frames [batch, n_streams, hist], pixel [batch] (-1 = leave the
+    frame alone).  -> (residual frames, beams [batch, 258 + 2 E]); `frames` itself is not written."""
+    frames, table, g, _keep = _peel_table(frames, off, frac, index, gain)
+    frames = frames.copy()
+    pixel = np.ascontiguousarray(pixel, np.int32)
+    if pixel.shape != (frames.shape[0],):
+        raise ValueError("pixel must be [batch]")
+    n = load().awpu_hip_peel_beam_length(*table)
+    beams = np.empty((frames.shape[0], max(n, 1)), np.float32)
+    _check(load().awpu_hip_peel_step_host(_f32(frames), frames.shape[0], *table, g, _i32(pixel), loop_gain, _f32(beams)), "awpu_hip_peel_step_host")
+    return frames, beams
+
+
+def peel_host(frames: np.ndarray, off: np.ndarray, frac: np.ndarray, steps: int, gain_loop: float = 1.0, stop_ratio: float = 0.0, index=None,
+              gain=None, want_frames: bool = True) -> PeelResult:
+    """The peel loop as executable C (awpu_hip_peel_host): frames [batch, n_streams, hist], the table off / frac [n_pixels,
+    lut_stride], index = the active stream ids (default: all of the table's), gain [usable] in their order or None."""
+    frames, table, g, _keep = _peel_table(frames, off, frac, index, gain)
+    batch, n_pixels = frames.shape[0], table[5]
+    pe = Peel(steps, gain_loop, stop_ratio)
+    rec = np.empty((batch, max(steps, 0)), PEEL_STEP_DTYPE)
+    maps = [np.empty((batch, n_pixels), np.float32) for _ in range(3)]
+    left = np.empty_like(frames) if want_frames else None
+    _check(load().awpu_hip_peel_host(_f32(frames), batch, *table, g, C.byref(pe), C.c_void_p(rec.ctypes.data or 16), *[_f32(m) for m in maps],
+                                     None if left is None else _f32(left)), "awpu_hip_peel_host")
+    return PeelResult(rec, *maps, left)
+
+
+def peel_sources(steps: np.ndarray) -> np.ndarray:
+    """The steps of one frame merged per pixel: records (pixel, power) -- the `removed` of the steps at a pixel, added in step
+    order, which is clean[pixel] --, strongest first."""
+    merged = {}
+    for s in np.asarray(steps).reshape(-1):
+        if s["pixel"] >= 0:
+            merged[int(s["pixel"])] = np.float32(merged.get(int(s["pixel"]), np.float32(0)) + s["removed"])
+    out = np.array(sorted(merged.items(), key=lambda kv: (-kv[1], kv[0])), dtype=[("pixel", "<i4"), ("power", "<f4")])
+    return out
 
 
 class CohereResult:
@@ -1354,6 +1494,89 @@ class Engine:
         _check(self._lib.awpu_hip_cohere_device_sums(self._h, C.c_void_p(d_frames_ptr), batch, C.c_void_p(d_power_ptr), C.c_void_p(d_coherence_ptr),
                                                      C.c_void_p(d_weighted_ptr), C.c_void_p(d_sums_ptr), C.c_void_p(d_energy_ptr),
                                                      C.c_void_p(stream)), "awpu_hip_cohere_device_sums")
+
+    def peel(self, frames: np.ndarray, steps: int, gain: float = 1.0, stop_ratio: float = 0.0, want_frames: bool = False) -> "PeelResult":
+        """Peel the sources of host frames [batch, n_streams, hist] (or one frame) (awpu_hip_peel): `steps` rounds of sweep, pick
+        the strongest pixel, subtract its beam from every active mic.  -> a PeelResult: .steps [batch, steps] (PEEL_STEP_DTYPE),
+        .clean, .residual, .map [batch, pixels], and with want_frames .frames, the residual frames.  The handle's gains apply."""
+        frames = np.ascontiguousarray(frames, np.float32)
+        single = frames.ndim == 2
+        if single:
+            frames = frames[None]
+        if frames.shape[1:] != (self.cfg.n_streams, self.cfg.hist):
+            raise ValueError(f"frames must be [batch, {self.cfg.n_streams}, {self.cfg.hist}]")
+        batch = frames.shape[0]
+        pe = Peel(steps, gain, stop_ratio)
+        rec = np.empty((batch, max(steps, 0)), PEEL_STEP_DTYPE)
+        maps = [np.empty((batch, self.pixel_count), np.float32) for _ in range(3)]
+        left = np.empty_like(frames) if want_frames else None
+        _check(self._lib.awpu_hip_peel(self._h, _f32(frames), batch, C.byref(pe), C.c_void_p(rec.ctypes.data or 16), *[_f32(m) for m in maps],
+                                       None if left is None else _f32(left)), "awpu_hip_peel")
+        out = [rec, *maps, left]
+        return PeelResult(*[m[0] if single and m is not None else m for m in out])
+
+    def peel_device(self, d_frames_ptr: int, batch: int, steps: int, gain: float = 1.0, stop_ratio: float = 0.0, d_steps_ptr: int = 0,
+                    d_clean_ptr: int = 0, d_residual_ptr: int = 0, d_map_ptr: int = 0, d_residual_frames_ptr: int = 0, stream: int = 0) -> None:
+        """The same on device pointers (frames [batch, n_streams, hist], not written; steps [batch, steps] records of 12 bytes;
+        each map [batch, pixels]; the residual frames; each output or 0) on `stream`; asynchronous, with no wait inside the loop
+        (awpu_hip_peel_device)."""
+        pe = Peel(steps, gain, stop_ratio)
+        _check(self._lib.awpu_hip_peel_device(self._h, C.c_void_p(d_frames_ptr), batch, C.byref(pe), C.c_void_p(d_steps_ptr), C.c_void_p(d_clean_ptr),
+                                              C.c_void_p(d_residual_ptr), C.c_void_p(d_map_ptr), C.c_void_p(d_residual_frames_ptr),
+                                              C.c_void_p(stream)), "awpu_hip_peel_device")
+
+    def peel_step_device(self, d_frames_ptr: int, batch: int, d_pixel_ptr: int, gain: float = 1.0, d_beams_ptr: int = 0, stream: int = 0) -> None:
+        """One step, in place, on device pointers: frames [batch, n_streams, hist]; pixel [batch] int32, -1 = leave the frame alone;
+        beams [batch, peel_beam_length] or 0 (awpu_hip_peel_step_device).  Asynchronous on `stream`."""
+        _check(self._lib.awpu_hip_peel_step_device(self._h, C.c_void_p(d_frames_ptr), batch, C.c_void_p(d_pixel_ptr), gain, C.c_void_p(d_beams_ptr),
+                                                   C.c_void_p(stream)), "awpu_hip_peel_step_device")
+
+    def _peel_run(self, call, where, n_blocks, rows, cols, first, every, steps, gain, stop_ratio, show, out_rows, out_cols, d_colormap_ptr, flip,
+                  want_image, want_power, find) -> PeelRunResult:
+        n_frames, next_first = watch_count(n_blocks, first, every)
+        w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(d_colormap_ptr))
+        pe = Peel(steps, gain, stop_ratio)
+        f = _find_struct(rows, cols, find)
+        (image, big, power, sources, count), ptrs = self._shown_outputs(n_frames, w, want_image, want_power, f)
+        rec = np.empty((n_frames, max(steps, 0)), PEEL_STEP_DTYPE)
+        _check(call(n_blocks, C.byref(w), C.byref(pe), show, None if f is None else C.byref(f), *ptrs[:3], _out_ptr(rec), *ptrs[3:]), where)
+        return PeelRunResult(image, big, power, rec, sources, count, next_first)
+
+    def peel_blocks(self, wire, rows: int, cols: int, steps: int, gain: float = 1.0, stop_ratio: float = 0.0, first: int = 0, every: int = 1,
+                    show: int = PEEL_MAP, out_rows: int = 0, out_cols: int = 0, d_colormap_ptr: int = 0, flip: bool = False,
+                    stride: int = DATAGRAM_BYTES, want_image: bool = True, want_power: bool = False, find: Optional[dict] = None) -> PeelRunResult:
+        """Watch a run of consecutive blocks of wire datagrams (as watch_blocks takes them) with every shown snapshot peeled
+        (awpu_hip_peel_blocks): the frame is its map row, or by `show` its clean or residual row.  `find` (a dict of find_peaks'
+        keywords, {} for the defaults) also finds the sources of every frame.  -> PeelRunResult."""
+        buf, n_blocks = _wire_blocks(wire, stride)
+        return self._peel_run(lambda *rest: self._lib.awpu_hip_peel_blocks(self._h, buf.ctypes.data_as(C.c_void_p), stride, *rest),
+                              "awpu_hip_peel_blocks", n_blocks, rows, cols, first, every, steps, gain, stop_ratio, show, out_rows, out_cols,
+                              d_colormap_ptr, flip, want_image, want_power, find)
+
+    def peel_samples(self, samples: np.ndarray, rows: int, cols: int, steps: int, gain: float = 1.0, stop_ratio: float = 0.0, first: int = 0,
+                     every: int = 1, show: int = PEEL_MAP, out_rows: int = 0, out_cols: int = 0, d_colormap_ptr: int = 0, flip: bool = False,
+                     want_image: bool = True, want_power: bool = False, find: Optional[dict] = None) -> PeelRunResult:
+        """The same from unpacked samples [n_streams, N] (N a multiple of 256, oldest first) (awpu_hip_peel_samples)."""
+        samples, n_blocks = self._sample_blocks(samples)
+        return self._peel_run(lambda *rest: self._lib.awpu_hip_peel_samples(self._h, _f32(samples), samples.shape[1], *rest),
+                              "awpu_hip_peel_samples", n_blocks, rows, cols, first, every, steps, gain, stop_ratio, show, out_rows, out_cols,
+                              d_colormap_ptr, flip, want_image, want_power, find)
+
+    def peel_samples_device(self, d_samples_ptr: int, pitch: int, n_blocks: int, rows: int, cols: int, steps: int, gain: float = 1.0,
+                            stop_ratio: float = 0.0, first: int = 0, every: int = 1, show: int = PEEL_MAP, d_image_ptr: int = 0, d_big_ptr: int = 0,
+                            d_power_ptr: int = 0, d_steps_ptr: int = 0, d_sources_ptr: int = 0, d_count_ptr: int = 0, out_rows: int = 0,
+                            out_cols: int = 0, d_colormap_ptr: int = 0, flip: bool = False, stream: int = 0, find: Optional[dict] = None) -> int:
+        """The same on device pointers (samples [n_streams, pitch]; image, big, power as watch_samples_device takes them, steps
+        [n_frames, steps] records of 12 bytes, sources and count as find_samples_device does, each or 0) on `stream`; asynchronous.
+        -> next_first (awpu_hip_peel_samples_device)."""
+        w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(d_colormap_ptr))
+        pe = Peel(steps, gain, stop_ratio)
+        f = _find_struct(rows, cols, find)
+        _check(self._lib.awpu_hip_peel_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, C.byref(w), C.byref(pe), show,
+                                                      None if f is None else C.byref(f), C.c_void_p(d_image_ptr), C.c_void_p(d_big_ptr),
+                                                      C.c_void_p(d_power_ptr), C.c_void_p(d_steps_ptr), C.c_void_p(d_sources_ptr),
+                                                      C.c_void_p(d_count_ptr), C.c_void_p(stream)), "awpu_hip_peel_samples_device")
+        return watch_count(n_blocks, first, every)[1]
 
     def _cohere_run(self, call, where, n_blocks, rows, cols, first, every, show, out_rows, out_cols, d_colormap_ptr, flip, want_image,
                     want_power, find) -> CohereResult:

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "awpu_hip.h"
+#include "awpu_hip_peel.h"
 #include "awpu_hip_spectral.h"
 #include "awpu_hip_track.h"
 
@@ -393,6 +394,14 @@ struct awpu_hip {
     // with the other tables), and the maps of a host-form call on their way back, one plane [batch][pixel_count] per map asked for
     Dev<awpu::LutEntry> d_cohere_lut;
     Dev<float> d_cohere_out;
+    // peeling (awpu_hip_peel.h; awpu_peel.cpp): the table's reach at the active mics, valid for the tables of peel_gen (table_gen;
+    // 0: none yet); the loop's residual frames [batch][n_streams][hist] where the caller keeps none, its power row P_k
+    // [batch][pixel_count], its bookkeeping (PeelState [batch]), and the results of a host-form call on their way back
+    int peel_min_off = 0, peel_max_off = 0;
+    unsigned long long peel_gen = 0;
+    Dev<float> d_peel_frames, d_peel_power;
+    Dev<unsigned char> d_peel_state, d_peel_out;
+    awpu::host::BufferPair peel_steps;  // peel runs (awpu_runs.cpp), host forms: piece i's steps in peel_steps.d[i & 1], back through pinned .h[i & 1]
 
     // the band (awpu_hip_band.h): its coefficients (empty = none; they travel to the pre-pass as kernel arguments), and the
     // filtered frames of a call whose own frames are the caller's or the ring's, in those frames' layout (band_sweep): a plane
@@ -488,6 +497,14 @@ struct CohereOut {
 };
 int ensure_cohere_table(awpu_hip *h);  // behind check_ready, before the call enqueues anything: the one step that may block
 int launch_cohere(awpu_hip *h, const float *d_frames, int batch, const CohereOut &out, hipStream_t s, int layout);
+// peeling (awpu_hip_peel.h): defined, and described, in awpu_peel.cpp; the runs of blocks (awpu_runs.cpp) peel their pieces through these
+struct PeelOut {  // what a loop writes, device memory, each or null: steps [batch][pe.steps]; clean, residual, map [batch][pixel_count]
+    awpu_peel_step_t *steps = nullptr;
+    float *clean = nullptr, *residual = nullptr, *map = nullptr;
+};
+int peel_handle_refusal(awpu_hip *h);    // the AWPU_ERR_STATE refusals that read the handle's configuration alone
+int peel_prepare(awpu_hip *h, int batch);  // behind check_ready, before anything is enqueued: all of a loop that may block
+int peel_enqueue(awpu_hip *h, float *work, int batch, const awpu_peel_t &pe, const PeelOut &out, hipStream_t s);
 bool takes_packed_pairs(awpu_hip *h, int batch, awpu::FastPlan *plan);
 int packed_shape(awpu_hip *h, int batch, awpu::FastPlan *plan);
 size_t packed_floats_of(const awpu_hip *h, const awpu::FastPlan &plan, int batch);

@@ -18,6 +18,7 @@
 
 #include "block_kernels.h"
 #include "cohere_rule.h"
+#include "peel_rule.h"
 #include "expose_kernels.h"
 #include "find_kernels.h"
 #include "find_rule.h"
@@ -129,6 +130,7 @@ struct Consumer {
     bool sweep = true;              // false: nothing is cut, swept or timed (listening without heatmaps)
     bool tail = false;              // a Piece::tail follows the last piece
     bool listens = false;           // steps 6, and 7 and 8 for what was heard
+    bool whole_frames = false;      // the snapshots are cut whole (kFull) even where the window could be cut out: the sweep reads outside it (PeelPieces)
     float *power = nullptr;         // [n_items][pixel_count], per band: host memory in the host forms, device memory in the device form; or null
     BandSet bands;                  // in front of the sweeps: the handle's own band unless check() has set a spectral run's
     int pitch = 0;                  // floats per stream of a history (set by ensure)
@@ -209,7 +211,7 @@ int run_pieces(awpu_hip *h, const BlockRun &src, hipStream_t user, Consumer &c) 
     }
     const int n_pieces = (int) pieces.size();  // ... with results
     if (c.tail) pieces.push_back({n_pieces, n_pieces & 1, 0, 0, true});
-    const bool compact = h->compact_hist > 0, host = !src.device;
+    const bool compact = h->compact_hist > 0 && !c.whole_frames, host = !src.device;
     const int S = cfg.n_streams;
     const size_t P = (size_t) cfg.pixel_count;
     hipStream_t sw = host ? h->stream : (user ? user : h->stream);
@@ -1105,9 +1107,92 @@ int cohere_run(awpu_hip *h, const BlockRun &src, int n_blocks, const awpu_watch_
     return run_pieces(h, src, user, c);
 }
 
+// ---- peel runs (awpu_hip_peel.h; the loop in awpu_peel.cpp) ------------------------------------------------------------------------
+// A watch run whose pieces are peeled (peel_enqueue) in place of swept: a piece's snapshots are cut whole -- the step reads E + 1
+// samples either side of the window -- into d_blk_frames, which the loop then turns into the residual, and the row a frame shows
+// -- and everything behind it -- is its map, clean or residual row.  The steps go to the caller's array (device form) or come back
+// with the piece's images through peel_steps (host forms).  Pieces, histories, the ring: the watch run's.
+struct PeelPieces final : WatchPieces {
+    const awpu_peel_t pe;
+    const int show_row;
+    awpu_peel_step_t *const steps;  // [n_frames][pe.steps], host or device memory as the run's other outputs, or null
+    int swept = 0, piece = 0;       // frames peeled so far, and pieces: sweep_frames sees the pieces in order, once each
+    PeelPieces(awpu_hip *h_, const BlockRun &src_, int n_blocks_, const WatchRun &wr_, const awpu_peel_t &pe_, int show_, awpu_peel_step_t *steps_)
+        : WatchPieces(h_, src_, n_blocks_, wr_), pe(pe_), show_row(show_), steps(steps_) {
+        whole_frames = true;
+    }
+    size_t step_bytes(int n) const { return (size_t) n * pe.steps * sizeof(awpu_peel_step_t); }
+    int check() override {
+        const int rc = peel_handle_refusal(h);
+        return rc != AWPU_OK ? rc : WatchPieces::check();
+    }
+    int ensure(int piece_max, int lo_, int width_, hipStream_t sw) override {  // (the handle is ready; none of the run's work is enqueued yet)
+        int rc = peel_prepare(h, piece_max);
+        if (rc == AWPU_OK && host && steps) rc = h->peel_steps.ensure(step_bytes(piece_max), true);
+        return rc != AWPU_OK ? rc : WatchPieces::ensure(piece_max, lo_, width_, sw);
+    }
+    int sweep_frames(awpu_hip *, const float *d_frames, int n, float *d_pow, hipStream_t s, int layout) override {
+        if (layout != kFull) return fail(AWPU_ERR_STATE, "a peel run cuts its snapshots whole");
+        PeelOut out;
+        (show_row == AWPU_PEEL_CLEAN ? out.clean : show_row == AWPU_PEEL_RESIDUAL ? out.residual : out.map) = d_pow;
+        if (steps) out.steps = host ? reinterpret_cast<awpu_peel_step_t *>(h->peel_steps.d[piece & 1].get()) : steps + (size_t) swept * pe.steps;
+        swept += n, piece++;
+        return peel_enqueue(h, const_cast<float *>(d_frames), n, pe, out, s);  // (d_blk_frames: the run's own scratch, cut anew for every piece)
+    }
+    int fetch_shown(const Piece &p, hipStream_t s) override {
+        if (steps) AWPU_HIP_TRY(hipMemcpyAsync(h->peel_steps.h[p.b], h->peel_steps.d[p.b], step_bytes(p.n), hipMemcpyDeviceToHost, s));
+        return WatchPieces::fetch_shown(p, s);
+    }
+    int deliver_shown(const Piece &p) override {
+        if (steps) std::memcpy(steps + (size_t) p.first * pe.steps, h->peel_steps.h[p.b], step_bytes(p.n));
+        return WatchPieces::deliver_shown(p);
+    }
+};
+
+// the checks of a peel run that read no handle; then the run
+int peel_run(awpu_hip *h, const BlockRun &src, int n_blocks, const awpu_watch_t *w, const awpu_peel_t *pe, int32_t show, const awpu_find_t *f,
+             uint8_t *image, uint8_t *big, float *power, awpu_peel_step_t *steps, awpu_source_t *sources, int32_t *count, hipStream_t user) {
+    WatchRun wr;
+    if (int rc = check_watch(w, image || big || power || steps || sources || count, big != nullptr, n_blocks, &wr)) return rc;
+    if (const char *why = awpu::peel_refusal(pe)) return invalid(why);
+    if (show != AWPU_PEEL_MAP && show != AWPU_PEEL_CLEAN && show != AWPU_PEEL_RESIDUAL) return invalid("show is AWPU_PEEL_MAP, AWPU_PEEL_CLEAN or AWPU_PEEL_RESIDUAL");
+    if (const int rc = check_find_request(w, f, sources, count)) return rc;
+    FindRun find;
+    if (f) find.f = *f, find.sources = sources, find.count = count;
+    wr.image = image, wr.big = big, wr.power = power;
+    wr.find = f ? &find : nullptr;
+    AWPU_CTX(h);
+    PeelPieces c(h, src, n_blocks, wr, *pe, show, steps);
+    return run_pieces(h, src, user, c);
+}
+
 }  // namespace
 
 extern "C" {
+
+int awpu_hip_peel_blocks(awpu_hip_t *h, const void *datagrams, int32_t stride_bytes, int32_t n_blocks, const awpu_watch_t *w,
+                         const awpu_peel_t *pe, int32_t show, const awpu_find_t *f, uint8_t *image, uint8_t *big_image, float *power,
+                         awpu_peel_step_t *steps, awpu_source_t *sources, int32_t *count) {
+    BlockRun src;
+    if (int rc = wire_source(h, datagrams, stride_bytes, n_blocks, &src)) return rc;
+    return peel_run(h, src, n_blocks, w, pe, show, f, image, big_image, power, steps, sources, count, nullptr);
+}
+
+int awpu_hip_peel_samples(awpu_hip_t *h, const float *samples, int64_t pitch, int32_t n_blocks, const awpu_watch_t *w,
+                          const awpu_peel_t *pe, int32_t show, const awpu_find_t *f, uint8_t *image, uint8_t *big_image, float *power,
+                          awpu_peel_step_t *steps, awpu_source_t *sources, int32_t *count) {
+    BlockRun src;
+    if (int rc = sample_source(h, samples, pitch, n_blocks, false, &src)) return rc;
+    return peel_run(h, src, n_blocks, w, pe, show, f, image, big_image, power, steps, sources, count, nullptr);
+}
+
+int awpu_hip_peel_samples_device(awpu_hip_t *h, const float *d_samples, int64_t pitch, int32_t n_blocks, const awpu_watch_t *w,
+                                 const awpu_peel_t *pe, int32_t show, const awpu_find_t *f, uint8_t *d_image, uint8_t *d_big_image,
+                                 float *d_power, awpu_peel_step_t *d_steps, awpu_source_t *d_sources, int32_t *d_count, void *stream) {
+    BlockRun src;
+    if (int rc = sample_source(h, d_samples, pitch, n_blocks, true, &src)) return rc;
+    return peel_run(h, src, n_blocks, w, pe, show, f, d_image, d_big_image, d_power, d_steps, d_sources, d_count, static_cast<hipStream_t>(stream));
+}
 
 int awpu_hip_process_blocks(awpu_hip_t *h, const void *datagrams, int32_t stride_bytes, int32_t n_blocks, float *power) {
     BlockRun src;

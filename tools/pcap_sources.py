@@ -22,6 +22,12 @@ carried from one --chunk call to the next, and the first block searched is then 
 weighted by the coherence factor -- a source's side lobes are then no sources --, or with `factor` the coherence factor itself; the
 `power` column is that row's value.  Off unless given; not with --exposure or --range.
 
+--peel STEPS[:GAIN] peels every searched block (Engine.peel_blocks, include/awpu_hip_peel.h): STEPS rounds of sweep, take the
+strongest pixel, subtract its beam from every mic, with loop gain GAIN (1 unless given).  A block's sources are then its steps
+merged per pixel -- the entries of its clean map, strongest first, `power` what the steps removed there, row and col the pixel's
+own --, which lists a weak source under a strong one's side lobes and not the side lobes.  Off unless given; not with --band,
+--exposure, --coherence or --range.
+
 Every block is ingested; every --every'th is swept and searched.  --chunk blocks go to the engine per call, each call continuing
 with the `next_first` of the one before, so a long capture streams through bounded memory.
 
@@ -84,6 +90,17 @@ def candidates_from_text(pkg, text: str) -> np.ndarray:
     return pkg.range_candidates(lo, hi, n)
 
 
+def peel_of_text(text: str):
+    """"STEPS[:GAIN]" (--peel) -> (steps, gain): steps in [1, 32], gain in (0, 1], 1 unless given."""
+    parts = text.split(":")
+    if len(parts) not in (1, 2):
+        raise ValueError("--peel takes STEPS[:GAIN]")
+    steps, gain = int(parts[0]), float(parts[1]) if len(parts) == 2 else 1.0
+    if not 1 <= steps <= 32 or not 0.0 < gain <= 1.0:
+        raise ValueError("--peel: STEPS in [1, 32], GAIN in (0, 1]")
+    return steps, gain
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("pcap")
@@ -108,8 +125,17 @@ def main(argv=None) -> int:
                     help="search heatmaps integrated over the L blocks that end with the searched one, 1 <= L <= --every (include/awpu_hip_expose.h)")
     ap.add_argument("--coherence", nargs="?", const="weighted", default=None, choices=("weighted", "factor"),
                     help="search the coherence-weighted power, or the coherence factor itself (include/awpu_hip_cohere.h)")
+    ap.add_argument("--peel", default=None, metavar="STEPS[:GAIN]",
+                    help="peel every searched block: its sources are the steps merged per pixel (include/awpu_hip_peel.h)")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
+    if a.peel and (a.exposure is not None or a.range_ or a.coherence or a.band):
+        ap.error("--peel together with --exposure, --range, --coherence or --band: those runs are not peeled")
+    if a.peel:
+        try:
+            peel = peel_of_text(a.peel)
+        except ValueError as e:
+            ap.error(str(e))
     if a.every < 1 or a.chunk < 1:
         ap.error("--every and --chunk are positive")
     if a.coherence and (a.exposure is not None or a.range_):
@@ -164,6 +190,9 @@ def main(argv=None) -> int:
                 what = {k: v for k, v in find.items() if k not in ("first", "every")}
                 res = eng.expose_blocks(chunk, a.cols, a.cols, a.exposure, first=first, every=a.every, carry=carry, want_image=False, find=what)
                 carry = res.carry
+            elif a.peel:
+                res = eng.peel_blocks(chunk, a.cols, a.cols, peel[0], peel[1], first=first, every=a.every, want_image=False)
+                res.sources, res.count = pkg.binding.peel_source_records(res.steps, a.cols, a.cols, a.max_sources, a.fov)
             elif a.coherence:
                 what = {k: v for k, v in find.items() if k not in ("first", "every")}
                 show = pkg.binding.COHERE_FACTOR if a.coherence == "factor" else pkg.binding.COHERE_WEIGHTED

@@ -27,6 +27,11 @@ unless given; not with --bands.
 delay-and-sum power weighted by the coherence factor, which takes the side lobes of a source out of the picture, or with `factor`
 the coherence factor itself.  Off unless given; not with --bands or --exposure.
 
+--peel STEPS[:GAIN] shows every frame peeled (Engine.peel_blocks, include/awpu_hip_peel.h): STEPS rounds of sweep, take the
+strongest pixel, subtract its beam from every mic, with loop gain GAIN (1 unless given); the frame is the clean map -- the removed
+powers at their pixels -- plus the residual, so a source's side lobes go with the source.  Off unless given; not with --band,
+--bands, --exposure or --coherence.
+
 Every block is ingested; every --every'th is swept and shown.  The default 3 gives 48828 / (256 * 3) = 63.6 frames per second, the
 nearest to the 60 the reference opens its writer with.  --chunk blocks go to the engine per call, each call continuing with the
 `next_first` of the one before, so a long capture streams through bounded memory.
@@ -188,6 +193,17 @@ def bands_of_text(binding, text: str):
     return bands, tuple(2 - c if 2 - c < len(bands) else -1 for c in range(3))  # red (byte 2) = band 0, green = band 1, blue = band 2
 
 
+def peel_of_text(text: str):
+    """"STEPS[:GAIN]" (--peel) -> (steps, gain): steps in [1, 32], gain in (0, 1], 1 unless given."""
+    parts = text.split(":")
+    if len(parts) not in (1, 2):
+        raise ValueError("--peel takes STEPS[:GAIN]")
+    steps, gain = int(parts[0]), float(parts[1]) if len(parts) == 2 else 1.0
+    if not 1 <= steps <= 32 or not 0.0 < gain <= 1.0:
+        raise ValueError("--peel: STEPS in [1, 32], GAIN in (0, 1]")
+    return steps, gain
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("pcap")
@@ -214,8 +230,17 @@ def main(argv=None) -> int:
     ap.add_argument("--peak-hold", action="store_true", help="--exposure: the per-pixel maximum of the L blocks instead of their mean")
     ap.add_argument("--coherence", nargs="?", const="weighted", default=None, choices=("weighted", "factor"),
                     help="show the coherence-weighted power, or the coherence factor itself (include/awpu_hip_cohere.h)")
+    ap.add_argument("--peel", default=None, metavar="STEPS[:GAIN]",
+                    help="show every frame peeled: the clean map plus the residual after STEPS steps (include/awpu_hip_peel.h)")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
+    if a.peel and (a.bands or a.band or a.exposure is not None or a.coherence):
+        ap.error("--peel together with --band, --bands, --exposure or --coherence: those runs are not peeled")
+    if a.peel:
+        try:
+            peel = peel_of_text(a.peel)
+        except ValueError as e:
+            ap.error(str(e))
     if a.every < 1 or a.chunk < 1 or a.size < a.cols:
         ap.error("--every and --chunk are positive, --size is at least --cols")
     if a.exposure is not None and not 1 <= a.exposure <= a.every:
@@ -280,6 +305,9 @@ def main(argv=None) -> int:
                                         mode=mode, carry=carry, out_rows=a.size, out_cols=a.size, d_colormap_ptr=table.data_ptr(), flip=a.flip,
                                         want_image=False)
                 carry = res.carry
+            elif a.peel:
+                res = eng.peel_blocks(wire[b * block_bytes: (b + nb) * block_bytes], a.cols, a.cols, peel[0], peel[1], first=first, every=a.every,
+                                      out_rows=a.size, out_cols=a.size, d_colormap_ptr=table.data_ptr(), flip=a.flip, want_image=False)
             elif a.coherence:
                 show = pkg.binding.COHERE_FACTOR if a.coherence == "factor" else pkg.binding.COHERE_WEIGHTED
                 res = eng.cohere_blocks(wire[b * block_bytes: (b + nb) * block_bytes], a.cols, a.cols, first=first, every=a.every, show=show,
