@@ -28,8 +28,7 @@ int cohere_device(awpu_hip *h, const float *d_frames, int batch, const CohereOut
     if (rc == AWPU_OK) rc = ensure_cohere_table(h);
     if (rc == AWPU_OK) rc = enter_stream(h, s);
     if (rc != AWPU_OK) return rc;
-    TimingOff untimed(h);  // asynchronous path: the caller times its own stream
-    return band_sweep(h, own_band(h), d_frames, (long long) h->cfg.n_streams * h->cfg.hist, h->cfg.hist, h->wstart, batch, nullptr, 0, s, kFull, &out);
+    return band_sweep(h, own_band(h), d_frames, (long long) h->cfg.n_streams * h->cfg.hist, h->cfg.hist, h->wstart, batch, nullptr, 0, s, kFull, {}, &out);
 }
 
 }  // namespace
@@ -68,11 +67,11 @@ int awpu_hip_cohere(awpu_hip_t *h, const float *frames, int32_t batch, float *po
     CohereOut out;
     out.power = d_out[0], out.coherence = d_out[1], out.weighted = d_out[2];
     rc = band_sweep(h, bands, h->d_frames, (long long) S * dev_hist, dev_hist, compact ? pre : h->wstart, batch, nullptr, 0, h->stream,
-                    compact ? kCompact : kFull, &out);
+                    compact ? kCompact : kFull, kTimed, &out);
     if (rc != AWPU_OK) return rc;
     for (int k = 0; k < 3; k++)
         if (host_out[k]) AWPU_HIP_TRY(hipMemcpyAsync(host_out[k], d_out[k], plane * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    return wait_and_time(h);
+    return wait_and_time(h, true);
 }
 
 int awpu_hip_cohere_device(awpu_hip_t *h, const float *d_frames, int32_t batch, float *d_power, float *d_coherence, float *d_weighted,

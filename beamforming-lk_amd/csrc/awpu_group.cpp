@@ -223,7 +223,7 @@ int group_process_async(awpu_hip *g, const float *frames, int batch, float *powe
 }
 
 int group_wait(awpu_hip *g) {
-    return for_each_part(g, [&](awpu_hip *part) { return wait_and_time(part); });
+    return for_each_part(g, [&](awpu_hip *part) { return wait_and_time(part, true); });
 }
 
 int group_ingest_block(awpu_hip *g, const void *datagrams, int32_t stride_bytes) {  // every device keeps the whole ring (264 KB per block each, over its own PCIe link)
@@ -248,7 +248,7 @@ int group_process_ring(awpu_hip *g, float *power) {  // every device sweeps its 
         if (r != AWPU_OK) return r;
         if (!part->d_ring) return fail(AWPU_ERR_STATE, "no block ingested yet");
         r = ensure_power(part, (size_t) part->cfg.pixel_count);
-        if (r == AWPU_OK) r = launch(part, part->d_ring + part->ring_pos, 1, part->d_power, part->stream, kRing);
+        if (r == AWPU_OK) r = launch(part, part->d_ring + part->ring_pos, 1, part->d_power, part->stream, kRing, kTimed);  // (a bracket nobody reads: awpu_hip_process_ring)
         return r != AWPU_OK ? r : enqueue_power_to_host(part, 1, power, (size_t) g->cfg.pixel_count);
     });
     return rc != AWPU_OK ? rc : group_wait(g);
@@ -467,7 +467,6 @@ int fan_sweep(const Fan &f, awpu_hip *part) {
     AWPU_HIP_TRY(hipSetDevice(part->cfg.device));
     int r = ensure_power(part, (size_t) part->cfg.pixel_count * f.batch);
     if (r != AWPU_OK) return r;
-    TimingOff untimed(part);  // asynchronous path: the caller times its own stream
     if (in_place(g, part)) {
         AWPU_HIP_TRY(hipStreamWaitEvent(part->stream, grp.ev_fan, 0));
         if (packed) {

@@ -1,6 +1,7 @@
 // awpu_handle.h -- internal to libawpu_hip.so: the handle, the owner types of what it holds on the device, the error helpers, and
-// what its four host files call in one another: awpu_hip.cpp (the C ABI and its call paths), awpu_group.cpp (the device group),
-// awpu_sweep.cpp (tables, launchers, dispatch) and awpu_runs.cpp (the runs of blocks).  Nothing here is part of the C ABI.
+// what its seven host files call in one another: awpu_hip.cpp (the C ABI and its call paths), awpu_group.cpp (the device group),
+// awpu_sweep.cpp (tables, launchers, dispatch), awpu_runs.cpp (the runs of blocks), awpu_cohere.cpp (coherence calls), awpu_peel.cpp
+// (the peeling loop) and awpu_focus.cpp (candidate distances).  Nothing here is part of the C ABI.
 #pragma once
 
 #include "awpu_hip.h"
@@ -246,8 +247,7 @@ struct awpu_hip {
 
     awpu_hip_cfg cfg{};
     Stream stream;
-    Event ev_begin, ev_end;  // the only two events that carry timing
-    bool timing = true;
+    Event ev_begin, ev_end;  // the only two events that carry timing: recorded where a call asks for it (SweepOpts::timed)
 
     // host copies of what the reference keeps in MIMOWorker / Antenna
     std::vector<int32_t> off;   // [pixel_count][lut_stride]  offsetDelays
@@ -279,7 +279,6 @@ struct awpu_hip {
     bool exact_ndh_ok = false, exact_ndhs_ok = false, fast_ndp_ok = false;
     bool identity_mics = false;   // the active-mic list is 0 .. usable-1 (awpu_hip_set_active_mics(NULL)): rows need no look-up
     bool exact_pairs_ok = false;  // AWPU_MATH_F32_EXACT + LERP and the window fits the pair image
-    float *sums_out = nullptr;    // awpu_hip_process_device_sums: where the launch in progress exports out[] (else null)
     Dev<uint32_t> d_fir_plane_lut;             // FIR8 on the four-plane layout: one dword per (pixel, mic): address, plane, coefficient row
     awpu::FastPlan fir_plane_plan{};
     bool fir_planes_ok = false;                // AWPU_MATH_F32_FAST + FIR8 and the window fits the plane image
@@ -334,12 +333,12 @@ struct awpu_hip {
     Pinned<float> h_live_in, h_live_out;                // pinned staging of awpu_hip_process's one-frame calls (the live path): window in, powers out
     unsigned live_calls = 0;                            // ... how many of them this handle has served (every 32nd is timed by events)
     // ... their completion flag (the resident single-frame kernels with one quad per wave): the device counter the workgroups count themselves on, what it will read
-    // when every launch armed so far is over, the pinned flag and the sequence number of the last armed launch
+    // when every launch armed so far is over, the pinned flag and the sequence number of the last armed launch.  (Whether a launch
+    // is armed is the call's: SweepOpts::flag)
     Dev<unsigned long long> d_done_counter;
     unsigned long long done_total = 0;
     Pinned<unsigned> h_done_flag;
     unsigned done_seq = 0;
-    bool done_arm = false, done_used = false;           // arm: the next single-frame sweep is to raise the flag; used: it will
     Dev<float> d_power;
     int wstart = 0, window = 0, tau_max = 0;
     int pair_cols = 0;  // frame-pair sweep: > 0 = waves take vertically adjacent pixels (grid row length), 0 = consecutive
@@ -486,17 +485,38 @@ inline BandSet own_band(const awpu_hip *h) {
 // sample 0 = history sample wstart; kRing one frame read in place from the ingest ring (rows 2048 apart)
 enum FrameLayout { kFull = 0, kCompact = 1, kRing = 2 };
 
+// What a sweep is asked besides its frames: arguments of the call in progress, handed down from the ABI function that starts it and
+// never kept in the handle.  The default is every asynchronous path's: the caller times its own stream ("Who records the
+// event bracket").
+struct SweepOpts {
+    bool timed = false;     // record ev_begin in front of the launch's first kernel, ev_end behind its last
+    float *sums = nullptr;  // awpu_hip_process_device_sums: where out[] goes
+    bool *flag = nullptr;   // live_host_call: non-null = raise the completion flag where the kernel can; *flag = it will
+};
+inline constexpr SweepOpts kTimed{true};
+// One sweep as its launcher sees it (awpu_sweep.cpp): built once in launch() and once in sweep_packed()
+struct SweepCall {
+    const float *frames;       // in `layout`; null: the caller's packed pairs
+    int batch;
+    float *power;
+    hipStream_t stream;
+    int layout;                // FrameLayout
+    int hist_eff, wstart_eff;  // floats between two streams of a frame, and where the window starts in such a row
+    SweepOpts opts;
+    int hist_ring() const { return layout == kRing ? AWPU_HIST : hist_eff; }  // the history a stream offers a filter (the ring's rows are 2048 floats apart)
+};
+
 // the sweep layer: defined, and described, in awpu_sweep.cpp
 int prepare(awpu_hip *h);
 void free_tables(awpu_hip *h);
-int launch(awpu_hip *h, const float *d_frames, int batch, float *d_power, hipStream_t s, int layout = kFull);
+int launch(awpu_hip *h, const float *d_frames, int batch, float *d_power, hipStream_t s, int layout = kFull, const SweepOpts &o = {});
 // what a coherence sweep (awpu_hip_cohere.h) writes, device memory, each or null: the three maps [batch][pixel_count], out[] and
 // e[] of every pixel [batch][pixel_count][256]
 struct CohereOut {
     float *power = nullptr, *coherence = nullptr, *weighted = nullptr, *sums = nullptr, *energy = nullptr;
 };
 int ensure_cohere_table(awpu_hip *h);  // behind check_ready, before the call enqueues anything: the one step that may block
-int launch_cohere(awpu_hip *h, const float *d_frames, int batch, const CohereOut &out, hipStream_t s, int layout);
+int launch_cohere(awpu_hip *h, const float *d_frames, int batch, const CohereOut &out, hipStream_t s, int layout, bool timed = false);
 // peeling (awpu_hip_peel.h): defined, and described, in awpu_peel.cpp; the runs of blocks (awpu_runs.cpp) peel their pieces through these
 struct PeelOut {  // what a loop writes, device memory, each or null: steps [batch][pe.steps]; clean, residual, map [batch][pixel_count]
     awpu_peel_step_t *steps = nullptr;
@@ -504,12 +524,12 @@ struct PeelOut {  // what a loop writes, device memory, each or null: steps [bat
 };
 int peel_handle_refusal(awpu_hip *h);    // the AWPU_ERR_STATE refusals that read the handle's configuration alone
 int peel_prepare(awpu_hip *h, int batch);  // behind check_ready, before anything is enqueued: all of a loop that may block
-int peel_enqueue(awpu_hip *h, float *work, int batch, const awpu_peel_t &pe, const PeelOut &out, hipStream_t s);
+int peel_enqueue(awpu_hip *h, float *work, int batch, const awpu_peel_t &pe, const PeelOut &out, hipStream_t s);  // (untimed: several sweeps)
 bool takes_packed_pairs(awpu_hip *h, int batch, awpu::FastPlan *plan);
 int packed_shape(awpu_hip *h, int batch, awpu::FastPlan *plan);
 size_t packed_floats_of(const awpu_hip *h, const awpu::FastPlan &plan, int batch);
 int pack_for_sweep(awpu_hip *h, const awpu::FastPlan &plan, const float *d_frames, int batch, float *d_packed, hipStream_t s);
-int sweep_packed(awpu_hip *h, const awpu::FastPlan &plan, const float *d_packed, size_t packed_floats, int batch, float *d_power, hipStream_t s);
+int sweep_packed(awpu_hip *h, const awpu::FastPlan &plan, const float *d_packed, size_t packed_floats, int batch, float *d_power, hipStream_t s);  // (untimed)
 
 // defined, and described, in awpu_hip.cpp
 void retire_live_graphs(awpu_hip *h);
@@ -523,7 +543,7 @@ extern const char *const kBandHistory;  // what AWPU_ERR_RANGE says where the ba
 int ensure_power(awpu_hip *h, size_t need_power);
 int ensure_ring(awpu_hip *h);
 int host_piece(int batch);
-int wait_and_time(awpu_hip *h);
+int wait_and_time(awpu_hip *h, bool timed);
 size_t align16(size_t n);
 int check_particles(const awpu_particle_t *p, int32_t n, double theta_limit, double reference);
 int check_antenna(const awpu_hip *h);
@@ -533,9 +553,10 @@ int ensure_taps(awpu_hip *h, int rows, int cols, int out_rows, int out_cols, hip
 int band_cut(awpu_hip *h, const BandSet &bands, const float *in, long long in_frame, long long in_row, int in_lo, int batch, float *out,
              long long out_plane, int layout, hipStream_t s);
 int band_sweep(awpu_hip *h, const BandSet &bands, const float *in, long long in_frame, long long in_row, int in_lo, int batch, float *d_power,
-               long long power_plane, hipStream_t s, int layout, const CohereOut *cohere = nullptr);
-inline int band_sweep(awpu_hip *h, const float *in, long long in_frame, long long in_row, int in_lo, int batch, float *d_power, hipStream_t s, int layout) {
-    return band_sweep(h, own_band(h), in, in_frame, in_row, in_lo, batch, d_power, 0, s, layout);  // the handle's own band: the one-band case
+               long long power_plane, hipStream_t s, int layout, const SweepOpts &o = {}, const CohereOut *cohere = nullptr);
+inline int band_sweep(awpu_hip *h, const float *in, long long in_frame, long long in_row, int in_lo, int batch, float *d_power, hipStream_t s, int layout,
+                      const SweepOpts &o = {}) {
+    return band_sweep(h, own_band(h), in, in_frame, in_row, in_lo, batch, d_power, 0, s, layout, o);  // the handle's own band: the one-band case
 }
 int check_spectral(awpu_hip *h, const awpu_spectral_t *sp, BandSet *bands);  // a spectral call's bands, or why the handle does not take them
 
@@ -547,14 +568,6 @@ int ensure_seen_by_live_graphs(awpu_hip *h, B &buf, size_t n) {
     retire_live_graphs(h);
     return buf.grow(n);
 }
-
-// switches a handle's event bracket off for one asynchronous call and back on whichever way the call ends
-struct TimingOff {
-    awpu_hip *h;
-    bool keep;
-    explicit TimingOff(awpu_hip *h_) : h(h_), keep(h_->timing) { h->timing = false; }
-    ~TimingOff() { h->timing = keep; }
-};
 
 // the device group: defined, and described, in awpu_group.cpp.  The ABI functions hand a group's handle over to these
 inline bool is_group(const awpu_hip *h) { return !h->group.parts.empty(); }

@@ -168,7 +168,7 @@ int host_piece(int batch) {
     return ((batch + n_pieces - 1) / n_pieces + 1) & ~1;
 }
 
-// upload of host frames + the sweep into h->d_power, all on h->stream, nothing waited for
+// upload of host frames + the sweep into h->d_power, all on h->stream, nothing waited for.  Timed: every caller ends in wait_and_time
 int enqueue_host_process(awpu_hip *h, const float *frames, int batch, const BandSet *given) {
     int rc = check_ready(h, batch);
     if (rc == AWPU_OK) rc = enter_stream(h, h->stream);
@@ -192,7 +192,6 @@ int enqueue_host_process(awpu_hip *h, const float *frames, int batch, const Band
             if (rc == AWPU_OK) rc = ev.ensure();
         if (rc != AWPU_OK) return rc;
     }
-    const bool keep_timing = h->timing;
     int turn = 0;
     for (int b0 = 0; b0 < batch; b0 += piece, turn++) {
         const int nb = std::min(piece, batch - b0);
@@ -208,15 +207,14 @@ int enqueue_host_process(awpu_hip *h, const float *frames, int batch, const Band
         if (n_pieces > 1) {
             AWPU_HIP_TRY(hipEventRecord(h->ev_copied[turn & 1], up));
             AWPU_HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_copied[turn & 1], 0));
-            if (keep_timing && b0 == 0) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, h->stream));
-            h->timing = false;
+            if (b0 == 0) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, h->stream));  // several pieces: the bracket spans them all, recorded here
         }
         rc = band_sweep(h, bands, dst, (long long) h->cfg.n_streams * dev_hist, dev_hist, compact ? pre : h->wstart, nb,
-                        h->d_power + (size_t) b0 * h->cfg.pixel_count, (long long) batch * h->cfg.pixel_count, h->stream, compact ? kCompact : kFull);
-        h->timing = keep_timing;
+                        h->d_power + (size_t) b0 * h->cfg.pixel_count, (long long) batch * h->cfg.pixel_count, h->stream, compact ? kCompact : kFull,
+                        n_pieces > 1 ? SweepOpts{} : kTimed);
         if (rc != AWPU_OK) return rc;
     }
-    if (n_pieces > 1 && keep_timing) AWPU_HIP_TRY(hipEventRecord(h->ev_end, h->stream));
+    if (n_pieces > 1) AWPU_HIP_TRY(hipEventRecord(h->ev_end, h->stream));
     return AWPU_OK;
 }
 
@@ -293,14 +291,15 @@ int band_cut(awpu_hip *h, const BandSet &bands, const float *in, long long in_fr
 // launch() on frames of the caller's or the ring's (kFull, kRing), or on windows uploaded with the bands' history in front of them
 // (kCompact: rows of max taps - 1 + compact_hist floats), through the bands where there are any: the pre-pass into d_band in
 // `layout`, a plane per band, then for every band the launch() a band-less handle makes for the same call -- the same layout and
-// batch, so the same kernel -- into d_power + b * power_plane.  The handle's event bracket spans all of it.  With `cohere` the
-// sweep behind the pre-pass is the coherence sweep (awpu_hip_cohere.h: at most one band, d_power unused)
+// batch, so the same kernel -- into d_power + b * power_plane.  A timed call's event bracket spans all of it: recorded here, the
+// sweeps behind the pre-pass untimed.  With `cohere` the sweep behind the pre-pass is the coherence sweep (awpu_hip_cohere.h: at
+// most one band, d_power unused)
 int band_sweep(awpu_hip *h, const BandSet &bands, const float *in, long long in_frame, long long in_row, int in_lo, int batch, float *d_power,
-               long long power_plane, hipStream_t s, int layout, const CohereOut *cohere) {
-    const auto sweep = [&](const float *frames, float *power) {
-        return cohere ? launch_cohere(h, frames, batch, *cohere, s, layout) : launch(h, frames, batch, power, s, layout);
+               long long power_plane, hipStream_t s, int layout, const SweepOpts &o, const CohereOut *cohere) {
+    const auto sweep = [&](const float *frames, float *power, const SweepOpts &so) {
+        return cohere ? launch_cohere(h, frames, batch, *cohere, s, layout, so.timed) : launch(h, frames, batch, power, s, layout, so);
     };
-    if (bands.n == 0) return sweep(in, d_power);
+    if (bands.n == 0) return sweep(in, d_power, o);
     const size_t S = (size_t) h->cfg.n_streams;
     const size_t plane = layout == kRing ? S * 2048 : S * (size_t) (layout == kCompact ? h->compact_hist : h->cfg.hist) * batch;
     const size_t need = plane * bands.n;
@@ -308,14 +307,11 @@ int band_sweep(awpu_hip *h, const BandSet &bands, const float *in, long long in_
         if (const int rc = h->d_band.grow(need); rc != AWPU_OK) return rc;
         AWPU_HIP_TRY(hipMemsetAsync(h->d_band, 0, need * sizeof(float), s));
     }
-    const bool timed = h->timing;
-    if (timed) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
+    if (o.timed) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
     int rc = band_cut(h, bands, in, in_frame, in_row, in_lo, batch, h->d_band, (long long) plane, layout, s);
-    if (rc != AWPU_OK) return rc;
-    h->timing = false;
-    for (int b = 0; b < bands.n && rc == AWPU_OK; b++) rc = sweep(h->d_band + b * plane, d_power + b * power_plane);
-    h->timing = timed;
-    if (rc == AWPU_OK && timed) AWPU_HIP_TRY(hipEventRecord(h->ev_end, s));
+    const SweepOpts untimed{false, o.sums, o.flag};
+    for (int b = 0; b < bands.n && rc == AWPU_OK; b++) rc = sweep(h->d_band + b * plane, d_power + b * power_plane, untimed);
+    if (rc == AWPU_OK && o.timed) AWPU_HIP_TRY(hipEventRecord(h->ev_end, s));
     return rc;
 }
 
@@ -399,17 +395,14 @@ int live_host_call(awpu_hip *h, const float *frames, float *power) {
     // calls leave last_kernel_ms / total_kernel_ms as they are
     {
         const bool timed = (h->live_calls++ & 31) == 0;
-        const bool keep = h->timing;
-        h->timing = keep && timed;
-        h->done_arm = !h->timing;  // (a timed call waits for the stream: its end event)
-        rc = launch(h, h->d_frames, 1, h->h_live_out, h->stream, compact ? kCompact : kFull);
-        h->done_arm = false;
+        bool flagged = false;  // this call's sweep will raise the completion flag (a timed call waits for the stream: its end event)
+        rc = launch(h, h->d_frames, 1, h->h_live_out, h->stream, compact ? kCompact : kFull, {timed, nullptr, timed ? nullptr : &flagged});
         if (rc == AWPU_OK) {
 #ifdef AWPU_TUNING_BUILD
             if (live_timing) lap(2, t);
 #endif
             bool seen = false;
-            if (h->done_used) {
+            if (flagged) {
                 // the sweep's last workgroup stores the call's number behind its powers (das_fast.hip: store_tile_and_signal): ~7 us
                 // sooner than the stream's completion signal.  Should it not arrive within 20 ms (it arrives within the sweep's ~25 us),
                 // the stream's own completion decides
@@ -423,9 +416,8 @@ int live_host_call(awpu_hip *h, const float *frames, float *power) {
                     if ((spins & 0xfff) == 0xfff && std::chrono::steady_clock::now() - spin_from > std::chrono::milliseconds(20)) break;
                 }
             }
-            if (!seen) rc = wait_and_time(h);
+            if (!seen) rc = wait_and_time(h, timed);
         }
-        h->timing = keep;
     }
     if (rc != AWPU_OK) return rc;
 #ifdef AWPU_TUNING_BUILD
@@ -448,10 +440,10 @@ int live_host_call(awpu_hip *h, const float *frames, float *power) {
 
 }  // namespace
 
-int awpu::host::wait_and_time(awpu_hip *h) {
+int awpu::host::wait_and_time(awpu_hip *h, bool timed) {
     AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
     AWPU_HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->timing) {
+    if (timed) {
         float ms = 0.0f;
         if (hipEventElapsedTime(&ms, h->ev_begin, h->ev_end) == hipSuccess) {
             h->stats.last_kernel_ms = ms;
@@ -979,7 +971,7 @@ int awpu_hip_process(awpu_hip_t *h, const float *frames, int32_t batch, float *p
     if (rc != AWPU_OK) return rc;
     rc = enqueue_power_to_host(h, batch, power, (size_t) h->cfg.pixel_count);
     if (rc != AWPU_OK) return rc;
-    return wait_and_time(h);
+    return wait_and_time(h, true);
 }
 
 int awpu_hip_process_async(awpu_hip_t *h, const float *frames, int32_t batch, float *power) {
@@ -1003,7 +995,7 @@ int awpu_hip_wait(awpu_hip_t *h) {
     if (!h) return invalid("null handle");
     if (!h->in_flight) return AWPU_OK;  // nothing to wait for
     h->in_flight = false;
-    return is_group(h) ? group_wait(h) : wait_and_time(h);
+    return is_group(h) ? group_wait(h) : wait_and_time(h, true);
 }
 
 int awpu_hip_process_device(awpu_hip_t *h, const float *d_frames, int32_t batch, float *d_power,
@@ -1016,7 +1008,6 @@ int awpu_hip_process_device(awpu_hip_t *h, const float *d_frames, int32_t batch,
     hipStream_t s = stream_of(h, stream);
     if (rc == AWPU_OK) rc = enter_stream(h, s);
     if (rc != AWPU_OK) return rc;
-    TimingOff untimed(h);  // asynchronous path: the caller times its own stream
     return band_sweep(h, d_frames, (long long) h->cfg.n_streams * h->cfg.hist, h->cfg.hist, h->wstart, batch, d_power, s, kFull);
 }
 
@@ -1031,7 +1022,7 @@ int awpu_hip_process_bands(awpu_hip_t *h, const float *frames, int32_t batch, co
     if (rc != AWPU_OK) return rc;
     rc = enqueue_power_to_host(h, batch * bands.n, power, (size_t) h->cfg.pixel_count);
     if (rc != AWPU_OK) return rc;
-    return wait_and_time(h);
+    return wait_and_time(h, true);
 }
 
 int awpu_hip_process_bands_device(awpu_hip_t *h, const float *d_frames, int32_t batch, const awpu_spectral_t *sp, float *d_power, void *stream) {
@@ -1046,7 +1037,6 @@ int awpu_hip_process_bands_device(awpu_hip_t *h, const float *d_frames, int32_t 
     if (bands.max_taps() - 1 > h->wstart) return fail(AWPU_ERR_RANGE, kBandHistory);
     hipStream_t s = stream_of(h, stream);
     if (rc = enter_stream(h, s); rc != AWPU_OK) return rc;
-    TimingOff untimed(h);  // asynchronous path: the caller times its own stream
     return band_sweep(h, bands, d_frames, (long long) h->cfg.n_streams * h->cfg.hist, h->cfg.hist, h->wstart, batch, d_power,
                       (long long) batch * h->cfg.pixel_count, s, kFull);
 }
@@ -1062,11 +1052,7 @@ int awpu_hip_process_device_sums(awpu_hip_t *h, const float *d_frames, int32_t b
     if (!h->exact_pairs_ok && !exact_fir8) return fail(AWPU_ERR_STATE, "the pre-epilogue sums need AWPU_MATH_F32_EXACT");
     hipStream_t s = stream_of(h, stream);
     if (const int erc = enter_stream(h, s); erc != AWPU_OK) return erc;
-    TimingOff untimed(h);
-    h->sums_out = d_sums;
-    const int lrc = band_sweep(h, d_frames, (long long) h->cfg.n_streams * h->cfg.hist, h->cfg.hist, h->wstart, batch, d_power, s, kFull);
-    h->sums_out = nullptr;
-    return lrc;
+    return band_sweep(h, d_frames, (long long) h->cfg.n_streams * h->cfg.hist, h->cfg.hist, h->wstart, batch, d_power, s, kFull, {false, d_sums});
 }
 
 int awpu_hip_ingest_block(awpu_hip_t *h, const void *datagrams, int32_t stride_bytes) {
@@ -1081,15 +1067,16 @@ int awpu_hip_ingest_block(awpu_hip_t *h, const void *datagrams, int32_t stride_b
 
 namespace {
 
-// the steps of one live block on h->stream, without the final wait
+// the steps of one live block on h->stream, without the final wait; `timed`: not inside a graph capture (event records there would
+// not bracket anything)
 int enqueue_live_block(awpu_hip *h, const void *datagrams, int32_t stride_bytes, float *power, int32_t rows, int32_t cols,
-                       uint8_t *image, int32_t out_rows, int32_t out_cols, const uint8_t *d_colormap, uint8_t *big_image) {
+                       uint8_t *image, int32_t out_rows, int32_t out_cols, const uint8_t *d_colormap, uint8_t *big_image, bool timed) {
     const int n = h->cfg.n_pixels;
     int rc = enqueue_ingest(h, datagrams, stride_bytes);
     if (rc != AWPU_OK) return rc;
     rc = ensure_power(h, (size_t) n);
     if (rc != AWPU_OK) return rc;
-    rc = launch(h, h->d_ring + h->ring_pos, 1, h->d_power, h->stream, kRing);
+    rc = launch(h, h->d_ring + h->ring_pos, 1, h->d_power, h->stream, kRing, {timed});
     if (rc != AWPU_OK) return rc;
     if (power) AWPU_HIP_TRY(hipMemcpyAsync(power, h->d_power, (size_t) n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     if (image || big_image) {
@@ -1169,19 +1156,16 @@ int awpu_hip_live_block(awpu_hip_t *h, const void *datagrams, int32_t stride_byt
         }
         {   // capture this variant (the stream is idle: every call ends with a wait)
             AWPU_HIP_TRY(hipSetDevice(h->cfg.device));
-            const bool keep_timing = h->timing;
             const int keep_pos = h->ring_pos;
             const auto keep_stats = h->stats;
-            h->timing = false;  // (event records inside a graph would not bracket anything)
             hipGraph_t graph = nullptr;
             hipError_t e = hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal);
             if (e == hipSuccess) {
-                rc = enqueue_live_block(h, datagrams, stride_bytes, power, rows, cols, image, out_rows, out_cols, d_colormap, big_image);
+                rc = enqueue_live_block(h, datagrams, stride_bytes, power, rows, cols, image, out_rows, out_cols, d_colormap, big_image, false);
                 e = hipStreamEndCapture(h->stream, &graph);  // (also on failure: it takes the stream out of capture mode)
             } else {
                 rc = AWPU_ERR_HIP;
             }
-            h->timing = keep_timing;
             h->ring_pos = keep_pos;  // nothing ran yet
             h->stats = keep_stats;
             hipGraphExec_t exec = nullptr;
@@ -1203,7 +1187,8 @@ int awpu_hip_live_block(awpu_hip_t *h, const void *datagrams, int32_t stride_byt
             if (!h->live_graph_broken) return awpu_hip_live_block(h, datagrams, stride_bytes, power, rows, cols, image, out_rows, out_cols, d_colormap, big_image);
         }
     }
-    rc = enqueue_live_block(h, datagrams, stride_bytes, power, rows, cols, image, out_rows, out_cols, d_colormap, big_image);
+    // (the plain path records a bracket that nobody reads, as it always has: whether this call should be timed is a separate question)
+    rc = enqueue_live_block(h, datagrams, stride_bytes, power, rows, cols, image, out_rows, out_cols, d_colormap, big_image, true);
     if (rc != AWPU_OK) return rc;
     AWPU_HIP_TRY(hipStreamSynchronize(h->stream));
     h->live_warm++;
@@ -1224,7 +1209,7 @@ int awpu_hip_process_ring(awpu_hip_t *h, float *power) {
     const size_t need_power = (size_t) h->cfg.pixel_count;
     rc = ensure_power(h, need_power);
     if (rc != AWPU_OK) return rc;
-    rc = band_sweep(h, h->d_ring + h->ring_pos, 0, 2048, h->wstart, 1, h->d_power, h->stream, kRing);
+    rc = band_sweep(h, h->d_ring + h->ring_pos, 0, 2048, h->wstart, 1, h->d_power, h->stream, kRing, kTimed);  // (a bracket nobody reads, as above)
     if (rc != AWPU_OK) return rc;
     AWPU_HIP_TRY(hipMemcpyAsync(power, h->d_power, need_power * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     AWPU_HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1348,7 +1333,6 @@ int awpu_hip_process_packed(awpu_hip_t *h, const float *d_packed, int32_t batch,
     if (rc != AWPU_OK) return rc;
     hipStream_t s = stream_of(h, stream);
     if (rc = enter_stream(h, s); rc != AWPU_OK) return rc;
-    TimingOff untimed(h);  // asynchronous path: the caller times its own stream
     // the shape awpu_hip_process_device takes for this batch, as long as that is a frame-pair shape (sweep_packed)
     // (the buffer is the caller's: awpu_hip_packed_bytes(batch) of it are taken to be there, and the sweep reads no further)
     return sweep_packed(h, plan, d_packed, packed_floats_of(h, plan, batch), batch, d_power, s);

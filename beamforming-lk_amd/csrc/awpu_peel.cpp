@@ -137,7 +137,6 @@ int awpu_hip_peel_device(awpu_hip_t *h, const float *d_frames, int32_t batch, co
     if (rc == AWPU_OK && !d_residual_frames) rc = h->d_peel_frames.ensure(floats);
     if (rc == AWPU_OK) rc = enter_stream(h, s);
     if (rc != AWPU_OK) return rc;
-    TimingOff untimed(h);  // asynchronous path: the caller times its own stream
     float *work = d_residual_frames ? d_residual_frames : h->d_peel_frames.get();
     AWPU_HIP_TRY(hipMemcpyAsync(work, d_frames, floats * sizeof(float), hipMemcpyDeviceToDevice, s));
     PeelOut out;
@@ -159,7 +158,6 @@ int awpu_hip_peel(awpu_hip_t *h, const float *frames, int32_t batch, const awpu_
     if (rc == AWPU_OK) rc = h->d_peel_out.ensure(step_bytes + 3 * plane * sizeof(float));
     if (rc == AWPU_OK) rc = enter_stream(h, h->stream);
     if (rc != AWPU_OK) return rc;
-    TimingOff untimed(h);  // (the loop is several sweeps with kernels of its own between them: no one launch to time)
     hipStream_t s = h->stream;
     AWPU_HIP_TRY(hipMemcpyAsync(h->d_peel_frames, frames, floats * sizeof(float), hipMemcpyHostToDevice, s));
     float *const d_maps = reinterpret_cast<float *>(h->d_peel_out.get() + step_bytes);

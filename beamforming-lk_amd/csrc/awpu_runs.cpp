@@ -103,7 +103,7 @@ void parallel_copy(void *dst, const void *src, size_t bytes) {
 //   2. upload to blk_in.d[b] on up, ev_blk_in[b] behind it
 //   3. up waits ev_blk_cut[b] (i >= 2, swept runs) and ev_listened[b] (i >= 2, listened runs): piece i-2 has read blk_hist.d[b]
 //   4. the history is formed on up, ev_blk_hist[b] behind it; sw waits it, and li where that is another stream
-//   5. the cut on sw, then ev_blk_cut[b]; ev_begin at piece 0; the sweep with the handle's own event bracket off; what the
+//   5. the cut on sw, then ev_blk_cut[b]; ev_begin at piece 0; the sweep, untimed (the run's bracket spans the pieces); what the
 //      consumer shows of the powers; ev_blk_swept[b].  With bands -- the handle's own (awpu_hip_band.h) or a spectral run's
 //      (awpu_hip_spectral.h) -- the cut is their pre-pass, which cuts and filters in one (band_cut) into a plane of d_blk_frames
 //      per band, and ev_begin stands in front of it; then one sweep per band, each the launch() of the band-by-band run, into a
@@ -141,9 +141,9 @@ struct Consumer {
     virtual int staged_blocks(const Piece &p) = 0;              // host forms: stages the input in blk_in.h[b]; the blocks to upload
     virtual int history(const Piece &p, hipStream_t s) = 0;     // blk_hist.d[b], out of blk_in.d[b] (host forms) or the caller's samples
     virtual int cut(const Piece &p, hipStream_t s) = 0;         // its snapshots' windows into d_blk_frames
-    // the sweep of a piece's n windows (one band's) into d_pow: launch(), unless the consumer sweeps otherwise (CoherePieces)
-    virtual int sweep_frames(awpu_hip *h, const float *d_frames, int n, float *d_pow, hipStream_t s, int layout) {
-        return launch(h, d_frames, n, d_pow, s, layout);
+    // the sweep of piece p's windows (one band's) into d_pow, untimed: launch(), unless the consumer sweeps otherwise (CoherePieces)
+    virtual int sweep_frames(awpu_hip *h, const Piece &p, const float *d_frames, float *d_pow, hipStream_t s, int layout) {
+        return launch(h, d_frames, p.n, d_pow, s, layout);
     }
     // behind the sweeps into d_pow (band b's powers `plane` floats behind band b-1's), before ev_blk_swept
     virtual int show(const Piece &, float *, long long, hipStream_t) { return AWPU_OK; }
@@ -221,9 +221,8 @@ int run_pieces(awpu_hip *h, const BlockRun &src, hipStream_t user, Consumer &c) 
     if (rc != AWPU_OK) return rc;
     hipStream_t up = host ? h->copy_stream : sw;
     hipStream_t li = host && c.sweep && h->listen_stream && env().listen_stream ? h->listen_stream : sw;
-    const bool keep_timing = h->timing;
-    const bool time_it = keep_timing && host && c.sweep && n_pieces > 0;
-    if (!time_it) h->timing = false;  // the device form is asynchronous: the caller times its own stream; nothing swept, nothing timed
+    // the device form is asynchronous: the caller times its own stream; nothing swept, nothing timed.  (The bracket is body()'s.)
+    const bool time_it = host && c.sweep && n_pieces > 0;
     const auto fetch = [&](const Piece &p) -> int {
         if (c.sweep) {
             AWPU_HIP_TRY(hipStreamWaitEvent(up, h->ev_blk_swept[p.b], 0));
@@ -291,10 +290,8 @@ int run_pieces(awpu_hip *h, const BlockRun &src, hipStream_t user, Consumer &c) 
                 float *d_pow = host ? h->d_power + (size_t) b * piece_max * P * planes : (c.power ? c.power + (size_t) p.first * P : h->d_power);
                 const long long pow_plane = !host && c.power ? (long long) c.n_items * P : (long long) p.n * P;
                 const size_t frames_plane = (size_t) S * (compact ? h->compact_hist : AWPU_HIST) * p.n;
-                h->timing = false;
                 for (int k = 0; k < planes && brc == AWPU_OK; k++)
-                    brc = c.sweep_frames(h, h->d_blk_frames + k * frames_plane, p.n, d_pow + k * pow_plane, sw, compact ? kCompact : kFull);
-                h->timing = time_it;
+                    brc = c.sweep_frames(h, p, h->d_blk_frames + k * frames_plane, d_pow + k * pow_plane, sw, compact ? kCompact : kFull);
                 if (brc == AWPU_OK) brc = c.show(p, d_pow, pow_plane, sw);
                 if (brc != AWPU_OK) return brc;
                 if (host) AWPU_HIP_TRY(hipEventRecord(h->ev_blk_swept[b], sw));
@@ -330,10 +327,9 @@ int run_pieces(awpu_hip *h, const BlockRun &src, hipStream_t user, Consumer &c) 
             if ((brc = deliver(pieces[delivered++])) != AWPU_OK) return brc;
         AWPU_HIP_TRY(hipStreamSynchronize(up));
         if (li != sw) AWPU_HIP_TRY(hipStreamSynchronize(li));
-        return wait_and_time(h);
+        return wait_and_time(h, time_it);
     };
     rc = body();
-    h->timing = keep_timing;
     if (rc != AWPU_OK && host) {
         (void) hipStreamSynchronize(h->copy_stream);
         if (h->listen_stream) (void) hipStreamSynchronize(h->listen_stream);
@@ -1084,10 +1080,10 @@ struct CoherePieces final : WatchPieces {
         const int rc = ensure_cohere_table(h);
         return rc != AWPU_OK ? rc : WatchPieces::ensure(piece_max, lo_, width_, sw);
     }
-    int sweep_frames(awpu_hip *, const float *d_frames, int n, float *d_pow, hipStream_t s, int layout) override {
+    int sweep_frames(awpu_hip *, const Piece &p, const float *d_frames, float *d_pow, hipStream_t s, int layout) override {
         CohereOut out;
         (show == AWPU_COHERE_FACTOR ? out.coherence : out.weighted) = d_pow;
-        return launch_cohere(h, d_frames, n, out, s, layout);
+        return launch_cohere(h, d_frames, p.n, out, s, layout);
     }
 };
 
@@ -1116,7 +1112,6 @@ struct PeelPieces final : WatchPieces {
     const awpu_peel_t pe;
     const int show_row;
     awpu_peel_step_t *const steps;  // [n_frames][pe.steps], host or device memory as the run's other outputs, or null
-    int swept = 0, piece = 0;       // frames peeled so far, and pieces: sweep_frames sees the pieces in order, once each
     PeelPieces(awpu_hip *h_, const BlockRun &src_, int n_blocks_, const WatchRun &wr_, const awpu_peel_t &pe_, int show_, awpu_peel_step_t *steps_)
         : WatchPieces(h_, src_, n_blocks_, wr_), pe(pe_), show_row(show_), steps(steps_) {
         whole_frames = true;
@@ -1131,13 +1126,12 @@ struct PeelPieces final : WatchPieces {
         if (rc == AWPU_OK && host && steps) rc = h->peel_steps.ensure(step_bytes(piece_max), true);
         return rc != AWPU_OK ? rc : WatchPieces::ensure(piece_max, lo_, width_, sw);
     }
-    int sweep_frames(awpu_hip *, const float *d_frames, int n, float *d_pow, hipStream_t s, int layout) override {
+    int sweep_frames(awpu_hip *, const Piece &p, const float *d_frames, float *d_pow, hipStream_t s, int layout) override {
         if (layout != kFull) return fail(AWPU_ERR_STATE, "a peel run cuts its snapshots whole");
         PeelOut out;
         (show_row == AWPU_PEEL_CLEAN ? out.clean : show_row == AWPU_PEEL_RESIDUAL ? out.residual : out.map) = d_pow;
-        if (steps) out.steps = host ? reinterpret_cast<awpu_peel_step_t *>(h->peel_steps.d[piece & 1].get()) : steps + (size_t) swept * pe.steps;
-        swept += n, piece++;
-        return peel_enqueue(h, const_cast<float *>(d_frames), n, pe, out, s);  // (d_blk_frames: the run's own scratch, cut anew for every piece)
+        if (steps) out.steps = host ? reinterpret_cast<awpu_peel_step_t *>(h->peel_steps.d[p.b].get()) : steps + (size_t) p.first * pe.steps;
+        return peel_enqueue(h, const_cast<float *>(d_frames), p.n, pe, out, s);  // (d_blk_frames: the run's own scratch, cut anew for every piece)
     }
     int fetch_shown(const Piece &p, hipStream_t s) override {
         if (steps) AWPU_HIP_TRY(hipMemcpyAsync(h->peel_steps.h[p.b], h->peel_steps.d[p.b], step_bytes(p.n), hipMemcpyDeviceToHost, s));

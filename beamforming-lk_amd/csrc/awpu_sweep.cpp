@@ -539,9 +539,9 @@ void choose_fast_variant(awpu_hip *h, int batch, int *fpi, int *ppw, int *nw) {
 }
 
 // a launch is over: close the timing bracket and count it (also on the diagnostic paths)
-int finish_launch(awpu_hip *h, int batch, hipStream_t s, int kernel_id) {
+int finish_launch(awpu_hip *h, int batch, hipStream_t s, bool timed, int kernel_id) {
     h->stats.kernel_variant = kernel_id;
-    if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_end, s));
+    if (timed) AWPU_HIP_TRY(hipEventRecord(h->ev_end, s));
     h->stats.launches += 1;
     h->stats.frames += (uint64_t) batch;
     return AWPU_OK;
@@ -580,65 +580,64 @@ void fill_shared(Args &a, const awpu_hip *h, const awpu::FastPlan &plan, int bat
     a.batch = batch;
 }
 
-int launch_exact_pairs(awpu_hip *h, const float *d_frames, int batch, float *d_power, hipStream_t s, int hist_eff, int wstart_eff) {
+int launch_exact_pairs(awpu_hip *h, const SweepCall &call) {
     if (const int rc = build_exact_pair_lut(h); rc != AWPU_OK) return rc;
     const awpu::FastPlan &pp = h->exact_plan;
-    if (const int prc = ensure_pack(h, pair_pack_floats(std::max(h->cfg.max_batch, batch), pp.usable_pad, pp.wr, 2)); prc != AWPU_OK) return prc;
+    if (const int prc = ensure_pack(h, pair_pack_floats(std::max(h->cfg.max_batch, call.batch), pp.usable_pad, pp.wr, 2)); prc != AWPU_OK) return prc;
     awpu::ExactPairArgs a{};
-    fill_shared(a, h, pp, batch, d_power);
+    fill_shared(a, h, pp, call.batch, call.power);
     a.packed = h->d_pack;
     a.lut = h->d_exact_pair_lut;
-    a.sums = h->sums_out;
+    a.sums = call.opts.sums;
     a.wp = pp.wr;
     a.cols = h->pair_cols;
     a.tiles = awpu::pair_tiles(a.pixel_count, a.cols);
-    a.n_pairs = (batch + 1) / 2;
+    a.n_pairs = (call.batch + 1) / 2;
     a.pair_group = awpu::xcd_pair_group((size_t) pp.usable_pad * pp.wr * 8, a.n_pairs);
-    if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
-    AWPU_HIP_TRY(awpu::launch_pack_pairs(d_frames, h->cfg.n_streams, hist_eff, wstart_eff, h->d_index, h->usable(), pp.usable_pad,
-                                         h->d_gain, pp.wr, batch, h->d_pack, false, s));  // raw samples: no stencil in front of the reference's order
-    AWPU_HIP_TRY(awpu::launch_das_exact_pairs(a, {h->exact_pair_lut_entries, h->d_pack.cap}, s));
-    return finish_launch(h, batch, s, AWPU_KERNEL_EXACT_PAIR);
+    if (call.opts.timed) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, call.stream));
+    AWPU_HIP_TRY(awpu::launch_pack_pairs(call.frames, h->cfg.n_streams, call.hist_eff, call.wstart_eff, h->d_index, h->usable(), pp.usable_pad,
+                                         h->d_gain, pp.wr, call.batch, h->d_pack, false, call.stream));  // raw samples: no stencil in front of the reference's order
+    AWPU_HIP_TRY(awpu::launch_das_exact_pairs(a, {h->exact_pair_lut_entries, h->d_pack.cap}, call.stream));
+    return finish_launch(h, call.batch, call.stream, call.opts.timed, AWPU_KERNEL_EXACT_PAIR);
 }
 
 // ... four vertically adjacent pixels per wave where the row length is known (das_exact_quad_kernel): same bits, fewer LDS reads
-int launch_exact_quads(awpu_hip *h, const float *d_frames, int batch, float *d_power, hipStream_t s, int hist_eff, int wstart_eff) {
+int launch_exact_quads(awpu_hip *h, const SweepCall &call) {
     if (const int rc = build_quad_lut(h, kQuadExact); rc != AWPU_OK) return rc;
     const QuadTable &table = h->quad_tables[kQuadExact];
     const awpu::FastPlan &pp = table.plan;
-    if (const int prc = ensure_pack(h, pair_pack_floats(std::max(h->cfg.max_batch, batch), pp.usable_pad, pp.wr, 2)); prc != AWPU_OK) return prc;
+    if (const int prc = ensure_pack(h, pair_pack_floats(std::max(h->cfg.max_batch, call.batch), pp.usable_pad, pp.wr, 2)); prc != AWPU_OK) return prc;
     awpu::ExactQuadArgs a{};
-    fill_shared(a, h, pp, batch, d_power);
+    fill_shared(a, h, pp, call.batch, call.power);
     a.packed = h->d_pack;
     a.lut = table.d;
-    a.sums = h->sums_out;
+    a.sums = call.opts.sums;
     a.wp = pp.wr;
     a.cols = h->cfg.grid_columns;
     a.rows = h->cfg.pixel_count / a.cols;
     a.tiles = awpu::quad_tiles(a.rows, a.cols);
-    a.n_pairs = (batch + 1) / 2;
+    a.n_pairs = (call.batch + 1) / 2;
     a.pair_group = awpu::xcd_pair_group((size_t) pp.usable_pad * pp.wr * 8, a.n_pairs);
-    if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
-    AWPU_HIP_TRY(awpu::launch_pack_pairs(d_frames, h->cfg.n_streams, hist_eff, wstart_eff, h->d_index, h->usable(), pp.usable_pad,
-                                         h->d_gain, pp.wr, batch, h->d_pack, false, s));
-    AWPU_HIP_TRY(awpu::launch_das_exact_quads(a, {table.entries, h->d_pack.cap}, s));
-    return finish_launch(h, batch, s, AWPU_KERNEL_EXACT_QUAD);
+    if (call.opts.timed) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, call.stream));
+    AWPU_HIP_TRY(awpu::launch_pack_pairs(call.frames, h->cfg.n_streams, call.hist_eff, call.wstart_eff, h->d_index, h->usable(), pp.usable_pad,
+                                         h->d_gain, pp.wr, call.batch, h->d_pack, false, call.stream));
+    AWPU_HIP_TRY(awpu::launch_das_exact_quads(a, {table.entries, h->d_pack.cap}, call.stream));
+    return finish_launch(h, call.batch, call.stream, call.opts.timed, AWPU_KERNEL_EXACT_QUAD);
 }
 
 // ... on the {next, d} layout (das_exact_nd_kernel, round 5): cur - next formed once per sample by the pack pass; nq quads per wave
-int launch_exact_nd(awpu_hip *h, const float *d_frames, int batch, float *d_power, hipStream_t s, int hist_eff, int wstart_eff, int nq,
-                    const float *prepacked = nullptr, size_t prepacked_floats = 0) {
+int launch_exact_nd(awpu_hip *h, const SweepCall &call, int nq, const float *prepacked = nullptr, size_t prepacked_floats = 0) {
     int rc = build_quad_lut(h, kQuadExactNd);
     if (rc != AWPU_OK) return rc;
     const QuadTable &table = h->quad_tables[kQuadExactNd];
     const awpu::FastPlan &pp = table.plan;
     if (!prepacked)
-        if (const int prc = ensure_pack(h, pair_pack_floats(std::max(h->cfg.max_batch, batch), pp.usable_pad, pp.wr, 4)); prc != AWPU_OK) return prc;
+        if (const int prc = ensure_pack(h, pair_pack_floats(std::max(h->cfg.max_batch, call.batch), pp.usable_pad, pp.wr, 4)); prc != AWPU_OK) return prc;
     awpu::ExactNdArgs a{};
-    fill_shared(a, h, pp, batch, d_power);
+    fill_shared(a, h, pp, call.batch, call.power);
     a.packed = prepacked ? prepacked : h->d_pack;
     a.lut = table.d;
-    a.sums = h->sums_out;
+    a.sums = call.opts.sums;
     a.wq = pp.wr;
     a.wq_tile = pp.row_bytes / 16;
     a.starts = h->d_nd_starts;
@@ -647,7 +646,7 @@ int launch_exact_nd(awpu_hip *h, const float *d_frames, int batch, float *d_powe
     a.rows = h->cfg.pixel_count / a.cols;
     a.nq = nq;
     a.tiles = awpu::nd_tiles(a.rows, a.cols, nq);
-    a.n_pairs = (batch + 1) / 2;
+    a.n_pairs = (call.batch + 1) / 2;
     a.pair_group = awpu::xcd_pair_group((size_t) pp.usable_pad * pp.wr * 16, a.n_pairs, env().pair_group);
     // Four pairs instead of two where four pairs' rows are at most 6 MiB (the headline: 5.7 MB): every XCD then walks the table twice per
     // launch instead of four times, and a tile stages only its window of a row.  Alternating runs on one box: -0.30 % (5.378 against
@@ -658,7 +657,7 @@ int launch_exact_nd(awpu_hip *h, const float *d_frames, int batch, float *d_powe
         const long long key = ((long long) a.n_pairs << 24) | ((long long) a.pair_group << 8) | nq;
         if (!h->d_nd_items.holds(items)) {
             retire_live_graphs(h);
-            AWPU_HIP_TRY(hipStreamSynchronize(s));  // (a sweep in flight may still read the old list)
+            AWPU_HIP_TRY(hipStreamSynchronize(call.stream));  // (a sweep in flight may still read the old list)
             if (rc = h->d_nd_items.grow(items); rc != AWPU_OK) return rc;
             h->nd_items_key = -1;
         }
@@ -673,21 +672,21 @@ int launch_exact_nd(awpu_hip *h, const float *d_frames, int batch, float *d_powe
         a.tail = std::max(1, std::atoi(v) >= 100 ? per : per * std::atoi(v) / 100);
     }
 #endif
-    if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
+    if (call.opts.timed) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, call.stream));
     if (!prepacked) {  // (the pack pass zeroes the sweep's queues too: one dispatch less than a memset between the two)
-        AWPU_HIP_TRY(awpu::launch_pack_nd(d_frames, h->cfg.n_streams, hist_eff, wstart_eff, h->d_index, h->usable(), pp.usable_pad, h->d_gain,
-                                          pp.wr, batch, h->d_pack, a.queue, s));
+        AWPU_HIP_TRY(awpu::launch_pack_nd(call.frames, h->cfg.n_streams, call.hist_eff, call.wstart_eff, h->d_index, h->usable(), pp.usable_pad, h->d_gain,
+                                          pp.wr, call.batch, h->d_pack, a.queue, call.stream));
         a.queue_zeroed = 1;
     }
 #ifdef AWPU_TUNING_BUILD
     const size_t n_wgs = std::min<size_t>((size_t) a.n_pairs * a.tiles, (size_t) a.wgs);
     if (env().debug & 16)  // per-workgroup timeline (where, when, phases)
-        if (const int drc = diag_begin(h, n_wgs * 8, true, s, &a.debug_out); drc != AWPU_OK) return drc;
+        if (const int drc = diag_begin(h, n_wgs * 8, true, call.stream, &a.debug_out); drc != AWPU_OK) return drc;
 #endif
-    AWPU_HIP_TRY(awpu::launch_das_exact_nd(a, {table.entries, prepacked ? prepacked_floats : h->d_pack.cap}, s));
-    rc = finish_launch(h, batch, s, AWPU_KERNEL_EXACT_ND);
+    AWPU_HIP_TRY(awpu::launch_das_exact_nd(a, {table.entries, prepacked ? prepacked_floats : h->d_pack.cap}, call.stream));
+    rc = finish_launch(h, call.batch, call.stream, call.opts.timed, AWPU_KERNEL_EXACT_ND);
 #ifdef AWPU_TUNING_BUILD
-    if (rc == AWPU_OK && (env().debug & 16)) return dump_nd_timeline(h, n_wgs, s);
+    if (rc == AWPU_OK && (env().debug & 16)) return dump_nd_timeline(h, n_wgs, call.stream);
 #endif
     return rc;
 }
@@ -710,7 +709,8 @@ bool takes_exact_nd(awpu_hip *h, int batch, int *nq) {
 }
 
 // The completion flag of the synchronous one-frame host call (das_kernels.h: DoneFlag; das_fast.hip: store_tile_and_signal): what the
-// next armed launch of `workgroups` workgroups gets, and what the handle remembers once that launch has gone out.
+// next armed launch of `workgroups` workgroups gets, and -- once that launch has gone out -- what the handle remembers and the
+// call that asked for the flag (SweepOpts::flag) is told.
 int arm_done_flag(awpu_hip *h, unsigned long long workgroups, awpu::DoneFlag *out) {
     if (!h->d_done_counter) {
         if (const int rc = h->d_done_counter.grow(1); rc != AWPU_OK) return rc;
@@ -726,36 +726,35 @@ int arm_done_flag(awpu_hip *h, unsigned long long workgroups, awpu::DoneFlag *ou
     out->seq = h->done_seq + 1;
     return AWPU_OK;
 }
-void done_flag_armed(awpu_hip *h, const awpu::DoneFlag &d) {
+void done_flag_armed(awpu_hip *h, const awpu::DoneFlag &d, bool *will_raise) {
     h->done_total = d.target;
     h->done_seq = d.seq;
-    h->done_used = true;
+    *will_raise = true;
 }
 
 // single frames in the reference's order: the halves form of the {next, d} layout (das_exact_ndh_kernel) -- every mic resident and
-// staged by the workgroups themselves (one array), or chunked behind a pack pre-pass.  `pitch` = floats between two streams of a frame
-int launch_exact_ndh(awpu_hip *h, const float *d_frames, int batch, float *d_power, hipStream_t s, int pitch, int wstart_eff, bool stationary,
-                     int nq, bool pixel_per_wave = false) {
+// staged by the workgroups themselves (one array), or chunked behind a pack pre-pass
+int launch_exact_ndh(awpu_hip *h, const SweepCall &call, bool stationary, int nq, bool pixel_per_wave = false) {
     const QuadLayout layout = stationary ? kQuadExactNdhStationary : kQuadExactNdh;
     int rc = build_quad_lut(h, layout);
     if (rc != AWPU_OK) return rc;
     const QuadTable &table = h->quad_tables[layout];
     const awpu::FastPlan &pp = table.plan;
     if (!stationary) {
-        const size_t need = std::max((size_t) h->cfg.max_batch, (size_t) batch) * pp.usable_pad * pp.wr * 4;
+        const size_t need = std::max((size_t) h->cfg.max_batch, (size_t) call.batch) * pp.usable_pad * pp.wr * 4;
         if (const int prc = ensure_pack(h, need); prc != AWPU_OK) return prc;
     }
     awpu::ExactNdhArgs a{};
-    fill_shared(a, h, pp, batch, d_power);
+    fill_shared(a, h, pp, call.batch, call.power);
     a.packed = stationary ? nullptr : h->d_pack;
-    a.frames = d_frames;
+    a.frames = call.frames;
     a.lut = table.d;
     a.index = h->d_index;
     a.gain = h->d_gain;
-    a.sums = h->sums_out;
+    a.sums = call.opts.sums;
     a.n_streams = h->cfg.n_streams;
-    a.pitch = pitch;
-    a.wstart = wstart_eff;
+    a.pitch = call.hist_eff;
+    a.wstart = call.wstart_eff;
     a.wh = pp.wr;
     a.cols = h->cfg.grid_columns;
     a.rows = h->cfg.pixel_count / a.cols;
@@ -763,74 +762,72 @@ int launch_exact_ndh(awpu_hip *h, const float *d_frames, int batch, float *d_pow
     a.tiles = pixel_per_wave ? awpu::ndp_tiles(a.rows, a.cols) : awpu::ndh_tiles(a.rows, a.cols, nq);
     a.lut_cols = (a.cols + 31) / 32 * 32;
     a.identity = h->identity_mics;
-    h->done_used = false;
-    if (h->done_arm && s == h->stream && stationary && nq == 1 && !pixel_per_wave) {  // (the one-frame host call: live_host_call)
-        if (rc = arm_done_flag(h, (unsigned long long) batch * a.tiles, &a.done); rc != AWPU_OK) return rc;
+    if (call.opts.flag && call.stream == h->stream && stationary && nq == 1 && !pixel_per_wave) {  // (the one-frame host call: live_host_call)
+        if (rc = arm_done_flag(h, (unsigned long long) call.batch * a.tiles, &a.done); rc != AWPU_OK) return rc;
     }
-    if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
+    if (call.opts.timed) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, call.stream));
     if (!stationary)
-        AWPU_HIP_TRY(awpu::launch_pack_ndh(d_frames, h->cfg.n_streams, pitch, wstart_eff, a.identity ? nullptr : h->d_index, h->usable(), pp.usable_pad, h->d_gain, pp.wr,
-                                           batch, h->d_pack, s));
+        AWPU_HIP_TRY(awpu::launch_pack_ndh(call.frames, h->cfg.n_streams, call.hist_eff, call.wstart_eff, a.identity ? nullptr : h->d_index, h->usable(), pp.usable_pad, h->d_gain, pp.wr,
+                                           call.batch, h->d_pack, call.stream));
     if (pixel_per_wave) {
-        AWPU_HIP_TRY(awpu::launch_das_exact_ndp(a, {table.entries, h->d_pack.cap}, s));
+        AWPU_HIP_TRY(awpu::launch_das_exact_ndp(a, {table.entries, h->d_pack.cap}, call.stream));
     } else {
-        AWPU_HIP_TRY(awpu::launch_das_exact_ndh(a, stationary, {table.entries, stationary ? 0 : h->d_pack.cap}, s));
+        AWPU_HIP_TRY(awpu::launch_das_exact_ndh(a, stationary, {table.entries, stationary ? 0 : h->d_pack.cap}, call.stream));
     }
-    if (a.done.flag) done_flag_armed(h, a.done);  // (the launch went out: its workgroups will count themselves)
-    return finish_launch(h, batch, s, pixel_per_wave ? AWPU_KERNEL_EXACT_NDP : stationary ? AWPU_KERNEL_EXACT_NDH_STATIONARY : AWPU_KERNEL_EXACT_NDH);
+    if (a.done.flag) done_flag_armed(h, a.done, call.opts.flag);  // (the launch went out: its workgroups will count themselves)
+    return finish_launch(h, call.batch, call.stream, call.opts.timed, pixel_per_wave ? AWPU_KERNEL_EXACT_NDP : stationary ? AWPU_KERNEL_EXACT_NDH_STATIONARY : AWPU_KERNEL_EXACT_NDH);
 }
 
-int launch_exact(awpu_hip *h, const float *d_frames, int batch, float *d_power, hipStream_t s, int hist_eff, int wstart_eff) {
+int launch_exact(awpu_hip *h, const SweepCall &call) {
     awpu::SweepArgs a{};
-    a.frames = d_frames;
+    a.frames = call.frames;
     a.lut = h->d_lut;
     a.index = h->d_index;
-    a.power = d_power;
+    a.power = call.power;
     a.gain = h->d_gain;
-    a.sums = h->sums_out;  // (choose_shape: EXACT + FIR8 only)
+    a.sums = call.opts.sums;  // (choose_shape: EXACT + FIR8 only)
     a.n_streams = h->cfg.n_streams;
-    a.hist = hist_eff;
+    a.hist = call.hist_eff;
     a.usable = h->usable();
     a.pixel_count = h->cfg.pixel_count;
-    a.wstart = wstart_eff;
+    a.wstart = call.wstart_eff;
     a.window = h->window;
-    a.batch = batch;
-    if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
+    a.batch = call.batch;
+    if (call.opts.timed) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, call.stream));
     if (h->cfg.interp == AWPU_INTERP_FIR8) {
         // AWPU_MATH_F32_EXACT: the reference's rounding, a multiply and an add per tap; AWPU_MATH_F32_FAST (a launch too small for the
         // plane kernel): one FMA per tap
-        AWPU_HIP_TRY(awpu::launch_das_fir8(a, h->d_fir, h->cfg.math == AWPU_MATH_F32_EXACT, s));
+        AWPU_HIP_TRY(awpu::launch_das_fir8(a, h->d_fir, h->cfg.math == AWPU_MATH_F32_EXACT, call.stream));
     } else {
-        AWPU_HIP_TRY(awpu::launch_das_exact(a, h->cfg.math == AWPU_MATH_BF16_ACC, s));
+        AWPU_HIP_TRY(awpu::launch_das_exact(a, h->cfg.math == AWPU_MATH_BF16_ACC, call.stream));
     }
-    return finish_launch(h, batch, s, h->cfg.interp == AWPU_INTERP_FIR8 ? AWPU_KERNEL_FIR8 : AWPU_KERNEL_EXACT_VERIFY);
+    return finish_launch(h, call.batch, call.stream, call.opts.timed, h->cfg.interp == AWPU_INTERP_FIR8 ? AWPU_KERNEL_FIR8 : AWPU_KERNEL_EXACT_VERIFY);
 }
 
 // FIR8 on the four-plane frame-pair layout (das_fir8_plane_kernel): a lane owns four consecutive outputs
-int launch_fir8_planes(awpu_hip *h, const float *d_frames, int batch, float *d_power, hipStream_t s, int hist_eff, int wstart_eff) {
+int launch_fir8_planes(awpu_hip *h, const SweepCall &call) {
     if (const int rc = build_fir8_plane_lut(h); rc != AWPU_OK) return rc;
     const awpu::FastPlan &pp = h->fir_plane_plan;
     const int U = h->usable(), P = h->cfg.pixel_count, cols = h->cfg.grid_columns;
     if (const int prc = ensure_pack(h, pair_pack_floats(h->cfg.max_batch, U, pp.wr, 2)); prc != AWPU_OK) return prc;
     awpu::PairArgs pa{};
-    fill_shared(pa, h, pp, batch, d_power);
+    fill_shared(pa, h, pp, call.batch, call.power);
     pa.packed = h->d_pack;
     pa.wp = pp.wr;
-    pa.pair_group = awpu::xcd_pair_group((size_t) U * pp.wr * 8, (batch + 1) / 2);
+    pa.pair_group = awpu::xcd_pair_group((size_t) U * pp.wr * 8, (call.batch + 1) / 2);
     // vertical pixel quads (samples shared between pixels of one column with the same integer delay) where the grid's row
     // length is known and the rows are staged at the pitch that block is generated for; AWPU_FIR8_SHARE=0: consecutive pixels
     if (env().fir_share != 0 && cols > 0 && P % cols == 0 && h->cfg.pixel_begin % cols == 0 && (uint32_t) pp.wr * 2u == awpu::kFirStaticPlaneBytesHost)
         pa.cols = cols;
-    if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
-    AWPU_HIP_TRY(awpu::launch_pack_planes(d_frames, h->cfg.n_streams, hist_eff, wstart_eff, h->d_index, U, h->d_gain, pp.wr,
-                                          batch, h->d_pack, s));
-    AWPU_HIP_TRY(awpu::launch_das_fir8_planes(pa, h->d_fir_plane_lut, h->d_fir, env().quad_variant, {h->fir_plane_lut_entries, h->d_pack.cap}, s));
-    return finish_launch(h, batch, s, AWPU_KERNEL_FIR8_PLANES);
+    if (call.opts.timed) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, call.stream));
+    AWPU_HIP_TRY(awpu::launch_pack_planes(call.frames, h->cfg.n_streams, call.hist_eff, call.wstart_eff, h->d_index, U, h->d_gain, pp.wr,
+                                          call.batch, h->d_pack, call.stream));
+    AWPU_HIP_TRY(awpu::launch_das_fir8_planes(pa, h->d_fir_plane_lut, h->d_fir, env().quad_variant, {h->fir_plane_lut_entries, h->d_pack.cap}, call.stream));
+    return finish_launch(h, call.batch, call.stream, call.opts.timed, AWPU_KERNEL_FIR8_PLANES);
 }
 
 // frame-pair shape: two frames per item, for batches on grids that fill the chip
-int launch_pairs(awpu_hip *h, const awpu_hip::FastLut *plut, const float *d_frames, int batch, float *d_power,
-                 hipStream_t s, int hist_eff, int wstart_eff, int stationary_tiles = 0, const float *prepacked = nullptr,
+int launch_pairs(awpu_hip *h, const awpu_hip::FastLut *plut, const SweepCall &call, int stationary_tiles = 0, const float *prepacked = nullptr,
                  size_t prepacked_floats = 0) {
     const awpu::FastPlan &pp = plut->plan;
     // the stationary shape stages its pairs itself, straight from the caller's frames (no pack pre-pass, no packed buffer)
@@ -838,44 +835,43 @@ int launch_pairs(awpu_hip *h, const awpu_hip::FastLut *plut, const float *d_fram
     if (!prepacked && !self_staged)
         if (const int prc = ensure_pack(h, pair_pack_floats(h->cfg.max_batch, h->usable(), pp.wr, 2)); prc != AWPU_OK) return prc;
     awpu::PairArgs pa{};
-    fill_shared(pa, h, pp, batch, d_power);
+    fill_shared(pa, h, pp, call.batch, call.power);
     pa.packed = prepacked ? prepacked : (self_staged ? nullptr : h->d_pack);
     if (self_staged) {
-        pa.frames = d_frames;
+        pa.frames = call.frames;
         pa.index = h->d_index;
         pa.n_streams = h->cfg.n_streams;
-        pa.hist = hist_eff;
-        pa.wstart = wstart_eff;
+        pa.hist = call.hist_eff;
+        pa.wstart = call.wstart_eff;
     }
     pa.lut = plut->d;
     pa.wp = pp.wr;
     pa.cols = h->pair_cols;
     pa.tiles = awpu::pair_tiles(h->cfg.pixel_count, h->pair_cols);
-    pa.n_pairs = (batch + 1) / 2;
+    pa.n_pairs = (call.batch + 1) / 2;
     pa.pair_group = awpu::xcd_pair_group((size_t) h->usable() * pp.wr * 8, pa.n_pairs);
     pa.debug = env().debug;
     size_t n_waves = 0;
     if (stationary_tiles > 0) pa.debug &= ~16;  // (no stamped build of the stationary shape)
     if (pa.debug & 16) {
-        n_waves = (size_t) 16 * ((batch + 1) / 2) * awpu::pair_tiles(h->cfg.pixel_count, h->pair_cols);
-        if (const int rc = diag_begin(h, n_waves * 12, false, s, &pa.debug_out); rc != AWPU_OK) return rc;
+        n_waves = (size_t) 16 * ((call.batch + 1) / 2) * awpu::pair_tiles(h->cfg.pixel_count, h->pair_cols);
+        if (const int rc = diag_begin(h, n_waves * 12, false, call.stream, &pa.debug_out); rc != AWPU_OK) return rc;
     }
-    if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
+    if (call.opts.timed) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, call.stream));
     if (!prepacked && !self_staged)
-        AWPU_HIP_TRY(awpu::launch_pack_pairs(d_frames, h->cfg.n_streams, hist_eff, wstart_eff, h->d_index, h->usable(),
-                                             h->usable(), nullptr, pp.wr, batch, h->d_pack, true, s));  // gains ride on the table weights here
+        AWPU_HIP_TRY(awpu::launch_pack_pairs(call.frames, h->cfg.n_streams, call.hist_eff, call.wstart_eff, h->d_index, h->usable(),
+                                             h->usable(), nullptr, pp.wr, call.batch, h->d_pack, true, call.stream));  // gains ride on the table weights here
     const awpu::Extents have{plut->entries, prepacked ? prepacked_floats : h->d_pack.cap};
     if (stationary_tiles > 0) {
-        AWPU_HIP_TRY(awpu::launch_das_pairs_stationary(pa, stationary_tiles, have, s));
+        AWPU_HIP_TRY(awpu::launch_das_pairs_stationary(pa, stationary_tiles, have, call.stream));
     } else {
-        AWPU_HIP_TRY(awpu::launch_das_pairs(pa, have, s));
+        AWPU_HIP_TRY(awpu::launch_das_pairs(pa, have, call.stream));
     }
-    return diag_end(h, finish_launch(h, batch, s, stationary_tiles > 0 ? AWPU_KERNEL_PAIR_STATIONARY : AWPU_KERNEL_PAIR), n_waves, 16, "pairs", s);
+    return diag_end(h, finish_launch(h, call.batch, call.stream, call.opts.timed, stationary_tiles > 0 ? AWPU_KERNEL_PAIR_STATIONARY : AWPU_KERNEL_PAIR), n_waves, 16, "pairs", call.stream);
 }
 
 // quad shape: the frame-pair layout swept four vertically adjacent pixels at a time (das_quad_kernel)
-int launch_quads(awpu_hip *h, const float *d_frames, int batch, float *d_power, hipStream_t s, int hist_eff, int wstart_eff,
-                 const float *prepacked = nullptr, size_t prepacked_floats = 0) {
+int launch_quads(awpu_hip *h, const SweepCall &call, const float *prepacked = nullptr, size_t prepacked_floats = 0) {
     int rc = build_quad_lut(h, kQuadPairs);
     if (rc != AWPU_OK) return rc;
     const QuadTable &table = h->quad_tables[kQuadPairs];
@@ -883,14 +879,14 @@ int launch_quads(awpu_hip *h, const float *d_frames, int batch, float *d_power, 
     if (!prepacked)
         if (const int prc = ensure_pack(h, pair_pack_floats(h->cfg.max_batch, pp.usable_pad, pp.wr, 2)); prc != AWPU_OK) return prc;
     awpu::QuadArgs qa{};
-    fill_shared(qa, h, pp, batch, d_power);
+    fill_shared(qa, h, pp, call.batch, call.power);
     qa.packed = prepacked ? prepacked : h->d_pack;
     qa.lut = table.d;
     qa.wp = pp.wr;
     qa.cols = h->cfg.grid_columns;
     qa.rows = h->cfg.pixel_count / qa.cols;
     qa.tiles = awpu::quad_tiles(qa.rows, qa.cols);
-    qa.n_pairs = (batch + 1) / 2;
+    qa.n_pairs = (call.batch + 1) / 2;
     qa.pair_group = awpu::xcd_pair_group((size_t) pp.usable_pad * pp.wr * 8, qa.n_pairs, env().pair_group);
     qa.debug = env().debug;
     qa.variant = env().quad_variant;
@@ -907,27 +903,26 @@ int launch_quads(awpu_hip *h, const float *d_frames, int batch, float *d_power, 
     if (qa.debug & 16) {
         const long per_xcd = ((long) qa.n_pairs * qa.tiles + 7) / 8;
         n_waves = (size_t) 16 * 8 * (size_t) (qa.wgs > 0 ? std::min<long>(per_xcd, std::max(1, qa.wgs / 8)) : per_xcd);
-        if (rc = diag_begin(h, n_waves * 12, true, s, &qa.debug_out); rc != AWPU_OK) return rc;
+        if (rc = diag_begin(h, n_waves * 12, true, call.stream, &qa.debug_out); rc != AWPU_OK) return rc;
     }
-    if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
+    if (call.opts.timed) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, call.stream));
     if (!prepacked)
-        AWPU_HIP_TRY(awpu::launch_pack_pairs(d_frames, h->cfg.n_streams, hist_eff, wstart_eff, h->d_index, h->usable(),
-                                             pp.usable_pad, h->d_gain, pp.wr, batch, h->d_pack, true, s));
-    AWPU_HIP_TRY(awpu::launch_das_quads(qa, {table.entries, prepacked ? prepacked_floats : h->d_pack.cap}, s));
-    return diag_end(h, finish_launch(h, batch, s, AWPU_KERNEL_QUAD), n_waves, 16, "quads", s);
+        AWPU_HIP_TRY(awpu::launch_pack_pairs(call.frames, h->cfg.n_streams, call.hist_eff, call.wstart_eff, h->d_index, h->usable(),
+                                             pp.usable_pad, h->d_gain, pp.wr, call.batch, h->d_pack, true, call.stream));
+    AWPU_HIP_TRY(awpu::launch_das_quads(qa, {table.entries, prepacked ? prepacked_floats : h->d_pack.cap}, call.stream));
+    return diag_end(h, finish_launch(h, call.batch, call.stream, call.opts.timed, AWPU_KERNEL_QUAD), n_waves, 16, "quads", call.stream);
 }
 
 // quad shape for single frames on the halves layout (das_quadh_kernel): a pack + filter pre-pass, then the sweep
-int launch_quadsh(awpu_hip *h, const float *d_frames, int batch, float *d_power, hipStream_t s, int pitch, int hist_eff, int wstart_eff,
-                  int qpw) {
+int launch_quadsh(awpu_hip *h, const SweepCall &call, int qpw) {
     int rc = build_quad_lut(h, kQuadHalves);
     if (rc != AWPU_OK) return rc;
     const QuadTable &table = h->quad_tables[kQuadHalves];
     const awpu::FastPlan &pp = table.plan;
-    const size_t need = std::max((size_t) h->cfg.max_batch, (size_t) batch) * pp.usable_pad * pp.wr * 2;
+    const size_t need = std::max((size_t) h->cfg.max_batch, (size_t) call.batch) * pp.usable_pad * pp.wr * 2;
     if (const int prc = ensure_pack(h, need); prc != AWPU_OK) return prc;
     awpu::QuadhArgs qa{};
-    fill_shared(qa, h, pp, batch, d_power);
+    fill_shared(qa, h, pp, call.batch, call.power);
     qa.packed = h->d_pack;
     qa.lut = table.d;
     qa.wp = pp.wr;
@@ -936,86 +931,83 @@ int launch_quadsh(awpu_hip *h, const float *d_frames, int batch, float *d_power,
     qa.debug = env().debug;
     size_t n_waves = 0;
     if (qa.debug & 16) {
-        n_waves = (size_t) 16 * batch * awpu::quad1_tiles(qa.rows, qa.cols, qpw);
-        if (rc = diag_begin(h, n_waves * 12, false, s, &qa.debug_out); rc != AWPU_OK) return rc;
+        n_waves = (size_t) 16 * call.batch * awpu::quad1_tiles(qa.rows, qa.cols, qpw);
+        if (rc = diag_begin(h, n_waves * 12, false, call.stream, &qa.debug_out); rc != AWPU_OK) return rc;
     }
-    if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
-    AWPU_HIP_TRY(awpu::launch_pack_halves(d_frames, h->cfg.n_streams, pitch, hist_eff, wstart_eff, h->identity_mics ? nullptr : h->d_index, h->usable(),
-                                          pp.usable_pad, h->d_gain, pp.wr, batch, h->d_pack, s));
-    AWPU_HIP_TRY(awpu::launch_das_quadh(qa, qpw, {table.entries, h->d_pack.cap}, s));
-    return diag_end(h, finish_launch(h, batch, s, AWPU_KERNEL_QUADH), n_waves, 16, "quadsh", s);
+    if (call.opts.timed) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, call.stream));
+    AWPU_HIP_TRY(awpu::launch_pack_halves(call.frames, h->cfg.n_streams, call.hist_eff, call.hist_ring(), call.wstart_eff, h->identity_mics ? nullptr : h->d_index, h->usable(),
+                                          pp.usable_pad, h->d_gain, pp.wr, call.batch, h->d_pack, call.stream));
+    AWPU_HIP_TRY(awpu::launch_das_quadh(qa, qpw, {table.entries, h->d_pack.cap}, call.stream));
+    return diag_end(h, finish_launch(h, call.batch, call.stream, call.opts.timed, AWPU_KERNEL_QUADH), n_waves, 16, "quadsh", call.stream);
 }
 
 // single frames of small arrays: every mic's halves row resident, the workgroup stages the window itself (das_quadh_stationary_kernel)
-int launch_quadsh_stationary(awpu_hip *h, const float *d_frames, int batch, float *d_power, hipStream_t s, int pitch, int hist_eff,
-                             int wstart_eff, int qpw) {
+int launch_quadsh_stationary(awpu_hip *h, const SweepCall &call, int qpw) {
     int rc = build_quad_lut(h, kQuadHalvesStationary);
     if (rc != AWPU_OK) return rc;
     const QuadTable &table = h->quad_tables[kQuadHalvesStationary];
     const awpu::FastPlan &pp = table.plan;
     awpu::QuadhStationaryArgs qa{};
-    qa.frames = d_frames;
+    qa.frames = call.frames;
     qa.lut = table.d;
     qa.index = h->d_index;
     qa.gain = h->d_gain;
-    qa.power = d_power;
+    qa.power = call.power;
     qa.n_streams = h->cfg.n_streams;
-    qa.pitch = pitch;
-    qa.hist = hist_eff;
-    qa.wstart = wstart_eff;
+    qa.pitch = call.hist_eff;
+    qa.hist = call.hist_ring();
+    qa.wstart = call.wstart_eff;
     qa.usable = h->usable();
     qa.usable_pad = pp.usable_pad;
     qa.pixel_count = h->cfg.pixel_count;
     qa.wp = pp.wr;
-    qa.batch = batch;
+    qa.batch = call.batch;
     qa.cols = h->cfg.grid_columns;
     qa.rows = h->cfg.pixel_count / qa.cols;
     qa.waves = 16;
     qa.identity = h->identity_mics;
-    qa.row_limit = pitch;  // (the ring's rows are 2048 floats of which any 1024 + window are valid: double-written)
-    if (!awpu::quadh_stationary_raw(pp, qa.usable, wstart_eff, qa.row_limit, &qa.raw_begin, &qa.raw_wr, &qa.image_offset))
+    qa.row_limit = call.hist_eff;  // (the ring's rows are 2048 floats of which any 1024 + window are valid: double-written)
+    if (!awpu::quadh_stationary_raw(pp, qa.usable, call.wstart_eff, qa.row_limit, &qa.raw_begin, &qa.raw_wr, &qa.image_offset))
         return invalid("the raw window does not fit the LDS beside the halves image");  // (launch() asks before it comes here)
-    h->done_used = false;
-    if (h->done_arm && s == h->stream && qpw == 1) {  // (the one-frame host call: live_host_call)
-        if (rc = arm_done_flag(h, (unsigned long long) batch * awpu::quad1_tiles(qa.rows, qa.cols, 1), &qa.done); rc != AWPU_OK) return rc;
+    if (call.opts.flag && call.stream == h->stream && qpw == 1) {  // (the one-frame host call: live_host_call)
+        if (rc = arm_done_flag(h, (unsigned long long) call.batch * awpu::quad1_tiles(qa.rows, qa.cols, 1), &qa.done); rc != AWPU_OK) return rc;
     }
-    if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
-    AWPU_HIP_TRY(awpu::launch_das_quadh_stationary(qa, qpw, {table.entries, 0}, s));
-    if (qa.done.flag) done_flag_armed(h, qa.done);
-    return finish_launch(h, batch, s, AWPU_KERNEL_QUADH_STATIONARY);
+    if (call.opts.timed) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, call.stream));
+    AWPU_HIP_TRY(awpu::launch_das_quadh_stationary(qa, qpw, {table.entries, 0}, call.stream));
+    if (qa.done.flag) done_flag_armed(h, qa.done, call.opts.flag);
+    return finish_launch(h, call.batch, call.stream, call.opts.timed, AWPU_KERNEL_QUADH_STATIONARY);
 }
 
 // single frames, whatever the table says: the 8-wave shape, or the double-buffered 16-wave one (das_fast_kernel / das_fast_db_kernel)
-int launch_single(awpu_hip *h, const float *d_frames, int batch, float *d_power, hipStream_t s, int layout, int hist_eff, int wstart_eff,
-                  int fpi, int ppw, int nw) {
+int launch_single(awpu_hip *h, const SweepCall &call, int fpi, int ppw, int nw) {
     const awpu_hip::FastLut *lut = nullptr;
     int rc = build_fast_lut(h, awpu::PackLayout::kSingle, fpi, awpu::fast_image_bytes(nw), &lut);
     if (rc != AWPU_OK) return rc;
     const awpu::FastPlan &plan = lut->plan;
     awpu::FastArgs a{};
-    fill_shared(a, h, plan, batch, d_power);
-    a.frames = d_frames;
+    fill_shared(a, h, plan, call.batch, call.power);
+    a.frames = call.frames;
     a.lut = lut->d;
     a.index = h->d_index;
-    a.row_off = layout == kCompact ? h->d_row_off_compact : (layout == kRing ? h->d_row_off_ring : h->d_row_off);
+    a.row_off = call.layout == kCompact ? h->d_row_off_compact : (call.layout == kRing ? h->d_row_off_ring : h->d_row_off);
     a.n_streams = h->cfg.n_streams;
-    a.hist = hist_eff;
-    a.wstart = wstart_eff;
+    a.hist = call.hist_eff;
+    a.wstart = call.wstart_eff;
     a.wr = plan.wr;
     // frames per persistent workgroup: measured, persistence over frames buys nothing
-    a.frames_per_wg = std::min(env().fpw > 0 ? env().fpw : 1, batch);
+    a.frames_per_wg = std::min(env().fpw > 0 ? env().fpw : 1, call.batch);
     a.debug = env().debug;
     size_t n_waves = 0;
     const int wg_waves = nw == 24 ? 12 : 16;
     if ((a.debug & 16) && nw != 8) {  // the double-buffered shapes have a stamped build
-        n_waves = (size_t) wg_waves * ((batch + a.frames_per_wg - 1) / a.frames_per_wg) *
+        n_waves = (size_t) wg_waves * ((call.batch + a.frames_per_wg - 1) / a.frames_per_wg) *
                   ((h->cfg.pixel_count + wg_waves * ppw - 1) / (wg_waves * ppw));
-        if (rc = diag_begin(h, n_waves * 12, false, s, &a.debug_out); rc != AWPU_OK) return rc;
+        if (rc = diag_begin(h, n_waves * 12, false, call.stream, &a.debug_out); rc != AWPU_OK) return rc;
     }
-    if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
-    AWPU_HIP_TRY(awpu::launch_das_fast(a, fpi, ppw, nw, {lut->entries, 0}, s));
+    if (call.opts.timed) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, call.stream));
+    AWPU_HIP_TRY(awpu::launch_das_fast(a, fpi, ppw, nw, {lut->entries, 0}, call.stream));
     const int id = nw == 32 ? AWPU_KERNEL_SINGLE_DB : (nw == 8 && fpi == 1 && ppw <= 4 ? AWPU_KERNEL_SINGLE_SMALL : AWPU_KERNEL_TUNING);
-    return diag_end(h, finish_launch(h, batch, s, id), n_waves, wg_waves, "single", s);
+    return diag_end(h, finish_launch(h, call.batch, call.stream, call.opts.timed, id), n_waves, wg_waves, "single", call.stream);
 }
 
 // ---- the dispatch rule.  Its predicates first: launch() and the packed-frame entry points ask the same ones.
@@ -1050,7 +1042,7 @@ struct ShapeChoice {
 };
 
 // Which kernel sweeps `batch` frames of `layout`?  Decides only: no table is built, and the device is asked nothing but its CU count.
-ShapeChoice choose_shape(awpu_hip *h, int batch, int layout, int hist_eff, int wstart_eff) {
+ShapeChoice choose_shape(awpu_hip *h, int batch, int layout, int hist_eff, int wstart_eff, const float *sums) {
     const auto &c = h->cfg;
     const int U = h->usable(), P = c.pixel_count, cols = c.grid_columns;
     const int rows = cols >= 1 ? P / cols : 0;
@@ -1093,7 +1085,7 @@ ShapeChoice choose_shape(awpu_hip *h, int batch, int layout, int hist_eff, int w
         return {kShapeExactPairs};
     }
     // (the pre-epilogue sums: the frame-pair reference-order kernels above and das_fir8_kernel with the reference's rounding only)
-    if (h->sums_out && !(c.math == AWPU_MATH_F32_EXACT && c.interp == AWPU_INTERP_FIR8)) return {kShapeNone};
+    if (sums && !(c.math == AWPU_MATH_F32_EXACT && c.interp == AWPU_INTERP_FIR8)) return {kShapeNone};
     if (c.math != AWPU_MATH_F32_FAST || c.interp == AWPU_INTERP_FIR8) return {kShapeExact};
 
     // ---- frame-pair shapes: batches on grids that fill the chip (AWPU_FAST_PAIRS=0/1 overrides), never off the ring
@@ -1158,30 +1150,29 @@ ShapeChoice choose_shape(awpu_hip *h, int batch, int layout, int hist_eff, int w
 
 namespace awpu::host {
 
-int launch(awpu_hip *h, const float *d_frames, int batch, float *d_power, hipStream_t s, int layout) {
+int launch(awpu_hip *h, const float *d_frames, int batch, float *d_power, hipStream_t s, int layout, const SweepOpts &o) {
     const int hist_eff = layout == kCompact ? h->compact_hist : (layout == kRing ? 2048 : h->cfg.hist);
-    const int wstart_eff = layout == kCompact ? 0 : h->wstart;
-    const int hist_ring = layout == kRing ? AWPU_HIST : hist_eff;  // the history a stream of the ring offers a filter (its rows are 2048 floats apart)
-    const ShapeChoice c = choose_shape(h, batch, layout, hist_eff, wstart_eff);
+    const SweepCall call{d_frames, batch, d_power, s, layout, hist_eff, layout == kCompact ? 0 : h->wstart, o};
+    const ShapeChoice c = choose_shape(h, batch, layout, hist_eff, call.wstart_eff, o.sums);
     const awpu_hip::FastLut *lut = nullptr;
     switch (c.shape) {
-    case kShapeFir8Planes: return launch_fir8_planes(h, d_frames, batch, d_power, s, hist_eff, wstart_eff);
-    case kShapeExactNdp: return launch_exact_ndh(h, d_frames, batch, d_power, s, hist_eff, wstart_eff, false, 1, true);
-    case kShapeExactNdh: return launch_exact_ndh(h, d_frames, batch, d_power, s, hist_eff, wstart_eff, c.stationary, c.nq);
-    case kShapeExactNd: return launch_exact_nd(h, d_frames, batch, d_power, s, hist_eff, wstart_eff, c.nq);
-    case kShapeExactQuads: return launch_exact_quads(h, d_frames, batch, d_power, s, hist_eff, wstart_eff);
-    case kShapeExactPairs: return launch_exact_pairs(h, d_frames, batch, d_power, s, hist_eff, wstart_eff);
-    case kShapeExact: return launch_exact(h, d_frames, batch, d_power, s, hist_eff, wstart_eff);
-    case kShapeQuads: return launch_quads(h, d_frames, batch, d_power, s, hist_eff, wstart_eff);
+    case kShapeFir8Planes: return launch_fir8_planes(h, call);
+    case kShapeExactNdp: return launch_exact_ndh(h, call, false, 1, true);
+    case kShapeExactNdh: return launch_exact_ndh(h, call, c.stationary, c.nq);
+    case kShapeExactNd: return launch_exact_nd(h, call, c.nq);
+    case kShapeExactQuads: return launch_exact_quads(h, call);
+    case kShapeExactPairs: return launch_exact_pairs(h, call);
+    case kShapeExact: return launch_exact(h, call);
+    case kShapeQuads: return launch_quads(h, call);
     case kShapePairsStationary:
         if (const int rc = build_fast_lut(h, awpu::PackLayout::kPairsStationary, 2, 0, &lut); rc != AWPU_OK) return rc;
-        return launch_pairs(h, lut, d_frames, batch, d_power, s, hist_eff, wstart_eff, c.tiles_per_wg);
+        return launch_pairs(h, lut, call, c.tiles_per_wg);
     case kShapePairs:
         if (const int rc = build_fast_lut(h, awpu::PackLayout::kPairs, 2, 0, &lut); rc != AWPU_OK) return rc;
-        return launch_pairs(h, lut, d_frames, batch, d_power, s, hist_eff, wstart_eff);
-    case kShapeQuadsh: return launch_quadsh(h, d_frames, batch, d_power, s, hist_eff, hist_ring, wstart_eff, c.qpw);
-    case kShapeQuadshStationary: return launch_quadsh_stationary(h, d_frames, batch, d_power, s, hist_eff, hist_ring, wstart_eff, c.qpw);
-    case kShapeSingle: return launch_single(h, d_frames, batch, d_power, s, layout, hist_eff, wstart_eff, c.fpi, c.ppw, c.nw);
+        return launch_pairs(h, lut, call);
+    case kShapeQuadsh: return launch_quadsh(h, call, c.qpw);
+    case kShapeQuadshStationary: return launch_quadsh_stationary(h, call, c.qpw);
+    case kShapeSingle: return launch_single(h, call, c.fpi, c.ppw, c.nw);
     case kShapeNone: break;
     }
     return fail(AWPU_ERR_STATE, "the pre-epilogue sums are exported by the frame-pair reference-order kernels and the reference-rounding FIR8 kernel only");
@@ -1213,7 +1204,7 @@ int ensure_cohere_table(awpu_hip *h) {
 // launch() takes (kFull, kCompact), whatever cfg.math is -- the rule has one arithmetic.  Its table is d_lut where prepare() built
 // it (every mode but AWPU_MATH_F32_FAST), else the same entries in d_cohere_lut (ensure_cohere_table).  Each output or null;
 // counted and timed like any sweep launch.  Nothing here waits for the device.
-int launch_cohere(awpu_hip *h, const float *d_frames, int batch, const CohereOut &out, hipStream_t s, int layout) {
+int launch_cohere(awpu_hip *h, const float *d_frames, int batch, const CohereOut &out, hipStream_t s, int layout, bool timed) {
     if (h->cfg.interp != AWPU_INTERP_LERP) return fail(AWPU_ERR_STATE, "the coherence sweep interpolates linearly: AWPU_INTERP_FIR8 is not taken");
     if (layout != kFull && layout != kCompact) return invalid("the coherence sweep takes whole frames or uploaded windows");
     const int U = h->usable(), P = h->cfg.pixel_count;
@@ -1236,9 +1227,9 @@ int launch_cohere(awpu_hip *h, const float *d_frames, int batch, const CohereOut
     a.coherence = out.coherence;
     a.weighted = out.weighted;
     a.energy = out.energy;
-    if (h->timing) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
+    if (timed) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
     AWPU_HIP_TRY(awpu::launch_cohere_sweep(a, s));
-    return finish_launch(h, batch, s, AWPU_KERNEL_COHERE);
+    return finish_launch(h, batch, s, timed, AWPU_KERNEL_COHERE);
 }
 
 // Would launch() sweep this batch with one of the frame-pair shapes that read the packed layout (quad or pair)?  The rule of
@@ -1279,17 +1270,17 @@ int pack_for_sweep(awpu_hip *h, const awpu::FastPlan &plan, const float *d_frame
 // never the stationary shape (it stages from the frames), and the quad shape only where its rows are the packed plan's.
 int sweep_packed(awpu_hip *h, const awpu::FastPlan &plan, const float *d_packed, size_t packed_floats, int batch, float *d_power,
                  hipStream_t s) {
+    const SweepCall call{nullptr, batch, d_power, s, kFull, h->cfg.hist, h->wstart, {}};  // (every caller is asynchronous: untimed)
     if (h->cfg.math == AWPU_MATH_F32_EXACT) {
         int nq = 1;
         if (!takes_exact_nd(h, batch, &nq)) return fail(AWPU_ERR_STATE, "packed frames: this batch is not swept by the {next, d} kernel");
-        return launch_exact_nd(h, nullptr, batch, d_power, s, h->cfg.hist, h->wstart, nq, d_packed, packed_floats);
+        return launch_exact_nd(h, call, nq, d_packed, packed_floats);
     }
-    if (fast_batch_takes_quads(h, batch) && quad_plan_is(h, plan))
-        return launch_quads(h, nullptr, batch, d_power, s, h->cfg.hist, h->wstart, d_packed, packed_floats);
+    if (fast_batch_takes_quads(h, batch) && quad_plan_is(h, plan)) return launch_quads(h, call, d_packed, packed_floats);
     const awpu_hip::FastLut *plut = nullptr;
     const int rc = build_fast_lut(h, awpu::PackLayout::kPairs, 2, 0, &plut);
     if (rc != AWPU_OK) return rc;
-    return launch_pairs(h, plut, nullptr, batch, d_power, s, h->cfg.hist, h->wstart, 0, d_packed, packed_floats);
+    return launch_pairs(h, plut, call, 0, d_packed, packed_floats);
 }
 
 // The layout both frame-pair shapes read when usable is a multiple of four and no gains are set:
