@@ -10,20 +10,15 @@ HIPCC ?= /opt/rocm/bin/hipcc
 PKG := beamforming-lk_amd
 CSRC := $(PKG)/csrc
 LIB := $(PKG)/libawpu_hip.so
-KERNEL_SRC := $(CSRC)/das_kernels.hip $(CSRC)/das_fast.hip $(CSRC)/track_kernels.hip $(CSRC)/block_kernels.hip $(CSRC)/watch_kernels.hip $(CSRC)/find_kernels.hip $(CSRC)/band_kernels.hip $(CSRC)/spectral_kernels.hip $(CSRC)/expose_kernels.hip $(CSRC)/cohere_kernels.hip $(CSRC)/peel_kernels.hip $(CSRC)/awpu_hip.cpp \
-              $(CSRC)/awpu_group.cpp $(CSRC)/awpu_sweep.cpp $(CSRC)/awpu_runs.cpp $(CSRC)/geometry_host.cpp $(CSRC)/find_host.cpp $(CSRC)/band_host.cpp $(CSRC)/spectral_host.cpp $(CSRC)/awpu_focus.cpp $(CSRC)/expose_host.cpp $(CSRC)/awpu_cohere.cpp $(CSRC)/cohere_host.cpp $(CSRC)/awpu_peel.cpp $(CSRC)/peel_host.cpp
 HOST_SRC := $(PKG)/host/mimo_worker_hip.cpp $(PKG)/host/aw_processing_unit_hip.cpp $(PKG)/host/pipeline_hip.cpp \
             $(PKG)/host/aw_processing_unit.cpp $(PKG)/host/spherical_gradient_hip.cpp
 # OPENCV_CFLAGS: where <opencv2/core.hpp> lives; defaults to the tests' few-line stand-in for cv::Mat (no OpenCV here)
 OPENCV_CFLAGS ?= -Itests/host/mock_opencv
 
 .PHONY: lib oracle host-test example trips clean
-lib: $(LIB)
-
-$(LIB): $(KERNEL_SRC) $(CSRC)/awpu_handle.h $(CSRC)/das_kernels.h $(CSRC)/sweep_plan.h $(CSRC)/nd_tile_window.h $(CSRC)/block_kernels.h $(CSRC)/watch_kernels.h $(CSRC)/find_kernels.h $(CSRC)/find_rule.h $(CSRC)/band_kernels.h $(CSRC)/band_rule.h $(CSRC)/spectral_kernels.h $(CSRC)/spectral_rule.h $(CSRC)/expose_kernels.h $(CSRC)/expose_rule.h $(CSRC)/cohere_kernels.h $(CSRC)/cohere_rule.h $(CSRC)/peel_kernels.h $(CSRC)/peel_rule.h $(CSRC)/das_fast_trip.inc include/awpu_hip.h include/awpu_hip_track.h \
-        include/awpu_hip_blocks.h include/awpu_hip_listen.h include/awpu_hip_watch.h include/awpu_hip_find.h include/awpu_hip_band.h include/awpu_hip_spectral.h include/awpu_hip_expose.h include/awpu_hip_cohere.h include/awpu_hip_peel.h
-	$(HIPCC) --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -Wall -Wno-unused-result -Werror=inline-asm -x hip \
-	    -Iinclude -I$(CSRC) $(KERNEL_SRC) -o $@
+# the recipe -- sources, headers, flags -- is $(PKG)/_build.py's alone; it rebuilds only a library older than one of them
+lib:
+	HIPCC=$(HIPCC) python3 $(PKG)/_build.py --out $(LIB)
 
 # the hand-scheduled inner loops are GENERATED at build time (tools/gen_trip_asm.py documents the schedule and its knobs;
 # the include is not tracked)
@@ -35,7 +30,7 @@ trips: $(CSRC)/das_fast_trip.inc
 oracle:
 	$(MAKE) -C oracle
 
-host-test: $(LIB) oracle
+host-test: lib oracle
 	g++ -O2 -std=c++17 -pthread -Iinclude -I$(PKG)/host -Ioracle tests/host/test_mimo_worker.cpp $(HOST_SRC) \
 	    -L$(PKG) -lawpu_hip -Loracle -loracle_das -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -Wl,-rpath,'$$ORIGIN/../../oracle' -Wl,-rpath,/opt/rocm/lib \
 	    -o tests/host/test_mimo_worker
@@ -46,7 +41,7 @@ host-test: $(LIB) oracle
 	    $(PKG)/host/spherical_gradient_hip.cpp -L$(PKG) -lawpu_hip -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN/../../$(PKG)' \
 	    -Wl,-rpath,/opt/rocm/lib -o tests/host/test_spherical_gradient
 
-example: $(LIB)
+example: lib
 	gcc -O2 -Wall -Iinclude examples/heatmap_min.c -L$(PKG) -lawpu_hip -lm -Wl,-rpath,'$$ORIGIN/../$(PKG)' \
 	    -Wl,-rpath,/opt/rocm/lib -o examples/heatmap_min
 	gcc -O2 -Wall -Iinclude examples/live_call_rate.c -L$(PKG) -lawpu_hip -lm -Wl,-rpath,'$$ORIGIN/../$(PKG)' \

@@ -405,6 +405,10 @@ _PEEL_SIGNATURES = {
 }
 PEEL_SYMBOLS = tuple(_PEEL_SIGNATURES)
 
+# every table above, one per public header: what load() sets the types of
+_ALL_SIGNATURES = (_SIGNATURES, _TRACK_SIGNATURES, _BLOCK_SIGNATURES, _LISTEN_SIGNATURES, _WATCH_SIGNATURES, _FIND_SIGNATURES, _BAND_SIGNATURES,
+                   _FOCUS_SIGNATURES, _SPECTRAL_SIGNATURES, _EXPOSE_SIGNATURES, _COHERE_SIGNATURES, _PEEL_SIGNATURES)
+
 # numpy view of awpu_range_t: what range_pick, Engine.range and Engine.locate_* return (unused entries: index -1)
 RANGE_DTYPE = np.dtype([("index", "<i4"), ("power", "<f4"), ("distance", "<f8")], align=True)
 assert RANGE_DTYPE.itemsize == C.sizeof(Range) == 16
@@ -440,13 +444,11 @@ def load(build: bool = True) -> C.CDLL:
     if not path.exists():
         raise RuntimeError(f"{path} is missing and there is no CPU fallback")
     lib = C.CDLL(str(path))
-    for name, (res, args) in list(_SIGNATURES.items()) + list(_TRACK_SIGNATURES.items()) + list(_BLOCK_SIGNATURES.items()) + \
-            list(_LISTEN_SIGNATURES.items()) + list(_WATCH_SIGNATURES.items()) + list(_FIND_SIGNATURES.items()) + list(_BAND_SIGNATURES.items()) + \
-            list(_FOCUS_SIGNATURES.items()) + list(_SPECTRAL_SIGNATURES.items()) + list(_EXPOSE_SIGNATURES.items()) + \
-            list(_COHERE_SIGNATURES.items()) + list(_PEEL_SIGNATURES.items()):
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
+    for table in _ALL_SIGNATURES:
+        for name, (res, args) in table.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
     _lib = lib
     return lib
 

@@ -1,11 +1,12 @@
 // awpu_handle.h -- internal to libawpu_hip.so: the handle, the owner types of what it holds on the device, the error helpers, and
-// what its seven host files call in one another: awpu_hip.cpp (the C ABI and its call paths), awpu_group.cpp (the device group),
-// awpu_sweep.cpp (tables, launchers, dispatch), awpu_runs.cpp (the runs of blocks), awpu_cohere.cpp (coherence calls), awpu_peel.cpp
-// (the peeling loop) and awpu_focus.cpp (candidate distances).  Nothing here is part of the C ABI.
+// what its host files call in one another: awpu_hip.cpp (the C ABI and its call paths), awpu_group.cpp (the device group),
+// awpu_sweep.cpp (tables, launchers, dispatch), awpu_focus.cpp (candidate distances), and the runs of blocks: run_pieces.cpp (the
+// pipeline; run_pieces.h), watch_run.cpp (the display step; watch_run.h), awpu_runs.cpp (blocks, listen, watch, find, locate) and one
+// file per feature with all of its calls -- awpu_spectral.cpp, awpu_expose.cpp, awpu_cohere.cpp, awpu_peel.cpp.  Nothing here is
+// part of the C ABI.
 #pragma once
 
 #include "awpu_hip.h"
-#include "awpu_hip_peel.h"
 #include "awpu_hip_spectral.h"
 #include "awpu_hip_track.h"
 
@@ -347,7 +348,7 @@ struct awpu_hip {
     awpu::host::Group group;
     awpu::host::GroupMember member;
     // a second stream for uploads that run beside the sweeps, and "upload b is over": shared by the pieces of a host batch
-    // (enqueue_host_process), the runs of blocks (awpu_runs.cpp) and a part's receive buffers, which is why they live here
+    // (enqueue_host_process), the runs of blocks (run_pieces.cpp) and a part's receive buffers, which is why they live here
     // and not in `member`.  Created at first use; a part's at its creation
     Stream copy_stream;
     Event ev_copied[2];
@@ -357,7 +358,7 @@ struct awpu_hip {
     // event that takes the next call's stream behind it where that is another stream
     hipStream_t last_stream = nullptr;
     Event ev_order;
-    // runs of blocks (awpu_runs.cpp), by piece: piece i's history [n_streams][768 + 256 * piece] in blk_hist.d[i & 1], its windows
+    // runs of blocks (run_pieces.cpp), by piece: piece i's history [n_streams][768 + 256 * piece] in blk_hist.d[i & 1], its windows
     // in d_blk_frames; the host forms stage piece i's input in pinned blk_in.h[i & 1], upload it to blk_in.d[i & 1] on copy_stream
     // and bring its powers back through pinned blk_out.h[i & 1]
     awpu::host::BufferPair blk_hist, blk_in, blk_out;
@@ -377,7 +378,7 @@ struct awpu_hip {
 
     // watching such runs (awpu_hip_watch.h), exposed and coherence runs alike: piece i's peaks, compact images and (host forms)
     // large images in watch.d[i & 1]; the host forms bring the images back through pinned watch.h[i & 1].  Laid out by the display
-    // step alone (struct Display in awpu_runs.cpp).  The events are those of the runs above: ev_blk_swept[b] is recorded behind the
+    // step alone (struct Display in watch_run.h).  The events are those of the runs above: ev_blk_swept[b] is recorded behind the
     // display kernels, ev_blk_out[b] behind the images' way back.
     awpu::host::BufferPair watch;
     // finding in such runs (awpu_hip_find.h), host forms: piece i's counts, then its sources, in find_out.d[i & 1] and back through
@@ -400,7 +401,7 @@ struct awpu_hip {
     unsigned long long peel_gen = 0;
     Dev<float> d_peel_frames, d_peel_power;
     Dev<unsigned char> d_peel_state, d_peel_out;
-    awpu::host::BufferPair peel_steps;  // peel runs (awpu_runs.cpp), host forms: piece i's steps in peel_steps.d[i & 1], back through pinned .h[i & 1]
+    awpu::host::BufferPair peel_steps;  // peel runs, host forms: piece i's steps in peel_steps.d[i & 1], back through pinned .h[i & 1]
 
     // the band (awpu_hip_band.h): its coefficients (empty = none; they travel to the pre-pass as kernel arguments), and the
     // filtered frames of a call whose own frames are the caller's or the ring's, in those frames' layout (band_sweep): a plane
@@ -517,14 +518,6 @@ struct CohereOut {
 };
 int ensure_cohere_table(awpu_hip *h);  // behind check_ready, before the call enqueues anything: the one step that may block
 int launch_cohere(awpu_hip *h, const float *d_frames, int batch, const CohereOut &out, hipStream_t s, int layout, bool timed = false);
-// peeling (awpu_hip_peel.h): defined, and described, in awpu_peel.cpp; the runs of blocks (awpu_runs.cpp) peel their pieces through these
-struct PeelOut {  // what a loop writes, device memory, each or null: steps [batch][pe.steps]; clean, residual, map [batch][pixel_count]
-    awpu_peel_step_t *steps = nullptr;
-    float *clean = nullptr, *residual = nullptr, *map = nullptr;
-};
-int peel_handle_refusal(awpu_hip *h);    // the AWPU_ERR_STATE refusals that read the handle's configuration alone
-int peel_prepare(awpu_hip *h, int batch);  // behind check_ready, before anything is enqueued: all of a loop that may block
-int peel_enqueue(awpu_hip *h, float *work, int batch, const awpu_peel_t &pe, const PeelOut &out, hipStream_t s);  // (untimed: several sweeps)
 bool takes_packed_pairs(awpu_hip *h, int batch, awpu::FastPlan *plan);
 int packed_shape(awpu_hip *h, int batch, awpu::FastPlan *plan);
 size_t packed_floats_of(const awpu_hip *h, const awpu::FastPlan &plan, int batch);
@@ -558,7 +551,6 @@ inline int band_sweep(awpu_hip *h, const float *in, long long in_frame, long lon
                       const SweepOpts &o = {}) {
     return band_sweep(h, own_band(h), in, in_frame, in_row, in_lo, batch, d_power, 0, s, layout, o);  // the handle's own band: the one-band case
 }
-int check_spectral(awpu_hip *h, const awpu_spectral_t *sp, BandSet *bands);  // a spectral call's bands, or why the handle does not take them
 
 // A buffer whose pointer the captured live-block graphs bake in (d_power, d_pack, d_display): they are retired before the old pointer
 // goes.  (prepare() and ensure_taps() retire for the tables and d_taps; launch_exact_nd for d_nd_items, a synchronize before it grows.)

@@ -1,6 +1,6 @@
 // awpu_hip.cpp -- the C ABI of libawpu_hip.so (include/awpu_hip.h) and its call paths: handle lifetime, setters, frame upload,
 // the single-call paths, the ring, display, tracking, the packed-frame entry points and the band in front of the sweeps.  The tables, the kernel launchers and
-// the dispatch rule are the sweep layer (awpu_sweep.cpp); the runs of blocks are awpu_runs.cpp; a device group's handle is
+// the dispatch rule are the sweep layer (awpu_sweep.cpp); the runs of blocks are run_pieces.cpp and the files on it; a device group's handle is
 // handed over to awpu_group.cpp.  No CPU fallback: every compute entry point ends in a gfx950 kernel launch or an error status.
 #include "awpu_handle.h"
 
@@ -18,7 +18,6 @@
 #include "band_kernels.h"
 #include "band_rule.h"
 #include "spectral_kernels.h"
-#include "spectral_rule.h"
 #include "das_kernels.h"
 #include "focus_rule.h"
 #include "watch_kernels.h"
@@ -315,19 +314,6 @@ int band_sweep(awpu_hip *h, const BandSet &bands, const float *in, long long in_
     return rc;
 }
 
-// The refusals of a spectral call (awpu_hip_spectral.h) that read the handle, in the header's order, and its bands as a set.  (The
-// missing table and the history rule come from check_ready and the caller: they need the prepared handle.)
-int check_spectral(awpu_hip *h, const awpu_spectral_t *sp, BandSet *bands) {
-    if (!h) return invalid("null handle");
-    if (const char *why = awpu::spectral_refusal(sp)) return invalid(why);
-    if (is_group(h)) return fail(AWPU_ERR_STATE, "a device group takes no bands");
-    if (h->in_flight) return fail(AWPU_ERR_STATE, "an awpu_hip_process_async call is in flight on this handle: awpu_hip_wait first");
-    if (!h->band.empty()) return fail(AWPU_ERR_STATE, "the handle has a band of its own: clear it (awpu_hip_set_band) before a spectral call");
-    bands->n = sp->n_bands;
-    for (int b = 0; b < sp->n_bands; b++) bands->taps[b] = sp->taps[b], bands->coef[b] = sp->coef[b];
-    return AWPU_OK;
-}
-
 }  // namespace awpu::host
 
 namespace {
@@ -453,7 +439,7 @@ int awpu::host::wait_and_time(awpu_hip *h, bool timed) {
     return AWPU_OK;
 }
 
-// what the runs of blocks (awpu_runs.cpp) share with the calls below
+// what the runs of blocks (run_pieces.cpp) share with the calls below
 namespace awpu::host {
 
 size_t align16(size_t n) { return (n + 15) & ~(size_t) 15; }
@@ -1009,36 +995,6 @@ int awpu_hip_process_device(awpu_hip_t *h, const float *d_frames, int32_t batch,
     if (rc == AWPU_OK) rc = enter_stream(h, s);
     if (rc != AWPU_OK) return rc;
     return band_sweep(h, d_frames, (long long) h->cfg.n_streams * h->cfg.hist, h->cfg.hist, h->wstart, batch, d_power, s, kFull);
-}
-
-int awpu_hip_process_bands(awpu_hip_t *h, const float *frames, int32_t batch, const awpu_spectral_t *sp, float *power) {
-    AWPU_CTX(h);
-    if (!h) return invalid("null handle");
-    if (!frames || !power) return invalid("null argument");
-    BandSet bands;
-    int rc = check_spectral(h, sp, &bands);
-    if (rc != AWPU_OK) return rc;
-    rc = enqueue_host_process(h, frames, batch, &bands);
-    if (rc != AWPU_OK) return rc;
-    rc = enqueue_power_to_host(h, batch * bands.n, power, (size_t) h->cfg.pixel_count);
-    if (rc != AWPU_OK) return rc;
-    return wait_and_time(h, true);
-}
-
-int awpu_hip_process_bands_device(awpu_hip_t *h, const float *d_frames, int32_t batch, const awpu_spectral_t *sp, float *d_power, void *stream) {
-    AWPU_CTX(h);
-    if (!h) return invalid("null handle");
-    if (!d_frames || !d_power) return invalid("null argument");
-    BandSet bands;
-    int rc = check_spectral(h, sp, &bands);
-    if (rc != AWPU_OK) return rc;
-    rc = check_ready(h, batch);
-    if (rc != AWPU_OK) return rc;
-    if (bands.max_taps() - 1 > h->wstart) return fail(AWPU_ERR_RANGE, kBandHistory);
-    hipStream_t s = stream_of(h, stream);
-    if (rc = enter_stream(h, s); rc != AWPU_OK) return rc;
-    return band_sweep(h, bands, d_frames, (long long) h->cfg.n_streams * h->cfg.hist, h->cfg.hist, h->wstart, batch, d_power,
-                      (long long) batch * h->cfg.pixel_count, s, kFull);
 }
 
 int awpu_hip_process_device_sums(awpu_hip_t *h, const float *d_frames, int32_t batch, float *d_power, float *d_sums, void *stream) {

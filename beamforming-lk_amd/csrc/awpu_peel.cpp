@@ -1,8 +1,9 @@
 // awpu_peel.cpp -- the handle forms of peeling (include/awpu_hip_peel.h): awpu_hip_peel_step_device, awpu_hip_peel and
 // awpu_hip_peel_device.  The rule is peel_rule.h's, the kernels peel_kernels.hip's; the loop's sweeps are the handle's own
 // launch() (awpu_sweep.cpp), the step's table the coherence sweep's (ensure_cohere_table).  Nothing in the loop waits for the
-// device: picks, stop tests and records stay there (PeelState).
-#include "awpu_handle.h"
+// device: picks, stop tests and records stay there (PeelState).  And the peel runs of blocks, watch runs (watch_run.h) whose
+// pieces go through the same loop.
+#include "watch_run.h"
 
 #include "awpu_hip_peel.h"
 #include "peel_kernels.h"
@@ -10,7 +11,12 @@
 
 using namespace awpu::host;
 
-namespace awpu::host {
+namespace {
+
+struct PeelOut {  // what a loop writes, device memory, each or null: steps [batch][pe.steps]; clean, residual, map [batch][pixel_count]
+    awpu_peel_step_t *steps = nullptr;
+    float *clean = nullptr, *residual = nullptr, *map = nullptr;
+};
 
 // the refusals of a handle that come before it is made ready (awpu_hip_peel.h)
 int peel_handle_refusal(awpu_hip *h) {
@@ -21,10 +27,6 @@ int peel_handle_refusal(awpu_hip *h) {
     if (!h->band.empty()) return fail(AWPU_ERR_STATE, "a handle with a band takes no peel: the step reads outside the window the band's pre-pass writes");
     return AWPU_OK;
 }
-
-}  // namespace awpu::host
-
-namespace {
 
 int check_peel(awpu_hip *h, const void *frames) {
     if (!h) return invalid("null handle");
@@ -69,10 +71,6 @@ void set_u(const awpu_hip *h, float loop_gain, awpu::PeelArgs *a) {
     for (int s = 0; s < a->usable; s++) a->u[s] = awpu::peel_u(loop_gain, g.empty() ? nullptr : g.data(), s);
 }
 
-}  // namespace
-
-namespace awpu::host {
-
 // Everything of a loop that may block -- the checks of peel_args, the table, the loop's own buffers for `batch` frames --, on a
 // handle that check_ready has made ready and before the call enqueues anything
 int peel_prepare(awpu_hip *h, int batch) {
@@ -103,7 +101,59 @@ int peel_enqueue(awpu_hip *h, float *work, int batch, const awpu_peel_t &pe, con
     return AWPU_OK;
 }
 
-}  // namespace awpu::host
+// ---- peel runs (awpu_hip_peel.h) ----------------------------------------------------------------------------------------------------
+// A watch run whose pieces are peeled (peel_enqueue) in place of swept: a piece's snapshots are cut whole -- the step reads E + 1
+// samples either side of the window -- into d_blk_frames, which the loop then turns into the residual, and the row a frame shows
+// -- and everything behind it -- is its map, clean or residual row.  The steps go to the caller's array (device form) or come back
+// with the piece's images through peel_steps (host forms).  Pieces, histories, the ring: the watch run's.
+struct PeelPieces final : WatchPieces {
+    const awpu_peel_t pe;
+    const int show_row;
+    awpu_peel_step_t *const steps;  // [n_frames][pe.steps], host or device memory as the run's other outputs, or null
+    PeelPieces(awpu_hip *h_, const BlockRun &src_, int n_blocks_, const WatchRun &wr_, const awpu_peel_t &pe_, int show_, awpu_peel_step_t *steps_)
+        : WatchPieces(h_, src_, n_blocks_, wr_), pe(pe_), show_row(show_), steps(steps_) {
+        whole_frames = true;
+    }
+    size_t step_bytes(int n) const { return (size_t) n * pe.steps * sizeof(awpu_peel_step_t); }
+    int check() override {
+        const int rc = peel_handle_refusal(h);
+        return rc != AWPU_OK ? rc : WatchPieces::check();
+    }
+    int ensure(int piece_max, int lo_, int width_, hipStream_t sw) override {  // (the handle is ready; none of the run's work is enqueued yet)
+        int rc = peel_prepare(h, piece_max);
+        if (rc == AWPU_OK && host && steps) rc = h->peel_steps.ensure(step_bytes(piece_max), true);
+        return rc != AWPU_OK ? rc : WatchPieces::ensure(piece_max, lo_, width_, sw);
+    }
+    int sweep_frames(awpu_hip *, const Piece &p, const float *d_frames, float *d_pow, hipStream_t s, int layout) override {
+        if (layout != kFull) return fail(AWPU_ERR_STATE, "a peel run cuts its snapshots whole");
+        PeelOut out;
+        (show_row == AWPU_PEEL_CLEAN ? out.clean : show_row == AWPU_PEEL_RESIDUAL ? out.residual : out.map) = d_pow;
+        if (steps) out.steps = host ? reinterpret_cast<awpu_peel_step_t *>(h->peel_steps.d[p.b].get()) : steps + (size_t) p.first * pe.steps;
+        return peel_enqueue(h, const_cast<float *>(d_frames), p.n, pe, out, s);  // (d_blk_frames: the run's own scratch, cut anew for every piece)
+    }
+    int fetch_shown(const Piece &p, hipStream_t s) override {
+        if (steps) AWPU_HIP_TRY(hipMemcpyAsync(h->peel_steps.h[p.b], h->peel_steps.d[p.b], step_bytes(p.n), hipMemcpyDeviceToHost, s));
+        return WatchPieces::fetch_shown(p, s);
+    }
+    int deliver_shown(const Piece &p) override {
+        if (steps) std::memcpy(steps + (size_t) p.first * pe.steps, h->peel_steps.h[p.b], step_bytes(p.n));
+        return WatchPieces::deliver_shown(p);
+    }
+};
+
+// the checks of a peel run that read no handle; then the run
+int peel_run(awpu_hip *h, const BlockRun &src, int n_blocks, const awpu_watch_t *w, const awpu_peel_t *pe, int32_t show, const awpu_find_t *f,
+             uint8_t *image, uint8_t *big, float *power, awpu_peel_step_t *steps, awpu_source_t *sources, int32_t *count, hipStream_t user) {
+    ShownRun sr;
+    const bool shows = show == AWPU_PEEL_MAP || show == AWPU_PEEL_CLEAN || show == AWPU_PEEL_RESIDUAL;
+    const auto refusal = [&] { const char *why = awpu::peel_refusal(pe); return why || shows ? why : "show is AWPU_PEEL_MAP, AWPU_PEEL_CLEAN or AWPU_PEEL_RESIDUAL"; };
+    if (const int rc = sr.open(w, n_blocks, refusal, f, image, big, power, sources, count, steps != nullptr)) return rc;
+    AWPU_CTX(h);
+    PeelPieces c(h, src, n_blocks, sr.wr, *pe, show, steps);
+    return run_pieces(h, src, user, c);
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -172,6 +222,30 @@ int awpu_hip_peel(awpu_hip_t *h, const float *frames, int32_t batch, const awpu_
     if (residual_frames) AWPU_HIP_TRY(hipMemcpyAsync(residual_frames, h->d_peel_frames, floats * sizeof(float), hipMemcpyDeviceToHost, s));
     AWPU_HIP_TRY(hipStreamSynchronize(s));
     return AWPU_OK;
+}
+
+int awpu_hip_peel_blocks(awpu_hip_t *h, const void *datagrams, int32_t stride_bytes, int32_t n_blocks, const awpu_watch_t *w,
+                         const awpu_peel_t *pe, int32_t show, const awpu_find_t *f, uint8_t *image, uint8_t *big_image, float *power,
+                         awpu_peel_step_t *steps, awpu_source_t *sources, int32_t *count) {
+    BlockRun src;
+    if (int rc = wire_source(h, datagrams, stride_bytes, n_blocks, &src)) return rc;
+    return peel_run(h, src, n_blocks, w, pe, show, f, image, big_image, power, steps, sources, count, nullptr);
+}
+
+int awpu_hip_peel_samples(awpu_hip_t *h, const float *samples, int64_t pitch, int32_t n_blocks, const awpu_watch_t *w,
+                          const awpu_peel_t *pe, int32_t show, const awpu_find_t *f, uint8_t *image, uint8_t *big_image, float *power,
+                          awpu_peel_step_t *steps, awpu_source_t *sources, int32_t *count) {
+    BlockRun src;
+    if (int rc = sample_source(h, samples, pitch, n_blocks, false, &src)) return rc;
+    return peel_run(h, src, n_blocks, w, pe, show, f, image, big_image, power, steps, sources, count, nullptr);
+}
+
+int awpu_hip_peel_samples_device(awpu_hip_t *h, const float *d_samples, int64_t pitch, int32_t n_blocks, const awpu_watch_t *w,
+                                 const awpu_peel_t *pe, int32_t show, const awpu_find_t *f, uint8_t *d_image, uint8_t *d_big_image,
+                                 float *d_power, awpu_peel_step_t *d_steps, awpu_source_t *d_sources, int32_t *d_count, void *stream) {
+    BlockRun src;
+    if (int rc = sample_source(h, d_samples, pitch, n_blocks, true, &src)) return rc;
+    return peel_run(h, src, n_blocks, w, pe, show, f, d_image, d_big_image, d_power, d_steps, d_sources, d_count, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

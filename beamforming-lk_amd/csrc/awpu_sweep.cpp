@@ -1,7 +1,7 @@
 // awpu_sweep.cpp -- the sweep layer of libawpu_hip.so: from a prepared handle and a batch of frames to kernel launches.  In order:
 // the diagnostics of the stamped builds, prepare() and the table builders, the small rules every launcher shares (CU count, item
 // queues; the XCD pair group is sweep_plan.h's, beside the planners), one launcher per kernel, the dispatch rule (choose_shape
-// decides, launch switches) and the packed-frame forms of it.  What awpu_hip.cpp and awpu_runs.cpp call here is declared in
+// decides, launch switches) and the packed-frame forms of it.  What awpu_hip.cpp and the runs of blocks call here is declared in
 // awpu_handle.h.
 #include "awpu_handle.h"
 

@@ -43,9 +43,6 @@ def test_cohere_symbols_exported_and_listed(pkg):
     H, S = pkg._build.HEADERS, pkg._build.SOURCES
     assert REPO / "include" / "awpu_hip_cohere.h" in H and CSRC / "cohere_kernels.h" in H and CSRC / "cohere_rule.h" in H
     assert CSRC / "cohere_kernels.hip" in S and CSRC / "cohere_host.cpp" in S and CSRC / "awpu_cohere.cpp" in S
-    for build_file in ("CMakeLists.txt", "Makefile"):
-        for name in ("awpu_hip_cohere.h", "cohere_kernels.hip", "cohere_kernels.h", "cohere_rule.h", "cohere_host.cpp", "awpu_cohere.cpp"):
-            assert name in (REPO / build_file).read_text(), (build_file, name)
     # the rule is host-only and lives in one header; the kernel file may not include it
     assert "cohere_rule.h" in (CSRC / "cohere_host.cpp").read_text() and "cohere_rule.h" in (REPO / "tests" / "host" / "cohere_rule_check.cpp").read_text()
     assert "cohere_rule.h" not in (CSRC / "cohere_kernels.hip").read_text() + (CSRC / "cohere_kernels.h").read_text()

@@ -66,13 +66,27 @@ def test_tuning_build_still_links(pkg, tmp_path):
     measurements DESIGN.md cites could not be repeated.  It reads the round-1..3 variables; the shipping library does not."""
     pkg._build.generate_blocks()
     out = tmp_path / "libawpu_tuning.so"
-    srcs = [str(f) for f in pkg._build.SOURCES]
-    subprocess.run([pkg._build.hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-result",
-                    "-Werror=inline-asm", "-x", "hip", "-DAWPU_TIMING_BUILD", f"-I{REPO / 'include'}", f"-I{CSRC}", *srcs, "-o", str(out)],
-                   check=True, capture_output=True)
+    subprocess.run(pkg._build.hipcc_command(out, ("-DAWPU_TIMING_BUILD",)), check=True, capture_output=True)
     names = {ln for ln in subprocess.run(["strings", "-a", str(out)], capture_output=True, text=True, check=True).stdout.splitlines()
              if re.fullmatch(r"AWPU_[A-Z0-9_]+", ln)}
     assert {"AWPU_SHAPE", "AWPU_FAST_DEBUG", "AWPU_FAST_QUADS", "AWPU_FAST_PAIRGROUP", "AWPU_FIR8_STATIC"} <= names
+
+
+def test_one_build_recipe(pkg):
+    """beamforming-lk_amd/_build.py is the only place that knows what the library is built from and how: it compiles every source of
+    csrc/, every header makes the library stale, and `make lib` and the CMake target run it instead of restating it."""
+    B = pkg._build
+    assert len(B.SOURCES) == len(set(B.SOURCES)) and len(B.HEADERS) == len(set(B.HEADERS))
+    assert set(B.SOURCES) == {p for p in CSRC.iterdir() if p.suffix in (".hip", ".cpp")}
+    headers = {p for d in (CSRC, REPO / "include") for p in d.iterdir() if p.suffix == ".h"}
+    assert set(B.HEADERS) == headers | {REPO / "tools" / "gen_trip_asm.py"}
+    csrc_names = {p.name for p in CSRC.iterdir()} - {"das_fast_trip.inc"}
+    for build_file in ("Makefile", "CMakeLists.txt"):
+        text = (REPO / build_file).read_text()
+        assert "--offload-arch" not in text, build_file
+        assert not sorted(n for n in csrc_names if n in text), build_file
+    dry = subprocess.run(["make", "-n", "lib"], cwd=REPO, capture_output=True, text=True, check=True).stdout
+    assert any("python" in ln and "_build.py" in ln for ln in dry.splitlines()), dry
 
 
 def test_every_sweep_launcher_checks_its_reach():

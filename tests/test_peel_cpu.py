@@ -44,9 +44,6 @@ def test_peel_symbols_exported_and_listed(pkg):
     H, S = pkg._build.HEADERS, pkg._build.SOURCES
     assert REPO / "include" / "awpu_hip_peel.h" in H and CSRC / "peel_kernels.h" in H and CSRC / "peel_rule.h" in H
     assert CSRC / "peel_kernels.hip" in S and CSRC / "peel_host.cpp" in S and CSRC / "awpu_peel.cpp" in S
-    for build_file in ("CMakeLists.txt", "Makefile"):
-        for name in ("awpu_hip_peel.h", "peel_kernels.hip", "peel_kernels.h", "peel_rule.h", "peel_host.cpp", "awpu_peel.cpp"):
-            assert name in (REPO / build_file).read_text(), (build_file, name)
     # the sweep of the host loop is the coherence rule's, shared and not restated; the kernels take the step's arithmetic from peel_rule.h
     assert "cohere_rule.h" in (CSRC / "peel_host.cpp").read_text() and "peel_rule.h" in (CSRC / "peel_kernels.hip").read_text()
 

@@ -38,9 +38,6 @@ def test_spectral_symbols_exported_and_listed(pkg):
     H, S = pkg._build.HEADERS, pkg._build.SOURCES
     assert REPO / "include" / "awpu_hip_spectral.h" in H and CSRC / "spectral_kernels.h" in H and CSRC / "spectral_rule.h" in H
     assert CSRC / "spectral_kernels.hip" in S and CSRC / "spectral_host.cpp" in S
-    for build_file in ("CMakeLists.txt", "Makefile"):
-        for name in ("awpu_hip_spectral.h", "spectral_kernels.hip", "spectral_kernels.h", "spectral_rule.h", "spectral_host.cpp"):
-            assert name in (REPO / build_file).read_text(), (build_file, name)
 
 
 def test_spectral_header_compiles_as_c(tmp_path):
