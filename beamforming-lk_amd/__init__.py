@@ -39,11 +39,17 @@ from .binding import (  # noqa: F401
     resize_linear_u8,
     steer_table,
     steering_delays,
+    tones_host,
+    tones_linear,
+    tones_of,
+    tones_twiddles,
+    tones_window,
 )
 
 __all__ = [
     "Engine", "AwpuError", "MATH_F32_EXACT", "MATH_F32_FAST", "MATH_BF16_ACC", "build_delay_table", "build_delay_table_device",
     "create_antenna", "create_tiled_antenna", "steering_delays", "heatmap_u8", "find_peaks", "expose_count", "expose_rows", "cohere_host", "peel_host", "peel_step_host", "peel_beam_length", "peel_sources", "band_design", "band_filter", "resize_linear_u8", "steer_table", "focus_delays", "focus_steer_table",
-    "build_focus_table", "build_focus_table_device", "range_pick", "range_candidates", "binding",
+    "build_focus_table", "build_focus_table_device", "range_pick", "range_candidates", "tones_host", "tones_linear", "tones_of", "tones_twiddles",
+    "tones_window", "binding",
     "synthetic", "_build",
 ]

@@ -75,7 +75,7 @@ EXCHANGE_NONE, EXCHANGE_WINDOWS, EXCHANGE_PACKED_PAIRS = 0, 1, 2  # Stats.group_
 # awpu_kernel_id (include/awpu_hip.h): Stats.kernel_variant after a launch
 KERNEL_NAMES = ("none", "quad", "pair", "pair_stationary", "quadh", "quadh_stationary", "single_db", "single_small", "fir8_planes",
                 "fir8", "exact_pair", "exact_verify", "tuning", "exact_quad", "exact_nd", "exact_ndh", "exact_ndh_stationary", "exact_ndp",
-                "cohere")
+                "cohere", "tones")
 
 _lib: Optional[C.CDLL] = None
 
@@ -405,9 +405,45 @@ _PEEL_SIGNATURES = {
 }
 PEEL_SYMBOLS = tuple(_PEEL_SIGNATURES)
 
+# tone maps: the entry points of include/awpu_hip_tones.h
+TONES_BINS = 129
+TONES_RECT, TONES_HANN = 0, 1
+TONES_SHOW_PITCH = -1
+
+
+class Tones(C.Structure):
+    """awpu_tones_t (include/awpu_hip_tones.h)."""
+    _fields_ = [
+        ("window", C.c_int32),
+        ("n_groups", C.c_int32),
+        ("edge", C.c_int32 * (TONES_BINS + 1)),
+    ]
+
+
+assert C.sizeof(Tones) == 528
+
+_TONES_TAIL = [*_WATCH_TAIL, C.POINTER(Tones), C.c_int32, C.POINTER(Find)]  # n_blocks, w, t, show, f
+_TONES_SIGNATURES = {
+    "awpu_hip_tones_window": (C.c_int, [C.c_int32, _f32p]),
+    "awpu_hip_tones_twiddles": (C.c_int, [_f32p]),
+    "awpu_hip_tones_linear": (C.c_int, [C.c_float, C.c_float, C.c_int32, C.c_float, C.POINTER(Tones)]),
+    "awpu_hip_tones_host": (C.c_int, [_f32p, C.c_int32, C.c_int32, C.c_int32, _i32p, _f32p, C.c_int32, C.c_int32, _i32p, C.c_int32, _f32p,
+                                      C.POINTER(Tones), _f32p, _i32p, _f32p, _f32p]),
+    "awpu_hip_tones": (C.c_int, [C.c_void_p, _f32p, C.c_int32, C.POINTER(Tones), _f32p, _i32p]),
+    "awpu_hip_tones_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Tones), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "awpu_hip_tones_device_bins": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Tones), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]),
+    "awpu_hip_tones_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, *_TONES_TAIL, _u8p, _u8p, _f32p, C.c_void_p, C.c_void_p]),
+    "awpu_hip_tones_samples": (C.c_int, [C.c_void_p, _f32p, C.c_int64, *_TONES_TAIL, _u8p, _u8p, _f32p, C.c_void_p, C.c_void_p]),
+    "awpu_hip_tones_samples_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, *_TONES_TAIL, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p]),
+}
+TONES_SYMBOLS = tuple(_TONES_SIGNATURES)
+
 # every table above, one per public header: what load() sets the types of
 _ALL_SIGNATURES = (_SIGNATURES, _TRACK_SIGNATURES, _BLOCK_SIGNATURES, _LISTEN_SIGNATURES, _WATCH_SIGNATURES, _FIND_SIGNATURES, _BAND_SIGNATURES,
-                   _FOCUS_SIGNATURES, _SPECTRAL_SIGNATURES, _EXPOSE_SIGNATURES, _COHERE_SIGNATURES, _PEEL_SIGNATURES)
+                   _FOCUS_SIGNATURES, _SPECTRAL_SIGNATURES, _EXPOSE_SIGNATURES, _COHERE_SIGNATURES, _PEEL_SIGNATURES,
+                   _TONES_SIGNATURES)
 
 # numpy view of awpu_range_t: what range_pick, Engine.range and Engine.locate_* return (unused entries: index -1)
 RANGE_DTYPE = np.dtype([("index", "<i4"), ("power", "<f4"), ("distance", "<f8")], align=True)
@@ -843,6 +879,110 @@ def cohere_host(frames: np.ndarray, off: np.ndarray, frac: np.ndarray, index=Non
                                        *[None if m is None else _f32(m) for m in wide]), "awpu_hip_cohere_host")
     out = maps + wide if want_sums else maps
     return tuple(m[0] for m in out) if single else tuple(out)
+
+
+def tones_window(window: int = TONES_RECT) -> np.ndarray:
+    """The window table [256] of the rule of include/awpu_hip_tones.h (awpu_hip_tones_window)."""
+    w = np.empty(256, np.float32)
+    _check(load().awpu_hip_tones_window(int(window), _f32(w)), "awpu_hip_tones_window")
+    return w
+
+
+def tones_twiddles() -> np.ndarray:
+    """The twiddle table [128, 2] of the rule: (cos, -sin) of 2 pi k / 256 (awpu_hip_tones_twiddles)."""
+    t = np.empty((128, 2), np.float32)
+    _check(load().awpu_hip_tones_twiddles(_f32(t)), "awpu_hip_tones_twiddles")
+    return t
+
+
+def tones_linear(lo_hz: float, hi_hz: float, n_groups: int = 1, window: int = TONES_RECT, sample_rate: float = 48828.125) -> Tones:
+    """A Tones whose n_groups groups deal out the bins with centres in [lo_hz, hi_hz) as equally as possible (awpu_hip_tones_linear)."""
+    t = Tones()
+    t.window = int(window)
+    _check(load().awpu_hip_tones_linear(float(lo_hz), float(hi_hz), int(n_groups), float(sample_rate), C.byref(t)), "awpu_hip_tones_linear")
+    return t
+
+
+def tones_of(groups, window: int = TONES_RECT, sample_rate: float = 48828.125) -> Tones:
+    """A Tones from a Tones (returned as it is), a list or array of edges (n_groups + 1 ascending bins) or a tuple
+    (lo_hz, hi_hz, n_groups) for tones_linear.  The edges are not judged here: the library refuses a bad request."""
+    if isinstance(groups, Tones):
+        return groups
+    if isinstance(groups, tuple) and len(groups) == 3:
+        return tones_linear(groups[0], groups[1], groups[2], window, sample_rate)
+    edges = [int(e) for e in groups]
+    if not 2 <= len(edges) <= TONES_BINS + 1:
+        raise ValueError("edges are n_groups + 1 bins, n_groups in [1, 129]")
+    t = Tones()
+    t.window, t.n_groups = int(window), len(edges) - 1
+    for g, e in enumerate(edges):
+        t.edge[g] = e
+    return t
+
+
+def tones_from_text(text: str, sample_rate: float = 48828.125) -> Tones:
+    """'LO:HI[:hann]' (Hz; the rectangular window unless 'hann' is given), as the tools' --tone and --pitch take it -> a Tones with
+    the one group of bins whose centres lie in [LO, HI)."""
+    parts = text.split(":")
+    if len(parts) not in (2, 3) or (len(parts) == 3 and parts[2] != "hann"):
+        raise ValueError(f"tone '{text}': LO:HI or LO:HI:hann, in Hz")
+    lo, hi = float(parts[0]), float(parts[1])
+    if not 0.0 <= lo < hi:
+        raise ValueError(f"tone '{text}': 0 <= LO < HI")
+    try:
+        return tones_linear(lo, hi, 1, TONES_HANN if len(parts) == 3 else TONES_RECT, sample_rate)
+    except AwpuError:
+        raise ValueError(f"tone '{text}': no bin of {sample_rate / 256:.1f} Hz has its centre in that range") from None
+
+
+def tones_edges(t: Tones) -> np.ndarray:
+    """edge[0 .. n_groups] of a Tones."""
+    return np.array(t.edge[:t.n_groups + 1], np.int32)
+
+
+def tones_host(frames: np.ndarray, off: np.ndarray, frac: np.ndarray, groups, window: int = TONES_RECT, index=None, gain=None,
+               want=("tone", "pitch")):
+    """The rule of include/awpu_hip_tones.h as executable C (awpu_hip_tones_host): frames, off, frac, index and gain as cohere_host
+    takes them, groups as tones_of does.  -> a dict of the outputs named in `want`: "tone" [batch, n_groups, n_pixels], "pitch"
+    [batch, n_pixels] int32, "bins" [batch, n_pixels, 129], "spectrum" [batch, n_pixels, 129, 2]; one frame in, arrays without
+    the batch axis out."""
+    t = tones_of(groups, window)
+    frames = np.ascontiguousarray(frames, np.float32)
+    single = frames.ndim == 2
+    if single:
+        frames = frames[None]
+    off = np.ascontiguousarray(off, np.int32)
+    frac = np.ascontiguousarray(frac, np.float32)
+    if frames.ndim != 3 or off.ndim != 2 or off.shape != frac.shape:
+        raise ValueError("frames must be [batch, n_streams, hist], off and frac [n_pixels, lut_stride]")
+    index = np.arange(off.shape[1], dtype=np.int32) if index is None else np.ascontiguousarray(index, np.int32)
+    if gain is not None:
+        gain = np.ascontiguousarray(gain, np.float32)
+        if gain.shape != index.shape:
+            raise ValueError("gain must be [usable], in the active list's order")
+    batch, n_pixels = frames.shape[0], off.shape[0]
+    shapes = {"tone": ((batch, max(t.n_groups, 0), n_pixels), np.float32), "pitch": ((batch, n_pixels), np.int32),
+              "bins": ((batch, n_pixels, TONES_BINS), np.float32), "spectrum": ((batch, n_pixels, TONES_BINS, 2), np.float32)}
+    if not want or any(name not in shapes for name in want):
+        raise ValueError(f"want names some of {tuple(shapes)}")
+    out = {name: np.empty(*shapes[name]) for name in shapes if name in want}
+    ptr = lambda name: _out_ptr(out.get(name), _i32p if name == "pitch" else _f32p)
+    _check(load().awpu_hip_tones_host(_f32(frames), batch, frames.shape[1], frames.shape[2], _i32(off), _f32(frac), off.shape[1], n_pixels,
+                                      _i32(index), len(index), None if gain is None else _f32(gain), C.byref(t), ptr("tone"), ptr("pitch"),
+                                      ptr("bins"), ptr("spectrum")), "awpu_hip_tones_host")
+    return {name: a[0] for name, a in out.items()} if single else out
+
+
+class TonesResult:
+    """What Engine.tones_blocks / tones_samples hand back: .image, .big, .power as a WatchResult has them -- of the shown group's
+    plane or, with show=TONES_SHOW_PITCH, of the pitch row --, .sources and .count as a FindResult has them (None without `find`),
+    .next_first for the call that continues the run."""
+
+    def __init__(self, image, big, power, sources, count, next_first: int):
+        self.image, self.big, self.power, self.sources, self.count, self.next_first = image, big, power, sources, count, next_first
+
+    def __len__(self):
+        return len(next(a for a in (self.image, self.big, self.power, self.count) if a is not None))
 
 
 class PeelResult:
@@ -1625,6 +1765,92 @@ class Engine:
                                                         None if f is None else C.byref(f), C.c_void_p(d_image_ptr), C.c_void_p(d_big_ptr),
                                                         C.c_void_p(d_power_ptr), C.c_void_p(d_sources_ptr), C.c_void_p(d_count_ptr),
                                                         C.c_void_p(stream)), "awpu_hip_cohere_samples_device")
+        return watch_count(n_blocks, first, every)[1]
+
+    def tones(self, frames: np.ndarray, groups, window: int = TONES_RECT, want=("tone", "pitch")):
+        """The tone sweep of host frames [batch, n_streams, hist] (or one frame), groups as tones_of takes them: -> a dict of the
+        outputs in `want`: "tone" [batch, n_groups, pixels], "pitch" [batch, pixels] int32 (awpu_hip_tones).  The handle's gains
+        and band apply."""
+        t = tones_of(groups, window)
+        frames = np.ascontiguousarray(frames, np.float32)
+        single = frames.ndim == 2
+        if single:
+            frames = frames[None]
+        if frames.shape[1:] != (self.cfg.n_streams, self.cfg.hist):
+            raise ValueError(f"frames must be [batch, {self.cfg.n_streams}, {self.cfg.hist}]")
+        if not want or any(name not in ("tone", "pitch") for name in want):
+            raise ValueError("want names some of ('tone', 'pitch')")
+        out = {}
+        if "tone" in want:
+            out["tone"] = np.empty((frames.shape[0], max(t.n_groups, 0), self.pixel_count), np.float32)
+        if "pitch" in want:
+            out["pitch"] = np.empty((frames.shape[0], self.pixel_count), np.int32)
+        _check(self._lib.awpu_hip_tones(self._h, _f32(frames), frames.shape[0], C.byref(t), _out_ptr(out.get("tone"), _f32p),
+                                        _out_ptr(out.get("pitch"), _i32p)), "awpu_hip_tones")
+        return {name: a[0] for name, a in out.items()} if single else out
+
+    def tones_device(self, d_frames_ptr: int, batch: int, groups, window: int = TONES_RECT, d_tone_ptr: int = 0, d_pitch_ptr: int = 0,
+                     stream: int = 0) -> None:
+        """The same on device pointers (frames [batch, n_streams, hist]; tone [batch, n_groups, pixels], pitch [batch, pixels] int32,
+        each or 0) on `stream`; asynchronous (awpu_hip_tones_device)."""
+        t = tones_of(groups, window)
+        _check(self._lib.awpu_hip_tones_device(self._h, C.c_void_p(d_frames_ptr), batch, C.byref(t), C.c_void_p(d_tone_ptr), C.c_void_p(d_pitch_ptr),
+                                               C.c_void_p(stream)), "awpu_hip_tones_device")
+
+    def tones_device_bins(self, d_frames_ptr: int, batch: int, groups, window: int = TONES_RECT, d_bins_ptr: int = 0, d_spectrum_ptr: int = 0,
+                          d_tone_ptr: int = 0, d_pitch_ptr: int = 0, stream: int = 0) -> None:
+        """tones_device plus every pixel's bins [batch, pixels, 129] and spectrum [batch, pixels, 129, 2] into d_bins / d_spectrum,
+        each or 0 (awpu_hip_tones_device_bins): the rule's bits."""
+        t = tones_of(groups, window)
+        _check(self._lib.awpu_hip_tones_device_bins(self._h, C.c_void_p(d_frames_ptr), batch, C.byref(t), C.c_void_p(d_tone_ptr),
+                                                    C.c_void_p(d_pitch_ptr), C.c_void_p(d_bins_ptr), C.c_void_p(d_spectrum_ptr),
+                                                    C.c_void_p(stream)), "awpu_hip_tones_device_bins")
+
+    def _tones_run(self, call, where, n_blocks, rows, cols, first, every, groups, window, show, out_rows, out_cols, d_colormap_ptr, flip,
+                   want_image, want_power, find) -> TonesResult:
+        n_frames, next_first = watch_count(n_blocks, first, every)
+        w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(d_colormap_ptr))
+        t = tones_of(groups, window)
+        f = _find_struct(rows, cols, find)
+        shown, ptrs = self._shown_outputs(n_frames, w, want_image, want_power, f)
+        _check(call(n_blocks, C.byref(w), C.byref(t), show, None if f is None else C.byref(f), *ptrs), where)
+        return TonesResult(*shown, next_first)
+
+    def tones_blocks(self, wire, rows: int, cols: int, groups, window: int = TONES_RECT, show: int = 0, first: int = 0, every: int = 1,
+                     out_rows: int = 0, out_cols: int = 0, d_colormap_ptr: int = 0, flip: bool = False, stride: int = DATAGRAM_BYTES,
+                     want_image: bool = True, want_power: bool = False, find: Optional[dict] = None) -> TonesResult:
+        """Watch a run of consecutive blocks of wire datagrams (as watch_blocks takes them) through the tone sweep: every shown
+        frame is the plane of group `show`, or with show=TONES_SHOW_PITCH the pitch row (awpu_hip_tones_blocks).  `find` (a dict
+        of find_peaks' keywords, {} for the defaults) also finds the sources of every frame.  -> TonesResult; pass its .next_first
+        as `first` of the call that continues the run."""
+        buf, n_blocks = _wire_blocks(wire, stride)
+        return self._tones_run(lambda *rest: self._lib.awpu_hip_tones_blocks(self._h, buf.ctypes.data_as(C.c_void_p), stride, *rest),
+                               "awpu_hip_tones_blocks", n_blocks, rows, cols, first, every, groups, window, show, out_rows, out_cols,
+                               d_colormap_ptr, flip, want_image, want_power, find)
+
+    def tones_samples(self, samples: np.ndarray, rows: int, cols: int, groups, window: int = TONES_RECT, show: int = 0, first: int = 0,
+                      every: int = 1, out_rows: int = 0, out_cols: int = 0, d_colormap_ptr: int = 0, flip: bool = False,
+                      want_image: bool = True, want_power: bool = False, find: Optional[dict] = None) -> TonesResult:
+        """The same from unpacked samples [n_streams, N] (N a multiple of 256, oldest first) (awpu_hip_tones_samples)."""
+        samples, n_blocks = self._sample_blocks(samples)
+        return self._tones_run(lambda *rest: self._lib.awpu_hip_tones_samples(self._h, _f32(samples), samples.shape[1], *rest),
+                               "awpu_hip_tones_samples", n_blocks, rows, cols, first, every, groups, window, show, out_rows, out_cols,
+                               d_colormap_ptr, flip, want_image, want_power, find)
+
+    def tones_samples_device(self, d_samples_ptr: int, pitch: int, n_blocks: int, rows: int, cols: int, groups, window: int = TONES_RECT,
+                             show: int = 0, first: int = 0, every: int = 1, d_image_ptr: int = 0, d_big_ptr: int = 0, d_power_ptr: int = 0,
+                             d_sources_ptr: int = 0, d_count_ptr: int = 0, out_rows: int = 0, out_cols: int = 0, d_colormap_ptr: int = 0,
+                             flip: bool = False, stream: int = 0, find: Optional[dict] = None) -> int:
+        """The same on device pointers (samples [n_streams, pitch]; image, big, power as watch_samples_device takes them, sources
+        and count as find_samples_device does, each or 0) on `stream`; asynchronous.  -> next_first
+        (awpu_hip_tones_samples_device)."""
+        w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(d_colormap_ptr))
+        t = tones_of(groups, window)
+        f = _find_struct(rows, cols, find)
+        _check(self._lib.awpu_hip_tones_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, C.byref(w), C.byref(t), show,
+                                                       None if f is None else C.byref(f), C.c_void_p(d_image_ptr), C.c_void_p(d_big_ptr),
+                                                       C.c_void_p(d_power_ptr), C.c_void_p(d_sources_ptr), C.c_void_p(d_count_ptr),
+                                                       C.c_void_p(stream)), "awpu_hip_tones_samples_device")
         return watch_count(n_blocks, first, every)[1]
 
     def range(self, theta, phi, distance, d_frame_ptr: int = 0):

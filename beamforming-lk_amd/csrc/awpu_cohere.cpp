@@ -30,7 +30,8 @@ int cohere_device(awpu_hip *h, const float *d_frames, int batch, const CohereOut
     if (rc == AWPU_OK) rc = ensure_cohere_table(h);
     if (rc == AWPU_OK) rc = enter_stream(h, s);
     if (rc != AWPU_OK) return rc;
-    return band_sweep(h, own_band(h), d_frames, (long long) h->cfg.n_streams * h->cfg.hist, h->cfg.hist, h->wstart, batch, nullptr, 0, s, kFull, {}, &out);
+    const OwnSweep sweep = [&](const float *frames, bool timed) { return launch_cohere(h, frames, batch, out, s, kFull, timed); };
+    return band_sweep(h, own_band(h), d_frames, (long long) h->cfg.n_streams * h->cfg.hist, h->cfg.hist, h->wstart, batch, nullptr, 0, s, kFull, {}, &sweep);
 }
 
 // ---- coherence runs (awpu_hip_cohere.h; kernel in cohere_kernels.hip) -------------------------------------------------------------
@@ -100,8 +101,10 @@ int awpu_hip_cohere(awpu_hip_t *h, const float *frames, int32_t batch, float *po
         if (host_out[k]) d_out[k] = h->d_cohere_out + plane * at++;
     CohereOut out;
     out.power = d_out[0], out.coherence = d_out[1], out.weighted = d_out[2];
-    rc = band_sweep(h, bands, h->d_frames, (long long) S * dev_hist, dev_hist, compact ? pre : h->wstart, batch, nullptr, 0, h->stream,
-                    compact ? kCompact : kFull, kTimed, &out);
+    const int layout = compact ? kCompact : kFull;
+    const OwnSweep sweep = [&](const float *swept, bool timed) { return launch_cohere(h, swept, batch, out, h->stream, layout, timed); };
+    rc = band_sweep(h, bands, h->d_frames, (long long) S * dev_hist, dev_hist, compact ? pre : h->wstart, batch, nullptr, 0, h->stream, layout, kTimed,
+                    &sweep);
     if (rc != AWPU_OK) return rc;
     for (int k = 0; k < 3; k++)
         if (host_out[k]) AWPU_HIP_TRY(hipMemcpyAsync(host_out[k], d_out[k], plane * sizeof(float), hipMemcpyDeviceToHost, h->stream));

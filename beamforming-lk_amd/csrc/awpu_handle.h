@@ -8,11 +8,13 @@
 
 #include "awpu_hip.h"
 #include "awpu_hip_spectral.h"
+#include "awpu_hip_tones.h"
 #include "awpu_hip_track.h"
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <functional>
 #include <string>
 #include <utility>
 #include <vector>
@@ -394,6 +396,11 @@ struct awpu_hip {
     // with the other tables), and the maps of a host-form call on their way back, one plane [batch][pixel_count] per map asked for
     Dev<awpu::LutEntry> d_cohere_lut;
     Dev<float> d_cohere_out;
+    // tones (awpu_hip_tones.h): the rule's tables as the host functions make them -- the two windows [2][256], then the twiddles
+    // [128][2] --, uploaded once per handle (ensure_tones_tables), and the planes of a host-form call on their way back: tone
+    // [batch][n_groups][pixel_count], then pitch [batch][pixel_count]
+    Dev<float> d_tones_tables;
+    Dev<float> d_tones_out;
     // peeling (awpu_hip_peel.h; awpu_peel.cpp): the table's reach at the active mics, valid for the tables of peel_gen (table_gen;
     // 0: none yet); the loop's residual frames [batch][n_streams][hist] where the caller keeps none, its power row P_k
     // [batch][pixel_count], its bookkeeping (PeelState [batch]), and the results of a host-form call on their way back
@@ -518,6 +525,15 @@ struct CohereOut {
 };
 int ensure_cohere_table(awpu_hip *h);  // behind check_ready, before the call enqueues anything: the one step that may block
 int launch_cohere(awpu_hip *h, const float *d_frames, int batch, const CohereOut &out, hipStream_t s, int layout, bool timed = false);
+// what a tone sweep (awpu_hip_tones.h) writes, device memory, each or null: tone [batch][n_groups][pixel_count], pitch and
+// pitch_row = (float) pitch [batch][pixel_count], bins [batch][pixel_count][129], spectrum [batch][pixel_count][129][2]
+struct TonesOut {
+    float *tone = nullptr;
+    int32_t *pitch = nullptr;
+    float *pitch_row = nullptr, *bins = nullptr, *spectrum = nullptr;
+};
+int ensure_tones_tables(awpu_hip *h);  // beside ensure_cohere_table: may block, before the call enqueues anything
+int launch_tones(awpu_hip *h, const float *d_frames, int batch, const awpu_tones_t &t, const TonesOut &out, hipStream_t s, int layout, bool timed = false);
 bool takes_packed_pairs(awpu_hip *h, int batch, awpu::FastPlan *plan);
 int packed_shape(awpu_hip *h, int batch, awpu::FastPlan *plan);
 size_t packed_floats_of(const awpu_hip *h, const awpu::FastPlan &plan, int batch);
@@ -543,10 +559,13 @@ int check_antenna(const awpu_hip *h);
 int ensure_track_index(awpu_hip *h);
 int check_candidates(const double *distance, int32_t n_dist);  // awpu_focus.cpp: the candidate distances of awpu_hip_focus.h
 int ensure_taps(awpu_hip *h, int rows, int cols, int out_rows, int out_cols, hipStream_t s);
+// a sweep of its own behind band_sweep's pre-pass, in place of launch() (the coherence sweep, the tone sweep): the frames in the
+// call's layout and whether to time it -> status
+using OwnSweep = std::function<int(const float *d_frames, bool timed)>;
 int band_cut(awpu_hip *h, const BandSet &bands, const float *in, long long in_frame, long long in_row, int in_lo, int batch, float *out,
              long long out_plane, int layout, hipStream_t s);
 int band_sweep(awpu_hip *h, const BandSet &bands, const float *in, long long in_frame, long long in_row, int in_lo, int batch, float *d_power,
-               long long power_plane, hipStream_t s, int layout, const SweepOpts &o = {}, const CohereOut *cohere = nullptr);
+               long long power_plane, hipStream_t s, int layout, const SweepOpts &o = {}, const OwnSweep *own = nullptr);
 inline int band_sweep(awpu_hip *h, const float *in, long long in_frame, long long in_row, int in_lo, int batch, float *d_power, hipStream_t s, int layout,
                       const SweepOpts &o = {}) {
     return band_sweep(h, own_band(h), in, in_frame, in_row, in_lo, batch, d_power, 0, s, layout, o);  // the handle's own band: the one-band case

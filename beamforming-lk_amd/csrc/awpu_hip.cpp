@@ -291,12 +291,12 @@ int band_cut(awpu_hip *h, const BandSet &bands, const float *in, long long in_fr
 // (kCompact: rows of max taps - 1 + compact_hist floats), through the bands where there are any: the pre-pass into d_band in
 // `layout`, a plane per band, then for every band the launch() a band-less handle makes for the same call -- the same layout and
 // batch, so the same kernel -- into d_power + b * power_plane.  A timed call's event bracket spans all of it: recorded here, the
-// sweeps behind the pre-pass untimed.  With `cohere` the sweep behind the pre-pass is the coherence sweep (awpu_hip_cohere.h: at
-// most one band, d_power unused)
+// sweeps behind the pre-pass untimed.  With `own` the sweep behind the pre-pass is the caller's (the coherence sweep of
+// awpu_hip_cohere.h, the tone sweep of awpu_hip_tones.h: at most one band, d_power unused)
 int band_sweep(awpu_hip *h, const BandSet &bands, const float *in, long long in_frame, long long in_row, int in_lo, int batch, float *d_power,
-               long long power_plane, hipStream_t s, int layout, const SweepOpts &o, const CohereOut *cohere) {
+               long long power_plane, hipStream_t s, int layout, const SweepOpts &o, const OwnSweep *own) {
     const auto sweep = [&](const float *frames, float *power, const SweepOpts &so) {
-        return cohere ? launch_cohere(h, frames, batch, *cohere, s, layout, so.timed) : launch(h, frames, batch, power, s, layout, so);
+        return own ? (*own)(frames, so.timed) : launch(h, frames, batch, power, s, layout, so);
     };
     if (bands.n == 0) return sweep(in, d_power, o);
     const size_t S = (size_t) h->cfg.n_streams;

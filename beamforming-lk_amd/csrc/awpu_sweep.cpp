@@ -16,6 +16,7 @@
 #include "cohere_kernels.h"
 #include "das_kernels.h"
 #include "nd_tile_window.h"
+#include "tones_kernels.h"
 
 using namespace awpu::host;
 
@@ -1230,6 +1231,57 @@ int launch_cohere(awpu_hip *h, const float *d_frames, int batch, const CohereOut
     if (timed) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
     AWPU_HIP_TRY(awpu::launch_cohere_sweep(a, s));
     return finish_launch(h, batch, s, timed, AWPU_KERNEL_COHERE);
+}
+
+// The tone sweep's two tables (awpu_hip_tones.h), from the library's own host functions: both windows, then the twiddles, once per
+// handle.  The copy blocks, so every tone call comes here beside ensure_cohere_table, before it enqueues anything.
+int ensure_tones_tables(awpu_hip *h) {
+    if (h->d_tones_tables) return AWPU_OK;
+    std::vector<float> tables(3 * awpu::kSamples);
+    awpu_hip_tones_window(AWPU_TONES_RECT, tables.data());
+    awpu_hip_tones_window(AWPU_TONES_HANN, tables.data() + awpu::kSamples);
+    awpu_hip_tones_twiddles(reinterpret_cast<float(*)[2]>(tables.data() + 2 * awpu::kSamples));
+    if (const int rc = h->d_tones_tables.grow(tables.size()); rc != AWPU_OK) return rc;
+    const hipError_t e = hipMemcpy(h->d_tones_tables, tables.data(), tables.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        h->d_tones_tables.release();
+        return hip_fail(e, "hipMemcpy of the tone sweep's tables");
+    }
+    return AWPU_OK;
+}
+
+// The tone sweep (awpu_hip_tones.h; tones_sweep_kernel), beside launch_cohere and with its arguments, table and layouts: whatever
+// cfg.math is, the rule has one arithmetic.  `t` has passed tones_refusal; it travels as a kernel argument.  Each output or null;
+// counted and timed like any sweep launch.  Nothing here waits for the device.
+int launch_tones(awpu_hip *h, const float *d_frames, int batch, const awpu_tones_t &t, const TonesOut &out, hipStream_t s, int layout, bool timed) {
+    if (h->cfg.interp != AWPU_INTERP_LERP) return fail(AWPU_ERR_STATE, "the tone sweep interpolates linearly: AWPU_INTERP_FIR8 is not taken");
+    if (layout != kFull && layout != kCompact) return invalid("the tone sweep takes whole frames or uploaded windows");
+    const awpu::LutEntry *lut = h->d_lut ? h->d_lut.get() : h->d_cohere_lut.get();
+    if (!lut || !h->d_tones_tables) return fail(AWPU_ERR_STATE, "the tone sweep has no tables: ensure_cohere_table and ensure_tones_tables come first");
+    awpu::TonesArgs a{};
+    a.sweep.frames = d_frames;
+    a.sweep.lut = lut;
+    a.sweep.index = h->d_index;
+    a.sweep.gain = h->d_gain;
+    a.sweep.n_streams = h->cfg.n_streams;
+    a.sweep.hist = layout == kCompact ? h->compact_hist : h->cfg.hist;
+    a.sweep.usable = h->usable();
+    a.sweep.pixel_count = h->cfg.pixel_count;
+    a.sweep.wstart = layout == kCompact ? 0 : h->wstart;
+    a.sweep.window = h->window;
+    a.sweep.batch = batch;
+    a.window = h->d_tones_tables.get() + (t.window == AWPU_TONES_HANN ? awpu::kSamples : 0);
+    a.twiddles = h->d_tones_tables.get() + 2 * awpu::kSamples;
+    a.wss = t.window == AWPU_TONES_HANN ? 96.0f : 256.0f;
+    a.tone = out.tone;
+    a.pitch = out.pitch;
+    a.pitch_row = out.pitch_row;
+    a.bins = out.bins;
+    a.spectrum = out.spectrum;
+    a.t = t;
+    if (timed) AWPU_HIP_TRY(hipEventRecord(h->ev_begin, s));
+    AWPU_HIP_TRY(awpu::launch_tones_sweep(a, s));
+    return finish_launch(h, batch, s, timed, AWPU_KERNEL_TONES);
 }
 
 // Would launch() sweep this batch with one of the frame-pair shapes that read the packed layout (quad or pair)?  The rule of

@@ -117,7 +117,8 @@ typedef enum {
     AWPU_KERNEL_EXACT_NDH = 15,       /* das_exact_ndh_kernel: single frames in the reference's order (the two halves of the block in the packed lanes) */
     AWPU_KERNEL_EXACT_NDH_STATIONARY = 16, /* ... with every active mic resident and staged by the workgroups themselves (the reference's own shape) */
     AWPU_KERNEL_EXACT_NDP = 17,       /* das_exact_ndp_kernel: ... one pixel per wave (grids of at most 32 pixels per CU: one AWPU's 4 arrays on a 64 x 64 grid; FAST takes it up to 16) */
-    AWPU_KERNEL_COHERE = 18           /* cohere_sweep_kernel: the coherence sweep of awpu_hip_cohere.h (das_exact_kernel's shape, every math mode) */
+    AWPU_KERNEL_COHERE = 18,          /* cohere_sweep_kernel: the coherence sweep of awpu_hip_cohere.h (das_exact_kernel's shape, every math mode) */
+    AWPU_KERNEL_TONES = 19            /* tones_sweep_kernel: the tone sweep of awpu_hip_tones.h (the same shape, every math mode) */
 } awpu_kernel_id;
 
 typedef struct awpu_hip awpu_hip_t;

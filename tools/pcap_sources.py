@@ -28,6 +28,10 @@ merged per pixel -- the entries of its clean map, strongest first, `power` what 
 own --, which lists a weak source under a strong one's side lobes and not the side lobes.  Off unless given; not with --band,
 --exposure, --coherence or --range.
 
+--tone LO:HI[:hann] searches the rows of the tone sweep (Engine.tones_blocks, include/awpu_hip_tones.h): per pixel, the power of its
+beam in the 190.7 Hz transform bins whose centres lie in [LO, HI) Hz (`hann`: behind a Hann window); the `power` column is that
+row's value.  Off unless given; --band applies in front; not with --exposure, --coherence, --peel or --range.
+
 Every block is ingested; every --every'th is swept and searched.  --chunk blocks go to the engine per call, each call continuing
 with the `next_first` of the one before, so a long capture streams through bounded memory.
 
@@ -127,8 +131,20 @@ def main(argv=None) -> int:
                     help="search the coherence-weighted power, or the coherence factor itself (include/awpu_hip_cohere.h)")
     ap.add_argument("--peel", default=None, metavar="STEPS[:GAIN]",
                     help="peel every searched block: its sources are the steps merged per pixel (include/awpu_hip_peel.h)")
+    ap.add_argument("--tone", default=None, metavar="LO:HI[:hann]",
+                    help="search the power in the transform bins between LO and HI Hz of every pixel's beam (include/awpu_hip_tones.h)")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
+    if a.tone and (a.exposure is not None or a.range_ or a.coherence or a.peel):
+        ap.error("--tone together with --exposure, --range, --coherence or --peel: those runs are not swept for tones")
+    if a.tone:
+        # (the one parser of LO:HI[:hann] is the binding's, and which bins a range takes is the library's to say: both are
+        # asked here, before the capture is opened)
+        sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+        try:
+            tone_groups = importlib.import_module("beamforming-lk_amd").binding.tones_from_text(a.tone)
+        except ValueError as e:
+            ap.error(str(e))
     if a.peel and (a.exposure is not None or a.range_ or a.coherence or a.band):
         ap.error("--peel together with --exposure, --range, --coherence or --band: those runs are not peeled")
     if a.peel:
@@ -193,6 +209,10 @@ def main(argv=None) -> int:
             elif a.peel:
                 res = eng.peel_blocks(chunk, a.cols, a.cols, peel[0], peel[1], first=first, every=a.every, want_image=False)
                 res.sources, res.count = pkg.binding.peel_source_records(res.steps, a.cols, a.cols, a.max_sources, a.fov)
+            elif a.tone:
+                what = {k: v for k, v in find.items() if k not in ("first", "every")}
+                res = eng.tones_blocks(chunk, a.cols, a.cols, tone_groups, first=first, every=a.every, want_image=False,
+                                       find=what)
             elif a.coherence:
                 what = {k: v for k, v in find.items() if k not in ("first", "every")}
                 show = pkg.binding.COHERE_FACTOR if a.coherence == "factor" else pkg.binding.COHERE_WEIGHTED

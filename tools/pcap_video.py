@@ -32,6 +32,12 @@ strongest pixel, subtract its beam from every mic, with loop gain GAIN (1 unless
 powers at their pixels -- plus the residual, so a source's side lobes go with the source.  Off unless given; not with --band,
 --bands, --exposure or --coherence.
 
+--tone LO:HI[:hann] shows every frame through the tone sweep (Engine.tones_blocks, include/awpu_hip_tones.h): per pixel, the power
+of its beam in the 190.7 Hz transform bins whose centres lie in [LO, HI) Hz -- no FIR band, any band at the same cost --, with the
+rectangular window or, with `hann`, the Hann window.  --pitch LO:HI[:hann] shows instead the strongest bin of that range per pixel,
+brighter where the pitch is higher.  Off unless given; --band applies in front; not with --bands, --exposure, --coherence or
+--peel, nor with each other.
+
 Every block is ingested; every --every'th is swept and shown.  The default 3 gives 48828 / (256 * 3) = 63.6 frames per second, the
 nearest to the 60 the reference opens its writer with.  --chunk blocks go to the engine per call, each call continuing with the
 `next_first` of the one before, so a long capture streams through bounded memory.
@@ -232,8 +238,24 @@ def main(argv=None) -> int:
                     help="show the coherence-weighted power, or the coherence factor itself (include/awpu_hip_cohere.h)")
     ap.add_argument("--peel", default=None, metavar="STEPS[:GAIN]",
                     help="show every frame peeled: the clean map plus the residual after STEPS steps (include/awpu_hip_peel.h)")
+    ap.add_argument("--tone", default=None, metavar="LO:HI[:hann]",
+                    help="show the power in the transform bins between LO and HI Hz of every pixel's beam (include/awpu_hip_tones.h)")
+    ap.add_argument("--pitch", default=None, metavar="LO:HI[:hann]",
+                    help="show every pixel's strongest bin between LO and HI Hz: brighter where the pitch is higher")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
+    if a.tone and a.pitch:
+        ap.error("--tone together with --pitch: one row per frame")
+    if (a.tone or a.pitch) and (a.bands or a.exposure is not None or a.coherence or a.peel):
+        ap.error("--tone and --pitch together with --bands, --exposure, --coherence or --peel: those runs are not swept for tones")
+    if a.tone or a.pitch:
+        # (the one parser of LO:HI[:hann] is the binding's, and which bins a range takes is the library's to say: both are
+        # asked here, before the capture is opened)
+        sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+        try:
+            tone_groups = importlib.import_module("beamforming-lk_amd").binding.tones_from_text(a.tone or a.pitch)
+        except ValueError as e:
+            ap.error(str(e))
     if a.peel and (a.bands or a.band or a.exposure is not None or a.coherence):
         ap.error("--peel together with --band, --bands, --exposure or --coherence: those runs are not peeled")
     if a.peel:
@@ -308,6 +330,10 @@ def main(argv=None) -> int:
             elif a.peel:
                 res = eng.peel_blocks(wire[b * block_bytes: (b + nb) * block_bytes], a.cols, a.cols, peel[0], peel[1], first=first, every=a.every,
                                       out_rows=a.size, out_cols=a.size, d_colormap_ptr=table.data_ptr(), flip=a.flip, want_image=False)
+            elif a.tone or a.pitch:
+                res = eng.tones_blocks(wire[b * block_bytes: (b + nb) * block_bytes], a.cols, a.cols, tone_groups,
+                                       show=0 if a.tone else pkg.binding.TONES_SHOW_PITCH, first=first, every=a.every, out_rows=a.size,
+                                       out_cols=a.size, d_colormap_ptr=table.data_ptr(), flip=a.flip, want_image=False)
             elif a.coherence:
                 show = pkg.binding.COHERE_FACTOR if a.coherence == "factor" else pkg.binding.COHERE_WEIGHTED
                 res = eng.cohere_blocks(wire[b * block_bytes: (b + nb) * block_bytes], a.cols, a.cols, first=first, every=a.every, show=show,
