@@ -440,10 +440,45 @@ _TONES_SIGNATURES = {
 }
 TONES_SYMBOLS = tuple(_TONES_SIGNATURES)
 
+# cross-spectral maps: the entry points of include/awpu_hip_csm.h
+CSM_MAX_BINS = 8
+CSM_CONVENTIONAL, CSM_DIAGONAL_REMOVED, CSM_CAPON = 0, 1, 2
+
+
+class Csm(C.Structure):
+    """awpu_csm_t (include/awpu_hip_csm.h)."""
+    _fields_ = [
+        ("window", C.c_int32),
+        ("n_bins", C.c_int32),
+        ("bin", C.c_int32 * CSM_MAX_BINS),
+        ("kind", C.c_int32),
+        ("loading", C.c_float),
+    ]
+
+
+assert C.sizeof(Csm) == 48
+
+_CSM_MICS = [_i32p, C.c_int32]  # index, usable
+_CSM_SAMPLES = [_f32p, C.c_int64, C.c_int32, C.c_int32, *_CSM_MICS, _f32p, C.POINTER(Csm)]  # samples, pitch, n_streams, n_blocks, .., gain, c
+_CSM_TABLE = [_i32p, _f32p, C.c_int32, C.c_int32, *_CSM_MICS, C.POINTER(Csm)]  # off, frac, lut_stride, n_pixels, .., c
+_CSM_SIGNATURES = {
+    "awpu_hip_csm_spectra_host": (C.c_int, [*_CSM_SAMPLES, _f32p]),
+    "awpu_hip_csm_accumulate_host": (C.c_int, [*_CSM_SAMPLES, _f32p, _i32p]),
+    "awpu_hip_csm_steer_host": (C.c_int, [*_CSM_TABLE, _f32p]),
+    "awpu_hip_csm_map_host": (C.c_int, [_f32p, C.c_int32, *_CSM_TABLE, _f32p, _f32p]),
+    "awpu_hip_csm_invert_host": (C.c_int, [_f32p, C.c_int32, C.c_int32, C.POINTER(Csm), _f32p]),
+    "awpu_hip_csm_samples": (C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int32, C.POINTER(Csm), _f32p, _i32p, _f32p]),
+    "awpu_hip_csm_samples_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(Csm), C.c_void_p, _i32p, C.c_void_p,
+                                              C.c_void_p]),
+    "awpu_hip_csm_map": (C.c_int, [C.c_void_p, _f32p, C.c_int32, C.POINTER(Csm), _f32p, _f32p]),
+    "awpu_hip_csm_map_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Csm), C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+CSM_SYMBOLS = tuple(_CSM_SIGNATURES)
+
 # every table above, one per public header: what load() sets the types of
 _ALL_SIGNATURES = (_SIGNATURES, _TRACK_SIGNATURES, _BLOCK_SIGNATURES, _LISTEN_SIGNATURES, _WATCH_SIGNATURES, _FIND_SIGNATURES, _BAND_SIGNATURES,
                    _FOCUS_SIGNATURES, _SPECTRAL_SIGNATURES, _EXPOSE_SIGNATURES, _COHERE_SIGNATURES, _PEEL_SIGNATURES,
-                   _TONES_SIGNATURES)
+                   _TONES_SIGNATURES, _CSM_SIGNATURES)
 
 # numpy view of awpu_range_t: what range_pick, Engine.range and Engine.locate_* return (unused entries: index -1)
 RANGE_DTYPE = np.dtype([("index", "<i4"), ("power", "<f4"), ("distance", "<f8")], align=True)
@@ -973,6 +1008,109 @@ def tones_host(frames: np.ndarray, off: np.ndarray, frac: np.ndarray, groups, wi
     return {name: a[0] for name, a in out.items()} if single else out
 
 
+def csm_of(bins, window: int = TONES_RECT, kind: int = CSM_CONVENTIONAL, loading: float = 0.0) -> Csm:
+    """The Csm of a list of bins (or a Csm, passed through).  Nothing is judged here: the library refuses a bad request."""
+    if isinstance(bins, Csm):
+        return bins
+    c = Csm()
+    bins = [int(b) for b in np.atleast_1d(bins)]
+    c.window, c.n_bins, c.kind, c.loading = int(window), len(bins), int(kind), float(loading)
+    for i, b in enumerate(bins[:CSM_MAX_BINS]):
+        c.bin[i] = b
+    return c
+
+
+def _csm_samples(samples, index, gain, n_blocks):
+    """(samples [n_streams, pitch] as contiguous floats, index, gain or None, n_blocks) as the csm host calls take them."""
+    samples = np.ascontiguousarray(samples, np.float32)
+    if samples.ndim != 2:
+        raise ValueError("samples must be [n_streams, pitch]")
+    index = np.arange(samples.shape[0], dtype=np.int32) if index is None else np.ascontiguousarray(index, np.int32)
+    if gain is not None:
+        gain = np.ascontiguousarray(gain, np.float32)
+        if gain.shape != index.shape:
+            raise ValueError("gain must be [usable], in the active list's order")
+    return samples, index, gain, samples.shape[1] // 256 if n_blocks is None else int(n_blocks)
+
+
+def _csm_table(off, frac, index):
+    off = np.ascontiguousarray(off, np.int32)
+    frac = np.ascontiguousarray(frac, np.float32)
+    if off.ndim != 2 or off.shape != frac.shape:
+        raise ValueError("off and frac must be [n_pixels, lut_stride]")
+    index = np.arange(off.shape[1], dtype=np.int32) if index is None else np.ascontiguousarray(index, np.int32)
+    return off, frac, index
+
+
+def csm_spectra_host(samples: np.ndarray, bins, window: int = TONES_RECT, index=None, gain=None, n_blocks: Optional[int] = None) -> np.ndarray:
+    """Step 1 of the rule of include/awpu_hip_csm.h (awpu_hip_csm_spectra_host): samples [n_streams, pitch], the first n_blocks
+    blocks of 256 (default: all whole ones) -> spectra [n_blocks, n_bins, usable, 2]."""
+    c = csm_of(bins, window)
+    samples, index, gain, n_blocks = _csm_samples(samples, index, gain, n_blocks)
+    out = np.empty((max(n_blocks, 0), max(c.n_bins, 0), len(index), 2), np.float32)
+    _check(load().awpu_hip_csm_spectra_host(_f32(samples), samples.shape[1], samples.shape[0], n_blocks, _i32(index), len(index),
+                                            None if gain is None else _f32(gain), C.byref(c), _out_ptr(out, _f32p)), "awpu_hip_csm_spectra_host")
+    return out
+
+
+def csm_accumulate_host(samples: np.ndarray, bins, window: int = TONES_RECT, index=None, gain=None, matrix: Optional[np.ndarray] = None,
+                        block_count: int = 0, n_blocks: Optional[int] = None):
+    """Steps 1 and 2 (awpu_hip_csm_accumulate_host): adds the blocks of samples [n_streams, pitch] into `matrix`
+    [n_bins, usable, usable, 2] (default: a new one of zeros; one given is added into in place) -> (matrix, block_count + n_blocks)."""
+    c = csm_of(bins, window)
+    samples, index, gain, n_blocks = _csm_samples(samples, index, gain, n_blocks)
+    shape = (max(c.n_bins, 0), len(index), len(index), 2)
+    if matrix is None:
+        matrix = np.zeros(shape, np.float32)
+    if matrix.dtype != np.float32 or matrix.shape != shape or not matrix.flags.c_contiguous:
+        raise ValueError(f"matrix must be contiguous float32 {shape}")
+    count = C.c_int32(block_count)
+    _check(load().awpu_hip_csm_accumulate_host(_f32(samples), samples.shape[1], samples.shape[0], n_blocks, _i32(index), len(index),
+                                               None if gain is None else _f32(gain), C.byref(c), _out_ptr(matrix, _f32p),
+                                               C.cast(C.byref(count), _i32p)), "awpu_hip_csm_accumulate_host")
+    return matrix, count.value
+
+
+def csm_steer_host(off: np.ndarray, frac: np.ndarray, bins, index=None) -> np.ndarray:
+    """Step 3 (awpu_hip_csm_steer_host): off, frac [n_pixels, lut_stride] -> steer [n_pixels, n_bins, usable, 2]."""
+    c = csm_of(bins)
+    off, frac, index = _csm_table(off, frac, index)
+    out = np.empty((off.shape[0], max(c.n_bins, 0), len(index), 2), np.float32)
+    _check(load().awpu_hip_csm_steer_host(_i32(off), _f32(frac), off.shape[1], off.shape[0], _i32(index), len(index), C.byref(c),
+                                          _out_ptr(out, _f32p)), "awpu_hip_csm_steer_host")
+    return out
+
+
+def csm_map_host(matrix: np.ndarray, block_count: int, off: np.ndarray, frac: np.ndarray, bins, window: int = TONES_RECT,
+                 kind: int = CSM_CONVENTIONAL, index=None, want=("map",)):
+    """Steps 3 to 5 (awpu_hip_csm_map_host) of matrix [n_bins, usable, usable, 2] -- C with its block count, or for CSM_CAPON the
+    inverse csm_invert_host made -> a dict of the outputs named in `want`: "map" and "q", each [n_bins, n_pixels]."""
+    c = csm_of(bins, window, kind)
+    off, frac, index = _csm_table(off, frac, index)
+    matrix = np.ascontiguousarray(matrix, np.float32)
+    if matrix.shape != (max(c.n_bins, 0), len(index), len(index), 2):
+        raise ValueError("matrix must be [n_bins, usable, usable, 2]")
+    if not want or any(name not in ("map", "q") for name in want):
+        raise ValueError("want names some of ('map', 'q')")
+    out = {name: np.empty((max(c.n_bins, 0), off.shape[0]), np.float32) for name in ("map", "q") if name in want}
+    _check(load().awpu_hip_csm_map_host(_f32(matrix), int(block_count), _i32(off), _f32(frac), off.shape[1], off.shape[0], _i32(index), len(index),
+                                        C.byref(c), _out_ptr(out.get("map"), _f32p), _out_ptr(out.get("q"), _f32p)), "awpu_hip_csm_map_host")
+    return out
+
+
+def csm_invert_host(matrix: np.ndarray, block_count: int, bins, loading: float = 1e-3) -> np.ndarray:
+    """Step 6 (awpu_hip_csm_invert_host): the loaded inverse [n_bins, usable, usable, 2] of matrix with its block count, what
+    csm_map_host and Engine.csm_map take with kind=CSM_CAPON."""
+    c = csm_of(bins, TONES_RECT, CSM_CAPON, loading)
+    matrix = np.ascontiguousarray(matrix, np.float32)
+    if matrix.ndim != 4 or matrix.shape[0] != max(c.n_bins, 0) or matrix.shape[1] != matrix.shape[2] or matrix.shape[3] != 2:
+        raise ValueError("matrix must be [n_bins, usable, usable, 2]")
+    out = np.empty_like(matrix)
+    _check(load().awpu_hip_csm_invert_host(_f32(matrix), int(block_count), matrix.shape[1], C.byref(c), _out_ptr(out, _f32p)),
+           "awpu_hip_csm_invert_host")
+    return out
+
+
 class TonesResult:
     """What Engine.tones_blocks / tones_samples hand back: .image, .big, .power as a WatchResult has them -- of the shown group's
     plane or, with show=TONES_SHOW_PITCH, of the pitch row --, .sources and .count as a FindResult has them (None without `find`),
@@ -1258,8 +1396,10 @@ class Engine:
             _check(self._lib.awpu_hip_set_active_mics(self._h, None, n), "set_active_mics")
         else:
             index = np.ascontiguousarray(index, np.int32)
+            n = index.size
             _check(self._lib.awpu_hip_set_active_mics(self._h, _i32(index), index.size),
                    "set_active_mics")
+        self._usable = int(n)  # (what the cross-spectral calls size their matrices by)
 
     def ingest_block(self, datagrams) -> None:
         """One block of 256 wire datagrams (bytes-like, 256 x 1032 B; src/fpga/receiver.h:24-30)."""
@@ -1852,6 +1992,62 @@ class Engine:
                                                        C.c_void_p(d_power_ptr), C.c_void_p(d_sources_ptr), C.c_void_p(d_count_ptr),
                                                        C.c_void_p(stream)), "awpu_hip_tones_samples_device")
         return watch_count(n_blocks, first, every)[1]
+
+    def csm_samples(self, samples: np.ndarray, bins, window: int = TONES_RECT, matrix: Optional[np.ndarray] = None, block_count: int = 0,
+                    n_blocks: Optional[int] = None, want_spectra: bool = False):
+        """Steps 1 and 2 of include/awpu_hip_csm.h on the device (awpu_hip_csm_samples): the blocks of host samples [n_streams, pitch]
+        (the first n_blocks, default all whole ones) of the handle's active mics, with its gains, added into `matrix`
+        [n_bins, usable, usable, 2] (default: a new one of zeros) -> (matrix, block_count + n_blocks), and with want_spectra the
+        blocks' spectra [n_blocks, n_bins, usable, 2] as a third item."""
+        c = csm_of(bins, window)
+        samples = np.ascontiguousarray(samples, np.float32)
+        if samples.ndim != 2 or samples.shape[0] != self.cfg.n_streams:
+            raise ValueError(f"samples must be [{self.cfg.n_streams}, pitch]")
+        n_blocks = samples.shape[1] // 256 if n_blocks is None else int(n_blocks)
+        usable = getattr(self, "_usable", self.cfg.n_streams)
+        shape = (max(c.n_bins, 0), usable, usable, 2)
+        if matrix is None:
+            matrix = np.zeros(shape, np.float32)
+        if matrix.dtype != np.float32 or matrix.shape != shape or not matrix.flags.c_contiguous:
+            raise ValueError(f"matrix must be contiguous float32 {shape}")
+        spectra = np.empty((max(n_blocks, 0), shape[0], usable, 2), np.float32) if want_spectra else None
+        count = C.c_int32(block_count)
+        _check(self._lib.awpu_hip_csm_samples(self._h, _f32(samples), samples.shape[1], n_blocks, C.byref(c), _out_ptr(matrix, _f32p),
+                                              C.cast(C.byref(count), _i32p), _out_ptr(spectra, _f32p)), "awpu_hip_csm_samples")
+        return (matrix, count.value, spectra) if want_spectra else (matrix, count.value)
+
+    def csm_samples_device(self, d_samples_ptr: int, pitch: int, n_blocks: int, bins, d_matrix_ptr: int, window: int = TONES_RECT,
+                           block_count: int = 0, d_spectra_ptr: int = 0, stream: int = 0) -> int:
+        """The same on device pointers (samples [n_streams, pitch], matrix [n_bins, usable, usable, 2] added into, spectra
+        [n_blocks, n_bins, usable, 2] or 0) on `stream`; asynchronous -> block_count + n_blocks (awpu_hip_csm_samples_device)."""
+        c = csm_of(bins, window)
+        count = C.c_int32(block_count)
+        _check(self._lib.awpu_hip_csm_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, C.byref(c), C.c_void_p(d_matrix_ptr),
+                                                     C.cast(C.byref(count), _i32p), C.c_void_p(d_spectra_ptr), C.c_void_p(stream)),
+               "awpu_hip_csm_samples_device")
+        return count.value
+
+    def csm_map(self, matrix: np.ndarray, block_count: int, bins, window: int = TONES_RECT, kind: int = CSM_CONVENTIONAL, want=("map",)):
+        """Steps 3 to 5 on the device with the handle's table and active mics (awpu_hip_csm_map): matrix [n_bins, usable, usable, 2]
+        as csm_map_host takes it -> a dict of the outputs in `want`: "map" and "q", each [n_bins, pixels]."""
+        c = csm_of(bins, window, kind)
+        matrix = np.ascontiguousarray(matrix, np.float32)
+        usable = getattr(self, "_usable", self.cfg.n_streams)
+        if matrix.shape != (max(c.n_bins, 0), usable, usable, 2):
+            raise ValueError(f"matrix must be [{max(c.n_bins, 0)}, {usable}, {usable}, 2]")
+        if not want or any(name not in ("map", "q") for name in want):
+            raise ValueError("want names some of ('map', 'q')")
+        out = {name: np.empty((max(c.n_bins, 0), self.pixel_count), np.float32) for name in ("map", "q") if name in want}
+        _check(self._lib.awpu_hip_csm_map(self._h, _f32(matrix), int(block_count), C.byref(c), _out_ptr(out.get("map"), _f32p),
+                                          _out_ptr(out.get("q"), _f32p)), "awpu_hip_csm_map")
+        return out
+
+    def csm_map_device(self, d_matrix_ptr: int, block_count: int, bins, window: int = TONES_RECT, kind: int = CSM_CONVENTIONAL,
+                       d_map_ptr: int = 0, d_q_ptr: int = 0, stream: int = 0) -> None:
+        """The same on device pointers (map and q [n_bins, pixels], each or 0) on `stream`; asynchronous (awpu_hip_csm_map_device)."""
+        c = csm_of(bins, window, kind)
+        _check(self._lib.awpu_hip_csm_map_device(self._h, C.c_void_p(d_matrix_ptr), int(block_count), C.byref(c), C.c_void_p(d_map_ptr),
+                                                 C.c_void_p(d_q_ptr), C.c_void_p(stream)), "awpu_hip_csm_map_device")
 
     def range(self, theta, phi, distance, d_frame_ptr: int = 0):
         """The beam power of every direction (theta[k], phi[k]) focused at every candidate distance[j] (metres, inf = a plane wave),

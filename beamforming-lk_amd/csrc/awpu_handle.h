@@ -401,6 +401,9 @@ struct awpu_hip {
     // [batch][n_groups][pixel_count], then pitch [batch][pixel_count]
     Dev<float> d_tones_tables;
     Dev<float> d_tones_out;
+    // cross-spectral maps (awpu_hip_csm.h; awpu_csm.cpp): the spectra of the blocks being accumulated where the caller keeps none,
+    // and what a host-form call brings up and back (samples or a matrix in, the matrix or the planes out)
+    Dev<float> d_csm_spectra, d_csm_io;
     // peeling (awpu_hip_peel.h; awpu_peel.cpp): the table's reach at the active mics, valid for the tables of peel_gen (table_gen;
     // 0: none yet); the loop's residual frames [batch][n_streams][hist] where the caller keeps none, its power row P_k
     // [batch][pixel_count], its bookkeeping (PeelState [batch]), and the results of a host-form call on their way back

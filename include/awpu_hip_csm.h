@@ -1,0 +1,142 @@
+/*
+ * awpu_hip_csm.h -- cross-spectral maps: conventional, diagonal-removed and Capon beamforming on the cross-spectral matrix (CSM) of
+ * a recording.  Every other map of the library comes from the time-domain delay-and-sum sweep, and none of them narrows the main
+ * lobe below what delay-and-sum gives: at 3 kHz the wavelength is 11 cm and the 8 x 8 array is 14 cm across, so two sources of one
+ * bin that are closer than a beam width are one blob in the power map, the tone map, the coherence map and the peel run.  The
+ * usual answer in array acoustics is the quadratic form P(p, k) = s^H C_k s on the matrix C_k of the microphones' cross spectra:
+ * with C as it is, the conventional map; without C's diagonal, a map free of uncorrelated microphone self-noise (wind, preamp),
+ * which no sweep here can remove; with a loaded inverse of C in the same form, Capon's minimum-variance map 1 / (s^H C^-1 s), which
+ * resolves two incoherent sources that delay-and-sum merges.  The reference has nothing like this; nothing of it is replaced.
+ *
+ * THE RULE.  Plain fp32 with one arithmetic: it does not depend on cfg.math.  Every step is written with explicit fmaf and no
+ * contraction.  The only tables are awpu_hip_tones_window's w[256] and awpu_hip_tones_twiddles' t[128] (awpu_hip_tones.h); t_j
+ * below is e^{-j 2 pi j / 256}: t[j] for j < 128 and the negation of t[j - 128] (both parts) for j >= 128.  Nothing evaluates a
+ * cosine on the device.
+ *
+ *   1. Spectra.  A block is 256 consecutive samples x[0..255] of one mic; no history and no ring are involved.  For the mic at
+ *      position a of the active list and bin k = c->bin[..]:
+ *          v = x[i] * w[i]                 (with gains: (x[i] * g) * w[i], two rounded products, staged as the sweeps stage them)
+ *          j = (k * i) & 255;   re = fmaf(v, t_j.re, re);   im = fmaf(v, t_j.im, im);      i ascending, from re = im = +0
+ *   2. Accumulate.  C[k][a][b], a and b positions of the active list, is an unnormalised sum over blocks in block order.  For
+ *      b < a, with Xa and Xb the block's spectra, in this order:
+ *          re = fmaf(Xa.re, Xb.re, re);   re = fmaf(Xa.im, Xb.im, re);   im = fmaf(Xa.im, Xb.re, im);   im = fmaf(-Xa.re, Xb.im, im)
+ *      (Xa conj(Xb)).  The diagonal accumulates re the same way (b = a) and its im is written as +0.  C[k][b][a] is written as the
+ *      exact conjugate (re, -im) of C[k][a][b]; only the diagonal and the entries b < a are ever read.  The call adds into the
+ *      caller's matrix and into the caller's block count: a recording split over several calls gives the bits of one call.
+ *   3. Steering.  For pixel p, mic id m = index[a] and bin k, from the table's off and frac:
+ *          n = 256 - off;  f = frac;  g = (float) k * f;  gi = (int) g;  gf = g - (float) gi;  j = (k * n + gi) & 255  (unsigned)
+ *          th = gf * 0.024543693f          ((float) (2 pi / 256): the small angle left over, at most 0.0246 rad)
+ *          t2 = th * th
+ *          cr = fmaf(t2, 1/24, -0.5f);    cr = fmaf(cr, t2, 1.0f)                                      (cos th, degree 4)
+ *          sn = fmaf(t2, 1/120, -1/6);    sn = fmaf(sn, t2, 1.0f);    sn = sn * th                     (sin th, degree 5)
+ *          s.re = t_j.re * cr + t_j.im * sn;      s.im = t_j.im * cr - t_j.re * sn           (every product rounded, then one + or -)
+ *      with 1/24, 1/120 and 1/6 the nearest floats.  s = e^{-j 2 pi k tau / 256} with tau = n + f.  The constant one-sample shift
+ *      of delay() is a phase common to all mics, and the rule drops it.
+ *   4. The quadratic form of a Hermitian matrix H (C, or the G of step 6), per pixel and bin:
+ *          y_a = sum over b < a, b ascending, of H[a][b] conj(s_b), from +0:
+ *              y.re = fmaf(H.re, s_b.re, y.re);  y.re = fmaf(H.im, s_b.im, y.re);  y.im = fmaf(H.im, s_b.re, y.im);  y.im = fmaf(-H.re, s_b.im, y.im)
+ *          d = sum over a ascending of H[a][a].re, plain additions from +0
+ *          x = sum over a ascending of Re(s_a y_a), from +0:   x = fmaf(s_a.re, y_a.re, x);   x = fmaf(-s_a.im, y_a.im, x)
+ *          q = d + (x + x);     AWPU_CSM_DIAGONAL_REMOVED:  q = x + x
+ *   5. The maps.  c_0 = c_128 = 1.0f, every other c_k = 2.0f; wss = 256.0f (RECT) or 96.0f (HANN), as in the tones rule:
+ *          conventional        map = (c_k * q) / (wss * 256.0f * ((float) (usable * usable) * (float) n_blocks))
+ *          diagonal-removed    the same with usable * (usable - 1); a result below zero becomes +0; usable == 1 is refused
+ *          Capon               map = q > 0 ? c_k / ((wss * 256.0f) * q) : +0,   with H = G
+ *      With the rectangular window a unit-amplitude sine at a bin centre that arrives from p gives 0.5 in the first two maps and
+ *      0.5 (1 + loading / usable) in Capon's.
+ *   6. G = awpu_hip_csm_invert_host(C): per bin, in double, A = C / n_blocks + loading * (trace(C / n_blocks) / usable) * I, a
+ *      Cholesky factorisation and the inverse from it, rounded to float; Hermitian exactly by mirroring the entries b < a, with an
+ *      exactly real diagonal.  Host only: usable^3 work per bin.
+ *
+ * The device forms perform these operations on these operands: spectra, C, q and the maps equal the host functions' bit for bit
+ * wherever the values are finite or infinite; where a NaN arises host and device agree on WHERE, not on its sign and payload.
+ *
+ * The planes are power rows: awpu_hip_heatmap_u8, the upscale and awpu_hip_find_peaks take them as they are.  Runs with images are
+ * out of scope here, and so is a device version of step 6.
+ *
+ * Conventions are those of awpu_hip.h (status codes, host pointers owned by the caller, one thread per handle).
+ */
+#ifndef AWPU_HIP_CSM_H
+#define AWPU_HIP_CSM_H
+
+#include "awpu_hip_tones.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define AWPU_CSM_MAX_BINS 8
+#define AWPU_CSM_CONVENTIONAL 0
+#define AWPU_CSM_DIAGONAL_REMOVED 1
+#define AWPU_CSM_CAPON 2
+
+/* What to map: 48 bytes.  window is AWPU_TONES_RECT or AWPU_TONES_HANN; n_bins lies in [1, 8]; bin[0 .. n_bins) is strictly
+ * ascending inside [0, 128]; kind is one of the three above; loading is finite and >= 0 and is read by awpu_hip_csm_invert_host
+ * alone.  Anything else: AWPU_ERR_INVALID with nothing written. */
+typedef struct awpu_csm {
+    int32_t window;
+    int32_t n_bins;
+    int32_t bin[AWPU_CSM_MAX_BINS];
+    int32_t kind;
+    float loading;
+} awpu_csm_t;
+
+/* The rule as executable C: pure host code, no handle.  samples [n_streams][pitch] as awpu_hip_process_samples takes them, block b
+ * of stream m at samples[m * pitch + 256 * b]; index [usable] stream ids, gain [usable] in the list's order or NULL; off / frac
+ * [n_pixels][lut_stride] by stream id.  Refusals follow awpu_hip_cohere_host: a null input or output, a bad c, counts below 1, a
+ * pitch below 256 * n_blocks, an index outside the streams (or the table's row), a frac outside [0, 1] or an off below 0 give
+ * AWPU_ERR_INVALID.  Nothing is written on refusal.
+ *
+ * Step 1: spectra [n_blocks][n_bins][usable][2]. */
+int awpu_hip_csm_spectra_host(const float *samples, int64_t pitch, int32_t n_streams, int32_t n_blocks, const int32_t *index, int32_t usable,
+                              const float *gain, const awpu_csm_t *c, float *spectra);
+
+/* Steps 1 and 2: adds the blocks into matrix [n_bins][usable][usable][2] and n_blocks into *block_count (both the caller's: zero
+ * them before the first call).  A *block_count below 0, or one that would pass 2^31 - 1: AWPU_ERR_INVALID. */
+int awpu_hip_csm_accumulate_host(const float *samples, int64_t pitch, int32_t n_streams, int32_t n_blocks, const int32_t *index, int32_t usable,
+                                 const float *gain, const awpu_csm_t *c, float *matrix, int32_t *block_count);
+
+/* Step 3: steer [n_pixels][n_bins][usable][2]. */
+int awpu_hip_csm_steer_host(const int32_t *off, const float *frac, int32_t lut_stride, int32_t n_pixels, const int32_t *index, int32_t usable,
+                            const awpu_csm_t *c, float *steer);
+
+/* Steps 3 to 5 on matrix [n_bins][usable][usable][2] -- C with its block count, or for AWPU_CSM_CAPON the G of step 6 (the count
+ * is then not read, but must still be >= 1): map [n_bins][n_pixels] and q [n_bins][n_pixels], each or NULL, not both.
+ * AWPU_CSM_DIAGONAL_REMOVED with usable == 1: AWPU_ERR_INVALID. */
+int awpu_hip_csm_map_host(const float *matrix, int32_t block_count, const int32_t *off, const float *frac, int32_t lut_stride, int32_t n_pixels,
+                          const int32_t *index, int32_t usable, const awpu_csm_t *c, float *map, float *q);
+
+/* Step 6: inverse [n_bins][usable][usable][2] of matrix with its block count (>= 1).  Of matrix the diagonal's real parts and the
+ * entries b < a are read.  A bin whose loaded matrix is not positive definite (or not finite): AWPU_ERR_RANGE, nothing written. */
+int awpu_hip_csm_invert_host(const float *matrix, int32_t block_count, int32_t usable, const awpu_csm_t *c, float *inverse);
+
+/* The handle forms use the handle's delay table, active list and gains; a slab handle (pixel_count < n_pixels) maps its own
+ * pixels: planes of pixel_count floats.  An AWPU_MATH_F32_FAST handle builds its off / frac table as the coherence sweep does
+ * (awpu_hip_cohere.h): a blocking copy in the first call, made before the call enqueues anything; the first call on a handle uploads
+ * the two tables of the rule in the same way.  AWPU_INTERP_FIR8, a band set on the handle (awpu_hip_band.h), a device group and a
+ * call while an awpu_hip_process_async call is in flight: AWPU_ERR_STATE.  These calls leave awpu_hip_stats' kernel_variant alone.
+ *
+ * awpu_hip_csm_samples: steps 1 and 2 of host samples [n_streams][pitch] into the host matrix and *block_count, as
+ * awpu_hip_csm_accumulate_host adds them; spectra [n_blocks][n_bins][usable][2] or NULL.  Synchronous. */
+int awpu_hip_csm_samples(awpu_hip_t *h, const float *samples, int64_t pitch, int32_t n_blocks, const awpu_csm_t *c, float *matrix,
+                         int32_t *block_count, float *spectra);
+
+/* ... on device buffers (d_samples, d_matrix, d_spectra; block_count stays a host pointer and is updated before the call
+ * returns), enqueued on `stream` (a hipStream_t, NULL = the handle's own); asynchronous. */
+int awpu_hip_csm_samples_device(awpu_hip_t *h, const float *d_samples, int64_t pitch, int32_t n_blocks, const awpu_csm_t *c, float *d_matrix,
+                                int32_t *block_count, float *d_spectra, void *stream);
+
+/* Steps 3 to 5 of a host matrix [n_bins][usable][usable][2] with its block count, as awpu_hip_csm_map_host takes them: host map
+ * [n_bins][pixel_count] and q [n_bins][pixel_count], each or NULL, not both.  Synchronous.  More active mics than the kernel can
+ * keep steering vectors for in one compute unit's LDS (2048): AWPU_ERR_RANGE. */
+int awpu_hip_csm_map(awpu_hip_t *h, const float *matrix, int32_t block_count, const awpu_csm_t *c, float *map, float *q);
+
+/* ... on device buffers, enqueued on `stream`; asynchronous.  *c is read before the call returns. */
+int awpu_hip_csm_map_device(awpu_hip_t *h, const float *d_matrix, int32_t block_count, const awpu_csm_t *c, float *d_map, float *d_q,
+                            void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* AWPU_HIP_CSM_H */
