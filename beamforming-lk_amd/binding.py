@@ -475,10 +475,33 @@ _CSM_SIGNATURES = {
 }
 CSM_SYMBOLS = tuple(_CSM_SIGNATURES)
 
+# the loaded inverse with a written arithmetic (step 6a): the entry points of include/awpu_hip_csm_invert.h
+CSM_INVERT_MAX_MICS = 512
+_CSM_INVERT_SIGNATURES = {
+    "awpu_hip_csm_invert_rule_host": (C.c_int, [_f32p, C.c_int32, C.c_int32, C.POINTER(Csm), _f32p, _i32p]),
+    "awpu_hip_csm_invert": (C.c_int, [C.c_void_p, _f32p, C.c_int32, C.POINTER(Csm), _f32p]),
+    "awpu_hip_csm_invert_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Csm), C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+CSM_INVERT_SYMBOLS = tuple(_CSM_INVERT_SIGNATURES)
+
+# cross-spectral runs: the entry points of include/awpu_hip_csm_watch.h
+CSM_SHOW_SUM = -1
+CSM_MAX_LENGTH = 1024
+# w, c, length, show, f, carry, carried, then image, big_image, power, sources, count, planes, solved
+_CSM_WATCH_HOST = [C.POINTER(Watch), C.POINTER(Csm), C.c_int32, C.c_int32, C.POINTER(Find), _f32p, _i32p, _u8p, _u8p, _f32p, C.c_void_p,
+                   C.c_void_p, _f32p, _i32p]
+_CSM_WATCH_SIGNATURES = {
+    "awpu_hip_csm_watch_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, *_CSM_WATCH_HOST]),
+    "awpu_hip_csm_watch_samples": (C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int32, *_CSM_WATCH_HOST]),
+    "awpu_hip_csm_watch_samples_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(Watch), C.POINTER(Csm), C.c_int32,
+                                                    C.c_int32, C.POINTER(Find), C.c_void_p, _i32p, *([C.c_void_p] * 8)]),
+}
+CSM_WATCH_SYMBOLS = tuple(_CSM_WATCH_SIGNATURES)
+
 # every table above, one per public header: what load() sets the types of
 _ALL_SIGNATURES = (_SIGNATURES, _TRACK_SIGNATURES, _BLOCK_SIGNATURES, _LISTEN_SIGNATURES, _WATCH_SIGNATURES, _FIND_SIGNATURES, _BAND_SIGNATURES,
                    _FOCUS_SIGNATURES, _SPECTRAL_SIGNATURES, _EXPOSE_SIGNATURES, _COHERE_SIGNATURES, _PEEL_SIGNATURES,
-                   _TONES_SIGNATURES, _CSM_SIGNATURES)
+                   _TONES_SIGNATURES, _CSM_SIGNATURES, _CSM_INVERT_SIGNATURES, _CSM_WATCH_SIGNATURES)
 
 # numpy view of awpu_range_t: what range_pick, Engine.range and Engine.locate_* return (unused entries: index -1)
 RANGE_DTYPE = np.dtype([("index", "<i4"), ("power", "<f4"), ("distance", "<f8")], align=True)
@@ -1109,6 +1132,68 @@ def csm_invert_host(matrix: np.ndarray, block_count: int, bins, loading: float =
     _check(load().awpu_hip_csm_invert_host(_f32(matrix), int(block_count), matrix.shape[1], C.byref(c), _out_ptr(out, _f32p)),
            "awpu_hip_csm_invert_host")
     return out
+
+
+def _csm_square(matrix, c) -> np.ndarray:
+    matrix = np.ascontiguousarray(matrix, np.float32)
+    if matrix.ndim != 4 or matrix.shape[0] != max(c.n_bins, 0) or matrix.shape[1] != matrix.shape[2] or matrix.shape[3] != 2:
+        raise ValueError("matrix must be [n_bins, usable, usable, 2]")
+    return matrix
+
+
+def csm_invert_rule_host(matrix: np.ndarray, block_count: int, bins, loading: float = 1e-3):
+    """Step 6a (awpu_hip_csm_invert_rule_host): the loaded inverse by the written arithmetic, what Engine.csm_invert_device gives
+    bit for bit -> (inverse [n_bins, usable, usable, 2], solved [n_bins] int32).  An unsolved bin is +0 with solved 0, no error."""
+    c = csm_of(bins, TONES_RECT, CSM_CAPON, loading)
+    matrix = _csm_square(matrix, c)
+    out = np.empty_like(matrix)
+    solved = np.empty(max(c.n_bins, 0), np.int32)
+    _check(load().awpu_hip_csm_invert_rule_host(_f32(matrix), int(block_count), matrix.shape[1], C.byref(c), _out_ptr(out, _f32p),
+                                                _out_ptr(solved, _i32p)), "awpu_hip_csm_invert_rule_host")
+    return out, solved
+
+
+class CsmWatchResult:
+    """What Engine.csm_watch_blocks / csm_watch_samples hand back: .image, .big, .power as a WatchResult has them -- of the shown
+    row --, .sources and .count as a FindResult has them (None without `find`), .planes [n_frames, n_bins, pixels] and .solved
+    [n_frames, n_bins] (None unless asked for), .next_first, and .carry / .carried for the call that continues the run."""
+
+    def __init__(self, image, big, power, sources, count, planes, solved, next_first: int, carry, carried: int):
+        self.image, self.big, self.power, self.sources, self.count = image, big, power, sources, count
+        self.planes, self.solved, self.next_first, self.carry, self.carried = planes, solved, next_first, carry, carried
+
+    def __len__(self):
+        return len(next(a for a in (self.image, self.big, self.power, self.count, self.planes, self.solved) if a is not None))
+
+
+def csm_from_text(text: str, sample_rate: float = 48828.125):
+    """'LO:HI[:hann]' (Hz; the rectangular window unless 'hann' is given), as the tools' --csm takes it -> (bins, window): the
+    transform bins whose centres lie in [LO, HI).  More than CSM_MAX_BINS of them is a ValueError that names the limit."""
+    parts = text.split(":")
+    if len(parts) not in (2, 3) or (len(parts) == 3 and parts[2] != "hann"):
+        raise ValueError(f"csm '{text}': LO:HI or LO:HI:hann, in Hz")
+    lo, hi = float(parts[0]), float(parts[1])
+    if not 0.0 <= lo < hi:
+        raise ValueError(f"csm '{text}': 0 <= LO < HI")
+    step = sample_rate / 256
+    bins = [k for k in range(129) if lo <= k * step < hi]
+    if not bins:
+        raise ValueError(f"csm '{text}': no bin of {step:.1f} Hz has its centre in that range")
+    if len(bins) > CSM_MAX_BINS:
+        raise ValueError(f"csm '{text}': {len(bins)} bins of {step:.1f} Hz have their centres in that range; a cross-spectral map takes at most {CSM_MAX_BINS}")
+    return bins, TONES_HANN if len(parts) == 3 else TONES_RECT
+
+
+def csm_kind_from_text(text: str):
+    """'conventional', 'diagonal-removed' or 'capon[:LOADING]' (1e-2 unless given), as the tools' --csm-kind takes it -> (kind, loading)."""
+    name, _, loading = text.partition(":")
+    kinds = {"conventional": CSM_CONVENTIONAL, "diagonal-removed": CSM_DIAGONAL_REMOVED, "capon": CSM_CAPON}
+    if name not in kinds or (loading and name != "capon"):
+        raise ValueError(f"csm kind '{text}': conventional, diagonal-removed or capon[:LOADING]")
+    value = float(loading) if loading else 1e-2
+    if not 0.0 <= value < float("inf"):
+        raise ValueError(f"csm kind '{text}': LOADING is finite and not negative")
+    return kinds[name], value
 
 
 class TonesResult:
@@ -1993,6 +2078,72 @@ class Engine:
                                                        C.c_void_p(stream)), "awpu_hip_tones_samples_device")
         return watch_count(n_blocks, first, every)[1]
 
+    def _csm_watch(self, call, where, n_blocks, rows, cols, bins, window, kind, loading, length, show, first, every, carry, carried, out_rows,
+                   out_cols, d_colormap_ptr, flip, want_image, want_power, want_planes, want_solved, find) -> CsmWatchResult:
+        n_frames, next_first = watch_count(n_blocks, first, every)
+        w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(d_colormap_ptr))
+        c = csm_of(bins, window, kind, loading)
+        f = _find_struct(rows, cols, find)
+        usable = getattr(self, "_usable", self.cfg.n_streams)
+        shape = (max(int(length) - 1, 0), max(c.n_bins, 0), usable, 2)
+        carry = np.zeros(shape, np.float32) if carry is None else np.ascontiguousarray(carry, np.float32).copy()
+        if carry.shape != shape:
+            raise ValueError(f"carry must be {shape}")
+        held = C.c_int32(int(carried))
+        shown, ptrs = self._shown_outputs(n_frames, w, want_image, want_power, f)
+        planes = np.empty((n_frames, max(c.n_bins, 0), self.pixel_count), np.float32) if want_planes else None
+        solved = np.empty((n_frames, max(c.n_bins, 0)), np.int32) if want_solved else None
+        _check(call(n_blocks, C.byref(w), C.byref(c), int(length), int(show), None if f is None else C.byref(f), _out_ptr(carry, _f32p),
+                    C.cast(C.byref(held), _i32p), *ptrs, _out_ptr(planes, _f32p), _out_ptr(solved, _i32p)), where)
+        return CsmWatchResult(*shown, planes, solved, next_first, carry, held.value)
+
+    def csm_watch_blocks(self, wire, rows: int, cols: int, bins, window: int = TONES_RECT, kind: int = CSM_CONVENTIONAL, loading: float = 1e-3,
+                         length: int = 64, show: int = CSM_SHOW_SUM, first: int = 0, every: int = 1, carry=None, carried: int = 0,
+                         out_rows: int = 0, out_cols: int = 0, d_colormap_ptr: int = 0, flip: bool = False, stride: int = DATAGRAM_BYTES,
+                         want_image: bool = True, want_power: bool = False, want_planes: bool = False, want_solved: bool = False,
+                         find: Optional[dict] = None) -> CsmWatchResult:
+        """Watch a run of consecutive blocks of wire datagrams (as watch_blocks takes them) through the cross-spectral maps
+        (awpu_hip_csm_watch_blocks): every shown frame is the map of the `length` blocks that end with it -- the plane of bin index
+        `show`, or with CSM_SHOW_SUM the planes added up --, conventional, diagonal-removed or Capon's.  `find` also finds the
+        sources of every frame.  -> CsmWatchResult; pass its .next_first, .carry and .carried to the call that continues the run."""
+        buf, n_blocks = _wire_blocks(wire, stride)
+        return self._csm_watch(lambda *rest: self._lib.awpu_hip_csm_watch_blocks(self._h, buf.ctypes.data_as(C.c_void_p), stride, *rest),
+                               "awpu_hip_csm_watch_blocks", n_blocks, rows, cols, bins, window, kind, loading, length, show, first, every, carry,
+                               carried, out_rows, out_cols, d_colormap_ptr, flip, want_image, want_power, want_planes, want_solved, find)
+
+    def csm_watch_samples(self, samples: np.ndarray, rows: int, cols: int, bins, window: int = TONES_RECT, kind: int = CSM_CONVENTIONAL,
+                          loading: float = 1e-3, length: int = 64, show: int = CSM_SHOW_SUM, first: int = 0, every: int = 1, carry=None,
+                          carried: int = 0, out_rows: int = 0, out_cols: int = 0, d_colormap_ptr: int = 0, flip: bool = False,
+                          want_image: bool = True, want_power: bool = False, want_planes: bool = False, want_solved: bool = False,
+                          find: Optional[dict] = None) -> CsmWatchResult:
+        """The same from unpacked samples [n_streams, N] (N a multiple of 256, oldest first) (awpu_hip_csm_watch_samples)."""
+        samples, n_blocks = self._sample_blocks(samples)
+        return self._csm_watch(lambda *rest: self._lib.awpu_hip_csm_watch_samples(self._h, _f32(samples), samples.shape[1], *rest),
+                               "awpu_hip_csm_watch_samples", n_blocks, rows, cols, bins, window, kind, loading, length, show, first, every, carry,
+                               carried, out_rows, out_cols, d_colormap_ptr, flip, want_image, want_power, want_planes, want_solved, find)
+
+    def csm_watch_samples_device(self, d_samples_ptr: int, pitch: int, n_blocks: int, rows: int, cols: int, bins, window: int = TONES_RECT,
+                                 kind: int = CSM_CONVENTIONAL, loading: float = 1e-3, length: int = 64, show: int = CSM_SHOW_SUM,
+                                 first: int = 0, every: int = 1, d_carry_ptr: int = 0, carried: int = 0, d_image_ptr: int = 0,
+                                 d_big_ptr: int = 0, d_power_ptr: int = 0, d_sources_ptr: int = 0, d_count_ptr: int = 0,
+                                 d_planes_ptr: int = 0, d_solved_ptr: int = 0, out_rows: int = 0, out_cols: int = 0, d_colormap_ptr: int = 0,
+                                 flip: bool = False, stream: int = 0, find: Optional[dict] = None):
+        """The same on device pointers (samples [n_streams, pitch]; carry [length - 1, n_bins, usable, 2]; image, big, power, sources
+        and count as tones_samples_device takes them; planes [n_frames, n_bins, pixels] and solved [n_frames, n_bins], each or 0) on
+        `stream`; asynchronous.  -> (next_first, carried) for the call that continues the run
+        (awpu_hip_csm_watch_samples_device)."""
+        w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(d_colormap_ptr))
+        c = csm_of(bins, window, kind, loading)
+        f = _find_struct(rows, cols, find)
+        held = C.c_int32(int(carried))
+        _check(self._lib.awpu_hip_csm_watch_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, C.byref(w), C.byref(c), int(length),
+                                                           int(show), None if f is None else C.byref(f), C.c_void_p(d_carry_ptr),
+                                                           C.cast(C.byref(held), _i32p), C.c_void_p(d_image_ptr), C.c_void_p(d_big_ptr),
+                                                           C.c_void_p(d_power_ptr), C.c_void_p(d_sources_ptr), C.c_void_p(d_count_ptr),
+                                                           C.c_void_p(d_planes_ptr), C.c_void_p(d_solved_ptr), C.c_void_p(stream)),
+               "awpu_hip_csm_watch_samples_device")
+        return watch_count(n_blocks, first, every)[1], held.value
+
     def csm_samples(self, samples: np.ndarray, bins, window: int = TONES_RECT, matrix: Optional[np.ndarray] = None, block_count: int = 0,
                     n_blocks: Optional[int] = None, want_spectra: bool = False):
         """Steps 1 and 2 of include/awpu_hip_csm.h on the device (awpu_hip_csm_samples): the blocks of host samples [n_streams, pitch]
@@ -2041,6 +2192,26 @@ class Engine:
         _check(self._lib.awpu_hip_csm_map(self._h, _f32(matrix), int(block_count), C.byref(c), _out_ptr(out.get("map"), _f32p),
                                           _out_ptr(out.get("q"), _f32p)), "awpu_hip_csm_map")
         return out
+
+    def csm_invert(self, matrix: np.ndarray, block_count: int, bins, loading: float = 1e-3) -> np.ndarray:
+        """Step 6a on the device (awpu_hip_csm_invert): the loaded inverse [n_bins, usable, usable, 2] of a host matrix, the bits
+        of csm_invert_rule_host.  An unsolved bin raises AwpuError (ERR_RANGE)."""
+        c = csm_of(bins, TONES_RECT, CSM_CAPON, loading)
+        matrix = _csm_square(matrix, c)
+        usable = getattr(self, "_usable", self.cfg.n_streams)
+        if matrix.shape[1] != usable:
+            raise ValueError(f"matrix must be [n_bins, {usable}, {usable}, 2]")
+        out = np.empty_like(matrix)
+        _check(self._lib.awpu_hip_csm_invert(self._h, _f32(matrix), int(block_count), C.byref(c), _out_ptr(out, _f32p)), "awpu_hip_csm_invert")
+        return out
+
+    def csm_invert_device(self, d_matrix_ptr: int, block_count: int, bins, d_inverse_ptr: int, loading: float = 1e-3, d_solved_ptr: int = 0,
+                          stream: int = 0) -> None:
+        """The same on device pointers (d_solved [n_bins] int32 or 0) on `stream`; asynchronous, and an unsolved bin is +0 with
+        solved 0, no error (awpu_hip_csm_invert_device)."""
+        c = csm_of(bins, TONES_RECT, CSM_CAPON, loading)
+        _check(self._lib.awpu_hip_csm_invert_device(self._h, C.c_void_p(d_matrix_ptr), int(block_count), C.byref(c), C.c_void_p(d_inverse_ptr),
+                                                    C.c_void_p(d_solved_ptr), C.c_void_p(stream)), "awpu_hip_csm_invert_device")
 
     def csm_map_device(self, d_matrix_ptr: int, block_count: int, bins, window: int = TONES_RECT, kind: int = CSM_CONVENTIONAL,
                        d_map_ptr: int = 0, d_q_ptr: int = 0, stream: int = 0) -> None:

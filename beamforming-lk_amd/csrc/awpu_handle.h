@@ -404,6 +404,12 @@ struct awpu_hip {
     // cross-spectral maps (awpu_hip_csm.h; awpu_csm.cpp): the spectra of the blocks being accumulated where the caller keeps none,
     // and what a host-form call brings up and back (samples or a matrix in, the matrix or the planes out)
     Dev<float> d_csm_spectra, d_csm_io;
+    // ... and the loaded inverse's scratch (awpu_csm.cpp; csm_invert_kernels.h): the factor L and its inverse M in double,
+    // [n_bins][usable][usable][2] each, then the bins' state words
+    Dev<double> d_csm_invert;
+    // ... and a cross-spectral run's (awpu_hip_csm_watch.h): the spectra store, the carry, one frame's matrix and inverse, a piece's
+    // rows, planes and solved words, a chunk's samples (csm_watch_run lays it out)
+    Dev<float> d_csm_run;
     // peeling (awpu_hip_peel.h; awpu_peel.cpp): the table's reach at the active mics, valid for the tables of peel_gen (table_gen;
     // 0: none yet); the loop's residual frames [batch][n_streams][hist] where the caller keeps none, its power row P_k
     // [batch][pixel_count], its bookkeeping (PeelState [batch]), and the results of a host-form call on their way back

@@ -59,4 +59,9 @@ inline int csm_map_pixels_per_wave(int usable) {
 }
 hipError_t launch_csm_map(const CsmMapArgs &a, hipStream_t stream);  // hipErrorInvalidValue where the mics do not fit
 
+
+// The row a run shows of one frame's planes [n_bins][pixel_count] (csm_show_kernels.hip): the plane of bin `show`, or with show
+// < 0 the planes added in ascending bin order with plain additions, from +0.
+hipError_t launch_csm_show(const float *planes, int n_bins, int pixel_count, int show, float *row, hipStream_t stream);
+
 }  // namespace awpu

@@ -46,13 +46,36 @@
  *      0.5 (1 + loading / usable) in Capon's.
  *   6. G = awpu_hip_csm_invert_host(C): per bin, in double, A = C / n_blocks + loading * (trace(C / n_blocks) / usable) * I, a
  *      Cholesky factorisation and the inverse from it, rounded to float; Hermitian exactly by mirroring the entries b < a, with an
- *      exactly real diagonal.  Host only: usable^3 work per bin.
+ *      exactly real diagonal.  Host only: usable^3 work per bin.  Its bits are whatever the compiler makes of std::complex<double>.
+ *  6a. The same mathematics with a written arithmetic, on the host and on the device (awpu_hip_csm_invert.h declares the calls;
+ *      csrc/csm_invert_rule.h is the rule as code).  Doubles throughout; fma is the fused double operation, `/` and sqrt are the
+ *      IEEE double operations, nothing else is fused.  Per bin, with n = (double) n_blocks and U = usable:
+ *        Load.    For b < a:  A[a][b] = ((double) C.re / n, (double) C.im / n);   A[a][a] = (double) C[a][a].re / n.
+ *                 trace = the sum of A[a][a], a ascending, plain additions from 0;   load = (double) loading * (trace / (double) U);
+ *                 A[a][a] = A[a][a] + load.  Of C only the diagonal's real parts and the entries b < a are read.
+ *        Factor   (A = L L^H).  For the entry (a, b), b <= a, from (sr, si) = A[a][b]; for j < b ascending, l = L[a][j], m = L[b][j]:
+ *                     sr = fma(-l.re, m.re, sr);  sr = fma(-l.im, m.im, sr);  si = fma(-l.im, m.re, si);  si = fma(l.re, m.im, si)
+ *                 b < a:   L[a][b] = (sr / L[b][b], si / L[b][b]).
+ *                 b == a:  si is not formed.  If !(sr > 0) or sr is not finite the bin is UNSOLVED; otherwise L[a][a] = sqrt(sr).
+ *        Invert the factor (M = L^-1, lower).  For the entry (a, col), a >= col, from (a == col ? 1 : 0, 0); for j = col .. a-1
+ *                 ascending, l = L[a][j], m = M[j][col]:
+ *                     sr = fma(-l.re, m.re, sr);  sr = fma(l.im, m.im, sr);  si = fma(-l.re, m.im, si);  si = fma(-l.im, m.re, si)
+ *                 M[a][col] = (sr / L[a][a], si / L[a][a]).
+ *        G = M^H M.  For b <= a, from 0; for j = a .. U-1 ascending, u = M[j][a], v = M[j][b]:
+ *                     sr = fma(u.re, v.re, sr);  sr = fma(u.im, v.im, sr);  si = fma(u.re, v.im, si);  si = fma(-u.im, v.re, si)
+ *                 A sum that is not finite (either part, on the diagonal too) makes the bin unsolved.
+ *                 G[a][b] = ((float) sr, b < a ? (float) si : +0), mirrored as the exact conjugate.
+ *        An unsolved bin: every entry of its G is +0, both parts -- Capon's step 5 then gives a +0 plane --, and its `solved`
+ *                 word is 0; every other bin's is 1.
+ *      Each entry's sum is serial in ascending j; the device spreads ENTRIES (and bins) over its threads, as a right-looking
+ *      factorisation does whose trailing updates each take step j, so the bits do not depend on the launch shape: the device's
+ *      G and solved words equal the host's bit for bit.
  *
  * The device forms perform these operations on these operands: spectra, C, q and the maps equal the host functions' bit for bit
  * wherever the values are finite or infinite; where a NaN arises host and device agree on WHERE, not on its sign and payload.
  *
- * The planes are power rows: awpu_hip_heatmap_u8, the upscale and awpu_hip_find_peaks take them as they are.  Runs with images are
- * out of scope here, and so is a device version of step 6.
+ * The planes are power rows: awpu_hip_heatmap_u8, the upscale and awpu_hip_find_peaks take them as they are.  Runs with images, a map
+ * per shown block of a recording: awpu_hip_csm_watch.h.
  *
  * Conventions are those of awpu_hip.h (status codes, host pointers owned by the caller, one thread per handle).
  */
@@ -138,5 +161,8 @@ int awpu_hip_csm_map_device(awpu_hip_t *h, const float *d_matrix, int32_t block_
 #ifdef __cplusplus
 }
 #endif
+
+#include "awpu_hip_csm_invert.h" /* step 6a's calls */
+#include "awpu_hip_csm_watch.h"  /* runs: a map per shown block */
 
 #endif /* AWPU_HIP_CSM_H */

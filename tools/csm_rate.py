@@ -3,20 +3,34 @@
 Engine.csm_samples_device for 8 bins, on device-resident buffers, at c1 (64 mics, 32 x 32), the reference's default (64 mics,
 100 x 100) and the headline shape (256 mics, 128 x 128); --repeats launches of each, every launch timed by HIP events on the
 stream it runs on.  One JSON line per shape: the median launch of each, maps per second, complex multiply-adds per second of the
-quadratic form (pixels x bins x usable (usable - 1) / 2 a map) and accumulated blocks per second.
+quadratic form (pixels x bins x usable (usable - 1) / 2 a map) and accumulated blocks per second.  And the loaded inverse
+(step 6a): Engine.csm_invert_device of the 8-bin matrix, timed the same way, beside awpu_hip_csm_invert_host on the host (wall
+clock); and one Capon frame of --blocks blocks two ways, wall clock from an idle device to an idle device: everything enqueued on
+one stream (accumulate, csm_invert_device, map: capon_device_ms) against the composition the device inverse replaces (accumulate,
+the matrix to the host, csm_invert_host, the inverse back up, map: capon_host_inverse_ms).  And the Capon run
+(Engine.csm_watch_samples_device, include/awpu_hip_csm_watch.h): 8 frames of length --blocks, one every --blocks blocks, in one call
+-- run_frames_per_s -- beside composition_frames_per_s, the frames a second of capon_host_inverse.
 
   tools/csm_rate.py --repeats 20
 
-No figure here is a gate: nobody has measured this workload before."""
+Measured on one MI355X (--repeats 20, 64 blocks, 8 bins; c1 / the reference's shape / the headline shape): invert_8 0.119 / 0.119 /
+2.00 ms beside map_8 0.035 / 0.072 / 2.45 ms and invert_host_8 0.88 / 0.88 / 91.6 ms -- at 64 mics the inverse costs more than the
+map it feeds (a chain of 64 dependent steps on 8 workgroups), at 256 less; one Capon frame 0.21 / 0.25 / 4.6 ms on the device against
+1.05 / 1.08 / 93.5 ms through the host inverse; the Capon run 4 950 / 4 090 / 218 frames/s against 957 / 926 / 10.7 for the
+composition.  No figure here is a gate."""
 import argparse
 import importlib
 import json
 import statistics
 import sys
+import time
 from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 pkg = importlib.import_module("beamforming-lk_amd")
+
+
+LOADING = 1e-2
 
 
 def main():
@@ -38,7 +52,9 @@ def main():
         samples = (torch.randn(U, 256 * a.blocks, device="cuda") * 1e-2).contiguous()
         matrix = torch.zeros(8, U, U, 2, device="cuda")
         plane = torch.empty(8, P, device="cuda")
-        with pkg.Engine(n_pixels=P, n_streams=U, grid_columns=spec.res) as eng:
+        inverse = torch.empty_like(matrix)
+        frame = torch.zeros_like(matrix)
+        with pkg.Engine(n_pixels=P, n_streams=U, grid_columns=spec.res, max_batch=8) as eng:
             eng.set_delay_table(off, frac)
             eng.set_active_mics(None)
             bins8, bins1 = [8, 16, 24, 32, 40, 48, 56, 64], [16]
@@ -46,6 +62,7 @@ def main():
                                                                     window=1, stream=side.cuda_stream),
                      "map_1": lambda: eng.csm_map_device(matrix.data_ptr(), a.blocks, bins1, 1, d_map_ptr=plane.data_ptr(), stream=side.cuda_stream),
                      "map_8": lambda: eng.csm_map_device(matrix.data_ptr(), a.blocks, bins8, 1, d_map_ptr=plane.data_ptr(), stream=side.cuda_stream)}
+            calls["invert_8"] = lambda: eng.csm_invert_device(matrix.data_ptr(), a.blocks, bins8, inverse.data_ptr(), LOADING, stream=side.cuda_stream)
             times = {name: [] for name in calls}
             for step in range(a.warmup + a.repeats):
                 for name, call in calls.items():
@@ -56,6 +73,45 @@ def main():
                     torch.cuda.synchronize()
                     if step >= a.warmup:
                         times[name].append(t0.elapsed_time(t1))
+
+            def capon_device():
+                with torch.cuda.stream(side):
+                    frame.zero_()
+                eng.csm_samples_device(samples.data_ptr(), samples.shape[1], a.blocks, bins8, frame.data_ptr(), window=1, stream=side.cuda_stream)
+                eng.csm_invert_device(frame.data_ptr(), a.blocks, bins8, inverse.data_ptr(), LOADING, stream=side.cuda_stream)
+                eng.csm_map_device(inverse.data_ptr(), a.blocks, bins8, 1, pkg.binding.CSM_CAPON, d_map_ptr=plane.data_ptr(), stream=side.cuda_stream)
+
+            def capon_host_inverse():
+                with torch.cuda.stream(side):
+                    frame.zero_()
+                    eng.csm_samples_device(samples.data_ptr(), samples.shape[1], a.blocks, bins8, frame.data_ptr(), window=1, stream=side.cuda_stream)
+                    host_matrix = frame.cpu().numpy()  # (waits for the stream)
+                    host_inverse = pkg.csm_invert_host(host_matrix, a.blocks, bins8, loading=LOADING)
+                    inverse.copy_(torch.from_numpy(host_inverse), non_blocking=True)
+                eng.csm_map_device(inverse.data_ptr(), a.blocks, bins8, 1, pkg.binding.CSM_CAPON, d_map_ptr=plane.data_ptr(), stream=side.cuda_stream)
+
+            run_frames = 8
+            run_samples = (torch.randn(U, 256 * a.blocks * run_frames, device="cuda") * 1e-2).contiguous()
+            run_carry = torch.zeros(max(a.blocks - 1, 1), 8, U, 2, device="cuda")
+            run_power = torch.empty(run_frames, P, device="cuda")
+
+            def capon_run():
+                eng.csm_watch_samples_device(run_samples.data_ptr(), run_samples.shape[1], a.blocks * run_frames, spec.res, spec.res, bins8, 1,
+                                             pkg.binding.CSM_CAPON, LOADING, a.blocks, pkg.binding.CSM_SHOW_SUM, a.blocks - 1, a.blocks,
+                                             d_carry_ptr=run_carry.data_ptr(), carried=0, d_power_ptr=run_power.data_ptr(), stream=side.cuda_stream)
+
+            host_matrix = matrix.cpu().numpy()
+            walls = {"capon_run": capon_run, "invert_host_8": lambda: pkg.csm_invert_host(host_matrix, a.blocks, bins8, loading=LOADING), "capon_device": capon_device,
+                     "capon_host_inverse": capon_host_inverse}
+            for name, call in walls.items():
+                times[name] = []
+                for step in range(a.warmup + a.repeats):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    call()
+                    torch.cuda.synchronize()
+                    if step >= a.warmup:
+                        times[name].append((time.perf_counter() - t0) * 1e3)
             row = {"shape": shape, "mics": U, "grid": f"{spec.res}x{spec.res}", "repeats": a.repeats, "blocks": a.blocks,
                    "device": torch.cuda.get_device_name(0)}
             for name, v in times.items():
@@ -66,6 +122,8 @@ def main():
                 med = statistics.median(times[f"map_{n_bins}"])
                 row[f"map_{n_bins}_per_s"] = round(1e3 / med, 1)
                 row[f"map_{n_bins}_gcmadd_per_s"] = round(P * n_bins * U * (U - 1) / 2 / med * 1e-6, 2)
+            row["run_frames_per_s"] = round(run_frames / statistics.median(times["capon_run"]) * 1e3, 1)
+            row["composition_frames_per_s"] = round(1e3 / statistics.median(times["capon_host_inverse"]), 1)
             row["blocks_per_s"] = round(a.blocks / statistics.median(times["accumulate_8"]) * 1e3, 1)
             print(json.dumps(row), flush=True)
 

@@ -32,6 +32,12 @@ own --, which lists a weak source under a strong one's side lobes and not the si
 beam in the 190.7 Hz transform bins whose centres lie in [LO, HI) Hz (`hann`: behind a Hann window); the `power` column is that
 row's value.  Off unless given; --band applies in front; not with --exposure, --coherence, --peel or --range.
 
+--csm LO:HI[:hann] searches the cross-spectral maps (Engine.csm_watch_blocks, include/awpu_hip_csm_watch.h): the map of the
+--csm-length blocks (64 unless given) that end with the searched one, summed over the transform bins whose centres lie in [LO, HI)
+Hz -- at most 8 of them --, by --csm-kind conventional (the default), diagonal-removed or capon[:LOADING] (Capon's minimum-variance
+map, which separates two sources closer than a beam width; loading 1e-2 unless given); the `power` column is that map's value.
+Off unless given; not with --band, --exposure, --coherence, --peel, --range or --tone.
+
 Every block is ingested; every --every'th is swept and searched.  --chunk blocks go to the engine per call, each call continuing
 with the `next_first` of the one before, so a long capture streams through bounded memory.
 
@@ -133,8 +139,24 @@ def main(argv=None) -> int:
                     help="peel every searched block: its sources are the steps merged per pixel (include/awpu_hip_peel.h)")
     ap.add_argument("--tone", default=None, metavar="LO:HI[:hann]",
                     help="search the power in the transform bins between LO and HI Hz of every pixel's beam (include/awpu_hip_tones.h)")
+    ap.add_argument("--csm", default=None, metavar="LO:HI[:hann]",
+                    help="search the cross-spectral map of the transform bins between LO and HI Hz, at most 8 (include/awpu_hip_csm_watch.h)")
+    ap.add_argument("--csm-kind", default="conventional", metavar="conventional|diagonal-removed|capon[:LOADING]", help="--csm: which map")
+    ap.add_argument("--csm-length", type=int, default=64, metavar="L", help="--csm: every searched map's matrix is added up over the L blocks that end with it")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
+    if a.csm and (a.band or a.exposure is not None or a.range_ or a.coherence or a.peel or a.tone):
+        ap.error("--csm together with --band, --exposure, --range, --coherence, --peel or --tone: the cross-spectral maps choose their bins themselves")
+    if a.csm:
+        sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+        binding = importlib.import_module("beamforming-lk_amd").binding
+        try:
+            csm_bins, csm_window = binding.csm_from_text(a.csm)
+            csm_kind, csm_loading = binding.csm_kind_from_text(a.csm_kind)
+        except ValueError as e:
+            ap.error(str(e))
+        if not 1 <= a.csm_length <= binding.CSM_MAX_LENGTH:
+            ap.error(f"--csm-length is between 1 and {binding.CSM_MAX_LENGTH}")
     if a.tone and (a.exposure is not None or a.range_ or a.coherence or a.peel):
         ap.error("--tone together with --exposure, --range, --coherence or --peel: those runs are not swept for tones")
     if a.tone:
@@ -186,7 +208,7 @@ def main(argv=None) -> int:
         print(f"{n} mics: the wire carries 256 streams per datagram")
         return 1
     searched, lines, first, block_bytes = 0, 0, 0 if a.exposure is None else a.exposure - 1, 256 * 1032
-    carry = None
+    carry, carried = None, 0
     with open(a.out, "w", newline="") as f, \
             pkg.Engine(n_pixels=a.cols * a.cols, n_streams=n, max_batch=a.max_batch, grid_columns=a.cols, device=a.device) as eng:
         writer = csv.writer(f, lineterminator="\n")
@@ -213,6 +235,11 @@ def main(argv=None) -> int:
                 what = {k: v for k, v in find.items() if k not in ("first", "every")}
                 res = eng.tones_blocks(chunk, a.cols, a.cols, tone_groups, first=first, every=a.every, want_image=False,
                                        find=what)
+            elif a.csm:
+                what = {k: v for k, v in find.items() if k not in ("first", "every")}
+                res = eng.csm_watch_blocks(chunk, a.cols, a.cols, csm_bins, csm_window, csm_kind, csm_loading, a.csm_length, pkg.binding.CSM_SHOW_SUM,
+                                           first=first, every=a.every, carry=carry, carried=carried, want_image=False, find=what)
+                carry, carried = res.carry, res.carried
             elif a.coherence:
                 what = {k: v for k, v in find.items() if k not in ("first", "every")}
                 show = pkg.binding.COHERE_FACTOR if a.coherence == "factor" else pkg.binding.COHERE_WEIGHTED

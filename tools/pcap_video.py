@@ -38,6 +38,13 @@ rectangular window or, with `hann`, the Hann window.  --pitch LO:HI[:hann] shows
 brighter where the pitch is higher.  Off unless given; --band applies in front; not with --bands, --exposure, --coherence or
 --peel, nor with each other.
 
+--csm LO:HI[:hann] shows every frame through the cross-spectral maps (Engine.csm_watch_blocks, include/awpu_hip_csm_watch.h): the
+map of the --csm-length blocks (64 unless given) that end with the shown one, summed over the transform bins whose centres lie in
+[LO, HI) Hz -- at most 8 of them --, by --csm-kind conventional (the default), diagonal-removed (uncorrelated microphone
+self-noise leaves the picture) or capon[:LOADING] (Capon's minimum-variance map, which separates sources closer than a beam width;
+loading 1e-2 unless given).  The window's spectra are carried from one --chunk call to the next.  Off unless given; not with
+--band, --bands, --exposure, --coherence, --peel, --tone or --pitch.
+
 Every block is ingested; every --every'th is swept and shown.  The default 3 gives 48828 / (256 * 3) = 63.6 frames per second, the
 nearest to the 60 the reference opens its writer with.  --chunk blocks go to the engine per call, each call continuing with the
 `next_first` of the one before, so a long capture streams through bounded memory.
@@ -242,8 +249,24 @@ def main(argv=None) -> int:
                     help="show the power in the transform bins between LO and HI Hz of every pixel's beam (include/awpu_hip_tones.h)")
     ap.add_argument("--pitch", default=None, metavar="LO:HI[:hann]",
                     help="show every pixel's strongest bin between LO and HI Hz: brighter where the pitch is higher")
+    ap.add_argument("--csm", default=None, metavar="LO:HI[:hann]",
+                    help="show the cross-spectral map of the transform bins between LO and HI Hz, at most 8 (include/awpu_hip_csm_watch.h)")
+    ap.add_argument("--csm-kind", default="conventional", metavar="conventional|diagonal-removed|capon[:LOADING]", help="--csm: which map")
+    ap.add_argument("--csm-length", type=int, default=64, metavar="L", help="--csm: every frame's matrix is added up over the L blocks that end with it")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
+    if a.csm and (a.band or a.bands or a.exposure is not None or a.coherence or a.peel or a.tone or a.pitch):
+        ap.error("--csm together with --band, --bands, --exposure, --coherence, --peel, --tone or --pitch: the cross-spectral maps choose their bins themselves")
+    if a.csm:
+        sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+        binding = importlib.import_module("beamforming-lk_amd").binding
+        try:
+            csm_bins, csm_window = binding.csm_from_text(a.csm)
+            csm_kind, csm_loading = binding.csm_kind_from_text(a.csm_kind)
+        except ValueError as e:
+            ap.error(str(e))
+        if not 1 <= a.csm_length <= binding.CSM_MAX_LENGTH:
+            ap.error(f"--csm-length is between 1 and {binding.CSM_MAX_LENGTH}")
     if a.tone and a.pitch:
         ap.error("--tone together with --pitch: one row per frame")
     if (a.tone or a.pitch) and (a.bands or a.exposure is not None or a.coherence or a.peel):
@@ -307,7 +330,7 @@ def main(argv=None) -> int:
         band_scale = pkg.binding.SPECTRAL_SCALE_COMMON if a.band_scale == "common" else pkg.binding.SPECTRAL_SCALE_PER_BAND
     rate, scale = frame_rate(a.every)
     shown, first, block_bytes, res = 0, 0, 256 * 1032, None
-    carry = None
+    carry, carried = None, 0
     if a.exposure is not None:
         first, mode = a.exposure - 1, pkg.binding.EXPOSE_PEAK if a.peak_hold else pkg.binding.EXPOSE_MEAN
     raw = open(f"{a.out}.bgr", "wb") if a.raw else None
@@ -334,6 +357,11 @@ def main(argv=None) -> int:
                 res = eng.tones_blocks(wire[b * block_bytes: (b + nb) * block_bytes], a.cols, a.cols, tone_groups,
                                        show=0 if a.tone else pkg.binding.TONES_SHOW_PITCH, first=first, every=a.every, out_rows=a.size,
                                        out_cols=a.size, d_colormap_ptr=table.data_ptr(), flip=a.flip, want_image=False)
+            elif a.csm:
+                res = eng.csm_watch_blocks(wire[b * block_bytes: (b + nb) * block_bytes], a.cols, a.cols, csm_bins, csm_window, csm_kind, csm_loading,
+                                           a.csm_length, pkg.binding.CSM_SHOW_SUM, first=first, every=a.every, carry=carry, carried=carried,
+                                           out_rows=a.size, out_cols=a.size, d_colormap_ptr=table.data_ptr(), flip=a.flip, want_image=False)
+                carry, carried = res.carry, res.carried
             elif a.coherence:
                 show = pkg.binding.COHERE_FACTOR if a.coherence == "factor" else pkg.binding.COHERE_WEIGHTED
                 res = eng.cohere_blocks(wire[b * block_bytes: (b + nb) * block_bytes], a.cols, a.cols, first=first, every=a.every, show=show,
