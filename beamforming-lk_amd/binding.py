@@ -498,10 +498,45 @@ _CSM_WATCH_SIGNATURES = {
 }
 CSM_WATCH_SYMBOLS = tuple(_CSM_WATCH_SIGNATURES)
 
+# CLEAN-SC (step 7): the entry points of include/awpu_hip_csm_clean.h
+CSM_CLEAN_MAX_STEPS = 32
+
+
+class CsmClean(C.Structure):
+    """awpu_csm_clean_t (include/awpu_hip_csm_clean.h)."""
+    _fields_ = [
+        ("steps", C.c_int32),
+        ("gain", C.c_float),
+        ("stop_ratio", C.c_float),
+    ]
+
+
+# numpy view of awpu_csm_clean_step_t: `steps` records per bin (unused: pixel -1)
+CSM_CLEAN_STEP_DTYPE = np.dtype([("pixel", "<i4"), ("before", "<f4"), ("removed", "<f4")])
+assert CSM_CLEAN_STEP_DTYPE.itemsize == 12 and C.sizeof(CsmClean) == 12
+
+CSM_CLEAN_MAP, CSM_CLEAN_CLEAN, CSM_CLEAN_RESIDUAL = 0, 1, 2  # what a CLEAN-SC run shows
+# w, c, length, show, f, carry, carried, cl, what, then image, big_image, power, sources, count, planes, steps
+_CSM_CLEAN_RUN_HOST = [C.POINTER(Watch), C.POINTER(Csm), C.c_int32, C.c_int32, C.POINTER(Find), _f32p, _i32p, C.POINTER(CsmClean), C.c_int32,
+                       _u8p, _u8p, _f32p, C.c_void_p, C.c_void_p, _f32p, C.c_void_p]
+_CSM_CLEAN_SIGNATURES = {
+    "awpu_hip_csm_clean_step_host": (C.c_int, [_f32p, _i32p, C.c_float, *_CSM_TABLE, _f32p, _f32p]),
+    "awpu_hip_csm_clean_host": (C.c_int, [_f32p, C.c_int32, *_CSM_TABLE, C.POINTER(CsmClean), C.c_void_p, _f32p, _f32p, _f32p, _f32p]),
+    "awpu_hip_csm_clean_step_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Csm), C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "awpu_hip_csm_clean": (C.c_int, [C.c_void_p, _f32p, C.c_int32, C.POINTER(Csm), C.POINTER(CsmClean), C.c_void_p, _f32p, _f32p, _f32p, _f32p]),
+    "awpu_hip_csm_clean_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Csm), C.POINTER(CsmClean), *([C.c_void_p] * 6)]),
+    "awpu_hip_csm_clean_blocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, *_CSM_CLEAN_RUN_HOST]),
+    "awpu_hip_csm_clean_samples": (C.c_int, [C.c_void_p, _f32p, C.c_int64, C.c_int32, *_CSM_CLEAN_RUN_HOST]),
+    "awpu_hip_csm_clean_samples_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(Watch), C.POINTER(Csm), C.c_int32,
+                                                    C.c_int32, C.POINTER(Find), C.c_void_p, _i32p, C.POINTER(CsmClean), C.c_int32,
+                                                    *([C.c_void_p] * 8)]),
+}
+CSM_CLEAN_SYMBOLS = tuple(_CSM_CLEAN_SIGNATURES)
+
 # every table above, one per public header: what load() sets the types of
 _ALL_SIGNATURES = (_SIGNATURES, _TRACK_SIGNATURES, _BLOCK_SIGNATURES, _LISTEN_SIGNATURES, _WATCH_SIGNATURES, _FIND_SIGNATURES, _BAND_SIGNATURES,
                    _FOCUS_SIGNATURES, _SPECTRAL_SIGNATURES, _EXPOSE_SIGNATURES, _COHERE_SIGNATURES, _PEEL_SIGNATURES,
-                   _TONES_SIGNATURES, _CSM_SIGNATURES, _CSM_INVERT_SIGNATURES, _CSM_WATCH_SIGNATURES)
+                   _TONES_SIGNATURES, _CSM_SIGNATURES, _CSM_INVERT_SIGNATURES, _CSM_WATCH_SIGNATURES, _CSM_CLEAN_SIGNATURES)
 
 # numpy view of awpu_range_t: what range_pick, Engine.range and Engine.locate_* return (unused entries: index -1)
 RANGE_DTYPE = np.dtype([("index", "<i4"), ("power", "<f4"), ("distance", "<f8")], align=True)
@@ -1153,6 +1188,60 @@ def csm_invert_rule_host(matrix: np.ndarray, block_count: int, bins, loading: fl
     return out, solved
 
 
+_CSM_CLEAN_OUTPUTS = ("steps", "clean", "residual", "map", "residual_matrix")
+
+
+def _csm_clean_outputs(want, n_bins: int, steps: int, pixels: int, usable: int) -> dict:
+    """The arrays a CLEAN-SC loop writes, those named in `want`."""
+    if not want or any(name not in _CSM_CLEAN_OUTPUTS for name in want):
+        raise ValueError(f"want names some of {_CSM_CLEAN_OUTPUTS}")
+    shapes = {"steps": ((n_bins, steps), CSM_CLEAN_STEP_DTYPE), "clean": ((n_bins, pixels), np.float32), "residual": ((n_bins, pixels), np.float32),
+              "map": ((n_bins, pixels), np.float32), "residual_matrix": ((n_bins, usable, usable, 2), np.float32)}
+    return {name: np.empty(*shapes[name]) for name in _CSM_CLEAN_OUTPUTS if name in want}
+
+
+def csm_clean_step_host(matrix: np.ndarray, pixel, off: np.ndarray, frac: np.ndarray, bins, gain: float = 1.0, window: int = TONES_RECT,
+                        kind: int = CSM_CONVENTIONAL, index=None, want=("component", "qs")):
+    """One CLEAN-SC step (step 7 of include/awpu_hip_csm.h; awpu_hip_csm_clean_step_host) of matrix [n_bins, usable, usable, 2] at
+    pixel [n_bins] (-1: the bin is left alone) -> (the updated matrix -- a copy --, a dict of the outputs in `want`: "component"
+    [n_bins, usable, 2] and "qs" [n_bins])."""
+    c = csm_of(bins, window, kind)
+    off, frac, index = _csm_table(off, frac, index)
+    matrix = np.array(matrix, np.float32, order="C")
+    if matrix.shape != (max(c.n_bins, 0), len(index), len(index), 2):
+        raise ValueError("matrix must be [n_bins, usable, usable, 2]")
+    pixel = np.ascontiguousarray(pixel, np.int32)
+    if pixel.shape != (max(c.n_bins, 0),):
+        raise ValueError("pixel must be [n_bins]")
+    if any(name not in ("component", "qs") for name in want):
+        raise ValueError("want names some of ('component', 'qs')")
+    shapes = {"component": (max(c.n_bins, 0), len(index), 2), "qs": (max(c.n_bins, 0),)}
+    out = {name: np.empty(shapes[name], np.float32) for name in ("component", "qs") if name in want}
+    _check(load().awpu_hip_csm_clean_step_host(_out_ptr(matrix, _f32p), _i32(pixel), float(gain), _i32(off), _f32(frac), off.shape[1], off.shape[0],
+                                               _i32(index), len(index), C.byref(c), _out_ptr(out.get("component"), _f32p),
+                                               _out_ptr(out.get("qs"), _f32p)), "awpu_hip_csm_clean_step_host")
+    return matrix, out
+
+
+def csm_clean_host(matrix: np.ndarray, block_count: int, off: np.ndarray, frac: np.ndarray, bins, steps: int, gain: float = 1.0,
+                   stop_ratio: float = 0.0, window: int = TONES_RECT, kind: int = CSM_CONVENTIONAL, index=None,
+                   want=("steps", "clean", "residual", "map")):
+    """The CLEAN-SC loop (awpu_hip_csm_clean_host) of matrix [n_bins, usable, usable, 2] with its block count -> a dict of the
+    outputs in `want`: "steps" [n_bins, steps] (CSM_CLEAN_STEP_DTYPE; unused: pixel -1), "clean", "residual", "map"
+    [n_bins, n_pixels] and "residual_matrix" [n_bins, usable, usable, 2]."""
+    c, cl = csm_of(bins, window, kind), CsmClean(int(steps), float(gain), float(stop_ratio))
+    off, frac, index = _csm_table(off, frac, index)
+    matrix = np.ascontiguousarray(matrix, np.float32)
+    if matrix.shape != (max(c.n_bins, 0), len(index), len(index), 2):
+        raise ValueError("matrix must be [n_bins, usable, usable, 2]")
+    out = _csm_clean_outputs(want, max(c.n_bins, 0), max(int(steps), 0), off.shape[0], len(index))
+    _check(load().awpu_hip_csm_clean_host(_f32(matrix), int(block_count), _i32(off), _f32(frac), off.shape[1], off.shape[0], _i32(index), len(index),
+                                          C.byref(c), C.byref(cl), _out_ptr(out.get("steps")),
+                                          *(_out_ptr(out.get(name), _f32p) for name in ("clean", "residual", "map", "residual_matrix"))),
+           "awpu_hip_csm_clean_host")
+    return out
+
+
 class CsmWatchResult:
     """What Engine.csm_watch_blocks / csm_watch_samples hand back: .image, .big, .power as a WatchResult has them -- of the shown
     row --, .sources and .count as a FindResult has them (None without `find`), .planes [n_frames, n_bins, pixels] and .solved
@@ -1164,6 +1253,39 @@ class CsmWatchResult:
 
     def __len__(self):
         return len(next(a for a in (self.image, self.big, self.power, self.count, self.planes, self.solved) if a is not None))
+
+
+class CsmCleanRunResult:
+    """What Engine.csm_clean_blocks / csm_clean_samples hand back: .image, .big, .power as a WatchResult has them -- of the shown
+    row --, .sources and .count as a FindResult has them (None without `find`), .planes [n_frames, n_bins, pixels] (the map, clean
+    or residual rows; None unless asked for), .steps [n_frames, n_bins, steps] CSM_CLEAN_STEP_DTYPE records, .next_first, and
+    .carry / .carried for the call that continues the run."""
+
+    def __init__(self, image, big, power, sources, count, planes, steps, next_first: int, carry, carried: int):
+        self.image, self.big, self.power, self.sources, self.count = image, big, power, sources, count
+        self.planes, self.steps, self.next_first, self.carry, self.carried = planes, steps, next_first, carry, carried
+
+    def __len__(self):
+        return len(self.steps)
+
+
+def csm_clean_from_text(text: str):
+    """'STEPS[:GAIN[:STOP]]' (gain 1 and stop ratio 0 unless given), as the tools' --csm-clean takes it -> (steps, gain, stop_ratio)."""
+    parts = text.split(":")
+    if not 1 <= len(parts) <= 3:
+        raise ValueError(f"csm clean '{text}': STEPS[:GAIN[:STOP]]")
+    steps, gain, stop = int(parts[0]), float(parts[1]) if len(parts) > 1 else 1.0, float(parts[2]) if len(parts) > 2 else 0.0
+    if not 1 <= steps <= CSM_CLEAN_MAX_STEPS or not 0.0 < gain <= 1.0 or not 0.0 <= stop < 1.0:
+        raise ValueError(f"csm clean '{text}': STEPS in [1, {CSM_CLEAN_MAX_STEPS}], GAIN in (0, 1], STOP in [0, 1)")
+    return steps, gain, stop
+
+
+def csm_clean_source_records(steps: np.ndarray, rows: int, cols: int, max_sources: int, fov_deg: float = 180.0):
+    """The steps of a CLEAN-SC run's frames [n_frames, n_bins, steps] as find results, as peel_source_records gives a peel run's: a
+    frame's sources are its steps merged per pixel over steps and bins, strongest first -> (sources [n_frames, max_sources]
+    SOURCE_DTYPE records, count [n_frames])."""
+    steps = np.asarray(steps)
+    return peel_source_records(steps.reshape(len(steps), -1), rows, cols, max_sources, fov_deg)
 
 
 def csm_from_text(text: str, sample_rate: float = 48828.125):
@@ -2144,6 +2266,70 @@ class Engine:
                "awpu_hip_csm_watch_samples_device")
         return watch_count(n_blocks, first, every)[1], held.value
 
+    def _csm_clean_run(self, call, where, n_blocks, rows, cols, bins, steps, gain, stop_ratio, what, window, length, show, first, every, carry,
+                       carried, out_rows, out_cols, d_colormap_ptr, flip, want_image, want_power, want_planes, find) -> CsmCleanRunResult:
+        n_frames, next_first = watch_count(n_blocks, first, every)
+        w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(d_colormap_ptr))
+        c, cl = csm_of(bins, window), CsmClean(int(steps), float(gain), float(stop_ratio))
+        f = _find_struct(rows, cols, find)
+        usable = getattr(self, "_usable", self.cfg.n_streams)
+        shape = (max(int(length) - 1, 0), max(c.n_bins, 0), usable, 2)
+        carry = np.zeros(shape, np.float32) if carry is None else np.ascontiguousarray(carry, np.float32).copy()
+        if carry.shape != shape:
+            raise ValueError(f"carry must be {shape}")
+        held = C.c_int32(int(carried))
+        shown, ptrs = self._shown_outputs(n_frames, w, want_image, want_power, f)
+        planes = np.empty((n_frames, max(c.n_bins, 0), self.pixel_count), np.float32) if want_planes else None
+        rec = np.empty((n_frames, max(c.n_bins, 0), max(int(steps), 0)), CSM_CLEAN_STEP_DTYPE)
+        _check(call(n_blocks, C.byref(w), C.byref(c), int(length), int(show), None if f is None else C.byref(f), _out_ptr(carry, _f32p),
+                    C.cast(C.byref(held), _i32p), C.byref(cl), int(what), *ptrs, _out_ptr(planes, _f32p), _out_ptr(rec)), where)
+        return CsmCleanRunResult(*shown, planes, rec, next_first, carry, held.value)
+
+    def csm_clean_blocks(self, wire, rows: int, cols: int, bins, steps: int, gain: float = 1.0, stop_ratio: float = 0.0,
+                         what: int = CSM_CLEAN_MAP, window: int = TONES_RECT, length: int = 64, show: int = CSM_SHOW_SUM, first: int = 0,
+                         every: int = 1, carry=None, carried: int = 0, out_rows: int = 0, out_cols: int = 0, d_colormap_ptr: int = 0,
+                         flip: bool = False, stride: int = DATAGRAM_BYTES, want_image: bool = True, want_power: bool = False,
+                         want_planes: bool = False, find: Optional[dict] = None) -> CsmCleanRunResult:
+        """Watch a run of consecutive blocks of wire datagrams through CLEAN-SC (awpu_hip_csm_clean_blocks): every shown frame is
+        csm_clean of the matrix of the `length` blocks that end with it -- its map (CSM_CLEAN_MAP), clean (CSM_CLEAN_CLEAN) or
+        residual (CSM_CLEAN_RESIDUAL) rows, of which the plane of bin index `show` or with CSM_SHOW_SUM their sum is shown.
+        -> CsmCleanRunResult; pass its .next_first, .carry and .carried to the call that continues the run."""
+        buf, n_blocks = _wire_blocks(wire, stride)
+        return self._csm_clean_run(lambda *rest: self._lib.awpu_hip_csm_clean_blocks(self._h, buf.ctypes.data_as(C.c_void_p), stride, *rest),
+                                   "awpu_hip_csm_clean_blocks", n_blocks, rows, cols, bins, steps, gain, stop_ratio, what, window, length, show,
+                                   first, every, carry, carried, out_rows, out_cols, d_colormap_ptr, flip, want_image, want_power, want_planes, find)
+
+    def csm_clean_samples(self, samples: np.ndarray, rows: int, cols: int, bins, steps: int, gain: float = 1.0, stop_ratio: float = 0.0,
+                          what: int = CSM_CLEAN_MAP, window: int = TONES_RECT, length: int = 64, show: int = CSM_SHOW_SUM, first: int = 0,
+                          every: int = 1, carry=None, carried: int = 0, out_rows: int = 0, out_cols: int = 0, d_colormap_ptr: int = 0,
+                          flip: bool = False, want_image: bool = True, want_power: bool = False, want_planes: bool = False,
+                          find: Optional[dict] = None) -> CsmCleanRunResult:
+        """The same from unpacked samples [n_streams, N] (N a multiple of 256, oldest first) (awpu_hip_csm_clean_samples)."""
+        samples, n_blocks = self._sample_blocks(samples)
+        return self._csm_clean_run(lambda *rest: self._lib.awpu_hip_csm_clean_samples(self._h, _f32(samples), samples.shape[1], *rest),
+                                   "awpu_hip_csm_clean_samples", n_blocks, rows, cols, bins, steps, gain, stop_ratio, what, window, length, show,
+                                   first, every, carry, carried, out_rows, out_cols, d_colormap_ptr, flip, want_image, want_power, want_planes, find)
+
+    def csm_clean_samples_device(self, d_samples_ptr: int, pitch: int, n_blocks: int, rows: int, cols: int, bins, steps: int, gain: float = 1.0,
+                                 stop_ratio: float = 0.0, what: int = CSM_CLEAN_MAP, window: int = TONES_RECT, length: int = 64,
+                                 show: int = CSM_SHOW_SUM, first: int = 0, every: int = 1, d_carry_ptr: int = 0, carried: int = 0,
+                                 d_image_ptr: int = 0, d_big_ptr: int = 0, d_power_ptr: int = 0, d_sources_ptr: int = 0, d_count_ptr: int = 0,
+                                 d_planes_ptr: int = 0, d_steps_ptr: int = 0, out_rows: int = 0, out_cols: int = 0, d_colormap_ptr: int = 0,
+                                 flip: bool = False, stream: int = 0, find: Optional[dict] = None):
+        """The same on device pointers (as csm_watch_samples_device takes them; steps [n_frames, n_bins, steps] records or 0) on
+        `stream`; asynchronous.  -> (next_first, carried) for the call that continues the run (awpu_hip_csm_clean_samples_device)."""
+        w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(d_colormap_ptr))
+        c, cl = csm_of(bins, window), CsmClean(int(steps), float(gain), float(stop_ratio))
+        f = _find_struct(rows, cols, find)
+        held = C.c_int32(int(carried))
+        _check(self._lib.awpu_hip_csm_clean_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, C.byref(w), C.byref(c), int(length),
+                                                           int(show), None if f is None else C.byref(f), C.c_void_p(d_carry_ptr),
+                                                           C.cast(C.byref(held), _i32p), C.byref(cl), int(what), C.c_void_p(d_image_ptr),
+                                                           C.c_void_p(d_big_ptr), C.c_void_p(d_power_ptr), C.c_void_p(d_sources_ptr),
+                                                           C.c_void_p(d_count_ptr), C.c_void_p(d_planes_ptr), C.c_void_p(d_steps_ptr),
+                                                           C.c_void_p(stream)), "awpu_hip_csm_clean_samples_device")
+        return watch_count(n_blocks, first, every)[1], held.value
+
     def csm_samples(self, samples: np.ndarray, bins, window: int = TONES_RECT, matrix: Optional[np.ndarray] = None, block_count: int = 0,
                     n_blocks: Optional[int] = None, want_spectra: bool = False):
         """Steps 1 and 2 of include/awpu_hip_csm.h on the device (awpu_hip_csm_samples): the blocks of host samples [n_streams, pitch]
@@ -2219,6 +2405,42 @@ class Engine:
         c = csm_of(bins, window, kind)
         _check(self._lib.awpu_hip_csm_map_device(self._h, C.c_void_p(d_matrix_ptr), int(block_count), C.byref(c), C.c_void_p(d_map_ptr),
                                                  C.c_void_p(d_q_ptr), C.c_void_p(stream)), "awpu_hip_csm_map_device")
+
+    def csm_clean(self, matrix: np.ndarray, block_count: int, bins, steps: int, gain: float = 1.0, stop_ratio: float = 0.0,
+                  window: int = TONES_RECT, kind: int = CSM_CONVENTIONAL, want=("steps", "clean", "residual", "map")):
+        """CLEAN-SC on the device with the handle's table and active mics (awpu_hip_csm_clean): matrix [n_bins, usable, usable, 2]
+        as csm_clean_host takes it -> a dict of the outputs in `want`: "steps" [n_bins, steps] (CSM_CLEAN_STEP_DTYPE), "clean",
+        "residual", "map" [n_bins, pixels] and "residual_matrix" [n_bins, usable, usable, 2]."""
+        c, cl = csm_of(bins, window, kind), CsmClean(int(steps), float(gain), float(stop_ratio))
+        matrix = np.ascontiguousarray(matrix, np.float32)
+        usable = getattr(self, "_usable", self.cfg.n_streams)
+        if matrix.shape != (max(c.n_bins, 0), usable, usable, 2):
+            raise ValueError(f"matrix must be [{max(c.n_bins, 0)}, {usable}, {usable}, 2]")
+        out = _csm_clean_outputs(want, max(c.n_bins, 0), max(int(steps), 0), self.pixel_count, usable)
+        _check(self._lib.awpu_hip_csm_clean(self._h, _f32(matrix), int(block_count), C.byref(c), C.byref(cl), _out_ptr(out.get("steps")),
+                                            *(_out_ptr(out.get(name), _f32p) for name in ("clean", "residual", "map", "residual_matrix"))),
+               "awpu_hip_csm_clean")
+        return out
+
+    def csm_clean_device(self, d_matrix_ptr: int, block_count: int, bins, steps: int, gain: float = 1.0, stop_ratio: float = 0.0,
+                         window: int = TONES_RECT, kind: int = CSM_CONVENTIONAL, d_steps_ptr: int = 0, d_clean_ptr: int = 0, d_residual_ptr: int = 0,
+                         d_map_ptr: int = 0, d_residual_matrix_ptr: int = 0, stream: int = 0) -> None:
+        """The same on device pointers (each output or 0, not all) on `stream`; asynchronous: the picks, the stop tests and the
+        records stay on the device (awpu_hip_csm_clean_device).  d_matrix is not written."""
+        c, cl = csm_of(bins, window, kind), CsmClean(int(steps), float(gain), float(stop_ratio))
+        _check(self._lib.awpu_hip_csm_clean_device(self._h, C.c_void_p(d_matrix_ptr), int(block_count), C.byref(c), C.byref(cl), C.c_void_p(d_steps_ptr),
+                                                   C.c_void_p(d_clean_ptr), C.c_void_p(d_residual_ptr), C.c_void_p(d_map_ptr),
+                                                   C.c_void_p(d_residual_matrix_ptr), C.c_void_p(stream)), "awpu_hip_csm_clean_device")
+
+    def csm_clean_step_device(self, d_matrix_ptr: int, d_pixel_ptr: int, bins, gain: float = 1.0, window: int = TONES_RECT,
+                              kind: int = CSM_CONVENTIONAL, d_component_ptr: int = 0, d_qs_ptr: int = 0, stream: int = 0) -> None:
+        """One CLEAN-SC step of d_matrix [n_bins, usable, usable, 2], in place, at the pixels d_pixel [n_bins] int32 holds (outside
+        the table: the bin is skipped); d_component [n_bins, usable, 2] and d_qs [n_bins], each or 0; asynchronous
+        (awpu_hip_csm_clean_step_device)."""
+        c = csm_of(bins, window, kind)
+        _check(self._lib.awpu_hip_csm_clean_step_device(self._h, C.c_void_p(d_matrix_ptr), C.c_void_p(d_pixel_ptr), C.byref(c), float(gain),
+                                                        C.c_void_p(d_component_ptr), C.c_void_p(d_qs_ptr), C.c_void_p(stream)),
+               "awpu_hip_csm_clean_step_device")
 
     def range(self, theta, phi, distance, d_frame_ptr: int = 0):
         """The beam power of every direction (theta[k], phi[k]) focused at every candidate distance[j] (metres, inf = a plane wave),

@@ -1,8 +1,9 @@
 // awpu_csm.cpp -- the handle forms of the cross-spectral maps (include/awpu_hip_csm.h): awpu_hip_csm_samples, _samples_device,
 // _map and _map_device, step 6a's awpu_hip_csm_invert and _invert_device, and the runs awpu_hip_csm_watch_blocks, _samples and
-// _samples_device (a loop of their own beside run_pieces.cpp's: their pieces read spectra, not snapshots).  The rule is csm_rule.h's and csm_invert_rule.h's,
-// the kernels and their launchers csm_kernels.hip's and csm_invert_kernels.hip's.  The calls read the handle's
-// active list, gains and delay table (the coherence sweep's LutEntry table: ensure_cohere_table) and the tone sweep's two tables
+// _samples_device (a loop of their own beside run_pieces.cpp's: their pieces read spectra, not snapshots) with the CLEAN-SC runs
+// awpu_hip_csm_clean_blocks, _samples and _samples_device, the same loop with one more way to turn a frame's matrix into planes.
+// The rule is csm_rule.h's and csm_invert_rule.h's, the kernels and their launchers csm_kernels.hip's and csm_invert_kernels.hip's;
+// CLEAN-SC's loop is awpu_csm_clean.cpp's (csm_calls.h).  The calls read the handle's active list, gains and delay table (the coherence sweep's LutEntry table: ensure_cohere_table) and the tone sweep's two tables
 // (ensure_tones_tables); they count no sweep launch and leave stats.kernel_variant alone.
 #include "watch_run.h"
 
@@ -10,6 +11,8 @@
 
 #include <cstring>
 
+#include "csm_calls.h"
+#include "csm_clean_rule.h"
 #include "csm_invert_kernels.h"
 #include "csm_kernels.h"
 #include "csm_rule.h"
@@ -155,15 +158,32 @@ struct CsmWatchOut {
     int32_t *solved;
 };
 
+// One more way to turn a frame's matrix into planes: CLEAN-SC in place of the map (the runs of awpu_hip_csm_clean.h).  The frame's
+// planes are then the chosen rows of the loop on its matrix -- the one awpu_hip_csm_clean_device runs (csm_calls.h), so its bits.
+struct CsmCleanRun {
+    const awpu_csm_clean_t *cl;
+    int32_t what;                  // AWPU_CSM_CLEAN_MAP, _CLEAN or _RESIDUAL
+    awpu_csm_clean_step_t *steps;  // [n_frames][n_bins][cl->steps], host or device memory as the run's other outputs, or null
+};
+
+const char *csm_clean_run_refusal(const awpu_csm_t *c, const CsmCleanRun &cr) {
+    if (const char *why = awpu::csm_clean_refusal(cr.cl)) return why;
+    if (cr.what != AWPU_CSM_CLEAN_MAP && cr.what != AWPU_CSM_CLEAN_CLEAN && cr.what != AWPU_CSM_CLEAN_RESIDUAL)
+        return "what is AWPU_CSM_CLEAN_MAP, AWPU_CSM_CLEAN_CLEAN or AWPU_CSM_CLEAN_RESIDUAL";
+    return awpu::csm_clean_kind_refusal(c);
+}
+
 int csm_watch_run(awpu_hip *h, const BlockRun &src, int n_blocks, const awpu_watch_t *w, const awpu_csm_t *c, int32_t length, int32_t show,
                   const awpu_find_t *f, uint8_t *image, uint8_t *big, float *power, awpu_source_t *sources, int32_t *count, const CsmWatchOut &o,
-                  hipStream_t user) {
+                  hipStream_t user, const CsmCleanRun *cr = nullptr) {
     ShownRun sr;
-    if (const int rc = sr.open(w, n_blocks, [&] { return csm_watch_refusal(c, length, show, o.carry, o.carried); }, f, image, big, power, sources,
-                               count, o.planes || o.solved))
-        return rc;
+    const auto refusal = [&] {
+        const char *why = csm_watch_refusal(c, length, show, o.carry, o.carried);
+        return why || !cr ? why : csm_clean_run_refusal(c, *cr);
+    };
+    if (const int rc = sr.open(w, n_blocks, refusal, f, image, big, power, sources, count, o.planes || o.solved || (cr && cr->steps))) return rc;
     AWPU_CTX(h);
-    if (int rc = check_csm(h, c)) return rc;
+    if (int rc = cr ? csm_clean_check(h, c) : check_csm(h, c)) return rc;
     if (h->cfg.hist != AWPU_HIST) return invalid("runs of blocks need hist 1024");
     if (src.wire && h->cfg.n_streams > 256) return invalid("the wire carries at most 256 streams");
     const bool host = !src.device, capon = c->kind == AWPU_CSM_CAPON;
@@ -172,6 +192,7 @@ int csm_watch_run(awpu_hip *h, const BlockRun &src, int n_blocks, const awpu_wat
     int rc = check_ready(h, 1);
     if (rc == AWPU_OK) rc = ready_map(h, c);
     if (rc == AWPU_OK && capon) rc = ready_invert(h, c);
+    if (rc == AWPU_OK && cr) rc = csm_clean_ready(h, *c, false);  // (the working matrix is the run's: the inverse's place)
     if (rc != AWPU_OK) return rc;
 
     const int S = h->cfg.n_streams, U = h->usable(), K = c->n_bins, n_frames = sr.wr.n_frames;
@@ -184,9 +205,12 @@ int csm_watch_run(awpu_hip *h, const BlockRun &src, int n_blocks, const awpu_wat
     const size_t rows_floats = host || !power ? part((size_t) piece * P) : 0;
     const size_t planes_floats = host ? (o.planes ? part((size_t) piece * K * P) : part((size_t) K * P)) : (o.planes ? 0 : part((size_t) K * P));
     const size_t solved_floats = host && o.solved ? part((size_t) piece * K) : 0;
+    static_assert(sizeof(awpu_csm_clean_step_t) == 3 * sizeof(float), "a piece's steps lie in the float buffer");
+    const size_t frame_steps = cr ? (size_t) K * cr->cl->steps : 0;  // records of a frame
+    const size_t steps_floats = host && cr && cr->steps ? part((size_t) piece * frame_steps * 3) : 0;
     const size_t stage_floats = host ? part((size_t) S * awpu::kSamples * chunk) : 0;
     const size_t wire_floats = src.wire ? part((size_t) awpu::kSamples * chunk * AWPU_DATAGRAM_BYTES / sizeof(float) + 1) : 0;
-    rc = h->d_csm_run.ensure(spec_floats + carry_floats + 2 * part(matrix_floats) + rows_floats + planes_floats + solved_floats + stage_floats + wire_floats);
+    rc = h->d_csm_run.ensure(spec_floats + carry_floats + 2 * part(matrix_floats) + rows_floats + planes_floats + solved_floats + steps_floats + stage_floats + wire_floats);
     hipStream_t s = host ? (hipStream_t) h->stream : (user ? user : (hipStream_t) h->stream);
     if (rc == AWPU_OK) rc = enter_stream(h, s);
     if (rc == AWPU_OK) rc = ensure_ring(h);
@@ -197,7 +221,8 @@ int csm_watch_run(awpu_hip *h, const BlockRun &src, int n_blocks, const awpu_wat
     float *d_C = spec + spec_floats + carry_floats, *d_G = d_C + part(matrix_floats), *d_rows = d_G + part(matrix_floats);
     float *d_planes = d_rows + rows_floats;
     int32_t *d_solved = reinterpret_cast<int32_t *>(d_planes + planes_floats);
-    float *d_stage = d_planes + planes_floats + solved_floats;
+    awpu_csm_clean_step_t *d_steps = reinterpret_cast<awpu_csm_clean_step_t *>(d_planes + planes_floats + solved_floats);
+    float *d_stage = d_planes + planes_floats + solved_floats + steps_floats;
     unsigned char *d_wire = reinterpret_cast<unsigned char *>(d_stage + stage_floats);
 
     const auto body = [&]() -> int {
@@ -248,6 +273,14 @@ int csm_watch_run(awpu_hip *h, const BlockRun &src, int n_blocks, const awpu_wat
                 ac.spectra = spec + (size_t) (keep + lo - c0) * per_block, ac.matrix = d_C;
                 ac.usable = U, ac.n_blocks = n, ac.n_bins = K;
                 AWPU_HIP_TRY(awpu::launch_csm_accumulate(ac, s));
+                if (cr) {  // the loop on the frame's matrix, its working D where the inverse would lie; the chosen rows are the frame's planes
+                    CsmCleanOut out;
+                    (cr->what == AWPU_CSM_CLEAN_CLEAN ? out.clean : cr->what == AWPU_CSM_CLEAN_RESIDUAL ? out.residual : out.map) = planes_k;
+                    if (cr->steps) out.steps = host ? d_steps + (size_t) k * frame_steps : cr->steps + (size_t) (j + k) * frame_steps;
+                    if (const int brc = csm_clean_enqueue(h, d_C, d_G, n, *c, *cr->cl, out, s)) return brc;
+                    AWPU_HIP_TRY(awpu::launch_csm_show(planes_k, K, (int) P, show, rows + (size_t) k * P, s));
+                    continue;
+                }
                 if (capon) {
                     if (const int brc = enqueue_invert(h, d_C, n, *c, d_G, solved_k, s)) return brc;
                 } else if (solved_k) {
@@ -261,6 +294,9 @@ int csm_watch_run(awpu_hip *h, const BlockRun &src, int n_blocks, const awpu_wat
                 if (power) AWPU_HIP_TRY(hipMemcpyAsync(power + (size_t) j * P, d_rows, (size_t) nf * P * sizeof(float), hipMemcpyDeviceToHost, s));
                 if (o.planes) AWPU_HIP_TRY(hipMemcpyAsync(o.planes + (size_t) j * K * P, d_planes, (size_t) nf * K * P * sizeof(float), hipMemcpyDeviceToHost, s));
                 if (o.solved) AWPU_HIP_TRY(hipMemcpyAsync(o.solved + (size_t) j * K, d_solved, (size_t) nf * K * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+                if (cr && cr->steps)
+                    AWPU_HIP_TRY(hipMemcpyAsync(cr->steps + (size_t) j * frame_steps, d_steps, (size_t) nf * frame_steps * sizeof(awpu_csm_clean_step_t),
+                                                hipMemcpyDeviceToHost, s));
                 if (const int brc = display.fetch(0, nf, s)) return brc;
                 AWPU_HIP_TRY(hipStreamSynchronize(s));
                 if (const int brc = display.deliver(0, j, nf)) return brc;
@@ -311,6 +347,15 @@ int csm_watch_run(awpu_hip *h, const BlockRun &src, int n_blocks, const awpu_wat
 }
 
 }  // namespace
+
+// what the other cross-spectral files call (csm_calls.h)
+namespace awpu::host {
+int csm_check(awpu_hip *h, const awpu_csm_t *c) { return check_csm(h, c); }
+int csm_ready_map(awpu_hip *h, const awpu_csm_t *c) { return ready_map(h, c); }
+int csm_enqueue_map(awpu_hip *h, const float *d_matrix, int block_count, const awpu_csm_t &c, float *d_map, float *d_q, hipStream_t s) {
+    return enqueue_map(h, d_matrix, block_count, c, d_map, d_q, s);
+}
+}  // namespace awpu::host
 
 extern "C" {
 
@@ -467,6 +512,40 @@ int awpu_hip_csm_watch_samples_device(awpu_hip_t *h, const float *d_samples, int
     if (int rc = sample_source(h, d_samples, pitch, n_blocks, true, &src)) return rc;
     return csm_watch_run(h, src, n_blocks, w, c, length, show, f, d_image, d_big_image, d_power, d_sources, d_count,
                          {d_carry, carried, d_planes, d_solved}, static_cast<hipStream_t>(stream));
+}
+
+// CLEAN-SC runs (awpu_hip_csm_clean.h): the watch run with the loop in place of the map
+
+int awpu_hip_csm_clean_blocks(awpu_hip_t *h, const void *datagrams, int32_t stride_bytes, int32_t n_blocks, const awpu_watch_t *w,
+                              const awpu_csm_t *c, int32_t length, int32_t show, const awpu_find_t *f, float *carry, int32_t *carried,
+                              const awpu_csm_clean_t *cl, int32_t what, uint8_t *image, uint8_t *big_image, float *power, awpu_source_t *sources,
+                              int32_t *count, float *planes, awpu_csm_clean_step_t *steps) {
+    BlockRun src;
+    if (int rc = wire_source(h, datagrams, stride_bytes, n_blocks, &src)) return rc;
+    const CsmCleanRun cr{cl, what, steps};
+    return csm_watch_run(h, src, n_blocks, w, c, length, show, f, image, big_image, power, sources, count, {carry, carried, planes, nullptr}, nullptr, &cr);
+}
+
+int awpu_hip_csm_clean_samples(awpu_hip_t *h, const float *samples, int64_t pitch, int32_t n_blocks, const awpu_watch_t *w,
+                               const awpu_csm_t *c, int32_t length, int32_t show, const awpu_find_t *f, float *carry, int32_t *carried,
+                               const awpu_csm_clean_t *cl, int32_t what, uint8_t *image, uint8_t *big_image, float *power, awpu_source_t *sources,
+                               int32_t *count, float *planes, awpu_csm_clean_step_t *steps) {
+    BlockRun src;
+    if (int rc = sample_source(h, samples, pitch, n_blocks, false, &src)) return rc;
+    const CsmCleanRun cr{cl, what, steps};
+    return csm_watch_run(h, src, n_blocks, w, c, length, show, f, image, big_image, power, sources, count, {carry, carried, planes, nullptr}, nullptr, &cr);
+}
+
+int awpu_hip_csm_clean_samples_device(awpu_hip_t *h, const float *d_samples, int64_t pitch, int32_t n_blocks, const awpu_watch_t *w,
+                                      const awpu_csm_t *c, int32_t length, int32_t show, const awpu_find_t *f, float *d_carry,
+                                      int32_t *carried, const awpu_csm_clean_t *cl, int32_t what, uint8_t *d_image, uint8_t *d_big_image,
+                                      float *d_power, awpu_source_t *d_sources, int32_t *d_count, float *d_planes,
+                                      awpu_csm_clean_step_t *d_steps, void *stream) {
+    BlockRun src;
+    if (int rc = sample_source(h, d_samples, pitch, n_blocks, true, &src)) return rc;
+    const CsmCleanRun cr{cl, what, d_steps};
+    return csm_watch_run(h, src, n_blocks, w, c, length, show, f, d_image, d_big_image, d_power, d_sources, d_count,
+                         {d_carry, carried, d_planes, nullptr}, static_cast<hipStream_t>(stream), &cr);
 }
 
 }  // extern "C"

@@ -410,6 +410,11 @@ struct awpu_hip {
     // ... and a cross-spectral run's (awpu_hip_csm_watch.h): the spectra store, the carry, one frame's matrix and inverse, a piece's
     // rows, planes and solved words, a chunk's samples (csm_watch_run lays it out)
     Dev<float> d_csm_run;
+    // ... and CLEAN-SC's (awpu_hip_csm_clean.h; awpu_csm_clean.cpp): the working matrix D [n_bins][usable][usable][2] where the
+    // caller keeps none; the component v [n_bins][usable][2], then the loop's dirty planes [n_bins][pixel_count]; the bins'
+    // bookkeeping (CsmCleanState [8]); and what a host-form call brings up and back (the matrix in, D, the steps and three planes out)
+    Dev<float> d_csm_clean_matrix, d_csm_clean_rows;
+    Dev<unsigned char> d_csm_clean_state, d_csm_clean_io;
     // peeling (awpu_hip_peel.h; awpu_peel.cpp): the table's reach at the active mics, valid for the tables of peel_gen (table_gen;
     // 0: none yet); the loop's residual frames [batch][n_streams][hist] where the caller keeps none, its power row P_k
     // [batch][pixel_count], its bookkeeping (PeelState [batch]), and the results of a host-form call on their way back

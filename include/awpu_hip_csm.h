@@ -70,6 +70,9 @@
  *      Each entry's sum is serial in ascending j; the device spreads ENTRIES (and bins) over its threads, as a right-looking
  *      factorisation does whose trailing updates each take step j, so the bits do not depend on the launch shape: the device's
  *      G and solved words equal the host's bit for bit.
+ *   7. CLEAN-SC: the conventional map deconvolved per bin -- map, take the strongest pixel, subtract the part of C that is
+ *      coherent with its beam, map again.  awpu_hip_csm_clean.h states the step's arithmetic and declares its calls;
+ *      csrc/csm_clean_rule.h is the rule as code.
  *
  * The device forms perform these operations on these operands: spectra, C, q and the maps equal the host functions' bit for bit
  * wherever the values are finite or infinite; where a NaN arises host and device agree on WHERE, not on its sign and payload.
@@ -164,5 +167,6 @@ int awpu_hip_csm_map_device(awpu_hip_t *h, const float *d_matrix, int32_t block_
 
 #include "awpu_hip_csm_invert.h" /* step 6a's calls */
 #include "awpu_hip_csm_watch.h"  /* runs: a map per shown block */
+#include "awpu_hip_csm_clean.h"  /* step 7: CLEAN-SC, its rule and its calls */
 
 #endif /* AWPU_HIP_CSM_H */

@@ -17,7 +17,12 @@ Measured on one MI355X (--repeats 20, 64 blocks, 8 bins; c1 / the reference's sh
 2.00 ms beside map_8 0.035 / 0.072 / 2.45 ms and invert_host_8 0.88 / 0.88 / 91.6 ms -- at 64 mics the inverse costs more than the
 map it feeds (a chain of 64 dependent steps on 8 workgroups), at 256 less; one Capon frame 0.21 / 0.25 / 4.6 ms on the device against
 1.05 / 1.08 / 93.5 ms through the host inverse; the Capon run 4 950 / 4 090 / 218 frames/s against 957 / 926 / 10.7 for the
-composition.  No figure here is a gate."""
+composition.  And CLEAN-SC (step 7, include/awpu_hip_csm_clean.h): Engine.csm_clean_device at 4 steps, 1 bin and 8 bins
+(clean_1, clean_8), beside the five maps the loop contains (clean_N_over_maps = clean_N / (5 map_N); clean_N_between_maps_ms = what
+is left per step for the two launches between two maps), and Engine.csm_clean_step_device by itself (load, component, update).
+Measured (--repeats 20; c1 / the reference's shape / the headline shape): clean_8 0.198 / 0.400 / 12.26 ms beside map_8 0.034 / 0.072 /
+2.43 ms (1.18 / 1.12 / 1.01 x its five maps), clean_1 0.192 / 0.204 / 1.69 ms beside map_1 0.033 / 0.032 / 0.306 ms (1.16 / 1.29 / 1.11 x).
+No figure here is a gate."""
 import argparse
 import importlib
 import json
@@ -31,6 +36,7 @@ pkg = importlib.import_module("beamforming-lk_amd")
 
 
 LOADING = 1e-2
+CLEAN_STEPS = 4
 
 
 def main():
@@ -54,6 +60,7 @@ def main():
         plane = torch.empty(8, P, device="cuda")
         inverse = torch.empty_like(matrix)
         frame = torch.zeros_like(matrix)
+        pixels = torch.full((8,), P // 2 + spec.res // 2, dtype=torch.int32, device="cuda")
         with pkg.Engine(n_pixels=P, n_streams=U, grid_columns=spec.res, max_batch=8) as eng:
             eng.set_delay_table(off, frac)
             eng.set_active_mics(None)
@@ -63,9 +70,19 @@ def main():
                      "map_1": lambda: eng.csm_map_device(matrix.data_ptr(), a.blocks, bins1, 1, d_map_ptr=plane.data_ptr(), stream=side.cuda_stream),
                      "map_8": lambda: eng.csm_map_device(matrix.data_ptr(), a.blocks, bins8, 1, d_map_ptr=plane.data_ptr(), stream=side.cuda_stream)}
             calls["invert_8"] = lambda: eng.csm_invert_device(matrix.data_ptr(), a.blocks, bins8, inverse.data_ptr(), LOADING, stream=side.cuda_stream)
+            # CLEAN-SC (step 7): the loop of CLEAN_STEPS steps -- CLEAN_STEPS + 1 maps and what runs between them --, and one step by itself
+            # on a copy of the matrix (it updates in place)
+            for n_bins, bins in ((1, bins1), (8, bins8)):
+                calls[f"clean_{n_bins}"] = lambda bins=bins: eng.csm_clean_device(matrix.data_ptr(), a.blocks, bins, CLEAN_STEPS, window=1,
+                                                                                  d_map_ptr=plane.data_ptr(), stream=side.cuda_stream)
+                calls[f"clean_step_{n_bins}"] = lambda bins=bins: eng.csm_clean_step_device(frame.data_ptr(), pixels.data_ptr(), bins, window=1,
+                                                                                            stream=side.cuda_stream)
             times = {name: [] for name in calls}
             for step in range(a.warmup + a.repeats):
                 for name, call in calls.items():
+                    if name.startswith("clean_step"):
+                        frame.copy_(matrix)
+                        torch.cuda.synchronize()
                     t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     t0.record(side)
                     call()
@@ -122,6 +139,10 @@ def main():
                 med = statistics.median(times[f"map_{n_bins}"])
                 row[f"map_{n_bins}_per_s"] = round(1e3 / med, 1)
                 row[f"map_{n_bins}_gcmadd_per_s"] = round(P * n_bins * U * (U - 1) / 2 / med * 1e-6, 2)
+            for n_bins in (1, 8):  # the loop beside the maps it contains, and what is left for the launches between them
+                loop, maps = statistics.median(times[f"clean_{n_bins}"]), (CLEAN_STEPS + 1) * statistics.median(times[f"map_{n_bins}"])
+                row[f"clean_{n_bins}_over_maps"] = round(loop / maps, 3)
+                row[f"clean_{n_bins}_between_maps_ms"] = round((loop - maps) / CLEAN_STEPS, 4)
             row["run_frames_per_s"] = round(run_frames / statistics.median(times["capon_run"]) * 1e3, 1)
             row["composition_frames_per_s"] = round(1e3 / statistics.median(times["capon_host_inverse"]), 1)
             row["blocks_per_s"] = round(a.blocks / statistics.median(times["accumulate_8"]) * 1e3, 1)

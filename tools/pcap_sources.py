@@ -36,7 +36,9 @@ row's value.  Off unless given; --band applies in front; not with --exposure, --
 --csm-length blocks (64 unless given) that end with the searched one, summed over the transform bins whose centres lie in [LO, HI)
 Hz -- at most 8 of them --, by --csm-kind conventional (the default), diagonal-removed or capon[:LOADING] (Capon's minimum-variance
 map, which separates two sources closer than a beam width; loading 1e-2 unless given); the `power` column is that map's value.
-Off unless given; not with --band, --exposure, --coherence, --peel, --range or --tone.
+Off unless given; not with --band, --exposure, --coherence, --peel, --range or --tone.  With --csm-clean STEPS[:GAIN[:STOP]] every
+searched conventional map is deconvolved by CLEAN-SC (Engine.csm_clean_blocks, include/awpu_hip_csm_clean.h), and the sources are
+its steps merged per pixel over steps and bins, as with --peel: the `power` column is the power removed there.
 
 Every block is ingested; every --every'th is swept and searched.  --chunk blocks go to the engine per call, each call continuing
 with the `next_first` of the one before, so a long capture streams through bounded memory.
@@ -143,6 +145,8 @@ def main(argv=None) -> int:
                     help="search the cross-spectral map of the transform bins between LO and HI Hz, at most 8 (include/awpu_hip_csm_watch.h)")
     ap.add_argument("--csm-kind", default="conventional", metavar="conventional|diagonal-removed|capon[:LOADING]", help="--csm: which map")
     ap.add_argument("--csm-length", type=int, default=64, metavar="L", help="--csm: every searched map's matrix is added up over the L blocks that end with it")
+    ap.add_argument("--csm-clean", default=None, metavar="STEPS[:GAIN[:STOP]]",
+                    help="--csm: deconvolve every searched map by CLEAN-SC; its sources are the steps merged per pixel (include/awpu_hip_csm_clean.h)")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     if a.csm and (a.band or a.exposure is not None or a.range_ or a.coherence or a.peel or a.tone):
@@ -157,6 +161,15 @@ def main(argv=None) -> int:
             ap.error(str(e))
         if not 1 <= a.csm_length <= binding.CSM_MAX_LENGTH:
             ap.error(f"--csm-length is between 1 and {binding.CSM_MAX_LENGTH}")
+        if a.csm_clean:
+            try:
+                csm_clean = binding.csm_clean_from_text(a.csm_clean)
+            except ValueError as e:
+                ap.error(str(e))
+            if csm_kind != binding.CSM_CONVENTIONAL:
+                ap.error("--csm-clean deconvolves the conventional map: not with --csm-kind diagonal-removed or capon")
+    elif a.csm_clean:
+        ap.error("--csm-clean goes with --csm")
     if a.tone and (a.exposure is not None or a.range_ or a.coherence or a.peel):
         ap.error("--tone together with --exposure, --range, --coherence or --peel: those runs are not swept for tones")
     if a.tone:
@@ -235,6 +248,11 @@ def main(argv=None) -> int:
                 what = {k: v for k, v in find.items() if k not in ("first", "every")}
                 res = eng.tones_blocks(chunk, a.cols, a.cols, tone_groups, first=first, every=a.every, want_image=False,
                                        find=what)
+            elif a.csm and a.csm_clean:
+                res = eng.csm_clean_blocks(chunk, a.cols, a.cols, csm_bins, *csm_clean, window=csm_window, length=a.csm_length, first=first,
+                                           every=a.every, carry=carry, carried=carried, want_image=False)
+                carry, carried = res.carry, res.carried
+                res.sources, res.count = pkg.binding.csm_clean_source_records(res.steps, a.cols, a.cols, a.max_sources, a.fov)
             elif a.csm:
                 what = {k: v for k, v in find.items() if k not in ("first", "every")}
                 res = eng.csm_watch_blocks(chunk, a.cols, a.cols, csm_bins, csm_window, csm_kind, csm_loading, a.csm_length, pkg.binding.CSM_SHOW_SUM,

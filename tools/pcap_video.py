@@ -43,7 +43,10 @@ map of the --csm-length blocks (64 unless given) that end with the shown one, su
 [LO, HI) Hz -- at most 8 of them --, by --csm-kind conventional (the default), diagonal-removed (uncorrelated microphone
 self-noise leaves the picture) or capon[:LOADING] (Capon's minimum-variance map, which separates sources closer than a beam width;
 loading 1e-2 unless given).  The window's spectra are carried from one --chunk call to the next.  Off unless given; not with
---band, --bands, --exposure, --coherence, --peel, --tone or --pitch.
+--band, --bands, --exposure, --coherence, --peel, --tone or --pitch.  With --csm-clean STEPS[:GAIN[:STOP]] every frame's conventional
+map is deconvolved by CLEAN-SC (Engine.csm_clean_blocks, include/awpu_hip_csm_clean.h): per bin, STEPS rounds of map, take the
+strongest pixel, subtract the part of the matrix coherent with its beam, with loop gain GAIN (1 unless given), a bin ending early
+below STOP times its first peak; the frame is the clean map plus the residual, summed over the bins.
 
 Every block is ingested; every --every'th is swept and shown.  The default 3 gives 48828 / (256 * 3) = 63.6 frames per second, the
 nearest to the 60 the reference opens its writer with.  --chunk blocks go to the engine per call, each call continuing with the
@@ -253,6 +256,8 @@ def main(argv=None) -> int:
                     help="show the cross-spectral map of the transform bins between LO and HI Hz, at most 8 (include/awpu_hip_csm_watch.h)")
     ap.add_argument("--csm-kind", default="conventional", metavar="conventional|diagonal-removed|capon[:LOADING]", help="--csm: which map")
     ap.add_argument("--csm-length", type=int, default=64, metavar="L", help="--csm: every frame's matrix is added up over the L blocks that end with it")
+    ap.add_argument("--csm-clean", default=None, metavar="STEPS[:GAIN[:STOP]]",
+                    help="--csm: show every frame deconvolved by CLEAN-SC, the clean map plus the residual after STEPS steps a bin (include/awpu_hip_csm_clean.h)")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     if a.csm and (a.band or a.bands or a.exposure is not None or a.coherence or a.peel or a.tone or a.pitch):
@@ -267,6 +272,15 @@ def main(argv=None) -> int:
             ap.error(str(e))
         if not 1 <= a.csm_length <= binding.CSM_MAX_LENGTH:
             ap.error(f"--csm-length is between 1 and {binding.CSM_MAX_LENGTH}")
+        if a.csm_clean:
+            try:
+                csm_clean = binding.csm_clean_from_text(a.csm_clean)
+            except ValueError as e:
+                ap.error(str(e))
+            if csm_kind != binding.CSM_CONVENTIONAL:
+                ap.error("--csm-clean deconvolves the conventional map: not with --csm-kind diagonal-removed or capon")
+    elif a.csm_clean:
+        ap.error("--csm-clean goes with --csm")
     if a.tone and a.pitch:
         ap.error("--tone together with --pitch: one row per frame")
     if (a.tone or a.pitch) and (a.bands or a.exposure is not None or a.coherence or a.peel):
@@ -357,6 +371,11 @@ def main(argv=None) -> int:
                 res = eng.tones_blocks(wire[b * block_bytes: (b + nb) * block_bytes], a.cols, a.cols, tone_groups,
                                        show=0 if a.tone else pkg.binding.TONES_SHOW_PITCH, first=first, every=a.every, out_rows=a.size,
                                        out_cols=a.size, d_colormap_ptr=table.data_ptr(), flip=a.flip, want_image=False)
+            elif a.csm and a.csm_clean:
+                res = eng.csm_clean_blocks(wire[b * block_bytes: (b + nb) * block_bytes], a.cols, a.cols, csm_bins, *csm_clean, window=csm_window,
+                                           length=a.csm_length, first=first, every=a.every, carry=carry, carried=carried, out_rows=a.size,
+                                           out_cols=a.size, d_colormap_ptr=table.data_ptr(), flip=a.flip, want_image=False)
+                carry, carried = res.carry, res.carried
             elif a.csm:
                 res = eng.csm_watch_blocks(wire[b * block_bytes: (b + nb) * block_bytes], a.cols, a.cols, csm_bins, csm_window, csm_kind, csm_loading,
                                            a.csm_length, pkg.binding.CSM_SHOW_SUM, first=first, every=a.every, carry=carry, carried=carried,
