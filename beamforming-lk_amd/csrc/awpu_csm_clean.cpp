@@ -22,10 +22,6 @@ int check_clean(awpu_hip *h, const awpu_csm_t *c, const void *matrix) {
     return AWPU_OK;
 }
 
-size_t matrix_floats(const awpu_hip *h, const awpu_csm_t &c) { return (size_t) c.n_bins * h->usable() * h->usable() * 2; }
-size_t v_floats(const awpu_hip *h, const awpu_csm_t &c) { return (size_t) c.n_bins * h->usable() * 2; }
-size_t plane_floats(const awpu_hip *h, const awpu_csm_t &c) { return (size_t) c.n_bins * h->cfg.pixel_count; }
-
 }  // namespace
 
 namespace awpu::host {
@@ -41,9 +37,9 @@ int csm_clean_check(awpu_hip *h, const awpu_csm_t *c) {
 int csm_clean_ready(awpu_hip *h, const awpu_csm_t &c, bool own_matrix) {
     int rc = check_ready(h, 1);
     if (rc == AWPU_OK) rc = csm_ready_map(h, &c);  // (more than 2048 active mics: AWPU_ERR_RANGE)
-    if (rc == AWPU_OK) rc = h->d_csm_clean_rows.ensure(v_floats(h, c) + plane_floats(h, c));
+    if (rc == AWPU_OK) rc = h->d_csm_clean_rows.ensure(csm_spectra_floats(h, c) + csm_plane_floats(h, c));
     if (rc == AWPU_OK) rc = h->d_csm_clean_state.ensure((size_t) AWPU_CSM_MAX_BINS * sizeof(awpu::CsmCleanState));
-    if (rc == AWPU_OK && own_matrix) rc = h->d_csm_clean_matrix.ensure(matrix_floats(h, c));
+    if (rc == AWPU_OK && own_matrix) rc = h->d_csm_clean_matrix.ensure(csm_matrix_floats(h, c));
     return rc;
 }
 
@@ -53,13 +49,12 @@ namespace {
 
 // the component kernel's arguments on the working matrix D, behind csm_clean_ready
 int clean_args(awpu_hip *h, const awpu_csm_t &c, float gain, const float *D, awpu::CsmCleanArgs *a) {
-    const awpu::LutEntry *lut = h->d_lut ? h->d_lut.get() : h->d_cohere_lut.get();
-    if (!lut || !h->d_tones_tables || !h->d_csm_clean_rows.holds(v_floats(h, c) + plane_floats(h, c)) || !h->d_csm_clean_state)
+    if (!csm_lut(h) || !h->d_tones_tables || !h->d_csm_clean_rows.holds(csm_spectra_floats(h, c) + csm_plane_floats(h, c)) || !h->d_csm_clean_state)
         return fail(AWPU_ERR_STATE, "csm_clean_ready comes first");
     *a = awpu::CsmCleanArgs{};
     a->matrix = D;
-    a->lut = lut;
-    a->twiddles = h->d_tones_tables.get() + 2 * awpu::kCsmSamples;
+    a->lut = csm_lut(h);
+    a->twiddles = csm_twiddles(h);
     a->v = h->d_csm_clean_rows.get();
     a->state = reinterpret_cast<awpu::CsmCleanState *>(h->d_csm_clean_state.get());
     a->usable = h->usable(), a->n_pixels = h->cfg.pixel_count, a->wstart = h->wstart, a->n_bins = c.n_bins;
@@ -73,7 +68,7 @@ int clean_args(awpu_hip *h, const awpu_csm_t &c, float gain, const float *D, awp
 int enqueue_loop(awpu_hip *h, float *D, int block_count, const awpu_csm_t &c, const awpu_csm_clean_t &cl, const CsmCleanOut &out, hipStream_t s) {
     awpu::CsmCleanArgs a;
     if (int rc = clean_args(h, c, cl.gain, D, &a)) return rc;
-    float *plane = h->d_csm_clean_rows.get() + v_floats(h, c);
+    float *plane = h->d_csm_clean_rows.get() + csm_spectra_floats(h, c);
     for (int i = 0; i < cl.steps; i++) {
         if (int rc = csm_enqueue_map(h, D, block_count, c, plane, nullptr, s)) return rc;  // P_i
         AWPU_HIP_TRY(awpu::launch_csm_clean_iteration(a, plane, i, cl.stop_ratio, s));
@@ -128,7 +123,7 @@ int awpu_hip_csm_clean_device(awpu_hip_t *h, const float *d_matrix, int32_t bloc
     if (!d_steps && !d_clean && !d_residual && !d_map && !d_residual_matrix) return invalid("no output asked for");
     if (block_count < 1) return invalid("the block count is at least 1");
     int rc = csm_clean_ready(h, *c, d_residual_matrix == nullptr);
-    if (rc == AWPU_OK && d_residual_matrix && overlap(d_matrix, d_residual_matrix, matrix_floats(h, *c)))
+    if (rc == AWPU_OK && d_residual_matrix && overlap(d_matrix, d_residual_matrix, csm_matrix_floats(h, *c)))
         rc = invalid("d_residual_matrix overlaps d_matrix");
     hipStream_t s = stream_of(h, stream);
     if (rc == AWPU_OK) rc = enter_stream(h, s);
@@ -148,7 +143,7 @@ int awpu_hip_csm_clean(awpu_hip_t *h, const float *matrix, int32_t block_count, 
     if (block_count < 1) return invalid("the block count is at least 1");
     int rc = csm_clean_ready(h, *c, false);
     // the matrix goes up; D, the three planes and the steps come back through a buffer of the library's
-    const size_t M = rc == AWPU_OK ? matrix_floats(h, *c) : 0, plane = rc == AWPU_OK ? plane_floats(h, *c) : 0;
+    const size_t M = rc == AWPU_OK ? csm_matrix_floats(h, *c) : 0, plane = rc == AWPU_OK ? csm_plane_floats(h, *c) : 0;
     const size_t step_bytes = (size_t) c->n_bins * cl->steps * sizeof(awpu_csm_clean_step_t), back_bytes = (M + 3 * plane) * sizeof(float) + step_bytes;
     if (rc == AWPU_OK) rc = h->d_csm_clean_io.ensure(M * sizeof(float) + back_bytes);
     if (rc == AWPU_OK) rc = enter_stream(h, h->stream);

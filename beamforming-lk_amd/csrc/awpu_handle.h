@@ -408,7 +408,7 @@ struct awpu_hip {
     // [n_bins][usable][usable][2] each, then the bins' state words
     Dev<double> d_csm_invert;
     // ... and a cross-spectral run's (awpu_hip_csm_watch.h): the spectra store, the carry, one frame's matrix and inverse, a piece's
-    // rows, planes and solved words, a chunk's samples (csm_watch_run lays it out)
+    // rows, planes, solved words and step records, a chunk's samples and datagrams (csm_run_plan.h lays it out)
     Dev<float> d_csm_run;
     // ... and CLEAN-SC's (awpu_hip_csm_clean.h; awpu_csm_clean.cpp): the working matrix D [n_bins][usable][usable][2] where the
     // caller keeps none; the component v [n_bins][usable][2], then the loop's dirty planes [n_bins][pixel_count]; the bins'

@@ -109,6 +109,24 @@ static void stage_watch(awpu_hip *h, const BlockRun &src, int b0, int every, int
     stage_slots(h, src, [=](int slot) { return awpu::watch_slot_block(slot, b0, every, m); }, q, slots, b);
 }
 
+int ring_tail(awpu_hip *h, const BlockRun &src, int n_blocks, hipStream_t s) {
+    const int S = h->cfg.n_streams, b0 = n_blocks - 1, q = std::max(0, std::min(3 - b0, 4));
+    const float *snapshot = h->d_ring + h->ring_pos;
+    if (!src.device) {
+        stage_watch(h, src, b0, 1, q, 4, 0);
+        const size_t block_bytes = (size_t) awpu::kSamples * (src.wire ? (size_t) AWPU_DATAGRAM_BYTES : (size_t) S * sizeof(float));
+        AWPU_HIP_TRY(hipMemcpyAsync(h->blk_in.d[0], h->blk_in.h[0], block_bytes * (4 - q), hipMemcpyHostToDevice, s));
+    }
+    const int rc = gathered_history(h, src, 0, q, 4, AWPU_HIST, s, [&](const float *from, long long from_pitch, int n) {
+        return awpu::launch_watch_gather(from, from_pitch, snapshot, b0, 1, S, hist_of(h, 0), AWPU_HIST, 0, n, s);
+    });
+    if (rc != AWPU_OK) return rc;
+    const int pos = (int) ((h->ring_pos + (long long) awpu::kSamples * n_blocks) % AWPU_HIST);
+    AWPU_HIP_TRY(awpu::launch_ring_write(hist_of(h, 0), AWPU_HIST, 0, S, h->d_ring, pos, s));
+    h->ring_pos = pos;
+    return AWPU_OK;
+}
+
 WatchPieces::WatchPieces(awpu_hip *h_, const BlockRun &src_, int n_blocks_, const WatchRun &wr_)
     : h(h_), src(src_), wr(wr_), w(wr_.w), host(!src_.device), S(h_->cfg.n_streams), m(std::min(wr_.w.every, 4)), P((size_t) h_->cfg.pixel_count),
       display(h_, wr_, !src_.device) {

@@ -133,6 +133,10 @@ int gathered_history(awpu_hip *h, const BlockRun &src, int b, int q, int slots, 
     return AWPU_OK;
 }
 
+// what a run that forms no watch pieces ends with (the cross-spectral runs): the call's last four blocks into the ring, as a watch
+// run's tail piece leaves them -- staged and uploaded (host forms), a history of four slots gathered, the ring written, ring_pos moved
+int ring_tail(awpu_hip *h, const BlockRun &src, int n_blocks, hipStream_t s);
+
 struct WatchPieces : Consumer {
     awpu_hip *const h;
     const BlockRun &src;

@@ -2,7 +2,8 @@
 
 1. Every shown frame equals, bit for bit, csm_accumulate_host over its window from zeros -> csm_clean_host -> the shown row ->
    heatmap_u8 / find_peaks: `what` map, clean and residual, one bin shown and the sum, length 1 and 5 with overlapping windows
-   (every 2), max_batch 2 (several pieces), planes and steps included.  12 blocks, 64 mics, an 8 x 8 grid.
+   (every 2), max_batch 2 (several pieces), planes and steps included.  12 blocks, 64 mics, an 8 x 8 grid.  And 300 blocks (more
+   than one chunk of 256 new blocks), 2 of 8 mics, a 4 x 4 grid.
 2. A recording split over three calls gives one call's bits.
 3. The three forms agree -- the device form between guards --, and the ring after each is the ring after watch_blocks.
 4. Refusals: a bad cl, a bad `what`, kinds 1 and 2; a slab handle.
@@ -50,16 +51,16 @@ def composition(pkg, rig, first, every, length, what, show, lo_block=0):
     return dict(planes=planes, steps=np.stack(steps), power=np.ascontiguousarray(rows))
 
 
-def check_run(pkg, got, want, where):
+def check_run(pkg, got, want, where, res=RES):
     same_where_not_nan(got.planes, want["planes"], (where, "planes"))
     same_where_not_nan(got.power, want["power"], (where, "power"))
     assert np.array_equal(got.steps["pixel"], want["steps"]["pixel"]), (where, "picks")
     same_where_not_nan(got.steps["before"], want["steps"]["before"], (where, "before"))
     same_where_not_nan(got.steps["removed"], want["steps"]["removed"], (where, "removed"))
     assert not np.isnan(want["power"]).any(), where
-    image = np.stack([pkg.heatmap_u8(p) for p in want["power"]]).reshape(-1, RES, RES)
+    image = np.stack([pkg.heatmap_u8(p) for p in want["power"]]).reshape(-1, res, res)
     assert np.array_equal(got.image, image), (where, "image")
-    found = pkg.find_peaks(want["power"], RES, RES, **FIND)
+    found = pkg.find_peaks(want["power"], res, res, **FIND)
     assert np.array_equal(got.count, found.count), (where, "count")
     assert np.array_equal(got.sources["pixel"], found.sources["pixel"]), (where, "sources")
     assert CU.same_bits(got.sources["power"], found.sources["power"]), (where, "source powers")
@@ -80,6 +81,28 @@ def test_runs_equal_the_composition(pkg, rig):
                     check_run(pkg, got, want, where)
                     assert got.carried == min(BLOCKS, length - 1) and got.next_first == B.watch_count(BLOCKS, 1, 2)[1]
         assert (want["steps"]["pixel"][:, :, 0] >= 0).all() and len(want["power"]) == 6  # (max_batch 2: three pieces)
+
+
+def test_more_blocks_than_a_chunk(pkg, oracle):
+    """300 blocks, 2 of 8 mics, a 4 x 4 grid, max_batch 2, length 3, 2 steps: frames at 99, 199, 299 (a full piece ends the first
+    chunk behind block 199; the step records come back piece by piece) and at 127, 256 (the second chunk of new blocks starts at
+    block 256, inside the second frame's window)."""
+    B = pkg.binding
+    rig = Rig(pkg, oracle, 8, [5, 2], False, 33, n_blocks=300, res=4)
+    length, steps, bins, what = 3, 2, [16], B.CSM_CLEAN_CLEAN
+    with rig.engine(max_batch=2) as eng:
+        for first, every in ((99, 100), (127, 129)):
+            frames = []
+            for t in range(first, 300, every):
+                Cm, n = pkg.csm_accumulate_host(np.ascontiguousarray(rig.samples[:, 256 * (t - length + 1): 256 * (t + 1)]), bins, 0, index=rig.index)
+                assert n == length
+                frames.append(pkg.csm_clean_host(Cm, n, rig.off, rig.frac, bins, steps, GAIN, STOP, 0, index=rig.index))
+            planes = np.stack([fr[ROWS[what]] for fr in frames])
+            want = dict(planes=planes, steps=np.stack([fr["steps"] for fr in frames]), power=np.ascontiguousarray(shown_sum(planes)))
+            got = eng.csm_clean_samples(rig.samples, 4, 4, bins, steps, GAIN, STOP, what, length=length, show=B.CSM_SHOW_SUM, first=first, every=every,
+                                        **dict(KW, window=0))
+            check_run(pkg, got, want, (first, every), res=4)
+            assert (want["steps"]["pixel"][:, :, 0] >= 0).all() and got.carried == length - 1
 
 
 def test_a_split_recording_gives_one_calls_bits(pkg, rig):

@@ -9,7 +9,8 @@ clock); and one Capon frame of --blocks blocks two ways, wall clock from an idle
 one stream (accumulate, csm_invert_device, map: capon_device_ms) against the composition the device inverse replaces (accumulate,
 the matrix to the host, csm_invert_host, the inverse back up, map: capon_host_inverse_ms).  And the Capon run
 (Engine.csm_watch_samples_device, include/awpu_hip_csm_watch.h): 8 frames of length --blocks, one every --blocks blocks, in one call
--- run_frames_per_s -- beside composition_frames_per_s, the frames a second of capon_host_inverse.
+-- run_frames_per_s -- beside composition_frames_per_s, the frames a second of capon_host_inverse, and the same frames through the
+CLEAN-SC run (Engine.csm_clean_samples_device, 4 steps): clean_run_frames_per_s.
 
   tools/csm_rate.py --repeats 20
 
@@ -117,8 +118,13 @@ def main():
                                              pkg.binding.CSM_CAPON, LOADING, a.blocks, pkg.binding.CSM_SHOW_SUM, a.blocks - 1, a.blocks,
                                              d_carry_ptr=run_carry.data_ptr(), carried=0, d_power_ptr=run_power.data_ptr(), stream=side.cuda_stream)
 
+            def clean_run():  # the same frames through the CLEAN-SC run (Engine.csm_clean_samples_device, CLEAN_STEPS steps): clean_run_frames_per_s
+                eng.csm_clean_samples_device(run_samples.data_ptr(), run_samples.shape[1], a.blocks * run_frames, spec.res, spec.res, bins8, CLEAN_STEPS,
+                                             1.0, 0.0, pkg.binding.CSM_CLEAN_CLEAN, 1, a.blocks, pkg.binding.CSM_SHOW_SUM, a.blocks - 1, a.blocks,
+                                             d_carry_ptr=run_carry.data_ptr(), carried=0, d_power_ptr=run_power.data_ptr(), stream=side.cuda_stream)
+
             host_matrix = matrix.cpu().numpy()
-            walls = {"capon_run": capon_run, "invert_host_8": lambda: pkg.csm_invert_host(host_matrix, a.blocks, bins8, loading=LOADING), "capon_device": capon_device,
+            walls = {"capon_run": capon_run, "clean_run": clean_run, "invert_host_8": lambda: pkg.csm_invert_host(host_matrix, a.blocks, bins8, loading=LOADING), "capon_device": capon_device,
                      "capon_host_inverse": capon_host_inverse}
             for name, call in walls.items():
                 times[name] = []
@@ -144,6 +150,7 @@ def main():
                 row[f"clean_{n_bins}_over_maps"] = round(loop / maps, 3)
                 row[f"clean_{n_bins}_between_maps_ms"] = round((loop - maps) / CLEAN_STEPS, 4)
             row["run_frames_per_s"] = round(run_frames / statistics.median(times["capon_run"]) * 1e3, 1)
+            row["clean_run_frames_per_s"] = round(run_frames / statistics.median(times["clean_run"]) * 1e3, 1)
             row["composition_frames_per_s"] = round(1e3 / statistics.median(times["capon_host_inverse"]), 1)
             row["blocks_per_s"] = round(a.blocks / statistics.median(times["accumulate_8"]) * 1e3, 1)
             print(json.dumps(row), flush=True)
