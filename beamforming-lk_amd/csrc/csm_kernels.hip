@@ -18,8 +18,8 @@
 // pixels, one a SIMD: a round is 16 rows, wave w takes rows 4 w .. 4 w + 3 of it, each y_a is one wave's chain in the rule's order;
 // the waves leave the round's y in a small LDS ring (two rounds deep, one barrier a round) and every wave then adds the round's
 // sixteen rows to x and d, a ascending -- the rule's order again, 32 fmaf done four times over beside the thousands of a round.
-// usable * ppw * 8 bytes plus the ring must fit 144 KiB: up to 256 mics a workgroup maps 64 pixels, up to 512 mics 32, .., up to
-// 2048 eight.
+// (usable + 32) * ppw * 8 bytes, the vectors and the ring, must fit 144 KiB: up to 256 mics a workgroup maps 64 pixels, up to 544
+// mics 32, up to 1120 sixteen, up to 2048 eight.
 //   Contraction is off in this file.
 #include "csm_kernels.h"
 

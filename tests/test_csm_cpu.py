@@ -3,7 +3,8 @@ built from the globbed files; every host function equals a numpy restatement of 
 exactly Hermitian and a recording split over two calls gives one call's bits; steering, spectra, the quadratic form and the
 inverse meet fp64; a unit sine gives 0.5 in the conventional and the diagonal-removed map and 0.5 (1 + loading / usable) in Capon's; on the two-source scene delay-and-sum's conventional plane shows one
 source, Capon's both, and the diagonal-removed plane a lower floor; refusals write nothing; the host code runs clean under the
-address and undefined-behaviour sanitizers as a program of its own; the kernels compile for gfx950 without spills or scratch."""
+address and undefined-behaviour sanitizers as a program of its own; the kernels compile for gfx950 without spills or scratch.
+The accuracy of q and of the loaded inverse at 545 to 2048 and at 512 mics: test_csm_large_cpu.py."""
 import ctypes as C
 import re
 import subprocess

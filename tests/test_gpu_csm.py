@@ -11,7 +11,9 @@
    has NaN.
 3. Stream order: csm_samples_device and csm_map_device behind pending work on their stream (tests/stream_order.py).
 4. The state refusals: FIR8, a band on the handle, a call during process_async, no table; bad requests; outputs left alone.
-5. The scene: its Capon plane, swept on the device and passed to find_peaks_device, has its two sources."""
+5. The scene: its Capon plane, swept on the device and passed to find_peaks_device, has its two sources.
+6. Above 257 mics -- 544, 545 of 640, 1120, 1121 and 2048, where a workgroup maps 32, 16 and 8 pixels; the refusal at 2049 --:
+   test_gpu_csm_large.py, with this file's Shape and helpers."""
 import ctypes as C
 
 import numpy as np
@@ -33,10 +35,13 @@ SLACK = 40  # floats between the last block of a stream and the next stream: pit
 
 
 class Shape:
-    """A hand-made table -- offsets at both ends of the history, fractions 0, 1 and in between --, an active list and samples."""
+    """A hand-made table -- offsets at both ends of the history, fractions 0, 1 and in between --, an active list and samples of
+    `blocks` blocks.  invert=False (test_gpu_csm_large.py's lists above 512 mics, where csm_invert_host takes minutes): the Capon
+    kind is given C itself in place of an inverse."""
 
-    def __init__(self, pkg, name, n_streams, lut_stride, index, pixels, gains, seed):
+    def __init__(self, pkg, name, n_streams, lut_stride, index, pixels, gains, seed, blocks=17, invert=True):
         rng = np.random.default_rng(seed)
+        self.invert = invert
         self.pkg, self.name, self.S, self.stride, self.P = pkg, name, n_streams, lut_stride, pixels
         self.index = np.asarray(index, np.int32)
         self.U = len(self.index)
@@ -47,7 +52,7 @@ class Shape:
         self.frac.reshape(-1)[::5] = 0.0
         self.frac.reshape(-1)[2::9] = 1.0
         self.gains = (0.5 + rng.random(n_streams)).astype(np.float32) if gains else None
-        self.samples = (rng.standard_normal((n_streams, 17 * 256 + SLACK)) * 0.1).astype(np.float32)
+        self.samples = (rng.standard_normal((n_streams, blocks * 256 + SLACK)) * 0.1).astype(np.float32)
         self._rules = {}
 
     def gain_list(self):
@@ -74,8 +79,8 @@ class Shape:
             pkg, x = self.pkg, self.samples_of(n_blocks)
             out = {"spectra": pkg.csm_spectra_host(x, bins, window, index=self.index, gain=self.gain_list(), n_blocks=n_blocks)}
             out["C"], out["n"] = pkg.csm_accumulate_host(x, bins, window, index=self.index, gain=self.gain_list(), n_blocks=n_blocks)
-            out["G"] = None
-            if np.isfinite(out["C"]).all():
+            out["G"] = None if self.invert else out["C"]
+            if self.invert and np.isfinite(out["C"]).all():
                 try:
                     out["G"] = pkg.csm_invert_host(out["C"], out["n"], bins, loading=0.05)
                 except pkg.AwpuError:

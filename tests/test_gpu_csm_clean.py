@@ -10,7 +10,9 @@
 4. EXACT and FAST handles give the same bits.
 5. One call behind pending work on its stream gives a settled handle's bits (tests/stream_order.py).
 6. A second call with more bins and more mics after a small one.
-7. The handle refusals: nothing is enqueued and nothing is written."""
+7. The handle refusals: nothing is enqueued and nothing is written.
+8. 545 of 640 and 2048 mics (three and eight passes of the component kernel's rows) and the refusal at 2049: test_gpu_csm_large.py,
+   with this file's helpers."""
 import ctypes as C
 
 import numpy as np

@@ -7,7 +7,8 @@
 2. A recording split over three calls gives one call's bits.
 3. The three forms agree -- the device form between guards --, and the ring after each is the ring after watch_blocks.
 4. Refusals: a bad cl, a bad `what`, kinds 1 and 2; a slab handle.
-5. tools/pcap_video.py and tools/pcap_sources.py with --csm-clean on a capture, in chunks: one csm_clean_blocks call's frames and steps."""
+5. tools/pcap_video.py and tools/pcap_sources.py with --csm-clean on a capture, in chunks: one csm_clean_blocks call's frames and steps.
+6. A run at 545 of 640 mics and the refusal at 2049: test_gpu_csm_large.py, with this file's check_run."""
 import numpy as np
 import pytest
 
@@ -51,16 +52,17 @@ def composition(pkg, rig, first, every, length, what, show, lo_block=0):
     return dict(planes=planes, steps=np.stack(steps), power=np.ascontiguousarray(rows))
 
 
-def check_run(pkg, got, want, where, res=RES):
+def check_run(pkg, got, want, where, res=RES, rows=None):
+    rows = res if rows is None else rows  # (test_gpu_csm_large.py's grid is not square)
     same_where_not_nan(got.planes, want["planes"], (where, "planes"))
     same_where_not_nan(got.power, want["power"], (where, "power"))
     assert np.array_equal(got.steps["pixel"], want["steps"]["pixel"]), (where, "picks")
     same_where_not_nan(got.steps["before"], want["steps"]["before"], (where, "before"))
     same_where_not_nan(got.steps["removed"], want["steps"]["removed"], (where, "removed"))
     assert not np.isnan(want["power"]).any(), where
-    image = np.stack([pkg.heatmap_u8(p) for p in want["power"]]).reshape(-1, res, res)
+    image = np.stack([pkg.heatmap_u8(p) for p in want["power"]]).reshape(-1, rows, res)
     assert np.array_equal(got.image, image), (where, "image")
-    found = pkg.find_peaks(want["power"], res, res, **FIND)
+    found = pkg.find_peaks(want["power"], rows, res, **FIND)
     assert np.array_equal(got.count, found.count), (where, "count")
     assert np.array_equal(got.sources["pixel"], found.sources["pixel"]), (where, "sources")
     assert CU.same_bits(got.sources["power"], found.sources["power"]), (where, "source powers")

@@ -7,7 +7,9 @@ runs on top of it (include/awpu_hip_csm_watch.h; 4 to 10, listed where they begi
    blocks than mics, one with fewer blocks than mics and loading > 0, and an unsolved bin among solved ones; guards intact.
 2. The synchronous csm_invert: the same bits; an unsolved bin gives AWPU_ERR_RANGE with the output untouched; more than 512 active
    mics give AWPU_ERR_RANGE; the state refusals of the cross-spectral calls.
-3. Stream order: csm_invert_device behind pending work on its stream (tests/stream_order.py)."""
+3. Stream order: csm_invert_device behind pending work on its stream (tests/stream_order.py).
+The inverse at 511 and 512 mics, its bound, and runs on lists of 545 and 512 mics with the runs' range refusals (11):
+test_gpu_csm_large.py, with this file's lists, helpers and rig."""
 import ctypes as C
 
 import numpy as np
@@ -31,7 +33,10 @@ MICS = {"one_mic": (8, [3]),
         "sixty_five_of_128": (128, list(range(0, 128, 2)) + [127]),
         "ninety_five_of_96": (96, [i for i in range(96) if i != 40]),
         "ninety_six": (96, list(range(96))),
-        "two_fifty_seven_of_320": (320, [i for i in range(320) if i % 5 != 4] + [319])}
+        "two_fifty_seven_of_320": (320, [i for i in range(320) if i % 5 != 4] + [319]),
+        # test_gpu_csm_large.py's: the bound of the inverse, and one below it on a ragged list
+        "five_eleven_of_512": (512, [i for i in range(512) if i != 300]),
+        "five_twelve": (512, list(range(512)))}
 
 
 def engine_of(pkg, name, **kw):
@@ -265,6 +270,8 @@ def test_csm_invert_device_behind_pending_work(pkg, scenes, busy):  # noqa: F811
 # 5. One recording in one call equals two and three calls through carry / carried, each cut inside a window.
 # 6. The three forms agree, and the ring after each is the ring after watch_blocks on the same datagrams.
 # 7. Value edges: an all-zero recording under Capon; one NaN sample.  8. Stream order.  9. The scene as one frame.  10. Refusals.
+# 11. (test_gpu_csm_large.py) Conventional and diagonal-removed runs at 545 of 640 mics and Capon's at 512, on a 3 x 7 grid; more
+#     mics than the map or the inverse takes: AWPU_ERR_RANGE.
 
 from test_gpu_blocks import recording  # noqa: E402
 
@@ -276,16 +283,21 @@ KINDS = (CU.CONVENTIONAL, CU.DIAGONAL_REMOVED, CU.CAPON)
 
 
 class Rig:
-    """A hand-made table on a RES x RES grid, an active list (with gains where ragged) and a recording as datagrams and samples."""
+    """A hand-made table on a grid of `rows` x `res` pixels (RES x RES unless given), an active list (with gains where ragged) and a
+    recording as datagrams and samples; above 256 streams, more than the wire carries, as samples alone."""
 
-    def __init__(self, pkg, oracle, n_streams, index, gains, seed, n_blocks=RUN_BLOCKS, res=RES):
+    def __init__(self, pkg, oracle, n_streams, index, gains, seed, n_blocks=RUN_BLOCKS, res=RES, rows=None):
         rng = np.random.default_rng(seed)
-        self.pkg, self.S, self.res, self.P, self.n_blocks = pkg, n_streams, res, res * res, n_blocks
+        self.rows = res if rows is None else rows
+        self.pkg, self.S, self.res, self.P, self.n_blocks = pkg, n_streams, res, self.rows * res, n_blocks
         self.index = np.asarray(index, np.int32)
         self.off = rng.integers(0, 1024 - 256, (self.P, n_streams)).astype(np.int32)
         self.frac = rng.random((self.P, n_streams)).astype(np.float32)
         self.gains = (0.5 + rng.random(n_streams)).astype(np.float32) if gains else None
-        self.wire, self.samples = recording(oracle, n_blocks, n_streams, seed)
+        if n_streams <= 256:
+            self.wire, self.samples = recording(oracle, n_blocks, n_streams, seed)
+        else:
+            self.wire, self.samples = None, rng.standard_normal((n_streams, 256 * n_blocks)).astype(np.float32)
         self.samples = np.ascontiguousarray(self.samples, np.float32)
         self._frames = {}
 
@@ -354,9 +366,9 @@ def check_run(pkg, rig, got, want, where, exact=True):
     assert np.array_equal(got.solved, want["solved"]), (where, "solved")
     assert same(got.power, want["power"]), (where, "power")
     if n_frames and not np.isnan(want["power"]).any():
-        image = np.stack([pkg.heatmap_u8(p) for p in want["power"]]).reshape(-1, rig.res, rig.res)
+        image = np.stack([pkg.heatmap_u8(p) for p in want["power"]]).reshape(-1, rig.rows, rig.res)
         assert np.array_equal(got.image, image), (where, "image")
-        found = pkg.find_peaks(want["power"], rig.res, rig.res, **RUN_FIND)
+        found = pkg.find_peaks(want["power"], rig.rows, rig.res, **RUN_FIND)
         assert np.array_equal(got.count, found.count), (where, "count")
         assert np.array_equal(got.sources["pixel"], found.sources["pixel"]), (where, "sources")
         assert CU.same_bits(got.sources["power"], found.sources["power"]), (where, "source powers")
