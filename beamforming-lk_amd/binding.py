@@ -6,7 +6,9 @@ loaded, importing a compute entry point raises.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import functools
 import os
 from typing import Optional
 
@@ -582,6 +584,18 @@ def load(build: bool = True) -> C.CDLL:
     return lib
 
 
+@contextlib.contextmanager
+def loaded_library(lib: C.CDLL):
+    """Within the block load() hands out `lib` -- a variant build whose entry points the caller has typed -- in place of this
+    build's; an Engine keeps the library it was created with, so one made in the block stays on `lib` after it."""
+    global _lib
+    mine, _lib = load(), lib
+    try:
+        yield lib
+    finally:
+        _lib = mine
+
+
 def _check(status: int, where: str) -> None:
     if status != OK:
         lib = load()
@@ -603,6 +617,21 @@ def _i32(a: np.ndarray):
     return a.ctypes.data_as(_i32p)
 
 
+def _f64_vector(x) -> np.ndarray:
+    """A scalar or sequence as the contiguous 1-D float64 array the calls take angles and distances as."""
+    return np.ascontiguousarray(np.atleast_1d(x), np.float64)
+
+
+def _ref(struct):
+    """An optional structure as a call's argument: by reference, or a null pointer for None (a run without `find`)."""
+    return None if struct is None else C.byref(struct)
+
+
+def _dev(*pointers):
+    """Device addresses (integers; 0 = not given) and a stream as the void pointers a call takes."""
+    return [C.c_void_p(p) for p in pointers]
+
+
 def _wire_blocks(wire, stride: int):
     """(the bytes of wire datagrams `stride` bytes apart, how many blocks of 256 they are)."""
     buf = np.frombuffer(wire, dtype=np.uint8)
@@ -617,6 +646,12 @@ def _find_struct(rows: int, cols: int, find: Optional[dict]) -> Optional[Find]:
         return None
     return Find(rows, cols, find.get("radius", 2), find.get("max_sources", 4), find.get("min_power", 0.0), find.get("min_ratio", 0.0),
                 find.get("fov_deg", 180.0))
+
+
+def _watch_struct(rows: int, cols: int, first: int, every: int, out_rows: int = 0, out_cols: int = 0, d_colormap_ptr: int = 0,
+                  flip: bool = False) -> Watch:
+    """The display keywords of a run's method as its awpu_watch_t: the run helpers take them as **shown and hand them on here."""
+    return Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(d_colormap_ptr))
 
 
 def _out_ptr(a: Optional[np.ndarray], ctype=None):
@@ -681,8 +716,8 @@ def build_delay_table_device(xyz: np.ndarray, rows: int, columns: int, fov_deg: 
 def steer_table(xyz: np.ndarray, theta, phi):
     """Particle::steer (src/dsp/particle.cpp:37-49) for a batch of directions -> (off, frac) [n_dir, n]."""
     xyz = np.ascontiguousarray(xyz, np.float32)
-    theta = np.ascontiguousarray(np.atleast_1d(theta), np.float64)
-    phi = np.ascontiguousarray(np.atleast_1d(phi), np.float64)
+    theta = _f64_vector(theta)
+    phi = _f64_vector(phi)
     if theta.shape != phi.shape or theta.ndim != 1:
         raise ValueError("theta and phi must be 1-D and alike")
     n = xyz.shape[1]
@@ -757,7 +792,7 @@ def range_pick(power: np.ndarray, distance) -> np.ndarray:
     """Which candidate distance wins for every row of power [n_src, n_dist], refined between the candidates -> RANGE_DTYPE records
     [n_src] (awpu_hip_range_pick: the rule of include/awpu_hip_focus.h as executable C)."""
     power = np.ascontiguousarray(power, np.float32)
-    distance = np.ascontiguousarray(np.atleast_1d(distance), np.float64)
+    distance = _f64_vector(distance)
     power = power.reshape(-1, max(distance.size, 1))
     best = np.zeros(len(power), RANGE_DTYPE)
     _check(load().awpu_hip_range_pick(_f32(power), len(power), distance.ctypes.data_as(_f64p), distance.size,
@@ -1606,7 +1641,12 @@ class Engine:
             n = index.size
             _check(self._lib.awpu_hip_set_active_mics(self._h, _i32(index), index.size),
                    "set_active_mics")
-        self._usable = int(n)  # (what the cross-spectral calls size their matrices by)
+        self._usable = int(n)
+
+    @property
+    def usable(self) -> int:
+        """How many mics are active: what the cross-spectral calls size their matrices by (all streams until set_active_mics)."""
+        return getattr(self, "_usable", self.cfg.n_streams)
 
     def ingest_block(self, datagrams) -> None:
         """One block of 256 wire datagrams (bytes-like, 256 x 1032 B; src/fpga/receiver.h:24-30)."""
@@ -1632,6 +1672,29 @@ class Engine:
             raise ValueError(f"samples must be [{self.cfg.n_streams}, N] with N a positive multiple of 256")
         return samples, samples.shape[1] // 256
 
+    def _wire_run(self, where: str, wire, stride: int):
+        """A run on wire datagrams as its helper takes it: (entry point `where` with the handle, the bytes and their stride in
+        place, where, n_blocks)."""
+        buf, n_blocks = _wire_blocks(wire, stride)
+        return functools.partial(getattr(self._lib, where), self._h, buf.ctypes.data_as(C.c_void_p), stride), where, n_blocks
+
+    def _sample_run(self, where: str, samples):
+        """The same on unpacked samples: the floats and their pitch in place."""
+        samples, n_blocks = self._sample_blocks(samples)
+        return functools.partial(getattr(self._lib, where), self._h, _f32(samples), samples.shape[1]), where, n_blocks
+
+    def _device_run(self, where: str, d_samples_ptr: int, pitch: int, n_blocks: int, w: Watch, *rest) -> int:
+        """A run on device pointers: entry point `where` on samples [n_streams, pitch], with `rest` behind n_blocks and w, in the
+        order of its prototype -> next_first."""
+        _check(getattr(self._lib, where)(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, C.byref(w), *rest), where)
+        return watch_count(n_blocks, w.first, w.every)[1]
+
+    @staticmethod
+    def _shown_frames(n_blocks: int, *, first: int, every: int, **shown):
+        """(n_frames, next_first, the awpu_watch_t) of a run of n_blocks blocks with these display keywords (_watch_struct's)."""
+        n_frames, next_first = watch_count(n_blocks, first, every)
+        return n_frames, next_first, _watch_struct(first=first, every=every, **shown)
+
     def _shown_outputs(self, n_frames, w: Watch, want_image, want_power, f: Optional[Find] = None, new=lambda shape, dtype, name: np.empty(shape, dtype)):
         """What a run shows of its n_frames frames: the arrays (image, big, power, sources, count), each or None, and their
         pointers as the C calls take them; new(shape, dtype, name) allocates one."""
@@ -1649,28 +1712,26 @@ class Engine:
         """A run of consecutive blocks of wire datagrams (bytes-like, n_blocks x 256 datagrams `stride` bytes apart) ->
         power [n_blocks, pixels]: row k = process_ring() after k + 1 ingest_block() calls, and the ring is left there
         (awpu_hip_process_blocks)."""
-        buf, n_blocks = _wire_blocks(wire, stride)
+        call, where, n_blocks = self._wire_run("awpu_hip_process_blocks", wire, stride)
         power = np.empty((n_blocks, self.pixel_count), np.float32)
-        _check(self._lib.awpu_hip_process_blocks(self._h, buf.ctypes.data_as(C.c_void_p), stride, n_blocks, _f32(power)),
-               "awpu_hip_process_blocks")
+        _check(call(n_blocks, _f32(power)), where)
         return power
 
     def process_samples(self, samples: np.ndarray) -> np.ndarray:
         """The same from unpacked samples [n_streams, N] (N a multiple of 256, oldest first) -> power [N // 256, pixels]
         (awpu_hip_process_samples)."""
-        samples, n_blocks = self._sample_blocks(samples)
+        call, where, n_blocks = self._sample_run("awpu_hip_process_samples", samples)
         power = np.empty((n_blocks, self.pixel_count), np.float32)
-        _check(self._lib.awpu_hip_process_samples(self._h, _f32(samples), samples.shape[1], n_blocks, _f32(power)),
-               "awpu_hip_process_samples")
+        _check(call(n_blocks, _f32(power)), where)
         return power
 
     def process_samples_device(self, d_samples_ptr: int, pitch: int, n_blocks: int, d_power_ptr: int, stream: int = 0) -> None:
         """The same on device pointers (samples [n_streams, pitch], power [n_blocks, pixels]) on `stream`; asynchronous."""
-        _check(self._lib.awpu_hip_process_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks,
-                                                         C.c_void_p(d_power_ptr), C.c_void_p(stream)),
+        _check(self._lib.awpu_hip_process_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, *_dev(d_power_ptr, stream)),
                "awpu_hip_process_samples_device")
 
-    def _listen(self, call, where, n_blocks, particles, theta_limit, reference, want_trail, want_power) -> ListenResult:
+    def _listen(self, run, *, particles, theta_limit, reference, want_trail, want_power) -> ListenResult:
+        call, where, n_blocks = run
         parts = _particles(*particles, where)
         n = parts.size
         audio = np.empty((n, 256 * n_blocks), np.float32)
@@ -1689,18 +1750,14 @@ class Engine:
         256 samples of its audio row; the ring is left where the run ends (awpu_hip_listen_blocks).  theta/phi/spread/rate/steps
         are per listener (scalars broadcast), or `theta` is the .listeners of an earlier result (the rest then None);
         reference None = from each block's own snapshot, as MISOWorker does.  -> ListenResult."""
-        buf, n_blocks = _wire_blocks(wire, stride)
-        return self._listen(lambda *rest: self._lib.awpu_hip_listen_blocks(self._h, buf.ctypes.data_as(C.c_void_p), stride, *rest),
-                            "awpu_hip_listen_blocks", n_blocks, (theta, phi, spread, rate, steps), theta_limit,
-                            reference, want_trail, want_power)
+        return self._listen(self._wire_run("awpu_hip_listen_blocks", wire, stride), particles=(theta, phi, spread, rate, steps),
+                            theta_limit=theta_limit, reference=reference, want_trail=want_trail, want_power=want_power)
 
     def listen_samples(self, samples: np.ndarray, theta, phi, spread, rate, steps, theta_limit: float,
                        reference: Optional[float] = None, want_trail: bool = True, want_power: bool = False) -> ListenResult:
         """The same from unpacked samples [n_streams, N] (N a multiple of 256, oldest first) (awpu_hip_listen_samples)."""
-        samples, n_blocks = self._sample_blocks(samples)
-        return self._listen(lambda *rest: self._lib.awpu_hip_listen_samples(self._h, _f32(samples), samples.shape[1], *rest),
-                            "awpu_hip_listen_samples", n_blocks, (theta, phi, spread, rate, steps), theta_limit,
-                            reference, want_trail, want_power)
+        return self._listen(self._sample_run("awpu_hip_listen_samples", samples), particles=(theta, phi, spread, rate, steps),
+                            theta_limit=theta_limit, reference=reference, want_trail=want_trail, want_power=want_power)
 
     def listen_samples_device(self, d_samples_ptr: int, pitch: int, n_blocks: int, theta, phi, spread, rate, steps, theta_limit: float,
                               d_audio_ptr: int, audio_pitch: int, reference: Optional[float] = None, d_trail_ptr: int = 0,
@@ -1712,13 +1769,12 @@ class Engine:
         _check(self._lib.awpu_hip_listen_samples_device(
             self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, parts.ctypes.data_as(C.POINTER(Particle)), parts.size,
             float(theta_limit), -1.0 if reference is None else float(reference), C.c_void_p(d_audio_ptr), audio_pitch,
-            C.c_void_p(d_trail_ptr), C.c_void_p(d_power_ptr), C.c_void_p(stream)), "awpu_hip_listen_samples_device")
+            *_dev(d_trail_ptr, d_power_ptr, stream)), "awpu_hip_listen_samples_device")
         return parts
 
-    def _watch(self, call, where, n_blocks, first, every, rows, cols, out_rows, out_cols, d_colormap_ptr, flip, want_image,
-               want_power, out) -> WatchResult:
-        n_frames, next_first = watch_count(n_blocks, first, every)
-        w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(d_colormap_ptr))
+    def _watch(self, run, *, want_image, want_power, out, **shown) -> WatchResult:
+        call, where, n_blocks = run
+        n_frames, next_first, w = self._shown_frames(n_blocks, **shown)
 
         def array(shape, dtype, old):  # the earlier result's array where it has room (its first n_frames rows), else a new one
             if isinstance(old, np.ndarray) and old.dtype == dtype and old.shape[1:] == shape[1:] and old.flags.c_contiguous:
@@ -1741,19 +1797,17 @@ class Engine:
         powers (awpu_hip_watch_blocks).  -> WatchResult; pass its .next_first as `first` of the call that continues the run, and
         the result itself as `out` when its arrays may be written again (a writer that is done with a chunk's frames: 3 MiB per
         1024 x 1024 colour frame are then not allocated and paged in anew for every call)."""
-        buf, n_blocks = _wire_blocks(wire, stride)
-        return self._watch(lambda *rest: self._lib.awpu_hip_watch_blocks(self._h, buf.ctypes.data_as(C.c_void_p), stride, *rest),
-                           "awpu_hip_watch_blocks", n_blocks, first, every, rows, cols, out_rows, out_cols,
-                           d_colormap_ptr, flip, want_image, want_power, out)
+        return self._watch(self._wire_run("awpu_hip_watch_blocks", wire, stride), rows=rows, cols=cols, first=first, every=every,
+                           out_rows=out_rows, out_cols=out_cols, d_colormap_ptr=d_colormap_ptr, flip=flip, want_image=want_image,
+                           want_power=want_power, out=out)
 
     def watch_samples(self, samples: np.ndarray, rows: int, cols: int, first: int = 0, every: int = 1, out_rows: int = 0,
                       out_cols: int = 0, d_colormap_ptr: int = 0, flip: bool = False, want_image: bool = True,
                       want_power: bool = False, out: Optional[WatchResult] = None) -> WatchResult:
         """The same from unpacked samples [n_streams, N] (N a multiple of 256, oldest first) (awpu_hip_watch_samples)."""
-        samples, n_blocks = self._sample_blocks(samples)
-        return self._watch(lambda *rest: self._lib.awpu_hip_watch_samples(self._h, _f32(samples), samples.shape[1], *rest),
-                           "awpu_hip_watch_samples", n_blocks, first, every, rows, cols, out_rows, out_cols,
-                           d_colormap_ptr, flip, want_image, want_power, out)
+        return self._watch(self._sample_run("awpu_hip_watch_samples", samples), rows=rows, cols=cols, first=first, every=every,
+                           out_rows=out_rows, out_cols=out_cols, d_colormap_ptr=d_colormap_ptr, flip=flip, want_image=want_image,
+                           want_power=want_power, out=out)
 
     def watch_samples_device(self, d_samples_ptr: int, pitch: int, n_blocks: int, rows: int, cols: int, first: int = 0, every: int = 1,
                              d_image_ptr: int = 0, d_big_ptr: int = 0, d_power_ptr: int = 0, out_rows: int = 0, out_cols: int = 0,
@@ -1761,11 +1815,10 @@ class Engine:
         """The same on device pointers (samples [n_streams, pitch]; image [n_frames, rows * cols], big [n_frames, out_rows,
         out_cols (, 3)], power [n_frames, pixels], each or 0) on `stream`; asynchronous.  -> next_first
         (awpu_hip_watch_samples_device)."""
-        w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(d_colormap_ptr))
-        _check(self._lib.awpu_hip_watch_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, C.byref(w),
-                                                       C.c_void_p(d_image_ptr), C.c_void_p(d_big_ptr), C.c_void_p(d_power_ptr),
-                                                       C.c_void_p(stream)), "awpu_hip_watch_samples_device")
-        return watch_count(n_blocks, first, every)[1]
+        w = _watch_struct(rows=rows, cols=cols, first=first, every=every, out_rows=out_rows, out_cols=out_cols, d_colormap_ptr=d_colormap_ptr,
+                          flip=flip)
+        return self._device_run("awpu_hip_watch_samples_device", d_samples_ptr, pitch, n_blocks, w,
+                                *_dev(d_image_ptr, d_big_ptr, d_power_ptr, stream))
 
     def process_bands(self, frames: np.ndarray, bands) -> np.ndarray:
         """frames [batch, n_streams, hist] through every band of `bands` (a sequence of up to four coefficient arrays) from one
@@ -1783,17 +1836,16 @@ class Engine:
         """The same on device pointers (frames [batch, n_streams, hist], power [n_bands, batch, pixels]) on `stream`; asynchronous
         (awpu_hip_process_bands_device)."""
         sp, _keep = spectral_of(bands)
-        _check(self._lib.awpu_hip_process_bands_device(self._h, C.c_void_p(d_frames_ptr), batch, C.byref(sp), C.c_void_p(d_power_ptr),
-                                                       C.c_void_p(stream)), "awpu_hip_process_bands_device")
+        _check(self._lib.awpu_hip_process_bands_device(self._h, C.c_void_p(d_frames_ptr), batch, C.byref(sp), *_dev(d_power_ptr, stream)),
+               "awpu_hip_process_bands_device")
 
-    def _spectral(self, call, where, n_blocks, first, every, rows, cols, out_rows, out_cols, flip, bands, channel, scale, want_image,
-                  want_dominant, want_power) -> SpectralResult:
-        n_frames, next_first = watch_count(n_blocks, first, every)
-        w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(0))
+    def _spectral(self, run, *, bands, channel, scale, want_image, want_dominant, want_power, **shown) -> SpectralResult:
+        call, where, n_blocks = run
+        n_frames, next_first, w = self._shown_frames(n_blocks, **shown)
         sp, _keep = spectral_of(bands, channel, scale)
-        image = np.empty((n_frames, rows, cols, 3), np.uint8) if want_image else None
-        big = np.empty((n_frames, out_rows, out_cols, 3), np.uint8) if out_rows else None
-        dominant = np.empty((n_frames, rows, cols), np.uint8) if want_dominant else None
+        image = np.empty((n_frames, w.rows, w.cols, 3), np.uint8) if want_image else None
+        big = np.empty((n_frames, w.out_rows, w.out_cols, 3), np.uint8) if w.out_rows else None
+        dominant = np.empty((n_frames, w.rows, w.cols), np.uint8) if want_dominant else None
         power = np.empty((max(sp.n_bands, 1), n_frames, self.pixel_count), np.float32) if want_power else None
         _check(call(n_blocks, C.byref(w), C.byref(sp), _out_ptr(image, _u8p), _out_ptr(big, _u8p), _out_ptr(dominant, _u8p),
                     _out_ptr(power, _f32p)), where)
@@ -1806,19 +1858,17 @@ class Engine:
         ring, blocks first, first + every, ... are filtered by every band of `bands` in one pre-pass and swept once per band; byte c
         of a pixel of .image shows band channel[c] (None: band c where there is one; spectral_compose), .big is that image upscaled (and mirrored when flip),
         .dominant the strongest band of every pixel, .power every band's powers (awpu_hip_spectral_blocks).  -> SpectralResult."""
-        buf, n_blocks = _wire_blocks(wire, stride)
-        return self._spectral(lambda *rest: self._lib.awpu_hip_spectral_blocks(self._h, buf.ctypes.data_as(C.c_void_p), stride, *rest),
-                              "awpu_hip_spectral_blocks", n_blocks, first, every, rows, cols, out_rows, out_cols, flip, bands,
-                              channel, scale, want_image, want_dominant, want_power)
+        return self._spectral(self._wire_run("awpu_hip_spectral_blocks", wire, stride), bands=bands, channel=channel, scale=scale,
+                              rows=rows, cols=cols, first=first, every=every, out_rows=out_rows, out_cols=out_cols, flip=flip,
+                              want_image=want_image, want_dominant=want_dominant, want_power=want_power)
 
     def spectral_samples(self, samples: np.ndarray, rows: int, cols: int, bands, channel=None, scale: int = SPECTRAL_SCALE_COMMON,
                          first: int = 0, every: int = 1, out_rows: int = 0, out_cols: int = 0, flip: bool = False, want_image: bool = True,
                          want_dominant: bool = True, want_power: bool = False) -> SpectralResult:
         """The same from unpacked samples [n_streams, N] (N a multiple of 256, oldest first) (awpu_hip_spectral_samples)."""
-        samples, n_blocks = self._sample_blocks(samples)
-        return self._spectral(lambda *rest: self._lib.awpu_hip_spectral_samples(self._h, _f32(samples), samples.shape[1], *rest),
-                              "awpu_hip_spectral_samples", n_blocks, first, every, rows, cols, out_rows, out_cols, flip, bands,
-                              channel, scale, want_image, want_dominant, want_power)
+        return self._spectral(self._sample_run("awpu_hip_spectral_samples", samples), bands=bands, channel=channel, scale=scale,
+                              rows=rows, cols=cols, first=first, every=every, out_rows=out_rows, out_cols=out_cols, flip=flip,
+                              want_image=want_image, want_dominant=want_dominant, want_power=want_power)
 
     def spectral_samples_device(self, d_samples_ptr: int, pitch: int, n_blocks: int, rows: int, cols: int, bands, channel=None,
                                 scale: int = SPECTRAL_SCALE_COMMON, first: int = 0, every: int = 1, d_image_ptr: int = 0, d_big_ptr: int = 0,
@@ -1827,12 +1877,10 @@ class Engine:
         """The same on device pointers (samples [n_streams, pitch]; image [n_frames, rows * cols, 3], big [n_frames, out_rows, out_cols,
         3], dominant [n_frames, rows * cols], power [n_bands, n_frames, pixels], each or 0) on `stream`; asynchronous.  -> next_first
         (awpu_hip_spectral_samples_device)."""
-        w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(0))
+        w = _watch_struct(rows=rows, cols=cols, first=first, every=every, out_rows=out_rows, out_cols=out_cols, flip=flip)
         sp, _keep = spectral_of(bands, channel, scale)
-        _check(self._lib.awpu_hip_spectral_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, C.byref(w), C.byref(sp),
-                                                          C.c_void_p(d_image_ptr), C.c_void_p(d_big_ptr), C.c_void_p(d_dominant_ptr),
-                                                          C.c_void_p(d_power_ptr), C.c_void_p(stream)), "awpu_hip_spectral_samples_device")
-        return watch_count(n_blocks, first, every)[1]
+        return self._device_run("awpu_hip_spectral_samples_device", d_samples_ptr, pitch, n_blocks, w, C.byref(sp),
+                                *_dev(d_image_ptr, d_big_ptr, d_dominant_ptr, d_power_ptr, stream))
 
     def find_peaks_device(self, d_power_ptr: int, n_frames: int, rows: int, cols: int, d_sources_ptr: int, d_count_ptr: int,
                           radius: int = 2, max_sources: int = 4, min_power: float = 0.0, min_ratio: float = 0.0, fov_deg: float = 180.0,
@@ -1840,13 +1888,13 @@ class Engine:
         """find_peaks on device pointers (power [n_frames, rows * cols] floats, sources [n_frames, max_sources] records of 40
         bytes, count [n_frames] int32) on `stream`; asynchronous (awpu_hip_find_peaks_device)."""
         f = Find(rows, cols, radius, max_sources, min_power, min_ratio, fov_deg)
-        _check(self._lib.awpu_hip_find_peaks_device(self._h, C.c_void_p(d_power_ptr), n_frames, C.byref(f), C.c_void_p(d_sources_ptr),
-                                                    C.c_void_p(d_count_ptr), C.c_void_p(stream)), "awpu_hip_find_peaks_device")
+        _check(self._lib.awpu_hip_find_peaks_device(self._h, C.c_void_p(d_power_ptr), n_frames, C.byref(f),
+                                                    *_dev(d_sources_ptr, d_count_ptr, stream)), "awpu_hip_find_peaks_device")
 
-    def _find(self, call, where, n_blocks, rows, cols, first, every, find, want_power) -> FindResult:
-        n_frames, next_first = watch_count(n_blocks, first, every)
-        w = Watch(first, every, rows, cols, 0, 0, 0, None)
-        f = _find_struct(rows, cols, find)
+    def _find(self, run, *, find, want_power, **shown) -> FindResult:
+        call, where, n_blocks = run
+        n_frames, next_first, w = self._shown_frames(n_blocks, **shown)
+        f = _find_struct(w.rows, w.cols, find)
         sources = np.empty((n_frames, max(f.max_sources, 0)), SOURCE_DTYPE)
         count = np.empty(n_frames, np.int32)
         power = np.empty((n_frames, self.pixel_count), np.float32) if want_power else None
@@ -1859,28 +1907,23 @@ class Engine:
         the ring, blocks first, first + every, ... are swept and their strongest peaks found on the device; find_peaks'
         keywords (radius, max_sources, min_power, min_ratio, fov_deg) say what a source is (awpu_hip_find_blocks).  -> FindResult;
         pass its .next_first as `first` of the call that continues the run."""
-        buf, n_blocks = _wire_blocks(wire, stride)
-        return self._find(lambda *rest: self._lib.awpu_hip_find_blocks(self._h, buf.ctypes.data_as(C.c_void_p), stride, *rest),
-                          "awpu_hip_find_blocks", n_blocks, rows, cols, first, every, find, want_power)
+        return self._find(self._wire_run("awpu_hip_find_blocks", wire, stride), rows=rows, cols=cols, first=first, every=every, find=find,
+                          want_power=want_power)
 
     def find_samples(self, samples: np.ndarray, rows: int, cols: int, first: int = 0, every: int = 1, want_power: bool = False,
                      **find) -> FindResult:
         """The same from unpacked samples [n_streams, N] (N a multiple of 256, oldest first) (awpu_hip_find_samples)."""
-        samples, n_blocks = self._sample_blocks(samples)
-        return self._find(lambda *rest: self._lib.awpu_hip_find_samples(self._h, _f32(samples), samples.shape[1], *rest),
-                          "awpu_hip_find_samples", n_blocks, rows, cols, first, every, find, want_power)
+        return self._find(self._sample_run("awpu_hip_find_samples", samples), rows=rows, cols=cols, first=first, every=every, find=find,
+                          want_power=want_power)
 
     def find_samples_device(self, d_samples_ptr: int, pitch: int, n_blocks: int, rows: int, cols: int, d_sources_ptr: int,
                             d_count_ptr: int, first: int = 0, every: int = 1, d_power_ptr: int = 0, stream: int = 0, **find) -> int:
         """The same on device pointers (samples [n_streams, pitch]; sources [n_frames, max_sources] records of 40 bytes, count
         [n_frames] int32, power [n_frames, pixels] or 0) on `stream`; asynchronous.  -> next_first
         (awpu_hip_find_samples_device)."""
-        w = Watch(first, every, rows, cols, 0, 0, 0, None)
-        f = _find_struct(rows, cols, find)
-        _check(self._lib.awpu_hip_find_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, C.byref(w), C.byref(f),
-                                                      C.c_void_p(d_sources_ptr), C.c_void_p(d_count_ptr), C.c_void_p(d_power_ptr),
-                                                      C.c_void_p(stream)), "awpu_hip_find_samples_device")
-        return watch_count(n_blocks, first, every)[1]
+        w = _watch_struct(rows=rows, cols=cols, first=first, every=every)
+        return self._device_run("awpu_hip_find_samples_device", d_samples_ptr, pitch, n_blocks, w, C.byref(_find_struct(rows, cols, find)),
+                                *_dev(d_sources_ptr, d_count_ptr, d_power_ptr, stream))
 
     def expose_rows_device(self, d_power_ptr: int, n_blocks: int, n_pixels: int, first: int, every: int, length: int, d_frames_ptr: int,
                            mode: int = EXPOSE_MEAN, d_carry_ptr: int = 0, stream: int = 0) -> int:
@@ -1888,23 +1931,21 @@ class Engine:
         `stream`; asynchronous.  -> next_first (awpu_hip_expose_rows_device)."""
         e = Expose(length, mode)
         _check(self._lib.awpu_hip_expose_rows_device(self._h, C.c_void_p(d_power_ptr), n_blocks, n_pixels, first, every, C.byref(e),
-                                                     C.c_void_p(d_carry_ptr), C.c_void_p(d_frames_ptr), C.c_void_p(stream)),
-               "awpu_hip_expose_rows_device")
+                                                     *_dev(d_carry_ptr, d_frames_ptr, stream)), "awpu_hip_expose_rows_device")
         return watch_count(n_blocks, first, every)[1]
 
-    def _expose(self, call, where, n_blocks, rows, cols, first, every, length, mode, carry, out_rows, out_cols, d_colormap_ptr, flip,
-                want_image, want_power, find) -> ExposeResult:
-        n_frames, next_first = watch_count(n_blocks, first, every)
-        w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(d_colormap_ptr))
+    def _expose(self, run, *, length, mode, carry, want_image, want_power, find, **shown) -> ExposeResult:
+        call, where, n_blocks = run
+        n_frames, next_first, w = self._shown_frames(n_blocks, **shown)
         e = Expose(length, mode)
         if carry is None:  # a recording's first call: silence before it
             carry = np.zeros(self.pixel_count, np.float32)
         elif carry.dtype != np.float32 or carry.shape != (self.pixel_count,) or not carry.flags.c_contiguous:
             raise ValueError("carry must be a contiguous float32 array [pixels]")
-        f = _find_struct(rows, cols, find)
-        shown, ptrs = self._shown_outputs(n_frames, w, want_image, want_power, f)
-        _check(call(n_blocks, C.byref(w), C.byref(e), None if f is None else C.byref(f), _f32(carry), *ptrs), where)
-        return ExposeResult(*shown, next_first, carry)
+        f = _find_struct(w.rows, w.cols, find)
+        arrays, ptrs = self._shown_outputs(n_frames, w, want_image, want_power, f)
+        _check(call(n_blocks, C.byref(w), C.byref(e), _ref(f), _f32(carry), *ptrs), where)
+        return ExposeResult(*arrays, next_first, carry)
 
     def expose_blocks(self, wire, rows: int, cols: int, length: int, first: Optional[int] = None, every: Optional[int] = None,
                       mode: int = EXPOSE_MEAN, carry: Optional[np.ndarray] = None, out_rows: int = 0, out_cols: int = 0,
@@ -1916,24 +1957,18 @@ class Engine:
         first block on.  `find` (a dict of find_peaks' keywords, {} for the defaults) also finds the sources of every exposed
         frame.  -> ExposeResult; pass its .next_first as `first` and its .carry as `carry` to the call that continues the run
         (carry is written in place)."""
-        buf, n_blocks = _wire_blocks(wire, stride)
-        every = length if every is None else every
-        first = length - 1 if first is None else first
-        return self._expose(lambda *rest: self._lib.awpu_hip_expose_blocks(self._h, buf.ctypes.data_as(C.c_void_p), stride, *rest),
-                            "awpu_hip_expose_blocks", n_blocks, rows, cols, first, every, length, mode, carry, out_rows,
-                            out_cols, d_colormap_ptr, flip, want_image, want_power, find)
+        return self._expose(self._wire_run("awpu_hip_expose_blocks", wire, stride), length=length, mode=mode, carry=carry, rows=rows, cols=cols,
+                            first=length - 1 if first is None else first, every=length if every is None else every, out_rows=out_rows,
+                            out_cols=out_cols, d_colormap_ptr=d_colormap_ptr, flip=flip, want_image=want_image, want_power=want_power, find=find)
 
     def expose_samples(self, samples: np.ndarray, rows: int, cols: int, length: int, first: Optional[int] = None,
                        every: Optional[int] = None, mode: int = EXPOSE_MEAN, carry: Optional[np.ndarray] = None, out_rows: int = 0,
                        out_cols: int = 0, d_colormap_ptr: int = 0, flip: bool = False, want_image: bool = True, want_power: bool = False,
                        find: Optional[dict] = None) -> ExposeResult:
         """The same from unpacked samples [n_streams, N] (N a multiple of 256, oldest first) (awpu_hip_expose_samples)."""
-        samples, n_blocks = self._sample_blocks(samples)
-        every = length if every is None else every
-        first = length - 1 if first is None else first
-        return self._expose(lambda *rest: self._lib.awpu_hip_expose_samples(self._h, _f32(samples), samples.shape[1], *rest),
-                            "awpu_hip_expose_samples", n_blocks, rows, cols, first, every, length, mode, carry, out_rows,
-                            out_cols, d_colormap_ptr, flip, want_image, want_power, find)
+        return self._expose(self._sample_run("awpu_hip_expose_samples", samples), length=length, mode=mode, carry=carry, rows=rows, cols=cols,
+                            first=length - 1 if first is None else first, every=length if every is None else every, out_rows=out_rows,
+                            out_cols=out_cols, d_colormap_ptr=d_colormap_ptr, flip=flip, want_image=want_image, want_power=want_power, find=find)
 
     def expose_samples_device(self, d_samples_ptr: int, pitch: int, n_blocks: int, rows: int, cols: int, length: int, first: int,
                               every: int, mode: int = EXPOSE_MEAN, d_carry_ptr: int = 0, d_image_ptr: int = 0, d_big_ptr: int = 0,
@@ -1942,14 +1977,11 @@ class Engine:
         """The same on device pointers (samples [n_streams, pitch]; carry [pixels]; image, big, power as watch_samples_device
         takes them, sources and count as find_samples_device does, each or 0) on `stream`; asynchronous.  -> next_first
         (awpu_hip_expose_samples_device)."""
-        w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(d_colormap_ptr))
-        e = Expose(length, mode)
-        f = _find_struct(rows, cols, find)
-        _check(self._lib.awpu_hip_expose_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, C.byref(w), C.byref(e),
-                                                        None if f is None else C.byref(f), C.c_void_p(d_carry_ptr), C.c_void_p(d_image_ptr),
-                                                        C.c_void_p(d_big_ptr), C.c_void_p(d_power_ptr), C.c_void_p(d_sources_ptr),
-                                                        C.c_void_p(d_count_ptr), C.c_void_p(stream)), "awpu_hip_expose_samples_device")
-        return watch_count(n_blocks, first, every)[1]
+        w = _watch_struct(rows=rows, cols=cols, first=first, every=every, out_rows=out_rows, out_cols=out_cols, d_colormap_ptr=d_colormap_ptr,
+                          flip=flip)
+        return self._device_run("awpu_hip_expose_samples_device", d_samples_ptr, pitch, n_blocks, w, C.byref(Expose(length, mode)),
+                                _ref(_find_struct(rows, cols, find)),
+                                *_dev(d_carry_ptr, d_image_ptr, d_big_ptr, d_power_ptr, d_sources_ptr, d_count_ptr, stream))
 
     def cohere(self, frames: np.ndarray, want=("power", "coherence", "weighted")):
         """The coherence sweep of host frames [batch, n_streams, hist] (or one frame): -> a dict of the maps in `want`, each
@@ -1973,16 +2005,16 @@ class Engine:
                       stream: int = 0) -> None:
         """The same on device pointers (frames [batch, n_streams, hist]; each map [batch, pixels] or 0) on `stream`; asynchronous
         (awpu_hip_cohere_device)."""
-        _check(self._lib.awpu_hip_cohere_device(self._h, C.c_void_p(d_frames_ptr), batch, C.c_void_p(d_power_ptr), C.c_void_p(d_coherence_ptr),
-                                                C.c_void_p(d_weighted_ptr), C.c_void_p(stream)), "awpu_hip_cohere_device")
+        _check(self._lib.awpu_hip_cohere_device(self._h, C.c_void_p(d_frames_ptr), batch,
+                                                *_dev(d_power_ptr, d_coherence_ptr, d_weighted_ptr, stream)), "awpu_hip_cohere_device")
 
     def cohere_device_sums(self, d_frames_ptr: int, batch: int, d_sums_ptr: int = 0, d_energy_ptr: int = 0, d_power_ptr: int = 0,
                            d_coherence_ptr: int = 0, d_weighted_ptr: int = 0, stream: int = 0) -> None:
         """cohere_device plus every pixel's out[0..255] and e[0..255] into d_sums / d_energy [batch, pixels, 256], each or 0
         (awpu_hip_cohere_device_sums): the rule's bits."""
-        _check(self._lib.awpu_hip_cohere_device_sums(self._h, C.c_void_p(d_frames_ptr), batch, C.c_void_p(d_power_ptr), C.c_void_p(d_coherence_ptr),
-                                                     C.c_void_p(d_weighted_ptr), C.c_void_p(d_sums_ptr), C.c_void_p(d_energy_ptr),
-                                                     C.c_void_p(stream)), "awpu_hip_cohere_device_sums")
+        _check(self._lib.awpu_hip_cohere_device_sums(self._h, C.c_void_p(d_frames_ptr), batch,
+                                                     *_dev(d_power_ptr, d_coherence_ptr, d_weighted_ptr, d_sums_ptr, d_energy_ptr, stream)),
+               "awpu_hip_cohere_device_sums")
 
     def peel(self, frames: np.ndarray, steps: int, gain: float = 1.0, stop_ratio: float = 0.0, want_frames: bool = False) -> "PeelResult":
         """Peel the sources of host frames [batch, n_streams, hist] (or one frame) (awpu_hip_peel): `steps` rounds of sweep, pick
@@ -2010,9 +2042,9 @@ class Engine:
         each map [batch, pixels]; the residual frames; each output or 0) on `stream`; asynchronous, with no wait inside the loop
         (awpu_hip_peel_device)."""
         pe = Peel(steps, gain, stop_ratio)
-        _check(self._lib.awpu_hip_peel_device(self._h, C.c_void_p(d_frames_ptr), batch, C.byref(pe), C.c_void_p(d_steps_ptr), C.c_void_p(d_clean_ptr),
-                                              C.c_void_p(d_residual_ptr), C.c_void_p(d_map_ptr), C.c_void_p(d_residual_frames_ptr),
-                                              C.c_void_p(stream)), "awpu_hip_peel_device")
+        _check(self._lib.awpu_hip_peel_device(self._h, C.c_void_p(d_frames_ptr), batch, C.byref(pe),
+                                              *_dev(d_steps_ptr, d_clean_ptr, d_residual_ptr, d_map_ptr, d_residual_frames_ptr, stream)),
+               "awpu_hip_peel_device")
 
     def peel_step_device(self, d_frames_ptr: int, batch: int, d_pixel_ptr: int, gain: float = 1.0, d_beams_ptr: int = 0, stream: int = 0) -> None:
         """One step, in place, on device pointers: frames [batch, n_streams, hist]; pixel [batch] int32, -1 = leave the frame alone;
@@ -2020,15 +2052,14 @@ class Engine:
         _check(self._lib.awpu_hip_peel_step_device(self._h, C.c_void_p(d_frames_ptr), batch, C.c_void_p(d_pixel_ptr), gain, C.c_void_p(d_beams_ptr),
                                                    C.c_void_p(stream)), "awpu_hip_peel_step_device")
 
-    def _peel_run(self, call, where, n_blocks, rows, cols, first, every, steps, gain, stop_ratio, show, out_rows, out_cols, d_colormap_ptr, flip,
-                  want_image, want_power, find) -> PeelRunResult:
-        n_frames, next_first = watch_count(n_blocks, first, every)
-        w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(d_colormap_ptr))
+    def _peel_run(self, run, *, steps, gain, stop_ratio, show, want_image, want_power, find, **shown) -> PeelRunResult:
+        call, where, n_blocks = run
+        n_frames, next_first, w = self._shown_frames(n_blocks, **shown)
         pe = Peel(steps, gain, stop_ratio)
-        f = _find_struct(rows, cols, find)
+        f = _find_struct(w.rows, w.cols, find)
         (image, big, power, sources, count), ptrs = self._shown_outputs(n_frames, w, want_image, want_power, f)
         rec = np.empty((n_frames, max(steps, 0)), PEEL_STEP_DTYPE)
-        _check(call(n_blocks, C.byref(w), C.byref(pe), show, None if f is None else C.byref(f), *ptrs[:3], _out_ptr(rec), *ptrs[3:]), where)
+        _check(call(n_blocks, C.byref(w), C.byref(pe), show, _ref(f), *ptrs[:3], _out_ptr(rec), *ptrs[3:]), where)
         return PeelRunResult(image, big, power, rec, sources, count, next_first)
 
     def peel_blocks(self, wire, rows: int, cols: int, steps: int, gain: float = 1.0, stop_ratio: float = 0.0, first: int = 0, every: int = 1,
@@ -2037,19 +2068,17 @@ class Engine:
         """Watch a run of consecutive blocks of wire datagrams (as watch_blocks takes them) with every shown snapshot peeled
         (awpu_hip_peel_blocks): the frame is its map row, or by `show` its clean or residual row.  `find` (a dict of find_peaks'
         keywords, {} for the defaults) also finds the sources of every frame.  -> PeelRunResult."""
-        buf, n_blocks = _wire_blocks(wire, stride)
-        return self._peel_run(lambda *rest: self._lib.awpu_hip_peel_blocks(self._h, buf.ctypes.data_as(C.c_void_p), stride, *rest),
-                              "awpu_hip_peel_blocks", n_blocks, rows, cols, first, every, steps, gain, stop_ratio, show, out_rows, out_cols,
-                              d_colormap_ptr, flip, want_image, want_power, find)
+        return self._peel_run(self._wire_run("awpu_hip_peel_blocks", wire, stride), steps=steps, gain=gain, stop_ratio=stop_ratio, show=show,
+                              rows=rows, cols=cols, first=first, every=every, out_rows=out_rows, out_cols=out_cols,
+                              d_colormap_ptr=d_colormap_ptr, flip=flip, want_image=want_image, want_power=want_power, find=find)
 
     def peel_samples(self, samples: np.ndarray, rows: int, cols: int, steps: int, gain: float = 1.0, stop_ratio: float = 0.0, first: int = 0,
                      every: int = 1, show: int = PEEL_MAP, out_rows: int = 0, out_cols: int = 0, d_colormap_ptr: int = 0, flip: bool = False,
                      want_image: bool = True, want_power: bool = False, find: Optional[dict] = None) -> PeelRunResult:
         """The same from unpacked samples [n_streams, N] (N a multiple of 256, oldest first) (awpu_hip_peel_samples)."""
-        samples, n_blocks = self._sample_blocks(samples)
-        return self._peel_run(lambda *rest: self._lib.awpu_hip_peel_samples(self._h, _f32(samples), samples.shape[1], *rest),
-                              "awpu_hip_peel_samples", n_blocks, rows, cols, first, every, steps, gain, stop_ratio, show, out_rows, out_cols,
-                              d_colormap_ptr, flip, want_image, want_power, find)
+        return self._peel_run(self._sample_run("awpu_hip_peel_samples", samples), steps=steps, gain=gain, stop_ratio=stop_ratio, show=show,
+                              rows=rows, cols=cols, first=first, every=every, out_rows=out_rows, out_cols=out_cols,
+                              d_colormap_ptr=d_colormap_ptr, flip=flip, want_image=want_image, want_power=want_power, find=find)
 
     def peel_samples_device(self, d_samples_ptr: int, pitch: int, n_blocks: int, rows: int, cols: int, steps: int, gain: float = 1.0,
                             stop_ratio: float = 0.0, first: int = 0, every: int = 1, show: int = PEEL_MAP, d_image_ptr: int = 0, d_big_ptr: int = 0,
@@ -2058,24 +2087,20 @@ class Engine:
         """The same on device pointers (samples [n_streams, pitch]; image, big, power as watch_samples_device takes them, steps
         [n_frames, steps] records of 12 bytes, sources and count as find_samples_device does, each or 0) on `stream`; asynchronous.
         -> next_first (awpu_hip_peel_samples_device)."""
-        w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(d_colormap_ptr))
-        pe = Peel(steps, gain, stop_ratio)
-        f = _find_struct(rows, cols, find)
-        _check(self._lib.awpu_hip_peel_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, C.byref(w), C.byref(pe), show,
-                                                      None if f is None else C.byref(f), C.c_void_p(d_image_ptr), C.c_void_p(d_big_ptr),
-                                                      C.c_void_p(d_power_ptr), C.c_void_p(d_steps_ptr), C.c_void_p(d_sources_ptr),
-                                                      C.c_void_p(d_count_ptr), C.c_void_p(stream)), "awpu_hip_peel_samples_device")
-        return watch_count(n_blocks, first, every)[1]
+        w = _watch_struct(rows=rows, cols=cols, first=first, every=every, out_rows=out_rows, out_cols=out_cols, d_colormap_ptr=d_colormap_ptr,
+                          flip=flip)
+        return self._device_run("awpu_hip_peel_samples_device", d_samples_ptr, pitch, n_blocks, w, C.byref(Peel(steps, gain, stop_ratio)), show,
+                                _ref(_find_struct(rows, cols, find)),
+                                *_dev(d_image_ptr, d_big_ptr, d_power_ptr, d_steps_ptr, d_sources_ptr, d_count_ptr, stream))
 
-    def _cohere_run(self, call, where, n_blocks, rows, cols, first, every, show, out_rows, out_cols, d_colormap_ptr, flip, want_image,
-                    want_power, find) -> CohereResult:
-        n_frames, next_first = watch_count(n_blocks, first, every)
-        w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(d_colormap_ptr))
+    def _cohere_run(self, run, *, show, want_image, want_power, find, **shown) -> CohereResult:
+        call, where, n_blocks = run
+        n_frames, next_first, w = self._shown_frames(n_blocks, **shown)
         co = Cohere(show)
-        f = _find_struct(rows, cols, find)
-        shown, ptrs = self._shown_outputs(n_frames, w, want_image, want_power, f)
-        _check(call(n_blocks, C.byref(w), C.byref(co), None if f is None else C.byref(f), *ptrs), where)
-        return CohereResult(*shown, next_first)
+        f = _find_struct(w.rows, w.cols, find)
+        arrays, ptrs = self._shown_outputs(n_frames, w, want_image, want_power, f)
+        _check(call(n_blocks, C.byref(w), C.byref(co), _ref(f), *ptrs), where)
+        return CohereResult(*arrays, next_first)
 
     def cohere_blocks(self, wire, rows: int, cols: int, first: int = 0, every: int = 1, show: int = COHERE_WEIGHTED, out_rows: int = 0,
                       out_cols: int = 0, d_colormap_ptr: int = 0, flip: bool = False, stride: int = DATAGRAM_BYTES, want_image: bool = True,
@@ -2084,19 +2109,17 @@ class Engine:
         shown frame is its coherence-weighted row, or with show=COHERE_FACTOR its coherence row (awpu_hip_cohere_blocks).  `find`
         (a dict of find_peaks' keywords, {} for the defaults) also finds the sources of every frame.  -> CohereResult; pass its
         .next_first as `first` of the call that continues the run."""
-        buf, n_blocks = _wire_blocks(wire, stride)
-        return self._cohere_run(lambda *rest: self._lib.awpu_hip_cohere_blocks(self._h, buf.ctypes.data_as(C.c_void_p), stride, *rest),
-                                "awpu_hip_cohere_blocks", n_blocks, rows, cols, first, every, show, out_rows, out_cols,
-                                d_colormap_ptr, flip, want_image, want_power, find)
+        return self._cohere_run(self._wire_run("awpu_hip_cohere_blocks", wire, stride), show=show, rows=rows, cols=cols, first=first, every=every,
+                                out_rows=out_rows, out_cols=out_cols, d_colormap_ptr=d_colormap_ptr, flip=flip, want_image=want_image,
+                                want_power=want_power, find=find)
 
     def cohere_samples(self, samples: np.ndarray, rows: int, cols: int, first: int = 0, every: int = 1, show: int = COHERE_WEIGHTED,
                        out_rows: int = 0, out_cols: int = 0, d_colormap_ptr: int = 0, flip: bool = False, want_image: bool = True,
                        want_power: bool = False, find: Optional[dict] = None) -> CohereResult:
         """The same from unpacked samples [n_streams, N] (N a multiple of 256, oldest first) (awpu_hip_cohere_samples)."""
-        samples, n_blocks = self._sample_blocks(samples)
-        return self._cohere_run(lambda *rest: self._lib.awpu_hip_cohere_samples(self._h, _f32(samples), samples.shape[1], *rest),
-                                "awpu_hip_cohere_samples", n_blocks, rows, cols, first, every, show, out_rows, out_cols,
-                                d_colormap_ptr, flip, want_image, want_power, find)
+        return self._cohere_run(self._sample_run("awpu_hip_cohere_samples", samples), show=show, rows=rows, cols=cols, first=first, every=every,
+                                out_rows=out_rows, out_cols=out_cols, d_colormap_ptr=d_colormap_ptr, flip=flip, want_image=want_image,
+                                want_power=want_power, find=find)
 
     def cohere_samples_device(self, d_samples_ptr: int, pitch: int, n_blocks: int, rows: int, cols: int, first: int = 0, every: int = 1,
                               show: int = COHERE_WEIGHTED, d_image_ptr: int = 0, d_big_ptr: int = 0, d_power_ptr: int = 0,
@@ -2105,14 +2128,10 @@ class Engine:
         """The same on device pointers (samples [n_streams, pitch]; image, big, power as watch_samples_device takes them, sources
         and count as find_samples_device does, each or 0) on `stream`; asynchronous.  -> next_first
         (awpu_hip_cohere_samples_device)."""
-        w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(d_colormap_ptr))
-        co = Cohere(show)
-        f = _find_struct(rows, cols, find)
-        _check(self._lib.awpu_hip_cohere_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, C.byref(w), C.byref(co),
-                                                        None if f is None else C.byref(f), C.c_void_p(d_image_ptr), C.c_void_p(d_big_ptr),
-                                                        C.c_void_p(d_power_ptr), C.c_void_p(d_sources_ptr), C.c_void_p(d_count_ptr),
-                                                        C.c_void_p(stream)), "awpu_hip_cohere_samples_device")
-        return watch_count(n_blocks, first, every)[1]
+        w = _watch_struct(rows=rows, cols=cols, first=first, every=every, out_rows=out_rows, out_cols=out_cols, d_colormap_ptr=d_colormap_ptr,
+                          flip=flip)
+        return self._device_run("awpu_hip_cohere_samples_device", d_samples_ptr, pitch, n_blocks, w, C.byref(Cohere(show)),
+                                _ref(_find_struct(rows, cols, find)), *_dev(d_image_ptr, d_big_ptr, d_power_ptr, d_sources_ptr, d_count_ptr, stream))
 
     def tones(self, frames: np.ndarray, groups, window: int = TONES_RECT, want=("tone", "pitch")):
         """The tone sweep of host frames [batch, n_streams, hist] (or one frame), groups as tones_of takes them: -> a dict of the
@@ -2141,27 +2160,25 @@ class Engine:
         """The same on device pointers (frames [batch, n_streams, hist]; tone [batch, n_groups, pixels], pitch [batch, pixels] int32,
         each or 0) on `stream`; asynchronous (awpu_hip_tones_device)."""
         t = tones_of(groups, window)
-        _check(self._lib.awpu_hip_tones_device(self._h, C.c_void_p(d_frames_ptr), batch, C.byref(t), C.c_void_p(d_tone_ptr), C.c_void_p(d_pitch_ptr),
-                                               C.c_void_p(stream)), "awpu_hip_tones_device")
+        _check(self._lib.awpu_hip_tones_device(self._h, C.c_void_p(d_frames_ptr), batch, C.byref(t), *_dev(d_tone_ptr, d_pitch_ptr, stream)),
+               "awpu_hip_tones_device")
 
     def tones_device_bins(self, d_frames_ptr: int, batch: int, groups, window: int = TONES_RECT, d_bins_ptr: int = 0, d_spectrum_ptr: int = 0,
                           d_tone_ptr: int = 0, d_pitch_ptr: int = 0, stream: int = 0) -> None:
         """tones_device plus every pixel's bins [batch, pixels, 129] and spectrum [batch, pixels, 129, 2] into d_bins / d_spectrum,
         each or 0 (awpu_hip_tones_device_bins): the rule's bits."""
         t = tones_of(groups, window)
-        _check(self._lib.awpu_hip_tones_device_bins(self._h, C.c_void_p(d_frames_ptr), batch, C.byref(t), C.c_void_p(d_tone_ptr),
-                                                    C.c_void_p(d_pitch_ptr), C.c_void_p(d_bins_ptr), C.c_void_p(d_spectrum_ptr),
-                                                    C.c_void_p(stream)), "awpu_hip_tones_device_bins")
+        _check(self._lib.awpu_hip_tones_device_bins(self._h, C.c_void_p(d_frames_ptr), batch, C.byref(t),
+                                                    *_dev(d_tone_ptr, d_pitch_ptr, d_bins_ptr, d_spectrum_ptr, stream)), "awpu_hip_tones_device_bins")
 
-    def _tones_run(self, call, where, n_blocks, rows, cols, first, every, groups, window, show, out_rows, out_cols, d_colormap_ptr, flip,
-                   want_image, want_power, find) -> TonesResult:
-        n_frames, next_first = watch_count(n_blocks, first, every)
-        w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(d_colormap_ptr))
+    def _tones_run(self, run, *, groups, window, show, want_image, want_power, find, **shown) -> TonesResult:
+        call, where, n_blocks = run
+        n_frames, next_first, w = self._shown_frames(n_blocks, **shown)
         t = tones_of(groups, window)
-        f = _find_struct(rows, cols, find)
-        shown, ptrs = self._shown_outputs(n_frames, w, want_image, want_power, f)
-        _check(call(n_blocks, C.byref(w), C.byref(t), show, None if f is None else C.byref(f), *ptrs), where)
-        return TonesResult(*shown, next_first)
+        f = _find_struct(w.rows, w.cols, find)
+        arrays, ptrs = self._shown_outputs(n_frames, w, want_image, want_power, f)
+        _check(call(n_blocks, C.byref(w), C.byref(t), show, _ref(f), *ptrs), where)
+        return TonesResult(*arrays, next_first)
 
     def tones_blocks(self, wire, rows: int, cols: int, groups, window: int = TONES_RECT, show: int = 0, first: int = 0, every: int = 1,
                      out_rows: int = 0, out_cols: int = 0, d_colormap_ptr: int = 0, flip: bool = False, stride: int = DATAGRAM_BYTES,
@@ -2170,19 +2187,17 @@ class Engine:
         frame is the plane of group `show`, or with show=TONES_SHOW_PITCH the pitch row (awpu_hip_tones_blocks).  `find` (a dict
         of find_peaks' keywords, {} for the defaults) also finds the sources of every frame.  -> TonesResult; pass its .next_first
         as `first` of the call that continues the run."""
-        buf, n_blocks = _wire_blocks(wire, stride)
-        return self._tones_run(lambda *rest: self._lib.awpu_hip_tones_blocks(self._h, buf.ctypes.data_as(C.c_void_p), stride, *rest),
-                               "awpu_hip_tones_blocks", n_blocks, rows, cols, first, every, groups, window, show, out_rows, out_cols,
-                               d_colormap_ptr, flip, want_image, want_power, find)
+        return self._tones_run(self._wire_run("awpu_hip_tones_blocks", wire, stride), groups=groups, window=window, show=show, rows=rows, cols=cols,
+                               first=first, every=every, out_rows=out_rows, out_cols=out_cols, d_colormap_ptr=d_colormap_ptr, flip=flip,
+                               want_image=want_image, want_power=want_power, find=find)
 
     def tones_samples(self, samples: np.ndarray, rows: int, cols: int, groups, window: int = TONES_RECT, show: int = 0, first: int = 0,
                       every: int = 1, out_rows: int = 0, out_cols: int = 0, d_colormap_ptr: int = 0, flip: bool = False,
                       want_image: bool = True, want_power: bool = False, find: Optional[dict] = None) -> TonesResult:
         """The same from unpacked samples [n_streams, N] (N a multiple of 256, oldest first) (awpu_hip_tones_samples)."""
-        samples, n_blocks = self._sample_blocks(samples)
-        return self._tones_run(lambda *rest: self._lib.awpu_hip_tones_samples(self._h, _f32(samples), samples.shape[1], *rest),
-                               "awpu_hip_tones_samples", n_blocks, rows, cols, first, every, groups, window, show, out_rows, out_cols,
-                               d_colormap_ptr, flip, want_image, want_power, find)
+        return self._tones_run(self._sample_run("awpu_hip_tones_samples", samples), groups=groups, window=window, show=show, rows=rows, cols=cols,
+                               first=first, every=every, out_rows=out_rows, out_cols=out_cols, d_colormap_ptr=d_colormap_ptr, flip=flip,
+                               want_image=want_image, want_power=want_power, find=find)
 
     def tones_samples_device(self, d_samples_ptr: int, pitch: int, n_blocks: int, rows: int, cols: int, groups, window: int = TONES_RECT,
                              show: int = 0, first: int = 0, every: int = 1, d_image_ptr: int = 0, d_big_ptr: int = 0, d_power_ptr: int = 0,
@@ -2191,33 +2206,34 @@ class Engine:
         """The same on device pointers (samples [n_streams, pitch]; image, big, power as watch_samples_device takes them, sources
         and count as find_samples_device does, each or 0) on `stream`; asynchronous.  -> next_first
         (awpu_hip_tones_samples_device)."""
-        w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(d_colormap_ptr))
-        t = tones_of(groups, window)
-        f = _find_struct(rows, cols, find)
-        _check(self._lib.awpu_hip_tones_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, C.byref(w), C.byref(t), show,
-                                                       None if f is None else C.byref(f), C.c_void_p(d_image_ptr), C.c_void_p(d_big_ptr),
-                                                       C.c_void_p(d_power_ptr), C.c_void_p(d_sources_ptr), C.c_void_p(d_count_ptr),
-                                                       C.c_void_p(stream)), "awpu_hip_tones_samples_device")
-        return watch_count(n_blocks, first, every)[1]
+        w = _watch_struct(rows=rows, cols=cols, first=first, every=every, out_rows=out_rows, out_cols=out_cols, d_colormap_ptr=d_colormap_ptr,
+                          flip=flip)
+        return self._device_run("awpu_hip_tones_samples_device", d_samples_ptr, pitch, n_blocks, w, C.byref(tones_of(groups, window)), show,
+                                _ref(_find_struct(rows, cols, find)), *_dev(d_image_ptr, d_big_ptr, d_power_ptr, d_sources_ptr, d_count_ptr, stream))
 
-    def _csm_watch(self, call, where, n_blocks, rows, cols, bins, window, kind, loading, length, show, first, every, carry, carried, out_rows,
-                   out_cols, d_colormap_ptr, flip, want_image, want_power, want_planes, want_solved, find) -> CsmWatchResult:
-        n_frames, next_first = watch_count(n_blocks, first, every)
-        w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(d_colormap_ptr))
-        c = csm_of(bins, window, kind, loading)
-        f = _find_struct(rows, cols, find)
-        usable = getattr(self, "_usable", self.cfg.n_streams)
-        shape = (max(int(length) - 1, 0), max(c.n_bins, 0), usable, 2)
+    def _csm_window(self, c: Csm, n_frames: int, *, length, carry, carried, want_planes):
+        """What the two cross-spectral runs carry from call to call and may hand out: (carry [length - 1, n_bins, usable, 2] -- the
+        caller's, copied, or zeros --, how many of its blocks are held as the C int the call updates, planes [n_frames, n_bins,
+        pixels] or None)."""
+        shape = (max(int(length) - 1, 0), max(c.n_bins, 0), self.usable, 2)
         carry = np.zeros(shape, np.float32) if carry is None else np.ascontiguousarray(carry, np.float32).copy()
         if carry.shape != shape:
             raise ValueError(f"carry must be {shape}")
-        held = C.c_int32(int(carried))
-        shown, ptrs = self._shown_outputs(n_frames, w, want_image, want_power, f)
         planes = np.empty((n_frames, max(c.n_bins, 0), self.pixel_count), np.float32) if want_planes else None
+        return carry, C.c_int32(int(carried)), planes
+
+    def _csm_watch(self, run, *, bins, window, kind, loading, length, show, carry, carried, want_image, want_power, want_planes, want_solved,
+                   find, **shown) -> CsmWatchResult:
+        call, where, n_blocks = run
+        n_frames, next_first, w = self._shown_frames(n_blocks, **shown)
+        c = csm_of(bins, window, kind, loading)
+        f = _find_struct(w.rows, w.cols, find)
+        carry, held, planes = self._csm_window(c, n_frames, length=length, carry=carry, carried=carried, want_planes=want_planes)
+        arrays, ptrs = self._shown_outputs(n_frames, w, want_image, want_power, f)
         solved = np.empty((n_frames, max(c.n_bins, 0)), np.int32) if want_solved else None
-        _check(call(n_blocks, C.byref(w), C.byref(c), int(length), int(show), None if f is None else C.byref(f), _out_ptr(carry, _f32p),
+        _check(call(n_blocks, C.byref(w), C.byref(c), int(length), int(show), _ref(f), _out_ptr(carry, _f32p),
                     C.cast(C.byref(held), _i32p), *ptrs, _out_ptr(planes, _f32p), _out_ptr(solved, _i32p)), where)
-        return CsmWatchResult(*shown, planes, solved, next_first, carry, held.value)
+        return CsmWatchResult(*arrays, planes, solved, next_first, carry, held.value)
 
     def csm_watch_blocks(self, wire, rows: int, cols: int, bins, window: int = TONES_RECT, kind: int = CSM_CONVENTIONAL, loading: float = 1e-3,
                          length: int = 64, show: int = CSM_SHOW_SUM, first: int = 0, every: int = 1, carry=None, carried: int = 0,
@@ -2228,10 +2244,10 @@ class Engine:
         (awpu_hip_csm_watch_blocks): every shown frame is the map of the `length` blocks that end with it -- the plane of bin index
         `show`, or with CSM_SHOW_SUM the planes added up --, conventional, diagonal-removed or Capon's.  `find` also finds the
         sources of every frame.  -> CsmWatchResult; pass its .next_first, .carry and .carried to the call that continues the run."""
-        buf, n_blocks = _wire_blocks(wire, stride)
-        return self._csm_watch(lambda *rest: self._lib.awpu_hip_csm_watch_blocks(self._h, buf.ctypes.data_as(C.c_void_p), stride, *rest),
-                               "awpu_hip_csm_watch_blocks", n_blocks, rows, cols, bins, window, kind, loading, length, show, first, every, carry,
-                               carried, out_rows, out_cols, d_colormap_ptr, flip, want_image, want_power, want_planes, want_solved, find)
+        return self._csm_watch(self._wire_run("awpu_hip_csm_watch_blocks", wire, stride), bins=bins, window=window, kind=kind, loading=loading,
+                               length=length, show=show, carry=carry, carried=carried, rows=rows, cols=cols, first=first, every=every,
+                               out_rows=out_rows, out_cols=out_cols, d_colormap_ptr=d_colormap_ptr, flip=flip, want_image=want_image,
+                               want_power=want_power, want_planes=want_planes, want_solved=want_solved, find=find)
 
     def csm_watch_samples(self, samples: np.ndarray, rows: int, cols: int, bins, window: int = TONES_RECT, kind: int = CSM_CONVENTIONAL,
                           loading: float = 1e-3, length: int = 64, show: int = CSM_SHOW_SUM, first: int = 0, every: int = 1, carry=None,
@@ -2239,10 +2255,10 @@ class Engine:
                           want_image: bool = True, want_power: bool = False, want_planes: bool = False, want_solved: bool = False,
                           find: Optional[dict] = None) -> CsmWatchResult:
         """The same from unpacked samples [n_streams, N] (N a multiple of 256, oldest first) (awpu_hip_csm_watch_samples)."""
-        samples, n_blocks = self._sample_blocks(samples)
-        return self._csm_watch(lambda *rest: self._lib.awpu_hip_csm_watch_samples(self._h, _f32(samples), samples.shape[1], *rest),
-                               "awpu_hip_csm_watch_samples", n_blocks, rows, cols, bins, window, kind, loading, length, show, first, every, carry,
-                               carried, out_rows, out_cols, d_colormap_ptr, flip, want_image, want_power, want_planes, want_solved, find)
+        return self._csm_watch(self._sample_run("awpu_hip_csm_watch_samples", samples), bins=bins, window=window, kind=kind, loading=loading,
+                               length=length, show=show, carry=carry, carried=carried, rows=rows, cols=cols, first=first, every=every,
+                               out_rows=out_rows, out_cols=out_cols, d_colormap_ptr=d_colormap_ptr, flip=flip, want_image=want_image,
+                               want_power=want_power, want_planes=want_planes, want_solved=want_solved, find=find)
 
     def csm_watch_samples_device(self, d_samples_ptr: int, pitch: int, n_blocks: int, rows: int, cols: int, bins, window: int = TONES_RECT,
                                  kind: int = CSM_CONVENTIONAL, loading: float = 1e-3, length: int = 64, show: int = CSM_SHOW_SUM,
@@ -2254,36 +2270,26 @@ class Engine:
         and count as tones_samples_device takes them; planes [n_frames, n_bins, pixels] and solved [n_frames, n_bins], each or 0) on
         `stream`; asynchronous.  -> (next_first, carried) for the call that continues the run
         (awpu_hip_csm_watch_samples_device)."""
-        w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(d_colormap_ptr))
-        c = csm_of(bins, window, kind, loading)
-        f = _find_struct(rows, cols, find)
-        held = C.c_int32(int(carried))
-        _check(self._lib.awpu_hip_csm_watch_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, C.byref(w), C.byref(c), int(length),
-                                                           int(show), None if f is None else C.byref(f), C.c_void_p(d_carry_ptr),
-                                                           C.cast(C.byref(held), _i32p), C.c_void_p(d_image_ptr), C.c_void_p(d_big_ptr),
-                                                           C.c_void_p(d_power_ptr), C.c_void_p(d_sources_ptr), C.c_void_p(d_count_ptr),
-                                                           C.c_void_p(d_planes_ptr), C.c_void_p(d_solved_ptr), C.c_void_p(stream)),
-               "awpu_hip_csm_watch_samples_device")
-        return watch_count(n_blocks, first, every)[1], held.value
+        w = _watch_struct(rows=rows, cols=cols, first=first, every=every, out_rows=out_rows, out_cols=out_cols, d_colormap_ptr=d_colormap_ptr,
+                          flip=flip)
+        c, held = csm_of(bins, window, kind, loading), C.c_int32(int(carried))
+        next_first = self._device_run("awpu_hip_csm_watch_samples_device", d_samples_ptr, pitch, n_blocks, w, C.byref(c), int(length), int(show),
+                                      _ref(_find_struct(rows, cols, find)), C.c_void_p(d_carry_ptr), C.cast(C.byref(held), _i32p),
+                                      *_dev(d_image_ptr, d_big_ptr, d_power_ptr, d_sources_ptr, d_count_ptr, d_planes_ptr, d_solved_ptr, stream))
+        return next_first, held.value
 
-    def _csm_clean_run(self, call, where, n_blocks, rows, cols, bins, steps, gain, stop_ratio, what, window, length, show, first, every, carry,
-                       carried, out_rows, out_cols, d_colormap_ptr, flip, want_image, want_power, want_planes, find) -> CsmCleanRunResult:
-        n_frames, next_first = watch_count(n_blocks, first, every)
-        w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(d_colormap_ptr))
+    def _csm_clean_run(self, run, *, bins, steps, gain, stop_ratio, what, window, length, show, carry, carried, want_image, want_power,
+                       want_planes, find, **shown) -> CsmCleanRunResult:
+        call, where, n_blocks = run
+        n_frames, next_first, w = self._shown_frames(n_blocks, **shown)
         c, cl = csm_of(bins, window), CsmClean(int(steps), float(gain), float(stop_ratio))
-        f = _find_struct(rows, cols, find)
-        usable = getattr(self, "_usable", self.cfg.n_streams)
-        shape = (max(int(length) - 1, 0), max(c.n_bins, 0), usable, 2)
-        carry = np.zeros(shape, np.float32) if carry is None else np.ascontiguousarray(carry, np.float32).copy()
-        if carry.shape != shape:
-            raise ValueError(f"carry must be {shape}")
-        held = C.c_int32(int(carried))
-        shown, ptrs = self._shown_outputs(n_frames, w, want_image, want_power, f)
-        planes = np.empty((n_frames, max(c.n_bins, 0), self.pixel_count), np.float32) if want_planes else None
+        f = _find_struct(w.rows, w.cols, find)
+        carry, held, planes = self._csm_window(c, n_frames, length=length, carry=carry, carried=carried, want_planes=want_planes)
+        arrays, ptrs = self._shown_outputs(n_frames, w, want_image, want_power, f)
         rec = np.empty((n_frames, max(c.n_bins, 0), max(int(steps), 0)), CSM_CLEAN_STEP_DTYPE)
-        _check(call(n_blocks, C.byref(w), C.byref(c), int(length), int(show), None if f is None else C.byref(f), _out_ptr(carry, _f32p),
+        _check(call(n_blocks, C.byref(w), C.byref(c), int(length), int(show), _ref(f), _out_ptr(carry, _f32p),
                     C.cast(C.byref(held), _i32p), C.byref(cl), int(what), *ptrs, _out_ptr(planes, _f32p), _out_ptr(rec)), where)
-        return CsmCleanRunResult(*shown, planes, rec, next_first, carry, held.value)
+        return CsmCleanRunResult(*arrays, planes, rec, next_first, carry, held.value)
 
     def csm_clean_blocks(self, wire, rows: int, cols: int, bins, steps: int, gain: float = 1.0, stop_ratio: float = 0.0,
                          what: int = CSM_CLEAN_MAP, window: int = TONES_RECT, length: int = 64, show: int = CSM_SHOW_SUM, first: int = 0,
@@ -2294,10 +2300,10 @@ class Engine:
         csm_clean of the matrix of the `length` blocks that end with it -- its map (CSM_CLEAN_MAP), clean (CSM_CLEAN_CLEAN) or
         residual (CSM_CLEAN_RESIDUAL) rows, of which the plane of bin index `show` or with CSM_SHOW_SUM their sum is shown.
         -> CsmCleanRunResult; pass its .next_first, .carry and .carried to the call that continues the run."""
-        buf, n_blocks = _wire_blocks(wire, stride)
-        return self._csm_clean_run(lambda *rest: self._lib.awpu_hip_csm_clean_blocks(self._h, buf.ctypes.data_as(C.c_void_p), stride, *rest),
-                                   "awpu_hip_csm_clean_blocks", n_blocks, rows, cols, bins, steps, gain, stop_ratio, what, window, length, show,
-                                   first, every, carry, carried, out_rows, out_cols, d_colormap_ptr, flip, want_image, want_power, want_planes, find)
+        return self._csm_clean_run(self._wire_run("awpu_hip_csm_clean_blocks", wire, stride), bins=bins, steps=steps, gain=gain, stop_ratio=stop_ratio,
+                                   what=what, window=window, length=length, show=show, carry=carry, carried=carried, rows=rows, cols=cols,
+                                   first=first, every=every, out_rows=out_rows, out_cols=out_cols, d_colormap_ptr=d_colormap_ptr, flip=flip,
+                                   want_image=want_image, want_power=want_power, want_planes=want_planes, find=find)
 
     def csm_clean_samples(self, samples: np.ndarray, rows: int, cols: int, bins, steps: int, gain: float = 1.0, stop_ratio: float = 0.0,
                           what: int = CSM_CLEAN_MAP, window: int = TONES_RECT, length: int = 64, show: int = CSM_SHOW_SUM, first: int = 0,
@@ -2305,10 +2311,10 @@ class Engine:
                           flip: bool = False, want_image: bool = True, want_power: bool = False, want_planes: bool = False,
                           find: Optional[dict] = None) -> CsmCleanRunResult:
         """The same from unpacked samples [n_streams, N] (N a multiple of 256, oldest first) (awpu_hip_csm_clean_samples)."""
-        samples, n_blocks = self._sample_blocks(samples)
-        return self._csm_clean_run(lambda *rest: self._lib.awpu_hip_csm_clean_samples(self._h, _f32(samples), samples.shape[1], *rest),
-                                   "awpu_hip_csm_clean_samples", n_blocks, rows, cols, bins, steps, gain, stop_ratio, what, window, length, show,
-                                   first, every, carry, carried, out_rows, out_cols, d_colormap_ptr, flip, want_image, want_power, want_planes, find)
+        return self._csm_clean_run(self._sample_run("awpu_hip_csm_clean_samples", samples), bins=bins, steps=steps, gain=gain, stop_ratio=stop_ratio,
+                                   what=what, window=window, length=length, show=show, carry=carry, carried=carried, rows=rows, cols=cols,
+                                   first=first, every=every, out_rows=out_rows, out_cols=out_cols, d_colormap_ptr=d_colormap_ptr, flip=flip,
+                                   want_image=want_image, want_power=want_power, want_planes=want_planes, find=find)
 
     def csm_clean_samples_device(self, d_samples_ptr: int, pitch: int, n_blocks: int, rows: int, cols: int, bins, steps: int, gain: float = 1.0,
                                  stop_ratio: float = 0.0, what: int = CSM_CLEAN_MAP, window: int = TONES_RECT, length: int = 64,
@@ -2318,17 +2324,14 @@ class Engine:
                                  flip: bool = False, stream: int = 0, find: Optional[dict] = None):
         """The same on device pointers (as csm_watch_samples_device takes them; steps [n_frames, n_bins, steps] records or 0) on
         `stream`; asynchronous.  -> (next_first, carried) for the call that continues the run (awpu_hip_csm_clean_samples_device)."""
-        w = Watch(first, every, rows, cols, out_rows, out_cols, int(flip), C.c_void_p(d_colormap_ptr))
-        c, cl = csm_of(bins, window), CsmClean(int(steps), float(gain), float(stop_ratio))
-        f = _find_struct(rows, cols, find)
-        held = C.c_int32(int(carried))
-        _check(self._lib.awpu_hip_csm_clean_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, C.byref(w), C.byref(c), int(length),
-                                                           int(show), None if f is None else C.byref(f), C.c_void_p(d_carry_ptr),
-                                                           C.cast(C.byref(held), _i32p), C.byref(cl), int(what), C.c_void_p(d_image_ptr),
-                                                           C.c_void_p(d_big_ptr), C.c_void_p(d_power_ptr), C.c_void_p(d_sources_ptr),
-                                                           C.c_void_p(d_count_ptr), C.c_void_p(d_planes_ptr), C.c_void_p(d_steps_ptr),
-                                                           C.c_void_p(stream)), "awpu_hip_csm_clean_samples_device")
-        return watch_count(n_blocks, first, every)[1], held.value
+        w = _watch_struct(rows=rows, cols=cols, first=first, every=every, out_rows=out_rows, out_cols=out_cols, d_colormap_ptr=d_colormap_ptr,
+                          flip=flip)
+        c, cl, held = csm_of(bins, window), CsmClean(int(steps), float(gain), float(stop_ratio)), C.c_int32(int(carried))
+        next_first = self._device_run("awpu_hip_csm_clean_samples_device", d_samples_ptr, pitch, n_blocks, w, C.byref(c), int(length), int(show),
+                                      _ref(_find_struct(rows, cols, find)), C.c_void_p(d_carry_ptr), C.cast(C.byref(held), _i32p), C.byref(cl),
+                                      int(what),
+                                      *_dev(d_image_ptr, d_big_ptr, d_power_ptr, d_sources_ptr, d_count_ptr, d_planes_ptr, d_steps_ptr, stream))
+        return next_first, held.value
 
     def csm_samples(self, samples: np.ndarray, bins, window: int = TONES_RECT, matrix: Optional[np.ndarray] = None, block_count: int = 0,
                     n_blocks: Optional[int] = None, want_spectra: bool = False):
@@ -2341,7 +2344,7 @@ class Engine:
         if samples.ndim != 2 or samples.shape[0] != self.cfg.n_streams:
             raise ValueError(f"samples must be [{self.cfg.n_streams}, pitch]")
         n_blocks = samples.shape[1] // 256 if n_blocks is None else int(n_blocks)
-        usable = getattr(self, "_usable", self.cfg.n_streams)
+        usable = self.usable
         shape = (max(c.n_bins, 0), usable, usable, 2)
         if matrix is None:
             matrix = np.zeros(shape, np.float32)
@@ -2360,8 +2363,7 @@ class Engine:
         c = csm_of(bins, window)
         count = C.c_int32(block_count)
         _check(self._lib.awpu_hip_csm_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, C.byref(c), C.c_void_p(d_matrix_ptr),
-                                                     C.cast(C.byref(count), _i32p), C.c_void_p(d_spectra_ptr), C.c_void_p(stream)),
-               "awpu_hip_csm_samples_device")
+                                                     C.cast(C.byref(count), _i32p), *_dev(d_spectra_ptr, stream)), "awpu_hip_csm_samples_device")
         return count.value
 
     def csm_map(self, matrix: np.ndarray, block_count: int, bins, window: int = TONES_RECT, kind: int = CSM_CONVENTIONAL, want=("map",)):
@@ -2369,7 +2371,7 @@ class Engine:
         as csm_map_host takes it -> a dict of the outputs in `want`: "map" and "q", each [n_bins, pixels]."""
         c = csm_of(bins, window, kind)
         matrix = np.ascontiguousarray(matrix, np.float32)
-        usable = getattr(self, "_usable", self.cfg.n_streams)
+        usable = self.usable
         if matrix.shape != (max(c.n_bins, 0), usable, usable, 2):
             raise ValueError(f"matrix must be [{max(c.n_bins, 0)}, {usable}, {usable}, 2]")
         if not want or any(name not in ("map", "q") for name in want):
@@ -2384,7 +2386,7 @@ class Engine:
         of csm_invert_rule_host.  An unsolved bin raises AwpuError (ERR_RANGE)."""
         c = csm_of(bins, TONES_RECT, CSM_CAPON, loading)
         matrix = _csm_square(matrix, c)
-        usable = getattr(self, "_usable", self.cfg.n_streams)
+        usable = self.usable
         if matrix.shape[1] != usable:
             raise ValueError(f"matrix must be [n_bins, {usable}, {usable}, 2]")
         out = np.empty_like(matrix)
@@ -2396,15 +2398,15 @@ class Engine:
         """The same on device pointers (d_solved [n_bins] int32 or 0) on `stream`; asynchronous, and an unsolved bin is +0 with
         solved 0, no error (awpu_hip_csm_invert_device)."""
         c = csm_of(bins, TONES_RECT, CSM_CAPON, loading)
-        _check(self._lib.awpu_hip_csm_invert_device(self._h, C.c_void_p(d_matrix_ptr), int(block_count), C.byref(c), C.c_void_p(d_inverse_ptr),
-                                                    C.c_void_p(d_solved_ptr), C.c_void_p(stream)), "awpu_hip_csm_invert_device")
+        _check(self._lib.awpu_hip_csm_invert_device(self._h, C.c_void_p(d_matrix_ptr), int(block_count), C.byref(c),
+                                                    *_dev(d_inverse_ptr, d_solved_ptr, stream)), "awpu_hip_csm_invert_device")
 
     def csm_map_device(self, d_matrix_ptr: int, block_count: int, bins, window: int = TONES_RECT, kind: int = CSM_CONVENTIONAL,
                        d_map_ptr: int = 0, d_q_ptr: int = 0, stream: int = 0) -> None:
         """The same on device pointers (map and q [n_bins, pixels], each or 0) on `stream`; asynchronous (awpu_hip_csm_map_device)."""
         c = csm_of(bins, window, kind)
-        _check(self._lib.awpu_hip_csm_map_device(self._h, C.c_void_p(d_matrix_ptr), int(block_count), C.byref(c), C.c_void_p(d_map_ptr),
-                                                 C.c_void_p(d_q_ptr), C.c_void_p(stream)), "awpu_hip_csm_map_device")
+        _check(self._lib.awpu_hip_csm_map_device(self._h, C.c_void_p(d_matrix_ptr), int(block_count), C.byref(c), *_dev(d_map_ptr, d_q_ptr, stream)),
+               "awpu_hip_csm_map_device")
 
     def csm_clean(self, matrix: np.ndarray, block_count: int, bins, steps: int, gain: float = 1.0, stop_ratio: float = 0.0,
                   window: int = TONES_RECT, kind: int = CSM_CONVENTIONAL, want=("steps", "clean", "residual", "map")):
@@ -2413,7 +2415,7 @@ class Engine:
         "residual", "map" [n_bins, pixels] and "residual_matrix" [n_bins, usable, usable, 2]."""
         c, cl = csm_of(bins, window, kind), CsmClean(int(steps), float(gain), float(stop_ratio))
         matrix = np.ascontiguousarray(matrix, np.float32)
-        usable = getattr(self, "_usable", self.cfg.n_streams)
+        usable = self.usable
         if matrix.shape != (max(c.n_bins, 0), usable, usable, 2):
             raise ValueError(f"matrix must be [{max(c.n_bins, 0)}, {usable}, {usable}, 2]")
         out = _csm_clean_outputs(want, max(c.n_bins, 0), max(int(steps), 0), self.pixel_count, usable)
@@ -2428,9 +2430,9 @@ class Engine:
         """The same on device pointers (each output or 0, not all) on `stream`; asynchronous: the picks, the stop tests and the
         records stay on the device (awpu_hip_csm_clean_device).  d_matrix is not written."""
         c, cl = csm_of(bins, window, kind), CsmClean(int(steps), float(gain), float(stop_ratio))
-        _check(self._lib.awpu_hip_csm_clean_device(self._h, C.c_void_p(d_matrix_ptr), int(block_count), C.byref(c), C.byref(cl), C.c_void_p(d_steps_ptr),
-                                                   C.c_void_p(d_clean_ptr), C.c_void_p(d_residual_ptr), C.c_void_p(d_map_ptr),
-                                                   C.c_void_p(d_residual_matrix_ptr), C.c_void_p(stream)), "awpu_hip_csm_clean_device")
+        _check(self._lib.awpu_hip_csm_clean_device(self._h, C.c_void_p(d_matrix_ptr), int(block_count), C.byref(c), C.byref(cl),
+                                                   *_dev(d_steps_ptr, d_clean_ptr, d_residual_ptr, d_map_ptr, d_residual_matrix_ptr, stream)),
+               "awpu_hip_csm_clean_device")
 
     def csm_clean_step_device(self, d_matrix_ptr: int, d_pixel_ptr: int, bins, gain: float = 1.0, window: int = TONES_RECT,
                               kind: int = CSM_CONVENTIONAL, d_component_ptr: int = 0, d_qs_ptr: int = 0, stream: int = 0) -> None:
@@ -2438,17 +2440,16 @@ class Engine:
         the table: the bin is skipped); d_component [n_bins, usable, 2] and d_qs [n_bins], each or 0; asynchronous
         (awpu_hip_csm_clean_step_device)."""
         c = csm_of(bins, window, kind)
-        _check(self._lib.awpu_hip_csm_clean_step_device(self._h, C.c_void_p(d_matrix_ptr), C.c_void_p(d_pixel_ptr), C.byref(c), float(gain),
-                                                        C.c_void_p(d_component_ptr), C.c_void_p(d_qs_ptr), C.c_void_p(stream)),
-               "awpu_hip_csm_clean_step_device")
+        _check(self._lib.awpu_hip_csm_clean_step_device(self._h, *_dev(d_matrix_ptr, d_pixel_ptr), C.byref(c), float(gain),
+                                                        *_dev(d_component_ptr, d_qs_ptr, stream)), "awpu_hip_csm_clean_step_device")
 
     def range(self, theta, phi, distance, d_frame_ptr: int = 0):
         """The beam power of every direction (theta[k], phi[k]) focused at every candidate distance[j] (metres, inf = a plane wave),
         in one launch on raw samples; d_frame_ptr 0 = the ingest ring's snapshot -> (power [n_src, n_dist], best [n_src]
         RANGE_DTYPE records = range_pick(power)) (awpu_hip_range)."""
-        theta = np.ascontiguousarray(np.atleast_1d(theta), np.float64)
-        phi = np.ascontiguousarray(np.atleast_1d(phi), np.float64)
-        distance = np.ascontiguousarray(np.atleast_1d(distance), np.float64)
+        theta = _f64_vector(theta)
+        phi = _f64_vector(phi)
+        distance = _f64_vector(distance)
         if theta.shape != phi.shape or theta.ndim != 1 or distance.ndim != 1:
             raise ValueError("theta and phi must be 1-D and alike, distance 1-D")
         power = np.empty((theta.size, distance.size), np.float32)
@@ -2458,11 +2459,11 @@ class Engine:
                                         best.ctypes.data_as(C.c_void_p)), "awpu_hip_range")
         return power, best
 
-    def _locate(self, call, where, n_blocks, rows, cols, first, every, distance, find, want_power, want_range_power) -> LocateResult:
-        n_frames, next_first = watch_count(n_blocks, first, every)
-        w = Watch(first, every, rows, cols, 0, 0, 0, None)
-        f = _find_struct(rows, cols, find)
-        distance = np.ascontiguousarray(np.atleast_1d(distance), np.float64)
+    def _locate(self, run, *, distance, find, want_power, want_range_power, **shown) -> LocateResult:
+        call, where, n_blocks = run
+        n_frames, next_first, w = self._shown_frames(n_blocks, **shown)
+        f = _find_struct(w.rows, w.cols, find)
+        distance = _f64_vector(distance)
         ms = max(f.max_sources, 0)
         sources = np.empty((n_frames, ms), SOURCE_DTYPE)
         count = np.empty(n_frames, np.int32)
@@ -2478,18 +2479,14 @@ class Engine:
         """find_blocks, and for every source it reports the beam power at that direction focused at every candidate `distance`
         (metres, inf = a plane wave), swept on the block's raw snapshot while it is on the device, and the distance at which it
         peaks (awpu_hip_locate_blocks).  Needs set_antenna.  -> LocateResult."""
-        buf, n_blocks = _wire_blocks(wire, stride)
-        return self._locate(lambda *rest: self._lib.awpu_hip_locate_blocks(self._h, buf.ctypes.data_as(C.c_void_p), stride, *rest),
-                            "awpu_hip_locate_blocks", n_blocks, rows, cols, first, every, distance, find, want_power,
-                            want_range_power)
+        return self._locate(self._wire_run("awpu_hip_locate_blocks", wire, stride), distance=distance, rows=rows, cols=cols, first=first,
+                            every=every, find=find, want_power=want_power, want_range_power=want_range_power)
 
     def locate_samples(self, samples: np.ndarray, rows: int, cols: int, distance, first: int = 0, every: int = 1, want_power: bool = False,
                        want_range_power: bool = False, **find) -> LocateResult:
         """The same from unpacked samples [n_streams, N] (N a multiple of 256, oldest first) (awpu_hip_locate_samples)."""
-        samples, n_blocks = self._sample_blocks(samples)
-        return self._locate(lambda *rest: self._lib.awpu_hip_locate_samples(self._h, _f32(samples), samples.shape[1], *rest),
-                            "awpu_hip_locate_samples", n_blocks, rows, cols, first, every, distance, find, want_power,
-                            want_range_power)
+        return self._locate(self._sample_run("awpu_hip_locate_samples", samples), distance=distance, rows=rows, cols=cols, first=first,
+                            every=every, find=find, want_power=want_power, want_range_power=want_range_power)
 
     def locate_samples_device(self, d_samples_ptr: int, pitch: int, n_blocks: int, rows: int, cols: int, distance, d_sources_ptr: int,
                               d_count_ptr: int, d_ranges_ptr: int, first: int = 0, every: int = 1, d_power_ptr: int = 0,
@@ -2497,14 +2494,11 @@ class Engine:
         """The same on device pointers (as find_samples_device takes them; ranges [n_frames, max_sources] records of 16 bytes,
         range_power [n_frames, max_sources, n_dist] floats or 0) on `stream`; asynchronous.  -> next_first
         (awpu_hip_locate_samples_device)."""
-        w = Watch(first, every, rows, cols, 0, 0, 0, None)
-        f = _find_struct(rows, cols, find)
-        distance = np.ascontiguousarray(np.atleast_1d(distance), np.float64)
-        _check(self._lib.awpu_hip_locate_samples_device(self._h, C.c_void_p(d_samples_ptr), pitch, n_blocks, C.byref(w), C.byref(f),
-                                                        C.c_void_p(d_sources_ptr), C.c_void_p(d_count_ptr), C.c_void_p(d_power_ptr),
-                                                        distance.ctypes.data_as(_f64p), distance.size, C.c_void_p(d_ranges_ptr),
-                                                        C.c_void_p(d_range_power_ptr), C.c_void_p(stream)), "awpu_hip_locate_samples_device")
-        return watch_count(n_blocks, first, every)[1]
+        w = _watch_struct(rows=rows, cols=cols, first=first, every=every)
+        distance = _f64_vector(distance)
+        return self._device_run("awpu_hip_locate_samples_device", d_samples_ptr, pitch, n_blocks, w, C.byref(_find_struct(rows, cols, find)),
+                                *_dev(d_sources_ptr, d_count_ptr, d_power_ptr), distance.ctypes.data_as(_f64p), distance.size,
+                                *_dev(d_ranges_ptr, d_range_power_ptr, stream))
 
     def set_fir_table(self, coeffs: np.ndarray) -> None:
         """The caller's [101, 8] coefficient table of the FIR variant (src/dsp/filter.h:10-112)."""
@@ -2543,15 +2537,12 @@ class Engine:
 
     def process_device(self, d_frames_ptr: int, batch: int, d_power_ptr: int, stream: int = 0) -> None:
         """Asynchronous sweep on device pointers (e.g. torch tensors' data_ptr()) on `stream`."""
-        _check(self._lib.awpu_hip_process_device(self._h, C.c_void_p(d_frames_ptr), batch,
-                                                 C.c_void_p(d_power_ptr), C.c_void_p(stream)),
-               "awpu_hip_process_device")
+        _check(self._lib.awpu_hip_process_device(self._h, C.c_void_p(d_frames_ptr), batch, *_dev(d_power_ptr, stream)), "awpu_hip_process_device")
 
     def process_device_sums(self, d_frames_ptr: int, batch: int, d_power_ptr: int, d_sums_ptr: int, stream: int = 0) -> None:
         """process_device plus every pixel's out[0..255] before the epilogue into d_sums [batch, pixels, 256]
         (awpu_hip_process_device_sums: MATH_F32_EXACT only, either interpolation; bit-identical to the reference's out[])."""
-        _check(self._lib.awpu_hip_process_device_sums(self._h, C.c_void_p(d_frames_ptr), batch, C.c_void_p(d_power_ptr),
-                                                      C.c_void_p(d_sums_ptr), C.c_void_p(stream)),
+        _check(self._lib.awpu_hip_process_device_sums(self._h, C.c_void_p(d_frames_ptr), batch, *_dev(d_power_ptr, d_sums_ptr, stream)),
                "awpu_hip_process_device_sums")
 
     def packed_bytes(self, batch: int) -> int:
@@ -2563,13 +2554,11 @@ class Engine:
 
     def pack_frames(self, d_frames_ptr: int, batch: int, d_packed_ptr: int, stream: int = 0) -> None:
         """The sweep's pack pass on its own (the ingest rank of a multi-GPU job): frames -> packed pairs, on `stream`."""
-        _check(self._lib.awpu_hip_pack_frames(self._h, C.c_void_p(d_frames_ptr), batch, C.c_void_p(d_packed_ptr),
-                                              C.c_void_p(stream)), "awpu_hip_pack_frames")
+        _check(self._lib.awpu_hip_pack_frames(self._h, C.c_void_p(d_frames_ptr), batch, *_dev(d_packed_ptr, stream)), "awpu_hip_pack_frames")
 
     def process_packed(self, d_packed_ptr: int, batch: int, d_power_ptr: int, stream: int = 0) -> None:
         """The sweep on packed frame pairs as they arrive from the ingest rank, on `stream`; asynchronous."""
-        _check(self._lib.awpu_hip_process_packed(self._h, C.c_void_p(d_packed_ptr), batch, C.c_void_p(d_power_ptr),
-                                                 C.c_void_p(stream)), "awpu_hip_process_packed")
+        _check(self._lib.awpu_hip_process_packed(self._h, C.c_void_p(d_packed_ptr), batch, *_dev(d_power_ptr, stream)), "awpu_hip_process_packed")
 
     def heatmap_device(self, d_power_ptr: int, n: int, batch: int, d_peak_ptr: int, d_pix_ptr: int,
                        peak_given: bool = False, stream: int = 0) -> None:
@@ -2602,8 +2591,8 @@ class Engine:
 
     def steer_table_device(self, theta, phi):
         """steer_table for the handle's antenna, computed on the device -> (off, frac) [n_dir, n]."""
-        theta = np.ascontiguousarray(np.atleast_1d(theta), np.float64)
-        phi = np.ascontiguousarray(np.atleast_1d(phi), np.float64)
+        theta = _f64_vector(theta)
+        phi = _f64_vector(phi)
         if theta.shape != phi.shape or theta.ndim != 1:
             raise ValueError("theta and phi must be 1-D and alike")
         # (the row length is the n of the last set_antenna call through this Engine: set the antenna here, not through the

@@ -52,18 +52,13 @@ def parent_library(path):
 
 def engine_on(lib, *args):
     """block_rate.engine on `lib` (None: this build).  An Engine keeps the library it was created with (Engine._lib, taken from
-    binding.load() in its constructor) for every later call, close() included; so the binding's cached library is pointed at `lib`
-    for the construction alone and put back before anything else runs.  Should Engine stop keeping its library at construction,
-    this is the place that has to change (an explicit library parameter on Engine would replace it)."""
-    B = pkg.binding
-    B.load()
-    mine = B._lib
-    if lib is not None:
-        B._lib = lib
-    try:
+    binding.load() in its constructor) for every later call, close() included; so binding.loaded_library hands out `lib` for the
+    construction alone.  Should Engine stop keeping its library at construction, this is the place that has to change (an explicit
+    library parameter on Engine would replace it)."""
+    if lib is None:
         return engine(*args)
-    finally:
-        B._lib = mine
+    with pkg.binding.loaded_library(lib):
+        return engine(*args)
 
 
 def spread(v):
