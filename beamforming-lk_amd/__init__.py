@@ -27,6 +27,9 @@ from .binding import (  # noqa: F401
     csm_accumulate_host,
     csm_clean_host,
     csm_clean_step_host,
+    csm_eig_host,
+    csm_eig_map_host,
+    csm_eig_weigh_host,
     csm_invert_host,
     csm_invert_rule_host,
     csm_map_host,
@@ -58,6 +61,7 @@ __all__ = [
     "Engine", "AwpuError", "MATH_F32_EXACT", "MATH_F32_FAST", "MATH_BF16_ACC", "build_delay_table", "build_delay_table_device",
     "create_antenna", "create_tiled_antenna", "steering_delays", "heatmap_u8", "find_peaks", "expose_count", "expose_rows", "cohere_host", "peel_host", "peel_step_host", "peel_beam_length", "peel_sources", "band_design", "band_filter", "resize_linear_u8", "steer_table", "focus_delays", "focus_steer_table",
     "build_focus_table", "build_focus_table_device", "range_pick", "range_candidates", "tones_host", "tones_linear", "tones_of", "tones_twiddles",
-    "tones_window", "csm_spectra_host", "csm_accumulate_host", "csm_steer_host", "csm_map_host", "csm_invert_host", "csm_invert_rule_host", "csm_clean_host", "csm_clean_step_host", "binding",
+    "tones_window", "csm_spectra_host", "csm_accumulate_host", "csm_steer_host", "csm_map_host", "csm_invert_host", "csm_invert_rule_host", "csm_clean_host", "csm_clean_step_host", "csm_eig_host",
+    "csm_eig_weigh_host", "csm_eig_map_host", "binding",
     "synthetic", "_build",
 ]

@@ -535,10 +535,41 @@ _CSM_CLEAN_SIGNATURES = {
 }
 CSM_CLEAN_SYMBOLS = tuple(_CSM_CLEAN_SIGNATURES)
 
+# the eigendecomposition and the subspace maps (step 8): the entry points of include/awpu_hip_csm_eig.h
+CSM_EIG_MUSIC, CSM_EIG_FUNCTIONAL = 0, 1
+CSM_EIG_MAX_MICS, CSM_EIG_MAX_SWEEPS, CSM_EIG_MAX_ROOT = 256, 32, 6
+
+
+class CsmEig(C.Structure):
+    """awpu_csm_eig_t (include/awpu_hip_csm_eig.h)."""
+    _fields_ = [
+        ("kind", C.c_int32),
+        ("n_sources", C.c_int32),
+        ("root", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+assert C.sizeof(CsmEig) == 16
+
+_CSM_EIG_SIGNATURES = {
+    "awpu_hip_csm_eig_host": (C.c_int, [_f32p, C.c_int32, C.c_int32, C.POINTER(Csm), _f32p, _f32p, _i32p, _i32p]),
+    "awpu_hip_csm_eig_weigh_host": (C.c_int, [_f32p, _f32p, C.c_int32, C.POINTER(Csm), C.POINTER(CsmEig), _f32p]),
+    "awpu_hip_csm_eig_map_host": (C.c_int, [_f32p, _i32p, *_CSM_TABLE, C.POINTER(CsmEig), _f32p]),
+    "awpu_hip_csm_eig": (C.c_int, [C.c_void_p, _f32p, C.c_int32, C.POINTER(Csm), _f32p, _f32p, _i32p, _i32p]),
+    "awpu_hip_csm_eig_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Csm), *([C.c_void_p] * 5)]),
+    "awpu_hip_csm_eig_weigh_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Csm), C.POINTER(CsmEig), C.c_void_p, C.c_void_p]),
+    "awpu_hip_csm_eig_map": (C.c_int, [C.c_void_p, _f32p, C.c_int32, C.POINTER(Csm), C.POINTER(CsmEig), _f32p, _f32p, _i32p]),
+    "awpu_hip_csm_eig_map_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Csm), C.POINTER(CsmEig), *([C.c_void_p] * 4)]),
+}
+CSM_EIG_SYMBOLS = tuple(_CSM_EIG_SIGNATURES)
+
 # every table above, one per public header: what load() sets the types of
 _ALL_SIGNATURES = (_SIGNATURES, _TRACK_SIGNATURES, _BLOCK_SIGNATURES, _LISTEN_SIGNATURES, _WATCH_SIGNATURES, _FIND_SIGNATURES, _BAND_SIGNATURES,
                    _FOCUS_SIGNATURES, _SPECTRAL_SIGNATURES, _EXPOSE_SIGNATURES, _COHERE_SIGNATURES, _PEEL_SIGNATURES,
                    _TONES_SIGNATURES, _CSM_SIGNATURES, _CSM_INVERT_SIGNATURES, _CSM_WATCH_SIGNATURES, _CSM_CLEAN_SIGNATURES)
+# ... and the tables of later headers, which load() walks behind those
+_LATER_SIGNATURES = (_CSM_EIG_SIGNATURES,)
 
 # numpy view of awpu_range_t: what range_pick, Engine.range and Engine.locate_* return (unused entries: index -1)
 RANGE_DTYPE = np.dtype([("index", "<i4"), ("power", "<f4"), ("distance", "<f8")], align=True)
@@ -575,7 +606,7 @@ def load(build: bool = True) -> C.CDLL:
     if not path.exists():
         raise RuntimeError(f"{path} is missing and there is no CPU fallback")
     lib = C.CDLL(str(path))
-    for table in _ALL_SIGNATURES:
+    for table in _ALL_SIGNATURES + _LATER_SIGNATURES:
         for name, (res, args) in table.items():
             fn = getattr(lib, name)
             fn.restype = res
@@ -1221,6 +1252,63 @@ def csm_invert_rule_host(matrix: np.ndarray, block_count: int, bins, loading: fl
     _check(load().awpu_hip_csm_invert_rule_host(_f32(matrix), int(block_count), matrix.shape[1], C.byref(c), _out_ptr(out, _f32p),
                                                 _out_ptr(solved, _i32p)), "awpu_hip_csm_invert_rule_host")
     return out, solved
+
+
+def csm_eig_of(kind, n_sources: int = 0, root: int = 0) -> CsmEig:
+    """The CsmEig of a subspace map (or a CsmEig, passed through): CSM_EIG_MUSIC with the signal subspace's dimension, or
+    CSM_EIG_FUNCTIONAL with the exponent 2 ** root.  Nothing is judged here: the library refuses a bad request."""
+    if isinstance(kind, CsmEig):
+        return kind
+    return CsmEig(int(kind), int(n_sources), int(root), 0)
+
+
+def csm_eig_host(matrix: np.ndarray, block_count: int, bins):
+    """Step 8a (awpu_hip_csm_eig_host): the eigendecomposition of matrix [n_bins, usable, usable, 2] with its block count by the
+    written arithmetic, what Engine.csm_eig_device gives bit for bit -> (values [n_bins, usable] descending, vectors
+    [n_bins, usable, usable, 2] with vectors[k, r] the eigenvector of values[k, r], solved [n_bins] int32, sweeps [n_bins] int32).
+    An unsolved bin is +0 with solved 0, no error."""
+    c = csm_of(bins)
+    matrix = _csm_square(matrix, c)
+    K, U = max(c.n_bins, 0), matrix.shape[1]
+    values, vectors = np.empty((K, U), np.float32), np.empty_like(matrix)
+    solved, sweeps = np.empty(K, np.int32), np.empty(K, np.int32)
+    _check(load().awpu_hip_csm_eig_host(_f32(matrix), int(block_count), U, C.byref(c), _out_ptr(values, _f32p), _out_ptr(vectors, _f32p),
+                                        _out_ptr(solved, _i32p), _out_ptr(sweeps, _i32p)), "awpu_hip_csm_eig_host")
+    return values, vectors, solved, sweeps
+
+
+def csm_eig_weigh_host(values: np.ndarray, vectors: np.ndarray, bins, kind: int = CSM_EIG_MUSIC, n_sources: int = 0, root: int = 0) -> np.ndarray:
+    """Step 8b (awpu_hip_csm_eig_weigh_host): the weighed matrix H [n_bins, usable, usable, 2] of csm_eig_host's values and
+    vectors: the noise subspace's projector (CSM_EIG_MUSIC) or C ** (1 / 2 ** root) (CSM_EIG_FUNCTIONAL)."""
+    c, e = csm_of(bins), csm_eig_of(kind, n_sources, root)
+    vectors = _csm_square(vectors, c)
+    values = np.ascontiguousarray(values, np.float32)
+    if values.shape != vectors.shape[:2]:
+        raise ValueError("values must be [n_bins, usable]")
+    out = np.empty_like(vectors)
+    _check(load().awpu_hip_csm_eig_weigh_host(_f32(values), _f32(vectors), vectors.shape[1], C.byref(c), C.byref(e), _out_ptr(out, _f32p)),
+           "awpu_hip_csm_eig_weigh_host")
+    return out
+
+
+def csm_eig_map_host(weighed: np.ndarray, solved, off: np.ndarray, frac: np.ndarray, bins, kind: int = CSM_EIG_MUSIC, n_sources: int = 0,
+                     root: int = 0, window: int = TONES_RECT, index=None) -> np.ndarray:
+    """Step 8c (awpu_hip_csm_eig_map_host): the subspace map [n_bins, n_pixels] of csm_eig_weigh_host's matrix; solved [n_bins]
+    (an unsolved bin is a +0 plane) or None."""
+    c, e = csm_of(bins, window), csm_eig_of(kind, n_sources, root)
+    off, frac, index = _csm_table(off, frac, index)
+    weighed = np.ascontiguousarray(weighed, np.float32)
+    if weighed.shape != (max(c.n_bins, 0), len(index), len(index), 2):
+        raise ValueError("weighed must be [n_bins, usable, usable, 2]")
+    if solved is not None:
+        solved = np.ascontiguousarray(solved, np.int32)
+        if solved.shape != (max(c.n_bins, 0),):
+            raise ValueError("solved must be [n_bins]")
+    out = np.empty((max(c.n_bins, 0), off.shape[0]), np.float32)
+    _check(load().awpu_hip_csm_eig_map_host(_f32(weighed), None if solved is None else _i32(solved), _i32(off), _f32(frac), off.shape[1],
+                                            off.shape[0], _i32(index), len(index), C.byref(c), C.byref(e), _out_ptr(out, _f32p)),
+           "awpu_hip_csm_eig_map_host")
+    return out
 
 
 _CSM_CLEAN_OUTPUTS = ("steps", "clean", "residual", "map", "residual_matrix")
@@ -2407,6 +2495,65 @@ class Engine:
         c = csm_of(bins, window, kind)
         _check(self._lib.awpu_hip_csm_map_device(self._h, C.c_void_p(d_matrix_ptr), int(block_count), C.byref(c), *_dev(d_map_ptr, d_q_ptr, stream)),
                "awpu_hip_csm_map_device")
+
+    def csm_eig(self, matrix: np.ndarray, block_count: int, bins):
+        """Step 8a on the device (awpu_hip_csm_eig): the eigendecomposition of a host matrix [n_bins, usable, usable, 2], the bits of
+        csm_eig_host -> (values, vectors, solved, sweeps) as csm_eig_host returns them."""
+        c = csm_of(bins)
+        matrix = _csm_square(matrix, c)
+        K, U = max(c.n_bins, 0), self.usable
+        if matrix.shape[1] != U:
+            raise ValueError(f"matrix must be [n_bins, {U}, {U}, 2]")
+        values, vectors = np.empty((K, U), np.float32), np.empty_like(matrix)
+        solved, sweeps = np.empty(K, np.int32), np.empty(K, np.int32)
+        _check(self._lib.awpu_hip_csm_eig(self._h, _f32(matrix), int(block_count), C.byref(c), _out_ptr(values, _f32p), _out_ptr(vectors, _f32p),
+                                          _out_ptr(solved, _i32p), _out_ptr(sweeps, _i32p)), "awpu_hip_csm_eig")
+        return values, vectors, solved, sweeps
+
+    def csm_eig_device(self, d_matrix_ptr: int, block_count: int, bins, d_values_ptr: int, d_vectors_ptr: int, d_solved_ptr: int = 0,
+                       d_sweeps_ptr: int = 0, stream: int = 0) -> None:
+        """The same on device pointers (values [n_bins, usable], vectors [n_bins, usable, usable, 2]; solved and sweeps [n_bins]
+        int32, each or 0) on `stream`; asynchronous (awpu_hip_csm_eig_device)."""
+        c = csm_of(bins)
+        _check(self._lib.awpu_hip_csm_eig_device(self._h, C.c_void_p(d_matrix_ptr), int(block_count), C.byref(c),
+                                                 *_dev(d_values_ptr, d_vectors_ptr, d_solved_ptr, d_sweeps_ptr, stream)), "awpu_hip_csm_eig_device")
+
+    def csm_eig_weigh_device(self, d_values_ptr: int, d_vectors_ptr: int, bins, d_weighed_ptr: int, kind: int = CSM_EIG_MUSIC, n_sources: int = 0,
+                             root: int = 0, stream: int = 0) -> None:
+        """Step 8b on device pointers (weighed [n_bins, usable, usable, 2]) on `stream`; asynchronous, the bits of
+        csm_eig_weigh_host (awpu_hip_csm_eig_weigh_device)."""
+        c, e = csm_of(bins), csm_eig_of(kind, n_sources, root)
+        _check(self._lib.awpu_hip_csm_eig_weigh_device(self._h, C.c_void_p(d_values_ptr), C.c_void_p(d_vectors_ptr), C.byref(c), C.byref(e),
+                                                       *_dev(d_weighed_ptr, stream)), "awpu_hip_csm_eig_weigh_device")
+
+    def csm_eig_map(self, matrix: np.ndarray, block_count: int, bins, kind: int = CSM_EIG_MUSIC, n_sources: int = 0, root: int = 0,
+                    window: int = TONES_RECT, want=("map",)):
+        """Steps 8a to 8c on the device with the handle's table and active mics (awpu_hip_csm_eig_map): the MUSIC or functional map
+        of a host matrix [n_bins, usable, usable, 2] with its block count -> a dict of the outputs in `want`: "map" [n_bins, pixels]
+        (always computed), "values" [n_bins, usable] and "solved" [n_bins] int32."""
+        c, e = csm_of(bins, window), csm_eig_of(kind, n_sources, root)
+        matrix = np.ascontiguousarray(matrix, np.float32)
+        K, U = max(c.n_bins, 0), self.usable
+        if matrix.shape != (K, U, U, 2):
+            raise ValueError(f"matrix must be [{K}, {U}, {U}, 2]")
+        if not want or any(name not in ("map", "values", "solved") for name in want):
+            raise ValueError("want names some of ('map', 'values', 'solved')")
+        out = {"map": np.empty((K, self.pixel_count), np.float32)}
+        if "values" in want:
+            out["values"] = np.empty((K, U), np.float32)
+        if "solved" in want:
+            out["solved"] = np.empty(K, np.int32)
+        _check(self._lib.awpu_hip_csm_eig_map(self._h, _f32(matrix), int(block_count), C.byref(c), C.byref(e), _out_ptr(out["map"], _f32p),
+                                              _out_ptr(out.get("values"), _f32p), _out_ptr(out.get("solved"), _i32p)), "awpu_hip_csm_eig_map")
+        return {name: out[name] for name in ("map", "values", "solved") if name in want}
+
+    def csm_eig_map_device(self, d_matrix_ptr: int, block_count: int, bins, d_map_ptr: int, kind: int = CSM_EIG_MUSIC, n_sources: int = 0,
+                           root: int = 0, window: int = TONES_RECT, d_values_ptr: int = 0, d_solved_ptr: int = 0, stream: int = 0) -> None:
+        """The same on device pointers (map [n_bins, pixels]; values [n_bins, usable] and solved [n_bins] int32, each or 0) on
+        `stream`; asynchronous (awpu_hip_csm_eig_map_device)."""
+        c, e = csm_of(bins, window), csm_eig_of(kind, n_sources, root)
+        _check(self._lib.awpu_hip_csm_eig_map_device(self._h, C.c_void_p(d_matrix_ptr), int(block_count), C.byref(c), C.byref(e),
+                                                     *_dev(d_map_ptr, d_values_ptr, d_solved_ptr, stream)), "awpu_hip_csm_eig_map_device")
 
     def csm_clean(self, matrix: np.ndarray, block_count: int, bins, steps: int, gain: float = 1.0, stop_ratio: float = 0.0,
                   window: int = TONES_RECT, kind: int = CSM_CONVENTIONAL, want=("steps", "clean", "residual", "map")):

@@ -407,6 +407,12 @@ struct awpu_hip {
     // ... and the loaded inverse's scratch (awpu_csm.cpp; csm_invert_kernels.h): the factor L and its inverse M in double,
     // [n_bins][usable][usable][2] each, then the bins' state words
     Dev<double> d_csm_invert;
+    // ... and the eigendecomposition's (awpu_hip_csm_eig.h; awpu_csm_eig.cpp): the Jacobi kernel's scratch in double
+    // (csm_eig_kernels.h lays it out), and what a subspace map keeps between its steps: the vectors and the weighed matrix
+    // [n_bins][usable][usable][2] each, q [n_bins][pixel_count], then the values [n_bins][usable] and the solved words [n_bins]
+    // where the caller keeps none
+    Dev<double> d_csm_eig;
+    Dev<float> d_csm_eig_rows;
     // ... and a cross-spectral run's (awpu_hip_csm_watch.h): the spectra store, the carry, one frame's matrix and inverse, a piece's
     // rows, planes, solved words and step records, a chunk's samples and datagrams (csm_run_plan.h lays it out)
     Dev<float> d_csm_run;

@@ -73,6 +73,49 @@
  *   7. CLEAN-SC: the conventional map deconvolved per bin -- map, take the strongest pixel, subtract the part of C that is
  *      coherent with its beam, map again.  awpu_hip_csm_clean.h states the step's arithmetic and declares its calls;
  *      csrc/csm_clean_rule.h is the rule as code.
+ *   8. The eigendecomposition C = V L V^H and the two subspace maps built on it, MUSIC and functional beamforming
+ *      (awpu_hip_csm_eig.h declares the calls; csrc/csm_eig_rule.h is the rule as code).  Doubles in 8a, floats in 8b and 8c;
+ *      fma / fmaf are the fused operations, `/` and sqrt the IEEE operations, nothing else is fused.
+ *  8a. Parallel-order cyclic Jacobi, per bin, with n = (double) n_blocks and U = usable:
+ *        Load.    As step 6a reads C: for b < a, A[a][b] = ((double) C.re / n, (double) C.im / n) and A[b][a] its exact conjugate;
+ *                 A[a][a] = ((double) C[a][a].re / n, 0);  V = I.  trace = the sum of A[a][a].re, a ascending, plain additions
+ *                 from 0.  The bin is UNSOLVED (with sweeps 0) if a read entry is not finite or trace is not finite or not > 0.
+ *                 thr = (trace / (double) U) * 2^-52.
+ *        Order.   M = U + (U & 1): the index U of an odd U is a dummy that sits out.  A sweep is M - 1 rounds; round r pairs
+ *                 (M-1, r) and ((r + i) mod (M-1), (r - i) mod (M-1)) for i = 1 .. M/2 - 1, each taken as p < q; a pair with the
+ *                 dummy is dropped.  The pairs of a round are disjoint.
+ *        A pair's parameters, from the matrix as the round finds it: beta = A[q][p], app = A[p][p].re, aqq = A[q][q].re;
+ *                 g = sqrt(fma(beta.re, beta.re, beta.im * beta.im));  the pair rotates iff g > thr;
+ *                 phi = (beta.re / g, beta.im / g);  theta = (aqq - app) / (g + g);  r = sqrt(fma(theta, theta, 1));
+ *                 t = 1 / (|theta| + r), negated when theta < 0;  c = 1 / sqrt(fma(t, t, 1));  s = t * c.
+ *        Phase 1, columns.  For X in {A, V}, every row i and every rotating pair, x = X[i][p], y = X[i][q], w = y phi:
+ *                     w.re = fma(y.re, phi.re, -(y.im * phi.im));   w.im = fma(y.re, phi.im, y.im * phi.re)
+ *                     X[i][p] = (fma(c, x.re, -(s * w.re)), fma(c, x.im, -(s * w.im)))
+ *                     X[i][q] = (fma(s, x.re, c * w.re), fma(s, x.im, c * w.im))
+ *        Phase 2, rows of A, behind phase 1 of the whole round.  For every column j other than p and q, x = A[p][j],
+ *                 y = A[q][j], w = y conj(phi):
+ *                     w.re = fma(y.re, phi.re, y.im * phi.im);      w.im = fma(y.im, phi.re, -(y.re * phi.im))
+ *                 and the same two combinations.  The pair's own four entries are written in closed form:
+ *                     A[p][p] = (fma(-t, g, app), 0);   A[q][q] = (fma(t, g, aqq), 0);   A[p][q] = A[q][p] = (0, 0).
+ *                 Every entry is written by at most one rotation a phase: the launch shape cannot change a bit.
+ *        Stop.    After the first sweep in which no pair rotated; `sweeps` counts the sweeps run, that one included.  A bin that
+ *                 still rotates in its 32nd sweep is unsolved.
+ *        Sort and round.  Eigenvalue j (A[j][j].re) has rank = the number of i with l_i > l_j, or l_i == l_j and i < j;
+ *                 values[k][rank] = (float) l_j;  vectors[k][rank][a] = ((float) V[a][j].re, (float) V[a][j].im): an eigenvector
+ *                 is one contiguous row.  A bin with an eigenvalue that is not finite is unsolved.  An unsolved bin: every value
+ *                 and every vector word +0, `solved` 0, `sweeps` as run; every other bin's `solved` is 1.
+ *  8b. The weighed matrix H [n_bins][usable][usable][2] from the float values and vectors and an awpu_csm_eig_t:
+ *          AWPU_CSM_EIG_MUSIC        w_r = r < n_sources ? 0 : 1                  (the projector on the noise subspace)
+ *          AWPU_CSM_EIG_FUNCTIONAL   w_r = l_r > 0 ? (float) ((double) l_r, square-rooted `root` times in double) : +0
+ *      -- nu = 2^root keeps the root and the power in written arithmetic; pow is not the same on host and device.  For b <= a, r
+ *      ascending, from +0, with u = vectors[r][a] and v = vectors[r][b] (w u conj(v)):
+ *          t = w_r * u.re;  re = fmaf(t, v.re, re);  t2 = w_r * u.im;  re = fmaf(t2, v.im, re);  im = fmaf(t2, v.re, im);  im = fmaf(-t, v.im, im)
+ *      The diagonal's im is written as +0, the mirror as the exact conjugate.
+ *  8c. The map.  q is steps 3 and 4 on H (kind AWPU_CSM_CONVENTIONAL); Uf = (float) usable; wss and c_k as in step 5:
+ *          MUSIC        floor = Uf * 2^-24;   map = Uf / (q > floor ? q : floor)     (a perfect match, a NaN or a negative q: 2^24)
+ *          functional   y = (q > 0 ? q : +0) / Uf;  y squared `root` times;  map = (c_k * y) / ((wss * 256.0f) * Uf)
+ *      A single source that arrives from the pixel shows the conventional map's level in the functional map (0.5 for a unit sine
+ *      at a bin centre).  An unsolved bin is a +0 plane in both kinds.
  *
  * The device forms perform these operations on these operands: spectra, C, q and the maps equal the host functions' bit for bit
  * wherever the values are finite or infinite; where a NaN arises host and device agree on WHERE, not on its sign and payload.
@@ -168,5 +211,6 @@ int awpu_hip_csm_map_device(awpu_hip_t *h, const float *d_matrix, int32_t block_
 #include "awpu_hip_csm_invert.h" /* step 6a's calls */
 #include "awpu_hip_csm_watch.h"  /* runs: a map per shown block */
 #include "awpu_hip_csm_clean.h"  /* step 7: CLEAN-SC, its rule and its calls */
+#include "awpu_hip_csm_eig.h"    /* step 8: the eigendecomposition and the subspace maps */
 
 #endif /* AWPU_HIP_CSM_H */

@@ -1,0 +1,389 @@
+"""Step 8 of include/awpu_hip_csm.h, the eigendecomposition with a written arithmetic and the two subspace maps, on a box without
+a GPU: the entry points are exported in a list of their own and declared by the header that awpu_hip_csm.h includes;
+awpu_hip_csm_eig_host meets numpy.linalg.eigh of the loaded matrix; values descend, equal values keep index order, and only the
+lower triangle is read; an unsolved bin is +0 with solved 0 and leaves the other bins alone; the weighed matrix is the noise
+projector (MUSIC) or C itself (functional, root 0), exactly Hermitian; on the two-source scene MUSIC shows both sources at their
+pixels where the conventional plane shows one, and functional beamforming keeps the peak and lowers the floor; refusals write
+nothing; the host code runs clean under the address and undefined-behaviour sanitizers as a program of its own; the kernels
+compile for gfx950 without spills or scratch."""
+import ctypes as C
+import re
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import csm_eig_util as EU
+import csm_util as CU
+
+REPO = Path(__file__).resolve().parent.parent
+CSRC = REPO / "beamforming-lk_amd" / "csrc"
+HOST_NAMES = ["awpu_hip_csm_eig_host", "awpu_hip_csm_eig_weigh_host", "awpu_hip_csm_eig_map_host"]
+NAMES = HOST_NAMES + ["awpu_hip_csm_eig", "awpu_hip_csm_eig_device", "awpu_hip_csm_eig_weigh_device", "awpu_hip_csm_eig_map",
+                      "awpu_hip_csm_eig_map_device"]
+BINS = [3, 16, 128]
+# Eigenvalues agree within 2^-22 of the bin's largest: Jacobi in double is exact to about 1e-14 of it and is then rounded to float
+# once (2^-24 relative); numpy's are exact to about 1e-15.  The factor 2 on one rounding of the largest value (2^-23, as
+# test_csm_invert_cpu.py argues for G) is slack.
+VALUE_BOUND = 2.0 ** -22
+
+
+def vector_bound(U):
+    """|A v - lambda v| over lambda_max, and |V^H V - I|: v's U entries and lambda are each rounded to float once (2^-24 of
+    at most 1, and of lambda_max), so a row of A v - lambda v is off by at most (|A| 1 + lambda_max) 2^-24 <= (sqrt(U) + 1) 2^-24
+    lambda_max and an entry of V^H V by 2 U 2^-24 / 2 in the worst case; (U + 2) 2^-23 covers both."""
+    return (U + 2) * 2.0 ** -23
+
+
+def vectors_of(vec):
+    """vectors [K, U, U, 2] -> V [K, U, U] complex128 with the eigenvectors as COLUMNS."""
+    return np.swapaxes(CU.as_complex(vec), 1, 2)
+
+
+# ------------------------------------------------------------------------------------------------ wiring
+
+def test_eig_symbols_exported_and_listed(pkg):
+    lib = pkg.binding.load()
+    B = pkg.binding
+    text = re.sub(r"/\*.*?\*/", "", (REPO / "include" / "awpu_hip_csm_eig.h").read_text(), flags=re.S)
+    assert sorted(set(re.findall(r"\b(awpu_hip_\w+)\s*\(", text))) == sorted(NAMES) == sorted(B.CSM_EIG_SYMBOLS)
+    assert int(re.search(r"#define AWPU_CSM_EIG_MAX_MICS (\d+)", text).group(1)) == 256 == B.CSM_EIG_MAX_MICS
+    assert int(re.search(r"#define AWPU_CSM_EIG_MUSIC (\d+)", text).group(1)) == 0 == B.CSM_EIG_MUSIC
+    assert int(re.search(r"#define AWPU_CSM_EIG_FUNCTIONAL (\d+)", text).group(1)) == 1 == B.CSM_EIG_FUNCTIONAL
+    assert '#include "awpu_hip_csm_eig.h"' in (REPO / "include" / "awpu_hip_csm.h").read_text()
+    for name in NAMES:
+        assert hasattr(lib, name) and getattr(lib, name).argtypes is not None, name
+    others = (B.EXPORTED_SYMBOLS, B.TRACK_SYMBOLS, B.BLOCK_SYMBOLS, B.LISTEN_SYMBOLS, B.WATCH_SYMBOLS, B.FIND_SYMBOLS, B.BAND_SYMBOLS, B.FOCUS_SYMBOLS,
+              B.SPECTRAL_SYMBOLS, B.EXPOSE_SYMBOLS, B.COHERE_SYMBOLS, B.PEEL_SYMBOLS, B.TONES_SYMBOLS, B.CSM_SYMBOLS, B.CSM_INVERT_SYMBOLS,
+              B.CSM_WATCH_SYMBOLS, B.CSM_CLEAN_SYMBOLS)
+    for other in others:
+        assert not set(B.CSM_EIG_SYMBOLS) & set(other)
+    # load() walks the seventeen recorded tables, then the later ones
+    assert len(B._ALL_SIGNATURES) == 17 and B._CSM_EIG_SIGNATURES not in B._ALL_SIGNATURES and B._LATER_SIGNATURES == (B._CSM_EIG_SIGNATURES,)
+    assert C.sizeof(B.CsmEig) == 16 and C.sizeof(B.Csm) == 48
+    e = B.csm_eig_of(B.CSM_EIG_FUNCTIONAL, root=4)
+    assert (e.kind, e.n_sources, e.root, e.reserved) == (1, 0, 4, 0) and B.csm_eig_of(e) is e
+    H, S = pkg._build.HEADERS, pkg._build.SOURCES
+    assert REPO / "include" / "awpu_hip_csm_eig.h" in H and CSRC / "csm_eig_rule.h" in H and CSRC / "csm_eig_kernels.h" in H
+    assert CSRC / "csm_eig_kernels.hip" in S and CSRC / "csm_eig_host.cpp" in S and CSRC / "awpu_csm_eig.cpp" in S
+    assert not any("fast-math" in word or "ffp-contract" in word for word in pkg._build.hipcc_command(Path("x.so")))
+    # one statement of the arithmetic: the host rule, the kernels and the checker compile the same header
+    for user in (CSRC / "csm_eig_host.cpp", CSRC / "csm_eig_kernels.h", REPO / "tests" / "host" / "csm_eig_check.cpp"):
+        assert '#include "csm_eig_rule.h"' in user.read_text(), user
+    assert '#include "csm_eig_kernels.h"' in (CSRC / "csm_eig_kernels.hip").read_text()
+    for name in ("csm_eig_host", "csm_eig_weigh_host", "csm_eig_map_host"):
+        assert name in pkg.__all__ and callable(getattr(pkg, name))
+    for name in ("csm_eig", "csm_eig_device", "csm_eig_weigh_device", "csm_eig_map", "csm_eig_map_device"):
+        assert callable(getattr(B.Engine, name))
+
+
+def test_header_compiles_as_c_from_either_include(tmp_path):
+    for first in ("awpu_hip_csm.h", "awpu_hip_csm_eig.h"):
+        src = tmp_path / "one.c"
+        src.write_text(f'#include "{first}"\n'
+                       "typedef char size_is_16[sizeof(awpu_csm_eig_t) == 16 ? 1 : -1];\n"
+                       "int main(void) { awpu_csm_t c; awpu_csm_eig_t e; float p[8]; int32_t s[2];\n"
+                       "  c.window = AWPU_TONES_RECT; c.n_bins = 1; c.bin[0] = 3; c.kind = AWPU_CSM_CONVENTIONAL; c.loading = 0.0f; p[0] = 1.0f; s[0] = 0;\n"
+                       "  e.kind = AWPU_CSM_EIG_FUNCTIONAL; e.n_sources = 0; e.root = AWPU_CSM_EIG_MAX_ROOT; e.reserved = 0;\n"
+                       "  return awpu_hip_csm_eig_host(p, 1, 1, &c, p + 2, p + 4, s, s + 1) + awpu_hip_csm_eig_weigh_host(p, p + 2, 1, &c, &e, p + 4)\n"
+                       "    + awpu_hip_csm_eig_map_host(p, s, s, p, 1, 1, s, 1, &c, &e, p + 2) + awpu_hip_csm_eig(0, p, 1, &c, p, p, s, s)\n"
+                       "    + awpu_hip_csm_eig_device(0, p, 1, &c, p, p, s, s, 0) + awpu_hip_csm_eig_weigh_device(0, p, p, &c, &e, p, 0)\n"
+                       "    + awpu_hip_csm_eig_map(0, p, 1, &c, &e, p, p, s) + awpu_hip_csm_eig_map_device(0, p, 1, &c, &e, p, p, s, 0)\n"
+                       "    + AWPU_CSM_EIG_MAX_MICS + AWPU_CSM_EIG_MAX_SWEEPS + AWPU_CSM_EIG_MUSIC + (int) sizeof(size_is_16); }\n")
+        subprocess.run(["cc", "-std=c99", "-Wall", "-Werror", "-fsyntax-only", f"-I{REPO / 'include'}", str(src)], check=True, capture_output=True)
+
+
+def test_host_file_compiles_with_a_plain_host_compiler(tmp_path):
+    subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", f"-I{REPO / 'include'}", f"-I{CSRC}", "-c", str(CSRC / "csm_eig_host.cpp"),
+                    "-o", str(tmp_path / "csm_eig_host.o")], check=True, capture_output=True)
+
+
+# ------------------------------------------------------------------------------------------------ the decomposition
+
+CASES = [(U, n) for U in (1, 2, 3, 5, 64, 65) for n in ([2 * U + 3] + ([U // 4] if U >= 5 else []))]
+
+
+@pytest.mark.parametrize("U,n", CASES)
+def test_eig_host_against_numpy(pkg, U, n):
+    """Two strong sources in noise, three bins, more blocks than mics and (from 5 mics) a rank-deficient matrix of U // 4 blocks:
+    against numpy.linalg.eigh of the loaded matrix in complex128 (bounds derived above)."""
+    Cm = EU.random_matrix(np.random.default_rng(1000 + 7 * U + n), 3, U, n)
+    val, vec, solved, sweeps = pkg.csm_eig_host(Cm, n, BINS)
+    assert val.dtype == vec.dtype == np.float32 and val.shape == (3, U) and vec.shape == Cm.shape
+    assert solved.tolist() == [1, 1, 1]
+    print(U, n, "sweeps", sweeps.tolist())
+    assert (sweeps >= 1).all() and (sweeps <= 16).all()
+    A = EU.loaded(Cm, n)
+    ref = np.linalg.eigvalsh(A)[:, ::-1]
+    top = ref[:, 0]
+    V = vectors_of(vec)
+    lam = val.astype(np.float64)
+    worst = {"values": (np.abs(lam - ref).max(axis=1) / top).max(),
+             "residual": (np.abs(A @ V - V * lam[:, None, :]).max(axis=(1, 2)) / top).max(),
+             "gram": np.abs(np.conj(np.swapaxes(V, 1, 2)) @ V - np.eye(U)).max()}
+    print(U, n, worst, "bounds", VALUE_BOUND, vector_bound(U))
+    assert worst["values"] <= VALUE_BOUND and worst["residual"] <= vector_bound(U) and worst["gram"] <= vector_bound(U), worst
+    assert (val[:, :-1] >= val[:, 1:]).all()
+
+
+def test_order_of_equal_values_and_what_is_read(pkg):
+    # a diagonal matrix rotates nothing: one sweep, and the eigenvectors are unit vectors, equal values in index order
+    U = 6
+    Cm = np.zeros((2, U, U, 2), np.float32)
+    Cm[0, np.arange(U), np.arange(U), 0] = [4.0, 8.0, 4.0, 2.0, 8.0, 4.0]
+    Cm[1, np.arange(U), np.arange(U), 0] = 3.0
+    val, vec, solved, sweeps = pkg.csm_eig_host(Cm, 2, [3, 16])
+    assert solved.tolist() == [1, 1] and sweeps.tolist() == [1, 1]
+    assert val[0].tolist() == [4.0, 4.0, 2.0, 2.0, 2.0, 1.0] and val[1].tolist() == [1.5] * U
+    assert np.argmax(vec[0, :, :, 0], axis=1).tolist() == [1, 4, 0, 2, 5, 3] and np.argmax(vec[1, :, :, 0], axis=1).tolist() == list(range(U))
+    assert np.array_equal(np.abs(vec[..., 0]).sum(axis=2), np.ones((2, U))) and not vec[..., 1].any()
+    # the upper triangle and the diagonal's imaginary parts are never read
+    rng = np.random.default_rng(7)
+    bins = [0, 5, 47, 128]
+    Cm = EU.random_matrix(rng, 4, 9, 30)
+    spoiled = Cm.copy()
+    spoiled[:, np.arange(9), np.arange(9), 1] = np.nan
+    spoiled[:, np.triu(np.ones((9, 9), bool), 1)] = np.nan
+    want, got = pkg.csm_eig_host(Cm, 30, bins), pkg.csm_eig_host(spoiled, 30, bins)
+    assert got[2].tolist() == [1, 1, 1, 1] and np.isfinite(got[0]).all() and np.isfinite(got[1]).all()
+    for g, w in zip(got, want):
+        assert CU.same_bits(g, w)
+
+
+@pytest.mark.parametrize("what", ["zeros", "nan_lower", "inf_diagonal", "negative_trace"])
+def test_unsolved_bins(pkg, what):
+    rng = np.random.default_rng(11)
+    U, n = 6, 20
+    Cm = EU.random_matrix(rng, 3, U, n)
+    want = pkg.csm_eig_host(Cm, n, BINS)
+    assert want[2].tolist() == [1, 1, 1]
+    bad = Cm.copy()
+    if what == "zeros":
+        bad[1] = 0.0
+    elif what == "nan_lower":
+        bad[1, 4, 2, 1] = np.nan
+    elif what == "inf_diagonal":
+        bad[1, 3, 3, 0] = np.inf
+    else:
+        bad[1, np.arange(U), np.arange(U), 0] *= -1.0
+    val, vec, solved, sweeps = pkg.csm_eig_host(bad, n, BINS)
+    assert solved.tolist() == [1, 0, 1] and sweeps[1] == 0
+    for a in (val[1], vec[1]):
+        assert not a.any() and not np.signbit(a).any()
+    for k in (0, 2):
+        assert CU.same_bits(val[k], want[0][k]) and CU.same_bits(vec[k], want[1][k]) and sweeps[k] == want[3][k]
+    assert not np.isnan(val).any() and not np.isnan(vec).any()
+    # ... and the maps of such a bin are +0 planes
+    off = rng.integers(0, 200, (4, U)).astype(np.int32)
+    frac = rng.random((4, U)).astype(np.float32)
+    for kind, root in ((EU.MUSIC, 0), (EU.FUNCTIONAL, 2)):
+        H = pkg.csm_eig_weigh_host(val, vec, BINS, kind, 1, root)
+        assert not np.isnan(H).any() and not H[1].any()
+        m = pkg.csm_eig_map_host(H, solved, off, frac, BINS, kind, 1, root)
+        assert not m[1].any() and not np.signbit(m[1]).any() and (m[[0, 2]] > 0).all()
+
+
+# ------------------------------------------------------------------------------------------------ the weighed matrix
+
+@pytest.mark.parametrize("U,n_sources", [(1, 0), (2, 1), (5, 2), (64, 2), (65, 64)])
+def test_weighed_matrix(pkg, U, n_sources):
+    n = 2 * U + 3
+    Cm = EU.random_matrix(np.random.default_rng(50 + U), 3, U, n)
+    val, vec, solved, _ = pkg.csm_eig_host(Cm, n, BINS)
+    assert solved.all()
+    bound = vector_bound(U)
+    V = vectors_of(vec)
+    # MUSIC: with the signal projector of the same float vectors, the identity; the trace counts the noise subspace
+    H = pkg.csm_eig_weigh_host(val, vec, BINS, EU.MUSIC, n_sources)
+    Vs = V[:, :, :n_sources]
+    whole = CU.as_complex(H) + Vs @ np.conj(np.swapaxes(Vs, 1, 2))
+    trace = np.diagonal(H[..., 0], axis1=1, axis2=2).astype(np.float64).sum(axis=1)
+    print(U, "identity", np.abs(whole - np.eye(U)).max(), "trace", np.abs(trace - (U - n_sources)).max(), "bound", bound)
+    assert np.abs(whole - np.eye(U)).max() <= bound and np.abs(trace - (U - n_sources)).max() <= bound
+    # functional, root 0: C itself
+    F0 = pkg.csm_eig_weigh_host(val, vec, BINS, EU.FUNCTIONAL, 0, 0)
+    A = EU.loaded(Cm, n)
+    off_by = np.abs(CU.as_complex(F0) - A).max(axis=(1, 2)) / val[:, 0].astype(np.float64)
+    print(U, "root 0", off_by.max(), "bound", 2 * bound)
+    assert (off_by <= 2 * bound).all()
+    # functional, root 4: H^16 = C within the 16-fold amplified roundings
+    F4 = CU.as_complex(pkg.csm_eig_weigh_host(val, vec, BINS, EU.FUNCTIONAL, 0, 4))
+    assert (np.abs(np.linalg.matrix_power(F4, 16) - A).max(axis=(1, 2)) / val[:, 0].astype(np.float64) <= 16 * 2 * bound).all()
+    for M in (H, F0):
+        diag_im = np.diagonal(M[..., 1], axis1=1, axis2=2)
+        assert not diag_im.any() and not np.signbit(diag_im).any()  # +0
+        low = np.tril(np.ones((U, U), bool), -1)
+        assert CU.same_bits(np.swapaxes(M[..., 0], 1, 2)[:, low], M[..., 0][:, low])
+        assert CU.same_bits(np.swapaxes(M[..., 1], 1, 2)[:, low], -M[..., 1][:, low])
+
+
+# ------------------------------------------------------------------------------------------------ the scene
+
+# Measured on this build's host rule (the figures the README quotes):
+FUNCTIONAL_FLOOR_DB = -35.5   # the median of the functional plane (root 4) under its maximum, two-source scene; conventional: -15.5
+ROOT0_MEASURED = 1.6e-7       # |functional root 0 - conventional| over the conventional plane's maximum, two-source scene
+
+
+@pytest.fixture(scope="module")
+def scene(pkg):
+    S = pkg.synthetic
+    spec = S.WORKLOADS["c1"]
+    xyz = S.geometry(spec)
+    off, frac = S.delay_table(spec, xyz)
+    b = [CU.SCENE_BIN]
+    out = dict(spec=spec, off=off, frac=frac, bins=b)
+    for name, x in (("two", CU.scene_samples(pkg, spec, xyz)[0]), ("one", EU.one_source_samples(pkg, spec, xyz))):
+        Cm, n = pkg.csm_accumulate_host(x, b, 1)
+        val, vec, solved, sweeps = pkg.csm_eig_host(Cm, n, b)
+        assert solved.tolist() == [1]
+        out[name] = dict(C=Cm, n=n, val=val, vec=vec, solved=solved, sweeps=sweeps,
+                         conventional=pkg.csm_map_host(Cm, n, off, frac, b, 1, CU.CONVENTIONAL)["map"][0])
+    return out
+
+
+def subspace_plane(pkg, sc, which, kind, n_sources=0, root=0):
+    s = sc[which]
+    H = pkg.csm_eig_weigh_host(s["val"], s["vec"], sc["bins"], kind, n_sources, root)
+    return pkg.csm_eig_map_host(H, s["solved"], sc["off"], sc["frac"], sc["bins"], kind, n_sources, root, 1)[0]
+
+
+def test_the_scene_that_justifies_the_feature(pkg, scene):
+    """csm_util's scene on c1 (32 x 32 pixels, 64 mics, the Hann window): two independent sources of bin 16 at pixels (16, 12) and
+    (16, 19), closer than a beam width, unequal self-noise.  On the host rule alone: the conventional plane shows ONE maximum, at
+    column 14 between the two; MUSIC with n_sources = 2 shows its two strongest maxima AT the sources' pixels, 524 and 531 (levels
+    14795 and 8882 of at most 2^24; the eigenvalues are 6.06e5, 1.84e5, then 464 and below; 10 sweeps).  Functional beamforming
+    with root 4 (nu = 16): its maximum is 0.28 dB under the conventional plane's 0.757, one pixel beside it, and its median lies
+    35.5 dB under its maximum where the conventional plane's lies 15.5 dB under -- 20.0 dB more; asserted at 15 dB more, a margin
+    of 5 dB under the measured gap.  With ONE source (csm_eig_util.one_source_samples) the functional maximum is at the
+    conventional plane's pixel and within 1 dB of it."""
+    two = scene["two"]
+    print("eigenvalues", two["val"][0, :4], "sweeps", two["sweeps"])
+    found = pkg.find_peaks(two["conventional"], 32, 32, **CU.SCENE_FIND)
+    assert int(np.ravel(found.count)[0]) == 1
+    music = subspace_plane(pkg, scene, "two", EU.MUSIC, 2)
+    found = pkg.find_peaks(music, 32, 32, **CU.SCENE_FIND)
+    count = int(np.ravel(found.count)[0])
+    pixels = [int(p) for p in np.ravel(found.sources)["pixel"][:count]]
+    print("music", pixels, np.ravel(found.sources)["power"][:count])
+    assert count >= 2 and sorted(pixels[:2]) == sorted(CU.scene_pixels(scene["spec"]))
+    functional = subspace_plane(pkg, scene, "two", EU.FUNCTIONAL, 0, 4)
+    floors = CU.median_over_max_db(functional), CU.median_over_max_db(two["conventional"])
+    print("functional floor", floors[0], "conventional floor", floors[1], "peak dB", 10 * np.log10(functional.max() / two["conventional"].max()))
+    assert abs(floors[0] - FUNCTIONAL_FLOOR_DB) < 0.5  # (the recorded figure is this build's)
+    assert floors[0] <= floors[1] - 15.0
+    # one source: the peak level stays
+    one = scene["one"]
+    functional = subspace_plane(pkg, scene, "one", EU.FUNCTIONAL, 0, 4)
+    at = int(np.argmax(one["conventional"]))
+    db = 10 * np.log10(functional[at] / one["conventional"][at])
+    print("one source: pixel", at, int(np.argmax(functional)), "dB", db)
+    assert int(np.argmax(functional)) == at == CU.scene_pixels(scene["spec"])[0] and abs(db) <= 1.0
+    assert CU.median_over_max_db(functional) < CU.median_over_max_db(one["conventional"])
+
+
+def test_functional_root_zero_is_the_conventional_map(pkg, scene):
+    """nu = 1: (s^H C s)^1 from the decomposition put together again.  Measured on the two-source scene: 1.6e-7 of the plane's
+    maximum; asserted at 4 x that, as test_csm_cpu.py's accuracy figures are -- a margin for other seeds, not for another
+    arithmetic."""
+    for which in ("two", "one"):
+        plane = subspace_plane(pkg, scene, which, EU.FUNCTIONAL, 0, 0)
+        conventional = scene[which]["conventional"]
+        rel = np.abs(plane - conventional).max() / conventional.max()
+        print(which, rel)
+        assert rel <= 4 * ROOT0_MEASURED
+
+
+# ------------------------------------------------------------------------------------------------ refusals
+
+def test_refusals_write_nothing(pkg):
+    B = pkg.binding
+    lib = B.load()
+    bins = [3, 47]
+    U = 4
+    Cm = EU.random_matrix(np.random.default_rng(3), 2, U, 9)
+    val, vec, solved, _ = pkg.csm_eig_host(Cm, 9, bins)
+    rng = np.random.default_rng(4)
+    off, frac, index = rng.integers(0, 200, (3, U)).astype(np.int32), rng.random((3, U)).astype(np.float32), np.arange(U, dtype=np.int32)
+    canary = np.float32(-3.0)
+    out = np.full(2 * U * U * 2, canary, np.float32)
+    out2 = np.full(2 * U, canary, np.float32)
+    words = np.full(4, -7, np.int32)
+    f, i = B._f32, B._i32
+    ref = lambda s: None if s is None else C.byref(s)  # noqa: E731
+
+    def eig(c, matrix=Cm, blocks=9, usable=U, values=True, vectors=True):
+        return lib.awpu_hip_csm_eig_host(None if matrix is None else f(matrix), blocks, usable, ref(c), f(out2) if values else None,
+                                         f(out) if vectors else None, i(words), i(words[2:]))
+
+    def weigh(c, e, values=val, usable=U, weighed=True):
+        return lib.awpu_hip_csm_eig_weigh_host(None if values is None else f(values), f(vec), usable, ref(c), ref(e), f(out) if weighed else None)
+
+    def mapped(c, e, weighed=vec, pixels=3, usable=U, fr=frac, map_out=True):
+        return lib.awpu_hip_csm_eig_map_host(None if weighed is None else f(weighed), i(solved), i(off), f(fr), U, pixels, i(index), usable, ref(c), ref(e),
+                                             f(out) if map_out else None)
+
+    def bad(**changes):
+        c = B.csm_of(bins)
+        for k, v in changes.items():
+            if k == "bin":
+                c.bin[v[0]] = v[1]
+            else:
+                setattr(c, k, v)
+        return c
+
+    good, e = bad(), B.csm_eig_of(B.CSM_EIG_MUSIC, 2)
+    for c in (None, bad(window=2), bad(n_bins=0), bad(n_bins=9), bad(bin=(1, 129)), bad(bin=(0, -1)), bad(bin=(1, 3)), bad(kind=3), bad(kind=-1)):
+        assert eig(c) == weigh(c, e) == mapped(c, e) == B.ERR_INVALID
+    for kind in (CU.DIAGONAL_REMOVED, CU.CAPON):  # the subspace maps take the conventional kind alone
+        assert weigh(bad(kind=kind), e) == mapped(bad(kind=kind), e) == B.ERR_INVALID
+    for request in (None, B.CsmEig(2, 0, 0, 0), B.CsmEig(-1, 0, 0, 0), B.CsmEig(0, U, 0, 0), B.CsmEig(0, -1, 0, 0), B.CsmEig(1, U, 0, 0),
+                    B.CsmEig(1, 0, 7, 0), B.CsmEig(1, 0, -1, 0), B.CsmEig(0, 0, 7, 0), B.CsmEig(0, 1, 0, 1), B.CsmEig(1, 0, 2, -1)):
+        assert weigh(good, request) == mapped(good, request) == B.ERR_INVALID
+    assert eig(good, matrix=None) == eig(good, values=False) == eig(good, vectors=False) == eig(good, blocks=0) == eig(good, usable=0) == B.ERR_INVALID
+    assert weigh(good, e, values=None) == weigh(good, e, weighed=False) == weigh(good, e, usable=0) == B.ERR_INVALID
+    assert mapped(good, e, weighed=None) == mapped(good, e, map_out=False) == mapped(good, e, pixels=0) == mapped(good, e, usable=0) == B.ERR_INVALID
+    nan_frac = frac.copy()
+    nan_frac[2, 3] = np.nan
+    assert mapped(good, e, fr=nan_frac) == B.ERR_INVALID
+    assert (out == canary).all() and (out2 == canary).all() and (words == -7).all()
+    assert weigh(good, e) == B.OK and (out != canary).all()
+    with pytest.raises(pkg.AwpuError) as ei:
+        pkg.csm_eig_host(Cm, 9, [47, 3])
+    assert ei.value.status == B.ERR_INVALID
+    with pytest.raises(pkg.AwpuError) as ei:
+        pkg.csm_eig_weigh_host(val, vec, bins, B.CSM_EIG_MUSIC, U)
+    assert ei.value.status == B.ERR_INVALID
+
+
+# ------------------------------------------------------------------------------------------------ sanitizers, and the kernels' build
+
+def test_host_code_runs_clean_under_sanitizers(tmp_path):
+    """tests/host/csm_eig_check.cpp with csm_eig_host.cpp: a program of its own under ASan and UBSan, every buffer exactly as long
+    as the header says."""
+    exe = tmp_path / "csm_eig_check"
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    f"-I{REPO / 'include'}", f"-I{CSRC}", str(REPO / "tests" / "host" / "csm_eig_check.cpp"), str(CSRC / "csm_eig_host.cpp"),
+                    "-o", str(exe)], check=True, capture_output=True)
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "csm eig rule: ok" in out.stdout, out.stdout + out.stderr
+
+
+def test_eig_kernels_compile_without_spills(tmp_path, pkg):
+    """The metadata of the code object only: no spills, no private segment; the Jacobi kernel's 1024 threads leave it 128
+    registers.  The fused steps are there as written, and so is the full-precision double division."""
+    out = tmp_path / "csm_eig_kernels.s"
+    subprocess.run([pkg._build.hipcc_path(), "--offload-arch=gfx950", "-O3", "-std=c++17", f"-I{REPO / 'include'}", f"-I{CSRC}",
+                    "-S", "--cuda-device-only", "-o", str(out), str(CSRC / "csm_eig_kernels.hip")], check=True, capture_output=True)
+    text = out.read_text()
+    assert "v_fma_f64" in text and "v_div_scale_f64" in text
+    meta = {}
+    for block in text.split("  - .agpr_count:")[1:]:
+        name = re.search(r"\.name:\s+(\S+)", block).group(1)
+        meta[name] = {k: int(re.search(rf"\.{k}:\s+(\d+)", block).group(1))
+                      for k in ("vgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size")}
+    assert len(meta) == 5 and all(any(k in name for name in meta) for k in ("jacobi_kernelILb0", "jacobi_kernelILb1", "sort", "weigh", "finish")), sorted(meta)
+    for name, m in meta.items():
+        print(name, m)
+        assert m["vgpr_spill_count"] == 0 and m["sgpr_spill_count"] == 0 and m["private_segment_fixed_size"] == 0, (name, m)
+        assert m["vgpr_count"] <= 128, (name, m)

@@ -23,6 +23,13 @@ composition.  And CLEAN-SC (step 7, include/awpu_hip_csm_clean.h): Engine.csm_cl
 is left per step for the two launches between two maps), and Engine.csm_clean_step_device by itself (load, component, update).
 Measured (--repeats 20; c1 / the reference's shape / the headline shape): clean_8 0.198 / 0.400 / 12.26 ms beside map_8 0.034 / 0.072 /
 2.43 ms (1.18 / 1.12 / 1.01 x its five maps), clean_1 0.192 / 0.204 / 1.69 ms beside map_1 0.033 / 0.032 / 0.306 ms (1.16 / 1.29 / 1.11 x).
+And the eigendecomposition (step 8, include/awpu_hip_csm_eig.h): Engine.csm_eig_device of the 8-bin matrix (eig_8) and one MUSIC and
+one functional map of it (Engine.csm_eig_map_device: music_8, functional_8 with root 4), timed by events as the maps are, beside
+numpy.linalg.eigh of the same eight matrices in complex128 on the host (eigh_host_8, wall clock).
+Measured (--repeats 20, 8 bins; c1 / the reference's shape / the headline shape): eig_8 3.20 / 3.13 / 193.3 ms, music_8 3.25 / 3.22 /
+196.0 ms, functional_8 3.28 / 3.22 / 196.2 ms beside eigh_host_8 2.52 / 2.51 / 77.4 ms -- the maps are the eigensolver plus 0.05 to 3 ms,
+and the solver, eight workgroups of one compute unit each walking about 700 (64 mics) or 3 300 (256 mics) rounds of three barriers, is
+slower than LAPACK on the host's cores at both sizes; what it buys is a result on the stream, with the host rule's bits.
 No figure here is a gate."""
 import argparse
 import importlib
@@ -31,6 +38,8 @@ import statistics
 import sys
 import time
 from pathlib import Path
+
+import numpy as np
 
 sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 pkg = importlib.import_module("beamforming-lk_amd")
@@ -60,6 +69,7 @@ def main():
         matrix = torch.zeros(8, U, U, 2, device="cuda")
         plane = torch.empty(8, P, device="cuda")
         inverse = torch.empty_like(matrix)
+        eig_values = torch.empty(8, U, device="cuda")
         frame = torch.zeros_like(matrix)
         pixels = torch.full((8,), P // 2 + spec.res // 2, dtype=torch.int32, device="cuda")
         with pkg.Engine(n_pixels=P, n_streams=U, grid_columns=spec.res, max_batch=8) as eng:
@@ -71,6 +81,13 @@ def main():
                      "map_1": lambda: eng.csm_map_device(matrix.data_ptr(), a.blocks, bins1, 1, d_map_ptr=plane.data_ptr(), stream=side.cuda_stream),
                      "map_8": lambda: eng.csm_map_device(matrix.data_ptr(), a.blocks, bins8, 1, d_map_ptr=plane.data_ptr(), stream=side.cuda_stream)}
             calls["invert_8"] = lambda: eng.csm_invert_device(matrix.data_ptr(), a.blocks, bins8, inverse.data_ptr(), LOADING, stream=side.cuda_stream)
+            # the eigendecomposition (step 8) of the 8-bin matrix, and one MUSIC and one functional map of it
+            calls["eig_8"] = lambda: eng.csm_eig_device(matrix.data_ptr(), a.blocks, bins8, eig_values.data_ptr(), inverse.data_ptr(),
+                                                        stream=side.cuda_stream)
+            calls["music_8"] = lambda: eng.csm_eig_map_device(matrix.data_ptr(), a.blocks, bins8, plane.data_ptr(), pkg.binding.CSM_EIG_MUSIC, 2, 0, 1,
+                                                              stream=side.cuda_stream)
+            calls["functional_8"] = lambda: eng.csm_eig_map_device(matrix.data_ptr(), a.blocks, bins8, plane.data_ptr(), pkg.binding.CSM_EIG_FUNCTIONAL,
+                                                                   0, 4, 1, stream=side.cuda_stream)
             # CLEAN-SC (step 7): the loop of CLEAN_STEPS steps -- CLEAN_STEPS + 1 maps and what runs between them --, and one step by itself
             # on a copy of the matrix (it updates in place)
             for n_bins, bins in ((1, bins1), (8, bins8)):
@@ -124,7 +141,8 @@ def main():
                                              d_carry_ptr=run_carry.data_ptr(), carried=0, d_power_ptr=run_power.data_ptr(), stream=side.cuda_stream)
 
             host_matrix = matrix.cpu().numpy()
-            walls = {"capon_run": capon_run, "clean_run": clean_run, "invert_host_8": lambda: pkg.csm_invert_host(host_matrix, a.blocks, bins8, loading=LOADING), "capon_device": capon_device,
+            host_complex = (host_matrix[..., 0] + 1j * host_matrix[..., 1]).astype(np.complex128) / a.blocks
+            walls = {"eigh_host_8": lambda: np.linalg.eigh(host_complex), "capon_run": capon_run, "clean_run": clean_run, "invert_host_8": lambda: pkg.csm_invert_host(host_matrix, a.blocks, bins8, loading=LOADING), "capon_device": capon_device,
                      "capon_host_inverse": capon_host_inverse}
             for name, call in walls.items():
                 times[name] = []
