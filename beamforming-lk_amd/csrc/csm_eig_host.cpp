@@ -75,7 +75,7 @@ bool eig_bin(const float *C, double n, int32_t usable, CsmZ *A, CsmZ *V, double 
     if (!converged) return false;
     for (size_t j = 0; j < U; j++) {
         lambda[j] = A[j * U + j].re;
-        if (!awpu::csm_inv_finite(lambda[j])) return false;
+        if (!awpu::csm_eig_fits(lambda[j])) return false;
     }
     return true;
 }

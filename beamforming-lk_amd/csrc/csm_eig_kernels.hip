@@ -13,7 +13,7 @@
 // uniform.  The kernel leaves the eigenvalues (the diagonal, unsorted), V and the bin's state -- converged, sweeps -- in the scratch.
 //
 // SORT (sort and round): entry-parallel, one thread per (eigenvalue j, mic a): the rank of j from all eigenvalues, the float
-// entry of eigenvector j in row `rank`; a bin that is unsolved (the Jacobi kernel's state, or an eigenvalue that is not finite)
+// entry of eigenvector j in row `rank`; a bin that is unsolved (the Jacobi kernel's state, or an eigenvalue that does not fit a float)
 // becomes +0 everywhere.  The solved and sweep words.
 //
 // WEIGH (step 8b): entry-parallel, one thread per entry b <= a, 16 x 16 a workgroup as the inverse's gram kernel; the weights of
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(256) void csm_eig_sort_kernel(CsmEigArgs a) {
         const double lj = sc.lambda[j];
         for (int i = 0; i < U; i++) {
             const double li = sc.lambda[i];
-            ok = ok && csm_inv_finite(li);
+            ok = ok && csm_eig_fits(li);
             rank += csm_eig_before(li, i, lj, j) ? 1 : 0;
         }
         if (ok) {

@@ -93,6 +93,10 @@ AWPU_CSM_HD void csm_eig_rows(double c, double s, double phr, double phi, CsmZ &
     csm_eig_combine(c, s, x, y, w);
 }
 
+// Sort and round: whether an eigenvalue fits a float, i.e. (float) lambda is finite (false for a NaN, for an infinite double and
+// for a finite one that rounds to inf); a bin with one that does not is unsolved
+AWPU_CSM_HD bool csm_eig_fits(double lambda) { return csm_inv_finite((double) (float) lambda); }
+
 // Sort: whether eigenvalue i comes before eigenvalue j (descending; equal values keep index order)
 AWPU_CSM_HD bool csm_eig_before(double li, int32_t i, double lj, int32_t j) { return li > lj || (li == lj && i < j); }
 

@@ -102,8 +102,9 @@
  *                 still rotates in its 32nd sweep is unsolved.
  *        Sort and round.  Eigenvalue j (A[j][j].re) has rank = the number of i with l_i > l_j, or l_i == l_j and i < j;
  *                 values[k][rank] = (float) l_j;  vectors[k][rank][a] = ((float) V[a][j].re, (float) V[a][j].im): an eigenvector
- *                 is one contiguous row.  A bin with an eigenvalue that is not finite is unsolved.  An unsolved bin: every value
- *                 and every vector word +0, `solved` 0, `sweeps` as run; every other bin's `solved` is 1.
+ *                 is one contiguous row.  A bin with an eigenvalue that does not fit a float -- (float) l_j is not finite: a NaN,
+ *                 an infinity, or a finite double that rounds past FLT_MAX -- is unsolved.  An unsolved bin: every value and
+ *                 every vector word +0, `solved` 0, `sweeps` as run; every other bin's `solved` is 1 and its values are finite.
  *  8b. The weighed matrix H [n_bins][usable][usable][2] from the float values and vectors and an awpu_csm_eig_t:
  *          AWPU_CSM_EIG_MUSIC        w_r = r < n_sources ? 0 : 1                  (the projector on the noise subspace)
  *          AWPU_CSM_EIG_FUNCTIONAL   w_r = l_r > 0 ? (float) ((double) l_r, square-rooted `root` times in double) : +0

@@ -39,7 +39,8 @@ typedef struct awpu_csm_eig {
  * diagonal's real parts and the entries b < a are read.  values [n_bins][usable] descend; vectors [n_bins][usable][usable][2]:
  * vectors[k][r] is the eigenvector of values[k][r], one contiguous row; solved [n_bins] and sweeps [n_bins], each or NULL.
  * Refusals: a null matrix, values or vectors, a bad c, counts below 1: AWPU_ERR_INVALID, nothing written.  An unsolved bin is no
- * error: its values and vectors are +0 and its solved word 0. */
+ * error: its values and vectors are +0 and its solved word 0.  A bin with an eigenvalue that does not fit a float ((float) of it
+ * is not finite) is unsolved too: the values of a solved bin are finite. */
 int awpu_hip_csm_eig_host(const float *matrix, int32_t block_count, int32_t usable, const awpu_csm_t *c, float *values, float *vectors,
                           int32_t *solved, int32_t *sweeps);
 

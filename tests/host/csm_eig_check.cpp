@@ -1,7 +1,8 @@
 // csm_eig_check.cpp -- awpu_hip_csm_eig_host, _eig_weigh_host and _eig_map_host (csrc/csm_eig_host.cpp, csm_eig_rule.h) as a
 // program of its own, meant to be built with -fsanitize=address,undefined: every buffer exactly as long as the header says, the
 // smallest sizes (one mic, one bin), odd sizes with the dummy that sits out, eight bins, `solved` and `sweeps` given and null, an
-// unsolved bin among solved ones (all zeros; a NaN entry), A v against lambda v, V's columns against the identity, H's structure,
+// unsolved bin among solved ones (all zeros; a NaN entry; an eigenvalue that fits no float), one bin of 129 mics, a matrix of equal
+// entries whose eigenvalues tie, A v against lambda v, V's columns against the identity, H's structure,
 // both maps on a small table, and the refusals -- which must leave the outputs as they were.
 #include <cmath>
 #include <cstdio>
@@ -54,6 +55,8 @@ void run(int K, int U, int n_blocks, int spoil) {
     const int dead = K > 1 ? 1 : 0;  // the bin that `spoil` makes unsolved
     if (spoil == 1) std::fill(C.begin() + dead * per_bin, C.begin() + (dead + 1) * per_bin, 0.0f);
     if (spoil == 2) C[dead * per_bin + ((size_t) (U - 1) * U) * 2] = NAN;  // entry (U-1, 0): read (or, with one mic, the diagonal)
+    if (spoil == 3)  // every entry (3e38, 0): finite entries, the eigenvalue U * 3e38 / n_blocks a finite double that no float holds
+        for (size_t i = 0; i < per_bin; i++) C[dead * per_bin + i] = i % 2 ? 0.0f : 3e38f;
     const awpu_csm_t c = csm_of(K);
     std::vector<float> values((size_t) K * U, -3.0f), vectors(K * per_bin, -3.0f), values2((size_t) K * U, -3.0f), vectors2(K * per_bin, -3.0f);
     std::vector<int32_t> solved(K, -7), sweeps(K, -7);
@@ -64,7 +67,7 @@ void run(int K, int U, int n_blocks, int spoil) {
     for (int k = 0; k < K; k++) {
         const float *val = &values[(size_t) k * U], *vec = &vectors[k * per_bin];
         if (spoil && k == dead) {
-            CHECK(solved[k] == 0 && sweeps[k] == 0);
+            CHECK(solved[k] == 0 && (spoil == 3 ? sweeps[k] >= 1 && sweeps[k] <= 16 : sweeps[k] == 0));  // (3 fails behind its sweeps)
             for (int i = 0; i < U; i++) CHECK(val[i] == 0.0f && !std::signbit(val[i]));
             for (size_t i = 0; i < per_bin; i++) CHECK(vec[i] == 0.0f && !std::signbit(vec[i]));
             continue;
@@ -178,6 +181,29 @@ void run(int K, int U, int n_blocks, int spoil) {
     CHECK(keep == values && keep_vec == vectors && keep_solved == solved && keep_sweeps == sweeps);
 }
 
+// every entry (2, 0), one block: rank one, eigenvalues that tie exactly behind rotations -- every row of vectors is written once
+void equal_entries(int U) {
+    const size_t per_bin = (size_t) U * U * 2;
+    std::vector<float> C(per_bin), values(U, -3.0f), vectors(per_bin, -3.0f);
+    for (size_t i = 0; i < per_bin; i++) C[i] = i % 2 ? 0.0f : 2.0f;
+    const awpu_csm_t c = csm_of(1);
+    int32_t solved = -7, sweeps = -7;
+    CHECK(awpu_hip_csm_eig_host(C.data(), 1, U, &c, values.data(), vectors.data(), &solved, &sweeps) == AWPU_OK);
+    CHECK(solved == 1 && sweeps >= 1 && sweeps <= 16);
+    int ties = 0;
+    for (int r = 1; r < U; r++) {
+        CHECK(values[r - 1] >= values[r]);
+        ties += values[r - 1] == values[r] ? 1 : 0;
+    }
+    CHECK(ties >= 1);
+    CHECK(std::fabs((double) values[0] - 2.0 * U) <= 2.0 * U * std::ldexp(1.0, -22));
+    for (int r = 0; r < U; r++) {  // a row that the sort left out would keep its -3 words: every row has norm 1
+        double norm = 0.0;
+        for (int a = 0; a < 2 * U; a++) norm += (double) vectors[(size_t) r * U * 2 + a] * vectors[(size_t) r * U * 2 + a];
+        CHECK(std::fabs(norm - 1.0) <= (U + 2) * std::ldexp(1.0, -23));
+    }
+}
+
 }  // namespace
 
 int main() {
@@ -190,6 +216,10 @@ int main() {
     run(2, 7, 3, 0);   // fewer blocks than mics: rank-deficient
     run(3, 17, 40, 2);  // a NaN entry
     run(1, 24, 6, 0);
+    run(3, 17, 9, 3);     // an eigenvalue past FLT_MAX: unsolved behind its sweeps
+    run(1, 129, 261, 0);  // above 64 mics, odd
+    equal_entries(5);
+    equal_entries(65);
     if (failures) return 1;
     std::printf("csm eig rule: ok\n");
     return 0;

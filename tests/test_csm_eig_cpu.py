@@ -16,6 +16,7 @@ import pytest
 
 import csm_eig_util as EU
 import csm_util as CU
+from csm_eig_util import VALUE_BOUND, vector_bound, vectors_of  # (the bounds are stated there, for the GPU tests too)
 
 REPO = Path(__file__).resolve().parent.parent
 CSRC = REPO / "beamforming-lk_amd" / "csrc"
@@ -23,22 +24,6 @@ HOST_NAMES = ["awpu_hip_csm_eig_host", "awpu_hip_csm_eig_weigh_host", "awpu_hip_
 NAMES = HOST_NAMES + ["awpu_hip_csm_eig", "awpu_hip_csm_eig_device", "awpu_hip_csm_eig_weigh_device", "awpu_hip_csm_eig_map",
                       "awpu_hip_csm_eig_map_device"]
 BINS = [3, 16, 128]
-# Eigenvalues agree within 2^-22 of the bin's largest: Jacobi in double is exact to about 1e-14 of it and is then rounded to float
-# once (2^-24 relative); numpy's are exact to about 1e-15.  The factor 2 on one rounding of the largest value (2^-23, as
-# test_csm_invert_cpu.py argues for G) is slack.
-VALUE_BOUND = 2.0 ** -22
-
-
-def vector_bound(U):
-    """|A v - lambda v| over lambda_max, and |V^H V - I|: v's U entries and lambda are each rounded to float once (2^-24 of
-    at most 1, and of lambda_max), so a row of A v - lambda v is off by at most (|A| 1 + lambda_max) 2^-24 <= (sqrt(U) + 1) 2^-24
-    lambda_max and an entry of V^H V by 2 U 2^-24 / 2 in the worst case; (U + 2) 2^-23 covers both."""
-    return (U + 2) * 2.0 ** -23
-
-
-def vectors_of(vec):
-    """vectors [K, U, U, 2] -> V [K, U, U] complex128 with the eigenvectors as COLUMNS."""
-    return np.swapaxes(CU.as_complex(vec), 1, 2)
 
 
 # ------------------------------------------------------------------------------------------------ wiring

@@ -1,10 +1,11 @@
 """Step 8 of include/awpu_hip_csm.h on the device (include/awpu_hip_csm_eig.h): the eigendecomposition, the weighed matrix and the
 two subspace maps.
 
-1. csm_eig_device equals csm_eig_host bit for bit -- values, vectors, solved and sweep words -- on 1, 2, 3, 5, 33, 63, 64, 65 and
-   96 mics (one entry; odd sizes with the dummy that sits out; 64, 256 and 1024 threads; the last size whose A and V live in LDS
-   and the first that lives in the scratch) with 1, 3 and 8 bins, a rank-deficient matrix included; guards intact; the synchronous
-   csm_eig gives the same.
+1. csm_eig_device equals csm_eig_host bit for bit -- values, vectors, solved and sweep words -- on 1, 2, 3, 5, 8, 9, 32, 33, 63, 64,
+   65 and 96 mics (one entry; odd sizes with the dummy that sits out; the Jacobi kernel's 64 threads up to 8 mics, 256 from 9 to
+   32 and 1024 from 33 on, each tier at both of its edges; the last size whose A and V live in LDS and the first that lives in
+   the scratch) with 1, 3 and 8 bins, a rank-deficient matrix included; guards intact; the synchronous csm_eig gives the same.
+   The sizes from 128 mics to the bound of 256 are test_gpu_csm_eig_edges.py's (BOUND_MICS below are its lists).
 2. Composition: csm_eig_weigh_device equals csm_eig_weigh_host, both kinds, root 0 and 4, n_sources 0, 2 and U - 1;
    csm_eig_map_device equals csm_eig_map_host of the host's decomposition, and equals the steps one by one on the device -- eig,
    weigh, csm_map_device's q, the finish (restated in numpy float32); a slab handle maps its own pixels.
@@ -32,12 +33,20 @@ MICS = {1: (8, [3]),
         2: (8, [5, 2]),
         3: (8, [6, 1, 3]),
         5: (8, [6, 1, 3, 0, 7]),
-        33: (40, [i for i in range(40) if i % 6 != 5][1:]),
+        8: (8, list(range(8))),                               # the last size of 64 threads
+        9: (12, [i for i in range(12) if i % 4 != 1]),        # the first of 256, ragged
+        32: (32, list(range(32))),                            # the last of 256
+        33: (40, [i for i in range(40) if i % 6 != 5][1:]),   # the first of 1024
         63: (64, [i for i in range(64) if i != 40]),
         64: (64, list(range(64))),
         65: (128, list(range(0, 128, 2)) + [127]),
         96: (96, list(range(96)))}
-assert all(len(index) == U for U, (_, index) in MICS.items())
+# the lists of test_gpu_csm_eig_edges.py, up to AWPU_CSM_EIG_MAX_MICS: too large for the eight-bin settings of this file's tests
+BOUND_MICS = {128: (128, list(range(128))),
+              129: (160, [i for i in range(160) if i % 5 != 4] + [159]),  # ragged and odd
+              255: (256, [i for i in range(256) if i != 100]),
+              256: (256, list(range(256)))}
+assert all(len(index) == U for U, (_, index) in {**MICS, **BOUND_MICS}.items())
 
 
 class Rig:
@@ -45,7 +54,7 @@ class Rig:
 
     def __init__(self, pkg, U):
         self.pkg, self.U = pkg, U
-        self.S, index = MICS[U]
+        self.S, index = MICS[U] if U in MICS else BOUND_MICS[U]
         self.index = np.asarray(index, np.int32)
         rng = np.random.default_rng(900 + U)
         self.off = rng.integers(0, 700, (PIXELS, self.S)).astype(np.int32)
@@ -132,14 +141,20 @@ def same(got, want):
 
 # ------------------------------------------------------------------------------------------------ 1. the rule's bits
 
-def check_bits(pkg, eng, Cm, n, bins, expect=None):
-    want = pkg.csm_eig_host(Cm, n, bins)
-    assert want[2].tolist() == (expect or [1] * len(bins))
+def device_equals(eng, Cm, n, bins, want):
+    """csm_eig_device against `want`, a result of csm_eig_host -> the device's own (values, vectors, solved, sweeps)."""
     got, _ = device_eig(eng, Cm, n, bins)
     print(Cm.shape, n, "sweeps", want[3].tolist(), got[3].tolist())
     assert got[2].tolist() == want[2].tolist() and got[3].tolist() == want[3].tolist()
     assert same(got, want)
     assert same(device_eig(eng, Cm, n, bins, want_words=False)[0][:2], want[:2])  # without the words: the same bits
+    return got
+
+
+def check_bits(pkg, eng, Cm, n, bins, expect=None):
+    want = pkg.csm_eig_host(Cm, n, bins)
+    assert want[2].tolist() == (expect or [1] * len(bins))
+    device_equals(eng, Cm, n, bins, want)
     return want
 
 
@@ -161,36 +176,44 @@ def test_device_eig_equals_the_host_rule(pkg, U):
 REQUESTS = [(EU.MUSIC, 0, 0), (EU.MUSIC, 2, 0), (EU.MUSIC, -1, 0), (EU.FUNCTIONAL, 0, 0), (EU.FUNCTIONAL, 0, 4)]  # n_sources -1: U - 1
 
 
-@pytest.mark.parametrize("U", [5, 64, 65])
-def test_composition(pkg, U):
+def check_composition(pkg, rig, eng, Cm, n, bins, window, requests, host):
+    """Steps 8a to 8c of Cm on the device against the host functions, with `host` the (values, vectors, solved) of csm_eig_host:
+    the weighed matrix, the map, the map without its optional outputs, the steps one by one, and the synchronous form."""
     import torch
 
+    U, K = rig.U, len(bins)
+    val, vec, solved = host
+    got, (d_val, d_vec) = device_eig(eng, Cm, n, bins)
+    assert same(got[:3], (val, vec, solved))
+    for kind, n_sources, root in requests:
+        n_sources = U - 1 if n_sources < 0 else n_sources
+        Hw = pkg.csm_eig_weigh_host(val, vec, bins, kind, n_sources, root)
+        Hd, d_H = device_weigh(eng, d_val, d_vec, K, U, bins, kind, n_sources, root)
+        assert CU.same_bits(Hd, Hw), (kind, n_sources, root)
+        want = pkg.csm_eig_map_host(Hw, solved, rig.off, rig.frac, bins, kind, n_sources, root, window, index=rig.index)
+        m, v, s = device_eig_map(eng, Cm, n, bins, kind, n_sources, root, window)
+        assert CU.same_bits(m, want) and CU.same_bits(v, val) and s.tolist() == [1] * K, (kind, n_sources, root)
+        assert CU.same_bits(device_eig_map(eng, Cm, n, bins, kind, n_sources, root, window, want=())[0], want)
+        # the steps one by one: q of the weighed matrix by the map's own call, then the finish
+        d_q = guarded(K * PIXELS, torch.float32, float(CANARY))
+        eng.csm_map_device(d_H.data_ptr() + 4 * GUARD, 1, bins, window, CU.CONVENTIONAL, d_q_ptr=d_q.data_ptr() + 4 * GUARD)
+        eng.synchronize()
+        q = inner(d_q, (K, PIXELS), CANARY, "q")
+        assert CU.same_bits(EU.finish(q, solved, bins, window, U, kind, root), m), (kind, n_sources, root)
+        # the synchronous form
+        out = eng.csm_eig_map(Cm, n, bins, kind, n_sources, root, window, want=("map", "values", "solved"))
+        assert CU.same_bits(out["map"], want) and CU.same_bits(out["values"], val) and out["solved"].tolist() == [1] * K
+
+
+@pytest.mark.parametrize("U", [5, 64, 65])
+def test_composition(pkg, U):
     rig = Rig(pkg, U)
     bins, window = THREE, 1
     n = 2 * U + 3
     Cm = matrix_of(U, 3, n)
     val, vec, solved, _ = pkg.csm_eig_host(Cm, n, bins)
     with rig.engine() as eng:
-        got, (d_val, d_vec) = device_eig(eng, Cm, n, bins)
-        assert same(got[:3], (val, vec, solved))
-        for kind, n_sources, root in REQUESTS:
-            n_sources = U - 1 if n_sources < 0 else n_sources
-            Hw = pkg.csm_eig_weigh_host(val, vec, bins, kind, n_sources, root)
-            Hd, d_H = device_weigh(eng, d_val, d_vec, 3, U, bins, kind, n_sources, root)
-            assert CU.same_bits(Hd, Hw), (kind, n_sources, root)
-            want = pkg.csm_eig_map_host(Hw, solved, rig.off, rig.frac, bins, kind, n_sources, root, window, index=rig.index)
-            m, v, s = device_eig_map(eng, Cm, n, bins, kind, n_sources, root, window)
-            assert CU.same_bits(m, want) and CU.same_bits(v, val) and s.tolist() == [1, 1, 1], (kind, n_sources, root)
-            assert CU.same_bits(device_eig_map(eng, Cm, n, bins, kind, n_sources, root, window, want=())[0], want)
-            # the steps one by one: q of the weighed matrix by the map's own call, then the finish
-            d_q = guarded(3 * PIXELS, torch.float32, float(CANARY))
-            eng.csm_map_device(d_H.data_ptr() + 4 * GUARD, 1, bins, window, CU.CONVENTIONAL, d_q_ptr=d_q.data_ptr() + 4 * GUARD)
-            eng.synchronize()
-            q = inner(d_q, (3, PIXELS), CANARY, "q")
-            assert CU.same_bits(EU.finish(q, solved, bins, window, U, kind, root), m), (kind, n_sources, root)
-            # the synchronous form
-            out = eng.csm_eig_map(Cm, n, bins, kind, n_sources, root, window, want=("map", "values", "solved"))
-            assert CU.same_bits(out["map"], want) and CU.same_bits(out["values"], val) and out["solved"].tolist() == [1, 1, 1]
+        check_composition(pkg, rig, eng, Cm, n, bins, window, REQUESTS, (val, vec, solved))
     # a slab handle maps its own pixels
     lo, count = 32, 70
     kind, n_sources, root = EU.MUSIC, 2, 0
